@@ -16,7 +16,7 @@ subproblems, no data-path collective (weak scaling).  Rank 0 prints ONE JSON lin
 without a launcher starts the N ranks itself (torch.distributed.run as a child process, before anything touches
 the GPU); a WORLD_SIZE that disagrees with --gpus is an error -- the line never reports another n_gpus than asked.
 At N>1 the line also carries `secondary.bnb_ilp_512x1024_dist`: the B&B node farm (mvolps_amd/dist_bnb.py,
-/root/reference/bs.cpp:96-327 sharded over the ranks) on the BASELINE config-5 instance over RCCL.
+the reference's bs.cpp:96-327 sharded over the ranks) on the BASELINE config-5 instance over RCCL.
 """
 import argparse
 import json
@@ -28,7 +28,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md (spec 8.0 TB/s)
+HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak (spec 8.0 TB/s)
 
 
 def bytes_per_pivot(m, n):
@@ -348,6 +348,39 @@ def dist_bnb_leg(api, dist, rank, world, dev_index, rehearsal, nodes, publish=la
     return res
 
 
+DUMP_TABLEAU_SAMPLE = 1 << 20  # tableau entries in the seeded sample of --dump-outputs (8 MB of fp64)
+
+
+def dump_outputs(P, outdir, seed=12345):
+    """--dump-outputs DIR: what a caller of the timed path holds after its last step -- the LP's state on the handle
+    the timed pivots ran on -- as DIR/<name>.npy (float64).  The (m+1) x (n+1) tableau is too large to store whole
+    at the bench size: its objective row goes in full, the rest as a fixed, seeded sample of entries (the flat
+    indices are stored beside it).  About 17 MB at 4096x8192."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    head, nb, flag = P.basis()
+    T = P.tableau()
+    rng = np.random.default_rng(seed)
+    k = min(DUMP_TABLEAU_SAMPLE, T.size)
+    idx = np.sort(rng.choice(T.size, size=k, replace=False))
+    arrays = {
+        "state": np.array([P.status, P.it_cnt, P.obj], dtype=np.float64),  # status, pivots on the handle, objective
+        "col_prim": P.col_prim().astype(np.float64),
+        "row_prim": P.row_prim().astype(np.float64),
+        "basis_head": head[1:].astype(np.float64),
+        "nonbasis": nb[1:].astype(np.float64),
+        "nonbasis_flag": flag[1:].astype(np.float64),
+        "tableau_row0": T[0].copy(),
+        "tableau_sample_index": idx.astype(np.float64),
+        "tableau_sample": T.reshape(-1)[idx],
+    }
+    del T
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def self_launch(args):
     """`python bench.py --gpus N` with N > 1 and no launcher around it: start the N ranks as a child process tree
     (torch.distributed.run), before this process has touched the GPU, and leave with its exit code."""
@@ -378,9 +411,13 @@ def main():
     ap.add_argument("--no-secondary", action="store_true", help="skip the side measurements of configs 2 and 3/5")
     ap.add_argument("--profile-steps", type=int, default=200, help="extra pivots timed per-kernel with HIP events")
     ap.add_argument("--bnb-nodes", type=int, default=3000, help="nodes of the wide 512x1024 tree the distributed B&B leg runs (N>1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's LP state (solution, basis, a seeded tableau sample) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     # rehearsal on a one-GPU box only: MVX_BENCH_REHEARSAL=1 puts every rank on device 0 and uses
     # gloo for the barrier / MAX-reduce, to exercise the multi-rank code path without N GPUs
     rehearsal = os.environ.get("MVX_BENCH_REHEARSAL") == "1"
@@ -435,7 +472,7 @@ def main():
     def run_pivots(k):
         """Exactly k pivots of the workload, HBM-resident: when the LP reaches its optimum first (devex pricing
         needs ~3.4k pivots at 4096x8192) the run carries on with a fresh device-to-device clone of the
-        initial tableau."""
+        initial tableau.  Returns the pivots done."""
         left = k
         state["device_ms"] = 0.0
         while left > 0:
@@ -448,7 +485,7 @@ def main():
                 if P.status != 5:
                     raise SystemExit("rank %d: LP ended with status %d" % (rank, P.status))
                 state["P"] = P0.copy()
-        return k
+        return k - left
 
     # warmup: W untimed pivots
     run_pivots(args.warmup)
@@ -464,6 +501,11 @@ def main():
     barrier()
     el = time.perf_counter() - t0
     device_ms = state["device_ms"]
+    if steps_done != args.steps:
+        raise SystemExit("rank %d: %d pivots timed, %d asked for (--steps)" % (rank, steps_done, args.steps))
+    if args.dump_outputs and rank == 0:
+        # before the per-kernel pass below, which pivots on from the same handle
+        dump_outputs(state["P"], args.dump_outputs)
 
     # max over ranks
     el_max = el
