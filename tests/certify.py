@@ -1,0 +1,556 @@
+"""Independent certificates for an engine handle's state: numpy only, no oracle, no scipy.
+
+Everything here is recomputed from the MODEL (A, row and column bounds, c, c0, direction, kinds, rows and columns
+appended later) and the BASIS a handle reports (`basis()`: head, nb, flag), then compared with what the handle
+returns through the C ABI (`tableau()`, `col_prim/row_prim`, `col_stat/row_stat`, `obj`, the duals, `eval_tab_row`,
+GMI cuts).  Whatever pivot sequence led to the basis, a correct engine passes; an engine and oracle that share a bug
+do not.
+
+Conventions (GLPK's numbering; the slack tableau of the oracle's build_slack_tableau_flags fixes the signs).
+Variables k = 1..m are the auxiliaries x_R, k = m+1..m+n the structurals x_S, tied by the homogeneous system
+x_R = A x_S, i.e. M x = 0 with M = [I | -A].  head[1..m] lists the basic variables by tableau row, nb[1..n] the
+non-basic ones by tableau column, flag[1..n] where each non-basic one sits (NL: lb, NU: ub, NF: 0, NS: lb).  The
+(m+1) x (n+1) tableau T is
+
+    T[i][j] = d x_B(i) / d x_N(j)     = (-B^-1 N)[i][j]          i, j >= 1   (slack basis: T = A)
+    T[i][0] = x_B(i) at the non-basic values = sum_j T[i][j] x_N(j)
+    T[0][j] = reduced cost d_j = c_N(j) + sum_i c_B(i) T[i][j]     (c = 0 on auxiliaries)
+    T[0][0] = c0 + c . x
+
+B and N are the columns of M by head and nb.  The reduced cost of a non-basic auxiliary is its row dual, that of a
+non-basic structural its column dual; both are 0 for a basic variable.
+
+Reference arithmetic.  `Ref` solves B X = -N in fp64 and refines once with the residual -N - B X0 formed in
+np.longdouble (80-bit on x86; B's auxiliary columns are unit vectors, so only the basic structural columns cost a
+product).  One refinement leaves the reference within about cond(B) * 1e-19 relative, far below every tolerance
+below.  For m <= EXACT_M the exact path (`exact=True`) does Gauss-Jordan in fractions.Fraction (all test data is
+integer or dyadic, so the result is exact).
+
+Tolerances are computed from the reference, never fitted to the result:
+
+    |T_handle - T_ref| <= RTOL * growth * (1 + |T_ref|),     growth = ||B^-1||_inf * ||M||_inf  (= cond of the basis)
+
+RTOL = 2**-44 (5.7e-14).  A fixed fp64 Gauss-Jordan tableau after k pivots has entrywise error of order
+k * u * growth (u = 2**-53, each pivot adds a few roundings of entries bounded by growth); at 1024 x 2048 after
+~1000 pivots k * u = 1.1e-13, about 2 * RTOL, and growth bounds the amplification from far above: the oracle's
+1024 x 2048 seed-12345 optimum (754 pivots, growth 9.0e4) is off by at most 1.7e-12, 3e-4 of its tolerance, and the
+GPU test holds the engine to the same bound.  A tableau entry nudged by 1e-7 on the small cases of the suite
+(growth below 1e3) fails by three orders of magnitude.
+
+Infeasibility.  The final basis of a NOFEAS solve certifies infeasibility through one combination u of its rows:
+L(x) = sum_i u_i (x_B(i) - sum_j T[i][j] x_N(j)) vanishes on every solution of x_R = A x_S, so if the interval of L
+over the box of bounds excludes 0 there is none.  The dual simplex stops on a row p that is out of bounds while no
+non-basic variable can move it back (u = +-e_p); phase 1 stops when no column improves the sum of infeasibilities
+(u = the signs g of the infeasible rows).  The certificate is guaranteed when every entry the engine's ratio test
+skips as |a| <= tol_piv multiplies a finite bound width whose sum, times |a|, stays below the violation; that holds on
+the generators of the suite, where entries are either zero or far above tol_piv, and the tests assert it is found.
+A basis where it does not hold makes `certify_nofeas` fail with that reason rather than pass silently.
+
+GMI (repaired mode only; the bug-compatible mode is wrong on purpose and left to the bitwise tests).  `gmi_ref`
+restates the repaired formula (non-basic variables measured from the bound they sit at, f0 from the row's value,
+back-substitution of auxiliaries through their model rows) on the RECOMPUTED tableau row; `cut_cuts_off` looks for
+an integer feasible point the cut excludes.
+"""
+from fractions import Fraction
+
+import numpy as np
+
+from mvolps_amd.capi import BS, DB, FR, FX, LO, MAX, NF, NL, NS, NU, UP, CV, IV
+
+LD = np.longdouble
+RTOL = 2.0 ** -44
+EXACT_M = 64
+TOL_BND = 1e-9  # the engine's default tolerances (smcp): feasibility, reduced costs, pivots
+TOL_DJ = 1e-9
+TOL_PIV = 1e-9
+
+
+class CertError(AssertionError):
+    pass
+
+
+def _check(cond, msg):
+    if not cond:
+        raise CertError(msg)
+
+
+def _bounds(t, lb, ub):
+    if t == FR:
+        return -np.inf, np.inf
+    if t == LO:
+        return lb, np.inf
+    if t == UP:
+        return -np.inf, ub
+    if t == FX:
+        return lb, lb
+    return lb, ub
+
+
+class Model:
+    """The LP as the test loaded it: A (m x n), bounds per row / column as (type, lb, ub), c, c0, direction, kinds."""
+
+    def __init__(self, A, rows, cols, c, c0=0.0, direction=MAX, kinds=None):
+        self.A = np.array(A, dtype=np.float64).reshape(len(rows), len(cols))
+        self.rows = [tuple(r) for r in rows]
+        self.cols = [tuple(r) for r in cols]
+        self.c = np.array(c, dtype=np.float64)
+        self.c0 = float(c0)
+        self.dir = direction
+        self.kinds = list(kinds) if kinds is not None else [CV] * len(cols)
+
+    @classmethod
+    def dense(cls, A, b, c):
+        """load_dense: max c x, A x <= b, x >= 0."""
+        return cls(A, [(UP, 0.0, float(v)) for v in b], [(LO, 0.0, 0.0)] * len(c), c)
+
+    @classmethod
+    def ilp(cls, A, b, c, U):
+        """synth.load_ilp: max c x, A x <= b, 0 <= x <= U integer."""
+        return cls(A, [(UP, 0.0, float(v)) for v in b], [(DB, 0.0, float(U))] * len(c), c, kinds=[IV] * len(c))
+
+    def copy(self):
+        return Model(self.A.copy(), list(self.rows), list(self.cols), self.c.copy(), self.c0, self.dir, list(self.kinds))
+
+    @property
+    def m(self):
+        return self.A.shape[0]
+
+    @property
+    def n(self):
+        return self.A.shape[1]
+
+    def add_row(self, coef, t, lb, ub):
+        self.A = np.vstack([self.A, np.asarray(coef, dtype=np.float64).reshape(1, -1)])
+        self.rows.append((t, lb, ub))
+
+    def add_col(self, coef, t, lb, ub, cost=0.0, kind=CV):
+        self.A = np.hstack([self.A, np.asarray(coef, dtype=np.float64).reshape(-1, 1)])
+        self.cols.append((t, lb, ub))
+        self.c = np.append(self.c, cost)
+        self.kinds.append(kind)
+
+    def set_col_bnds(self, j, t, lb, ub):
+        self.cols[j - 1] = (t, lb, ub)
+
+    def set_row_bnds(self, i, t, lb, ub):
+        self.rows[i - 1] = (t, lb, ub)
+
+    def lo_hi(self):
+        """Bounds of every variable k = 1..m+n at index k - 1 (+-inf where absent)."""
+        b = [_bounds(*r) for r in self.rows] + [_bounds(*r) for r in self.cols]
+        return np.array([x for x, _ in b]), np.array([y for _, y in b])
+
+    def is_int(self):
+        return np.array([False] * self.m + [k != CV for k in self.kinds])
+
+    def Mcol(self, k):
+        """Column of M = [I | -A] for variable k (1-based)."""
+        if k <= self.m:
+            e = np.zeros(self.m)
+            e[k - 1] = 1.0
+            return e
+        return -self.A[:, k - self.m - 1]
+
+
+class Snapshot:
+    """What a handle returns through the C ABI, read once (the checks take this, so tests can damage it)."""
+
+    def __init__(self, P, status=None):
+        m, n = P.m, P.n
+        self.m, self.n = m, n
+        self.status = P.status if status is None else status
+        self.head, self.nb, self.flag = P.basis()
+        self.tab = P.tableau()
+        self.row_prim, self.col_prim = P.row_prim(), P.col_prim()
+        self.row_stat, self.col_stat = P.row_stat(), P.col_stat()
+        self.obj = P.obj
+        self.row_dual = np.array([P.api.get_row_dual(P.h, i) for i in range(1, m + 1)])
+        self.col_dual = np.array([P.api.get_col_dual(P.h, j) for j in range(1, n + 1)])
+
+    def basis(self):
+        return self.head, self.nb, self.flag
+
+
+class Ref:
+    """What the model and a basis imply: tableau body, values, reduced costs, growth."""
+
+    def __init__(self, model, basis, exact=None):
+        head, nb, flag = (np.asarray(x, dtype=np.int64) for x in basis)
+        self.model, self.head, self.nb, self.flag = model, head[1:].copy(), nb[1:].copy(), flag[1:].copy()
+        m, n = model.m, model.n
+        _check(sorted(np.concatenate([self.head, self.nb]).tolist()) == list(range(1, m + n + 1)),
+               "head and nb are not a partition of 1..m+n")
+        lo, hi = model.lo_hi()
+        self.lo, self.hi = lo, hi
+        B = np.stack([model.Mcol(k) for k in self.head], axis=1)
+        N = np.stack([model.Mcol(k) for k in self.nb], axis=1)
+        Binv = np.linalg.inv(B)
+        self.growth = float(np.abs(Binv).sum(axis=1).max() * max(1.0, np.abs(np.hstack([np.eye(m), model.A])).sum(axis=1).max()))
+        if exact is None:
+            exact = False
+        if exact:
+            self.T = _exact_solve(B, -N)
+        else:
+            X0 = np.linalg.solve(B, -N)
+            R = (-N).astype(LD) - _times_B(model, self.head, X0.astype(LD))
+            self.T = X0.astype(LD) + np.linalg.solve(B, R.astype(np.float64)).astype(LD)
+        # non-basic values by flag
+        xN = np.zeros(n, dtype=LD)
+        for j, (k, f) in enumerate(zip(self.nb, self.flag)):
+            l, u = lo[k - 1], hi[k - 1]
+            if f == NL or f == NS:
+                _check(np.isfinite(l), "non-basic variable %d flagged NL/NS has no lower bound" % k)
+                xN[j] = l
+            elif f == NU:
+                _check(np.isfinite(u), "non-basic variable %d flagged NU has no upper bound" % k)
+                xN[j] = u
+            elif f == NF:
+                xN[j] = 0.0
+            else:
+                raise CertError("flag %d of non-basic variable %d is not NL/NU/NF/NS" % (f, k))
+            _check(f != NS or l == u, "variable %d flagged NS is not fixed" % k)
+        self.xN = xN
+        self.xB = self.T @ xN
+        x = np.zeros(m + n, dtype=LD)
+        x[self.head - 1] = self.xB
+        x[self.nb - 1] = xN
+        self.x = x  # every variable, index k - 1
+        cost = np.concatenate([np.zeros(m), model.c]).astype(LD)
+        self.d = cost[self.nb - 1] + cost[self.head - 1] @ self.T
+        self.z = LD(model.c0) + cost @ x
+        self.sgn = 1.0 if model.dir == MAX else -1.0
+
+    def tol(self, ref):
+        return RTOL * self.growth * (1.0 + np.abs(np.asarray(ref, dtype=np.float64)))
+
+    def full_tableau(self):
+        m, n = self.model.m, self.model.n
+        out = np.zeros((m + 1, n + 1), dtype=LD)
+        out[1:, 1:] = self.T
+        out[1:, 0] = self.xB
+        out[0, 1:] = self.d
+        out[0, 0] = self.z
+        return out
+
+
+def _times_B(model, head, X):
+    """B X in longdouble without forming a product over the auxiliary (unit) columns."""
+    m = model.m
+    out = np.zeros((m, X.shape[1]), dtype=LD)
+    aux = head <= m
+    out[head[aux] - 1] += X[aux]
+    s = np.nonzero(~aux)[0]
+    if len(s):
+        As = model.A[:, head[s] - m - 1].astype(LD)
+        out -= np.einsum("ik,kj->ij", As, X[s])
+    return out
+
+
+def _exact_solve(B, R):
+    """B^-1 R in fractions (Gauss-Jordan, first non-zero pivot), returned as longdouble."""
+    m = B.shape[0]
+    W = [[Fraction(float(v)) for v in B[i]] + [Fraction(float(v)) for v in R[i]] for i in range(m)]
+    for p in range(m):
+        r = next(i for i in range(p, m) if W[i][p] != 0)
+        W[p], W[r] = W[r], W[p]
+        piv = W[p][p]
+        W[p] = [v / piv for v in W[p]]
+        for i in range(m):
+            if i != p and W[i][p] != 0:
+                f = W[i][p]
+                W[i] = [a - f * b for a, b in zip(W[i], W[p])]
+    return np.array([[LD(v.numerator) / LD(v.denominator) for v in row[m:]] for row in W], dtype=LD)
+
+
+# ------------------------------------------------------------------------------------------------ state checks
+
+
+def certify_tableau(ref, tab, what=""):
+    """The handle's (m+1) x (n+1) tableau against the reference, every entry."""
+    full = ref.full_tableau()
+    tab = np.asarray(tab, dtype=np.float64)
+    _check(tab.shape == full.shape, "%s: tableau shape %s, model says %s" % (what, tab.shape, full.shape))
+    _check(np.all(np.isfinite(tab)), "%s: non-finite tableau entry" % what)
+    err = np.abs(tab.astype(LD) - full).astype(np.float64)
+    lim = ref.tol(full)
+    bad = err > lim
+    if bad.any():
+        i, j = np.unravel_index(np.argmax(err / lim), err.shape)
+        raise CertError("%s: tableau entry (%d,%d) = %.17g, reference %.17g (|diff| %.3g > tol %.3g, growth %.3g)"
+                        % (what, i, j, tab[i, j], float(full[i, j]), err[i, j], lim[i, j], ref.growth))
+    return float((err / lim).max()) if err.size else 0.0
+
+
+def certify_values(ref, P, what=""):
+    """Statuses from the basis, primal values from the flags, row_prim = A col_prim, objective = c x + c0 (P: Snapshot)."""
+    m, n = ref.model.m, ref.model.n
+    stat = np.empty(m + n, dtype=np.int64)
+    stat[ref.head - 1] = BS
+    stat[ref.nb - 1] = ref.flag
+    _check(np.array_equal(np.asarray(P.row_stat), stat[:m]), "%s: row statuses disagree with the basis" % what)
+    _check(np.array_equal(np.asarray(P.col_stat), stat[m:]), "%s: column statuses disagree with the basis" % what)
+    xr, xs = np.asarray(P.row_prim), np.asarray(P.col_prim)
+    x = np.concatenate([xr, xs])
+    lim = ref.tol(ref.x)
+    err = np.abs(x.astype(LD) - ref.x).astype(np.float64)
+    _check(np.all(err <= lim), "%s: primal value of variable %d is %.17g, reference %.17g"
+           % (what, int(np.argmax(err / lim)) + 1, x[np.argmax(err / lim)], float(ref.x[np.argmax(err / lim)])))
+    Ax = ref.model.A.astype(LD) @ xs.astype(LD)
+    scale = np.abs(ref.model.A) @ np.abs(xs) + 1.0
+    _check(np.all(np.abs(Ax - xr.astype(LD)).astype(np.float64) <= RTOL * ref.growth * scale),
+           "%s: row_prim != A col_prim" % what)
+    _check(abs(float(LD(P.obj) - ref.z)) <= RTOL * ref.growth * (1.0 + abs(float(ref.z)) + np.abs(ref.model.c) @ np.abs(xs)),
+           "%s: objective %.17g, c x + c0 = %.17g" % (what, P.obj, float(ref.z)))
+
+
+def primal_violation(ref):
+    """Largest violation of the model's TRUE bounds, relative like the engine's (1 + |bound|)."""
+    x = ref.x.astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        vl = np.where(np.isfinite(ref.lo), (ref.lo - x) / (1.0 + np.abs(ref.lo)), 0.0)
+        vu = np.where(np.isfinite(ref.hi), (x - ref.hi) / (1.0 + np.abs(ref.hi)), 0.0)
+    return float(max(vl.max(initial=0.0), vu.max(initial=0.0)))
+
+
+def _dj_slack(ref):
+    return TOL_DJ + ref.tol(ref.d)
+
+
+def certify_opt(ref, P, what="", tol_bnd=TOL_BND, tol_dj=TOL_DJ):
+    """OPT: primal feasible against the true bounds, reduced-cost signs fit every non-basic status and the direction,
+    get_row_dual / get_col_dual equal the recomputed reduced costs (0 on basic variables).  P: Snapshot."""
+    v = primal_violation(ref)
+    _check(v <= tol_bnd + RTOL * ref.growth, "%s: OPT but a bound is violated by %.3g" % (what, v))
+    d = (ref.sgn * ref.d).astype(np.float64)
+    slack = tol_dj + ref.tol(ref.d)
+    for j, f in enumerate(ref.flag):
+        k = ref.nb[j]
+        ok = {NL: d[j] <= slack[j], NU: d[j] >= -slack[j], NF: abs(d[j]) <= slack[j], NS: True}[int(f)]
+        _check(ok, "%s: OPT but variable %d (flag %d) has reduced cost %.3g of the improving sign" % (what, k, f, float(ref.d[j])))
+    m, n = ref.model.m, ref.model.n
+    dual = np.zeros(m + n, dtype=LD)
+    dual[ref.nb - 1] = ref.d
+    got = np.concatenate([P.row_dual, P.col_dual])
+    err = np.abs(got.astype(LD) - dual).astype(np.float64)
+    lim = ref.tol(dual)
+    _check(np.all(err <= lim), "%s: dual of variable %d is %.17g, reference %.17g"
+           % (what, int(np.argmax(err / lim)) + 1, got[np.argmax(err / lim)], float(dual[np.argmax(err / lim)])))
+
+
+def unbounded_ray(ref, tol_dj=TOL_DJ, tol_piv=TOL_PIV):
+    """An improving non-basic column with no blocking entry in the recomputed column: (j, ray over all m+n variables)
+    or None."""
+    lo, hi = ref.lo, ref.hi
+    d = (ref.sgn * ref.d).astype(np.float64)
+    for j, f in enumerate(ref.flag):
+        k = ref.nb[j]
+        for sdir in (1, -1):
+            if sdir > 0 and not (f in (NL, NF) and d[j] > tol_dj and hi[k - 1] == np.inf):
+                continue
+            if sdir < 0 and not (f in (NU, NF) and d[j] < -tol_dj and lo[k - 1] == -np.inf):
+                continue
+            a = (ref.T[:, j] * sdir).astype(np.float64)
+            hb, lb = hi[ref.head - 1], lo[ref.head - 1]
+            if np.any((a > tol_piv) & np.isfinite(hb)) or np.any((a < -tol_piv) & np.isfinite(lb)):
+                continue
+            ray = np.zeros(ref.model.m + ref.model.n, dtype=LD)
+            ray[k - 1] = sdir
+            ray[ref.head - 1] = ref.T[:, j] * sdir
+            return k, ray
+    return None
+
+
+def certify_unbnd(ref, what="", tol_bnd=TOL_BND):
+    """UNBND: the current point is primal feasible and a ray from it improves the objective without end: A r_S = r_R,
+    c r improving, no variable with a finite bound moves towards it."""
+    v = primal_violation(ref)
+    _check(v <= tol_bnd + RTOL * ref.growth, "%s: UNBND but the point is infeasible by %.3g" % (what, v))
+    found = unbounded_ray(ref)
+    _check(found is not None, "%s: UNBND but no non-basic column of the final basis is an improving unblocked ray" % what)
+    k, r = found
+    m = ref.model.m
+    res = ref.model.A.astype(LD) @ r[m:] - r[:m]
+    _check(float(np.abs(res).max(initial=0.0)) <= RTOL * ref.growth * (1.0 + float(np.abs(r).max())), "%s: ray violates A x_S = x_R" % what)
+    gain = ref.sgn * float(np.concatenate([np.zeros(m), ref.model.c]).astype(LD) @ r)
+    _check(gain > TOL_DJ, "%s: ray does not improve the objective (%.3g)" % (what, gain))
+    rf = r.astype(np.float64)
+    _check(not np.any((rf > TOL_PIV) & np.isfinite(ref.hi)) and not np.any((rf < -TOL_PIV) & np.isfinite(ref.lo)),
+           "%s: ray runs into a bound" % what)
+    return k
+
+
+def _interval(coefB, coefN, ref):
+    """Interval of sum coefB . x_B + coefN . x_N over the box of bounds (longdouble; 0 * inf = 0)."""
+    lo = np.concatenate([ref.lo[ref.head - 1], ref.lo[ref.nb - 1]]).astype(LD)
+    hi = np.concatenate([ref.hi[ref.head - 1], ref.hi[ref.nb - 1]]).astype(LD)
+    a = np.concatenate([coefB, coefN]).astype(LD)
+    nz = a != 0
+    a, lo, hi = a[nz], lo[nz], hi[nz]
+    lower = np.where(a > 0, a * lo, a * hi).sum()
+    upper = np.where(a > 0, a * hi, a * lo).sum()
+    scale = (np.abs(a) * np.where(np.isfinite(lo), np.abs(lo), 0) + np.abs(a) * np.where(np.isfinite(hi), np.abs(hi), 0)).sum()
+    return lower, upper, float(scale)
+
+
+def farkas(ref, tol_bnd=TOL_BND):
+    """A row combination u of the final basis whose interval over the box excludes 0: ('row', p) for a single out-of-
+    bounds row (dual simplex), ('sum', None) for the signs of all infeasible rows (phase 1), or None."""
+    xB = ref.xB.astype(np.float64)
+    lb, ub = ref.lo[ref.head - 1], ref.hi[ref.head - 1]
+    g = np.zeros(len(xB))
+    g[np.isfinite(lb) & (xB < lb - tol_bnd * (1 + np.abs(np.where(np.isfinite(lb), lb, 0))))] = 1.0
+    g[np.isfinite(ub) & (xB > ub + tol_bnd * (1 + np.abs(np.where(np.isfinite(ub), ub, 0))))] = -1.0
+    cands = [("row", p, np.eye(len(xB))[p] * g[p]) for p in np.nonzero(g)[0]]
+    if np.count_nonzero(g) > 1:
+        cands.append(("sum", None, g))
+    for kind, p, u in cands:
+        cu = u.astype(LD)
+        lo_, hi_, scale = _interval(cu, -(cu @ ref.T), ref)
+        margin = RTOL * ref.growth * (1.0 + scale)
+        if lo_ > margin or hi_ < -margin:
+            return kind, p
+    return None
+
+
+def certify_nofeas(ref, what=""):
+    _check(primal_violation(ref) > TOL_BND, "%s: NOFEAS but the final basis is primal feasible" % what)
+    found = farkas(ref)
+    _check(found is not None, "%s: NOFEAS but no row combination of the final basis excludes 0 over the bounds" % what)
+    return found
+
+
+def certify(model, P, status=None, exact=None, what="", tableau=True):
+    """All checks that apply to a handle's state (P: a handle or a Snapshot); returns the Ref.  status: the handle's
+    unless given."""
+    from mvolps_amd.capi import NOFEAS, OPT, UNBND
+
+    S = P if isinstance(P, Snapshot) else Snapshot(P, status)
+    ref = Ref(model, S.basis(), exact=exact)
+    if tableau:
+        certify_tableau(ref, S.tab, what)
+    certify_values(ref, S, what)
+    st = S.status
+    if st == OPT:
+        certify_opt(ref, S, what)
+    elif st == UNBND:
+        certify_unbnd(ref, what)
+    elif st == NOFEAS:
+        certify_nofeas(ref, what)
+    return ref
+
+
+def certify_eval_tab_row(ref, P, what=""):
+    """eval_tab_row(k) of every basic variable: (ind, val) = the non-zeros of the recomputed row, by non-basic position."""
+    for i, k in enumerate(ref.head):
+        ind, val = P.eval_tab_row(int(k))
+        row = ref.T[i]
+        pos = {int(v): j for j, v in enumerate(ref.nb)}
+        _check(all(int(v) in pos for v in ind), "%s: eval_tab_row(%d) names a basic variable" % (what, k))
+        got = np.zeros(len(row))
+        got[[pos[int(v)] for v in ind]] = val
+        lim = ref.tol(row)
+        _check(np.all(np.abs(got.astype(LD) - row).astype(np.float64) <= lim), "%s: eval_tab_row(%d) differs from the reference row" % (what, k))
+        big = np.abs(row.astype(np.float64)) > lim
+        _check(np.all(got[big] != 0), "%s: eval_tab_row(%d) drops a non-zero" % (what, k))
+
+
+# ------------------------------------------------------------------------------------------------ GMI
+
+
+def frac(x):
+    return x - np.floor(x)
+
+
+def gmi_ref(ref, j):
+    """Repaired GMI cut of basic integer column j from the recomputed row: (coef[1..n] as array of n, rhs) for the cut
+    coef . x_S >= rhs, or None where the formula gives none (f0 out of (1e-6, 1 - 1e-6), a free non-basic entry,
+    no coefficient).
+
+    Row i of x_j: x_j = beta + sum_k T_k (x_k - v_k).  Measure every non-basic variable from the bound it sits at,
+    y_k = x_k - lb_k (NL) or ub_k - x_k (NU), so x_j + sum_k abar_k y_k = beta with abar_k = -T_k (NL), +T_k (NU).  With
+    f0 = frac(beta): integer y_k contribute g_k = f_k / f0 if f_k <= f0 else (1 - f_k) / (1 - f0) (f_k = frac(abar_k)),
+    continuous ones abar_k / f0 if abar_k >= 0 else -abar_k / (1 - f0), and sum_k g_k y_k >= 1 holds at every integer
+    point.  Back in x: y_k expands to +-(x_k - bound), auxiliaries to their model rows."""
+    model = ref.model
+    m, n = model.m, model.n
+    i = int(np.nonzero(ref.head == m + j)[0][0])
+    beta = float(ref.xB[i])
+    f0 = frac(beta)
+    if f0 < 1e-6 or f0 > 1 - 1e-6:
+        return None
+    isint = model.is_int()
+    w = np.zeros(m + n, dtype=LD)
+    rhs = LD(1.0)
+    row = ref.T[i]
+    for t, k in enumerate(ref.nb):
+        a = float(row[t])
+        if a == 0.0 or abs(a) <= 1e-300:
+            continue
+        f = ref.flag[t]
+        if f == NS:
+            continue
+        if f == NF:
+            return None
+        abar = -a if f == NL else a
+        if isint[k - 1]:
+            fj = frac(abar)
+            g = fj / f0 if fj <= f0 else (1 - fj) / (1 - f0)
+        else:
+            g = abar / f0 if abar >= 0 else -abar / (1 - f0)
+        if f == NL:
+            w[k - 1] += g
+            rhs += LD(g) * LD(ref.lo[k - 1])
+        else:
+            w[k - 1] -= g
+            rhs -= LD(g) * LD(ref.hi[k - 1])
+    coef = w[m:] + w[:m] @ model.A.astype(LD)
+    if not np.any(coef != 0):
+        return None
+    return coef, rhs
+
+
+def integer_points(model, limit=600000):
+    """Every integer point of the column box (finite bounds) that satisfies the model rows, as a float array."""
+    lo, hi = model.lo_hi()
+    lo, hi = lo[model.m:], hi[model.m:]
+    _check(np.all(np.isfinite(lo) & np.isfinite(hi)), "enumeration needs a finite box")
+    ranges = [np.arange(np.ceil(l), np.floor(u) + 1) for l, u in zip(lo, hi)]
+    total = int(np.prod([len(r) for r in ranges]))
+    _check(total <= limit, "box has %d points, more than %d" % (total, limit))
+    X = np.stack(np.meshgrid(*ranges, indexing="ij"), axis=-1).reshape(-1, model.n)
+    r = X @ model.A.T
+    rl, rh = model.lo_hi()
+    ok = np.all((r >= rl[: model.m] - 1e-9) & (r <= rh[: model.m] + 1e-9), axis=1)
+    return X[ok]
+
+
+def cut_cuts_off(coef, rhs, points, tol=1e-9):
+    """Indices of the points the cut coef . x >= rhs excludes (beyond tol * (1 + |rhs|))."""
+    lhs = np.asarray(points, dtype=np.float64) @ np.asarray(coef, dtype=np.float64)
+    return np.nonzero(lhs < float(rhs) - tol * (1.0 + abs(float(rhs)) + np.abs(coef).sum()))[0]
+
+
+def certify_gmi(ref, j, coef, rhs, points=(), what=""):
+    """A repaired cut the handle returned for column j: (a) equals the formula on the recomputed row, (b) is violated by
+    the LP vertex (returns the efficacy), (c) excludes none of `points` (integer feasible points)."""
+    exp = gmi_ref(ref, j)
+    _check(exp is not None, "%s: the engine cut column %d, the formula gives no cut" % (what, j))
+    ec, er = exp
+    coef = np.asarray(coef, dtype=np.float64)
+    # a coefficient is g_j (an entry of the row over f0 or 1 - f0) plus the auxiliaries' g_i times a column of A: its
+    # relative error is the row's, amplified by at most the column sums of A
+    amp = 1.0 + np.abs(ref.model.A).sum(axis=0).max()
+    lim = RTOL * ref.growth * amp * (1.0 + np.abs(ec).astype(np.float64))
+    _check(np.all(np.abs(coef.astype(LD) - ec).astype(np.float64) <= lim), "%s: cut of column %d differs from the formula (max %.3g)"
+           % (what, j, float(np.abs(coef.astype(LD) - ec).max())))
+    bnd = np.abs(np.concatenate([ref.lo, ref.hi]))
+    bnd = 1.0 + bnd[np.isfinite(bnd)].max(initial=0.0)
+    _check(abs(float(LD(rhs) - er)) <= RTOL * ref.growth * amp * bnd * (1.0 + abs(float(er))),
+           "%s: cut rhs of column %d is %.17g, formula %.17g" % (what, j, rhs, float(er)))
+    xs = ref.x[ref.model.m:].astype(np.float64)
+    viol = float(rhs) - coef @ xs
+    eff = viol / np.sqrt(coef @ coef)
+    _check(eff > 1e-9, "%s: cut of column %d is not violated by the LP vertex (efficacy %.3g)" % (what, j, eff))
+    off = cut_cuts_off(coef, rhs, points) if len(points) else []
+    _check(len(off) == 0, "%s: cut of column %d excludes the integer feasible point %s" % (what, j, None if not len(off) else points[off[0]].tolist()))
+    return eff

@@ -1,0 +1,456 @@
+"""GPU: the engine's state certified directly against the model (tests/certify.py), without the oracle: tableau identity,
+values, statuses, duals and the OPT / UNBND / NOFEAS certificates at the places where kernels go wrong -- iteration
+limits inside and at the end of chains, every forced path, warm-started children, clones, batches, dual chains, cut rows
+appended in the current basis, eval_tab_row, and the repaired GMI cuts of mvx_gmi_cuts / mvx_gmi_cuts_many against
+integer points.  The bitwise parity tests stay the primary bar; these catch what engine and oracle could share."""
+import collections
+import ctypes as C
+import json
+import os
+
+import numpy as np
+import pytest
+
+from mvolps_amd import capi, synth
+from mvolps_amd.capi import DB, LO, NOFEAS, OPT, UNBND, UP
+
+from . import certify as cf
+from . import lpgen
+from .test_certify import infeasible_general_lp
+
+pytestmark = pytest.mark.gpu
+
+COUNTS = collections.Counter()  # (path, status) -> certified states
+PINS = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "milp_pins.json")))
+
+
+def cert(model, P, path, status=None, **kw):
+    ref = cf.certify(model, P, status=status, what=path, **kw)
+    COUNTS[(path, P.status if status is None else status)] += 1
+    return ref
+
+
+def dense(api, m, n, seed):
+    A, b, c = synth.dense_lp(m, n, seed)
+    P = api.create()
+    P.load_dense(A, b, c)
+    return P, cf.Model.dense(A, b, c)
+
+
+def ilp(api, m, n, seed, U, cap=0.4):
+    A, b, c, U = synth.dense_ilp(m, n, seed, U, cap)
+    return lpgen.load_ilp(api, A, b, c, U), cf.Model.ilp(A, b, c, U)
+
+
+def child(P, M, j, t, lo, hi):
+    ch, Mc = P.copy(), M.copy()
+    ch.api.set_col_bnds(ch.h, j, t, lo, hi)
+    Mc.set_col_bnds(j, t, lo, hi)
+    return ch, Mc
+
+
+def fractional(P):
+    x = P.col_prim()
+    return x, [j + 1 for j in range(len(x)) if abs(x[j] - np.round(x[j])) > 1e-6]
+
+
+def batch(api, probs):
+    arr = (C.c_void_p * len(probs))(*[p.h for p in probs])
+    rcs = (C.c_int * len(probs))()
+    assert api.simplex_batch(arr, len(probs), None, rcs) == 0
+    return list(rcs)
+
+
+# ---------------------------------------------------------------------------------------- dense and ragged shapes
+
+
+@pytest.mark.parametrize("m,n,seed", [(3, 5, 1), (1, 1, 102), (2, 511, 613), (33, 513, 646), (257, 31, 388), (17, 33, 2),
+                                      (64, 128, 12345), (100, 37, 5), (512, 1024, 12345), (1024, 2048, 12345)])
+def test_dense_identity_at_stops_then_opt(gpu, m, n, seed):
+    P, M = dense(gpu, m, n, seed)
+    for lim in (1, 1, 2):  # stops after the first, second and fourth pivot
+        P.simplex(it_lim=lim)
+        if P.status == OPT:
+            break
+        cert(M, P, "dense stop", exact=(m <= 17))
+    assert P.simplex() == 0 and P.status == OPT
+    ref = cert(M, P, "dense", exact=(m <= 17))
+    if m <= 512:
+        cf.certify_eval_tab_row(ref, P, "dense %dx%d" % (m, n))
+
+
+@pytest.fixture
+def paths(gpu):
+    yield gpu
+    gpu.set_chain(0)
+    gpu.set_cluster(1)
+    gpu.set_persist(1)
+    gpu.set_tuning(0, 1, 0)
+    gpu.set_dual_chain(0)
+    gpu.set_refresh(1024, 1e-9)
+
+
+@pytest.mark.parametrize("cluster", [1, 0], ids=["cluster", "two-launch"])
+@pytest.mark.parametrize("chain", [5, 32])
+def test_chain_stops_inside_and_at_the_end(paths, cluster, chain):
+    """Chain length k forced: limits k - 1, k, k + 1 (and 33 for k = 32) end inside a chain, at its end and one past."""
+    paths.set_persist(0)
+    paths.set_cluster(cluster)
+    paths.set_chain(chain)
+    for (m, n, seed) in ((64, 128, 1), (300, 700, 11)):
+        for lim in sorted({chain - 1, chain, chain + 1, 33}):
+            P, M = dense(paths, m, n, seed)
+            P.simplex(it_lim=lim)
+            cert(M, P, "chain stop")
+        P.simplex()
+        cert(M, P, "chain")
+
+
+def test_resident_tableau_and_update_variants(paths):
+    """k_persist (resident tableau) on a degenerate LP, then every tr, hot, nt variant of the streamed update."""
+    A, b, c = lpgen.degenerate_lp(200, 300, 4)
+    paths.set_cluster(0)
+    P = lpgen.load_degenerate(paths, A, b, c)
+    assert P.simplex() == 0
+    cert(cf.Model(A, [(UP, 0.0, float(x)) for x in b], [(DB, 0.0, 2.0)] * 300, c), P, "persist")
+    paths.set_cluster(1)
+    for tr, hot, nt in ((4, 1, 0), (8, 1, 0), (16, 1, 0), (32, 1, 0), (16, 0, 0), (8, 1, 1)):
+        paths.set_tuning(tr, hot, nt)
+        P, M = dense(paths, 301, 1031, 77)
+        for lim in (1, 2, 37):
+            P.simplex(it_lim=lim)
+            cert(M, P, "update variant stop")
+        P.simplex()
+        cert(M, P, "update variant")
+
+
+def test_forced_refresh(paths):
+    """Refresh with tolerance 0 after 8 pivots: the rebuilt tableau is the model's for the same basis."""
+    paths.set_refresh(8, 0.0)
+    for (m, n, seed) in ((40, 64, 3), (96, 160, 5), (128, 256, 1)):
+        P, M = dense(paths, m, n, seed)
+        P.simplex()
+        assert paths.get_refresh_cnt(P.h) >= 1
+        cert(M, P, "refresh")
+        x, frac = fractional(P)
+        ch, Mc = child(P, M, int(np.argmax(x)) + 1, UP, 0.0, float(np.floor(x.max()) - 1.0))
+        ch.simplex()
+        cert(Mc, ch, "refresh child")
+
+
+def test_general_bounds_every_status(gpu):
+    """600 general-bounds LPs (seeds 7, 1..4; one in four infeasible by two contradicting rows): phase 1, bound flips,
+    FX / FR rows and columns, both directions -- each state with the certificate of its status."""
+    seen = collections.Counter()
+    for seed in (7, 1, 2, 3, 4):
+        rng = np.random.default_rng(seed)
+        for t in range(120):
+            A, rb, cb, c, d = infeasible_general_lp(rng) if (seed != 7 and t % 4 == 3) else lpgen.random_general_lp(rng)
+            P = gpu.create()
+            P.load_general(A, rb, cb, c, direction=d)
+            assert P.simplex() == 0
+            cert(cf.Model(A, rb, cb, c, direction=d), P, "general", exact=True)
+            seen[P.status] += 1
+    assert seen[OPT] > 200 and seen[UNBND] > 40 and seen[NOFEAS] > 100, seen
+
+
+# ---------------------------------------------------------------------------------------- B&B-shaped state
+
+
+def test_children_clones_and_pending_edits(gpu):
+    P, M = ilp(gpu, 64, 128, 3, 3)
+    P.simplex()
+    cert(M, P, "root")
+    x, frac = fractional(P)
+    assert len(frac) >= 13
+    for j in frac[:3]:
+        for (t, lo, hi) in ((UP, 0.0, float(np.floor(x[j - 1]))), (LO, float(np.ceil(x[j - 1])), 0.0)):
+            ch, Mc = child(P, M, j, t, lo, hi)
+            cert(Mc, ch, "child before solve", status=capi.UNDEF)
+            ch.simplex()
+            cert(Mc, ch, "child")
+            gc, Mg = child(ch, Mc, frac[5], capi.FX, 0.0, 0.0)  # clone of a clone
+            gc.simplex()
+            cert(Mg, gc, "grandchild")
+    for k in (3, 8, 9, 13):  # pending bound edits on a fresh clone
+        Q, MQ = P.copy(), M.copy()
+        for j in frac[:k]:
+            Q.api.set_col_bnds(Q.h, j, DB, 0.0, float(np.floor(x[j - 1])))
+            MQ.set_col_bnds(j, DB, 0.0, float(np.floor(x[j - 1])))
+        cert(MQ, Q, "edits before solve", status=capi.UNDEF)
+        Q.simplex()
+        cert(MQ, Q, "edits")
+    Q, MQ = P.copy(), M.copy()
+    for j in range(1, 129):
+        Q.api.set_col_bnds(Q.h, j, capi.FX, 3.0, 3.0)
+        MQ.set_col_bnds(j, capi.FX, 3.0, 3.0)
+    Q.simplex()
+    assert Q.status == NOFEAS
+    cert(MQ, Q, "child")
+
+
+@pytest.mark.parametrize("slots", [2, 3, 5, 64])
+def test_batch_children(paths, slots):
+    paths.set_batch_slots(slots)
+    try:
+        P, M = ilp(paths, 24, 48, 6, 2)
+        P.simplex()
+        x, frac = fractional(P)
+        kids = [child(P, M, j, t, lo, hi) for j in frac[:6]
+                for (t, lo, hi) in ((UP, 0.0, float(np.floor(x[j - 1]))), (LO, float(np.ceil(x[j - 1])), 0.0))]
+        rcs = batch(paths, [k for k, _ in kids])
+        for (k, Mk), rc in zip(kids, rcs):
+            assert rc == 0
+            cert(Mk, k, "batch")
+    finally:
+        paths.set_batch_slots(64)
+
+
+@pytest.mark.parametrize("dchain", [3, 8])
+def test_dual_chains_on_512x1024_children(paths, dchain):
+    """Dual chains on the children of the 512x1024 root, then one batch of 64 of them (a full window)."""
+    paths.set_dual_chain(dchain)
+    P, M = ilp(paths, 512, 1024, 12345, 3)
+    P.simplex()
+    x, frac = fractional(P)
+    kids = []
+    for j in frac[:32]:
+        for (t, lo, hi) in ((UP, 0.0, float(np.floor(x[j - 1]))), (LO, float(np.ceil(x[j - 1])), 0.0)):
+            kids.append(child(P, M, j, t, lo, hi))
+    for k, Mk in kids[:2]:
+        k.simplex()
+        cert(Mk, k, "dual chain")
+    if dchain == 8:
+        rcs = batch(paths, [k for k, _ in kids[2:]])
+        for i, ((k, Mk), rc) in enumerate(zip(kids[2:], rcs)):
+            assert rc == 0
+            cert(Mk, k, "window", tableau=(i % 8 == 0))  # every eighth tableau in full, values and certificates of all
+
+
+# ---------------------------------------------------------------------------------------- cut rows
+
+
+def append_row(P, M, coef, t, lb, ub):
+    n = P.n
+    r = P.api.add_rows(P.h, 1)
+    P.set_mat_row(r, np.arange(n + 1, dtype=np.int32), np.concatenate([[0.0], coef]))
+    P.api.set_row_bnds(P.h, r, t, lb, ub)
+    M.add_row(coef, t, lb, ub)
+
+
+def test_appended_rows_in_the_current_basis(gpu):
+    """The new row written in terms of the CURRENT basis right after mvx_add_rows + set_mat_row (no pivot yet), again
+    after the dual re-solve; 80 rows across the spare rows and the slab growth."""
+    P, M = ilp(gpu, 12, 24, 7, 3)
+    P.simplex()
+    rng = np.random.default_rng(11)
+    for k in range(80):
+        v = np.round(rng.normal(size=24) * 2)
+        x = P.col_prim()
+        append_row(P, M, v, LO, float(v @ x) - (0.0 if k % 3 else -0.25), 0.0)
+        cert(M, P, "cut row before a pivot", status=capi.UNDEF, exact=(k < 20))
+        P.simplex()
+        cert(M, P, "cut row")
+    assert P.m == 92
+    P, M = ilp(gpu, 512, 1024, 12345, 3)
+    P.simplex()
+    x = P.col_prim()
+    for k in range(3):
+        v = np.round(rng.normal(size=1024))
+        append_row(P, M, v, UP, float(np.floor(v @ x)), 0.0)
+        cert(M, P, "cut row before a pivot", status=capi.UNDEF)
+        P.simplex()
+        cert(M, P, "cut row")
+
+
+def test_columns_added_after_a_solve(gpu):
+    P, M = dense(gpu, 30, 50, 4)
+    P.simplex()
+    rng = np.random.default_rng(2)
+    j0 = P.api.add_cols(P.h, 3)
+    for j in range(j0, j0 + 3):
+        coef = np.round(rng.random(30) * 4)
+        P.api.set_col_bnds(P.h, j, DB, 0.0, 2.0)
+        P.api.set_obj_coef(P.h, j, 1.5)
+        M.add_col(coef, DB, 0.0, 2.0, cost=1.5)
+    for i in range(1, 31):
+        P.set_mat_row(i, np.arange(54, dtype=np.int32), np.concatenate([[0.0], M.A[i - 1]]))
+    P.simplex()
+    cert(M, P, "added columns")
+
+
+# ---------------------------------------------------------------------------------------- GMI
+
+
+def device_cuts(gpu, P, cols):
+    lib = gpu.lib
+    k, n = len(cols), P.n
+    vals, rhs, ok = np.zeros((k, n + 1)), np.zeros(k), np.zeros(k, dtype=np.int32)
+    arr = np.asarray(cols, dtype=np.int32)
+    lib.mvx_gmi_cuts.restype = C.c_int
+    lib.mvx_gmi_cuts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    assert lib.mvx_gmi_cuts(P.h, 1, arr.ctypes.data, k, vals.ctypes.data, rhs.ctypes.data, ok.ctypes.data) == 0
+    return vals, rhs, ok
+
+
+def device_cuts_many(gpu, Ps, cols):
+    lib = gpu.lib
+    k, n = len(cols), Ps[0].n
+    vals, rhs, ok = np.zeros((k, n + 1)), np.zeros(k), np.zeros(k, dtype=np.int32)
+    arr = np.asarray(cols, dtype=np.int32)
+    hs = (C.c_void_p * k)(*[p.h for p in Ps])
+    lib.mvx_gmi_cuts_many.restype = C.c_int
+    lib.mvx_gmi_cuts_many.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    assert lib.mvx_gmi_cuts_many(hs, 1, arr.ctypes.data, k, vals.ctypes.data, rhs.ctypes.data, ok.ctypes.data) == 0
+    return vals, rhs, ok
+
+
+def eligible(ref, P):
+    """Basic integer columns the repaired filter keeps (fractional part inside (1e-6, 1 - 1e-6))."""
+    m = ref.model.m
+    out = []
+    for i, k in enumerate(ref.head):
+        if k > m and cf.gmi_ref(ref, int(k) - m) is not None:
+            out.append(int(k) - m)
+    return out
+
+
+def gmi_rounds(gpu, P, M, points, what, rounds=3):
+    """Three rounds: cut every eligible column on the device, certify each cut, append the most efficacious, re-solve.
+    Returns the number of certified cuts."""
+    done = 0
+    for rnd in range(rounds):
+        ref = cert(M, P, "gmi node", tableau=M.m <= 600)
+        cols = eligible(ref, P)
+        if not cols:
+            break
+        vals, rhs, ok = device_cuts(gpu, P, cols)
+        best = None
+        for t, j in enumerate(cols):
+            if not ok[t]:
+                continue
+            eff = cf.certify_gmi(ref, j, vals[t, 1:], rhs[t], points, what="%s round %d" % (what, rnd))
+            COUNTS[("gmi cut", OPT)] += 1
+            done += 1
+            if best is None or eff > best[0]:
+                best = (eff, vals[t, 1:].copy(), rhs[t])
+        if best is None:
+            break
+        append_row(P, M, best[1], LO, float(best[2]), 0.0)
+        P.simplex()
+    return done
+
+
+@pytest.mark.parametrize("case", [(6, 10, 3, 2), (5, 12, 8, 2), (8, 11, 21, 2)], ids=lambda c: "%dx%d" % c[:2])
+def test_gmi_cuts_keep_every_integer_point(gpu, case):
+    P, M = ilp(gpu, *case)
+    pts = cf.integer_points(M)
+    P.simplex()
+    assert gmi_rounds(gpu, P, M, pts, "enumerated %dx%d" % case[:2]) >= 3
+
+
+@pytest.mark.parametrize("which", range(len(PINS["points"])), ids=lambda w: "%dx%d" % (PINS["points"][w]["m"], PINS["points"][w]["n"]))
+def test_gmi_cuts_keep_the_milp_optimum(gpu, which):
+    """24x48, the two cut-path ILPs and the 512x1024 config-5 instance: every repaired cut of three rounds keeps the
+    HiGHS milp optimum point, whose objective equals the committed pin."""
+    pin = PINS["points"][which]
+    A, b, c, U = synth.dense_ilp(pin["m"], pin["n"], pin["seed"], pin["U"], pin["cap"])
+    xs = np.array(pin["x"], dtype=np.float64)
+    assert c @ xs == pin["milp_obj"] and np.all(A @ xs <= b) and np.all((xs >= 0) & (xs <= U))
+    P, M = lpgen.load_ilp(gpu, A, b, c, U), cf.Model.ilp(A, b, c, U)
+    P.simplex()
+    assert gmi_rounds(gpu, P, M, xs[None, :], "pin %dx%d" % (pin["m"], pin["n"])) >= 3
+
+
+def test_gmi_cuts_many_over_children(gpu):
+    """mvx_gmi_cuts_many: one cut from each of several children of one root (each with its own bounds and basis)."""
+    pin = PINS["points"][0]
+    A, b, c, U = synth.dense_ilp(pin["m"], pin["n"], pin["seed"], pin["U"], pin["cap"])
+    P, M = lpgen.load_ilp(gpu, A, b, c, U), cf.Model.ilp(A, b, c, U)
+    P.simplex()
+    x, frac = fractional(P)
+    kids, refs, cols = [], [], []
+    xs = np.array(pin["x"], dtype=np.float64)
+    for j in frac[:4]:
+        for (t, lo, hi) in ((DB, 0.0, float(np.floor(x[j - 1]))), (DB, float(np.ceil(x[j - 1])), U)):
+            ch, Mc = child(P, M, j, t, lo, hi)
+            ch.simplex()
+            if ch.status != OPT:
+                continue
+            ref = cert(Mc, ch, "gmi child")
+            el = eligible(ref, ch)
+            if el:
+                kids.append((ch, Mc))
+                refs.append(ref)
+                cols.append(el[-1])
+    assert len(kids) >= 3
+    vals, rhs, ok = device_cuts_many(gpu, [k for k, _ in kids], cols)
+    for t, ((ch, Mc), ref, j) in enumerate(zip(kids, refs, cols)):
+        assert ok[t]
+        # a child's cut is valid for the child's box: the pin point counts only where it lies inside that box
+        lo, hi = Mc.lo_hi()
+        inside = np.all((xs >= lo[Mc.m:]) & (xs <= hi[Mc.m:]))
+        cf.certify_gmi(ref, j, vals[t, 1:], rhs[t], xs[None, :] if inside else (), what="many %d" % t)
+        COUNTS[("gmi cut many", OPT)] += 1
+
+
+# ---------------------------------------------------------------------------------------- the headline, sampled
+
+
+def test_headline_sampled_certificate(gpu):
+    """4096x8192 (BASELINE config 4) at its optimum: 256 tableau rows recomputed, each one solve with B^T (fp64, refined
+    once), with the per-row growth ||e_i B^-1||_1 ||M||_inf; all values; the OPT
+    certificate with get_col_dual over every column.  A full longdouble factor of this size takes minutes."""
+    A, b, c = synth.dense_lp(4096, 8192, 12345)
+    P = gpu.create()
+    P.load_dense(A, b, c)
+    assert P.simplex() == 0 and P.status == OPT
+    M = cf.Model.dense(A, b, c)
+    head, nb, flag = P.basis()
+    head, nb, flag = head[1:], nb[1:], flag[1:]
+    m, n = 4096, 8192
+    T = P.tableau()
+    B = np.stack([M.Mcol(k) for k in head], axis=1)
+    rows = np.random.default_rng(0).choice(m, 256, replace=False)
+    E = np.zeros((m, len(rows)))
+    E[rows, np.arange(len(rows))] = 1.0
+    Y = np.linalg.solve(B.T, E)  # columns: rows of B^-1
+    Y = Y + np.linalg.solve(B.T, E - B.T @ Y)
+    N = np.stack([M.Mcol(k) for k in nb], axis=1)
+    Tr = -(Y.T @ N)
+    normM = 1.0 + np.abs(A).sum(axis=1).max()
+    g = np.abs(Y).sum(axis=0) * normM
+    err = np.abs(T[1 + rows, 1:] - Tr)
+    assert np.all(err <= 2.0 ** -44 * g[:, None] * (1.0 + np.abs(Tr)) * 16), float((err / (g[:, None] * (1 + np.abs(Tr)))).max())
+    # values, statuses and duals with the full-size certificate (no factor needed: x_B from the model's rows)
+    x = P.col_prim()
+    xr = P.row_prim()
+    assert np.all(np.abs(A @ x - xr) <= 1e-9 * (1.0 + np.abs(A) @ np.abs(x)))
+    lo, hi = M.lo_hi()
+    allx = np.concatenate([xr, x])
+    assert np.all(allx >= lo - 1e-9 * (1 + np.abs(lo))) and np.all(allx <= hi + 1e-9 * (1 + np.abs(hi)))
+    cB = np.concatenate([np.zeros(m), c])[head - 1]
+    y = np.linalg.solve(B.T, cB)  # pi = B^-T c_B; reduced costs d_N = c_N - pi N
+    d = np.concatenate([np.zeros(m), c])[nb - 1] - y @ N
+    assert np.allclose(d, T[0, 1:], rtol=1e-9, atol=1e-9)
+    assert np.all(d[flag == capi.NL] <= 1e-9) and np.all(d[flag == capi.NU] >= -1e-9)
+    col_dual = np.array([P.api.get_col_dual(P.h, j) for j in range(1, n + 1)])
+    full = np.zeros(m + n)
+    full[nb - 1] = d
+    assert np.allclose(col_dual, full[m:], rtol=1e-9, atol=1e-9)
+    assert abs(P.obj - float(c @ x)) <= 1e-9 * abs(P.obj)
+    COUNTS[("headline sampled", OPT)] += 1
+
+
+def test_zz_certified_state_counts():
+    """Coverage of the file above: every status certified; the counts go to $MVX_CERTIFY_REPORT when set."""
+    by_status = collections.Counter()
+    for (path, st), k in COUNTS.items():
+        by_status[st] += k
+    out = os.environ.get("MVX_CERTIFY_REPORT")
+    if out:
+        with open(out, "w") as f:
+            json.dump({"by_status": {str(k): v for k, v in by_status.items()},
+                       "by_path": {"%s/%d" % k: v for k, v in sorted(COUNTS.items())}}, f, indent=1)
+    if len(COUNTS) > 20:  # the whole file ran
+        assert by_status[OPT] and by_status[NOFEAS] and by_status[UNBND], by_status
