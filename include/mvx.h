@@ -158,6 +158,13 @@ int mvx_gmi_cuts(const mvx_prob *P, int repaired, const int *cols, int count, do
    cut rows): a round of a B&B window takes one cut from each of its branching nodes (bs.cpp:249-258 run for 64 nodes at
    once).  vals is count x (n+1).  Returns -3 when the handles do not share a root (call mvx_gmi_cuts per handle then). */
 int mvx_gmi_cuts_many(const mvx_prob *const *Ps, int repaired, const int *cols, int count, double *vals, double *rhs, int *ok);
+/* printInfo (util.cpp:414-473) of `count` solved handles with the same columns, one device launch for all of them.  Per
+   handle t: status[t] = -1 (NOFEAS / INFEAS / UNBND), 0 (some integer column fractional) or 1; nviol[t] violated columns,
+   ascending, in viol[t*cap .. t*cap + nviol[t] - 1] and their primal values (the bits get_col_prim returns) in xviol[same].
+   quirks = 1: bug-compatible test (x != 0, objective coefficient != 0, trunc(x) != x); 0: 1e-9 tolerance.
+   Returns 0; -1 bad arguments (a handle without a solved tableau, different columns or objective); -2 device out of
+   memory; -3 some handle has more than `cap` violated columns. */
+int mvx_classify_many(const mvx_prob *const *Ps, int count, int quirks, int *status, int *nviol, int *viol, double *xviol, int cap);
 
 /* ---- engine-state access (parity tests, visualisers) --------------------------- */
 int mvx_get_tableau_ld(const mvx_prob *P);

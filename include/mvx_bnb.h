@@ -67,6 +67,10 @@ typedef struct mvx_lp_api {
   /* optional (may be NULL): get_col_prim for every column at once, x[1..n] -- printInfo (util.cpp:414-473) reads all n
      values of every node */
   void (*get_col_prim_all)(const void *P, double *x);
+  /* optional (may be NULL): printInfo (util.cpp:414-473) of `count` solved handles in one call (mvx_classify_many):
+     status[t] -1/0/1, nviol[t] violated columns, their indices (ascending) in viol[t*cap ...] and their values in
+     xviol[t*cap ...]; non-zero return: the caller classifies on the host */
+  int (*classify_many)(const void *const *Ps, int count, int quirks, int *status, int *nviol, int *viol, double *xviol, int cap);
 } mvx_lp_api;
 
 const mvx_lp_api *mvx_hip_lp_api(void);
@@ -96,6 +100,10 @@ typedef struct {
                            order, so the persistent pool sees the nodes as bs.cpp does) -- same tree, oids,
                            events and incumbent as node-at-a-time; default 64, 1 = node
                            at a time */
+  int best_window;      /* BEST order (node_strat = 1), engine with a batch entry: the top `best_window` open nodes
+                           are solved, classified and branched together and their decisions replayed in true
+                           best-bound order; the longest prefix the serial loop would also have popped is kept --
+                           same tree, oids, events and incumbent as node-at-a-time.  Default 0 = node at a time */
 } mvx_bnb_params;
 
 /* B&B events at the emit points of bs.cpp (message.h EventType) */
@@ -129,6 +137,8 @@ typedef struct {
   double *x;          /* x[1..n] of the incumbent (bs.cpp:181-187) */
   long long total_pivots;
   int hit_limit;
+  long long rounds;     /* best_window driver only (0 otherwise): rounds of speculation */
+  long long speculated; /* best_window driver only (0 otherwise): nodes taken into a round's window, summed */
 } mvx_bnb_result;
 
 void mvx_bnb_default_params(mvx_bnb_params *p);

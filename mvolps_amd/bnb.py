@@ -14,7 +14,7 @@ _FIELDS = [
     "get_col_stat", "get_row_stat", "get_row_ub", "get_row_lb", "get_col_ub", "get_col_lb", "get_col_type", "get_mat_row", "eval_tab_row",
     "get_it_cnt",
 ]
-_OPTIONAL = ["simplex_batch", "get_obj_dir", "gmi_cuts", "gmi_cuts_many", "get_col_prim_all"]
+_OPTIONAL = ["simplex_batch", "get_obj_dir", "gmi_cuts", "gmi_cuts_many", "get_col_prim_all", "classify_many"]
 
 
 class LpApiTable(C.Structure):
@@ -35,6 +35,7 @@ class BnbParams(C.Structure):
         ("lazy_pool", C.c_int),
         ("cut_select", C.c_int),
         ("window", C.c_int),
+        ("best_window", C.c_int),
     ]
 
 
@@ -67,6 +68,8 @@ class BnbResult(C.Structure):
         ("x", C.POINTER(C.c_double)),
         ("total_pivots", C.c_longlong),
         ("hit_limit", C.c_int),
+        ("rounds", C.c_longlong),
+        ("speculated", C.c_longlong),
     ]
 
 
@@ -98,6 +101,9 @@ def _bind(lib):
     lib.mvx_bnb_make_children.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.mvx_bnb_node_cuts.restype = C.c_int
     lib.mvx_bnb_node_cuts.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BnbParams)]
+    lib.mvx_classify_many.restype = C.c_int
+    lib.mvx_classify_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                      C.POINTER(C.c_double), C.c_int]
     lib.mvx_generateCut3.restype = C.c_int
     lib.mvx_generateCut3.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     return lib
@@ -133,10 +139,13 @@ def result_to_dict(res):
         "x": [res.x[j] for j in range(1, res.n + 1)],
         "total_pivots": res.total_pivots,
         "hit_limit": res.hit_limit,
+        "rounds": res.rounds,
+        "speculated": res.speculated,
     }
 
 
-def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, window=None, cut_select=0, cut_chance=1.0):
+def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, window=None, cut_select=0, cut_chance=1.0,
+                best_window=None):
     """mvx_bnb_params with ParameterObj's defaults (util.h:65-67) overridden by the arguments."""
     pr = BnbParams()
     lib().mvx_bnb_default_params(C.byref(pr))
@@ -145,14 +154,17 @@ def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, l
     pr.cut_select, pr.cut_chance = cut_select, cut_chance
     if window is not None:
         pr.window = window
+    if best_window is not None:
+        pr.best_window = best_window
     return pr
 
 
 def branch_and_bound(prob, var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, table=None, window=None,
-                     cut_select=0, cut_chance=1.0):
-    """Run the driver on `prob` (a capi.Prob).  table=None uses the gfx950 engine's own table."""
+                     cut_select=0, cut_chance=1.0, best_window=None):
+    """Run the driver on `prob` (a capi.Prob).  table=None uses the gfx950 engine's own table.  best_window > 1 with
+    node_strat=1: the speculative best-bound window (mvx_bnb_params.best_window)."""
     L = lib()
-    pr = make_params(var_strat, node_strat, cut_strat, max_nodes, quirks, lazy_pool, window, cut_select, cut_chance)
+    pr = make_params(var_strat, node_strat, cut_strat, max_nodes, quirks, lazy_pool, window, cut_select, cut_chance, best_window)
     res = BnbResult()
     tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
     L.mvx_branchAndBound(tptr, prob.h, C.byref(pr), C.byref(res))
@@ -210,3 +222,26 @@ def make_children(a, pick, quirks=1, table=None):
     tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
     lib().mvx_bnb_make_children(tptr, a.h, pick, quirks, S2.h, S3.h)
     return S2, S3
+
+
+def classify_many(probs, quirks=1, cap=None):
+    """mvx_classify_many over capi.Prob handles: (rc, [(status, violated columns, their values) per handle])."""
+    import numpy as np
+
+    k = len(probs)
+    n = probs[0].n if k else 0
+    cap = max(1, n) if cap is None else cap
+    hs = (C.c_void_p * max(1, k))(*[p.h for p in probs])
+    st = np.zeros(max(1, k), dtype=np.int32)
+    nv = np.zeros(max(1, k), dtype=np.int32)
+    viol = np.zeros(max(1, k) * max(1, cap), dtype=np.int32)
+    xv = np.zeros(max(1, k) * max(1, cap), dtype=np.float64)
+    rc = lib().mvx_classify_many(hs, k, quirks, st.ctypes.data_as(C.POINTER(C.c_int)), nv.ctypes.data_as(C.POINTER(C.c_int)),
+                                 viol.ctypes.data_as(C.POINTER(C.c_int)), xv.ctypes.data_as(C.POINTER(C.c_double)), cap)
+    if rc != 0:
+        return rc, None
+    out = []
+    for t in range(k):
+        c = int(nv[t])
+        out.append((int(st[t]), viol[t * cap: t * cap + c].tolist(), xv[t * cap: t * cap + c].tolist()))
+    return rc, out

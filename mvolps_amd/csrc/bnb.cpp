@@ -14,12 +14,16 @@
 #include <future>
 #include <limits>
 #include <memory>
+#include <set>
 #include <unordered_map>
 #include <unordered_set>
 #include <utility>
 #include <vector>
 
 #include "../../include/mvx_bnb.h"
+
+extern "C" int mvx_classify_many(const mvx_prob *const *Ps, int count, int quirks, int *status, int *nviol, int *viol, double *xviol,
+                                 int cap) __attribute__((weak));
 
 namespace {
 
@@ -50,6 +54,21 @@ public:
     _api->set_mat_row(in, index, (int)sel.inds.size() - 1, sel.inds.data(), sel.vals.data()); // cut.cpp:40
     _api->set_row_bnds(in, index, MVX_LO, sel.lb, 0);                                          // cut.cpp:43
     return cID;
+  }
+  // the best-bound window speculates a round's cut steps in key order and rolls the pool back to where its replay stopped
+  struct Mark {
+    size_t size = 0;
+    CutContainer last;
+  };
+  Mark mark() const {
+    Mark m;
+    m.size = _cuts.size();
+    if (!_cuts.empty()) m.last = _cuts.back();
+    return m;
+  }
+  void rollback(const Mark &m) { // addToPool only appends, replaceLast only rewrites the last element
+    _cuts.resize(m.size);
+    if (!_cuts.empty()) _cuts.back() = m.last;
   }
 
 private:
@@ -1114,6 +1133,297 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
   return 0;
 }
 
+// printInfo of a round's nodes: one mvx_lp_api.classify_many call when the engine has it (one device launch for all of
+// them), else one printInfo per node.  xs[t] holds the values of node t's violated columns, in the order of its list --
+// the bits get_col_prim returns, so the host sums (bs.cpp:229-233) and the branching bound (bs.cpp:261) are unchanged.
+static void classify_round(const mvx_lp_api *api, const std::vector<void *> &hs, bool quirks, int n,
+                           std::vector<std::pair<int, std::vector<int>>> &info, std::vector<std::vector<double>> &xs) {
+  const size_t K = hs.size();
+  info.assign(K, {});
+  xs.assign(K, {});
+  if (api->classify_many && K > 0) {
+    const int cap = std::max(1, n);
+    std::vector<int> st(K), nv(K), viol(K * (size_t)cap);
+    std::vector<double> xv(K * (size_t)cap);
+    const int rc = api->classify_many(hs.data(), (int)K, quirks ? 1 : 0, st.data(), nv.data(), viol.data(), xv.data(), cap);
+    if (rc == 0) {
+      for (size_t t = 0; t < K; t++) {
+        const int *v = &viol[t * (size_t)cap];
+        const double *x = &xv[t * (size_t)cap];
+        info[t].first = st[t];
+        info[t].second.assign(v, v + nv[t]);
+        xs[t].assign(x, x + nv[t]);
+      }
+      return;
+    }
+    if (std::getenv("MVX_BNB_TIMING")) std::fprintf(stderr, "classify_round: classify_many returned %d for %zu nodes\n", rc, K);
+  }
+  for (size_t t = 0; t < K; t++) {
+    info[t] = printInfo(api, hs[t], quirks);
+    for (int i : info[t].second) xs[t].push_back(api->get_col_prim(hs[t], i));
+  }
+}
+
+// Best-bound window (node_strat = 1, best_window > 1).  The serial loop pops the open node of largest sg * upperBound
+// (pickNode's first maximum: ties go to the node inserted first), and its next pick depends on the bounds of the
+// children it has just solved, so the pops cannot be batched the way FIFO's can.  Instead each round speculates: the top
+// W open nodes S[0..W-1] are re-solved (bs.cpp:114-117), classified and -- those that would branch under the current
+// incumbent -- cut and branched, and ALL their children solved in one batched call.  The replay then walks S in key
+// order and commits S[j] with the serial logic as long as (a) S[j] is the argmax of the live open set, which now holds
+// the children committed so far in this round, and (b) S[j]'s decision is the speculated one (an incumbent found
+// earlier in the replay may prune it now, bs.cpp:210).  The first node that fails either test ends the round: it and
+// the nodes behind it stay open, untouched (cut rows go onto a clone, never onto the node's handle), their children are
+// deleted, and the persistent pool of the bug-compatible mode (bs.cpp:73, cut.cpp:16-21) is rolled back to the state
+// the committed prefix left.  oids, parents, events, pivot counts and the incumbent are booked at commit, in the order
+// the serial loop books them: the tree is the node-at-a-time one.
+int branchAndBoundBest(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm, mvx_bnb_result *res) {
+  MVOLP::ParameterObj params(api, prob, prm);
+  CutPool pool(api);
+  Recorder rec;
+  int id = 1;
+  const bool quirks = prm.reference_quirks != 0;
+  const double sg = params.sense();
+  // the open set in pop order: (sg * upperBound descending, insertion ascending) is pickNode's first maximum over the
+  // deque, whose order is insertion order (erase keeps it, children are pushed at the back).  A NaN bound sorts last.
+  struct Open {
+    double key;
+    long long ins;
+    std::shared_ptr<MVOLP::NodeData> node;
+    bool operator<(const Open &o) const { return key != o.key ? key > o.key : ins < o.ins; }
+  };
+  std::set<Open> open;
+  long long ins = 0;
+  auto push = [&](const std::shared_ptr<MVOLP::NodeData> &nd) {
+    const double k = sg * nd->upperBound;
+    open.insert(Open{std::isnan(k) ? -std::numeric_limits<double>::infinity() : k, ins++, nd});
+  };
+  auto S1 = std::make_shared<MVOLP::NodeData>(api, prob, id);
+  S1->inital = true;
+  rec.node(S1->oid, 0);
+  push(S1);
+  double bestLower = -sg * std::numeric_limits<double>::infinity();
+  const int n0 = api->get_num_cols(prob);
+  std::vector<double> xbest((size_t)n0 + 1, 0.0);
+  int incumbent_oid = 0, has_incumbent = 0, hit_limit = 0, count = 0;
+  long long rounds = 0, speculated = 0;
+  bool stop = false;
+  const size_t W = (size_t)prm.best_window;
+  const bool timing = std::getenv("MVX_BNB_TIMING") != nullptr;
+  double tA = 0, tInfo = 0, tSpec = 0, tKids = 0, tReplay = 0;
+  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+
+  struct Spec {
+    std::shared_ptr<MVOLP::NodeData> node;
+    bool branch = false;
+    int pick = 0;
+    double bound = 0.0;
+    void *S2 = nullptr, *S3 = nullptr; // speculative children, no oid yet
+    int before2 = 0, before3 = 0;
+    bool marked = false; // pool state in front of this node's cut step
+    CutPool::Mark mark;
+  };
+  std::vector<std::pair<int, std::vector<int>>> info;
+  std::vector<std::vector<double>> xs;
+  while (!open.empty() && !stop) {
+    if (prm.max_nodes > 0 && count >= prm.max_nodes) {
+      hit_limit = 1;
+      break;
+    }
+    double t0 = now();
+    std::vector<Spec> S;
+    for (auto it = open.begin(); it != open.end() && S.size() < W; ++it) {
+      S.emplace_back();
+      S.back().node = it->node;
+    }
+    const size_t K = S.size();
+    rounds++;
+    speculated += (long long)K;
+    std::vector<void *> hs(K);
+    for (size_t j = 0; j < K; j++) hs[j] = S[j].node->prob;
+    // A. the pop-time re-solve (bs.cpp:114-117) of every node of S that has not had it, in place: a node's handle is
+    // only ever read after that (its cut rows and children are clones), so a node that stays open keeps its solve and
+    // its pivot count (repiv) until it is committed.  A node whose last solve ended OPT goes through zero pivots.
+    std::vector<void *> need;
+    std::vector<int> before(K, 0);
+    for (size_t j = 0; j < K; j++) {
+      if (S[j].node->repiv >= 0) continue;
+      before[j] = api->get_it_cnt(hs[j]);
+      if (api->get_status(hs[j]) != MVX_OPT) need.push_back(hs[j]);
+    }
+    if (!need.empty()) api->simplex_batch(need.data(), (int)need.size(), nullptr, nullptr);
+    for (size_t j = 0; j < K; j++)
+      if (S[j].node->repiv < 0) S[j].node->repiv = api->get_it_cnt(hs[j]) - before[j];
+    tA += now() - t0;
+    t0 = now();
+    classify_round(api, hs, quirks, n0, info, xs);
+    tInfo += now() - t0;
+    t0 = now();
+    // B. speculate under the incumbent as it stands
+    std::vector<char> wanted(K, 0);
+    for (size_t j = 0; j < K; j++)
+      wanted[j] = S[j].branch = info[j].first == 0 && sg * api->get_obj_val(hs[j]) > sg * bestLower; // bs.cpp:210
+    std::vector<std::unique_ptr<CutContainer>> pre = round_cuts(api, hs, wanted, prm, quirks);
+    std::vector<void *> kids;
+    for (size_t j = 0; j < K; j++) {
+      Spec &sp = S[j];
+      if (!sp.branch) continue;
+      const std::vector<int> &vars = info[j].second;
+      sp.pick = params.pickVar(vars); // bs.cpp:260-261, in front of the cut step (see the FIFO window)
+      for (size_t k = 0; k < vars.size(); k++)
+        if (vars[k] == sp.pick) {
+          sp.bound = xs[j][k];
+          break;
+        }
+      void *aw = hs[j];
+      const int t = api->get_col_type(aw, sp.pick);
+      const double l = api->get_col_lb(aw, sp.pick), u = api->get_col_ub(aw, sp.pick);
+      void *base = aw;
+      if (prm.cut_strat != 0) { // bs.cpp:249-258 on a clone: the node itself stays as it is until it is committed
+        base = api->create_prob();
+        api->copy_prob(base, aw, MVX_ON);
+        sp.mark = pool.mark();
+        sp.marked = true;
+        add_node_cuts(api, base, prm, quirks, pool, pre.empty() ? nullptr : pre[j].get());
+      }
+      sp.S2 = api->create_prob();
+      api->copy_prob(sp.S2, base, MVX_ON);
+      if (base != aw) {
+        sp.S3 = base; // the cut clone becomes the second child: one clone fewer
+      } else {
+        sp.S3 = api->create_prob();
+        api->copy_prob(sp.S3, aw, MVX_ON);
+      }
+      const double fl = std::floor(sp.bound), ce = std::ceil(sp.bound);
+      if (quirks) { // same bounds as the serial loop (bs.cpp:274,282)
+        api->set_col_bnds(sp.S2, sp.pick, MVX_UP, 0, fl);
+        api->set_col_bnds(sp.S3, sp.pick, MVX_LO, ce, 0);
+      } else {
+        if (t == MVX_LO || t == MVX_DB || t == MVX_FX) api->set_col_bnds(sp.S2, sp.pick, (l == fl) ? MVX_FX : MVX_DB, l, fl);
+        else api->set_col_bnds(sp.S2, sp.pick, MVX_UP, 0, fl);
+        if (t == MVX_UP || t == MVX_DB || t == MVX_FX) api->set_col_bnds(sp.S3, sp.pick, (u == ce) ? MVX_FX : MVX_DB, ce, u);
+        else api->set_col_bnds(sp.S3, sp.pick, MVX_LO, ce, 0);
+      }
+      sp.before2 = api->get_it_cnt(sp.S2);
+      sp.before3 = api->get_it_cnt(sp.S3);
+      kids.push_back(sp.S2);
+      kids.push_back(sp.S3);
+    }
+    tSpec += now() - t0;
+    t0 = now();
+    if (!kids.empty()) api->simplex_batch(kids.data(), (int)kids.size(), nullptr, nullptr); // bs.cpp:279,287 for the round
+    tKids += now() - t0;
+    t0 = now();
+    // C. replay in true best-bound order
+    size_t j = 0;
+    for (; j < K; j++) {
+      if (prm.max_nodes > 0 && count >= prm.max_nodes) {
+        hit_limit = 1;
+        stop = true;
+        break;
+      }
+      Spec &sp = S[j];
+      if (open.begin()->node != sp.node) break; // a child committed in this round outranks it
+      const int status = info[j].first;
+      const std::vector<int> &vars = info[j].second;
+      void *aw = hs[j];
+      const double obj = api->get_obj_val(aw);
+      if (status == 0 && (sg * obj > sg * bestLower) != sp.branch) break; // pruned by an incumbent of this round
+      std::shared_ptr<MVOLP::NodeData> node = sp.node;
+      open.erase(open.begin());
+      rec.pivots += node->repiv;
+      rec.emit(MVX_EV_PREGNANT, node->oid, obj, 0.0, 0, 0);
+      if (node->inital) {
+        if (status == -1) {
+          rec.prune[(size_t)node->oid] = MVOLP::FEAS;
+          stop = true;
+          j++;
+          break;
+        }
+        if (status == 1) {
+          node->upperBound = obj;
+          rec.bound[(size_t)node->oid] = node->upperBound;
+          rec.prune[(size_t)node->oid] = MVOLP::INTG;
+          if (!quirks) { // bs.cpp:144-149 leaves without recording the solution; repaired mode keeps it
+            bestLower = node->upperBound;
+            has_incumbent = 1;
+            incumbent_oid = node->oid;
+            for (int i = 1; i <= n0; i++) xbest[(size_t)i] = api->get_col_prim(aw, i);
+          }
+          stop = true;
+          j++;
+          break;
+        }
+      }
+      node->upperBound = obj;
+      rec.bound[(size_t)node->oid] = node->upperBound;
+      if (status == 1) {
+        rec.prune[(size_t)node->oid] = MVOLP::INTG;
+        rec.emit(MVX_EV_INTEGER, node->oid, node->upperBound, 0.0, 0, 0);
+        if (sg * node->upperBound > sg * bestLower) {
+          bestLower = node->upperBound;
+          has_incumbent = 1;
+          incumbent_oid = node->oid;
+          for (int i = 1; i <= n0; i++) xbest[(size_t)i] = api->get_col_prim(aw, i);
+        }
+      } else if (status == -1) {
+        rec.prune[(size_t)node->oid] = MVOLP::FEAS;
+        rec.emit(MVX_EV_INFEASIBLE, node->oid, 0.0, 0.0, 0, 0);
+      } else if (!sp.branch) {
+        rec.prune[(size_t)node->oid] = MVOLP::BNDS;
+        rec.emit(MVX_EV_FATHOMED, node->oid, 0.0, 0.0, 0, 0);
+      } else {
+        double acc = 0;
+        for (size_t k = 0; k < vars.size(); k++)
+          if (vars[k] != 0) acc += getFract(xs[j][k]); // bs.cpp:229-233
+        rec.emit(MVX_EV_BRANCHED, node->oid, node->upperBound, acc, (int)vars.size(), sp.pick);
+        auto S2 = std::make_shared<MVOLP::NodeData>(api, sp.S2, id, true); // even oid (R), then odd (L): bs.cpp:43-52
+        auto S3 = std::make_shared<MVOLP::NodeData>(api, sp.S3, id, true);
+        sp.S2 = sp.S3 = nullptr;
+        rec.node(S2->oid, node->oid);
+        rec.node(S3->oid, node->oid);
+        rec.pivots += (api->get_it_cnt(S2->prob) - sp.before2) + (api->get_it_cnt(S3->prob) - sp.before3);
+        S2->upperBound = api->get_obj_val(S2->prob);
+        S3->upperBound = api->get_obj_val(S3->prob);
+        rec.bound[(size_t)S2->oid] = S2->upperBound;
+        rec.bound[(size_t)S3->oid] = S3->upperBound;
+        push(S2); // bs.cpp:297-298
+        push(S3);
+        rec.emit(MVX_EV_CANDIDATE, S2->oid, S2->upperBound, 0.0, 0, 0);
+        rec.emit(MVX_EV_CANDIDATE, S3->oid, S3->upperBound, 0.0, 0, 0);
+        if (count > prm.loop_limit) { // bs.cpp:320-323
+          hit_limit = 1;
+          count++;
+          stop = true;
+          j++;
+          break;
+        }
+      }
+      count++;
+    }
+    // S[j..] stay open: drop their speculative children and undo their cut steps on the pool
+    bool rolled = false;
+    for (size_t r = j; r < K; r++) {
+      Spec &sp = S[r];
+      if (sp.marked && !rolled) {
+        pool.rollback(sp.mark);
+        rolled = true;
+      }
+      if (sp.S2) api->delete_prob(sp.S2);
+      if (sp.S3) api->delete_prob(sp.S3);
+      sp.S2 = sp.S3 = nullptr;
+    }
+    tReplay += now() - t0;
+  }
+  if (timing)
+    std::fprintf(stderr, "bnb best window timing: %lld rounds, %lld speculated, %d committed: re-solve %.1f ms  classify %.1f ms  speculate %.1f ms  children %.1f ms  replay %.1f ms\n",
+                 rounds, speculated, count, tA * 1e3, tInfo * 1e3, tSpec * 1e3, tKids * 1e3, tReplay * 1e3);
+  open.clear();
+  pack_result(res, rec, id, count, has_incumbent, bestLower, incumbent_oid, n0, xbest, hit_limit);
+  res->rounds = rounds;
+  res->speculated = speculated;
+  return 0;
+}
+
 // ---- the gfx950 engine's table ----
 const mvx_lp_api g_hip_api = {
     []() -> void * { return mvx_create_prob(); },
@@ -1153,6 +1463,10 @@ const mvx_lp_api g_hip_api = {
       return mvx_gmi_cuts_many((const mvx_prob *const *)Ps, repaired, cols, count, vals, rhs, ok);
     },
     [](const void *P, double *x) { mvx_get_col_prim_all((const mvx_prob *)P, x); },
+    // weak: a build of this driver against another engine (tests/tsan) need not define it -- the entry is then NULL
+    mvx_classify_many ? +[](const void *const *Ps, int count, int quirks, int *status, int *nviol, int *viol, double *xviol, int cap) {
+      return mvx_classify_many((const mvx_prob *const *)Ps, count, quirks, status, nviol, viol, xviol, cap);
+    } : nullptr,
 };
 
 } // namespace
@@ -1172,6 +1486,7 @@ void mvx_bnb_default_params(mvx_bnb_params *p) {
   p->lazy_pool = 1;
   p->cut_select = 0;
   p->window = 64;
+  p->best_window = 0;
 }
 
 int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *params, mvx_bnb_result *res) {
@@ -1183,6 +1498,7 @@ int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *
   if (!api) api = &g_hip_api;
   if (api->simplex_batch && params->node_strat == 0 && params->window > 1)
     return branchAndBoundWindow(api, prob, *params, res);
+  if (api->simplex_batch && params->node_strat == 1 && params->best_window > 1) return branchAndBoundBest(api, prob, *params, res);
   return branchAndBound(api, prob, *params, res);
 }
 

@@ -501,6 +501,10 @@ int mvx_gmi_cuts_many(const mvx_prob *const *Ps, int repaired, const int *cols, 
   return mvx::engine_gmi_cuts_many(Ps, repaired ? 1 : 0, cols, count, vals, rhs, ok);
 }
 
+int mvx_classify_many(const mvx_prob *const *Ps, int count, int quirks, int *status, int *nviol, int *viol, double *xviol, int cap) {
+  return mvx::engine_classify_many(Ps, count, quirks ? 1 : 0, status, nviol, viol, xviol, cap);
+}
+
 int mvx_device_count(void) { return mvx::device_count(); }
 int mvx_set_device(int dev) { return mvx::set_device(dev); }
 long long mvx_pack_size(const mvx_prob *P) { return mvx::engine_pack_size(P, P->m); }

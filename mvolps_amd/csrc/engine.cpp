@@ -70,6 +70,7 @@ void launch_p1_fix(Ctl *, int n, hipStream_t);
 void launch_scatter_ctl(Ctl *dst, const Ctl *src, const int *idx, int count, hipStream_t);
 void launch_copy_many(const CopyBatch &b, hipStream_t);
 void launch_gmi(const GmiArgs &a, hipStream_t);
+void launch_classify(const ClsArgs &a, hipStream_t);
 void launch_refresh_select(Ctl *, const int *tflag, int var, hipStream_t);
 size_t persist_lds_bytes(int m, int cpw);
 int persist_max_cpw();
@@ -183,6 +184,12 @@ struct Context {
   // and column kinds, and the pinned host side of the transfers
   void *gmi_dev = nullptr, *gmi_host = nullptr;
   size_t gmi_bytes = 0;
+  // classification (engine_classify_many): device side of the descriptors, objective, kinds and the value scratch; the
+  // pinned host buffer holds the uploaded part and the results, which k_classify writes straight into it when the
+  // buffer has a device address (cls_out_dev), else into the device buffer behind the scratch and one copy brings them
+  void *cls_dev = nullptr, *cls_host = nullptr;
+  unsigned char *cls_out_dev = nullptr;
+  size_t cls_dev_bytes = 0, cls_host_bytes = 0;
   // profiling (main context only)
   bool prof = false;
   double prof_update_ms = 0.0;
@@ -2278,6 +2285,103 @@ int engine_gmi_cuts(const mvx_prob *Pc, int mode, const int *cols, int count, do
 
 int engine_gmi_cuts_many(const mvx_prob *const *Ps, int mode, const int *cols, int count, double *vals, double *rhs, int *ok) {
   return gmi_core(const_cast<mvx_prob *const *>(Ps), mode, cols, count, vals, rhs, ok);
+}
+
+// ------------------------------------------------------------------ classification (printInfo on the device)
+// The B&B drivers classify every node they pop: status, and the integer columns whose value is fractional (util.cpp:414-473).
+// On the host that reads n values out of the handle's mirrors (~15 us a node on 512 x 1024, and an export first when they
+// are stale).  k_classify does it for a whole batch of handles in one launch: the same selection of values the mirrors make
+// (basic value from column 0 of the tableau, bound of a non-basic variable by its status -- no arithmetic, same bits), the
+// same tests, and only the violated columns come back.
+int engine_classify_many(const mvx_prob *const *Ps, int count, int quirks, int *status, int *nviol, int *viol, double *xviol, int cap) {
+  if (count < 1 || !Ps || !status || !nviol || !viol || !xviol || cap < 1) return -1;
+  for (int t = 0; t < count; t++)
+    if (!Ps[t]) return -1;
+  const mvx_prob *P0 = Ps[0];
+  const int n = P0->n;
+  for (int t = 0; t < count; t++) {
+    const mvx_prob *P = Ps[t];
+    if (!P->valid || P->n != n || (P != P0 && (P->c != P0->c || P->kind != P0->kind))) return -1;
+  }
+  Context &c = ctx();
+  MAIN_LOCK(c);
+  flush_copies(c); // a clone recorded into one of these slabs lands first
+  SolveCtx &sc = c.main;
+  size_t off = 0;
+  auto carve = [&](size_t bytes) {
+    size_t o = off;
+    off = align_up(off + bytes, 256);
+    return o;
+  };
+  // up: [descriptors][c][kind]; out: [status][nviol][viol][xviol]; device only: [x scratch]
+  const size_t o_nodes = carve((size_t)count * sizeof(ClsNode)), o_c = carve((size_t)(n + 1) * 8), o_kind = carve((size_t)(n + 1) * 4);
+  const size_t up_bytes = off;
+  const size_t o_st = carve((size_t)count * 4), o_nv = carve((size_t)count * 4), o_viol = carve((size_t)count * cap * 4),
+               o_xv = carve((size_t)count * cap * 8);
+  const size_t host_bytes = off;
+  const size_t o_x = carve((size_t)count * (n + 1) * 8);
+  const size_t dev_bytes = off;
+  if (dev_bytes > c.cls_dev_bytes || host_bytes > c.cls_host_bytes) {
+    HIPCHECK(hipStreamSynchronize(sc.stream));
+    if (c.cls_dev) HIPCHECK(hipFree(c.cls_dev));
+    if (c.cls_host) HIPCHECK(hipHostFree(c.cls_host));
+    c.cls_dev = c.cls_host = nullptr;
+    c.cls_out_dev = nullptr;
+    c.cls_dev_bytes = c.cls_host_bytes = 0;
+    const size_t want_dev = dev_bytes + dev_bytes / 2, want_host = host_bytes + host_bytes / 2;
+    if (hipMalloc(&c.cls_dev, want_dev) != hipSuccess) {
+      (void)hipGetLastError();
+      c.cls_dev = nullptr;
+      g_last_error.store(MVX_ENOMEM);
+      return -2;
+    }
+    if (hipHostMalloc(&c.cls_host, want_host) != hipSuccess) {
+      (void)hipGetLastError();
+      HIPCHECK(hipFree(c.cls_dev));
+      c.cls_dev = c.cls_host = nullptr;
+      g_last_error.store(MVX_ENOMEM);
+      return -2;
+    }
+    void *dp = nullptr;
+    if (hipHostGetDevicePointer(&dp, c.cls_host, 0) == hipSuccess && dp) c.cls_out_dev = (unsigned char *)dp;
+    else (void)hipGetLastError();
+    c.cls_dev_bytes = want_dev;
+    c.cls_host_bytes = want_host;
+  }
+  unsigned char *hb = (unsigned char *)c.cls_host, *db = (unsigned char *)c.cls_dev;
+  ClsNode *h_nodes = (ClsNode *)(hb + o_nodes);
+  for (int t = 0; t < count; t++) {
+    const mvx_prob *P = Ps[t];
+    ClsNode &nd = h_nodes[t];
+    nd.T = P->d_T; nd.bvar = P->d_bvar; nd.nvar = P->d_nvar; nd.nflag = P->d_nflag; nd.nlb = P->d_nlb; nd.nub = P->d_nub;
+    nd.m = P->m; nd.ld = P->ld; nd.status = P->status; nd.pad = 0;
+  }
+  std::memcpy(hb + o_c, P0->c.data(), (size_t)(n + 1) * 8);
+  std::memcpy(hb + o_kind, P0->kind.data(), (size_t)(n + 1) * 4);
+  HIPCHECK(hipMemcpyAsync(db, hb, up_bytes, hipMemcpyHostToDevice, sc.stream));
+  unsigned char *ob = c.cls_out_dev ? c.cls_out_dev : db; // where the results go: the pinned buffer itself, or the device one
+  ClsArgs a;
+  a.nodes = (const ClsNode *)(db + o_nodes);
+  a.c = (const double *)(db + o_c);
+  a.kind = (const int *)(db + o_kind);
+  a.x = (double *)(db + o_x);
+  a.st = (int *)(ob + o_st); a.nv = (int *)(ob + o_nv); a.viol = (int *)(ob + o_viol); a.xv = (double *)(ob + o_xv);
+  a.n = n; a.cap = cap; a.quirks = quirks; a.count = count;
+  launch_classify(a, sc.stream);
+  if (!c.cls_out_dev) HIPCHECK(hipMemcpyAsync(hb + o_st, db + o_st, host_bytes - o_st, hipMemcpyDeviceToHost, sc.stream));
+  HIPCHECK(hipStreamSynchronize(sc.stream));
+  const int *h_st = (const int *)(hb + o_st), *h_nv = (const int *)(hb + o_nv), *h_viol = (const int *)(hb + o_viol);
+  const double *h_xv = (const double *)(hb + o_xv);
+  int rc = 0;
+  for (int t = 0; t < count; t++) {
+    status[t] = h_st[t];
+    nviol[t] = h_nv[t];
+    if (h_nv[t] > cap) rc = -3;
+    const int k = std::min(h_nv[t], cap);
+    std::memcpy(viol + (size_t)t * cap, h_viol + (size_t)t * cap, (size_t)k * 4);
+    std::memcpy(xviol + (size_t)t * cap, h_xv + (size_t)t * cap, (size_t)k * 8);
+  }
+  return rc;
 }
 
 // ------------------------------------------------------------------ pack / unpack (migration)

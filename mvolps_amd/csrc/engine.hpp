@@ -33,6 +33,9 @@ int engine_get_row(const mvx_prob *P, int row, double *out); // out[0..n]
 int engine_gmi_cuts(const mvx_prob *P, int mode, const int *cols, int count, double *vals, double *rhs, int *ok);
 int engine_gmi_cuts_many(const mvx_prob *const *Ps, int mode, const int *cols, int count, double *vals, double *rhs, int *ok);
 
+// printInfo (util.cpp:414-473) of `count` solved handles in one launch (k_classify); see engine.cpp
+int engine_classify_many(const mvx_prob *const *Ps, int count, int quirks, int *status, int *nviol, int *viol, double *xviol, int cap);
+
 long long engine_pack_size(const mvx_prob *P, int m_base);
 int engine_pack(const mvx_prob *P, int m_base, void *dev_buf);
 int engine_unpack(mvx_prob *dst, const void *dev_buf);

@@ -3981,6 +3981,83 @@ void launch_gmi(const GmiArgs &a, hipStream_t s) {
   hipLaunchKernelGGL(k_gmi_backsub, dim3((unsigned)((a.n + 255) / 256), (unsigned)((a.count + GMI_CT - 1) / GMI_CT)), dim3(256), 0, s, a);
 }
 
+// ---------------------------------------------------------------------------- k_classify
+// printInfo (util.cpp:414-473) of a batch of solved handles, one workgroup per handle (mvx_classify_many).  The value of
+// structural column j is what get_col_prim reads out of the host mirrors: column 0 of its tableau row when it is basic,
+// else the bound its status names (dev_nb_value) -- a selection, no arithmetic, so the bits are those of the host.  The
+// tests are printInfo's: bug-compatible, x != 0, c_j != 0 and trunc(x) != x (util.cpp:437,443); repaired, a distance
+// to the nearest integer above 1e-9; integer columns only.  The violated columns are compacted in ascending order: per
+// chunk of 256 columns a ballot in each wave, the waves' counts through LDS, the running base carried across chunks.
+__global__ __launch_bounds__(256) void k_classify(ClsArgs a) {
+  __shared__ int s_cnt[4];
+  const int t = (int)blockIdx.x;
+  const ClsNode nd = a.nodes[t];
+  const int n = a.n, m = nd.m, cap = a.cap;
+  const int st = nd.status;
+  if (st == MVX_NOFEAS || st == MVX_INFEAS || st == MVX_UNBND) { // util.cpp:423-431
+    if (TIDX == 0) {
+      a.st[t] = -1;
+      a.nv[t] = 0;
+    }
+    return;
+  }
+  double *x = a.x + (size_t)t * (size_t)(n + 1);
+  for (int i = 1 + TIDX; i <= m; i += 256) {
+    const int k = nd.bvar[i];
+    if (k > m && k <= m + n) x[k - m] = nd.T[(size_t)i * (size_t)nd.ld];
+  }
+  for (int q = 1 + TIDX; q <= n; q += 256) {
+    const int k = nd.nvar[q];
+    if (k > m && k <= m + n) x[k - m] = dev_nb_value(nd.nflag[q], nd.nlb[q], nd.nub[q]);
+  }
+  __syncthreads();
+  const int lane = TIDX & 63, wv = TIDX >> 6;
+  int *viol = a.viol + (size_t)t * (size_t)cap;
+  double *xv = a.xv + (size_t)t * (size_t)cap;
+  int base = 0;
+  for (int j0 = 1; j0 <= n; j0 += 256) {
+    const int j = j0 + TIDX;
+    bool bad = false;
+    double v = 0.0;
+    if (j <= n) {
+      v = x[j];
+      const double tr = fabs(v) < 4503599627370496.0 ? (double)(long long)v : v; // bnb.cpp printInfo's trunc_of
+      const bool integer = a.kind[j] != MVX_CV;
+      if (a.quirks) {
+        bad = v != 0 && a.c[j] != 0 && tr != v && integer;
+      } else {
+        const double f = fabs(v - tr);
+        bad = (f < 1.0 - f ? f : 1.0 - f) > 1e-9 && integer;
+      }
+    }
+    const unsigned long long mask = __ballot(bad);
+    if (lane == 0) s_cnt[wv] = __popcll(mask);
+    __syncthreads();
+    int off = base, tot = 0;
+    for (int w = 0; w < 4; w++) {
+      if (w < wv) off += s_cnt[w];
+      tot += s_cnt[w];
+    }
+    if (bad) {
+      const int o = off + __popcll(mask & ((1ull << lane) - 1ull));
+      if (o < cap) {
+        viol[o] = j;
+        xv[o] = v;
+      }
+    }
+    base += tot;
+    __syncthreads(); // s_cnt is written again by the next chunk
+  }
+  if (TIDX == 0) {
+    a.nv[t] = base;
+    a.st[t] = base == 0 ? 1 : 0;
+  }
+}
+
+void launch_classify(const ClsArgs &a, hipStream_t s) {
+  hipLaunchKernelGGL(k_classify, dim3((unsigned)a.count), dim3(256), 0, s, a);
+}
+
 // ------------------------------------------------------------------ launch wrappers
 
 // tuning knobs of the streamed update (mvx_set_tuning; defaults are the measured best)

@@ -54,6 +54,7 @@ int main(int argc, char **argv) {
               << "      Percentage of generated cuts to be added per node\n"
               << "  --repaired      children keep the opposite bound, integrality within 1e-9, repaired GMI cuts\n"
               << "  --cut-select K  with --repaired -cm 1: 0 add the last cut, 1 add the -cf fraction of most effective cuts\n"
+              << "  --best-window N with -bs 1: speculate on the top N open nodes per round (same tree; 0 = node at a time)\n"
               << "  --max-nodes N   stop after N loop iterations\n"
               << "Help:\n  -h/--help\n";
     return 0;
@@ -113,6 +114,7 @@ int main(int argc, char **argv) {
   if (input.CMDOptionExists("--repaired")) params.reference_quirks = 0;
   if (input.CMDOptionExists("--cut-select")) params.cut_select = std::atoi(input.getCMDOption("--cut-select").c_str());
   if (input.CMDOptionExists("--window")) params.window = std::atoi(input.getCMDOption("--window").c_str());
+  if (input.CMDOptionExists("--best-window")) params.best_window = std::atoi(input.getCMDOption("--best-window").c_str());
   if (input.CMDOptionExists("--max-nodes")) params.max_nodes = std::atoi(input.getCMDOption("--max-nodes").c_str());
   if (input.CMDOptionExists("--server"))
     std::fprintf(stderr, "--server: the ZeroMQ sink is not part of this build; use --events FILE for the same stream\n");

@@ -222,6 +222,26 @@ struct GmiArgs {
   int n, wld, lda, m0, old, count, mode; // mode 0 bug-compatible (gmi.cpp:41-89), 1 repaired
 };
 
+// one handle of a classification launch (k_classify, mvx_classify_many): where its basis and tableau live
+struct ClsNode {
+  const double *T;
+  const int *bvar, *nvar, *nflag;
+  const double *nlb, *nub;
+  int m, ld, status, pad; // rows of this handle, its row stride, its solve status (MVX_OPT, MVX_NOFEAS, ...)
+};
+
+// arguments of k_classify: `count` handles with the same n columns, objective and column kinds
+struct ClsArgs {
+  const ClsNode *nodes; // [count]
+  const double *c;      // [n+1] objective coefficients (util.cpp:437)
+  const int *kind;      // [n+1] column kinds (MVX_CV / MVX_IV)
+  double *x;            // [count][n+1] scratch: structural values by column
+  int *st, *nv;         // [count] printInfo status (-1 / 0 / 1), violated columns
+  int *viol;            // [count][cap] violated columns, ascending
+  double *xv;           // [count][cap] their values
+  int n, cap, quirks, count;
+};
+
 // shared immutable matrix row (1-based, n+1 doubles)
 using RowPtr = std::shared_ptr<std::vector<double>>;
 
