@@ -165,6 +165,15 @@ int mvx_gmi_cuts_many(const mvx_prob *const *Ps, int repaired, const int *cols, 
    Returns 0; -1 bad arguments (a handle without a solved tableau, different columns or objective); -2 device out of
    memory; -3 some handle has more than `cap` violated columns. */
 int mvx_classify_many(const mvx_prob *const *Ps, int count, int quirks, int *status, int *nviol, int *viol, double *xviol, int cap);
+/* One-step dual penalties (DESIGN.md "Branching on the node LP") of candidate columns of `count` solved handles, one device
+   launch for all of them.  The candidates of handle t are cols[col_off[t] .. col_off[t+1]-1] (1-based columns, each one
+   basic); the results go to the same indices of pen_down / pen_up (+inf: that child is infeasible) and arg_down / arg_up
+   (the non-basic position that attains each side's minimum, the lowest one on ties; 0 when the side is +inf).  A position
+   q counts only where |T[i][q]| > tol; the B&B driver passes the pivot tolerance.  Bit-identical to mvx_bnb_penalties
+   (mvx_bnb.h).  Returns 0; -1 bad arguments or a column outside 1..n; -2 device out of memory; -3 a handle whose status
+   is not MVX_OPT; -4 a column that is not basic. */
+int mvx_branch_penalties_many(const mvx_prob *const *Ps, int count, const int *cols, const int *col_off, double tol, double *pen_down,
+                              double *pen_up, int *arg_down, int *arg_up);
 
 /* ---- engine-state access (parity tests, visualisers) --------------------------- */
 int mvx_get_tableau_ld(const mvx_prob *P);

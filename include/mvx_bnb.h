@@ -71,13 +71,24 @@ typedef struct mvx_lp_api {
      status[t] -1/0/1, nviol[t] violated columns, their indices (ascending) in viol[t*cap ...] and their values in
      xviol[t*cap ...]; non-zero return: the caller classifies on the host */
   int (*classify_many)(const void *const *Ps, int count, int quirks, int *status, int *nviol, int *viol, double *xviol, int cap);
+  /* optional (may be NULL): the solved tableau, (m+1) x (n+1) packed row-major (mvx_get_tableau), and the basis, head[0..m],
+     nb[0..n], flag[0..n] (mvx_get_basis); mvx_bnb_penalties computes the branching penalties of var_strat 3 / 4 from them */
+  int (*get_tableau)(const void *P, double *out);
+  int (*get_basis)(const void *P, int *head, int *nb, int *flag);
+  /* optional (may be NULL): the same penalties for the candidates of `count` solved handles in one call
+     (mvx_branch_penalties_many); the driver prefers it to the host computation */
+  int (*branch_penalties_many)(const void *const *Ps, int count, const int *cols, const int *col_off, double tol, double *pen_down,
+                               double *pen_up, int *arg_down, int *arg_up);
 } mvx_lp_api;
 
 const mvx_lp_api *mvx_hip_lp_api(void);
 
 /* ParameterObj (util.h:61-99); defaults VO / DFS(=FIFO) / no cuts (util.h:65-67) */
 typedef struct {
-  int var_strat;        /* 0 VO, 1 VFP, 2 VGO   (util.h:30) */
+  int var_strat;        /* 0 VO, 1 VFP, 2 VGO   (util.h:30); extensions that read the node LP (DESIGN.md "Branching on
+                           the node LP"): 3 largest product of one-step dual penalties, 4 strong branching on the
+                           sb_cands best of them.  3 / 4 need get_tableau + get_basis or branch_penalties_many in the
+                           table, and are refused (mvx_branchAndBound returns -1) together with best_window > 0 */
   int node_strat;       /* 0 DFS (problems.front(), util.cpp:165), 1 BEST (util.cpp:170-186) */
   int cut_strat;        /* 0 NONE, 1 GMI         (util.h:32) */
   double cut_chance;    /* -cf: stored, never read (util.cpp:259-261) */
@@ -104,6 +115,9 @@ typedef struct {
                            are solved, classified and branched together and their decisions replayed in true
                            best-bound order; the longest prefix the serial loop would also have popped is kept --
                            same tree, oids, events and incumbent as node-at-a-time.  Default 0 = node at a time */
+  int sb_cands;         /* var_strat = 4: candidates (best penalty scores first) whose two children are strong-branched;
+                           default 2 (CPU sweep) */
+  int sb_iters;         /* var_strat = 4: pivot limit of each strong-branching child solve; default 4 */
 } mvx_bnb_params;
 
 /* B&B events at the emit points of bs.cpp (message.h EventType) */
@@ -139,10 +153,15 @@ typedef struct {
   int hit_limit;
   long long rounds;     /* best_window driver only (0 otherwise): rounds of speculation */
   long long speculated; /* best_window driver only (0 otherwise): nodes taken into a round's window, summed */
+  long long sb_lps;     /* var_strat = 4: strong-branching child LPs solved for the nodes that branched */
+  long long sb_pivots;  /* their pivots (not part of total_pivots) */
 } mvx_bnb_result;
 
 void mvx_bnb_default_params(mvx_bnb_params *p);
-/* int branchAndBound(glp_prob*, MVOLP::ParameterObj&)  bs.h:7 */
+/* int branchAndBound(glp_prob*, MVOLP::ParameterObj&)  bs.h:7.  Returns 0; -1 refused parameters (var_strat outside
+   0..4, var_strat >= 3 with best_window > 0) -- *res is then empty; -2 var_strat >= 3 and the branching penalties could
+   not be computed (the table has neither branch_penalties_many nor get_tableau + get_basis, or they failed) -- *res holds
+   the tree up to that node */
 int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *params, mvx_bnb_result *res);
 void mvx_bnb_free_result(mvx_bnb_result *res);
 
@@ -161,11 +180,20 @@ int mvx_generateCutGMI(const mvx_lp_api *api, const void *prob, int j, int *inds
    one per query.  Same arithmetic, same order as the loop body of bs.cpp. ---- */
 /* classification of a solved node (bs.cpp:135-156,227-241,260): out[0] status -1/0/1 (printInfo),
    out[1] objective, out[2] number of violated columns, out[3] sum of their fractional parts,
-   out[4] pickVar's choice (0 when none), `root` = ParameterObj::_prob */
+   out[4] pickVar's choice (0 when none), `root` = ParameterObj::_prob;
+   var_strat 0..2 only: -1 (nothing written) for var_strat >= 3, whose choice needs the node LP's penalties */
 int mvx_bnb_classify(const mvx_lp_api *api, const void *prob, const void *root, int quirks, int var_strat, double *out);
 /* bs.cpp:261-282: bound = col_prim(a, pick); S2/S3 = clones of `a` (created by the caller with
    create_prob) with the branching bounds set; they are NOT solved here (the caller batches them) */
 int mvx_bnb_make_children(const mvx_lp_api *api, const void *a, int pick, int quirks, void *S2, void *S3);
+
+/* Host twin of mvx_branch_penalties_many for one solved handle, from get_tableau and get_basis: for each basic column
+   cols[t], pen_down[t] / pen_up[t] = fd / fu times the smallest |T[0][q]| / |T[i][q]| over the non-basic positions q that
+   move x_j down / up (|T[i][q]| > tol), +inf where none does; arg_down[t] / arg_up[t] the position (lowest on ties, 0 for
+   +inf).  Returns 0; -1 bad arguments or a column outside 1..n; -3 the handle is not MVX_OPT; -4 a column that is not
+   basic; -5 the table has no get_tableau / get_basis or they failed */
+int mvx_bnb_penalties(const mvx_lp_api *api, const void *prob, const int *cols, int count, double tol, double *pen_down, double *pen_up,
+                      int *arg_down, int *arg_up);
 
 /* bs.cpp:249-258 on one solved node `a` that is about to be branched: generate its GMI cut(s) and append the
    row(s) (cut_strat / reference_quirks / lazy_pool / cut_select / cut_chance of `params`).  Returns the number

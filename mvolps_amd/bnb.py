@@ -14,7 +14,8 @@ _FIELDS = [
     "get_col_stat", "get_row_stat", "get_row_ub", "get_row_lb", "get_col_ub", "get_col_lb", "get_col_type", "get_mat_row", "eval_tab_row",
     "get_it_cnt",
 ]
-_OPTIONAL = ["simplex_batch", "get_obj_dir", "gmi_cuts", "gmi_cuts_many", "get_col_prim_all", "classify_many"]
+_OPTIONAL = ["simplex_batch", "get_obj_dir", "gmi_cuts", "gmi_cuts_many", "get_col_prim_all", "classify_many", "get_tableau", "get_basis",
+             "branch_penalties_many"]
 
 
 class LpApiTable(C.Structure):
@@ -36,6 +37,8 @@ class BnbParams(C.Structure):
         ("cut_select", C.c_int),
         ("window", C.c_int),
         ("best_window", C.c_int),
+        ("sb_cands", C.c_int),
+        ("sb_iters", C.c_int),
     ]
 
 
@@ -70,6 +73,8 @@ class BnbResult(C.Structure):
         ("hit_limit", C.c_int),
         ("rounds", C.c_longlong),
         ("speculated", C.c_longlong),
+        ("sb_lps", C.c_longlong),
+        ("sb_pivots", C.c_longlong),
     ]
 
 
@@ -104,6 +109,11 @@ def _bind(lib):
     lib.mvx_classify_many.restype = C.c_int
     lib.mvx_classify_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                       C.POINTER(C.c_double), C.c_int]
+    _DP, _IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    lib.mvx_branch_penalties_many.restype = C.c_int
+    lib.mvx_branch_penalties_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, _IP, _IP, C.c_double, _DP, _DP, _IP, _IP]
+    lib.mvx_bnb_penalties.restype = C.c_int
+    lib.mvx_bnb_penalties.argtypes = [C.c_void_p, C.c_void_p, _IP, C.c_int, C.c_double, _DP, _DP, _IP, _IP]
     lib.mvx_generateCut3.restype = C.c_int
     lib.mvx_generateCut3.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     return lib
@@ -141,12 +151,14 @@ def result_to_dict(res):
         "hit_limit": res.hit_limit,
         "rounds": res.rounds,
         "speculated": res.speculated,
+        "sb_lps": res.sb_lps,
+        "sb_pivots": res.sb_pivots,
     }
 
 
 def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, window=None, cut_select=0, cut_chance=1.0,
-                best_window=None):
-    """mvx_bnb_params with ParameterObj's defaults (util.h:65-67) overridden by the arguments."""
+                best_window=None, sb_cands=None, sb_iters=None):
+    """mvx_bnb_params with ParameterObj's defaults (util.h:65-67) overridden by the arguments (None: the default)."""
     pr = BnbParams()
     lib().mvx_bnb_default_params(C.byref(pr))
     pr.var_strat, pr.node_strat, pr.cut_strat, pr.max_nodes = var_strat, node_strat, cut_strat, max_nodes
@@ -156,19 +168,27 @@ def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, l
         pr.window = window
     if best_window is not None:
         pr.best_window = best_window
+    if sb_cands is not None:
+        pr.sb_cands = sb_cands
+    if sb_iters is not None:
+        pr.sb_iters = sb_iters
     return pr
 
 
 def branch_and_bound(prob, var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, table=None, window=None,
-                     cut_select=0, cut_chance=1.0, best_window=None):
+                     cut_select=0, cut_chance=1.0, best_window=None, sb_cands=None, sb_iters=None):
     """Run the driver on `prob` (a capi.Prob).  table=None uses the gfx950 engine's own table.  best_window > 1 with
-    node_strat=1: the speculative best-bound window (mvx_bnb_params.best_window)."""
+    node_strat=1: the speculative best-bound window (mvx_bnb_params.best_window).  var_strat 3 / 4: branching on the node
+    LP's penalties / strong branching (sb_cands candidates, sb_iters pivots per child).  The dictionary's "rc" is
+    mvx_branchAndBound's return code (-1 refused parameters, -2 penalties unavailable)."""
     L = lib()
-    pr = make_params(var_strat, node_strat, cut_strat, max_nodes, quirks, lazy_pool, window, cut_select, cut_chance, best_window)
+    pr = make_params(var_strat, node_strat, cut_strat, max_nodes, quirks, lazy_pool, window, cut_select, cut_chance, best_window, sb_cands,
+                     sb_iters)
     res = BnbResult()
     tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
-    L.mvx_branchAndBound(tptr, prob.h, C.byref(pr), C.byref(res))
+    rc = L.mvx_branchAndBound(tptr, prob.h, C.byref(pr), C.byref(res))
     out = result_to_dict(res)
+    out["rc"] = rc
     L.mvx_bnb_free_result(C.byref(res))
     return out
 
@@ -245,3 +265,50 @@ def classify_many(probs, quirks=1, cap=None):
         c = int(nv[t])
         out.append((int(st[t]), viol[t * cap: t * cap + c].tolist(), xv[t * cap: t * cap + c].tolist()))
     return rc, out
+
+
+def _flat(probs, cols):
+    import numpy as np
+
+    hs = (C.c_void_p * max(1, len(probs)))(*[p.h for p in probs])
+    off = np.zeros(len(probs) + 1, dtype=np.int32)
+    off[1:] = np.cumsum([len(c) for c in cols])
+    flat = np.array([j for c in cols for j in c] or [0], dtype=np.int32)
+    return hs, off, flat
+
+
+def _pen_out(k):
+    import numpy as np
+
+    k = max(1, k)
+    return np.zeros(k), np.zeros(k), np.zeros(k, dtype=np.int32), np.zeros(k, dtype=np.int32)
+
+
+def _ptrs(pd, pu, ad, au):
+    return (pd.ctypes.data_as(C.POINTER(C.c_double)), pu.ctypes.data_as(C.POINTER(C.c_double)), ad.ctypes.data_as(C.POINTER(C.c_int)),
+            au.ctypes.data_as(C.POINTER(C.c_int)))
+
+
+def branch_penalties_many(probs, cols, tol=1e-9):
+    """mvx_branch_penalties_many over capi.Prob handles of the gfx950 engine; cols[t] lists handle t's candidate columns.
+    Returns (rc, [(pen_down, pen_up, arg_down, arg_up) arrays per handle])."""
+    hs, off, flat = _flat(probs, cols)
+    pd, pu, ad, au = _pen_out(int(off[-1]))
+    rc = lib().mvx_branch_penalties_many(hs, len(probs), flat.ctypes.data_as(C.POINTER(C.c_int)), off.ctypes.data_as(C.POINTER(C.c_int)), tol,
+                                         *_ptrs(pd, pu, ad, au))
+    if rc != 0:
+        return rc, None
+    return rc, [(pd[off[t]:off[t + 1]], pu[off[t]:off[t + 1]], ad[off[t]:off[t + 1]], au[off[t]:off[t + 1]]) for t in range(len(probs))]
+
+
+def penalties(prob, cols, tol=1e-9, table=None):
+    """mvx_bnb_penalties (the host twin, from get_tableau / get_basis of `table`; None = the gfx950 engine's table).
+    Returns (rc, (pen_down, pen_up, arg_down, arg_up))."""
+    import numpy as np
+
+    cs = np.array(list(cols) or [0], dtype=np.int32)
+    pd, pu, ad, au = _pen_out(len(cols))
+    tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
+    rc = lib().mvx_bnb_penalties(tptr, prob.h, cs.ctypes.data_as(C.POINTER(C.c_int)), len(cols), tol, *_ptrs(pd, pu, ad, au))
+    k = len(cols)
+    return rc, (pd[:k], pu[:k], ad[:k], au[:k])

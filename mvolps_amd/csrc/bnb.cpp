@@ -6,6 +6,7 @@
 //   generateCut3           gmi.cpp:11-117     CutPool::addToPool/addCutConstraint    cut.cpp:6-46
 //   branchAndBound         bs.cpp:54-348      getParentOid / getBranchDirection      bs.cpp:26-52
 // Every LP call goes through `mvx_lp_api`; with the default table that is the gfx950 engine.
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
@@ -24,6 +25,11 @@
 
 extern "C" int mvx_classify_many(const mvx_prob *const *Ps, int count, int quirks, int *status, int *nviol, int *viol, double *xviol,
                                  int cap) __attribute__((weak));
+extern "C" int mvx_branch_penalties_many(const mvx_prob *const *Ps, int count, const int *cols, const int *col_off, double tol,
+                                         double *pen_down, double *pen_up, int *arg_down, int *arg_up) __attribute__((weak));
+extern "C" int mvx_get_tableau(const mvx_prob *P, double *out) __attribute__((weak));
+extern "C" int mvx_get_basis(const mvx_prob *P, int *head, int *nb, int *flag) __attribute__((weak));
+extern "C" void mvx_init_smcp(mvx_smcp *parm) __attribute__((weak));
 
 namespace {
 
@@ -624,6 +630,246 @@ static int add_node_cuts(const mvx_lp_api *api, void *a, const mvx_bnb_params &p
   return take;
 }
 
+
+// ---- branching on the node LP (var_strat 3 / 4, DESIGN.md "Branching on the node LP") ----
+
+// The bounds the drivers give the two children of a branching on `pick` at value `bound` (bs.cpp:274,282; repaired mode
+// keeps the opposite bound): S2 the down child, S3 the up child.  mvx_bnb_make_children and strong branching use it.
+static void child_bounds(const mvx_lp_api *api, const void *a, int pick, double bound, bool quirks, void *S2, void *S3) {
+  if (quirks) {
+    api->set_col_bnds(S2, pick, MVX_UP, 0, std::floor(bound)); // bs.cpp:274
+    api->set_col_bnds(S3, pick, MVX_LO, std::ceil(bound), 0);  // bs.cpp:282
+    return;
+  }
+  const int t = api->get_col_type(a, pick);
+  const double l = api->get_col_lb(a, pick), u = api->get_col_ub(a, pick);
+  if (t == MVX_LO || t == MVX_DB || t == MVX_FX)
+    api->set_col_bnds(S2, pick, (l == std::floor(bound)) ? MVX_FX : MVX_DB, l, std::floor(bound));
+  else
+    api->set_col_bnds(S2, pick, MVX_UP, 0, std::floor(bound));
+  if (t == MVX_UP || t == MVX_DB || t == MVX_FX)
+    api->set_col_bnds(S3, pick, (u == std::ceil(bound)) ? MVX_FX : MVX_DB, std::ceil(bound), u);
+  else
+    api->set_col_bnds(S3, pick, MVX_LO, std::ceil(bound), 0);
+}
+
+// One-step dual penalties of basic columns of one solved handle from its exported tableau and basis: the host twin of
+// k_penalty, same tests, same division, same strict minimum over ascending positions -- the same bits.
+static int host_penalties(const mvx_lp_api *api, const void *P, const int *cols, int count, double tol, double *pd, double *pu, int *ad,
+                          int *au) {
+  if (!P || count < 0 || (count > 0 && (!cols || !pd || !pu || !ad || !au))) return -1;
+  const int m = api->get_num_rows(P), n = api->get_num_cols(P);
+  for (int k = 0; k < count; k++)
+    if (cols[k] < 1 || cols[k] > n) return -1;
+  if (api->get_status(P) != MVX_OPT) return -3;
+  if (count == 0) return 0;
+  if (!api->get_tableau || !api->get_basis) return -5;
+  std::vector<double> T((size_t)(m + 1) * (size_t)(n + 1));
+  std::vector<int> head((size_t)m + 1), nb((size_t)n + 1), flag((size_t)n + 1);
+  if (api->get_basis(P, head.data(), nb.data(), flag.data()) != 0 || api->get_tableau(P, T.data()) != 0) return -5;
+  std::vector<int> rowof((size_t)n + 1, 0);
+  for (int i = 1; i <= m; i++)
+    if (head[(size_t)i] > m && head[(size_t)i] <= m + n) rowof[(size_t)(head[(size_t)i] - m)] = i;
+  for (int k = 0; k < count; k++)
+    if (rowof[(size_t)cols[k]] == 0) return -4;
+  const double inf = std::numeric_limits<double>::infinity();
+  const double *r0 = T.data();
+  for (int k = 0; k < count; k++) {
+    const double *ri = &T[(size_t)rowof[(size_t)cols[k]] * (size_t)(n + 1)];
+    double bd = inf, bu = inf;
+    int qd = 0, qu = 0;
+    for (int q = 1; q <= n; q++) {
+      const double e = ri[q];
+      if (!(std::fabs(e) > tol)) continue;
+      const int f = flag[(size_t)q];
+      const bool inc = f == MVX_NL || f == MVX_NF, dec = f == MVX_NU || f == MVX_NF; // allowed directions s = +1 / -1
+      const bool down = (inc && e < 0.0) || (dec && e > 0.0);
+      const bool up = (inc && e > 0.0) || (dec && e < 0.0);
+      if (!down && !up) continue;
+      const double r = std::fabs(r0[q]) / std::fabs(e);
+      if (down && r < bd) {
+        bd = r;
+        qd = q;
+      }
+      if (up && r < bu) {
+        bu = r;
+        qu = q;
+      }
+    }
+    const double v = ri[0];
+    const double fd = v - std::floor(v), fu = std::ceil(v) - v;
+    pd[k] = qd ? fd * bd : inf;
+    pu[k] = qu ? fu * bu : inf;
+    ad[k] = qd;
+    au[k] = qu;
+  }
+  return 0;
+}
+
+// pivot tolerance of the engine's default solve (mvx_init_smcp), passed to the penalty tests; an smcp with the defaults
+static mvx_smcp default_smcp() {
+  mvx_smcp p;
+  p.msg_lev = 0;
+  p.meth = 1;
+  p.it_lim = -1;
+  p.tol_bnd = p.tol_dj = p.tol_piv = 1e-9; // the engine's defaults (mvx.h)
+  if (mvx_init_smcp) mvx_init_smcp(&p);
+  return p;
+}
+
+inline double pen_score(double d, double u) { return std::max(d, 1e-6) * std::max(u, 1e-6); }
+
+// What var_strat 3 / 4 decide for one branching node, and the strong-branching work it took (booked only if it branches).
+struct Choice {
+  int pick = 0;
+  long long sb_lps = 0, sb_pivots = 0;
+};
+
+// Penalties of the basic candidates of several solved nodes: one branch_penalties_many call when the table has it, else
+// the host twin per node.  Columns that are not basic (a fractional value at a fractional bound) keep 0 / 0.
+static int penalties_of(const mvx_lp_api *api, const std::vector<const void *> &hs, const std::vector<std::vector<int>> &cands, double tol,
+                        std::vector<std::vector<double>> &pd, std::vector<std::vector<double>> &pu) {
+  const size_t K = hs.size();
+  pd.assign(K, {});
+  pu.assign(K, {});
+  std::vector<const void *> ps;
+  std::vector<int> cols, off(1, 0);
+  std::vector<std::vector<size_t>> where(K);
+  for (size_t t = 0; t < K; t++) {
+    pd[t].assign(cands[t].size(), 0.0);
+    pu[t].assign(cands[t].size(), 0.0);
+    for (size_t k = 0; k < cands[t].size(); k++)
+      if (api->get_col_stat(hs[t], cands[t][k]) == MVX_BS) {
+        cols.push_back(cands[t][k]);
+        where[t].push_back(k);
+      }
+    if (where[t].empty()) continue;
+    ps.push_back(hs[t]);
+    off.push_back((int)cols.size());
+  }
+  if (cols.empty()) return 0;
+  std::vector<double> d(cols.size()), u(cols.size());
+  std::vector<int> ad(cols.size()), au(cols.size());
+  if (api->branch_penalties_many) {
+    const int rc = api->branch_penalties_many(ps.data(), (int)ps.size(), cols.data(), off.data(), tol, d.data(), u.data(), ad.data(), au.data());
+    if (rc != 0) return rc;
+  } else {
+    for (size_t p = 0; p < ps.size(); p++) {
+      const int rc = host_penalties(api, ps[p], cols.data() + off[p], off[p + 1] - off[p], tol, d.data() + off[p], u.data() + off[p],
+                                    ad.data() + off[p], au.data() + off[p]);
+      if (rc != 0) return rc;
+    }
+  }
+  size_t g = 0;
+  for (size_t t = 0; t < K; t++)
+    for (size_t k : where[t]) {
+      pd[t][k] = d[g];
+      pu[t][k] = u[g];
+      g++;
+    }
+  return 0;
+}
+
+// Bytes of child tableaux one strong-branching batch may hold (MVX_SB_BUDGET_MB overrides; results do not depend on it).
+static size_t sb_budget() {
+  size_t mb = 4096;
+  if (const char *e = std::getenv("MVX_SB_BUDGET_MB")) mb = (size_t)std::max(0, std::atoi(e));
+  return mb << 20;
+}
+
+// var_strat 3 / 4 for a set of branching nodes: hs[t] solved (OPT), vars[t] its printInfo violated list (ascending).
+// 3: the argmax of max(pen_down, 1e-6) * max(pen_up, 1e-6), ties to the lowest column.  4: the sb_cands best candidates by
+// that score (same tie rule) are branched on clones with the drivers' own bounds, all their children solved by batched
+// solves of at most sb_iters pivots each; each side's degradation is max(penalty, objective drop in the LP's own sense)
+// (+inf for a NOFEAS child), scored by the same product.  The pick depends on each node's own LP only.
+static int choose_many(const mvx_lp_api *api, const std::vector<const void *> &hs, const std::vector<std::vector<int>> &vars,
+                       const mvx_bnb_params &prm, std::vector<Choice> &out) {
+  const size_t K = hs.size();
+  out.assign(K, Choice());
+  if (K == 0) return 0;
+  const mvx_smcp dflt = default_smcp();
+  std::vector<std::vector<double>> pd, pu;
+  const int rc = penalties_of(api, hs, vars, dflt.tol_piv, pd, pu);
+  if (rc != 0) return rc;
+  const bool quirks = prm.reference_quirks != 0;
+  // candidates of each node in score order (descending, ties to the lower column: vars is ascending and the sort stable)
+  std::vector<std::vector<size_t>> order(K);
+  for (size_t t = 0; t < K; t++) {
+    std::vector<size_t> &o = order[t];
+    for (size_t k = 0; k < vars[t].size(); k++) o.push_back(k);
+    std::stable_sort(o.begin(), o.end(), [&](size_t x, size_t y) { return pen_score(pd[t][x], pu[t][x]) > pen_score(pd[t][y], pu[t][y]); });
+    if (!o.empty()) out[t].pick = vars[t][o.front()];
+  }
+  if (prm.var_strat != 4 || prm.sb_cands <= 0) return 0;
+  // strong branching: children of the top candidates, solved in batches that fit the memory budget
+  struct Job {
+    size_t t, k;
+    void *S2, *S3;
+    int before2, before3;
+  };
+  std::vector<Job> jobs;
+  for (size_t t = 0; t < K; t++)
+    for (size_t r = 0; r < order[t].size() && (int)r < prm.sb_cands; r++) jobs.push_back(Job{t, order[t][r], nullptr, nullptr, 0, 0});
+  std::vector<double> dd(jobs.size()), du(jobs.size());
+  mvx_smcp parm = dflt;
+  parm.it_lim = std::max(0, prm.sb_iters);
+  size_t per = jobs.size();
+  if (!jobs.empty()) {
+    const size_t tab = (size_t)(api->get_num_rows(hs[0]) + 1) * (size_t)(api->get_num_cols(hs[0]) + 1) * 8;
+    per = std::max<size_t>(1, std::min(jobs.size(), sb_budget() / (2 * tab + 1)));
+  }
+  for (size_t j0 = 0; j0 < jobs.size(); j0 += per) {
+    const size_t j1 = std::min(jobs.size(), j0 + per);
+    std::vector<void *> kids;
+    for (size_t j = j0; j < j1; j++) {
+      Job &jb = jobs[j];
+      const void *a = hs[jb.t];
+      const int col = vars[jb.t][jb.k];
+      jb.S2 = api->create_prob();
+      jb.S3 = api->create_prob();
+      api->copy_prob(jb.S2, a, MVX_ON);
+      api->copy_prob(jb.S3, a, MVX_ON);
+      child_bounds(api, a, col, api->get_col_prim(a, col), quirks, jb.S2, jb.S3);
+      jb.before2 = api->get_it_cnt(jb.S2);
+      jb.before3 = api->get_it_cnt(jb.S3);
+      kids.push_back(jb.S2);
+      kids.push_back(jb.S3);
+    }
+    if (api->simplex_batch) api->simplex_batch(kids.data(), (int)kids.size(), &parm, nullptr);
+    else
+      for (void *k : kids) api->simplex(k, &parm);
+    for (size_t j = j0; j < j1; j++) {
+      Job &jb = jobs[j];
+      const void *a = hs[jb.t];
+      const double lpsg = (api->get_obj_dir && api->get_obj_dir(a) == MVX_MIN) ? -1.0 : 1.0;
+      const double z = api->get_obj_val(a);
+      auto delta = [&](void *S, double pen) {
+        if (api->get_status(S) == MVX_NOFEAS) return std::numeric_limits<double>::infinity();
+        return std::max(pen, lpsg * (z - api->get_obj_val(S)));
+      };
+      dd[j] = delta(jb.S2, pd[jb.t][jb.k]);
+      du[j] = delta(jb.S3, pu[jb.t][jb.k]);
+      Choice &ch = out[jb.t];
+      ch.sb_lps += 2;
+      ch.sb_pivots += (api->get_it_cnt(jb.S2) - jb.before2) + (api->get_it_cnt(jb.S3) - jb.before3);
+      api->delete_prob(jb.S2);
+      api->delete_prob(jb.S3);
+    }
+  }
+  // best strong-branching score per node; ties to the lowest column
+  std::vector<double> best(K, -1.0);
+  for (size_t j = 0; j < jobs.size(); j++) {
+    const Job &jb = jobs[j];
+    const double sc = pen_score(dd[j], du[j]);
+    const int col = vars[jb.t][jb.k];
+    if (best[jb.t] < 0.0 || sc > best[jb.t] || (sc == best[jb.t] && col < out[jb.t].pick)) {
+      best[jb.t] = sc;
+      out[jb.t].pick = col;
+    }
+  }
+  return 0;
+}
+
 int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm, mvx_bnb_result *res) { // bs.cpp:54
   MVOLP::ParameterObj params(api, prob, prm);
   CutPool pool(api);
@@ -644,6 +890,8 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm,
   std::vector<double> xbest((size_t)n0 + 1, 0.0);
   int incumbent_oid = 0, has_incumbent = 0, hit_limit = 0;
   int count = 0;
+  int rc_out = 0;
+  long long sb_lps = 0, sb_pivots = 0;
 
   while (!leafContainer.empty()) { // bs.cpp:96
     if (prm.max_nodes > 0 && count >= prm.max_nodes) {
@@ -707,9 +955,26 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm,
         if (i != 0) acc += getFract(api->get_col_prim(a, i)); // bs.cpp:229-233
       leafContainer.erase(leafContainer.begin() + index);       // bs.cpp:247
 
+      // var_strat 3 / 4 read the node's LP: they choose on it as solved, in front of the cut step
+      int pick = 0;
+      double bound = 0.0;
+      if (prm.var_strat >= 3) {
+        std::vector<Choice> ch;
+        const int prc = choose_many(api, {a}, {vars}, prm, ch);
+        if (prc != 0) {
+          rc_out = -2;
+          break;
+        }
+        pick = ch[0].pick;
+        bound = api->get_col_prim(a, pick);
+        sb_lps += ch[0].sb_lps;
+        sb_pivots += ch[0].sb_pivots;
+      }
       add_node_cuts(api, a, prm, quirks, pool); // bs.cpp:249-258
-      const int pick = params.pickVar(vars);         // bs.cpp:260
-      const double bound = api->get_col_prim(a, pick); // bs.cpp:261
+      if (prm.var_strat < 3) {
+        pick = params.pickVar(vars);         // bs.cpp:260
+        bound = api->get_col_prim(a, pick); // bs.cpp:261
+      }
       rec.emit(MVX_EV_BRANCHED, node->oid, node->upperBound, acc, (int)vars.size(), pick);
 
       auto S2 = std::make_shared<MVOLP::NodeData>(api, a, id); // bs.cpp:269-273
@@ -767,7 +1032,9 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm,
   leafContainer.clear();
   api->delete_prob(a);
   pack_result(res, rec, id, count, has_incumbent, bestLower, incumbent_oid, n0, xbest, hit_limit);
-  return 0;
+  res->sb_lps = sb_lps;
+  res->sb_pivots = sb_pivots;
+  return rc_out;
 }
 
 // Window mode: the front W nodes of the FIFO deque are solved together (one batched launch carries
@@ -789,7 +1056,8 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
   double bestLower = -sg * std::numeric_limits<double>::infinity();
   const int n0 = api->get_num_cols(prob);
   std::vector<double> xbest((size_t)n0 + 1, 0.0);
-  int incumbent_oid = 0, has_incumbent = 0, hit_limit = 0, count = 0;
+  int incumbent_oid = 0, has_incumbent = 0, hit_limit = 0, count = 0, rc_out = 0;
+  long long sb_lps = 0, sb_pivots = 0;
   bool stop = false;
 
   struct Branch {
@@ -931,6 +1199,32 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
       tB_cuts += now() - ti;
       tB_rcuts += now() - ti;
     }
+    // var_strat 3 / 4: the choice of every node of the window that may branch, in one penalty call (and one strong-branching
+    // batch).  It depends on the node's own LP only, so the replay takes the serial loop's picks; a node the replay then
+    // prunes by bound has only cost work, and its strong-branching counts are not booked.
+    std::vector<Choice> choice;
+    if (prm.var_strat >= 3) {
+      if (info.empty()) {
+        info.resize(W);
+        for (size_t w = 0; w < W; w++) info[w] = printInfo(api, a[w], quirks);
+      }
+      std::vector<const void *> bh;
+      std::vector<std::vector<int>> bv;
+      std::vector<size_t> slot;
+      for (size_t w = 0; w < W; w++)
+        if (info[w].first == 0) {
+          bh.push_back(a[w]);
+          bv.push_back(info[w].second);
+          slot.push_back(w);
+        }
+      std::vector<Choice> got;
+      if (choose_many(api, bh, bv, prm, got) != 0) {
+        rc_out = -2;
+        break;
+      }
+      choice.assign(W, Choice());
+      for (size_t k = 0; k < slot.size(); k++) choice[slot[k]] = got[k];
+    }
     // B. replay in queue order
     Round cur;
     cur.node_events.resize(W);
@@ -1000,8 +1294,12 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
         // pick looks at the violated list and the root problem only, and appending a row leaves every other row's value
         // as it is -- but it marks the handle's solution mirrors stale, and reading one value afterwards is a device
         // export and a host round trip per branching node (~40 us, a tenth of the cut modes' run)
-        const int pick = params.pickVar(vars);
+        const int pick = prm.var_strat >= 3 ? choice[w].pick : params.pickVar(vars);
         const double bound = api->get_col_prim(aw, pick);
+        if (prm.var_strat >= 3) {
+          sb_lps += choice[w].sb_lps;
+          sb_pivots += choice[w].sb_pivots;
+        }
         ti = now();
         add_node_cuts(api, aw, prm, quirks, pool, pre.empty() ? nullptr : pre[w].get());
         tB_cuts += now() - ti;
@@ -1130,7 +1428,9 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
                  tB * 1e3, tB_info * 1e3, tB_clone * 1e3, tB_cuts * 1e3, tB_rcuts * 1e3, tWait * 1e3);
   leafContainer.clear();
   pack_result(res, rec, id, count, has_incumbent, bestLower, incumbent_oid, n0, xbest, hit_limit);
-  return 0;
+  res->sb_lps = sb_lps;
+  res->sb_pivots = sb_pivots;
+  return rc_out;
 }
 
 // printInfo of a round's nodes: one mvx_lp_api.classify_many call when the engine has it (one device launch for all of
@@ -1467,6 +1767,12 @@ const mvx_lp_api g_hip_api = {
     mvx_classify_many ? +[](const void *const *Ps, int count, int quirks, int *status, int *nviol, int *viol, double *xviol, int cap) {
       return mvx_classify_many((const mvx_prob *const *)Ps, count, quirks, status, nviol, viol, xviol, cap);
     } : nullptr,
+    mvx_get_tableau ? +[](const void *P, double *out) { return mvx_get_tableau((const mvx_prob *)P, out); } : nullptr,
+    mvx_get_basis ? +[](const void *P, int *head, int *nb, int *flag) { return mvx_get_basis((const mvx_prob *)P, head, nb, flag); } : nullptr,
+    mvx_branch_penalties_many ? +[](const void *const *Ps, int count, const int *cols, const int *col_off, double tol, double *pd, double *pu,
+                                    int *ad, int *au) {
+      return mvx_branch_penalties_many((const mvx_prob *const *)Ps, count, cols, col_off, tol, pd, pu, ad, au);
+    } : nullptr,
 };
 
 } // namespace
@@ -1487,6 +1793,8 @@ void mvx_bnb_default_params(mvx_bnb_params *p) {
   p->cut_select = 0;
   p->window = 64;
   p->best_window = 0;
+  p->sb_cands = 2;
+  p->sb_iters = 4;
 }
 
 int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *params, mvx_bnb_result *res) {
@@ -1496,6 +1804,11 @@ int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *
     params = &dflt;
   }
   if (!api) api = &g_hip_api;
+  // var_strat 3 / 4 are not (yet) in the speculative best-bound window: refused, not run with another rule
+  if (params->var_strat < 0 || params->var_strat > 4 || (params->var_strat >= 3 && params->best_window > 0)) {
+    std::memset(res, 0, sizeof(*res));
+    return -1;
+  }
   if (api->simplex_batch && params->node_strat == 0 && params->window > 1)
     return branchAndBoundWindow(api, prob, *params, res);
   if (api->simplex_batch && params->node_strat == 1 && params->best_window > 1) return branchAndBoundBest(api, prob, *params, res);
@@ -1525,6 +1838,7 @@ int mvx_generateCutGMI(const mvx_lp_api *api, const void *prob, int j, int *inds
 }
 
 int mvx_bnb_classify(const mvx_lp_api *api, const void *prob, const void *root, int quirks, int var_strat, double *out) {
+  if (var_strat >= 3) return -1; // the node-LP rules need the penalties of the node's candidates (mvx_bnb_penalties)
   if (!api) api = &g_hip_api;
   auto ret = printInfo(api, prob, quirks != 0);
   mvx_bnb_params p;
@@ -1547,22 +1861,13 @@ int mvx_bnb_make_children(const mvx_lp_api *api, const void *a, int pick, int qu
   const double bound = api->get_col_prim(a, pick); // bs.cpp:261
   api->copy_prob(S2, a, MVX_ON);                   // NodeData(a), util.cpp:33-34
   api->copy_prob(S3, a, MVX_ON);
-  if (quirks) {
-    api->set_col_bnds(S2, pick, MVX_UP, 0, std::floor(bound)); // bs.cpp:274
-    api->set_col_bnds(S3, pick, MVX_LO, std::ceil(bound), 0);  // bs.cpp:282
-  } else {
-    const int t = api->get_col_type(a, pick);
-    const double l = api->get_col_lb(a, pick), u = api->get_col_ub(a, pick);
-    if (t == MVX_LO || t == MVX_DB || t == MVX_FX)
-      api->set_col_bnds(S2, pick, (l == std::floor(bound)) ? MVX_FX : MVX_DB, l, std::floor(bound));
-    else
-      api->set_col_bnds(S2, pick, MVX_UP, 0, std::floor(bound));
-    if (t == MVX_UP || t == MVX_DB || t == MVX_FX)
-      api->set_col_bnds(S3, pick, (u == std::ceil(bound)) ? MVX_FX : MVX_DB, std::ceil(bound), u);
-    else
-      api->set_col_bnds(S3, pick, MVX_LO, std::ceil(bound), 0);
-  }
+  child_bounds(api, a, pick, bound, quirks != 0, S2, S3);
   return 0;
+}
+
+int mvx_bnb_penalties(const mvx_lp_api *api, const void *prob, const int *cols, int count, double tol, double *pen_down, double *pen_up,
+                      int *arg_down, int *arg_up) {
+  return host_penalties(api ? api : &g_hip_api, prob, cols, count, tol, pen_down, pen_up, arg_down, arg_up);
 }
 
 int mvx_bnb_node_cuts(const mvx_lp_api *api, void *a, const mvx_bnb_params *params) {

@@ -504,6 +504,10 @@ int mvx_gmi_cuts_many(const mvx_prob *const *Ps, int repaired, const int *cols, 
 int mvx_classify_many(const mvx_prob *const *Ps, int count, int quirks, int *status, int *nviol, int *viol, double *xviol, int cap) {
   return mvx::engine_classify_many(Ps, count, quirks ? 1 : 0, status, nviol, viol, xviol, cap);
 }
+int mvx_branch_penalties_many(const mvx_prob *const *Ps, int count, const int *cols, const int *col_off, double tol, double *pen_down,
+                              double *pen_up, int *arg_down, int *arg_up) {
+  return mvx::engine_penalties_many(Ps, count, cols, col_off, tol, pen_down, pen_up, arg_down, arg_up);
+}
 
 int mvx_device_count(void) { return mvx::device_count(); }
 int mvx_set_device(int dev) { return mvx::set_device(dev); }

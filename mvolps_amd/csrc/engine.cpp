@@ -71,6 +71,7 @@ void launch_scatter_ctl(Ctl *dst, const Ctl *src, const int *idx, int count, hip
 void launch_copy_many(const CopyBatch &b, hipStream_t);
 void launch_gmi(const GmiArgs &a, hipStream_t);
 void launch_classify(const ClsArgs &a, hipStream_t);
+void launch_penalty(const PenArgs &a, hipStream_t);
 void launch_refresh_select(Ctl *, const int *tflag, int var, hipStream_t);
 size_t persist_lds_bytes(int m, int cpw);
 int persist_max_cpw();
@@ -190,6 +191,11 @@ struct Context {
   void *cls_dev = nullptr, *cls_host = nullptr;
   unsigned char *cls_out_dev = nullptr;
   size_t cls_dev_bytes = 0, cls_host_bytes = 0;
+  // branching penalties (engine_penalties_many): device copy of the descriptors, pinned host side of the upload and the
+  // results (k_penalty writes them straight into it when it has a device address, pen_out_dev)
+  void *pen_dev = nullptr, *pen_host = nullptr;
+  unsigned char *pen_out_dev = nullptr;
+  size_t pen_dev_bytes = 0, pen_host_bytes = 0;
   // profiling (main context only)
   bool prof = false;
   double prof_update_ms = 0.0;
@@ -2382,6 +2388,97 @@ int engine_classify_many(const mvx_prob *const *Ps, int count, int quirks, int *
     std::memcpy(xviol + (size_t)t * cap, h_xv + (size_t)t * cap, (size_t)k * 8);
   }
   return rc;
+}
+
+// ------------------------------------------------------------------ branching penalties (k_penalty)
+// One-step dual penalties of the candidate columns of a batch of solved handles (mvx_branch_penalties_many): the host finds
+// each candidate's tableau row in the handle's basis mirror, one launch evaluates every (handle, candidate) pair on the
+// tableaux where they lie.  Return codes: 0; -1 bad arguments or a column outside 1..n; -2 device out of memory; -3 a
+// handle whose status is not MVX_OPT (or that has no tableau); -4 a column that is not basic.
+int engine_penalties_many(const mvx_prob *const *Ps, int count, const int *cols, const int *col_off, double tol, double *pen_down,
+                          double *pen_up, int *arg_down, int *arg_up) {
+  if (count < 1 || !Ps || !cols || !col_off || !pen_down || !pen_up || !arg_down || !arg_up || col_off[0] < 0) return -1;
+  for (int t = 0; t < count; t++)
+    if (!Ps[t] || col_off[t + 1] < col_off[t]) return -1;
+  const int k0 = col_off[0], total = col_off[count] - k0;
+  for (int t = 0; t < count; t++) {
+    const mvx_prob *P = Ps[t];
+    for (int k = col_off[t]; k < col_off[t + 1]; k++)
+      if (cols[k] < 1 || cols[k] > P->n) return -1;
+    if (!P->valid || P->status != MVX_OPT) return -3;
+    for (int k = col_off[t]; k < col_off[t + 1]; k++) {
+      const int row = P->pos[(size_t)(P->m + cols[k])];
+      if (row < 1 || row > P->m || P->bvar[(size_t)row] != P->m + cols[k]) return -4;
+    }
+  }
+  if (total == 0) return 0;
+  Context &c = ctx();
+  MAIN_LOCK(c);
+  flush_copies(c); // a clone recorded into one of these slabs lands first
+  SolveCtx &sc = c.main;
+  size_t off = 0;
+  auto carve = [&](size_t bytes) {
+    size_t o = off;
+    off = align_up(off + bytes, 256);
+    return o;
+  };
+  // up: [descriptors]; out: [pen_down][pen_up][arg_down][arg_up]
+  const size_t o_nodes = carve((size_t)total * sizeof(PenNode));
+  const size_t up_bytes = off;
+  const size_t o_pd = carve((size_t)total * 8), o_pu = carve((size_t)total * 8), o_ad = carve((size_t)total * 4),
+               o_au = carve((size_t)total * 4);
+  const size_t host_bytes = off, dev_bytes = off;
+  if (dev_bytes > c.pen_dev_bytes || host_bytes > c.pen_host_bytes) {
+    HIPCHECK(hipStreamSynchronize(sc.stream));
+    if (c.pen_dev) HIPCHECK(hipFree(c.pen_dev));
+    if (c.pen_host) HIPCHECK(hipHostFree(c.pen_host));
+    c.pen_dev = c.pen_host = nullptr;
+    c.pen_out_dev = nullptr;
+    c.pen_dev_bytes = c.pen_host_bytes = 0;
+    const size_t want = dev_bytes + dev_bytes / 2;
+    if (hipMalloc(&c.pen_dev, want) != hipSuccess) {
+      (void)hipGetLastError();
+      c.pen_dev = nullptr;
+      g_last_error.store(MVX_ENOMEM);
+      return -2;
+    }
+    if (hipHostMalloc(&c.pen_host, want) != hipSuccess) {
+      (void)hipGetLastError();
+      HIPCHECK(hipFree(c.pen_dev));
+      c.pen_dev = c.pen_host = nullptr;
+      g_last_error.store(MVX_ENOMEM);
+      return -2;
+    }
+    void *dp = nullptr;
+    if (hipHostGetDevicePointer(&dp, c.pen_host, 0) == hipSuccess && dp) c.pen_out_dev = (unsigned char *)dp;
+    else (void)hipGetLastError();
+    c.pen_dev_bytes = c.pen_host_bytes = want;
+  }
+  unsigned char *hb = (unsigned char *)c.pen_host, *db = (unsigned char *)c.pen_dev;
+  PenNode *h_nodes = (PenNode *)(hb + o_nodes);
+  for (int t = 0; t < count; t++) {
+    const mvx_prob *P = Ps[t];
+    for (int k = col_off[t]; k < col_off[t + 1]; k++) {
+      PenNode &nd = h_nodes[k - k0];
+      nd.T = P->d_T; nd.nflag = P->d_nflag;
+      nd.m = P->m; nd.ld = P->ld; nd.row = P->pos[(size_t)(P->m + cols[k])]; nd.n = P->n;
+    }
+  }
+  HIPCHECK(hipMemcpyAsync(db, hb, up_bytes, hipMemcpyHostToDevice, sc.stream));
+  unsigned char *ob = c.pen_out_dev ? c.pen_out_dev : db;
+  PenArgs a;
+  a.nodes = (const PenNode *)(db + o_nodes);
+  a.pen_down = (double *)(ob + o_pd); a.pen_up = (double *)(ob + o_pu);
+  a.arg_down = (int *)(ob + o_ad); a.arg_up = (int *)(ob + o_au);
+  a.tol = tol; a.count = total; a.pad = 0;
+  launch_penalty(a, sc.stream);
+  if (!c.pen_out_dev) HIPCHECK(hipMemcpyAsync(hb + o_pd, db + o_pd, host_bytes - o_pd, hipMemcpyDeviceToHost, sc.stream));
+  HIPCHECK(hipStreamSynchronize(sc.stream));
+  std::memcpy(pen_down + k0, hb + o_pd, (size_t)total * 8);
+  std::memcpy(pen_up + k0, hb + o_pu, (size_t)total * 8);
+  std::memcpy(arg_down + k0, hb + o_ad, (size_t)total * 4);
+  std::memcpy(arg_up + k0, hb + o_au, (size_t)total * 4);
+  return 0;
 }
 
 // ------------------------------------------------------------------ pack / unpack (migration)

@@ -35,6 +35,9 @@ int engine_gmi_cuts_many(const mvx_prob *const *Ps, int mode, const int *cols, i
 
 // printInfo (util.cpp:414-473) of `count` solved handles in one launch (k_classify); see engine.cpp
 int engine_classify_many(const mvx_prob *const *Ps, int count, int quirks, int *status, int *nviol, int *viol, double *xviol, int cap);
+// one-step dual penalties of the candidate columns of `count` solved handles in one launch (k_penalty); see engine.cpp
+int engine_penalties_many(const mvx_prob *const *Ps, int count, const int *cols, const int *col_off, double tol, double *pen_down,
+                          double *pen_up, int *arg_down, int *arg_up);
 
 long long engine_pack_size(const mvx_prob *P, int m_base);
 int engine_pack(const mvx_prob *P, int m_base, void *dev_buf);

@@ -4058,6 +4058,81 @@ void launch_classify(const ClsArgs &a, hipStream_t s) {
   hipLaunchKernelGGL(k_classify, dim3((unsigned)a.count), dim3(256), 0, s, a);
 }
 
+// ---------------------------------------------------------------------------- k_penalty
+// One-step dual penalties of a basic integer column (mvx_branch_penalties_many, DESIGN.md "Branching on the node LP"),
+// one workgroup per (handle, candidate).  Row 0 (reduced costs) and the candidate's row i are streamed once, coalesced;
+// position q is down-eligible when its variable may move in a direction s that lowers x_j (s * T[i][q] < 0), up-eligible
+// when one raises it, and |T[i][q]| > tol; r_q = |T[0][q]| / |T[i][q]| (a true division, xdiv).  Each thread keeps the running
+// (r, q) minimum of each side over its strided positions -- q ascending, strict compare, so the lowest q wins a tie -- the
+// waves reduce with shuffles, four partials meet in LDS.  min is exact: the result has the host twin's bits.
+struct PenMin {
+  double r;
+  int q;
+};
+__device__ __forceinline__ PenMin pen_min(PenMin a, PenMin b) { // smaller r; equal r: smaller q (q = INT_MAX: none)
+  return (b.r < a.r || (b.r == a.r && b.q < a.q)) ? b : a;
+}
+__device__ __forceinline__ PenMin pen_wave_min(PenMin v) {
+  for (int off = 32; off > 0; off >>= 1) {
+    PenMin o;
+    o.r = __shfl_xor(v.r, off, 64);
+    o.q = __shfl_xor(v.q, off, 64);
+    v = pen_min(v, o);
+  }
+  return v;
+}
+
+__global__ __launch_bounds__(256) void k_penalty(PenArgs a) {
+  __shared__ double s_r[2][4];
+  __shared__ int s_q[2][4];
+  const int t = (int)blockIdx.x;
+  const PenNode nd = a.nodes[t];
+  const double *r0 = nd.T;
+  const double *ri = nd.T + (size_t)nd.row * (size_t)nd.ld;
+  const double tol = a.tol;
+  const double inf = __builtin_huge_val();
+  PenMin dn = {inf, 0x7fffffff}, up = {inf, 0x7fffffff};
+  for (int q = 1 + TIDX; q <= nd.n; q += 256) {
+    const double e = ri[q];
+    const double d = r0[q];
+    const int f = nd.nflag[q];
+    if (!(fabs(e) > tol)) continue;
+    const bool inc = f == MVX_NL || f == MVX_NF, dec = f == MVX_NU || f == MVX_NF; // allowed directions s = +1 / -1
+    const bool down = (inc && e < 0.0) || (dec && e > 0.0);
+    const bool upw = (inc && e > 0.0) || (dec && e < 0.0);
+    if (!down && !upw) continue;
+    const double r = xdiv(fabs(d), fabs(e)); // the correctly rounded quotient: the host's division
+    if (down && r < dn.r) dn = PenMin{r, q};
+    if (upw && r < up.r) up = PenMin{r, q};
+  }
+  dn = pen_wave_min(dn);
+  up = pen_wave_min(up);
+  const int lane = TIDX & 63, wv = TIDX >> 6;
+  if (lane == 0) {
+    s_r[0][wv] = dn.r; s_q[0][wv] = dn.q;
+    s_r[1][wv] = up.r; s_q[1][wv] = up.q;
+  }
+  __syncthreads();
+  if (TIDX == 0) {
+    PenMin bd = {s_r[0][0], s_q[0][0]}, bu = {s_r[1][0], s_q[1][0]};
+    for (int w = 1; w < 4; w++) {
+      bd = pen_min(bd, PenMin{s_r[0][w], s_q[0][w]});
+      bu = pen_min(bu, PenMin{s_r[1][w], s_q[1][w]});
+    }
+    const double v = ri[0];
+    const double fd = v - floor(v), fu = ceil(v) - v;
+    const bool hd = bd.q != 0x7fffffff, hu = bu.q != 0x7fffffff;
+    a.pen_down[t] = hd ? fd * bd.r : inf;
+    a.pen_up[t] = hu ? fu * bu.r : inf;
+    a.arg_down[t] = hd ? bd.q : 0;
+    a.arg_up[t] = hu ? bu.q : 0;
+  }
+}
+
+void launch_penalty(const PenArgs &a, hipStream_t s) {
+  hipLaunchKernelGGL(k_penalty, dim3((unsigned)a.count), dim3(256), 0, s, a);
+}
+
 // ------------------------------------------------------------------ launch wrappers
 
 // tuning knobs of the streamed update (mvx_set_tuning; defaults are the measured best)

@@ -40,10 +40,12 @@ int main(int argc, char **argv) {
               << "Output verbosity options:\n"
               << "  -s/--silent\n  -v/--verbose\n  -d/--debug\n  -so/--solver-output\n\n"
               << "Algorithm strategy options:\n"
-              << "  -vs [{0|1|2}]\n"
+              << "  -vs [{0|1|2|3|4}]\n"
               << "    0. vars are picked on order\n"
               << "    1. vars are picked on fractional part closeness to 0.5\n"
               << "    2. vars are picked on greatest impact on obj. function\n"
+              << "    3. vars are picked on the node LP's dual penalties (largest product of both sides)\n"
+              << "    4. strong branching on the --sb-cands best penalty candidates (not with --best-window)\n"
               << "  -bs [{0|1}]\n"
               << "    0. nodes are picked for DFS (FIFO/queue)\n"
               << "    1. nodes are picked for best-FS (greatest z-value)\n"
@@ -56,6 +58,8 @@ int main(int argc, char **argv) {
               << "  --cut-select K  with --repaired -cm 1: 0 add the last cut, 1 add the -cf fraction of most effective cuts\n"
               << "  --best-window N with -bs 1: speculate on the top N open nodes per round (same tree; 0 = node at a time)\n"
               << "  --max-nodes N   stop after N loop iterations\n"
+              << "  --sb-cands K    with -vs 4: candidates strong-branched per node (default 2)\n"
+              << "  --sb-iters L    with -vs 4: pivot limit of each strong-branching child solve (default 4)\n"
               << "Help:\n  -h/--help\n";
     return 0;
   }
@@ -98,7 +102,9 @@ int main(int argc, char **argv) {
     return true;
   };
   if (!int_opt("-bs", 0, 1, &params.node_strat)) return -1; // 2test.cpp:92-104
-  if (!int_opt("-vs", 0, 2, &params.var_strat)) return -1;  // 2test.cpp:106-121
+  if (!int_opt("-vs", 0, 4, &params.var_strat)) return -1;  // 2test.cpp:106-121; 3 / 4 read the node LP
+  if (!int_opt("--sb-cands", 0, 1 << 20, &params.sb_cands)) return -1;
+  if (!int_opt("--sb-iters", 0, 1 << 30, &params.sb_iters)) return -1;
   if (!int_opt("-cm", 0, 1, &params.cut_strat)) return -1;  // 2test.cpp:123-134
   if (input.CMDOptionExists("-cm")) {
     params.cut_chance = 1.0;
@@ -120,14 +126,21 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "--server: the ZeroMQ sink is not part of this build; use --events FILE for the same stream\n");
 
   mvx_bnb_result res;
-  mvx_branchAndBound(nullptr, prob, &params, &res);
+  const int brc = mvx_branchAndBound(nullptr, prob, &params, &res);
+  if (brc == -1) {
+    std::fprintf(stderr, "-vs %d is not supported with these options (-vs 3 / 4: not with --best-window)\n", params.var_strat);
+    mvx_delete_prob(prob);
+    return -1;
+  }
+  if (brc != 0) std::fprintf(stderr, "branch-and-bound stopped: the branching penalties could not be computed (%d)\n", brc);
   if (input.CMDOptionExists("--events")) mvx_bnb_write_events(&res, input.getCMDOption("--events").c_str());
   mvx_bnb_print_tree(&res, nullptr); // bs.cpp:329-343
   std::vector<char> buf(64 + 64 * (size_t)res.n);
   mvx_bnb_solution_string(nullptr, prob, &res, buf.data(), (int)buf.size());
   std::printf("\n%s\n", buf.data()); // bs.cpp:345
   if (verbose) std::printf("Solution found after %d iterations (%lld pivots)\n", res.count, res.total_pivots);
-  const int limit = res.hit_limit;
+  if (verbose && params.var_strat == 4) std::printf("Strong branching: %lld child LPs, %lld pivots\n", res.sb_lps, res.sb_pivots);
+  const int limit = res.hit_limit || brc != 0;
   mvx_bnb_free_result(&res);
   mvx_delete_prob(prob);
   return limit ? -1 : 0;

@@ -242,6 +242,23 @@ struct ClsArgs {
   int n, cap, quirks, count;
 };
 
+// one (handle, candidate) of a penalty launch (k_penalty, mvx_branch_penalties_many): where the handle's tableau and
+// non-basic statuses live, and the tableau row the candidate column is basic in (found by the host from its bvar mirror)
+struct PenNode {
+  const double *T;
+  const int *nflag;
+  int m, ld, row, n; // rows of this handle, its row stride, the candidate's tableau row, the non-basic positions
+};
+
+// arguments of k_penalty: `count` (handle, candidate) pairs, one workgroup each
+struct PenArgs {
+  const PenNode *nodes; // [count]
+  double *pen_down, *pen_up; // [count]
+  int *arg_down, *arg_up;    // [count] arg-min non-basic position of each side (0 when the side is +inf)
+  double tol;                // |T[i][q]| must exceed it
+  int count, pad;
+};
+
 // shared immutable matrix row (1-based, n+1 doubles)
 using RowPtr = std::shared_ptr<std::vector<double>>;
 

@@ -137,6 +137,8 @@ def branch_and_bound(engine, root, var_strat=0, quirks=1, max_nodes=0, loop_limi
     per_rank // 4, at least 1): moving a tableau costs about as much as solving the node, so a little imbalance
     is cheaper than the traffic that would remove it.
     """
+    if var_strat not in (0, 1, 2):  # var_strat 3 / 4 read the node LP's penalties: not on several ranks yet
+        raise ValueError("dist_bnb.branch_and_bound: var_strat %r is not supported (0..2)" % (var_strat,))
     import torch.distributed as dist
 
     if dist.is_available() and dist.is_initialized():
