@@ -174,6 +174,16 @@ int mvx_classify_many(const mvx_prob *const *Ps, int count, int quirks, int *sta
    is not MVX_OPT; -4 a column that is not basic. */
 int mvx_branch_penalties_many(const mvx_prob *const *Ps, int count, const int *cols, const int *col_off, double tol, double *pen_down,
                               double *pen_up, int *arg_down, int *arg_up);
+/* Primal rounding heuristic (DESIGN.md "Primal rounding heuristic") on `count` solved handles, one device launch: each
+   handle's column values rounded (mode 1) and filled greedily (mode 2), checked against the model of `root` -- its rows
+   1..m0 (m0 = root's row count; rows a handle has beyond them, cut rows, are ignored), row bounds, column bounds and
+   objective.  The handles are B&B nodes of root's tree: their own column bounds are tightened, so the root names the
+   model.  The model is uploaded once and kept with `root` while root's rows, bounds, objective and kinds stay as they
+   are.  obj[t], found[t] (1: feasible) and the candidate x[t*(n+1) + 1 .. t*(n+1) + n] per handle.  Bit-identical to
+   mvx_bnb_round (mvx_bnb.h).  Returns 0; -1 bad arguments (mode outside 1..2, a handle with another column count); -2
+   device out of memory; -3 a handle whose status is not MVX_OPT; -5 n > 4096 (the kernel keeps a handle's values and
+   its sort in LDS). */
+int mvx_round_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, int mode, double *obj, int *found, double *x);
 
 /* ---- engine-state access (parity tests, visualisers) --------------------------- */
 int mvx_get_tableau_ld(const mvx_prob *P);

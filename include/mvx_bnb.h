@@ -79,6 +79,10 @@ typedef struct mvx_lp_api {
      (mvx_branch_penalties_many); the driver prefers it to the host computation */
   int (*branch_penalties_many)(const void *const *Ps, int count, const int *cols, const int *col_off, double tol, double *pen_down,
                                double *pen_up, int *arg_down, int *arg_up);
+  /* optional (may be NULL): the primal rounding heuristic (DESIGN.md "Primal rounding heuristic") on `count` solved handles
+     in one call (mvx_round_many), the model taken from `root`; without it, or when it returns -5 (more columns than the
+     kernel holds), the driver runs the host twin mvx_bnb_round */
+  int (*round_many)(const void *root, const void *const *Ps, int count, int mode, double *obj, int *found, double *x);
 } mvx_lp_api;
 
 const mvx_lp_api *mvx_hip_lp_api(void);
@@ -118,6 +122,9 @@ typedef struct {
   int sb_cands;         /* var_strat = 4: candidates (best penalty scores first) whose two children are strong-branched;
                            default 2 (CPU sweep) */
   int sb_iters;         /* var_strat = 4: pivot limit of each strong-branching child solve; default 4 */
+  int heur;             /* primal rounding heuristic (DESIGN.md "Primal rounding heuristic") on every node that branches, on
+                           its LP as solved: 0 off (default), 1 round and check, 2 round, check and fill.  Needs
+                           reference_quirks = 0; a better feasible point becomes the incumbent */
 } mvx_bnb_params;
 
 /* B&B events at the emit points of bs.cpp (message.h EventType) */
@@ -155,13 +162,19 @@ typedef struct {
   long long speculated; /* best_window driver only (0 otherwise): nodes taken into a round's window, summed */
   long long sb_lps;     /* var_strat = 4: strong-branching child LPs solved for the nodes that branched */
   long long sb_pivots;  /* their pivots (not part of total_pivots) */
+  long long heur_calls;    /* heur > 0: nodes the rounding heuristic ran on (the nodes that branched) */
+  long long heur_found;    /* ... of which it returned a feasible point */
+  long long heur_improved; /* ... of which the point became the incumbent */
+  int incumbent_heur;      /* 1: the final incumbent came from the heuristic, 0: from an integral node LP (or none) */
 } mvx_bnb_result;
 
 void mvx_bnb_default_params(mvx_bnb_params *p);
 /* int branchAndBound(glp_prob*, MVOLP::ParameterObj&)  bs.h:7.  Returns 0; -1 refused parameters (var_strat outside
-   0..4, var_strat >= 3 with best_window > 0) -- *res is then empty; -2 var_strat >= 3 and the branching penalties could
-   not be computed (the table has neither branch_penalties_many nor get_tableau + get_basis, or they failed) -- *res holds
-   the tree up to that node */
+   0..4, var_strat >= 3 with best_window > 0, heur outside 0..2, heur > 0 with reference_quirks = 1) -- *res is then
+   empty; -2 var_strat >= 3 and the branching penalties could not be computed (the table has neither
+   branch_penalties_many nor get_tableau + get_basis, or they failed), or heur > 0 and the heuristic could not run (the
+   table has neither round_many nor the accessors of mvx_bnb_round, or they failed) -- *res holds the tree up to that
+   node */
 int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *params, mvx_bnb_result *res);
 void mvx_bnb_free_result(mvx_bnb_result *res);
 
@@ -194,6 +207,15 @@ int mvx_bnb_make_children(const mvx_lp_api *api, const void *a, int pick, int qu
    basic; -5 the table has no get_tableau / get_basis or they failed */
 int mvx_bnb_penalties(const mvx_lp_api *api, const void *prob, const int *cols, int count, double tol, double *pen_down, double *pen_up,
                       int *arg_down, int *arg_up);
+
+/* Primal rounding heuristic (DESIGN.md "Primal rounding heuristic"), host twin of mvx_round_many for one solved handle:
+   the node LP's column values (get_col_prim) rounded, checked against rows 1..m0 of `root` (m0 = its row count; cut
+   rows are ignored), root's column bounds and objective, and with mode 2 filled greedily.  *obj the candidate's
+   objective, *found 1 when it is feasible, x[1..n] the candidate (x[0] untouched).  Works through the table only
+   (get_col_prim_all / get_col_prim, get_mat_row, bounds, get_obj_coef, get_col_kind, get_obj_dir).  Returns 0; -1 bad
+   arguments (mode outside 1..2, another column count); -2 the table lacks an accessor it needs; -3 the handle is not
+   MVX_OPT */
+int mvx_bnb_round(const mvx_lp_api *api, const void *prob, const void *root, int mode, double *obj, int *found, double *x);
 
 /* bs.cpp:249-258 on one solved node `a` that is about to be branched: generate its GMI cut(s) and append the
    row(s) (cut_strat / reference_quirks / lazy_pool / cut_select / cut_chance of `params`).  Returns the number

@@ -72,7 +72,8 @@ void mvx_dist_default_params(mvx_dist_params *p);
 /* The multi-rank counterpart of mvx_branchAndBound (bs.h:7).  Call it on every rank of `comm` with that rank's handle
    of the identical root problem; `res` comes out identical on every rank (mvx_bnb_free_result frees it).  FIFO node
    order only (params->node_strat 0: best-bound order picks by fresh child bounds and is not window-batchable), var_strat
-   0..2 only (3 / 4 read the node LP's penalties and are refused with MVX_EFAIL).
+   0..2 only (3 / 4 read the node LP's penalties and are refused with MVX_EFAIL), heur 0 only (the rounding heuristic is
+   refused with MVX_EFAIL).
    comm NULL = one rank.  Returns 0, MVX_EFAIL for an unsupported parameter, a transport error code of `comm`, or
    MVX_EDIST_NOCUT when a bug-compatible run meets a branched node that generates no cut (bs.cpp would re-add a cut
    pooled by an earlier node, cut.cpp:16-21, which is not carried between ranks). */

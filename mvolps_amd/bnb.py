@@ -15,7 +15,7 @@ _FIELDS = [
     "get_it_cnt",
 ]
 _OPTIONAL = ["simplex_batch", "get_obj_dir", "gmi_cuts", "gmi_cuts_many", "get_col_prim_all", "classify_many", "get_tableau", "get_basis",
-             "branch_penalties_many"]
+             "branch_penalties_many", "round_many"]
 
 
 class LpApiTable(C.Structure):
@@ -39,6 +39,7 @@ class BnbParams(C.Structure):
         ("best_window", C.c_int),
         ("sb_cands", C.c_int),
         ("sb_iters", C.c_int),
+        ("heur", C.c_int),
     ]
 
 
@@ -75,6 +76,10 @@ class BnbResult(C.Structure):
         ("speculated", C.c_longlong),
         ("sb_lps", C.c_longlong),
         ("sb_pivots", C.c_longlong),
+        ("heur_calls", C.c_longlong),
+        ("heur_found", C.c_longlong),
+        ("heur_improved", C.c_longlong),
+        ("incumbent_heur", C.c_int),
     ]
 
 
@@ -114,6 +119,10 @@ def _bind(lib):
     lib.mvx_branch_penalties_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, _IP, _IP, C.c_double, _DP, _DP, _IP, _IP]
     lib.mvx_bnb_penalties.restype = C.c_int
     lib.mvx_bnb_penalties.argtypes = [C.c_void_p, C.c_void_p, _IP, C.c_int, C.c_double, _DP, _DP, _IP, _IP]
+    lib.mvx_round_many.restype = C.c_int
+    lib.mvx_round_many.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, _DP, _IP, _DP]
+    lib.mvx_bnb_round.restype = C.c_int
+    lib.mvx_bnb_round.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _DP, _IP, _DP]
     lib.mvx_generateCut3.restype = C.c_int
     lib.mvx_generateCut3.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     return lib
@@ -153,11 +162,15 @@ def result_to_dict(res):
         "speculated": res.speculated,
         "sb_lps": res.sb_lps,
         "sb_pivots": res.sb_pivots,
+        "heur_calls": res.heur_calls,
+        "heur_found": res.heur_found,
+        "heur_improved": res.heur_improved,
+        "incumbent_heur": res.incumbent_heur,
     }
 
 
 def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, window=None, cut_select=0, cut_chance=1.0,
-                best_window=None, sb_cands=None, sb_iters=None):
+                best_window=None, sb_cands=None, sb_iters=None, heur=None):
     """mvx_bnb_params with ParameterObj's defaults (util.h:65-67) overridden by the arguments (None: the default)."""
     pr = BnbParams()
     lib().mvx_bnb_default_params(C.byref(pr))
@@ -172,18 +185,21 @@ def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, l
         pr.sb_cands = sb_cands
     if sb_iters is not None:
         pr.sb_iters = sb_iters
+    if heur is not None:
+        pr.heur = heur
     return pr
 
 
 def branch_and_bound(prob, var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, table=None, window=None,
-                     cut_select=0, cut_chance=1.0, best_window=None, sb_cands=None, sb_iters=None):
+                     cut_select=0, cut_chance=1.0, best_window=None, sb_cands=None, sb_iters=None, heur=None):
     """Run the driver on `prob` (a capi.Prob).  table=None uses the gfx950 engine's own table.  best_window > 1 with
     node_strat=1: the speculative best-bound window (mvx_bnb_params.best_window).  var_strat 3 / 4: branching on the node
-    LP's penalties / strong branching (sb_cands candidates, sb_iters pivots per child).  The dictionary's "rc" is
-    mvx_branchAndBound's return code (-1 refused parameters, -2 penalties unavailable)."""
+    LP's penalties / strong branching (sb_cands candidates, sb_iters pivots per child).  heur 1 / 2: the primal rounding
+    heuristic on every branching node (round and check / round, check and fill; quirks=0 only).  The dictionary's "rc" is
+    mvx_branchAndBound's return code (-1 refused parameters, -2 penalties or heuristic unavailable)."""
     L = lib()
     pr = make_params(var_strat, node_strat, cut_strat, max_nodes, quirks, lazy_pool, window, cut_select, cut_chance, best_window, sb_cands,
-                     sb_iters)
+                     sb_iters, heur)
     res = BnbResult()
     tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
     rc = L.mvx_branchAndBound(tptr, prob.h, C.byref(pr), C.byref(res))
@@ -312,3 +328,54 @@ def penalties(prob, cols, tol=1e-9, table=None):
     rc = lib().mvx_bnb_penalties(tptr, prob.h, cs.ctypes.data_as(C.POINTER(C.c_int)), len(cols), tol, *_ptrs(pd, pu, ad, au))
     k = len(cols)
     return rc, (pd[:k], pu[:k], ad[:k], au[:k])
+
+
+def round_many(root, probs, mode=2):
+    """mvx_round_many over capi.Prob handles of the gfx950 engine against the model of `root`: one launch for all of them.
+    Returns (rc, obj array, found array, x array of shape (len(probs), n + 1); x[:, 0] unused)."""
+    import numpy as np
+
+    k = len(probs)
+    n = root.n
+    hs = (C.c_void_p * max(1, k))(*[p.h for p in probs])
+    obj = np.zeros(max(1, k))
+    found = np.zeros(max(1, k), dtype=np.int32)
+    x = np.zeros((max(1, k), n + 1))
+    rc = lib().mvx_round_many(root.h, hs, k, mode, obj.ctypes.data_as(C.POINTER(C.c_double)), found.ctypes.data_as(C.POINTER(C.c_int)),
+                              x.ctypes.data_as(C.POINTER(C.c_double)))
+    return rc, obj[:k], found[:k], x[:k]
+
+
+def round_node(prob, root, mode=2, table=None):
+    """mvx_bnb_round (the host twin, through `table`; None = the gfx950 engine's table) on one solved node against the model
+    of `root`.  Returns (rc, obj, found, x array of n + 1 entries; x[0] unused)."""
+    import numpy as np
+
+    n = root.n
+    obj = C.c_double(0.0)
+    found = C.c_int(0)
+    x = np.zeros(n + 1)
+    tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
+    rc = lib().mvx_bnb_round(tptr, prob.h, root.h, mode, C.byref(obj), C.byref(found), x.ctypes.data_as(C.POINTER(C.c_double)))
+    return rc, obj.value, found.value, x
+
+
+def node_sample(root, count, quirks=0, table=None):
+    """Solved OPT node LPs below `root` (a capi.Prob that is left as it is), breadth first: a solved clone of the root,
+    then children and grandchildren (each node branched on one of its violated columns, in turn), at most `count` of them.
+    Real B&B nodes for exercising and timing the per-node entries (mvx_round_many, the branching penalties)."""
+    first = root.copy()
+    first.simplex()
+    out, queue = [], [first]
+    while queue and len(out) < count:
+        P = queue.pop(0)
+        if P.status != capi.OPT:
+            continue
+        out.append(P)
+        _st, viol = print_info(P, quirks=quirks, table=table)
+        if viol:
+            S2, S3 = make_children(P, viol[len(out) % len(viol)], quirks=quirks, table=table)
+            S2.simplex()
+            S3.simplex()
+            queue += [S2, S3]
+    return out

@@ -8,6 +8,7 @@
 // Every LP call goes through `mvx_lp_api`; with the default table that is the gfx950 engine.
 #include <algorithm>
 #include <chrono>
+#include <cfloat>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -30,6 +31,8 @@ extern "C" int mvx_branch_penalties_many(const mvx_prob *const *Ps, int count, c
 extern "C" int mvx_get_tableau(const mvx_prob *P, double *out) __attribute__((weak));
 extern "C" int mvx_get_basis(const mvx_prob *P, int *head, int *nb, int *flag) __attribute__((weak));
 extern "C" void mvx_init_smcp(mvx_smcp *parm) __attribute__((weak));
+extern "C" int mvx_round_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, int mode, double *obj, int *found, double *x)
+    __attribute__((weak));
 
 namespace {
 
@@ -870,6 +873,230 @@ static int choose_many(const mvx_lp_api *api, const std::vector<const void *> &h
   return 0;
 }
 
+// ---- primal rounding heuristic (heur 1 / 2, DESIGN.md "Primal rounding heuristic") ----
+
+// The model the heuristic checks a candidate against, read once per tree from the root through the table: rows 1..m0 with
+// their non-zeros in ascending column order (and by column for the fill), row and column bounds (+-inf where absent),
+// the objective, and which columns are integer and locked down / up by some row.
+struct RoundHost {
+  int m0 = 0, n = 0;
+  double sg = 1.0;
+  std::vector<std::vector<std::pair<int, double>>> rows, cols; // rows[i-1]: (j, a_ij) ascending j; cols[j]: (i-1, a_ij)
+  std::vector<double> rlo, rhi, clo, chi, c;
+  std::vector<char> isint, dlock, ulock;
+};
+
+static double tab_bound(double b) { // the table reports an absent bound as -+DBL_MAX (GLPK)
+  const double inf = std::numeric_limits<double>::infinity();
+  return b <= -DBL_MAX ? -inf : b >= DBL_MAX ? inf : b;
+}
+static double round_tol(double b) { return 1e-9 * std::max(1.0, std::fabs(b)); } // a row bound's feasibility tolerance
+
+static int round_host_model(const mvx_lp_api *api, const void *root, RoundHost &M) {
+  if (!api->get_mat_row || !api->get_row_lb || !api->get_row_ub || !api->get_col_lb || !api->get_col_ub || !api->get_obj_coef ||
+      !api->get_col_kind || !api->get_status || !(api->get_col_prim_all || api->get_col_prim))
+    return -2;
+  const int m0 = api->get_num_rows(root), n = api->get_num_cols(root);
+  M.m0 = m0;
+  M.n = n;
+  M.sg = (api->get_obj_dir && api->get_obj_dir(root) == MVX_MIN) ? -1.0 : 1.0;
+  M.rows.assign((size_t)m0, {});
+  M.cols.assign((size_t)n + 1, {});
+  M.rlo.resize((size_t)m0);
+  M.rhi.resize((size_t)m0);
+  M.clo.resize((size_t)n + 1);
+  M.chi.resize((size_t)n + 1);
+  M.c.resize((size_t)n + 1);
+  M.isint.assign((size_t)n + 1, 0);
+  M.dlock.assign((size_t)n + 1, 0);
+  M.ulock.assign((size_t)n + 1, 0);
+  std::vector<int> ind((size_t)n + 1);
+  std::vector<double> val((size_t)n + 1);
+  for (int i = 1; i <= m0; i++) {
+    const int len = api->get_mat_row(root, i, ind.data(), val.data());
+    auto &row = M.rows[(size_t)i - 1];
+    for (int k = 1; k <= len; k++)
+      if (val[(size_t)k] != 0.0) row.emplace_back(ind[(size_t)k], val[(size_t)k]);
+    std::sort(row.begin(), row.end());
+    const double lo = tab_bound(api->get_row_lb(root, i)), up = tab_bound(api->get_row_ub(root, i));
+    M.rlo[(size_t)i - 1] = lo;
+    M.rhi[(size_t)i - 1] = up;
+    for (const auto &e : row) {
+      M.cols[(size_t)e.first].emplace_back(i - 1, e.second);
+      if ((e.second > 0.0 && std::isfinite(lo)) || (e.second < 0.0 && std::isfinite(up))) M.dlock[(size_t)e.first] = 1;
+      if ((e.second > 0.0 && std::isfinite(up)) || (e.second < 0.0 && std::isfinite(lo))) M.ulock[(size_t)e.first] = 1;
+    }
+  }
+  for (int j = 0; j <= n; j++) M.c[(size_t)j] = api->get_obj_coef(root, j);
+  for (int j = 1; j <= n; j++) {
+    M.clo[(size_t)j] = tab_bound(api->get_col_lb(root, j));
+    M.chi[(size_t)j] = tab_bound(api->get_col_ub(root, j));
+    M.isint[(size_t)j] = api->get_col_kind(root, j) != MVX_CV;
+  }
+  return 0;
+}
+
+// The heuristic on one solved node (the host twin of k_round, same operations in the same order): x[0..n] gets the
+// candidate, *obj its objective, *found whether it is feasible.
+static int round_host(const mvx_lp_api *api, const RoundHost &M, const void *P, int mode, double *obj, int *found, double *x) {
+  const int n = M.n, m0 = M.m0;
+  if (mode < 1 || mode > 2 || !obj || !found || !x || api->get_num_cols(P) != n) return -1;
+  if (api->get_status(P) != MVX_OPT) return -3;
+  std::vector<double> v((size_t)n + 1, 0.0);
+  if (api->get_col_prim_all) api->get_col_prim_all(P, v.data());
+  else
+    for (int j = 1; j <= n; j++) v[(size_t)j] = api->get_col_prim(P, j);
+  std::vector<double> xt((size_t)n + 1, 0.0), r((size_t)m0, 0.0);
+  for (int j = 1; j <= n; j++) {
+    const double vj = v[(size_t)j];
+    double xr = vj;
+    if (M.isint[(size_t)j]) {
+      const double ri = std::rint(vj);
+      if (std::fabs(vj - ri) <= 1e-9) xr = ri;
+      else if (!M.dlock[(size_t)j]) xr = std::floor(vj);
+      else if (!M.ulock[(size_t)j]) xr = std::ceil(vj);
+      else xr = std::floor(vj + 0.5);
+      const double lo = std::ceil(M.clo[(size_t)j]), hi = std::floor(M.chi[(size_t)j]);
+      if (xr < lo) xr = lo;
+      if (xr > hi) xr = hi;
+    }
+    xt[(size_t)j] = xr;
+  }
+  for (int i = 0; i < m0; i++) {
+    double acc = 0.0;
+    for (const auto &e : M.rows[(size_t)i])
+      if (xt[(size_t)e.first] != 0.0) acc = acc + e.second * xt[(size_t)e.first];
+    r[(size_t)i] = acc;
+  }
+  auto feasible = [&]() {
+    for (int j = 1; j <= n; j++)
+      if (!(M.clo[(size_t)j] <= xt[(size_t)j] && xt[(size_t)j] <= M.chi[(size_t)j])) return false;
+    for (int i = 0; i < m0; i++) {
+      const double lo = M.rlo[(size_t)i], hi = M.rhi[(size_t)i];
+      if (!(r[(size_t)i] >= lo - round_tol(lo) && r[(size_t)i] <= hi + round_tol(hi))) return false;
+    }
+    return true;
+  };
+  bool ok = feasible();
+  if (ok && mode == 2) {
+    std::vector<int> order;
+    for (int j = 1; j <= n; j++)
+      if (M.isint[(size_t)j]) order.push_back(j);
+    std::vector<double> key((size_t)n + 1, 0.0);
+    for (int j : order) key[(size_t)j] = v[(size_t)j] - std::floor(v[(size_t)j]);
+    std::sort(order.begin(), order.end(), [&](int p, int q) { return key[(size_t)p] > key[(size_t)q] || (key[(size_t)p] == key[(size_t)q] && p < q); });
+    const double inf = std::numeric_limits<double>::infinity();
+    for (int j : order) {
+      const double sc = M.sg * M.c[(size_t)j];
+      if (!(sc != 0.0)) continue;
+      const double d = sc > 0.0 ? 1.0 : -1.0;
+      double q = inf;
+      for (const auto &e : M.cols[(size_t)j]) {
+        const double da = d * e.second;
+        const int i = e.first;
+        if (da > 0.0 && std::isfinite(M.rhi[(size_t)i])) {
+          const double hi = M.rhi[(size_t)i];
+          q = std::min(q, ((hi + round_tol(hi)) - r[(size_t)i]) / da);
+        } else if (da < 0.0 && std::isfinite(M.rlo[(size_t)i])) {
+          const double lo = M.rlo[(size_t)i];
+          q = std::min(q, ((r[(size_t)i] - lo) + round_tol(lo)) / -da);
+        }
+      }
+      const double room = d > 0.0 ? std::floor(M.chi[(size_t)j]) - xt[(size_t)j] : xt[(size_t)j] - std::ceil(M.clo[(size_t)j]);
+      const double tt = std::min(room, std::floor(q));
+      if (!(tt > 0.0) || std::isinf(tt)) continue; // no room, or nothing limits the column
+      const double step = d * tt;
+      for (const auto &e : M.cols[(size_t)j]) r[(size_t)e.first] = r[(size_t)e.first] + step * e.second;
+      xt[(size_t)j] = xt[(size_t)j] + step;
+    }
+    ok = feasible();
+  }
+  double sum = 0.0;
+  for (int j = 1; j <= n; j++) sum = sum + M.c[(size_t)j] * xt[(size_t)j];
+  *obj = sum + M.c[0];
+  *found = ok ? 1 : 0;
+  for (int j = 1; j <= n; j++) x[j] = xt[(size_t)j];
+  return 0;
+}
+
+// One tree's heuristic: round_many (one call for a batch of nodes) when the table has it and the model fits the kernel,
+// else the host twin with the model read once.  Results depend on each node's own LP only.
+struct HeurOut {
+  double obj = 0.0;
+  int found = 0;
+  std::vector<double> x; // [0..n]
+};
+
+class Heuristic {
+public:
+  Heuristic(const mvx_lp_api *api, const void *root, int mode) : _api(api), _root(root), _mode(mode) {}
+  // hs: solved (OPT) nodes; 0, or the failing call's code
+  int run(const std::vector<const void *> &hs, std::vector<HeurOut> &out) {
+    const size_t K = hs.size();
+    out.assign(K, HeurOut());
+    if (K == 0) return 0;
+    const int n = _api->get_num_cols(_root);
+    if (_api->round_many && _device) {
+      std::vector<double> obj(K), x(K * (size_t)(n + 1));
+      std::vector<int> found(K);
+      const int rc = _api->round_many(_root, hs.data(), (int)K, _mode, obj.data(), found.data(), x.data());
+      if (rc == 0) {
+        for (size_t t = 0; t < K; t++) {
+          out[t].obj = obj[t];
+          out[t].found = found[t];
+          out[t].x.assign(x.begin() + (long)(t * (size_t)(n + 1)), x.begin() + (long)((t + 1) * (size_t)(n + 1)));
+        }
+        return 0;
+      }
+      if (rc != -5) return rc;
+      _device = false; // more columns than the kernel holds (mvx_round_many): the host twin, same bits, for the rest of the tree
+    }
+    if (!_ready) {
+      const int rc = round_host_model(_api, _root, _M);
+      if (rc != 0) return rc;
+      _ready = true;
+    }
+    for (size_t t = 0; t < K; t++) {
+      out[t].x.assign((size_t)n + 1, 0.0);
+      const int rc = round_host(_api, _M, hs[t], _mode, &out[t].obj, &out[t].found, out[t].x.data());
+      if (rc != 0) return rc;
+    }
+    return 0;
+  }
+
+private:
+  const mvx_lp_api *_api;
+  const void *_root;
+  int _mode;
+  bool _device = true; // round_many is used while it accepts the model
+  bool _ready = false;
+  RoundHost _M;
+};
+
+// The heuristic's counts and its part in the incumbent, booked the way the serial loop meets the nodes.
+struct HeurBook {
+  long long calls = 0, found = 0, improved = 0;
+  int incumbent = 0; // 1: the incumbent in hand came from the heuristic
+  void book(const HeurOut &h, int oid, double sg, double &bestLower, int &has_incumbent, int &incumbent_oid, std::vector<double> &xbest) {
+    calls++;
+    if (!h.found) return;
+    found++;
+    if (!(sg * h.obj > sg * bestLower)) return;
+    improved++;
+    bestLower = h.obj;
+    has_incumbent = 1;
+    incumbent_oid = oid;
+    incumbent = 1;
+    for (size_t j = 1; j < xbest.size() && j < h.x.size(); j++) xbest[j] = h.x[j];
+  }
+  void store(mvx_bnb_result *res) const {
+    res->heur_calls = calls;
+    res->heur_found = found;
+    res->heur_improved = improved;
+    res->incumbent_heur = incumbent;
+  }
+};
+
 int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm, mvx_bnb_result *res) { // bs.cpp:54
   MVOLP::ParameterObj params(api, prob, prm);
   CutPool pool(api);
@@ -892,6 +1119,8 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm,
   int count = 0;
   int rc_out = 0;
   long long sb_lps = 0, sb_pivots = 0;
+  Heuristic heur(api, prob, prm.heur);
+  HeurBook hbook;
 
   while (!leafContainer.empty()) { // bs.cpp:96
     if (prm.max_nodes > 0 && count >= prm.max_nodes) {
@@ -937,6 +1166,7 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm,
         bestLower = node->upperBound;
         has_incumbent = 1;
         incumbent_oid = node->oid;
+        hbook.incumbent = 0;
         const int na = api->get_num_cols(a);
         for (int i = 1; i <= na && i <= n0; i++) xbest[(size_t)i] = api->get_col_prim(a, i);
       }
@@ -955,6 +1185,15 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm,
         if (i != 0) acc += getFract(api->get_col_prim(a, i)); // bs.cpp:229-233
       leafContainer.erase(leafContainer.begin() + index);       // bs.cpp:247
 
+      // the rounding heuristic reads the node's LP as solved, in front of the cut step
+      if (prm.heur > 0 && api->get_status(a) == MVX_OPT) {
+        std::vector<HeurOut> ho;
+        if (heur.run({a}, ho) != 0) {
+          rc_out = -2;
+          break;
+        }
+        hbook.book(ho[0], node->oid, sg, bestLower, has_incumbent, incumbent_oid, xbest);
+      }
       // var_strat 3 / 4 read the node's LP: they choose on it as solved, in front of the cut step
       int pick = 0;
       double bound = 0.0;
@@ -1034,6 +1273,7 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm,
   pack_result(res, rec, id, count, has_incumbent, bestLower, incumbent_oid, n0, xbest, hit_limit);
   res->sb_lps = sb_lps;
   res->sb_pivots = sb_pivots;
+  hbook.store(res);
   return rc_out;
 }
 
@@ -1059,6 +1299,8 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
   int incumbent_oid = 0, has_incumbent = 0, hit_limit = 0, count = 0, rc_out = 0;
   long long sb_lps = 0, sb_pivots = 0;
   bool stop = false;
+  Heuristic heur(api, prob, prm.heur);
+  HeurBook hbook;
 
   struct Branch {
     size_t slot;
@@ -1225,6 +1467,34 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
       choice.assign(W, Choice());
       for (size_t k = 0; k < slot.size(); k++) choice[slot[k]] = got[k];
     }
+    // the rounding heuristic on every node of the window that may branch, in one call; booked by the replay for the nodes
+    // that do branch, so the incumbent moves where the serial loop's does
+    std::vector<HeurOut> hres;
+    std::vector<char> hran;
+    if (prm.heur > 0) {
+      if (info.empty()) {
+        info.resize(W);
+        for (size_t w = 0; w < W; w++) info[w] = printInfo(api, a[w], quirks);
+      }
+      std::vector<const void *> hh;
+      std::vector<size_t> slot;
+      for (size_t w = 0; w < W; w++)
+        if (info[w].first == 0 && api->get_status(a[w]) == MVX_OPT) {
+          hh.push_back(a[w]);
+          slot.push_back(w);
+        }
+      std::vector<HeurOut> got;
+      if (heur.run(hh, got) != 0) {
+        rc_out = -2;
+        break;
+      }
+      hres.assign(W, HeurOut());
+      hran.assign(W, 0);
+      for (size_t k = 0; k < slot.size(); k++) {
+        hres[slot[k]] = std::move(got[k]);
+        hran[slot[k]] = 1;
+      }
+    }
     // B. replay in queue order
     Round cur;
     cur.node_events.resize(W);
@@ -1276,6 +1546,7 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
           bestLower = node->upperBound;
           has_incumbent = 1;
           incumbent_oid = node->oid;
+          hbook.incumbent = 0;
           for (int i = 1; i <= n0; i++) xbest[(size_t)i] = api->get_col_prim(aw, i);
         }
       } else if (status == -1) {
@@ -1294,6 +1565,7 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
         // pick looks at the violated list and the root problem only, and appending a row leaves every other row's value
         // as it is -- but it marks the handle's solution mirrors stale, and reading one value afterwards is a device
         // export and a host round trip per branching node (~40 us, a tenth of the cut modes' run)
+        if (prm.heur > 0 && hran[w]) hbook.book(hres[w], node->oid, sg, bestLower, has_incumbent, incumbent_oid, xbest);
         const int pick = prm.var_strat >= 3 ? choice[w].pick : params.pickVar(vars);
         const double bound = api->get_col_prim(aw, pick);
         if (prm.var_strat >= 3) {
@@ -1430,6 +1702,7 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
   pack_result(res, rec, id, count, has_incumbent, bestLower, incumbent_oid, n0, xbest, hit_limit);
   res->sb_lps = sb_lps;
   res->sb_pivots = sb_pivots;
+  hbook.store(res);
   return rc_out;
 }
 
@@ -1504,9 +1777,11 @@ int branchAndBoundBest(const mvx_lp_api *api, void *prob, const mvx_bnb_params &
   double bestLower = -sg * std::numeric_limits<double>::infinity();
   const int n0 = api->get_num_cols(prob);
   std::vector<double> xbest((size_t)n0 + 1, 0.0);
-  int incumbent_oid = 0, has_incumbent = 0, hit_limit = 0, count = 0;
+  int incumbent_oid = 0, has_incumbent = 0, hit_limit = 0, count = 0, rc_out = 0;
   long long rounds = 0, speculated = 0;
   bool stop = false;
+  Heuristic heur(api, prob, prm.heur);
+  HeurBook hbook;
   const size_t W = (size_t)prm.best_window;
   const bool timing = std::getenv("MVX_BNB_TIMING") != nullptr;
   double tA = 0, tInfo = 0, tSpec = 0, tKids = 0, tReplay = 0;
@@ -1562,6 +1837,30 @@ int branchAndBoundBest(const mvx_lp_api *api, void *prob, const mvx_bnb_params &
     std::vector<char> wanted(K, 0);
     for (size_t j = 0; j < K; j++)
       wanted[j] = S[j].branch = info[j].first == 0 && sg * api->get_obj_val(hs[j]) > sg * bestLower; // bs.cpp:210
+    // the rounding heuristic on every node speculated to branch, in one call; booked when the node commits, so that an
+    // incumbent it finds enters the commit test of the nodes behind it
+    std::vector<HeurOut> hres;
+    std::vector<char> hran;
+    if (prm.heur > 0) {
+      std::vector<const void *> hh;
+      std::vector<size_t> slot;
+      for (size_t j = 0; j < K; j++)
+        if (wanted[j] && api->get_status(hs[j]) == MVX_OPT) {
+          hh.push_back(hs[j]);
+          slot.push_back(j);
+        }
+      std::vector<HeurOut> got;
+      if (heur.run(hh, got) != 0) {
+        rc_out = -2;
+        break;
+      }
+      hres.assign(K, HeurOut());
+      hran.assign(K, 0);
+      for (size_t k = 0; k < slot.size(); k++) {
+        hres[slot[k]] = std::move(got[k]);
+        hran[slot[k]] = 1;
+      }
+    }
     std::vector<std::unique_ptr<CutContainer>> pre = round_cuts(api, hs, wanted, prm, quirks);
     std::vector<void *> kids;
     for (size_t j = 0; j < K; j++) {
@@ -1663,6 +1962,7 @@ int branchAndBoundBest(const mvx_lp_api *api, void *prob, const mvx_bnb_params &
           bestLower = node->upperBound;
           has_incumbent = 1;
           incumbent_oid = node->oid;
+          hbook.incumbent = 0;
           for (int i = 1; i <= n0; i++) xbest[(size_t)i] = api->get_col_prim(aw, i);
         }
       } else if (status == -1) {
@@ -1675,6 +1975,7 @@ int branchAndBoundBest(const mvx_lp_api *api, void *prob, const mvx_bnb_params &
         double acc = 0;
         for (size_t k = 0; k < vars.size(); k++)
           if (vars[k] != 0) acc += getFract(xs[j][k]); // bs.cpp:229-233
+        if (prm.heur > 0 && hran[j]) hbook.book(hres[j], node->oid, sg, bestLower, has_incumbent, incumbent_oid, xbest);
         rec.emit(MVX_EV_BRANCHED, node->oid, node->upperBound, acc, (int)vars.size(), sp.pick);
         auto S2 = std::make_shared<MVOLP::NodeData>(api, sp.S2, id, true); // even oid (R), then odd (L): bs.cpp:43-52
         auto S3 = std::make_shared<MVOLP::NodeData>(api, sp.S3, id, true);
@@ -1721,7 +2022,8 @@ int branchAndBoundBest(const mvx_lp_api *api, void *prob, const mvx_bnb_params &
   pack_result(res, rec, id, count, has_incumbent, bestLower, incumbent_oid, n0, xbest, hit_limit);
   res->rounds = rounds;
   res->speculated = speculated;
-  return 0;
+  hbook.store(res);
+  return rc_out;
 }
 
 // ---- the gfx950 engine's table ----
@@ -1773,6 +2075,9 @@ const mvx_lp_api g_hip_api = {
                                     int *ad, int *au) {
       return mvx_branch_penalties_many((const mvx_prob *const *)Ps, count, cols, col_off, tol, pd, pu, ad, au);
     } : nullptr,
+    mvx_round_many ? +[](const void *root, const void *const *Ps, int count, int mode, double *obj, int *found, double *x) {
+      return mvx_round_many((const mvx_prob *)root, (const mvx_prob *const *)Ps, count, mode, obj, found, x);
+    } : nullptr,
 };
 
 } // namespace
@@ -1795,6 +2100,7 @@ void mvx_bnb_default_params(mvx_bnb_params *p) {
   p->best_window = 0;
   p->sb_cands = 2;
   p->sb_iters = 4;
+  p->heur = 0;
 }
 
 int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *params, mvx_bnb_result *res) {
@@ -1805,7 +2111,9 @@ int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *
   }
   if (!api) api = &g_hip_api;
   // var_strat 3 / 4 are not (yet) in the speculative best-bound window: refused, not run with another rule
-  if (params->var_strat < 0 || params->var_strat > 4 || (params->var_strat >= 3 && params->best_window > 0)) {
+  // heur > 0 needs the repaired mode: bug-compatible mode reproduces bs.cpp, which has no heuristic
+  if (params->var_strat < 0 || params->var_strat > 4 || (params->var_strat >= 3 && params->best_window > 0) || params->heur < 0 ||
+      params->heur > 2 || (params->heur > 0 && params->reference_quirks != 0)) {
     std::memset(res, 0, sizeof(*res));
     return -1;
   }
@@ -1868,6 +2176,15 @@ int mvx_bnb_make_children(const mvx_lp_api *api, const void *a, int pick, int qu
 int mvx_bnb_penalties(const mvx_lp_api *api, const void *prob, const int *cols, int count, double tol, double *pen_down, double *pen_up,
                       int *arg_down, int *arg_up) {
   return host_penalties(api ? api : &g_hip_api, prob, cols, count, tol, pen_down, pen_up, arg_down, arg_up);
+}
+
+int mvx_bnb_round(const mvx_lp_api *api, const void *prob, const void *root, int mode, double *obj, int *found, double *x) {
+  if (!api) api = &g_hip_api;
+  if (!prob || !root || mode < 1 || mode > 2 || !obj || !found || !x) return -1;
+  RoundHost M;
+  const int rc = round_host_model(api, root, M);
+  if (rc != 0) return rc;
+  return round_host(api, M, prob, mode, obj, found, x);
 }
 
 int mvx_bnb_node_cuts(const mvx_lp_api *api, void *a, const mvx_bnb_params *params) {

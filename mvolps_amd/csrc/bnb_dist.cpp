@@ -102,8 +102,9 @@ extern "C" int mvx_branchAndBound_dist(const mvx_lp_api *api, const mvx_image_ap
   mvx_dist_params dp;
   if (dist_in) dp = *dist_in;
   else mvx_dist_default_params(&dp);
-  // var_strat 3 / 4 (branching on the node LP's penalties) are not carried to several ranks yet: refused
-  if (prm.node_strat != 0 || dp.per_rank < 1 || prm.var_strat < 0 || prm.var_strat > 2) return MVX_EFAIL;
+  // var_strat 3 / 4 (branching on the node LP's penalties) and the rounding heuristic are not carried to several ranks yet:
+  // refused
+  if (prm.node_strat != 0 || dp.per_rank < 1 || prm.var_strat < 0 || prm.var_strat > 2 || prm.heur != 0) return MVX_EFAIL;
   const int rank = comm ? comm->rank : 0, world = comm ? comm->size : 1;
   const int per_rank = dp.per_rank;
   const int slack = dp.slack >= 0 ? dp.slack : std::max(1, per_rank / 4);

@@ -70,6 +70,7 @@ static void reset_model(mvx_prob *P) {
   P->bvar.clear(); P->nvar.clear(); P->nflag.clear(); P->pos.clear();
   P->pending.clear();
   P->dmat.reset();
+  P->rmod.reset();
   P->sol_fresh = false;
   P->fresh_rows = -1;
   P->beta.clear(); P->dj.clear();
@@ -149,6 +150,7 @@ void mvx_copy_prob(mvx_prob *dst, const mvx_prob *src, int names) {
   dst->refresh_cnt = src->refresh_cnt;
   dst->pending = src->pending;
   dst->dmat = src->dmat;
+  dst->rmod.reset(); // describes dst's old model; a root's rounding model is never passed on
   std::memcpy(dst->last_tol, src->last_tol, sizeof(dst->last_tol));
   dst->bvar = src->bvar; dst->nvar = src->nvar; dst->nflag = src->nflag; dst->pos = src->pos;
   dst->sol_fresh = src->sol_fresh; dst->fresh_rows = src->fresh_rows; dst->beta = src->beta; dst->dj = src->dj;
@@ -507,6 +509,9 @@ int mvx_classify_many(const mvx_prob *const *Ps, int count, int quirks, int *sta
 int mvx_branch_penalties_many(const mvx_prob *const *Ps, int count, const int *cols, const int *col_off, double tol, double *pen_down,
                               double *pen_up, int *arg_down, int *arg_up) {
   return mvx::engine_penalties_many(Ps, count, cols, col_off, tol, pen_down, pen_up, arg_down, arg_up);
+}
+int mvx_round_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, int mode, double *obj, int *found, double *x) {
+  return mvx::engine_round_many(root, Ps, count, mode, obj, found, x);
 }
 
 int mvx_device_count(void) { return mvx::device_count(); }

@@ -32,6 +32,20 @@ struct DevMatrix {
   }
 };
 
+// Device copy of a root's model for the rounding heuristic (see mvx_prob::rmod, engine_round_many), and the host state it
+// was built from: it is rebuilt when any of that has changed.
+struct RoundModel {
+  int m0 = 0, n = 0, ldm = 0, dir = 0;
+  void *dev = nullptr; // [At (n+1) x ldm][rlo m0][rhi m0][clo n+1][chi n+1][c n+1][flags n+1]
+  size_t o_rlo = 0, o_rhi = 0, o_clo = 0, o_chi = 0, o_c = 0, o_flags = 0;
+  std::vector<mvx::RowPtr> rows; // owned: a row's address cannot be reused while the model compares against it
+  std::vector<double> c, clb, cub, rlb, rub;
+  std::vector<int> kind;
+  ~RoundModel() {
+    if (dev) (void)hipFree(dev);
+  }
+};
+
 namespace mvx {
 
 #define HIPCHECK(expr)                                                                         \
@@ -72,6 +86,7 @@ void launch_copy_many(const CopyBatch &b, hipStream_t);
 void launch_gmi(const GmiArgs &a, hipStream_t);
 void launch_classify(const ClsArgs &a, hipStream_t);
 void launch_penalty(const PenArgs &a, hipStream_t);
+void launch_round(const RndArgs &a, hipStream_t);
 void launch_refresh_select(Ctl *, const int *tflag, int var, hipStream_t);
 size_t persist_lds_bytes(int m, int cpw);
 int persist_max_cpw();
@@ -196,6 +211,10 @@ struct Context {
   void *pen_dev = nullptr, *pen_host = nullptr;
   unsigned char *pen_out_dev = nullptr;
   size_t pen_dev_bytes = 0, pen_host_bytes = 0;
+  // rounding heuristic (engine_round_many): device descriptors and row scratch, pinned upload / results
+  void *rnd_dev = nullptr, *rnd_host = nullptr;
+  unsigned char *rnd_out_dev = nullptr;
+  size_t rnd_dev_bytes = 0, rnd_host_bytes = 0;
   // profiling (main context only)
   bool prof = false;
   double prof_update_ms = 0.0;
@@ -2478,6 +2497,156 @@ int engine_penalties_many(const mvx_prob *const *Ps, int count, const int *cols,
   std::memcpy(pen_up + k0, hb + o_pu, (size_t)total * 8);
   std::memcpy(arg_down + k0, hb + o_ad, (size_t)total * 4);
   std::memcpy(arg_up + k0, hb + o_au, (size_t)total * 4);
+  return 0;
+}
+
+// ------------------------------------------------------------------ rounding heuristic (k_round)
+// The model k_round reads, built from `root` and kept with it (root->rmod) for as long as rows 1..m0 are the same objects
+// and the objective, kinds, direction and bounds are unchanged -- once per B&B tree.  Rows go up by column (At[j][i]) so
+// that a wave reads one column of consecutive rows at a time; the locks are taken from the same rows.
+static bool round_model_current(const mvx_prob *R) {
+  const RoundModel *M = R->rmod.get();
+  if (!M || M->m0 != R->m || M->n != R->n || M->dir != R->dir) return false;
+  for (int i = 1; i <= R->m; i++)
+    if (M->rows[(size_t)i - 1] != R->A[(size_t)i]) return false;
+  return M->c == R->c && M->kind == R->kind && M->clb == R->clb && M->cub == R->cub && M->rlb == R->rlb && M->rub == R->rub;
+}
+
+static const RoundModel *round_model(Context &c, const mvx_prob *R) {
+  if (round_model_current(R)) return R->rmod.get();
+  R->rmod.reset();
+  SolveCtx &sc = c.main;
+  auto M = std::make_shared<RoundModel>();
+  const int m0 = R->m, n = R->n;
+  const size_t ldm = align_up((size_t)std::max(1, m0), 64);
+  M->m0 = m0; M->n = n; M->ldm = (int)ldm; M->dir = R->dir;
+  size_t off = 0;
+  auto carve = [&](size_t bytes) {
+    size_t o = off;
+    off = align_up(off + bytes, 256);
+    return o;
+  };
+  carve((size_t)(n + 1) * ldm * 8);
+  M->o_rlo = carve((size_t)m0 * 8); M->o_rhi = carve((size_t)m0 * 8);
+  M->o_clo = carve((size_t)(n + 1) * 8); M->o_chi = carve((size_t)(n + 1) * 8); M->o_c = carve((size_t)(n + 1) * 8);
+  M->o_flags = carve((size_t)(n + 1) * 4);
+  std::vector<unsigned char> h(off, 0);
+  double *At = (double *)h.data();
+  int *flags = (int *)(h.data() + M->o_flags);
+  for (int j = 1; j <= n; j++) flags[j] = R->kind[(size_t)j] != MVX_CV ? RND_INT : 0;
+  for (int i = 1; i <= m0; i++) {
+    const double *ai = R->A[(size_t)i]->data();
+    M->rows.push_back(R->A[(size_t)i]);
+    const bool lo = std::isfinite(R->rlb[(size_t)i]), up = std::isfinite(R->rub[(size_t)i]);
+    ((double *)(h.data() + M->o_rlo))[i - 1] = R->rlb[(size_t)i];
+    ((double *)(h.data() + M->o_rhi))[i - 1] = R->rub[(size_t)i];
+    for (int j = 1; j <= n; j++) {
+      const double v = ai[j];
+      At[(size_t)j * ldm + (size_t)(i - 1)] = v;
+      if ((v > 0.0 && lo) || (v < 0.0 && up)) flags[j] |= RND_DLOCK; // lowering x_j can break the row
+      if ((v > 0.0 && up) || (v < 0.0 && lo)) flags[j] |= RND_ULOCK;
+    }
+  }
+  std::memcpy(h.data() + M->o_clo, R->clb.data(), (size_t)(n + 1) * 8);
+  std::memcpy(h.data() + M->o_chi, R->cub.data(), (size_t)(n + 1) * 8);
+  std::memcpy(h.data() + M->o_c, R->c.data(), (size_t)(n + 1) * 8);
+  if (hipMalloc(&M->dev, off) != hipSuccess) {
+    (void)hipGetLastError();
+    M->dev = nullptr;
+    g_last_error.store(MVX_ENOMEM);
+    return nullptr;
+  }
+  HIPCHECK(hipMemcpyAsync(M->dev, h.data(), off, hipMemcpyHostToDevice, sc.stream));
+  HIPCHECK(hipStreamSynchronize(sc.stream)); // the pageable source goes out of scope
+  M->c = R->c; M->kind = R->kind; M->clb = R->clb; M->cub = R->cub; M->rlb = R->rlb; M->rub = R->rub;
+  R->rmod = M;
+  return M.get();
+}
+
+// Primal rounding heuristic on `count` solved handles against root's model (mvx_round_many): one upload of the
+// descriptors, one k_round launch, results straight into the pinned buffer.  Return codes: 0; -1 bad arguments; -2 device
+// out of memory; -3 a handle whose status is not MVX_OPT; -5 n > RND_NMAX.
+int engine_round_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, int mode, double *obj, int *found, double *x) {
+  if (!root || count < 1 || !Ps || mode < 1 || mode > 2 || !obj || !found || !x) return -1;
+  const int n = root->n, m0 = root->m;
+  for (int t = 0; t < count; t++)
+    if (!Ps[t] || Ps[t]->n != n) return -1;
+  if (n > RND_NMAX) return -5;
+  for (int t = 0; t < count; t++)
+    if (!Ps[t]->valid || Ps[t]->status != MVX_OPT) return -3;
+  Context &c = ctx();
+  MAIN_LOCK(c);
+  flush_copies(c); // a clone recorded into one of these slabs lands first
+  SolveCtx &sc = c.main;
+  const RoundModel *M = round_model(c, root);
+  if (!M) return -2;
+  size_t off = 0;
+  auto carve = [&](size_t bytes) {
+    size_t o = off;
+    off = align_up(off + bytes, 256);
+    return o;
+  };
+  // up: [descriptors]; out: [obj][found][x]; device only: [row scratch] when the rows do not fit in LDS
+  const size_t o_nodes = carve((size_t)count * sizeof(RndNode));
+  const size_t up_bytes = off;
+  const size_t o_obj = carve((size_t)count * 8), o_found = carve((size_t)count * 4), o_x = carve((size_t)count * (n + 1) * 8);
+  const size_t host_bytes = off;
+  const size_t o_scr = carve(m0 > RND_NMAX ? (size_t)count * m0 * 8 : 0);
+  const size_t dev_bytes = off;
+  if (dev_bytes > c.rnd_dev_bytes || host_bytes > c.rnd_host_bytes) {
+    HIPCHECK(hipStreamSynchronize(sc.stream));
+    if (c.rnd_dev) HIPCHECK(hipFree(c.rnd_dev));
+    if (c.rnd_host) HIPCHECK(hipHostFree(c.rnd_host));
+    c.rnd_dev = c.rnd_host = nullptr;
+    c.rnd_out_dev = nullptr;
+    c.rnd_dev_bytes = c.rnd_host_bytes = 0;
+    const size_t want_dev = dev_bytes + dev_bytes / 2, want_host = host_bytes + host_bytes / 2;
+    if (hipMalloc(&c.rnd_dev, want_dev) != hipSuccess) {
+      (void)hipGetLastError();
+      c.rnd_dev = nullptr;
+      g_last_error.store(MVX_ENOMEM);
+      return -2;
+    }
+    if (hipHostMalloc(&c.rnd_host, want_host) != hipSuccess) {
+      (void)hipGetLastError();
+      HIPCHECK(hipFree(c.rnd_dev));
+      c.rnd_dev = c.rnd_host = nullptr;
+      g_last_error.store(MVX_ENOMEM);
+      return -2;
+    }
+    void *dp = nullptr;
+    if (hipHostGetDevicePointer(&dp, c.rnd_host, 0) == hipSuccess && dp) c.rnd_out_dev = (unsigned char *)dp;
+    else (void)hipGetLastError();
+    c.rnd_dev_bytes = want_dev;
+    c.rnd_host_bytes = want_host;
+  }
+  unsigned char *hb = (unsigned char *)c.rnd_host, *db = (unsigned char *)c.rnd_dev;
+  RndNode *h_nodes = (RndNode *)(hb + o_nodes);
+  for (int t = 0; t < count; t++) {
+    const mvx_prob *P = Ps[t];
+    RndNode &nd = h_nodes[t];
+    nd.T = P->d_T; nd.bvar = P->d_bvar; nd.nvar = P->d_nvar; nd.nflag = P->d_nflag; nd.nlb = P->d_nlb; nd.nub = P->d_nub;
+    nd.m = P->m; nd.ld = P->ld;
+  }
+  HIPCHECK(hipMemcpyAsync(db, hb, up_bytes, hipMemcpyHostToDevice, sc.stream));
+  unsigned char *ob = c.rnd_out_dev ? c.rnd_out_dev : db;
+  const unsigned char *mb = (const unsigned char *)M->dev;
+  RndArgs a;
+  a.nodes = (const RndNode *)(db + o_nodes);
+  a.At = (const double *)mb;
+  a.rlo = (const double *)(mb + M->o_rlo); a.rhi = (const double *)(mb + M->o_rhi);
+  a.clo = (const double *)(mb + M->o_clo); a.chi = (const double *)(mb + M->o_chi); a.c = (const double *)(mb + M->o_c);
+  a.flags = (const int *)(mb + M->o_flags);
+  a.scratch = m0 > RND_NMAX ? (double *)(db + o_scr) : nullptr;
+  a.obj = (double *)(ob + o_obj); a.found = (int *)(ob + o_found); a.x = (double *)(ob + o_x);
+  a.sg = root->dir == MVX_MIN ? -1.0 : 1.0;
+  a.n = n; a.m0 = m0; a.ldm = M->ldm; a.mode = mode; a.count = count; a.pad = 0;
+  launch_round(a, sc.stream);
+  if (!c.rnd_out_dev) HIPCHECK(hipMemcpyAsync(hb + o_obj, db + o_obj, host_bytes - o_obj, hipMemcpyDeviceToHost, sc.stream));
+  HIPCHECK(hipStreamSynchronize(sc.stream));
+  std::memcpy(obj, hb + o_obj, (size_t)count * 8);
+  std::memcpy(found, hb + o_found, (size_t)count * 4);
+  std::memcpy(x, hb + o_x, (size_t)count * (n + 1) * 8);
   return 0;
 }
 

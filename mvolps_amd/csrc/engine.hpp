@@ -38,6 +38,8 @@ int engine_classify_many(const mvx_prob *const *Ps, int count, int quirks, int *
 // one-step dual penalties of the candidate columns of `count` solved handles in one launch (k_penalty); see engine.cpp
 int engine_penalties_many(const mvx_prob *const *Ps, int count, const int *cols, const int *col_off, double tol, double *pen_down,
                           double *pen_up, int *arg_down, int *arg_up);
+// primal rounding heuristic on `count` solved handles against root's model, one launch (k_round); see engine.cpp
+int engine_round_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, int mode, double *obj, int *found, double *x);
 
 long long engine_pack_size(const mvx_prob *P, int m_base);
 int engine_pack(const mvx_prob *P, int m_base, void *dev_buf);

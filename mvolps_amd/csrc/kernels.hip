@@ -4133,6 +4133,213 @@ void launch_penalty(const PenArgs &a, hipStream_t s) {
   hipLaunchKernelGGL(k_penalty, dim3((unsigned)a.count), dim3(256), 0, s, a);
 }
 
+// ---------------------------------------------------------------------------- k_round
+// Primal rounding heuristic (mvx_round_many, DESIGN.md "Primal rounding heuristic"), one workgroup per handle.
+//  1. the node LP's column values, selected as k_classify selects them (get_col_prim's bits), into LDS;
+//  2. each integer column rounded (within 1e-9 of an integer: that integer; else away from its locks; else to nearest)
+//     and clipped to the root's integer range; the fill order's key, the value's fractional part;
+//  3. mode 2: the columns sorted into the fill order (fractional part descending, column ascending) by a bitonic sort in LDS;
+//  4. row activities: a row per lane, the columns in ascending order, zero values skipped (they add nothing: a sum started
+//     at +0 never holds -0), products and sums rounded one by one -- the host twin's bits;
+//  5. mode 2 on a feasible point: one column at a time, the largest step every row allows, a minimum over the rows
+//     (correctly rounded quotients, xdiv) by wave shuffles and four partials in LDS; the activities follow the step;
+//  6. the objective: the non-zero products in ascending column order, summed by one wave.
+// The row activities live in the LDS of the sort keys once the order is taken, or in a global slice when m0 > RND_NMAX.
+__device__ __forceinline__ double rnd_tol(double b) { return 1e-9 * fmax(1.0, fabs(b)); } // a row bound's tolerance
+__device__ __forceinline__ bool rnd_before(double ka, int ia, double kb, int ib) {          // fill order
+  return ka > kb || (ka == kb && ia < ib);
+}
+
+__global__ __launch_bounds__(256) void k_round(RndArgs a) {
+  __shared__ double s_x[RND_NMAX + 1];
+  __shared__ double s_key[RND_NMAX]; // fill-order keys; the row activities once the order is taken (m0 <= RND_NMAX)
+  __shared__ int s_idx[RND_NMAX];
+  __shared__ double s_red[2][4];
+  __shared__ int s_bad;
+  const int t = (int)blockIdx.x;
+  const RndNode nd = a.nodes[t];
+  const int n = a.n, m0 = a.m0, m = nd.m;
+  const size_t ldm = (size_t)a.ldm;
+  const double inf = __builtin_huge_val();
+  const int lane = TIDX & 63, wv = TIDX >> 6;
+  if (TIDX == 0) s_bad = 0;
+  for (int i = 1 + TIDX; i <= m; i += 256) {
+    const int k = nd.bvar[i];
+    if (k > m && k <= m + n) s_x[k - m] = nd.T[(size_t)i * (size_t)nd.ld];
+  }
+  for (int q = 1 + TIDX; q <= n; q += 256) {
+    const int k = nd.nvar[q];
+    if (k > m && k <= m + n) s_x[k - m] = dev_nb_value(nd.nflag[q], nd.nlb[q], nd.nub[q]);
+  }
+  __syncthreads();
+  int np = 1;
+  while (np < n) np <<= 1;
+  bool bad = false;
+  for (int j = 1 + TIDX; j <= n; j += 256) {
+    const double v = s_x[j];
+    const int f = a.flags[j];
+    double xr = v, key = -1.0;
+    if (f & RND_INT) {
+      const double r = rint(v);
+      if (fabs(v - r) <= 1e-9) xr = r;
+      else if (!(f & RND_DLOCK)) xr = floor(v);
+      else if (!(f & RND_ULOCK)) xr = ceil(v);
+      else xr = floor(v + 0.5);
+      const double lo = ceil(a.clo[j]), hi = floor(a.chi[j]);
+      if (xr < lo) xr = lo;
+      if (xr > hi) xr = hi;
+      key = v - floor(v);
+    }
+    bad = bad || !(a.clo[j] <= xr && xr <= a.chi[j]);
+    s_x[j] = xr;
+    s_key[j - 1] = key;
+    s_idx[j - 1] = j;
+  }
+  for (int p = n + TIDX; p < np; p += 256) {
+    s_key[p] = -2.0;
+    s_idx[p] = 0x7fffffff;
+  }
+  __syncthreads();
+  if (a.mode == 2) {
+    for (int k2 = 2; k2 <= np; k2 <<= 1)
+      for (int jj = k2 >> 1; jj > 0; jj >>= 1) {
+        for (int i = TIDX; i < np; i += 256) {
+          const int l = i ^ jj;
+          if (l <= i) continue;
+          const double ki = s_key[i], kl = s_key[l];
+          const int ii = s_idx[i], il = s_idx[l];
+          const bool sw = ((i & k2) == 0) ? rnd_before(kl, il, ki, ii) : rnd_before(ki, ii, kl, il);
+          if (sw) {
+            s_key[i] = kl; s_key[l] = ki;
+            s_idx[i] = il; s_idx[l] = ii;
+          }
+        }
+        __syncthreads();
+      }
+  }
+  double *r = m0 <= RND_NMAX ? s_key : a.scratch + (size_t)t * (size_t)m0;
+  for (int i = TIDX; i < m0; i += 256) {
+    double acc = 0.0;
+    for (int j = 1; j <= n; j++) {
+      const double xj = s_x[j];
+      if (xj != 0.0) acc = __dadd_rn(acc, __dmul_rn(a.At[(size_t)j * ldm + i], xj));
+    }
+    r[i] = acc;
+    const double lo = a.rlo[i], hi = a.rhi[i];
+    bad = bad || !(acc >= lo - rnd_tol(lo) && acc <= hi + rnd_tol(hi));
+  }
+  if (bad) s_bad = 1;
+  __syncthreads();
+  if (a.mode == 2 && !s_bad) {
+    // up to RND_RPT * 256 rows: each thread keeps its rows' activities and the column at hand in registers, and loads the
+    // next column of the order while this one is reduced (same values, same operations: only the loads move)
+    const bool regs = m0 <= RND_RPT * 256;
+    double av[RND_RPT], nx[RND_RPT], rr[RND_RPT];
+    auto load_col = [&](int jj, double *dst) {
+#pragma unroll
+      for (int q = 0; q < RND_RPT; q++) {
+        const int i = TIDX + 256 * q;
+        dst[q] = (jj <= n && i < m0) ? a.At[(size_t)jj * ldm + i] : 0.0;
+      }
+    };
+    if (regs) {
+#pragma unroll
+      for (int q = 0; q < RND_RPT; q++) rr[q] = TIDX + 256 * q < m0 ? r[TIDX + 256 * q] : 0.0;
+      load_col(s_idx[0], nx);
+    }
+    int ph = 0; // s_red buffer of the next barrier: it flips at every barrier, not at every column (zero-cost columns have none)
+    for (int k = 0; k < n; k++) {
+      const int j = s_idx[k];
+      if (j > n || !(a.flags[j] & RND_INT)) break; // integer columns come first; then the continuous ones, the padding
+      if (regs) {
+#pragma unroll
+        for (int q = 0; q < RND_RPT; q++) av[q] = nx[q];
+        load_col(k + 1 < n ? s_idx[k + 1] : n + 1, nx);
+      }
+      const double sc = a.sg * a.c[j];
+      if (!(sc != 0.0)) continue; // uniform: every thread skips the column, and its barrier
+      const double d = sc > 0.0 ? 1.0 : -1.0;
+      const double *col = a.At + (size_t)j * ldm;
+      // x_j and its room are read in front of the barrier: thread 0 writes x_j behind it, in this same interval
+      const double xj = s_x[j];
+      const double room = d > 0.0 ? floor(a.chi[j]) - xj : xj - ceil(a.clo[j]);
+      double q = inf;
+      auto limit = [&](double aij, double ri, int i) {
+        const double da = d * aij;
+        if (da > 0.0) {
+          const double hi = a.rhi[i];
+          if (hi < inf) q = fmin(q, xdiv(__dsub_rn(__dadd_rn(hi, rnd_tol(hi)), ri), da));
+        } else if (da < 0.0) {
+          const double lo = a.rlo[i];
+          if (lo > -inf) q = fmin(q, xdiv(__dadd_rn(__dsub_rn(ri, lo), rnd_tol(lo)), -da));
+        }
+      };
+      if (regs) {
+#pragma unroll
+        for (int u = 0; u < RND_RPT; u++)
+          if (TIDX + 256 * u < m0) limit(av[u], rr[u], TIDX + 256 * u);
+      } else {
+        for (int i = TIDX; i < m0; i += 256) limit(col[i], r[i], i);
+      }
+      for (int off = 32; off > 0; off >>= 1) q = fmin(q, __shfl_xor(q, off, 64));
+      // s_red is double-buffered: a wave writes buffer ph only after every wave has passed the barrier that followed the
+      // last reads of ph (the one in between), so one barrier per column suffices
+      if (lane == 0) s_red[ph][wv] = q;
+      __syncthreads();
+      const double qm = fmin(fmin(s_red[ph][0], s_red[ph][1]), fmin(s_red[ph][2], s_red[ph][3]));
+      ph ^= 1;
+      const double tt = fmin(room, floor(qm));
+      if (!(tt > 0.0) || isinf(tt)) continue; // no room, or nothing limits the column
+      const double step = d * tt;
+      if (regs) {
+#pragma unroll
+        for (int u = 0; u < RND_RPT; u++) rr[u] = __dadd_rn(rr[u], __dmul_rn(step, av[u]));
+      } else {
+        for (int i = TIDX; i < m0; i += 256) r[i] = __dadd_rn(r[i], __dmul_rn(step, col[i]));
+      }
+      if (TIDX == 0) s_x[j] = xj + step;
+    }
+    if (regs) {
+#pragma unroll
+      for (int u = 0; u < RND_RPT; u++)
+        if (TIDX + 256 * u < m0) r[TIDX + 256 * u] = rr[u];
+    }
+    __syncthreads();
+    bad = false; // the filled point, checked again
+    for (int j = 1 + TIDX; j <= n; j += 256) bad = bad || !(a.clo[j] <= s_x[j] && s_x[j] <= a.chi[j]);
+    for (int i = TIDX; i < m0; i += 256) {
+      const double lo = a.rlo[i], hi = a.rhi[i];
+      bad = bad || !(r[i] >= lo - rnd_tol(lo) && r[i] <= hi + rnd_tol(hi));
+    }
+    if (bad) s_bad = 2;
+    __syncthreads();
+  }
+  double *xo = a.x + (size_t)t * (size_t)(n + 1);
+  for (int j = 1 + TIDX; j <= n; j += 256) xo[j] = s_x[j];
+  if (wv == 0) {
+    double s = 0.0;
+    for (int j0 = 1; j0 <= n; j0 += 64) {
+      const int j = j0 + lane;
+      const double p = j <= n ? __dmul_rn(a.c[j], s_x[j]) : 0.0;
+      unsigned long long mk = __ballot(p != 0.0);
+      while (mk) {
+        const int b = __builtin_ctzll(mk);
+        mk &= mk - 1ull;
+        s = __dadd_rn(s, __shfl(p, b, 64));
+      }
+    }
+    if (lane == 0) {
+      xo[0] = 0.0;
+      a.obj[t] = __dadd_rn(s, a.c[0]);
+      a.found[t] = s_bad == 0 ? 1 : 0;
+    }
+  }
+}
+
+void launch_round(const RndArgs &a, hipStream_t s) {
+  hipLaunchKernelGGL(k_round, dim3((unsigned)a.count), dim3(256), 0, s, a);
+}
+
 // ------------------------------------------------------------------ launch wrappers
 
 // tuning knobs of the streamed update (mvx_set_tuning; defaults are the measured best)

@@ -60,6 +60,11 @@ int main(int argc, char **argv) {
               << "  --max-nodes N   stop after N loop iterations\n"
               << "  --sb-cands K    with -vs 4: candidates strong-branched per node (default 2)\n"
               << "  --sb-iters L    with -vs 4: pivot limit of each strong-branching child solve (default 4)\n"
+              << "  --heur [{0|1|2}] with --repaired: primal rounding heuristic on every branching node's LP (on the device\n"
+              << "                  up to 4096 columns, on the host beyond)\n"
+              << "    0. off (default)\n"
+              << "    1. round the LP values (away from the rows' locks) and keep the point when it is feasible\n"
+              << "    2. as 1, then raise the columns greedily along the objective while every row allows it\n"
               << "Help:\n  -h/--help\n";
     return 0;
   }
@@ -105,6 +110,7 @@ int main(int argc, char **argv) {
   if (!int_opt("-vs", 0, 4, &params.var_strat)) return -1;  // 2test.cpp:106-121; 3 / 4 read the node LP
   if (!int_opt("--sb-cands", 0, 1 << 20, &params.sb_cands)) return -1;
   if (!int_opt("--sb-iters", 0, 1 << 30, &params.sb_iters)) return -1;
+  if (!int_opt("--heur", 0, 2, &params.heur)) return -1;
   if (!int_opt("-cm", 0, 1, &params.cut_strat)) return -1;  // 2test.cpp:123-134
   if (input.CMDOptionExists("-cm")) {
     params.cut_chance = 1.0;
@@ -128,11 +134,12 @@ int main(int argc, char **argv) {
   mvx_bnb_result res;
   const int brc = mvx_branchAndBound(nullptr, prob, &params, &res);
   if (brc == -1) {
-    std::fprintf(stderr, "-vs %d is not supported with these options (-vs 3 / 4: not with --best-window)\n", params.var_strat);
+    std::fprintf(stderr, "-vs %d / --heur %d are not supported with these options (-vs 3 / 4: not with --best-window; --heur: only "
+                 "with --repaired)\n", params.var_strat, params.heur);
     mvx_delete_prob(prob);
     return -1;
   }
-  if (brc != 0) std::fprintf(stderr, "branch-and-bound stopped: the branching penalties could not be computed (%d)\n", brc);
+  if (brc != 0) std::fprintf(stderr, "branch-and-bound stopped: the branching penalties or the heuristic could not be computed (%d)\n", brc);
   if (input.CMDOptionExists("--events")) mvx_bnb_write_events(&res, input.getCMDOption("--events").c_str());
   mvx_bnb_print_tree(&res, nullptr); // bs.cpp:329-343
   std::vector<char> buf(64 + 64 * (size_t)res.n);
@@ -140,6 +147,9 @@ int main(int argc, char **argv) {
   std::printf("\n%s\n", buf.data()); // bs.cpp:345
   if (verbose) std::printf("Solution found after %d iterations (%lld pivots)\n", res.count, res.total_pivots);
   if (verbose && params.var_strat == 4) std::printf("Strong branching: %lld child LPs, %lld pivots\n", res.sb_lps, res.sb_pivots);
+  if (verbose && params.heur > 0)
+    std::printf("Rounding heuristic: %lld nodes, %lld feasible, %lld improved the incumbent%s\n", res.heur_calls, res.heur_found,
+                res.heur_improved, res.incumbent_heur ? " (the final incumbent is one of them)" : "");
   const int limit = res.hit_limit || brc != 0;
   mvx_bnb_free_result(&res);
   mvx_delete_prob(prob);

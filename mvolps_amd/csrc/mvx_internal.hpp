@@ -259,6 +259,36 @@ struct PenArgs {
   int count, pad;
 };
 
+// one handle of a rounding launch (k_round, mvx_round_many): where its tableau and basis live -- the values are selected the
+// way k_classify selects them
+struct RndNode {
+  const double *T;
+  const int *bvar, *nvar, *nflag;
+  const double *nlb, *nub;
+  int m, ld; // rows of this handle (cut rows included), its row stride
+};
+
+// the tree's model for k_round, uploaded once per root (engine_round_many): rows 1..m0 by column, their bounds, the root's
+// column bounds, the objective and per-column flags (RND_INT integer, RND_DLOCK / RND_ULOCK a row locks it down / up)
+#define RND_INT 1
+#define RND_DLOCK 2
+#define RND_ULOCK 4
+#define RND_NMAX 4096 // columns a k_round workgroup holds in LDS (values and the fill order)
+#define RND_RPT 4     // rows per thread k_round's fill keeps in registers (up to RND_RPT * 256 rows; beyond, LDS / scratch)
+struct RndArgs {
+  const RndNode *nodes;           // [count]
+  const double *At;               // [n+1][ldm]: At[j*ldm + i] = a_(i+1),j, rows 0..m0-1
+  const double *rlo, *rhi;        // [m0] row bounds, +-inf when absent
+  const double *clo, *chi, *c;    // [n+1] root column bounds (+-inf when absent), objective (c[0] the constant)
+  const int *flags;               // [n+1] RND_* bits
+  double *scratch;                // [count][m0] row activities when m0 > RND_NMAX (else LDS), nullptr otherwise
+  double *obj;                    // [count]
+  int *found;                     // [count]
+  double *x;                      // [count][n+1] the candidates
+  double sg;                      // +1 maximise, -1 minimise: the fill's direction sign(sg * c_j)
+  int n, m0, ldm, mode, count, pad;
+};
+
 // shared immutable matrix row (1-based, n+1 doubles)
 using RowPtr = std::shared_ptr<std::vector<double>>;
 
@@ -360,6 +390,9 @@ struct mvx_prob {
   // device copy of model rows 1..m0 for the GMI back-substitution (gmi.cpp:81-89), shared by every clone whose first
   // m0 rows are the same objects (B&B nodes share their root's rows); built on first use
   std::shared_ptr<struct DevMatrix> dmat;
+  // device copy of this handle's model as the root of a rounding-heuristic tree (mvx_round_many): rows 1..m by column,
+  // bounds, objective, lock flags; not passed on by copy_prob, checked against the model before every use
+  mutable std::shared_ptr<struct RoundModel> rmod;
   // host mirrors of the basis (always in sync while valid)
   std::vector<int> bvar, nvar, nflag; // [m+1], [n+1], [n+1]
   std::vector<int> pos;               // pos[k], k=1..m+n: +row or -column
