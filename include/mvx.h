@@ -184,6 +184,20 @@ int mvx_branch_penalties_many(const mvx_prob *const *Ps, int count, const int *c
    device out of memory; -3 a handle whose status is not MVX_OPT; -5 n > 4096 (the kernel keeps a handle's values and
    its sort in LDS). */
 int mvx_round_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, int mode, double *obj, int *found, double *x);
+/* Reduced-cost bound tightening (DESIGN.md "Reduced-cost tightening") of `count` solved handles against cutoff[t] (the
+   incumbent's objective), one device launch (k_rcfix) over row 0 of every tableau: a non-basic integer column at an
+   integral bound with |d_q| > tol may move at most t = ceil(gap2 / |d_q|) - 1 units off it, gap2 = sg*z - sg*cutoff plus a
+   slack of 1e-9 * max(1, |cutoff|).  Handle t's changed columns, ascending, in cols[t*n .. t*n + cnt[t] - 1] with their new
+   bounds in lb / ub[same].  Pure: no handle changes.  Bit-identical to mvx_bnb_rc_tighten (mvx_bnb.h).  Returns 0; -1 bad
+   arguments (different column counts or kinds); -2 device out of memory; -3 a handle whose status is not MVX_OPT. */
+int mvx_rc_tighten_many(const mvx_prob *const *Ps, int count, const double *cutoff, double tol, int *cnt, int *cols, double *lb,
+                        double *ub);
+/* Bound lists of many handles applied with one device launch (k_tighten): handle t takes the entries off[t] .. off[t+1]-1
+   (columns strictly ascending within a handle, finite bounds, lb <= ub).  Afterwards each handle is in the state
+   mvx_set_col_bnds(P, col, lb == ub ? MVX_FX : MVX_DB, lb, ub) per entry would leave.  Only for edits that leave a non-basic
+   column's resting value where it is: returns -4, nothing changed, when a listed column is basic in its handle or the edit
+   would move its value; -1 bad arguments; -2 device out of memory. */
+int mvx_tighten_cols_many(mvx_prob *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub);
 
 /* ---- engine-state access (parity tests, visualisers) --------------------------- */
 int mvx_get_tableau_ld(const mvx_prob *P);

@@ -83,6 +83,13 @@ typedef struct mvx_lp_api {
      in one call (mvx_round_many), the model taken from `root`; without it, or when it returns -5 (more columns than the
      kernel holds), the driver runs the host twin mvx_bnb_round */
   int (*round_many)(const void *root, const void *const *Ps, int count, int mode, double *obj, int *found, double *x);
+  /* optional (may be NULL): reduced-cost bound tightening (DESIGN.md "Reduced-cost tightening") of `count` solved handles
+     in one call (mvx_rc_tighten_many): handle t's changed columns, ascending, in cols / lb / ub[t*n .. t*n + cnt[t] - 1];
+     without it the driver runs the host twin mvx_bnb_rc_tighten */
+  int (*rc_tighten_many)(const void *const *Ps, int count, const double *cutoff, double tol, int *cnt, int *cols, double *lb, double *ub);
+  /* optional (may be NULL): the bound lists of `count` handles applied in one call (mvx_tighten_cols_many), handle t taking
+     entries off[t] .. off[t+1]-1; without it the driver calls set_col_bnds per entry */
+  int (*tighten_cols_many)(void *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub);
 } mvx_lp_api;
 
 const mvx_lp_api *mvx_hip_lp_api(void);
@@ -125,6 +132,9 @@ typedef struct {
   int heur;             /* primal rounding heuristic (DESIGN.md "Primal rounding heuristic") on every node that branches, on
                            its LP as solved: 0 off (default), 1 round and check, 2 round, check and fill.  Needs
                            reference_quirks = 0; a better feasible point becomes the incumbent */
+  int rc_fix;           /* reduced-cost bound tightening (DESIGN.md "Reduced-cost tightening"): 0 off (default), 1 on every node
+                           that reaches the branch decision while an incumbent exists, on its LP as solved; the tightened
+                           bounds go to both children.  Needs reference_quirks = 0 and best_window = 0 */
 } mvx_bnb_params;
 
 /* B&B events at the emit points of bs.cpp (message.h EventType) */
@@ -166,6 +176,9 @@ typedef struct {
   long long heur_found;    /* ... of which it returned a feasible point */
   long long heur_improved; /* ... of which the point became the incumbent */
   int incumbent_heur;      /* 1: the final incumbent came from the heuristic, 0: from an integral node LP (or none) */
+  long long rc_calls;      /* rc_fix = 1: branching nodes the reduced-cost tightening ran on */
+  long long rc_fixed;      /* ... entries of their lists with lb == ub */
+  long long rc_tightened;  /* ... the other entries */
 } mvx_bnb_result;
 
 void mvx_bnb_default_params(mvx_bnb_params *p);
@@ -216,6 +229,15 @@ int mvx_bnb_penalties(const mvx_lp_api *api, const void *prob, const int *cols, 
    arguments (mode outside 1..2, another column count); -2 the table lacks an accessor it needs; -3 the handle is not
    MVX_OPT */
 int mvx_bnb_round(const mvx_lp_api *api, const void *prob, const void *root, int mode, double *obj, int *found, double *x);
+
+/* Reduced-cost bound tightening (DESIGN.md "Reduced-cost tightening"), host twin of mvx_rc_tighten_many for one solved handle
+   against the cutoff (the incumbent's objective): the columns whose bounds change, ascending, in cols[0 .. *cnt - 1] with
+   their new bounds in lb / ub (room for n entries each).  Works through the table only (get_tableau, get_basis, get_col_kind,
+   column bounds, get_obj_dir, get_obj_val); the handle is not changed.  Returns 0; -1 bad arguments; -3 the handle is not
+   MVX_OPT; -5 the table lacks an accessor it needs, or one failed.  mvx_branchAndBound with rc_fix = 1 returns -1 (*res
+   empty) for rc_fix outside 0..1, reference_quirks = 1 or best_window > 0, and -2 when neither rc_tighten_many nor this
+   twin can run */
+int mvx_bnb_rc_tighten(const mvx_lp_api *api, const void *prob, double cutoff, double tol, int *cnt, int *cols, double *lb, double *ub);
 
 /* bs.cpp:249-258 on one solved node `a` that is about to be branched: generate its GMI cut(s) and append the
    row(s) (cut_strat / reference_quirks / lazy_pool / cut_select / cut_chance of `params`).  Returns the number

@@ -15,7 +15,7 @@ _FIELDS = [
     "get_it_cnt",
 ]
 _OPTIONAL = ["simplex_batch", "get_obj_dir", "gmi_cuts", "gmi_cuts_many", "get_col_prim_all", "classify_many", "get_tableau", "get_basis",
-             "branch_penalties_many", "round_many"]
+             "branch_penalties_many", "round_many", "rc_tighten_many", "tighten_cols_many"]
 
 
 class LpApiTable(C.Structure):
@@ -40,6 +40,7 @@ class BnbParams(C.Structure):
         ("sb_cands", C.c_int),
         ("sb_iters", C.c_int),
         ("heur", C.c_int),
+        ("rc_fix", C.c_int),
     ]
 
 
@@ -80,6 +81,9 @@ class BnbResult(C.Structure):
         ("heur_found", C.c_longlong),
         ("heur_improved", C.c_longlong),
         ("incumbent_heur", C.c_int),
+        ("rc_calls", C.c_longlong),
+        ("rc_fixed", C.c_longlong),
+        ("rc_tightened", C.c_longlong),
     ]
 
 
@@ -123,6 +127,12 @@ def _bind(lib):
     lib.mvx_round_many.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, _DP, _IP, _DP]
     lib.mvx_bnb_round.restype = C.c_int
     lib.mvx_bnb_round.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _DP, _IP, _DP]
+    lib.mvx_rc_tighten_many.restype = C.c_int
+    lib.mvx_rc_tighten_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, _DP, C.c_double, _IP, _IP, _DP, _DP]
+    lib.mvx_tighten_cols_many.restype = C.c_int
+    lib.mvx_tighten_cols_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, _IP, _IP, _DP, _DP]
+    lib.mvx_bnb_rc_tighten.restype = C.c_int
+    lib.mvx_bnb_rc_tighten.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, _IP, _IP, _DP, _DP]
     lib.mvx_generateCut3.restype = C.c_int
     lib.mvx_generateCut3.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     return lib
@@ -166,11 +176,14 @@ def result_to_dict(res):
         "heur_found": res.heur_found,
         "heur_improved": res.heur_improved,
         "incumbent_heur": res.incumbent_heur,
+        "rc_calls": res.rc_calls,
+        "rc_fixed": res.rc_fixed,
+        "rc_tightened": res.rc_tightened,
     }
 
 
 def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, window=None, cut_select=0, cut_chance=1.0,
-                best_window=None, sb_cands=None, sb_iters=None, heur=None):
+                best_window=None, sb_cands=None, sb_iters=None, heur=None, rc_fix=None):
     """mvx_bnb_params with ParameterObj's defaults (util.h:65-67) overridden by the arguments (None: the default)."""
     pr = BnbParams()
     lib().mvx_bnb_default_params(C.byref(pr))
@@ -187,19 +200,22 @@ def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, l
         pr.sb_iters = sb_iters
     if heur is not None:
         pr.heur = heur
+    if rc_fix is not None:
+        pr.rc_fix = rc_fix
     return pr
 
 
 def branch_and_bound(prob, var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, table=None, window=None,
-                     cut_select=0, cut_chance=1.0, best_window=None, sb_cands=None, sb_iters=None, heur=None):
+                     cut_select=0, cut_chance=1.0, best_window=None, sb_cands=None, sb_iters=None, heur=None, rc_fix=None):
     """Run the driver on `prob` (a capi.Prob).  table=None uses the gfx950 engine's own table.  best_window > 1 with
     node_strat=1: the speculative best-bound window (mvx_bnb_params.best_window).  var_strat 3 / 4: branching on the node
     LP's penalties / strong branching (sb_cands candidates, sb_iters pivots per child).  heur 1 / 2: the primal rounding
-    heuristic on every branching node (round and check / round, check and fill; quirks=0 only).  The dictionary's "rc" is
-    mvx_branchAndBound's return code (-1 refused parameters, -2 penalties or heuristic unavailable)."""
+    heuristic on every branching node (round and check / round, check and fill; quirks=0 only).  rc_fix 1: reduced-cost bound
+    tightening on every branching node once an incumbent exists (quirks=0, not with best_window).  The dictionary's "rc" is
+    mvx_branchAndBound's return code (-1 refused parameters, -2 penalties, heuristic or tightening unavailable)."""
     L = lib()
     pr = make_params(var_strat, node_strat, cut_strat, max_nodes, quirks, lazy_pool, window, cut_select, cut_chance, best_window, sb_cands,
-                     sb_iters, heur)
+                     sb_iters, heur, rc_fix)
     res = BnbResult()
     tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
     rc = L.mvx_branchAndBound(tptr, prob.h, C.byref(pr), C.byref(res))
@@ -358,6 +374,53 @@ def round_node(prob, root, mode=2, table=None):
     tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
     rc = lib().mvx_bnb_round(tptr, prob.h, root.h, mode, C.byref(obj), C.byref(found), x.ctypes.data_as(C.POINTER(C.c_double)))
     return rc, obj.value, found.value, x
+
+
+def rc_tighten_many(probs, cutoffs, tol=1e-9):
+    """mvx_rc_tighten_many over solved capi.Prob handles of the gfx950 engine, cutoffs[t] the incumbent's objective for
+    handle t: one launch for all of them.  Returns (rc, [[(column, lb, ub), ...] per handle]), columns ascending."""
+    import numpy as np
+
+    k = len(probs)
+    n = probs[0].n if k else 0
+    hs = (C.c_void_p * max(1, k))(*[p.h for p in probs])
+    cut = np.array(list(cutoffs) or [0.0], dtype=np.float64)
+    cnt = np.zeros(max(1, k), dtype=np.int32)
+    cols = np.zeros(max(1, k * n), dtype=np.int32)
+    lb, ub = np.zeros(max(1, k * n)), np.zeros(max(1, k * n))
+    DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    rc = lib().mvx_rc_tighten_many(hs, k, cut.ctypes.data_as(DP), tol, cnt.ctypes.data_as(IP), cols.ctypes.data_as(IP), lb.ctypes.data_as(DP),
+                                   ub.ctypes.data_as(DP))
+    if rc != 0:
+        return rc, None
+    return rc, [[(int(cols[t * n + i]), float(lb[t * n + i]), float(ub[t * n + i])) for i in range(int(cnt[t]))] for t in range(k)]
+
+
+def rc_tighten_node(prob, cutoff, tol=1e-9, table=None):
+    """mvx_bnb_rc_tighten (the host twin, through `table`; None = the gfx950 engine's table) on one solved node.
+    Returns (rc, [(column, lb, ub), ...]), columns ascending."""
+    import numpy as np
+
+    n = prob.n
+    cnt = C.c_int(0)
+    cols = np.zeros(max(1, n), dtype=np.int32)
+    lb, ub = np.zeros(max(1, n)), np.zeros(max(1, n))
+    DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
+    rc = lib().mvx_bnb_rc_tighten(tptr, prob.h, cutoff, tol, C.byref(cnt), cols.ctypes.data_as(IP), lb.ctypes.data_as(DP), ub.ctypes.data_as(DP))
+    return rc, [(int(cols[i]), float(lb[i]), float(ub[i])) for i in range(cnt.value)]
+
+
+def tighten_cols_many(probs, lists):
+    """mvx_tighten_cols_many: handle t of the gfx950 engine takes the (column, lb, ub) entries of lists[t], all of them in
+    one launch.  Returns the call's code (0; -4 and nothing changed when an entry's column is basic or would move)."""
+    hs, off, flat = _flat(probs, [[e[0] for e in l] for l in lists])
+    import numpy as np
+
+    lb = np.array([e[1] for l in lists for e in l] or [0.0], dtype=np.float64)
+    ub = np.array([e[2] for l in lists for e in l] or [0.0], dtype=np.float64)
+    DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    return lib().mvx_tighten_cols_many(hs, len(probs), off.ctypes.data_as(IP), flat.ctypes.data_as(IP), lb.ctypes.data_as(DP), ub.ctypes.data_as(DP))
 
 
 def node_sample(root, count, quirks=0, table=None):

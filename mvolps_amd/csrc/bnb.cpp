@@ -33,6 +33,10 @@ extern "C" int mvx_get_basis(const mvx_prob *P, int *head, int *nb, int *flag) _
 extern "C" void mvx_init_smcp(mvx_smcp *parm) __attribute__((weak));
 extern "C" int mvx_round_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, int mode, double *obj, int *found, double *x)
     __attribute__((weak));
+extern "C" int mvx_rc_tighten_many(const mvx_prob *const *Ps, int count, const double *cutoff, double tol, int *cnt, int *cols, double *lb,
+                                   double *ub) __attribute__((weak));
+extern "C" int mvx_tighten_cols_many(mvx_prob *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub)
+    __attribute__((weak));
 
 namespace {
 
@@ -1097,6 +1101,114 @@ struct HeurBook {
   }
 };
 
+// ---- reduced-cost bound tightening (rc_fix, DESIGN.md "Reduced-cost tightening") ----
+
+struct RcEntry {
+  int col;
+  double lb, ub;
+};
+using RcList = std::vector<RcEntry>;
+
+// The rule on one solved node from its exported tableau and basis (the host twin of k_rcfix: same tests, the same correctly
+// rounded division): the changed columns in ascending order.
+static int rc_tighten_host(const mvx_lp_api *api, const void *P, double B, double tol, RcList &out) {
+  out.clear();
+  if (!P) return -1;
+  if (api->get_status(P) != MVX_OPT) return -3;
+  if (!api->get_tableau || !api->get_basis || !api->get_col_kind || !api->get_col_lb || !api->get_col_ub) return -5;
+  const int m = api->get_num_rows(P), n = api->get_num_cols(P);
+  const double sg = (api->get_obj_dir && api->get_obj_dir(P) == MVX_MIN) ? -1.0 : 1.0;
+  const double gap = sg * api->get_obj_val(P) - sg * B;
+  const double gap2 = gap + 1e-9 * std::max(1.0, std::fabs(B));
+  if (!(gap2 > 0.0)) return 0; // the node cannot beat the cutoff, or a NaN: no change
+  std::vector<double> T((size_t)(m + 1) * (size_t)(n + 1));
+  std::vector<int> head((size_t)m + 1), nb((size_t)n + 1), flag((size_t)n + 1);
+  if (api->get_basis(P, head.data(), nb.data(), flag.data()) != 0 || api->get_tableau(P, T.data()) != 0) return -5;
+  for (int q = 1; q <= n; q++) {
+    const int j = nb[(size_t)q] - m;
+    if (j < 1 || j > n || api->get_col_kind(P, j) == MVX_CV) continue;
+    const int f = flag[(size_t)q];
+    const double d = std::fabs(T[(size_t)q]);
+    if ((f != MVX_NL && f != MVX_NU) || !(d > tol)) continue;
+    const double lb = tab_bound(api->get_col_lb(P, j)), ub = tab_bound(api->get_col_ub(P, j));
+    const double at = f == MVX_NL ? lb : ub;
+    if (!(at == std::rint(at))) continue;
+    const double room = std::ceil(gap2 / d) - 1.0;
+    if (f == MVX_NL) {
+      const double nu = at + room;
+      if (nu < ub) out.push_back(RcEntry{j, lb, nu});
+    } else {
+      const double nl = at - room;
+      if (nl > lb) out.push_back(RcEntry{j, nl, ub});
+    }
+  }
+  std::sort(out.begin(), out.end(), [](const RcEntry &a, const RcEntry &b) { return a.col < b.col; });
+  return 0;
+}
+
+// One tree's tightening: the lists of a batch of solved nodes through rc_tighten_many (one call) when the table has it, else
+// the host twin per node; a batch of handles takes its lists through tighten_cols_many (one call), else set_col_bnds per
+// entry.  A list depends on its node's LP and the cutoff only.
+class RcFix {
+public:
+  explicit RcFix(const mvx_lp_api *api) : _api(api) {}
+  long long calls = 0, fixed = 0, tightened = 0;
+  // hs: solved (OPT) nodes, one cutoff for all of them; 0, or the failing call's code
+  int compute(const std::vector<const void *> &hs, double cutoff, std::vector<RcList> &out) const {
+    const size_t K = hs.size();
+    out.assign(K, RcList());
+    if (K == 0) return 0;
+    if (_api->rc_tighten_many) {
+      const size_t n = (size_t)_api->get_num_cols(hs[0]);
+      std::vector<double> cut(K, cutoff), lb(K * n), ub(K * n);
+      std::vector<int> cnt(K), cols(K * n);
+      const int rc = _api->rc_tighten_many(hs.data(), (int)K, cut.data(), 1e-9, cnt.data(), cols.data(), lb.data(), ub.data());
+      if (rc != 0) return rc;
+      for (size_t t = 0; t < K; t++)
+        for (int k = 0; k < cnt[t]; k++) out[t].push_back(RcEntry{cols[t * n + (size_t)k], lb[t * n + (size_t)k], ub[t * n + (size_t)k]});
+      return 0;
+    }
+    for (size_t t = 0; t < K; t++) {
+      const int rc = rc_tighten_host(_api, hs[t], cutoff, 1e-9, out[t]);
+      if (rc != 0) return rc;
+    }
+    return 0;
+  }
+  // the node branches: its list is booked
+  void book(const RcList &l) {
+    calls++;
+    for (const RcEntry &e : l) (e.lb == e.ub ? fixed : tightened)++;
+  }
+  // kids[k] takes *lists[k]
+  int apply(const std::vector<void *> &kids, const std::vector<const RcList *> &lists) const {
+    if (_api->tighten_cols_many) {
+      std::vector<int> off(1, 0), cols;
+      std::vector<double> lb, ub;
+      for (const RcList *l : lists) {
+        for (const RcEntry &e : *l) {
+          cols.push_back(e.col);
+          lb.push_back(e.lb);
+          ub.push_back(e.ub);
+        }
+        off.push_back((int)cols.size());
+      }
+      if (cols.empty()) return 0;
+      return _api->tighten_cols_many(kids.data(), (int)kids.size(), off.data(), cols.data(), lb.data(), ub.data());
+    }
+    for (size_t k = 0; k < kids.size(); k++)
+      for (const RcEntry &e : *lists[k]) _api->set_col_bnds(kids[k], e.col, e.lb == e.ub ? MVX_FX : MVX_DB, e.lb, e.ub);
+    return 0;
+  }
+  void store(mvx_bnb_result *res) const {
+    res->rc_calls = calls;
+    res->rc_fixed = fixed;
+    res->rc_tightened = tightened;
+  }
+
+private:
+  const mvx_lp_api *_api;
+};
+
 int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm, mvx_bnb_result *res) { // bs.cpp:54
   MVOLP::ParameterObj params(api, prob, prm);
   CutPool pool(api);
@@ -1121,6 +1233,7 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm,
   long long sb_lps = 0, sb_pivots = 0;
   Heuristic heur(api, prob, prm.heur);
   HeurBook hbook;
+  RcFix rcfix(api);
 
   while (!leafContainer.empty()) { // bs.cpp:96
     if (prm.max_nodes > 0 && count >= prm.max_nodes) {
@@ -1194,6 +1307,18 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm,
         }
         hbook.book(ho[0], node->oid, sg, bestLower, has_incumbent, incumbent_oid, xbest);
       }
+      // reduced-cost tightening against the incumbent in hand (a point the heuristic has just found counts), on the LP as
+      // solved; the list goes to both children
+      RcList rcl;
+      if (prm.rc_fix > 0 && has_incumbent && api->get_status(a) == MVX_OPT) {
+        std::vector<RcList> got;
+        if (rcfix.compute({a}, bestLower, got) != 0) {
+          rc_out = -2;
+          break;
+        }
+        rcl = std::move(got[0]);
+        rcfix.book(rcl);
+      }
       // var_strat 3 / 4 read the node's LP: they choose on it as solved, in front of the cut step
       int pick = 0;
       double bound = 0.0;
@@ -1240,6 +1365,10 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm,
         else
           api->set_col_bnds(S3->prob, pick, MVX_LO, std::ceil(bound), 0);
       }
+      if (!rcl.empty() && rcfix.apply({S2->prob, S3->prob}, {&rcl, &rcl}) != 0) {
+        rc_out = -2;
+        break;
+      }
       // bs.cpp:279 and :287 solve two independent clones; an engine with a batch entry runs them
       // side by side (identical results), otherwise one after the other as the reference does
       if (api->simplex_batch) {
@@ -1274,6 +1403,7 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm,
   res->sb_lps = sb_lps;
   res->sb_pivots = sb_pivots;
   hbook.store(res);
+  rcfix.store(res);
   return rc_out;
 }
 
@@ -1301,11 +1431,13 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
   bool stop = false;
   Heuristic heur(api, prob, prm.heur);
   HeurBook hbook;
+  RcFix rcfix(api);
 
   struct Branch {
     size_t slot;
     std::shared_ptr<MVOLP::NodeData> S2, S3;
     int before2, before3;
+    RcList rc; // rc_fix: the bound list both children take in front of their first solve
   };
   // One round of the loop.  Its child solves (phase C) run on a worker thread while the main thread replays
   // the next window, whose nodes were solved rounds ago: a breadth-first queue is longer than the window
@@ -1495,6 +1627,48 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
         hran[slot[k]] = 1;
       }
     }
+    // rc_fix: the lists of every node of the window that may branch, in one call against the incumbent as it stands (none
+    // yet: no call).  The replay uses a list only while the incumbent is the one it was computed with; once the replay has
+    // moved the incumbent, the lists of the nodes from there on are computed again in one further call (rc_from).
+    std::vector<char> rcwant;
+    std::vector<RcList> rclist;
+    std::vector<char> rchave;
+    double rc_cut = 0.0;
+    bool rc_fail = false;
+    auto rc_from = [&](size_t w0) {
+      std::vector<const void *> hh;
+      std::vector<size_t> slot;
+      for (size_t w = w0; w < W; w++)
+        if (rcwant[w]) {
+          hh.push_back(a[w]);
+          slot.push_back(w);
+        }
+      std::vector<RcList> got;
+      if (rcfix.compute(hh, bestLower, got) != 0) {
+        rc_fail = true;
+        return;
+      }
+      for (size_t k = 0; k < slot.size(); k++) {
+        rclist[slot[k]] = std::move(got[k]);
+        rchave[slot[k]] = 1;
+      }
+      rc_cut = bestLower;
+    };
+    if (prm.rc_fix > 0) {
+      if (info.empty()) {
+        info.resize(W);
+        for (size_t w = 0; w < W; w++) info[w] = printInfo(api, a[w], quirks);
+      }
+      rcwant.assign(W, 0);
+      rclist.assign(W, RcList());
+      rchave.assign(W, 0);
+      for (size_t w = 0; w < W; w++) rcwant[w] = info[w].first == 0 && api->get_status(a[w]) == MVX_OPT;
+      if (has_incumbent) rc_from(0);
+      if (rc_fail) {
+        rc_out = -2;
+        break;
+      }
+    }
     // B. replay in queue order
     Round cur;
     cur.node_events.resize(W);
@@ -1566,6 +1740,17 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
         // as it is -- but it marks the handle's solution mirrors stale, and reading one value afterwards is a device
         // export and a host round trip per branching node (~40 us, a tenth of the cut modes' run)
         if (prm.heur > 0 && hran[w]) hbook.book(hres[w], node->oid, sg, bestLower, has_incumbent, incumbent_oid, xbest);
+        RcList node_rc;
+        if (prm.rc_fix > 0 && has_incumbent && rcwant[w]) {
+          if (!rchave[w] || rc_cut != bestLower) rc_from(w); // the incumbent has moved since the lists were computed
+          if (rc_fail) {
+            rc_out = -2;
+            stop = true;
+            break;
+          }
+          node_rc = std::move(rclist[w]);
+          rcfix.book(node_rc);
+        }
         const int pick = prm.var_strat >= 3 ? choice[w].pick : params.pickVar(vars);
         const double bound = api->get_col_prim(aw, pick);
         if (prm.var_strat >= 3) {
@@ -1606,6 +1791,7 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
         }
         br.before2 = api->get_it_cnt(br.S2->prob);
         br.before3 = api->get_it_cnt(br.S3->prob);
+        br.rc = std::move(node_rc);
         branches.push_back(br);
         leafContainer.push_back(br.S2); // the queue order bs.cpp:297-298 gives them
         leafContainer.push_back(br.S3);
@@ -1619,6 +1805,23 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
       count++;
     }
     rec.sink = nullptr;
+    // rc_fix: every child of the round takes its parent's list in one call, behind its branching bound and in front of its
+    // first solve
+    if (prm.rc_fix > 0) {
+      std::vector<void *> kids;
+      std::vector<const RcList *> lists;
+      for (const Branch &br : branches)
+        if (!br.rc.empty()) {
+          kids.push_back(br.S2->prob);
+          kids.push_back(br.S3->prob);
+          lists.push_back(&br.rc);
+          lists.push_back(&br.rc);
+        }
+      if (!kids.empty() && rcfix.apply(kids, lists) != 0) {
+        rc_out = -2;
+        stop = true;
+      }
+    }
     tB += now() - t0;
     // C. every child of this round is an independent LP (bs.cpp:279,287): batched solves on worker threads; then, for
     // the children found infeasible (or unbounded), the re-solve bs.cpp:117 will ask for when they are
@@ -1703,6 +1906,7 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
   res->sb_lps = sb_lps;
   res->sb_pivots = sb_pivots;
   hbook.store(res);
+  rcfix.store(res);
   return rc_out;
 }
 
@@ -2078,6 +2282,12 @@ const mvx_lp_api g_hip_api = {
     mvx_round_many ? +[](const void *root, const void *const *Ps, int count, int mode, double *obj, int *found, double *x) {
       return mvx_round_many((const mvx_prob *)root, (const mvx_prob *const *)Ps, count, mode, obj, found, x);
     } : nullptr,
+    mvx_rc_tighten_many ? +[](const void *const *Ps, int count, const double *cutoff, double tol, int *cnt, int *cols, double *lb, double *ub) {
+      return mvx_rc_tighten_many((const mvx_prob *const *)Ps, count, cutoff, tol, cnt, cols, lb, ub);
+    } : nullptr,
+    mvx_tighten_cols_many ? +[](void *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub) {
+      return mvx_tighten_cols_many((mvx_prob *const *)Ps, count, off, cols, lb, ub);
+    } : nullptr,
 };
 
 } // namespace
@@ -2101,6 +2311,7 @@ void mvx_bnb_default_params(mvx_bnb_params *p) {
   p->sb_cands = 2;
   p->sb_iters = 4;
   p->heur = 0;
+  p->rc_fix = 0;
 }
 
 int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *params, mvx_bnb_result *res) {
@@ -2113,7 +2324,9 @@ int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *
   // var_strat 3 / 4 are not (yet) in the speculative best-bound window: refused, not run with another rule
   // heur > 0 needs the repaired mode: bug-compatible mode reproduces bs.cpp, which has no heuristic
   if (params->var_strat < 0 || params->var_strat > 4 || (params->var_strat >= 3 && params->best_window > 0) || params->heur < 0 ||
-      params->heur > 2 || (params->heur > 0 && params->reference_quirks != 0)) {
+      params->heur > 2 || (params->heur > 0 && params->reference_quirks != 0) || params->rc_fix < 0 || params->rc_fix > 1 ||
+      // rc_fix: the bound argument needs the repaired mode's children and cuts; not (yet) in the best-bound window
+      (params->rc_fix > 0 && (params->reference_quirks != 0 || params->best_window > 0))) {
     std::memset(res, 0, sizeof(*res));
     return -1;
   }
@@ -2185,6 +2398,22 @@ int mvx_bnb_round(const mvx_lp_api *api, const void *prob, const void *root, int
   const int rc = round_host_model(api, root, M);
   if (rc != 0) return rc;
   return round_host(api, M, prob, mode, obj, found, x);
+}
+
+int mvx_bnb_rc_tighten(const mvx_lp_api *api, const void *prob, double cutoff, double tol, int *cnt, int *cols, double *lb, double *ub) {
+  if (!api) api = &g_hip_api;
+  if (!prob || !cnt || !cols || !lb || !ub) return -1;
+  RcList l;
+  *cnt = 0;
+  const int rc = rc_tighten_host(api, prob, cutoff, tol, l);
+  if (rc != 0) return rc;
+  *cnt = (int)l.size();
+  for (size_t k = 0; k < l.size(); k++) {
+    cols[k] = l[k].col;
+    lb[k] = l[k].lb;
+    ub[k] = l[k].ub;
+  }
+  return 0;
 }
 
 int mvx_bnb_node_cuts(const mvx_lp_api *api, void *a, const mvx_bnb_params *params) {

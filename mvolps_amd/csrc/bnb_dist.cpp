@@ -105,6 +105,7 @@ extern "C" int mvx_branchAndBound_dist(const mvx_lp_api *api, const mvx_image_ap
   // var_strat 3 / 4 (branching on the node LP's penalties) and the rounding heuristic are not carried to several ranks yet:
   // refused
   if (prm.node_strat != 0 || dp.per_rank < 1 || prm.var_strat < 0 || prm.var_strat > 2 || prm.heur != 0) return MVX_EFAIL;
+  if (prm.rc_fix != 0) return MVX_EFAIL; // reduced-cost tightening is not carried to several ranks yet either
   const int rank = comm ? comm->rank : 0, world = comm ? comm->size : 1;
   const int per_rank = dp.per_rank;
   const int slack = dp.slack >= 0 ? dp.slack : std::max(1, per_rank / 4);

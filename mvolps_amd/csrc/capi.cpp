@@ -513,6 +513,13 @@ int mvx_branch_penalties_many(const mvx_prob *const *Ps, int count, const int *c
 int mvx_round_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, int mode, double *obj, int *found, double *x) {
   return mvx::engine_round_many(root, Ps, count, mode, obj, found, x);
 }
+int mvx_rc_tighten_many(const mvx_prob *const *Ps, int count, const double *cutoff, double tol, int *cnt, int *cols, double *lb,
+                        double *ub) {
+  return mvx::engine_rc_tighten_many(Ps, count, cutoff, tol, cnt, cols, lb, ub);
+}
+int mvx_tighten_cols_many(mvx_prob *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub) {
+  return mvx::engine_tighten_many(Ps, count, off, cols, lb, ub);
+}
 
 int mvx_device_count(void) { return mvx::device_count(); }
 int mvx_set_device(int dev) { return mvx::set_device(dev); }

@@ -87,6 +87,8 @@ void launch_gmi(const GmiArgs &a, hipStream_t);
 void launch_classify(const ClsArgs &a, hipStream_t);
 void launch_penalty(const PenArgs &a, hipStream_t);
 void launch_round(const RndArgs &a, hipStream_t);
+void launch_rcfix(const RcArgs &a, hipStream_t);
+void launch_tighten(const TightHandle *hs, const TightEntry *es, int count, hipStream_t);
 void launch_refresh_select(Ctl *, const int *tflag, int var, hipStream_t);
 size_t persist_lds_bytes(int m, int cpw);
 int persist_max_cpw();
@@ -215,6 +217,10 @@ struct Context {
   void *rnd_dev = nullptr, *rnd_host = nullptr;
   unsigned char *rnd_out_dev = nullptr;
   size_t rnd_dev_bytes = 0, rnd_host_bytes = 0;
+  // reduced-cost tightening (engine_rc_tighten_many, engine_tighten_many): device side and pinned host side of the upload
+  // and of k_rcfix's results
+  void *rcf_dev = nullptr, *rcf_host = nullptr;
+  size_t rcf_bytes = 0;
   // profiling (main context only)
   bool prof = false;
   double prof_update_ms = 0.0;
@@ -2497,6 +2503,185 @@ int engine_penalties_many(const mvx_prob *const *Ps, int count, const int *cols,
   std::memcpy(pen_up + k0, hb + o_pu, (size_t)total * 8);
   std::memcpy(arg_down + k0, hb + o_ad, (size_t)total * 4);
   std::memcpy(arg_up + k0, hb + o_au, (size_t)total * 4);
+  return 0;
+}
+
+// ------------------------------------------------------------------ reduced-cost tightening (k_rcfix, k_tighten)
+// caller holds main_mu; one device and one pinned buffer of at least `bytes` for both entries
+static bool rcf_reserve(Context &c, SolveCtx &sc, size_t bytes) {
+  if (bytes <= c.rcf_bytes) return true;
+  HIPCHECK(hipStreamSynchronize(sc.stream));
+  if (c.rcf_dev) HIPCHECK(hipFree(c.rcf_dev));
+  if (c.rcf_host) HIPCHECK(hipHostFree(c.rcf_host));
+  c.rcf_dev = c.rcf_host = nullptr;
+  c.rcf_bytes = 0;
+  const size_t want = bytes + bytes / 2;
+  if (hipMalloc(&c.rcf_dev, want) != hipSuccess) {
+    (void)hipGetLastError();
+    c.rcf_dev = nullptr;
+    g_last_error.store(MVX_ENOMEM);
+    return false;
+  }
+  if (hipHostMalloc(&c.rcf_host, want) != hipSuccess) {
+    (void)hipGetLastError();
+    HIPCHECK(hipFree(c.rcf_dev));
+    c.rcf_dev = c.rcf_host = nullptr;
+    g_last_error.store(MVX_ENOMEM);
+    return false;
+  }
+  c.rcf_bytes = want;
+  return true;
+}
+
+// Reduced-cost bound tightening of `count` solved handles (mvx_rc_tighten_many): one upload of the descriptors and the
+// kinds, one k_rcfix launch, one copy back; the per-position results are mapped to columns through the nvar mirror and
+// sorted by column.  Return codes: 0; -1 bad arguments (other column counts or kinds); -2 device out of memory; -3 a handle
+// whose status is not MVX_OPT.
+int engine_rc_tighten_many(const mvx_prob *const *Ps, int count, const double *cutoff, double tol, int *cnt, int *cols, double *lb,
+                           double *ub) {
+  if (count < 1 || !Ps || !cutoff || !cnt || !cols || !lb || !ub || !Ps[0]) return -1;
+  const mvx_prob *P0 = Ps[0];
+  const int n = P0->n;
+  for (int t = 0; t < count; t++) {
+    const mvx_prob *P = Ps[t];
+    if (!P || P->n != n || (P != P0 && P->kind != P0->kind)) return -1;
+  }
+  for (int t = 0; t < count; t++)
+    if (!Ps[t]->valid || Ps[t]->status != MVX_OPT) return -3;
+  std::vector<double> z((size_t)count);
+  for (int t = 0; t < count; t++) z[(size_t)t] = mvx_get_obj_val(Ps[t]); // the mirror; exports first when it is stale
+  Context &c = ctx();
+  MAIN_LOCK(c);
+  flush_copies(c); // a clone recorded into one of these slabs lands first
+  SolveCtx &sc = c.main;
+  size_t off = 0;
+  auto carve = [&](size_t bytes) {
+    size_t o = off;
+    off = align_up(off + bytes, 256);
+    return o;
+  };
+  // up: [descriptors][kind]; back: [code][val]
+  const size_t o_nodes = carve((size_t)count * sizeof(RcNode)), o_kind = carve((size_t)(n + 1) * 4), up_bytes = off;
+  const size_t o_code = carve((size_t)count * (size_t)(n + 1) * 4), o_val = carve((size_t)count * (size_t)(n + 1) * 8);
+  if (!rcf_reserve(c, sc, off)) return -2;
+  unsigned char *hb = (unsigned char *)c.rcf_host, *db = (unsigned char *)c.rcf_dev;
+  RcNode *h_nodes = (RcNode *)(hb + o_nodes);
+  for (int t = 0; t < count; t++) {
+    const mvx_prob *P = Ps[t];
+    const double sg = P->dir == MVX_MIN ? -1.0 : 1.0, B = cutoff[t];
+    const double gap = sg * z[(size_t)t] - sg * B;
+    RcNode &nd = h_nodes[t];
+    nd.T = P->d_T; nd.nvar = P->d_nvar; nd.nflag = P->d_nflag; nd.nlb = P->d_nlb; nd.nub = P->d_nub;
+    nd.gap2 = gap + 1e-9 * std::max(1.0, std::fabs(B));
+    nd.m = P->m; nd.pad = 0;
+  }
+  std::memcpy(hb + o_kind, P0->kind.data(), (size_t)(n + 1) * 4);
+  HIPCHECK(hipMemcpyAsync(db, hb, up_bytes, hipMemcpyHostToDevice, sc.stream));
+  RcArgs a;
+  a.nodes = (const RcNode *)(db + o_nodes);
+  a.kind = (const int *)(db + o_kind);
+  a.code = (int *)(db + o_code);
+  a.val = (double *)(db + o_val);
+  a.tol = tol; a.n = n; a.count = count;
+  launch_rcfix(a, sc.stream);
+  HIPCHECK(hipMemcpyAsync(hb + o_code, db + o_code, off - o_code, hipMemcpyDeviceToHost, sc.stream));
+  HIPCHECK(hipStreamSynchronize(sc.stream));
+  const int *h_code = (const int *)(hb + o_code);
+  const double *h_val = (const double *)(hb + o_val);
+  std::vector<std::pair<int, int>> hit; // (column, position)
+  for (int t = 0; t < count; t++) {
+    const mvx_prob *P = Ps[t];
+    const int *cd = h_code + (size_t)t * (size_t)(n + 1);
+    const double *vl = h_val + (size_t)t * (size_t)(n + 1);
+    hit.clear();
+    for (int q = 1; q <= n; q++)
+      if (cd[q] != 0) hit.emplace_back(P->nvar[(size_t)q] - P->m, q);
+    std::sort(hit.begin(), hit.end());
+    cnt[t] = (int)hit.size();
+    for (size_t k = 0; k < hit.size(); k++) {
+      const int j = hit[k].first, q = hit[k].second;
+      const size_t o = (size_t)t * (size_t)n + k;
+      cols[o] = j;
+      lb[o] = cd[q] == 2 ? vl[q] : P->clb[(size_t)j];
+      ub[o] = cd[q] == 1 ? vl[q] : P->cub[(size_t)j];
+    }
+  }
+  return 0;
+}
+
+// The bound lists of many handles with one launch (mvx_tighten_cols_many): every entry is checked first (-1 / -4 change
+// nothing), then the host model, the nflag mirror and the status of each handle are edited as mvx_set_col_bnds would,
+// and one k_tighten launch writes every position's bounds and status on the device.
+int engine_tighten_many(mvx_prob *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub) {
+  if (count < 0 || (count > 0 && (!Ps || !off))) return -1;
+  if (count == 0) return 0;
+  if (off[0] < 0) return -1;
+  for (int t = 0; t < count; t++)
+    if (!Ps[t] || off[t + 1] < off[t]) return -1;
+  const int k0 = off[0], total = off[count] - k0;
+  if (total == 0) return 0;
+  if (!cols || !lb || !ub) return -1;
+  for (int t = 0; t < count; t++) {
+    int prev = 0;
+    for (int k = off[t]; k < off[t + 1]; k++) {
+      const int j = cols[k];
+      if (j < 1 || j > Ps[t]->n || j <= prev || !std::isfinite(lb[k]) || !std::isfinite(ub[k]) || lb[k] > ub[k]) return -1;
+      prev = j;
+    }
+  }
+  std::vector<int> flags((size_t)total, MVX_NS);
+  int nent = 0;
+  for (int t = 0; t < count; t++) {
+    const mvx_prob *P = Ps[t];
+    if (!P->valid) continue;
+    for (int k = off[t]; k < off[t + 1]; k++) {
+      const int j = cols[k], pos = P->pos[(size_t)(P->m + j)];
+      if (pos > 0) return -4;
+      const int jj = -pos;
+      const int flag = lb[k] == ub[k] ? MVX_NS : (P->nflag[(size_t)jj] == MVX_NU ? MVX_NU : MVX_NL);
+      if (nb_value(flag, lb[k], ub[k]) != nb_value(P->nflag[(size_t)jj], P->clb[(size_t)j], P->cub[(size_t)j])) return -4;
+      flags[(size_t)(k - k0)] = flag;
+      nent++;
+    }
+  }
+  Context &c = ctx();
+  MAIN_LOCK(c);
+  SolveCtx &sc = c.main;
+  const size_t o_hs = 0, o_es = align_up((size_t)count * sizeof(TightHandle), 256);
+  const size_t bytes = o_es + (size_t)nent * sizeof(TightEntry);
+  if (nent > 0 && !rcf_reserve(c, sc, bytes)) return -2;
+  TightHandle *h_hs = nent > 0 ? (TightHandle *)((unsigned char *)c.rcf_host + o_hs) : nullptr;
+  TightEntry *h_es = nent > 0 ? (TightEntry *)((unsigned char *)c.rcf_host + o_es) : nullptr;
+  int e = 0;
+  for (int t = 0; t < count; t++) {
+    mvx_prob *P = Ps[t];
+    if (h_hs) h_hs[t] = TightHandle{P->d_nlb, P->d_nub, P->d_nflag};
+    for (int k = off[t]; k < off[t + 1]; k++) {
+      const int j = cols[k];
+      P->ctype[(size_t)j] = lb[k] == ub[k] ? MVX_FX : MVX_DB;
+      P->clb[(size_t)j] = lb[k];
+      P->cub[(size_t)j] = ub[k];
+      if (P->valid) {
+        const int jj = -P->pos[(size_t)(P->m + j)];
+        P->nflag[(size_t)jj] = flags[(size_t)(k - k0)];
+        h_es[e++] = TightEntry{lb[k], ub[k], t, jj, flags[(size_t)(k - k0)], 0};
+      }
+    }
+    if (off[t + 1] > off[t]) {
+      if (P->valid) {
+        P->sol_fresh = false;
+        P->fresh_rows = -1;
+      }
+      P->status = MVX_UNDEF;
+    }
+  }
+  if (nent > 0) {
+    flush_copies(c); // a recorded clone INTO one of these slabs must land before the edits do
+    unsigned char *db = (unsigned char *)c.rcf_dev;
+    HIPCHECK(hipMemcpyAsync(db, c.rcf_host, bytes, hipMemcpyHostToDevice, sc.stream));
+    launch_tighten((const TightHandle *)(db + o_hs), (const TightEntry *)(db + o_es), nent, sc.stream);
+    HIPCHECK(hipStreamSynchronize(sc.stream)); // the pinned side is free for the next call
+  }
   return 0;
 }
 

@@ -40,6 +40,11 @@ int engine_penalties_many(const mvx_prob *const *Ps, int count, const int *cols,
                           double *pen_up, int *arg_down, int *arg_up);
 // primal rounding heuristic on `count` solved handles against root's model, one launch (k_round); see engine.cpp
 int engine_round_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, int mode, double *obj, int *found, double *x);
+// reduced-cost bound tightening of `count` solved handles, one launch (k_rcfix), and the bound lists of many handles applied
+// with one launch (k_tighten); see engine.cpp
+int engine_rc_tighten_many(const mvx_prob *const *Ps, int count, const double *cutoff, double tol, int *cnt, int *cols, double *lb,
+                           double *ub);
+int engine_tighten_many(mvx_prob *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub);
 
 long long engine_pack_size(const mvx_prob *P, int m_base);
 int engine_pack(const mvx_prob *P, int m_base, void *dev_buf);

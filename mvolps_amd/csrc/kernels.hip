@@ -4340,6 +4340,68 @@ void launch_round(const RndArgs &a, hipStream_t s) {
   hipLaunchKernelGGL(k_round, dim3((unsigned)a.count), dim3(256), 0, s, a);
 }
 
+// ---------------------------------------------------------------------------- k_rcfix / k_tighten
+// Reduced-cost bound tightening (mvx_rc_tighten_many, DESIGN.md "Reduced-cost tightening"), one workgroup per handle.  Row 0
+// and the position-indexed nvar / nflag / nlb / nub are streamed once, coalesced; each non-basic position is decided on its
+// own -- no reduction, so nothing depends on an order -- and written exactly once: code 0 (no change), 1 (upper bound
+// becomes val) or 2 (lower bound becomes val).  The host maps positions to columns through its nvar mirror.  The quotient
+// is the correctly rounded one (xdiv): the host twin's bits.
+__global__ __launch_bounds__(256) void k_rcfix(RcArgs a) {
+  const int t = (int)blockIdx.x;
+  const RcNode nd = a.nodes[t];
+  int *code = a.code + (size_t)t * (size_t)(a.n + 1);
+  double *val = a.val + (size_t)t * (size_t)(a.n + 1);
+  const double gap2 = nd.gap2;
+  const bool live = gap2 > 0.0; // a NaN or a cutoff the node cannot beat: no change anywhere
+  for (int q = 1 + TIDX; q <= a.n; q += 256) {
+    int cd = 0;
+    double v = 0.0;
+    const int var = nd.nvar[q];
+    const int j = var - nd.m;
+    if (live && j >= 1 && j <= a.n && a.kind[j] != MVX_CV) {
+      const int f = nd.nflag[q];
+      const double d = fabs(nd.T[q]);
+      if ((f == MVX_NL || f == MVX_NU) && d > a.tol) {
+        const double lb = nd.nlb[q], ub = nd.nub[q];
+        const double at = f == MVX_NL ? lb : ub;
+        if (at == rint(at)) {
+          const double room = __dsub_rn(ceil(xdiv(gap2, d)), 1.0);
+          if (f == MVX_NL) {
+            v = __dadd_rn(at, room);
+            if (v < ub) cd = 1;
+          } else {
+            v = __dsub_rn(at, room);
+            if (v > lb) cd = 2;
+          }
+        }
+      }
+    }
+    code[q] = cd;
+    val[q] = v;
+  }
+}
+
+void launch_rcfix(const RcArgs &a, hipStream_t s) {
+  hipLaunchKernelGGL(k_rcfix, dim3((unsigned)a.count), dim3(256), 0, s, a);
+}
+
+// The bound lists of many handles in one launch (mvx_tighten_cols_many): a thread per (handle, position) entry writes the
+// position's bounds and status.  The host only sends edits that leave the variable's resting value where it is, so column 0
+// and the tableau stay as they are.
+__global__ __launch_bounds__(256) void k_tighten(const TightHandle *hs, const TightEntry *es, int count) {
+  const int k = (int)blockIdx.x * 256 + TIDX;
+  if (k >= count) return;
+  const TightEntry e = es[k];
+  const TightHandle h = hs[e.h];
+  h.nlb[e.q] = e.lb;
+  h.nub[e.q] = e.ub;
+  h.nflag[e.q] = e.flag;
+}
+
+void launch_tighten(const TightHandle *hs, const TightEntry *es, int count, hipStream_t s) {
+  hipLaunchKernelGGL(k_tighten, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, hs, es, count);
+}
+
 // ------------------------------------------------------------------ launch wrappers
 
 // tuning knobs of the streamed update (mvx_set_tuning; defaults are the measured best)

@@ -65,6 +65,8 @@ int main(int argc, char **argv) {
               << "    0. off (default)\n"
               << "    1. round the LP values (away from the rows' locks) and keep the point when it is feasible\n"
               << "    2. as 1, then raise the columns greedily along the objective while every row allows it\n"
+              << "  --rcfix         with --repaired (not with --best-window): once an incumbent exists, tighten the bounds of non-basic\n"
+              << "                  integer columns from their reduced costs on every branching node; both children inherit them\n"
               << "Help:\n  -h/--help\n";
     return 0;
   }
@@ -124,6 +126,7 @@ int main(int argc, char **argv) {
     }
   }
   if (input.CMDOptionExists("--repaired")) params.reference_quirks = 0;
+  if (input.CMDOptionExists("--rcfix")) params.rc_fix = 1;
   if (input.CMDOptionExists("--cut-select")) params.cut_select = std::atoi(input.getCMDOption("--cut-select").c_str());
   if (input.CMDOptionExists("--window")) params.window = std::atoi(input.getCMDOption("--window").c_str());
   if (input.CMDOptionExists("--best-window")) params.best_window = std::atoi(input.getCMDOption("--best-window").c_str());
@@ -134,8 +137,9 @@ int main(int argc, char **argv) {
   mvx_bnb_result res;
   const int brc = mvx_branchAndBound(nullptr, prob, &params, &res);
   if (brc == -1) {
-    std::fprintf(stderr, "-vs %d / --heur %d are not supported with these options (-vs 3 / 4: not with --best-window; --heur: only "
-                 "with --repaired)\n", params.var_strat, params.heur);
+    std::fprintf(stderr, "-vs %d / --heur %d%s are not supported with these options (-vs 3 / 4: not with --best-window; --heur: only "
+                 "with --repaired; --rcfix: only with --repaired and without --best-window)\n", params.var_strat, params.heur,
+                 params.rc_fix ? " / --rcfix" : "");
     mvx_delete_prob(prob);
     return -1;
   }
@@ -150,6 +154,8 @@ int main(int argc, char **argv) {
   if (verbose && params.heur > 0)
     std::printf("Rounding heuristic: %lld nodes, %lld feasible, %lld improved the incumbent%s\n", res.heur_calls, res.heur_found,
                 res.heur_improved, res.incumbent_heur ? " (the final incumbent is one of them)" : "");
+  if (verbose && params.rc_fix > 0)
+    std::printf("Reduced-cost tightening: %lld nodes, %lld columns fixed, %lld tightened\n", res.rc_calls, res.rc_fixed, res.rc_tightened);
   const int limit = res.hit_limit || brc != 0;
   mvx_bnb_free_result(&res);
   mvx_delete_prob(prob);

@@ -289,6 +289,37 @@ struct RndArgs {
   int n, m0, ldm, mode, count, pad;
 };
 
+// one handle of a reduced-cost tightening launch (k_rcfix, mvx_rc_tighten_many): row 0 of its tableau and its non-basic
+// arrays; gap2 = sg*z - sg*cutoff plus the slack, computed by the host from the handle's objective mirror
+struct RcNode {
+  const double *T; // row 0: reduced costs by non-basic position
+  const int *nvar, *nflag;
+  const double *nlb, *nub;
+  double gap2;
+  int m, pad; // rows of this handle: position q holds structural column nvar[q] - m
+};
+
+// arguments of k_rcfix: `count` handles with the same n columns and kinds.  Results by non-basic position (every position
+// is written exactly once): code 0 no change, 1 the upper bound becomes val, 2 the lower bound becomes val
+struct RcArgs {
+  const RcNode *nodes; // [count]
+  const int *kind;     // [n+1] column kinds (MVX_CV / MVX_IV)
+  int *code;           // [count][n+1]
+  double *val;         // [count][n+1]
+  double tol;
+  int n, count;
+};
+
+// one bound edit of a k_tighten launch (mvx_tighten_cols_many): non-basic position q of handle h takes (lb, ub, flag)
+struct TightHandle {
+  double *nlb, *nub;
+  int *nflag;
+};
+struct TightEntry {
+  double lb, ub;
+  int h, q, flag, pad;
+};
+
 // shared immutable matrix row (1-based, n+1 doubles)
 using RowPtr = std::shared_ptr<std::vector<double>>;
 
