@@ -105,6 +105,16 @@ void launch_export(Ctl *, unsigned char *stage, int m, int n, int force, hipStre
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// lays pieces out one after the other on 256-byte boundaries: carve(bytes) is the piece's offset, `off` the total so far
+struct Carver {
+  size_t off = 0;
+  size_t operator()(size_t bytes) {
+    size_t o = off;
+    off = align_up(off + bytes, 256);
+    return o;
+  }
+};
+
 // ------------------------------------------------------------------------------ context
 // One solve context = one HIP stream with its own control block, scratch and staging.  The main
 // context serves every single-handle call; mvx_simplex_batch has its own (BatchCtx below).
@@ -181,6 +191,17 @@ struct SlabCache {
   size_t idle_bytes = 0; // bytes held by idle slabs, arena slabs included
 };
 
+// The one device buffer + pinned host buffer of the batched node entries (GMI cuts, classification, penalties, rounding,
+// rc-tightening, tighten): descriptors go up through `host`, results come back into it -- written there by the kernel
+// itself through `host_dev`, the pinned buffer's device address (null when it has none), or by a copy out of `dev`.
+// Sharing rule: the pointers are valid from node_scratch_reserve until the entry's closing stream synchronise, under
+// main_mu; an entry that holds pointers into it calls no other entry.
+struct NodeScratch {
+  void *dev = nullptr, *host = nullptr;
+  unsigned char *host_dev = nullptr;
+  size_t dev_bytes = 0, host_bytes = 0;
+};
+
 struct Context {
   int dev = -1;
   bool aux_ready = false;
@@ -198,29 +219,7 @@ struct Context {
   // branching with only host-side work in between, so they leave as ONE k_copy_many launch when the next entry point
   // that touches device data arrives (flush_copies)
   std::vector<CopyJob> copies;
-  // GMI cut generation (engine_gmi_cuts): device buffers for `work`, the cuts, right-hand sides, flags, row positions
-  // and column kinds, and the pinned host side of the transfers
-  void *gmi_dev = nullptr, *gmi_host = nullptr;
-  size_t gmi_bytes = 0;
-  // classification (engine_classify_many): device side of the descriptors, objective, kinds and the value scratch; the
-  // pinned host buffer holds the uploaded part and the results, which k_classify writes straight into it when the
-  // buffer has a device address (cls_out_dev), else into the device buffer behind the scratch and one copy brings them
-  void *cls_dev = nullptr, *cls_host = nullptr;
-  unsigned char *cls_out_dev = nullptr;
-  size_t cls_dev_bytes = 0, cls_host_bytes = 0;
-  // branching penalties (engine_penalties_many): device copy of the descriptors, pinned host side of the upload and the
-  // results (k_penalty writes them straight into it when it has a device address, pen_out_dev)
-  void *pen_dev = nullptr, *pen_host = nullptr;
-  unsigned char *pen_out_dev = nullptr;
-  size_t pen_dev_bytes = 0, pen_host_bytes = 0;
-  // rounding heuristic (engine_round_many): device descriptors and row scratch, pinned upload / results
-  void *rnd_dev = nullptr, *rnd_host = nullptr;
-  unsigned char *rnd_out_dev = nullptr;
-  size_t rnd_dev_bytes = 0, rnd_host_bytes = 0;
-  // reduced-cost tightening (engine_rc_tighten_many, engine_tighten_many): device side and pinned host side of the upload
-  // and of k_rcfix's results
-  void *rcf_dev = nullptr, *rcf_host = nullptr;
-  size_t rcf_bytes = 0;
+  NodeScratch nodes;
   // profiling (main context only)
   bool prof = false;
   double prof_update_ms = 0.0;
@@ -284,6 +283,48 @@ static Context &ctx() {
   return *c;
 }
 
+// Binds the context's device for the calling thread, once per thread: clones, node entries and solution queries come
+// from the B&B driver's helper threads too.
+static void bind_device(const Context &c) {
+  static thread_local bool bound = false;
+  if (bound) return;
+  HIPCHECK(hipSetDevice(c.dev));
+  bound = true;
+}
+
+// Caller holds main_mu.  Grows c.nodes (see NodeScratch for the sharing rule) to at least dev_bytes / host_bytes, each
+// side on its own and to 1.5 x the request; a call that fits costs two comparisons and does not touch the stream.
+// false: out of memory -- the arena is left empty, mvx_last_error() reads MVX_ENOMEM, the entry returns -2.
+static bool node_scratch_reserve(Context &c, size_t dev_bytes, size_t host_bytes) {
+  NodeScratch &s = c.nodes;
+  if (dev_bytes <= s.dev_bytes && host_bytes <= s.host_bytes) return true;
+  HIPCHECK(hipStreamSynchronize(c.main.stream));
+  bool ok = true;
+  if (dev_bytes > s.dev_bytes) {
+    if (s.dev) HIPCHECK(hipFree(s.dev));
+    s.dev_bytes = dev_bytes + dev_bytes / 2;
+    ok = hipMalloc(&s.dev, s.dev_bytes) == hipSuccess;
+    if (!ok) s.dev = nullptr;
+  }
+  if (ok && host_bytes > s.host_bytes) {
+    if (s.host) HIPCHECK(hipHostFree(s.host));
+    s.host_dev = nullptr;
+    s.host_bytes = host_bytes + host_bytes / 2;
+    ok = hipHostMalloc(&s.host, s.host_bytes) == hipSuccess;
+    void *dp = nullptr;
+    if (!ok) s.host = nullptr;
+    else if (hipHostGetDevicePointer(&dp, s.host, 0) == hipSuccess && dp) s.host_dev = (unsigned char *)dp;
+    else (void)hipGetLastError();
+  }
+  if (ok) return true;
+  (void)hipGetLastError();
+  if (s.dev) HIPCHECK(hipFree(s.dev));
+  if (s.host) HIPCHECK(hipHostFree(s.host));
+  s = NodeScratch();
+  g_last_error.store(MVX_ENOMEM);
+  return false;
+}
+
 static void sync_batch_stream();
 static void flush_copies(Context &c);
 void sync_stream() {
@@ -322,13 +363,8 @@ static void ensure_scratch(SolveCtx &sc, int m_cap, int ld) {
   if (sc.h_stage) HIPCHECK(hipHostFree(sc.h_stage));
   sc.d_stage = nullptr;
   const int nchunks = (mc + ROWCOMB_CHUNK - 1) / ROWCOMB_CHUNK + 1;
-  size_t off = 0;
-  auto carve = [&](size_t bytes) {
-    size_t o = off;
-    off = align_up(off + bytes, 256);
-    return o;
-  };
-  size_t o_colq = carve((size_t)(mc + 1) * 8), o_srow = carve((size_t)l * 8), o_cost1 = carve((size_t)l * 8);
+  Carver carve;
+  size_t o_colq =carve((size_t)(mc + 1) * 8), o_srow = carve((size_t)l * 8), o_cost1 = carve((size_t)l * 8);
   size_t o_wts = carve((size_t)(mc + 1) * 8), o_rcb = carve((size_t)l * 8), o_g = carve((size_t)(mc + 1) * 4);
   size_t o_part = carve((size_t)nchunks * l * 8);
   size_t o_cx0 = carve((size_t)(mc + 1) * 8), o_cx1 = carve((size_t)(mc + 1) * 8);
@@ -352,8 +388,8 @@ static void ensure_scratch(SolveCtx &sc, int m_cap, int ld) {
   const size_t pps = align_up((size_t)chain_ncb(l) + 1, 32), rps = align_up((size_t)chain_nrb(mc) + 1, 32);
   const size_t o_betab = carve((size_t)(mc + 1) * 8), o_ppart = carve(8 * pps * 8), o_rpart = carve(4 * rps * 8);
   const size_t o_zeros = carve((size_t)std::max(l, mc + 1) * 8 + 256);
-  HIPCHECK(hipMalloc(&sc.scratch, off));
-  HIPCHECK(hipMemsetAsync(sc.scratch, 0, off, sc.stream));
+  HIPCHECK(hipMalloc(&sc.scratch, carve.off));
+  HIPCHECK(hipMemsetAsync(sc.scratch, 0, carve.off, sc.stream));
   unsigned char *b = (unsigned char *)sc.scratch;
   sc.d_colq = (double *)(b + o_colq);
   sc.d_srow = (double *)(b + o_srow);
@@ -426,13 +462,8 @@ struct SlabLayout {
 };
 static SlabLayout slab_layout(int m_cap, int ld) {
   SlabLayout L;
-  size_t off = 0;
-  auto carve = [&](size_t bytes) {
-    size_t o = off;
-    off = align_up(off + bytes, 256);
-    return o;
-  };
-  L.o_T = carve((size_t)(m_cap + 1) * ld * 8);
+  Carver carve;
+  L.o_T =carve((size_t)(m_cap + 1) * ld * 8);
   L.o_bvar = carve((size_t)(m_cap + 1) * 4);
   L.o_blb = carve((size_t)(m_cap + 1) * 8);
   L.o_bub = carve((size_t)(m_cap + 1) * 8);
@@ -440,7 +471,7 @@ static SlabLayout slab_layout(int m_cap, int ld) {
   L.o_nflag = carve((size_t)ld * 4);
   L.o_nlb = carve((size_t)ld * 8);
   L.o_nub = carve((size_t)ld * 8);
-  L.total = off;
+  L.total = carve.off;
   return L;
 }
 
@@ -833,6 +864,7 @@ void refresh_solution(const mvx_prob *Pc) {
   mvx_prob *P = const_cast<mvx_prob *>(Pc);
   if (!P->valid || P->sol_fresh) return;
   Context &c = ctx();
+  bind_device(c);
   MAIN_LOCK(c);
   flush_copies(c);
   SolveCtx &sc = c.main;
@@ -2051,13 +2083,7 @@ void engine_copy(mvx_prob *dst, const mvx_prob *src) {
     return;
   }
   Context &c = ctx();
-  {
-    static thread_local bool bound = false; // clones are made from the B&B driver's helper threads too
-    if (!bound) {
-      HIPCHECK(hipSetDevice(c.dev));
-      bound = true;
-    }
-  }
+  bind_device(c);
   MAIN_LOCK(c);
   SolveCtx &sc = c.main;
   void *slab = slab_alloc(c, src->slab_bytes);
@@ -2193,6 +2219,7 @@ static bool dev_matrix_current(const mvx_prob *P) {
 static int gmi_core(mvx_prob *const *Ps, int mode, const int *cols, int count, double *vals, double *rhs, int *ok) {
   if (count < 1) return -1;
   Context &c = ctx();
+  bind_device(c);
   MAIN_LOCK(c);
   flush_copies(c);
   SolveCtx &sc = c.main;
@@ -2226,32 +2253,13 @@ static int gmi_core(mvx_prob *const *Ps, int mode, const int *cols, int count, d
   for (int t = 0; t < count; t++) Ps[t]->dmat = Dp; // (their children inherit it)
   const DevMatrix &D = *Dp;
   const size_t wld = align_up((size_t)mmax + n + 1, 32), old = align_up((size_t)n + 1, 32);
-  size_t off = 0;
-  auto carve = [&](size_t bytes) {
-    size_t o = off;
-    off = align_up(off + bytes, 256);
-    return o;
-  };
+  Carver carve;
   // [node descriptors x count][kind i32 x (n+1)] go up; [rhs][ok][out][work] come back (work: the auxiliaries' part only)
-  const size_t o_nodes = carve((size_t)count * sizeof(GmiNode)), o_kind = carve((size_t)(n + 1) * 4), up_bytes = off;
+  const size_t o_nodes = carve((size_t)count * sizeof(GmiNode)), o_kind = carve((size_t)(n + 1) * 4), up_bytes = carve.off;
   const size_t o_rhs = carve((size_t)count * 8), o_ok = carve((size_t)count * 4);
   const size_t o_out = carve((size_t)count * old * 8), o_work = carve((size_t)count * wld * 8);
-  if (off > c.gmi_bytes) {
-    HIPCHECK(hipStreamSynchronize(sc.stream));
-    if (c.gmi_dev) HIPCHECK(hipFree(c.gmi_dev));
-    if (c.gmi_host) HIPCHECK(hipHostFree(c.gmi_host));
-    c.gmi_dev = c.gmi_host = nullptr;
-    c.gmi_bytes = 0;
-    const size_t want = off + off / 2;
-    if (hipMalloc(&c.gmi_dev, want) != hipSuccess) {
-      (void)hipGetLastError();
-      g_last_error.store(MVX_ENOMEM);
-      return -2;
-    }
-    HIPCHECK(hipHostMalloc(&c.gmi_host, want));
-    c.gmi_bytes = want;
-  }
-  unsigned char *hb = (unsigned char *)c.gmi_host, *db = (unsigned char *)c.gmi_dev;
+  if (!node_scratch_reserve(c, carve.off, carve.off)) return -2;
+  unsigned char *hb = (unsigned char *)c.nodes.host, *db = (unsigned char *)c.nodes.dev;
   GmiNode *h_nodes = (GmiNode *)(hb + o_nodes);
   int *h_kind = (int *)(hb + o_kind);
   bool own_rows = false;
@@ -2335,51 +2343,20 @@ int engine_classify_many(const mvx_prob *const *Ps, int count, int quirks, int *
     if (!P->valid || P->n != n || (P != P0 && (P->c != P0->c || P->kind != P0->kind))) return -1;
   }
   Context &c = ctx();
+  bind_device(c);
   MAIN_LOCK(c);
   flush_copies(c); // a clone recorded into one of these slabs lands first
   SolveCtx &sc = c.main;
-  size_t off = 0;
-  auto carve = [&](size_t bytes) {
-    size_t o = off;
-    off = align_up(off + bytes, 256);
-    return o;
-  };
+  Carver carve;
   // up: [descriptors][c][kind]; out: [status][nviol][viol][xviol]; device only: [x scratch]
   const size_t o_nodes = carve((size_t)count * sizeof(ClsNode)), o_c = carve((size_t)(n + 1) * 8), o_kind = carve((size_t)(n + 1) * 4);
-  const size_t up_bytes = off;
+  const size_t up_bytes = carve.off;
   const size_t o_st = carve((size_t)count * 4), o_nv = carve((size_t)count * 4), o_viol = carve((size_t)count * cap * 4),
                o_xv = carve((size_t)count * cap * 8);
-  const size_t host_bytes = off;
+  const size_t host_bytes = carve.off;
   const size_t o_x = carve((size_t)count * (n + 1) * 8);
-  const size_t dev_bytes = off;
-  if (dev_bytes > c.cls_dev_bytes || host_bytes > c.cls_host_bytes) {
-    HIPCHECK(hipStreamSynchronize(sc.stream));
-    if (c.cls_dev) HIPCHECK(hipFree(c.cls_dev));
-    if (c.cls_host) HIPCHECK(hipHostFree(c.cls_host));
-    c.cls_dev = c.cls_host = nullptr;
-    c.cls_out_dev = nullptr;
-    c.cls_dev_bytes = c.cls_host_bytes = 0;
-    const size_t want_dev = dev_bytes + dev_bytes / 2, want_host = host_bytes + host_bytes / 2;
-    if (hipMalloc(&c.cls_dev, want_dev) != hipSuccess) {
-      (void)hipGetLastError();
-      c.cls_dev = nullptr;
-      g_last_error.store(MVX_ENOMEM);
-      return -2;
-    }
-    if (hipHostMalloc(&c.cls_host, want_host) != hipSuccess) {
-      (void)hipGetLastError();
-      HIPCHECK(hipFree(c.cls_dev));
-      c.cls_dev = c.cls_host = nullptr;
-      g_last_error.store(MVX_ENOMEM);
-      return -2;
-    }
-    void *dp = nullptr;
-    if (hipHostGetDevicePointer(&dp, c.cls_host, 0) == hipSuccess && dp) c.cls_out_dev = (unsigned char *)dp;
-    else (void)hipGetLastError();
-    c.cls_dev_bytes = want_dev;
-    c.cls_host_bytes = want_host;
-  }
-  unsigned char *hb = (unsigned char *)c.cls_host, *db = (unsigned char *)c.cls_dev;
+  if (!node_scratch_reserve(c, carve.off, host_bytes)) return -2;
+  unsigned char *hb = (unsigned char *)c.nodes.host, *db = (unsigned char *)c.nodes.dev;
   ClsNode *h_nodes = (ClsNode *)(hb + o_nodes);
   for (int t = 0; t < count; t++) {
     const mvx_prob *P = Ps[t];
@@ -2390,7 +2367,7 @@ int engine_classify_many(const mvx_prob *const *Ps, int count, int quirks, int *
   std::memcpy(hb + o_c, P0->c.data(), (size_t)(n + 1) * 8);
   std::memcpy(hb + o_kind, P0->kind.data(), (size_t)(n + 1) * 4);
   HIPCHECK(hipMemcpyAsync(db, hb, up_bytes, hipMemcpyHostToDevice, sc.stream));
-  unsigned char *ob = c.cls_out_dev ? c.cls_out_dev : db; // where the results go: the pinned buffer itself, or the device one
+  unsigned char *ob = c.nodes.host_dev ? c.nodes.host_dev : db; // where the results go: the pinned buffer itself, or the device one
   ClsArgs a;
   a.nodes = (const ClsNode *)(db + o_nodes);
   a.c = (const double *)(db + o_c);
@@ -2399,7 +2376,7 @@ int engine_classify_many(const mvx_prob *const *Ps, int count, int quirks, int *
   a.st = (int *)(ob + o_st); a.nv = (int *)(ob + o_nv); a.viol = (int *)(ob + o_viol); a.xv = (double *)(ob + o_xv);
   a.n = n; a.cap = cap; a.quirks = quirks; a.count = count;
   launch_classify(a, sc.stream);
-  if (!c.cls_out_dev) HIPCHECK(hipMemcpyAsync(hb + o_st, db + o_st, host_bytes - o_st, hipMemcpyDeviceToHost, sc.stream));
+  if (!c.nodes.host_dev) HIPCHECK(hipMemcpyAsync(hb + o_st, db + o_st, host_bytes - o_st, hipMemcpyDeviceToHost, sc.stream));
   HIPCHECK(hipStreamSynchronize(sc.stream));
   const int *h_st = (const int *)(hb + o_st), *h_nv = (const int *)(hb + o_nv), *h_viol = (const int *)(hb + o_viol);
   const double *h_xv = (const double *)(hb + o_xv);
@@ -2438,48 +2415,19 @@ int engine_penalties_many(const mvx_prob *const *Ps, int count, const int *cols,
   }
   if (total == 0) return 0;
   Context &c = ctx();
+  bind_device(c);
   MAIN_LOCK(c);
   flush_copies(c); // a clone recorded into one of these slabs lands first
   SolveCtx &sc = c.main;
-  size_t off = 0;
-  auto carve = [&](size_t bytes) {
-    size_t o = off;
-    off = align_up(off + bytes, 256);
-    return o;
-  };
+  Carver carve;
   // up: [descriptors]; out: [pen_down][pen_up][arg_down][arg_up]
   const size_t o_nodes = carve((size_t)total * sizeof(PenNode));
-  const size_t up_bytes = off;
+  const size_t up_bytes = carve.off;
   const size_t o_pd = carve((size_t)total * 8), o_pu = carve((size_t)total * 8), o_ad = carve((size_t)total * 4),
                o_au = carve((size_t)total * 4);
-  const size_t host_bytes = off, dev_bytes = off;
-  if (dev_bytes > c.pen_dev_bytes || host_bytes > c.pen_host_bytes) {
-    HIPCHECK(hipStreamSynchronize(sc.stream));
-    if (c.pen_dev) HIPCHECK(hipFree(c.pen_dev));
-    if (c.pen_host) HIPCHECK(hipHostFree(c.pen_host));
-    c.pen_dev = c.pen_host = nullptr;
-    c.pen_out_dev = nullptr;
-    c.pen_dev_bytes = c.pen_host_bytes = 0;
-    const size_t want = dev_bytes + dev_bytes / 2;
-    if (hipMalloc(&c.pen_dev, want) != hipSuccess) {
-      (void)hipGetLastError();
-      c.pen_dev = nullptr;
-      g_last_error.store(MVX_ENOMEM);
-      return -2;
-    }
-    if (hipHostMalloc(&c.pen_host, want) != hipSuccess) {
-      (void)hipGetLastError();
-      HIPCHECK(hipFree(c.pen_dev));
-      c.pen_dev = c.pen_host = nullptr;
-      g_last_error.store(MVX_ENOMEM);
-      return -2;
-    }
-    void *dp = nullptr;
-    if (hipHostGetDevicePointer(&dp, c.pen_host, 0) == hipSuccess && dp) c.pen_out_dev = (unsigned char *)dp;
-    else (void)hipGetLastError();
-    c.pen_dev_bytes = c.pen_host_bytes = want;
-  }
-  unsigned char *hb = (unsigned char *)c.pen_host, *db = (unsigned char *)c.pen_dev;
+  const size_t host_bytes = carve.off;
+  if (!node_scratch_reserve(c, host_bytes, host_bytes)) return -2;
+  unsigned char *hb = (unsigned char *)c.nodes.host, *db = (unsigned char *)c.nodes.dev;
   PenNode *h_nodes = (PenNode *)(hb + o_nodes);
   for (int t = 0; t < count; t++) {
     const mvx_prob *P = Ps[t];
@@ -2490,14 +2438,14 @@ int engine_penalties_many(const mvx_prob *const *Ps, int count, const int *cols,
     }
   }
   HIPCHECK(hipMemcpyAsync(db, hb, up_bytes, hipMemcpyHostToDevice, sc.stream));
-  unsigned char *ob = c.pen_out_dev ? c.pen_out_dev : db;
+  unsigned char *ob = c.nodes.host_dev ? c.nodes.host_dev : db;
   PenArgs a;
   a.nodes = (const PenNode *)(db + o_nodes);
   a.pen_down = (double *)(ob + o_pd); a.pen_up = (double *)(ob + o_pu);
   a.arg_down = (int *)(ob + o_ad); a.arg_up = (int *)(ob + o_au);
   a.tol = tol; a.count = total; a.pad = 0;
   launch_penalty(a, sc.stream);
-  if (!c.pen_out_dev) HIPCHECK(hipMemcpyAsync(hb + o_pd, db + o_pd, host_bytes - o_pd, hipMemcpyDeviceToHost, sc.stream));
+  if (!c.nodes.host_dev) HIPCHECK(hipMemcpyAsync(hb + o_pd, db + o_pd, host_bytes - o_pd, hipMemcpyDeviceToHost, sc.stream));
   HIPCHECK(hipStreamSynchronize(sc.stream));
   std::memcpy(pen_down + k0, hb + o_pd, (size_t)total * 8);
   std::memcpy(pen_up + k0, hb + o_pu, (size_t)total * 8);
@@ -2507,32 +2455,6 @@ int engine_penalties_many(const mvx_prob *const *Ps, int count, const int *cols,
 }
 
 // ------------------------------------------------------------------ reduced-cost tightening (k_rcfix, k_tighten)
-// caller holds main_mu; one device and one pinned buffer of at least `bytes` for both entries
-static bool rcf_reserve(Context &c, SolveCtx &sc, size_t bytes) {
-  if (bytes <= c.rcf_bytes) return true;
-  HIPCHECK(hipStreamSynchronize(sc.stream));
-  if (c.rcf_dev) HIPCHECK(hipFree(c.rcf_dev));
-  if (c.rcf_host) HIPCHECK(hipHostFree(c.rcf_host));
-  c.rcf_dev = c.rcf_host = nullptr;
-  c.rcf_bytes = 0;
-  const size_t want = bytes + bytes / 2;
-  if (hipMalloc(&c.rcf_dev, want) != hipSuccess) {
-    (void)hipGetLastError();
-    c.rcf_dev = nullptr;
-    g_last_error.store(MVX_ENOMEM);
-    return false;
-  }
-  if (hipHostMalloc(&c.rcf_host, want) != hipSuccess) {
-    (void)hipGetLastError();
-    HIPCHECK(hipFree(c.rcf_dev));
-    c.rcf_dev = c.rcf_host = nullptr;
-    g_last_error.store(MVX_ENOMEM);
-    return false;
-  }
-  c.rcf_bytes = want;
-  return true;
-}
-
 // Reduced-cost bound tightening of `count` solved handles (mvx_rc_tighten_many): one upload of the descriptors and the
 // kinds, one k_rcfix launch, one copy back; the per-position results are mapped to columns through the nvar mirror and
 // sorted by column.  Return codes: 0; -1 bad arguments (other column counts or kinds); -2 device out of memory; -3 a handle
@@ -2551,20 +2473,16 @@ int engine_rc_tighten_many(const mvx_prob *const *Ps, int count, const double *c
   std::vector<double> z((size_t)count);
   for (int t = 0; t < count; t++) z[(size_t)t] = mvx_get_obj_val(Ps[t]); // the mirror; exports first when it is stale
   Context &c = ctx();
+  bind_device(c);
   MAIN_LOCK(c);
   flush_copies(c); // a clone recorded into one of these slabs lands first
   SolveCtx &sc = c.main;
-  size_t off = 0;
-  auto carve = [&](size_t bytes) {
-    size_t o = off;
-    off = align_up(off + bytes, 256);
-    return o;
-  };
+  Carver carve;
   // up: [descriptors][kind]; back: [code][val]
-  const size_t o_nodes = carve((size_t)count * sizeof(RcNode)), o_kind = carve((size_t)(n + 1) * 4), up_bytes = off;
+  const size_t o_nodes = carve((size_t)count * sizeof(RcNode)), o_kind = carve((size_t)(n + 1) * 4), up_bytes = carve.off;
   const size_t o_code = carve((size_t)count * (size_t)(n + 1) * 4), o_val = carve((size_t)count * (size_t)(n + 1) * 8);
-  if (!rcf_reserve(c, sc, off)) return -2;
-  unsigned char *hb = (unsigned char *)c.rcf_host, *db = (unsigned char *)c.rcf_dev;
+  if (!node_scratch_reserve(c, carve.off, carve.off)) return -2;
+  unsigned char *hb = (unsigned char *)c.nodes.host, *db = (unsigned char *)c.nodes.dev;
   RcNode *h_nodes = (RcNode *)(hb + o_nodes);
   for (int t = 0; t < count; t++) {
     const mvx_prob *P = Ps[t];
@@ -2584,7 +2502,7 @@ int engine_rc_tighten_many(const mvx_prob *const *Ps, int count, const double *c
   a.val = (double *)(db + o_val);
   a.tol = tol; a.n = n; a.count = count;
   launch_rcfix(a, sc.stream);
-  HIPCHECK(hipMemcpyAsync(hb + o_code, db + o_code, off - o_code, hipMemcpyDeviceToHost, sc.stream));
+  HIPCHECK(hipMemcpyAsync(hb + o_code, db + o_code, carve.off - o_code, hipMemcpyDeviceToHost, sc.stream));
   HIPCHECK(hipStreamSynchronize(sc.stream));
   const int *h_code = (const int *)(hb + o_code);
   const double *h_val = (const double *)(hb + o_val);
@@ -2645,13 +2563,14 @@ int engine_tighten_many(mvx_prob *const *Ps, int count, const int *off, const in
     }
   }
   Context &c = ctx();
+  bind_device(c);
   MAIN_LOCK(c);
   SolveCtx &sc = c.main;
   const size_t o_hs = 0, o_es = align_up((size_t)count * sizeof(TightHandle), 256);
   const size_t bytes = o_es + (size_t)nent * sizeof(TightEntry);
-  if (nent > 0 && !rcf_reserve(c, sc, bytes)) return -2;
-  TightHandle *h_hs = nent > 0 ? (TightHandle *)((unsigned char *)c.rcf_host + o_hs) : nullptr;
-  TightEntry *h_es = nent > 0 ? (TightEntry *)((unsigned char *)c.rcf_host + o_es) : nullptr;
+  if (nent > 0 && !node_scratch_reserve(c, bytes, bytes)) return -2;
+  TightHandle *h_hs = nent > 0 ? (TightHandle *)((unsigned char *)c.nodes.host + o_hs) : nullptr;
+  TightEntry *h_es = nent > 0 ? (TightEntry *)((unsigned char *)c.nodes.host + o_es) : nullptr;
   int e = 0;
   for (int t = 0; t < count; t++) {
     mvx_prob *P = Ps[t];
@@ -2677,8 +2596,8 @@ int engine_tighten_many(mvx_prob *const *Ps, int count, const int *off, const in
   }
   if (nent > 0) {
     flush_copies(c); // a recorded clone INTO one of these slabs must land before the edits do
-    unsigned char *db = (unsigned char *)c.rcf_dev;
-    HIPCHECK(hipMemcpyAsync(db, c.rcf_host, bytes, hipMemcpyHostToDevice, sc.stream));
+    unsigned char *db = (unsigned char *)c.nodes.dev;
+    HIPCHECK(hipMemcpyAsync(db, c.nodes.host, bytes, hipMemcpyHostToDevice, sc.stream));
     launch_tighten((const TightHandle *)(db + o_hs), (const TightEntry *)(db + o_es), nent, sc.stream);
     HIPCHECK(hipStreamSynchronize(sc.stream)); // the pinned side is free for the next call
   }
@@ -2705,17 +2624,12 @@ static const RoundModel *round_model(Context &c, const mvx_prob *R) {
   const int m0 = R->m, n = R->n;
   const size_t ldm = align_up((size_t)std::max(1, m0), 64);
   M->m0 = m0; M->n = n; M->ldm = (int)ldm; M->dir = R->dir;
-  size_t off = 0;
-  auto carve = [&](size_t bytes) {
-    size_t o = off;
-    off = align_up(off + bytes, 256);
-    return o;
-  };
+  Carver carve;
   carve((size_t)(n + 1) * ldm * 8);
   M->o_rlo = carve((size_t)m0 * 8); M->o_rhi = carve((size_t)m0 * 8);
   M->o_clo = carve((size_t)(n + 1) * 8); M->o_chi = carve((size_t)(n + 1) * 8); M->o_c = carve((size_t)(n + 1) * 8);
   M->o_flags = carve((size_t)(n + 1) * 4);
-  std::vector<unsigned char> h(off, 0);
+  std::vector<unsigned char> h(carve.off, 0);
   double *At = (double *)h.data();
   int *flags = (int *)(h.data() + M->o_flags);
   for (int j = 1; j <= n; j++) flags[j] = R->kind[(size_t)j] != MVX_CV ? RND_INT : 0;
@@ -2735,13 +2649,13 @@ static const RoundModel *round_model(Context &c, const mvx_prob *R) {
   std::memcpy(h.data() + M->o_clo, R->clb.data(), (size_t)(n + 1) * 8);
   std::memcpy(h.data() + M->o_chi, R->cub.data(), (size_t)(n + 1) * 8);
   std::memcpy(h.data() + M->o_c, R->c.data(), (size_t)(n + 1) * 8);
-  if (hipMalloc(&M->dev, off) != hipSuccess) {
+  if (hipMalloc(&M->dev, carve.off) != hipSuccess) {
     (void)hipGetLastError();
     M->dev = nullptr;
     g_last_error.store(MVX_ENOMEM);
     return nullptr;
   }
-  HIPCHECK(hipMemcpyAsync(M->dev, h.data(), off, hipMemcpyHostToDevice, sc.stream));
+  HIPCHECK(hipMemcpyAsync(M->dev, h.data(), carve.off, hipMemcpyHostToDevice, sc.stream));
   HIPCHECK(hipStreamSynchronize(sc.stream)); // the pageable source goes out of scope
   M->c = R->c; M->kind = R->kind; M->clb = R->clb; M->cub = R->cub; M->rlb = R->rlb; M->rub = R->rub;
   R->rmod = M;
@@ -2760,52 +2674,21 @@ int engine_round_many(const mvx_prob *root, const mvx_prob *const *Ps, int count
   for (int t = 0; t < count; t++)
     if (!Ps[t]->valid || Ps[t]->status != MVX_OPT) return -3;
   Context &c = ctx();
+  bind_device(c);
   MAIN_LOCK(c);
   flush_copies(c); // a clone recorded into one of these slabs lands first
   SolveCtx &sc = c.main;
   const RoundModel *M = round_model(c, root);
   if (!M) return -2;
-  size_t off = 0;
-  auto carve = [&](size_t bytes) {
-    size_t o = off;
-    off = align_up(off + bytes, 256);
-    return o;
-  };
+  Carver carve;
   // up: [descriptors]; out: [obj][found][x]; device only: [row scratch] when the rows do not fit in LDS
   const size_t o_nodes = carve((size_t)count * sizeof(RndNode));
-  const size_t up_bytes = off;
+  const size_t up_bytes = carve.off;
   const size_t o_obj = carve((size_t)count * 8), o_found = carve((size_t)count * 4), o_x = carve((size_t)count * (n + 1) * 8);
-  const size_t host_bytes = off;
+  const size_t host_bytes = carve.off;
   const size_t o_scr = carve(m0 > RND_NMAX ? (size_t)count * m0 * 8 : 0);
-  const size_t dev_bytes = off;
-  if (dev_bytes > c.rnd_dev_bytes || host_bytes > c.rnd_host_bytes) {
-    HIPCHECK(hipStreamSynchronize(sc.stream));
-    if (c.rnd_dev) HIPCHECK(hipFree(c.rnd_dev));
-    if (c.rnd_host) HIPCHECK(hipHostFree(c.rnd_host));
-    c.rnd_dev = c.rnd_host = nullptr;
-    c.rnd_out_dev = nullptr;
-    c.rnd_dev_bytes = c.rnd_host_bytes = 0;
-    const size_t want_dev = dev_bytes + dev_bytes / 2, want_host = host_bytes + host_bytes / 2;
-    if (hipMalloc(&c.rnd_dev, want_dev) != hipSuccess) {
-      (void)hipGetLastError();
-      c.rnd_dev = nullptr;
-      g_last_error.store(MVX_ENOMEM);
-      return -2;
-    }
-    if (hipHostMalloc(&c.rnd_host, want_host) != hipSuccess) {
-      (void)hipGetLastError();
-      HIPCHECK(hipFree(c.rnd_dev));
-      c.rnd_dev = c.rnd_host = nullptr;
-      g_last_error.store(MVX_ENOMEM);
-      return -2;
-    }
-    void *dp = nullptr;
-    if (hipHostGetDevicePointer(&dp, c.rnd_host, 0) == hipSuccess && dp) c.rnd_out_dev = (unsigned char *)dp;
-    else (void)hipGetLastError();
-    c.rnd_dev_bytes = want_dev;
-    c.rnd_host_bytes = want_host;
-  }
-  unsigned char *hb = (unsigned char *)c.rnd_host, *db = (unsigned char *)c.rnd_dev;
+  if (!node_scratch_reserve(c, carve.off, host_bytes)) return -2;
+  unsigned char *hb = (unsigned char *)c.nodes.host, *db = (unsigned char *)c.nodes.dev;
   RndNode *h_nodes = (RndNode *)(hb + o_nodes);
   for (int t = 0; t < count; t++) {
     const mvx_prob *P = Ps[t];
@@ -2814,7 +2697,7 @@ int engine_round_many(const mvx_prob *root, const mvx_prob *const *Ps, int count
     nd.m = P->m; nd.ld = P->ld;
   }
   HIPCHECK(hipMemcpyAsync(db, hb, up_bytes, hipMemcpyHostToDevice, sc.stream));
-  unsigned char *ob = c.rnd_out_dev ? c.rnd_out_dev : db;
+  unsigned char *ob = c.nodes.host_dev ? c.nodes.host_dev : db;
   const unsigned char *mb = (const unsigned char *)M->dev;
   RndArgs a;
   a.nodes = (const RndNode *)(db + o_nodes);
@@ -2827,7 +2710,7 @@ int engine_round_many(const mvx_prob *root, const mvx_prob *const *Ps, int count
   a.sg = root->dir == MVX_MIN ? -1.0 : 1.0;
   a.n = n; a.m0 = m0; a.ldm = M->ldm; a.mode = mode; a.count = count; a.pad = 0;
   launch_round(a, sc.stream);
-  if (!c.rnd_out_dev) HIPCHECK(hipMemcpyAsync(hb + o_obj, db + o_obj, host_bytes - o_obj, hipMemcpyDeviceToHost, sc.stream));
+  if (!c.nodes.host_dev) HIPCHECK(hipMemcpyAsync(hb + o_obj, db + o_obj, host_bytes - o_obj, hipMemcpyDeviceToHost, sc.stream));
   HIPCHECK(hipStreamSynchronize(sc.stream));
   std::memcpy(obj, hb + o_obj, (size_t)count * 8);
   std::memcpy(found, hb + o_found, (size_t)count * 4);
