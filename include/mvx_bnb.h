@@ -212,6 +212,13 @@ int mvx_bnb_classify(const mvx_lp_api *api, const void *prob, const void *root, 
 /* bs.cpp:261-282: bound = col_prim(a, pick); S2/S3 = clones of `a` (created by the caller with
    create_prob) with the branching bounds set; they are NOT solved here (the caller batches them) */
 int mvx_bnb_make_children(const mvx_lp_api *api, const void *a, int pick, int quirks, void *S2, void *S3);
+/* The repaired mode's rule for integer columns with fractional bounds, which every repaired driver applies to (a copy of)
+   its root before the first solve: lb -> ceil(lb), ub -> floor(ub), type FX where they meet; integral bounds are not
+   touched.  Edits `prob` in place.  Returns 0 nothing to round, 1 bounds rounded, 2 some column's range holds no integer
+   (the model is infeasible; `prob` may be partly edited) */
+int mvx_bnb_integral_bounds(const mvx_lp_api *api, void *prob);
+/* The same scan without writing anything: what mvx_bnb_integral_bounds would return for `prob` */
+int mvx_bnb_fractional_bounds(const mvx_lp_api *api, const void *prob);
 
 /* Host twin of mvx_branch_penalties_many for one solved handle, from get_tableau and get_basis: for each basic column
    cols[t], pen_down[t] / pen_up[t] = fd / fu times the smallest |T[0][q]| / |T[i][q]| over the non-basic positions q that

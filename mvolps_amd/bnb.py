@@ -113,6 +113,10 @@ def _bind(lib):
     lib.mvx_bnb_classify.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
     lib.mvx_bnb_make_children.restype = C.c_int
     lib.mvx_bnb_make_children.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.mvx_bnb_integral_bounds.restype = C.c_int
+    lib.mvx_bnb_integral_bounds.argtypes = [C.c_void_p, C.c_void_p]
+    lib.mvx_bnb_fractional_bounds.restype = C.c_int
+    lib.mvx_bnb_fractional_bounds.argtypes = [C.c_void_p, C.c_void_p]
     lib.mvx_bnb_node_cuts.restype = C.c_int
     lib.mvx_bnb_node_cuts.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BnbParams)]
     lib.mvx_classify_many.restype = C.c_int
@@ -274,6 +278,19 @@ def make_children(a, pick, quirks=1, table=None):
     tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
     lib().mvx_bnb_make_children(tptr, a.h, pick, quirks, S2.h, S3.h)
     return S2, S3
+
+
+def integral_bounds(prob, table=None):
+    """mvx_bnb_integral_bounds: round the bounds of `prob`'s integer columns inward, in place (what the repaired drivers do to
+    a copy of their root).  Returns 0 nothing to round, 1 rounded, 2 a column's range holds no integer."""
+    tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
+    return lib().mvx_bnb_integral_bounds(tptr, prob.h)
+
+
+def fractional_bounds(prob, table=None):
+    """mvx_bnb_fractional_bounds: what integral_bounds would return, nothing written."""
+    tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
+    return lib().mvx_bnb_fractional_bounds(tptr, prob.h)
 
 
 def classify_many(probs, quirks=1, cap=None):

@@ -2314,6 +2314,41 @@ void mvx_bnb_default_params(mvx_bnb_params *p) {
   p->rc_fix = 0;
 }
 
+// Repaired mode's rule for an integer column whose bounds are not integers (legal input: LP and MPS files may carry them):
+// the bounds are rounded inward, ceil(lb) and floor(ub), before the first solve, so every branching splits an integral range
+// (no child with crossed bounds) and a repaired GMI cut measures an integer column from an integral bound.  Returns 0: every
+// bound is integral already (nothing written), 1: some were rounded (written when `apply`), 2: a column's range holds no
+// integer (the model is infeasible; the handle is left half edited).  Bounds that are integers come back as they went in.
+static int integral_bounds(const mvx_lp_api *api, void *P, bool apply) {
+  const int n = api->get_num_cols(P);
+  int out = 0;
+  for (int j = 1; j <= n; j++) {
+    if (api->get_col_kind(P, j) == MVX_CV) continue;
+    const int t = api->get_col_type(P, j);
+    if (t == MVX_FR) continue;
+    const double l = api->get_col_lb(P, j), u = api->get_col_ub(P, j);
+    const bool has_l = t == MVX_LO || t == MVX_DB || t == MVX_FX, has_u = t == MVX_UP || t == MVX_DB;
+    const double nl = has_l ? std::ceil(l) : l, nu = t == MVX_FX ? std::floor(l) : (has_u ? std::floor(u) : u);
+    if ((!has_l || nl == l) && (t == MVX_FX ? nu == l : (!has_u || nu == u))) continue;
+    if ((t == MVX_DB || t == MVX_FX) && nl > nu) return 2;
+    out = 1;
+    if (apply) api->set_col_bnds(P, j, (t == MVX_DB && nl == nu) ? MVX_FX : t, nl, nu);
+  }
+  return out;
+}
+
+int mvx_bnb_integral_bounds(const mvx_lp_api *api, void *prob) { return integral_bounds(api ? api : &g_hip_api, prob, true); }
+int mvx_bnb_fractional_bounds(const mvx_lp_api *api, const void *prob) {
+  return integral_bounds(api ? api : &g_hip_api, const_cast<void *>(prob), false);
+}
+
+static int run_driver(const mvx_lp_api *api, void *prob, const mvx_bnb_params *params, mvx_bnb_result *res) {
+  if (api->simplex_batch && params->node_strat == 0 && params->window > 1)
+    return branchAndBoundWindow(api, prob, *params, res);
+  if (api->simplex_batch && params->node_strat == 1 && params->best_window > 1) return branchAndBoundBest(api, prob, *params, res);
+  return branchAndBound(api, prob, *params, res);
+}
+
 int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *params, mvx_bnb_result *res) {
   mvx_bnb_params dflt;
   if (!params) {
@@ -2330,10 +2365,25 @@ int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *
     std::memset(res, 0, sizeof(*res));
     return -1;
   }
-  if (api->simplex_batch && params->node_strat == 0 && params->window > 1)
-    return branchAndBoundWindow(api, prob, *params, res);
-  if (api->simplex_batch && params->node_strat == 1 && params->best_window > 1) return branchAndBoundBest(api, prob, *params, res);
-  return branchAndBound(api, prob, *params, res);
+  if (params->reference_quirks == 0 && integral_bounds(api, prob, false) != 0) {
+    // the caller's handle stays as it is: the tree runs on a copy with the rounded bounds
+    void *work = api->create_prob();
+    api->copy_prob(work, prob, MVX_OFF);
+    int rc = 0;
+    if (integral_bounds(api, work, true) == 2) { // no integer in some column's range: the root is infeasible, nothing to solve
+      Recorder rec;
+      rec.node(1, 0);
+      rec.prune[1] = MVOLP::FEAS;
+      const double sg = (api->get_obj_dir && api->get_obj_dir(prob) == MVX_MIN) ? -1.0 : 1.0;
+      const int n0 = api->get_num_cols(prob);
+      pack_result(res, rec, 2, 0, 0, -sg * std::numeric_limits<double>::infinity(), 0, n0, std::vector<double>((size_t)n0 + 1, 0.0), 0);
+    } else {
+      rc = run_driver(api, work, params, res);
+    }
+    api->delete_prob(work);
+    return rc;
+  }
+  return run_driver(api, prob, params, res);
 }
 
 void mvx_bnb_free_result(mvx_bnb_result *res) {

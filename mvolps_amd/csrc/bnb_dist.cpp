@@ -123,7 +123,19 @@ extern "C" int mvx_branchAndBound_dist(const mvx_lp_api *api, const mvx_image_ap
   std::deque<Node> queue;
   queue.push_back(Node{1, 0, POS_INF, true});
   std::unordered_map<int, void *> local; // nodes this rank holds
-  if (rank == 0) {
+  // the repaired mode's rule (mvx_bnb_integral_bounds): integer columns' bounds rounded inward before the first solve, on
+  // every rank's own copy of the root, which is also the base of the migration images
+  void *rounded = nullptr;
+  if (!prm.reference_quirks && mvx_bnb_fractional_bounds(api, root) != 0) { // integral bounds: the caller's handle, as before
+    rounded = api->create_prob();
+    api->copy_prob(rounded, root, MVX_ON);
+    if (mvx_bnb_integral_bounds(api, rounded) == 2) { // a range without an integer: the root is infeasible
+      tree.prune[1] = FEAS;
+      queue.clear();
+    }
+    root = rounded;
+  }
+  if (rank == 0 && !queue.empty()) {
     void *s1 = api->create_prob();
     api->copy_prob(s1, root, MVX_ON); // S1 = NodeData(prob), bs.cpp:80
     local[1] = s1;
@@ -498,6 +510,7 @@ extern "C" int mvx_branchAndBound_dist(const mvx_lp_api *api, const mvx_image_ap
     rc = MVX_EFAIL;
   for (auto &kv : local) api->delete_prob(kv.second);
   local.clear();
+  if (rounded) api->delete_prob(rounded);
   if (rc != 0) return rc;
 
   // incumbent solution (bs.cpp:181-187) from the rank that solved it

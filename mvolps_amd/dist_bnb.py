@@ -160,8 +160,15 @@ def branch_and_bound(engine, root, var_strat=0, quirks=1, max_nodes=0, loop_limi
     parent, prune, bound = {1: 0}, {1: NONE}, {1: float("inf")}
     events = []
     queue = deque([_Node(1, 0, float("inf"), True)])
+    if not quirks and engine._bnb.fractional_bounds(root, table=engine.table) != 0:  # integral bounds: the caller's handle
+        # the repaired mode's rule (mvx_bnb_integral_bounds): integer columns' bounds rounded inward before the first solve,
+        # on every rank's own copy of the root, which is also the base of the migration images
+        root = root.copy(capi.ON)
+        if engine._bnb.integral_bounds(root, table=engine.table) == 2:  # a range without an integer: the root is infeasible
+            prune[1] = FEAS
+            queue.clear()
     local = {}
-    if rank == 0:
+    if rank == 0 and queue:
         local[1] = root.copy(capi.ON)  # S1 = NodeData(prob), bs.cpp:80
     next_id = 2
     child_seq = 0

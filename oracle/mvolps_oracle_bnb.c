@@ -351,7 +351,55 @@ static int solve(ctx_t *cx, orc_prob *p) {
   return rc;
 }
 
+/* The repaired mode's rule for an integer column with fractional bounds (restated from mvx_bnb_integral_bounds): the bounds
+   are rounded inward before the first solve.  0: all integral, nothing written; 1: some rounded (written when `apply`);
+   2: a column's range holds no integer. */
+static int integral_bounds(orc_prob *P, int apply) {
+  int n = orc_get_num_cols(P), out = 0;
+  for (int j = 1; j <= n; j++) {
+    if (orc_get_col_kind(P, j) == ORC_CV) continue;
+    int t = orc_get_col_type(P, j);
+    if (t == ORC_FR) continue;
+    double l = orc_get_col_lb(P, j), u = orc_get_col_ub(P, j);
+    int has_l = t == ORC_LO || t == ORC_DB || t == ORC_FX, has_u = t == ORC_UP || t == ORC_DB;
+    double nl = has_l ? ceil(l) : l, nu = t == ORC_FX ? floor(l) : (has_u ? floor(u) : u);
+    if ((!has_l || nl == l) && (t == ORC_FX ? nu == l : (!has_u || nu == u))) continue;
+    if ((t == ORC_DB || t == ORC_FX) && nl > nu) return 2;
+    out = 1;
+    if (apply) orc_set_col_bnds(P, j, (t == ORC_DB && nl == nu) ? ORC_FX : t, nl, nu);
+  }
+  return out;
+}
+
+static int bnb_run(orc_prob *prob, const orc_bnb_params *params, orc_bnb_result *res);
+
 int orc_branchAndBound(orc_prob *prob, const orc_bnb_params *params, orc_bnb_result *res) {
+  if (params->reference_quirks || integral_bounds(prob, 0) == 0) return bnb_run(prob, params, res);
+  /* the caller's problem stays as it is: the tree runs on a copy with the rounded bounds */
+  orc_prob *work = orc_create_prob();
+  orc_copy_prob(work, prob, ORC_OFF);
+  int rc = 0;
+  if (integral_bounds(work, 1) == 2) { /* the root is infeasible, nothing to solve */
+    int n0 = orc_get_num_cols(prob);
+    memset(res, 0, sizeof(*res));
+    res->n_nodes = 1;
+    res->parent = (int *)xcalloc(2, sizeof(int));
+    res->prune = (int *)xcalloc(2, sizeof(int));
+    res->node_bound = (double *)xcalloc(2, sizeof(double));
+    res->prune[0] = 4;
+    res->prune[1] = 1;
+    res->node_bound[0] = res->node_bound[1] = HUGE_VAL;
+    res->n = n0;
+    res->x = (double *)xcalloc((size_t)n0 + 1, sizeof(double));
+    res->best_lower = orc_get_obj_dir(prob) == ORC_MIN ? HUGE_VAL : -HUGE_VAL;
+  } else {
+    rc = bnb_run(work, params, res);
+  }
+  orc_delete_prob(work);
+  return rc;
+}
+
+static int bnb_run(orc_prob *prob, const orc_bnb_params *params, orc_bnb_result *res) {
   memset(res, 0, sizeof(*res));
   ctx_t cx;
   memset(&cx, 0, sizeof(cx));
