@@ -198,6 +198,24 @@ int mvx_rc_tighten_many(const mvx_prob *const *Ps, int count, const double *cuto
    column's resting value where it is: returns -4, nothing changed, when a listed column is basic in its handle or the edit
    would move its value; -1 bad arguments; -2 device out of memory. */
 int mvx_tighten_cols_many(mvx_prob *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub);
+/* Node bound propagation (DESIGN.md "Node bound propagation") of `count` handles, one device launch (k_prop) for all handles and
+   all rounds: up to max_rounds Jacobi rounds of activity-based tightening of the integer columns' bounds from rows 1..m0 of
+   `root` (m0 = root's row count; cut rows are ignored) and each handle's own column bounds as its host model has them (a
+   pending branching edit counts).  The model is uploaded once and kept with `root`, as for mvx_round_many.  infeasible[t],
+   rounds[t], and handle t's changed columns, ascending, in cols[t*n .. t*n + cnt[t] - 1] with their bounds in lb / ub[same]
+   (+-inf for an absent bound; none for an infeasible handle).  Pure: no handle changes, none need be solved.  Bit-identical to
+   mvx_bnb_propagate (mvx_bnb.h).  Returns 0; -1 bad arguments (max_rounds < 1, a handle with another column count); -2 device
+   out of memory; -5 n > 4096 (the kernel keeps a handle's bounds in LDS). */
+int mvx_propagate_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, int max_rounds, int *infeasible, int *rounds, int *cnt,
+                       int *cols, double *lb, double *ub);
+/* General bound lists of many handles applied with one device launch (k_setbnds): handle t takes the entries off[t] .. off[t+1]-1
+   (columns strictly ascending within a handle, lb <= ub, +-inf for an absent bound; every handle listed once).  The bound type
+   follows from which bounds are finite (FX where they are equal, DB, LO, UP, FR), and each handle is left in the state
+   mvx_set_col_bnds per entry, in list order, leaves it in: bounds of basic columns wait for the next solve (merged with a
+   pending edit of the same row), non-basic positions take their bounds and status, and where a resting value moves column 0 of
+   every tableau row follows.  Clones recorded and not yet launched are flushed first.  Returns 0; -1 bad arguments or a bad list
+   (nothing is changed); -2 device out of memory. */
+int mvx_set_col_bnds_many(mvx_prob *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub);
 
 /* ---- engine-state access (parity tests, visualisers) --------------------------- */
 int mvx_get_tableau_ld(const mvx_prob *P);

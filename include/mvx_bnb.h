@@ -90,6 +90,14 @@ typedef struct mvx_lp_api {
   /* optional (may be NULL): the bound lists of `count` handles applied in one call (mvx_tighten_cols_many), handle t taking
      entries off[t] .. off[t+1]-1; without it the driver calls set_col_bnds per entry */
   int (*tighten_cols_many)(void *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub);
+  /* optional (may be NULL): node bound propagation (DESIGN.md "Node bound propagation") of `count` handles over the rows of
+     `root` in one call (mvx_propagate_many); without it, or when it returns -5 (more columns than the kernel holds), the
+     driver runs the host twin mvx_bnb_propagate */
+  int (*propagate_many)(const void *root, const void *const *Ps, int count, int max_rounds, int *infeasible, int *rounds, int *cnt, int *cols,
+                        double *lb, double *ub);
+  /* optional (may be NULL): general bound lists of `count` handles applied in one call (mvx_set_col_bnds_many), handle t taking
+     entries off[t] .. off[t+1]-1, +-inf for an absent bound; without it the driver calls set_col_bnds per entry */
+  int (*set_col_bnds_many)(void *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub);
 } mvx_lp_api;
 
 const mvx_lp_api *mvx_hip_lp_api(void);
@@ -135,6 +143,10 @@ typedef struct {
   int rc_fix;           /* reduced-cost bound tightening (DESIGN.md "Reduced-cost tightening"): 0 off (default), 1 on every node
                            that reaches the branch decision while an incumbent exists, on its LP as solved; the tightened
                            bounds go to both children.  Needs reference_quirks = 0 and best_window = 0 */
+  int prop;             /* node bound propagation (DESIGN.md "Node bound propagation"): 0 off (default), 1..16 the round limit.  The
+                           root (behind the rounding of its bounds) and every child (behind its branching bound and its rc_fix
+                           list, in front of its first solve) have the bounds of their integer columns tightened from the
+                           activities of the root's rows.  Needs reference_quirks = 0 and best_window = 0 */
 } mvx_bnb_params;
 
 /* B&B events at the emit points of bs.cpp (message.h EventType) */
@@ -179,6 +191,10 @@ typedef struct {
   long long rc_calls;      /* rc_fix = 1: branching nodes the reduced-cost tightening ran on */
   long long rc_fixed;      /* ... entries of their lists with lb == ub */
   long long rc_tightened;  /* ... the other entries */
+  long long prop_calls;      /* prop > 0: handles the propagation ran on (the root and every child) */
+  long long prop_fixed;      /* ... entries of their applied lists with lb == ub */
+  long long prop_tightened;  /* ... the other entries */
+  long long prop_infeasible; /* ... handles it proved infeasible (a child keeps its bounds and is solved as before) */
 } mvx_bnb_result;
 
 void mvx_bnb_default_params(mvx_bnb_params *p);
@@ -245,6 +261,19 @@ int mvx_bnb_round(const mvx_lp_api *api, const void *prob, const void *root, int
    empty) for rc_fix outside 0..1, reference_quirks = 1 or best_window > 0, and -2 when neither rc_tighten_many nor this
    twin can run */
 int mvx_bnb_rc_tighten(const mvx_lp_api *api, const void *prob, double cutoff, double tol, int *cnt, int *cols, double *lb, double *ub);
+
+/* Node bound propagation (DESIGN.md "Node bound propagation"), host twin of mvx_propagate_many for one handle, which need not
+   be solved and is not changed: up to max_rounds Jacobi rounds of activity-based tightening of the integer columns' bounds,
+   from rows 1..m0 of `root` (m0 = its row count; cut rows are ignored) and the column bounds of `prob` itself.  *infeasible 1
+   when a row is contradictory or a column's bounds cross, *rounds the rounds run, the columns whose bounds changed, ascending,
+   in cols[0 .. *cnt - 1] with their bounds in lb / ub (room for n entries each; +-inf for an absent bound; no entries for an
+   infeasible handle).  Works through the table only (get_mat_row, row and column bounds, get_col_kind).  Returns 0; -1 bad
+   arguments (max_rounds < 1, another column count); -2 the table lacks an accessor it needs.  mvx_branchAndBound returns -1
+   (*res empty) for prop outside 0..16 and for prop > 0 with reference_quirks = 1 or best_window > 0, and -2, with the tree so
+   far, when the propagation could not be carried out: neither propagate_many nor this twin can run, or one of its calls
+   (propagate_many, set_col_bnds_many) failed, whatever that call's own code was */
+int mvx_bnb_propagate(const mvx_lp_api *api, const void *prob, const void *root, int max_rounds, int *infeasible, int *rounds, int *cnt,
+                      int *cols, double *lb, double *ub);
 
 /* bs.cpp:249-258 on one solved node `a` that is about to be branched: generate its GMI cut(s) and append the
    row(s) (cut_strat / reference_quirks / lazy_pool / cut_select / cut_chance of `params`).  Returns the number

@@ -15,7 +15,7 @@ _FIELDS = [
     "get_it_cnt",
 ]
 _OPTIONAL = ["simplex_batch", "get_obj_dir", "gmi_cuts", "gmi_cuts_many", "get_col_prim_all", "classify_many", "get_tableau", "get_basis",
-             "branch_penalties_many", "round_many", "rc_tighten_many", "tighten_cols_many"]
+             "branch_penalties_many", "round_many", "rc_tighten_many", "tighten_cols_many", "propagate_many", "set_col_bnds_many"]
 
 
 class LpApiTable(C.Structure):
@@ -41,6 +41,7 @@ class BnbParams(C.Structure):
         ("sb_iters", C.c_int),
         ("heur", C.c_int),
         ("rc_fix", C.c_int),
+        ("prop", C.c_int),
     ]
 
 
@@ -84,6 +85,10 @@ class BnbResult(C.Structure):
         ("rc_calls", C.c_longlong),
         ("rc_fixed", C.c_longlong),
         ("rc_tightened", C.c_longlong),
+        ("prop_calls", C.c_longlong),
+        ("prop_fixed", C.c_longlong),
+        ("prop_tightened", C.c_longlong),
+        ("prop_infeasible", C.c_longlong),
     ]
 
 
@@ -137,6 +142,12 @@ def _bind(lib):
     lib.mvx_tighten_cols_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, _IP, _IP, _DP, _DP]
     lib.mvx_bnb_rc_tighten.restype = C.c_int
     lib.mvx_bnb_rc_tighten.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, _IP, _IP, _DP, _DP]
+    lib.mvx_propagate_many.restype = C.c_int
+    lib.mvx_propagate_many.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, _IP, _IP, _IP, _IP, _DP, _DP]
+    lib.mvx_bnb_propagate.restype = C.c_int
+    lib.mvx_bnb_propagate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _IP, _IP, _IP, _IP, _DP, _DP]
+    lib.mvx_set_col_bnds_many.restype = C.c_int
+    lib.mvx_set_col_bnds_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, _IP, _IP, _DP, _DP]
     lib.mvx_generateCut3.restype = C.c_int
     lib.mvx_generateCut3.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     return lib
@@ -183,11 +194,15 @@ def result_to_dict(res):
         "rc_calls": res.rc_calls,
         "rc_fixed": res.rc_fixed,
         "rc_tightened": res.rc_tightened,
+        "prop_calls": res.prop_calls,
+        "prop_fixed": res.prop_fixed,
+        "prop_tightened": res.prop_tightened,
+        "prop_infeasible": res.prop_infeasible,
     }
 
 
 def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, window=None, cut_select=0, cut_chance=1.0,
-                best_window=None, sb_cands=None, sb_iters=None, heur=None, rc_fix=None):
+                best_window=None, sb_cands=None, sb_iters=None, heur=None, rc_fix=None, prop=None):
     """mvx_bnb_params with ParameterObj's defaults (util.h:65-67) overridden by the arguments (None: the default)."""
     pr = BnbParams()
     lib().mvx_bnb_default_params(C.byref(pr))
@@ -206,20 +221,24 @@ def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, l
         pr.heur = heur
     if rc_fix is not None:
         pr.rc_fix = rc_fix
+    if prop is not None:
+        pr.prop = prop
     return pr
 
 
 def branch_and_bound(prob, var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, table=None, window=None,
-                     cut_select=0, cut_chance=1.0, best_window=None, sb_cands=None, sb_iters=None, heur=None, rc_fix=None):
+                     cut_select=0, cut_chance=1.0, best_window=None, sb_cands=None, sb_iters=None, heur=None, rc_fix=None, prop=None):
     """Run the driver on `prob` (a capi.Prob).  table=None uses the gfx950 engine's own table.  best_window > 1 with
     node_strat=1: the speculative best-bound window (mvx_bnb_params.best_window).  var_strat 3 / 4: branching on the node
     LP's penalties / strong branching (sb_cands candidates, sb_iters pivots per child).  heur 1 / 2: the primal rounding
     heuristic on every branching node (round and check / round, check and fill; quirks=0 only).  rc_fix 1: reduced-cost bound
-    tightening on every branching node once an incumbent exists (quirks=0, not with best_window).  The dictionary's "rc" is
-    mvx_branchAndBound's return code (-1 refused parameters, -2 penalties, heuristic or tightening unavailable)."""
+    tightening on every branching node once an incumbent exists (quirks=0, not with best_window).  prop 1..16: node bound
+    propagation of the root and of every child with that round limit (quirks=0, not with best_window).  The dictionary's "rc"
+    is mvx_branchAndBound's return code (-1 refused parameters, -2 penalties, heuristic, tightening or propagation
+    unavailable)."""
     L = lib()
     pr = make_params(var_strat, node_strat, cut_strat, max_nodes, quirks, lazy_pool, window, cut_select, cut_chance, best_window, sb_cands,
-                     sb_iters, heur, rc_fix)
+                     sb_iters, heur, rc_fix, prop)
     res = BnbResult()
     tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
     rc = L.mvx_branchAndBound(tptr, prob.h, C.byref(pr), C.byref(res))
@@ -438,6 +457,62 @@ def tighten_cols_many(probs, lists):
     ub = np.array([e[2] for l in lists for e in l] or [0.0], dtype=np.float64)
     DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
     return lib().mvx_tighten_cols_many(hs, len(probs), off.ctypes.data_as(IP), flat.ctypes.data_as(IP), lb.ctypes.data_as(DP), ub.ctypes.data_as(DP))
+
+
+def _prop_lists(k, n, inf, rounds, cnt, cols, lb, ub):
+    return [(int(inf[t]), int(rounds[t]), [(int(cols[t * n + i]), float(lb[t * n + i]), float(ub[t * n + i])) for i in range(int(cnt[t]))])
+            for t in range(k)]
+
+
+def propagate_many(root, probs, max_rounds=8):
+    """mvx_propagate_many over capi.Prob handles of the gfx950 engine (solved or not) against the rows of `root`: one launch
+    for all handles and all rounds.  Returns (rc, [(infeasible, rounds, [(column, lb, ub), ...]) per handle]), columns
+    ascending, +-inf for an absent bound."""
+    import numpy as np
+
+    k = len(probs)
+    n = root.n
+    hs = (C.c_void_p * max(1, k))(*[p.h for p in probs])
+    inf, rounds, cnt = (np.zeros(max(1, k), dtype=np.int32) for _ in range(3))
+    cols = np.zeros(max(1, k * n), dtype=np.int32)
+    lb, ub = np.zeros(max(1, k * n)), np.zeros(max(1, k * n))
+    DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    rc = lib().mvx_propagate_many(root.h, hs, k, max_rounds, inf.ctypes.data_as(IP), rounds.ctypes.data_as(IP), cnt.ctypes.data_as(IP),
+                                  cols.ctypes.data_as(IP), lb.ctypes.data_as(DP), ub.ctypes.data_as(DP))
+    if rc != 0:
+        return rc, None
+    return rc, _prop_lists(k, n, inf, rounds, cnt, cols, lb, ub)
+
+
+def propagate_node(prob, root, max_rounds=8, table=None):
+    """mvx_bnb_propagate (the host twin, through `table`; None = the gfx950 engine's table) on one handle against the rows of
+    `root`.  Returns (rc, (infeasible, rounds, [(column, lb, ub), ...]))."""
+    import numpy as np
+
+    n = root.n
+    inf, rounds, cnt = (np.zeros(1, dtype=np.int32) for _ in range(3))
+    cols = np.zeros(max(1, n), dtype=np.int32)
+    lb, ub = np.zeros(max(1, n)), np.zeros(max(1, n))
+    DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
+    rc = lib().mvx_bnb_propagate(tptr, prob.h, root.h, max_rounds, inf.ctypes.data_as(IP), rounds.ctypes.data_as(IP), cnt.ctypes.data_as(IP),
+                                 cols.ctypes.data_as(IP), lb.ctypes.data_as(DP), ub.ctypes.data_as(DP))
+    if rc != 0:
+        return rc, None
+    return rc, _prop_lists(1, n, inf, rounds, cnt, cols, lb, ub)[0]
+
+
+def set_col_bnds_many(probs, lists):
+    """mvx_set_col_bnds_many: handle t of the gfx950 engine takes the (column, lb, ub) entries of lists[t] (+-inf for an absent
+    bound), all of them in one launch; every handle is left as mvx_set_col_bnds per entry would leave it.  Returns the call's
+    code (0; -1 and nothing changed for a bad list)."""
+    hs, off, flat = _flat(probs, [[e[0] for e in l] for l in lists])
+    import numpy as np
+
+    lb = np.array([e[1] for l in lists for e in l] or [0.0], dtype=np.float64)
+    ub = np.array([e[2] for l in lists for e in l] or [0.0], dtype=np.float64)
+    DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    return lib().mvx_set_col_bnds_many(hs, len(probs), off.ctypes.data_as(IP), flat.ctypes.data_as(IP), lb.ctypes.data_as(DP), ub.ctypes.data_as(DP))
 
 
 def node_sample(root, count, quirks=0, table=None):

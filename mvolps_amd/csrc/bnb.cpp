@@ -37,6 +37,10 @@ extern "C" int mvx_rc_tighten_many(const mvx_prob *const *Ps, int count, const d
                                    double *ub) __attribute__((weak));
 extern "C" int mvx_tighten_cols_many(mvx_prob *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub)
     __attribute__((weak));
+extern "C" int mvx_propagate_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, int max_rounds, int *infeasible, int *rounds,
+                                  int *cnt, int *cols, double *lb, double *ub) __attribute__((weak));
+extern "C" int mvx_set_col_bnds_many(mvx_prob *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub)
+    __attribute__((weak));
 
 namespace {
 
@@ -1209,6 +1213,229 @@ private:
   const mvx_lp_api *_api;
 };
 
+// ---- node bound propagation (prop, DESIGN.md "Node bound propagation") ----
+
+// The rows the propagation reads, taken once per tree from the root through the table: rows 1..m0 with their non-zeros in
+// ascending column order and by column, their bounds (+-inf where absent) and which columns are integer.
+struct PropHost {
+  int m0 = 0, n = 0;
+  std::vector<std::vector<std::pair<int, double>>> rows, cols; // rows[i-1]: (j, a_ij) ascending j; cols[j]: (i-1, a_ij) ascending i
+  std::vector<double> rlo, rhi;
+  std::vector<char> isint;
+};
+
+static int prop_host_model(const mvx_lp_api *api, const void *root, PropHost &M) {
+  if (!api->get_mat_row || !api->get_row_lb || !api->get_row_ub || !api->get_col_lb || !api->get_col_ub || !api->get_col_kind) return -2;
+  const int m0 = api->get_num_rows(root), n = api->get_num_cols(root);
+  M.m0 = m0;
+  M.n = n;
+  M.rows.assign((size_t)m0, {});
+  M.cols.assign((size_t)n + 1, {});
+  M.rlo.resize((size_t)m0);
+  M.rhi.resize((size_t)m0);
+  M.isint.assign((size_t)n + 1, 0);
+  std::vector<int> ind((size_t)n + 1);
+  std::vector<double> val((size_t)n + 1);
+  for (int i = 1; i <= m0; i++) {
+    const int len = api->get_mat_row(root, i, ind.data(), val.data());
+    auto &row = M.rows[(size_t)i - 1];
+    for (int k = 1; k <= len; k++)
+      if (val[(size_t)k] != 0.0) row.emplace_back(ind[(size_t)k], val[(size_t)k]);
+    std::sort(row.begin(), row.end());
+    M.rlo[(size_t)i - 1] = tab_bound(api->get_row_lb(root, i));
+    M.rhi[(size_t)i - 1] = tab_bound(api->get_row_ub(root, i));
+    for (const auto &e : row) M.cols[(size_t)e.first].emplace_back(i - 1, e.second);
+  }
+  for (int j = 1; j <= n; j++) M.isint[(size_t)j] = api->get_col_kind(root, j) != MVX_CV;
+  return 0;
+}
+
+struct PropOut {
+  int infeasible = 0, rounds = 0;
+  RcList list; // the columns whose bounds changed, ascending; +-inf for an absent bound; empty when infeasible
+};
+
+// The propagation of one handle from its own column bounds (the host twin of k_prop: same tests, every product, sum and
+// quotient rounded on its own, in the same order).
+static int prop_host(const mvx_lp_api *api, const PropHost &M, const void *P, int max_rounds, PropOut &out) {
+  const int n = M.n, m0 = M.m0;
+  out = PropOut();
+  if (!P || max_rounds < 1 || api->get_num_cols(P) != n) return -1;
+  std::vector<double> l0((size_t)n + 1, 0.0), u0((size_t)n + 1, 0.0);
+  for (int j = 1; j <= n; j++) {
+    l0[(size_t)j] = tab_bound(api->get_col_lb(P, j));
+    u0[(size_t)j] = tab_bound(api->get_col_ub(P, j));
+  }
+  std::vector<double> l = l0, u = u0, amin((size_t)m0), amax((size_t)m0);
+  std::vector<int> kmins((size_t)m0), kmaxs((size_t)m0);
+  for (int r = 0; r < max_rounds && !out.infeasible; r++) {
+    out.rounds = r + 1;
+    for (int i = 0; i < m0; i++) {
+      double lmin = 0.0, lmax = 0.0;
+      int kmin = 0, kmax = 0;
+      for (const auto &e : M.rows[(size_t)i]) {
+        const double v = e.second;
+        const double bmin = v > 0.0 ? l[(size_t)e.first] : u[(size_t)e.first], bmax = v > 0.0 ? u[(size_t)e.first] : l[(size_t)e.first];
+        if (std::isinf(bmin)) kmin++;
+        else lmin = lmin + v * bmin;
+        if (std::isinf(bmax)) kmax++;
+        else lmax = lmax + v * bmax;
+      }
+      amin[(size_t)i] = lmin;
+      amax[(size_t)i] = lmax;
+      kmins[(size_t)i] = kmin;
+      kmaxs[(size_t)i] = kmax;
+      const double lo = M.rlo[(size_t)i], hi = M.rhi[(size_t)i];
+      if ((kmin == 0 && std::isfinite(hi) && lmin > hi + round_tol(hi)) || (kmax == 0 && std::isfinite(lo) && lmax < lo - round_tol(lo)))
+        out.infeasible = 1;
+    }
+    if (out.infeasible) break;
+    bool changed = false;
+    std::vector<double> nl = l, nu = u; // Jacobi: every candidate comes from the bounds the round started with
+    for (int j = 1; j <= n; j++) {
+      if (!M.isint[(size_t)j]) continue;
+      const double lj = l[(size_t)j], uj = u[(size_t)j];
+      double a = lj, b = uj;
+      for (const auto &e : M.cols[(size_t)j]) {
+        const int i = e.first;
+        const double v = e.second;
+        const int kmin = kmins[(size_t)i], kmax = kmaxs[(size_t)i];
+        const double lo = M.rlo[(size_t)i], hi = M.rhi[(size_t)i];
+        const double bmin = v > 0.0 ? lj : uj, bmax = v > 0.0 ? uj : lj;
+        if (std::isfinite(hi) && (kmin == 0 || (kmin == 1 && std::isinf(bmin)))) {
+          const double res = kmin == 0 ? amin[(size_t)i] - v * bmin : amin[(size_t)i];
+          const double q = (hi - res) / v;
+          if (std::isfinite(q)) {
+            if (v > 0.0) {
+              const double c = std::floor(q + round_tol(q));
+              if (c < b) b = c;
+            } else {
+              const double c = std::ceil(q - round_tol(q));
+              if (c > a) a = c;
+            }
+          }
+        }
+        if (std::isfinite(lo) && (kmax == 0 || (kmax == 1 && std::isinf(bmax)))) {
+          const double res = kmax == 0 ? amax[(size_t)i] - v * bmax : amax[(size_t)i];
+          const double q = (lo - res) / v;
+          if (std::isfinite(q)) {
+            if (v > 0.0) {
+              const double c = std::ceil(q - round_tol(q));
+              if (c > a) a = c;
+            } else {
+              const double c = std::floor(q + round_tol(q));
+              if (c < b) b = c;
+            }
+          }
+        }
+      }
+      if (a != lj || b != uj) {
+        nl[(size_t)j] = a;
+        nu[(size_t)j] = b;
+        changed = true;
+      }
+      if (a > b) out.infeasible = 1;
+    }
+    l.swap(nl);
+    u.swap(nu);
+    if (!changed) break;
+  }
+  if (!out.infeasible)
+    for (int j = 1; j <= n; j++)
+      if (l[(size_t)j] != l0[(size_t)j] || u[(size_t)j] != u0[(size_t)j]) out.list.push_back(RcEntry{j, l[(size_t)j], u[(size_t)j]});
+  return 0;
+}
+
+// One tree's propagation: a batch of handles through propagate_many (one call) when the table has it and the model fits the
+// kernel, else the host twin with the rows read once; the lists go on through set_col_bnds_many (one call), else
+// set_col_bnds per entry.  A result depends on the handle's own bounds and the root's rows only.
+class Prop {
+public:
+  Prop(const mvx_lp_api *api, const void *root, int max_rounds) : _api(api), _root(root), _rounds(max_rounds) {}
+  long long calls = 0, fixed = 0, tightened = 0, infeasible = 0;
+  // 0, or the failing call's code (-2: neither propagate_many nor the twin's accessors)
+  int compute(const std::vector<void *> &hs, std::vector<PropOut> &out) {
+    const size_t K = hs.size();
+    out.assign(K, PropOut());
+    if (K == 0) return 0;
+    if (_api->propagate_many && _device) {
+      const size_t n = (size_t)_api->get_num_cols(_root);
+      std::vector<int> inf(K), rounds(K), cnt(K), cols(K * n + 1);
+      std::vector<double> lb(K * n + 1), ub(K * n + 1);
+      const int rc = _api->propagate_many(_root, hs.data(), (int)K, _rounds, inf.data(), rounds.data(), cnt.data(), cols.data(), lb.data(), ub.data());
+      if (rc == 0) {
+        for (size_t t = 0; t < K; t++) {
+          out[t].infeasible = inf[t];
+          out[t].rounds = rounds[t];
+          for (int k = 0; k < cnt[t]; k++) out[t].list.push_back(RcEntry{cols[t * n + (size_t)k], lb[t * n + (size_t)k], ub[t * n + (size_t)k]});
+        }
+        return 0;
+      }
+      if (rc != -5) return rc;
+      _device = false; // more columns than the kernel holds: the host twin, same bits, for the rest of the tree
+    }
+    if (!_ready) {
+      if (prop_host_model(_api, _root, _M) != 0) return -2;
+      _ready = true;
+    }
+    for (size_t t = 0; t < K; t++) {
+      const int rc = prop_host(_api, _M, hs[t], _rounds, out[t]);
+      if (rc != 0) return rc;
+    }
+    return 0;
+  }
+  // the handles take their lists (a handle proved infeasible has none and keeps its bounds) and are booked
+  int apply(const std::vector<void *> &hs, const std::vector<PropOut> &res) {
+    for (const PropOut &o : res) {
+      calls++;
+      infeasible += o.infeasible;
+      for (const RcEntry &e : o.list) (e.lb == e.ub ? fixed : tightened)++;
+    }
+    if (_api->set_col_bnds_many) {
+      std::vector<int> off(1, 0), cols;
+      std::vector<double> lb, ub;
+      for (const PropOut &o : res) {
+        for (const RcEntry &e : o.list) {
+          cols.push_back(e.col);
+          lb.push_back(e.lb);
+          ub.push_back(e.ub);
+        }
+        off.push_back((int)cols.size());
+      }
+      if (cols.empty()) return 0;
+      return _api->set_col_bnds_many(hs.data(), (int)hs.size(), off.data(), cols.data(), lb.data(), ub.data());
+    }
+    for (size_t k = 0; k < hs.size(); k++)
+      for (const RcEntry &e : res[k].list) {
+        const bool has_l = std::isfinite(e.lb), has_u = std::isfinite(e.ub);
+        _api->set_col_bnds(hs[k], e.col, has_l && has_u ? (e.lb == e.ub ? MVX_FX : MVX_DB) : has_l ? MVX_LO : has_u ? MVX_UP : MVX_FR, e.lb,
+                           e.ub);
+      }
+    return 0;
+  }
+  // compute + apply on a batch of children in front of their first solve
+  int run(const std::vector<void *> &hs) {
+    std::vector<PropOut> res;
+    const int rc = compute(hs, res);
+    if (rc != 0) return rc;
+    return apply(hs, res);
+  }
+  void store(mvx_bnb_result *res) const {
+    res->prop_calls = calls;
+    res->prop_fixed = fixed;
+    res->prop_tightened = tightened;
+    res->prop_infeasible = infeasible;
+  }
+
+private:
+  const mvx_lp_api *_api;
+  const void *_root;
+  int _rounds;
+  bool _device = true; // propagate_many is used while it accepts the model
+  bool _ready = false;
+  PropHost _M;
+};
+
 int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm, mvx_bnb_result *res) { // bs.cpp:54
   MVOLP::ParameterObj params(api, prob, prm);
   CutPool pool(api);
@@ -1234,6 +1461,7 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm,
   Heuristic heur(api, prob, prm.heur);
   HeurBook hbook;
   RcFix rcfix(api);
+  Prop prop(api, prob, prm.prop);
 
   while (!leafContainer.empty()) { // bs.cpp:96
     if (prm.max_nodes > 0 && count >= prm.max_nodes) {
@@ -1369,6 +1597,12 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm,
         rc_out = -2;
         break;
       }
+      // prop: both children behind their branching bound and the rc_fix list, in front of their first solve; whatever code
+      // a failing call gives (no accessors, device memory, a refused list), the tree so far goes back with -2
+      if (prm.prop > 0 && prop.run({S2->prob, S3->prob}) != 0) {
+        rc_out = -2;
+        break;
+      }
       // bs.cpp:279 and :287 solve two independent clones; an engine with a batch entry runs them
       // side by side (identical results), otherwise one after the other as the reference does
       if (api->simplex_batch) {
@@ -1404,6 +1638,7 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm,
   res->sb_pivots = sb_pivots;
   hbook.store(res);
   rcfix.store(res);
+  prop.store(res);
   return rc_out;
 }
 
@@ -1432,6 +1667,7 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
   Heuristic heur(api, prob, prm.heur);
   HeurBook hbook;
   RcFix rcfix(api);
+  Prop prop(api, prob, prm.prop);
 
   struct Branch {
     size_t slot;
@@ -1822,6 +2058,19 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
         stop = true;
       }
     }
+    // prop: every child of the round in one compute and one apply call, behind its branching bound and its rc_fix list, in
+    // front of the round's batched solve.  A child's result depends on its own bounds only: the serial driver's
+    if (prm.prop > 0 && !branches.empty() && rc_out == 0) {
+      std::vector<void *> kids;
+      for (const Branch &br : branches) {
+        kids.push_back(br.S2->prob);
+        kids.push_back(br.S3->prob);
+      }
+      if (prop.run(kids) != 0) {
+        rc_out = -2;
+        stop = true;
+      }
+    }
     tB += now() - t0;
     // C. every child of this round is an independent LP (bs.cpp:279,287): batched solves on worker threads; then, for
     // the children found infeasible (or unbounded), the re-solve bs.cpp:117 will ask for when they are
@@ -1907,6 +2156,7 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
   res->sb_pivots = sb_pivots;
   hbook.store(res);
   rcfix.store(res);
+  prop.store(res);
   return rc_out;
 }
 
@@ -2288,6 +2538,13 @@ const mvx_lp_api g_hip_api = {
     mvx_tighten_cols_many ? +[](void *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub) {
       return mvx_tighten_cols_many((mvx_prob *const *)Ps, count, off, cols, lb, ub);
     } : nullptr,
+    mvx_propagate_many ? +[](const void *root, const void *const *Ps, int count, int max_rounds, int *infeasible, int *rounds, int *cnt, int *cols,
+                             double *lb, double *ub) {
+      return mvx_propagate_many((const mvx_prob *)root, (const mvx_prob *const *)Ps, count, max_rounds, infeasible, rounds, cnt, cols, lb, ub);
+    } : nullptr,
+    mvx_set_col_bnds_many ? +[](void *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub) {
+      return mvx_set_col_bnds_many((mvx_prob *const *)Ps, count, off, cols, lb, ub);
+    } : nullptr,
 };
 
 } // namespace
@@ -2312,6 +2569,7 @@ void mvx_bnb_default_params(mvx_bnb_params *p) {
   p->sb_iters = 4;
   p->heur = 0;
   p->rc_fix = 0;
+  p->prop = 0;
 }
 
 // Repaired mode's rule for an integer column whose bounds are not integers (legal input: LP and MPS files may carry them):
@@ -2361,22 +2619,47 @@ int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *
   if (params->var_strat < 0 || params->var_strat > 4 || (params->var_strat >= 3 && params->best_window > 0) || params->heur < 0 ||
       params->heur > 2 || (params->heur > 0 && params->reference_quirks != 0) || params->rc_fix < 0 || params->rc_fix > 1 ||
       // rc_fix: the bound argument needs the repaired mode's children and cuts; not (yet) in the best-bound window
-      (params->rc_fix > 0 && (params->reference_quirks != 0 || params->best_window > 0))) {
+      (params->rc_fix > 0 && (params->reference_quirks != 0 || params->best_window > 0)) ||
+      // prop: children with both bounds kept, and not (yet) in the best-bound window either
+      params->prop < 0 || params->prop > 16 || (params->prop > 0 && (params->reference_quirks != 0 || params->best_window > 0))) {
     std::memset(res, 0, sizeof(*res));
     return -1;
   }
-  if (params->reference_quirks == 0 && integral_bounds(api, prob, false) != 0) {
-    // the caller's handle stays as it is: the tree runs on a copy with the rounded bounds
+  if (params->reference_quirks == 0 && (params->prop > 0 || integral_bounds(api, prob, false) != 0)) {
+    // the caller's handle stays as it is: the tree runs on a copy with the rounded (and, with prop, propagated) bounds
     void *work = api->create_prob();
     api->copy_prob(work, prob, MVX_OFF);
     int rc = 0;
-    if (integral_bounds(api, work, true) == 2) { // no integer in some column's range: the root is infeasible, nothing to solve
+    // no integer in some column's range, or the propagation proves it: the root is infeasible, nothing to solve
+    auto infeasible_root = [&](int prune) {
       Recorder rec;
       rec.node(1, 0);
-      rec.prune[1] = MVOLP::FEAS;
+      rec.prune[1] = prune;
       const double sg = (api->get_obj_dir && api->get_obj_dir(prob) == MVX_MIN) ? -1.0 : 1.0;
       const int n0 = api->get_num_cols(prob);
       pack_result(res, rec, 2, 0, 0, -sg * std::numeric_limits<double>::infinity(), 0, n0, std::vector<double>((size_t)n0 + 1, 0.0), 0);
+    };
+    if (integral_bounds(api, work, true) == 2) {
+      infeasible_root(MVOLP::FEAS);
+    } else if (params->prop > 0) {
+      // the root's own propagation, on the same copy: its list is applied before the first solve
+      Prop root_prop(api, work, params->prop);
+      std::vector<PropOut> got;
+      if (root_prop.compute({work}, got) != 0) {
+        infeasible_root(MVOLP::NONE); // nothing ran: the tree so far is the unsolved root
+        rc = -2;
+      } else if (got[0].infeasible) {
+        root_prop.apply({work}, got);
+        infeasible_root(MVOLP::FEAS);
+        root_prop.store(res);
+      } else {
+        root_prop.apply({work}, got);
+        rc = run_driver(api, work, params, res);
+        res->prop_calls += root_prop.calls;
+        res->prop_fixed += root_prop.fixed;
+        res->prop_tightened += root_prop.tightened;
+        res->prop_infeasible += root_prop.infeasible;
+      }
     } else {
       rc = run_driver(api, work, params, res);
     }
@@ -2462,6 +2745,28 @@ int mvx_bnb_rc_tighten(const mvx_lp_api *api, const void *prob, double cutoff, d
     cols[k] = l[k].col;
     lb[k] = l[k].lb;
     ub[k] = l[k].ub;
+  }
+  return 0;
+}
+
+int mvx_bnb_propagate(const mvx_lp_api *api, const void *prob, const void *root, int max_rounds, int *infeasible, int *rounds, int *cnt,
+                      int *cols, double *lb, double *ub) {
+  if (!api) api = &g_hip_api;
+  if (!prob || !root || max_rounds < 1 || !infeasible || !rounds || !cnt || !cols || !lb || !ub) return -1;
+  PropHost M;
+  *infeasible = *rounds = *cnt = 0;
+  int rc = prop_host_model(api, root, M);
+  if (rc != 0) return rc;
+  PropOut out;
+  rc = prop_host(api, M, prob, max_rounds, out);
+  if (rc != 0) return rc;
+  *infeasible = out.infeasible;
+  *rounds = out.rounds;
+  *cnt = (int)out.list.size();
+  for (size_t k = 0; k < out.list.size(); k++) {
+    cols[k] = out.list[k].col;
+    lb[k] = out.list[k].lb;
+    ub[k] = out.list[k].ub;
   }
   return 0;
 }

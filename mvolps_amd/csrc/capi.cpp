@@ -520,6 +520,13 @@ int mvx_rc_tighten_many(const mvx_prob *const *Ps, int count, const double *cuto
 int mvx_tighten_cols_many(mvx_prob *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub) {
   return mvx::engine_tighten_many(Ps, count, off, cols, lb, ub);
 }
+int mvx_propagate_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, int max_rounds, int *infeasible, int *rounds, int *cnt,
+                       int *cols, double *lb, double *ub) {
+  return mvx::engine_propagate_many(root, Ps, count, max_rounds, infeasible, rounds, cnt, cols, lb, ub);
+}
+int mvx_set_col_bnds_many(mvx_prob *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub) {
+  return mvx::engine_set_bounds_many(Ps, count, off, cols, lb, ub);
+}
 
 int mvx_device_count(void) { return mvx::device_count(); }
 int mvx_set_device(int dev) { return mvx::set_device(dev); }

@@ -9,10 +9,12 @@
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
+#include <limits>
 #include <map>
 #include <mutex>
 #include <tuple>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "engine.hpp"
@@ -37,12 +39,15 @@ struct DevMatrix {
 struct RoundModel {
   int m0 = 0, n = 0, ldm = 0, dir = 0;
   void *dev = nullptr; // [At (n+1) x ldm][rlo m0][rhi m0][clo n+1][chi n+1][c n+1][flags n+1]
+  void *dev_rows = nullptr; // [Ar m0 x ldn]: the same rows by row, for k_prop; uploaded on the first propagation
+  int ldn = 0;
   size_t o_rlo = 0, o_rhi = 0, o_clo = 0, o_chi = 0, o_c = 0, o_flags = 0;
   std::vector<mvx::RowPtr> rows; // owned: a row's address cannot be reused while the model compares against it
   std::vector<double> c, clb, cub, rlb, rub;
   std::vector<int> kind;
   ~RoundModel() {
     if (dev) (void)hipFree(dev);
+    if (dev_rows) (void)hipFree(dev_rows);
   }
 };
 
@@ -89,6 +94,8 @@ void launch_penalty(const PenArgs &a, hipStream_t);
 void launch_round(const RndArgs &a, hipStream_t);
 void launch_rcfix(const RcArgs &a, hipStream_t);
 void launch_tighten(const TightHandle *hs, const TightEntry *es, int count, hipStream_t);
+void launch_prop(const PropArgs &a, hipStream_t);
+void launch_setbnds(const SetbHandle *hs, const SetbEntry *es, const SetbShift *ss, int handles, hipStream_t);
 void launch_refresh_select(Ctl *, const int *tflag, int var, hipStream_t);
 size_t persist_lds_bytes(int m, int cpw);
 int persist_max_cpw();
@@ -2715,6 +2722,208 @@ int engine_round_many(const mvx_prob *root, const mvx_prob *const *Ps, int count
   std::memcpy(obj, hb + o_obj, (size_t)count * 8);
   std::memcpy(found, hb + o_found, (size_t)count * 4);
   std::memcpy(x, hb + o_x, (size_t)count * (n + 1) * 8);
+  return 0;
+}
+
+// ------------------------------------------------------------------ node bound propagation (k_prop, k_setbnds)
+// The second orientation of root's rounding model, rows 1..m0 by row (Ar[i][j]), next to the first: k_prop's column phase
+// reads a row of consecutive columns at a time.  Built on the first propagation over this model.
+static bool round_model_rows(Context &c, const mvx_prob *R, RoundModel *M) {
+  if (M->dev_rows) return true;
+  const int m0 = M->m0, n = M->n;
+  const size_t ldn = align_up((size_t)n + 1, 64);
+  std::vector<double> h((size_t)std::max(1, m0) * ldn, 0.0);
+  for (int i = 1; i <= m0; i++) std::memcpy(h.data() + (size_t)(i - 1) * ldn, R->A[(size_t)i]->data(), (size_t)(n + 1) * 8);
+  if (hipMalloc(&M->dev_rows, h.size() * 8) != hipSuccess) {
+    (void)hipGetLastError();
+    M->dev_rows = nullptr;
+    g_last_error.store(MVX_ENOMEM);
+    return false;
+  }
+  HIPCHECK(hipMemcpyAsync(M->dev_rows, h.data(), h.size() * 8, hipMemcpyHostToDevice, c.main.stream));
+  HIPCHECK(hipStreamSynchronize(c.main.stream)); // the pageable source goes out of scope
+  M->ldn = (int)ldn;
+  return true;
+}
+
+// Node bound propagation of `count` handles over root's rows (mvx_propagate_many): the handles' bounds go up with the call
+// through the node-entry arena, one k_prop launch runs every round of every handle, the final bounds come back and are
+// compared with what went up.  Return codes: 0; -1 bad arguments; -2 device out of memory; -5 n > RND_NMAX.
+int engine_propagate_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, int max_rounds, int *infeasible, int *rounds, int *cnt,
+                          int *cols, double *lb, double *ub) {
+  if (!root || count < 1 || !Ps || max_rounds < 1 || !infeasible || !rounds || !cnt || !cols || !lb || !ub) return -1;
+  const int n = root->n, m0 = root->m;
+  for (int t = 0; t < count; t++)
+    if (!Ps[t] || Ps[t]->n != n) return -1;
+  if (n > RND_NMAX) return -5;
+  Context &c = ctx();
+  bind_device(c);
+  MAIN_LOCK(c);
+  SolveCtx &sc = c.main;
+  const RoundModel *M = round_model(c, root);
+  if (!M || !round_model_rows(c, root, root->rmod.get())) return -2;
+  Carver carve;
+  // up: [lb0][ub0]; back: [lb][ub][info]; device only: the row activities when they do not fit in LDS
+  const size_t nb = (size_t)count * (size_t)(n + 1) * 8;
+  const size_t o_lb0 = carve(nb), o_ub0 = carve(nb), up_bytes = carve.off;
+  const size_t o_lb = carve(nb), o_ub = carve(nb), o_info = carve((size_t)count * 8);
+  const size_t host_bytes = carve.off;
+  const bool spill = m0 > RND_NMAX;
+  const size_t o_act = carve(spill ? (size_t)count * 2 * (size_t)m0 * 8 : 0), o_actk = carve(spill ? (size_t)count * (size_t)m0 * 4 : 0);
+  if (!node_scratch_reserve(c, carve.off, host_bytes)) return -2;
+  unsigned char *hb = (unsigned char *)c.nodes.host, *db = (unsigned char *)c.nodes.dev;
+  for (int t = 0; t < count; t++) {
+    std::memcpy(hb + o_lb0 + (size_t)t * (size_t)(n + 1) * 8, Ps[t]->clb.data(), (size_t)(n + 1) * 8);
+    std::memcpy(hb + o_ub0 + (size_t)t * (size_t)(n + 1) * 8, Ps[t]->cub.data(), (size_t)(n + 1) * 8);
+  }
+  HIPCHECK(hipMemcpyAsync(db, hb, up_bytes, hipMemcpyHostToDevice, sc.stream));
+  const unsigned char *mb = (const unsigned char *)M->dev;
+  PropArgs a;
+  a.At = (const double *)mb;
+  a.Ar = (const double *)M->dev_rows;
+  a.rlo = (const double *)(mb + M->o_rlo); a.rhi = (const double *)(mb + M->o_rhi);
+  a.flags = (const int *)(mb + M->o_flags);
+  a.lb0 = (const double *)(db + o_lb0); a.ub0 = (const double *)(db + o_ub0);
+  a.lb = (double *)(db + o_lb); a.ub = (double *)(db + o_ub); a.info = (int *)(db + o_info);
+  a.act = spill ? (double *)(db + o_act) : nullptr;
+  a.actk = spill ? (int *)(db + o_actk) : nullptr;
+  a.n = n; a.m0 = m0; a.ldm = M->ldm; a.ldn = M->ldn; a.max_rounds = max_rounds; a.count = count;
+  launch_prop(a, sc.stream);
+  HIPCHECK(hipMemcpyAsync(hb + o_lb, db + o_lb, host_bytes - o_lb, hipMemcpyDeviceToHost, sc.stream));
+  HIPCHECK(hipStreamSynchronize(sc.stream));
+  const int *h_info = (const int *)(hb + o_info);
+  for (int t = 0; t < count; t++) {
+    const double *l0 = Ps[t]->clb.data(), *u0 = Ps[t]->cub.data();
+    const double *l1 = (const double *)(hb + o_lb) + (size_t)t * (size_t)(n + 1), *u1 = (const double *)(hb + o_ub) + (size_t)t * (size_t)(n + 1);
+    infeasible[t] = h_info[2 * t];
+    rounds[t] = h_info[2 * t + 1];
+    int k = 0;
+    if (!infeasible[t])
+      for (int j = 1; j <= n; j++)
+        if (l1[j] != l0[j] || u1[j] != u0[j]) {
+          const size_t o = (size_t)t * (size_t)n + (size_t)k++;
+          cols[o] = j;
+          lb[o] = l1[j];
+          ub[o] = u1[j];
+        }
+    cnt[t] = k;
+  }
+  return 0;
+}
+
+// General bound lists of many handles with one launch (mvx_set_col_bnds_many).  Every list is checked first (-1 changes
+// nothing).  Then each entry does on the host what mvx_set_col_bnds + engine_apply_bounds do, in list order -- the model, the
+// nflag mirror, the pending edits of basic rows (merged by row; flushed when the ninth arrives), hint_dual, status -- and
+// what they would have launched is collected: bound writes (one per row or position and handle: the last one the ordered
+// launches would have made) and shifts of column 0, which leave as one k_setbnds launch.
+int engine_set_bounds_many(mvx_prob *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub) {
+  if (count < 0 || (count > 0 && (!Ps || !off))) return -1;
+  if (count == 0) return 0;
+  if (off[0] < 0) return -1;
+  std::unordered_set<const mvx_prob *> seen;
+  for (int t = 0; t < count; t++)
+    if (!Ps[t] || off[t + 1] < off[t] || !seen.insert(Ps[t]).second) return -1;
+  if (off[count] == off[0]) return 0;
+  if (!cols || !lb || !ub) return -1;
+  const double inf = std::numeric_limits<double>::infinity();
+  for (int t = 0; t < count; t++) {
+    int prev = 0;
+    for (int k = off[t]; k < off[t + 1]; k++) {
+      const int j = cols[k];
+      if (j < 1 || j > Ps[t]->n || j <= prev || !(lb[k] <= ub[k]) || lb[k] == inf || ub[k] == -inf) return -1;
+      prev = j;
+    }
+  }
+  std::vector<SetbHandle> hs;
+  std::vector<SetbEntry> es;
+  std::vector<SetbShift> ss;
+  bool device = false; // a handle without a tableau is a model edit only, as in mvx_set_col_bnds: no engine call
+  for (int t = 0; t < count; t++) device = device || (Ps[t]->valid && off[t + 1] > off[t]);
+  std::unique_lock<std::recursive_mutex> lock;
+  if (device) {
+    Context &c = ctx();
+    bind_device(c);
+    lock = std::unique_lock<std::recursive_mutex>(c.main_mu);
+  }
+  // laid out for the most the lists can ask for, so that out of memory is known before anything is edited
+  const size_t total = (size_t)(off[count] - off[0]);
+  Carver carve;
+  const size_t o_hs = carve((size_t)count * sizeof(SetbHandle)), o_es = carve((total + (size_t)count * MAX_EDITS) * sizeof(SetbEntry)),
+               o_ss = carve(total * sizeof(SetbShift));
+  if (device && !node_scratch_reserve(ctx(), carve.off, carve.off)) return -2;
+  for (int t = 0; t < count; t++) {
+    mvx_prob *P = Ps[t];
+    if (off[t + 1] == off[t]) continue;
+    SetbHandle h{P->d_T, P->d_blb, P->d_bub, P->d_nlb, P->d_nub, P->d_nflag, P->ld, P->m, (int)es.size(), 0, (int)ss.size(), 0};
+    // A row can be sent twice by one list: a pending edit of column j's row goes out with the first eight, j's own entry
+    // queues the row again and a later overflow sends it.  The per-entry path's launches are ordered, so the later bounds
+    // win; the lanes of one launch are not, so each row has ONE entry per handle and a later flush overwrites it.
+    std::unordered_map<int, size_t> sent; // row -> its entry in es
+    for (int k = off[t]; k < off[t + 1]; k++) {
+      const int j = cols[k];
+      const bool has_l = std::isfinite(lb[k]), has_u = std::isfinite(ub[k]);
+      const int type = has_l && has_u ? (lb[k] == ub[k] ? MVX_FX : MVX_DB) : has_l ? MVX_LO : has_u ? MVX_UP : MVX_FR;
+      const double olb = P->clb[(size_t)j], oub = P->cub[(size_t)j];
+      P->ctype[(size_t)j] = type;
+      P->clb[(size_t)j] = lb[k];
+      P->cub[(size_t)j] = ub[k];
+      if (!P->valid) continue;
+      const int pos = P->pos[(size_t)(P->m + j)];
+      if (pos > 0) {
+        bool merged = false;
+        for (auto &e : P->pending)
+          if (e.row == pos) {
+            e.lb = lb[k];
+            e.ub = ub[k];
+            merged = true;
+          }
+        if (!merged) {
+          if ((int)P->pending.size() == MAX_EDITS) {
+            for (const auto &e : P->pending) {
+              auto it = sent.find(e.row);
+              if (it != sent.end()) {
+                es[it->second].lb = e.lb;
+                es[it->second].ub = e.ub;
+              } else {
+                sent.emplace(e.row, es.size());
+                es.push_back(SetbEntry{e.lb, e.ub, e.row, -1});
+              }
+            }
+            P->pending.clear();
+          }
+          P->pending.push_back({pos, lb[k], ub[k]});
+        }
+        P->hint_dual = true;
+      } else {
+        const int jj = -pos;
+        const double xo = nb_value(P->nflag[(size_t)jj], olb, oub);
+        const int flag = type == MVX_FR ? MVX_NF : type == MVX_LO ? MVX_NL : type == MVX_UP ? MVX_NU
+                         : type == MVX_DB ? (P->nflag[(size_t)jj] == MVX_NU ? MVX_NU : MVX_NL) : MVX_NS;
+        P->nflag[(size_t)jj] = flag;
+        es.push_back(SetbEntry{lb[k], ub[k], jj, flag});
+        const double xn = nb_value(flag, lb[k], ub[k]);
+        if (xn != xo) ss.push_back(SetbShift{xn - xo, jj, 0});
+      }
+    }
+    P->status = MVX_UNDEF;
+    if (!P->valid) continue;
+    P->sol_fresh = false;
+    P->fresh_rows = -1;
+    h.e1 = (int)es.size();
+    h.s1 = (int)ss.size();
+    if (h.e1 > h.e0 || h.s1 > h.s0) hs.push_back(h);
+  }
+  if (hs.empty()) return 0;
+  Context &c = ctx();
+  SolveCtx &sc = c.main;
+  unsigned char *hb = (unsigned char *)c.nodes.host, *db = (unsigned char *)c.nodes.dev;
+  std::memcpy(hb + o_hs, hs.data(), hs.size() * sizeof(SetbHandle));
+  if (!es.empty()) std::memcpy(hb + o_es, es.data(), es.size() * sizeof(SetbEntry));
+  if (!ss.empty()) std::memcpy(hb + o_ss, ss.data(), ss.size() * sizeof(SetbShift));
+  flush_copies(c); // a recorded clone INTO one of these slabs must land before the edits do
+  HIPCHECK(hipMemcpyAsync(db, hb, carve.off, hipMemcpyHostToDevice, sc.stream));
+  launch_setbnds((const SetbHandle *)(db + o_hs), (const SetbEntry *)(db + o_es), (const SetbShift *)(db + o_ss), (int)hs.size(), sc.stream);
+  HIPCHECK(hipStreamSynchronize(sc.stream)); // the pinned side is free for the next call
   return 0;
 }
 

@@ -45,6 +45,11 @@ int engine_round_many(const mvx_prob *root, const mvx_prob *const *Ps, int count
 int engine_rc_tighten_many(const mvx_prob *const *Ps, int count, const double *cutoff, double tol, int *cnt, int *cols, double *lb,
                            double *ub);
 int engine_tighten_many(mvx_prob *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub);
+// node bound propagation of `count` handles over root's rows, one launch for all rounds (k_prop), and general bound lists of
+// many handles applied with one launch (k_setbnds)
+int engine_propagate_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, int max_rounds, int *infeasible, int *rounds, int *cnt,
+                          int *cols, double *lb, double *ub);
+int engine_set_bounds_many(mvx_prob *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub);
 
 long long engine_pack_size(const mvx_prob *P, int m_base);
 int engine_pack(const mvx_prob *P, int m_base, void *dev_buf);

@@ -4402,6 +4402,163 @@ void launch_tighten(const TightHandle *hs, const TightEntry *es, int count, hipS
   hipLaunchKernelGGL(k_tighten, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, hs, es, count);
 }
 
+// ---------------------------------------------------------------------------- k_prop / k_setbnds
+// Node bound propagation (mvx_propagate_many, DESIGN.md "Node bound propagation"), one workgroup per handle, all rounds in
+// one launch.  A round is two private serial loops with one barrier between them and one behind:
+//  A. rows on lanes: the activities of a row, its non-zeros in ascending column order out of the by-column model (a wave
+//     reads one column of consecutive rows), the bounds broadcast from LDS; terms with an infinite bound are counted;
+//  B. columns on lanes: the candidates of an integer column, its non-zeros out of the by-row model (a wave reads one row of
+//     consecutive columns), the row activities broadcast from LDS (or the handle's global slice when m0 > RND_NMAX).  A
+//     column's new bounds are exact minima / maxima of its candidates and depend on the bounds the round started with only
+//     (a lane reads no other column's bounds here), so they go to LDS in place.
+// Products, sums and quotients are rounded one by one (xdiv): the host twin's bits.  No atomics: the flags are set to 1 by
+// whoever has a reason and read behind a barrier.
+__global__ __launch_bounds__(256) void k_prop(PropArgs a) {
+  __shared__ double s_l[RND_NMAX + 1], s_u[RND_NMAX + 1];
+  __shared__ double s_min[RND_NMAX], s_max[RND_NMAX];
+  __shared__ int s_k[RND_NMAX];
+  __shared__ int s_badrow, s_cross, s_chg[2];
+  const int t = (int)blockIdx.x;
+  const int n = a.n, m0 = a.m0;
+  const size_t ldm = (size_t)a.ldm, ldn = (size_t)a.ldn, base = (size_t)t * (size_t)(n + 1);
+  for (int j = TIDX; j <= n; j += 256) {
+    s_l[j] = a.lb0[base + j];
+    s_u[j] = a.ub0[base + j];
+  }
+  if (TIDX == 0) {
+    s_badrow = 0;
+    s_cross = 0;
+    s_chg[0] = s_chg[1] = 0;
+  }
+  const bool lds = m0 <= RND_NMAX;
+  double *amin = lds ? s_min : a.act + (size_t)t * 2 * (size_t)m0;
+  double *amax = lds ? s_max : amin + m0;
+  int *ak = lds ? s_k : a.actk + (size_t)t * (size_t)m0;
+  __syncthreads();
+  int rounds = 0, infeasible = 0;
+  for (int r = 0; r < a.max_rounds; r++) {
+    rounds = r + 1;
+    if (TIDX == 0) s_chg[r & 1] = 0; // last read two barriers ago; written again behind the next barrier
+    for (int i = TIDX; i < m0; i += 256) {
+      double lmin = 0.0, lmax = 0.0;
+      int kmin = 0, kmax = 0;
+      for (int j = 1; j <= n; j++) {
+        const double v = a.At[(size_t)j * ldm + i];
+        if (v == 0.0) continue;
+        const double l = s_l[j], u = s_u[j];
+        const double bmin = v > 0.0 ? l : u, bmax = v > 0.0 ? u : l;
+        if (isinf(bmin)) kmin++;
+        else lmin = __dadd_rn(lmin, __dmul_rn(v, bmin));
+        if (isinf(bmax)) kmax++;
+        else lmax = __dadd_rn(lmax, __dmul_rn(v, bmax));
+      }
+      amin[i] = lmin;
+      amax[i] = lmax;
+      ak[i] = (kmin > 2 ? 2 : kmin) | ((kmax > 2 ? 2 : kmax) << 2);
+      const double lo = a.rlo[i], hi = a.rhi[i];
+      if ((kmin == 0 && isfinite(hi) && lmin > __dadd_rn(hi, rnd_tol(hi))) || (kmax == 0 && isfinite(lo) && lmax < __dsub_rn(lo, rnd_tol(lo))))
+        s_badrow = 1;
+    }
+    __syncthreads();
+    if (s_badrow) {
+      infeasible = 1;
+      break;
+    }
+    for (int j = 1 + TIDX; j <= n; j += 256) {
+      if (!(a.flags[j] & RND_INT)) continue;
+      const double l = s_l[j], u = s_u[j];
+      double nl = l, nu = u;
+      for (int i = 0; i < m0; i++) {
+        const double v = a.Ar[(size_t)i * ldn + j];
+        if (v == 0.0) continue;
+        const int kk = ak[i], kmin = kk & 3, kmax = kk >> 2;
+        const double lo = a.rlo[i], hi = a.rhi[i];
+        const double bmin = v > 0.0 ? l : u, bmax = v > 0.0 ? u : l;
+        if (isfinite(hi) && (kmin == 0 || (kmin == 1 && isinf(bmin)))) {
+          const double res = kmin == 0 ? __dsub_rn(amin[i], __dmul_rn(v, bmin)) : amin[i];
+          const double q = xdiv(__dsub_rn(hi, res), v);
+          if (isfinite(q)) {
+            if (v > 0.0) {
+              const double c = floor(__dadd_rn(q, rnd_tol(q)));
+              if (c < nu) nu = c;
+            } else {
+              const double c = ceil(__dsub_rn(q, rnd_tol(q)));
+              if (c > nl) nl = c;
+            }
+          }
+        }
+        if (isfinite(lo) && (kmax == 0 || (kmax == 1 && isinf(bmax)))) {
+          const double res = kmax == 0 ? __dsub_rn(amax[i], __dmul_rn(v, bmax)) : amax[i];
+          const double q = xdiv(__dsub_rn(lo, res), v);
+          if (isfinite(q)) {
+            if (v > 0.0) {
+              const double c = ceil(__dsub_rn(q, rnd_tol(q)));
+              if (c > nl) nl = c;
+            } else {
+              const double c = floor(__dadd_rn(q, rnd_tol(q)));
+              if (c < nu) nu = c;
+            }
+          }
+        }
+      }
+      if (nl != l || nu != u) {
+        s_l[j] = nl;
+        s_u[j] = nu;
+        s_chg[r & 1] = 1;
+      }
+      if (nl > nu) s_cross = 1;
+    }
+    __syncthreads();
+    if (s_cross) {
+      infeasible = 1;
+      break;
+    }
+    if (!s_chg[r & 1]) break;
+  }
+  for (int j = TIDX; j <= n; j += 256) {
+    a.lb[base + j] = s_l[j];
+    a.ub[base + j] = s_u[j];
+  }
+  if (TIDX == 0) {
+    a.info[2 * t] = infeasible;
+    a.info[2 * t + 1] = rounds;
+  }
+}
+
+void launch_prop(const PropArgs &a, hipStream_t s) {
+  hipLaunchKernelGGL(k_prop, dim3((unsigned)a.count), dim3(256), 0, s, a);
+}
+
+// General bound lists of many handles in one launch (mvx_set_col_bnds_many), one workgroup per handle with device work: its
+// bound writes (a lane each; the host sends every row / position of a handle at most once), then a lane per tableau row 0..m, cut rows included, applies the
+// handle's shifts of column 0 in list order -- the fma k_shift_nonbasic applies per launch, so the bits are the per-entry
+// path's.  The shifts read columns jj >= 1 and write column 0 only, the writes touch the bound arrays only: no barrier.
+__global__ __launch_bounds__(256) void k_setbnds(const SetbHandle *hs, const SetbEntry *es, const SetbShift *ss) {
+  const SetbHandle h = hs[blockIdx.x];
+  for (int k = h.e0 + TIDX; k < h.e1; k += 256) {
+    const SetbEntry e = es[k];
+    if (e.flag < 0) {
+      h.blb[e.idx] = e.lb;
+      h.bub[e.idx] = e.ub;
+    } else {
+      h.nlb[e.idx] = e.lb;
+      h.nub[e.idx] = e.ub;
+      h.nflag[e.idx] = e.flag;
+    }
+  }
+  if (h.s1 <= h.s0) return;
+  for (int i = TIDX; i <= h.m; i += 256) {
+    double *row = h.T + (size_t)i * (size_t)h.ld;
+    double acc = row[0];
+    for (int k = h.s0; k < h.s1; k++) acc = fma(row[ss[k].jj], ss[k].delta, acc);
+    row[0] = acc;
+  }
+}
+
+void launch_setbnds(const SetbHandle *hs, const SetbEntry *es, const SetbShift *ss, int handles, hipStream_t s) {
+  hipLaunchKernelGGL(k_setbnds, dim3((unsigned)handles), dim3(256), 0, s, hs, es, ss);
+}
+
 // ------------------------------------------------------------------ launch wrappers
 
 // tuning knobs of the streamed update (mvx_set_tuning; defaults are the measured best)

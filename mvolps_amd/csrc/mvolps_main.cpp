@@ -67,6 +67,8 @@ int main(int argc, char **argv) {
               << "    2. as 1, then raise the columns greedily along the objective while every row allows it\n"
               << "  --rcfix         with --repaired (not with --best-window): once an incumbent exists, tighten the bounds of non-basic\n"
               << "                  integer columns from their reduced costs on every branching node; both children inherit them\n"
+              << "  --prop [K]      with --repaired (not with --best-window): bound propagation over the model's rows, at most K rounds\n"
+              << "                  (1..16; 8 without a number), on the root and on every child in front of its first solve\n"
               << "Help:\n  -h/--help\n";
     return 0;
   }
@@ -127,6 +129,17 @@ int main(int argc, char **argv) {
   }
   if (input.CMDOptionExists("--repaired")) params.reference_quirks = 0;
   if (input.CMDOptionExists("--rcfix")) params.rc_fix = 1;
+  if (input.CMDOptionExists("--prop")) {
+    // the number is optional: the next token is K only when all of it is digits (another option or a file name is not)
+    const std::string &k = input.getCMDOption("--prop");
+    const bool numeric = !k.empty() && std::all_of(k.begin(), k.end(), [](char ch) { return ch >= '0' && ch <= '9'; });
+    const long kv = numeric ? std::strtol(k.c_str(), nullptr, 10) : 8;
+    params.prop = kv >= 1 && kv <= 16 ? (int)kv : -1;
+    if (params.prop < 1) {
+      std::fprintf(stderr, "Unknown parameter value for --prop\n");
+      return -1;
+    }
+  }
   if (input.CMDOptionExists("--cut-select")) params.cut_select = std::atoi(input.getCMDOption("--cut-select").c_str());
   if (input.CMDOptionExists("--window")) params.window = std::atoi(input.getCMDOption("--window").c_str());
   if (input.CMDOptionExists("--best-window")) params.best_window = std::atoi(input.getCMDOption("--best-window").c_str());
@@ -137,13 +150,14 @@ int main(int argc, char **argv) {
   mvx_bnb_result res;
   const int brc = mvx_branchAndBound(nullptr, prob, &params, &res);
   if (brc == -1) {
-    std::fprintf(stderr, "-vs %d / --heur %d%s are not supported with these options (-vs 3 / 4: not with --best-window; --heur: only "
-                 "with --repaired; --rcfix: only with --repaired and without --best-window)\n", params.var_strat, params.heur,
-                 params.rc_fix ? " / --rcfix" : "");
+    std::fprintf(stderr, "-vs %d / --heur %d%s%s are not supported with these options (-vs 3 / 4: not with --best-window; --heur: only "
+                 "with --repaired; --rcfix / --prop: only with --repaired and without --best-window)\n", params.var_strat, params.heur,
+                 params.rc_fix ? " / --rcfix" : "", params.prop ? " / --prop" : "");
     mvx_delete_prob(prob);
     return -1;
   }
-  if (brc != 0) std::fprintf(stderr, "branch-and-bound stopped: the branching penalties or the heuristic could not be computed (%d)\n", brc);
+  if (brc != 0)
+    std::fprintf(stderr, "branch-and-bound stopped: the branching penalties, the heuristic or the propagation could not be computed (%d)\n", brc);
   if (input.CMDOptionExists("--events")) mvx_bnb_write_events(&res, input.getCMDOption("--events").c_str());
   mvx_bnb_print_tree(&res, nullptr); // bs.cpp:329-343
   std::vector<char> buf(64 + 64 * (size_t)res.n);
@@ -156,6 +170,9 @@ int main(int argc, char **argv) {
                 res.heur_improved, res.incumbent_heur ? " (the final incumbent is one of them)" : "");
   if (verbose && params.rc_fix > 0)
     std::printf("Reduced-cost tightening: %lld nodes, %lld columns fixed, %lld tightened\n", res.rc_calls, res.rc_fixed, res.rc_tightened);
+  if (verbose && params.prop > 0)
+    std::printf("Bound propagation: %lld handles, %lld columns fixed, %lld tightened, %lld handles proved infeasible\n", res.prop_calls,
+                res.prop_fixed, res.prop_tightened, res.prop_infeasible);
   const int limit = res.hit_limit || brc != 0;
   mvx_bnb_free_result(&res);
   mvx_delete_prob(prob);

@@ -320,6 +320,39 @@ struct TightEntry {
   int h, q, flag, pad;
 };
 
+// arguments of k_prop (mvx_propagate_many): `count` handles over the model of one root -- its rows by column (At, k_round's
+// copy) and by row (Ar), the row bounds and the RND_INT flags -- each with its own column bounds.  A handle's final bounds are
+// written once per column; the host compares them with what it sent.
+struct PropArgs {
+  const double *At;        // [n+1][ldm]: At[j*ldm + i] = a_(i+1),j
+  const double *Ar;        // [m0][ldn]: Ar[i*ldn + j] = a_(i+1),j
+  const double *rlo, *rhi; // [m0] row bounds, +-inf when absent
+  const int *flags;        // [n+1] RND_INT: the column is integer
+  const double *lb0, *ub0; // [count][n+1] the handles' column bounds, +-inf when absent
+  double *lb, *ub;         // [count][n+1] the propagated bounds
+  int *info;               // [count][2]: infeasible, rounds run
+  double *act;             // [count][2][m0] row activities when m0 > RND_NMAX (else LDS), nullptr otherwise
+  int *actk;               // [count][m0] their counts of infinite terms, likewise
+  int n, m0, ldm, ldn, max_rounds, count;
+};
+
+// k_setbnds (mvx_set_col_bnds_many): per handle a range of bound writes and a range of shifts of column 0
+struct SetbHandle {
+  double *T, *blb, *bub, *nlb, *nub;
+  int *nflag;
+  int ld, m;   // row stride and rows of the tableau (cut rows included)
+  int e0, e1;  // its entries [e0, e1)
+  int s0, s1;  // its shifts [s0, s1), in list order
+};
+struct SetbEntry {
+  double lb, ub;
+  int idx, flag; // flag < 0: row idx of a basic variable (blb / bub); else non-basic position idx with that status
+};
+struct SetbShift {
+  double delta; // T[i][0] = fma(T[i][jj], delta, T[i][0]) for every row i = 0..m
+  int jj, pad;
+};
+
 // shared immutable matrix row (1-based, n+1 doubles)
 using RowPtr = std::shared_ptr<std::vector<double>>;
 
