@@ -403,25 +403,6 @@ T *dup(const std::vector<T> &v) {
   return p;
 }
 
-void pack_result(mvx_bnb_result *res, const Recorder &rec, int id, int count, int has_incumbent, double bestLower, int incumbent_oid,
-                 int n0, const std::vector<double> &xbest, int hit_limit) {
-  std::memset(res, 0, sizeof(*res));
-  res->n_nodes = id - 1;
-  res->parent = dup(rec.parent);
-  res->prune = dup(rec.prune);
-  res->node_bound = dup(rec.bound);
-  res->n_events = (int)rec.events.size();
-  res->events = dup(rec.events);
-  res->count = count;
-  res->has_incumbent = has_incumbent;
-  res->best_lower = bestLower;
-  res->incumbent_oid = incumbent_oid;
-  res->n = n0;
-  res->x = dup(xbest);
-  res->total_pivots = rec.pivots;
-  res->hit_limit = hit_limit;
-}
-
 // A node's cuts through the engine's batch entry (mvx_lp_api.gmi_cuts): `cols` are the candidate columns (each one
 // basic and integer, checked by the caller the way gmi.cpp:18-27 / the repaired filter do); returns one container per
 // column, oid -1 where the engine found no cut.
@@ -644,8 +625,10 @@ static int add_node_cuts(const mvx_lp_api *api, void *a, const mvx_bnb_params &p
 
 // ---- branching on the node LP (var_strat 3 / 4, DESIGN.md "Branching on the node LP") ----
 
-// The bounds the drivers give the two children of a branching on `pick` at value `bound` (bs.cpp:274,282; repaired mode
-// keeps the opposite bound): S2 the down child, S3 the up child.  mvx_bnb_make_children and strong branching use it.
+// The bounds the two children of a branching on `pick` at value `bound` get (bs.cpp:274,282; repaired mode keeps the
+// opposite bound): S2 the down child, S3 the up child.  Every driver, strong branching and mvx_bnb_make_children use it.
+// `a` is the branching node; the window driver's up child has adopted a's handle, so S3 may be `a` itself: the node's type
+// and bounds are all read before the first write, and that order has to stay.
 static void child_bounds(const mvx_lp_api *api, const void *a, int pick, double bound, bool quirks, void *S2, void *S3) {
   if (quirks) {
     api->set_col_bnds(S2, pick, MVX_UP, 0, std::floor(bound)); // bs.cpp:274
@@ -1436,112 +1419,205 @@ private:
   PropHost _M;
 };
 
+// ---- what the three drivers share: the tree's state and what happens to a node once its LP is solved ----
+
+// bs.cpp:229-233: the sum of the fractional parts of a solved node's violated columns
+static double sum_infeas(const mvx_lp_api *api, const void *a, const std::vector<int> &vars) {
+  double acc = 0;
+  for (int i : vars)
+    if (i != 0) acc += getFract(api->get_col_prim(a, i));
+  return acc;
+}
+
+enum Verdict { STOP, INTEGER, INFEASIBLE, FATHOMED, BRANCH }; // STOP: the root ended the run (bs.cpp:139-149)
+
+// One tree: the record, the incumbent and the counters.  The drivers differ in which nodes they solve together and when;
+// what a solved node means for the tree is written here, once.
+struct Tree {
+  const mvx_lp_api *api;
+  const mvx_bnb_params &prm;
+  const bool quirks;
+  const double sg; // sense_of
+  const int n0;
+  Recorder rec;
+  int id = 1; // util.h:17
+  double bestLower; // bs.cpp:90
+  std::vector<double> xbest;
+  int has_incumbent = 0, incumbent_oid = 0;
+  int hit_limit = 0, count = 0, rc_out = 0;
+  long long sb_lps = 0, sb_pivots = 0;
+  HeurBook hbook;
+
+  Tree(const mvx_lp_api *api_, const void *prob, const mvx_bnb_params &p)
+      : api(api_), prm(p), quirks(p.reference_quirks != 0), sg(MVOLP::sense_of(api_, prob, p)), n0(api_->get_num_cols(prob)),
+        bestLower(-sg * std::numeric_limits<double>::infinity()), xbest((size_t)n0 + 1, 0.0) {}
+
+  std::shared_ptr<MVOLP::NodeData> root(const void *prob) { // bs.cpp:80
+    auto S1 = std::make_shared<MVOLP::NodeData>(api, prob, id);
+    S1->inital = true;
+    rec.node(S1->oid, 0);
+    return S1;
+  }
+
+  bool node_limit() {
+    if (prm.max_nodes > 0 && count >= prm.max_nodes) hit_limit = 1;
+    return hit_limit != 0;
+  }
+
+  // bs.cpp:210 fathoms a node whose bound does not beat the incumbent, ties included; a NaN bound is not fathomed
+  bool beats(double obj) const { return !(sg * obj <= sg * bestLower); }
+
+  // A node whose LP `h` holds solved, `status` from printInfo, `obj` its objective value: bound, label, event and incumbent
+  // (bs.cpp:135-223).  On BRANCH nothing but the bound is booked yet.
+  Verdict verdict(MVOLP::NodeData &node, const void *h, int status, double obj) {
+    const size_t o = (size_t)node.oid;
+    if (node.inital && status == -1) { // bs.cpp:139-143
+      rec.prune[o] = MVOLP::FEAS;
+      return STOP;
+    }
+    node.upperBound = obj; // bs.cpp:156
+    rec.bound[o] = obj;
+    if (status == 1) { // prune by integrality, bs.cpp:158-193
+      rec.prune[o] = MVOLP::INTG;
+      if (!node.inital) rec.emit(MVX_EV_INTEGER, node.oid, obj, 0.0, 0, 0);
+      // the root: bs.cpp:144-149 leaves without the event and without recording the solution; repaired mode keeps it
+      if (node.inital ? !quirks : sg * obj > sg * bestLower) {
+        bestLower = obj;
+        has_incumbent = 1;
+        incumbent_oid = node.oid;
+        hbook.incumbent = 0; // the node's own point, not the heuristic's
+        const int na = api->get_num_cols(h);
+        for (int i = 1; i <= na && i <= n0; i++) xbest[(size_t)i] = api->get_col_prim(h, i);
+      }
+      return node.inital ? STOP : INTEGER;
+    }
+    if (status == -1) { // bs.cpp:194-209
+      rec.prune[o] = MVOLP::FEAS;
+      rec.emit(MVX_EV_INFEASIBLE, node.oid, 0.0, 0.0, 0, 0);
+      return INFEASIBLE;
+    }
+    if (!beats(obj)) { // bs.cpp:210-223
+      rec.prune[o] = MVOLP::BNDS;
+      rec.emit(MVX_EV_FATHOMED, node.oid, 0.0, 0.0, 0, 0);
+      return FATHOMED;
+    }
+    return BRANCH;
+  }
+
+  void book_heur(const HeurOut &h, int oid) { hbook.book(h, oid, sg, bestLower, has_incumbent, incumbent_oid, xbest); }
+  void book_choice(const Choice &c) {
+    sb_lps += c.sb_lps;
+    sb_pivots += c.sb_pivots;
+  }
+  void branched(const MVOLP::NodeData &node, double acc, int nviol, int pick) {
+    rec.emit(MVX_EV_BRANCHED, node.oid, node.upperBound, acc, nviol, pick);
+  }
+  void children(const MVOLP::NodeData &node, const MVOLP::NodeData &S2, const MVOLP::NodeData &S3) { // bs.cpp:269-273
+    rec.node(S2.oid, node.oid);
+    rec.node(S3.oid, node.oid);
+  }
+  // the children's first solves have ended (bs.cpp:280,288,300-318)
+  void candidates(MVOLP::NodeData &S2, double obj2, MVOLP::NodeData &S3, double obj3) {
+    S2.upperBound = rec.bound[(size_t)S2.oid] = obj2;
+    S3.upperBound = rec.bound[(size_t)S3.oid] = obj3;
+    rec.emit(MVX_EV_CANDIDATE, S2.oid, obj2, 0.0, 0, 0);
+    rec.emit(MVX_EV_CANDIDATE, S3.oid, obj3, 0.0, 0, 0);
+  }
+  // a node is done (bs.cpp:326); true when a branching met the loop limit: bs.cpp:320-323 calls std::exit(-1), here the run stops
+  bool counted(bool branching) {
+    if (branching && count > prm.loop_limit) hit_limit = 1;
+    count++;
+    return hit_limit != 0;
+  }
+
+  int finish(mvx_bnb_result *res, const RcFix *rcfix, const Prop *prop) const {
+    std::memset(res, 0, sizeof(*res));
+    res->n_nodes = id - 1;
+    res->parent = dup(rec.parent);
+    res->prune = dup(rec.prune);
+    res->node_bound = dup(rec.bound);
+    res->n_events = (int)rec.events.size();
+    res->events = dup(rec.events);
+    res->count = count;
+    res->has_incumbent = has_incumbent;
+    res->best_lower = bestLower;
+    res->incumbent_oid = incumbent_oid;
+    res->n = n0;
+    res->x = dup(xbest);
+    res->total_pivots = rec.pivots;
+    res->hit_limit = hit_limit;
+    res->sb_lps = sb_lps;
+    res->sb_pivots = sb_pivots;
+    hbook.store(res);
+    if (rcfix) rcfix->store(res);
+    if (prop) prop->store(res);
+    return rc_out;
+  }
+};
+
+// The handles of the slots whose `mask` is set, from slot w0 on, go through `call(handles, slots, results)` together, and
+// result k lands on its slot of `out`; the other slots keep what they hold.  Returns call's code.
+template <typename R, typename F>
+static int on_slots(const std::vector<void *> &hs, const std::vector<char> &mask, size_t w0, std::vector<R> &out, F call) {
+  std::vector<const void *> sub;
+  std::vector<size_t> slot;
+  for (size_t w = w0; w < hs.size(); w++)
+    if (mask[w]) {
+      sub.push_back(hs[w]);
+      slot.push_back(w);
+    }
+  std::vector<R> got;
+  const int rc = call(sub, slot, got);
+  if (rc != 0) return rc;
+  for (size_t k = 0; k < slot.size(); k++) out[slot[k]] = std::move(got[k]);
+  return 0;
+}
+
 int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm, mvx_bnb_result *res) { // bs.cpp:54
   MVOLP::ParameterObj params(api, prob, prm);
   CutPool pool(api);
-  Recorder rec;
-  int id = 1; // util.h:17
-  const bool quirks = prm.reference_quirks != 0;
-
+  Tree T(api, prob, prm);
+  Recorder &rec = T.rec;
   std::deque<std::shared_ptr<MVOLP::NodeData>> leafContainer;
-  auto S1 = std::make_shared<MVOLP::NodeData>(api, prob, id); // bs.cpp:80
-  S1->inital = true;
-  rec.node(S1->oid, 0);
-  leafContainer.push_back(S1);
-
-  void *a = api->create_prob();                                 // bs.cpp:89
-  const double sg = params.sense();
-  double bestLower = -sg * std::numeric_limits<double>::infinity(); // bs.cpp:90
-  const int n0 = api->get_num_cols(prob);
-  std::vector<double> xbest((size_t)n0 + 1, 0.0);
-  int incumbent_oid = 0, has_incumbent = 0, hit_limit = 0;
-  int count = 0;
-  int rc_out = 0;
-  long long sb_lps = 0, sb_pivots = 0;
+  leafContainer.push_back(T.root(prob));
+  void *a = api->create_prob(); // bs.cpp:89
   Heuristic heur(api, prob, prm.heur);
-  HeurBook hbook;
   RcFix rcfix(api);
   Prop prop(api, prob, prm.prop);
 
   while (!leafContainer.empty()) { // bs.cpp:96
-    if (prm.max_nodes > 0 && count >= prm.max_nodes) {
-      hit_limit = 1;
-      break;
-    }
+    if (T.node_limit()) break;
     int index;
     std::shared_ptr<MVOLP::NodeData> node = params.pickNode(leafContainer, index); // bs.cpp:101
     api->erase_prob(a);                       // bs.cpp:114-115
     api->copy_prob(a, node->prob, MVX_OFF);   // bs.cpp:116
     solve(api, a, rec);                       // bs.cpp:117
-    rec.emit(MVX_EV_PREGNANT, node->oid, api->get_obj_val(a), 0.0, 0, 0); // bs.cpp:119-129
+    const double obj = api->get_obj_val(a);
+    rec.emit(MVX_EV_PREGNANT, node->oid, obj, 0.0, 0, 0); // bs.cpp:119-129
 
-    auto ret = printInfo(api, a, quirks); // bs.cpp:135|151
-    const int status = ret.first;
+    auto ret = printInfo(api, a, T.quirks); // bs.cpp:135|151
     const std::vector<int> &vars = ret.second;
-    if (node->inital) {
-      if (status == -1) { // bs.cpp:139-143
-        rec.prune[(size_t)node->oid] = MVOLP::FEAS;
-        break;
-      }
-      if (status == 1) { // bs.cpp:144-149: leaves without recording the solution; repaired mode keeps it
-        node->upperBound = api->get_obj_val(a);
-        rec.bound[(size_t)node->oid] = node->upperBound;
-        rec.prune[(size_t)node->oid] = MVOLP::INTG;
-        if (!quirks) {
-          bestLower = node->upperBound;
-          has_incumbent = 1;
-          incumbent_oid = node->oid;
-          const int na = api->get_num_cols(a);
-          for (int i = 1; i <= na && i <= n0; i++) xbest[(size_t)i] = api->get_col_prim(a, i);
-        }
-        break;
-      }
-    }
-    node->upperBound = api->get_obj_val(a); // bs.cpp:156
-    rec.bound[(size_t)node->oid] = node->upperBound;
-
-    if (status == 1) { // prune by integrality, bs.cpp:158-193
-      rec.prune[(size_t)node->oid] = MVOLP::INTG;
-      rec.emit(MVX_EV_INTEGER, node->oid, node->upperBound, 0.0, 0, 0);
-      if (sg * node->upperBound > sg * bestLower) {
-        bestLower = node->upperBound;
-        has_incumbent = 1;
-        incumbent_oid = node->oid;
-        hbook.incumbent = 0;
-        const int na = api->get_num_cols(a);
-        for (int i = 1; i <= na && i <= n0; i++) xbest[(size_t)i] = api->get_col_prim(a, i);
-      }
-      leafContainer.erase(leafContainer.begin() + index);
-    } else if (status == -1) { // bs.cpp:194-209
-      rec.prune[(size_t)node->oid] = MVOLP::FEAS;
-      rec.emit(MVX_EV_INFEASIBLE, node->oid, 0.0, 0.0, 0, 0);
-      leafContainer.erase(leafContainer.begin() + index);
-    } else if (sg * api->get_obj_val(a) <= sg * bestLower) { // bs.cpp:210-223 (ties pruned)
-      rec.prune[(size_t)node->oid] = MVOLP::BNDS;
-      rec.emit(MVX_EV_FATHOMED, node->oid, 0.0, 0.0, 0, 0);
-      leafContainer.erase(leafContainer.begin() + index);
-    } else { // branch, bs.cpp:224-324
-      double acc = 0;
-      for (int i : vars)
-        if (i != 0) acc += getFract(api->get_col_prim(a, i)); // bs.cpp:229-233
-      leafContainer.erase(leafContainer.begin() + index);       // bs.cpp:247
-
+    const Verdict v = T.verdict(*node, a, ret.first, obj);
+    if (v == STOP) break;
+    leafContainer.erase(leafContainer.begin() + index); // bs.cpp:247
+    if (v == BRANCH) {                                  // bs.cpp:224-324
+      const double acc = sum_infeas(api, a, vars);
       // the rounding heuristic reads the node's LP as solved, in front of the cut step
       if (prm.heur > 0 && api->get_status(a) == MVX_OPT) {
         std::vector<HeurOut> ho;
         if (heur.run({a}, ho) != 0) {
-          rc_out = -2;
+          T.rc_out = -2;
           break;
         }
-        hbook.book(ho[0], node->oid, sg, bestLower, has_incumbent, incumbent_oid, xbest);
+        T.book_heur(ho[0], node->oid);
       }
       // reduced-cost tightening against the incumbent in hand (a point the heuristic has just found counts), on the LP as
       // solved; the list goes to both children
       RcList rcl;
-      if (prm.rc_fix > 0 && has_incumbent && api->get_status(a) == MVX_OPT) {
+      if (prm.rc_fix > 0 && T.has_incumbent && api->get_status(a) == MVX_OPT) {
         std::vector<RcList> got;
-        if (rcfix.compute({a}, bestLower, got) != 0) {
-          rc_out = -2;
+        if (rcfix.compute({a}, T.bestLower, got) != 0) {
+          T.rc_out = -2;
           break;
         }
         rcl = std::move(got[0]);
@@ -1552,55 +1628,29 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm,
       double bound = 0.0;
       if (prm.var_strat >= 3) {
         std::vector<Choice> ch;
-        const int prc = choose_many(api, {a}, {vars}, prm, ch);
-        if (prc != 0) {
-          rc_out = -2;
+        if (choose_many(api, {a}, {vars}, prm, ch) != 0) {
+          T.rc_out = -2;
           break;
         }
         pick = ch[0].pick;
         bound = api->get_col_prim(a, pick);
-        sb_lps += ch[0].sb_lps;
-        sb_pivots += ch[0].sb_pivots;
+        T.book_choice(ch[0]);
       }
-      add_node_cuts(api, a, prm, quirks, pool); // bs.cpp:249-258
+      add_node_cuts(api, a, prm, T.quirks, pool); // bs.cpp:249-258
       if (prm.var_strat < 3) {
         pick = params.pickVar(vars);         // bs.cpp:260
         bound = api->get_col_prim(a, pick); // bs.cpp:261
       }
-      rec.emit(MVX_EV_BRANCHED, node->oid, node->upperBound, acc, (int)vars.size(), pick);
+      T.branched(*node, acc, (int)vars.size(), pick);
 
-      auto S2 = std::make_shared<MVOLP::NodeData>(api, a, id); // bs.cpp:269-273
-      auto S3 = std::make_shared<MVOLP::NodeData>(api, a, id);
-      rec.node(S2->oid, node->oid);
-      rec.node(S3->oid, node->oid);
-      if (quirks) {
-        api->set_col_bnds(S2->prob, pick, MVX_UP, 0, std::floor(bound)); // bs.cpp:274
-      } else {
-        const int t = api->get_col_type(a, pick);
-        const double l = api->get_col_lb(a, pick);
-        if (t == MVX_LO || t == MVX_DB || t == MVX_FX)
-          api->set_col_bnds(S2->prob, pick, (l == std::floor(bound)) ? MVX_FX : MVX_DB, l, std::floor(bound));
-        else
-          api->set_col_bnds(S2->prob, pick, MVX_UP, 0, std::floor(bound));
-      }
-      if (quirks) {
-        api->set_col_bnds(S3->prob, pick, MVX_LO, std::ceil(bound), 0); // bs.cpp:282
-      } else {
-        const int t = api->get_col_type(a, pick);
-        const double u = api->get_col_ub(a, pick);
-        if (t == MVX_UP || t == MVX_DB || t == MVX_FX)
-          api->set_col_bnds(S3->prob, pick, (u == std::ceil(bound)) ? MVX_FX : MVX_DB, std::ceil(bound), u);
-        else
-          api->set_col_bnds(S3->prob, pick, MVX_LO, std::ceil(bound), 0);
-      }
-      if (!rcl.empty() && rcfix.apply({S2->prob, S3->prob}, {&rcl, &rcl}) != 0) {
-        rc_out = -2;
-        break;
-      }
+      auto S2 = std::make_shared<MVOLP::NodeData>(api, a, T.id); // bs.cpp:269-273
+      auto S3 = std::make_shared<MVOLP::NodeData>(api, a, T.id);
+      T.children(*node, *S2, *S3);
+      child_bounds(api, a, pick, bound, T.quirks, S2->prob, S3->prob);
       // prop: both children behind their branching bound and the rc_fix list, in front of their first solve; whatever code
       // a failing call gives (no accessors, device memory, a refused list), the tree so far goes back with -2
-      if (prm.prop > 0 && prop.run({S2->prob, S3->prob}) != 0) {
-        rc_out = -2;
+      if ((!rcl.empty() && rcfix.apply({S2->prob, S3->prob}, {&rcl, &rcl}) != 0) || (prm.prop > 0 && prop.run({S2->prob, S3->prob}) != 0)) {
+        T.rc_out = -2;
         break;
       }
       // bs.cpp:279 and :287 solve two independent clones; an engine with a batch entry runs them
@@ -1614,32 +1664,15 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm,
         solve(api, S2->prob, rec);
         solve(api, S3->prob, rec);
       }
-      S2->upperBound = api->get_obj_val(S2->prob);
-      S3->upperBound = api->get_obj_val(S3->prob);
-      rec.bound[(size_t)S2->oid] = S2->upperBound;
-      rec.bound[(size_t)S3->oid] = S3->upperBound;
-
       leafContainer.push_back(S2); // bs.cpp:297-298
       leafContainer.push_back(S3);
-      rec.emit(MVX_EV_CANDIDATE, S2->oid, S2->upperBound, 0.0, 0, 0); // bs.cpp:300-318
-      rec.emit(MVX_EV_CANDIDATE, S3->oid, S3->upperBound, 0.0, 0, 0);
-      if (count > prm.loop_limit) { // bs.cpp:320-323 calls std::exit(-1); here the run stops
-        hit_limit = 1;
-        count++;
-        break;
-      }
+      T.candidates(*S2, api->get_obj_val(S2->prob), *S3, api->get_obj_val(S3->prob));
     }
-    count++; // bs.cpp:326
+    if (T.counted(v == BRANCH)) break;
   }
   leafContainer.clear();
   api->delete_prob(a);
-  pack_result(res, rec, id, count, has_incumbent, bestLower, incumbent_oid, n0, xbest, hit_limit);
-  res->sb_lps = sb_lps;
-  res->sb_pivots = sb_pivots;
-  hbook.store(res);
-  rcfix.store(res);
-  prop.store(res);
-  return rc_out;
+  return T.finish(res, &rcfix, &prop);
 }
 
 // Window mode: the front W nodes of the FIFO deque are solved together (one batched launch carries
@@ -1649,25 +1682,19 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm,
 // incumbent are those of the node-at-a-time loop above.
 int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm, mvx_bnb_result *res) {
   MVOLP::ParameterObj params(api, prob, prm);
-  Recorder rec;
-  int id = 1;
-  const bool quirks = prm.reference_quirks != 0;
+  Tree T(api, prob, prm);
+  Recorder &rec = T.rec;
+  const bool quirks = T.quirks;
   std::deque<std::shared_ptr<MVOLP::NodeData>> leafContainer;
-  auto S1 = std::make_shared<MVOLP::NodeData>(api, prob, id);
-  S1->inital = true;
-  rec.node(S1->oid, 0);
-  leafContainer.push_back(S1);
-  const double sg = params.sense();
-  double bestLower = -sg * std::numeric_limits<double>::infinity();
-  const int n0 = api->get_num_cols(prob);
-  std::vector<double> xbest((size_t)n0 + 1, 0.0);
-  int incumbent_oid = 0, has_incumbent = 0, hit_limit = 0, count = 0, rc_out = 0;
-  long long sb_lps = 0, sb_pivots = 0;
+  leafContainer.push_back(T.root(prob));
   bool stop = false;
   Heuristic heur(api, prob, prm.heur);
-  HeurBook hbook;
   RcFix rcfix(api);
   Prop prop(api, prob, prm.prop);
+  auto fail = [&]() { // whatever code a failing call gives, the tree so far goes back with -2
+    T.rc_out = -2;
+    stop = true;
+  };
 
   struct Branch {
     size_t slot;
@@ -1718,15 +1745,10 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
       Branch &br = R.branches[b];
       const size_t k2 = 2 * b, k3 = 2 * b + 1;
       rec.pivots += (R.after1[k2] - br.before2) + (R.after1[k3] - br.before3);
-      br.S2->upperBound = R.obj1[k2];
-      br.S3->upperBound = R.obj1[k3];
       br.S2->repiv = R.repiv[k2];
       br.S3->repiv = R.repiv[k3];
-      rec.bound[(size_t)br.S2->oid] = br.S2->upperBound;
-      rec.bound[(size_t)br.S3->oid] = br.S3->upperBound;
       rec.sink = &R.node_events[br.slot];
-      rec.emit(MVX_EV_CANDIDATE, br.S2->oid, br.S2->upperBound, 0.0, 0, 0);
-      rec.emit(MVX_EV_CANDIDATE, br.S3->oid, br.S3->upperBound, 0.0, 0, 0);
+      T.candidates(*br.S2, R.obj1[k2], *br.S3, R.obj1[k3]);
     }
     rec.sink = nullptr;
     for (auto &ne : R.node_events) rec.events.insert(rec.events.end(), ne.begin(), ne.end());
@@ -1747,10 +1769,7 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
   };
 
   while (!leafContainer.empty() && !stop) {
-    if (prm.max_nodes > 0 && count >= prm.max_nodes) {
-      hit_limit = 1;
-      break;
-    }
+    if (T.node_limit()) break;
     double t0 = now();
     size_t W = std::min(leafContainer.size(), (size_t)prm.window);
     // The window may reach into the children that are still being solved: it ends in front of the first node whose
@@ -1809,101 +1828,55 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
       tB_cuts += now() - ti;
       tB_rcuts += now() - ti;
     }
+    // var_strat 3 / 4, the heuristic and rc_fix work on the window ahead of the replay, each in one batched call over the slots
+    // that qualify.  may[w]: node w is neither infeasible nor integral, so it branches unless its bound prunes it; opt[w]: and
+    // its LP ended OPT.
+    std::vector<char> may, opt;
+    if (prm.var_strat >= 3 || prm.heur > 0 || prm.rc_fix > 0) {
+      if (info.empty()) {
+        info.resize(W);
+        for (size_t w = 0; w < W; w++) info[w] = printInfo(api, a[w], quirks);
+      }
+      may.resize(W);
+      opt.resize(W);
+      for (size_t w = 0; w < W; w++) {
+        may[w] = info[w].first == 0;
+        opt[w] = may[w] && api->get_status(a[w]) == MVX_OPT;
+      }
+    }
     // var_strat 3 / 4: the choice of every node of the window that may branch, in one penalty call (and one strong-branching
     // batch).  It depends on the node's own LP only, so the replay takes the serial loop's picks; a node the replay then
     // prunes by bound has only cost work, and its strong-branching counts are not booked.
-    std::vector<Choice> choice;
-    if (prm.var_strat >= 3) {
-      if (info.empty()) {
-        info.resize(W);
-        for (size_t w = 0; w < W; w++) info[w] = printInfo(api, a[w], quirks);
-      }
-      std::vector<const void *> bh;
-      std::vector<std::vector<int>> bv;
-      std::vector<size_t> slot;
-      for (size_t w = 0; w < W; w++)
-        if (info[w].first == 0) {
-          bh.push_back(a[w]);
-          bv.push_back(info[w].second);
-          slot.push_back(w);
-        }
-      std::vector<Choice> got;
-      if (choose_many(api, bh, bv, prm, got) != 0) {
-        rc_out = -2;
-        break;
-      }
-      choice.assign(W, Choice());
-      for (size_t k = 0; k < slot.size(); k++) choice[slot[k]] = got[k];
+    std::vector<Choice> choice(may.size());
+    if (prm.var_strat >= 3 && on_slots(a, may, 0, choice, [&](const auto &hs, const auto &slot, auto &got) {
+          std::vector<std::vector<int>> vs;
+          for (size_t w : slot) vs.push_back(info[w].second);
+          return choose_many(api, hs, vs, prm, got);
+        }) != 0) {
+      fail();
+      break;
     }
     // the rounding heuristic on every node of the window that may branch, in one call; booked by the replay for the nodes
     // that do branch, so the incumbent moves where the serial loop's does
-    std::vector<HeurOut> hres;
-    std::vector<char> hran;
-    if (prm.heur > 0) {
-      if (info.empty()) {
-        info.resize(W);
-        for (size_t w = 0; w < W; w++) info[w] = printInfo(api, a[w], quirks);
-      }
-      std::vector<const void *> hh;
-      std::vector<size_t> slot;
-      for (size_t w = 0; w < W; w++)
-        if (info[w].first == 0 && api->get_status(a[w]) == MVX_OPT) {
-          hh.push_back(a[w]);
-          slot.push_back(w);
-        }
-      std::vector<HeurOut> got;
-      if (heur.run(hh, got) != 0) {
-        rc_out = -2;
-        break;
-      }
-      hres.assign(W, HeurOut());
-      hran.assign(W, 0);
-      for (size_t k = 0; k < slot.size(); k++) {
-        hres[slot[k]] = std::move(got[k]);
-        hran[slot[k]] = 1;
-      }
+    std::vector<HeurOut> hres(opt.size());
+    if (prm.heur > 0 && on_slots(a, opt, 0, hres, [&](const auto &hs, const auto &, auto &got) { return heur.run(hs, got); }) != 0) {
+      fail();
+      break;
     }
     // rc_fix: the lists of every node of the window that may branch, in one call against the incumbent as it stands (none
     // yet: no call).  The replay uses a list only while the incumbent is the one it was computed with; once the replay has
     // moved the incumbent, the lists of the nodes from there on are computed again in one further call (rc_from).
-    std::vector<char> rcwant;
-    std::vector<RcList> rclist;
-    std::vector<char> rchave;
+    std::vector<RcList> rclist(opt.size());
+    bool rc_have = false;
     double rc_cut = 0.0;
-    bool rc_fail = false;
     auto rc_from = [&](size_t w0) {
-      std::vector<const void *> hh;
-      std::vector<size_t> slot;
-      for (size_t w = w0; w < W; w++)
-        if (rcwant[w]) {
-          hh.push_back(a[w]);
-          slot.push_back(w);
-        }
-      std::vector<RcList> got;
-      if (rcfix.compute(hh, bestLower, got) != 0) {
-        rc_fail = true;
-        return;
-      }
-      for (size_t k = 0; k < slot.size(); k++) {
-        rclist[slot[k]] = std::move(got[k]);
-        rchave[slot[k]] = 1;
-      }
-      rc_cut = bestLower;
+      rc_have = true;
+      rc_cut = T.bestLower;
+      return on_slots(a, opt, w0, rclist, [&](const auto &hs, const auto &, auto &got) { return rcfix.compute(hs, T.bestLower, got); });
     };
-    if (prm.rc_fix > 0) {
-      if (info.empty()) {
-        info.resize(W);
-        for (size_t w = 0; w < W; w++) info[w] = printInfo(api, a[w], quirks);
-      }
-      rcwant.assign(W, 0);
-      rclist.assign(W, RcList());
-      rchave.assign(W, 0);
-      for (size_t w = 0; w < W; w++) rcwant[w] = info[w].first == 0 && api->get_status(a[w]) == MVX_OPT;
-      if (has_incumbent) rc_from(0);
-      if (rc_fail) {
-        rc_out = -2;
-        break;
-      }
+    if (prm.rc_fix > 0 && T.has_incumbent && rc_from(0) != 0) {
+      fail();
+      break;
     }
     // B. replay in queue order
     Round cur;
@@ -1911,8 +1884,7 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
     std::vector<Branch> &branches = cur.branches;
     size_t processed = 0;
     for (size_t w = 0; w < W; w++) {
-      if (prm.max_nodes > 0 && count >= prm.max_nodes) {
-        hit_limit = 1;
+      if (T.node_limit()) {
         stop = true;
         break;
       }
@@ -1921,67 +1893,31 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
       rec.sink = &cur.node_events[w];
       rec.pivots += (node->repiv >= 0) ? node->repiv : api->get_it_cnt(aw) - before[w];
       processed++;
-      rec.emit(MVX_EV_PREGNANT, node->oid, api->get_obj_val(aw), 0.0, 0, 0);
+      const double obj = api->get_obj_val(aw);
+      rec.emit(MVX_EV_PREGNANT, node->oid, obj, 0.0, 0, 0);
       double ti = now();
       auto ret = info.empty() ? printInfo(api, aw, quirks) : std::move(info[w]);
       tB_info += now() - ti;
-      const int status = ret.first;
       const std::vector<int> &vars = ret.second;
-      if (node->inital) {
-        if (status == -1) {
-          rec.prune[(size_t)node->oid] = MVOLP::FEAS;
-          stop = true;
-          break;
-        }
-        if (status == 1) {
-          node->upperBound = api->get_obj_val(aw);
-          rec.bound[(size_t)node->oid] = node->upperBound;
-          rec.prune[(size_t)node->oid] = MVOLP::INTG;
-          if (!quirks) { // bs.cpp:144-149 leaves without recording the solution; repaired mode keeps it
-            bestLower = node->upperBound;
-            has_incumbent = 1;
-            incumbent_oid = node->oid;
-            for (int i = 1; i <= n0; i++) xbest[(size_t)i] = api->get_col_prim(aw, i);
-          }
-          stop = true;
-          break;
-        }
+      const Verdict v = T.verdict(*node, aw, ret.first, obj);
+      if (v == STOP) {
+        stop = true;
+        break;
       }
-      node->upperBound = api->get_obj_val(aw);
-      rec.bound[(size_t)node->oid] = node->upperBound;
-      if (status == 1) {
-        rec.prune[(size_t)node->oid] = MVOLP::INTG;
-        rec.emit(MVX_EV_INTEGER, node->oid, node->upperBound, 0.0, 0, 0);
-        if (sg * node->upperBound > sg * bestLower) {
-          bestLower = node->upperBound;
-          has_incumbent = 1;
-          incumbent_oid = node->oid;
-          hbook.incumbent = 0;
-          for (int i = 1; i <= n0; i++) xbest[(size_t)i] = api->get_col_prim(aw, i);
-        }
-      } else if (status == -1) {
-        rec.prune[(size_t)node->oid] = MVOLP::FEAS;
-        rec.emit(MVX_EV_INFEASIBLE, node->oid, 0.0, 0.0, 0, 0);
-      } else if (sg * api->get_obj_val(aw) <= sg * bestLower) {
-        rec.prune[(size_t)node->oid] = MVOLP::BNDS;
-        rec.emit(MVX_EV_FATHOMED, node->oid, 0.0, 0.0, 0, 0);
-      } else {
-        double acc = 0;
-        for (int i : vars)
-          if (i != 0) acc += getFract(api->get_col_prim(aw, i));
+      if (v == BRANCH) {
+        const double acc = sum_infeas(api, aw, vars);
         // cuts go onto the node's own problem (the serial driver's scratch copy `a`): both children inherit them.
         // The replay runs in queue order, so the persistent pool sees the nodes in bs.cpp's order.
         // bs.cpp:260-261 pick the variable and read its value behind the cut step; both are taken in front of it here: the
         // pick looks at the violated list and the root problem only, and appending a row leaves every other row's value
         // as it is -- but it marks the handle's solution mirrors stale, and reading one value afterwards is a device
         // export and a host round trip per branching node (~40 us, a tenth of the cut modes' run)
-        if (prm.heur > 0 && hran[w]) hbook.book(hres[w], node->oid, sg, bestLower, has_incumbent, incumbent_oid, xbest);
+        if (prm.heur > 0 && opt[w]) T.book_heur(hres[w], node->oid);
         RcList node_rc;
-        if (prm.rc_fix > 0 && has_incumbent && rcwant[w]) {
-          if (!rchave[w] || rc_cut != bestLower) rc_from(w); // the incumbent has moved since the lists were computed
-          if (rc_fail) {
-            rc_out = -2;
-            stop = true;
+        if (prm.rc_fix > 0 && T.has_incumbent && opt[w]) {
+          // no lists yet, or the incumbent has moved since they were computed
+          if ((!rc_have || rc_cut != T.bestLower) && rc_from(w) != 0) {
+            fail();
             break;
           }
           node_rc = std::move(rclist[w]);
@@ -1989,56 +1925,34 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
         }
         const int pick = prm.var_strat >= 3 ? choice[w].pick : params.pickVar(vars);
         const double bound = api->get_col_prim(aw, pick);
-        if (prm.var_strat >= 3) {
-          sb_lps += choice[w].sb_lps;
-          sb_pivots += choice[w].sb_pivots;
-        }
+        if (prm.var_strat >= 3) T.book_choice(choice[w]);
         ti = now();
         add_node_cuts(api, aw, prm, quirks, pool, pre.empty() ? nullptr : pre[w].get());
         tB_cuts += now() - ti;
-        rec.emit(MVX_EV_BRANCHED, node->oid, node->upperBound, acc, (int)vars.size(), pick);
+        T.branched(*node, acc, (int)vars.size(), pick);
         Branch br;
         br.slot = w;
         // bs.cpp:269-273 clones the solved node twice.  The node itself is dropped at the end of this
         // round, so the second child takes over its problem object instead of cloning it (same state,
         // one device-to-device tableau copy fewer per branching).
-        const int t = api->get_col_type(aw, pick);
-        const double l = api->get_col_lb(aw, pick), u = api->get_col_ub(aw, pick);
         double tc = now();
-        br.S2 = std::make_shared<MVOLP::NodeData>(api, aw, id); // even oid (R), then odd (L): bs.cpp:43-52
+        br.S2 = std::make_shared<MVOLP::NodeData>(api, aw, T.id); // even oid (R), then odd (L): bs.cpp:43-52
         tB_clone += now() - tc;
-        br.S3 = std::make_shared<MVOLP::NodeData>(api, aw, id, true);
+        br.S3 = std::make_shared<MVOLP::NodeData>(api, aw, T.id, true);
         node->prob = nullptr;
-        rec.node(br.S2->oid, node->oid);
-        rec.node(br.S3->oid, node->oid);
-        // same bounds as mvx_bnb_make_children
-        if (quirks) {
-          api->set_col_bnds(br.S2->prob, pick, MVX_UP, 0, std::floor(bound));
-          api->set_col_bnds(br.S3->prob, pick, MVX_LO, std::ceil(bound), 0);
-        } else {
-          if (t == MVX_LO || t == MVX_DB || t == MVX_FX)
-            api->set_col_bnds(br.S2->prob, pick, (l == std::floor(bound)) ? MVX_FX : MVX_DB, l, std::floor(bound));
-          else
-            api->set_col_bnds(br.S2->prob, pick, MVX_UP, 0, std::floor(bound));
-          if (t == MVX_UP || t == MVX_DB || t == MVX_FX)
-            api->set_col_bnds(br.S3->prob, pick, (u == std::ceil(bound)) ? MVX_FX : MVX_DB, std::ceil(bound), u);
-          else
-            api->set_col_bnds(br.S3->prob, pick, MVX_LO, std::ceil(bound), 0);
-        }
+        T.children(*node, *br.S2, *br.S3);
+        child_bounds(api, aw, pick, bound, quirks, br.S2->prob, br.S3->prob); // aw is S3's own handle by now
         br.before2 = api->get_it_cnt(br.S2->prob);
         br.before3 = api->get_it_cnt(br.S3->prob);
         br.rc = std::move(node_rc);
         branches.push_back(br);
         leafContainer.push_back(br.S2); // the queue order bs.cpp:297-298 gives them
         leafContainer.push_back(br.S3);
-        if (count > prm.loop_limit) { // bs.cpp:320-323
-          hit_limit = 1;
-          count++;
-          stop = true;
-          break;
-        }
       }
-      count++;
+      if (T.counted(v == BRANCH)) {
+        stop = true;
+        break;
+      }
     }
     rec.sink = nullptr;
     // rc_fix: every child of the round takes its parent's list in one call, behind its branching bound and in front of its
@@ -2053,23 +1967,17 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
           lists.push_back(&br.rc);
           lists.push_back(&br.rc);
         }
-      if (!kids.empty() && rcfix.apply(kids, lists) != 0) {
-        rc_out = -2;
-        stop = true;
-      }
+      if (!kids.empty() && rcfix.apply(kids, lists) != 0) fail();
     }
     // prop: every child of the round in one compute and one apply call, behind its branching bound and its rc_fix list, in
     // front of the round's batched solve.  A child's result depends on its own bounds only: the serial driver's
-    if (prm.prop > 0 && !branches.empty() && rc_out == 0) {
+    if (prm.prop > 0 && !branches.empty() && T.rc_out == 0) {
       std::vector<void *> kids;
       for (const Branch &br : branches) {
         kids.push_back(br.S2->prob);
         kids.push_back(br.S3->prob);
       }
-      if (prop.run(kids) != 0) {
-        rc_out = -2;
-        stop = true;
-      }
+      if (prop.run(kids) != 0) fail();
     }
     tB += now() - t0;
     // C. every child of this round is an independent LP (bs.cpp:279,287): batched solves on worker threads; then, for
@@ -2151,13 +2059,7 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
     std::fprintf(stderr, "bnb window timing: A %.1f ms  B %.1f ms (printInfo %.1f, clone %.1f, cuts %.1f of which the round's device pass %.1f)  waiting for child solves %.1f ms\n", tA * 1e3,
                  tB * 1e3, tB_info * 1e3, tB_clone * 1e3, tB_cuts * 1e3, tB_rcuts * 1e3, tWait * 1e3);
   leafContainer.clear();
-  pack_result(res, rec, id, count, has_incumbent, bestLower, incumbent_oid, n0, xbest, hit_limit);
-  res->sb_lps = sb_lps;
-  res->sb_pivots = sb_pivots;
-  hbook.store(res);
-  rcfix.store(res);
-  prop.store(res);
-  return rc_out;
+  return T.finish(res, &rcfix, &prop);
 }
 
 // printInfo of a round's nodes: one mvx_lp_api.classify_many call when the engine has it (one device launch for all of
@@ -2206,10 +2108,10 @@ static void classify_round(const mvx_lp_api *api, const std::vector<void *> &hs,
 int branchAndBoundBest(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm, mvx_bnb_result *res) {
   MVOLP::ParameterObj params(api, prob, prm);
   CutPool pool(api);
-  Recorder rec;
-  int id = 1;
-  const bool quirks = prm.reference_quirks != 0;
-  const double sg = params.sense();
+  Tree T(api, prob, prm);
+  Recorder &rec = T.rec;
+  const bool quirks = T.quirks;
+  const double sg = T.sg;
   // the open set in pop order: (sg * upperBound descending, insertion ascending) is pickNode's first maximum over the
   // deque, whose order is insertion order (erase keeps it, children are pushed at the back).  A NaN bound sorts last.
   struct Open {
@@ -2224,18 +2126,10 @@ int branchAndBoundBest(const mvx_lp_api *api, void *prob, const mvx_bnb_params &
     const double k = sg * nd->upperBound;
     open.insert(Open{std::isnan(k) ? -std::numeric_limits<double>::infinity() : k, ins++, nd});
   };
-  auto S1 = std::make_shared<MVOLP::NodeData>(api, prob, id);
-  S1->inital = true;
-  rec.node(S1->oid, 0);
-  push(S1);
-  double bestLower = -sg * std::numeric_limits<double>::infinity();
-  const int n0 = api->get_num_cols(prob);
-  std::vector<double> xbest((size_t)n0 + 1, 0.0);
-  int incumbent_oid = 0, has_incumbent = 0, hit_limit = 0, count = 0, rc_out = 0;
+  push(T.root(prob));
   long long rounds = 0, speculated = 0;
   bool stop = false;
   Heuristic heur(api, prob, prm.heur);
-  HeurBook hbook;
   const size_t W = (size_t)prm.best_window;
   const bool timing = std::getenv("MVX_BNB_TIMING") != nullptr;
   double tA = 0, tInfo = 0, tSpec = 0, tKids = 0, tReplay = 0;
@@ -2254,10 +2148,7 @@ int branchAndBoundBest(const mvx_lp_api *api, void *prob, const mvx_bnb_params &
   std::vector<std::pair<int, std::vector<int>>> info;
   std::vector<std::vector<double>> xs;
   while (!open.empty() && !stop) {
-    if (prm.max_nodes > 0 && count >= prm.max_nodes) {
-      hit_limit = 1;
-      break;
-    }
+    if (T.node_limit()) break;
     double t0 = now();
     std::vector<Spec> S;
     for (auto it = open.begin(); it != open.end() && S.size() < W; ++it) {
@@ -2284,36 +2175,20 @@ int branchAndBoundBest(const mvx_lp_api *api, void *prob, const mvx_bnb_params &
       if (S[j].node->repiv < 0) S[j].node->repiv = api->get_it_cnt(hs[j]) - before[j];
     tA += now() - t0;
     t0 = now();
-    classify_round(api, hs, quirks, n0, info, xs);
+    classify_round(api, hs, quirks, T.n0, info, xs);
     tInfo += now() - t0;
     t0 = now();
     // B. speculate under the incumbent as it stands
     std::vector<char> wanted(K, 0);
-    for (size_t j = 0; j < K; j++)
-      wanted[j] = S[j].branch = info[j].first == 0 && sg * api->get_obj_val(hs[j]) > sg * bestLower; // bs.cpp:210
+    for (size_t j = 0; j < K; j++) wanted[j] = S[j].branch = info[j].first == 0 && T.beats(api->get_obj_val(hs[j]));
     // the rounding heuristic on every node speculated to branch, in one call; booked when the node commits, so that an
     // incumbent it finds enters the commit test of the nodes behind it
-    std::vector<HeurOut> hres;
-    std::vector<char> hran;
-    if (prm.heur > 0) {
-      std::vector<const void *> hh;
-      std::vector<size_t> slot;
-      for (size_t j = 0; j < K; j++)
-        if (wanted[j] && api->get_status(hs[j]) == MVX_OPT) {
-          hh.push_back(hs[j]);
-          slot.push_back(j);
-        }
-      std::vector<HeurOut> got;
-      if (heur.run(hh, got) != 0) {
-        rc_out = -2;
-        break;
-      }
-      hres.assign(K, HeurOut());
-      hran.assign(K, 0);
-      for (size_t k = 0; k < slot.size(); k++) {
-        hres[slot[k]] = std::move(got[k]);
-        hran[slot[k]] = 1;
-      }
+    std::vector<char> opt(prm.heur > 0 ? K : 0);
+    for (size_t j = 0; j < opt.size(); j++) opt[j] = wanted[j] && api->get_status(hs[j]) == MVX_OPT;
+    std::vector<HeurOut> hres(opt.size());
+    if (prm.heur > 0 && on_slots(hs, opt, 0, hres, [&](const auto &sub, const auto &, auto &got) { return heur.run(sub, got); }) != 0) {
+      T.rc_out = -2;
+      break;
     }
     std::vector<std::unique_ptr<CutContainer>> pre = round_cuts(api, hs, wanted, prm, quirks);
     std::vector<void *> kids;
@@ -2328,8 +2203,6 @@ int branchAndBoundBest(const mvx_lp_api *api, void *prob, const mvx_bnb_params &
           break;
         }
       void *aw = hs[j];
-      const int t = api->get_col_type(aw, sp.pick);
-      const double l = api->get_col_lb(aw, sp.pick), u = api->get_col_ub(aw, sp.pick);
       void *base = aw;
       if (prm.cut_strat != 0) { // bs.cpp:249-258 on a clone: the node itself stays as it is until it is committed
         base = api->create_prob();
@@ -2346,16 +2219,7 @@ int branchAndBoundBest(const mvx_lp_api *api, void *prob, const mvx_bnb_params &
         sp.S3 = api->create_prob();
         api->copy_prob(sp.S3, aw, MVX_ON);
       }
-      const double fl = std::floor(sp.bound), ce = std::ceil(sp.bound);
-      if (quirks) { // same bounds as the serial loop (bs.cpp:274,282)
-        api->set_col_bnds(sp.S2, sp.pick, MVX_UP, 0, fl);
-        api->set_col_bnds(sp.S3, sp.pick, MVX_LO, ce, 0);
-      } else {
-        if (t == MVX_LO || t == MVX_DB || t == MVX_FX) api->set_col_bnds(sp.S2, sp.pick, (l == fl) ? MVX_FX : MVX_DB, l, fl);
-        else api->set_col_bnds(sp.S2, sp.pick, MVX_UP, 0, fl);
-        if (t == MVX_UP || t == MVX_DB || t == MVX_FX) api->set_col_bnds(sp.S3, sp.pick, (u == ce) ? MVX_FX : MVX_DB, ce, u);
-        else api->set_col_bnds(sp.S3, sp.pick, MVX_LO, ce, 0);
-      }
+      child_bounds(api, aw, sp.pick, sp.bound, quirks, sp.S2, sp.S3);
       sp.before2 = api->get_it_cnt(sp.S2);
       sp.before3 = api->get_it_cnt(sp.S3);
       kids.push_back(sp.S2);
@@ -2369,8 +2233,7 @@ int branchAndBoundBest(const mvx_lp_api *api, void *prob, const mvx_bnb_params &
     // C. replay in true best-bound order
     size_t j = 0;
     for (; j < K; j++) {
-      if (prm.max_nodes > 0 && count >= prm.max_nodes) {
-        hit_limit = 1;
+      if (T.node_limit()) {
         stop = true;
         break;
       }
@@ -2380,80 +2243,37 @@ int branchAndBoundBest(const mvx_lp_api *api, void *prob, const mvx_bnb_params &
       const std::vector<int> &vars = info[j].second;
       void *aw = hs[j];
       const double obj = api->get_obj_val(aw);
-      if (status == 0 && (sg * obj > sg * bestLower) != sp.branch) break; // pruned by an incumbent of this round
+      if (status == 0 && T.beats(obj) != sp.branch) break; // pruned by an incumbent of this round
       std::shared_ptr<MVOLP::NodeData> node = sp.node;
       open.erase(open.begin());
       rec.pivots += node->repiv;
       rec.emit(MVX_EV_PREGNANT, node->oid, obj, 0.0, 0, 0);
-      if (node->inital) {
-        if (status == -1) {
-          rec.prune[(size_t)node->oid] = MVOLP::FEAS;
-          stop = true;
-          j++;
-          break;
-        }
-        if (status == 1) {
-          node->upperBound = obj;
-          rec.bound[(size_t)node->oid] = node->upperBound;
-          rec.prune[(size_t)node->oid] = MVOLP::INTG;
-          if (!quirks) { // bs.cpp:144-149 leaves without recording the solution; repaired mode keeps it
-            bestLower = node->upperBound;
-            has_incumbent = 1;
-            incumbent_oid = node->oid;
-            for (int i = 1; i <= n0; i++) xbest[(size_t)i] = api->get_col_prim(aw, i);
-          }
-          stop = true;
-          j++;
-          break;
-        }
+      const Verdict v = T.verdict(*node, aw, status, obj); // BRANCH exactly when speculated so: the test above
+      if (v == STOP) {
+        stop = true;
+        j++;
+        break;
       }
-      node->upperBound = obj;
-      rec.bound[(size_t)node->oid] = node->upperBound;
-      if (status == 1) {
-        rec.prune[(size_t)node->oid] = MVOLP::INTG;
-        rec.emit(MVX_EV_INTEGER, node->oid, node->upperBound, 0.0, 0, 0);
-        if (sg * node->upperBound > sg * bestLower) {
-          bestLower = node->upperBound;
-          has_incumbent = 1;
-          incumbent_oid = node->oid;
-          hbook.incumbent = 0;
-          for (int i = 1; i <= n0; i++) xbest[(size_t)i] = api->get_col_prim(aw, i);
-        }
-      } else if (status == -1) {
-        rec.prune[(size_t)node->oid] = MVOLP::FEAS;
-        rec.emit(MVX_EV_INFEASIBLE, node->oid, 0.0, 0.0, 0, 0);
-      } else if (!sp.branch) {
-        rec.prune[(size_t)node->oid] = MVOLP::BNDS;
-        rec.emit(MVX_EV_FATHOMED, node->oid, 0.0, 0.0, 0, 0);
-      } else {
+      if (v == BRANCH) {
         double acc = 0;
         for (size_t k = 0; k < vars.size(); k++)
           if (vars[k] != 0) acc += getFract(xs[j][k]); // bs.cpp:229-233
-        if (prm.heur > 0 && hran[j]) hbook.book(hres[j], node->oid, sg, bestLower, has_incumbent, incumbent_oid, xbest);
-        rec.emit(MVX_EV_BRANCHED, node->oid, node->upperBound, acc, (int)vars.size(), sp.pick);
-        auto S2 = std::make_shared<MVOLP::NodeData>(api, sp.S2, id, true); // even oid (R), then odd (L): bs.cpp:43-52
-        auto S3 = std::make_shared<MVOLP::NodeData>(api, sp.S3, id, true);
+        if (prm.heur > 0 && opt[j]) T.book_heur(hres[j], node->oid);
+        T.branched(*node, acc, (int)vars.size(), sp.pick);
+        auto S2 = std::make_shared<MVOLP::NodeData>(api, sp.S2, T.id, true); // even oid (R), then odd (L): bs.cpp:43-52
+        auto S3 = std::make_shared<MVOLP::NodeData>(api, sp.S3, T.id, true);
         sp.S2 = sp.S3 = nullptr;
-        rec.node(S2->oid, node->oid);
-        rec.node(S3->oid, node->oid);
+        T.children(*node, *S2, *S3);
         rec.pivots += (api->get_it_cnt(S2->prob) - sp.before2) + (api->get_it_cnt(S3->prob) - sp.before3);
-        S2->upperBound = api->get_obj_val(S2->prob);
-        S3->upperBound = api->get_obj_val(S3->prob);
-        rec.bound[(size_t)S2->oid] = S2->upperBound;
-        rec.bound[(size_t)S3->oid] = S3->upperBound;
+        T.candidates(*S2, api->get_obj_val(S2->prob), *S3, api->get_obj_val(S3->prob));
         push(S2); // bs.cpp:297-298
         push(S3);
-        rec.emit(MVX_EV_CANDIDATE, S2->oid, S2->upperBound, 0.0, 0, 0);
-        rec.emit(MVX_EV_CANDIDATE, S3->oid, S3->upperBound, 0.0, 0, 0);
-        if (count > prm.loop_limit) { // bs.cpp:320-323
-          hit_limit = 1;
-          count++;
-          stop = true;
-          j++;
-          break;
-        }
       }
-      count++;
+      if (T.counted(v == BRANCH)) {
+        stop = true;
+        j++;
+        break;
+      }
     }
     // S[j..] stay open: drop their speculative children and undo their cut steps on the pool
     bool rolled = false;
@@ -2471,13 +2291,12 @@ int branchAndBoundBest(const mvx_lp_api *api, void *prob, const mvx_bnb_params &
   }
   if (timing)
     std::fprintf(stderr, "bnb best window timing: %lld rounds, %lld speculated, %d committed: re-solve %.1f ms  classify %.1f ms  speculate %.1f ms  children %.1f ms  replay %.1f ms\n",
-                 rounds, speculated, count, tA * 1e3, tInfo * 1e3, tSpec * 1e3, tKids * 1e3, tReplay * 1e3);
+                 rounds, speculated, T.count, tA * 1e3, tInfo * 1e3, tSpec * 1e3, tKids * 1e3, tReplay * 1e3);
   open.clear();
-  pack_result(res, rec, id, count, has_incumbent, bestLower, incumbent_oid, n0, xbest, hit_limit);
+  const int rc = T.finish(res, nullptr, nullptr);
   res->rounds = rounds;
   res->speculated = speculated;
-  hbook.store(res);
-  return rc_out;
+  return rc;
 }
 
 // ---- the gfx950 engine's table ----
@@ -2632,12 +2451,10 @@ int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *
     int rc = 0;
     // no integer in some column's range, or the propagation proves it: the root is infeasible, nothing to solve
     auto infeasible_root = [&](int prune) {
-      Recorder rec;
-      rec.node(1, 0);
-      rec.prune[1] = prune;
-      const double sg = (api->get_obj_dir && api->get_obj_dir(prob) == MVX_MIN) ? -1.0 : 1.0;
-      const int n0 = api->get_num_cols(prob);
-      pack_result(res, rec, 2, 0, 0, -sg * std::numeric_limits<double>::infinity(), 0, n0, std::vector<double>((size_t)n0 + 1, 0.0), 0);
+      Tree T(api, prob, *params);
+      T.rec.node(T.id++, 0);
+      T.rec.prune[1] = prune;
+      T.finish(res, nullptr, nullptr);
     };
     if (integral_bounds(api, work, true) == 2) {
       infeasible_root(MVOLP::FEAS);
@@ -2699,13 +2516,10 @@ int mvx_bnb_classify(const mvx_lp_api *api, const void *prob, const void *root, 
   mvx_bnb_default_params(&p);
   p.var_strat = var_strat;
   MVOLP::ParameterObj params(api, root, p);
-  double acc = 0;
-  for (int i : ret.second)
-    if (i != 0) acc += getFract(api->get_col_prim(prob, i)); // bs.cpp:229-233
   out[0] = (double)ret.first;
   out[1] = api->get_obj_val(prob);
   out[2] = (double)ret.second.size();
-  out[3] = acc;
+  out[3] = sum_infeas(api, prob, ret.second);
   out[4] = ret.second.empty() ? 0.0 : (double)params.pickVar(ret.second);
   return 0;
 }
