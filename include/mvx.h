@@ -216,6 +216,16 @@ int mvx_propagate_many(const mvx_prob *root, const mvx_prob *const *Ps, int coun
    every tableau row follows.  Clones recorded and not yet launched are flushed first.  Returns 0; -1 bad arguments or a bad list
    (nothing is changed); -2 device out of memory. */
 int mvx_set_col_bnds_many(mvx_prob *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub);
+/* LP diving heuristic (DESIGN.md "LP diving heuristic"): the branching pick of `count` (solved handle, rule) pairs, one device
+   launch (k_divepick), rules[t] one of 1 fractional, 2 locks, 4 vector length.  The values are each handle's own, the locks,
+   column lengths and objective those of rows 1..m0 of `root` (m0 = root's row count; cut rows are ignored); the model is
+   uploaded once and kept with `root`, as for mvx_round_many.  nfrac[t] the fractional integer columns of handle t, col[t] the
+   one rule rules[t] branches on (0 when there is none), dir[t] 0 down / 1 up, val[t] its value.  Pure: no handle changes.
+   Bit-identical to mvx_bnb_dive_pick (mvx_bnb.h).  Returns 0; -1 bad arguments (a rule outside {1, 2, 4}, a handle with
+   another column count); -2 device out of memory; -3 a handle whose status is not MVX_OPT; -5 n > 4096, as for
+   mvx_round_many, whose model it shares. */
+int mvx_dive_pick_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, const int *rules, int *nfrac, int *col, int *dir,
+                       double *val);
 
 /* ---- engine-state access (parity tests, visualisers) --------------------------- */
 int mvx_get_tableau_ld(const mvx_prob *P);

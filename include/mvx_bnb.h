@@ -98,6 +98,10 @@ typedef struct mvx_lp_api {
   /* optional (may be NULL): general bound lists of `count` handles applied in one call (mvx_set_col_bnds_many), handle t taking
      entries off[t] .. off[t+1]-1, +-inf for an absent bound; without it the driver calls set_col_bnds per entry */
   int (*set_col_bnds_many)(void *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub);
+  /* optional (may be NULL): the diving heuristic's branching pick (DESIGN.md "LP diving heuristic") for `count` (solved handle,
+     rule) pairs in one call (mvx_dive_pick_many), the model taken from `root`; without it, or when it returns -5 (more columns
+     than the kernel holds), the driver runs the host twin mvx_bnb_dive_pick */
+  int (*dive_pick_many)(const void *root, const void *const *Ps, int count, const int *rules, int *nfrac, int *col, int *dir, double *val);
 } mvx_lp_api;
 
 const mvx_lp_api *mvx_hip_lp_api(void);
@@ -147,6 +151,12 @@ typedef struct {
                            root (behind the rounding of its bounds) and every child (behind its branching bound and its rc_fix
                            list, in front of its first solve) have the bounds of their integer columns tightened from the
                            activities of the root's rows.  Needs reference_quirks = 0 and best_window = 0 */
+  int dive;             /* LP diving heuristic (DESIGN.md "LP diving heuristic"): 0 off (default), 1..7 the rules that dive, as bits:
+                           1 fractional, 2 locks, 4 vector length.  A node that reaches the branch decision with an OPT LP is
+                           dived behind the rounding heuristic and in front of rc_fix, on its LP as solved; a better feasible
+                           point becomes the incumbent.  Needs reference_quirks = 0 and best_window = 0 */
+  int dive_freq;        /* 0 (default): the root only; F > 0: also every branching node with oid % F == 0 */
+  int dive_depth;       /* step limit of one dive; 0 (default): 4 n + 64, a cap against a dive that never ends */
 } mvx_bnb_params;
 
 /* B&B events at the emit points of bs.cpp (message.h EventType) */
@@ -187,7 +197,8 @@ typedef struct {
   long long heur_calls;    /* heur > 0: nodes the rounding heuristic ran on (the nodes that branched) */
   long long heur_found;    /* ... of which it returned a feasible point */
   long long heur_improved; /* ... of which the point became the incumbent */
-  int incumbent_heur;      /* 1: the final incumbent came from the heuristic, 0: from an integral node LP (or none) */
+  int incumbent_heur;      /* 1: the final incumbent came from the rounding heuristic, 2: from a dive, 0: from an integral node
+                              LP (or none) */
   long long rc_calls;      /* rc_fix = 1: branching nodes the reduced-cost tightening ran on */
   long long rc_fixed;      /* ... entries of their lists with lb == ub */
   long long rc_tightened;  /* ... the other entries */
@@ -195,6 +206,11 @@ typedef struct {
   long long prop_fixed;      /* ... entries of their applied lists with lb == ub */
   long long prop_tightened;  /* ... the other entries */
   long long prop_infeasible; /* ... handles it proved infeasible (a child keeps its bounds and is solved as before) */
+  long long dive_calls;    /* dive > 0: nodes dived */
+  long long dive_found;    /* ... of which at least one rule's dive returned a feasible point */
+  long long dive_improved; /* ... of which the point became the incumbent */
+  long long dive_lps;      /* child LPs the dives solved, failed sides included */
+  long long dive_pivots;   /* their pivots (not part of total_pivots) */
 } mvx_bnb_result;
 
 void mvx_bnb_default_params(mvx_bnb_params *p);
@@ -203,7 +219,7 @@ void mvx_bnb_default_params(mvx_bnb_params *p);
    empty; -2 var_strat >= 3 and the branching penalties could not be computed (the table has neither
    branch_penalties_many nor get_tableau + get_basis, or they failed), or heur > 0 and the heuristic could not run (the
    table has neither round_many nor the accessors of mvx_bnb_round, or they failed) -- *res holds the tree up to that
-   node */
+   node.  rc_fix, prop and dive have the same two codes; their refusals are listed with their host twins below */
 int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *params, mvx_bnb_result *res);
 void mvx_bnb_free_result(mvx_bnb_result *res);
 
@@ -274,6 +290,24 @@ int mvx_bnb_rc_tighten(const mvx_lp_api *api, const void *prob, double cutoff, d
    (propagate_many, set_col_bnds_many) failed, whatever that call's own code was */
 int mvx_bnb_propagate(const mvx_lp_api *api, const void *prob, const void *root, int max_rounds, int *infeasible, int *rounds, int *cnt,
                       int *cols, double *lb, double *ub);
+
+/* LP diving heuristic (DESIGN.md "LP diving heuristic"), host twin of mvx_dive_pick_many for one solved handle and one rule
+   (1 fractional, 2 locks, 4 vector length): *nfrac the number of fractional integer columns, *col the one the rule branches on
+   (0 when there is none), *dir 0 down / 1 up, *val its value.  The locks, column lengths and objective are those of rows
+   1..m0 of `root` (m0 = its row count; cut rows are ignored).  Works through the table only (get_col_prim_all / get_col_prim,
+   get_mat_row, bounds, get_obj_coef, get_col_kind, get_obj_dir).  Returns 0; -1 bad arguments (a rule outside {1, 2, 4},
+   another column count); -2 the table lacks an accessor it needs; -3 the handle is not MVX_OPT */
+int mvx_bnb_dive_pick(const mvx_lp_api *api, const void *prob, const void *root, int rule, int *nfrac, int *col, int *dir, double *val);
+/* The whole dives of one solved node `prob` (left untouched; every clone is freed) under the rules whose bits are set in
+   `rules` (1..7), each at most `depth` steps (0: 4 n + 64): per step one pick, one bounded clone solved with the default
+   parameters, the opposite side once when that fails.  A dive that ends integral is rounded and checked (mvx_bnb_round, mode
+   1).  *found 1 when some rule found a point, *obj / x[1..n] the best of them (ties to the lower rule), *lps / *pivots the
+   child LPs solved and their pivots.  Uses the table's batched entries where it has them (dive_pick_many, simplex_batch,
+   set_col_bnds_many, round_many) and the twins otherwise.  Returns 0; -1 bad arguments; -2 the table lacks an accessor; -3 the
+   handle is not MVX_OPT.  mvx_branchAndBound returns -1 (*res empty) for dive outside 0..7, negative dive_freq / dive_depth and
+   dive > 0 with reference_quirks = 1 or best_window > 0, and -2, with the tree so far, when a dive could not be carried out */
+int mvx_bnb_dive(const mvx_lp_api *api, const void *prob, const void *root, int rules, int depth, double *obj, int *found, double *x,
+                 long long *lps, long long *pivots);
 
 /* bs.cpp:249-258 on one solved node `a` that is about to be branched: generate its GMI cut(s) and append the
    row(s) (cut_strat / reference_quirks / lazy_pool / cut_select / cut_chance of `params`).  Returns the number

@@ -15,7 +15,8 @@ _FIELDS = [
     "get_it_cnt",
 ]
 _OPTIONAL = ["simplex_batch", "get_obj_dir", "gmi_cuts", "gmi_cuts_many", "get_col_prim_all", "classify_many", "get_tableau", "get_basis",
-             "branch_penalties_many", "round_many", "rc_tighten_many", "tighten_cols_many", "propagate_many", "set_col_bnds_many"]
+             "branch_penalties_many", "round_many", "rc_tighten_many", "tighten_cols_many", "propagate_many", "set_col_bnds_many",
+             "dive_pick_many"]
 
 
 class LpApiTable(C.Structure):
@@ -42,6 +43,9 @@ class BnbParams(C.Structure):
         ("heur", C.c_int),
         ("rc_fix", C.c_int),
         ("prop", C.c_int),
+        ("dive", C.c_int),
+        ("dive_freq", C.c_int),
+        ("dive_depth", C.c_int),
     ]
 
 
@@ -89,6 +93,11 @@ class BnbResult(C.Structure):
         ("prop_fixed", C.c_longlong),
         ("prop_tightened", C.c_longlong),
         ("prop_infeasible", C.c_longlong),
+        ("dive_calls", C.c_longlong),
+        ("dive_found", C.c_longlong),
+        ("dive_improved", C.c_longlong),
+        ("dive_lps", C.c_longlong),
+        ("dive_pivots", C.c_longlong),
     ]
 
 
@@ -148,6 +157,13 @@ def _bind(lib):
     lib.mvx_bnb_propagate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _IP, _IP, _IP, _IP, _DP, _DP]
     lib.mvx_set_col_bnds_many.restype = C.c_int
     lib.mvx_set_col_bnds_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, _IP, _IP, _DP, _DP]
+    lib.mvx_dive_pick_many.restype = C.c_int
+    lib.mvx_dive_pick_many.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, _IP, _IP, _IP, _IP, _DP]
+    lib.mvx_bnb_dive_pick.restype = C.c_int
+    lib.mvx_bnb_dive_pick.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _IP, _IP, _IP, _DP]
+    lib.mvx_bnb_dive.restype = C.c_int
+    lib.mvx_bnb_dive.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, _DP, _IP, _DP, C.POINTER(C.c_longlong),
+                                 C.POINTER(C.c_longlong)]
     lib.mvx_generateCut3.restype = C.c_int
     lib.mvx_generateCut3.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     return lib
@@ -198,11 +214,17 @@ def result_to_dict(res):
         "prop_fixed": res.prop_fixed,
         "prop_tightened": res.prop_tightened,
         "prop_infeasible": res.prop_infeasible,
+        "dive_calls": res.dive_calls,
+        "dive_found": res.dive_found,
+        "dive_improved": res.dive_improved,
+        "dive_lps": res.dive_lps,
+        "dive_pivots": res.dive_pivots,
     }
 
 
 def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, window=None, cut_select=0, cut_chance=1.0,
-                best_window=None, sb_cands=None, sb_iters=None, heur=None, rc_fix=None, prop=None):
+                best_window=None, sb_cands=None, sb_iters=None, heur=None, rc_fix=None, prop=None, dive=None, dive_freq=None,
+                dive_depth=None):
     """mvx_bnb_params with ParameterObj's defaults (util.h:65-67) overridden by the arguments (None: the default)."""
     pr = BnbParams()
     lib().mvx_bnb_default_params(C.byref(pr))
@@ -223,22 +245,31 @@ def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, l
         pr.rc_fix = rc_fix
     if prop is not None:
         pr.prop = prop
+    if dive is not None:
+        pr.dive = dive
+    if dive_freq is not None:
+        pr.dive_freq = dive_freq
+    if dive_depth is not None:
+        pr.dive_depth = dive_depth
     return pr
 
 
 def branch_and_bound(prob, var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, table=None, window=None,
-                     cut_select=0, cut_chance=1.0, best_window=None, sb_cands=None, sb_iters=None, heur=None, rc_fix=None, prop=None):
+                     cut_select=0, cut_chance=1.0, best_window=None, sb_cands=None, sb_iters=None, heur=None, rc_fix=None, prop=None,
+                     dive=None, dive_freq=None, dive_depth=None):
     """Run the driver on `prob` (a capi.Prob).  table=None uses the gfx950 engine's own table.  best_window > 1 with
     node_strat=1: the speculative best-bound window (mvx_bnb_params.best_window).  var_strat 3 / 4: branching on the node
     LP's penalties / strong branching (sb_cands candidates, sb_iters pivots per child).  heur 1 / 2: the primal rounding
     heuristic on every branching node (round and check / round, check and fill; quirks=0 only).  rc_fix 1: reduced-cost bound
     tightening on every branching node once an incumbent exists (quirks=0, not with best_window).  prop 1..16: node bound
-    propagation of the root and of every child with that round limit (quirks=0, not with best_window).  The dictionary's "rc"
-    is mvx_branchAndBound's return code (-1 refused parameters, -2 penalties, heuristic, tightening or propagation
-    unavailable)."""
+    propagation of the root and of every child with that round limit (quirks=0, not with best_window).  dive 1..7: the LP
+    diving heuristic with those rules (bits 1 fractional, 2 locks, 4 vector length) at the root and, with dive_freq = F > 0,
+    at every branching node whose oid F divides; dive_depth limits a dive's steps (quirks=0, not with best_window).  The
+    dictionary's "rc" is mvx_branchAndBound's return code (-1 refused parameters, -2 penalties, heuristic, tightening,
+    propagation or dives unavailable)."""
     L = lib()
     pr = make_params(var_strat, node_strat, cut_strat, max_nodes, quirks, lazy_pool, window, cut_select, cut_chance, best_window, sb_cands,
-                     sb_iters, heur, rc_fix, prop)
+                     sb_iters, heur, rc_fix, prop, dive, dive_freq, dive_depth)
     res = BnbResult()
     tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
     rc = L.mvx_branchAndBound(tptr, prob.h, C.byref(pr), C.byref(res))
@@ -513,6 +544,48 @@ def set_col_bnds_many(probs, lists):
     ub = np.array([e[2] for l in lists for e in l] or [0.0], dtype=np.float64)
     DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
     return lib().mvx_set_col_bnds_many(hs, len(probs), off.ctypes.data_as(IP), flat.ctypes.data_as(IP), lb.ctypes.data_as(DP), ub.ctypes.data_as(DP))
+
+
+def dive_pick_many(root, probs, rules):
+    """mvx_dive_pick_many over solved capi.Prob handles of the gfx950 engine against the model of `root`, rules[t] (1, 2 or 4)
+    the rule of handle t: one launch for all of them.  Returns (rc, [(nfrac, col, dir, val) per handle])."""
+    import numpy as np
+
+    k = len(probs)
+    hs = (C.c_void_p * max(1, k))(*[p.h for p in probs])
+    rl = np.array(list(rules) or [0], dtype=np.int32)
+    nfrac, col, dr = (np.zeros(max(1, k), dtype=np.int32) for _ in range(3))
+    val = np.zeros(max(1, k))
+    DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    rc = lib().mvx_dive_pick_many(root.h, hs, k, rl.ctypes.data_as(IP), nfrac.ctypes.data_as(IP), col.ctypes.data_as(IP), dr.ctypes.data_as(IP),
+                                  val.ctypes.data_as(DP))
+    if rc != 0:
+        return rc, None
+    return rc, [(int(nfrac[t]), int(col[t]), int(dr[t]), float(val[t])) for t in range(k)]
+
+
+def dive_pick_node(prob, root, rule, table=None):
+    """mvx_bnb_dive_pick (the host twin, through `table`; None = the gfx950 engine's table) on one solved node against the
+    model of `root`.  Returns (rc, (nfrac, col, dir, val))."""
+    nfrac, col, dr, val = C.c_int(0), C.c_int(0), C.c_int(0), C.c_double(0.0)
+    tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
+    rc = lib().mvx_bnb_dive_pick(tptr, prob.h, root.h, rule, C.byref(nfrac), C.byref(col), C.byref(dr), C.byref(val))
+    return rc, (nfrac.value, col.value, dr.value, val.value)
+
+
+def dive_node(prob, root, rules=7, depth=0, table=None):
+    """mvx_bnb_dive: the whole dives of one solved node under the rules whose bits are set, through `table` (None = the gfx950
+    engine's table, whose batched entries then run).  Returns (rc, obj, found, x array of n + 1 entries, lps, pivots)."""
+    import numpy as np
+
+    n = root.n
+    obj, found = C.c_double(0.0), C.c_int(0)
+    lps, piv = C.c_longlong(0), C.c_longlong(0)
+    x = np.zeros(n + 1)
+    tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
+    rc = lib().mvx_bnb_dive(tptr, prob.h, root.h, rules, depth, C.byref(obj), C.byref(found), x.ctypes.data_as(C.POINTER(C.c_double)),
+                            C.byref(lps), C.byref(piv))
+    return rc, obj.value, found.value, x, lps.value, piv.value
 
 
 def node_sample(root, count, quirks=0, table=None):

@@ -41,6 +41,9 @@ extern "C" int mvx_propagate_many(const mvx_prob *root, const mvx_prob *const *P
                                   int *cnt, int *cols, double *lb, double *ub) __attribute__((weak));
 extern "C" int mvx_set_col_bnds_many(mvx_prob *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub)
     __attribute__((weak));
+extern "C" int mvx_dive_pick_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, const int *rules, int *nfrac, int *col, int *dir,
+                                  double *val)
+    __attribute__((weak));
 
 namespace {
 
@@ -868,13 +871,15 @@ static int choose_many(const mvx_lp_api *api, const std::vector<const void *> &h
 
 // The model the heuristic checks a candidate against, read once per tree from the root through the table: rows 1..m0 with
 // their non-zeros in ascending column order (and by column for the fill), row and column bounds (+-inf where absent),
-// the objective, and which columns are integer and locked down / up by some row.
+// the objective, and which columns are integer and locked down / up by some row; for the diving rules, how many rows lock a
+// column down / up and how many non-zeros it has.
 struct RoundHost {
   int m0 = 0, n = 0;
   double sg = 1.0;
   std::vector<std::vector<std::pair<int, double>>> rows, cols; // rows[i-1]: (j, a_ij) ascending j; cols[j]: (i-1, a_ij)
   std::vector<double> rlo, rhi, clo, chi, c;
   std::vector<char> isint, dlock, ulock;
+  std::vector<int> dl, ul; // rows that lock column j down / up
 };
 
 static double tab_bound(double b) { // the table reports an absent bound as -+DBL_MAX (GLPK)
@@ -901,6 +906,8 @@ static int round_host_model(const mvx_lp_api *api, const void *root, RoundHost &
   M.isint.assign((size_t)n + 1, 0);
   M.dlock.assign((size_t)n + 1, 0);
   M.ulock.assign((size_t)n + 1, 0);
+  M.dl.assign((size_t)n + 1, 0);
+  M.ul.assign((size_t)n + 1, 0);
   std::vector<int> ind((size_t)n + 1);
   std::vector<double> val((size_t)n + 1);
   for (int i = 1; i <= m0; i++) {
@@ -914,8 +921,14 @@ static int round_host_model(const mvx_lp_api *api, const void *root, RoundHost &
     M.rhi[(size_t)i - 1] = up;
     for (const auto &e : row) {
       M.cols[(size_t)e.first].emplace_back(i - 1, e.second);
-      if ((e.second > 0.0 && std::isfinite(lo)) || (e.second < 0.0 && std::isfinite(up))) M.dlock[(size_t)e.first] = 1;
-      if ((e.second > 0.0 && std::isfinite(up)) || (e.second < 0.0 && std::isfinite(lo))) M.ulock[(size_t)e.first] = 1;
+      if ((e.second > 0.0 && std::isfinite(lo)) || (e.second < 0.0 && std::isfinite(up))) {
+        M.dlock[(size_t)e.first] = 1;
+        M.dl[(size_t)e.first]++;
+      }
+      if ((e.second > 0.0 && std::isfinite(up)) || (e.second < 0.0 && std::isfinite(lo))) {
+        M.ulock[(size_t)e.first] = 1;
+        M.ul[(size_t)e.first]++;
+      }
     }
   }
   for (int j = 0; j <= n; j++) M.c[(size_t)j] = api->get_obj_coef(root, j);
@@ -1329,6 +1342,31 @@ static int prop_host(const mvx_lp_api *api, const PropHost &M, const void *P, in
   return 0;
 }
 
+// hs[k] takes *lists[k] (+-inf for an absent bound): set_col_bnds_many (one call) when the table has it, else set_col_bnds per
+// entry with the type the finite bounds give, FX where they meet.
+static int apply_bound_lists(const mvx_lp_api *api, const std::vector<void *> &hs, const std::vector<const RcList *> &lists) {
+  if (api->set_col_bnds_many) {
+    std::vector<int> off(1, 0), cols;
+    std::vector<double> lb, ub;
+    for (const RcList *l : lists) {
+      for (const RcEntry &e : *l) {
+        cols.push_back(e.col);
+        lb.push_back(e.lb);
+        ub.push_back(e.ub);
+      }
+      off.push_back((int)cols.size());
+    }
+    if (cols.empty()) return 0;
+    return api->set_col_bnds_many(hs.data(), (int)hs.size(), off.data(), cols.data(), lb.data(), ub.data());
+  }
+  for (size_t k = 0; k < hs.size(); k++)
+    for (const RcEntry &e : *lists[k]) {
+      const bool has_l = std::isfinite(e.lb), has_u = std::isfinite(e.ub);
+      api->set_col_bnds(hs[k], e.col, has_l && has_u ? (e.lb == e.ub ? MVX_FX : MVX_DB) : has_l ? MVX_LO : has_u ? MVX_UP : MVX_FR, e.lb, e.ub);
+    }
+  return 0;
+}
+
 // One tree's propagation: a batch of handles through propagate_many (one call) when the table has it and the model fits the
 // kernel, else the host twin with the rows read once; the lists go on through set_col_bnds_many (one call), else
 // set_col_bnds per entry.  A result depends on the handle's own bounds and the root's rows only.
@@ -1374,27 +1412,9 @@ public:
       infeasible += o.infeasible;
       for (const RcEntry &e : o.list) (e.lb == e.ub ? fixed : tightened)++;
     }
-    if (_api->set_col_bnds_many) {
-      std::vector<int> off(1, 0), cols;
-      std::vector<double> lb, ub;
-      for (const PropOut &o : res) {
-        for (const RcEntry &e : o.list) {
-          cols.push_back(e.col);
-          lb.push_back(e.lb);
-          ub.push_back(e.ub);
-        }
-        off.push_back((int)cols.size());
-      }
-      if (cols.empty()) return 0;
-      return _api->set_col_bnds_many(hs.data(), (int)hs.size(), off.data(), cols.data(), lb.data(), ub.data());
-    }
-    for (size_t k = 0; k < hs.size(); k++)
-      for (const RcEntry &e : res[k].list) {
-        const bool has_l = std::isfinite(e.lb), has_u = std::isfinite(e.ub);
-        _api->set_col_bnds(hs[k], e.col, has_l && has_u ? (e.lb == e.ub ? MVX_FX : MVX_DB) : has_l ? MVX_LO : has_u ? MVX_UP : MVX_FR, e.lb,
-                           e.ub);
-      }
-    return 0;
+    std::vector<const RcList *> lists;
+    for (const PropOut &o : res) lists.push_back(&o.list);
+    return apply_bound_lists(_api, hs, lists);
   }
   // compute + apply on a batch of children in front of their first solve
   int run(const std::vector<void *> &hs) {
@@ -1417,6 +1437,305 @@ private:
   bool _device = true; // propagate_many is used while it accepts the model
   bool _ready = false;
   PropHost _M;
+};
+
+// ---- LP diving heuristic (dive, DESIGN.md "LP diving heuristic") ----
+
+// What a rule picks on one solved node.
+struct DivePick {
+  int nfrac = 0, col = 0, dir = 0;
+  double val = 0.0;
+};
+
+// The pick on one solved node (the host twin of k_divepick: same tests, every product rounded, the quotient correctly
+// rounded): the smallest key in lexicographic order with the column last, so the lowest column wins a tie.
+static int dive_pick_host(const mvx_lp_api *api, const RoundHost &M, const void *P, int rule, DivePick &out) {
+  const int n = M.n;
+  out = DivePick();
+  if (!P || (rule != 1 && rule != 2 && rule != 4) || api->get_num_cols(P) != n) return -1;
+  if (api->get_status(P) != MVX_OPT) return -3;
+  std::vector<double> v((size_t)n + 1, 0.0);
+  if (api->get_col_prim_all) api->get_col_prim_all(P, v.data());
+  else
+    for (int j = 1; j <= n; j++) v[(size_t)j] = api->get_col_prim(P, j);
+  double b1 = 0.0, b2 = 0.0;
+  for (int j = 1; j <= n; j++) {
+    if (!M.isint[(size_t)j]) continue;
+    const double vj = v[(size_t)j];
+    if (!(std::fabs(vj - std::rint(vj)) > 1e-9)) continue;
+    const double fd = vj - std::floor(vj), fu = std::ceil(vj) - vj;
+    const int near = fd <= fu ? 0 : 1;
+    int dir = near;
+    double k1 = 0.0, k2 = 0.0;
+    if (rule == 1) {
+      k1 = std::min(fd, fu);
+    } else if (rule == 2) {
+      const int dl = M.dl[(size_t)j], ul = M.ul[(size_t)j];
+      dir = dl < ul ? 0 : ul < dl ? 1 : near;
+      k1 = (double)std::min(dl, ul);
+      k2 = dir ? fu : fd;
+    } else {
+      const double s = M.sg * M.c[(size_t)j];
+      dir = s > 0.0 ? 0 : s < 0.0 ? 1 : near;
+      k1 = (std::fabs(M.c[(size_t)j]) * (dir ? fu : fd)) / (double)(M.cols[(size_t)j].size() + 1);
+    }
+    if (out.nfrac == 0 || k1 < b1 || (k1 == b1 && k2 < b2)) { // columns ascend: a tie keeps the lower one
+      b1 = k1;
+      b2 = k2;
+      out.col = j;
+      out.dir = dir;
+      out.val = vj;
+    }
+    out.nfrac++;
+  }
+  return 0;
+}
+
+// What the dives of one node gave: the best point of its rules (ties to the lower rule) and the work they took.
+struct DiveOut {
+  int found = 0;
+  double obj = 0.0;
+  std::vector<double> x; // [0..n] when found
+  long long lps = 0, pivots = 0;
+};
+
+// One tree's dives.  run() takes solved (OPT) nodes and advances all their (node, rule) dives in lockstep: per round one
+// pick call for the dives that stand on a fresh LP (dive_pick_many when the table has it and the model fits the kernel,
+// else the twin), one clone each, one bound-list apply and one batched solve for all of them, and at the end one rounding
+// call (mode 1) for the dives that ended integral.  No cutoff is used inside a dive: a result depends on its node's LP only.
+class Dive {
+public:
+  Dive(const mvx_lp_api *api, const void *root, const mvx_bnb_params &prm)
+      : _api(api), _root(root), _rules(prm.dive), _freq(prm.dive_freq), _depth(prm.dive_depth), _round(api, root, 1) {}
+  Dive(const mvx_lp_api *api, const void *root, int rules, int depth)
+      : _api(api), _root(root), _rules(rules), _freq(0), _depth(depth), _round(api, root, 1) {}
+  bool on() const { return _rules > 0; }
+  // the root, and with dive_freq = F > 0 every node whose oid F divides
+  bool selects(const MVOLP::NodeData &node) const { return _rules > 0 && (node.inital || (_freq > 0 && node.oid % _freq == 0)); }
+
+  // the picks of (hs[k], rules[k]); 0, or the failing call's code
+  int pick(const std::vector<const void *> &hs, const std::vector<int> &rules, std::vector<DivePick> &out) {
+    const size_t K = hs.size();
+    out.assign(K, DivePick());
+    if (K == 0) return 0;
+    if (_api->dive_pick_many && _device) {
+      std::vector<int> nfrac(K), col(K), dir(K);
+      std::vector<double> val(K);
+      const int rc = _api->dive_pick_many(_root, hs.data(), (int)K, rules.data(), nfrac.data(), col.data(), dir.data(), val.data());
+      if (rc == 0) {
+        for (size_t k = 0; k < K; k++) {
+          out[k].nfrac = nfrac[k];
+          out[k].col = col[k];
+          out[k].dir = dir[k];
+          out[k].val = val[k];
+        }
+        return 0;
+      }
+      if (rc != -5) return rc;
+      _device = false; // more columns than the kernel holds: the host twin, same bits, for the rest of the tree
+    }
+    if (!_ready) {
+      const int rc = round_host_model(_api, _root, _M);
+      if (rc != 0) return rc;
+      _ready = true;
+    }
+    for (size_t k = 0; k < K; k++) {
+      const int rc = dive_pick_host(_api, _M, hs[k], rules[k], out[k]);
+      if (rc != 0) return rc;
+    }
+    return 0;
+  }
+
+  // hs: solved (OPT) nodes; 0, or the failing call's code.  The dives are cut into batches that fit the strong-branching
+  // memory budget (two tableaux per live dive); results do not depend on the cut.
+  int run(const std::vector<const void *> &hs, std::vector<DiveOut> &out) {
+    out.assign(hs.size(), DiveOut());
+    if (hs.empty() || _rules <= 0) return 0;
+    std::vector<Job> jobs;
+    for (size_t t = 0; t < hs.size(); t++)
+      for (int rule = 1; rule <= 4; rule <<= 1)
+        if (_rules & rule) {
+          Job jb;
+          jb.node = t;
+          jb.rule = rule;
+          jb.cur = hs[t];
+          jobs.push_back(jb);
+        }
+    const size_t tab = (size_t)(_api->get_num_rows(hs[0]) + 1) * (size_t)(_api->get_num_cols(hs[0]) + 1) * 8;
+    const size_t per = std::max<size_t>(1, std::min(jobs.size(), sb_budget() / (2 * tab + 1)));
+    int rc = 0;
+    for (size_t j0 = 0; j0 < jobs.size() && rc == 0; j0 += per) rc = advance(jobs, j0, std::min(jobs.size(), j0 + per));
+    for (Job &jb : jobs) drop_cur(jb); // a failing call leaves clones behind
+    if (rc != 0) return rc;
+    // the node's result: its rules in ascending order, a strictly better point wins
+    const double sg = (_api->get_obj_dir && _api->get_obj_dir(_root) == MVX_MIN) ? -1.0 : 1.0;
+    for (Job &jb : jobs) {
+      DiveOut &o = out[jb.node];
+      o.lps += jb.lps;
+      o.pivots += jb.pivots;
+      if (jb.res.found && (!o.found || sg * jb.res.obj > sg * o.obj)) {
+        o.found = 1;
+        o.obj = jb.res.obj;
+        o.x = std::move(jb.res.x);
+      }
+    }
+    return 0;
+  }
+
+private:
+  enum State { PICK, FLIP, INTEGRAL, ENDED }; // PICK: stands on a solved LP; FLIP: a side failed, the other one is next
+  struct Job {
+    size_t node = 0;
+    int rule = 0;
+    const void *cur = nullptr; // the node itself, or the dive's own clone
+    bool owned = false;
+    State state = PICK;
+    int d = 0, col = 0, dir = 0;
+    double val = 0.0;
+    long long lps = 0, pivots = 0;
+    HeurOut res;
+  };
+  void drop_cur(Job &jb) {
+    if (jb.owned && jb.cur) _api->delete_prob(const_cast<void *>(jb.cur));
+    jb.cur = nullptr;
+    jb.owned = false;
+  }
+  // the bounds side `dir` of jb.col gives a clone of jb.cur; false when they cross
+  bool side_bounds(const Job &jb, int dir, RcEntry &e) const {
+    const double inf = std::numeric_limits<double>::infinity();
+    const int t = _api->get_col_type(jb.cur, jb.col);
+    const double l = (t == MVX_LO || t == MVX_DB || t == MVX_FX) ? _api->get_col_lb(jb.cur, jb.col) : -inf;
+    const double u = t == MVX_FX ? l : (t == MVX_UP || t == MVX_DB) ? _api->get_col_ub(jb.cur, jb.col) : inf;
+    e.col = jb.col;
+    e.lb = dir ? std::ceil(jb.val) : l;
+    e.ub = dir ? u : std::floor(jb.val);
+    return e.lb <= e.ub;
+  }
+
+  int advance(std::vector<Job> &jobs, size_t j0, size_t j1) {
+    const int n = _api->get_num_cols(_root);
+    const int limit = _depth > 0 ? _depth : 4 * n + 64;
+    for (;;) {
+      // 1. the picks of the dives that stand on a fresh LP
+      std::vector<const void *> ph;
+      std::vector<int> pr;
+      std::vector<size_t> pj;
+      for (size_t j = j0; j < j1; j++)
+        if (jobs[j].state == PICK) {
+          ph.push_back(jobs[j].cur);
+          pr.push_back(jobs[j].rule);
+          pj.push_back(j);
+        }
+      std::vector<DivePick> picks;
+      const int rc = pick(ph, pr, picks);
+      if (rc != 0) return rc;
+      for (size_t k = 0; k < pj.size(); k++) {
+        Job &jb = jobs[pj[k]];
+        if (picks[k].nfrac == 0) jb.state = INTEGRAL;
+        else if (jb.d >= limit) jb.state = ENDED;
+        else {
+          jb.col = picks[k].col;
+          jb.dir = picks[k].dir;
+          jb.val = picks[k].val;
+        }
+      }
+      // 2. one clone per live dive with its side's bounds; a side whose bounds cross fails without a solve
+      std::vector<size_t> kj;
+      std::vector<void *> kids;
+      std::vector<RcList> lists;
+      for (size_t j = j0; j < j1; j++) {
+        Job &jb = jobs[j];
+        if (jb.state != PICK && jb.state != FLIP) continue;
+        RcEntry e{0, 0.0, 0.0};
+        bool ok = side_bounds(jb, jb.dir, e);
+        if (!ok && jb.state == PICK) {
+          jb.state = FLIP;
+          jb.dir = 1 - jb.dir;
+          ok = side_bounds(jb, jb.dir, e);
+        }
+        if (!ok) {
+          jb.state = ENDED; // infeasible
+          continue;
+        }
+        void *kid = _api->create_prob();
+        _api->copy_prob(kid, jb.cur, MVX_ON);
+        kj.push_back(j);
+        kids.push_back(kid);
+        lists.push_back(RcList(1, e));
+      }
+      if (kids.empty()) break;
+      std::vector<const RcList *> lp;
+      for (const RcList &l : lists) lp.push_back(&l);
+      int brc = apply_bound_lists(_api, kids, lp);
+      // 3. one batched solve of the round's children, with the default parameters like a B&B child
+      std::vector<int> before(kids.size());
+      if (brc == 0) {
+        for (size_t k = 0; k < kids.size(); k++) before[k] = _api->get_it_cnt(kids[k]);
+        if (_api->simplex_batch) _api->simplex_batch(kids.data(), (int)kids.size(), nullptr, nullptr);
+        else
+          for (void *k : kids) _api->simplex(k, nullptr);
+      }
+      for (size_t k = 0; k < kids.size(); k++) {
+        Job &jb = jobs[kj[k]];
+        if (brc != 0) {
+          _api->delete_prob(kids[k]);
+          continue;
+        }
+        jb.lps++;
+        jb.pivots += _api->get_it_cnt(kids[k]) - before[k];
+        if (_api->get_status(kids[k]) == MVX_OPT) { // the child replaces cur
+          drop_cur(jb);
+          jb.cur = kids[k];
+          jb.owned = true;
+          jb.d++;
+          jb.state = PICK;
+        } else {
+          _api->delete_prob(kids[k]);
+          if (jb.state == PICK) { // the opposite side of the same column, once
+            jb.state = FLIP;
+            jb.dir = 1 - jb.dir;
+          } else {
+            jb.state = ENDED; // infeasible
+          }
+        }
+      }
+      if (brc != 0) return brc;
+    }
+    // 4. the dives that ended integral: rounded and checked against the root's model
+    std::vector<const void *> rh;
+    std::vector<size_t> rj;
+    for (size_t j = j0; j < j1; j++)
+      if (jobs[j].state == INTEGRAL) {
+        rh.push_back(jobs[j].cur);
+        rj.push_back(j);
+      }
+    std::vector<HeurOut> got;
+    const int rc = _round.run(rh, got);
+    if (rc != 0) return rc;
+    for (size_t k = 0; k < rj.size(); k++) jobs[rj[k]].res = std::move(got[k]);
+    for (size_t j = j0; j < j1; j++) drop_cur(jobs[j]);
+    return 0;
+  }
+
+  const mvx_lp_api *_api;
+  const void *_root;
+  int _rules, _freq, _depth;
+  Heuristic _round;
+  bool _device = true; // dive_pick_many is used while it accepts the model
+  bool _ready = false;
+  RoundHost _M;
+};
+
+// The dives' counts, booked the way the serial loop meets the nodes.
+struct DiveBook {
+  long long calls = 0, found = 0, improved = 0, lps = 0, pivots = 0;
+  void store(mvx_bnb_result *res) const {
+    res->dive_calls = calls;
+    res->dive_found = found;
+    res->dive_improved = improved;
+    res->dive_lps = lps;
+    res->dive_pivots = pivots;
+  }
 };
 
 // ---- what the three drivers share: the tree's state and what happens to a node once its LP is solved ----
@@ -1447,6 +1766,7 @@ struct Tree {
   int hit_limit = 0, count = 0, rc_out = 0;
   long long sb_lps = 0, sb_pivots = 0;
   HeurBook hbook;
+  DiveBook dbook;
 
   Tree(const mvx_lp_api *api_, const void *prob, const mvx_bnb_params &p)
       : api(api_), prm(p), quirks(p.reference_quirks != 0), sg(MVOLP::sense_of(api_, prob, p)), n0(api_->get_num_cols(prob)),
@@ -1505,6 +1825,21 @@ struct Tree {
   }
 
   void book_heur(const HeurOut &h, int oid) { hbook.book(h, oid, sg, bestLower, has_incumbent, incumbent_oid, xbest); }
+  // a dived node that branches: its work is booked, and its point becomes the incumbent when it is strictly better
+  void book_dive(const DiveOut &d, int oid) {
+    dbook.calls++;
+    dbook.lps += d.lps;
+    dbook.pivots += d.pivots;
+    if (!d.found) return;
+    dbook.found++;
+    if (!(sg * d.obj > sg * bestLower)) return;
+    dbook.improved++;
+    bestLower = d.obj;
+    has_incumbent = 1;
+    incumbent_oid = oid;
+    hbook.incumbent = 2;
+    for (size_t j = 1; j < xbest.size() && j < d.x.size(); j++) xbest[j] = d.x[j];
+  }
   void book_choice(const Choice &c) {
     sb_lps += c.sb_lps;
     sb_pivots += c.sb_pivots;
@@ -1549,6 +1884,7 @@ struct Tree {
     res->sb_lps = sb_lps;
     res->sb_pivots = sb_pivots;
     hbook.store(res);
+    dbook.store(res);
     if (rcfix) rcfix->store(res);
     if (prop) prop->store(res);
     return rc_out;
@@ -1584,6 +1920,7 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm,
   Heuristic heur(api, prob, prm.heur);
   RcFix rcfix(api);
   Prop prop(api, prob, prm.prop);
+  Dive dive(api, prob, prm);
 
   while (!leafContainer.empty()) { // bs.cpp:96
     if (T.node_limit()) break;
@@ -1611,7 +1948,16 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm,
         }
         T.book_heur(ho[0], node->oid);
       }
-      // reduced-cost tightening against the incumbent in hand (a point the heuristic has just found counts), on the LP as
+      // the dives start from the node's LP as solved, behind the rounding heuristic and in front of rc_fix and the cut step
+      if (dive.selects(*node) && api->get_status(a) == MVX_OPT) {
+        std::vector<DiveOut> dout;
+        if (dive.run({a}, dout) != 0) {
+          T.rc_out = -2;
+          break;
+        }
+        T.book_dive(dout[0], node->oid);
+      }
+      // reduced-cost tightening against the incumbent in hand (a point the heuristic or a dive has just found counts), on the LP as
       // solved; the list goes to both children
       RcList rcl;
       if (prm.rc_fix > 0 && T.has_incumbent && api->get_status(a) == MVX_OPT) {
@@ -1691,6 +2037,7 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
   Heuristic heur(api, prob, prm.heur);
   RcFix rcfix(api);
   Prop prop(api, prob, prm.prop);
+  Dive dive(api, prob, prm);
   auto fail = [&]() { // whatever code a failing call gives, the tree so far goes back with -2
     T.rc_out = -2;
     stop = true;
@@ -1832,7 +2179,7 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
     // that qualify.  may[w]: node w is neither infeasible nor integral, so it branches unless its bound prunes it; opt[w]: and
     // its LP ended OPT.
     std::vector<char> may, opt;
-    if (prm.var_strat >= 3 || prm.heur > 0 || prm.rc_fix > 0) {
+    if (prm.var_strat >= 3 || prm.heur > 0 || prm.rc_fix > 0 || dive.on()) {
       if (info.empty()) {
         info.resize(W);
         for (size_t w = 0; w < W; w++) info[w] = printInfo(api, a[w], quirks);
@@ -1860,6 +2207,15 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
     // that do branch, so the incumbent moves where the serial loop's does
     std::vector<HeurOut> hres(opt.size());
     if (prm.heur > 0 && on_slots(a, opt, 0, hres, [&](const auto &hs, const auto &, auto &got) { return heur.run(hs, got); }) != 0) {
+      fail();
+      break;
+    }
+    // the dives of every selected node of the window that may branch, all in lockstep in one call; booked by the replay for
+    // the nodes that do branch.  No cutoff enters a dive, so a result is the serial loop's
+    std::vector<char> dsel(dive.on() ? W : 0);
+    for (size_t w = 0; w < dsel.size(); w++) dsel[w] = opt[w] && dive.selects(*leafContainer[w]);
+    std::vector<DiveOut> dres(dsel.size());
+    if (dive.on() && on_slots(a, dsel, 0, dres, [&](const auto &hs, const auto &, auto &got) { return dive.run(hs, got); }) != 0) {
       fail();
       break;
     }
@@ -1913,6 +2269,7 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
         // as it is -- but it marks the handle's solution mirrors stale, and reading one value afterwards is a device
         // export and a host round trip per branching node (~40 us, a tenth of the cut modes' run)
         if (prm.heur > 0 && opt[w]) T.book_heur(hres[w], node->oid);
+        if (dive.on() && dsel[w]) T.book_dive(dres[w], node->oid);
         RcList node_rc;
         if (prm.rc_fix > 0 && T.has_incumbent && opt[w]) {
           // no lists yet, or the incumbent has moved since they were computed
@@ -2364,6 +2721,9 @@ const mvx_lp_api g_hip_api = {
     mvx_set_col_bnds_many ? +[](void *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub) {
       return mvx_set_col_bnds_many((mvx_prob *const *)Ps, count, off, cols, lb, ub);
     } : nullptr,
+    mvx_dive_pick_many ? +[](const void *root, const void *const *Ps, int count, const int *rules, int *nfrac, int *col, int *dir, double *val) {
+      return mvx_dive_pick_many((const mvx_prob *)root, (const mvx_prob *const *)Ps, count, rules, nfrac, col, dir, val);
+    } : nullptr,
 };
 
 } // namespace
@@ -2389,6 +2749,9 @@ void mvx_bnb_default_params(mvx_bnb_params *p) {
   p->heur = 0;
   p->rc_fix = 0;
   p->prop = 0;
+  p->dive = 0;
+  p->dive_freq = 0;
+  p->dive_depth = 0;
 }
 
 // Repaired mode's rule for an integer column whose bounds are not integers (legal input: LP and MPS files may carry them):
@@ -2440,7 +2803,10 @@ int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *
       // rc_fix: the bound argument needs the repaired mode's children and cuts; not (yet) in the best-bound window
       (params->rc_fix > 0 && (params->reference_quirks != 0 || params->best_window > 0)) ||
       // prop: children with both bounds kept, and not (yet) in the best-bound window either
-      params->prop < 0 || params->prop > 16 || (params->prop > 0 && (params->reference_quirks != 0 || params->best_window > 0))) {
+      params->prop < 0 || params->prop > 16 || (params->prop > 0 && (params->reference_quirks != 0 || params->best_window > 0)) ||
+      // dive: children with both bounds kept, and not (yet) in the best-bound window either
+      params->dive < 0 || params->dive > 7 || params->dive_freq < 0 || params->dive_depth < 0 ||
+      (params->dive > 0 && (params->reference_quirks != 0 || params->best_window > 0))) {
     std::memset(res, 0, sizeof(*res));
     return -1;
   }
@@ -2545,6 +2911,41 @@ int mvx_bnb_round(const mvx_lp_api *api, const void *prob, const void *root, int
   const int rc = round_host_model(api, root, M);
   if (rc != 0) return rc;
   return round_host(api, M, prob, mode, obj, found, x);
+}
+
+int mvx_bnb_dive_pick(const mvx_lp_api *api, const void *prob, const void *root, int rule, int *nfrac, int *col, int *dir, double *val) {
+  if (!api) api = &g_hip_api;
+  if (!prob || !root || (rule != 1 && rule != 2 && rule != 4) || !nfrac || !col || !dir || !val) return -1;
+  RoundHost M;
+  int rc = round_host_model(api, root, M);
+  if (rc != 0) return rc;
+  DivePick p;
+  rc = dive_pick_host(api, M, prob, rule, p);
+  if (rc != 0) return rc;
+  *nfrac = p.nfrac;
+  *col = p.col;
+  *dir = p.dir;
+  *val = p.val;
+  return 0;
+}
+
+int mvx_bnb_dive(const mvx_lp_api *api, const void *prob, const void *root, int rules, int depth, double *obj, int *found, double *x,
+                 long long *lps, long long *pivots) {
+  if (!api) api = &g_hip_api;
+  if (!prob || !root || rules < 1 || rules > 7 || depth < 0 || !obj || !found || !x || !lps || !pivots ||
+      api->get_num_cols(prob) != api->get_num_cols(root))
+    return -1;
+  if (api->get_status(prob) != MVX_OPT) return -3;
+  Dive dive(api, root, rules, depth);
+  std::vector<DiveOut> out;
+  const int rc = dive.run({prob}, out);
+  if (rc != 0) return rc;
+  *obj = out[0].obj;
+  *found = out[0].found;
+  *lps = out[0].lps;
+  *pivots = out[0].pivots;
+  for (size_t j = 1; j < out[0].x.size(); j++) x[j] = out[0].x[j];
+  return 0;
 }
 
 int mvx_bnb_rc_tighten(const mvx_lp_api *api, const void *prob, double cutoff, double tol, int *cnt, int *cols, double *lb, double *ub) {

@@ -107,6 +107,7 @@ extern "C" int mvx_branchAndBound_dist(const mvx_lp_api *api, const mvx_image_ap
   if (prm.node_strat != 0 || dp.per_rank < 1 || prm.var_strat < 0 || prm.var_strat > 2 || prm.heur != 0) return MVX_EFAIL;
   if (prm.rc_fix != 0) return MVX_EFAIL; // reduced-cost tightening is not carried to several ranks yet either
   if (prm.prop != 0) return MVX_EFAIL;   // nor is node bound propagation
+  if (prm.dive != 0) return MVX_EFAIL;   // nor are the dives
   const int rank = comm ? comm->rank : 0, world = comm ? comm->size : 1;
   const int per_rank = dp.per_rank;
   const int slack = dp.slack >= 0 ? dp.slack : std::max(1, per_rank / 4);

@@ -527,6 +527,10 @@ int mvx_propagate_many(const mvx_prob *root, const mvx_prob *const *Ps, int coun
 int mvx_set_col_bnds_many(mvx_prob *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub) {
   return mvx::engine_set_bounds_many(Ps, count, off, cols, lb, ub);
 }
+int mvx_dive_pick_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, const int *rules, int *nfrac, int *col, int *dir,
+                       double *val) {
+  return mvx::engine_dive_pick_many(root, Ps, count, rules, nfrac, col, dir, val);
+}
 
 int mvx_device_count(void) { return mvx::device_count(); }
 int mvx_set_device(int dev) { return mvx::set_device(dev); }

@@ -38,10 +38,11 @@ struct DevMatrix {
 // was built from: it is rebuilt when any of that has changed.
 struct RoundModel {
   int m0 = 0, n = 0, ldm = 0, dir = 0;
-  void *dev = nullptr; // [At (n+1) x ldm][rlo m0][rhi m0][clo n+1][chi n+1][c n+1][flags n+1]
+  void *dev = nullptr; // [At (n+1) x ldm][rlo m0][rhi m0][clo n+1][chi n+1][c n+1][flags n+1][dl n+1][ul n+1][len n+1]
   void *dev_rows = nullptr; // [Ar m0 x ldn]: the same rows by row, for k_prop; uploaded on the first propagation
   int ldn = 0;
   size_t o_rlo = 0, o_rhi = 0, o_clo = 0, o_chi = 0, o_c = 0, o_flags = 0;
+  size_t o_dl = 0, o_ul = 0, o_len = 0; // per column: rows that lock it down / up, its non-zeros (k_divepick)
   std::vector<mvx::RowPtr> rows; // owned: a row's address cannot be reused while the model compares against it
   std::vector<double> c, clb, cub, rlb, rub;
   std::vector<int> kind;
@@ -95,6 +96,7 @@ void launch_round(const RndArgs &a, hipStream_t);
 void launch_rcfix(const RcArgs &a, hipStream_t);
 void launch_tighten(const TightHandle *hs, const TightEntry *es, int count, hipStream_t);
 void launch_prop(const PropArgs &a, hipStream_t);
+void launch_divepick(const DiveArgs &a, hipStream_t);
 void launch_setbnds(const SetbHandle *hs, const SetbEntry *es, const SetbShift *ss, int handles, hipStream_t);
 void launch_refresh_select(Ctl *, const int *tflag, int var, hipStream_t);
 size_t persist_lds_bytes(int m, int cpw);
@@ -2636,9 +2638,11 @@ static const RoundModel *round_model(Context &c, const mvx_prob *R) {
   M->o_rlo = carve((size_t)m0 * 8); M->o_rhi = carve((size_t)m0 * 8);
   M->o_clo = carve((size_t)(n + 1) * 8); M->o_chi = carve((size_t)(n + 1) * 8); M->o_c = carve((size_t)(n + 1) * 8);
   M->o_flags = carve((size_t)(n + 1) * 4);
+  M->o_dl = carve((size_t)(n + 1) * 4); M->o_ul = carve((size_t)(n + 1) * 4); M->o_len = carve((size_t)(n + 1) * 4);
   std::vector<unsigned char> h(carve.off, 0);
   double *At = (double *)h.data();
   int *flags = (int *)(h.data() + M->o_flags);
+  int *dl = (int *)(h.data() + M->o_dl), *ul = (int *)(h.data() + M->o_ul), *len = (int *)(h.data() + M->o_len);
   for (int j = 1; j <= n; j++) flags[j] = R->kind[(size_t)j] != MVX_CV ? RND_INT : 0;
   for (int i = 1; i <= m0; i++) {
     const double *ai = R->A[(size_t)i]->data();
@@ -2649,8 +2653,15 @@ static const RoundModel *round_model(Context &c, const mvx_prob *R) {
     for (int j = 1; j <= n; j++) {
       const double v = ai[j];
       At[(size_t)j * ldm + (size_t)(i - 1)] = v;
-      if ((v > 0.0 && lo) || (v < 0.0 && up)) flags[j] |= RND_DLOCK; // lowering x_j can break the row
-      if ((v > 0.0 && up) || (v < 0.0 && lo)) flags[j] |= RND_ULOCK;
+      if ((v > 0.0 && lo) || (v < 0.0 && up)) {
+        flags[j] |= RND_DLOCK; // lowering x_j can break the row
+        dl[j]++;
+      }
+      if ((v > 0.0 && up) || (v < 0.0 && lo)) {
+        flags[j] |= RND_ULOCK;
+        ul[j]++;
+      }
+      if (v != 0.0) len[j]++;
     }
   }
   std::memcpy(h.data() + M->o_clo, R->clb.data(), (size_t)(n + 1) * 8);
@@ -2722,6 +2733,63 @@ int engine_round_many(const mvx_prob *root, const mvx_prob *const *Ps, int count
   std::memcpy(obj, hb + o_obj, (size_t)count * 8);
   std::memcpy(found, hb + o_found, (size_t)count * 4);
   std::memcpy(x, hb + o_x, (size_t)count * (n + 1) * 8);
+  return 0;
+}
+
+// ------------------------------------------------------------------ diving pick (k_divepick)
+// The branching pick of `count` (solved handle, rule) pairs against root's model (mvx_dive_pick_many): one upload of the
+// descriptors, one k_divepick launch, results straight into the pinned buffer.  Return codes: 0; -1 bad arguments (a rule
+// outside {1, 2, 4}, another column count); -2 device out of memory; -3 a handle whose status is not MVX_OPT; -5 n > RND_NMAX,
+// as for engine_round_many, whose model it shares.
+int engine_dive_pick_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, const int *rules, int *nfrac, int *col, int *dir,
+                          double *val) {
+  if (!root || count < 1 || !Ps || !rules || !nfrac || !col || !dir || !val) return -1;
+  const int n = root->n;
+  for (int t = 0; t < count; t++)
+    if (!Ps[t] || Ps[t]->n != n || (rules[t] != 1 && rules[t] != 2 && rules[t] != 4)) return -1;
+  if (n > RND_NMAX) return -5;
+  for (int t = 0; t < count; t++)
+    if (!Ps[t]->valid || Ps[t]->status != MVX_OPT) return -3;
+  Context &c = ctx();
+  bind_device(c);
+  MAIN_LOCK(c);
+  flush_copies(c); // a clone recorded into one of these slabs lands first
+  SolveCtx &sc = c.main;
+  const RoundModel *M = round_model(c, root);
+  if (!M) return -2;
+  Carver carve;
+  // up: [descriptors]; out: [nfrac][col][dir][val]
+  const size_t o_nodes = carve((size_t)count * sizeof(DiveNode));
+  const size_t up_bytes = carve.off;
+  const size_t o_nf = carve((size_t)count * 4), o_col = carve((size_t)count * 4), o_dir = carve((size_t)count * 4),
+               o_val = carve((size_t)count * 8);
+  if (!node_scratch_reserve(c, carve.off, carve.off)) return -2;
+  unsigned char *hb = (unsigned char *)c.nodes.host, *db = (unsigned char *)c.nodes.dev;
+  DiveNode *h_nodes = (DiveNode *)(hb + o_nodes);
+  for (int t = 0; t < count; t++) {
+    const mvx_prob *P = Ps[t];
+    DiveNode &nd = h_nodes[t];
+    nd.T = P->d_T; nd.bvar = P->d_bvar; nd.nvar = P->d_nvar; nd.nflag = P->d_nflag; nd.nlb = P->d_nlb; nd.nub = P->d_nub;
+    nd.m = P->m; nd.ld = P->ld; nd.rule = rules[t]; nd.pad = 0;
+  }
+  HIPCHECK(hipMemcpyAsync(db, hb, up_bytes, hipMemcpyHostToDevice, sc.stream));
+  unsigned char *ob = c.nodes.host_dev ? c.nodes.host_dev : db;
+  const unsigned char *mb = (const unsigned char *)M->dev;
+  DiveArgs a;
+  a.nodes = (const DiveNode *)(db + o_nodes);
+  a.c = (const double *)(mb + M->o_c);
+  a.flags = (const int *)(mb + M->o_flags);
+  a.dl = (const int *)(mb + M->o_dl); a.ul = (const int *)(mb + M->o_ul); a.len = (const int *)(mb + M->o_len);
+  a.nfrac = (int *)(ob + o_nf); a.col = (int *)(ob + o_col); a.dir = (int *)(ob + o_dir); a.val = (double *)(ob + o_val);
+  a.sg = root->dir == MVX_MIN ? -1.0 : 1.0;
+  a.n = n; a.count = count;
+  launch_divepick(a, sc.stream);
+  if (!c.nodes.host_dev) HIPCHECK(hipMemcpyAsync(hb + o_nf, db + o_nf, carve.off - o_nf, hipMemcpyDeviceToHost, sc.stream));
+  HIPCHECK(hipStreamSynchronize(sc.stream));
+  std::memcpy(nfrac, hb + o_nf, (size_t)count * 4);
+  std::memcpy(col, hb + o_col, (size_t)count * 4);
+  std::memcpy(dir, hb + o_dir, (size_t)count * 4);
+  std::memcpy(val, hb + o_val, (size_t)count * 8);
   return 0;
 }
 

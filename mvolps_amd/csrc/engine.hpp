@@ -40,6 +40,9 @@ int engine_penalties_many(const mvx_prob *const *Ps, int count, const int *cols,
                           double *pen_up, int *arg_down, int *arg_up);
 // primal rounding heuristic on `count` solved handles against root's model, one launch (k_round); see engine.cpp
 int engine_round_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, int mode, double *obj, int *found, double *x);
+// the diving heuristic's branching pick for `count` (solved handle, rule) pairs against root's model, one launch (k_divepick)
+int engine_dive_pick_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, const int *rules, int *nfrac, int *col, int *dir,
+                          double *val);
 // reduced-cost bound tightening of `count` solved handles, one launch (k_rcfix), and the bound lists of many handles applied
 // with one launch (k_tighten); see engine.cpp
 int engine_rc_tighten_many(const mvx_prob *const *Ps, int count, const double *cutoff, double tol, int *cnt, int *cols, double *lb,

@@ -4559,6 +4559,95 @@ void launch_setbnds(const SetbHandle *hs, const SetbEntry *es, const SetbShift *
   hipLaunchKernelGGL(k_setbnds, dim3((unsigned)handles), dim3(256), 0, s, hs, es, ss);
 }
 
+// ---------------------------------------------------------------------------- k_divepick
+// The branching pick of a diving rule (mvx_dive_pick_many, DESIGN.md "LP diving heuristic"), one workgroup per (handle,
+// rule).  A lane over the tableau rows takes the basic structural columns' values from column 0, a lane over the non-basic
+// positions the bound the status names (dev_nb_value) -- k_classify's selection, get_col_prim's bits -- and evaluates the
+// column on the spot from the per-column model arrays: integer and more than 1e-9 off an integer makes it a candidate, its
+// key is the rule's.  Each lane keeps the count and the smallest (k1, k2, column) it met; the waves reduce with shuffles,
+// four partials meet in LDS.  The order is strict and total, so the winner does not depend on the reduction tree: the host
+// twin's bits.  No value array, no atomics.
+struct DiveKey {
+  double k1, k2, v; // k1 = +inf, j = INT_MAX: none
+  int j, dir;
+};
+__device__ __forceinline__ bool dive_before(const DiveKey &a, const DiveKey &b) {
+  return a.k1 < b.k1 || (a.k1 == b.k1 && (a.k2 < b.k2 || (a.k2 == b.k2 && a.j < b.j)));
+}
+__device__ __forceinline__ void dive_eval(const DiveArgs &a, int rule, int j, double v, DiveKey &best, int &cnt) {
+  if (!(a.flags[j] & RND_INT)) return;
+  if (!(fabs(v - rint(v)) > 1e-9)) return;
+  const double fd = v - floor(v), fu = ceil(v) - v;
+  const int near = fd <= fu ? 0 : 1;
+  DiveKey k = {0.0, 0.0, v, j, near};
+  if (rule == 1) {
+    k.k1 = fd <= fu ? fd : fu;
+  } else if (rule == 2) {
+    const int dl = a.dl[j], ul = a.ul[j];
+    k.dir = dl < ul ? 0 : ul < dl ? 1 : near;
+    k.k1 = (double)(dl < ul ? dl : ul);
+    k.k2 = k.dir ? fu : fd;
+  } else {
+    const double cj = a.c[j], s = a.sg * cj;
+    k.dir = s > 0.0 ? 0 : s < 0.0 ? 1 : near;
+    k.k1 = xdiv(fabs(cj) * (k.dir ? fu : fd), (double)(a.len[j] + 1)); // the host's division
+  }
+  cnt++;
+  if (dive_before(k, best)) best = k;
+}
+
+__global__ __launch_bounds__(256) void k_divepick(DiveArgs a) {
+  __shared__ double s_k1[4], s_k2[4], s_v[4];
+  __shared__ int s_j[4], s_dir[4], s_cnt[4];
+  const int t = (int)blockIdx.x;
+  const DiveNode nd = a.nodes[t];
+  const int n = a.n, m = nd.m, rule = nd.rule;
+  const double inf = __builtin_huge_val();
+  DiveKey best = {inf, inf, 0.0, 0x7fffffff, 0};
+  int cnt = 0;
+  for (int i = 1 + TIDX; i <= m; i += 256) {
+    const int k = nd.bvar[i];
+    if (k > m && k <= m + n) dive_eval(a, rule, k - m, nd.T[(size_t)i * (size_t)nd.ld], best, cnt);
+  }
+  for (int q = 1 + TIDX; q <= n; q += 256) {
+    const int k = nd.nvar[q];
+    if (k > m && k <= m + n) dive_eval(a, rule, k - m, dev_nb_value(nd.nflag[q], nd.nlb[q], nd.nub[q]), best, cnt);
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    DiveKey o;
+    o.k1 = __shfl_xor(best.k1, off, 64);
+    o.k2 = __shfl_xor(best.k2, off, 64);
+    o.v = __shfl_xor(best.v, off, 64);
+    o.j = __shfl_xor(best.j, off, 64);
+    o.dir = __shfl_xor(best.dir, off, 64);
+    cnt += __shfl_xor(cnt, off, 64);
+    if (dive_before(o, best)) best = o;
+  }
+  const int lane = TIDX & 63, wv = TIDX >> 6;
+  if (lane == 0) {
+    s_k1[wv] = best.k1; s_k2[wv] = best.k2; s_v[wv] = best.v;
+    s_j[wv] = best.j; s_dir[wv] = best.dir; s_cnt[wv] = cnt;
+  }
+  __syncthreads();
+  if (TIDX == 0) {
+    int total = s_cnt[0];
+    for (int w = 1; w < 4; w++) {
+      const DiveKey o = {s_k1[w], s_k2[w], s_v[w], s_j[w], s_dir[w]};
+      total += s_cnt[w];
+      if (dive_before(o, best)) best = o;
+    }
+    const bool any = best.j != 0x7fffffff;
+    a.nfrac[t] = total;
+    a.col[t] = any ? best.j : 0;
+    a.dir[t] = any ? best.dir : 0;
+    a.val[t] = any ? best.v : 0.0;
+  }
+}
+
+void launch_divepick(const DiveArgs &a, hipStream_t s) {
+  hipLaunchKernelGGL(k_divepick, dim3((unsigned)a.count), dim3(256), 0, s, a);
+}
+
 // ------------------------------------------------------------------ launch wrappers
 
 // tuning knobs of the streamed update (mvx_set_tuning; defaults are the measured best)

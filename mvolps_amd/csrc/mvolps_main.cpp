@@ -69,6 +69,10 @@ int main(int argc, char **argv) {
               << "                  integer columns from their reduced costs on every branching node; both children inherit them\n"
               << "  --prop [K]      with --repaired (not with --best-window): bound propagation over the model's rows, at most K rounds\n"
               << "                  (1..16; 8 without a number), on the root and on every child in front of its first solve\n"
+              << "  --dive [R]      with --repaired (not with --best-window): LP diving heuristic at the root, R the rules as bits\n"
+              << "                  (1 fractional, 2 locks, 4 vector length; 7 without a number); a better point becomes the incumbent\n"
+              << "  --dive-freq F   with --dive: also dive at every branching node whose number F divides (default 0: the root only)\n"
+              << "  --dive-depth D  with --dive: step limit of one dive (default 0: 4 n + 64)\n"
               << "Help:\n  -h/--help\n";
     return 0;
   }
@@ -140,6 +144,19 @@ int main(int argc, char **argv) {
       return -1;
     }
   }
+  if (input.CMDOptionExists("--dive")) {
+    // the number is optional, as for --prop
+    const std::string &k = input.getCMDOption("--dive");
+    const bool numeric = !k.empty() && std::all_of(k.begin(), k.end(), [](char ch) { return ch >= '0' && ch <= '9'; });
+    const long kv = numeric ? std::strtol(k.c_str(), nullptr, 10) : 7;
+    params.dive = kv >= 1 && kv <= 7 ? (int)kv : -1;
+    if (params.dive < 1) {
+      std::fprintf(stderr, "Unknown parameter value for --dive\n");
+      return -1;
+    }
+  }
+  if (!int_opt("--dive-freq", 0, 1 << 30, &params.dive_freq)) return -1;
+  if (!int_opt("--dive-depth", 0, 1 << 30, &params.dive_depth)) return -1;
   if (input.CMDOptionExists("--cut-select")) params.cut_select = std::atoi(input.getCMDOption("--cut-select").c_str());
   if (input.CMDOptionExists("--window")) params.window = std::atoi(input.getCMDOption("--window").c_str());
   if (input.CMDOptionExists("--best-window")) params.best_window = std::atoi(input.getCMDOption("--best-window").c_str());
@@ -150,14 +167,14 @@ int main(int argc, char **argv) {
   mvx_bnb_result res;
   const int brc = mvx_branchAndBound(nullptr, prob, &params, &res);
   if (brc == -1) {
-    std::fprintf(stderr, "-vs %d / --heur %d%s%s are not supported with these options (-vs 3 / 4: not with --best-window; --heur: only "
-                 "with --repaired; --rcfix / --prop: only with --repaired and without --best-window)\n", params.var_strat, params.heur,
-                 params.rc_fix ? " / --rcfix" : "", params.prop ? " / --prop" : "");
+    std::fprintf(stderr, "-vs %d / --heur %d%s%s%s are not supported with these options (-vs 3 / 4: not with --best-window; --heur: only "
+                 "with --repaired; --rcfix / --prop / --dive: only with --repaired and without --best-window)\n", params.var_strat,
+                 params.heur, params.rc_fix ? " / --rcfix" : "", params.prop ? " / --prop" : "", params.dive ? " / --dive" : "");
     mvx_delete_prob(prob);
     return -1;
   }
   if (brc != 0)
-    std::fprintf(stderr, "branch-and-bound stopped: the branching penalties, the heuristic or the propagation could not be computed (%d)\n", brc);
+    std::fprintf(stderr, "branch-and-bound stopped: the branching penalties, the heuristic, the propagation or a dive could not be computed (%d)\n", brc);
   if (input.CMDOptionExists("--events")) mvx_bnb_write_events(&res, input.getCMDOption("--events").c_str());
   mvx_bnb_print_tree(&res, nullptr); // bs.cpp:329-343
   std::vector<char> buf(64 + 64 * (size_t)res.n);
@@ -167,12 +184,16 @@ int main(int argc, char **argv) {
   if (verbose && params.var_strat == 4) std::printf("Strong branching: %lld child LPs, %lld pivots\n", res.sb_lps, res.sb_pivots);
   if (verbose && params.heur > 0)
     std::printf("Rounding heuristic: %lld nodes, %lld feasible, %lld improved the incumbent%s\n", res.heur_calls, res.heur_found,
-                res.heur_improved, res.incumbent_heur ? " (the final incumbent is one of them)" : "");
+                res.heur_improved, res.incumbent_heur == 1 ? " (the final incumbent is one of them)" : "");
   if (verbose && params.rc_fix > 0)
     std::printf("Reduced-cost tightening: %lld nodes, %lld columns fixed, %lld tightened\n", res.rc_calls, res.rc_fixed, res.rc_tightened);
   if (verbose && params.prop > 0)
     std::printf("Bound propagation: %lld handles, %lld columns fixed, %lld tightened, %lld handles proved infeasible\n", res.prop_calls,
                 res.prop_fixed, res.prop_tightened, res.prop_infeasible);
+  if (verbose && params.dive > 0)
+    std::printf("Diving: %lld nodes, %lld with a feasible point, %lld improved the incumbent, %lld child LPs, %lld pivots%s\n", res.dive_calls,
+                res.dive_found, res.dive_improved, res.dive_lps, res.dive_pivots,
+                res.incumbent_heur == 2 ? " (the final incumbent is one of them)" : "");
   const int limit = res.hit_limit || brc != 0;
   mvx_bnb_free_result(&res);
   mvx_delete_prob(prob);

@@ -336,6 +336,28 @@ struct PropArgs {
   int n, m0, ldm, ldn, max_rounds, count;
 };
 
+// one (handle, rule) of a diving pick launch (k_divepick, mvx_dive_pick_many): where the handle's tableau and basis live -- the
+// values are selected the way k_classify selects them -- and the rule (1 fractional, 2 locks, 4 vector length)
+struct DiveNode {
+  const double *T;
+  const int *bvar, *nvar, *nflag;
+  const double *nlb, *nub;
+  int m, ld, rule, pad; // rows of this handle (cut rows included), its row stride
+};
+
+// arguments of k_divepick: `count` (handle, rule) pairs over the model of one root (k_round's copy: objective, RND_INT flags,
+// and per column the rows that lock it down / up and its non-zeros in rows 1..m0)
+struct DiveArgs {
+  const DiveNode *nodes;   // [count]
+  const double *c;         // [n+1] objective
+  const int *flags;        // [n+1] RND_* bits
+  const int *dl, *ul, *len; // [n+1]
+  int *nfrac, *col, *dir;  // [count] candidates, the picked column (0: none), 0 down / 1 up
+  double *val;             // [count] the picked column's value
+  double sg;               // +1 maximise, -1 minimise
+  int n, count;
+};
+
 // k_setbnds (mvx_set_col_bnds_many): per handle a range of bound writes and a range of shifts of column 0
 struct SetbHandle {
   double *T, *blb, *bub, *nlb, *nub;
