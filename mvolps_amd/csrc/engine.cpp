@@ -1577,8 +1577,35 @@ extern "C" void mvx_debug_counters(long long *out, int reset) {
   }
 }
 
+// oracle: NOFEAS_RECHECK / largest_violation -- a NOFEAS verdict whose largest violation is within the rounding an
+// ill-conditioned tableau puts on column 0 counts on a rebuilt tableau only.  A recheck, not a cure: column 0 still drifts
+// on such a basis.  (The oracle's refresh_tableau cannot fail; here a rebuild that cannot get its slab leaves the verdict
+// as it is.)
+constexpr double NOFEAS_RECHECK = 1e-6;
+static double largest_violation(const mvx_prob *P) {
+  refresh_solution(P);
+  double worst = 0.0;
+  for (int i = 1; i <= P->m; i++) {
+    double lb, ub, v = 0.0;
+    var_bounds(P, P->bvar[(size_t)i], &lb, &ub);
+    const double beta = P->beta[(size_t)i];
+    if (lb > -INFINITY && beta < lb) v = (lb - beta) / (1.0 + std::fabs(lb));
+    if (ub < INFINITY && beta > ub) v = (beta - ub) / (1.0 + std::fabs(ub));
+    if (v > worst) worst = v;
+  }
+  return worst;
+}
+
 static int after_solve(mvx_prob *P, const mvx_smcp *parm, int rc, int pivots) {
   P->piv_since_check += pivots;
+  if (rc == 0 && P->status == MVX_NOFEAS && P->it_cnt > 0 && largest_violation(P) <= NOFEAS_RECHECK && refresh_tableau(P)) {
+    g_dbg[0]++;
+    P->piv_since_check = 0;
+    const int before = P->it_cnt;
+    P->status = MVX_UNDEF;
+    rc = solve_once(P, parm, true); // the pivot limit of the call, if any, applies to this leg afresh
+    P->piv_since_check += P->it_cnt - before;
+  }
   if (rc == 0 && P->status == MVX_OPT && P->piv_since_check >= g_check_every) {
     P->piv_since_check = 0;
     g_dbg[1]++;

@@ -1140,10 +1140,36 @@ void orc_init_smcp(orc_smcp *parm) {
 
 static int simplex_once(orc_prob *P, const orc_smcp *parm);
 
+/* A NOFEAS verdict is a statement about column 0: some basic variable lies outside its bounds and no column can move it
+   back.  On a tableau that has been pivoted, column 0 carries the rounding of those pivots, amplified by the entries of
+   an ill-conditioned basis (general_lp 2049x256: entries of 2e5 after a small pivot put 5e-8 on 300 rows while the row
+   equations A x = x_R still held to 2e-12), and the dual simplex or phase 1 then "proves" infeasible what no vertex
+   has.  Rule, identical in the HIP engine: when a solve ends NOFEAS on a handle that has pivoted and the largest
+   violation max_i viol_i / (1 + |bound_i|) is no more than NOFEAS_RECHECK, the tableau is rebuilt from the model for the
+   same basis (refresh_tableau) and the simplex runs again; what that run says stands (one rebuild per call). */
+#define NOFEAS_RECHECK 1e-6
+static double largest_violation(const orc_prob *P) {
+  double worst = 0.0;
+  for (int i = 1; i <= P->m; i++) {
+    double beta = TT(P, i, 0), lb = P->blb[i], ub = P->bub[i], v = 0.0;
+    if (lb > -INF && beta < lb) v = (lb - beta) / (1.0 + fabs(lb));
+    if (ub < INF && beta > ub) v = (beta - ub) / (1.0 + fabs(ub));
+    if (v > worst) worst = v;
+  }
+  return worst;
+}
+
 int orc_simplex(orc_prob *P, const orc_smcp *parm) {
   int before = P->it_cnt;
   int rc = simplex_once(P, parm);
   P->piv_since_check += P->it_cnt - before;
+  if (rc == 0 && P->status == ORC_NOFEAS && P->it_cnt > 0 && largest_violation(P) <= NOFEAS_RECHECK) {
+    refresh_tableau(P);
+    P->piv_since_check = 0;
+    before = P->it_cnt;
+    rc = simplex_once(P, parm); /* the pivot limit of the call, if any, applies to this leg afresh */
+    P->piv_since_check += P->it_cnt - before;
+  }
   if (rc == 0 && P->status == ORC_OPT && P->piv_since_check >= g_check_every) {
     P->piv_since_check = 0;
     if (row_residual_sample(P, REFRESH_SAMPLE_ROWS) > g_refresh_tol) {

@@ -188,6 +188,7 @@ class Ref:
         self.growth = float(np.abs(Binv).sum(axis=1).max() * max(1.0, np.abs(np.hstack([np.eye(m), model.A])).sum(axis=1).max()))
         if exact is None:
             exact = False
+        self.exact = bool(exact)
         if exact:
             self.T = _exact_solve(B, -N)
         else:
@@ -405,7 +406,13 @@ def farkas(ref, tol_bnd=TOL_BND):
         cands.append(("sum", None, g))
     for kind, p, u in cands:
         cu = u.astype(LD)
-        lo_, hi_, scale = _interval(cu, -(cu @ ref.T), ref)
+        cN = -(cu @ ref.T)
+        if not ref.exact:
+            # off the exact path an entry that is zero comes out as rounding noise of the reference (1e-19 relative to
+            # the growth); times an infinite bound it would void every interval.  Below the reference's own resolution,
+            # which is below the tol_piv the engine's ratio test skips, it is zero.  The exact path keeps every entry.
+            cN = np.where(np.abs(cN.astype(np.float64)) <= np.minimum(ref.tol(0.0), TOL_PIV), LD(0.0), cN)
+        lo_, hi_, scale = _interval(cu, cN, ref)
         margin = RTOL * ref.growth * (1.0 + scale)
         if lo_ > margin or hi_ < -margin:
             return kind, p

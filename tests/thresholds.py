@@ -222,6 +222,16 @@ def persist_plan(m, n, cus):
     return cpw, nw, lds
 
 
+def update_tile_rows(m_grid, n, slots=1):
+    """kernels.hip launch_update: rows per tile of k_update for a grid of m_grid rows (m, or m + 1 in phase 1, whose cost
+    row is tableau row m + 1) -- 16 while the launch keeps 2048 workgroups, else 8, else 4"""
+    tiles = ((n + 2) // 2 + 255) // 256
+    for tr in (16, 8):
+        if (m_grid + tr) // tr * tiles * slots >= 2048:
+            return tr
+    return 4
+
+
 PERSIST_LIMITS = {"widest-strips": 700, "strips-too-wide": 700}  # pivot limits: these two stall for 10^5 pivots and more
 
 
