@@ -192,7 +192,7 @@ int mvx_round_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, i
    arguments (different column counts or kinds); -2 device out of memory; -3 a handle whose status is not MVX_OPT. */
 int mvx_rc_tighten_many(const mvx_prob *const *Ps, int count, const double *cutoff, double tol, int *cnt, int *cols, double *lb,
                         double *ub);
-/* Bound lists of many handles applied with one device launch (k_tighten): handle t takes the entries off[t] .. off[t+1]-1
+/* Bound lists of many handles applied with one device launch (k_setbnds): handle t takes the entries off[t] .. off[t+1]-1
    (columns strictly ascending within a handle, finite bounds, lb <= ub).  Afterwards each handle is in the state
    mvx_set_col_bnds(P, col, lb == ub ? MVX_FX : MVX_DB, lb, ub) per entry would leave.  Only for edits that leave a non-basic
    column's resting value where it is: returns -4, nothing changed, when a listed column is basic in its handle or the edit

@@ -10,7 +10,7 @@ LIB = os.path.join(LIBDIR, "libmvolps_amd.so")
 RCCL_LIB = os.path.join(LIBDIR, "libmvolps_rccl.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-SOURCES = ["kernels.hip", "engine.cpp", "capi.cpp", "bnb.cpp", "bnb_dist.cpp", "io.cpp"]
+SOURCES = ["kernels.hip", "node_kernels.hip", "engine.cpp", "capi.cpp", "bnb.cpp", "bnb_dist.cpp", "io.cpp"]
 BINDIR = os.path.join(HERE, "bin")
 CLI = os.path.join(BINDIR, "mvolps")
 # -ffp-contract=off: fma() only where written, on host and device alike (bit-exact parity

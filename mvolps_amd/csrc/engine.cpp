@@ -63,55 +63,6 @@ namespace mvx {
     }                                                                                          \
   } while (0)
 
-// kernel launch wrappers (kernels.hip)
-void set_tuning(int tr, int hot, int nt);
-int fused_npb(int n);
-int fused_nrb_max(int m);
-int chain_ncb(int n);
-int chain_nrb(int m);
-void launch_pboot(const ChainArgs &, hipStream_t);
-void launch_pstep(const ChainArgs &, int g, hipStream_t);
-void launch_pc(const ChainArgs &, int g, hipStream_t);
-void launch_fbc3(const ChainArgs &, int steps, hipStream_t);
-void launch_fpatch(const ChainArgs &, int steps, hipStream_t);
-int launch_chain(const ChainArgs &, hipStream_t);
-int chain_cluster_nw(int m, int n);
-int chain_cluster_kmax(int m, int n);
-void launch_dboot(Ctl *, int n, hipStream_t);
-void launch_da(Ctl *, int n, hipStream_t);
-void launch_db(Ctl *, int m, int n, hipStream_t);
-void launch_select(Ctl *, hipStream_t, int slots = 1);
-int launch_dsel(Ctl *, int m, int n, hipStream_t, int slots = 1);
-void launch_select_queue(Ctl *, const BatchQueue &q, hipStream_t, int slots);
-void launch_update(Ctl *, int m, int n, hipStream_t, int slots = 1, int chained = 0, int busy_slots = 0);
-void launch_p1_head(Ctl *, hipStream_t);
-void launch_p1_select(Ctl *, hipStream_t);
-void launch_p1_fix(Ctl *, int n, hipStream_t);
-void launch_scatter_ctl(Ctl *dst, const Ctl *src, const int *idx, int count, hipStream_t);
-void launch_copy_many(const CopyBatch &b, hipStream_t);
-void launch_gmi(const GmiArgs &a, hipStream_t);
-void launch_classify(const ClsArgs &a, hipStream_t);
-void launch_penalty(const PenArgs &a, hipStream_t);
-void launch_round(const RndArgs &a, hipStream_t);
-void launch_rcfix(const RcArgs &a, hipStream_t);
-void launch_tighten(const TightHandle *hs, const TightEntry *es, int count, hipStream_t);
-void launch_prop(const PropArgs &a, hipStream_t);
-void launch_divepick(const DiveArgs &a, hipStream_t);
-void launch_setbnds(const SetbHandle *hs, const SetbEntry *es, const SetbShift *ss, int handles, hipStream_t);
-void launch_refresh_select(Ctl *, const int *tflag, int var, hipStream_t);
-size_t persist_lds_bytes(int m, int cpw);
-int persist_max_cpw();
-int persist_slot_words(int m_cap);
-int launch_persist(Ctl *, unsigned long long *head, unsigned long long *slot, int *abort_flag, unsigned long long *dbg, int m, int cpw, int nw,
-                   int slot_stride, int max_steps, int head_stride, hipStream_t);
-void launch_rowcomb(Ctl *, int m, int n, int respect_done, hipStream_t);
-void launch_shift_nonbasic(double *T, int ld, int m, int jj, double delta, hipStream_t);
-void launch_set_basic_bounds(double *blb, double *bub, int i, double lb, double ub, hipStream_t);
-void launch_set_nonbasic(double *nlb, double *nub, int *nflag, int j, double lb, double ub, int flag, hipStream_t);
-void launch_add_rows(double *T, int ld, int n, int *bvar, double *blb, double *bub, int *nvar, int first, int nrs, int m_new,
-                     hipStream_t);
-void launch_export(Ctl *, unsigned char *stage, int m, int n, int force, hipStream_t, int slots = 1, size_t slot_stride = 0);
-
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // lays pieces out one after the other on 256-byte boundaries: carve(bytes) is the piece's offset, `off` the total so far
@@ -200,10 +151,11 @@ struct SlabCache {
   size_t idle_bytes = 0; // bytes held by idle slabs, arena slabs included
 };
 
-// The one device buffer + pinned host buffer of the batched node entries (GMI cuts, classification, penalties, rounding,
-// rc-tightening, tighten): descriptors go up through `host`, results come back into it -- written there by the kernel
-// itself through `host_dev`, the pinned buffer's device address (null when it has none), or by a copy out of `dev`.
-// Sharing rule: the pointers are valid from node_scratch_reserve until the entry's closing stream synchronise, under
+// The one device buffer + pinned host buffer of the batched node entries -- GMI cuts, classification, penalties, rounding,
+// the diving pick, rc-tightening, propagation and the two bound-list entries (tighten, set bounds), all through NodeCall:
+// descriptors go up through `host`, results come back into it -- written there by the kernel itself through `host_dev`, the
+// pinned buffer's device address (null when it has none), or by a copy out of `dev`.
+// Sharing rule: the pointers are valid from NodeCall::reserve until the entry's closing stream synchronise, under
 // main_mu; an entry that holds pointers into it calls no other entry.
 struct NodeScratch {
   void *dev = nullptr, *host = nullptr;
@@ -357,6 +309,77 @@ static void flush_copies(Context &c) {
   }
   c.copies.clear();
 }
+
+// The call frame of a batched node entry: the main lock, the layout of the arena (pieces that go up, then results, then
+// device-only scratch, in that order), the reservation, the one upload, where the kernel writes its results, and the closing
+// copy back + synchronise.  What differs between the entries is said in the constructor's arguments, nowhere else.
+enum class NodeFlush {
+  AtEntry,      // the recorded clones leave first: a clone INTO one of the slabs the entry reads must have landed
+  BeforeUpload, // the bound-list entries: only once there is device work, in front of its upload
+  Never         // propagation: it reads the handles' host bounds only, and its handles are freshly cloned, unsolved
+                // children -- flushing here would split the round's clones over more k_copy_many launches
+};
+enum class NodeResults {
+  Pinned, // the kernel writes into the pinned buffer itself when it has a device address: no copy back
+  Device, // the kernel writes device memory, fetch() copies back
+  None    // nothing comes back: fetch() only synchronises (the pinned side is free for the next call)
+};
+class NodeCall {
+  std::unique_lock<std::recursive_mutex> lock_;
+  Carver carve_;
+  size_t up_end_ = 0, out_end_ = 0;
+  const NodeFlush flush_;
+  const NodeResults where_;
+
+public:
+  Context *c = nullptr;
+  unsigned char *hb = nullptr, *db = nullptr, *ob = nullptr; // pinned side, device side, where the results are written
+  // device = false: the call has no device work (bound lists of handles without a tableau): no context, no lock
+  NodeCall(NodeFlush flush, NodeResults where, bool device = true) : flush_(flush), where_(where) {
+    if (!device) return;
+    c = &ctx();
+    bind_device(*c);
+    lock_ = std::unique_lock<std::recursive_mutex>(c->main_mu);
+    if (flush_ == NodeFlush::AtEntry) flush_copies(*c);
+  }
+  hipStream_t stream() const { return c->main.stream; }
+  size_t up(size_t bytes) { // a piece of the upload
+    const size_t o = carve_(bytes);
+    up_end_ = out_end_ = carve_.off;
+    return o;
+  }
+  size_t out(size_t bytes) { // a piece of the results: needs room on the pinned side too
+    const size_t o = carve_(bytes);
+    out_end_ = carve_.off;
+    return o;
+  }
+  size_t dev(size_t bytes) { return carve_(bytes); } // device-only scratch
+  // false: out of memory, the entry returns -2 (node_scratch_reserve)
+  bool reserve() {
+    if (!node_scratch_reserve(*c, carve_.off, out_end_)) return false;
+    hb = (unsigned char *)c->nodes.host;
+    db = (unsigned char *)c->nodes.dev;
+    ob = where_ == NodeResults::Pinned && c->nodes.host_dev ? c->nodes.host_dev : db;
+    return true;
+  }
+  void upload() {
+    if (flush_ == NodeFlush::BeforeUpload) flush_copies(*c);
+    HIPCHECK(hipMemcpyAsync(db, hb, up_end_, hipMemcpyHostToDevice, stream()));
+  }
+  // queues the copy back of the results in front of offset `end` (default: all of them) when the kernel wrote device memory
+  void copy_back(size_t end = 0) {
+    if (where_ != NodeResults::None && ob == db)
+      HIPCHECK(hipMemcpyAsync(hb + up_end_, db + up_end_, (end ? end : out_end_) - up_end_, hipMemcpyDeviceToHost, stream()));
+  }
+  void sync() { HIPCHECK(hipStreamSynchronize(stream())); }
+  void fetch() { // the results are on the pinned side when this returns
+    copy_back();
+    sync();
+  }
+};
+
+// the common part of a node-entry descriptor
+static NodeRef node_ref(const mvx_prob *P) { return NodeRef{P->d_T, P->d_bvar, P->d_nvar, P->d_nflag, P->d_nlb, P->d_nub, P->m, P->ld}; }
 
 static size_t stage_size(int m_cap, int ld) {
   return align_up(sizeof(Ctl) + (size_t)(m_cap + 1) * 8 + (size_t)ld * 8 + (size_t)(m_cap + 1) * 4 + (size_t)ld * 8, 256);
@@ -2254,11 +2277,7 @@ static bool dev_matrix_current(const mvx_prob *P) {
 // window takes one cut from each of its branching nodes (bs.cpp:249-258 with cut.cpp:20's "last cut only").
 static int gmi_core(mvx_prob *const *Ps, int mode, const int *cols, int count, double *vals, double *rhs, int *ok) {
   if (count < 1) return -1;
-  Context &c = ctx();
-  bind_device(c);
-  MAIN_LOCK(c);
-  flush_copies(c);
-  SolveCtx &sc = c.main;
+  NodeCall f(NodeFlush::AtEntry, NodeResults::Device);
   const int n = Ps[0]->n;
   int mmax = 0;
   for (int t = 0; t < count; t++) {
@@ -2283,19 +2302,18 @@ static int gmi_core(mvx_prob *const *Ps, int mode, const int *cols, int count, d
     if (P->dmat && P->dmat->m0 <= common && dev_matrix_current(P) && (!Dp || P->dmat->m0 > Dp->m0)) Dp = P->dmat;
   }
   if (!Dp) {
-    Dp = build_dev_matrix(c, Ps[0], common);
+    Dp = build_dev_matrix(*f.c, Ps[0], common);
     if (!Dp) return -2;
   }
   for (int t = 0; t < count; t++) Ps[t]->dmat = Dp; // (their children inherit it)
   const DevMatrix &D = *Dp;
   const size_t wld = align_up((size_t)mmax + n + 1, 32), old = align_up((size_t)n + 1, 32);
-  Carver carve;
   // [node descriptors x count][kind i32 x (n+1)] go up; [rhs][ok][out][work] come back (work: the auxiliaries' part only)
-  const size_t o_nodes = carve((size_t)count * sizeof(GmiNode)), o_kind = carve((size_t)(n + 1) * 4), up_bytes = carve.off;
-  const size_t o_rhs = carve((size_t)count * 8), o_ok = carve((size_t)count * 4);
-  const size_t o_out = carve((size_t)count * old * 8), o_work = carve((size_t)count * wld * 8);
-  if (!node_scratch_reserve(c, carve.off, carve.off)) return -2;
-  unsigned char *hb = (unsigned char *)c.nodes.host, *db = (unsigned char *)c.nodes.dev;
+  const size_t o_nodes = f.up((size_t)count * sizeof(GmiNode)), o_kind = f.up((size_t)(n + 1) * 4);
+  const size_t o_rhs = f.out((size_t)count * 8), o_ok = f.out((size_t)count * 4);
+  const size_t o_out = f.out((size_t)count * old * 8), o_work = f.out((size_t)count * wld * 8);
+  if (!f.reserve()) return -2;
+  unsigned char *hb = f.hb, *db = f.db;
   GmiNode *h_nodes = (GmiNode *)(hb + o_nodes);
   int *h_kind = (int *)(hb + o_kind);
   bool own_rows = false;
@@ -2303,25 +2321,23 @@ static int gmi_core(mvx_prob *const *Ps, int mode, const int *cols, int count, d
     const mvx_prob *P = Ps[t];
     const int j = cols[t];
     if (j < 1 || j > n || P->pos[(size_t)P->m + j] <= 0) return -1; // the column must be basic (gmi.cpp:23)
-    GmiNode &nd = h_nodes[t];
-    nd.T = P->d_T; nd.nvar = P->d_nvar; nd.nflag = P->d_nflag; nd.nlb = P->d_nlb; nd.nub = P->d_nub;
-    nd.m = P->m; nd.ld = P->ld; nd.pos = P->pos[(size_t)P->m + j]; nd.pad = 0;
+    h_nodes[t] = GmiNode{node_ref(P), P->pos[(size_t)P->m + j], 0};
     own_rows = own_rows || P->m > D.m0;
   }
   h_kind[0] = 0;
   for (int j = 1; j <= n; j++) h_kind[j] = Ps[0]->kind[(size_t)j];
-  HIPCHECK(hipMemcpyAsync(db, hb, up_bytes, hipMemcpyHostToDevice, sc.stream));
+  f.upload();
   GmiArgs a;
   a.nodes = (const GmiNode *)(db + o_nodes);
   a.kind = (const int *)(db + o_kind);
   a.work = (double *)(db + o_work); a.rhs = (double *)(db + o_rhs); a.ok = (int *)(db + o_ok);
   a.A = mode == 0 ? D.packed : D.plain; a.len = mode == 0 ? D.len : nullptr; a.out = (double *)(db + o_out);
   a.n = n; a.wld = (int)wld; a.lda = D.lda; a.m0 = D.m0; a.old = (int)old; a.count = count; a.mode = mode;
-  launch_gmi(a, sc.stream);
-  HIPCHECK(hipMemcpyAsync(hb + o_rhs, db + o_rhs, o_work - o_rhs, hipMemcpyDeviceToHost, sc.stream)); // rhs, ok, out
+  launch_gmi(a, f.stream());
+  f.copy_back(o_work); // rhs, ok, out
   if (own_rows) // the auxiliaries of the rows appended since: their terms are added below
-    HIPCHECK(hipMemcpy2DAsync(hb + o_work, wld * 8, db + o_work, wld * 8, (size_t)(mmax + 1) * 8, (size_t)count, hipMemcpyDeviceToHost, sc.stream));
-  HIPCHECK(hipStreamSynchronize(sc.stream));
+    HIPCHECK(hipMemcpy2DAsync(hb + o_work, wld * 8, db + o_work, wld * 8, (size_t)(mmax + 1) * 8, (size_t)count, hipMemcpyDeviceToHost, f.stream()));
+  f.sync();
   const double *h_rhs = (const double *)(hb + o_rhs), *h_out = (const double *)(hb + o_out), *h_work = (const double *)(hb + o_work);
   const int *h_ok = (const int *)(hb + o_ok);
   for (int t = 0; t < count; t++) {
@@ -2378,32 +2394,19 @@ int engine_classify_many(const mvx_prob *const *Ps, int count, int quirks, int *
     const mvx_prob *P = Ps[t];
     if (!P->valid || P->n != n || (P != P0 && (P->c != P0->c || P->kind != P0->kind))) return -1;
   }
-  Context &c = ctx();
-  bind_device(c);
-  MAIN_LOCK(c);
-  flush_copies(c); // a clone recorded into one of these slabs lands first
-  SolveCtx &sc = c.main;
-  Carver carve;
+  NodeCall f(NodeFlush::AtEntry, NodeResults::Pinned);
   // up: [descriptors][c][kind]; out: [status][nviol][viol][xviol]; device only: [x scratch]
-  const size_t o_nodes = carve((size_t)count * sizeof(ClsNode)), o_c = carve((size_t)(n + 1) * 8), o_kind = carve((size_t)(n + 1) * 4);
-  const size_t up_bytes = carve.off;
-  const size_t o_st = carve((size_t)count * 4), o_nv = carve((size_t)count * 4), o_viol = carve((size_t)count * cap * 4),
-               o_xv = carve((size_t)count * cap * 8);
-  const size_t host_bytes = carve.off;
-  const size_t o_x = carve((size_t)count * (n + 1) * 8);
-  if (!node_scratch_reserve(c, carve.off, host_bytes)) return -2;
-  unsigned char *hb = (unsigned char *)c.nodes.host, *db = (unsigned char *)c.nodes.dev;
+  const size_t o_nodes = f.up((size_t)count * sizeof(ClsNode)), o_c = f.up((size_t)(n + 1) * 8), o_kind = f.up((size_t)(n + 1) * 4);
+  const size_t o_st = f.out((size_t)count * 4), o_nv = f.out((size_t)count * 4), o_viol = f.out((size_t)count * cap * 4),
+               o_xv = f.out((size_t)count * cap * 8);
+  const size_t o_x = f.dev((size_t)count * (n + 1) * 8);
+  if (!f.reserve()) return -2;
+  unsigned char *hb = f.hb, *db = f.db, *ob = f.ob;
   ClsNode *h_nodes = (ClsNode *)(hb + o_nodes);
-  for (int t = 0; t < count; t++) {
-    const mvx_prob *P = Ps[t];
-    ClsNode &nd = h_nodes[t];
-    nd.T = P->d_T; nd.bvar = P->d_bvar; nd.nvar = P->d_nvar; nd.nflag = P->d_nflag; nd.nlb = P->d_nlb; nd.nub = P->d_nub;
-    nd.m = P->m; nd.ld = P->ld; nd.status = P->status; nd.pad = 0;
-  }
+  for (int t = 0; t < count; t++) h_nodes[t] = ClsNode{node_ref(Ps[t]), Ps[t]->status, 0};
   std::memcpy(hb + o_c, P0->c.data(), (size_t)(n + 1) * 8);
   std::memcpy(hb + o_kind, P0->kind.data(), (size_t)(n + 1) * 4);
-  HIPCHECK(hipMemcpyAsync(db, hb, up_bytes, hipMemcpyHostToDevice, sc.stream));
-  unsigned char *ob = c.nodes.host_dev ? c.nodes.host_dev : db; // where the results go: the pinned buffer itself, or the device one
+  f.upload();
   ClsArgs a;
   a.nodes = (const ClsNode *)(db + o_nodes);
   a.c = (const double *)(db + o_c);
@@ -2411,9 +2414,8 @@ int engine_classify_many(const mvx_prob *const *Ps, int count, int quirks, int *
   a.x = (double *)(db + o_x);
   a.st = (int *)(ob + o_st); a.nv = (int *)(ob + o_nv); a.viol = (int *)(ob + o_viol); a.xv = (double *)(ob + o_xv);
   a.n = n; a.cap = cap; a.quirks = quirks; a.count = count;
-  launch_classify(a, sc.stream);
-  if (!c.nodes.host_dev) HIPCHECK(hipMemcpyAsync(hb + o_st, db + o_st, host_bytes - o_st, hipMemcpyDeviceToHost, sc.stream));
-  HIPCHECK(hipStreamSynchronize(sc.stream));
+  launch_classify(a, f.stream());
+  f.fetch();
   const int *h_st = (const int *)(hb + o_st), *h_nv = (const int *)(hb + o_nv), *h_viol = (const int *)(hb + o_viol);
   const double *h_xv = (const double *)(hb + o_xv);
   int rc = 0;
@@ -2450,39 +2452,26 @@ int engine_penalties_many(const mvx_prob *const *Ps, int count, const int *cols,
     }
   }
   if (total == 0) return 0;
-  Context &c = ctx();
-  bind_device(c);
-  MAIN_LOCK(c);
-  flush_copies(c); // a clone recorded into one of these slabs lands first
-  SolveCtx &sc = c.main;
-  Carver carve;
+  NodeCall f(NodeFlush::AtEntry, NodeResults::Pinned);
   // up: [descriptors]; out: [pen_down][pen_up][arg_down][arg_up]
-  const size_t o_nodes = carve((size_t)total * sizeof(PenNode));
-  const size_t up_bytes = carve.off;
-  const size_t o_pd = carve((size_t)total * 8), o_pu = carve((size_t)total * 8), o_ad = carve((size_t)total * 4),
-               o_au = carve((size_t)total * 4);
-  const size_t host_bytes = carve.off;
-  if (!node_scratch_reserve(c, host_bytes, host_bytes)) return -2;
-  unsigned char *hb = (unsigned char *)c.nodes.host, *db = (unsigned char *)c.nodes.dev;
+  const size_t o_nodes = f.up((size_t)total * sizeof(PenNode));
+  const size_t o_pd = f.out((size_t)total * 8), o_pu = f.out((size_t)total * 8), o_ad = f.out((size_t)total * 4),
+               o_au = f.out((size_t)total * 4);
+  if (!f.reserve()) return -2;
+  unsigned char *hb = f.hb, *db = f.db, *ob = f.ob;
   PenNode *h_nodes = (PenNode *)(hb + o_nodes);
   for (int t = 0; t < count; t++) {
     const mvx_prob *P = Ps[t];
-    for (int k = col_off[t]; k < col_off[t + 1]; k++) {
-      PenNode &nd = h_nodes[k - k0];
-      nd.T = P->d_T; nd.nflag = P->d_nflag;
-      nd.m = P->m; nd.ld = P->ld; nd.row = P->pos[(size_t)(P->m + cols[k])]; nd.n = P->n;
-    }
+    for (int k = col_off[t]; k < col_off[t + 1]; k++) h_nodes[k - k0] = PenNode{node_ref(P), P->pos[(size_t)(P->m + cols[k])], P->n};
   }
-  HIPCHECK(hipMemcpyAsync(db, hb, up_bytes, hipMemcpyHostToDevice, sc.stream));
-  unsigned char *ob = c.nodes.host_dev ? c.nodes.host_dev : db;
+  f.upload();
   PenArgs a;
   a.nodes = (const PenNode *)(db + o_nodes);
   a.pen_down = (double *)(ob + o_pd); a.pen_up = (double *)(ob + o_pu);
   a.arg_down = (int *)(ob + o_ad); a.arg_up = (int *)(ob + o_au);
   a.tol = tol; a.count = total; a.pad = 0;
-  launch_penalty(a, sc.stream);
-  if (!c.nodes.host_dev) HIPCHECK(hipMemcpyAsync(hb + o_pd, db + o_pd, host_bytes - o_pd, hipMemcpyDeviceToHost, sc.stream));
-  HIPCHECK(hipStreamSynchronize(sc.stream));
+  launch_penalty(a, f.stream());
+  f.fetch();
   std::memcpy(pen_down + k0, hb + o_pd, (size_t)total * 8);
   std::memcpy(pen_up + k0, hb + o_pu, (size_t)total * 8);
   std::memcpy(arg_down + k0, hb + o_ad, (size_t)total * 4);
@@ -2490,7 +2479,7 @@ int engine_penalties_many(const mvx_prob *const *Ps, int count, const int *cols,
   return 0;
 }
 
-// ------------------------------------------------------------------ reduced-cost tightening (k_rcfix, k_tighten)
+// ------------------------------------------------------------------ reduced-cost tightening (k_rcfix)
 // Reduced-cost bound tightening of `count` solved handles (mvx_rc_tighten_many): one upload of the descriptors and the
 // kinds, one k_rcfix launch, one copy back; the per-position results are mapped to columns through the nvar mirror and
 // sorted by column.  Return codes: 0; -1 bad arguments (other column counts or kinds); -2 device out of memory; -3 a handle
@@ -2508,38 +2497,29 @@ int engine_rc_tighten_many(const mvx_prob *const *Ps, int count, const double *c
     if (!Ps[t]->valid || Ps[t]->status != MVX_OPT) return -3;
   std::vector<double> z((size_t)count);
   for (int t = 0; t < count; t++) z[(size_t)t] = mvx_get_obj_val(Ps[t]); // the mirror; exports first when it is stale
-  Context &c = ctx();
-  bind_device(c);
-  MAIN_LOCK(c);
-  flush_copies(c); // a clone recorded into one of these slabs lands first
-  SolveCtx &sc = c.main;
-  Carver carve;
+  NodeCall f(NodeFlush::AtEntry, NodeResults::Device);
   // up: [descriptors][kind]; back: [code][val]
-  const size_t o_nodes = carve((size_t)count * sizeof(RcNode)), o_kind = carve((size_t)(n + 1) * 4), up_bytes = carve.off;
-  const size_t o_code = carve((size_t)count * (size_t)(n + 1) * 4), o_val = carve((size_t)count * (size_t)(n + 1) * 8);
-  if (!node_scratch_reserve(c, carve.off, carve.off)) return -2;
-  unsigned char *hb = (unsigned char *)c.nodes.host, *db = (unsigned char *)c.nodes.dev;
+  const size_t o_nodes = f.up((size_t)count * sizeof(RcNode)), o_kind = f.up((size_t)(n + 1) * 4);
+  const size_t o_code = f.out((size_t)count * (size_t)(n + 1) * 4), o_val = f.out((size_t)count * (size_t)(n + 1) * 8);
+  if (!f.reserve()) return -2;
+  unsigned char *hb = f.hb, *db = f.db;
   RcNode *h_nodes = (RcNode *)(hb + o_nodes);
   for (int t = 0; t < count; t++) {
     const mvx_prob *P = Ps[t];
     const double sg = P->dir == MVX_MIN ? -1.0 : 1.0, B = cutoff[t];
     const double gap = sg * z[(size_t)t] - sg * B;
-    RcNode &nd = h_nodes[t];
-    nd.T = P->d_T; nd.nvar = P->d_nvar; nd.nflag = P->d_nflag; nd.nlb = P->d_nlb; nd.nub = P->d_nub;
-    nd.gap2 = gap + 1e-9 * std::max(1.0, std::fabs(B));
-    nd.m = P->m; nd.pad = 0;
+    h_nodes[t] = RcNode{node_ref(P), gap + 1e-9 * std::max(1.0, std::fabs(B))};
   }
   std::memcpy(hb + o_kind, P0->kind.data(), (size_t)(n + 1) * 4);
-  HIPCHECK(hipMemcpyAsync(db, hb, up_bytes, hipMemcpyHostToDevice, sc.stream));
+  f.upload();
   RcArgs a;
   a.nodes = (const RcNode *)(db + o_nodes);
   a.kind = (const int *)(db + o_kind);
   a.code = (int *)(db + o_code);
   a.val = (double *)(db + o_val);
   a.tol = tol; a.n = n; a.count = count;
-  launch_rcfix(a, sc.stream);
-  HIPCHECK(hipMemcpyAsync(hb + o_code, db + o_code, carve.off - o_code, hipMemcpyDeviceToHost, sc.stream));
-  HIPCHECK(hipStreamSynchronize(sc.stream));
+  launch_rcfix(a, f.stream());
+  f.fetch();
   const int *h_code = (const int *)(hb + o_code);
   const double *h_val = (const double *)(hb + o_val);
   std::vector<std::pair<int, int>> hit; // (column, position)
@@ -2559,83 +2539,6 @@ int engine_rc_tighten_many(const mvx_prob *const *Ps, int count, const double *c
       lb[o] = cd[q] == 2 ? vl[q] : P->clb[(size_t)j];
       ub[o] = cd[q] == 1 ? vl[q] : P->cub[(size_t)j];
     }
-  }
-  return 0;
-}
-
-// The bound lists of many handles with one launch (mvx_tighten_cols_many): every entry is checked first (-1 / -4 change
-// nothing), then the host model, the nflag mirror and the status of each handle are edited as mvx_set_col_bnds would,
-// and one k_tighten launch writes every position's bounds and status on the device.
-int engine_tighten_many(mvx_prob *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub) {
-  if (count < 0 || (count > 0 && (!Ps || !off))) return -1;
-  if (count == 0) return 0;
-  if (off[0] < 0) return -1;
-  for (int t = 0; t < count; t++)
-    if (!Ps[t] || off[t + 1] < off[t]) return -1;
-  const int k0 = off[0], total = off[count] - k0;
-  if (total == 0) return 0;
-  if (!cols || !lb || !ub) return -1;
-  for (int t = 0; t < count; t++) {
-    int prev = 0;
-    for (int k = off[t]; k < off[t + 1]; k++) {
-      const int j = cols[k];
-      if (j < 1 || j > Ps[t]->n || j <= prev || !std::isfinite(lb[k]) || !std::isfinite(ub[k]) || lb[k] > ub[k]) return -1;
-      prev = j;
-    }
-  }
-  std::vector<int> flags((size_t)total, MVX_NS);
-  int nent = 0;
-  for (int t = 0; t < count; t++) {
-    const mvx_prob *P = Ps[t];
-    if (!P->valid) continue;
-    for (int k = off[t]; k < off[t + 1]; k++) {
-      const int j = cols[k], pos = P->pos[(size_t)(P->m + j)];
-      if (pos > 0) return -4;
-      const int jj = -pos;
-      const int flag = lb[k] == ub[k] ? MVX_NS : (P->nflag[(size_t)jj] == MVX_NU ? MVX_NU : MVX_NL);
-      if (nb_value(flag, lb[k], ub[k]) != nb_value(P->nflag[(size_t)jj], P->clb[(size_t)j], P->cub[(size_t)j])) return -4;
-      flags[(size_t)(k - k0)] = flag;
-      nent++;
-    }
-  }
-  Context &c = ctx();
-  bind_device(c);
-  MAIN_LOCK(c);
-  SolveCtx &sc = c.main;
-  const size_t o_hs = 0, o_es = align_up((size_t)count * sizeof(TightHandle), 256);
-  const size_t bytes = o_es + (size_t)nent * sizeof(TightEntry);
-  if (nent > 0 && !node_scratch_reserve(c, bytes, bytes)) return -2;
-  TightHandle *h_hs = nent > 0 ? (TightHandle *)((unsigned char *)c.nodes.host + o_hs) : nullptr;
-  TightEntry *h_es = nent > 0 ? (TightEntry *)((unsigned char *)c.nodes.host + o_es) : nullptr;
-  int e = 0;
-  for (int t = 0; t < count; t++) {
-    mvx_prob *P = Ps[t];
-    if (h_hs) h_hs[t] = TightHandle{P->d_nlb, P->d_nub, P->d_nflag};
-    for (int k = off[t]; k < off[t + 1]; k++) {
-      const int j = cols[k];
-      P->ctype[(size_t)j] = lb[k] == ub[k] ? MVX_FX : MVX_DB;
-      P->clb[(size_t)j] = lb[k];
-      P->cub[(size_t)j] = ub[k];
-      if (P->valid) {
-        const int jj = -P->pos[(size_t)(P->m + j)];
-        P->nflag[(size_t)jj] = flags[(size_t)(k - k0)];
-        h_es[e++] = TightEntry{lb[k], ub[k], t, jj, flags[(size_t)(k - k0)], 0};
-      }
-    }
-    if (off[t + 1] > off[t]) {
-      if (P->valid) {
-        P->sol_fresh = false;
-        P->fresh_rows = -1;
-      }
-      P->status = MVX_UNDEF;
-    }
-  }
-  if (nent > 0) {
-    flush_copies(c); // a recorded clone INTO one of these slabs must land before the edits do
-    unsigned char *db = (unsigned char *)c.nodes.dev;
-    HIPCHECK(hipMemcpyAsync(db, c.nodes.host, bytes, hipMemcpyHostToDevice, sc.stream));
-    launch_tighten((const TightHandle *)(db + o_hs), (const TightEntry *)(db + o_es), nent, sc.stream);
-    HIPCHECK(hipStreamSynchronize(sc.stream)); // the pinned side is free for the next call
   }
   return 0;
 }
@@ -2718,31 +2621,18 @@ int engine_round_many(const mvx_prob *root, const mvx_prob *const *Ps, int count
   if (n > RND_NMAX) return -5;
   for (int t = 0; t < count; t++)
     if (!Ps[t]->valid || Ps[t]->status != MVX_OPT) return -3;
-  Context &c = ctx();
-  bind_device(c);
-  MAIN_LOCK(c);
-  flush_copies(c); // a clone recorded into one of these slabs lands first
-  SolveCtx &sc = c.main;
-  const RoundModel *M = round_model(c, root);
+  NodeCall f(NodeFlush::AtEntry, NodeResults::Pinned);
+  const RoundModel *M = round_model(*f.c, root);
   if (!M) return -2;
-  Carver carve;
   // up: [descriptors]; out: [obj][found][x]; device only: [row scratch] when the rows do not fit in LDS
-  const size_t o_nodes = carve((size_t)count * sizeof(RndNode));
-  const size_t up_bytes = carve.off;
-  const size_t o_obj = carve((size_t)count * 8), o_found = carve((size_t)count * 4), o_x = carve((size_t)count * (n + 1) * 8);
-  const size_t host_bytes = carve.off;
-  const size_t o_scr = carve(m0 > RND_NMAX ? (size_t)count * m0 * 8 : 0);
-  if (!node_scratch_reserve(c, carve.off, host_bytes)) return -2;
-  unsigned char *hb = (unsigned char *)c.nodes.host, *db = (unsigned char *)c.nodes.dev;
+  const size_t o_nodes = f.up((size_t)count * sizeof(RndNode));
+  const size_t o_obj = f.out((size_t)count * 8), o_found = f.out((size_t)count * 4), o_x = f.out((size_t)count * (n + 1) * 8);
+  const size_t o_scr = f.dev(m0 > RND_NMAX ? (size_t)count * m0 * 8 : 0);
+  if (!f.reserve()) return -2;
+  unsigned char *hb = f.hb, *db = f.db, *ob = f.ob;
   RndNode *h_nodes = (RndNode *)(hb + o_nodes);
-  for (int t = 0; t < count; t++) {
-    const mvx_prob *P = Ps[t];
-    RndNode &nd = h_nodes[t];
-    nd.T = P->d_T; nd.bvar = P->d_bvar; nd.nvar = P->d_nvar; nd.nflag = P->d_nflag; nd.nlb = P->d_nlb; nd.nub = P->d_nub;
-    nd.m = P->m; nd.ld = P->ld;
-  }
-  HIPCHECK(hipMemcpyAsync(db, hb, up_bytes, hipMemcpyHostToDevice, sc.stream));
-  unsigned char *ob = c.nodes.host_dev ? c.nodes.host_dev : db;
+  for (int t = 0; t < count; t++) h_nodes[t] = node_ref(Ps[t]);
+  f.upload();
   const unsigned char *mb = (const unsigned char *)M->dev;
   RndArgs a;
   a.nodes = (const RndNode *)(db + o_nodes);
@@ -2754,9 +2644,8 @@ int engine_round_many(const mvx_prob *root, const mvx_prob *const *Ps, int count
   a.obj = (double *)(ob + o_obj); a.found = (int *)(ob + o_found); a.x = (double *)(ob + o_x);
   a.sg = root->dir == MVX_MIN ? -1.0 : 1.0;
   a.n = n; a.m0 = m0; a.ldm = M->ldm; a.mode = mode; a.count = count; a.pad = 0;
-  launch_round(a, sc.stream);
-  if (!c.nodes.host_dev) HIPCHECK(hipMemcpyAsync(hb + o_obj, db + o_obj, host_bytes - o_obj, hipMemcpyDeviceToHost, sc.stream));
-  HIPCHECK(hipStreamSynchronize(sc.stream));
+  launch_round(a, f.stream());
+  f.fetch();
   std::memcpy(obj, hb + o_obj, (size_t)count * 8);
   std::memcpy(found, hb + o_found, (size_t)count * 4);
   std::memcpy(x, hb + o_x, (size_t)count * (n + 1) * 8);
@@ -2777,30 +2666,18 @@ int engine_dive_pick_many(const mvx_prob *root, const mvx_prob *const *Ps, int c
   if (n > RND_NMAX) return -5;
   for (int t = 0; t < count; t++)
     if (!Ps[t]->valid || Ps[t]->status != MVX_OPT) return -3;
-  Context &c = ctx();
-  bind_device(c);
-  MAIN_LOCK(c);
-  flush_copies(c); // a clone recorded into one of these slabs lands first
-  SolveCtx &sc = c.main;
-  const RoundModel *M = round_model(c, root);
+  NodeCall f(NodeFlush::AtEntry, NodeResults::Pinned);
+  const RoundModel *M = round_model(*f.c, root);
   if (!M) return -2;
-  Carver carve;
   // up: [descriptors]; out: [nfrac][col][dir][val]
-  const size_t o_nodes = carve((size_t)count * sizeof(DiveNode));
-  const size_t up_bytes = carve.off;
-  const size_t o_nf = carve((size_t)count * 4), o_col = carve((size_t)count * 4), o_dir = carve((size_t)count * 4),
-               o_val = carve((size_t)count * 8);
-  if (!node_scratch_reserve(c, carve.off, carve.off)) return -2;
-  unsigned char *hb = (unsigned char *)c.nodes.host, *db = (unsigned char *)c.nodes.dev;
+  const size_t o_nodes = f.up((size_t)count * sizeof(DiveNode));
+  const size_t o_nf = f.out((size_t)count * 4), o_col = f.out((size_t)count * 4), o_dir = f.out((size_t)count * 4),
+               o_val = f.out((size_t)count * 8);
+  if (!f.reserve()) return -2;
+  unsigned char *hb = f.hb, *db = f.db, *ob = f.ob;
   DiveNode *h_nodes = (DiveNode *)(hb + o_nodes);
-  for (int t = 0; t < count; t++) {
-    const mvx_prob *P = Ps[t];
-    DiveNode &nd = h_nodes[t];
-    nd.T = P->d_T; nd.bvar = P->d_bvar; nd.nvar = P->d_nvar; nd.nflag = P->d_nflag; nd.nlb = P->d_nlb; nd.nub = P->d_nub;
-    nd.m = P->m; nd.ld = P->ld; nd.rule = rules[t]; nd.pad = 0;
-  }
-  HIPCHECK(hipMemcpyAsync(db, hb, up_bytes, hipMemcpyHostToDevice, sc.stream));
-  unsigned char *ob = c.nodes.host_dev ? c.nodes.host_dev : db;
+  for (int t = 0; t < count; t++) h_nodes[t] = DiveNode{node_ref(Ps[t]), rules[t], 0};
+  f.upload();
   const unsigned char *mb = (const unsigned char *)M->dev;
   DiveArgs a;
   a.nodes = (const DiveNode *)(db + o_nodes);
@@ -2810,9 +2687,8 @@ int engine_dive_pick_many(const mvx_prob *root, const mvx_prob *const *Ps, int c
   a.nfrac = (int *)(ob + o_nf); a.col = (int *)(ob + o_col); a.dir = (int *)(ob + o_dir); a.val = (double *)(ob + o_val);
   a.sg = root->dir == MVX_MIN ? -1.0 : 1.0;
   a.n = n; a.count = count;
-  launch_divepick(a, sc.stream);
-  if (!c.nodes.host_dev) HIPCHECK(hipMemcpyAsync(hb + o_nf, db + o_nf, carve.off - o_nf, hipMemcpyDeviceToHost, sc.stream));
-  HIPCHECK(hipStreamSynchronize(sc.stream));
+  launch_divepick(a, f.stream());
+  f.fetch();
   std::memcpy(nfrac, hb + o_nf, (size_t)count * 4);
   std::memcpy(col, hb + o_col, (size_t)count * 4);
   std::memcpy(dir, hb + o_dir, (size_t)count * 4);
@@ -2851,27 +2727,22 @@ int engine_propagate_many(const mvx_prob *root, const mvx_prob *const *Ps, int c
   for (int t = 0; t < count; t++)
     if (!Ps[t] || Ps[t]->n != n) return -1;
   if (n > RND_NMAX) return -5;
-  Context &c = ctx();
-  bind_device(c);
-  MAIN_LOCK(c);
-  SolveCtx &sc = c.main;
-  const RoundModel *M = round_model(c, root);
-  if (!M || !round_model_rows(c, root, root->rmod.get())) return -2;
-  Carver carve;
+  NodeCall f(NodeFlush::Never, NodeResults::Device);
+  const RoundModel *M = round_model(*f.c, root);
+  if (!M || !round_model_rows(*f.c, root, root->rmod.get())) return -2;
   // up: [lb0][ub0]; back: [lb][ub][info]; device only: the row activities when they do not fit in LDS
   const size_t nb = (size_t)count * (size_t)(n + 1) * 8;
-  const size_t o_lb0 = carve(nb), o_ub0 = carve(nb), up_bytes = carve.off;
-  const size_t o_lb = carve(nb), o_ub = carve(nb), o_info = carve((size_t)count * 8);
-  const size_t host_bytes = carve.off;
+  const size_t o_lb0 = f.up(nb), o_ub0 = f.up(nb);
+  const size_t o_lb = f.out(nb), o_ub = f.out(nb), o_info = f.out((size_t)count * 8);
   const bool spill = m0 > RND_NMAX;
-  const size_t o_act = carve(spill ? (size_t)count * 2 * (size_t)m0 * 8 : 0), o_actk = carve(spill ? (size_t)count * (size_t)m0 * 4 : 0);
-  if (!node_scratch_reserve(c, carve.off, host_bytes)) return -2;
-  unsigned char *hb = (unsigned char *)c.nodes.host, *db = (unsigned char *)c.nodes.dev;
+  const size_t o_act = f.dev(spill ? (size_t)count * 2 * (size_t)m0 * 8 : 0), o_actk = f.dev(spill ? (size_t)count * (size_t)m0 * 4 : 0);
+  if (!f.reserve()) return -2;
+  unsigned char *hb = f.hb, *db = f.db;
   for (int t = 0; t < count; t++) {
     std::memcpy(hb + o_lb0 + (size_t)t * (size_t)(n + 1) * 8, Ps[t]->clb.data(), (size_t)(n + 1) * 8);
     std::memcpy(hb + o_ub0 + (size_t)t * (size_t)(n + 1) * 8, Ps[t]->cub.data(), (size_t)(n + 1) * 8);
   }
-  HIPCHECK(hipMemcpyAsync(db, hb, up_bytes, hipMemcpyHostToDevice, sc.stream));
+  f.upload();
   const unsigned char *mb = (const unsigned char *)M->dev;
   PropArgs a;
   a.At = (const double *)mb;
@@ -2883,9 +2754,8 @@ int engine_propagate_many(const mvx_prob *root, const mvx_prob *const *Ps, int c
   a.act = spill ? (double *)(db + o_act) : nullptr;
   a.actk = spill ? (int *)(db + o_actk) : nullptr;
   a.n = n; a.m0 = m0; a.ldm = M->ldm; a.ldn = M->ldn; a.max_rounds = max_rounds; a.count = count;
-  launch_prop(a, sc.stream);
-  HIPCHECK(hipMemcpyAsync(hb + o_lb, db + o_lb, host_bytes - o_lb, hipMemcpyDeviceToHost, sc.stream));
-  HIPCHECK(hipStreamSynchronize(sc.stream));
+  launch_prop(a, f.stream());
+  f.fetch();
   const int *h_info = (const int *)(hb + o_info);
   for (int t = 0; t < count; t++) {
     const double *l0 = Ps[t]->clb.data(), *u0 = Ps[t]->cub.data();
@@ -2906,18 +2776,17 @@ int engine_propagate_many(const mvx_prob *root, const mvx_prob *const *Ps, int c
   return 0;
 }
 
-// General bound lists of many handles with one launch (mvx_set_col_bnds_many).  Every list is checked first (-1 changes
-// nothing).  Then each entry does on the host what mvx_set_col_bnds + engine_apply_bounds do, in list order -- the model, the
-// nflag mirror, the pending edits of basic rows (merged by row; flushed when the ninth arrives), hint_dual, status -- and
-// what they would have launched is collected: bound writes (one per row or position and handle: the last one the ordered
-// launches would have made) and shifts of column 0, which leave as one k_setbnds launch.
-int engine_set_bounds_many(mvx_prob *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub) {
+// ------------------------------------------------------------------ bound lists (k_setbnds)
+// What the two bound-list entries check alike, before anything is edited: 1 go on, 0 nothing to do, -1 a bad list.  `general`
+// (mvx_set_col_bnds_many): infinite bounds are allowed, a handle listed twice is not; else (mvx_tighten_cols_many) the
+// reverse.
+static int check_bound_lists(mvx_prob *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub, bool general) {
   if (count < 0 || (count > 0 && (!Ps || !off))) return -1;
   if (count == 0) return 0;
   if (off[0] < 0) return -1;
   std::unordered_set<const mvx_prob *> seen;
   for (int t = 0; t < count; t++)
-    if (!Ps[t] || off[t + 1] < off[t] || !seen.insert(Ps[t]).second) return -1;
+    if (!Ps[t] || off[t + 1] < off[t] || (general && !seen.insert(Ps[t]).second)) return -1;
   if (off[count] == off[0]) return 0;
   if (!cols || !lb || !ub) return -1;
   const double inf = std::numeric_limits<double>::infinity();
@@ -2925,27 +2794,30 @@ int engine_set_bounds_many(mvx_prob *const *Ps, int count, const int *off, const
     int prev = 0;
     for (int k = off[t]; k < off[t + 1]; k++) {
       const int j = cols[k];
-      if (j < 1 || j > Ps[t]->n || j <= prev || !(lb[k] <= ub[k]) || lb[k] == inf || ub[k] == -inf) return -1;
+      const bool ok = general ? lb[k] <= ub[k] && lb[k] != inf && ub[k] != -inf : std::isfinite(lb[k]) && std::isfinite(ub[k]) && lb[k] <= ub[k];
+      if (j < 1 || j > Ps[t]->n || j <= prev || !ok) return -1;
       prev = j;
     }
   }
+  return 1;
+}
+
+// Checked bound lists of many handles with one launch.  Each entry does on the host what mvx_set_col_bnds + engine_apply_bounds
+// do, in list order -- the model, the nflag mirror, the pending edits of basic rows (merged by row; flushed when the ninth
+// arrives), hint_dual, status -- and what they would have launched is collected: bound writes (one per row or position and
+// handle: the last one the ordered launches would have made) and shifts of column 0, which leave as one k_setbnds launch.
+static int apply_bound_lists(mvx_prob *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub) {
   std::vector<SetbHandle> hs;
   std::vector<SetbEntry> es;
   std::vector<SetbShift> ss;
   bool device = false; // a handle without a tableau is a model edit only, as in mvx_set_col_bnds: no engine call
   for (int t = 0; t < count; t++) device = device || (Ps[t]->valid && off[t + 1] > off[t]);
-  std::unique_lock<std::recursive_mutex> lock;
-  if (device) {
-    Context &c = ctx();
-    bind_device(c);
-    lock = std::unique_lock<std::recursive_mutex>(c.main_mu);
-  }
+  NodeCall f(NodeFlush::BeforeUpload, NodeResults::None, device);
   // laid out for the most the lists can ask for, so that out of memory is known before anything is edited
   const size_t total = (size_t)(off[count] - off[0]);
-  Carver carve;
-  const size_t o_hs = carve((size_t)count * sizeof(SetbHandle)), o_es = carve((total + (size_t)count * MAX_EDITS) * sizeof(SetbEntry)),
-               o_ss = carve(total * sizeof(SetbShift));
-  if (device && !node_scratch_reserve(ctx(), carve.off, carve.off)) return -2;
+  const size_t o_hs = f.up((size_t)count * sizeof(SetbHandle)), o_es = f.up((total + (size_t)count * MAX_EDITS) * sizeof(SetbEntry)),
+               o_ss = f.up(total * sizeof(SetbShift));
+  if (device && !f.reserve()) return -2;
   for (int t = 0; t < count; t++) {
     mvx_prob *P = Ps[t];
     if (off[t + 1] == off[t]) continue;
@@ -3009,17 +2881,38 @@ int engine_set_bounds_many(mvx_prob *const *Ps, int count, const int *off, const
     if (h.e1 > h.e0 || h.s1 > h.s0) hs.push_back(h);
   }
   if (hs.empty()) return 0;
-  Context &c = ctx();
-  SolveCtx &sc = c.main;
-  unsigned char *hb = (unsigned char *)c.nodes.host, *db = (unsigned char *)c.nodes.dev;
-  std::memcpy(hb + o_hs, hs.data(), hs.size() * sizeof(SetbHandle));
-  if (!es.empty()) std::memcpy(hb + o_es, es.data(), es.size() * sizeof(SetbEntry));
-  if (!ss.empty()) std::memcpy(hb + o_ss, ss.data(), ss.size() * sizeof(SetbShift));
-  flush_copies(c); // a recorded clone INTO one of these slabs must land before the edits do
-  HIPCHECK(hipMemcpyAsync(db, hb, carve.off, hipMemcpyHostToDevice, sc.stream));
-  launch_setbnds((const SetbHandle *)(db + o_hs), (const SetbEntry *)(db + o_es), (const SetbShift *)(db + o_ss), (int)hs.size(), sc.stream);
-  HIPCHECK(hipStreamSynchronize(sc.stream)); // the pinned side is free for the next call
+  std::memcpy(f.hb + o_hs, hs.data(), hs.size() * sizeof(SetbHandle));
+  if (!es.empty()) std::memcpy(f.hb + o_es, es.data(), es.size() * sizeof(SetbEntry));
+  if (!ss.empty()) std::memcpy(f.hb + o_ss, ss.data(), ss.size() * sizeof(SetbShift));
+  f.upload(); // behind the recorded clones: a clone INTO one of these slabs must land before the edits do
+  launch_setbnds((const SetbHandle *)(f.db + o_hs), (const SetbEntry *)(f.db + o_es), (const SetbShift *)(f.db + o_ss), (int)hs.size(), f.stream());
+  f.fetch();
   return 0;
+}
+
+// General bound lists of many handles (mvx_set_col_bnds_many): -1 changes nothing.
+int engine_set_bounds_many(mvx_prob *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub) {
+  const int rc = check_bound_lists(Ps, count, off, cols, lb, ub, true);
+  return rc <= 0 ? rc : apply_bound_lists(Ps, count, off, cols, lb, ub);
+}
+
+// Bound lists that tighten columns where they rest (mvx_tighten_cols_many): finite bounds on non-basic columns whose resting
+// value stays put -- -1 and -4 change nothing -- so the shared edit queues bound writes only: no pending row edits, no shifts
+// of column 0, the tableau is not touched.  A handle may be listed twice (with disjoint columns).
+int engine_tighten_many(mvx_prob *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub) {
+  const int rc = check_bound_lists(Ps, count, off, cols, lb, ub, false);
+  if (rc <= 0) return rc;
+  for (int t = 0; t < count; t++) {
+    const mvx_prob *P = Ps[t];
+    if (!P->valid) continue;
+    for (int k = off[t]; k < off[t + 1]; k++) {
+      const int j = cols[k], pos = P->pos[(size_t)(P->m + j)];
+      if (pos > 0) return -4;
+      const int flag = lb[k] == ub[k] ? MVX_NS : (P->nflag[(size_t)-pos] == MVX_NU ? MVX_NU : MVX_NL);
+      if (nb_value(flag, lb[k], ub[k]) != nb_value(P->nflag[(size_t)-pos], P->clb[(size_t)j], P->cub[(size_t)j])) return -4;
+    }
+  }
+  return apply_bound_lists(Ps, count, off, cols, lb, ub);
 }
 
 // ------------------------------------------------------------------ pack / unpack (migration)

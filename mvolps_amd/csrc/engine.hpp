@@ -44,7 +44,7 @@ int engine_round_many(const mvx_prob *root, const mvx_prob *const *Ps, int count
 int engine_dive_pick_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, const int *rules, int *nfrac, int *col, int *dir,
                           double *val);
 // reduced-cost bound tightening of `count` solved handles, one launch (k_rcfix), and the bound lists of many handles applied
-// with one launch (k_tighten); see engine.cpp
+// with one launch (k_setbnds, entries on non-basic positions only); see engine.cpp
 int engine_rc_tighten_many(const mvx_prob *const *Ps, int count, const double *cutoff, double tol, int *cnt, int *cols, double *lb,
                            double *ub);
 int engine_tighten_many(mvx_prob *const *Ps, int count, const int *off, const int *cols, const double *lb, const double *ub);

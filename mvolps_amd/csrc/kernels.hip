@@ -19,34 +19,11 @@
 #include <cmath>
 #include <cstdlib>
 
-#include "mvx_internal.hpp"
+#include "kernel_common.hpp"
 
 namespace mvx {
 
-#define TIDX ((int)threadIdx.x)
-
 // MODE 0: larger k1, then smaller idx.   MODE 1: smaller k1, then larger k2, then smaller idx.
-// a / b, correctly rounded.  The fp64 division sequence of gfx950 is almost, not exactly, IEEE: a quotient that lies
-// very close to the midpoint of two doubles can come out one ulp off (-0x1.6666666666663p-1 / -0x1.ffffffffffffbp-1
-// gives ...666p-1, the nearest double is ...667p-1).  Random operands never hit it (scripts/divcheck.py: 0 of 3e8), the
-// near-rational entries of a tableau do: one such quotient parted a 641-node B&B run from the oracle.  The residual a - q*b of a quotient that is
-// within one ulp is exact in one fma, so the better of q and its neighbour on the side the residual points to is
-// the correctly rounded quotient, whatever the native division returned.  The oracle runs the same function
-// (there the native quotient is already the nearest and comes back unchanged).
-__device__ __forceinline__ double xdiv(double a, double b) {
-  const double q = a / b;
-  const double aq = fabs(q);
-  if (!(aq > 1e-290 && aq < 1e290)) return q; // zero, subnormal range, inf, nan
-  const double r = fma(-q, b, a);
-  if (r == 0.0) return q;
-  const bool up = (r > 0.0) == (b > 0.0); // the true quotient lies above q
-  long long bits = __double_as_longlong(q);
-  bits += ((q > 0.0) == up) ? 1 : -1;
-  const double q1 = __longlong_as_double(bits);
-  const double r1 = fma(-q1, b, a);
-  return (fabs(r1) < fabs(r)) ? q1 : q;
-}
-
 template <int MODE>
 __device__ __forceinline__ bool cand_better(const Cand &a, const Cand &b) {
   if (a.idx == 0) return false;
@@ -341,9 +318,6 @@ __device__ Cand dev_dual_ratio(const KC &k, int p, int to_upper, Cand *lds) {
   return block_best<1>(best, lds);
 }
 
-__device__ __forceinline__ double dev_nb_value(int flag, double lb, double ub) {
-  return flag == MVX_NL ? lb : flag == MVX_NU ? ub : flag == MVX_NS ? lb : 0.0;
-}
 __device__ __forceinline__ int dev_leave_flag(double lb, double ub, int to_upper) {
   if (lb == ub) return MVX_NS;
   return to_upper ? MVX_NU : MVX_NL;
@@ -3785,174 +3759,6 @@ __global__ __launch_bounds__(256) void k_persist(PersistArgs a) {
   }
 }
 
-// ======================================================================= GMI cuts on the device
-// generateCut3 (/root/reference/gmi.cpp:11-117) and its repaired variant, for `count` basic integer columns of one
-// solved node at once.  k_gmi_work turns the tableau row of each column into the coefficient vector `work` by
-// variable number (gmi.cpp:41-74): the bug-compatible formula threads a RUNNING right-hand side through the
-// non-basic columns in ascending position order (gmi.cpp:55,73), so one lane walks the row; everything around
-// it (row loads, bound / kind look-ups, the repaired formula's per-column terms) is done by the whole workgroup.
-// k_gmi_backsub is gmi.cpp:81-89: out[col] = work[m+col] + sum over model rows i = 1..m0, in that order, of
-// work[i] * A[i][col] -- multiply and add rounded separately, as the host loop does (-ffp-contract=off).
-// The caller finishes rows m0+1..m (the node's own appended cut rows) on the host, in the same order.
-__device__ __forceinline__ double dev_fract(double x) { // util.cpp:11-23
-  double ip;
-  double f = modf(x, &ip);
-  if (f < 0.0) f += 1;
-  return f;
-}
-__device__ __forceinline__ double api_ub(double ub) { return ub == INFINITY ? 1.79769313486231570815e+308 : ub; }
-__device__ __forceinline__ double api_lb(double lb) { return lb == -INFINITY ? -1.79769313486231570815e+308 : lb; }
-
-constexpr int GMI_CH = 1024; // non-basic positions staged per pass
-
-__global__ __launch_bounds__(256) void k_gmi_work(GmiArgs a) {
-  __shared__ double s_val[GMI_CH], s_aux[GMI_CH];
-  __shared__ int s_var[GMI_CH], s_kind[GMI_CH];
-  __shared__ double s_rhs, s_temp;
-  __shared__ int s_bad;
-  const int c = (int)blockIdx.x;
-  const GmiNode nd = a.nodes[c];
-  const int m = nd.m, n = a.n;
-  const double *row = nd.T + (size_t)nd.pos * nd.ld;
-  double *work = a.work + (size_t)c * a.wld;
-  for (int v = TIDX; v <= m + n; v += 256) work[v] = 0.0;
-  const double beta = row[0];
-  const double f0 = dev_fract(beta);
-  if (TIDX == 0) {
-    s_rhs = a.mode == 0 ? beta : 1.0; // gmi.cpp:37 / the repaired cut's right-hand side starts at 1
-    s_temp = 0.0;                     // `temp` is uninitialised at gmi.cpp:13; 0 here and in the oracle
-    s_bad = 0;
-  }
-  __syncthreads();
-  for (int base = 1; base <= n; base += GMI_CH) {
-    const int cnt = (n - base + 1 < GMI_CH) ? n - base + 1 : GMI_CH;
-    for (int t = TIDX; t < cnt; t += 256) {
-      const int jj = base + t;
-      const double val = row[jj];
-      const int var = nd.nvar[jj];
-      // glp_get_col_kind: an integer column with bounds [0,1] reads as GLP_BV; auxiliaries are continuous
-      int kind = MVX_CV;
-      const double lb = nd.nlb[jj], ub = nd.nub[jj];
-      if (var > m) {
-        kind = a.kind[var - m];
-        if (kind == MVX_IV && lb == 0.0 && ub == 1.0) kind = MVX_BV;
-      }
-      s_val[t] = val;
-      s_var[t] = var;
-      if (a.mode == 0) {
-        s_kind[t] = kind;
-        s_aux[t] = api_ub(ub); // gmi.cpp:47,52
-      } else {
-        // repaired: this column's term of the cut and of its right-hand side
-        const int stat = nd.nflag[jj];
-        int code = 0; // 0 skip, 1 at lower, 2 at upper
-        double g = 0.0, term = 0.0;
-        if (val != 0.0 && stat != MVX_NS) {
-          if (stat == MVX_NF) {
-            code = 3;
-          } else {
-            const double abar = (stat == MVX_NL) ? -val : val;
-            if (kind != MVX_CV) {
-              const double fj = dev_fract(abar);
-              g = (fj <= f0) ? xdiv(fj, f0) : xdiv(1.0 - fj, 1.0 - f0);
-            } else {
-              g = (abar >= 0.0) ? xdiv(abar, f0) : xdiv(-abar, 1.0 - f0);
-            }
-            if (stat == MVX_NL) {
-              code = 1;
-              term = g * api_lb(lb);
-            } else {
-              code = 2;
-              term = -(g * api_ub(ub));
-            }
-          }
-        }
-        s_kind[t] = code;
-        s_aux[t] = term;
-        if (code == 1) work[var] = 0.0 + g;
-        if (code == 2) work[var] = 0.0 - g;
-      }
-    }
-    __syncthreads();
-    if (TIDX == 0) {
-      double rhs = s_rhs;
-      if (a.mode == 0) {
-        double temp = s_temp;
-        for (int t = 0; t < cnt; t++) {
-          const double val = s_val[t];
-          if (val == 0.0) continue; // glp_eval_tab_row returns the non-zeros only
-          const int kind = s_kind[t];
-          const double fRhs = dev_fract(rhs); // the RUNNING rhs (gmi.cpp:55,73)
-          const double fVal = dev_fract(val);
-          if (kind == MVX_IV) temp = (fRhs >= fVal) ? fVal : xdiv(fRhs, 1.0 - fRhs) * (1.0 - fVal);
-          if (kind == MVX_CV) temp = (val >= 0.0) ? val : xdiv(fRhs, 1.0 - fRhs) * (-1.0 * val);
-          work[s_var[t]] = -1.0 * temp; // gmi.cpp:72
-          rhs = rhs - temp * s_aux[t];  // gmi.cpp:73
-        }
-        s_temp = temp;
-      } else {
-        int bad = s_bad;
-        for (int t = 0; t < cnt; t++) {
-          const int code = s_kind[t];
-          if (code == 3) bad = 1;
-          if (code == 1 || code == 2) rhs = rhs + s_aux[t];
-        }
-        s_bad = bad;
-      }
-      s_rhs = rhs;
-    }
-    __syncthreads();
-  }
-  if (TIDX == 0) {
-    a.rhs[c] = s_rhs;
-    a.ok[c] = s_bad ? 0 : 1;
-  }
-}
-
-constexpr int GMI_CT = 4; // cuts per lane in the back-substitution (each loaded matrix entry serves four cuts)
-
-__global__ __launch_bounds__(256) void k_gmi_backsub(GmiArgs a) {
-  __shared__ double s_w[64][GMI_CT];
-  const int col = 1 + (int)blockIdx.x * 256 + TIDX;
-  const int c0 = (int)blockIdx.y * GMI_CT;
-  const bool act = col <= a.n;
-  double acc[GMI_CT];
-#pragma unroll
-  for (int u = 0; u < GMI_CT; u++) acc[u] = (act && c0 + u < a.count) ? a.work[(size_t)(c0 + u) * a.wld + a.nodes[c0 + u].m + col] : 0.0;
-  for (int i0 = 1; i0 <= a.m0; i0 += 64) {
-    __syncthreads();
-    {
-      const int r = TIDX >> 2, u = TIDX & 3; // 64 rows x 4 cuts
-      const int i = i0 + r;
-      s_w[r][u] = (i <= a.m0 && c0 + u < a.count) ? a.work[(size_t)(c0 + u) * a.wld + i] : 0.0;
-    }
-    __syncthreads();
-    const int cnt = (a.m0 - i0 + 1 < 64) ? a.m0 - i0 + 1 : 64;
-    if (act) {
-      for (int r = 0; r < cnt; r++) {
-        const int i = i0 + r;
-        const double av = a.A[(size_t)i * a.lda + col];
-        if (a.mode == 0) {
-          // position `col` of row i's non-zero list (gmi.cpp:87 indexes by position, not by column)
-          if (a.len && col > a.len[i]) continue;
-#pragma unroll
-          for (int u = 0; u < GMI_CT; u++) acc[u] = acc[u] + s_w[r][u] * av;
-        } else {
-          if (av == 0.0) continue;
-#pragma unroll
-          for (int u = 0; u < GMI_CT; u++)
-            if (s_w[r][u] != 0.0) acc[u] = acc[u] + s_w[r][u] * av;
-        }
-      }
-    }
-  }
-  if (act) {
-#pragma unroll
-    for (int u = 0; u < GMI_CT; u++)
-      if (c0 + u < a.count) a.out[(size_t)(c0 + u) * a.old + col] = acc[u];
-  }
-}
-
 // LDS bytes of one k_persist workgroup: the strip, column 0, the pivot column, row bounds (f64) and basic variables (i32)
 size_t persist_lds_bytes(int m, int cpw) { return ((size_t)(m + 1) * (size_t)(cpw + 4)) * 8 + (size_t)(m + 1) * 4 + 64; }
 int persist_max_cpw() { return PERSIST_MAX_CPW; }
@@ -3974,678 +3780,6 @@ int launch_persist(Ctl *d_ctl, unsigned long long *head, unsigned long long *slo
   a.head_stride = head_stride;
   hipLaunchKernelGGL(k_persist, dim3((unsigned)nw), dim3(256), lds, s, a);
   return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-void launch_gmi(const GmiArgs &a, hipStream_t s) {
-  hipLaunchKernelGGL(k_gmi_work, dim3((unsigned)a.count), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(k_gmi_backsub, dim3((unsigned)((a.n + 255) / 256), (unsigned)((a.count + GMI_CT - 1) / GMI_CT)), dim3(256), 0, s, a);
-}
-
-// ---------------------------------------------------------------------------- k_classify
-// printInfo (util.cpp:414-473) of a batch of solved handles, one workgroup per handle (mvx_classify_many).  The value of
-// structural column j is what get_col_prim reads out of the host mirrors: column 0 of its tableau row when it is basic,
-// else the bound its status names (dev_nb_value) -- a selection, no arithmetic, so the bits are those of the host.  The
-// tests are printInfo's: bug-compatible, x != 0, c_j != 0 and trunc(x) != x (util.cpp:437,443); repaired, a distance
-// to the nearest integer above 1e-9; integer columns only.  The violated columns are compacted in ascending order: per
-// chunk of 256 columns a ballot in each wave, the waves' counts through LDS, the running base carried across chunks.
-__global__ __launch_bounds__(256) void k_classify(ClsArgs a) {
-  __shared__ int s_cnt[4];
-  const int t = (int)blockIdx.x;
-  const ClsNode nd = a.nodes[t];
-  const int n = a.n, m = nd.m, cap = a.cap;
-  const int st = nd.status;
-  if (st == MVX_NOFEAS || st == MVX_INFEAS || st == MVX_UNBND) { // util.cpp:423-431
-    if (TIDX == 0) {
-      a.st[t] = -1;
-      a.nv[t] = 0;
-    }
-    return;
-  }
-  double *x = a.x + (size_t)t * (size_t)(n + 1);
-  for (int i = 1 + TIDX; i <= m; i += 256) {
-    const int k = nd.bvar[i];
-    if (k > m && k <= m + n) x[k - m] = nd.T[(size_t)i * (size_t)nd.ld];
-  }
-  for (int q = 1 + TIDX; q <= n; q += 256) {
-    const int k = nd.nvar[q];
-    if (k > m && k <= m + n) x[k - m] = dev_nb_value(nd.nflag[q], nd.nlb[q], nd.nub[q]);
-  }
-  __syncthreads();
-  const int lane = TIDX & 63, wv = TIDX >> 6;
-  int *viol = a.viol + (size_t)t * (size_t)cap;
-  double *xv = a.xv + (size_t)t * (size_t)cap;
-  int base = 0;
-  for (int j0 = 1; j0 <= n; j0 += 256) {
-    const int j = j0 + TIDX;
-    bool bad = false;
-    double v = 0.0;
-    if (j <= n) {
-      v = x[j];
-      const double tr = fabs(v) < 4503599627370496.0 ? (double)(long long)v : v; // bnb.cpp printInfo's trunc_of
-      const bool integer = a.kind[j] != MVX_CV;
-      if (a.quirks) {
-        bad = v != 0 && a.c[j] != 0 && tr != v && integer;
-      } else {
-        const double f = fabs(v - tr);
-        bad = (f < 1.0 - f ? f : 1.0 - f) > 1e-9 && integer;
-      }
-    }
-    const unsigned long long mask = __ballot(bad);
-    if (lane == 0) s_cnt[wv] = __popcll(mask);
-    __syncthreads();
-    int off = base, tot = 0;
-    for (int w = 0; w < 4; w++) {
-      if (w < wv) off += s_cnt[w];
-      tot += s_cnt[w];
-    }
-    if (bad) {
-      const int o = off + __popcll(mask & ((1ull << lane) - 1ull));
-      if (o < cap) {
-        viol[o] = j;
-        xv[o] = v;
-      }
-    }
-    base += tot;
-    __syncthreads(); // s_cnt is written again by the next chunk
-  }
-  if (TIDX == 0) {
-    a.nv[t] = base;
-    a.st[t] = base == 0 ? 1 : 0;
-  }
-}
-
-void launch_classify(const ClsArgs &a, hipStream_t s) {
-  hipLaunchKernelGGL(k_classify, dim3((unsigned)a.count), dim3(256), 0, s, a);
-}
-
-// ---------------------------------------------------------------------------- k_penalty
-// One-step dual penalties of a basic integer column (mvx_branch_penalties_many, DESIGN.md "Branching on the node LP"),
-// one workgroup per (handle, candidate).  Row 0 (reduced costs) and the candidate's row i are streamed once, coalesced;
-// position q is down-eligible when its variable may move in a direction s that lowers x_j (s * T[i][q] < 0), up-eligible
-// when one raises it, and |T[i][q]| > tol; r_q = |T[0][q]| / |T[i][q]| (a true division, xdiv).  Each thread keeps the running
-// (r, q) minimum of each side over its strided positions -- q ascending, strict compare, so the lowest q wins a tie -- the
-// waves reduce with shuffles, four partials meet in LDS.  min is exact: the result has the host twin's bits.
-struct PenMin {
-  double r;
-  int q;
-};
-__device__ __forceinline__ PenMin pen_min(PenMin a, PenMin b) { // smaller r; equal r: smaller q (q = INT_MAX: none)
-  return (b.r < a.r || (b.r == a.r && b.q < a.q)) ? b : a;
-}
-__device__ __forceinline__ PenMin pen_wave_min(PenMin v) {
-  for (int off = 32; off > 0; off >>= 1) {
-    PenMin o;
-    o.r = __shfl_xor(v.r, off, 64);
-    o.q = __shfl_xor(v.q, off, 64);
-    v = pen_min(v, o);
-  }
-  return v;
-}
-
-__global__ __launch_bounds__(256) void k_penalty(PenArgs a) {
-  __shared__ double s_r[2][4];
-  __shared__ int s_q[2][4];
-  const int t = (int)blockIdx.x;
-  const PenNode nd = a.nodes[t];
-  const double *r0 = nd.T;
-  const double *ri = nd.T + (size_t)nd.row * (size_t)nd.ld;
-  const double tol = a.tol;
-  const double inf = __builtin_huge_val();
-  PenMin dn = {inf, 0x7fffffff}, up = {inf, 0x7fffffff};
-  for (int q = 1 + TIDX; q <= nd.n; q += 256) {
-    const double e = ri[q];
-    const double d = r0[q];
-    const int f = nd.nflag[q];
-    if (!(fabs(e) > tol)) continue;
-    const bool inc = f == MVX_NL || f == MVX_NF, dec = f == MVX_NU || f == MVX_NF; // allowed directions s = +1 / -1
-    const bool down = (inc && e < 0.0) || (dec && e > 0.0);
-    const bool upw = (inc && e > 0.0) || (dec && e < 0.0);
-    if (!down && !upw) continue;
-    const double r = xdiv(fabs(d), fabs(e)); // the correctly rounded quotient: the host's division
-    if (down && r < dn.r) dn = PenMin{r, q};
-    if (upw && r < up.r) up = PenMin{r, q};
-  }
-  dn = pen_wave_min(dn);
-  up = pen_wave_min(up);
-  const int lane = TIDX & 63, wv = TIDX >> 6;
-  if (lane == 0) {
-    s_r[0][wv] = dn.r; s_q[0][wv] = dn.q;
-    s_r[1][wv] = up.r; s_q[1][wv] = up.q;
-  }
-  __syncthreads();
-  if (TIDX == 0) {
-    PenMin bd = {s_r[0][0], s_q[0][0]}, bu = {s_r[1][0], s_q[1][0]};
-    for (int w = 1; w < 4; w++) {
-      bd = pen_min(bd, PenMin{s_r[0][w], s_q[0][w]});
-      bu = pen_min(bu, PenMin{s_r[1][w], s_q[1][w]});
-    }
-    const double v = ri[0];
-    const double fd = v - floor(v), fu = ceil(v) - v;
-    const bool hd = bd.q != 0x7fffffff, hu = bu.q != 0x7fffffff;
-    a.pen_down[t] = hd ? fd * bd.r : inf;
-    a.pen_up[t] = hu ? fu * bu.r : inf;
-    a.arg_down[t] = hd ? bd.q : 0;
-    a.arg_up[t] = hu ? bu.q : 0;
-  }
-}
-
-void launch_penalty(const PenArgs &a, hipStream_t s) {
-  hipLaunchKernelGGL(k_penalty, dim3((unsigned)a.count), dim3(256), 0, s, a);
-}
-
-// ---------------------------------------------------------------------------- k_round
-// Primal rounding heuristic (mvx_round_many, DESIGN.md "Primal rounding heuristic"), one workgroup per handle.
-//  1. the node LP's column values, selected as k_classify selects them (get_col_prim's bits), into LDS;
-//  2. each integer column rounded (within 1e-9 of an integer: that integer; else away from its locks; else to nearest)
-//     and clipped to the root's integer range; the fill order's key, the value's fractional part;
-//  3. mode 2: the columns sorted into the fill order (fractional part descending, column ascending) by a bitonic sort in LDS;
-//  4. row activities: a row per lane, the columns in ascending order, zero values skipped (they add nothing: a sum started
-//     at +0 never holds -0), products and sums rounded one by one -- the host twin's bits;
-//  5. mode 2 on a feasible point: one column at a time, the largest step every row allows, a minimum over the rows
-//     (correctly rounded quotients, xdiv) by wave shuffles and four partials in LDS; the activities follow the step;
-//  6. the objective: the non-zero products in ascending column order, summed by one wave.
-// The row activities live in the LDS of the sort keys once the order is taken, or in a global slice when m0 > RND_NMAX.
-__device__ __forceinline__ double rnd_tol(double b) { return 1e-9 * fmax(1.0, fabs(b)); } // a row bound's tolerance
-__device__ __forceinline__ bool rnd_before(double ka, int ia, double kb, int ib) {          // fill order
-  return ka > kb || (ka == kb && ia < ib);
-}
-
-__global__ __launch_bounds__(256) void k_round(RndArgs a) {
-  __shared__ double s_x[RND_NMAX + 1];
-  __shared__ double s_key[RND_NMAX]; // fill-order keys; the row activities once the order is taken (m0 <= RND_NMAX)
-  __shared__ int s_idx[RND_NMAX];
-  __shared__ double s_red[2][4];
-  __shared__ int s_bad;
-  const int t = (int)blockIdx.x;
-  const RndNode nd = a.nodes[t];
-  const int n = a.n, m0 = a.m0, m = nd.m;
-  const size_t ldm = (size_t)a.ldm;
-  const double inf = __builtin_huge_val();
-  const int lane = TIDX & 63, wv = TIDX >> 6;
-  if (TIDX == 0) s_bad = 0;
-  for (int i = 1 + TIDX; i <= m; i += 256) {
-    const int k = nd.bvar[i];
-    if (k > m && k <= m + n) s_x[k - m] = nd.T[(size_t)i * (size_t)nd.ld];
-  }
-  for (int q = 1 + TIDX; q <= n; q += 256) {
-    const int k = nd.nvar[q];
-    if (k > m && k <= m + n) s_x[k - m] = dev_nb_value(nd.nflag[q], nd.nlb[q], nd.nub[q]);
-  }
-  __syncthreads();
-  int np = 1;
-  while (np < n) np <<= 1;
-  bool bad = false;
-  for (int j = 1 + TIDX; j <= n; j += 256) {
-    const double v = s_x[j];
-    const int f = a.flags[j];
-    double xr = v, key = -1.0;
-    if (f & RND_INT) {
-      const double r = rint(v);
-      if (fabs(v - r) <= 1e-9) xr = r;
-      else if (!(f & RND_DLOCK)) xr = floor(v);
-      else if (!(f & RND_ULOCK)) xr = ceil(v);
-      else xr = floor(v + 0.5);
-      const double lo = ceil(a.clo[j]), hi = floor(a.chi[j]);
-      if (xr < lo) xr = lo;
-      if (xr > hi) xr = hi;
-      key = v - floor(v);
-    }
-    bad = bad || !(a.clo[j] <= xr && xr <= a.chi[j]);
-    s_x[j] = xr;
-    s_key[j - 1] = key;
-    s_idx[j - 1] = j;
-  }
-  for (int p = n + TIDX; p < np; p += 256) {
-    s_key[p] = -2.0;
-    s_idx[p] = 0x7fffffff;
-  }
-  __syncthreads();
-  if (a.mode == 2) {
-    for (int k2 = 2; k2 <= np; k2 <<= 1)
-      for (int jj = k2 >> 1; jj > 0; jj >>= 1) {
-        for (int i = TIDX; i < np; i += 256) {
-          const int l = i ^ jj;
-          if (l <= i) continue;
-          const double ki = s_key[i], kl = s_key[l];
-          const int ii = s_idx[i], il = s_idx[l];
-          const bool sw = ((i & k2) == 0) ? rnd_before(kl, il, ki, ii) : rnd_before(ki, ii, kl, il);
-          if (sw) {
-            s_key[i] = kl; s_key[l] = ki;
-            s_idx[i] = il; s_idx[l] = ii;
-          }
-        }
-        __syncthreads();
-      }
-  }
-  double *r = m0 <= RND_NMAX ? s_key : a.scratch + (size_t)t * (size_t)m0;
-  for (int i = TIDX; i < m0; i += 256) {
-    double acc = 0.0;
-    for (int j = 1; j <= n; j++) {
-      const double xj = s_x[j];
-      if (xj != 0.0) acc = __dadd_rn(acc, __dmul_rn(a.At[(size_t)j * ldm + i], xj));
-    }
-    r[i] = acc;
-    const double lo = a.rlo[i], hi = a.rhi[i];
-    bad = bad || !(acc >= lo - rnd_tol(lo) && acc <= hi + rnd_tol(hi));
-  }
-  if (bad) s_bad = 1;
-  __syncthreads();
-  if (a.mode == 2 && !s_bad) {
-    // up to RND_RPT * 256 rows: each thread keeps its rows' activities and the column at hand in registers, and loads the
-    // next column of the order while this one is reduced (same values, same operations: only the loads move)
-    const bool regs = m0 <= RND_RPT * 256;
-    double av[RND_RPT], nx[RND_RPT], rr[RND_RPT];
-    auto load_col = [&](int jj, double *dst) {
-#pragma unroll
-      for (int q = 0; q < RND_RPT; q++) {
-        const int i = TIDX + 256 * q;
-        dst[q] = (jj <= n && i < m0) ? a.At[(size_t)jj * ldm + i] : 0.0;
-      }
-    };
-    if (regs) {
-#pragma unroll
-      for (int q = 0; q < RND_RPT; q++) rr[q] = TIDX + 256 * q < m0 ? r[TIDX + 256 * q] : 0.0;
-      load_col(s_idx[0], nx);
-    }
-    int ph = 0; // s_red buffer of the next barrier: it flips at every barrier, not at every column (zero-cost columns have none)
-    for (int k = 0; k < n; k++) {
-      const int j = s_idx[k];
-      if (j > n || !(a.flags[j] & RND_INT)) break; // integer columns come first; then the continuous ones, the padding
-      if (regs) {
-#pragma unroll
-        for (int q = 0; q < RND_RPT; q++) av[q] = nx[q];
-        load_col(k + 1 < n ? s_idx[k + 1] : n + 1, nx);
-      }
-      const double sc = a.sg * a.c[j];
-      if (!(sc != 0.0)) continue; // uniform: every thread skips the column, and its barrier
-      const double d = sc > 0.0 ? 1.0 : -1.0;
-      const double *col = a.At + (size_t)j * ldm;
-      // x_j and its room are read in front of the barrier: thread 0 writes x_j behind it, in this same interval
-      const double xj = s_x[j];
-      const double room = d > 0.0 ? floor(a.chi[j]) - xj : xj - ceil(a.clo[j]);
-      double q = inf;
-      auto limit = [&](double aij, double ri, int i) {
-        const double da = d * aij;
-        if (da > 0.0) {
-          const double hi = a.rhi[i];
-          if (hi < inf) q = fmin(q, xdiv(__dsub_rn(__dadd_rn(hi, rnd_tol(hi)), ri), da));
-        } else if (da < 0.0) {
-          const double lo = a.rlo[i];
-          if (lo > -inf) q = fmin(q, xdiv(__dadd_rn(__dsub_rn(ri, lo), rnd_tol(lo)), -da));
-        }
-      };
-      if (regs) {
-#pragma unroll
-        for (int u = 0; u < RND_RPT; u++)
-          if (TIDX + 256 * u < m0) limit(av[u], rr[u], TIDX + 256 * u);
-      } else {
-        for (int i = TIDX; i < m0; i += 256) limit(col[i], r[i], i);
-      }
-      for (int off = 32; off > 0; off >>= 1) q = fmin(q, __shfl_xor(q, off, 64));
-      // s_red is double-buffered: a wave writes buffer ph only after every wave has passed the barrier that followed the
-      // last reads of ph (the one in between), so one barrier per column suffices
-      if (lane == 0) s_red[ph][wv] = q;
-      __syncthreads();
-      const double qm = fmin(fmin(s_red[ph][0], s_red[ph][1]), fmin(s_red[ph][2], s_red[ph][3]));
-      ph ^= 1;
-      const double tt = fmin(room, floor(qm));
-      if (!(tt > 0.0) || isinf(tt)) continue; // no room, or nothing limits the column
-      const double step = d * tt;
-      if (regs) {
-#pragma unroll
-        for (int u = 0; u < RND_RPT; u++) rr[u] = __dadd_rn(rr[u], __dmul_rn(step, av[u]));
-      } else {
-        for (int i = TIDX; i < m0; i += 256) r[i] = __dadd_rn(r[i], __dmul_rn(step, col[i]));
-      }
-      if (TIDX == 0) s_x[j] = xj + step;
-    }
-    if (regs) {
-#pragma unroll
-      for (int u = 0; u < RND_RPT; u++)
-        if (TIDX + 256 * u < m0) r[TIDX + 256 * u] = rr[u];
-    }
-    __syncthreads();
-    bad = false; // the filled point, checked again
-    for (int j = 1 + TIDX; j <= n; j += 256) bad = bad || !(a.clo[j] <= s_x[j] && s_x[j] <= a.chi[j]);
-    for (int i = TIDX; i < m0; i += 256) {
-      const double lo = a.rlo[i], hi = a.rhi[i];
-      bad = bad || !(r[i] >= lo - rnd_tol(lo) && r[i] <= hi + rnd_tol(hi));
-    }
-    if (bad) s_bad = 2;
-    __syncthreads();
-  }
-  double *xo = a.x + (size_t)t * (size_t)(n + 1);
-  for (int j = 1 + TIDX; j <= n; j += 256) xo[j] = s_x[j];
-  if (wv == 0) {
-    double s = 0.0;
-    for (int j0 = 1; j0 <= n; j0 += 64) {
-      const int j = j0 + lane;
-      const double p = j <= n ? __dmul_rn(a.c[j], s_x[j]) : 0.0;
-      unsigned long long mk = __ballot(p != 0.0);
-      while (mk) {
-        const int b = __builtin_ctzll(mk);
-        mk &= mk - 1ull;
-        s = __dadd_rn(s, __shfl(p, b, 64));
-      }
-    }
-    if (lane == 0) {
-      xo[0] = 0.0;
-      a.obj[t] = __dadd_rn(s, a.c[0]);
-      a.found[t] = s_bad == 0 ? 1 : 0;
-    }
-  }
-}
-
-void launch_round(const RndArgs &a, hipStream_t s) {
-  hipLaunchKernelGGL(k_round, dim3((unsigned)a.count), dim3(256), 0, s, a);
-}
-
-// ---------------------------------------------------------------------------- k_rcfix / k_tighten
-// Reduced-cost bound tightening (mvx_rc_tighten_many, DESIGN.md "Reduced-cost tightening"), one workgroup per handle.  Row 0
-// and the position-indexed nvar / nflag / nlb / nub are streamed once, coalesced; each non-basic position is decided on its
-// own -- no reduction, so nothing depends on an order -- and written exactly once: code 0 (no change), 1 (upper bound
-// becomes val) or 2 (lower bound becomes val).  The host maps positions to columns through its nvar mirror.  The quotient
-// is the correctly rounded one (xdiv): the host twin's bits.
-__global__ __launch_bounds__(256) void k_rcfix(RcArgs a) {
-  const int t = (int)blockIdx.x;
-  const RcNode nd = a.nodes[t];
-  int *code = a.code + (size_t)t * (size_t)(a.n + 1);
-  double *val = a.val + (size_t)t * (size_t)(a.n + 1);
-  const double gap2 = nd.gap2;
-  const bool live = gap2 > 0.0; // a NaN or a cutoff the node cannot beat: no change anywhere
-  for (int q = 1 + TIDX; q <= a.n; q += 256) {
-    int cd = 0;
-    double v = 0.0;
-    const int var = nd.nvar[q];
-    const int j = var - nd.m;
-    if (live && j >= 1 && j <= a.n && a.kind[j] != MVX_CV) {
-      const int f = nd.nflag[q];
-      const double d = fabs(nd.T[q]);
-      if ((f == MVX_NL || f == MVX_NU) && d > a.tol) {
-        const double lb = nd.nlb[q], ub = nd.nub[q];
-        const double at = f == MVX_NL ? lb : ub;
-        if (at == rint(at)) {
-          const double room = __dsub_rn(ceil(xdiv(gap2, d)), 1.0);
-          if (f == MVX_NL) {
-            v = __dadd_rn(at, room);
-            if (v < ub) cd = 1;
-          } else {
-            v = __dsub_rn(at, room);
-            if (v > lb) cd = 2;
-          }
-        }
-      }
-    }
-    code[q] = cd;
-    val[q] = v;
-  }
-}
-
-void launch_rcfix(const RcArgs &a, hipStream_t s) {
-  hipLaunchKernelGGL(k_rcfix, dim3((unsigned)a.count), dim3(256), 0, s, a);
-}
-
-// The bound lists of many handles in one launch (mvx_tighten_cols_many): a thread per (handle, position) entry writes the
-// position's bounds and status.  The host only sends edits that leave the variable's resting value where it is, so column 0
-// and the tableau stay as they are.
-__global__ __launch_bounds__(256) void k_tighten(const TightHandle *hs, const TightEntry *es, int count) {
-  const int k = (int)blockIdx.x * 256 + TIDX;
-  if (k >= count) return;
-  const TightEntry e = es[k];
-  const TightHandle h = hs[e.h];
-  h.nlb[e.q] = e.lb;
-  h.nub[e.q] = e.ub;
-  h.nflag[e.q] = e.flag;
-}
-
-void launch_tighten(const TightHandle *hs, const TightEntry *es, int count, hipStream_t s) {
-  hipLaunchKernelGGL(k_tighten, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, hs, es, count);
-}
-
-// ---------------------------------------------------------------------------- k_prop / k_setbnds
-// Node bound propagation (mvx_propagate_many, DESIGN.md "Node bound propagation"), one workgroup per handle, all rounds in
-// one launch.  A round is two private serial loops with one barrier between them and one behind:
-//  A. rows on lanes: the activities of a row, its non-zeros in ascending column order out of the by-column model (a wave
-//     reads one column of consecutive rows), the bounds broadcast from LDS; terms with an infinite bound are counted;
-//  B. columns on lanes: the candidates of an integer column, its non-zeros out of the by-row model (a wave reads one row of
-//     consecutive columns), the row activities broadcast from LDS (or the handle's global slice when m0 > RND_NMAX).  A
-//     column's new bounds are exact minima / maxima of its candidates and depend on the bounds the round started with only
-//     (a lane reads no other column's bounds here), so they go to LDS in place.
-// Products, sums and quotients are rounded one by one (xdiv): the host twin's bits.  No atomics: the flags are set to 1 by
-// whoever has a reason and read behind a barrier.
-__global__ __launch_bounds__(256) void k_prop(PropArgs a) {
-  __shared__ double s_l[RND_NMAX + 1], s_u[RND_NMAX + 1];
-  __shared__ double s_min[RND_NMAX], s_max[RND_NMAX];
-  __shared__ int s_k[RND_NMAX];
-  __shared__ int s_badrow, s_cross, s_chg[2];
-  const int t = (int)blockIdx.x;
-  const int n = a.n, m0 = a.m0;
-  const size_t ldm = (size_t)a.ldm, ldn = (size_t)a.ldn, base = (size_t)t * (size_t)(n + 1);
-  for (int j = TIDX; j <= n; j += 256) {
-    s_l[j] = a.lb0[base + j];
-    s_u[j] = a.ub0[base + j];
-  }
-  if (TIDX == 0) {
-    s_badrow = 0;
-    s_cross = 0;
-    s_chg[0] = s_chg[1] = 0;
-  }
-  const bool lds = m0 <= RND_NMAX;
-  double *amin = lds ? s_min : a.act + (size_t)t * 2 * (size_t)m0;
-  double *amax = lds ? s_max : amin + m0;
-  int *ak = lds ? s_k : a.actk + (size_t)t * (size_t)m0;
-  __syncthreads();
-  int rounds = 0, infeasible = 0;
-  for (int r = 0; r < a.max_rounds; r++) {
-    rounds = r + 1;
-    if (TIDX == 0) s_chg[r & 1] = 0; // last read two barriers ago; written again behind the next barrier
-    for (int i = TIDX; i < m0; i += 256) {
-      double lmin = 0.0, lmax = 0.0;
-      int kmin = 0, kmax = 0;
-      for (int j = 1; j <= n; j++) {
-        const double v = a.At[(size_t)j * ldm + i];
-        if (v == 0.0) continue;
-        const double l = s_l[j], u = s_u[j];
-        const double bmin = v > 0.0 ? l : u, bmax = v > 0.0 ? u : l;
-        if (isinf(bmin)) kmin++;
-        else lmin = __dadd_rn(lmin, __dmul_rn(v, bmin));
-        if (isinf(bmax)) kmax++;
-        else lmax = __dadd_rn(lmax, __dmul_rn(v, bmax));
-      }
-      amin[i] = lmin;
-      amax[i] = lmax;
-      ak[i] = (kmin > 2 ? 2 : kmin) | ((kmax > 2 ? 2 : kmax) << 2);
-      const double lo = a.rlo[i], hi = a.rhi[i];
-      if ((kmin == 0 && isfinite(hi) && lmin > __dadd_rn(hi, rnd_tol(hi))) || (kmax == 0 && isfinite(lo) && lmax < __dsub_rn(lo, rnd_tol(lo))))
-        s_badrow = 1;
-    }
-    __syncthreads();
-    if (s_badrow) {
-      infeasible = 1;
-      break;
-    }
-    for (int j = 1 + TIDX; j <= n; j += 256) {
-      if (!(a.flags[j] & RND_INT)) continue;
-      const double l = s_l[j], u = s_u[j];
-      double nl = l, nu = u;
-      for (int i = 0; i < m0; i++) {
-        const double v = a.Ar[(size_t)i * ldn + j];
-        if (v == 0.0) continue;
-        const int kk = ak[i], kmin = kk & 3, kmax = kk >> 2;
-        const double lo = a.rlo[i], hi = a.rhi[i];
-        const double bmin = v > 0.0 ? l : u, bmax = v > 0.0 ? u : l;
-        if (isfinite(hi) && (kmin == 0 || (kmin == 1 && isinf(bmin)))) {
-          const double res = kmin == 0 ? __dsub_rn(amin[i], __dmul_rn(v, bmin)) : amin[i];
-          const double q = xdiv(__dsub_rn(hi, res), v);
-          if (isfinite(q)) {
-            if (v > 0.0) {
-              const double c = floor(__dadd_rn(q, rnd_tol(q)));
-              if (c < nu) nu = c;
-            } else {
-              const double c = ceil(__dsub_rn(q, rnd_tol(q)));
-              if (c > nl) nl = c;
-            }
-          }
-        }
-        if (isfinite(lo) && (kmax == 0 || (kmax == 1 && isinf(bmax)))) {
-          const double res = kmax == 0 ? __dsub_rn(amax[i], __dmul_rn(v, bmax)) : amax[i];
-          const double q = xdiv(__dsub_rn(lo, res), v);
-          if (isfinite(q)) {
-            if (v > 0.0) {
-              const double c = ceil(__dsub_rn(q, rnd_tol(q)));
-              if (c > nl) nl = c;
-            } else {
-              const double c = floor(__dadd_rn(q, rnd_tol(q)));
-              if (c < nu) nu = c;
-            }
-          }
-        }
-      }
-      if (nl != l || nu != u) {
-        s_l[j] = nl;
-        s_u[j] = nu;
-        s_chg[r & 1] = 1;
-      }
-      if (nl > nu) s_cross = 1;
-    }
-    __syncthreads();
-    if (s_cross) {
-      infeasible = 1;
-      break;
-    }
-    if (!s_chg[r & 1]) break;
-  }
-  for (int j = TIDX; j <= n; j += 256) {
-    a.lb[base + j] = s_l[j];
-    a.ub[base + j] = s_u[j];
-  }
-  if (TIDX == 0) {
-    a.info[2 * t] = infeasible;
-    a.info[2 * t + 1] = rounds;
-  }
-}
-
-void launch_prop(const PropArgs &a, hipStream_t s) {
-  hipLaunchKernelGGL(k_prop, dim3((unsigned)a.count), dim3(256), 0, s, a);
-}
-
-// General bound lists of many handles in one launch (mvx_set_col_bnds_many), one workgroup per handle with device work: its
-// bound writes (a lane each; the host sends every row / position of a handle at most once), then a lane per tableau row 0..m, cut rows included, applies the
-// handle's shifts of column 0 in list order -- the fma k_shift_nonbasic applies per launch, so the bits are the per-entry
-// path's.  The shifts read columns jj >= 1 and write column 0 only, the writes touch the bound arrays only: no barrier.
-__global__ __launch_bounds__(256) void k_setbnds(const SetbHandle *hs, const SetbEntry *es, const SetbShift *ss) {
-  const SetbHandle h = hs[blockIdx.x];
-  for (int k = h.e0 + TIDX; k < h.e1; k += 256) {
-    const SetbEntry e = es[k];
-    if (e.flag < 0) {
-      h.blb[e.idx] = e.lb;
-      h.bub[e.idx] = e.ub;
-    } else {
-      h.nlb[e.idx] = e.lb;
-      h.nub[e.idx] = e.ub;
-      h.nflag[e.idx] = e.flag;
-    }
-  }
-  if (h.s1 <= h.s0) return;
-  for (int i = TIDX; i <= h.m; i += 256) {
-    double *row = h.T + (size_t)i * (size_t)h.ld;
-    double acc = row[0];
-    for (int k = h.s0; k < h.s1; k++) acc = fma(row[ss[k].jj], ss[k].delta, acc);
-    row[0] = acc;
-  }
-}
-
-void launch_setbnds(const SetbHandle *hs, const SetbEntry *es, const SetbShift *ss, int handles, hipStream_t s) {
-  hipLaunchKernelGGL(k_setbnds, dim3((unsigned)handles), dim3(256), 0, s, hs, es, ss);
-}
-
-// ---------------------------------------------------------------------------- k_divepick
-// The branching pick of a diving rule (mvx_dive_pick_many, DESIGN.md "LP diving heuristic"), one workgroup per (handle,
-// rule).  A lane over the tableau rows takes the basic structural columns' values from column 0, a lane over the non-basic
-// positions the bound the status names (dev_nb_value) -- k_classify's selection, get_col_prim's bits -- and evaluates the
-// column on the spot from the per-column model arrays: integer and more than 1e-9 off an integer makes it a candidate, its
-// key is the rule's.  Each lane keeps the count and the smallest (k1, k2, column) it met; the waves reduce with shuffles,
-// four partials meet in LDS.  The order is strict and total, so the winner does not depend on the reduction tree: the host
-// twin's bits.  No value array, no atomics.
-struct DiveKey {
-  double k1, k2, v; // k1 = +inf, j = INT_MAX: none
-  int j, dir;
-};
-__device__ __forceinline__ bool dive_before(const DiveKey &a, const DiveKey &b) {
-  return a.k1 < b.k1 || (a.k1 == b.k1 && (a.k2 < b.k2 || (a.k2 == b.k2 && a.j < b.j)));
-}
-__device__ __forceinline__ void dive_eval(const DiveArgs &a, int rule, int j, double v, DiveKey &best, int &cnt) {
-  if (!(a.flags[j] & RND_INT)) return;
-  if (!(fabs(v - rint(v)) > 1e-9)) return;
-  const double fd = v - floor(v), fu = ceil(v) - v;
-  const int near = fd <= fu ? 0 : 1;
-  DiveKey k = {0.0, 0.0, v, j, near};
-  if (rule == 1) {
-    k.k1 = fd <= fu ? fd : fu;
-  } else if (rule == 2) {
-    const int dl = a.dl[j], ul = a.ul[j];
-    k.dir = dl < ul ? 0 : ul < dl ? 1 : near;
-    k.k1 = (double)(dl < ul ? dl : ul);
-    k.k2 = k.dir ? fu : fd;
-  } else {
-    const double cj = a.c[j], s = a.sg * cj;
-    k.dir = s > 0.0 ? 0 : s < 0.0 ? 1 : near;
-    k.k1 = xdiv(fabs(cj) * (k.dir ? fu : fd), (double)(a.len[j] + 1)); // the host's division
-  }
-  cnt++;
-  if (dive_before(k, best)) best = k;
-}
-
-__global__ __launch_bounds__(256) void k_divepick(DiveArgs a) {
-  __shared__ double s_k1[4], s_k2[4], s_v[4];
-  __shared__ int s_j[4], s_dir[4], s_cnt[4];
-  const int t = (int)blockIdx.x;
-  const DiveNode nd = a.nodes[t];
-  const int n = a.n, m = nd.m, rule = nd.rule;
-  const double inf = __builtin_huge_val();
-  DiveKey best = {inf, inf, 0.0, 0x7fffffff, 0};
-  int cnt = 0;
-  for (int i = 1 + TIDX; i <= m; i += 256) {
-    const int k = nd.bvar[i];
-    if (k > m && k <= m + n) dive_eval(a, rule, k - m, nd.T[(size_t)i * (size_t)nd.ld], best, cnt);
-  }
-  for (int q = 1 + TIDX; q <= n; q += 256) {
-    const int k = nd.nvar[q];
-    if (k > m && k <= m + n) dive_eval(a, rule, k - m, dev_nb_value(nd.nflag[q], nd.nlb[q], nd.nub[q]), best, cnt);
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    DiveKey o;
-    o.k1 = __shfl_xor(best.k1, off, 64);
-    o.k2 = __shfl_xor(best.k2, off, 64);
-    o.v = __shfl_xor(best.v, off, 64);
-    o.j = __shfl_xor(best.j, off, 64);
-    o.dir = __shfl_xor(best.dir, off, 64);
-    cnt += __shfl_xor(cnt, off, 64);
-    if (dive_before(o, best)) best = o;
-  }
-  const int lane = TIDX & 63, wv = TIDX >> 6;
-  if (lane == 0) {
-    s_k1[wv] = best.k1; s_k2[wv] = best.k2; s_v[wv] = best.v;
-    s_j[wv] = best.j; s_dir[wv] = best.dir; s_cnt[wv] = cnt;
-  }
-  __syncthreads();
-  if (TIDX == 0) {
-    int total = s_cnt[0];
-    for (int w = 1; w < 4; w++) {
-      const DiveKey o = {s_k1[w], s_k2[w], s_v[w], s_j[w], s_dir[w]};
-      total += s_cnt[w];
-      if (dive_before(o, best)) best = o;
-    }
-    const bool any = best.j != 0x7fffffff;
-    a.nfrac[t] = total;
-    a.col[t] = any ? best.j : 0;
-    a.dir[t] = any ? best.dir : 0;
-    a.val[t] = any ? best.v : 0.0;
-  }
-}
-
-void launch_divepick(const DiveArgs &a, hipStream_t s) {
-  hipLaunchKernelGGL(k_divepick, dim3((unsigned)a.count), dim3(256), 0, s, a);
 }
 
 // ------------------------------------------------------------------ launch wrappers

@@ -14,6 +14,8 @@
 #include <string>
 #include <vector>
 
+#include <hip/hip_runtime_api.h>
+
 #include "../../include/mvx.h"
 
 struct DevMatrix;
@@ -200,13 +202,19 @@ struct CopyBatch {
   CopyJob jobs[COPY_BATCH];
 };
 
+// Where a solved handle's tableau and basis live on the device: the common part of every node-entry descriptor (node_ref
+// fills it from the handle; node_col_values in node_kernels.hip walks it)
+struct NodeRef {
+  const double *T; // tableau
+  const int *bvar, *nvar, *nflag;
+  const double *nlb, *nub;
+  int m, ld; // rows of this handle (cut rows included), its row stride
+};
+
 // one cut of a GMI launch: the solved handle it is taken from (a round of a B&B window takes one cut from each of up to
 // 64 node LPs: same columns and same first m0 model rows, their own tableaux, bases and appended cut rows)
-struct GmiNode {
-  const double *T; // tableau
-  const int *nvar, *nflag;
-  const double *nlb, *nub;
-  int m, ld, pos, pad; // rows of this handle, its row stride, the tableau row of the cut's basic column
+struct GmiNode : NodeRef {
+  int pos, pad; // the tableau row of the cut's basic column
 };
 
 // arguments of the GMI cut kernels (k_gmi_work / k_gmi_backsub): `count` cuts, each with its node
@@ -222,12 +230,9 @@ struct GmiArgs {
   int n, wld, lda, m0, old, count, mode; // mode 0 bug-compatible (gmi.cpp:41-89), 1 repaired
 };
 
-// one handle of a classification launch (k_classify, mvx_classify_many): where its basis and tableau live
-struct ClsNode {
-  const double *T;
-  const int *bvar, *nvar, *nflag;
-  const double *nlb, *nub;
-  int m, ld, status, pad; // rows of this handle, its row stride, its solve status (MVX_OPT, MVX_NOFEAS, ...)
+// one handle of a classification launch (k_classify, mvx_classify_many)
+struct ClsNode : NodeRef {
+  int status, pad; // its solve status (MVX_OPT, MVX_NOFEAS, ...)
 };
 
 // arguments of k_classify: `count` handles with the same n columns, objective and column kinds
@@ -242,12 +247,10 @@ struct ClsArgs {
   int n, cap, quirks, count;
 };
 
-// one (handle, candidate) of a penalty launch (k_penalty, mvx_branch_penalties_many): where the handle's tableau and
-// non-basic statuses live, and the tableau row the candidate column is basic in (found by the host from its bvar mirror)
-struct PenNode {
-  const double *T;
-  const int *nflag;
-  int m, ld, row, n; // rows of this handle, its row stride, the candidate's tableau row, the non-basic positions
+// one (handle, candidate) of a penalty launch (k_penalty, mvx_branch_penalties_many): the handle, and the tableau row the
+// candidate column is basic in (found by the host from its bvar mirror)
+struct PenNode : NodeRef {
+  int row, n; // the candidate's tableau row, the non-basic positions
 };
 
 // arguments of k_penalty: `count` (handle, candidate) pairs, one workgroup each
@@ -259,14 +262,8 @@ struct PenArgs {
   int count, pad;
 };
 
-// one handle of a rounding launch (k_round, mvx_round_many): where its tableau and basis live -- the values are selected the
-// way k_classify selects them
-struct RndNode {
-  const double *T;
-  const int *bvar, *nvar, *nflag;
-  const double *nlb, *nub;
-  int m, ld; // rows of this handle (cut rows included), its row stride
-};
+// one handle of a rounding launch (k_round, mvx_round_many)
+using RndNode = NodeRef;
 
 // the tree's model for k_round, uploaded once per root (engine_round_many): rows 1..m0 by column, their bounds, the root's
 // column bounds, the objective and per-column flags (RND_INT integer, RND_DLOCK / RND_ULOCK a row locks it down / up)
@@ -289,14 +286,11 @@ struct RndArgs {
   int n, m0, ldm, mode, count, pad;
 };
 
-// one handle of a reduced-cost tightening launch (k_rcfix, mvx_rc_tighten_many): row 0 of its tableau and its non-basic
-// arrays; gap2 = sg*z - sg*cutoff plus the slack, computed by the host from the handle's objective mirror
-struct RcNode {
-  const double *T; // row 0: reduced costs by non-basic position
-  const int *nvar, *nflag;
-  const double *nlb, *nub;
+// one handle of a reduced-cost tightening launch (k_rcfix, mvx_rc_tighten_many): it reads row 0 of the tableau (reduced costs
+// by non-basic position; position q holds structural column nvar[q] - m) and the non-basic arrays; gap2 = sg*z - sg*cutoff
+// plus the slack, computed by the host from the handle's objective mirror
+struct RcNode : NodeRef {
   double gap2;
-  int m, pad; // rows of this handle: position q holds structural column nvar[q] - m
 };
 
 // arguments of k_rcfix: `count` handles with the same n columns and kinds.  Results by non-basic position (every position
@@ -308,16 +302,6 @@ struct RcArgs {
   double *val;         // [count][n+1]
   double tol;
   int n, count;
-};
-
-// one bound edit of a k_tighten launch (mvx_tighten_cols_many): non-basic position q of handle h takes (lb, ub, flag)
-struct TightHandle {
-  double *nlb, *nub;
-  int *nflag;
-};
-struct TightEntry {
-  double lb, ub;
-  int h, q, flag, pad;
 };
 
 // arguments of k_prop (mvx_propagate_many): `count` handles over the model of one root -- its rows by column (At, k_round's
@@ -336,13 +320,10 @@ struct PropArgs {
   int n, m0, ldm, ldn, max_rounds, count;
 };
 
-// one (handle, rule) of a diving pick launch (k_divepick, mvx_dive_pick_many): where the handle's tableau and basis live -- the
-// values are selected the way k_classify selects them -- and the rule (1 fractional, 2 locks, 4 vector length)
-struct DiveNode {
-  const double *T;
-  const int *bvar, *nvar, *nflag;
-  const double *nlb, *nub;
-  int m, ld, rule, pad; // rows of this handle (cut rows included), its row stride
+// one (handle, rule) of a diving pick launch (k_divepick, mvx_dive_pick_many): the handle and the rule (1 fractional,
+// 2 locks, 4 vector length)
+struct DiveNode : NodeRef {
+  int rule, pad;
 };
 
 // arguments of k_divepick: `count` (handle, rule) pairs over the model of one root (k_round's copy: objective, RND_INT flags,
@@ -358,7 +339,7 @@ struct DiveArgs {
   int n, count;
 };
 
-// k_setbnds (mvx_set_col_bnds_many): per handle a range of bound writes and a range of shifts of column 0
+// k_setbnds (mvx_set_col_bnds_many, mvx_tighten_cols_many): per handle a range of bound writes and a range of shifts of column 0
 struct SetbHandle {
   double *T, *blb, *bub, *nlb, *nub;
   int *nflag;
@@ -374,6 +355,55 @@ struct SetbShift {
   double delta; // T[i][0] = fma(T[i][jj], delta, T[i][0]) for every row i = 0..m
   int jj, pad;
 };
+
+// Kernel launch wrappers and launch geometry: defined in kernels.hip and node_kernels.hip (the node-entry kernels), called by
+// engine.cpp.  Declared here, where both sides see them, so that a drifted signature does not compile.
+void set_tuning(int tr, int hot, int nt);
+int fused_npb(int n);
+int fused_nrb_max(int m);
+int chain_ncb(int n);
+int chain_nrb(int m);
+void launch_pboot(const ChainArgs &, hipStream_t);
+void launch_pstep(const ChainArgs &, int g, hipStream_t);
+void launch_pc(const ChainArgs &, int g, hipStream_t);
+void launch_fbc3(const ChainArgs &, int steps, hipStream_t);
+void launch_fpatch(const ChainArgs &, int steps, hipStream_t);
+int launch_chain(const ChainArgs &, hipStream_t);
+int chain_cluster_nw(int m, int n);
+int chain_cluster_kmax(int m, int n);
+void launch_dboot(Ctl *, int n, hipStream_t);
+void launch_da(Ctl *, int n, hipStream_t);
+void launch_db(Ctl *, int m, int n, hipStream_t);
+void launch_select(Ctl *, hipStream_t, int slots = 1);
+int launch_dsel(Ctl *, int m, int n, hipStream_t, int slots = 1);
+void launch_select_queue(Ctl *, const BatchQueue &q, hipStream_t, int slots);
+void launch_update(Ctl *, int m, int n, hipStream_t, int slots = 1, int chained = 0, int busy_slots = 0);
+void launch_p1_head(Ctl *, hipStream_t);
+void launch_p1_select(Ctl *, hipStream_t);
+void launch_p1_fix(Ctl *, int n, hipStream_t);
+void launch_scatter_ctl(Ctl *dst, const Ctl *src, const int *idx, int count, hipStream_t);
+void launch_copy_many(const CopyBatch &b, hipStream_t);
+void launch_gmi(const GmiArgs &a, hipStream_t);
+void launch_classify(const ClsArgs &a, hipStream_t);
+void launch_penalty(const PenArgs &a, hipStream_t);
+void launch_round(const RndArgs &a, hipStream_t);
+void launch_rcfix(const RcArgs &a, hipStream_t);
+void launch_prop(const PropArgs &a, hipStream_t);
+void launch_divepick(const DiveArgs &a, hipStream_t);
+void launch_setbnds(const SetbHandle *hs, const SetbEntry *es, const SetbShift *ss, int handles, hipStream_t);
+void launch_refresh_select(Ctl *, const int *tflag, int var, hipStream_t);
+size_t persist_lds_bytes(int m, int cpw);
+int persist_max_cpw();
+int persist_slot_words(int m_cap);
+int launch_persist(Ctl *, unsigned long long *head, unsigned long long *slot, int *abort_flag, unsigned long long *dbg, int m, int cpw, int nw,
+                   int slot_stride, int max_steps, int head_stride, hipStream_t);
+void launch_rowcomb(Ctl *, int m, int n, int respect_done, hipStream_t);
+void launch_shift_nonbasic(double *T, int ld, int m, int jj, double delta, hipStream_t);
+void launch_set_basic_bounds(double *blb, double *bub, int i, double lb, double ub, hipStream_t);
+void launch_set_nonbasic(double *nlb, double *nub, int *nflag, int j, double lb, double ub, int flag, hipStream_t);
+void launch_add_rows(double *T, int ld, int n, int *bvar, double *blb, double *bub, int *nvar, int first, int nrs, int m_new,
+                     hipStream_t);
+void launch_export(Ctl *, unsigned char *stage, int m, int n, int force, hipStream_t, int slots = 1, size_t slot_stride = 0);
 
 // shared immutable matrix row (1-based, n+1 doubles)
 using RowPtr = std::shared_ptr<std::vector<double>>;

@@ -2,12 +2,12 @@
 
   --part window   a 64-node window of the config-5 instance against the cutoff 20: one mvx_rc_tighten_many call (k_rcfix) against
                   the host twin on every node (mvx_bnb_rc_tighten through the engine's table: a tableau export per node), and
-                  one mvx_tighten_cols_many call (k_tighten) for the two children of every node against mvx_set_col_bnds per
+                  one mvx_tighten_cols_many call (k_setbnds) for the two children of every node against mvx_set_col_bnds per
                   entry on clones of the same children.
   --part trees    config 5 closed at heur 2 and at heur 2 + rc_fix (FIFO, window 64), twice each, alternating: nodes, pivots,
                   seconds, counters.
   --part trace    the heur 2 + rc_fix tree alone, then the heur 2 tree alone when --off is given: run under
-                  `rocprofv3 --kernel-trace --stats` for the launch counts of k_rcfix, k_tighten and k_set_nonbasic.
+                  `rocprofv3 --kernel-trace --stats` for the launch counts of k_rcfix, k_setbnds and k_set_nonbasic.
 One JSON object per line on stdout (and appended to --out when given)."""
 import argparse
 import json

@@ -66,7 +66,7 @@ def test_interrupted_solve_reaches_the_same_vertex(gpu):
 def test_headline_lp_bit_exact_to_optimality(gpu, orc):
     """BASELINE config 4 (4096x8192, seed 12345) to optimality on both sides: pivot count, basis and the whole
     268 MB tableau bitwise equal, objective on the HiGHS golden.  (~15 s of oracle time; this is the run in
-    which a device division one ulp off used to show -- see xdiv() in kernels.hip.)"""
+    which a device division one ulp off used to show -- see xdiv() in kernel_common.hpp.)"""
     case = next(g for g in GOLD["dense"] if g["m"] == 4096)
     A, b, c = synth.dense_lp(case["m"], case["n"], case["seed"])
     g, o = gpu.create(), orc.create()

@@ -1,5 +1,6 @@
-"""GPU: the batched node entries (mvx_classify_many, mvx_branch_penalties_many, mvx_round_many, mvx_rc_tighten_many,
-mvx_gmi_cuts_many) share one device + pinned scratch arena.  Called in turn in one process, small batches around full
+"""GPU: the batched node entries (mvx_classify_many, mvx_branch_penalties_many, mvx_round_many, mvx_dive_pick_many,
+mvx_rc_tighten_many, mvx_propagate_many, mvx_gmi_cuts_many, and the two that apply bound lists, mvx_tighten_cols_many and
+mvx_set_col_bnds_many) share one device + pinned scratch arena.  Called in turn in one process, small batches around full
 ones so that the arena grows under different entries, each must give the same bits whatever ran in between.  (What
 each entry computes is checked against its host twin in the entry's own test file.)"""
 import ctypes as C
@@ -8,8 +9,11 @@ import numpy as np
 import pytest
 
 from mvolps_amd import bnb, synth
+from mvolps_amd.capi import DB, FX
 
 from . import lpgen
+from .test_bnb_prop import set_bounds
+from .test_gpu_rcfix import state
 
 pytestmark = pytest.mark.gpu
 
@@ -80,12 +84,64 @@ def test_entries_share_one_arena(gpu):
         ts = cut[:2] if k == 2 else cut
         return gmi_cuts_many(gpu, [nodes[t] for t in ts], [cand[t][0] for t in ts])
 
-    entries = dict(classify=classify, penalties=penalties, rounding=rounding, rcfix=rcfix, cuts=cuts)
-    small = {name: entries[name](2) for name in ("classify", "penalties", "rounding", "rcfix", "cuts")}
+    kids = [S for t in cut for S in bnb.make_children(nodes[t], cand[t][0], quirks=0)][:64]  # unsolved: a pending branching edit
+    assert len(kids) == 64
+    rules = [(1, 2, 4)[t % 3] for t in range(64)]
+
+    def dive(k):
+        rc, out = bnb.dive_pick_many(root, nodes[:k], rules[:k])
+        assert rc == 0
+        return out
+
+    def prop(k):
+        rc, out = bnb.propagate_many(root, kids[:k])
+        assert rc == 0
+        return out
+
+    applied = []  # (clone, twin, list, per-entry edit)
+
+    def tighten_entry(R, e):
+        gpu.set_col_bnds(R.h, e[0], FX if e[1] == e[2] else DB, e[1], e[2])
+
+    def apply(k, res):
+        """The two apply entries on clones of the first k nodes / children, one call each: a node takes its reduced-cost
+        list, a child its parent's and, over it, the bounds propagation found for the child (what a child of the rc_fix +
+        prop driver takes; on this sample propagation finds nothing).  nodes and kids themselves stay untouched."""
+        def kid_list(t):
+            lst = {e[0]: e for e in res["rcfix"][cut[t // 2]]}
+            lst.update((e[0], e) for e in res["prop"][t][2])
+            return [lst[j] for j in sorted(lst)]
+
+        live = [t for t in range(k) if not res["prop"][t][0]]
+        tc, pc = [P.copy() for P in nodes[:k]], [kids[t].copy() for t in live]
+        tl, pl = res["rcfix"][:k], [kid_list(t) for t in live]
+        applied.extend((S, P.copy(), l, tighten_entry) for S, P, l in zip(tc, nodes[:k], tl))
+        applied.extend((S, kids[t].copy(), l, lambda R, e: set_bounds(gpu, R, *e)) for S, t, l in zip(pc, live, pl))
+        assert bnb.tighten_cols_many(tc, tl) == 0
+        assert bnb.set_col_bnds_many(pc, pl) == 0
+        return sum(len(l) for l in tl), sum(len(l) for l in pl)
+
+    entries = dict(classify=classify, penalties=penalties, rounding=rounding, rcfix=rcfix, cuts=cuts, dive=dive, prop=prop)
+    small = {name: entries[name](2) for name in ("classify", "penalties", "rounding", "dive", "rcfix", "prop", "cuts")}
     assert small["rcfix"][0] or small["rcfix"][1]
     assert small["cuts"][2].any() and all(len(p[0]) > 0 for p in small["penalties"])
-    full = {name: entries[name](64) for name in ("penalties", "cuts", "classify", "rcfix", "rounding")}
-    for name in ("rcfix", "rounding", "cuts", "penalties", "classify"):
+    assert all(r[1] > 0 for r in small["dive"])
+    apply(2, small)
+    full = {name: entries[name](64) for name in ("penalties", "cuts", "prop", "classify", "rcfix")}
+    counts = apply(64, full)  # between two full read-only calls
+    print("entries applied to 64 clones: %d tighten, %d set-bounds" % counts)
+    assert counts[0] > 0 and counts[1] > 0
+    full.update({name: entries[name](64) for name in ("rounding", "dive")})
+    for name in ("rcfix", "rounding", "dive", "cuts"):
+        same(entries[name](2), small[name])
+    apply(2, small)
+    for name in ("penalties", "prop", "classify"):
         same(entries[name](2), small[name])
     for name in entries:
         same(head(full[name]), small[name])
+    # the clones against clones edited one entry at a time (mvx_set_col_bnds)
+    for S, R, lst, edit in applied:
+        for e in lst:
+            edit(R, e)
+        assert state(S) == state(R)
+        assert np.array_equal(S.tableau(), R.tableau())

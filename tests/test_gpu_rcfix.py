@@ -1,4 +1,4 @@
-"""GPU: reduced-cost bound tightening on the device (k_rcfix through mvx_rc_tighten_many, k_tighten through
+"""GPU: reduced-cost bound tightening on the device (k_rcfix through mvx_rc_tighten_many, k_setbnds through
 mvx_tighten_cols_many) against the host twins through the engine's own table (mvx_bnb_rc_tighten, mvx_set_col_bnds per entry),
 and rc_fix = 1 trees on the HIP engine against the same driver over the oracle's table."""
 import json
@@ -149,6 +149,37 @@ def test_batched_apply_equals_one_by_one(gpu, case):
     assert len(kids) >= 8
     assert bnb.tighten_cols_many(kids, kid_lists) == 0
     for S, R in zip(kids, twins):
+        assert_same_handles(S, R)
+
+
+def test_one_call_over_empty_short_unsolved_and_fixing_lists(gpu):
+    """One mvx_tighten_cols_many call over four handles: an empty list, a one-entry list, a handle that was loaded and never
+    solved (a model edit only: no device entry) and a list that fixes a column (lb == ub: MVX_NS)."""
+    A, b, c, U = synth.dense_ilp(40, 80, 3, 3)
+    nodes = bnb.node_sample(lpgen.load_ilp(gpu, A, b, c, U), 8)
+    rc, lists = bnb.rc_tighten_many(nodes, spread_cutoffs(nodes, (1.0, 5.0, 20.0)), TOL)
+    assert rc == 0
+    one = next((P, [e]) for P, l in zip(nodes, lists) for e in l)
+    stat = nodes[1].col_stat()
+    j = next(j for j in range(1, nodes[1].n + 1) if stat[j - 1] in (capi.NL, capi.NU)
+             and gpu.get_col_lb(nodes[1].h, j) < gpu.get_col_ub(nodes[1].h, j))
+    at = gpu.get_col_lb(nodes[1].h, j) if stat[j - 1] == capi.NL else gpu.get_col_ub(nodes[1].h, j)
+    cases = [(nodes[0], []), one, (lpgen.load_ilp(gpu, A, b, c, U), [(3, 0.0, 1.0), (7, 2.0, 2.0)]), (nodes[1], [(j, at, at)])]
+    kids, twins = [P.copy() for P, _l in cases], [P.copy() for P, _l in cases]
+    assert bnb.tighten_cols_many(kids, [l for _P, l in cases]) == 0
+    for R, (_P, l) in zip(twins, cases):
+        for (col, lb, ub) in l:
+            gpu.set_col_bnds(R.h, col, FX if lb == ub else DB, lb, ub)
+    assert kids[0].status == OPT and kids[3].col_stat()[j - 1] == capi.NS
+    S, R = kids[2], twins[2]  # no basis, no tableau: the model, then what a solve makes of it
+    cols = range(1, S.n + 1)
+    assert [(gpu.get_col_lb(S.h, q), gpu.get_col_ub(S.h, q), gpu.get_col_type(S.h, q)) for q in cols] == \
+        [(gpu.get_col_lb(R.h, q), gpu.get_col_ub(R.h, q), gpu.get_col_type(R.h, q)) for q in cols]
+    assert (gpu.get_col_lb(S.h, 7), gpu.get_col_ub(S.h, 7), gpu.get_col_type(S.h, 7), S.status) == (2.0, 2.0, FX, R.status)
+    S.simplex()
+    R.simplex()
+    assert (S.status, S.obj, S.it_cnt) == (R.status, R.obj, R.it_cnt) and np.array_equal(S.tableau(), R.tableau())
+    for S, R in ((kids[0], twins[0]), (kids[1], twins[1]), (kids[3], twins[3])):
         assert_same_handles(S, R)
 
 

@@ -1,7 +1,8 @@
 """Instances at the engine's built-in size limits and path thresholds, shared by test_thresholds_inputs.py (CPU: the
 oracle alone proves each instance has the property its GPU test relies on) and test_gpu_thresholds.py (GPU: the engine
-against the oracle, bitwise, on those instances).  The constants restate mvx_internal.hpp / kernels.hip / engine.cpp;
-they decide which side of a threshold an instance is meant to lie on, never what the engine does."""
+against the oracle, bitwise, on those instances).  The constants restate mvx_internal.hpp / kernels.hip /
+node_kernels.hip / engine.cpp; they decide which side of a threshold an instance is meant to lie on, never what the
+engine does."""
 import ctypes as C
 
 import numpy as np
@@ -10,7 +11,7 @@ from mvolps_amd import capi, synth
 
 MIB = 1 << 20
 LD_ALIGN, ROW_SLACK, ROWCOMB_CHUNK, DCH_MAX = 32, 64, 64, 8  # mvx_internal.hpp (a fresh slab has m + ROW_SLACK rows)
-GMI_CH, GMI_CT = 1024, 4  # kernels.hip: non-basic positions per pass of k_gmi_work, cuts per lane of k_gmi_backsub
+GMI_CH, GMI_CT = 1024, 4  # node_kernels.hip: non-basic positions per pass of k_gmi_work, cuts per lane of k_gmi_backsub
 DSEL_MAX = 1024  # k_dsel: one row and one column per lane
 PERSIST_MAX_CPW, PERSIST_LDS_MAX, PERSIST_AREA_MIN, PERSIST_AREA_MAX = 16, 150 * 1024, 32768, 700000
 COPY_KERNEL_MAX, COPY_ONE_PASS, COPY_WHOLE_SPARE = 64 * MIB, 32 * MIB, 1 * MIB  # engine_copy / launch_copy_many
