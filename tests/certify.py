@@ -361,21 +361,21 @@ def unbounded_ray(ref, tol_dj=TOL_DJ, tol_piv=TOL_PIV):
     return None
 
 
-def certify_unbnd(ref, what="", tol_bnd=TOL_BND):
+def certify_unbnd(ref, what="", tol_bnd=TOL_BND, tol_dj=TOL_DJ, tol_piv=TOL_PIV):
     """UNBND: the current point is primal feasible and a ray from it improves the objective without end: A r_S = r_R,
     c r improving, no variable with a finite bound moves towards it."""
     v = primal_violation(ref)
     _check(v <= tol_bnd + RTOL * ref.growth, "%s: UNBND but the point is infeasible by %.3g" % (what, v))
-    found = unbounded_ray(ref)
+    found = unbounded_ray(ref, tol_dj, tol_piv)
     _check(found is not None, "%s: UNBND but no non-basic column of the final basis is an improving unblocked ray" % what)
     k, r = found
     m = ref.model.m
     res = ref.model.A.astype(LD) @ r[m:] - r[:m]
     _check(float(np.abs(res).max(initial=0.0)) <= RTOL * ref.growth * (1.0 + float(np.abs(r).max())), "%s: ray violates A x_S = x_R" % what)
     gain = ref.sgn * float(np.concatenate([np.zeros(m), ref.model.c]).astype(LD) @ r)
-    _check(gain > TOL_DJ, "%s: ray does not improve the objective (%.3g)" % (what, gain))
+    _check(gain > tol_dj, "%s: ray does not improve the objective (%.3g)" % (what, gain))
     rf = r.astype(np.float64)
-    _check(not np.any((rf > TOL_PIV) & np.isfinite(ref.hi)) and not np.any((rf < -TOL_PIV) & np.isfinite(ref.lo)),
+    _check(not np.any((rf > tol_piv) & np.isfinite(ref.hi)) and not np.any((rf < -tol_piv) & np.isfinite(ref.lo)),
            "%s: ray runs into a bound" % what)
     return k
 
@@ -393,7 +393,7 @@ def _interval(coefB, coefN, ref):
     return lower, upper, float(scale)
 
 
-def farkas(ref, tol_bnd=TOL_BND):
+def farkas(ref, tol_bnd=TOL_BND, tol_piv=TOL_PIV):
     """A row combination u of the final basis whose interval over the box excludes 0: ('row', p) for a single out-of-
     bounds row (dual simplex), ('sum', None) for the signs of all infeasible rows (phase 1), or None."""
     xB = ref.xB.astype(np.float64)
@@ -411,7 +411,7 @@ def farkas(ref, tol_bnd=TOL_BND):
             # off the exact path an entry that is zero comes out as rounding noise of the reference (1e-19 relative to
             # the growth); times an infinite bound it would void every interval.  Below the reference's own resolution,
             # which is below the tol_piv the engine's ratio test skips, it is zero.  The exact path keeps every entry.
-            cN = np.where(np.abs(cN.astype(np.float64)) <= np.minimum(ref.tol(0.0), TOL_PIV), LD(0.0), cN)
+            cN = np.where(np.abs(cN.astype(np.float64)) <= np.minimum(ref.tol(0.0), tol_piv), LD(0.0), cN)
         lo_, hi_, scale = _interval(cu, cN, ref)
         margin = RTOL * ref.growth * (1.0 + scale)
         if lo_ > margin or hi_ < -margin:
@@ -419,16 +419,17 @@ def farkas(ref, tol_bnd=TOL_BND):
     return None
 
 
-def certify_nofeas(ref, what=""):
-    _check(primal_violation(ref) > TOL_BND, "%s: NOFEAS but the final basis is primal feasible" % what)
-    found = farkas(ref)
+def certify_nofeas(ref, what="", tol_bnd=TOL_BND, tol_piv=TOL_PIV):
+    _check(primal_violation(ref) > tol_bnd, "%s: NOFEAS but the final basis is primal feasible" % what)
+    found = farkas(ref, tol_bnd, tol_piv)
     _check(found is not None, "%s: NOFEAS but no row combination of the final basis excludes 0 over the bounds" % what)
     return found
 
 
-def certify(model, P, status=None, exact=None, what="", tableau=True):
+def certify(model, P, status=None, exact=None, what="", tableau=True, tol_bnd=TOL_BND, tol_dj=TOL_DJ, tol_piv=TOL_PIV):
     """All checks that apply to a handle's state (P: a handle or a Snapshot); returns the Ref.  status: the handle's
-    unless given."""
+    unless given.  tol_bnd / tol_dj / tol_piv: the tolerances of the call that left the state (the engine's defaults
+    unless given); the OPT, UNBND and NOFEAS certificates hold the state to those."""
     from mvolps_amd.capi import NOFEAS, OPT, UNBND
 
     S = P if isinstance(P, Snapshot) else Snapshot(P, status)
@@ -438,11 +439,11 @@ def certify(model, P, status=None, exact=None, what="", tableau=True):
     certify_values(ref, S, what)
     st = S.status
     if st == OPT:
-        certify_opt(ref, S, what)
+        certify_opt(ref, S, what, tol_bnd=tol_bnd, tol_dj=tol_dj)
     elif st == UNBND:
-        certify_unbnd(ref, what)
+        certify_unbnd(ref, what, tol_bnd=tol_bnd, tol_dj=tol_dj, tol_piv=tol_piv)
     elif st == NOFEAS:
-        certify_nofeas(ref, what)
+        certify_nofeas(ref, what, tol_bnd=tol_bnd, tol_piv=tol_piv)
     return ref
 
 
