@@ -226,6 +226,25 @@ int mvx_set_col_bnds_many(mvx_prob *const *Ps, int count, const int *off, const 
    mvx_round_many, whose model it shares. */
 int mvx_dive_pick_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, const int *rules, int *nfrac, int *col, int *dir,
                        double *val);
+/* The whole objective of `count` handles replaced, one device launch (k_objrow) for all their cost rows: handle t takes
+   c[t*(n+1) + 0 .. n], entry 0 the constant.  The handles have the same n; their row counts may differ (cut rows).  Each is
+   left, bit for bit, as mvx_set_obj_coef(P, j, c[j]) for j = 0..n leaves it: the objective replaced, the status MVX_UNDEF, and
+   where it has a valid tableau row 0 rebuilt (the basis stays, so a solved handle restarts primal feasible); a handle without
+   a tableau only takes its objective.  Pending bound edits stay pending.  Returns 0; -1 bad arguments (a null, count < 0,
+   differing column counts, a handle listed twice); -2 device out of memory, nothing changed. */
+int mvx_set_obj_many(mvx_prob *const *Ps, int count, const double *c);
+/* Feasibility pump (DESIGN.md "Feasibility pump"): the rounding and the distance objective of `count` solved handles, one
+   device launch (k_pumpobj).  Values and bounds are each handle's own, the integer flags and the objective c0 those of `root`
+   (model kept with it, as for mvx_round_many).  xt[t][1..n] the rounding of the integer columns (nearest integer, clamped to
+   the column's integral bounds; 0 for continuous columns); when has_prev[t] is set and it equals xprev[t] on every integer
+   column, the up to 10 movable columns farthest from their LP value are moved one unit towards it.  c[t][0..n] the new
+   objective in the handle's own direction, c_j = a * (-sg * d_j) + (q * sqrt(nnz(d))) * c0_j with (a, q) = ab[2t], ab[2t+1] and
+   d the distance slopes; c[t][0] = 0.  info[4t..] = fractional integer columns, columns moved, stalled (a repeated rounding
+   with nothing to move), nnz(d).  xprev may be NULL when no has_prev is set.  Pure: no handle changes.  Bit-identical to
+   mvx_bnb_pump_obj (mvx_bnb.h).  Returns 0; -1 bad arguments; -2 device out of memory; -3 a handle whose status is not
+   MVX_OPT; -5 n > 4096, as for mvx_round_many, whose model it shares. */
+int mvx_pump_obj_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, const double *xprev, const int *has_prev,
+                      const double *ab, int *info, double *xt, double *c);
 
 /* ---- engine-state access (parity tests, visualisers) --------------------------- */
 int mvx_get_tableau_ld(const mvx_prob *P);

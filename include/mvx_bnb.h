@@ -102,6 +102,17 @@ typedef struct mvx_lp_api {
      rule) pairs in one call (mvx_dive_pick_many), the model taken from `root`; without it, or when it returns -5 (more columns
      than the kernel holds), the driver runs the host twin mvx_bnb_dive_pick */
   int (*dive_pick_many)(const void *root, const void *const *Ps, int count, const int *rules, int *nfrac, int *col, int *dir, double *val);
+  /* optional (may be NULL): glp_set_obj_coef; on a handle with a tableau the cost row follows.  The feasibility pump applies
+     its objectives through it, column by column, where the table has no set_obj_many */
+  void (*set_obj_coef)(void *P, int j, double coef);
+  /* optional (may be NULL): the whole objective of `count` handles replaced in one call (mvx_set_obj_many), handle t taking
+     c[t*(n+1) .. ]; each is left as set_obj_coef per entry leaves it */
+  int (*set_obj_many)(void *const *Ps, int count, const double *c);
+  /* optional (may be NULL): the feasibility pump's rounding and distance objective (DESIGN.md "Feasibility pump") of `count`
+     solved handles in one call (mvx_pump_obj_many), the model taken from `root`; without it, or when it returns -5 (more
+     columns than the kernel holds), the host twin mvx_bnb_pump_obj runs */
+  int (*pump_obj_many)(const void *root, const void *const *Ps, int count, const double *xprev, const int *has_prev, const double *ab,
+                       int *info, double *xt, double *c);
 } mvx_lp_api;
 
 const mvx_lp_api *mvx_hip_lp_api(void);
@@ -157,6 +168,13 @@ typedef struct {
                            point becomes the incumbent.  Needs reference_quirks = 0 and best_window = 0 */
   int dive_freq;        /* 0 (default): the root only; F > 0: also every branching node with oid % F == 0 */
   int dive_depth;       /* step limit of one dive; 0 (default): 4 n + 64, a cap against a dive that never ends */
+  int pump;             /* feasibility pump (DESIGN.md "Feasibility pump"): 0 off (default), 1..1000 the limit of distance LPs of one
+                           pump.  A node that reaches the branch decision with an OPT LP is pumped behind the rounding heuristic
+                           and in front of the dives, on its LP as solved; a better feasible point becomes the incumbent.
+                           Needs reference_quirks = 0 and best_window = 0 */
+  int pump_freq;        /* 0 (default): the root only; F > 0: also every branching node with oid % F == 0 */
+  double pump_alpha;    /* 0 (default) the plain pump; up to 1: the weight of the root's objective in the first distance LP, times
+                           0.9 with every further one */
 } mvx_bnb_params;
 
 /* B&B events at the emit points of bs.cpp (message.h EventType) */
@@ -197,8 +215,8 @@ typedef struct {
   long long heur_calls;    /* heur > 0: nodes the rounding heuristic ran on (the nodes that branched) */
   long long heur_found;    /* ... of which it returned a feasible point */
   long long heur_improved; /* ... of which the point became the incumbent */
-  int incumbent_heur;      /* 1: the final incumbent came from the rounding heuristic, 2: from a dive, 0: from an integral node
-                              LP (or none) */
+  int incumbent_heur;      /* 1: the final incumbent came from the rounding heuristic, 2: from a dive, 3: from a pump, 0: from an
+                              integral node LP (or none) */
   long long rc_calls;      /* rc_fix = 1: branching nodes the reduced-cost tightening ran on */
   long long rc_fixed;      /* ... entries of their lists with lb == ub */
   long long rc_tightened;  /* ... the other entries */
@@ -211,6 +229,11 @@ typedef struct {
   long long dive_improved; /* ... of which the point became the incumbent */
   long long dive_lps;      /* child LPs the dives solved, failed sides included */
   long long dive_pivots;   /* their pivots (not part of total_pivots) */
+  long long pump_calls;    /* pump > 0: nodes pumped */
+  long long pump_found;    /* ... of which the pump returned a feasible point */
+  long long pump_improved; /* ... of which the point became the incumbent */
+  long long pump_lps;      /* distance LPs the pumps solved */
+  long long pump_pivots;   /* their pivots (not part of total_pivots) */
 } mvx_bnb_result;
 
 void mvx_bnb_default_params(mvx_bnb_params *p);
@@ -219,7 +242,7 @@ void mvx_bnb_default_params(mvx_bnb_params *p);
    empty; -2 var_strat >= 3 and the branching penalties could not be computed (the table has neither
    branch_penalties_many nor get_tableau + get_basis, or they failed), or heur > 0 and the heuristic could not run (the
    table has neither round_many nor the accessors of mvx_bnb_round, or they failed) -- *res holds the tree up to that
-   node.  rc_fix, prop and dive have the same two codes; their refusals are listed with their host twins below */
+   node.  rc_fix, prop, dive and pump have the same two codes; their refusals are listed with their host twins below */
 int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *params, mvx_bnb_result *res);
 void mvx_bnb_free_result(mvx_bnb_result *res);
 
@@ -308,6 +331,34 @@ int mvx_bnb_dive_pick(const mvx_lp_api *api, const void *prob, const void *root,
    dive > 0 with reference_quirks = 1 or best_window > 0, and -2, with the tree so far, when a dive could not be carried out */
 int mvx_bnb_dive(const mvx_lp_api *api, const void *prob, const void *root, int rules, int depth, double *obj, int *found, double *x,
                  long long *lps, long long *pivots);
+
+/* Feasibility pump (DESIGN.md "Feasibility pump"), host twin of mvx_pump_obj_many for one solved handle: the rounding of its
+   integer columns (xt[0..n]; the move of a repeated rounding when has_prev is set and it equals xprev[1..n]), and the distance
+   objective c[0..n] with ab = (a, q); info[0..3] = fractional integer columns, columns moved, stalled, nnz(d).  The column
+   bounds are the handle's own, the integer flags and the objective those of `root`.  Works through the table only
+   (get_col_prim_all / get_col_prim, get_mat_row, bounds, get_obj_coef, get_col_kind, get_obj_dir).  Returns 0; -1 bad
+   arguments; -2 the table lacks an accessor it needs; -3 the handle is not MVX_OPT */
+int mvx_bnb_pump_obj(const mvx_lp_api *api, const void *prob, const void *root, const double *xprev, int has_prev, const double *ab,
+                     int *info, double *xt, double *c);
+/* How a pump ended (mvx_bnb_pump's *end): the LP point became integral; `iters` LPs were solved; a repeated rounding had no
+   column to move; a moved rounding repeated an earlier one; a distance LP did not end optimal */
+#define MVX_PUMP_INTEGRAL 1
+#define MVX_PUMP_LIMIT 2
+#define MVX_PUMP_STALLED 3
+#define MVX_PUMP_CYCLE 4
+#define MVX_PUMP_FAILED 5
+/* One whole pump of the solved node `prob` (left untouched; its clone is freed): at most `iters` (1..1000) distance LPs, the
+   objective weight alpha (0..1; alpha_k = alpha * 0.9^k, a = 1 - alpha_k, q = alpha_k / ||c0||, 0 for a zero objective).  Per
+   LP one step, one objective apply (set_obj_many, else set_obj_coef for the columns whose coefficient differs from
+   get_obj_coef) and one solve with the default parameters.  A pump that ends integral is rounded and checked (mvx_bnb_round,
+   mode 1).  *found 1 when that point is feasible, *obj / x[1..n] the point, *lps / *pivots the LPs solved and their pivots.
+   Uses the table's batched entries where it has them (pump_obj_many, set_obj_many, simplex_batch, round_many) and the twins
+   otherwise.  Returns 0; -1 bad arguments; -2 the table lacks an accessor, or can not change an objective; -3 the handle is
+   not MVX_OPT.  mvx_branchAndBound returns -1 (*res empty) for pump outside 0..1000, a negative pump_freq, pump_alpha outside
+   [0, 1] and pump > 0 with reference_quirks = 1 or best_window > 0, and -2, with the tree so far, when a pump could not be
+   carried out */
+int mvx_bnb_pump(const mvx_lp_api *api, const void *prob, const void *root, int iters, double alpha, double *obj, int *found, double *x,
+                 long long *lps, long long *pivots, int *end);
 
 /* bs.cpp:249-258 on one solved node `a` that is about to be branched: generate its GMI cut(s) and append the
    row(s) (cut_strat / reference_quirks / lazy_pool / cut_select / cut_chance of `params`).  Returns the number

@@ -16,7 +16,7 @@ _FIELDS = [
 ]
 _OPTIONAL = ["simplex_batch", "get_obj_dir", "gmi_cuts", "gmi_cuts_many", "get_col_prim_all", "classify_many", "get_tableau", "get_basis",
              "branch_penalties_many", "round_many", "rc_tighten_many", "tighten_cols_many", "propagate_many", "set_col_bnds_many",
-             "dive_pick_many"]
+             "dive_pick_many", "set_obj_coef", "set_obj_many", "pump_obj_many"]
 
 
 class LpApiTable(C.Structure):
@@ -46,6 +46,9 @@ class BnbParams(C.Structure):
         ("dive", C.c_int),
         ("dive_freq", C.c_int),
         ("dive_depth", C.c_int),
+        ("pump", C.c_int),
+        ("pump_freq", C.c_int),
+        ("pump_alpha", C.c_double),
     ]
 
 
@@ -98,6 +101,11 @@ class BnbResult(C.Structure):
         ("dive_improved", C.c_longlong),
         ("dive_lps", C.c_longlong),
         ("dive_pivots", C.c_longlong),
+        ("pump_calls", C.c_longlong),
+        ("pump_found", C.c_longlong),
+        ("pump_improved", C.c_longlong),
+        ("pump_lps", C.c_longlong),
+        ("pump_pivots", C.c_longlong),
     ]
 
 
@@ -164,6 +172,15 @@ def _bind(lib):
     lib.mvx_bnb_dive.restype = C.c_int
     lib.mvx_bnb_dive.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, _DP, _IP, _DP, C.POINTER(C.c_longlong),
                                  C.POINTER(C.c_longlong)]
+    lib.mvx_set_obj_many.restype = C.c_int
+    lib.mvx_set_obj_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, _DP]
+    lib.mvx_pump_obj_many.restype = C.c_int
+    lib.mvx_pump_obj_many.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, _DP, _IP, _DP, _IP, _DP, _DP]
+    lib.mvx_bnb_pump_obj.restype = C.c_int
+    lib.mvx_bnb_pump_obj.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _DP, C.c_int, _DP, _IP, _DP, _DP]
+    lib.mvx_bnb_pump.restype = C.c_int
+    lib.mvx_bnb_pump.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, _DP, _IP, _DP, C.POINTER(C.c_longlong),
+                                 C.POINTER(C.c_longlong), _IP]
     lib.mvx_generateCut3.restype = C.c_int
     lib.mvx_generateCut3.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     return lib
@@ -219,12 +236,17 @@ def result_to_dict(res):
         "dive_improved": res.dive_improved,
         "dive_lps": res.dive_lps,
         "dive_pivots": res.dive_pivots,
+        "pump_calls": res.pump_calls,
+        "pump_found": res.pump_found,
+        "pump_improved": res.pump_improved,
+        "pump_lps": res.pump_lps,
+        "pump_pivots": res.pump_pivots,
     }
 
 
 def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, window=None, cut_select=0, cut_chance=1.0,
                 best_window=None, sb_cands=None, sb_iters=None, heur=None, rc_fix=None, prop=None, dive=None, dive_freq=None,
-                dive_depth=None):
+                dive_depth=None, pump=None, pump_freq=None, pump_alpha=None):
     """mvx_bnb_params with ParameterObj's defaults (util.h:65-67) overridden by the arguments (None: the default)."""
     pr = BnbParams()
     lib().mvx_bnb_default_params(C.byref(pr))
@@ -251,12 +273,18 @@ def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, l
         pr.dive_freq = dive_freq
     if dive_depth is not None:
         pr.dive_depth = dive_depth
+    if pump is not None:
+        pr.pump = pump
+    if pump_freq is not None:
+        pr.pump_freq = pump_freq
+    if pump_alpha is not None:
+        pr.pump_alpha = pump_alpha
     return pr
 
 
 def branch_and_bound(prob, var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, table=None, window=None,
                      cut_select=0, cut_chance=1.0, best_window=None, sb_cands=None, sb_iters=None, heur=None, rc_fix=None, prop=None,
-                     dive=None, dive_freq=None, dive_depth=None):
+                     dive=None, dive_freq=None, dive_depth=None, pump=None, pump_freq=None, pump_alpha=None):
     """Run the driver on `prob` (a capi.Prob).  table=None uses the gfx950 engine's own table.  best_window > 1 with
     node_strat=1: the speculative best-bound window (mvx_bnb_params.best_window).  var_strat 3 / 4: branching on the node
     LP's penalties / strong branching (sb_cands candidates, sb_iters pivots per child).  heur 1 / 2: the primal rounding
@@ -264,12 +292,15 @@ def branch_and_bound(prob, var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, 
     tightening on every branching node once an incumbent exists (quirks=0, not with best_window).  prop 1..16: node bound
     propagation of the root and of every child with that round limit (quirks=0, not with best_window).  dive 1..7: the LP
     diving heuristic with those rules (bits 1 fractional, 2 locks, 4 vector length) at the root and, with dive_freq = F > 0,
-    at every branching node whose oid F divides; dive_depth limits a dive's steps (quirks=0, not with best_window).  The
+    at every branching node whose oid F divides; dive_depth limits a dive's steps (quirks=0, not with best_window).  pump 1..1000: the
+    feasibility pump with that limit of distance LPs at the root and, with pump_freq = F > 0, at every branching node whose oid F
+    divides, behind the rounding heuristic and in front of the dives; pump_alpha (0..1) weighs the model's objective into the
+    distance LPs (quirks=0, not with best_window).  The
     dictionary's "rc" is mvx_branchAndBound's return code (-1 refused parameters, -2 penalties, heuristic, tightening,
-    propagation or dives unavailable)."""
+    propagation, pumps or dives unavailable)."""
     L = lib()
     pr = make_params(var_strat, node_strat, cut_strat, max_nodes, quirks, lazy_pool, window, cut_select, cut_chance, best_window, sb_cands,
-                     sb_iters, heur, rc_fix, prop, dive, dive_freq, dive_depth)
+                     sb_iters, heur, rc_fix, prop, dive, dive_freq, dive_depth, pump, pump_freq, pump_alpha)
     res = BnbResult()
     tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
     rc = L.mvx_branchAndBound(tptr, prob.h, C.byref(pr), C.byref(res))
@@ -586,6 +617,80 @@ def dive_node(prob, root, rules=7, depth=0, table=None):
     rc = lib().mvx_bnb_dive(tptr, prob.h, root.h, rules, depth, C.byref(obj), C.byref(found), x.ctypes.data_as(C.POINTER(C.c_double)),
                             C.byref(lps), C.byref(piv))
     return rc, obj.value, found.value, x, lps.value, piv.value
+
+
+PUMP_ENDS = {1: "integral", 2: "limit", 3: "stalled", 4: "cycle", 5: "failed"}
+
+
+def set_obj_many(probs, c):
+    """mvx_set_obj_many: handle t of the gfx950 engine takes the objective c[t] (n + 1 entries, entry 0 the constant), the cost
+    rows of all handles rebuilt in one launch; every handle is left as set_obj_coef per entry would leave it.  Returns the
+    call's code (0; -1 bad arguments; -2 device out of memory, nothing changed)."""
+    import numpy as np
+
+    k = len(probs)
+    hs = (C.c_void_p * max(1, k))(*[p.h for p in probs])
+    flat = np.ascontiguousarray(np.asarray(c, dtype=np.float64).reshape(-1)) if k else np.zeros(1)
+    return lib().mvx_set_obj_many(hs, k, flat.ctypes.data_as(C.POINTER(C.c_double)))
+
+
+def pump_obj_many(root, probs, xprev=None, ab=None):
+    """mvx_pump_obj_many over solved capi.Prob handles of the gfx950 engine against the model of `root`: one launch for all of
+    them.  xprev[t]: handle t's last rounding (n + 1 entries) or None; ab[t] = (a, q), default (1, 0), the plain pump.  Returns
+    (rc, info array (k, 4): nfrac, moved, stalled, nnz; xt array (k, n + 1); c array (k, n + 1))."""
+    import numpy as np
+
+    k = len(probs)
+    n = root.n
+    hs = (C.c_void_p * max(1, k))(*[p.h for p in probs])
+    xp = np.zeros((max(1, k), n + 1))
+    hp = np.zeros(max(1, k), dtype=np.int32)
+    for t in range(k):
+        if xprev is not None and xprev[t] is not None:
+            xp[t] = xprev[t]
+            hp[t] = 1
+    w = np.array([(1.0, 0.0)] * max(1, k) if ab is None else list(ab), dtype=np.float64).reshape(-1)
+    info = np.zeros((max(1, k), 4), dtype=np.int32)
+    xt, c = np.zeros((max(1, k), n + 1)), np.zeros((max(1, k), n + 1))
+    DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    rc = lib().mvx_pump_obj_many(root.h, hs, k, xp.ctypes.data_as(DP), hp.ctypes.data_as(IP), w.ctypes.data_as(DP), info.ctypes.data_as(IP),
+                                 xt.ctypes.data_as(DP), c.ctypes.data_as(DP))
+    if rc != 0:
+        return rc, None, None, None
+    return rc, info[:k], xt[:k], c[:k]
+
+
+def pump_obj_node(prob, root, xprev=None, ab=(1.0, 0.0), table=None):
+    """mvx_bnb_pump_obj (the host twin, through `table`; None = the gfx950 engine's table) on one solved node against the
+    model of `root`.  Returns (rc, info array of 4, xt array of n + 1, c array of n + 1)."""
+    import numpy as np
+
+    n = root.n
+    xp = np.zeros(n + 1) if xprev is None else np.ascontiguousarray(xprev, dtype=np.float64)
+    w = np.array(ab, dtype=np.float64)
+    info = np.zeros(4, dtype=np.int32)
+    xt, c = np.zeros(n + 1), np.zeros(n + 1)
+    DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
+    rc = lib().mvx_bnb_pump_obj(tptr, prob.h, root.h, xp.ctypes.data_as(DP), 0 if xprev is None else 1, w.ctypes.data_as(DP),
+                                info.ctypes.data_as(IP), xt.ctypes.data_as(DP), c.ctypes.data_as(DP))
+    return rc, info, xt, c
+
+
+def pump_node(prob, root, iters=30, alpha=0.0, table=None):
+    """mvx_bnb_pump: one whole feasibility pump of the solved node `prob`, at most `iters` distance LPs, objective weight
+    `alpha`, through `table` (None = the gfx950 engine's table, whose batched entries then run).  Returns (rc, obj, found,
+    x array of n + 1 entries, lps, pivots, end) with end a key of PUMP_ENDS."""
+    import numpy as np
+
+    n = root.n
+    obj, found, end = C.c_double(0.0), C.c_int(0), C.c_int(0)
+    lps, piv = C.c_longlong(0), C.c_longlong(0)
+    x = np.zeros(n + 1)
+    tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
+    rc = lib().mvx_bnb_pump(tptr, prob.h, root.h, iters, alpha, C.byref(obj), C.byref(found), x.ctypes.data_as(C.POINTER(C.c_double)),
+                            C.byref(lps), C.byref(piv), C.byref(end))
+    return rc, obj.value, found.value, x, lps.value, piv.value, end.value
 
 
 def node_sample(root, count, quirks=0, table=None):

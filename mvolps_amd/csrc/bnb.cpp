@@ -44,6 +44,9 @@ extern "C" int mvx_set_col_bnds_many(mvx_prob *const *Ps, int count, const int *
 extern "C" int mvx_dive_pick_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, const int *rules, int *nfrac, int *col, int *dir,
                                   double *val)
     __attribute__((weak));
+extern "C" int mvx_set_obj_many(mvx_prob *const *Ps, int count, const double *c) __attribute__((weak));
+extern "C" int mvx_pump_obj_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, const double *xprev, const int *has_prev,
+                                 const double *ab, int *info, double *xt, double *c) __attribute__((weak));
 
 namespace {
 
@@ -1726,6 +1729,325 @@ private:
   RoundHost _M;
 };
 
+// ---- feasibility pump (DESIGN.md "Feasibility pump") ----
+
+// What the rounding and objective step gives on one solved node.
+struct PumpStep {
+  int nfrac = 0, moved = 0, stalled = 0, nnz = 0;
+  std::vector<double> xt, c; // [0..n]
+};
+
+// The step on one solved node (the host twin of k_pumpobj: same tests, every operation rounded on its own): the rounding of the
+// integer columns, the move of a repeated rounding, the distance slopes and the new objective in the node's own direction,
+// c_j = a * (-sg * d_j) + (q * sqrt(nnz(d))) * c0_j.  The bounds are the node's own, the integer flags and c0 the root's.
+static int pump_obj_host(const mvx_lp_api *api, const RoundHost &M, const void *P, const double *xprev, int has_prev, double a, double q,
+                         PumpStep &out) {
+  const int n = M.n;
+  if (!P || api->get_num_cols(P) != n || (has_prev && !xprev)) return -1;
+  if (api->get_status(P) != MVX_OPT) return -3;
+  std::vector<double> v((size_t)n + 1, 0.0), lo((size_t)n + 1, 0.0), hi((size_t)n + 1, 0.0);
+  if (api->get_col_prim_all) api->get_col_prim_all(P, v.data());
+  else
+    for (int j = 1; j <= n; j++) v[(size_t)j] = api->get_col_prim(P, j);
+  const double sg = (api->get_obj_dir && api->get_obj_dir(P) == MVX_MIN) ? -1.0 : 1.0;
+  out = PumpStep();
+  out.xt.assign((size_t)n + 1, 0.0);
+  out.c.assign((size_t)n + 1, 0.0);
+  std::vector<double> &xt = out.xt;
+  bool differs = false;
+  for (int j = 1; j <= n; j++) {
+    if (!M.isint[(size_t)j]) continue;
+    const double vj = v[(size_t)j];
+    if (std::fabs(vj - std::rint(vj)) > 1e-9) out.nfrac++;
+    const double L = std::ceil(tab_bound(api->get_col_lb(P, j))), U = std::floor(tab_bound(api->get_col_ub(P, j)));
+    double x = std::floor(vj + 0.5); // round_host's nearest integer
+    if (x < L) x = L;
+    if (x > U) x = U;
+    lo[(size_t)j] = L;
+    hi[(size_t)j] = U;
+    xt[(size_t)j] = x;
+    if (has_prev && x != xprev[j]) differs = true;
+  }
+  const bool stall = has_prev && !differs;
+  if (stall) {
+    std::vector<double> sig((size_t)n + 1, -1.0);
+    for (int j = 1; j <= n; j++) {
+      if (!M.isint[(size_t)j]) continue;
+      const double d = v[(size_t)j] - xt[(size_t)j], sd = std::fabs(d);
+      if (!(sd > 0.0)) continue;
+      const double xn = xt[(size_t)j] + (d > 0.0 ? 1.0 : -1.0);
+      if (xn >= lo[(size_t)j] && xn <= hi[(size_t)j]) sig[(size_t)j] = sd;
+    }
+    for (int r = 0; r < 10; r++) {
+      int win = 0;
+      double bk = 0.0;
+      for (int j = 1; j <= n; j++) // columns ascend: a tie keeps the lower one
+        if (sig[(size_t)j] > bk) {
+          bk = sig[(size_t)j];
+          win = j;
+        }
+      if (!win) break;
+      xt[(size_t)win] = xt[(size_t)win] + (v[(size_t)win] - xt[(size_t)win] > 0.0 ? 1.0 : -1.0);
+      sig[(size_t)win] = -1.0;
+      out.moved++;
+    }
+  }
+  out.stalled = (stall && out.moved == 0) ? 1 : 0;
+  std::vector<double> d((size_t)n + 1, 0.0);
+  for (int j = 1; j <= n; j++) {
+    if (!M.isint[(size_t)j]) continue;
+    const double L = lo[(size_t)j], U = hi[(size_t)j], x = xt[(size_t)j];
+    double dj;
+    if (L == U) dj = 0.0;
+    else if (x == L) dj = 1.0;
+    else if (x == U) dj = -1.0;
+    else {
+      const double df = v[(size_t)j] - x;
+      dj = df > 0.0 ? 1.0 : df < 0.0 ? -1.0 : 0.0;
+    }
+    d[(size_t)j] = dj;
+    if (dj != 0.0) out.nnz++;
+  }
+  const double b = q * std::sqrt((double)out.nnz);
+  for (int j = 1; j <= n; j++) {
+    const double t1 = a * (-sg * d[(size_t)j]), t2 = b * M.c[(size_t)j];
+    out.c[(size_t)j] = t1 + t2;
+  }
+  return 0;
+}
+
+// What the pump of one node gave: the point when it ended integral and the point checked out, the work, and how it ended.
+struct PumpOut {
+  int found = 0, end = 0; // end: MVX_PUMP_*
+  double obj = 0.0;
+  std::vector<double> x; // [0..n] when found
+  long long lps = 0, pivots = 0;
+};
+
+// One tree's pumps.  run() takes solved (OPT) nodes and advances their pumps in lockstep: per round one rounding and
+// objective step for the live pumps (pump_obj_many when the table has it and the model fits the kernel, else the twin), the
+// history check on the host, one objective apply (set_obj_many, else set_obj_coef per changed column) and one batched solve,
+// and at the end one rounding call (mode 1) for the pumps that ended integral.  Nothing of the incumbent enters: a result
+// depends on its node's LP only.
+class Pump {
+public:
+  Pump(const mvx_lp_api *api, const void *root, const mvx_bnb_params &prm)
+      : _api(api), _root(root), _iters(prm.pump), _freq(prm.pump_freq), _alpha(prm.pump_alpha), _round(api, root, 1) {}
+  Pump(const mvx_lp_api *api, const void *root, int iters, double alpha)
+      : _api(api), _root(root), _iters(iters), _freq(0), _alpha(alpha), _round(api, root, 1) {}
+  bool on() const { return _iters > 0; }
+  // the root, and with pump_freq = F > 0 every node whose oid F divides
+  bool selects(const MVOLP::NodeData &node) const { return _iters > 0 && (node.inital || (_freq > 0 && node.oid % _freq == 0)); }
+
+  // the step on hs[k]; 0, or the failing call's code
+  int step(const std::vector<const void *> &hs, const std::vector<const double *> &xprev, const std::vector<double> &ab,
+           std::vector<PumpStep> &out) {
+    const size_t K = hs.size();
+    out.assign(K, PumpStep());
+    if (K == 0) return 0;
+    const int n = _api->get_num_cols(_root);
+    const size_t row = (size_t)n + 1;
+    if (_api->pump_obj_many && _device) {
+      std::vector<double> xp(K * row, 0.0), xt(K * row), c(K * row);
+      std::vector<int> hp(K), info(K * 4);
+      for (size_t k = 0; k < K; k++) {
+        hp[k] = xprev[k] ? 1 : 0;
+        if (xprev[k]) std::memcpy(xp.data() + k * row, xprev[k], row * 8);
+      }
+      const int rc = _api->pump_obj_many(_root, hs.data(), (int)K, xp.data(), hp.data(), ab.data(), info.data(), xt.data(), c.data());
+      if (rc == 0) {
+        for (size_t k = 0; k < K; k++) {
+          out[k].nfrac = info[4 * k];
+          out[k].moved = info[4 * k + 1];
+          out[k].stalled = info[4 * k + 2];
+          out[k].nnz = info[4 * k + 3];
+          out[k].xt.assign(xt.begin() + k * row, xt.begin() + (k + 1) * row);
+          out[k].c.assign(c.begin() + k * row, c.begin() + (k + 1) * row);
+        }
+        return 0;
+      }
+      if (rc != -5) return rc;
+      _device = false; // more columns than the kernel holds: the host twin, same bits, for the rest of the tree
+    }
+    int rc = model();
+    if (rc != 0) return rc;
+    for (size_t k = 0; k < K; k++) {
+      rc = pump_obj_host(_api, _M, hs[k], xprev[k], xprev[k] ? 1 : 0, ab[2 * k], ab[2 * k + 1], out[k]);
+      if (rc != 0) return rc;
+    }
+    return 0;
+  }
+
+  // hs: solved (OPT) nodes, left untouched; 0, or the failing call's code.  The pumps are cut into batches that fit the
+  // strong-branching memory budget (one tableau per live pump); results do not depend on the cut.
+  int run(const std::vector<const void *> &hs, std::vector<PumpOut> &out) {
+    out.assign(hs.size(), PumpOut());
+    if (hs.empty() || _iters <= 0) return 0;
+    if (!_api->set_obj_many && !(_api->set_obj_coef && _api->get_obj_coef)) return -2;
+    if (!_norm_ready) { // once per tree: the 2-norm of the root's objective, ascending j, plain adds
+      if (!_api->get_obj_coef) return -2;
+      const int n = _api->get_num_cols(_root);
+      double sum = 0.0;
+      for (int j = 1; j <= n; j++) {
+        const double cj = _api->get_obj_coef(_root, j);
+        sum = sum + cj * cj;
+      }
+      _norm = std::sqrt(sum);
+      _norm_ready = true;
+    }
+    std::vector<Job> jobs(hs.size());
+    const size_t tab = (size_t)(_api->get_num_rows(hs[0]) + 1) * (size_t)(_api->get_num_cols(hs[0]) + 1) * 8;
+    const size_t per = std::max<size_t>(1, std::min(jobs.size(), sb_budget() / (tab + 1)));
+    int rc = 0;
+    for (size_t j0 = 0; j0 < jobs.size() && rc == 0; j0 += per) rc = advance(hs, jobs, j0, std::min(jobs.size(), j0 + per));
+    for (Job &jb : jobs) drop(jb); // a failing call leaves clones behind
+    if (rc != 0) return rc;
+    for (size_t t = 0; t < jobs.size(); t++) {
+      out[t].end = jobs[t].end;
+      out[t].lps = jobs[t].lps;
+      out[t].pivots = jobs[t].pivots;
+      if (jobs[t].res.found) {
+        out[t].found = 1;
+        out[t].obj = jobs[t].res.obj;
+        out[t].x = std::move(jobs[t].res.x);
+      }
+    }
+    return 0;
+  }
+
+private:
+  struct Job {
+    void *cur = nullptr; // the pump's own clone of its node
+    int k = 0, end = 0;  // LPs solved so far; 0 while the pump is live
+    double alpha = 0.0;  // alpha_k
+    std::vector<std::vector<double>> hist; // the roundings so far, the last one being xprev
+    long long lps = 0, pivots = 0;
+    HeurOut res;
+  };
+  void drop(Job &jb) {
+    if (jb.cur) _api->delete_prob(jb.cur);
+    jb.cur = nullptr;
+  }
+  int model() {
+    if (_ready) return 0;
+    const int rc = round_host_model(_api, _root, _M);
+    if (rc == 0) _ready = true;
+    return rc;
+  }
+  // the objectives cs[k] applied to hs[k]
+  int apply(const std::vector<void *> &hs, const std::vector<const std::vector<double> *> &cs) {
+    const int n = _api->get_num_cols(_root);
+    const size_t row = (size_t)n + 1;
+    if (_api->set_obj_many) {
+      std::vector<double> flat(hs.size() * row);
+      for (size_t k = 0; k < hs.size(); k++) std::memcpy(flat.data() + k * row, cs[k]->data(), row * 8);
+      return _api->set_obj_many(hs.data(), (int)hs.size(), flat.data()) == 0 ? 0 : -2;
+    }
+    for (size_t k = 0; k < hs.size(); k++)
+      for (int j = 0; j <= n; j++)
+        if (_api->get_obj_coef(hs[k], j) != (*cs[k])[(size_t)j]) _api->set_obj_coef(hs[k], j, (*cs[k])[(size_t)j]);
+    return 0;
+  }
+
+  int advance(const std::vector<const void *> &nodes, std::vector<Job> &jobs, size_t j0, size_t j1) {
+    for (size_t j = j0; j < j1; j++) {
+      jobs[j].cur = _api->create_prob();
+      _api->copy_prob(jobs[j].cur, nodes[j], MVX_ON);
+      jobs[j].alpha = _alpha;
+    }
+    for (;;) {
+      // 1. the step of the live pumps
+      std::vector<const void *> sh;
+      std::vector<const double *> sp;
+      std::vector<double> ab;
+      std::vector<size_t> sj;
+      for (size_t j = j0; j < j1; j++) {
+        Job &jb = jobs[j];
+        if (jb.end) continue;
+        sh.push_back(jb.cur);
+        sp.push_back(jb.hist.empty() ? nullptr : jb.hist.back().data());
+        ab.push_back(1.0 - jb.alpha);
+        ab.push_back(_norm > 0.0 ? jb.alpha / _norm : 0.0);
+        sj.push_back(j);
+      }
+      if (sh.empty()) break;
+      std::vector<PumpStep> steps;
+      int rc = step(sh, sp, ab, steps);
+      if (rc != 0) return rc;
+      // 2. how each goes on: integral, the limit, a stall, a cycle (the history is the host's), or the next LP
+      std::vector<void *> gh;
+      std::vector<const std::vector<double> *> gc;
+      std::vector<size_t> gj;
+      for (size_t k = 0; k < sj.size(); k++) {
+        Job &jb = jobs[sj[k]];
+        PumpStep &st = steps[k];
+        if (st.nfrac == 0) jb.end = MVX_PUMP_INTEGRAL;
+        else if (jb.k == _iters) jb.end = MVX_PUMP_LIMIT;
+        else if (st.stalled) jb.end = MVX_PUMP_STALLED;
+        else if (st.moved > 0 && std::find(jb.hist.begin(), jb.hist.end(), st.xt) != jb.hist.end()) jb.end = MVX_PUMP_CYCLE;
+        if (jb.end) continue;
+        jb.hist.push_back(st.xt);
+        gh.push_back(jb.cur);
+        gc.push_back(&st.c);
+        gj.push_back(sj[k]);
+      }
+      if (gh.empty()) continue;
+      // 3. one objective apply and one batched solve with the default parameters: the basis is primal feasible
+      rc = apply(gh, gc);
+      if (rc != 0) return rc;
+      std::vector<int> before(gh.size());
+      for (size_t k = 0; k < gh.size(); k++) before[k] = _api->get_it_cnt(gh[k]);
+      if (_api->simplex_batch) _api->simplex_batch(gh.data(), (int)gh.size(), nullptr, nullptr);
+      else
+        for (void *h : gh) _api->simplex(h, nullptr);
+      for (size_t k = 0; k < gh.size(); k++) {
+        Job &jb = jobs[gj[k]];
+        jb.lps++;
+        jb.pivots += _api->get_it_cnt(gh[k]) - before[k];
+        jb.k++;
+        jb.alpha = jb.alpha * 0.9;
+        if (_api->get_status(gh[k]) != MVX_OPT) jb.end = MVX_PUMP_FAILED;
+      }
+    }
+    // 4. the pumps that ended integral: rounded and checked against the root's model, priced with the root's objective
+    std::vector<const void *> rh;
+    std::vector<size_t> rj;
+    for (size_t j = j0; j < j1; j++)
+      if (jobs[j].end == MVX_PUMP_INTEGRAL) {
+        rh.push_back(jobs[j].cur);
+        rj.push_back(j);
+      }
+    std::vector<HeurOut> got;
+    const int rc = _round.run(rh, got);
+    if (rc != 0) return rc;
+    for (size_t k = 0; k < rj.size(); k++) jobs[rj[k]].res = std::move(got[k]);
+    for (size_t j = j0; j < j1; j++) drop(jobs[j]);
+    return 0;
+  }
+
+  const mvx_lp_api *_api;
+  const void *_root;
+  int _iters, _freq;
+  double _alpha;
+  Heuristic _round;
+  bool _device = true; // pump_obj_many is used while it accepts the model
+  bool _ready = false, _norm_ready = false;
+  double _norm = 0.0;
+  RoundHost _M;
+};
+
+// The pumps' counts, booked the way the serial loop meets the nodes.
+struct PumpBook {
+  long long calls = 0, found = 0, improved = 0, lps = 0, pivots = 0;
+  void store(mvx_bnb_result *res) const {
+    res->pump_calls = calls;
+    res->pump_found = found;
+    res->pump_improved = improved;
+    res->pump_lps = lps;
+    res->pump_pivots = pivots;
+  }
+};
+
 // The dives' counts, booked the way the serial loop meets the nodes.
 struct DiveBook {
   long long calls = 0, found = 0, improved = 0, lps = 0, pivots = 0;
@@ -1767,6 +2089,7 @@ struct Tree {
   long long sb_lps = 0, sb_pivots = 0;
   HeurBook hbook;
   DiveBook dbook;
+  PumpBook pbook;
 
   Tree(const mvx_lp_api *api_, const void *prob, const mvx_bnb_params &p)
       : api(api_), prm(p), quirks(p.reference_quirks != 0), sg(MVOLP::sense_of(api_, prob, p)), n0(api_->get_num_cols(prob)),
@@ -1840,6 +2163,21 @@ struct Tree {
     hbook.incumbent = 2;
     for (size_t j = 1; j < xbest.size() && j < d.x.size(); j++) xbest[j] = d.x[j];
   }
+  // a pumped node that branches: its work is booked, and its point becomes the incumbent when it is strictly better
+  void book_pump(const PumpOut &p, int oid) {
+    pbook.calls++;
+    pbook.lps += p.lps;
+    pbook.pivots += p.pivots;
+    if (!p.found) return;
+    pbook.found++;
+    if (!(sg * p.obj > sg * bestLower)) return;
+    pbook.improved++;
+    bestLower = p.obj;
+    has_incumbent = 1;
+    incumbent_oid = oid;
+    hbook.incumbent = 3;
+    for (size_t j = 1; j < xbest.size() && j < p.x.size(); j++) xbest[j] = p.x[j];
+  }
   void book_choice(const Choice &c) {
     sb_lps += c.sb_lps;
     sb_pivots += c.sb_pivots;
@@ -1885,6 +2223,7 @@ struct Tree {
     res->sb_pivots = sb_pivots;
     hbook.store(res);
     dbook.store(res);
+    pbook.store(res);
     if (rcfix) rcfix->store(res);
     if (prop) prop->store(res);
     return rc_out;
@@ -1921,6 +2260,7 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm,
   RcFix rcfix(api);
   Prop prop(api, prob, prm.prop);
   Dive dive(api, prob, prm);
+  Pump pump(api, prob, prm);
 
   while (!leafContainer.empty()) { // bs.cpp:96
     if (T.node_limit()) break;
@@ -1947,6 +2287,15 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm,
           break;
         }
         T.book_heur(ho[0], node->oid);
+      }
+      // the pump starts from the node's LP as solved, behind the rounding heuristic and in front of the dives
+      if (pump.selects(*node) && api->get_status(a) == MVX_OPT) {
+        std::vector<PumpOut> pout;
+        if (pump.run({a}, pout) != 0) {
+          T.rc_out = -2;
+          break;
+        }
+        T.book_pump(pout[0], node->oid);
       }
       // the dives start from the node's LP as solved, behind the rounding heuristic and in front of rc_fix and the cut step
       if (dive.selects(*node) && api->get_status(a) == MVX_OPT) {
@@ -2038,6 +2387,7 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
   RcFix rcfix(api);
   Prop prop(api, prob, prm.prop);
   Dive dive(api, prob, prm);
+  Pump pump(api, prob, prm);
   auto fail = [&]() { // whatever code a failing call gives, the tree so far goes back with -2
     T.rc_out = -2;
     stop = true;
@@ -2179,7 +2529,7 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
     // that qualify.  may[w]: node w is neither infeasible nor integral, so it branches unless its bound prunes it; opt[w]: and
     // its LP ended OPT.
     std::vector<char> may, opt;
-    if (prm.var_strat >= 3 || prm.heur > 0 || prm.rc_fix > 0 || dive.on()) {
+    if (prm.var_strat >= 3 || prm.heur > 0 || prm.rc_fix > 0 || dive.on() || pump.on()) {
       if (info.empty()) {
         info.resize(W);
         for (size_t w = 0; w < W; w++) info[w] = printInfo(api, a[w], quirks);
@@ -2207,6 +2557,15 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
     // that do branch, so the incumbent moves where the serial loop's does
     std::vector<HeurOut> hres(opt.size());
     if (prm.heur > 0 && on_slots(a, opt, 0, hres, [&](const auto &hs, const auto &, auto &got) { return heur.run(hs, got); }) != 0) {
+      fail();
+      break;
+    }
+    // the pumps of every selected node of the window that may branch, all in lockstep in one call; booked by the replay for
+    // the nodes that do branch.  Nothing of the incumbent enters a pump, so a result is the serial loop's
+    std::vector<char> psel(pump.on() ? W : 0);
+    for (size_t w = 0; w < psel.size(); w++) psel[w] = opt[w] && pump.selects(*leafContainer[w]);
+    std::vector<PumpOut> pres(psel.size());
+    if (pump.on() && on_slots(a, psel, 0, pres, [&](const auto &hs, const auto &, auto &got) { return pump.run(hs, got); }) != 0) {
       fail();
       break;
     }
@@ -2269,6 +2628,7 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
         // as it is -- but it marks the handle's solution mirrors stale, and reading one value afterwards is a device
         // export and a host round trip per branching node (~40 us, a tenth of the cut modes' run)
         if (prm.heur > 0 && opt[w]) T.book_heur(hres[w], node->oid);
+        if (pump.on() && psel[w]) T.book_pump(pres[w], node->oid);
         if (dive.on() && dsel[w]) T.book_dive(dres[w], node->oid);
         RcList node_rc;
         if (prm.rc_fix > 0 && T.has_incumbent && opt[w]) {
@@ -2724,6 +3084,12 @@ const mvx_lp_api g_hip_api = {
     mvx_dive_pick_many ? +[](const void *root, const void *const *Ps, int count, const int *rules, int *nfrac, int *col, int *dir, double *val) {
       return mvx_dive_pick_many((const mvx_prob *)root, (const mvx_prob *const *)Ps, count, rules, nfrac, col, dir, val);
     } : nullptr,
+    [](void *P, int j, double coef) { mvx_set_obj_coef((mvx_prob *)P, j, coef); },
+    mvx_set_obj_many ? +[](void *const *Ps, int count, const double *c) { return mvx_set_obj_many((mvx_prob *const *)Ps, count, c); } : nullptr,
+    mvx_pump_obj_many ? +[](const void *root, const void *const *Ps, int count, const double *xprev, const int *has_prev, const double *ab,
+                            int *info, double *xt, double *c) {
+      return mvx_pump_obj_many((const mvx_prob *)root, (const mvx_prob *const *)Ps, count, xprev, has_prev, ab, info, xt, c);
+    } : nullptr,
 };
 
 } // namespace
@@ -2752,6 +3118,9 @@ void mvx_bnb_default_params(mvx_bnb_params *p) {
   p->dive = 0;
   p->dive_freq = 0;
   p->dive_depth = 0;
+  p->pump = 0;
+  p->pump_freq = 0;
+  p->pump_alpha = 0.0;
 }
 
 // Repaired mode's rule for an integer column whose bounds are not integers (legal input: LP and MPS files may carry them):
@@ -2806,7 +3175,10 @@ int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *
       params->prop < 0 || params->prop > 16 || (params->prop > 0 && (params->reference_quirks != 0 || params->best_window > 0)) ||
       // dive: children with both bounds kept, and not (yet) in the best-bound window either
       params->dive < 0 || params->dive > 7 || params->dive_freq < 0 || params->dive_depth < 0 ||
-      (params->dive > 0 && (params->reference_quirks != 0 || params->best_window > 0))) {
+      (params->dive > 0 && (params->reference_quirks != 0 || params->best_window > 0)) ||
+      // pump: the same
+      params->pump < 0 || params->pump > 1000 || params->pump_freq < 0 || !(params->pump_alpha >= 0.0 && params->pump_alpha <= 1.0) ||
+      (params->pump > 0 && (params->reference_quirks != 0 || params->best_window > 0))) {
     std::memset(res, 0, sizeof(*res));
     return -1;
   }
@@ -2945,6 +3317,43 @@ int mvx_bnb_dive(const mvx_lp_api *api, const void *prob, const void *root, int 
   *lps = out[0].lps;
   *pivots = out[0].pivots;
   for (size_t j = 1; j < out[0].x.size(); j++) x[j] = out[0].x[j];
+  return 0;
+}
+
+int mvx_bnb_pump_obj(const mvx_lp_api *api, const void *prob, const void *root, const double *xprev, int has_prev, const double *ab,
+                     int *info, double *xt, double *c) {
+  if (!api) api = &g_hip_api;
+  if (!prob || !root || !ab || !info || !xt || !c || (has_prev && !xprev)) return -1;
+  RoundHost M;
+  int rc = round_host_model(api, root, M);
+  if (rc != 0) return rc;
+  PumpStep st;
+  rc = pump_obj_host(api, M, prob, xprev, has_prev ? 1 : 0, ab[0], ab[1], st);
+  if (rc != 0) return rc;
+  info[0] = st.nfrac; info[1] = st.moved; info[2] = st.stalled; info[3] = st.nnz;
+  std::memcpy(xt, st.xt.data(), st.xt.size() * 8);
+  std::memcpy(c, st.c.data(), st.c.size() * 8);
+  return 0;
+}
+
+int mvx_bnb_pump(const mvx_lp_api *api, const void *prob, const void *root, int iters, double alpha, double *obj, int *found, double *x,
+                 long long *lps, long long *pivots, int *end) {
+  if (!api) api = &g_hip_api;
+  if (!prob || !root || iters < 1 || iters > 1000 || !(alpha >= 0.0 && alpha <= 1.0) || !obj || !found || !x || !lps || !pivots || !end)
+    return -1;
+  if (api->get_num_cols(prob) != api->get_num_cols(root)) return -1;
+  if (!api->get_status) return -2;
+  if (api->get_status(prob) != MVX_OPT) return -3;
+  Pump pump(api, root, iters, alpha);
+  std::vector<PumpOut> out;
+  const int rc = pump.run(std::vector<const void *>(1, prob), out);
+  if (rc != 0) return rc;
+  *found = out[0].found;
+  *obj = out[0].obj;
+  *lps = out[0].lps;
+  *pivots = out[0].pivots;
+  *end = out[0].end;
+  if (out[0].found) std::memcpy(x + 1, out[0].x.data() + 1, (size_t)api->get_num_cols(root) * 8);
   return 0;
 }
 

@@ -108,6 +108,7 @@ extern "C" int mvx_branchAndBound_dist(const mvx_lp_api *api, const mvx_image_ap
   if (prm.rc_fix != 0) return MVX_EFAIL; // reduced-cost tightening is not carried to several ranks yet either
   if (prm.prop != 0) return MVX_EFAIL;   // nor is node bound propagation
   if (prm.dive != 0) return MVX_EFAIL;   // nor are the dives
+  if (prm.pump != 0) return MVX_EFAIL;   // nor are the pumps
   const int rank = comm ? comm->rank : 0, world = comm ? comm->size : 1;
   const int per_rank = dp.per_rank;
   const int slack = dp.slack >= 0 ? dp.slack : std::max(1, per_rank / 4);

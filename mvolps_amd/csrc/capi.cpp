@@ -531,6 +531,11 @@ int mvx_dive_pick_many(const mvx_prob *root, const mvx_prob *const *Ps, int coun
                        double *val) {
   return mvx::engine_dive_pick_many(root, Ps, count, rules, nfrac, col, dir, val);
 }
+int mvx_set_obj_many(mvx_prob *const *Ps, int count, const double *c) { return mvx::engine_set_obj_many(Ps, count, c); }
+int mvx_pump_obj_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, const double *xprev, const int *has_prev,
+                      const double *ab, int *info, double *xt, double *c) {
+  return mvx::engine_pump_obj_many(root, Ps, count, xprev, has_prev, ab, info, xt, c);
+}
 
 int mvx_device_count(void) { return mvx::device_count(); }
 int mvx_set_device(int dev) { return mvx::set_device(dev); }

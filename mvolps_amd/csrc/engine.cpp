@@ -2696,6 +2696,134 @@ int engine_dive_pick_many(const mvx_prob *root, const mvx_prob *const *Ps, int c
   return 0;
 }
 
+// ------------------------------------------------------------------ objective replacement (k_objrow)
+// The whole objective of `count` handles replaced (mvx_set_obj_many): handle t takes c[t*(n+1) .. ], and where it has a valid
+// tableau its row 0 is rebuilt -- the weights and the base of engine_recompute_cost_row for every handle staged in the one
+// pinned block of the call, one upload, one k_objrow launch for all of them.  Each handle is left as n + 1 mvx_set_obj_coef
+// calls leave it; pending bound edits stay pending, as they do there.  Return codes: 0; -1 bad arguments (a null, count < 0,
+// another column count, a handle listed twice); -2 device out of memory, nothing changed.
+int engine_set_obj_many(mvx_prob *const *Ps, int count, const double *c) {
+  if (count < 0 || (count > 0 && (!Ps || !c))) return -1;
+  if (count == 0) return 0;
+  for (int t = 0; t < count; t++)
+    if (!Ps[t] || Ps[t]->n != Ps[0]->n) return -1;
+  {
+    std::vector<const mvx_prob *> seen(Ps, Ps + count);
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return -1;
+  }
+  const int n = Ps[0]->n;
+  const size_t row = (size_t)n + 1;
+  auto take = [&](int t) {
+    mvx_prob *P = Ps[t];
+    P->c.assign(c + (size_t)t * row, c + (size_t)(t + 1) * row);
+    P->status = MVX_UNDEF;
+  };
+  std::vector<int> live;
+  for (int t = 0; t < count; t++)
+    if (Ps[t]->valid) live.push_back(t);
+  if (live.empty()) {
+    for (int t = 0; t < count; t++) take(t);
+    return 0;
+  }
+  NodeCall f(NodeFlush::AtEntry, NodeResults::None);
+  // up: [descriptors][w, base of each handle with a tableau]
+  const size_t o_nodes = f.up(live.size() * sizeof(ObjNode));
+  std::vector<size_t> o_w(live.size()), o_base(live.size());
+  for (size_t k = 0; k < live.size(); k++) {
+    o_w[k] = f.up((size_t)(Ps[live[k]]->m + 1) * 8);
+    o_base[k] = f.up(row * 8);
+  }
+  if (!f.reserve()) return -2;
+  for (int t = 0; t < count; t++) take(t);
+  unsigned char *hb = f.hb, *db = f.db;
+  ObjNode *h_nodes = (ObjNode *)(hb + o_nodes);
+  for (size_t k = 0; k < live.size(); k++) {
+    mvx_prob *P = Ps[live[k]];
+    const int m = P->m;
+    double *w = (double *)(hb + o_w[k]), *base = (double *)(hb + o_base[k]);
+    w[0] = 0.0;
+    for (int i = 1; i <= m; i++) w[i] = (P->bvar[i] > m) ? P->c[P->bvar[i] - m] : 0.0;
+    double z = P->c[0];
+    for (int j = 1; j <= n; j++) {
+      const int v = P->nvar[j];
+      const double cj = (v > m) ? P->c[v - m] : 0.0;
+      double lb, ub;
+      var_bounds(P, v, &lb, &ub);
+      const double x = nb_value(P->nflag[j], lb, ub);
+      base[j] = cj;
+      if (x != 0.0 && cj != 0.0) z = std::fma(cj, x, z);
+    }
+    base[0] = z;
+    h_nodes[k] = ObjNode{P->d_T, (const double *)(db + o_w[k]), (const double *)(db + o_base[k]), m, P->ld};
+    P->sol_fresh = false;
+    P->fresh_rows = -1;
+  }
+  f.upload();
+  launch_objrow((const ObjNode *)(db + o_nodes), n, (int)live.size(), f.stream());
+  f.fetch(); // the pinned block is free again
+  return 0;
+}
+
+// ------------------------------------------------------------------ feasibility pump: rounding and objective (k_pumpobj)
+// The rounding and the distance objective of `count` solved handles against root's model (mvx_pump_obj_many): one upload of
+// the descriptors, the last roundings and the table of square roots, one k_pumpobj launch, one copy back.  ab[t] = (a, q):
+// c_j = a * (-sg * d_j) + (q * sqrt(nnz(d))) * c0_j.  Return codes: 0; -1 bad arguments; -2 device out of memory; -3 a handle
+// whose status is not MVX_OPT; -5 n > RND_NMAX, as for engine_round_many, whose model it shares.
+int engine_pump_obj_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, const double *xprev, const int *has_prev,
+                         const double *ab, int *info, double *xt, double *c) {
+  if (!root || count < 1 || !Ps || !has_prev || !ab || !info || !xt || !c) return -1;
+  const int n = root->n;
+  for (int t = 0; t < count; t++)
+    if (!Ps[t] || Ps[t]->n != n || (has_prev[t] && !xprev)) return -1;
+  if (n > RND_NMAX) return -5;
+  for (int t = 0; t < count; t++)
+    if (!Ps[t]->valid || Ps[t]->status != MVX_OPT) return -3;
+  NodeCall f(NodeFlush::AtEntry, NodeResults::Device);
+  const RoundModel *M = round_model(*f.c, root);
+  if (!M) return -2;
+  // up: [descriptors][sqrt table][xprev]; back: [info][xt][c]; device only: [v][lo][hi]
+  const size_t row = (size_t)n + 1, all = (size_t)count * row * 8;
+  const size_t o_nodes = f.up((size_t)count * sizeof(PumpNode)), o_sq = f.up(row * 8), o_xp = f.up(all);
+  const size_t o_info = f.out((size_t)count * 4 * 4), o_xt = f.out(all), o_c = f.out(all);
+  const size_t o_v = f.dev(all), o_lo = f.dev(all), o_hi = f.dev(all);
+  if (!f.reserve()) return -2;
+  unsigned char *hb = f.hb, *db = f.db;
+  PumpNode *h_nodes = (PumpNode *)(hb + o_nodes);
+  for (int t = 0; t < count; t++) {
+    const mvx_prob *P = Ps[t];
+    PumpNode nd;
+    static_cast<NodeRef &>(nd) = node_ref(P);
+    nd.blb = P->d_blb; nd.bub = P->d_bub;
+    nd.sg = P->dir == MVX_MIN ? -1.0 : 1.0;
+    nd.a = ab[2 * (size_t)t]; nd.q = ab[2 * (size_t)t + 1];
+    nd.has_prev = has_prev[t] ? 1 : 0; nd.pad = 0;
+    h_nodes[t] = nd;
+    double *xp = (double *)(hb + o_xp) + (size_t)t * row;
+    if (has_prev[t]) std::memcpy(xp, xprev + (size_t)t * row, row * 8);
+    else std::memset(xp, 0, row * 8);
+  }
+  double *sq = (double *)(hb + o_sq);
+  for (int k = 0; k <= n; k++) sq[k] = std::sqrt((double)k);
+  f.upload();
+  const unsigned char *mb = (const unsigned char *)M->dev;
+  PumpArgs a;
+  a.nodes = (const PumpNode *)(db + o_nodes);
+  a.c0 = (const double *)(mb + M->o_c);
+  a.flags = (const int *)(mb + M->o_flags);
+  a.xprev = (const double *)(db + o_xp);
+  a.sq = (const double *)(db + o_sq);
+  a.v = (double *)(db + o_v); a.lo = (double *)(db + o_lo); a.hi = (double *)(db + o_hi);
+  a.info = (int *)(db + o_info); a.xt = (double *)(db + o_xt); a.c = (double *)(db + o_c);
+  a.n = n; a.count = count;
+  launch_pumpobj(a, f.stream());
+  f.fetch();
+  std::memcpy(info, hb + o_info, (size_t)count * 4 * 4);
+  std::memcpy(xt, hb + o_xt, all);
+  std::memcpy(c, hb + o_c, all);
+  return 0;
+}
+
 // ------------------------------------------------------------------ node bound propagation (k_prop, k_setbnds)
 // The second orientation of root's rounding model, rows 1..m0 by row (Ar[i][j]), next to the first: k_prop's column phase
 // reads a row of consecutive columns at a time.  Built on the first propagation over this model.

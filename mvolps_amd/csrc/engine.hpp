@@ -43,6 +43,11 @@ int engine_round_many(const mvx_prob *root, const mvx_prob *const *Ps, int count
 // the diving heuristic's branching pick for `count` (solved handle, rule) pairs against root's model, one launch (k_divepick)
 int engine_dive_pick_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, const int *rules, int *nfrac, int *col, int *dir,
                           double *val);
+// the whole objective of `count` handles replaced, rows 0 rebuilt in one launch (k_objrow); the feasibility pump's rounding and
+// distance objective for `count` solved handles against root's model, one launch (k_pumpobj); see engine.cpp
+int engine_set_obj_many(mvx_prob *const *Ps, int count, const double *c);
+int engine_pump_obj_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, const double *xprev, const int *has_prev,
+                         const double *ab, int *info, double *xt, double *c);
 // reduced-cost bound tightening of `count` solved handles, one launch (k_rcfix), and the bound lists of many handles applied
 // with one launch (k_setbnds, entries on non-basic positions only); see engine.cpp
 int engine_rc_tighten_many(const mvx_prob *const *Ps, int count, const double *cutoff, double tol, int *cnt, int *cols, double *lb,

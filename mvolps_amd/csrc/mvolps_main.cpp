@@ -73,6 +73,11 @@ int main(int argc, char **argv) {
               << "                  (1 fractional, 2 locks, 4 vector length; 7 without a number); a better point becomes the incumbent\n"
               << "  --dive-freq F   with --dive: also dive at every branching node whose number F divides (default 0: the root only)\n"
               << "  --dive-depth D  with --dive: step limit of one dive (default 0: 4 n + 64)\n"
+              << "  --pump [N]      with --repaired (not with --best-window): feasibility pump at the root, at most N distance LPs\n"
+              << "                  (1..1000; 30 without a number), in front of the dives; a better point becomes the incumbent\n"
+              << "  --pump-freq F   with --pump: also pump at every branching node whose number F divides (default 0: the root only)\n"
+              << "  --pump-alpha A  with --pump: weight of the model's objective in the first distance LP (0..1, default 0; times 0.9\n"
+              << "                  with every further LP)\n"
               << "Help:\n  -h/--help\n";
     return 0;
   }
@@ -157,6 +162,27 @@ int main(int argc, char **argv) {
   }
   if (!int_opt("--dive-freq", 0, 1 << 30, &params.dive_freq)) return -1;
   if (!int_opt("--dive-depth", 0, 1 << 30, &params.dive_depth)) return -1;
+  if (input.CMDOptionExists("--pump")) {
+    // the number is optional, as for --prop
+    const std::string &k = input.getCMDOption("--pump");
+    const bool numeric = !k.empty() && std::all_of(k.begin(), k.end(), [](char ch) { return ch >= '0' && ch <= '9'; });
+    const long kv = numeric ? std::strtol(k.c_str(), nullptr, 10) : 30;
+    params.pump = kv >= 1 && kv <= 1000 ? (int)kv : -1;
+    if (params.pump < 1) {
+      std::fprintf(stderr, "Unknown parameter value for --pump\n");
+      return -1;
+    }
+  }
+  if (!int_opt("--pump-freq", 0, 1 << 30, &params.pump_freq)) return -1;
+  if (input.CMDOptionExists("--pump-alpha")) {
+    char *end = nullptr;
+    const std::string &k = input.getCMDOption("--pump-alpha");
+    params.pump_alpha = std::strtod(k.c_str(), &end);
+    if (k.empty() || *end != 0 || !(params.pump_alpha >= 0.0 && params.pump_alpha <= 1.0)) {
+      std::fprintf(stderr, "Unknown parameter value for --pump-alpha\n");
+      return -1;
+    }
+  }
   if (input.CMDOptionExists("--cut-select")) params.cut_select = std::atoi(input.getCMDOption("--cut-select").c_str());
   if (input.CMDOptionExists("--window")) params.window = std::atoi(input.getCMDOption("--window").c_str());
   if (input.CMDOptionExists("--best-window")) params.best_window = std::atoi(input.getCMDOption("--best-window").c_str());
@@ -167,14 +193,15 @@ int main(int argc, char **argv) {
   mvx_bnb_result res;
   const int brc = mvx_branchAndBound(nullptr, prob, &params, &res);
   if (brc == -1) {
-    std::fprintf(stderr, "-vs %d / --heur %d%s%s%s are not supported with these options (-vs 3 / 4: not with --best-window; --heur: only "
-                 "with --repaired; --rcfix / --prop / --dive: only with --repaired and without --best-window)\n", params.var_strat,
-                 params.heur, params.rc_fix ? " / --rcfix" : "", params.prop ? " / --prop" : "", params.dive ? " / --dive" : "");
+    std::fprintf(stderr, "-vs %d / --heur %d%s%s%s%s are not supported with these options (-vs 3 / 4: not with --best-window; --heur: only "
+                 "with --repaired; --rcfix / --prop / --dive / --pump: only with --repaired and without --best-window)\n", params.var_strat,
+                 params.heur, params.rc_fix ? " / --rcfix" : "", params.prop ? " / --prop" : "", params.dive ? " / --dive" : "",
+                 params.pump ? " / --pump" : "");
     mvx_delete_prob(prob);
     return -1;
   }
   if (brc != 0)
-    std::fprintf(stderr, "branch-and-bound stopped: the branching penalties, the heuristic, the propagation or a dive could not be computed (%d)\n", brc);
+    std::fprintf(stderr, "branch-and-bound stopped: the branching penalties, the heuristic, the propagation, a pump or a dive could not be computed (%d)\n", brc);
   if (input.CMDOptionExists("--events")) mvx_bnb_write_events(&res, input.getCMDOption("--events").c_str());
   mvx_bnb_print_tree(&res, nullptr); // bs.cpp:329-343
   std::vector<char> buf(64 + 64 * (size_t)res.n);
@@ -194,6 +221,10 @@ int main(int argc, char **argv) {
     std::printf("Diving: %lld nodes, %lld with a feasible point, %lld improved the incumbent, %lld child LPs, %lld pivots%s\n", res.dive_calls,
                 res.dive_found, res.dive_improved, res.dive_lps, res.dive_pivots,
                 res.incumbent_heur == 2 ? " (the final incumbent is one of them)" : "");
+  if (verbose && params.pump > 0)
+    std::printf("Feasibility pump: %lld nodes, %lld with a feasible point, %lld improved the incumbent, %lld distance LPs, %lld pivots%s\n",
+                res.pump_calls, res.pump_found, res.pump_improved, res.pump_lps, res.pump_pivots,
+                res.incumbent_heur == 3 ? " (the final incumbent is one of them)" : "");
   const int limit = res.hit_limit || brc != 0;
   mvx_bnb_free_result(&res);
   mvx_delete_prob(prob);

@@ -339,6 +339,39 @@ struct DiveArgs {
   int n, count;
 };
 
+// one handle of an objective-row launch (k_objrow, mvx_set_obj_many): its tableau, the weights of its rows (the new cost of each
+// row's basic variable, 0 for an auxiliary) and the base of its row 0 (base[0] the constant z, base[q] the new cost of the
+// variable at non-basic position q), both in the call's upload
+struct ObjNode {
+  double *T;
+  const double *w;    // [m+1]
+  const double *base; // [n+1]
+  int m, ld;
+};
+#define OBJ_COLS 64 // columns per k_objrow workgroup (one per lane; its four waves take a row chunk each)
+
+// one handle of a pump-objective launch (k_pumpobj, mvx_pump_obj_many): the handle, the bounds of its basic variables by
+// tableau row, its direction, the weights (a, q) of its new objective and whether xprev holds its last rounding
+struct PumpNode : NodeRef {
+  const double *blb, *bub; // [m+1]
+  double sg, a, q;         // +1 maximise / -1 minimise; c_j = a * (-sg * d_j) + (q * sqrt(nnz(d))) * c0_j
+  int has_prev, pad;
+};
+#define PUMP_MOVES 10 // columns a stalled rounding moves
+
+// arguments of k_pumpobj: `count` solved handles over the model of one root (k_round's copy: objective and RND_INT flags)
+struct PumpArgs {
+  const PumpNode *nodes; // [count]
+  const double *c0;      // [n+1] the root's objective
+  const int *flags;      // [n+1] RND_* bits
+  const double *xprev;   // [count][n+1] the last roundings (read where has_prev is set)
+  const double *sq;      // [n+1] sqrt(k), k = 0..n, from the host
+  double *v, *lo, *hi;   // [count][n+1] scratch: column values and clamped bounds
+  int *info;             // [count][4]: nfrac, moved, stalled, nnz(d)
+  double *xt, *c;        // [count][n+1] the rounding and the new objective
+  int n, count;
+};
+
 // k_setbnds (mvx_set_col_bnds_many, mvx_tighten_cols_many): per handle a range of bound writes and a range of shifts of column 0
 struct SetbHandle {
   double *T, *blb, *bub, *nlb, *nub;
@@ -390,6 +423,8 @@ void launch_round(const RndArgs &a, hipStream_t);
 void launch_rcfix(const RcArgs &a, hipStream_t);
 void launch_prop(const PropArgs &a, hipStream_t);
 void launch_divepick(const DiveArgs &a, hipStream_t);
+void launch_objrow(const ObjNode *nodes, int n, int count, hipStream_t);
+void launch_pumpobj(const PumpArgs &a, hipStream_t);
 void launch_setbnds(const SetbHandle *hs, const SetbEntry *es, const SetbShift *ss, int handles, hipStream_t);
 void launch_refresh_select(Ctl *, const int *tflag, int var, hipStream_t);
 size_t persist_lds_bytes(int m, int cpw);

@@ -1,6 +1,6 @@
 // node_kernels.hip -- gfx950 kernels of the batched node entries of branch and bound (engine.cpp: engine_*_many): GMI cuts,
-// classification, branching penalties, the rounding heuristic, reduced-cost tightening, bound propagation, bound lists and the
-// diving pick.  Each takes its arguments by value and the handles it works on as an array of descriptors (NodeRef and what
+// classification, branching penalties, the rounding heuristic, reduced-cost tightening, bound propagation, bound lists, the
+// diving pick, objective replacement and the feasibility pump's step.  Each takes its arguments by value and the handles it works on as an array of descriptors (NodeRef and what
 // the kernel needs beyond it, mvx_internal.hpp).  Same flags as kernels.hip: -ffp-contract=off, so every kernel has the bits
 // of its host twin.
 #include <hip/hip_runtime.h>
@@ -828,6 +828,192 @@ __global__ __launch_bounds__(256) void k_divepick(DiveArgs a) {
 
 void launch_divepick(const DiveArgs &a, hipStream_t s) {
   hipLaunchKernelGGL(k_divepick, dim3((unsigned)a.count), dim3(256), 0, s, a);
+}
+
+// ---------------------------------------------------------------------------- k_objrow
+// Row 0 of many tableaux under a new objective (mvx_set_obj_many, DESIGN.md "Feasibility pump"): T[0][j] = base[j] + the sum
+// over 64-row chunks, in chunk order, of the fma chain sum_i w[i] * T[i][j] over the chunk's rows in ascending order, rows of
+// weight zero skipped -- the arithmetic of k_rowcomb_partial / k_rowcomb_final, without part[] and the second launch.  One
+// workgroup per (64 columns, handle): a lane owns a column, the four waves take one chunk each, their partials meet in LDS
+// and wave 0 adds them in chunk order.  Rows 1..m are only read and row 0 only written, so the workgroups of a handle do not
+// depend on each other.
+__global__ __launch_bounds__(256) void k_objrow(const ObjNode *nodes, int n) {
+  __shared__ double s_part[4][OBJ_COLS];
+  const ObjNode nd = nodes[blockIdx.y];
+  const int lane = TIDX & 63, wv = TIDX >> 6;
+  const int j = (int)blockIdx.x * OBJ_COLS + lane;
+  const bool live = j <= n;
+  const int m = nd.m;
+  const size_t ld = (size_t)nd.ld;
+  const int nchunks = (m + ROWCOMB_CHUNK - 1) / ROWCOMB_CHUNK;
+  double out = (wv == 0 && live) ? nd.base[j] : 0.0;
+  for (int g = 0; g < nchunks; g += 4) {
+    const int ch = g + wv;
+    double acc = 0.0;
+    if (ch < nchunks && live) {
+      const int i0 = 1 + ch * ROWCOMB_CHUNK;
+      int i1 = i0 + ROWCOMB_CHUNK - 1;
+      if (i1 > m) i1 = m;
+      for (int i = i0; i <= i1; i++) {
+        const double w = nd.w[i];
+        if (w != 0.0) acc = fma(w, nd.T[(size_t)i * ld + j], acc);
+      }
+    }
+    s_part[wv][lane] = acc;
+    __syncthreads();
+    if (wv == 0) {
+      const int k1 = nchunks - g < 4 ? nchunks - g : 4;
+      for (int k = 0; k < k1; k++) out = out + s_part[k][lane];
+    }
+    __syncthreads();
+  }
+  if (wv == 0 && live) nd.T[j] = out;
+}
+
+void launch_objrow(const ObjNode *nodes, int n, int count, hipStream_t s) {
+  hipLaunchKernelGGL(k_objrow, dim3((unsigned)((n + 1 + OBJ_COLS - 1) / OBJ_COLS), (unsigned)count), dim3(256), 0, s, nodes, n);
+}
+
+// ---------------------------------------------------------------------------- k_pumpobj
+// The feasibility pump's rounding and distance objective (mvx_pump_obj_many, DESIGN.md "Feasibility pump"), one workgroup per
+// solved handle.  The walk is k_divepick's -- a lane over the tableau rows takes a basic structural column's value from
+// column 0 and its bounds from the row's bound arrays, a lane over the non-basic positions the bound the status names and
+// the position's bounds -- and rounds the column on the spot.  A rounding that repeats the last one moves the (at most)
+// PUMP_MOVES movable columns that lie farthest from their LP value, found by successive arg-max reductions under the strict
+// total key (distance descending, column ascending): the result does not depend on the reduction tree.  Then the slopes, their
+// count, and the objective; every operation is rounded on its own (-ffp-contract=off) and sqrt comes from the host's table, so
+// the bits are the host twin's.  No atomics.
+__device__ __forceinline__ int pump_block_sum(int x, int *s4) {
+  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+  __syncthreads(); // the readers of the last sum are done with s4
+  if ((TIDX & 63) == 0) s4[TIDX >> 6] = x;
+  __syncthreads();
+  return s4[0] + s4[1] + s4[2] + s4[3];
+}
+
+__global__ __launch_bounds__(256) void k_pumpobj(PumpArgs a) {
+  __shared__ double s_sig[RND_NMAX + 1]; // the movable columns' distances, then the slopes
+  __shared__ double s_bk[4];
+  __shared__ int s_bj[4], s_sum[4], s_win;
+  const int t = (int)blockIdx.x;
+  const PumpNode nd = a.nodes[t];
+  const int n = a.n, m = nd.m;
+  const size_t o = (size_t)t * (size_t)(n + 1);
+  double *v = a.v + o, *lo = a.lo + o, *hi = a.hi + o, *xt = a.xt + o, *c = a.c + o;
+  const double *xp = a.xprev + o;
+  int nfrac = 0, differs = 0;
+  auto column = [&](int j, double vj, double l, double u) {
+    double x = 0.0, L = 0.0, U = 0.0;
+    if (a.flags[j] & RND_INT) {
+      if (fabs(vj - rint(vj)) > 1e-9) nfrac++;
+      L = ceil(l);
+      U = floor(u);
+      x = floor(vj + 0.5); // k_round's nearest integer
+      if (x < L) x = L;
+      if (x > U) x = U;
+      if (nd.has_prev && x != xp[j]) differs = 1;
+    }
+    v[j] = vj; lo[j] = L; hi[j] = U; xt[j] = x;
+  };
+  for (int i = 1 + TIDX; i <= m; i += 256) {
+    const int k = nd.bvar[i];
+    if (k > m && k <= m + n) column(k - m, nd.T[(size_t)i * (size_t)nd.ld], nd.blb[i], nd.bub[i]);
+  }
+  for (int q = 1 + TIDX; q <= n; q += 256) {
+    const int k = nd.nvar[q];
+    if (k > m && k <= m + n) column(k - m, dev_nb_value(nd.nflag[q], nd.nlb[q], nd.nub[q]), nd.nlb[q], nd.nub[q]);
+  }
+  nfrac = pump_block_sum(nfrac, s_sum);
+  differs = pump_block_sum(differs, s_sum);
+  const bool stall = nd.has_prev && differs == 0;
+  int moved = 0;
+  if (stall) { // uniform over the workgroup
+    for (int j = 1 + TIDX; j <= n; j += 256) {
+      double sig = -1.0;
+      if (a.flags[j] & RND_INT) {
+        const double d = v[j] - xt[j], sd = fabs(d);
+        if (sd > 0.0) {
+          const double xn = xt[j] + (d > 0.0 ? 1.0 : -1.0);
+          if (xn >= lo[j] && xn <= hi[j]) sig = sd;
+        }
+      }
+      s_sig[j] = sig;
+    }
+    __syncthreads();
+    for (int r = 0; r < PUMP_MOVES; r++) {
+      double bk = 0.0;
+      int bj = 0x7fffffff;
+      for (int j = 1 + TIDX; j <= n; j += 256) {
+        const double sg = s_sig[j];
+        if (sg > 0.0 && (sg > bk || (sg == bk && j < bj))) {
+          bk = sg;
+          bj = j;
+        }
+      }
+      for (int off = 32; off > 0; off >>= 1) {
+        const double ok = __shfl_xor(bk, off, 64);
+        const int oj = __shfl_xor(bj, off, 64);
+        if (ok > bk || (ok == bk && oj < bj)) {
+          bk = ok;
+          bj = oj;
+        }
+      }
+      if ((TIDX & 63) == 0) {
+        s_bk[TIDX >> 6] = bk;
+        s_bj[TIDX >> 6] = bj;
+      }
+      __syncthreads();
+      if (TIDX == 0) {
+        for (int w = 1; w < 4; w++)
+          if (s_bk[w] > bk || (s_bk[w] == bk && s_bj[w] < bj)) {
+            bk = s_bk[w];
+            bj = s_bj[w];
+          }
+        const int win = bj != 0x7fffffff ? bj : 0;
+        if (win) {
+          xt[win] = xt[win] + (v[win] - xt[win] > 0.0 ? 1.0 : -1.0);
+          s_sig[win] = -1.0;
+        }
+        s_win = win;
+      }
+      __syncthreads();
+      if (s_win == 0) break; // uniform
+      moved++;
+    }
+    __syncthreads(); // xt of the moved columns, s_sig before it is reused
+  }
+  int nnz = 0;
+  for (int j = 1 + TIDX; j <= n; j += 256) {
+    double d = 0.0;
+    if (a.flags[j] & RND_INT) {
+      const double L = lo[j], U = hi[j], x = xt[j];
+      if (L == U) d = 0.0;
+      else if (x == L) d = 1.0;
+      else if (x == U) d = -1.0;
+      else {
+        const double df = v[j] - x;
+        d = df > 0.0 ? 1.0 : df < 0.0 ? -1.0 : 0.0;
+      }
+    }
+    s_sig[j] = d;
+    if (d != 0.0) nnz++;
+  }
+  nnz = pump_block_sum(nnz, s_sum);
+  const double b = nd.q * a.sq[nnz];
+  for (int j = 1 + TIDX; j <= n; j += 256) c[j] = (nd.a * (-nd.sg * s_sig[j])) + (b * a.c0[j]);
+  if (TIDX == 0) {
+    c[0] = 0.0;
+    xt[0] = 0.0;
+    int *info = a.info + 4 * (size_t)t;
+    info[0] = nfrac;
+    info[1] = moved;
+    info[2] = (stall && moved == 0) ? 1 : 0;
+    info[3] = nnz;
+  }
+}
+
+void launch_pumpobj(const PumpArgs &a, hipStream_t s) {
+  hipLaunchKernelGGL(k_pumpobj, dim3((unsigned)a.count), dim3(256), 0, s, a);
 }
 
 } // namespace mvx
