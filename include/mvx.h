@@ -245,6 +245,19 @@ int mvx_set_obj_many(mvx_prob *const *Ps, int count, const double *c);
    MVX_OPT; -5 n > 4096, as for mvx_round_many, whose model it shares. */
 int mvx_pump_obj_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, const double *xprev, const int *has_prev,
                       const double *ab, int *info, double *xt, double *c);
+/* Root cut rounds (DESIGN.md "Root cut rounds"): the scores of `k` candidate cut rows against a solved handle, one device
+   launch (k_cutgram).  vals is k x (n+1) in the layout of mvx_gmi_cuts (entry 0 of a row is not read).  dot[t] = sum_j v_tj x_j
+   with x the handle's column values (the bits mvx_get_col_prim returns), gram[t*k + s] = sum_j v_tj v_sj; every sum runs over
+   ascending j from +0.0, product and sum rounded separately.  gram is exactly symmetric.  Pure: the handle does not change.
+   Bit-identical to mvx_bnb_cut_scores (mvx_bnb.h).  Returns 0; -1 bad arguments or a handle that is not MVX_OPT; -2 device
+   out of memory. */
+int mvx_cut_scores(const mvx_prob *P, int k, const double *vals, double *dot, double *gram);
+/* `k` dense MVX_LO rows appended in one device pass (k_cutrows): row t has the coefficients vals[t*(n+1) + 1 .. n] and the
+   lower bound rhs[t].  The handle is left, bit for bit, as k times (mvx_add_rows(P, 1), mvx_set_mat_row with all n indices,
+   mvx_set_row_bnds(MVX_LO)) in list order leave it: model, tableau, basis, bounds, status MVX_UNDEF, and a dual warm start
+   for the next solve.  Returns 0; -1 bad arguments, nothing changed (k < 1, a null, a NaN, a handle without a valid tableau);
+   -2 device out of memory: the model has the rows, the tableau is given up as mvx_add_rows gives it up. */
+int mvx_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rhs);
 
 /* ---- engine-state access (parity tests, visualisers) --------------------------- */
 int mvx_get_tableau_ld(const mvx_prob *P);

@@ -113,6 +113,13 @@ typedef struct mvx_lp_api {
      columns than the kernel holds), the host twin mvx_bnb_pump_obj runs */
   int (*pump_obj_many)(const void *root, const void *const *Ps, int count, const double *xprev, const int *has_prev, const double *ab,
                        int *info, double *xt, double *c);
+  /* optional (may be NULL): the scores of `k` candidate cut rows against a solved handle in one call (mvx_cut_scores; DESIGN.md
+     "Root cut rounds"): dot[t] against the column values and the k x k Gram matrix; without it the host twin mvx_bnb_cut_scores
+     runs */
+  int (*cut_scores)(const void *P, int k, const double *vals, double *dot, double *gram);
+  /* optional (may be NULL): `k` dense MVX_LO rows appended in one call (mvx_add_cut_rows), the handle left as k times add_rows(1),
+     set_mat_row, set_row_bnds leave it; without it the root cut loop appends row by row */
+  int (*add_cut_rows)(void *P, int k, const double *vals, const double *rhs);
 } mvx_lp_api;
 
 const mvx_lp_api *mvx_hip_lp_api(void);
@@ -175,6 +182,13 @@ typedef struct {
   int pump_freq;        /* 0 (default): the root only; F > 0: also every branching node with oid % F == 0 */
   double pump_alpha;    /* 0 (default) the plain pump; up to 1: the weight of the root's objective in the first distance LP, times
                            0.9 with every further one */
+  int cut_rounds;       /* root cut rounds (DESIGN.md "Root cut rounds"): 0 off (default), 1..64 the rounds of GMI cuts the root LP
+                           takes before the tree starts: per round the repaired cuts of all fractional basic integer columns,
+                           ranked by efficacy, filtered by pairwise parallelism and appended together.  Needs reference_quirks = 0;
+                           the tree then runs on a copy of the caller's handle.  Independent of cut_strat */
+  int cut_round_max;    /* most cuts one round appends, 0..4096; 0 (default): 32 */
+  double cut_maxpar;    /* a cut is taken when its cosine to every cut already taken in the round is at most this, in (0, 1];
+                           0.0 (default): 0.9.  With cut_rounds = 0 neither this nor cut_round_max is read */
 } mvx_bnb_params;
 
 /* B&B events at the emit points of bs.cpp (message.h EventType) */
@@ -234,6 +248,13 @@ typedef struct {
   long long pump_improved; /* ... of which the point became the incumbent */
   long long pump_lps;      /* distance LPs the pumps solved */
   long long pump_pivots;   /* their pivots (not part of total_pivots) */
+  long long cutloop_rounds;     /* cut_rounds > 0: rounds that appended cuts and re-solved */
+  long long cutloop_candidates; /* ... cuts made for them (one per fractional basic integer column that yields a cut) */
+  long long cutloop_rows;       /* ... rows appended */
+  long long cutloop_lps;        /* ... LPs solved: the root's first solve and one per round */
+  long long cutloop_pivots;     /* their pivots (not part of total_pivots; the root's own LP is among them) */
+  double cutloop_bound0;        /* the root LP before the loop */
+  double cutloop_bound;         /* the root LP after it (the last one that ended optimal) */
 } mvx_bnb_result;
 
 void mvx_bnb_default_params(mvx_bnb_params *p);
@@ -359,6 +380,25 @@ int mvx_bnb_pump_obj(const mvx_lp_api *api, const void *prob, const void *root, 
    carried out */
 int mvx_bnb_pump(const mvx_lp_api *api, const void *prob, const void *root, int iters, double alpha, double *obj, int *found, double *x,
                  long long *lps, long long *pivots, int *end);
+
+/* Root cut rounds (DESIGN.md "Root cut rounds"), host twin of mvx_cut_scores through the table (get_col_prim, get_num_cols,
+   get_status): dot[t] = sum_j vals[t][j] * x_j and gram[t*k + s] = sum_j vals[t][j] * vals[s][j] over ascending j = 1..n from
+   +0.0, product and sum rounded separately.  Returns 0; -1 bad arguments or a handle that is not MVX_OPT */
+int mvx_bnb_cut_scores(const mvx_lp_api *api, const void *prob, int k, const double *vals, double *dot, double *gram);
+/* The selection of one round, from numbers only: the k cuts are walked by efficacy descending (ties to the lower index) and cut
+   t is taken when gram[t][s] <= maxpar * (sqrt(gram[t][t]) * sqrt(gram[s][s])) for every cut s already taken, until K are
+   taken or `budget` are.  taken[0 .. *ntaken - 1] the indices in taken order (room for min(k, K) entries).  Returns 0; -1 bad
+   arguments (k < 0, K < 1, maxpar outside (0, 1], budget < 0, a null) */
+int mvx_bnb_cut_select(int k, const double *eff, const double *gram, int K, double maxpar, int budget, int *taken, int *ntaken);
+/* The whole loop on the handle `prob`, which is edited in place: solved with the default parameters, then up to `rounds`
+   (1..64) rounds of candidates, scores, selection, append and re-solve with at most K (0: 32) cuts a round and the parallelism
+   limit maxpar (0.0: 0.9); the row budget is max(64, rows of `prob` at entry).  Uses gmi_cuts, cut_scores and add_cut_rows
+   where the table has them, mvx_generateCutGMI, the twins and the per-row appends otherwise.  counters[0..4] = rounds, cuts
+   made, rows appended, LPs solved, their pivots; bounds[0..1] = the LP before the loop and after it.  Returns 0; -1 bad
+   arguments; -2 the table lacks an accessor, or a call of the table failed.  mvx_branchAndBound returns -1 (*res empty) for
+   cut_rounds outside 0..64, cut_round_max outside 0..4096, cut_maxpar outside (0, 1] other than 0.0 and cut_rounds > 0 with
+   reference_quirks = 1, and -2, with the unsolved root as the tree, when the loop could not be carried out */
+int mvx_bnb_cut_loop(const mvx_lp_api *api, void *prob, int rounds, int K, double maxpar, long long *counters, double *bounds);
 
 /* bs.cpp:249-258 on one solved node `a` that is about to be branched: generate its GMI cut(s) and append the
    row(s) (cut_strat / reference_quirks / lazy_pool / cut_select / cut_chance of `params`).  Returns the number

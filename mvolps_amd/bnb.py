@@ -16,7 +16,7 @@ _FIELDS = [
 ]
 _OPTIONAL = ["simplex_batch", "get_obj_dir", "gmi_cuts", "gmi_cuts_many", "get_col_prim_all", "classify_many", "get_tableau", "get_basis",
              "branch_penalties_many", "round_many", "rc_tighten_many", "tighten_cols_many", "propagate_many", "set_col_bnds_many",
-             "dive_pick_many", "set_obj_coef", "set_obj_many", "pump_obj_many"]
+             "dive_pick_many", "set_obj_coef", "set_obj_many", "pump_obj_many", "cut_scores", "add_cut_rows"]
 
 
 class LpApiTable(C.Structure):
@@ -49,6 +49,9 @@ class BnbParams(C.Structure):
         ("pump", C.c_int),
         ("pump_freq", C.c_int),
         ("pump_alpha", C.c_double),
+        ("cut_rounds", C.c_int),
+        ("cut_round_max", C.c_int),
+        ("cut_maxpar", C.c_double),
     ]
 
 
@@ -106,6 +109,13 @@ class BnbResult(C.Structure):
         ("pump_improved", C.c_longlong),
         ("pump_lps", C.c_longlong),
         ("pump_pivots", C.c_longlong),
+        ("cutloop_rounds", C.c_longlong),
+        ("cutloop_candidates", C.c_longlong),
+        ("cutloop_rows", C.c_longlong),
+        ("cutloop_lps", C.c_longlong),
+        ("cutloop_pivots", C.c_longlong),
+        ("cutloop_bound0", C.c_double),
+        ("cutloop_bound", C.c_double),
     ]
 
 
@@ -181,6 +191,18 @@ def _bind(lib):
     lib.mvx_bnb_pump.restype = C.c_int
     lib.mvx_bnb_pump.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, _DP, _IP, _DP, C.POINTER(C.c_longlong),
                                  C.POINTER(C.c_longlong), _IP]
+    lib.mvx_cut_scores.restype = C.c_int
+    lib.mvx_cut_scores.argtypes = [C.c_void_p, C.c_int, _DP, _DP, _DP]
+    lib.mvx_add_cut_rows.restype = C.c_int
+    lib.mvx_add_cut_rows.argtypes = [C.c_void_p, C.c_int, _DP, _DP]
+    lib.mvx_bnb_cut_scores.restype = C.c_int
+    lib.mvx_bnb_cut_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_int, _DP, _DP, _DP]
+    lib.mvx_bnb_cut_select.restype = C.c_int
+    lib.mvx_bnb_cut_select.argtypes = [C.c_int, _DP, _DP, C.c_int, C.c_double, C.c_int, _IP, _IP]
+    lib.mvx_bnb_cut_loop.restype = C.c_int
+    lib.mvx_bnb_cut_loop.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_longlong), _DP]
+    lib.mvx_generateCutGMI.restype = C.c_int
+    lib.mvx_generateCutGMI.argtypes = [C.c_void_p, C.c_void_p, C.c_int, _IP, _DP, _DP, _DP]
     lib.mvx_generateCut3.restype = C.c_int
     lib.mvx_generateCut3.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     return lib
@@ -241,12 +263,19 @@ def result_to_dict(res):
         "pump_improved": res.pump_improved,
         "pump_lps": res.pump_lps,
         "pump_pivots": res.pump_pivots,
+        "cutloop_rounds": res.cutloop_rounds,
+        "cutloop_candidates": res.cutloop_candidates,
+        "cutloop_rows": res.cutloop_rows,
+        "cutloop_lps": res.cutloop_lps,
+        "cutloop_pivots": res.cutloop_pivots,
+        "cutloop_bound0": res.cutloop_bound0,
+        "cutloop_bound": res.cutloop_bound,
     }
 
 
 def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, window=None, cut_select=0, cut_chance=1.0,
                 best_window=None, sb_cands=None, sb_iters=None, heur=None, rc_fix=None, prop=None, dive=None, dive_freq=None,
-                dive_depth=None, pump=None, pump_freq=None, pump_alpha=None):
+                dive_depth=None, pump=None, pump_freq=None, pump_alpha=None, cut_rounds=None, cut_round_max=None, cut_maxpar=None):
     """mvx_bnb_params with ParameterObj's defaults (util.h:65-67) overridden by the arguments (None: the default)."""
     pr = BnbParams()
     lib().mvx_bnb_default_params(C.byref(pr))
@@ -279,12 +308,19 @@ def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, l
         pr.pump_freq = pump_freq
     if pump_alpha is not None:
         pr.pump_alpha = pump_alpha
+    if cut_rounds is not None:
+        pr.cut_rounds = cut_rounds
+    if cut_round_max is not None:
+        pr.cut_round_max = cut_round_max
+    if cut_maxpar is not None:
+        pr.cut_maxpar = cut_maxpar
     return pr
 
 
 def branch_and_bound(prob, var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, table=None, window=None,
                      cut_select=0, cut_chance=1.0, best_window=None, sb_cands=None, sb_iters=None, heur=None, rc_fix=None, prop=None,
-                     dive=None, dive_freq=None, dive_depth=None, pump=None, pump_freq=None, pump_alpha=None):
+                     dive=None, dive_freq=None, dive_depth=None, pump=None, pump_freq=None, pump_alpha=None, cut_rounds=None,
+                     cut_round_max=None, cut_maxpar=None):
     """Run the driver on `prob` (a capi.Prob).  table=None uses the gfx950 engine's own table.  best_window > 1 with
     node_strat=1: the speculative best-bound window (mvx_bnb_params.best_window).  var_strat 3 / 4: branching on the node
     LP's penalties / strong branching (sb_cands candidates, sb_iters pivots per child).  heur 1 / 2: the primal rounding
@@ -295,12 +331,15 @@ def branch_and_bound(prob, var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, 
     at every branching node whose oid F divides; dive_depth limits a dive's steps (quirks=0, not with best_window).  pump 1..1000: the
     feasibility pump with that limit of distance LPs at the root and, with pump_freq = F > 0, at every branching node whose oid F
     divides, behind the rounding heuristic and in front of the dives; pump_alpha (0..1) weighs the model's objective into the
-    distance LPs (quirks=0, not with best_window).  The
+    distance LPs (quirks=0, not with best_window).  cut_rounds 1..64: that many rounds of GMI cuts on the root LP before the
+    tree starts, at most cut_round_max (default 32) cuts a round, none more than cut_maxpar (default 0.9) parallel to one
+    taken before it in the round (quirks=0; every single-GPU driver).  The
     dictionary's "rc" is mvx_branchAndBound's return code (-1 refused parameters, -2 penalties, heuristic, tightening,
     propagation, pumps or dives unavailable)."""
     L = lib()
     pr = make_params(var_strat, node_strat, cut_strat, max_nodes, quirks, lazy_pool, window, cut_select, cut_chance, best_window, sb_cands,
-                     sb_iters, heur, rc_fix, prop, dive, dive_freq, dive_depth, pump, pump_freq, pump_alpha)
+                     sb_iters, heur, rc_fix, prop, dive, dive_freq, dive_depth, pump, pump_freq, pump_alpha, cut_rounds, cut_round_max,
+                     cut_maxpar)
     res = BnbResult()
     tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
     rc = L.mvx_branchAndBound(tptr, prob.h, C.byref(pr), C.byref(res))
@@ -691,6 +730,83 @@ def pump_node(prob, root, iters=30, alpha=0.0, table=None):
     rc = lib().mvx_bnb_pump(tptr, prob.h, root.h, iters, alpha, C.byref(obj), C.byref(found), x.ctypes.data_as(C.POINTER(C.c_double)),
                             C.byref(lps), C.byref(piv), C.byref(end))
     return rc, obj.value, found.value, x, lps.value, piv.value, end.value
+
+
+CUTLOOP_COUNTERS = ("cutloop_rounds", "cutloop_candidates", "cutloop_rows", "cutloop_lps", "cutloop_pivots")
+
+
+def cut_scores(prob, vals, table=False):
+    """The scores of the candidate cut rows `vals` (k x (n + 1), entry 0 of a row unused) against the solved handle `prob`:
+    (rc, dot array of k, gram array (k, k)).  table=False: mvx_cut_scores, one launch of the gfx950 engine; otherwise the host
+    twin mvx_bnb_cut_scores through `table` (None = the gfx950 engine's table)."""
+    import numpy as np
+
+    v = np.ascontiguousarray(np.asarray(vals, dtype=np.float64))
+    k = v.shape[0] if v.ndim == 2 else 0
+    dot, gram = np.zeros(max(1, k)), np.zeros((max(1, k), max(1, k)))
+    DP = C.POINTER(C.c_double)
+    if table is False:
+        rc = lib().mvx_cut_scores(prob.h, k, v.ctypes.data_as(DP), dot.ctypes.data_as(DP), gram.ctypes.data_as(DP))
+    else:
+        tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
+        rc = lib().mvx_bnb_cut_scores(tptr, prob.h, k, v.ctypes.data_as(DP), dot.ctypes.data_as(DP), gram.ctypes.data_as(DP))
+    return rc, dot[:k], gram[:k, :k]
+
+
+def cut_select(eff, gram, K=32, maxpar=0.9, budget=1 << 30):
+    """mvx_bnb_cut_select, the selection of one round from numbers only: (rc, indices in taken order)."""
+    import numpy as np
+
+    e = np.ascontiguousarray(np.asarray(eff, dtype=np.float64))
+    g = np.ascontiguousarray(np.asarray(gram, dtype=np.float64))
+    k = len(e)
+    taken = np.zeros(max(1, k), dtype=np.int32)
+    nt = C.c_int(0)
+    DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    rc = lib().mvx_bnb_cut_select(k, e.ctypes.data_as(DP), g.ctypes.data_as(DP), K, maxpar, budget, taken.ctypes.data_as(IP), C.byref(nt))
+    return rc, taken[: nt.value].tolist()
+
+
+def add_cut_rows(prob, vals, rhs):
+    """mvx_add_cut_rows: the rows `vals` (k x (n + 1), entry 0 of a row unused) appended to the handle `prob` of the gfx950 engine
+    as MVX_LO rows with the bounds `rhs`, in one device pass; the handle is left as k single appends leave it.  Returns the
+    call's code (0; -1 bad arguments, nothing changed; -2 device out of memory)."""
+    import numpy as np
+
+    v = np.ascontiguousarray(np.asarray(vals, dtype=np.float64))
+    r = np.ascontiguousarray(np.asarray(rhs, dtype=np.float64))
+    k = v.shape[0] if v.ndim == 2 else 0
+    if k and (v.shape[1] != prob.n + 1 or len(r) != k):
+        return -1
+    DP = C.POINTER(C.c_double)
+    return lib().mvx_add_cut_rows(prob.h, k, v.ctypes.data_as(DP), r.ctypes.data_as(DP))
+
+
+def cut_loop(prob, rounds=5, K=0, maxpar=0.0, table=None):
+    """mvx_bnb_cut_loop: the root cut loop on the handle `prob`, which is edited in place, through `table` (None = the gfx950
+    engine's table, whose batched entries then run).  Returns (rc, dictionary of the cutloop_* counters and bounds)."""
+    cnt = (C.c_longlong * 5)()
+    bnd = (C.c_double * 2)()
+    tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
+    rc = lib().mvx_bnb_cut_loop(tptr, prob.h, rounds, K, maxpar, cnt, bnd)
+    out = {name: int(cnt[i]) for i, name in enumerate(CUTLOOP_COUNTERS)}
+    out["cutloop_bound0"], out["cutloop_bound"] = bnd[0], bnd[1]
+    return rc, out
+
+
+def generate_cut_gmi(prob, j, table=None):
+    """mvx_generateCutGMI, the repaired cut of the basic integer column j of a solved handle: (vals array of n + 1, lb, efficacy),
+    or None when there is none."""
+    import numpy as np
+
+    n = prob.n
+    inds = np.zeros(n + 1, dtype=np.int32)
+    vals = np.zeros(n + 1, dtype=np.float64)
+    lb, eff = C.c_double(0.0), C.c_double(0.0)
+    tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
+    rc = lib().mvx_generateCutGMI(tptr, prob.h, j, inds.ctypes.data_as(C.POINTER(C.c_int)), vals.ctypes.data_as(C.POINTER(C.c_double)),
+                                  C.byref(lb), C.byref(eff))
+    return None if rc != 0 else (vals, lb.value, eff.value)
 
 
 def node_sample(root, count, quirks=0, table=None):

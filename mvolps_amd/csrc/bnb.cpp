@@ -48,6 +48,9 @@ extern "C" int mvx_set_obj_many(mvx_prob *const *Ps, int count, const double *c)
 extern "C" int mvx_pump_obj_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, const double *xprev, const int *has_prev,
                                  const double *ab, int *info, double *xt, double *c) __attribute__((weak));
 
+extern "C" int mvx_cut_scores(const mvx_prob *P, int k, const double *vals, double *dot, double *gram) __attribute__((weak));
+extern "C" int mvx_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rhs) __attribute__((weak));
+
 namespace {
 
 struct CutContainer { // cut.h:7-13
@@ -2248,7 +2251,10 @@ static int on_slots(const std::vector<void *> &hs, const std::vector<char> &mask
   return 0;
 }
 
-int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm, mvx_bnb_result *res) { // bs.cpp:54
+// `model`: the handle whose rows 1..m0, bounds and objective the rules that read the model work on (rounding, propagation,
+// dives, pump).  It is `prob` itself unless the root cut loop has appended rows to `prob`: a cut computed in floating point may
+// be violated by a feasible point by more than those rules' margins, so they keep reading the model from before the cuts.
+int branchAndBound(const mvx_lp_api *api, void *prob, const void *model, const mvx_bnb_params &prm, mvx_bnb_result *res) { // bs.cpp:54
   MVOLP::ParameterObj params(api, prob, prm);
   CutPool pool(api);
   Tree T(api, prob, prm);
@@ -2256,11 +2262,11 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm,
   std::deque<std::shared_ptr<MVOLP::NodeData>> leafContainer;
   leafContainer.push_back(T.root(prob));
   void *a = api->create_prob(); // bs.cpp:89
-  Heuristic heur(api, prob, prm.heur);
+  Heuristic heur(api, model, prm.heur);
   RcFix rcfix(api);
-  Prop prop(api, prob, prm.prop);
-  Dive dive(api, prob, prm);
-  Pump pump(api, prob, prm);
+  Prop prop(api, model, prm.prop);
+  Dive dive(api, model, prm);
+  Pump pump(api, model, prm);
 
   while (!leafContainer.empty()) { // bs.cpp:96
     if (T.node_limit()) break;
@@ -2375,7 +2381,7 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm,
 // the back (bs.cpp:297-298) and no node is discarded unsolved, so the next W nodes the serial loop
 // would pop are exactly the front W whatever their outcome: the tree, oids, events, pivot counts and
 // incumbent are those of the node-at-a-time loop above.
-int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm, mvx_bnb_result *res) {
+int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const void *model, const mvx_bnb_params &prm, mvx_bnb_result *res) {
   MVOLP::ParameterObj params(api, prob, prm);
   Tree T(api, prob, prm);
   Recorder &rec = T.rec;
@@ -2383,11 +2389,11 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const mvx_bnb_params
   std::deque<std::shared_ptr<MVOLP::NodeData>> leafContainer;
   leafContainer.push_back(T.root(prob));
   bool stop = false;
-  Heuristic heur(api, prob, prm.heur);
+  Heuristic heur(api, model, prm.heur);
   RcFix rcfix(api);
-  Prop prop(api, prob, prm.prop);
-  Dive dive(api, prob, prm);
-  Pump pump(api, prob, prm);
+  Prop prop(api, model, prm.prop);
+  Dive dive(api, model, prm);
+  Pump pump(api, model, prm);
   auto fail = [&]() { // whatever code a failing call gives, the tree so far goes back with -2
     T.rc_out = -2;
     stop = true;
@@ -2822,7 +2828,7 @@ static void classify_round(const mvx_lp_api *api, const std::vector<void *> &hs,
 // deleted, and the persistent pool of the bug-compatible mode (bs.cpp:73, cut.cpp:16-21) is rolled back to the state
 // the committed prefix left.  oids, parents, events, pivot counts and the incumbent are booked at commit, in the order
 // the serial loop books them: the tree is the node-at-a-time one.
-int branchAndBoundBest(const mvx_lp_api *api, void *prob, const mvx_bnb_params &prm, mvx_bnb_result *res) {
+int branchAndBoundBest(const mvx_lp_api *api, void *prob, const void *model, const mvx_bnb_params &prm, mvx_bnb_result *res) {
   MVOLP::ParameterObj params(api, prob, prm);
   CutPool pool(api);
   Tree T(api, prob, prm);
@@ -2846,7 +2852,7 @@ int branchAndBoundBest(const mvx_lp_api *api, void *prob, const mvx_bnb_params &
   push(T.root(prob));
   long long rounds = 0, speculated = 0;
   bool stop = false;
-  Heuristic heur(api, prob, prm.heur);
+  Heuristic heur(api, model, prm.heur);
   const size_t W = (size_t)prm.best_window;
   const bool timing = std::getenv("MVX_BNB_TIMING") != nullptr;
   double tA = 0, tInfo = 0, tSpec = 0, tKids = 0, tReplay = 0;
@@ -3090,6 +3096,11 @@ const mvx_lp_api g_hip_api = {
                             int *info, double *xt, double *c) {
       return mvx_pump_obj_many((const mvx_prob *)root, (const mvx_prob *const *)Ps, count, xprev, has_prev, ab, info, xt, c);
     } : nullptr,
+    mvx_cut_scores ? +[](const void *P, int k, const double *vals, double *dot, double *gram) {
+      return mvx_cut_scores((const mvx_prob *)P, k, vals, dot, gram);
+    } : nullptr,
+    mvx_add_cut_rows ? +[](void *P, int k, const double *vals, const double *rhs) { return mvx_add_cut_rows((mvx_prob *)P, k, vals, rhs); }
+                     : nullptr,
 };
 
 } // namespace
@@ -3121,6 +3132,9 @@ void mvx_bnb_default_params(mvx_bnb_params *p) {
   p->pump = 0;
   p->pump_freq = 0;
   p->pump_alpha = 0.0;
+  p->cut_rounds = 0;
+  p->cut_round_max = 0;
+  p->cut_maxpar = 0.0;
 }
 
 // Repaired mode's rule for an integer column whose bounds are not integers (legal input: LP and MPS files may carry them):
@@ -3151,11 +3165,182 @@ int mvx_bnb_fractional_bounds(const mvx_lp_api *api, const void *prob) {
   return integral_bounds(api ? api : &g_hip_api, const_cast<void *>(prob), false);
 }
 
-static int run_driver(const mvx_lp_api *api, void *prob, const mvx_bnb_params *params, mvx_bnb_result *res) {
+static int run_driver(const mvx_lp_api *api, void *prob, const void *model, const mvx_bnb_params *params, mvx_bnb_result *res) {
   if (api->simplex_batch && params->node_strat == 0 && params->window > 1)
-    return branchAndBoundWindow(api, prob, *params, res);
-  if (api->simplex_batch && params->node_strat == 1 && params->best_window > 1) return branchAndBoundBest(api, prob, *params, res);
-  return branchAndBound(api, prob, *params, res);
+    return branchAndBoundWindow(api, prob, model, *params, res);
+  if (api->simplex_batch && params->node_strat == 1 && params->best_window > 1) return branchAndBoundBest(api, prob, model, *params, res);
+  return branchAndBound(api, prob, model, *params, res);
+}
+
+// ---- root cut rounds (DESIGN.md "Root cut rounds") ----
+
+// dot[t] = sum_j v_tj x_j and gram[t][s] = sum_j v_tj v_sj, j ascending from +0.0, product and sum rounded separately (the
+// efficacy loop of cuts_via_engine): the arithmetic k_cutgram repeats.  A product commutes, so the lower triangle is a copy.
+static void cut_scores_host(const mvx_lp_api *api, const void *P, int k, const double *vals, double *dot, double *gram) {
+  const int n = api->get_num_cols(P);
+  const size_t row = (size_t)n + 1;
+  std::vector<double> x(row, 0.0);
+  for (int j = 1; j <= n; j++) x[(size_t)j] = api->get_col_prim(P, j);
+  for (int t = 0; t < k; t++) {
+    const double *vt = vals + (size_t)t * row;
+    double d = 0.0;
+    for (int j = 1; j <= n; j++) d += vt[j] * x[(size_t)j];
+    dot[t] = d;
+    for (int s = t; s < k; s++) {
+      const double *vs = vals + (size_t)s * row;
+      double g = 0.0;
+      for (int j = 1; j <= n; j++) g += vt[j] * vs[j];
+      gram[(size_t)t * (size_t)k + (size_t)s] = g;
+      gram[(size_t)s * (size_t)k + (size_t)t] = g;
+    }
+  }
+}
+
+// Step 4 of a round, from numbers only: efficacy descending (ties to the lower index), a cut is taken when it is at most
+// `maxpar` parallel to every cut taken before it, until K are taken or `budget` are.
+static std::vector<int> cut_select(int k, const double *eff, const double *gram, int K, double maxpar, int budget) {
+  std::vector<int> order((size_t)k), taken;
+  for (int t = 0; t < k; t++) order[(size_t)t] = t;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return eff[a] > eff[b]; });
+  for (int t : order) {
+    if ((int)taken.size() >= K || (int)taken.size() >= budget) break;
+    const double nt = std::sqrt(gram[(size_t)t * (size_t)k + (size_t)t]);
+    bool ok = true;
+    for (int s : taken) {
+      const double ns = std::sqrt(gram[(size_t)s * (size_t)k + (size_t)s]);
+      if (!(gram[(size_t)t * (size_t)k + (size_t)s] <= maxpar * (nt * ns))) {
+        ok = false;
+        break;
+      }
+    }
+    if (ok) taken.push_back(t);
+  }
+  return taken;
+}
+
+struct CutLoopOut {
+  long long rounds = 0, candidates = 0, rows = 0, lps = 0, pivots = 0;
+  double bound0 = 0.0, bound = 0.0;
+  void store(mvx_bnb_result *res) const {
+    res->cutloop_rounds = rounds;
+    res->cutloop_candidates = candidates;
+    res->cutloop_rows = rows;
+    res->cutloop_lps = lps;
+    res->cutloop_pivots = pivots;
+    res->cutloop_bound0 = bound0;
+    res->cutloop_bound = bound;
+  }
+};
+
+// Coefficient-range safeguard of step 2: a cut whose largest |coefficient| is more than this many times its smallest non-zero
+// one is not taken into a round.  Such a row carries cancellation noise (entries of 1e-15 where the exact cut has zeros) from
+// a late-round tableau; in-tree cuts derived from tableaux that hold such rows kept a fixture tree from closing.  Over the
+// general fixtures the ratios fall into two groups, up to 1.2e5 and from 3.4e14 on; 1e9 parts them, and is the relative size
+// (1e-9) below which the driver's other rules treat a number as zero.
+constexpr double CUT_MAX_RANGE = 1e9;
+
+// The loop on `P`, edited in place: first solve, then up to R rounds of (candidates, scores, selection, append, re-solve).
+// Returns 0; -2 when the table lacks an accessor or one of its calls failed.
+static int cut_loop(const mvx_lp_api *api, void *P, int R, int K, double maxpar, CutLoopOut &o) {
+  if (!api->add_rows || !api->set_mat_row || !api->set_row_bnds || !api->simplex || !api->get_status || !api->get_obj_val ||
+      !api->get_col_prim || !api->get_num_rows || !api->get_num_cols || !api->get_col_kind || !api->get_col_stat || !api->get_it_cnt ||
+      !api->eval_tab_row || !api->get_mat_row)
+    return -2;
+  if (K == 0) K = 32;
+  if (maxpar == 0.0) maxpar = 0.9;
+  const int n = api->get_num_cols(P);
+  const size_t row = (size_t)n + 1;
+  const int budget = std::max(64, api->get_num_rows(P));
+  auto solve_lp = [&]() {
+    const int before = api->get_it_cnt(P);
+    api->simplex(P, nullptr);
+    o.pivots += api->get_it_cnt(P) - before;
+    o.lps++;
+  };
+  solve_lp();
+  o.bound0 = o.bound = api->get_obj_val(P);
+  std::vector<int> inds(row);
+  for (int j = 0; j <= n; j++) inds[(size_t)j] = j;
+  for (int r = 1; r <= R && api->get_status(P) == MVX_OPT; r++) {
+    // 1. candidates: the repaired cut of every column generateCutGMI would not reject out of hand
+    std::vector<int> cols;
+    for (int j = 1; j <= n; j++)
+      if (gmi_candidate(api, P, j)) cols.push_back(j);
+    if (cols.empty()) break; // the root LP is integral
+    const int k = (int)cols.size();
+    std::vector<double> vals((size_t)k * row, 0.0), rhs((size_t)k, 0.0);
+    std::vector<int> ok((size_t)k, 0);
+    if (!api->gmi_cuts || api->gmi_cuts(P, 1, cols.data(), k, vals.data(), rhs.data(), ok.data()) != 0) {
+      for (int t = 0; t < k; t++) {
+        double e = 0.0;
+        CutContainer c = generateCutGMI(api, P, cols[(size_t)t], &e);
+        ok[(size_t)t] = c.oid != -1;
+        if (!ok[(size_t)t]) continue;
+        std::copy(c.vals.begin(), c.vals.end(), vals.begin() + (long)((size_t)t * row));
+        rhs[(size_t)t] = c.lb;
+      }
+    }
+    // 2. scores: efficacy at the LP point, as cuts_via_engine computes it
+    std::vector<double> x(row, 0.0);
+    for (int j = 1; j <= n; j++) x[(size_t)j] = api->get_col_prim(P, j);
+    std::vector<int> live;
+    std::vector<double> eff((size_t)k, 0.0);
+    for (int t = 0; t < k; t++) {
+      if (!ok[(size_t)t]) continue;
+      const double *v = &vals[(size_t)t * row];
+      double dot = 0.0, nrm = 0.0, big = 0.0, small = std::numeric_limits<double>::infinity();
+      for (int j = 1; j <= n; j++) {
+        dot += v[j] * x[(size_t)j];
+        nrm += v[j] * v[j];
+        const double a = std::fabs(v[j]);
+        if (a > big) big = a;
+        if (a != 0.0 && a < small) small = a;
+      }
+      if (!(nrm > 0.0)) continue;
+      o.candidates++;
+      if (big > CUT_MAX_RANGE * small) continue;
+      eff[(size_t)t] = (rhs[(size_t)t] - dot) / std::sqrt(nrm);
+      if (eff[(size_t)t] > 1e-6) live.push_back(t);
+    }
+    std::stable_sort(live.begin(), live.end(), [&](int a, int b) { return eff[(size_t)a] > eff[(size_t)b]; });
+    if (live.size() > (size_t)4 * (size_t)K) live.resize((size_t)4 * (size_t)K);
+    const int C = (int)live.size();
+    if (C == 0) break;
+    // 3. the Gram matrix of the survivors
+    std::vector<double> sv((size_t)C * row), se((size_t)C), sdot((size_t)C), gram((size_t)C * (size_t)C);
+    for (int t = 0; t < C; t++) {
+      std::copy(vals.begin() + (long)((size_t)live[(size_t)t] * row), vals.begin() + (long)((size_t)(live[(size_t)t] + 1) * row),
+                sv.begin() + (long)((size_t)t * row));
+      se[(size_t)t] = eff[(size_t)live[(size_t)t]];
+    }
+    if (!api->cut_scores || api->cut_scores(P, C, sv.data(), sdot.data(), gram.data()) != 0)
+      cut_scores_host(api, P, C, sv.data(), sdot.data(), gram.data());
+    // 4. selection
+    const int left = budget - (int)o.rows;
+    std::vector<int> taken = cut_select(C, se.data(), gram.data(), K, maxpar, left);
+    if (taken.empty()) break;
+    // 5. append in taken order and re-solve (the dual simplex, warm)
+    const int nt = (int)taken.size();
+    std::vector<double> tv((size_t)nt * row), tr((size_t)nt);
+    for (int t = 0; t < nt; t++) {
+      std::copy(sv.begin() + (long)((size_t)taken[(size_t)t] * row), sv.begin() + (long)((size_t)(taken[(size_t)t] + 1) * row),
+                tv.begin() + (long)((size_t)t * row));
+      tr[(size_t)t] = rhs[(size_t)live[(size_t)taken[(size_t)t]]];
+    }
+    int arc = -1;
+    if (api->add_cut_rows) arc = api->add_cut_rows(P, nt, tv.data(), tr.data());
+    if (arc != 0 && arc != -2) // -2: device memory, the rows are in the model and the next solve starts from the slack basis
+      for (int t = 0; t < nt; t++) {
+        const int index = api->add_rows(P, 1);
+        api->set_mat_row(P, index, n, inds.data(), &tv[(size_t)t * row]);
+        api->set_row_bnds(P, index, MVX_LO, tr[(size_t)t], 0);
+      }
+    o.rows += nt;
+    solve_lp();
+    o.rounds++;
+    if (api->get_status(P) == MVX_OPT) o.bound = api->get_obj_val(P);
+  }
+  return 0;
 }
 
 int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *params, mvx_bnb_result *res) {
@@ -3178,11 +3363,15 @@ int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *
       (params->dive > 0 && (params->reference_quirks != 0 || params->best_window > 0)) ||
       // pump: the same
       params->pump < 0 || params->pump > 1000 || params->pump_freq < 0 || !(params->pump_alpha >= 0.0 && params->pump_alpha <= 1.0) ||
-      (params->pump > 0 && (params->reference_quirks != 0 || params->best_window > 0))) {
+      (params->pump > 0 && (params->reference_quirks != 0 || params->best_window > 0)) ||
+      // root cut rounds: repaired cuts only; every single-GPU driver runs behind them
+      params->cut_rounds < 0 || params->cut_rounds > 64 ||
+      (params->cut_rounds > 0 && (params->reference_quirks != 0 || params->cut_round_max < 0 || params->cut_round_max > 4096 ||
+                                  !(params->cut_maxpar == 0.0 || (params->cut_maxpar > 0.0 && params->cut_maxpar <= 1.0))))) {
     std::memset(res, 0, sizeof(*res));
     return -1;
   }
-  if (params->reference_quirks == 0 && (params->prop > 0 || integral_bounds(api, prob, false) != 0)) {
+  if (params->reference_quirks == 0 && (params->prop > 0 || params->cut_rounds > 0 || integral_bounds(api, prob, false) != 0)) {
     // the caller's handle stays as it is: the tree runs on a copy with the rounded (and, with prop, propagated) bounds
     void *work = api->create_prob();
     api->copy_prob(work, prob, MVX_OFF);
@@ -3193,6 +3382,23 @@ int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *
       T.rec.node(T.id++, 0);
       T.rec.prune[1] = prune;
       T.finish(res, nullptr, nullptr);
+    };
+    // the tree behind the root cut loop (cut_rounds > 0): `work` takes the cuts, a copy from before them stays the model
+    auto run_tree = [&]() {
+      if (params->cut_rounds <= 0) return run_driver(api, work, work, params, res);
+      void *model = api->create_prob();
+      api->copy_prob(model, work, MVX_OFF);
+      CutLoopOut lo;
+      int r = cut_loop(api, work, params->cut_rounds, params->cut_round_max, params->cut_maxpar, lo);
+      if (r != 0) {
+        infeasible_root(MVOLP::NONE); // the loop could not run: the tree so far is the unsolved root
+        r = -2;
+      } else {
+        r = run_driver(api, work, model, params, res);
+      }
+      lo.store(res);
+      api->delete_prob(model);
+      return r;
     };
     if (integral_bounds(api, work, true) == 2) {
       infeasible_root(MVOLP::FEAS);
@@ -3209,19 +3415,19 @@ int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *
         root_prop.store(res);
       } else {
         root_prop.apply({work}, got);
-        rc = run_driver(api, work, params, res);
+        rc = run_tree();
         res->prop_calls += root_prop.calls;
         res->prop_fixed += root_prop.fixed;
         res->prop_tightened += root_prop.tightened;
         res->prop_infeasible += root_prop.infeasible;
       }
     } else {
-      rc = run_driver(api, work, params, res);
+      rc = run_tree();
     }
     api->delete_prob(work);
     return rc;
   }
-  return run_driver(api, prob, params, res);
+  return run_driver(api, prob, prob, params, res);
 }
 
 void mvx_bnb_free_result(mvx_bnb_result *res) {
@@ -3393,6 +3599,33 @@ int mvx_bnb_propagate(const mvx_lp_api *api, const void *prob, const void *root,
     ub[k] = out.list[k].ub;
   }
   return 0;
+}
+
+int mvx_bnb_cut_scores(const mvx_lp_api *api, const void *prob, int k, const double *vals, double *dot, double *gram) {
+  if (!api) api = &g_hip_api;
+  if (!prob || k < 1 || !vals || !dot || !gram || api->get_status(prob) != MVX_OPT) return -1;
+  cut_scores_host(api, prob, k, vals, dot, gram);
+  return 0;
+}
+
+int mvx_bnb_cut_select(int k, const double *eff, const double *gram, int K, double maxpar, int budget, int *taken, int *ntaken) {
+  if (k < 0 || K < 1 || !(maxpar > 0.0 && maxpar <= 1.0) || budget < 0 || !ntaken || (k > 0 && (!eff || !gram || !taken))) return -1;
+  std::vector<int> got = cut_select(k, eff, gram, K, maxpar, budget);
+  for (size_t i = 0; i < got.size(); i++) taken[i] = got[i];
+  *ntaken = (int)got.size();
+  return 0;
+}
+
+int mvx_bnb_cut_loop(const mvx_lp_api *api, void *prob, int rounds, int K, double maxpar, long long *counters, double *bounds) {
+  if (!api) api = &g_hip_api;
+  if (!prob || rounds < 1 || rounds > 64 || K < 0 || K > 4096 || !(maxpar == 0.0 || (maxpar > 0.0 && maxpar <= 1.0)) || !counters ||
+      !bounds)
+    return -1;
+  CutLoopOut lo;
+  const int rc = cut_loop(api, prob, rounds, K, maxpar, lo);
+  counters[0] = lo.rounds; counters[1] = lo.candidates; counters[2] = lo.rows; counters[3] = lo.lps; counters[4] = lo.pivots;
+  bounds[0] = lo.bound0; bounds[1] = lo.bound;
+  return rc;
 }
 
 int mvx_bnb_node_cuts(const mvx_lp_api *api, void *a, const mvx_bnb_params *params) {

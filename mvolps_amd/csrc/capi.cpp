@@ -537,6 +537,14 @@ int mvx_pump_obj_many(const mvx_prob *root, const mvx_prob *const *Ps, int count
   return mvx::engine_pump_obj_many(root, Ps, count, xprev, has_prev, ab, info, xt, c);
 }
 
+int mvx_cut_scores(const mvx_prob *P, int k, const double *vals, double *dot, double *gram) {
+  if (!P || k < 1 || !vals || !dot || !gram || !P->valid || P->status != MVX_OPT) return -1;
+  std::vector<double> x((size_t)P->n + 1, 0.0);
+  mvx_get_col_prim_all(P, x.data()); // the bits get_col_prim returns
+  return mvx::engine_cut_scores(P, k, vals, x.data(), dot, gram);
+}
+int mvx_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rhs) { return mvx::engine_add_cut_rows(P, k, vals, rhs); }
+
 int mvx_device_count(void) { return mvx::device_count(); }
 int mvx_set_device(int dev) { return mvx::set_device(dev); }
 long long mvx_pack_size(const mvx_prob *P) { return mvx::engine_pack_size(P, P->m); }

@@ -2102,6 +2102,134 @@ void engine_row_from_model(mvx_prob *P, int i) {
   P->status = MVX_UNDEF;
 }
 
+// ------------------------------------------------------------------ a round of cuts: scores (k_cutgram), append (k_cutrows)
+// dot[t] = sum_j v_tj x_j and gram[t][s] = sum_j v_tj v_sj of `k` candidate rows (mvx_cut_scores; vals is k x (n+1) in the
+// layout of mvx_gmi_cuts, x[1..n] the column values of the solved handle, read by the caller out of the mirrors): one upload,
+// one k_cutgram launch, one copy back.  Nothing of the handle changes.  Return codes: 0; -1 bad arguments or a handle that
+// is not MVX_OPT; -2 device out of memory.
+int engine_cut_scores(const mvx_prob *P, int k, const double *vals, const double *x, double *dot, double *gram) {
+  if (!P || k < 1 || !vals || !x || !dot || !gram || !P->valid || P->status != MVX_OPT) return -1;
+  const int n = P->n;
+  const size_t row = (size_t)n + 1;
+  NodeCall f(NodeFlush::AtEntry, NodeResults::Device);
+  const size_t o_vals = f.up((size_t)k * row * 8), o_x = f.up(row * 8);
+  const size_t o_dot = f.out((size_t)k * 8), o_gram = f.out((size_t)k * (size_t)k * 8);
+  if (!f.reserve()) return -2;
+  std::memcpy(f.hb + o_vals, vals, (size_t)k * row * 8);
+  std::memcpy(f.hb + o_x, x, row * 8);
+  *(double *)(f.hb + o_x) = 0.0; // entry 0 is not a column
+  f.upload();
+  CutGramArgs a;
+  a.vals = (const double *)(f.db + o_vals);
+  a.x = (const double *)(f.db + o_x);
+  a.dot = (double *)(f.db + o_dot);
+  a.gram = (double *)(f.db + o_gram);
+  a.k = k; a.n = n;
+  launch_cutgram(a, f.stream());
+  f.fetch();
+  std::memcpy(dot, f.hb + o_dot, (size_t)k * 8);
+  std::memcpy(gram, f.hb + o_gram, (size_t)k * (size_t)k * 8);
+  return 0;
+}
+
+// `k` dense MVX_LO rows appended in one device pass (mvx_add_cut_rows): the handle is left as k times (add_rows(1), set_mat_row
+// with all n indices, set_row_bnds(LO)) leave it -- model, mirrors, tableau, pending bound edits, fresh_rows, hint_dual,
+// status -- with one grow_rows call, one renumbering of the mirrors, one upload and one k_cutrows launch.  What the kernel
+// needs of the basis goes up as two index lists (the structural column of every row and of every non-basic position, taken
+// before the renumbering); the weights and the base of engine_row_from_model are entries of `vals` under those lists, and
+// only the row's value at the non-basic point (base[0]) is computed here, in engine_row_from_model's order.
+// The bound of a new row is a pending edit, as engine_apply_bounds leaves it; of the edits that the k single calls would have
+// flushed on the way (MAX_EDITS), those of new rows are written by the kernel itself and those of older rows are launched.
+// Return codes: 0; -1 bad arguments, nothing changed (k < 1, a null, a NaN, a handle without a valid tableau); -2 device out of
+// memory: the model has the rows and the tableau is given up, as engine_add_rows gives it up.
+int engine_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rhs) {
+  if (!P || k < 1 || !vals || !rhs || !P->valid) return -1;
+  const int m = P->m, n = P->n;
+  const size_t row = (size_t)n + 1;
+  for (int t = 0; t < k; t++) {
+    if (std::isnan(rhs[t])) return -1;
+    for (int j = 1; j <= n; j++)
+      if (std::isnan(vals[(size_t)t * row + (size_t)j])) return -1;
+  }
+  // the model: what add_rows + set_mat_row + set_row_bnds write
+  for (int t = 0; t < k; t++) {
+    auto r = std::make_shared<std::vector<double>>(vals + (size_t)t * row, vals + (size_t)(t + 1) * row);
+    (*r)[0] = 0.0;
+    P->A.push_back(std::move(r));
+    P->rtype.push_back(MVX_LO);
+    P->rlb.push_back(rhs[t]);
+    P->rub.push_back(INFINITY);
+  }
+  P->m = m + k;
+  P->status = MVX_UNDEF;
+  NodeCall f(NodeFlush::AtEntry, NodeResults::None);
+  const size_t o_vals = f.up((size_t)k * row * 8), o_rowcol = f.up((size_t)(m + 1) * 4), o_nbcol = f.up(row * 4);
+  const size_t o_rowlb = f.up((size_t)k * 8), o_extra = f.up((size_t)k * 4);
+  if (!grow_rows(P, P->m) || !f.reserve()) {
+    release_device(P);
+    engine_invalidate(P);
+    return -2;
+  }
+  unsigned char *hb = f.hb, *db = f.db;
+  double *h_vals = (double *)(hb + o_vals), *h_rowlb = (double *)(hb + o_rowlb);
+  int *h_rowcol = (int *)(hb + o_rowcol), *h_nbcol = (int *)(hb + o_nbcol), *h_extra = (int *)(hb + o_extra);
+  std::memcpy(h_vals, vals, (size_t)k * row * 8);
+  h_rowcol[0] = 0;
+  for (int i = 1; i <= m; i++) h_rowcol[i] = P->bvar[i] > m ? P->bvar[i] - m : 0;
+  h_nbcol[0] = 0;
+  for (int q = 1; q <= n; q++) h_nbcol[q] = P->nvar[q] > m ? P->nvar[q] - m : 0;
+  const int real_chunks = (m + ROWCOMB_CHUNK - 1) / ROWCOMB_CHUNK;
+  for (int t = 0; t < k; t++) {
+    const double *a = vals + (size_t)t * row;
+    double b0 = 0.0;
+    for (int q = 1; q <= n; q++) {
+      const int col = h_nbcol[q];
+      if (!col) continue;
+      const double v = a[col], x = nb_value(P->nflag[q], P->clb[col], P->cub[col]);
+      if (x != 0.0 && v != 0.0) b0 = std::fma(v, x, b0);
+    }
+    h_vals[(size_t)t * row] = b0;
+    h_extra[t] = (m + t + 1 + ROWCOMB_CHUNK - 1) / ROWCOMB_CHUNK > real_chunks ? 1 : 0;
+    h_rowlb[t] = -INFINITY;
+  }
+  // the bounds: k set_row_bnds calls on basic rows, MAX_EDITS pending at a time
+  for (int t = 0; t < k; t++) {
+    if ((int)P->pending.size() == MAX_EDITS) {
+      for (const auto &e : P->pending) {
+        if (e.row <= m) launch_set_basic_bounds(P->d_blb, P->d_bub, e.row, e.lb, e.ub, f.stream());
+        else h_rowlb[e.row - m - 1] = e.lb;
+      }
+      P->pending.clear();
+    }
+    P->pending.push_back({m + 1 + t, rhs[t], INFINITY});
+  }
+  f.upload();
+  CutRowsArgs a;
+  a.T = P->d_T;
+  a.bvar = P->d_bvar; a.nvar = P->d_nvar;
+  a.blb = P->d_blb; a.bub = P->d_bub;
+  a.vals = (const double *)(db + o_vals);
+  a.rowcol = (const int *)(db + o_rowcol);
+  a.nbcol = (const int *)(db + o_nbcol);
+  a.rowlb = (const double *)(db + o_rowlb);
+  a.extra = (const int *)(db + o_extra);
+  a.m = m; a.n = n; a.ld = P->ld; a.k = k;
+  launch_cutrows(a, f.stream());
+  // host mirrors, once
+  for (int i = 1; i <= m; i++)
+    if (P->bvar[i] > m) P->bvar[i] += k;
+  for (int q = 1; q <= n; q++)
+    if (P->nvar[q] > m) P->nvar[q] += k;
+  P->bvar.resize((size_t)P->m + 1);
+  for (int t = 0; t < k; t++) P->bvar[(size_t)(m + 1 + t)] = m + 1 + t;
+  rebuild_pos(P);
+  P->hint_dual = true;
+  P->fresh_rows = P->sol_fresh ? m : std::min(P->fresh_rows, m);
+  P->sol_fresh = false;
+  f.fetch(); // the pinned block is free again
+  return 0;
+}
+
 void engine_recompute_cost_row(mvx_prob *P) {
   if (!P->valid) return;
   const int m = P->m, n = P->n;

@@ -48,6 +48,10 @@ int engine_dive_pick_many(const mvx_prob *root, const mvx_prob *const *Ps, int c
 int engine_set_obj_many(mvx_prob *const *Ps, int count, const double *c);
 int engine_pump_obj_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, const double *xprev, const int *has_prev,
                          const double *ab, int *info, double *xt, double *c);
+// a round of candidate cuts scored against a solved handle in one launch (k_cutgram: dot products with the column values x and
+// the Gram matrix), and `k` dense MVX_LO rows appended in one device pass (k_cutrows); see engine.cpp
+int engine_cut_scores(const mvx_prob *P, int k, const double *vals, const double *x, double *dot, double *gram);
+int engine_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rhs);
 // reduced-cost bound tightening of `count` solved handles, one launch (k_rcfix), and the bound lists of many handles applied
 // with one launch (k_setbnds, entries on non-basic positions only); see engine.cpp
 int engine_rc_tighten_many(const mvx_prob *const *Ps, int count, const double *cutoff, double tol, int *cnt, int *cols, double *lb,

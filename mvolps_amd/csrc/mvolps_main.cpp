@@ -78,6 +78,11 @@ int main(int argc, char **argv) {
               << "  --pump-freq F   with --pump: also pump at every branching node whose number F divides (default 0: the root only)\n"
               << "  --pump-alpha A  with --pump: weight of the model's objective in the first distance LP (0..1, default 0; times 0.9\n"
               << "                  with every further LP)\n"
+              << "  --cut-rounds [R] with --repaired: R rounds of GMI cuts on the root LP before the tree starts (1..64; 5 without a\n"
+              << "                  number): per round the cuts of all fractional integer columns, the most effective first, none\n"
+              << "                  nearly parallel to one already taken\n"
+              << "  --cut-round-max K with --cut-rounds: most cuts one round appends (1..4096, default 32)\n"
+              << "  --cut-maxpar P  with --cut-rounds: largest cosine between two cuts of a round (0 < P <= 1, default 0.9)\n"
               << "Help:\n  -h/--help\n";
     return 0;
   }
@@ -183,6 +188,27 @@ int main(int argc, char **argv) {
       return -1;
     }
   }
+  if (input.CMDOptionExists("--cut-rounds")) {
+    // the number is optional, as for --prop
+    const std::string &k = input.getCMDOption("--cut-rounds");
+    const bool numeric = !k.empty() && std::all_of(k.begin(), k.end(), [](char ch) { return ch >= '0' && ch <= '9'; });
+    const long kv = numeric ? std::strtol(k.c_str(), nullptr, 10) : 5;
+    params.cut_rounds = kv >= 1 && kv <= 64 ? (int)kv : -1;
+    if (params.cut_rounds < 1) {
+      std::fprintf(stderr, "Unknown parameter value for --cut-rounds\n");
+      return -1;
+    }
+  }
+  if (!int_opt("--cut-round-max", 1, 4096, &params.cut_round_max)) return -1;
+  if (input.CMDOptionExists("--cut-maxpar")) {
+    char *end = nullptr;
+    const std::string &k = input.getCMDOption("--cut-maxpar");
+    params.cut_maxpar = std::strtod(k.c_str(), &end);
+    if (k.empty() || *end != 0 || !(params.cut_maxpar > 0.0 && params.cut_maxpar <= 1.0)) {
+      std::fprintf(stderr, "Unknown parameter value for --cut-maxpar\n");
+      return -1;
+    }
+  }
   if (input.CMDOptionExists("--cut-select")) params.cut_select = std::atoi(input.getCMDOption("--cut-select").c_str());
   if (input.CMDOptionExists("--window")) params.window = std::atoi(input.getCMDOption("--window").c_str());
   if (input.CMDOptionExists("--best-window")) params.best_window = std::atoi(input.getCMDOption("--best-window").c_str());
@@ -193,15 +219,15 @@ int main(int argc, char **argv) {
   mvx_bnb_result res;
   const int brc = mvx_branchAndBound(nullptr, prob, &params, &res);
   if (brc == -1) {
-    std::fprintf(stderr, "-vs %d / --heur %d%s%s%s%s are not supported with these options (-vs 3 / 4: not with --best-window; --heur: only "
-                 "with --repaired; --rcfix / --prop / --dive / --pump: only with --repaired and without --best-window)\n", params.var_strat,
-                 params.heur, params.rc_fix ? " / --rcfix" : "", params.prop ? " / --prop" : "", params.dive ? " / --dive" : "",
-                 params.pump ? " / --pump" : "");
+    std::fprintf(stderr, "-vs %d / --heur %d%s%s%s%s%s are not supported with these options (-vs 3 / 4: not with --best-window; --heur: only "
+                 "with --repaired; --rcfix / --prop / --dive / --pump: only with --repaired and without --best-window; --cut-rounds: only with --repaired)\n",
+                 params.var_strat, params.heur, params.rc_fix ? " / --rcfix" : "", params.prop ? " / --prop" : "",
+                 params.dive ? " / --dive" : "", params.pump ? " / --pump" : "", params.cut_rounds ? " / --cut-rounds" : "");
     mvx_delete_prob(prob);
     return -1;
   }
   if (brc != 0)
-    std::fprintf(stderr, "branch-and-bound stopped: the branching penalties, the heuristic, the propagation, a pump or a dive could not be computed (%d)\n", brc);
+    std::fprintf(stderr, "branch-and-bound stopped: the branching penalties, the heuristic, the propagation, a pump, a dive or the root cut rounds could not be computed (%d)\n", brc);
   if (input.CMDOptionExists("--events")) mvx_bnb_write_events(&res, input.getCMDOption("--events").c_str());
   mvx_bnb_print_tree(&res, nullptr); // bs.cpp:329-343
   std::vector<char> buf(64 + 64 * (size_t)res.n);
@@ -225,6 +251,10 @@ int main(int argc, char **argv) {
     std::printf("Feasibility pump: %lld nodes, %lld with a feasible point, %lld improved the incumbent, %lld distance LPs, %lld pivots%s\n",
                 res.pump_calls, res.pump_found, res.pump_improved, res.pump_lps, res.pump_pivots,
                 res.incumbent_heur == 3 ? " (the final incumbent is one of them)" : "");
+  if (verbose && params.cut_rounds > 0)
+    std::printf("Root cut rounds: %lld rounds, %lld cuts made, %lld rows appended, %lld LPs, %lld pivots, root LP %.10g -> %.10g\n",
+                res.cutloop_rounds, res.cutloop_candidates, res.cutloop_rows, res.cutloop_lps, res.cutloop_pivots, res.cutloop_bound0,
+                res.cutloop_bound);
   const int limit = res.hit_limit || brc != 0;
   mvx_bnb_free_result(&res);
   mvx_delete_prob(prob);

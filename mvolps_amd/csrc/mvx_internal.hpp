@@ -372,6 +372,36 @@ struct PumpArgs {
   int n, count;
 };
 
+// arguments of k_cutgram (mvx_cut_scores): `k` candidate cut rows of n + 1 doubles each (entry 0 unused), the column values of
+// the solved handle they are scored on, and where dot[k] and the k x k Gram matrix go
+#define GRAM_TILE 16 // a workgroup holds GRAM_TILE x GRAM_TILE pairs (t, s), one per lane
+#define GRAM_COLS 64 // columns staged in LDS per pass
+struct CutGramArgs {
+  const double *vals; // [k][n+1]
+  const double *x;    // [n+1] column values by structural column
+  double *dot;        // [k]    sum_j v_tj x_j
+  double *gram;       // [k][k] sum_j v_tj v_sj
+  int k, n;
+};
+
+// arguments of k_cutrows (mvx_add_cut_rows): `k` dense rows appended behind row m of one tableau.  Row t (0-based) is
+// base_t + W_t . T over rows 1..m, where W_t[i] = vals[t][rowcol[i]] (0 where row i's basic variable is an auxiliary) and
+// base_t[q] = vals[t][nbcol[q]] (0 for a non-basic auxiliary), base_t[0] = vals[t][0], which the host has replaced by the row's
+// value at the non-basic point.  The kernel also does what k_add_rows does k times: the new rows' basic auxiliaries and bounds,
+// and the structural variable numbers moved up by k
+#define CUT_TILE 8 // cuts per lane: each T[i][j] is loaded once for that many new rows
+struct CutRowsArgs {
+  double *T;
+  int *bvar, *nvar;
+  double *blb, *bub;
+  const double *vals;  // [k][n+1]
+  const int *rowcol;   // [m+1] structural column basic in row i, 0 for an auxiliary
+  const int *nbcol;    // [n+1] structural column at non-basic position q, 0 for an auxiliary
+  const double *rowlb; // [k] lower bound of new row t on the device (-inf while its edit is still pending on the host)
+  const int *extra;    // [k] 1: the t-th single append would have summed a trailing chunk of zero weights (+0.0 added once more)
+  int m, n, ld, k;     // m: rows before the append
+};
+
 // k_setbnds (mvx_set_col_bnds_many, mvx_tighten_cols_many): per handle a range of bound writes and a range of shifts of column 0
 struct SetbHandle {
   double *T, *blb, *bub, *nlb, *nub;
@@ -425,6 +455,8 @@ void launch_prop(const PropArgs &a, hipStream_t);
 void launch_divepick(const DiveArgs &a, hipStream_t);
 void launch_objrow(const ObjNode *nodes, int n, int count, hipStream_t);
 void launch_pumpobj(const PumpArgs &a, hipStream_t);
+void launch_cutgram(const CutGramArgs &a, hipStream_t);
+void launch_cutrows(const CutRowsArgs &a, hipStream_t);
 void launch_setbnds(const SetbHandle *hs, const SetbEntry *es, const SetbShift *ss, int handles, hipStream_t);
 void launch_refresh_select(Ctl *, const int *tflag, int var, hipStream_t);
 size_t persist_lds_bytes(int m, int cpw);

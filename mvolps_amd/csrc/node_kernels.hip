@@ -1,6 +1,6 @@
 // node_kernels.hip -- gfx950 kernels of the batched node entries of branch and bound (engine.cpp: engine_*_many): GMI cuts,
 // classification, branching penalties, the rounding heuristic, reduced-cost tightening, bound propagation, bound lists, the
-// diving pick, objective replacement and the feasibility pump's step.  Each takes its arguments by value and the handles it works on as an array of descriptors (NodeRef and what
+// diving pick, objective replacement, the feasibility pump's step, and the scores and the batched append of a cut round.  Each takes its arguments by value and the handles it works on as an array of descriptors (NodeRef and what
 // the kernel needs beyond it, mvx_internal.hpp).  Same flags as kernels.hip: -ffp-contract=off, so every kernel has the bits
 // of its host twin.
 #include <hip/hip_runtime.h>
@@ -1014,6 +1014,138 @@ __global__ __launch_bounds__(256) void k_pumpobj(PumpArgs a) {
 
 void launch_pumpobj(const PumpArgs &a, hipStream_t s) {
   hipLaunchKernelGGL(k_pumpobj, dim3((unsigned)a.count), dim3(256), 0, s, a);
+}
+
+// ---------------------------------------------------------------------------- k_cutgram
+// Scores of a round of candidate cuts (mvx_cut_scores, DESIGN.md "Root cut rounds"): dot[t] = sum_j v_tj x_j and the Gram matrix
+// G[t][s] = sum_j v_tj v_sj, each sum over ascending j = 1..n from +0.0 with the product and the sum rounded separately -- the
+// host's efficacy loop, bit for bit.  One workgroup per GRAM_TILE x GRAM_TILE block of pairs with block row <= block column, one
+// lane per pair: the lane runs the whole serial sum of its pair, so nothing is reduced across lanes and there are no atomics.
+// The two row groups of the block are staged in LDS GRAM_COLS columns at a time; a row is padded by one double, so the 16
+// different rows a wave reads in one step fall on different banks (the row of the other operand is a broadcast).  A product
+// commutes, so the lane's sum is G[s][t] too and the same lane writes the mirror entry; on a diagonal block only the lanes with
+// t <= s write.  The lanes of the diagonal (t == s) also carry dot[t].
+__global__ __launch_bounds__(GRAM_TILE *GRAM_TILE) void k_cutgram(CutGramArgs a) {
+  if (blockIdx.y > blockIdx.x) return; // block row <= block column
+  __shared__ double s_a[GRAM_TILE][GRAM_COLS + 1], s_b[GRAM_TILE][GRAM_COLS + 1], s_x[GRAM_COLS];
+  const int ty = TIDX / GRAM_TILE, tx = TIDX % GRAM_TILE;
+  const int t0 = (int)blockIdx.y * GRAM_TILE, s0 = (int)blockIdx.x * GRAM_TILE;
+  const int t = t0 + ty, s = s0 + tx;
+  const int n = a.n, k = a.k;
+  const size_t row = (size_t)n + 1;
+  const bool diag = t == s; // only on a diagonal block
+  double acc = 0.0, dot = 0.0;
+  for (int j0 = 1; j0 <= n; j0 += GRAM_COLS) {
+    const int cnt = n - j0 + 1 < GRAM_COLS ? n - j0 + 1 : GRAM_COLS;
+    __syncthreads(); // the last pass's readers are done
+    for (int e = TIDX; e < GRAM_TILE * GRAM_COLS; e += GRAM_TILE * GRAM_TILE) {
+      const int r = e / GRAM_COLS, c = e % GRAM_COLS; // a wave loads 64 consecutive doubles of one row
+      const bool in = c < cnt;
+      s_a[r][c] = (in && t0 + r < k) ? a.vals[(size_t)(t0 + r) * row + (size_t)(j0 + c)] : 0.0;
+      s_b[r][c] = (in && s0 + r < k) ? a.vals[(size_t)(s0 + r) * row + (size_t)(j0 + c)] : 0.0;
+    }
+    if (TIDX < cnt) s_x[TIDX] = a.x[j0 + TIDX];
+    __syncthreads();
+    for (int c = 0; c < cnt; c++) {
+      const double va = s_a[ty][c];
+      acc = acc + va * s_b[tx][c];
+      if (diag) dot = dot + va * s_x[c];
+    }
+  }
+  if (t >= k || s >= k) return;
+  if (blockIdx.y == blockIdx.x && t > s) return;
+  a.gram[(size_t)t * (size_t)k + (size_t)s] = acc;
+  if (t != s) a.gram[(size_t)s * (size_t)k + (size_t)t] = acc;
+  else a.dot[t] = dot;
+}
+
+void launch_cutgram(const CutGramArgs &a, hipStream_t s) {
+  const unsigned nt = (unsigned)((a.k + GRAM_TILE - 1) / GRAM_TILE);
+  hipLaunchKernelGGL(k_cutgram, dim3(nt, nt), dim3(GRAM_TILE * GRAM_TILE), 0, s, a);
+}
+
+// ---------------------------------------------------------------------------- k_cutrows
+// k dense rows appended to one tableau in one pass (mvx_add_cut_rows, DESIGN.md "Root cut rounds").  A row that is appended to a
+// tableau is the combination base + sum_i w[i] T[i][.] of the rows whose basic variable is a structural column; the appended
+// rows are basic auxiliaries themselves, so none of the k rows depends on another and all of them read rows 1..m only.  The
+// arithmetic is k_rowcomb's, for every row: per 64-row chunk from row 1 an fma chain from +0.0 in ascending row order that
+// skips zero weights, the chunk sums added onto the base in chunk order.  The t-th of k single appends sums ceil((m + t) / 64)
+// chunks; those behind row m hold zero weights only and add +0.0, which turns a -0.0 into +0.0 and changes nothing else, so
+// one more `+ 0.0` where extra[t] says so leaves the same bits.
+// One workgroup per (256 columns, CUT_TILE rows): a lane owns a column and CUT_TILE accumulators, loads each T[i][j] once for
+// all of them (coalesced), and reads the chunk's weights from LDS, where the workgroup gathers them from `vals` once per chunk
+// (every lane reads the same word: a broadcast).  No partial buffer, no second launch.  The workgroups of the first tile row
+// also do the bookkeeping of k_add_rows; they write bvar / nvar / blb / bub, which no workgroup of this kernel reads.
+__global__ __launch_bounds__(256) void k_cutrows(CutRowsArgs a) {
+  __shared__ double s_w[CUT_TILE][ROWCOMB_CHUNK];
+  const int m = a.m, n = a.n, k = a.k;
+  const size_t ld = (size_t)a.ld, row = (size_t)n + 1;
+  const int t0 = (int)blockIdx.y * CUT_TILE;
+  const int nt = k - t0 < CUT_TILE ? k - t0 : CUT_TILE;
+  const int j = (int)blockIdx.x * 256 + TIDX;
+  const bool live = j <= n;
+  double out[CUT_TILE], acc[CUT_TILE];
+  {
+    const int col = live ? (j == 0 ? 0 : a.nbcol[j]) : 0;
+#pragma unroll
+    for (int c = 0; c < CUT_TILE; c++) out[c] = (live && c < nt && (j == 0 || col != 0)) ? a.vals[(size_t)(t0 + c) * row + (size_t)col] : 0.0;
+  }
+  const int nchunks = (m + ROWCOMB_CHUNK - 1) / ROWCOMB_CHUNK;
+  for (int ch = 0; ch < nchunks; ch++) {
+    const int i0 = 1 + ch * ROWCOMB_CHUNK;
+    const int cnt = m - i0 + 1 < ROWCOMB_CHUNK ? m - i0 + 1 : ROWCOMB_CHUNK;
+    __syncthreads(); // the last chunk's readers are done
+    for (int e = TIDX; e < CUT_TILE * ROWCOMB_CHUNK; e += 256) {
+      const int c = e / ROWCOMB_CHUNK, r = e % ROWCOMB_CHUNK;
+      double w = 0.0;
+      if (r < cnt && c < nt) {
+        const int col = a.rowcol[i0 + r];
+        if (col != 0) w = a.vals[(size_t)(t0 + c) * row + (size_t)col];
+      }
+      s_w[c][r] = w;
+    }
+    __syncthreads();
+    if (live) {
+#pragma unroll
+      for (int c = 0; c < CUT_TILE; c++) acc[c] = 0.0;
+      const double *Tj = a.T + (size_t)i0 * ld + (size_t)j;
+      for (int r = 0; r < cnt; r++) {
+        const double v = Tj[(size_t)r * ld];
+#pragma unroll
+        for (int c = 0; c < CUT_TILE; c++) {
+          const double w = s_w[c][r];
+          if (w != 0.0) acc[c] = fma(w, v, acc[c]);
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < CUT_TILE; c++) out[c] = out[c] + acc[c];
+    }
+  }
+  if (live) {
+#pragma unroll
+    for (int c = 0; c < CUT_TILE; c++)
+      if (c < nt) {
+        double o = out[c];
+        if (a.extra[t0 + c]) o = o + 0.0;
+        a.T[(size_t)(m + 1 + t0 + c) * ld + (size_t)j] = o;
+      }
+  }
+  if (blockIdx.y != 0) return;
+  // k_add_rows, k times over: the structural variable numbers move up by k, the new rows hold their own auxiliaries
+  const int span = (int)gridDim.x * 256;
+  for (int g = j; g <= m || g <= n || g < k; g += span) {
+    if (g >= 1 && g <= m && a.bvar[g] > m) a.bvar[g] += k;
+    if (g >= 1 && g <= n && a.nvar[g] > m) a.nvar[g] += k;
+    if (g < k) {
+      a.bvar[m + 1 + g] = m + 1 + g;
+      a.blb[m + 1 + g] = a.rowlb[g];
+      a.bub[m + 1 + g] = INFINITY;
+    }
+  }
+}
+
+void launch_cutrows(const CutRowsArgs &a, hipStream_t s) {
+  hipLaunchKernelGGL(k_cutrows, dim3((unsigned)((a.n + 1 + 255) / 256), (unsigned)((a.k + CUT_TILE - 1) / CUT_TILE)), dim3(256), 0, s, a);
 }
 
 } // namespace mvx
