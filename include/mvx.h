@@ -258,6 +258,15 @@ int mvx_cut_scores(const mvx_prob *P, int k, const double *vals, double *dot, do
    for the next solve.  Returns 0; -1 bad arguments, nothing changed (k < 1, a null, a NaN, a handle without a valid tableau);
    -2 device out of memory: the model has the rows, the tableau is given up as mvx_add_rows gives it up. */
 int mvx_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rhs);
+/* Clique cuts (DESIGN.md "Clique cuts (cut_families)"): the conflict graph of the binary columns of `model` (integer, bounds 0
+   and 1 exactly), two device launches (k_conflict_rows, k_conflict).  Columns j < k are adjacent when one of rows 1..m (m the
+   handle's row count) forbids x_j = x_k = 1 with every other term at its least: (Lmin_i + a_ij) + a_ik > rub_i + tol(rub_i) on
+   the upper side, the mirror on the lower side, the activities those of mvx_propagate_many at the handle's own bounds.  adj
+   holds (n+1) rows of W = ceil((n+1)/64) 64-bit words, bit k of row j being bit (k mod 64) of word k/64; row 0 and bit 0 are
+   zero, the relation is symmetric.  *edges the number of pairs j < k.  Pure: the handle need not be solved and does not change.
+   Bit-identical to mvx_bnb_conflict_graph (mvx_bnb.h).  Returns 0; -1 bad arguments; -2 device out of memory; -5 is kept for a
+   kernel with a size limit (the driver then runs the twin): k_conflict has none and never returns it. */
+int mvx_conflict_graph(const mvx_prob *model, unsigned long long *adj, long long *edges);
 
 /* ---- engine-state access (parity tests, visualisers) --------------------------- */
 int mvx_get_tableau_ld(const mvx_prob *P);

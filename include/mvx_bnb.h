@@ -120,6 +120,9 @@ typedef struct mvx_lp_api {
   /* optional (may be NULL): `k` dense MVX_LO rows appended in one call (mvx_add_cut_rows), the handle left as k times add_rows(1),
      set_mat_row, set_row_bnds leave it; without it the root cut loop appends row by row */
   int (*add_cut_rows)(void *P, int k, const double *vals, const double *rhs);
+  /* optional (may be NULL): the conflict graph of the binary columns of a handle in one call (mvx_conflict_graph; DESIGN.md
+     "Clique cuts (cut_families)"); without it, or when it returns -5, the host twin mvx_bnb_conflict_graph runs */
+  int (*conflict_graph)(const void *model, unsigned long long *adj, long long *edges);
 } mvx_lp_api;
 
 const mvx_lp_api *mvx_hip_lp_api(void);
@@ -189,6 +192,9 @@ typedef struct {
   int cut_round_max;    /* most cuts one round appends, 0..4096; 0 (default): 32 */
   double cut_maxpar;    /* a cut is taken when its cosine to every cut already taken in the round is at most this, in (0, 1];
                            0.0 (default): 0.9.  With cut_rounds = 0 neither this nor cut_round_max is read */
+  int cut_families;     /* the cut families of the root cut rounds (DESIGN.md "Clique cuts (cut_families)"), as bits: 1 the repaired
+                           GMI cuts, 2 clique cuts from the conflict graph of the binary columns; 0 (default) means 1.  Read only
+                           when cut_rounds > 0; a value outside 0..3 is then refused */
 } mvx_bnb_params;
 
 /* B&B events at the emit points of bs.cpp (message.h EventType) */
@@ -255,6 +261,9 @@ typedef struct {
   long long cutloop_pivots;     /* their pivots (not part of total_pivots; the root's own LP is among them) */
   double cutloop_bound0;        /* the root LP before the loop */
   double cutloop_bound;         /* the root LP after it (the last one that ended optimal) */
+  long long cutloop_conflicts;    /* cut_families & 2: edges of the conflict graph */
+  long long cutloop_clique_cands; /* ... violated cliques the separation kept, summed over the rounds (part of cutloop_candidates) */
+  long long cutloop_clique_rows;  /* ... clique rows appended (part of cutloop_rows) */
 } mvx_bnb_result;
 
 void mvx_bnb_default_params(mvx_bnb_params *p);
@@ -396,9 +405,28 @@ int mvx_bnb_cut_select(int k, const double *eff, const double *gram, int K, doub
    where the table has them, mvx_generateCutGMI, the twins and the per-row appends otherwise.  counters[0..4] = rounds, cuts
    made, rows appended, LPs solved, their pivots; bounds[0..1] = the LP before the loop and after it.  Returns 0; -1 bad
    arguments; -2 the table lacks an accessor, or a call of the table failed.  mvx_branchAndBound returns -1 (*res empty) for
-   cut_rounds outside 0..64, cut_round_max outside 0..4096, cut_maxpar outside (0, 1] other than 0.0 and cut_rounds > 0 with
-   reference_quirks = 1, and -2, with the unsolved root as the tree, when the loop could not be carried out */
+   cut_rounds outside 0..64, cut_round_max outside 0..4096, cut_maxpar outside (0, 1] other than 0.0, cut_families outside
+   0..3 (all three read only with cut_rounds > 0) and cut_rounds > 0 with reference_quirks = 1, and -2, with the unsolved root as the tree, when the loop could not be carried out */
 int mvx_bnb_cut_loop(const mvx_lp_api *api, void *prob, int rounds, int K, double maxpar, long long *counters, double *bounds);
+/* The same loop with the cut families chosen (bits: 1 GMI, 2 clique; 0 means 1; outside 0..3: -1): counters[0..7] = the five of
+   mvx_bnb_cut_loop, then the edges of the conflict graph, the cliques the separation kept, the clique rows appended.
+   mvx_bnb_cut_loop is this function with families = 1.  With bit 2 the graph is computed once at entry from `prob` as it is
+   handed in (conflict_graph of the table, the twin without it or on -5; any other failure ends the loop with -2) */
+int mvx_bnb_cut_loop_families(const mvx_lp_api *api, void *prob, int rounds, int K, double maxpar, int families, long long *counters,
+                              double *bounds);
+
+/* Clique cuts (DESIGN.md "Clique cuts (cut_families)"), host twin of mvx_conflict_graph through the table only (get_mat_row, row
+   and column bounds, get_col_kind): the same (n+1) x W words and edge count for the handle `model`, which need not be solved and
+   is not changed.  Returns 0; -1 bad arguments; -2 the table lacks an accessor it needs */
+int mvx_bnb_conflict_graph(const mvx_lp_api *api, const void *model, unsigned long long *adj, long long *edges);
+/* The separation, from numbers only: adj as above for n columns, x[1..n] the LP point.  The columns with a non-empty row of adj
+   are ordered by x descending (ties to the lower column); every one of them with x_j > 1e-6 is a seed, in that order.  A seed's
+   clique Q starts as {seed} with mask = adj[seed]; the whole order is walked, a column whose bit is set in mask joins Q and mask
+   &= adj[column] (zero-valued columns too: Q is maximal).  Q is kept when (sum of x_j over Q, ascending j from +0.0) - 1 > 1e-6
+   and no earlier seed gave the same set.  Kept clique t fills row t of vals (n + 1 entries, the layout of mvx_gmi_cuts) with -1
+   on Q and 0 elsewhere and rhs[t] = -1: the MVX_LO row sum_{j in Q} x_j <= 1.  Stops at max_cuts; *count the rows written.
+   Returns 0; -1 bad arguments (n < 0, max_cuts < 0, a null) */
+int mvx_bnb_clique_cuts(int n, const unsigned long long *adj, const double *x, int max_cuts, double *vals, double *rhs, int *count);
 
 /* bs.cpp:249-258 on one solved node `a` that is about to be branched: generate its GMI cut(s) and append the
    row(s) (cut_strat / reference_quirks / lazy_pool / cut_select / cut_chance of `params`).  Returns the number

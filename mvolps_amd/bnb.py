@@ -16,7 +16,7 @@ _FIELDS = [
 ]
 _OPTIONAL = ["simplex_batch", "get_obj_dir", "gmi_cuts", "gmi_cuts_many", "get_col_prim_all", "classify_many", "get_tableau", "get_basis",
              "branch_penalties_many", "round_many", "rc_tighten_many", "tighten_cols_many", "propagate_many", "set_col_bnds_many",
-             "dive_pick_many", "set_obj_coef", "set_obj_many", "pump_obj_many", "cut_scores", "add_cut_rows"]
+             "dive_pick_many", "set_obj_coef", "set_obj_many", "pump_obj_many", "cut_scores", "add_cut_rows", "conflict_graph"]
 
 
 class LpApiTable(C.Structure):
@@ -52,6 +52,7 @@ class BnbParams(C.Structure):
         ("cut_rounds", C.c_int),
         ("cut_round_max", C.c_int),
         ("cut_maxpar", C.c_double),
+        ("cut_families", C.c_int),
     ]
 
 
@@ -116,6 +117,9 @@ class BnbResult(C.Structure):
         ("cutloop_pivots", C.c_longlong),
         ("cutloop_bound0", C.c_double),
         ("cutloop_bound", C.c_double),
+        ("cutloop_conflicts", C.c_longlong),
+        ("cutloop_clique_cands", C.c_longlong),
+        ("cutloop_clique_rows", C.c_longlong),
     ]
 
 
@@ -201,6 +205,15 @@ def _bind(lib):
     lib.mvx_bnb_cut_select.argtypes = [C.c_int, _DP, _DP, C.c_int, C.c_double, C.c_int, _IP, _IP]
     lib.mvx_bnb_cut_loop.restype = C.c_int
     lib.mvx_bnb_cut_loop.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_longlong), _DP]
+    _UP, _LP = C.POINTER(C.c_ulonglong), C.POINTER(C.c_longlong)
+    lib.mvx_bnb_cut_loop_families.restype = C.c_int
+    lib.mvx_bnb_cut_loop_families.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, _LP, _DP]
+    lib.mvx_conflict_graph.restype = C.c_int
+    lib.mvx_conflict_graph.argtypes = [C.c_void_p, _UP, _LP]
+    lib.mvx_bnb_conflict_graph.restype = C.c_int
+    lib.mvx_bnb_conflict_graph.argtypes = [C.c_void_p, C.c_void_p, _UP, _LP]
+    lib.mvx_bnb_clique_cuts.restype = C.c_int
+    lib.mvx_bnb_clique_cuts.argtypes = [C.c_int, _UP, _DP, C.c_int, _DP, _DP, _IP]
     lib.mvx_generateCutGMI.restype = C.c_int
     lib.mvx_generateCutGMI.argtypes = [C.c_void_p, C.c_void_p, C.c_int, _IP, _DP, _DP, _DP]
     lib.mvx_generateCut3.restype = C.c_int
@@ -270,12 +283,16 @@ def result_to_dict(res):
         "cutloop_pivots": res.cutloop_pivots,
         "cutloop_bound0": res.cutloop_bound0,
         "cutloop_bound": res.cutloop_bound,
+        "cutloop_conflicts": res.cutloop_conflicts,
+        "cutloop_clique_cands": res.cutloop_clique_cands,
+        "cutloop_clique_rows": res.cutloop_clique_rows,
     }
 
 
 def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, window=None, cut_select=0, cut_chance=1.0,
                 best_window=None, sb_cands=None, sb_iters=None, heur=None, rc_fix=None, prop=None, dive=None, dive_freq=None,
-                dive_depth=None, pump=None, pump_freq=None, pump_alpha=None, cut_rounds=None, cut_round_max=None, cut_maxpar=None):
+                dive_depth=None, pump=None, pump_freq=None, pump_alpha=None, cut_rounds=None, cut_round_max=None, cut_maxpar=None,
+                cut_families=None):
     """mvx_bnb_params with ParameterObj's defaults (util.h:65-67) overridden by the arguments (None: the default)."""
     pr = BnbParams()
     lib().mvx_bnb_default_params(C.byref(pr))
@@ -314,13 +331,15 @@ def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, l
         pr.cut_round_max = cut_round_max
     if cut_maxpar is not None:
         pr.cut_maxpar = cut_maxpar
+    if cut_families is not None:
+        pr.cut_families = cut_families
     return pr
 
 
 def branch_and_bound(prob, var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, table=None, window=None,
                      cut_select=0, cut_chance=1.0, best_window=None, sb_cands=None, sb_iters=None, heur=None, rc_fix=None, prop=None,
                      dive=None, dive_freq=None, dive_depth=None, pump=None, pump_freq=None, pump_alpha=None, cut_rounds=None,
-                     cut_round_max=None, cut_maxpar=None):
+                     cut_round_max=None, cut_maxpar=None, cut_families=None):
     """Run the driver on `prob` (a capi.Prob).  table=None uses the gfx950 engine's own table.  best_window > 1 with
     node_strat=1: the speculative best-bound window (mvx_bnb_params.best_window).  var_strat 3 / 4: branching on the node
     LP's penalties / strong branching (sb_cands candidates, sb_iters pivots per child).  heur 1 / 2: the primal rounding
@@ -333,13 +352,14 @@ def branch_and_bound(prob, var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, 
     divides, behind the rounding heuristic and in front of the dives; pump_alpha (0..1) weighs the model's objective into the
     distance LPs (quirks=0, not with best_window).  cut_rounds 1..64: that many rounds of GMI cuts on the root LP before the
     tree starts, at most cut_round_max (default 32) cuts a round, none more than cut_maxpar (default 0.9) parallel to one
-    taken before it in the round (quirks=0; every single-GPU driver).  The
+    taken before it in the round (quirks=0; every single-GPU driver); cut_families chooses the families of those rounds as bits, 1 GMI
+    (the default), 2 clique cuts from the conflict graph of the binary columns.  The
     dictionary's "rc" is mvx_branchAndBound's return code (-1 refused parameters, -2 penalties, heuristic, tightening,
     propagation, pumps or dives unavailable)."""
     L = lib()
     pr = make_params(var_strat, node_strat, cut_strat, max_nodes, quirks, lazy_pool, window, cut_select, cut_chance, best_window, sb_cands,
                      sb_iters, heur, rc_fix, prop, dive, dive_freq, dive_depth, pump, pump_freq, pump_alpha, cut_rounds, cut_round_max,
-                     cut_maxpar)
+                     cut_maxpar, cut_families)
     res = BnbResult()
     tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
     rc = L.mvx_branchAndBound(tptr, prob.h, C.byref(pr), C.byref(res))
@@ -733,6 +753,7 @@ def pump_node(prob, root, iters=30, alpha=0.0, table=None):
 
 
 CUTLOOP_COUNTERS = ("cutloop_rounds", "cutloop_candidates", "cutloop_rows", "cutloop_lps", "cutloop_pivots")
+CLIQUE_COUNTERS = ("cutloop_conflicts", "cutloop_clique_cands", "cutloop_clique_rows")
 
 
 def cut_scores(prob, vals, table=False):
@@ -782,16 +803,79 @@ def add_cut_rows(prob, vals, rhs):
     return lib().mvx_add_cut_rows(prob.h, k, v.ctypes.data_as(DP), r.ctypes.data_as(DP))
 
 
-def cut_loop(prob, rounds=5, K=0, maxpar=0.0, table=None):
+def cut_loop(prob, rounds=5, K=0, maxpar=0.0, table=None, families=None):
     """mvx_bnb_cut_loop: the root cut loop on the handle `prob`, which is edited in place, through `table` (None = the gfx950
-    engine's table, whose batched entries then run).  Returns (rc, dictionary of the cutloop_* counters and bounds)."""
-    cnt = (C.c_longlong * 5)()
+    engine's table, whose batched entries then run).  Returns (rc, dictionary of the cutloop_* counters and bounds).
+    families (bits: 1 GMI, 2 clique) goes through mvx_bnb_cut_loop_families, and the dictionary then has CLIQUE_COUNTERS too."""
+    cnt = (C.c_longlong * 8)()
     bnd = (C.c_double * 2)()
     tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
-    rc = lib().mvx_bnb_cut_loop(tptr, prob.h, rounds, K, maxpar, cnt, bnd)
-    out = {name: int(cnt[i]) for i, name in enumerate(CUTLOOP_COUNTERS)}
+    names = CUTLOOP_COUNTERS
+    if families is None:
+        rc = lib().mvx_bnb_cut_loop(tptr, prob.h, rounds, K, maxpar, cnt, bnd)
+    else:
+        rc = lib().mvx_bnb_cut_loop_families(tptr, prob.h, rounds, K, maxpar, families, cnt, bnd)
+        names = CUTLOOP_COUNTERS + CLIQUE_COUNTERS
+    out = {name: int(cnt[i]) for i, name in enumerate(names)}
     out["cutloop_bound0"], out["cutloop_bound"] = bnd[0], bnd[1]
     return rc, out
+
+
+def conflict_graph(prob, table=False):
+    """The conflict graph of the binary columns of the handle `prob` (DESIGN.md "Clique cuts (cut_families)"): (rc, boolean
+    (n + 1) x (n + 1) array, edges); row 0 and column 0 are empty.  table=False: mvx_conflict_graph, the gfx950 engine's kernels;
+    otherwise the host twin mvx_bnb_conflict_graph through `table` (None = the gfx950 engine's table)."""
+    rc, words, edges = conflict_words(prob, table)
+    return rc, words_to_bool(words, prob.n), edges
+
+
+def conflict_words(prob, table=False):
+    """conflict_graph's words as the library writes them: (rc, uint64 array (n + 1, W), edges)."""
+    import numpy as np
+
+    n = prob.n
+    words = np.zeros((n + 1, (n + 1 + 63) // 64), dtype=np.uint64)
+    edges = C.c_longlong(0)
+    UP = C.POINTER(C.c_ulonglong)
+    if table is False:
+        rc = lib().mvx_conflict_graph(prob.h, words.ctypes.data_as(UP), C.byref(edges))
+    else:
+        tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
+        rc = lib().mvx_bnb_conflict_graph(tptr, prob.h, words.ctypes.data_as(UP), C.byref(edges))
+    return rc, words, edges.value
+
+
+def words_to_bool(words, n):
+    import numpy as np
+
+    bits = np.unpackbits(np.ascontiguousarray(words).view(np.uint8), axis=1, bitorder="little")
+    return bits[:, : n + 1].astype(bool)
+
+
+def bool_to_words(adj):
+    import numpy as np
+
+    a = np.asarray(adj, dtype=bool)
+    W = (a.shape[1] + 63) // 64
+    padded = np.zeros((a.shape[0], W * 64), dtype=np.uint8)
+    padded[:, : a.shape[1]] = a
+    return np.ascontiguousarray(np.packbits(padded, axis=1, bitorder="little")).view(np.uint64)
+
+
+def clique_cuts(adj, x, max_cuts):
+    """mvx_bnb_clique_cuts, the clique separation from numbers only: adj the boolean (n + 1) x (n + 1) array of conflict_graph,
+    x the LP point (n + 1 entries, entry 0 unused).  Returns (rc, vals array (count, n + 1), rhs array of count)."""
+    import numpy as np
+
+    words = bool_to_words(adj)
+    n = words.shape[0] - 1
+    xs = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
+    vals, rhs = np.zeros((max(1, max_cuts), n + 1)), np.zeros(max(1, max_cuts))
+    cnt = C.c_int(0)
+    DP = C.POINTER(C.c_double)
+    rc = lib().mvx_bnb_clique_cuts(n, words.ctypes.data_as(C.POINTER(C.c_ulonglong)), xs.ctypes.data_as(DP), max_cuts, vals.ctypes.data_as(DP),
+                                   rhs.ctypes.data_as(DP), C.byref(cnt))
+    return rc, vals[: cnt.value], rhs[: cnt.value]
 
 
 def generate_cut_gmi(prob, j, table=None):

@@ -50,6 +50,7 @@ extern "C" int mvx_pump_obj_many(const mvx_prob *root, const mvx_prob *const *Ps
 
 extern "C" int mvx_cut_scores(const mvx_prob *P, int k, const double *vals, double *dot, double *gram) __attribute__((weak));
 extern "C" int mvx_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rhs) __attribute__((weak));
+extern "C" int mvx_conflict_graph(const mvx_prob *model, unsigned long long *adj, long long *edges) __attribute__((weak));
 
 namespace {
 
@@ -3101,6 +3102,9 @@ const mvx_lp_api g_hip_api = {
     } : nullptr,
     mvx_add_cut_rows ? +[](void *P, int k, const double *vals, const double *rhs) { return mvx_add_cut_rows((mvx_prob *)P, k, vals, rhs); }
                      : nullptr,
+    mvx_conflict_graph ? +[](const void *model, unsigned long long *adj, long long *edges) {
+      return mvx_conflict_graph((const mvx_prob *)model, adj, edges);
+    } : nullptr,
 };
 
 } // namespace
@@ -3135,6 +3139,7 @@ void mvx_bnb_default_params(mvx_bnb_params *p) {
   p->cut_rounds = 0;
   p->cut_round_max = 0;
   p->cut_maxpar = 0.0;
+  p->cut_families = 0;
 }
 
 // Repaired mode's rule for an integer column whose bounds are not integers (legal input: LP and MPS files may carry them):
@@ -3218,8 +3223,107 @@ static std::vector<int> cut_select(int k, const double *eff, const double *gram,
   return taken;
 }
 
+// ---- clique cuts (cut_families bit 2, DESIGN.md "Clique cuts (cut_families)") ----
+
+// The conflict graph of the binary columns of `P` through the table (the host twin of k_conflict_rows / k_conflict: the
+// activities are step 1 of prop_host at the handle's own bounds, every product and sum rounded on its own, and a pair's test
+// adds the lower column's coefficient first).  adj: (n+1) x W words.
+static int conflict_graph_host(const mvx_lp_api *api, const void *P, unsigned long long *adj, long long *edges) {
+  PropHost M;
+  if (prop_host_model(api, P, M) != 0) return -2;
+  const int n = M.n, m0 = M.m0;
+  const size_t W = ((size_t)n + 1 + 63) / 64;
+  std::vector<double> l((size_t)n + 1, 0.0), u((size_t)n + 1, 0.0);
+  std::vector<char> inB((size_t)n + 1, 0);
+  for (int j = 1; j <= n; j++) {
+    l[(size_t)j] = tab_bound(api->get_col_lb(P, j));
+    u[(size_t)j] = tab_bound(api->get_col_ub(P, j));
+    inB[(size_t)j] = M.isint[(size_t)j] && l[(size_t)j] == 0.0 && u[(size_t)j] == 1.0;
+  }
+  std::fill(adj, adj + ((size_t)n + 1) * W, 0ULL);
+  auto set = [&](int j, int k) {
+    adj[(size_t)j * W + (size_t)k / 64] |= 1ULL << (k % 64);
+    adj[(size_t)k * W + (size_t)j / 64] |= 1ULL << (j % 64);
+  };
+  std::vector<std::pair<int, double>> pos, neg;
+  for (int i = 0; i < m0; i++) {
+    double lmin = 0.0, lmax = 0.0;
+    int kmin = 0, kmax = 0;
+    for (const auto &e : M.rows[(size_t)i]) {
+      const double v = e.second;
+      const double bmin = v > 0.0 ? l[(size_t)e.first] : u[(size_t)e.first], bmax = v > 0.0 ? u[(size_t)e.first] : l[(size_t)e.first];
+      if (std::isinf(bmin)) kmin++;
+      else lmin = lmin + v * bmin;
+      if (std::isinf(bmax)) kmax++;
+      else lmax = lmax + v * bmax;
+    }
+    const double lo = M.rlo[(size_t)i], hi = M.rhi[(size_t)i];
+    const bool upper = kmin == 0 && std::isfinite(hi), lower = kmax == 0 && std::isfinite(lo);
+    if (!upper && !lower) continue;
+    pos.clear();
+    neg.clear();
+    for (const auto &e : M.rows[(size_t)i])
+      if (inB[(size_t)e.first]) (e.second > 0.0 ? pos : neg).push_back(e);
+    if (upper) {
+      const double thr = hi + round_tol(hi);
+      for (size_t a = 0; a < pos.size(); a++) {
+        const double first = lmin + pos[a].second;
+        for (size_t b = a + 1; b < pos.size(); b++)
+          if (first + pos[b].second > thr) set(pos[a].first, pos[b].first);
+      }
+    }
+    if (lower) {
+      const double thr = lo - round_tol(lo);
+      for (size_t a = 0; a < neg.size(); a++) {
+        const double first = lmax + neg[a].second;
+        for (size_t b = a + 1; b < neg.size(); b++)
+          if (first + neg[b].second < thr) set(neg[a].first, neg[b].first);
+      }
+    }
+  }
+  long long bits = 0;
+  for (size_t w = 0; w < ((size_t)n + 1) * W; w++) bits += __builtin_popcountll(adj[w]);
+  *edges = bits / 2;
+  return 0;
+}
+
+// The separation, from numbers only: greedy maximal cliques around the LP point, one per seed, the violated ones kept once
+// each, at most max_cuts.  A clique is its columns in ascending order.
+static std::vector<std::vector<int>> clique_cuts(int n, const unsigned long long *adj, const double *x, int max_cuts) {
+  const size_t W = ((size_t)n + 1 + 63) / 64;
+  std::vector<int> order;
+  for (int j = 1; j <= n; j++)
+    for (size_t w = 0; w < W; w++)
+      if (adj[(size_t)j * W + w]) {
+        order.push_back(j);
+        break;
+      }
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return x[a] > x[b]; });
+  std::vector<std::vector<int>> kept;
+  std::vector<unsigned long long> mask(W);
+  for (int seed : order) {
+    if ((int)kept.size() >= max_cuts) break;
+    if (!(x[seed] > 1e-6)) continue;
+    std::copy(adj + (size_t)seed * W, adj + (size_t)(seed + 1) * W, mask.begin());
+    std::vector<int> Q(1, seed);
+    for (int c : order) {
+      if (!((mask[(size_t)c / 64] >> (c % 64)) & 1ULL)) continue;
+      Q.push_back(c);
+      for (size_t w = 0; w < W; w++) mask[w] &= adj[(size_t)c * W + w];
+    }
+    std::sort(Q.begin(), Q.end());
+    double s = 0.0;
+    for (int j : Q) s = s + x[j];
+    if (!(s - 1.0 > 1e-6)) continue;
+    if (std::find(kept.begin(), kept.end(), Q) != kept.end()) continue;
+    kept.push_back(std::move(Q));
+  }
+  return kept;
+}
+
 struct CutLoopOut {
   long long rounds = 0, candidates = 0, rows = 0, lps = 0, pivots = 0;
+  long long conflicts = 0, clique_cands = 0, clique_rows = 0;
   double bound0 = 0.0, bound = 0.0;
   void store(mvx_bnb_result *res) const {
     res->cutloop_rounds = rounds;
@@ -3229,6 +3333,9 @@ struct CutLoopOut {
     res->cutloop_pivots = pivots;
     res->cutloop_bound0 = bound0;
     res->cutloop_bound = bound;
+    res->cutloop_conflicts = conflicts;
+    res->cutloop_clique_cands = clique_cands;
+    res->cutloop_clique_rows = clique_rows;
   }
 };
 
@@ -3240,8 +3347,9 @@ struct CutLoopOut {
 constexpr double CUT_MAX_RANGE = 1e9;
 
 // The loop on `P`, edited in place: first solve, then up to R rounds of (candidates, scores, selection, append, re-solve).
+// `families`: bit 1 the repaired GMI cuts, bit 2 clique cuts out of the conflict graph of `P` as it is handed in (0 means 1).
 // Returns 0; -2 when the table lacks an accessor or one of its calls failed.
-static int cut_loop(const mvx_lp_api *api, void *P, int R, int K, double maxpar, CutLoopOut &o) {
+static int cut_loop(const mvx_lp_api *api, void *P, int R, int K, double maxpar, int families, CutLoopOut &o) {
   if (!api->add_rows || !api->set_mat_row || !api->set_row_bnds || !api->simplex || !api->get_status || !api->get_obj_val ||
       !api->get_col_prim || !api->get_num_rows || !api->get_num_cols || !api->get_col_kind || !api->get_col_stat || !api->get_it_cnt ||
       !api->eval_tab_row || !api->get_mat_row)
@@ -3251,6 +3359,15 @@ static int cut_loop(const mvx_lp_api *api, void *P, int R, int K, double maxpar,
   const int n = api->get_num_cols(P);
   const size_t row = (size_t)n + 1;
   const int budget = std::max(64, api->get_num_rows(P));
+  if (families == 0) families = 1;
+  // the conflict graph, once, from the rows the handle has before any cut: the table's entry, the twin without it or on -5
+  std::vector<unsigned long long> adj;
+  if (families & 2) {
+    adj.assign(row * ((row + 63) / 64), 0ULL);
+    int grc = api->conflict_graph ? api->conflict_graph(P, adj.data(), &o.conflicts) : -5;
+    if (grc == -5) grc = conflict_graph_host(api, P, adj.data(), &o.conflicts);
+    if (grc != 0) return -2;
+  }
   auto solve_lp = [&]() {
     const int before = api->get_it_cnt(P);
     api->simplex(P, nullptr);
@@ -3267,11 +3384,23 @@ static int cut_loop(const mvx_lp_api *api, void *P, int R, int K, double maxpar,
     for (int j = 1; j <= n; j++)
       if (gmi_candidate(api, P, j)) cols.push_back(j);
     if (cols.empty()) break; // the root LP is integral
-    const int k = (int)cols.size();
+    std::vector<double> x(row, 0.0);
+    for (int j = 1; j <= n; j++) x[(size_t)j] = api->get_col_prim(P, j);
+    // the GMI candidates first, the cliques of this LP point behind them: ties in efficacy go to the lower index
+    const int kg = (families & 1) ? (int)cols.size() : 0;
+    std::vector<std::vector<int>> cliques;
+    if ((families & 2) && o.conflicts > 0) cliques = clique_cuts(n, adj.data(), x.data(), 4 * K);
+    o.clique_cands += (long long)cliques.size();
+    const int k = kg + (int)cliques.size();
     std::vector<double> vals((size_t)k * row, 0.0), rhs((size_t)k, 0.0);
     std::vector<int> ok((size_t)k, 0);
-    if (!api->gmi_cuts || api->gmi_cuts(P, 1, cols.data(), k, vals.data(), rhs.data(), ok.data()) != 0) {
-      for (int t = 0; t < k; t++) {
+    for (size_t q = 0; q < cliques.size(); q++) {
+      for (int j : cliques[q]) vals[((size_t)kg + q) * row + (size_t)j] = -1.0;
+      rhs[(size_t)kg + q] = -1.0;
+      ok[(size_t)kg + q] = 1;
+    }
+    if (kg > 0 && (!api->gmi_cuts || api->gmi_cuts(P, 1, cols.data(), kg, vals.data(), rhs.data(), ok.data()) != 0)) {
+      for (int t = 0; t < kg; t++) {
         double e = 0.0;
         CutContainer c = generateCutGMI(api, P, cols[(size_t)t], &e);
         ok[(size_t)t] = c.oid != -1;
@@ -3281,8 +3410,6 @@ static int cut_loop(const mvx_lp_api *api, void *P, int R, int K, double maxpar,
       }
     }
     // 2. scores: efficacy at the LP point, as cuts_via_engine computes it
-    std::vector<double> x(row, 0.0);
-    for (int j = 1; j <= n; j++) x[(size_t)j] = api->get_col_prim(P, j);
     std::vector<int> live;
     std::vector<double> eff((size_t)k, 0.0);
     for (int t = 0; t < k; t++) {
@@ -3326,6 +3453,7 @@ static int cut_loop(const mvx_lp_api *api, void *P, int R, int K, double maxpar,
       std::copy(sv.begin() + (long)((size_t)taken[(size_t)t] * row), sv.begin() + (long)((size_t)(taken[(size_t)t] + 1) * row),
                 tv.begin() + (long)((size_t)t * row));
       tr[(size_t)t] = rhs[(size_t)live[(size_t)taken[(size_t)t]]];
+      if (live[(size_t)taken[(size_t)t]] >= kg) o.clique_rows++;
     }
     int arc = -1;
     if (api->add_cut_rows) arc = api->add_cut_rows(P, nt, tv.data(), tr.data());
@@ -3367,7 +3495,8 @@ int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *
       // root cut rounds: repaired cuts only; every single-GPU driver runs behind them
       params->cut_rounds < 0 || params->cut_rounds > 64 ||
       (params->cut_rounds > 0 && (params->reference_quirks != 0 || params->cut_round_max < 0 || params->cut_round_max > 4096 ||
-                                  !(params->cut_maxpar == 0.0 || (params->cut_maxpar > 0.0 && params->cut_maxpar <= 1.0))))) {
+                                  !(params->cut_maxpar == 0.0 || (params->cut_maxpar > 0.0 && params->cut_maxpar <= 1.0)) ||
+                                  params->cut_families < 0 || params->cut_families > 3))) {
     std::memset(res, 0, sizeof(*res));
     return -1;
   }
@@ -3389,7 +3518,7 @@ int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *
       void *model = api->create_prob();
       api->copy_prob(model, work, MVX_OFF);
       CutLoopOut lo;
-      int r = cut_loop(api, work, params->cut_rounds, params->cut_round_max, params->cut_maxpar, lo);
+      int r = cut_loop(api, work, params->cut_rounds, params->cut_round_max, params->cut_maxpar, params->cut_families, lo);
       if (r != 0) {
         infeasible_root(MVOLP::NONE); // the loop could not run: the tree so far is the unsolved root
         r = -2;
@@ -3616,16 +3745,46 @@ int mvx_bnb_cut_select(int k, const double *eff, const double *gram, int K, doub
   return 0;
 }
 
-int mvx_bnb_cut_loop(const mvx_lp_api *api, void *prob, int rounds, int K, double maxpar, long long *counters, double *bounds) {
+int mvx_bnb_cut_loop_families(const mvx_lp_api *api, void *prob, int rounds, int K, double maxpar, int families, long long *counters,
+                              double *bounds) {
   if (!api) api = &g_hip_api;
-  if (!prob || rounds < 1 || rounds > 64 || K < 0 || K > 4096 || !(maxpar == 0.0 || (maxpar > 0.0 && maxpar <= 1.0)) || !counters ||
-      !bounds)
+  if (!prob || rounds < 1 || rounds > 64 || K < 0 || K > 4096 || !(maxpar == 0.0 || (maxpar > 0.0 && maxpar <= 1.0)) || families < 0 ||
+      families > 3 || !counters || !bounds)
     return -1;
   CutLoopOut lo;
-  const int rc = cut_loop(api, prob, rounds, K, maxpar, lo);
+  const int rc = cut_loop(api, prob, rounds, K, maxpar, families, lo);
   counters[0] = lo.rounds; counters[1] = lo.candidates; counters[2] = lo.rows; counters[3] = lo.lps; counters[4] = lo.pivots;
+  counters[5] = lo.conflicts; counters[6] = lo.clique_cands; counters[7] = lo.clique_rows;
   bounds[0] = lo.bound0; bounds[1] = lo.bound;
   return rc;
+}
+
+int mvx_bnb_cut_loop(const mvx_lp_api *api, void *prob, int rounds, int K, double maxpar, long long *counters, double *bounds) {
+  if (!counters) return -1;
+  long long all[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const int rc = mvx_bnb_cut_loop_families(api, prob, rounds, K, maxpar, 1, all, bounds);
+  if (rc != -1) std::copy(all, all + 5, counters);
+  return rc;
+}
+
+int mvx_bnb_conflict_graph(const mvx_lp_api *api, const void *model, unsigned long long *adj, long long *edges) {
+  if (!api) api = &g_hip_api;
+  if (!model || !adj || !edges) return -1;
+  *edges = 0;
+  return conflict_graph_host(api, model, adj, edges);
+}
+
+int mvx_bnb_clique_cuts(int n, const unsigned long long *adj, const double *x, int max_cuts, double *vals, double *rhs, int *count) {
+  if (n < 0 || max_cuts < 0 || !adj || !x || !count || (max_cuts > 0 && (!vals || !rhs))) return -1;
+  const std::vector<std::vector<int>> got = clique_cuts(n, adj, x, max_cuts);
+  const size_t row = (size_t)n + 1;
+  for (size_t t = 0; t < got.size(); t++) {
+    std::fill(vals + t * row, vals + (t + 1) * row, 0.0);
+    for (int j : got[t]) vals[t * row + (size_t)j] = -1.0;
+    rhs[t] = -1.0;
+  }
+  *count = (int)got.size();
+  return 0;
 }
 
 int mvx_bnb_node_cuts(const mvx_lp_api *api, void *a, const mvx_bnb_params *params) {

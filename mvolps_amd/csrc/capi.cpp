@@ -544,6 +544,9 @@ int mvx_cut_scores(const mvx_prob *P, int k, const double *vals, double *dot, do
   return mvx::engine_cut_scores(P, k, vals, x.data(), dot, gram);
 }
 int mvx_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rhs) { return mvx::engine_add_cut_rows(P, k, vals, rhs); }
+int mvx_conflict_graph(const mvx_prob *model, unsigned long long *adj, long long *edges) {
+  return mvx::engine_conflict_graph(model, adj, edges);
+}
 
 int mvx_device_count(void) { return mvx::device_count(); }
 int mvx_set_device(int dev) { return mvx::set_device(dev); }

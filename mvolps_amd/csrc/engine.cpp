@@ -3032,6 +3032,40 @@ int engine_propagate_many(const mvx_prob *root, const mvx_prob *const *Ps, int c
   return 0;
 }
 
+// ------------------------------------------------------------------ conflict graph (k_conflict_rows, k_conflict)
+// The conflict graph of the binary columns of `R` (mvx_conflict_graph): the model is the one k_prop reads (both orientations,
+// uploaded on first use and kept with the handle), nothing goes up with the call, two launches, the words come back and the
+// edges are counted here.  Return codes: 0; -1 bad arguments; -2 device out of memory.
+int engine_conflict_graph(const mvx_prob *R, unsigned long long *adj, long long *edges) {
+  if (!R || !adj || !edges) return -1;
+  const int n = R->n, m0 = R->m;
+  NodeCall f(NodeFlush::Never, NodeResults::Device);
+  const RoundModel *M = round_model(*f.c, R);
+  if (!M || !round_model_rows(*f.c, R, R->rmod.get())) return -2;
+  const size_t W = ((size_t)n + 1 + 63) / 64, words = ((size_t)n + 1) * W;
+  // back: [adj]; device only: [rowinfo]
+  const size_t o_adj = f.out(words * 8);
+  const size_t o_info = f.dev((size_t)std::max(1, m0) * 4 * 8);
+  if (!f.reserve()) return -2;
+  const unsigned char *mb = (const unsigned char *)M->dev;
+  ConflictArgs a;
+  a.At = (const double *)mb;
+  a.Ar = (const double *)M->dev_rows;
+  a.rlo = (const double *)(mb + M->o_rlo); a.rhi = (const double *)(mb + M->o_rhi);
+  a.clo = (const double *)(mb + M->o_clo); a.chi = (const double *)(mb + M->o_chi);
+  a.flags = (const int *)(mb + M->o_flags);
+  a.rowinfo = (double *)(f.db + o_info);
+  a.adj = (unsigned long long *)(f.db + o_adj);
+  a.n = n; a.m0 = m0; a.ldm = M->ldm; a.ldn = M->ldn; a.W = (int)W; a.pad = 0;
+  launch_conflict(a, f.stream());
+  f.fetch();
+  std::memcpy(adj, f.hb + o_adj, words * 8);
+  long long bits = 0;
+  for (size_t w = 0; w < words; w++) bits += __builtin_popcountll(adj[w]);
+  *edges = bits / 2;
+  return 0;
+}
+
 // ------------------------------------------------------------------ bound lists (k_setbnds)
 // What the two bound-list entries check alike, before anything is edited: 1 go on, 0 nothing to do, -1 a bad list.  `general`
 // (mvx_set_col_bnds_many): infinite bounds are allowed, a handle listed twice is not; else (mvx_tighten_cols_many) the

@@ -83,6 +83,8 @@ int main(int argc, char **argv) {
               << "                  nearly parallel to one already taken\n"
               << "  --cut-round-max K with --cut-rounds: most cuts one round appends (1..4096, default 32)\n"
               << "  --cut-maxpar P  with --cut-rounds: largest cosine between two cuts of a round (0 < P <= 1, default 0.9)\n"
+              << "  --cut-families F with --cut-rounds: the cut families as bits (1..3, default 1): 1 GMI cuts, 2 clique cuts from the\n"
+              << "                  conflict graph of the binary columns\n"
               << "Help:\n  -h/--help\n";
     return 0;
   }
@@ -209,6 +211,7 @@ int main(int argc, char **argv) {
       return -1;
     }
   }
+  if (!int_opt("--cut-families", 1, 3, &params.cut_families)) return -1;
   if (input.CMDOptionExists("--cut-select")) params.cut_select = std::atoi(input.getCMDOption("--cut-select").c_str());
   if (input.CMDOptionExists("--window")) params.window = std::atoi(input.getCMDOption("--window").c_str());
   if (input.CMDOptionExists("--best-window")) params.best_window = std::atoi(input.getCMDOption("--best-window").c_str());
@@ -255,6 +258,9 @@ int main(int argc, char **argv) {
     std::printf("Root cut rounds: %lld rounds, %lld cuts made, %lld rows appended, %lld LPs, %lld pivots, root LP %.10g -> %.10g\n",
                 res.cutloop_rounds, res.cutloop_candidates, res.cutloop_rows, res.cutloop_lps, res.cutloop_pivots, res.cutloop_bound0,
                 res.cutloop_bound);
+  if (verbose && params.cut_rounds > 0 && (params.cut_families & 2))
+    std::printf("Clique cuts: %lld conflicts, %lld violated cliques, %lld rows appended\n", res.cutloop_conflicts, res.cutloop_clique_cands,
+                res.cutloop_clique_rows);
   const int limit = res.hit_limit || brc != 0;
   mvx_bnb_free_result(&res);
   mvx_delete_prob(prob);

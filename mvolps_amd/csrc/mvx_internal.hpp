@@ -402,6 +402,21 @@ struct CutRowsArgs {
   int m, n, ld, k;     // m: rows before the append
 };
 
+// arguments of k_conflict_rows / k_conflict (mvx_conflict_graph): the model of one handle as k_prop reads it -- its rows by
+// column (At) and by row (Ar), the row bounds, the RND_INT flags and the handle's own column bounds -- the per-row numbers the
+// first kernel leaves for the second, and the adjacency words
+#define CONF_WAVES 4 // waves of a k_conflict workgroup: one column, CONF_WAVES consecutive words of its row
+struct ConflictArgs {
+  const double *At;        // [n+1][ldm]: At[j*ldm + i] = a_(i+1),j
+  const double *Ar;        // [m0][ldn]: Ar[i*ldn + j] = a_(i+1),j; ldn = 64 * W, the padding is zero
+  const double *rlo, *rhi; // [m0] row bounds, +-inf when absent
+  const double *clo, *chi; // [n+1] the handle's column bounds, +-inf when absent
+  const int *flags;        // [n+1] RND_INT: the column is integer
+  double *rowinfo;         // [m0][4]: Lmin, the upper side's threshold (+inf: the side says nothing), Lmax, the lower side's (-inf)
+  unsigned long long *adj; // [n+1][W]
+  int n, m0, ldm, ldn, W, pad;
+};
+
 // k_setbnds (mvx_set_col_bnds_many, mvx_tighten_cols_many): per handle a range of bound writes and a range of shifts of column 0
 struct SetbHandle {
   double *T, *blb, *bub, *nlb, *nub;
@@ -457,6 +472,7 @@ void launch_objrow(const ObjNode *nodes, int n, int count, hipStream_t);
 void launch_pumpobj(const PumpArgs &a, hipStream_t);
 void launch_cutgram(const CutGramArgs &a, hipStream_t);
 void launch_cutrows(const CutRowsArgs &a, hipStream_t);
+void launch_conflict(const ConflictArgs &a, hipStream_t);
 void launch_setbnds(const SetbHandle *hs, const SetbEntry *es, const SetbShift *ss, int handles, hipStream_t);
 void launch_refresh_select(Ctl *, const int *tflag, int var, hipStream_t);
 size_t persist_lds_bytes(int m, int cpw);

@@ -1148,4 +1148,80 @@ void launch_cutrows(const CutRowsArgs &a, hipStream_t s) {
   hipLaunchKernelGGL(k_cutrows, dim3((unsigned)((a.n + 1 + 255) / 256), (unsigned)((a.k + CUT_TILE - 1) / CUT_TILE)), dim3(256), 0, s, a);
 }
 
+// ---------------------------------------------------------------------------- k_conflict_rows / k_conflict
+// The conflict graph of a handle's binary columns (mvx_conflict_graph, DESIGN.md "Clique cuts (cut_families)"), two launches.
+// k_conflict_rows, rows on lanes: the activities of a row at the handle's bounds, phase A of k_prop word for word (the by-column
+// model, a wave reads one column of consecutive rows; the bounds are the same address in every lane), and what a side needs to
+// speak: Lmin and rub + tol(rub) where kmin = 0 and rub is finite, else +inf, which no sum exceeds; the mirror with -inf.
+__global__ __launch_bounds__(256) void k_conflict_rows(ConflictArgs a) {
+  const int i = (int)blockIdx.x * 256 + TIDX;
+  if (i >= a.m0) return;
+  const int n = a.n;
+  const size_t ldm = (size_t)a.ldm;
+  double lmin = 0.0, lmax = 0.0;
+  int kmin = 0, kmax = 0;
+  for (int j = 1; j <= n; j++) {
+    const double v = a.At[(size_t)j * ldm + i];
+    if (v == 0.0) continue;
+    const double l = a.clo[j], u = a.chi[j];
+    const double bmin = v > 0.0 ? l : u, bmax = v > 0.0 ? u : l;
+    if (isinf(bmin)) kmin++;
+    else lmin = __dadd_rn(lmin, __dmul_rn(v, bmin));
+    if (isinf(bmax)) kmax++;
+    else lmax = __dadd_rn(lmax, __dmul_rn(v, bmax));
+  }
+  const double lo = a.rlo[i], hi = a.rhi[i];
+  double *out = a.rowinfo + 4 * (size_t)i;
+  out[0] = lmin;
+  out[1] = (kmin == 0 && isfinite(hi)) ? __dadd_rn(hi, rnd_tol(hi)) : INFINITY;
+  out[2] = lmax;
+  out[3] = (kmax == 0 && isfinite(lo)) ? __dsub_rn(lo, rnd_tol(lo)) : -INFINITY;
+}
+
+// k_conflict: a wave owns one column j and one 64-bit word of its adjacency row, a lane the column k = 64 w + lane.  Per row
+// the wave reads a_ij through one address (a scalar load) and skips the row when it is zero or its side says nothing: both
+// branches are uniform, which is how a sparse row costs nothing.  Otherwise the lanes read Ar[i][k] coalesced (the row stride
+// is 64 W, so k stays inside the row and the padding reads as zero) and test (L + a_lower) + a_higher against the threshold, the
+// lower column's coefficient first: wave k's lane j adds the same numbers in the same order, so the relation is symmetric
+// without a second write.  The word is the ballot of the lanes' flags, written by lane 0.  No atomics, no LDS, no reduction.
+__global__ __launch_bounds__(64 * CONF_WAVES) void k_conflict(ConflictArgs a) {
+  const int j = (int)blockIdx.x; // 0..n
+  const int w = (int)blockIdx.y * CONF_WAVES + __builtin_amdgcn_readfirstlane(TIDX >> 6);
+  if (w >= a.W) return;
+  const int lane = TIDX & 63, k = w * 64 + lane;
+  const int n = a.n, m0 = a.m0;
+  const size_t ldn = (size_t)a.ldn;
+  bool flag = false;
+  if (j >= 1 && (a.flags[j] & RND_INT) && a.clo[j] == 0.0 && a.chi[j] == 1.0) {
+    const bool kB = k >= 1 && k <= n && k != j && (a.flags[k] & RND_INT) && a.clo[k] == 0.0 && a.chi[k] == 1.0;
+    const bool jlow = j < k;
+    for (int i = 0; i < m0; i++) {
+      const double aj = a.Ar[(size_t)i * ldn + (size_t)j];
+      if (aj == 0.0) continue;
+      const double *info = a.rowinfo + 4 * (size_t)i;
+      if (aj > 0.0) {
+        const double thr = info[1];
+        if (thr == INFINITY) continue;
+        const double L = info[0], ak = a.Ar[(size_t)i * ldn + (size_t)k];
+        const double s = jlow ? __dadd_rn(__dadd_rn(L, aj), ak) : __dadd_rn(__dadd_rn(L, ak), aj);
+        flag = flag || (ak > 0.0 && s > thr);
+      } else {
+        const double thr = info[3];
+        if (thr == -INFINITY) continue;
+        const double L = info[2], ak = a.Ar[(size_t)i * ldn + (size_t)k];
+        const double s = jlow ? __dadd_rn(__dadd_rn(L, aj), ak) : __dadd_rn(__dadd_rn(L, ak), aj);
+        flag = flag || (ak < 0.0 && s < thr);
+      }
+    }
+    flag = flag && kB;
+  }
+  const unsigned long long word = __ballot(flag);
+  if (lane == 0) a.adj[(size_t)j * (size_t)a.W + (size_t)w] = word;
+}
+
+void launch_conflict(const ConflictArgs &a, hipStream_t s) {
+  if (a.m0 > 0) hipLaunchKernelGGL(k_conflict_rows, dim3((unsigned)((a.m0 + 255) / 256)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_conflict, dim3((unsigned)(a.n + 1), (unsigned)((a.W + CONF_WAVES - 1) / CONF_WAVES)), dim3(64 * CONF_WAVES), 0, s, a);
+}
+
 } // namespace mvx
