@@ -78,6 +78,13 @@ void mvx_copy_prob(mvx_prob *dst, const mvx_prob *src, int names);
 /* ---- build / modify ----------------------------------------------------------- */
 void mvx_set_obj_dir(mvx_prob *P, int dir);                                  /* util.cpp:58 */
 int mvx_add_rows(mvx_prob *P, int nrs);                                      /* cut.cpp:23 */
+/* glp_del_rows' shape: num[1..nrs] are distinct row numbers in 1..m (num[0] is not read).  The rows leave the model, the others
+   keep their order and move up.  With a tableau on the device (DESIGN.md "Cut purging (cut_purge)"): when the auxiliary variable
+   of every deleted row is basic, the tableau rows leave in place (k_delrows), every other entry keeps its bits, the variable
+   numbers follow (an auxiliary k becomes k - #{deleted < k}, a structural one moves down by nrs), the basis stays, the status
+   becomes MVX_UNDEF and the next solve takes no pivot; when one is non-basic the tableau is given up and the next solve starts
+   from the slack basis.  Returns 0; -1 and nothing changed for a null, nrs < 1, a number out of range or a duplicate. */
+int mvx_del_rows(mvx_prob *P, int nrs, const int *num);
 int mvx_add_cols(mvx_prob *P, int ncs);                                      /* (readers) */
 void mvx_set_row_bnds(mvx_prob *P, int i, int type, double lb, double ub);   /* cut.cpp:43 */
 void mvx_set_col_bnds(mvx_prob *P, int j, int type, double lb, double ub);   /* bs.cpp:274,282 */

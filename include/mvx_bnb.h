@@ -123,6 +123,9 @@ typedef struct mvx_lp_api {
   /* optional (may be NULL): the conflict graph of the binary columns of a handle in one call (mvx_conflict_graph; DESIGN.md
      "Clique cuts (cut_families)"); without it, or when it returns -5, the host twin mvx_bnb_conflict_graph runs */
   int (*conflict_graph)(const void *model, unsigned long long *adj, long long *edges);
+  /* optional (may be NULL): rows num[1..nrs] taken out of a handle in one call (mvx_del_rows, glp_del_rows' shape; DESIGN.md "Cut
+     purging (cut_purge)"), 0 on success; without it, or when it fails, the root cut loop turns a purged row into a free row */
+  int (*del_rows)(void *P, int nrs, const int *num);
 } mvx_lp_api;
 
 const mvx_lp_api *mvx_hip_lp_api(void);
@@ -195,6 +198,9 @@ typedef struct {
   int cut_families;     /* the cut families of the root cut rounds (DESIGN.md "Clique cuts (cut_families)"), as bits: 1 the repaired
                            GMI cuts, 2 clique cuts from the conflict graph of the binary columns; 0 (default) means 1.  Read only
                            when cut_rounds > 0; a value outside 0..3 is then refused */
+  int cut_purge;        /* purging of slack cut rows in the root cut rounds (DESIGN.md "Cut purging (cut_purge)"): 0 (default) no row
+                           leaves; A = 1..64: a row the loop appended is taken out again once its auxiliary variable has been basic
+                           after A consecutive re-solves.  Read only when cut_rounds > 0; a value outside 0..64 is then refused */
 } mvx_bnb_params;
 
 /* B&B events at the emit points of bs.cpp (message.h EventType) */
@@ -264,6 +270,8 @@ typedef struct {
   long long cutloop_conflicts;    /* cut_families & 2: edges of the conflict graph */
   long long cutloop_clique_cands; /* ... violated cliques the separation kept, summed over the rounds (part of cutloop_candidates) */
   long long cutloop_clique_rows;  /* ... clique rows appended (part of cutloop_rows) */
+  long long cutloop_purged;       /* cut_purge > 0: rows of the loop taken out again (deleted, or made free rows) */
+  long long cutloop_live_rows;    /* rows of the loop the tree starts with: cutloop_rows - cutloop_purged */
 } mvx_bnb_result;
 
 void mvx_bnb_default_params(mvx_bnb_params *p);
@@ -406,7 +414,7 @@ int mvx_bnb_cut_select(int k, const double *eff, const double *gram, int K, doub
    made, rows appended, LPs solved, their pivots; bounds[0..1] = the LP before the loop and after it.  Returns 0; -1 bad
    arguments; -2 the table lacks an accessor, or a call of the table failed.  mvx_branchAndBound returns -1 (*res empty) for
    cut_rounds outside 0..64, cut_round_max outside 0..4096, cut_maxpar outside (0, 1] other than 0.0, cut_families outside
-   0..3 (all three read only with cut_rounds > 0) and cut_rounds > 0 with reference_quirks = 1, and -2, with the unsolved root as the tree, when the loop could not be carried out */
+   0..3, cut_purge outside 0..64 (all four read only with cut_rounds > 0) and cut_rounds > 0 with reference_quirks = 1, and -2, with the unsolved root as the tree, when the loop could not be carried out */
 int mvx_bnb_cut_loop(const mvx_lp_api *api, void *prob, int rounds, int K, double maxpar, long long *counters, double *bounds);
 /* The same loop with the cut families chosen (bits: 1 GMI, 2 clique; 0 means 1; outside 0..3: -1): counters[0..7] = the five of
    mvx_bnb_cut_loop, then the edges of the conflict graph, the cliques the separation kept, the clique rows appended.
@@ -414,6 +422,14 @@ int mvx_bnb_cut_loop(const mvx_lp_api *api, void *prob, int rounds, int K, doubl
    handed in (conflict_graph of the table, the twin without it or on -5; any other failure ends the loop with -2) */
 int mvx_bnb_cut_loop_families(const mvx_lp_api *api, void *prob, int rounds, int K, double maxpar, int families, long long *counters,
                               double *bounds);
+/* The same loop with the age limit of the purge (DESIGN.md "Cut purging (cut_purge)"; 0: no purge; outside 0..64: -1): after the
+   re-solve of a round that ended MVX_OPT, every live row of the loop whose auxiliary is basic ages by one and every other one
+   starts again at 0; the rows that have reached `purge` leave in one del_rows call of the table (without it, or when it fails,
+   each becomes a free row), and one more solve follows whose pivots are counted and whose LP is not.  The row budget counts live
+   rows.  counters[0..9] = the eight of mvx_bnb_cut_loop_families, then the rows purged and the live rows left.
+   mvx_bnb_cut_loop_families is this function with purge = 0 */
+int mvx_bnb_cut_loop_purge(const mvx_lp_api *api, void *prob, int rounds, int K, double maxpar, int families, int purge,
+                           long long *counters, double *bounds);
 
 /* Clique cuts (DESIGN.md "Clique cuts (cut_families)"), host twin of mvx_conflict_graph through the table only (get_mat_row, row
    and column bounds, get_col_kind): the same (n+1) x W words and edge count for the handle `model`, which need not be solved and

@@ -16,7 +16,7 @@ _FIELDS = [
 ]
 _OPTIONAL = ["simplex_batch", "get_obj_dir", "gmi_cuts", "gmi_cuts_many", "get_col_prim_all", "classify_many", "get_tableau", "get_basis",
              "branch_penalties_many", "round_many", "rc_tighten_many", "tighten_cols_many", "propagate_many", "set_col_bnds_many",
-             "dive_pick_many", "set_obj_coef", "set_obj_many", "pump_obj_many", "cut_scores", "add_cut_rows", "conflict_graph"]
+             "dive_pick_many", "set_obj_coef", "set_obj_many", "pump_obj_many", "cut_scores", "add_cut_rows", "conflict_graph", "del_rows"]
 
 
 class LpApiTable(C.Structure):
@@ -53,6 +53,7 @@ class BnbParams(C.Structure):
         ("cut_round_max", C.c_int),
         ("cut_maxpar", C.c_double),
         ("cut_families", C.c_int),
+        ("cut_purge", C.c_int),
     ]
 
 
@@ -120,6 +121,8 @@ class BnbResult(C.Structure):
         ("cutloop_conflicts", C.c_longlong),
         ("cutloop_clique_cands", C.c_longlong),
         ("cutloop_clique_rows", C.c_longlong),
+        ("cutloop_purged", C.c_longlong),
+        ("cutloop_live_rows", C.c_longlong),
     ]
 
 
@@ -208,6 +211,10 @@ def _bind(lib):
     _UP, _LP = C.POINTER(C.c_ulonglong), C.POINTER(C.c_longlong)
     lib.mvx_bnb_cut_loop_families.restype = C.c_int
     lib.mvx_bnb_cut_loop_families.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, _LP, _DP]
+    lib.mvx_bnb_cut_loop_purge.restype = C.c_int
+    lib.mvx_bnb_cut_loop_purge.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, _LP, _DP]
+    lib.mvx_del_rows.restype = C.c_int
+    lib.mvx_del_rows.argtypes = [C.c_void_p, C.c_int, _IP]
     lib.mvx_conflict_graph.restype = C.c_int
     lib.mvx_conflict_graph.argtypes = [C.c_void_p, _UP, _LP]
     lib.mvx_bnb_conflict_graph.restype = C.c_int
@@ -286,13 +293,15 @@ def result_to_dict(res):
         "cutloop_conflicts": res.cutloop_conflicts,
         "cutloop_clique_cands": res.cutloop_clique_cands,
         "cutloop_clique_rows": res.cutloop_clique_rows,
+        "cutloop_purged": res.cutloop_purged,
+        "cutloop_live_rows": res.cutloop_live_rows,
     }
 
 
 def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, window=None, cut_select=0, cut_chance=1.0,
                 best_window=None, sb_cands=None, sb_iters=None, heur=None, rc_fix=None, prop=None, dive=None, dive_freq=None,
                 dive_depth=None, pump=None, pump_freq=None, pump_alpha=None, cut_rounds=None, cut_round_max=None, cut_maxpar=None,
-                cut_families=None):
+                cut_families=None, cut_purge=None):
     """mvx_bnb_params with ParameterObj's defaults (util.h:65-67) overridden by the arguments (None: the default)."""
     pr = BnbParams()
     lib().mvx_bnb_default_params(C.byref(pr))
@@ -333,13 +342,15 @@ def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, l
         pr.cut_maxpar = cut_maxpar
     if cut_families is not None:
         pr.cut_families = cut_families
+    if cut_purge is not None:
+        pr.cut_purge = cut_purge
     return pr
 
 
 def branch_and_bound(prob, var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, table=None, window=None,
                      cut_select=0, cut_chance=1.0, best_window=None, sb_cands=None, sb_iters=None, heur=None, rc_fix=None, prop=None,
                      dive=None, dive_freq=None, dive_depth=None, pump=None, pump_freq=None, pump_alpha=None, cut_rounds=None,
-                     cut_round_max=None, cut_maxpar=None, cut_families=None):
+                     cut_round_max=None, cut_maxpar=None, cut_families=None, cut_purge=None):
     """Run the driver on `prob` (a capi.Prob).  table=None uses the gfx950 engine's own table.  best_window > 1 with
     node_strat=1: the speculative best-bound window (mvx_bnb_params.best_window).  var_strat 3 / 4: branching on the node
     LP's penalties / strong branching (sb_cands candidates, sb_iters pivots per child).  heur 1 / 2: the primal rounding
@@ -353,13 +364,14 @@ def branch_and_bound(prob, var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, 
     distance LPs (quirks=0, not with best_window).  cut_rounds 1..64: that many rounds of GMI cuts on the root LP before the
     tree starts, at most cut_round_max (default 32) cuts a round, none more than cut_maxpar (default 0.9) parallel to one
     taken before it in the round (quirks=0; every single-GPU driver); cut_families chooses the families of those rounds as bits, 1 GMI
-    (the default), 2 clique cuts from the conflict graph of the binary columns.  The
+    (the default), 2 clique cuts from the conflict graph of the binary columns; cut_purge = A in 1..64 takes a row of those rounds
+    out again once its auxiliary variable has been basic after A consecutive re-solves (0, the default: no row leaves).  The
     dictionary's "rc" is mvx_branchAndBound's return code (-1 refused parameters, -2 penalties, heuristic, tightening,
     propagation, pumps or dives unavailable)."""
     L = lib()
     pr = make_params(var_strat, node_strat, cut_strat, max_nodes, quirks, lazy_pool, window, cut_select, cut_chance, best_window, sb_cands,
                      sb_iters, heur, rc_fix, prop, dive, dive_freq, dive_depth, pump, pump_freq, pump_alpha, cut_rounds, cut_round_max,
-                     cut_maxpar, cut_families)
+                     cut_maxpar, cut_families, cut_purge)
     res = BnbResult()
     tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
     rc = L.mvx_branchAndBound(tptr, prob.h, C.byref(pr), C.byref(res))
@@ -803,15 +815,23 @@ def add_cut_rows(prob, vals, rhs):
     return lib().mvx_add_cut_rows(prob.h, k, v.ctypes.data_as(DP), r.ctypes.data_as(DP))
 
 
-def cut_loop(prob, rounds=5, K=0, maxpar=0.0, table=None, families=None):
+PURGE_COUNTERS = ("cutloop_purged", "cutloop_live_rows")
+
+
+def cut_loop(prob, rounds=5, K=0, maxpar=0.0, table=None, families=None, purge=None):
     """mvx_bnb_cut_loop: the root cut loop on the handle `prob`, which is edited in place, through `table` (None = the gfx950
     engine's table, whose batched entries then run).  Returns (rc, dictionary of the cutloop_* counters and bounds).
-    families (bits: 1 GMI, 2 clique) goes through mvx_bnb_cut_loop_families, and the dictionary then has CLIQUE_COUNTERS too."""
-    cnt = (C.c_longlong * 8)()
+    families (bits: 1 GMI, 2 clique) goes through mvx_bnb_cut_loop_families, and the dictionary then has CLIQUE_COUNTERS too.
+    purge (the age limit A of DESIGN.md "Cut purging (cut_purge)", 0..64) goes through mvx_bnb_cut_loop_purge, with families or 1,
+    and the dictionary then has PURGE_COUNTERS as well."""
+    cnt = (C.c_longlong * 10)()
     bnd = (C.c_double * 2)()
     tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
     names = CUTLOOP_COUNTERS
-    if families is None:
+    if purge is not None:
+        rc = lib().mvx_bnb_cut_loop_purge(tptr, prob.h, rounds, K, maxpar, 1 if families is None else families, purge, cnt, bnd)
+        names = CUTLOOP_COUNTERS + CLIQUE_COUNTERS + PURGE_COUNTERS
+    elif families is None:
         rc = lib().mvx_bnb_cut_loop(tptr, prob.h, rounds, K, maxpar, cnt, bnd)
     else:
         rc = lib().mvx_bnb_cut_loop_families(tptr, prob.h, rounds, K, maxpar, families, cnt, bnd)

@@ -179,6 +179,12 @@ class Prob:
         val = np.ascontiguousarray(val, dtype=np.float64)
         self.api.set_mat_row(self.h, i, len(ind) - 1, _ip(ind), _dp(val))
 
+    def del_rows(self, rows):
+        """mvx_del_rows (the gfx950 engine's library only): the distinct 1-based row numbers `rows` leave the model and, where
+        their auxiliary variables are basic, the device tableau in place.  Returns 0, or -1 with nothing changed."""
+        num = np.concatenate([[0], np.asarray(list(rows), dtype=np.int32)]).astype(np.int32)
+        return self.api.del_rows(self.h, len(num) - 1, _ip(num))
+
     # --- solve
     def simplex(self, it_lim=None, meth=None, tol=None):
         if it_lim is None and meth is None and tol is None:

@@ -51,6 +51,7 @@ extern "C" int mvx_pump_obj_many(const mvx_prob *root, const mvx_prob *const *Ps
 extern "C" int mvx_cut_scores(const mvx_prob *P, int k, const double *vals, double *dot, double *gram) __attribute__((weak));
 extern "C" int mvx_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rhs) __attribute__((weak));
 extern "C" int mvx_conflict_graph(const mvx_prob *model, unsigned long long *adj, long long *edges) __attribute__((weak));
+extern "C" int mvx_del_rows(mvx_prob *P, int nrs, const int *num) __attribute__((weak));
 
 namespace {
 
@@ -3105,6 +3106,7 @@ const mvx_lp_api g_hip_api = {
     mvx_conflict_graph ? +[](const void *model, unsigned long long *adj, long long *edges) {
       return mvx_conflict_graph((const mvx_prob *)model, adj, edges);
     } : nullptr,
+    mvx_del_rows ? +[](void *P, int nrs, const int *num) { return mvx_del_rows((mvx_prob *)P, nrs, num); } : nullptr,
 };
 
 } // namespace
@@ -3140,6 +3142,7 @@ void mvx_bnb_default_params(mvx_bnb_params *p) {
   p->cut_round_max = 0;
   p->cut_maxpar = 0.0;
   p->cut_families = 0;
+  p->cut_purge = 0;
 }
 
 // Repaired mode's rule for an integer column whose bounds are not integers (legal input: LP and MPS files may carry them):
@@ -3324,6 +3327,7 @@ static std::vector<std::vector<int>> clique_cuts(int n, const unsigned long long
 struct CutLoopOut {
   long long rounds = 0, candidates = 0, rows = 0, lps = 0, pivots = 0;
   long long conflicts = 0, clique_cands = 0, clique_rows = 0;
+  long long purged = 0;
   double bound0 = 0.0, bound = 0.0;
   void store(mvx_bnb_result *res) const {
     res->cutloop_rounds = rounds;
@@ -3336,6 +3340,8 @@ struct CutLoopOut {
     res->cutloop_conflicts = conflicts;
     res->cutloop_clique_cands = clique_cands;
     res->cutloop_clique_rows = clique_rows;
+    res->cutloop_purged = purged;
+    res->cutloop_live_rows = rows - purged;
   }
 };
 
@@ -3348,8 +3354,11 @@ constexpr double CUT_MAX_RANGE = 1e9;
 
 // The loop on `P`, edited in place: first solve, then up to R rounds of (candidates, scores, selection, append, re-solve).
 // `families`: bit 1 the repaired GMI cuts, bit 2 clique cuts out of the conflict graph of `P` as it is handed in (0 means 1).
+// `purge` = A (DESIGN.md "Cut purging (cut_purge)"): 0 no row leaves; otherwise a row this call appended is purged once its
+// auxiliary variable has been basic after A consecutive re-solves -- through del_rows of the table, or, without it or when it
+// fails, as a free row (the same LP), which stays where it is and is never looked at again.
 // Returns 0; -2 when the table lacks an accessor or one of its calls failed.
-static int cut_loop(const mvx_lp_api *api, void *P, int R, int K, double maxpar, int families, CutLoopOut &o) {
+static int cut_loop(const mvx_lp_api *api, void *P, int R, int K, double maxpar, int families, int purge, CutLoopOut &o) {
   if (!api->add_rows || !api->set_mat_row || !api->set_row_bnds || !api->simplex || !api->get_status || !api->get_obj_val ||
       !api->get_col_prim || !api->get_num_rows || !api->get_num_cols || !api->get_col_kind || !api->get_col_stat || !api->get_it_cnt ||
       !api->eval_tab_row || !api->get_mat_row)
@@ -3378,6 +3387,8 @@ static int cut_loop(const mvx_lp_api *api, void *P, int R, int K, double maxpar,
   o.bound0 = o.bound = api->get_obj_val(P);
   std::vector<int> inds(row);
   for (int j = 0; j <= n; j++) inds[(size_t)j] = j;
+  if (purge > 0 && !api->get_row_stat) return -2;
+  std::vector<int> live_row, live_age; // the live rows of the loop, ascending, and their ages
   for (int r = 1; r <= R && api->get_status(P) == MVX_OPT; r++) {
     // 1. candidates: the repaired cut of every column generateCutGMI would not reject out of hand
     std::vector<int> cols;
@@ -3443,7 +3454,7 @@ static int cut_loop(const mvx_lp_api *api, void *P, int R, int K, double maxpar,
     if (!api->cut_scores || api->cut_scores(P, C, sv.data(), sdot.data(), gram.data()) != 0)
       cut_scores_host(api, P, C, sv.data(), sdot.data(), gram.data());
     // 4. selection
-    const int left = budget - (int)o.rows;
+    const int left = budget - (int)live_row.size();
     std::vector<int> taken = cut_select(C, se.data(), gram.data(), K, maxpar, left);
     if (taken.empty()) break;
     // 5. append in taken order and re-solve (the dual simplex, warm)
@@ -3464,9 +3475,50 @@ static int cut_loop(const mvx_lp_api *api, void *P, int R, int K, double maxpar,
         api->set_row_bnds(P, index, MVX_LO, tr[(size_t)t], 0);
       }
     o.rows += nt;
+    {
+      const int m_now = api->get_num_rows(P);
+      for (int t = 0; t < nt; t++) {
+        live_row.push_back(m_now - nt + 1 + t);
+        live_age.push_back(0);
+      }
+    }
     solve_lp();
     o.rounds++;
     if (api->get_status(P) == MVX_OPT) o.bound = api->get_obj_val(P);
+    // 6. the purge: slack rows that have stayed slack for `purge` re-solves leave, in one call
+    if (purge > 0 && api->get_status(P) == MVX_OPT) {
+      std::vector<int> num(1, 0);
+      for (size_t l = 0; l < live_row.size(); l++) {
+        live_age[l] = api->get_row_stat(P, live_row[l]) == MVX_BS ? live_age[l] + 1 : 0;
+        if (live_age[l] >= purge) num.push_back(live_row[l]);
+      }
+      const int cnt = (int)num.size() - 1;
+      if (cnt > 0) {
+        const bool deleted = api->del_rows && api->del_rows(P, cnt, num.data()) == 0;
+        if (!deleted)
+          for (int t = 1; t <= cnt; t++) api->set_row_bnds(P, num[(size_t)t], MVX_FR, 0.0, 0.0);
+        // the purged rows are not live any more; behind a deletion the others move up
+        size_t w = 0;
+        int gone = 0;
+        for (size_t l = 0; l < live_row.size(); l++) {
+          if (live_age[l] >= purge) {
+            gone++;
+            continue;
+          }
+          live_row[w] = deleted ? live_row[l] - gone : live_row[l];
+          live_age[w] = live_age[l];
+          w++;
+        }
+        live_row.resize(w);
+        live_age.resize(w);
+        o.purged += cnt;
+        // one more solve (no pivot behind a deletion): its pivots count, it is not one of the loop's LPs
+        const int before = api->get_it_cnt(P);
+        api->simplex(P, nullptr);
+        o.pivots += api->get_it_cnt(P) - before;
+        if (api->get_status(P) == MVX_OPT) o.bound = api->get_obj_val(P);
+      }
+    }
   }
   return 0;
 }
@@ -3496,7 +3548,8 @@ int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *
       params->cut_rounds < 0 || params->cut_rounds > 64 ||
       (params->cut_rounds > 0 && (params->reference_quirks != 0 || params->cut_round_max < 0 || params->cut_round_max > 4096 ||
                                   !(params->cut_maxpar == 0.0 || (params->cut_maxpar > 0.0 && params->cut_maxpar <= 1.0)) ||
-                                  params->cut_families < 0 || params->cut_families > 3))) {
+                                  params->cut_families < 0 || params->cut_families > 3 || params->cut_purge < 0 ||
+                                  params->cut_purge > 64))) {
     std::memset(res, 0, sizeof(*res));
     return -1;
   }
@@ -3518,7 +3571,8 @@ int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *
       void *model = api->create_prob();
       api->copy_prob(model, work, MVX_OFF);
       CutLoopOut lo;
-      int r = cut_loop(api, work, params->cut_rounds, params->cut_round_max, params->cut_maxpar, params->cut_families, lo);
+      int r = cut_loop(api, work, params->cut_rounds, params->cut_round_max, params->cut_maxpar, params->cut_families, params->cut_purge,
+                       lo);
       if (r != 0) {
         infeasible_root(MVOLP::NONE); // the loop could not run: the tree so far is the unsolved root
         r = -2;
@@ -3745,17 +3799,27 @@ int mvx_bnb_cut_select(int k, const double *eff, const double *gram, int K, doub
   return 0;
 }
 
-int mvx_bnb_cut_loop_families(const mvx_lp_api *api, void *prob, int rounds, int K, double maxpar, int families, long long *counters,
-                              double *bounds) {
+int mvx_bnb_cut_loop_purge(const mvx_lp_api *api, void *prob, int rounds, int K, double maxpar, int families, int purge,
+                           long long *counters, double *bounds) {
   if (!api) api = &g_hip_api;
   if (!prob || rounds < 1 || rounds > 64 || K < 0 || K > 4096 || !(maxpar == 0.0 || (maxpar > 0.0 && maxpar <= 1.0)) || families < 0 ||
-      families > 3 || !counters || !bounds)
+      families > 3 || purge < 0 || purge > 64 || !counters || !bounds)
     return -1;
   CutLoopOut lo;
-  const int rc = cut_loop(api, prob, rounds, K, maxpar, families, lo);
+  const int rc = cut_loop(api, prob, rounds, K, maxpar, families, purge, lo);
   counters[0] = lo.rounds; counters[1] = lo.candidates; counters[2] = lo.rows; counters[3] = lo.lps; counters[4] = lo.pivots;
   counters[5] = lo.conflicts; counters[6] = lo.clique_cands; counters[7] = lo.clique_rows;
+  counters[8] = lo.purged; counters[9] = lo.rows - lo.purged;
   bounds[0] = lo.bound0; bounds[1] = lo.bound;
+  return rc;
+}
+
+int mvx_bnb_cut_loop_families(const mvx_lp_api *api, void *prob, int rounds, int K, double maxpar, int families, long long *counters,
+                              double *bounds) {
+  if (!counters) return -1;
+  long long all[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  const int rc = mvx_bnb_cut_loop_purge(api, prob, rounds, K, maxpar, families, 0, all, bounds);
+  if (rc != -1) std::copy(all, all + 8, counters);
   return rc;
 }
 

@@ -185,6 +185,41 @@ int mvx_add_rows(mvx_prob *P, int nrs) {
   return first;
 }
 
+int mvx_del_rows(mvx_prob *P, int nrs, const int *num) {
+  if (!P || nrs < 1 || !num) return -1;
+  const int m = P->m;
+  std::vector<char> mark((size_t)m + 1, 0);
+  for (int k = 1; k <= nrs; k++) {
+    const int i = num[k];
+    if (i < 1 || i > m || mark[(size_t)i]) return -1;
+    mark[(size_t)i] = 1;
+  }
+  std::vector<int> rows;
+  std::vector<size_t> idx;
+  rows.reserve((size_t)nrs);
+  idx.reserve((size_t)nrs);
+  int w = 0;
+  for (int i = 1; i <= m; i++) {
+    if (mark[(size_t)i]) {
+      rows.push_back(i);
+      idx.push_back((size_t)i);
+      continue;
+    }
+    ++w;
+    P->rtype[(size_t)w] = P->rtype[(size_t)i];
+    P->rlb[(size_t)w] = P->rlb[(size_t)i];
+    P->rub[(size_t)w] = P->rub[(size_t)i];
+  }
+  P->A.erase(idx); // the list is copy-on-write: a clone that shares rows or the frozen head keeps what it has
+  P->rtype.resize((size_t)w + 1);
+  P->rlb.resize((size_t)w + 1);
+  P->rub.resize((size_t)w + 1);
+  P->m = w;
+  mvx::engine_del_rows(P, rows, m);
+  P->status = MVX_UNDEF;
+  return 0;
+}
+
 int mvx_add_cols(mvx_prob *P, int ncs) {
   if (ncs < 1) fault("add_cols: invalid count");
   const int first = P->n + 1;

@@ -2230,6 +2230,83 @@ int engine_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rh
   return 0;
 }
 
+// Model rows `rows` (ascending, distinct, numbered as before the call) have left the model (mvx_del_rows; P->m is the new row
+// count, the mirrors and P->pos still describe the m_old rows).  The device copies of the model that cover one of them are
+// dropped.  With a valid tableau: when every deleted row's auxiliary variable is basic, its tableau rows are taken out in place
+// by one k_delrows launch -- the rows that stay keep their order and their bits, bvar / blb / bub move with them, the variable
+// numbers are rewritten on the device and in the mirrors, pending edits follow their rows -- and the basis stays what it was,
+// so a solve that follows takes no pivot.  The map goes up through the node entries' pinned block; nothing waits for the device
+// in front of the launch.  When a deleted row's auxiliary is non-basic, the column it holds cannot be dropped without a pivot:
+// the tableau is given up and the next solve starts from the slack basis.
+void engine_del_rows(mvx_prob *P, const std::vector<int> &rows, int m_old) {
+  if (P->dmat && rows.front() <= P->dmat->m0) P->dmat.reset();
+  if (P->rmod && rows.front() <= P->rmod->m0) P->rmod.reset();
+  if (!P->valid) return;
+  const int nrs = (int)rows.size(), n = P->n;
+  std::vector<char> gone((size_t)m_old + 1, 0); // by tableau row
+  int first = m_old + 1;
+  for (int i : rows) {
+    const int pos = P->pos[i];
+    if (pos <= 0) {
+      // the slab is kept (the out-of-memory path below gives it back): the next solve builds the slack tableau in it, so a
+      // recorded clone INTO it must land first
+      Context &c = ctx();
+      MAIN_LOCK(c);
+      flush_copies(c);
+      engine_invalidate(P);
+      return;
+    }
+    gone[(size_t)pos] = 1;
+    first = std::min(first, pos);
+  }
+  std::vector<int> newpos((size_t)m_old + 1, 0); // tableau row -> its new place, 0 for a removed one
+  std::vector<int> src;
+  for (int r = 1, w = 0; r <= m_old; r++) {
+    if (gone[(size_t)r]) continue;
+    newpos[(size_t)r] = ++w;
+    if (r > first) src.push_back(r);
+  }
+  const int nmove = (int)src.size();
+  NodeCall f(NodeFlush::AtEntry, NodeResults::None);
+  const size_t o_src = f.up((size_t)std::max(1, nmove) * 4), o_del = f.up((size_t)nrs * 4);
+  if (!f.reserve()) {
+    release_device(P);
+    engine_invalidate(P);
+    return;
+  }
+  if (nmove) std::memcpy(f.hb + o_src, src.data(), (size_t)nmove * 4);
+  std::memcpy(f.hb + o_del, rows.data(), (size_t)nrs * 4);
+  f.upload();
+  DelRowsArgs a;
+  a.T = P->d_T;
+  a.bvar = P->d_bvar; a.nvar = P->d_nvar;
+  a.blb = P->d_blb; a.bub = P->d_bub;
+  a.src = (const int *)(f.db + o_src);
+  a.del = (const int *)(f.db + o_del);
+  a.first = first; a.nmove = nmove; a.m_old = m_old; a.nrs = nrs; a.n = n; a.ld = P->ld;
+  launch_delrows(a, f.stream());
+  // host mirrors: the same compaction and renumbering
+  auto renumber = [&](int k) {
+    if (k > m_old) return k - nrs;
+    return k - (int)(std::lower_bound(rows.begin(), rows.end(), k) - rows.begin());
+  };
+  for (int r = 1; r <= m_old; r++)
+    if (newpos[(size_t)r]) P->bvar[(size_t)newpos[(size_t)r]] = renumber(P->bvar[(size_t)r]);
+  P->bvar.resize((size_t)P->m + 1);
+  for (int q = 1; q <= n; q++) P->nvar[(size_t)q] = renumber(P->nvar[(size_t)q]);
+  rebuild_pos(P);
+  // pending bound edits follow their rows; those of removed rows have nothing left to apply to
+  size_t w = 0;
+  for (const auto &e : P->pending)
+    if (newpos[(size_t)e.row]) P->pending[w++] = {newpos[(size_t)e.row], e.lb, e.ub};
+  P->pending.resize(w);
+  // the rows in front of the first removed one sit where they sat: what the mirrors hold of those stays current
+  P->fresh_rows = P->sol_fresh ? first - 1 : std::min(P->fresh_rows, first - 1);
+  P->sol_fresh = false;
+  P->status = MVX_UNDEF;
+  f.fetch(); // the pinned block is free again
+}
+
 void engine_recompute_cost_row(mvx_prob *P) {
   if (!P->valid) return;
   const int m = P->m, n = P->n;

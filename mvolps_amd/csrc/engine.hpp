@@ -17,7 +17,10 @@ int engine_simplex_batch(mvx_prob **probs, int count, const mvx_smcp *parm, int 
 // tableau maintenance under model edits; all no-ops while !P->valid
 void engine_apply_bounds(mvx_prob *P, int k, int type, double old_lb, double old_ub, double lb, double ub);
 void engine_add_rows(mvx_prob *P, int first, int nrs); // P->m already updated
-void engine_row_from_model(mvx_prob *P, int i);        // row i's auxiliary is basic: rebuild its tableau row
+// model rows `rows` (ascending, old numbers) are gone, P->m already updated, the mirrors still those of m_old rows; also drops
+// the device copies of the model that covered one of them (that part runs without a tableau)
+void engine_del_rows(mvx_prob *P, const std::vector<int> &rows, int m_old);
+void engine_row_from_model(mvx_prob *P, int i);      // row i's auxiliary is basic: rebuild its tableau row
 void engine_recompute_cost_row(mvx_prob *P);
 void engine_invalidate(mvx_prob *P); // drop device state; next solve starts from the slack basis
 

@@ -85,6 +85,8 @@ int main(int argc, char **argv) {
               << "  --cut-maxpar P  with --cut-rounds: largest cosine between two cuts of a round (0 < P <= 1, default 0.9)\n"
               << "  --cut-families F with --cut-rounds: the cut families as bits (1..3, default 1): 1 GMI cuts, 2 clique cuts from the\n"
               << "                  conflict graph of the binary columns\n"
+              << "  --cut-purge [A] with --cut-rounds: a cut row leaves the root LP again once it has been slack after A re-solves in a\n"
+              << "                  row (1..64; 3 without a number)\n"
               << "Help:\n  -h/--help\n";
     return 0;
   }
@@ -212,6 +214,17 @@ int main(int argc, char **argv) {
     }
   }
   if (!int_opt("--cut-families", 1, 3, &params.cut_families)) return -1;
+  if (input.CMDOptionExists("--cut-purge")) {
+    // the number is optional, as for --cut-rounds
+    const std::string &k = input.getCMDOption("--cut-purge");
+    const bool numeric = !k.empty() && std::all_of(k.begin(), k.end(), [](char ch) { return ch >= '0' && ch <= '9'; });
+    const long kv = numeric ? std::strtol(k.c_str(), nullptr, 10) : 3;
+    params.cut_purge = kv >= 1 && kv <= 64 ? (int)kv : -1;
+    if (params.cut_purge < 1) {
+      std::fprintf(stderr, "Unknown parameter value for --cut-purge\n");
+      return -1;
+    }
+  }
   if (input.CMDOptionExists("--cut-select")) params.cut_select = std::atoi(input.getCMDOption("--cut-select").c_str());
   if (input.CMDOptionExists("--window")) params.window = std::atoi(input.getCMDOption("--window").c_str());
   if (input.CMDOptionExists("--best-window")) params.best_window = std::atoi(input.getCMDOption("--best-window").c_str());
@@ -261,6 +274,8 @@ int main(int argc, char **argv) {
   if (verbose && params.cut_rounds > 0 && (params.cut_families & 2))
     std::printf("Clique cuts: %lld conflicts, %lld violated cliques, %lld rows appended\n", res.cutloop_conflicts, res.cutloop_clique_cands,
                 res.cutloop_clique_rows);
+  if (verbose && params.cut_rounds > 0 && params.cut_purge > 0)
+    std::printf("Cut purging: %lld rows purged, %lld live rows\n", res.cutloop_purged, res.cutloop_live_rows);
   const int limit = res.hit_limit || brc != 0;
   mvx_bnb_free_result(&res);
   mvx_delete_prob(prob);

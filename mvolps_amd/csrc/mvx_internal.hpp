@@ -402,6 +402,19 @@ struct CutRowsArgs {
   int m, n, ld, k;     // m: rows before the append
 };
 
+// arguments of k_delrows (mvx_del_rows): rows taken out of one tableau in place.  Tableau rows 0..first-1 stay where they are;
+// destination row first + t takes source row src[t] (ascending, src[t] > first + t); rows first + nmove .. m_old (behind the new
+// row m = first + nmove - 1) are vacated and zeroed.  del[0..nrs) are the deleted auxiliary variables (= model rows), ascending, for the renumbering
+#define DEL_BATCH 8 // source rows a lane holds in registers before it stores them
+struct DelRowsArgs {
+  double *T;
+  int *bvar, *nvar;
+  double *blb, *bub;
+  const int *src; // [nmove]
+  const int *del; // [nrs]
+  int first, nmove, m_old, nrs, n, ld;
+};
+
 // arguments of k_conflict_rows / k_conflict (mvx_conflict_graph): the model of one handle as k_prop reads it -- its rows by
 // column (At) and by row (Ar), the row bounds, the RND_INT flags and the handle's own column bounds -- the per-row numbers the
 // first kernel leaves for the second, and the adjacency words
@@ -472,6 +485,7 @@ void launch_objrow(const ObjNode *nodes, int n, int count, hipStream_t);
 void launch_pumpobj(const PumpArgs &a, hipStream_t);
 void launch_cutgram(const CutGramArgs &a, hipStream_t);
 void launch_cutrows(const CutRowsArgs &a, hipStream_t);
+void launch_delrows(const DelRowsArgs &a, hipStream_t);
 void launch_conflict(const ConflictArgs &a, hipStream_t);
 void launch_setbnds(const SetbHandle *hs, const SetbEntry *es, const SetbShift *ss, int handles, hipStream_t);
 void launch_refresh_select(Ctl *, const int *tflag, int var, hipStream_t);
@@ -539,6 +553,31 @@ public:
     if (head_.use_count() != 1) head_ = std::make_shared<std::vector<RowPtr>>(head_->begin(), head_->begin() + (long)n);
     else head_->resize(n);
     tail_.clear();
+  }
+  // the entries idx (ascending, distinct) leave, the others keep their order.  Entries of the tail (cut rows) leave the tail
+  // alone; one in the head gives this handle a head of its own, and the sharers keep theirs
+  void erase(const std::vector<size_t> &idx) {
+    const size_t nh = head_->size();
+    size_t in_head = 0;
+    while (in_head < idx.size() && idx[in_head] < nh) in_head++;
+    if (in_head > 0) {
+      auto h = std::make_shared<std::vector<RowPtr>>();
+      h->reserve(nh - in_head);
+      for (size_t i = 0, d = 0; i < nh; i++) {
+        if (d < in_head && idx[d] == i) d++;
+        else h->push_back((*head_)[i]);
+      }
+      head_ = std::move(h);
+    }
+    size_t w = 0;
+    for (size_t i = 0, d = in_head; i < tail_.size(); i++) {
+      if (d < idx.size() && idx[d] == nh + i) d++;
+      else {
+        if (w != i) tail_[w] = std::move(tail_[i]);
+        w++;
+      }
+    }
+    tail_.resize(w);
   }
   void reset(size_t n) { // n empty rows
     head_ = std::make_shared<std::vector<RowPtr>>();

@@ -1148,6 +1148,82 @@ void launch_cutrows(const CutRowsArgs &a, hipStream_t s) {
   hipLaunchKernelGGL(k_cutrows, dim3((unsigned)((a.n + 1 + 255) / 256), (unsigned)((a.k + CUT_TILE - 1) / CUT_TILE)), dim3(256), 0, s, a);
 }
 
+// ---------------------------------------------------------------------------- k_delrows
+// Rows taken out of one tableau in place (mvx_del_rows, DESIGN.md "Cut purging (cut_purge)"): the kept rows behind the first
+// removed one move towards lower indices, in their order, bit for bit.  A row may land where another kept row still waits to be
+// read, so no two workgroups share a column: a workgroup is one wave and owns 64 columns (512 B of every row, coalesced), and
+// walks the moved rows in ascending order, DEL_BATCH source rows loaded into registers before the batch is stored.  Within a
+// wave that is safe: dst_t < src_t for every moved row and the sources ascend, so a store never lands on a row that is still
+// to be loaded.  The map src[t] (the source of destination row first + t) is the same address in every lane: scalar loads.
+// The rows the compaction vacates (behind the new row m) are zeroed, which is what k_update / k_fb / k_fbc3 assume of the spare
+// rows they stream through.  The wave of the first column tile also moves bvar / blb / bub, 64 rows a step (every lane's load
+// is done before any lane's store, a barrier stands between them; the same ordering argument), and rewrites the variable numbers of bvar and nvar:
+// an auxiliary k becomes k - #{deleted < k}, a structural one moves down by the number of deleted rows.
+// No atomics, no LDS, no hand-off between workgroups.
+__device__ __forceinline__ int del_renumber(int k, const int *del, int nrs, int m_old) {
+  if (k > m_old) return k - nrs;
+  int lo = 0, hi = nrs; // deleted auxiliaries below k: del is ascending and does not hold k
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (del[mid] < k) lo = mid + 1;
+    else hi = mid;
+  }
+  return k - lo;
+}
+
+__global__ __launch_bounds__(64) void k_delrows(DelRowsArgs a) {
+  const int lane = TIDX;
+  const int j = (int)blockIdx.x * 64 + lane;
+  const size_t ld = (size_t)a.ld;
+  const int first = a.first, nmove = a.nmove;
+  if (j < a.ld) {
+    double *Tj = a.T + (size_t)j;
+    int t0 = 0;
+    for (; t0 + DEL_BATCH <= nmove; t0 += DEL_BATCH) {
+      double v[DEL_BATCH];
+#pragma unroll
+      for (int b = 0; b < DEL_BATCH; b++) v[b] = Tj[(size_t)a.src[t0 + b] * ld];
+#pragma unroll
+      for (int b = 0; b < DEL_BATCH; b++) Tj[(size_t)(first + t0 + b) * ld] = v[b];
+    }
+    if (t0 < nmove) {
+      const int nb = nmove - t0;
+      double v[DEL_BATCH];
+#pragma unroll
+      for (int b = 0; b < DEL_BATCH; b++) v[b] = b < nb ? Tj[(size_t)a.src[t0 + b] * ld] : 0.0;
+#pragma unroll
+      for (int b = 0; b < DEL_BATCH; b++)
+        if (b < nb) Tj[(size_t)(first + t0 + b) * ld] = v[b];
+    }
+    for (int i = first + nmove; i <= a.m_old; i++) Tj[(size_t)i * ld] = 0.0;
+  }
+  if (blockIdx.x != 0) return;
+  const int nrs = a.nrs, m_old = a.m_old;
+  for (int i = 1 + lane; i < first; i += 64) a.bvar[i] = del_renumber(a.bvar[i], a.del, nrs, m_old);
+  for (int t0 = 0; t0 < nmove; t0 += 64) {
+    const int t = t0 + lane;
+    int k = 0;
+    double lb = 0.0, ub = 0.0;
+    if (t < nmove) {
+      const int s = a.src[t];
+      k = a.bvar[s];
+      lb = a.blb[s];
+      ub = a.bub[s];
+    }
+    __syncthreads(); // every lane's loads of this step are done before any lane stores: a destination may be another lane's source
+    if (t < nmove) {
+      a.bvar[first + t] = del_renumber(k, a.del, nrs, m_old);
+      a.blb[first + t] = lb;
+      a.bub[first + t] = ub;
+    }
+  }
+  for (int q = 1 + lane; q <= a.n; q += 64) a.nvar[q] = del_renumber(a.nvar[q], a.del, nrs, m_old);
+}
+
+void launch_delrows(const DelRowsArgs &a, hipStream_t s) {
+  hipLaunchKernelGGL(k_delrows, dim3((unsigned)((a.ld + 63) / 64)), dim3(64), 0, s, a);
+}
+
 // ---------------------------------------------------------------------------- k_conflict_rows / k_conflict
 // The conflict graph of a handle's binary columns (mvx_conflict_graph, DESIGN.md "Clique cuts (cut_families)"), two launches.
 // k_conflict_rows, rows on lanes: the activities of a row at the handle's bounds, phase A of k_prop word for word (the by-column
