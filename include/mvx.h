@@ -274,6 +274,18 @@ int mvx_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rhs);
    Bit-identical to mvx_bnb_conflict_graph (mvx_bnb.h).  Returns 0; -1 bad arguments; -2 device out of memory; -5 is kept for a
    kernel with a size limit (the driver then runs the twin): k_conflict has none and never returns it. */
 int mvx_conflict_graph(const mvx_prob *model, unsigned long long *adj, long long *edges);
+/* Incumbent polishing (DESIGN.md "Incumbent polishing (polish)"): a best-improvement search over one- and two-column unit moves
+   from each of `count` points, against the model of `root` (rows 1..m0, row and column bounds, kinds, objective and sense; kept
+   with `root` and checked on every call, as for mvx_round_many, the by-row copy of mvx_propagate_many included).  x is count x
+   (n+1) in the layout of mvx_round_many and is edited in place (entry 0 of a point is not read or written).  A point whose
+   integer columns are not within 1e-9 of an integer, or that fails the rounding heuristic's check, is refused: ok[t] = 0, its x
+   untouched, obj[t] = 0 and moves[t] = 0.  Otherwise ok[t] = 1, x the polished point (integer columns rounded at entry), obj[t]
+   its objective and moves[t] the moves taken, at most max_moves (1..100000).  Per iteration two launches (k_lsmove, k_lsapply),
+   enqueued eight iterations at a time.  Pure: no handle changes, none need be solved.  Bit-identical to mvx_bnb_polish
+   (mvx_bnb.h).  Returns 0; -1 bad arguments (a null, count < 0, max_moves outside 1..100000); -2 device out of memory, nothing
+   written; -5 is kept for a kernel with a size limit (the driver then runs the twin): these kernels have none and never
+   return it. */
+int mvx_polish_many(const mvx_prob *root, int count, double *x, int max_moves, double *obj, int *moves, int *ok);
 
 /* ---- engine-state access (parity tests, visualisers) --------------------------- */
 int mvx_get_tableau_ld(const mvx_prob *P);

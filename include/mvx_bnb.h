@@ -126,6 +126,9 @@ typedef struct mvx_lp_api {
   /* optional (may be NULL): rows num[1..nrs] taken out of a handle in one call (mvx_del_rows, glp_del_rows' shape; DESIGN.md "Cut
      purging (cut_purge)"), 0 on success; without it, or when it fails, the root cut loop turns a purged row into a free row */
   int (*del_rows)(void *P, int nrs, const int *num);
+  /* optional (may be NULL): the incumbent polishing (DESIGN.md "Incumbent polishing (polish)") of `count` points in one call
+     (mvx_polish_many), the model taken from `root`; without it, or when it returns -5, the host twin mvx_bnb_polish runs */
+  int (*polish_many)(const void *root, int count, double *x, int max_moves, double *obj, int *moves, int *ok);
 } mvx_lp_api;
 
 const mvx_lp_api *mvx_hip_lp_api(void);
@@ -201,6 +204,11 @@ typedef struct {
   int cut_purge;        /* purging of slack cut rows in the root cut rounds (DESIGN.md "Cut purging (cut_purge)"): 0 (default) no row
                            leaves; A = 1..64: a row the loop appended is taken out again once its auxiliary variable has been basic
                            after A consecutive re-solves.  Read only when cut_rounds > 0; a value outside 0..64 is then refused */
+  int polish;           /* incumbent polishing (DESIGN.md "Incumbent polishing (polish)"): 0 off (default), N = 1..100000 the move cap.
+                           Every point that becomes the incumbent -- an integral node LP's, the rounding heuristic's, a dive's, a
+                           pump's -- is first improved by a best-improvement search over one- and two-column unit moves; the
+                           decision whether it becomes the incumbent is taken on the point as found.  Needs reference_quirks = 0;
+                           allowed with best_window > 0 */
 } mvx_bnb_params;
 
 /* B&B events at the emit points of bs.cpp (message.h EventType) */
@@ -272,6 +280,9 @@ typedef struct {
   long long cutloop_clique_rows;  /* ... clique rows appended (part of cutloop_rows) */
   long long cutloop_purged;       /* cut_purge > 0: rows of the loop taken out again (deleted, or made free rows) */
   long long cutloop_live_rows;    /* rows of the loop the tree starts with: cutloop_rows - cutloop_purged */
+  long long polish_calls;    /* polish > 0: points polished (every point that became the incumbent) */
+  long long polish_moves;    /* ... moves taken, summed */
+  long long polish_improved; /* ... points that came back with a better objective */
 } mvx_bnb_result;
 
 void mvx_bnb_default_params(mvx_bnb_params *p);
@@ -443,6 +454,16 @@ int mvx_bnb_conflict_graph(const mvx_lp_api *api, const void *model, unsigned lo
    on Q and 0 elsewhere and rhs[t] = -1: the MVX_LO row sum_{j in Q} x_j <= 1.  Stops at max_cuts; *count the rows written.
    Returns 0; -1 bad arguments (n < 0, max_cuts < 0, a null) */
 int mvx_bnb_clique_cuts(int n, const unsigned long long *adj, const double *x, int max_cuts, double *vals, double *rhs, int *count);
+
+/* Incumbent polishing (DESIGN.md "Incumbent polishing (polish)"), host twin of mvx_polish_many for one point x[1..n] (x[0] is not
+   touched), edited in place, against the model of `root`: its rows, bounds, kinds, objective and sense.  *ok 0: the point is
+   refused (an integer column farther than 1e-9 from an integer, or the rounding heuristic's check fails) and stays as it is,
+   *obj = 0, *moves = 0; 1: x the polished point, *obj its objective, *moves the moves taken (at most max_moves, 1..100000).
+   Works through the table only (get_mat_row, row and column bounds, get_obj_coef, get_col_kind, get_obj_dir).  Returns 0; -1 bad
+   arguments; -2 the table lacks an accessor it needs.  mvx_branchAndBound returns -1 (*res empty) for polish outside 0..100000
+   and polish > 0 with reference_quirks = 1, and -2, with the tree so far, when a point could not be polished (polish_many failed
+   with a code other than -5, or the twin cannot run) */
+int mvx_bnb_polish(const mvx_lp_api *api, const void *root, double *x, int max_moves, double *obj, int *moves, int *ok);
 
 /* bs.cpp:249-258 on one solved node `a` that is about to be branched: generate its GMI cut(s) and append the
    row(s) (cut_strat / reference_quirks / lazy_pool / cut_select / cut_chance of `params`).  Returns the number

@@ -16,7 +16,8 @@ _FIELDS = [
 ]
 _OPTIONAL = ["simplex_batch", "get_obj_dir", "gmi_cuts", "gmi_cuts_many", "get_col_prim_all", "classify_many", "get_tableau", "get_basis",
              "branch_penalties_many", "round_many", "rc_tighten_many", "tighten_cols_many", "propagate_many", "set_col_bnds_many",
-             "dive_pick_many", "set_obj_coef", "set_obj_many", "pump_obj_many", "cut_scores", "add_cut_rows", "conflict_graph", "del_rows"]
+             "dive_pick_many", "set_obj_coef", "set_obj_many", "pump_obj_many", "cut_scores", "add_cut_rows", "conflict_graph", "del_rows",
+             "polish_many"]
 
 
 class LpApiTable(C.Structure):
@@ -54,6 +55,7 @@ class BnbParams(C.Structure):
         ("cut_maxpar", C.c_double),
         ("cut_families", C.c_int),
         ("cut_purge", C.c_int),
+        ("polish", C.c_int),
     ]
 
 
@@ -123,6 +125,9 @@ class BnbResult(C.Structure):
         ("cutloop_clique_rows", C.c_longlong),
         ("cutloop_purged", C.c_longlong),
         ("cutloop_live_rows", C.c_longlong),
+        ("polish_calls", C.c_longlong),
+        ("polish_moves", C.c_longlong),
+        ("polish_improved", C.c_longlong),
     ]
 
 
@@ -221,6 +226,10 @@ def _bind(lib):
     lib.mvx_bnb_conflict_graph.argtypes = [C.c_void_p, C.c_void_p, _UP, _LP]
     lib.mvx_bnb_clique_cuts.restype = C.c_int
     lib.mvx_bnb_clique_cuts.argtypes = [C.c_int, _UP, _DP, C.c_int, _DP, _DP, _IP]
+    lib.mvx_polish_many.restype = C.c_int
+    lib.mvx_polish_many.argtypes = [C.c_void_p, C.c_int, _DP, C.c_int, _DP, _IP, _IP]
+    lib.mvx_bnb_polish.restype = C.c_int
+    lib.mvx_bnb_polish.argtypes = [C.c_void_p, C.c_void_p, _DP, C.c_int, _DP, _IP, _IP]
     lib.mvx_generateCutGMI.restype = C.c_int
     lib.mvx_generateCutGMI.argtypes = [C.c_void_p, C.c_void_p, C.c_int, _IP, _DP, _DP, _DP]
     lib.mvx_generateCut3.restype = C.c_int
@@ -295,13 +304,16 @@ def result_to_dict(res):
         "cutloop_clique_rows": res.cutloop_clique_rows,
         "cutloop_purged": res.cutloop_purged,
         "cutloop_live_rows": res.cutloop_live_rows,
+        "polish_calls": res.polish_calls,
+        "polish_moves": res.polish_moves,
+        "polish_improved": res.polish_improved,
     }
 
 
 def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, window=None, cut_select=0, cut_chance=1.0,
                 best_window=None, sb_cands=None, sb_iters=None, heur=None, rc_fix=None, prop=None, dive=None, dive_freq=None,
                 dive_depth=None, pump=None, pump_freq=None, pump_alpha=None, cut_rounds=None, cut_round_max=None, cut_maxpar=None,
-                cut_families=None, cut_purge=None):
+                cut_families=None, cut_purge=None, polish=None):
     """mvx_bnb_params with ParameterObj's defaults (util.h:65-67) overridden by the arguments (None: the default)."""
     pr = BnbParams()
     lib().mvx_bnb_default_params(C.byref(pr))
@@ -344,13 +356,15 @@ def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, l
         pr.cut_families = cut_families
     if cut_purge is not None:
         pr.cut_purge = cut_purge
+    if polish is not None:
+        pr.polish = polish
     return pr
 
 
 def branch_and_bound(prob, var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, table=None, window=None,
                      cut_select=0, cut_chance=1.0, best_window=None, sb_cands=None, sb_iters=None, heur=None, rc_fix=None, prop=None,
                      dive=None, dive_freq=None, dive_depth=None, pump=None, pump_freq=None, pump_alpha=None, cut_rounds=None,
-                     cut_round_max=None, cut_maxpar=None, cut_families=None, cut_purge=None):
+                     cut_round_max=None, cut_maxpar=None, cut_families=None, cut_purge=None, polish=None):
     """Run the driver on `prob` (a capi.Prob).  table=None uses the gfx950 engine's own table.  best_window > 1 with
     node_strat=1: the speculative best-bound window (mvx_bnb_params.best_window).  var_strat 3 / 4: branching on the node
     LP's penalties / strong branching (sb_cands candidates, sb_iters pivots per child).  heur 1 / 2: the primal rounding
@@ -365,13 +379,15 @@ def branch_and_bound(prob, var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, 
     tree starts, at most cut_round_max (default 32) cuts a round, none more than cut_maxpar (default 0.9) parallel to one
     taken before it in the round (quirks=0; every single-GPU driver); cut_families chooses the families of those rounds as bits, 1 GMI
     (the default), 2 clique cuts from the conflict graph of the binary columns; cut_purge = A in 1..64 takes a row of those rounds
-    out again once its auxiliary variable has been basic after A consecutive re-solves (0, the default: no row leaves).  The
+    out again once its auxiliary variable has been basic after A consecutive re-solves (0, the default: no row leaves).
+    polish = N in 1..100000: every point that becomes the incumbent is first improved by a best-improvement search over one- and
+    two-column unit moves, at most N of them (quirks=0; every single-GPU driver, best_window included).  The
     dictionary's "rc" is mvx_branchAndBound's return code (-1 refused parameters, -2 penalties, heuristic, tightening,
     propagation, pumps or dives unavailable)."""
     L = lib()
     pr = make_params(var_strat, node_strat, cut_strat, max_nodes, quirks, lazy_pool, window, cut_select, cut_chance, best_window, sb_cands,
                      sb_iters, heur, rc_fix, prop, dive, dive_freq, dive_depth, pump, pump_freq, pump_alpha, cut_rounds, cut_round_max,
-                     cut_maxpar, cut_families, cut_purge)
+                     cut_maxpar, cut_families, cut_purge, polish)
     res = BnbResult()
     tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
     rc = L.mvx_branchAndBound(tptr, prob.h, C.byref(pr), C.byref(res))
@@ -543,6 +559,41 @@ def round_node(prob, root, mode=2, table=None):
     tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
     rc = lib().mvx_bnb_round(tptr, prob.h, root.h, mode, C.byref(obj), C.byref(found), x.ctypes.data_as(C.POINTER(C.c_double)))
     return rc, obj.value, found.value, x
+
+
+POLISH_COUNTERS = ("polish_calls", "polish_moves", "polish_improved")
+
+
+def polish_many(root, xs, max_moves=1000, table=False):
+    """The incumbent polishing (DESIGN.md "Incumbent polishing (polish)") of the points xs, shape (count, n + 1) with entry 0 of a
+    point unused, against the model of the handle `root`.  table=False: mvx_polish_many, the gfx950 engine's kernels, one call for
+    all points; otherwise the host twin mvx_bnb_polish through `table` (None = the gfx950 engine's table), point by point.
+    Returns (rc, x array (count, n + 1), obj array, moves array, ok array); the input is not modified."""
+    import numpy as np
+
+    x = np.array(xs, dtype=np.float64, order="C", copy=True)
+    if x.ndim == 1:
+        x = x.reshape(1, -1)
+    k = x.shape[0]
+    if x.shape[1] != root.n + 1:
+        raise ValueError("polish_many: points need n + 1 = %d entries, got %d" % (root.n + 1, x.shape[1]))
+    obj = np.zeros(max(1, k))
+    moves = np.zeros(max(1, k), dtype=np.int32)
+    ok = np.zeros(max(1, k), dtype=np.int32)
+    DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    if table is False:
+        rc = lib().mvx_polish_many(root.h, k, x.ctypes.data_as(DP), max_moves, obj.ctypes.data_as(DP), moves.ctypes.data_as(IP),
+                                   ok.ctypes.data_as(IP))
+    else:
+        tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
+        rc = 0
+        for t in range(k):
+            o, mv, good = C.c_double(0.0), C.c_int(0), C.c_int(0)
+            rc = lib().mvx_bnb_polish(tptr, root.h, x[t].ctypes.data_as(DP), max_moves, C.byref(o), C.byref(mv), C.byref(good))
+            if rc != 0:
+                break
+            obj[t], moves[t], ok[t] = o.value, mv.value, good.value
+    return rc, x, obj[:k], moves[:k], ok[:k]
 
 
 def rc_tighten_many(probs, cutoffs, tol=1e-9):

@@ -51,6 +51,8 @@ extern "C" int mvx_pump_obj_many(const mvx_prob *root, const mvx_prob *const *Ps
 extern "C" int mvx_cut_scores(const mvx_prob *P, int k, const double *vals, double *dot, double *gram) __attribute__((weak));
 extern "C" int mvx_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rhs) __attribute__((weak));
 extern "C" int mvx_conflict_graph(const mvx_prob *model, unsigned long long *adj, long long *edges) __attribute__((weak));
+extern "C" int mvx_polish_many(const mvx_prob *root, int count, double *x, int max_moves, double *obj, int *moves, int *ok)
+    __attribute__((weak));
 extern "C" int mvx_del_rows(mvx_prob *P, int nrs, const int *num) __attribute__((weak));
 
 namespace {
@@ -1109,6 +1111,173 @@ struct HeurBook {
   }
 };
 
+// ---- incumbent polishing (polish, DESIGN.md "Incumbent polishing (polish)") ----
+
+// The exchange search on one point against the model M (the host twin of k_lsact / k_lsmove / k_lsapply: the same test values in
+// the same order).  The candidates of an iteration are walked singles first, then pairs by index(u), index(v), and one is taken
+// only when its gain is strictly above the best so far: that is the tie rule.  A candidate that cannot win is not tested, which
+// changes no result.  x[1..n] is edited in place when *ok comes back 1.
+static void polish_host(const RoundHost &M, double *x, int max_moves, double *obj, int *moves, int *ok) {
+  const int n = M.n, m0 = M.m0;
+  *obj = 0.0;
+  *moves = 0;
+  *ok = 0;
+  std::vector<double> xt((size_t)n + 1, 0.0), r((size_t)m0, 0.0);
+  for (int j = 1; j <= n; j++) {
+    double v = x[j];
+    if (M.isint[(size_t)j]) {
+      const double ri = std::rint(v);
+      if (!(std::fabs(v - ri) <= 1e-9)) return; // refused
+      v = ri;
+    }
+    xt[(size_t)j] = v;
+  }
+  std::vector<double> lo_t((size_t)m0), hi_t((size_t)m0);
+  for (int i = 0; i < m0; i++) {
+    lo_t[(size_t)i] = M.rlo[(size_t)i] - round_tol(M.rlo[(size_t)i]);
+    hi_t[(size_t)i] = M.rhi[(size_t)i] + round_tol(M.rhi[(size_t)i]);
+  }
+  auto inside = [&](int i, double t) { return t >= lo_t[(size_t)i] && t <= hi_t[(size_t)i]; };
+  // the rounding heuristic's Activity and Feasible on xt
+  auto feasible = [&](std::vector<double> &act) {
+    for (int j = 1; j <= n; j++)
+      if (!(M.clo[(size_t)j] <= xt[(size_t)j] && xt[(size_t)j] <= M.chi[(size_t)j])) return false;
+    bool good = true;
+    for (int i = 0; i < m0; i++) {
+      double acc = 0.0;
+      for (const auto &e : M.rows[(size_t)i])
+        if (xt[(size_t)e.first] != 0.0) acc = acc + e.second * xt[(size_t)e.first];
+      act[(size_t)i] = acc;
+      good = good && inside(i, acc);
+    }
+    return good;
+  };
+  auto objective = [&]() {
+    double sum = 0.0;
+    for (int j = 1; j <= n; j++) sum = sum + M.c[(size_t)j] * xt[(size_t)j];
+    return sum + M.c[0];
+  };
+  if (!feasible(r)) return; // refused
+  const std::vector<double> x0 = xt;
+  const double obj0 = objective();
+  const int U = 2 * n;
+  std::vector<char> adm((size_t)U, 0), ubad((size_t)m0, 0);
+  std::vector<double> gain((size_t)U, 0.0), ru((size_t)m0, 0.0);
+  auto col_of = [](int u) { return (u >> 1) + 1; };
+  auto dir_of = [](int u) { return (u & 1) ? -1.0 : 1.0; };
+  int taken = 0;
+  while (taken < max_moves) {
+    double gmax = 0.0; // the greatest gain of an admissible move: no pair gains more than g(u) + gmax
+    for (int u = 0; u < U; u++) {
+      const int j = col_of(u);
+      const double d = dir_of(u), xn = xt[(size_t)j] + d;
+      adm[(size_t)u] = M.isint[(size_t)j] && xn >= std::ceil(M.clo[(size_t)j]) && xn <= std::floor(M.chi[(size_t)j]);
+      gain[(size_t)u] = M.sg * (d * M.c[(size_t)j]);
+      if (adm[(size_t)u] && gain[(size_t)u] > gmax) gmax = gain[(size_t)u];
+    }
+    double best = 0.0;
+    int bu = -1, bv = -1;
+    for (int u = 0; u < U; u++) { // singles
+      if (!adm[(size_t)u] || !(gain[(size_t)u] > best)) continue;
+      const double d = dir_of(u);
+      bool good = true;
+      for (const auto &e : M.cols[(size_t)col_of(u)])
+        if (!inside(e.first, r[(size_t)e.first] + d * e.second)) {
+          good = false;
+          break;
+        }
+      if (good) {
+        best = gain[(size_t)u];
+        bu = u;
+      }
+    }
+    for (int u = 0; u < U; u++) { // pairs: the partner's column lies behind u's
+      if (!adm[(size_t)u] || !(gain[(size_t)u] + gmax > best)) continue;
+      const int ju = col_of(u);
+      const double du = dir_of(u);
+      ru = r;
+      int nbad = 0;
+      for (const auto &e : M.cols[(size_t)ju]) {
+        const double t = r[(size_t)e.first] + du * e.second;
+        ru[(size_t)e.first] = t;
+        if (!inside(e.first, t)) {
+          ubad[(size_t)e.first] = 1;
+          nbad++;
+        }
+      }
+      for (int v = 2 * ju; v < U; v++) {
+        if (!adm[(size_t)v]) continue;
+        const double g = gain[(size_t)u] + gain[(size_t)v];
+        if (!(g > best)) continue;
+        const double dv = dir_of(v);
+        bool good = true;
+        int mended = 0; // rows the single move u breaks that v touches: the others stay broken
+        for (const auto &e : M.cols[(size_t)col_of(v)]) {
+          if (!inside(e.first, ru[(size_t)e.first] + dv * e.second)) {
+            good = false;
+            break;
+          }
+          mended += ubad[(size_t)e.first];
+        }
+        if (good && mended == nbad) {
+          best = g;
+          bu = u;
+          bv = v;
+        }
+      }
+      if (nbad)
+        for (const auto &e : M.cols[(size_t)ju]) ubad[(size_t)e.first] = 0;
+    }
+    if (bu < 0) break;
+    for (const auto &e : M.cols[(size_t)col_of(bu)]) r[(size_t)e.first] = r[(size_t)e.first] + dir_of(bu) * e.second;
+    xt[(size_t)col_of(bu)] = xt[(size_t)col_of(bu)] + dir_of(bu);
+    if (bv >= 0) {
+      for (const auto &e : M.cols[(size_t)col_of(bv)]) r[(size_t)e.first] = r[(size_t)e.first] + dir_of(bv) * e.second;
+      xt[(size_t)col_of(bv)] = xt[(size_t)col_of(bv)] + dir_of(bv);
+    }
+    taken++;
+  }
+  *ok = 1;
+  if (feasible(ru)) { // the freshly summed activities
+    *obj = objective();
+    *moves = taken;
+  } else { // a tolerance edge: the entry point
+    xt = x0;
+    *obj = obj0;
+  }
+  for (int j = 1; j <= n; j++) x[j] = xt[(size_t)j];
+}
+
+// One tree's polishing: polish_many when the table has it, the twin with the model read once without it or on -5.
+class Polish {
+public:
+  Polish(const mvx_lp_api *api, const void *root, int cap) : _api(api), _root(root), _cap(cap) {}
+  // x[0..n] edited in place when *ok; 0, or the failing call's code
+  int run(std::vector<double> &x, double *obj, int *moves, int *ok) {
+    if (_api->polish_many && _device) {
+      const int rc = _api->polish_many(_root, 1, x.data(), _cap, obj, moves, ok);
+      if (rc == 0) return 0;
+      if (rc != -5) return rc;
+      _device = false; // the kernel's size limit: the host twin, same bits, for the rest of the tree
+    }
+    if (!_ready) {
+      const int rc = round_host_model(_api, _root, _M);
+      if (rc != 0) return rc;
+      _ready = true;
+    }
+    polish_host(_M, x.data(), _cap, obj, moves, ok);
+    return 0;
+  }
+
+private:
+  const mvx_lp_api *_api;
+  const void *_root;
+  int _cap;
+  bool _device = true;
+  bool _ready = false;
+  RoundHost _M;
+};
+
 // ---- reduced-cost bound tightening (rc_fix, DESIGN.md "Reduced-cost tightening") ----
 
 struct RcEntry {
@@ -2095,10 +2264,13 @@ struct Tree {
   HeurBook hbook;
   DiveBook dbook;
   PumpBook pbook;
+  Polish pol; // reads `model`: the rows from before the root cut loop, as the other rules that read the model do
+  long long polish_calls = 0, polish_moves = 0, polish_improved = 0;
+  bool failed = false; // a point could not be polished: the run ends with -2
 
-  Tree(const mvx_lp_api *api_, const void *prob, const mvx_bnb_params &p)
+  Tree(const mvx_lp_api *api_, const void *prob, const mvx_bnb_params &p, const void *model = nullptr)
       : api(api_), prm(p), quirks(p.reference_quirks != 0), sg(MVOLP::sense_of(api_, prob, p)), n0(api_->get_num_cols(prob)),
-        bestLower(-sg * std::numeric_limits<double>::infinity()), xbest((size_t)n0 + 1, 0.0) {}
+        bestLower(-sg * std::numeric_limits<double>::infinity()), xbest((size_t)n0 + 1, 0.0), pol(api_, model ? model : prob, p.polish) {}
 
   std::shared_ptr<MVOLP::NodeData> root(const void *prob) { // bs.cpp:80
     auto S1 = std::make_shared<MVOLP::NodeData>(api, prob, id);
@@ -2108,6 +2280,7 @@ struct Tree {
   }
 
   bool node_limit() {
+    if (failed) return true;
     if (prm.max_nodes > 0 && count >= prm.max_nodes) hit_limit = 1;
     return hit_limit != 0;
   }
@@ -2136,6 +2309,7 @@ struct Tree {
         hbook.incumbent = 0; // the node's own point, not the heuristic's
         const int na = api->get_num_cols(h);
         for (int i = 1; i <= na && i <= n0; i++) xbest[(size_t)i] = api->get_col_prim(h, i);
+        polish_incumbent();
       }
       return node.inital ? STOP : INTEGER;
     }
@@ -2152,7 +2326,31 @@ struct Tree {
     return BRANCH;
   }
 
-  void book_heur(const HeurOut &h, int oid) { hbook.book(h, oid, sg, bestLower, has_incumbent, incumbent_oid, xbest); }
+  // polish > 0: the point that has just become the incumbent is polished where the serial loop books it, whichever source it
+  // came from; the source's decision and counters are those of the point as found.  A refused point (ok = 0) stays as booked.
+  void polish_incumbent() {
+    if (prm.polish <= 0 || failed) return;
+    std::vector<double> x = xbest;
+    double obj = 0.0;
+    int moves = 0, ok = 0;
+    if (pol.run(x, &obj, &moves, &ok) != 0) {
+      rc_out = -2;
+      failed = true;
+      return;
+    }
+    polish_calls++;
+    if (!ok) return;
+    polish_moves += moves;
+    if (sg * obj > sg * bestLower) polish_improved++;
+    bestLower = obj;
+    for (size_t j = 1; j < xbest.size(); j++) xbest[j] = x[j];
+  }
+
+  void book_heur(const HeurOut &h, int oid) {
+    const long long before = hbook.improved;
+    hbook.book(h, oid, sg, bestLower, has_incumbent, incumbent_oid, xbest);
+    if (hbook.improved != before) polish_incumbent();
+  }
   // a dived node that branches: its work is booked, and its point becomes the incumbent when it is strictly better
   void book_dive(const DiveOut &d, int oid) {
     dbook.calls++;
@@ -2167,6 +2365,7 @@ struct Tree {
     incumbent_oid = oid;
     hbook.incumbent = 2;
     for (size_t j = 1; j < xbest.size() && j < d.x.size(); j++) xbest[j] = d.x[j];
+    polish_incumbent();
   }
   // a pumped node that branches: its work is booked, and its point becomes the incumbent when it is strictly better
   void book_pump(const PumpOut &p, int oid) {
@@ -2182,6 +2381,7 @@ struct Tree {
     incumbent_oid = oid;
     hbook.incumbent = 3;
     for (size_t j = 1; j < xbest.size() && j < p.x.size(); j++) xbest[j] = p.x[j];
+    polish_incumbent();
   }
   void book_choice(const Choice &c) {
     sb_lps += c.sb_lps;
@@ -2229,6 +2429,9 @@ struct Tree {
     hbook.store(res);
     dbook.store(res);
     pbook.store(res);
+    res->polish_calls = polish_calls;
+    res->polish_moves = polish_moves;
+    res->polish_improved = polish_improved;
     if (rcfix) rcfix->store(res);
     if (prop) prop->store(res);
     return rc_out;
@@ -2259,7 +2462,7 @@ static int on_slots(const std::vector<void *> &hs, const std::vector<char> &mask
 int branchAndBound(const mvx_lp_api *api, void *prob, const void *model, const mvx_bnb_params &prm, mvx_bnb_result *res) { // bs.cpp:54
   MVOLP::ParameterObj params(api, prob, prm);
   CutPool pool(api);
-  Tree T(api, prob, prm);
+  Tree T(api, prob, prm, model);
   Recorder &rec = T.rec;
   std::deque<std::shared_ptr<MVOLP::NodeData>> leafContainer;
   leafContainer.push_back(T.root(prob));
@@ -2385,7 +2588,7 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const void *model, const m
 // incumbent are those of the node-at-a-time loop above.
 int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const void *model, const mvx_bnb_params &prm, mvx_bnb_result *res) {
   MVOLP::ParameterObj params(api, prob, prm);
-  Tree T(api, prob, prm);
+  Tree T(api, prob, prm, model);
   Recorder &rec = T.rec;
   const bool quirks = T.quirks;
   std::deque<std::shared_ptr<MVOLP::NodeData>> leafContainer;
@@ -2833,7 +3036,7 @@ static void classify_round(const mvx_lp_api *api, const std::vector<void *> &hs,
 int branchAndBoundBest(const mvx_lp_api *api, void *prob, const void *model, const mvx_bnb_params &prm, mvx_bnb_result *res) {
   MVOLP::ParameterObj params(api, prob, prm);
   CutPool pool(api);
-  Tree T(api, prob, prm);
+  Tree T(api, prob, prm, model);
   Recorder &rec = T.rec;
   const bool quirks = T.quirks;
   const double sg = T.sg;
@@ -3107,6 +3310,9 @@ const mvx_lp_api g_hip_api = {
       return mvx_conflict_graph((const mvx_prob *)model, adj, edges);
     } : nullptr,
     mvx_del_rows ? +[](void *P, int nrs, const int *num) { return mvx_del_rows((mvx_prob *)P, nrs, num); } : nullptr,
+    mvx_polish_many ? +[](const void *root, int count, double *x, int max_moves, double *obj, int *moves, int *ok) {
+      return mvx_polish_many((const mvx_prob *)root, count, x, max_moves, obj, moves, ok);
+    } : nullptr,
 };
 
 } // namespace
@@ -3143,6 +3349,7 @@ void mvx_bnb_default_params(mvx_bnb_params *p) {
   p->cut_maxpar = 0.0;
   p->cut_families = 0;
   p->cut_purge = 0;
+  p->polish = 0;
 }
 
 // Repaired mode's rule for an integer column whose bounds are not integers (legal input: LP and MPS files may carry them):
@@ -3549,7 +3756,9 @@ int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *
       (params->cut_rounds > 0 && (params->reference_quirks != 0 || params->cut_round_max < 0 || params->cut_round_max > 4096 ||
                                   !(params->cut_maxpar == 0.0 || (params->cut_maxpar > 0.0 && params->cut_maxpar <= 1.0)) ||
                                   params->cut_families < 0 || params->cut_families > 3 || params->cut_purge < 0 ||
-                                  params->cut_purge > 64))) {
+                                  params->cut_purge > 64)) ||
+      // polish: the repaired mode's incumbent; every single-GPU driver
+      params->polish < 0 || params->polish > 100000 || (params->polish > 0 && params->reference_quirks != 0)) {
     std::memset(res, 0, sizeof(*res));
     return -1;
   }
@@ -3829,6 +4038,16 @@ int mvx_bnb_cut_loop(const mvx_lp_api *api, void *prob, int rounds, int K, doubl
   const int rc = mvx_bnb_cut_loop_families(api, prob, rounds, K, maxpar, 1, all, bounds);
   if (rc != -1) std::copy(all, all + 5, counters);
   return rc;
+}
+
+int mvx_bnb_polish(const mvx_lp_api *api, const void *root, double *x, int max_moves, double *obj, int *moves, int *ok) {
+  if (!api) api = &g_hip_api;
+  if (!root || !x || !obj || !moves || !ok || max_moves < 1 || max_moves > 100000) return -1;
+  RoundHost M;
+  const int rc = round_host_model(api, root, M);
+  if (rc != 0) return rc;
+  polish_host(M, x, max_moves, obj, moves, ok);
+  return 0;
 }
 
 int mvx_bnb_conflict_graph(const mvx_lp_api *api, const void *model, unsigned long long *adj, long long *edges) {

@@ -582,6 +582,9 @@ int mvx_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rhs) 
 int mvx_conflict_graph(const mvx_prob *model, unsigned long long *adj, long long *edges) {
   return mvx::engine_conflict_graph(model, adj, edges);
 }
+int mvx_polish_many(const mvx_prob *root, int count, double *x, int max_moves, double *obj, int *moves, int *ok) {
+  return mvx::engine_polish_many(root, count, x, max_moves, obj, moves, ok);
+}
 
 int mvx_device_count(void) { return mvx::device_count(); }
 int mvx_set_device(int dev) { return mvx::set_device(dev); }

@@ -3143,6 +3143,74 @@ int engine_conflict_graph(const mvx_prob *R, unsigned long long *adj, long long 
   return 0;
 }
 
+// ------------------------------------------------------------------ incumbent polishing (k_lsact, k_lsmove, k_lsapply)
+// The exchange search of mvx_polish_many on `count` points against root's model (both orientations, as the conflict graph
+// reads it): the points go up, k_lsact takes the entry, then iterations (k_lsmove + k_lsapply) are enqueued LS_GROUP at a time
+// with one look at the done flags per group, never more than max_moves in all, k_lsact again for the end, and the results come
+// back.  No handle is read or changed.  The points go through in chunks that keep the records (2n per point) within 256 MiB
+// and the grid's second dimension within its limit; the arena is reserved once for all of them, so -2 leaves nothing written.
+// Return codes: 0; -1 bad arguments; -2 device out of memory.  The kernels have no size limit.
+int engine_polish_many(const mvx_prob *root, int count, double *x, int max_moves, double *obj, int *moves, int *ok) {
+  if (!root || count < 0 || max_moves < 1 || max_moves > 100000 || (count > 0 && (!x || !obj || !moves || !ok))) return -1;
+  if (count == 0) return 0;
+  const int n = root->n, m0 = root->m;
+  NodeCall f(NodeFlush::Never, NodeResults::Device);
+  const RoundModel *M = round_model(*f.c, root);
+  if (!M || !round_model_rows(*f.c, root, root->rmod.get())) return -2;
+  const size_t row = (size_t)n + 1, recs = (size_t)std::max(1, 2 * n) * sizeof(LsRec);
+  const int chunk = (int)std::min<size_t>((size_t)count, std::max<size_t>(1, std::min<size_t>(4096, ((size_t)256 << 20) / recs)));
+  // up: [xin]; back: [x][obj][moves][ok][done]; device only: [r][obj0][records]
+  const size_t o_xin = f.up((size_t)chunk * row * 8);
+  const size_t o_x = f.out((size_t)chunk * row * 8), o_obj = f.out((size_t)chunk * 8), o_moves = f.out((size_t)chunk * 4);
+  const size_t o_ok = f.out((size_t)chunk * 4), o_done = f.out((size_t)chunk * 4);
+  const size_t o_r = f.dev((size_t)chunk * (size_t)M->ldm * 8), o_obj0 = f.dev((size_t)chunk * 8), o_rec = f.dev((size_t)chunk * recs);
+  if (!f.reserve()) return -2;
+  unsigned char *hb = f.hb, *db = f.db;
+  const unsigned char *mb = (const unsigned char *)M->dev;
+  LsArgs a;
+  a.At = (const double *)mb;
+  a.Ar = (const double *)M->dev_rows;
+  a.rlo = (const double *)(mb + M->o_rlo); a.rhi = (const double *)(mb + M->o_rhi);
+  a.clo = (const double *)(mb + M->o_clo); a.chi = (const double *)(mb + M->o_chi); a.c = (const double *)(mb + M->o_c);
+  a.flags = (const int *)(mb + M->o_flags);
+  a.xin = (const double *)(db + o_xin); a.x = (double *)(db + o_x); a.r = (double *)(db + o_r);
+  a.obj = (double *)(db + o_obj); a.obj0 = (double *)(db + o_obj0);
+  a.moves = (int *)(db + o_moves); a.ok = (int *)(db + o_ok); a.done = (int *)(db + o_done);
+  a.rec = (LsRec *)(db + o_rec);
+  a.sg = root->dir == MVX_MIN ? -1.0 : 1.0;
+  a.n = n; a.m0 = m0; a.ldm = M->ldm; a.ldn = M->ldn; a.pad = 0;
+  for (int t0 = 0; t0 < count; t0 += chunk) {
+    const int k = std::min(chunk, count - t0);
+    a.count = k;
+    std::memcpy(hb + o_xin, x + (size_t)t0 * row, (size_t)k * row * 8);
+    f.upload();
+    launch_lsact(a, 0, f.stream());
+    const int *h_done = (const int *)(hb + o_done);
+    for (int queued = 0; queued < max_moves;) {
+      const int g = std::min(LS_GROUP, max_moves - queued);
+      for (int q = 0; q < g; q++) launch_lsiter(a, f.stream());
+      queued += g;
+      HIPCHECK(hipMemcpyAsync(hb + o_done, db + o_done, (size_t)k * 4, hipMemcpyDeviceToHost, f.stream()));
+      f.sync();
+      bool all = true;
+      for (int t = 0; t < k; t++) all = all && h_done[t] != 0;
+      if (all) break;
+    }
+    launch_lsact(a, 1, f.stream());
+    f.fetch();
+    const double *h_x = (const double *)(hb + o_x), *h_obj = (const double *)(hb + o_obj);
+    const int *h_moves = (const int *)(hb + o_moves), *h_ok = (const int *)(hb + o_ok);
+    for (int t = 0; t < k; t++) {
+      const size_t g = (size_t)(t0 + t);
+      ok[g] = h_ok[t];
+      obj[g] = h_ok[t] ? h_obj[t] : 0.0;
+      moves[g] = h_ok[t] ? h_moves[t] : 0;
+      if (h_ok[t]) std::memcpy(x + g * row + 1, h_x + (size_t)t * row + 1, (size_t)n * 8); // a refused point stays untouched
+    }
+  }
+  return 0;
+}
+
 // ------------------------------------------------------------------ bound lists (k_setbnds)
 // What the two bound-list entries check alike, before anything is edited: 1 go on, 0 nothing to do, -1 a bad list.  `general`
 // (mvx_set_col_bnds_many): infinite bounds are allowed, a handle listed twice is not; else (mvx_tighten_cols_many) the

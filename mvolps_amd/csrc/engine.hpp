@@ -56,6 +56,8 @@ int engine_pump_obj_many(const mvx_prob *root, const mvx_prob *const *Ps, int co
 int engine_cut_scores(const mvx_prob *P, int k, const double *vals, const double *x, double *dot, double *gram);
 int engine_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rhs);
 int engine_conflict_graph(const mvx_prob *R, unsigned long long *adj, long long *edges);
+// incumbent polishing of `count` points against root's model (k_lsact, k_lsmove, k_lsapply); see engine.cpp
+int engine_polish_many(const mvx_prob *root, int count, double *x, int max_moves, double *obj, int *moves, int *ok);
 // reduced-cost bound tightening of `count` solved handles, one launch (k_rcfix), and the bound lists of many handles applied
 // with one launch (k_setbnds, entries on non-basic positions only); see engine.cpp
 int engine_rc_tighten_many(const mvx_prob *const *Ps, int count, const double *cutoff, double tol, int *cnt, int *cols, double *lb,

@@ -87,6 +87,8 @@ int main(int argc, char **argv) {
               << "                  conflict graph of the binary columns\n"
               << "  --cut-purge [A] with --cut-rounds: a cut row leaves the root LP again once it has been slack after A re-solves in a\n"
               << "                  row (1..64; 3 without a number)\n"
+              << "  --polish [N]    with --repaired: every point that becomes the incumbent is first improved by a search over one- and\n"
+              << "                  two-column unit moves, at most N of them (1..100000; 1000 without a number)\n"
               << "Help:\n  -h/--help\n";
     return 0;
   }
@@ -225,6 +227,17 @@ int main(int argc, char **argv) {
       return -1;
     }
   }
+  if (input.CMDOptionExists("--polish")) {
+    // the number is optional, as for --prop
+    const std::string &k = input.getCMDOption("--polish");
+    const bool numeric = !k.empty() && std::all_of(k.begin(), k.end(), [](char ch) { return ch >= '0' && ch <= '9'; });
+    const long kv = numeric ? std::strtol(k.c_str(), nullptr, 10) : 1000;
+    params.polish = kv >= 1 && kv <= 100000 ? (int)kv : -1;
+    if (params.polish < 1) {
+      std::fprintf(stderr, "Unknown parameter value for --polish\n");
+      return -1;
+    }
+  }
   if (input.CMDOptionExists("--cut-select")) params.cut_select = std::atoi(input.getCMDOption("--cut-select").c_str());
   if (input.CMDOptionExists("--window")) params.window = std::atoi(input.getCMDOption("--window").c_str());
   if (input.CMDOptionExists("--best-window")) params.best_window = std::atoi(input.getCMDOption("--best-window").c_str());
@@ -235,15 +248,16 @@ int main(int argc, char **argv) {
   mvx_bnb_result res;
   const int brc = mvx_branchAndBound(nullptr, prob, &params, &res);
   if (brc == -1) {
-    std::fprintf(stderr, "-vs %d / --heur %d%s%s%s%s%s are not supported with these options (-vs 3 / 4: not with --best-window; --heur: only "
-                 "with --repaired; --rcfix / --prop / --dive / --pump: only with --repaired and without --best-window; --cut-rounds: only with --repaired)\n",
+    std::fprintf(stderr, "-vs %d / --heur %d%s%s%s%s%s%s are not supported with these options (-vs 3 / 4: not with --best-window; --heur: only "
+                 "with --repaired; --rcfix / --prop / --dive / --pump: only with --repaired and without --best-window; --cut-rounds / --polish: only with --repaired)\n",
                  params.var_strat, params.heur, params.rc_fix ? " / --rcfix" : "", params.prop ? " / --prop" : "",
-                 params.dive ? " / --dive" : "", params.pump ? " / --pump" : "", params.cut_rounds ? " / --cut-rounds" : "");
+                 params.dive ? " / --dive" : "", params.pump ? " / --pump" : "", params.cut_rounds ? " / --cut-rounds" : "",
+                 params.polish ? " / --polish" : "");
     mvx_delete_prob(prob);
     return -1;
   }
   if (brc != 0)
-    std::fprintf(stderr, "branch-and-bound stopped: the branching penalties, the heuristic, the propagation, a pump, a dive or the root cut rounds could not be computed (%d)\n", brc);
+    std::fprintf(stderr, "branch-and-bound stopped: the branching penalties, the heuristic, the propagation, a pump, a dive, the root cut rounds or the polishing could not be computed (%d)\n", brc);
   if (input.CMDOptionExists("--events")) mvx_bnb_write_events(&res, input.getCMDOption("--events").c_str());
   mvx_bnb_print_tree(&res, nullptr); // bs.cpp:329-343
   std::vector<char> buf(64 + 64 * (size_t)res.n);
@@ -276,6 +290,9 @@ int main(int argc, char **argv) {
                 res.cutloop_clique_rows);
   if (verbose && params.cut_rounds > 0 && params.cut_purge > 0)
     std::printf("Cut purging: %lld rows purged, %lld live rows\n", res.cutloop_purged, res.cutloop_live_rows);
+  if (verbose && params.polish > 0)
+    std::printf("Incumbent polishing: %lld points, %lld moves, %lld came back better\n", res.polish_calls, res.polish_moves,
+                res.polish_improved);
   const int limit = res.hit_limit || brc != 0;
   mvx_bnb_free_result(&res);
   mvx_delete_prob(prob);

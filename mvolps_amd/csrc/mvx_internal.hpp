@@ -430,6 +430,30 @@ struct ConflictArgs {
   int n, m0, ldm, ldn, W, pad;
 };
 
+// arguments of k_lsact / k_lsmove / k_lsapply (mvx_polish_many): the root's model in both orientations, as k_conflict reads it,
+// with the objective, and per point its values, row activities, the records of one iteration and its counters
+#define LS_GROUP 8 // iterations the host enqueues between two looks at the done flags
+struct LsRec {
+  double gain;            // the best feasible candidate's gain, 0.0 when there is none
+  unsigned long long key; // single: index(u) << 31; pair: 1 << 62 | index(u) << 31 | index(v); ~0 when there is none
+};
+struct LsArgs {
+  const double *At;        // [n+1][ldm]: At[j*ldm + i] = a_(i+1),j
+  const double *Ar;        // [m0][ldn]: Ar[i*ldn + j] = a_(i+1),j; ldn = 64 * W, the padding is zero
+  const double *rlo, *rhi; // [m0] row bounds, +-inf when absent
+  const double *clo, *chi; // [n+1] the root's column bounds, +-inf when absent
+  const double *c;         // [n+1] objective, c[0] the constant
+  const int *flags;        // [n+1] RND_INT: the column is integer
+  const double *xin;       // [count][n+1] the points as handed in
+  double *x;               // [count][n+1] the points at work, and the result
+  double *r;               // [count][ldm] row activities
+  double *obj, *obj0;      // [count] the result's objective; the entry point's
+  int *moves, *ok, *done;  // [count]
+  LsRec *rec;              // [count][2n] one record per unit move
+  double sg;
+  int n, m0, ldm, ldn, count, pad;
+};
+
 // k_setbnds (mvx_set_col_bnds_many, mvx_tighten_cols_many): per handle a range of bound writes and a range of shifts of column 0
 struct SetbHandle {
   double *T, *blb, *bub, *nlb, *nub;
@@ -487,6 +511,8 @@ void launch_cutgram(const CutGramArgs &a, hipStream_t);
 void launch_cutrows(const CutRowsArgs &a, hipStream_t);
 void launch_delrows(const DelRowsArgs &a, hipStream_t);
 void launch_conflict(const ConflictArgs &a, hipStream_t);
+void launch_lsact(const LsArgs &a, int final, hipStream_t);
+void launch_lsiter(const LsArgs &a, hipStream_t);
 void launch_setbnds(const SetbHandle *hs, const SetbEntry *es, const SetbShift *ss, int handles, hipStream_t);
 void launch_refresh_select(Ctl *, const int *tflag, int var, hipStream_t);
 size_t persist_lds_bytes(int m, int cpw);

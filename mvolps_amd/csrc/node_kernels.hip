@@ -1300,4 +1300,270 @@ void launch_conflict(const ConflictArgs &a, hipStream_t s) {
   hipLaunchKernelGGL(k_conflict, dim3((unsigned)(a.n + 1), (unsigned)((a.W + CONF_WAVES - 1) / CONF_WAVES)), dim3(64 * CONF_WAVES), 0, s, a);
 }
 
+// ---------------------------------------------------------------------------- k_lsact / k_lsmove / k_lsapply
+// Incumbent polishing (mvx_polish_many, DESIGN.md "Incumbent polishing (polish)"): a best-improvement search over one- and
+// two-column unit moves from a feasible point.  A candidate is (gain, key); the greater gain wins, and on equal gains the
+// lower key: a single before a pair, then the lower index(u), then the lower index(v).
+__device__ __forceinline__ bool ls_better(double ga, unsigned long long ka, double gb, unsigned long long kb) {
+  return ga > gb || (ga == gb && ka < kb);
+}
+__device__ __forceinline__ void ls_wave_best(double &g, unsigned long long &k) {
+  for (int off = 32; off > 0; off >>= 1) {
+    const double og = __shfl_xor(g, off, 64);
+    const unsigned kl = (unsigned)k, kh = (unsigned)(k >> 32);
+    const unsigned long long ok = ((unsigned long long)(unsigned)__shfl_xor((int)kh, off, 64) << 32) | (unsigned)__shfl_xor((int)kl, off, 64);
+    if (ls_better(og, ok, g, k)) {
+      g = og;
+      k = ok;
+    }
+  }
+}
+__device__ __forceinline__ bool ls_inside(double t, double lo_t, double hi_t) { return t >= lo_t && t <= hi_t; }
+
+// k_lsact, one workgroup per point.  final = 0, the entry: integer columns take rint(x) when they are within 1e-9 of it, the
+// activities are summed as k_round sums them (a row per lane, ascending columns, zero values skipped) and the point is refused
+// (ok = 0, done = 1) when an integer column is fractional or the rounding heuristic's check fails.  final = 1, the end: the
+// same sums and check on the point the moves left; where it fails the entry point returns with moves = 0.  The objective is
+// k_round's, by one wave over the products in order.
+__global__ __launch_bounds__(256) void k_lsact(LsArgs a, int final) {
+  __shared__ int s_bad;
+  const int p = (int)blockIdx.x;
+  if (final && !a.ok[p]) return;
+  const int n = a.n, m0 = a.m0;
+  const size_t ldm = (size_t)a.ldm;
+  const double *xin = a.xin + (size_t)p * (size_t)(n + 1);
+  double *x = a.x + (size_t)p * (size_t)(n + 1);
+  double *r = a.r + (size_t)p * ldm;
+  const int lane = TIDX & 63;
+  if (TIDX == 0) s_bad = 0;
+  __syncthreads();
+  bool bad = false;
+  for (int j = 1 + TIDX; j <= n; j += 256) {
+    double v;
+    if (final) {
+      v = x[j];
+    } else {
+      v = xin[j];
+      if (a.flags[j] & RND_INT) {
+        const double ri = rint(v);
+        if (fabs(v - ri) <= 1e-9) v = ri;
+        else bad = true;
+      }
+      x[j] = v;
+    }
+    bad = bad || !(a.clo[j] <= v && v <= a.chi[j]);
+  }
+  __syncthreads(); // x is read below by every lane
+  for (int i = TIDX; i < m0; i += 256) {
+    double acc = 0.0;
+    for (int j = 1; j <= n; j++) {
+      const double xj = x[j];
+      if (xj != 0.0) acc = __dadd_rn(acc, __dmul_rn(a.At[(size_t)j * ldm + i], xj));
+    }
+    r[i] = acc;
+    const double lo = a.rlo[i], hi = a.rhi[i];
+    bad = bad || !(acc >= lo - rnd_tol(lo) && acc <= hi + rnd_tol(hi));
+  }
+  if (bad) s_bad = 1;
+  __syncthreads();
+  const bool refused = s_bad != 0;
+  if (final && refused) { // a tolerance edge: the entry point comes back
+    for (int j = 1 + TIDX; j <= n; j += 256) x[j] = (a.flags[j] & RND_INT) ? rint(xin[j]) : xin[j];
+    if (TIDX == 0) {
+      a.obj[p] = a.obj0[p];
+      a.moves[p] = 0;
+    }
+    return;
+  }
+  if (TIDX < 64) {
+    double s = 0.0;
+    for (int j0 = 1; j0 <= n; j0 += 64) {
+      const int j = j0 + lane;
+      const double pr = j <= n ? __dmul_rn(a.c[j], x[j]) : 0.0;
+      unsigned long long mk = __ballot(pr != 0.0);
+      while (mk) {
+        const int b = __builtin_ctzll(mk);
+        mk &= mk - 1ull;
+        s = __dadd_rn(s, __shfl(pr, b, 64));
+      }
+    }
+    if (lane == 0) {
+      const double o = refused ? 0.0 : __dadd_rn(s, a.c[0]);
+      a.obj[p] = o;
+      if (!final) {
+        a.obj0[p] = o;
+        a.moves[p] = 0;
+        a.ok[p] = refused ? 0 : 1;
+        a.done[p] = refused ? 1 : 0;
+      }
+    }
+  }
+}
+
+// k_lsmove, one iteration's evaluation: a workgroup owns one unit move u = (j, du) of one point, its four waves the words of
+// partner columns from j's own word on, a lane the column k = 64 w + lane > j with both signs.  Per row the wave reads a_ij and
+// r_i through one address and Ar[i][k] coalesced (the row stride is 64 W: k stays inside the row, the padding reads as zero),
+// and tests t = (r_i + du a_ij) +- a_ik against the row's bounds.  Every row is tested, not only those with a non-zero: r_i
+// itself lies within the bounds, and adding a zero leaves it as it is.  A wave leaves a word as soon as no lane has a candidate
+// left (a uniform branch), and never starts on a word none of whose lanes can beat what it holds.  The first wave carries the
+// single move u along: its test value is the inner sum.  The workgroup's best candidate goes to rec[point][u].
+__global__ __launch_bounds__(256) void k_lsmove(LsArgs a) {
+  __shared__ double s_g[4];
+  __shared__ unsigned long long s_k[4];
+  const int p = (int)blockIdx.y;
+  if (a.done[p]) return;
+  const int u = (int)blockIdx.x;
+  const int n = a.n, m0 = a.m0;
+  const int j = (u >> 1) + 1;
+  const bool neg = (u & 1) != 0;
+  const double du = neg ? -1.0 : 1.0;
+  const size_t ldn = (size_t)a.ldn;
+  const double *x = a.x + (size_t)p * (size_t)(n + 1);
+  const double *r = a.r + (size_t)p * (size_t)a.ldm;
+  LsRec *out = a.rec + (size_t)p * (size_t)(2 * n) + (size_t)u;
+  const double xj = x[j];
+  const bool adm = (a.flags[j] & RND_INT) && (xj + du >= ceil(a.clo[j])) && (xj + du <= floor(a.chi[j]));
+  if (!adm) {
+    if (TIDX == 0) {
+      out->gain = 0.0;
+      out->key = ~0ull;
+    }
+    return;
+  }
+  const double cj = a.c[j];
+  const double gu = a.sg * (neg ? -cj : cj);
+  const int wave = __builtin_amdgcn_readfirstlane(TIDX >> 6), lane = TIDX & 63;
+  const int W = a.ldn >> 6;
+  const unsigned long long ukey = (unsigned long long)u << 31;
+  double bg = 0.0; // the lane's best: only a gain above 0 counts
+  unsigned long long bk = ~0ull;
+  bool first = wave == 0; // the single rides with the first word of the first wave
+  for (int w = (j >> 6) + wave; w < W; w += 4) { // j <= n < 64 W: the first wave always has a word
+    const int k = w * 64 + lane;
+    const bool kint = k > j && k <= n && (a.flags[k] & RND_INT);
+    double gp = 0.0, gm = 0.0;
+    bool ap = false, am = false;
+    if (kint) {
+      const double xk = x[k], ck = a.c[k];
+      gp = __dadd_rn(gu, a.sg * ck);
+      gm = __dadd_rn(gu, a.sg * -ck);
+      ap = xk + 1.0 <= floor(a.chi[k]) && xk + 1.0 >= ceil(a.clo[k]) && gp > bg;
+      am = xk - 1.0 >= ceil(a.clo[k]) && xk - 1.0 <= floor(a.chi[k]) && gm > bg;
+    }
+    bool sa = first && gu > 0.0;
+    if (__any(ap || am) || sa) {
+      for (int i = 0; i < m0; i++) {
+        const double aj = a.Ar[(size_t)i * ldn + (size_t)j];
+        const double lo = a.rlo[i], hi = a.rhi[i];
+        const double lo_t = __dsub_rn(lo, rnd_tol(lo)), hi_t = __dadd_rn(hi, rnd_tol(hi));
+        const double s = __dadd_rn(r[i], neg ? -aj : aj);
+        sa = sa && ls_inside(s, lo_t, hi_t);
+        const double ak = a.Ar[(size_t)i * ldn + (size_t)k];
+        ap = ap && ls_inside(__dadd_rn(s, ak), lo_t, hi_t);
+        am = am && ls_inside(__dadd_rn(s, -ak), lo_t, hi_t);
+        if (!(__any(ap || am) || sa)) break;
+      }
+    }
+    // within a lane a later word has the higher index(v): it must be strictly better
+    if (ap && gp > bg) {
+      bg = gp;
+      bk = (1ull << 62) | ukey | (unsigned long long)(2 * (k - 1));
+    }
+    if (am && gm > bg) {
+      bg = gm;
+      bk = (1ull << 62) | ukey | (unsigned long long)(2 * (k - 1) + 1);
+    }
+    if (sa && lane == 0 && ls_better(gu, ukey, bg, bk)) {
+      bg = gu;
+      bk = ukey;
+    }
+    first = false;
+  }
+  ls_wave_best(bg, bk);
+  if (lane == 0) {
+    s_g[wave] = bg;
+    s_k[wave] = bk;
+  }
+  __syncthreads();
+  if (TIDX == 0) {
+    for (int q = 1; q < 4; q++)
+      if (ls_better(s_g[q], s_k[q], bg, bk)) {
+        bg = s_g[q];
+        bk = s_k[q];
+      }
+    out->gain = bg;
+    out->key = bk;
+  }
+}
+
+// k_lsapply, one workgroup per point: the best of the 2n records, the move applied to x and r (every row takes its tested
+// value; a zero coefficient leaves it as it is), the move counted; a point without a candidate is done, and every later
+// launch of k_lsmove / k_lsapply returns at once for it.
+__global__ __launch_bounds__(256) void k_lsapply(LsArgs a) {
+  __shared__ double s_g[4];
+  __shared__ unsigned long long s_k[4];
+  const int p = (int)blockIdx.x;
+  if (a.done[p]) return;
+  const int n = a.n, m0 = a.m0;
+  const size_t ldn = (size_t)a.ldn;
+  const LsRec *rec = a.rec + (size_t)p * (size_t)(2 * n);
+  double bg = 0.0;
+  unsigned long long bk = ~0ull;
+  for (int u = TIDX; u < 2 * n; u += 256) {
+    const double g = rec[u].gain;
+    const unsigned long long k = rec[u].key;
+    if (ls_better(g, k, bg, bk)) {
+      bg = g;
+      bk = k;
+    }
+  }
+  ls_wave_best(bg, bk);
+  if ((TIDX & 63) == 0) {
+    s_g[TIDX >> 6] = bg;
+    s_k[TIDX >> 6] = bk;
+  }
+  __syncthreads();
+  bg = s_g[0];
+  bk = s_k[0];
+  for (int q = 1; q < 4; q++)
+    if (ls_better(s_g[q], s_k[q], bg, bk)) {
+      bg = s_g[q];
+      bk = s_k[q];
+    }
+  if (!(bg > 0.0)) {
+    if (TIDX == 0) a.done[p] = 1;
+    return;
+  }
+  const bool pair = (bk >> 62) != 0;
+  const int u = (int)((bk >> 31) & 0x7fffffffull), v = (int)(bk & 0x7fffffffull);
+  const int ju = (u >> 1) + 1, jv = pair ? (v >> 1) + 1 : 0;
+  const bool nu = (u & 1) != 0, nv = (v & 1) != 0;
+  double *x = a.x + (size_t)p * (size_t)(n + 1);
+  double *r = a.r + (size_t)p * (size_t)a.ldm;
+  for (int i = TIDX; i < m0; i += 256) {
+    const double au = a.Ar[(size_t)i * ldn + (size_t)ju];
+    double t = __dadd_rn(r[i], nu ? -au : au);
+    if (pair) {
+      const double av = a.Ar[(size_t)i * ldn + (size_t)jv];
+      t = __dadd_rn(t, nv ? -av : av);
+    }
+    r[i] = t;
+  }
+  if (TIDX == 0) {
+    x[ju] = x[ju] + (nu ? -1.0 : 1.0);
+    if (pair) x[jv] = x[jv] + (nv ? -1.0 : 1.0);
+    a.moves[p] = a.moves[p] + 1;
+  }
+}
+
+void launch_lsact(const LsArgs &a, int final, hipStream_t s) {
+  hipLaunchKernelGGL(k_lsact, dim3((unsigned)a.count), dim3(256), 0, s, a, final);
+}
+
+// one iteration: the evaluation and the move
+void launch_lsiter(const LsArgs &a, hipStream_t s) {
+  if (a.n > 0) hipLaunchKernelGGL(k_lsmove, dim3((unsigned)(2 * a.n), (unsigned)a.count), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_lsapply, dim3((unsigned)a.count), dim3(256), 0, s, a);
+}
+
 } // namespace mvx
