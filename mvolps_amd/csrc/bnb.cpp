@@ -784,6 +784,30 @@ static size_t sb_budget() {
   return mb << 20;
 }
 
+// `count` jobs in batches whose tableaux (`per_job` each) fit the strong-branching memory budget: advance(j0, j1) per batch,
+// until one fails; its code.  Results do not depend on the cut.
+template <typename F>
+static int in_batches(const mvx_lp_api *api, const void *h0, size_t count, size_t per_job, F advance) {
+  const size_t tab = (size_t)(api->get_num_rows(h0) + 1) * (size_t)(api->get_num_cols(h0) + 1) * 8;
+  const size_t per = std::max<size_t>(1, std::min(count, sb_budget() / (per_job * tab + 1)));
+  for (size_t j0 = 0; j0 < count; j0 += per) {
+    const int rc = advance(j0, std::min(count, j0 + per));
+    if (rc != 0) return rc;
+  }
+  return 0;
+}
+
+// hs solved together: simplex_batch where the table has it, else simplex per handle; the pivots of hs[k]
+static std::vector<int> solve_counted(const mvx_lp_api *api, const std::vector<void *> &hs, const mvx_smcp *parm) {
+  std::vector<int> pivots(hs.size());
+  for (size_t k = 0; k < hs.size(); k++) pivots[k] = api->get_it_cnt(hs[k]);
+  if (api->simplex_batch) api->simplex_batch(const_cast<void **>(hs.data()), (int)hs.size(), parm, nullptr);
+  else
+    for (void *h : hs) api->simplex(h, parm);
+  for (size_t k = 0; k < hs.size(); k++) pivots[k] = api->get_it_cnt(hs[k]) - pivots[k];
+  return pivots;
+}
+
 // var_strat 3 / 4 for a set of branching nodes: hs[t] solved (OPT), vars[t] its printInfo violated list (ascending).
 // 3: the argmax of max(pen_down, 1e-6) * max(pen_up, 1e-6), ties to the lowest column.  4: the sb_cands best candidates by
 // that score (same tie rule) are branched on clones with the drivers' own bounds, all their children solved by batched
@@ -812,21 +836,14 @@ static int choose_many(const mvx_lp_api *api, const std::vector<const void *> &h
   struct Job {
     size_t t, k;
     void *S2, *S3;
-    int before2, before3;
   };
   std::vector<Job> jobs;
   for (size_t t = 0; t < K; t++)
-    for (size_t r = 0; r < order[t].size() && (int)r < prm.sb_cands; r++) jobs.push_back(Job{t, order[t][r], nullptr, nullptr, 0, 0});
+    for (size_t r = 0; r < order[t].size() && (int)r < prm.sb_cands; r++) jobs.push_back(Job{t, order[t][r], nullptr, nullptr});
   std::vector<double> dd(jobs.size()), du(jobs.size());
   mvx_smcp parm = dflt;
   parm.it_lim = std::max(0, prm.sb_iters);
-  size_t per = jobs.size();
-  if (!jobs.empty()) {
-    const size_t tab = (size_t)(api->get_num_rows(hs[0]) + 1) * (size_t)(api->get_num_cols(hs[0]) + 1) * 8;
-    per = std::max<size_t>(1, std::min(jobs.size(), sb_budget() / (2 * tab + 1)));
-  }
-  for (size_t j0 = 0; j0 < jobs.size(); j0 += per) {
-    const size_t j1 = std::min(jobs.size(), j0 + per);
+  in_batches(api, hs[0], jobs.size(), 2, [&](size_t j0, size_t j1) {
     std::vector<void *> kids;
     for (size_t j = j0; j < j1; j++) {
       Job &jb = jobs[j];
@@ -837,14 +854,10 @@ static int choose_many(const mvx_lp_api *api, const std::vector<const void *> &h
       api->copy_prob(jb.S2, a, MVX_ON);
       api->copy_prob(jb.S3, a, MVX_ON);
       child_bounds(api, a, col, api->get_col_prim(a, col), quirks, jb.S2, jb.S3);
-      jb.before2 = api->get_it_cnt(jb.S2);
-      jb.before3 = api->get_it_cnt(jb.S3);
       kids.push_back(jb.S2);
       kids.push_back(jb.S3);
     }
-    if (api->simplex_batch) api->simplex_batch(kids.data(), (int)kids.size(), &parm, nullptr);
-    else
-      for (void *k : kids) api->simplex(k, &parm);
+    const std::vector<int> pivots = solve_counted(api, kids, &parm);
     for (size_t j = j0; j < j1; j++) {
       Job &jb = jobs[j];
       const void *a = hs[jb.t];
@@ -858,11 +871,12 @@ static int choose_many(const mvx_lp_api *api, const std::vector<const void *> &h
       du[j] = delta(jb.S3, pu[jb.t][jb.k]);
       Choice &ch = out[jb.t];
       ch.sb_lps += 2;
-      ch.sb_pivots += (api->get_it_cnt(jb.S2) - jb.before2) + (api->get_it_cnt(jb.S3) - jb.before3);
+      ch.sb_pivots += pivots[2 * (j - j0)] + pivots[2 * (j - j0) + 1];
       api->delete_prob(jb.S2);
       api->delete_prob(jb.S3);
     }
-  }
+    return 0;
+  });
   // best strong-branching score per node; ties to the lowest column
   std::vector<double> best(K, -1.0);
   for (size_t j = 0; j < jobs.size(); j++) {
@@ -877,16 +891,24 @@ static int choose_many(const mvx_lp_api *api, const std::vector<const void *> &h
   return 0;
 }
 
-// ---- primal rounding heuristic (heur 1 / 2, DESIGN.md "Primal rounding heuristic") ----
+// ---- the host model and the device-or-twin route (DESIGN.md "Host model, device flags and adoption") ----
 
-// The model the heuristic checks a candidate against, read once per tree from the root through the table: rows 1..m0 with
-// their non-zeros in ascending column order (and by column for the fill), row and column bounds (+-inf where absent),
-// the objective, and which columns are integer and locked down / up by some row; for the diving rules, how many rows lock a
-// column down / up and how many non-zeros it has.
-struct RoundHost {
+struct RcEntry {
+  int col;
+  double lb, ub;
+};
+using RcList = std::vector<RcEntry>;
+
+// The model the host twins work on, read from a handle through the table in one pass over its rows: rows 1..m0 with their
+// non-zeros in ascending column order (and by column, ascending row), row and column bounds (+-inf where absent), which
+// columns are integer and locked down / up by some row, and how many rows lock a column down / up.  `priced`: the table also
+// has the objective and the column values of a solved handle, and c and sg are filled; the rounding family needs that part,
+// propagation and the conflict graph do not.
+struct HostModel {
   int m0 = 0, n = 0;
+  bool priced = false;
   double sg = 1.0;
-  std::vector<std::vector<std::pair<int, double>>> rows, cols; // rows[i-1]: (j, a_ij) ascending j; cols[j]: (i-1, a_ij)
+  std::vector<std::vector<std::pair<int, double>>> rows, cols; // rows[i-1]: (j, a_ij) ascending j; cols[j]: (i-1, a_ij) ascending i
   std::vector<double> rlo, rhi, clo, chi, c;
   std::vector<char> isint, dlock, ulock;
   std::vector<int> dl, ul; // rows that lock column j down / up
@@ -898,21 +920,18 @@ static double tab_bound(double b) { // the table reports an absent bound as -+DB
 }
 static double round_tol(double b) { return 1e-9 * std::max(1.0, std::fabs(b)); } // a row bound's feasibility tolerance
 
-static int round_host_model(const mvx_lp_api *api, const void *root, RoundHost &M) {
-  if (!api->get_mat_row || !api->get_row_lb || !api->get_row_ub || !api->get_col_lb || !api->get_col_ub || !api->get_obj_coef ||
-      !api->get_col_kind || !api->get_status || !(api->get_col_prim_all || api->get_col_prim))
-    return -2;
+// 0, or -2 when the table lacks an accessor of the rows, the bounds or the column kinds
+static int read_host_model(const mvx_lp_api *api, const void *root, HostModel &M) {
+  if (!api->get_mat_row || !api->get_row_lb || !api->get_row_ub || !api->get_col_lb || !api->get_col_ub || !api->get_col_kind) return -2;
   const int m0 = api->get_num_rows(root), n = api->get_num_cols(root);
   M.m0 = m0;
   M.n = n;
-  M.sg = (api->get_obj_dir && api->get_obj_dir(root) == MVX_MIN) ? -1.0 : 1.0;
   M.rows.assign((size_t)m0, {});
   M.cols.assign((size_t)n + 1, {});
   M.rlo.resize((size_t)m0);
   M.rhi.resize((size_t)m0);
   M.clo.resize((size_t)n + 1);
   M.chi.resize((size_t)n + 1);
-  M.c.resize((size_t)n + 1);
   M.isint.assign((size_t)n + 1, 0);
   M.dlock.assign((size_t)n + 1, 0);
   M.ulock.assign((size_t)n + 1, 0);
@@ -941,18 +960,98 @@ static int round_host_model(const mvx_lp_api *api, const void *root, RoundHost &
       }
     }
   }
-  for (int j = 0; j <= n; j++) M.c[(size_t)j] = api->get_obj_coef(root, j);
   for (int j = 1; j <= n; j++) {
     M.clo[(size_t)j] = tab_bound(api->get_col_lb(root, j));
     M.chi[(size_t)j] = tab_bound(api->get_col_ub(root, j));
     M.isint[(size_t)j] = api->get_col_kind(root, j) != MVX_CV;
   }
+  M.priced = api->get_obj_coef && api->get_status && (api->get_col_prim_all || api->get_col_prim);
+  if (M.priced) {
+    M.sg = (api->get_obj_dir && api->get_obj_dir(root) == MVX_MIN) ? -1.0 : 1.0;
+    M.c.resize((size_t)n + 1);
+    for (int j = 0; j <= n; j++) M.c[(size_t)j] = api->get_obj_coef(root, j);
+  }
   return 0;
 }
 
+// The model of one handle, read on first use.  A tree owns one for its `model` handle and its rules borrow it.
+struct LazyModel {
+  const mvx_lp_api *api;
+  const void *root;
+  LazyModel(const mvx_lp_api *api_, const void *root_) : api(api_), root(root_) {}
+  // 0 and the model, or the reader's code
+  int get(const HostModel *&M) {
+    if (!_ready) {
+      const int rc = read_host_model(api, root, _M);
+      if (rc != 0) return rc;
+      _ready = true;
+    }
+    M = &_M;
+    return 0;
+  }
+
+private:
+  bool _ready = false;
+  HostModel _M;
+};
+
+// One rule's route to its results: the table's batched entry while it accepts the model, the host twin (same bits) without the
+// entry or, once the entry has answered -5 (the kernel's size limit), for the rest of the tree.  `device()` makes the call and
+// unpacks its arrays, `twin(M)` loops over the handles; 0, or the failing call's code.  The flag is the rule's own.
+class DeviceOrTwin {
+public:
+  template <typename D, typename T>
+  int run(bool has_entry, LazyModel &lm, D device, T twin) {
+    if (has_entry && _device) {
+      const int rc = device();
+      if (rc != -5) return rc;
+      _device = false;
+    }
+    const HostModel *M = nullptr;
+    const int rc = lm.get(M);
+    if (rc != 0) return rc;
+    return twin(*M);
+  }
+
+private:
+  bool _device = true;
+};
+
+// lists[k] one behind the other: list k is entries off[k] .. off[k+1]-1
+struct FlatLists {
+  std::vector<int> off, cols;
+  std::vector<double> lb, ub;
+  explicit FlatLists(const std::vector<const RcList *> &lists) : off(1, 0) {
+    for (const RcList *l : lists) {
+      for (const RcEntry &e : *l) {
+        cols.push_back(e.col);
+        lb.push_back(e.lb);
+        ub.push_back(e.ub);
+      }
+      off.push_back((int)cols.size());
+    }
+  }
+};
+static void list_out(const RcList &l, int *cnt, int *cols, double *lb, double *ub) {
+  *cnt = (int)l.size();
+  for (size_t k = 0; k < l.size(); k++) {
+    cols[k] = l[k].col;
+    lb[k] = l[k].lb;
+    ub[k] = l[k].ub;
+  }
+}
+static RcList list_in(int cnt, const int *cols, const double *lb, const double *ub) {
+  RcList l;
+  for (int k = 0; k < cnt; k++) l.push_back(RcEntry{cols[k], lb[k], ub[k]});
+  return l;
+}
+
+// ---- primal rounding heuristic (heur 1 / 2, DESIGN.md "Primal rounding heuristic") ----
+
 // The heuristic on one solved node (the host twin of k_round, same operations in the same order): x[0..n] gets the
 // candidate, *obj its objective, *found whether it is feasible.
-static int round_host(const mvx_lp_api *api, const RoundHost &M, const void *P, int mode, double *obj, int *found, double *x) {
+static int round_host(const mvx_lp_api *api, const HostModel &M, const void *P, int mode, double *obj, int *found, double *x) {
+  if (!M.priced) return -2;
   const int n = M.n, m0 = M.m0;
   if (mode < 1 || mode > 2 || !obj || !found || !x || api->get_num_cols(P) != n) return -1;
   if (api->get_status(P) != MVX_OPT) return -3;
@@ -1034,7 +1133,7 @@ static int round_host(const mvx_lp_api *api, const RoundHost &M, const void *P, 
 }
 
 // One tree's heuristic: round_many (one call for a batch of nodes) when the table has it and the model fits the kernel,
-// else the host twin with the model read once.  Results depend on each node's own LP only.
+// else the host twin on the tree's model.  Results depend on each node's own LP only.
 struct HeurOut {
   double obj = 0.0;
   int found = 0;
@@ -1043,72 +1142,40 @@ struct HeurOut {
 
 class Heuristic {
 public:
-  Heuristic(const mvx_lp_api *api, const void *root, int mode) : _api(api), _root(root), _mode(mode) {}
+  Heuristic(LazyModel &lm, int mode) : _lm(lm), _mode(mode) {}
   // hs: solved (OPT) nodes; 0, or the failing call's code
   int run(const std::vector<const void *> &hs, std::vector<HeurOut> &out) {
-    const size_t K = hs.size();
+    const mvx_lp_api *api = _lm.api;
+    const size_t K = hs.size(), row = (size_t)api->get_num_cols(_lm.root) + 1;
     out.assign(K, HeurOut());
     if (K == 0) return 0;
-    const int n = _api->get_num_cols(_root);
-    if (_api->round_many && _device) {
-      std::vector<double> obj(K), x(K * (size_t)(n + 1));
-      std::vector<int> found(K);
-      const int rc = _api->round_many(_root, hs.data(), (int)K, _mode, obj.data(), found.data(), x.data());
-      if (rc == 0) {
-        for (size_t t = 0; t < K; t++) {
-          out[t].obj = obj[t];
-          out[t].found = found[t];
-          out[t].x.assign(x.begin() + (long)(t * (size_t)(n + 1)), x.begin() + (long)((t + 1) * (size_t)(n + 1)));
-        }
-        return 0;
-      }
-      if (rc != -5) return rc;
-      _device = false; // more columns than the kernel holds (mvx_round_many): the host twin, same bits, for the rest of the tree
-    }
-    if (!_ready) {
-      const int rc = round_host_model(_api, _root, _M);
-      if (rc != 0) return rc;
-      _ready = true;
-    }
-    for (size_t t = 0; t < K; t++) {
-      out[t].x.assign((size_t)n + 1, 0.0);
-      const int rc = round_host(_api, _M, hs[t], _mode, &out[t].obj, &out[t].found, out[t].x.data());
-      if (rc != 0) return rc;
-    }
-    return 0;
+    return _route.run(
+        api->round_many != nullptr, _lm,
+        [&]() {
+          std::vector<double> obj(K), x(K * row);
+          std::vector<int> found(K);
+          const int rc = api->round_many(_lm.root, hs.data(), (int)K, _mode, obj.data(), found.data(), x.data());
+          for (size_t t = 0; t < K && rc == 0; t++) {
+            out[t].obj = obj[t];
+            out[t].found = found[t];
+            out[t].x.assign(x.begin() + (long)(t * row), x.begin() + (long)((t + 1) * row));
+          }
+          return rc;
+        },
+        [&](const HostModel &M) {
+          for (size_t t = 0; t < K; t++) {
+            out[t].x.assign(row, 0.0);
+            const int rc = round_host(api, M, hs[t], _mode, &out[t].obj, &out[t].found, out[t].x.data());
+            if (rc != 0) return rc;
+          }
+          return 0;
+        });
   }
 
 private:
-  const mvx_lp_api *_api;
-  const void *_root;
+  LazyModel &_lm;
   int _mode;
-  bool _device = true; // round_many is used while it accepts the model
-  bool _ready = false;
-  RoundHost _M;
-};
-
-// The heuristic's counts and its part in the incumbent, booked the way the serial loop meets the nodes.
-struct HeurBook {
-  long long calls = 0, found = 0, improved = 0;
-  int incumbent = 0; // 1: the incumbent in hand came from the heuristic
-  void book(const HeurOut &h, int oid, double sg, double &bestLower, int &has_incumbent, int &incumbent_oid, std::vector<double> &xbest) {
-    calls++;
-    if (!h.found) return;
-    found++;
-    if (!(sg * h.obj > sg * bestLower)) return;
-    improved++;
-    bestLower = h.obj;
-    has_incumbent = 1;
-    incumbent_oid = oid;
-    incumbent = 1;
-    for (size_t j = 1; j < xbest.size() && j < h.x.size(); j++) xbest[j] = h.x[j];
-  }
-  void store(mvx_bnb_result *res) const {
-    res->heur_calls = calls;
-    res->heur_found = found;
-    res->heur_improved = improved;
-    res->incumbent_heur = incumbent;
-  }
+  DeviceOrTwin _route;
 };
 
 // ---- incumbent polishing (polish, DESIGN.md "Incumbent polishing (polish)") ----
@@ -1117,7 +1184,8 @@ struct HeurBook {
 // the same order).  The candidates of an iteration are walked singles first, then pairs by index(u), index(v), and one is taken
 // only when its gain is strictly above the best so far: that is the tie rule.  A candidate that cannot win is not tested, which
 // changes no result.  x[1..n] is edited in place when *ok comes back 1.
-static void polish_host(const RoundHost &M, double *x, int max_moves, double *obj, int *moves, int *ok) {
+static int polish_host(const HostModel &M, double *x, int max_moves, double *obj, int *moves, int *ok) {
+  if (!M.priced) return -2;
   const int n = M.n, m0 = M.m0;
   *obj = 0.0;
   *moves = 0;
@@ -1127,7 +1195,7 @@ static void polish_host(const RoundHost &M, double *x, int max_moves, double *ob
     double v = x[j];
     if (M.isint[(size_t)j]) {
       const double ri = std::rint(v);
-      if (!(std::fabs(v - ri) <= 1e-9)) return; // refused
+      if (!(std::fabs(v - ri) <= 1e-9)) return 0; // refused
       v = ri;
     }
     xt[(size_t)j] = v;
@@ -1157,7 +1225,7 @@ static void polish_host(const RoundHost &M, double *x, int max_moves, double *ob
     for (int j = 1; j <= n; j++) sum = sum + M.c[(size_t)j] * xt[(size_t)j];
     return sum + M.c[0];
   };
-  if (!feasible(r)) return; // refused
+  if (!feasible(r)) return 0; // refused
   const std::vector<double> x0 = xt;
   const double obj0 = objective();
   const int U = 2 * n;
@@ -1246,45 +1314,27 @@ static void polish_host(const RoundHost &M, double *x, int max_moves, double *ob
     *obj = obj0;
   }
   for (int j = 1; j <= n; j++) x[j] = xt[(size_t)j];
+  return 0;
 }
 
-// One tree's polishing: polish_many when the table has it, the twin with the model read once without it or on -5.
+// One tree's polishing: polish_many when the table has it, the twin on the tree's model without it or on -5.
 class Polish {
 public:
-  Polish(const mvx_lp_api *api, const void *root, int cap) : _api(api), _root(root), _cap(cap) {}
+  Polish(LazyModel &lm, int cap) : _lm(lm), _cap(cap) {}
   // x[0..n] edited in place when *ok; 0, or the failing call's code
   int run(std::vector<double> &x, double *obj, int *moves, int *ok) {
-    if (_api->polish_many && _device) {
-      const int rc = _api->polish_many(_root, 1, x.data(), _cap, obj, moves, ok);
-      if (rc == 0) return 0;
-      if (rc != -5) return rc;
-      _device = false; // the kernel's size limit: the host twin, same bits, for the rest of the tree
-    }
-    if (!_ready) {
-      const int rc = round_host_model(_api, _root, _M);
-      if (rc != 0) return rc;
-      _ready = true;
-    }
-    polish_host(_M, x.data(), _cap, obj, moves, ok);
-    return 0;
+    return _route.run(
+        _lm.api->polish_many != nullptr, _lm, [&]() { return _lm.api->polish_many(_lm.root, 1, x.data(), _cap, obj, moves, ok); },
+        [&](const HostModel &M) { return polish_host(M, x.data(), _cap, obj, moves, ok); });
   }
 
 private:
-  const mvx_lp_api *_api;
-  const void *_root;
+  LazyModel &_lm;
   int _cap;
-  bool _device = true;
-  bool _ready = false;
-  RoundHost _M;
+  DeviceOrTwin _route;
 };
 
 // ---- reduced-cost bound tightening (rc_fix, DESIGN.md "Reduced-cost tightening") ----
-
-struct RcEntry {
-  int col;
-  double lb, ub;
-};
-using RcList = std::vector<RcEntry>;
 
 // The rule on one solved node from its exported tableau and basis (the host twin of k_rcfix: same tests, the same correctly
 // rounded division): the changed columns in ascending order.
@@ -1341,8 +1391,7 @@ public:
       std::vector<int> cnt(K), cols(K * n);
       const int rc = _api->rc_tighten_many(hs.data(), (int)K, cut.data(), 1e-9, cnt.data(), cols.data(), lb.data(), ub.data());
       if (rc != 0) return rc;
-      for (size_t t = 0; t < K; t++)
-        for (int k = 0; k < cnt[t]; k++) out[t].push_back(RcEntry{cols[t * n + (size_t)k], lb[t * n + (size_t)k], ub[t * n + (size_t)k]});
+      for (size_t t = 0; t < K; t++) out[t] = list_in(cnt[t], cols.data() + t * n, lb.data() + t * n, ub.data() + t * n);
       return 0;
     }
     for (size_t t = 0; t < K; t++) {
@@ -1359,18 +1408,9 @@ public:
   // kids[k] takes *lists[k]
   int apply(const std::vector<void *> &kids, const std::vector<const RcList *> &lists) const {
     if (_api->tighten_cols_many) {
-      std::vector<int> off(1, 0), cols;
-      std::vector<double> lb, ub;
-      for (const RcList *l : lists) {
-        for (const RcEntry &e : *l) {
-          cols.push_back(e.col);
-          lb.push_back(e.lb);
-          ub.push_back(e.ub);
-        }
-        off.push_back((int)cols.size());
-      }
-      if (cols.empty()) return 0;
-      return _api->tighten_cols_many(kids.data(), (int)kids.size(), off.data(), cols.data(), lb.data(), ub.data());
+      const FlatLists f(lists);
+      if (f.cols.empty()) return 0;
+      return _api->tighten_cols_many(kids.data(), (int)kids.size(), f.off.data(), f.cols.data(), f.lb.data(), f.ub.data());
     }
     for (size_t k = 0; k < kids.size(); k++)
       for (const RcEntry &e : *lists[k]) _api->set_col_bnds(kids[k], e.col, e.lb == e.ub ? MVX_FX : MVX_DB, e.lb, e.ub);
@@ -1388,41 +1428,6 @@ private:
 
 // ---- node bound propagation (prop, DESIGN.md "Node bound propagation") ----
 
-// The rows the propagation reads, taken once per tree from the root through the table: rows 1..m0 with their non-zeros in
-// ascending column order and by column, their bounds (+-inf where absent) and which columns are integer.
-struct PropHost {
-  int m0 = 0, n = 0;
-  std::vector<std::vector<std::pair<int, double>>> rows, cols; // rows[i-1]: (j, a_ij) ascending j; cols[j]: (i-1, a_ij) ascending i
-  std::vector<double> rlo, rhi;
-  std::vector<char> isint;
-};
-
-static int prop_host_model(const mvx_lp_api *api, const void *root, PropHost &M) {
-  if (!api->get_mat_row || !api->get_row_lb || !api->get_row_ub || !api->get_col_lb || !api->get_col_ub || !api->get_col_kind) return -2;
-  const int m0 = api->get_num_rows(root), n = api->get_num_cols(root);
-  M.m0 = m0;
-  M.n = n;
-  M.rows.assign((size_t)m0, {});
-  M.cols.assign((size_t)n + 1, {});
-  M.rlo.resize((size_t)m0);
-  M.rhi.resize((size_t)m0);
-  M.isint.assign((size_t)n + 1, 0);
-  std::vector<int> ind((size_t)n + 1);
-  std::vector<double> val((size_t)n + 1);
-  for (int i = 1; i <= m0; i++) {
-    const int len = api->get_mat_row(root, i, ind.data(), val.data());
-    auto &row = M.rows[(size_t)i - 1];
-    for (int k = 1; k <= len; k++)
-      if (val[(size_t)k] != 0.0) row.emplace_back(ind[(size_t)k], val[(size_t)k]);
-    std::sort(row.begin(), row.end());
-    M.rlo[(size_t)i - 1] = tab_bound(api->get_row_lb(root, i));
-    M.rhi[(size_t)i - 1] = tab_bound(api->get_row_ub(root, i));
-    for (const auto &e : row) M.cols[(size_t)e.first].emplace_back(i - 1, e.second);
-  }
-  for (int j = 1; j <= n; j++) M.isint[(size_t)j] = api->get_col_kind(root, j) != MVX_CV;
-  return 0;
-}
-
 struct PropOut {
   int infeasible = 0, rounds = 0;
   RcList list; // the columns whose bounds changed, ascending; +-inf for an absent bound; empty when infeasible
@@ -1430,7 +1435,7 @@ struct PropOut {
 
 // The propagation of one handle from its own column bounds (the host twin of k_prop: same tests, every product, sum and
 // quotient rounded on its own, in the same order).
-static int prop_host(const mvx_lp_api *api, const PropHost &M, const void *P, int max_rounds, PropOut &out) {
+static int prop_host(const mvx_lp_api *api, const HostModel &M, const void *P, int max_rounds, PropOut &out) {
   const int n = M.n, m0 = M.m0;
   out = PropOut();
   if (!P || max_rounds < 1 || api->get_num_cols(P) != n) return -1;
@@ -1523,18 +1528,9 @@ static int prop_host(const mvx_lp_api *api, const PropHost &M, const void *P, in
 // entry with the type the finite bounds give, FX where they meet.
 static int apply_bound_lists(const mvx_lp_api *api, const std::vector<void *> &hs, const std::vector<const RcList *> &lists) {
   if (api->set_col_bnds_many) {
-    std::vector<int> off(1, 0), cols;
-    std::vector<double> lb, ub;
-    for (const RcList *l : lists) {
-      for (const RcEntry &e : *l) {
-        cols.push_back(e.col);
-        lb.push_back(e.lb);
-        ub.push_back(e.ub);
-      }
-      off.push_back((int)cols.size());
-    }
-    if (cols.empty()) return 0;
-    return api->set_col_bnds_many(hs.data(), (int)hs.size(), off.data(), cols.data(), lb.data(), ub.data());
+    const FlatLists f(lists);
+    if (f.cols.empty()) return 0;
+    return api->set_col_bnds_many(hs.data(), (int)hs.size(), f.off.data(), f.cols.data(), f.lb.data(), f.ub.data());
   }
   for (size_t k = 0; k < hs.size(); k++)
     for (const RcEntry &e : *lists[k]) {
@@ -1545,42 +1541,39 @@ static int apply_bound_lists(const mvx_lp_api *api, const std::vector<void *> &h
 }
 
 // One tree's propagation: a batch of handles through propagate_many (one call) when the table has it and the model fits the
-// kernel, else the host twin with the rows read once; the lists go on through set_col_bnds_many (one call), else
+// kernel, else the host twin on the tree's model; the lists go on through set_col_bnds_many (one call), else
 // set_col_bnds per entry.  A result depends on the handle's own bounds and the root's rows only.
 class Prop {
 public:
-  Prop(const mvx_lp_api *api, const void *root, int max_rounds) : _api(api), _root(root), _rounds(max_rounds) {}
+  Prop(LazyModel &lm, int max_rounds) : _api(lm.api), _lm(lm), _rounds(max_rounds) {}
   long long calls = 0, fixed = 0, tightened = 0, infeasible = 0;
   // 0, or the failing call's code (-2: neither propagate_many nor the twin's accessors)
   int compute(const std::vector<void *> &hs, std::vector<PropOut> &out) {
     const size_t K = hs.size();
     out.assign(K, PropOut());
     if (K == 0) return 0;
-    if (_api->propagate_many && _device) {
-      const size_t n = (size_t)_api->get_num_cols(_root);
-      std::vector<int> inf(K), rounds(K), cnt(K), cols(K * n + 1);
-      std::vector<double> lb(K * n + 1), ub(K * n + 1);
-      const int rc = _api->propagate_many(_root, hs.data(), (int)K, _rounds, inf.data(), rounds.data(), cnt.data(), cols.data(), lb.data(), ub.data());
-      if (rc == 0) {
-        for (size_t t = 0; t < K; t++) {
-          out[t].infeasible = inf[t];
-          out[t].rounds = rounds[t];
-          for (int k = 0; k < cnt[t]; k++) out[t].list.push_back(RcEntry{cols[t * n + (size_t)k], lb[t * n + (size_t)k], ub[t * n + (size_t)k]});
-        }
-        return 0;
-      }
-      if (rc != -5) return rc;
-      _device = false; // more columns than the kernel holds: the host twin, same bits, for the rest of the tree
-    }
-    if (!_ready) {
-      if (prop_host_model(_api, _root, _M) != 0) return -2;
-      _ready = true;
-    }
-    for (size_t t = 0; t < K; t++) {
-      const int rc = prop_host(_api, _M, hs[t], _rounds, out[t]);
-      if (rc != 0) return rc;
-    }
-    return 0;
+    return _route.run(
+        _api->propagate_many != nullptr, _lm,
+        [&]() {
+          const size_t n = (size_t)_api->get_num_cols(_lm.root);
+          std::vector<int> inf(K), rounds(K), cnt(K), cols(K * n + 1);
+          std::vector<double> lb(K * n + 1), ub(K * n + 1);
+          const int rc =
+              _api->propagate_many(_lm.root, hs.data(), (int)K, _rounds, inf.data(), rounds.data(), cnt.data(), cols.data(), lb.data(), ub.data());
+          for (size_t t = 0; t < K && rc == 0; t++) {
+            out[t].infeasible = inf[t];
+            out[t].rounds = rounds[t];
+            out[t].list = list_in(cnt[t], cols.data() + t * n, lb.data() + t * n, ub.data() + t * n);
+          }
+          return rc;
+        },
+        [&](const HostModel &M) {
+          for (size_t t = 0; t < K; t++) {
+            const int rc = prop_host(_api, M, hs[t], _rounds, out[t]);
+            if (rc != 0) return rc;
+          }
+          return 0;
+        });
   }
   // the handles take their lists (a handle proved infeasible has none and keeps its bounds) and are booked
   int apply(const std::vector<void *> &hs, const std::vector<PropOut> &res) {
@@ -1609,12 +1602,30 @@ public:
 
 private:
   const mvx_lp_api *_api;
-  const void *_root;
+  LazyModel &_lm;
   int _rounds;
-  bool _device = true; // propagate_many is used while it accepts the model
-  bool _ready = false;
-  PropHost _M;
+  DeviceOrTwin _route;
 };
+
+// ---- what the lockstep runners (dives, pumps) share ----
+
+// the jobs of [j0, j1) that ended integral: one rounding call (mode 1) checks their LPs (job.cur) against the root's model and
+// prices them with the root's objective; the results land in job.res
+template <typename Job, typename Pred>
+static int round_integral(Heuristic &round, std::vector<Job> &jobs, size_t j0, size_t j1, Pred integral) {
+  std::vector<const void *> rh;
+  std::vector<size_t> rj;
+  for (size_t j = j0; j < j1; j++)
+    if (integral(jobs[j])) {
+      rh.push_back(jobs[j].cur);
+      rj.push_back(j);
+    }
+  std::vector<HeurOut> got;
+  const int rc = round.run(rh, got);
+  if (rc != 0) return rc;
+  for (size_t k = 0; k < rj.size(); k++) jobs[rj[k]].res = std::move(got[k]);
+  return 0;
+}
 
 // ---- LP diving heuristic (dive, DESIGN.md "LP diving heuristic") ----
 
@@ -1626,7 +1637,8 @@ struct DivePick {
 
 // The pick on one solved node (the host twin of k_divepick: same tests, every product rounded, the quotient correctly
 // rounded): the smallest key in lexicographic order with the column last, so the lowest column wins a tie.
-static int dive_pick_host(const mvx_lp_api *api, const RoundHost &M, const void *P, int rule, DivePick &out) {
+static int dive_pick_host(const mvx_lp_api *api, const HostModel &M, const void *P, int rule, DivePick &out) {
+  if (!M.priced) return -2;
   const int n = M.n;
   out = DivePick();
   if (!P || (rule != 1 && rule != 2 && rule != 4) || api->get_num_cols(P) != n) return -1;
@@ -1682,10 +1694,9 @@ struct DiveOut {
 // call (mode 1) for the dives that ended integral.  No cutoff is used inside a dive: a result depends on its node's LP only.
 class Dive {
 public:
-  Dive(const mvx_lp_api *api, const void *root, const mvx_bnb_params &prm)
-      : _api(api), _root(root), _rules(prm.dive), _freq(prm.dive_freq), _depth(prm.dive_depth), _round(api, root, 1) {}
-  Dive(const mvx_lp_api *api, const void *root, int rules, int depth)
-      : _api(api), _root(root), _rules(rules), _freq(0), _depth(depth), _round(api, root, 1) {}
+  Dive(LazyModel &lm, const mvx_bnb_params &prm) : Dive(lm, prm.dive, prm.dive_depth, prm.dive_freq) {}
+  Dive(LazyModel &lm, int rules, int depth, int freq = 0)
+      : _api(lm.api), _root(lm.root), _lm(lm), _rules(rules), _freq(freq), _depth(depth), _round(lm, 1) {}
   bool on() const { return _rules > 0; }
   // the root, and with dive_freq = F > 0 every node whose oid F divides
   bool selects(const MVOLP::NodeData &node) const { return _rules > 0 && (node.inital || (_freq > 0 && node.oid % _freq == 0)); }
@@ -1695,32 +1706,27 @@ public:
     const size_t K = hs.size();
     out.assign(K, DivePick());
     if (K == 0) return 0;
-    if (_api->dive_pick_many && _device) {
-      std::vector<int> nfrac(K), col(K), dir(K);
-      std::vector<double> val(K);
-      const int rc = _api->dive_pick_many(_root, hs.data(), (int)K, rules.data(), nfrac.data(), col.data(), dir.data(), val.data());
-      if (rc == 0) {
-        for (size_t k = 0; k < K; k++) {
-          out[k].nfrac = nfrac[k];
-          out[k].col = col[k];
-          out[k].dir = dir[k];
-          out[k].val = val[k];
-        }
-        return 0;
-      }
-      if (rc != -5) return rc;
-      _device = false; // more columns than the kernel holds: the host twin, same bits, for the rest of the tree
-    }
-    if (!_ready) {
-      const int rc = round_host_model(_api, _root, _M);
-      if (rc != 0) return rc;
-      _ready = true;
-    }
-    for (size_t k = 0; k < K; k++) {
-      const int rc = dive_pick_host(_api, _M, hs[k], rules[k], out[k]);
-      if (rc != 0) return rc;
-    }
-    return 0;
+    return _route.run(
+        _api->dive_pick_many != nullptr, _lm,
+        [&]() {
+          std::vector<int> nfrac(K), col(K), dir(K);
+          std::vector<double> val(K);
+          const int rc = _api->dive_pick_many(_root, hs.data(), (int)K, rules.data(), nfrac.data(), col.data(), dir.data(), val.data());
+          for (size_t k = 0; k < K && rc == 0; k++) {
+            out[k].nfrac = nfrac[k];
+            out[k].col = col[k];
+            out[k].dir = dir[k];
+            out[k].val = val[k];
+          }
+          return rc;
+        },
+        [&](const HostModel &M) {
+          for (size_t k = 0; k < K; k++) {
+            const int rc = dive_pick_host(_api, M, hs[k], rules[k], out[k]);
+            if (rc != 0) return rc;
+          }
+          return 0;
+        });
   }
 
   // hs: solved (OPT) nodes; 0, or the failing call's code.  The dives are cut into batches that fit the strong-branching
@@ -1738,10 +1744,7 @@ public:
           jb.cur = hs[t];
           jobs.push_back(jb);
         }
-    const size_t tab = (size_t)(_api->get_num_rows(hs[0]) + 1) * (size_t)(_api->get_num_cols(hs[0]) + 1) * 8;
-    const size_t per = std::max<size_t>(1, std::min(jobs.size(), sb_budget() / (2 * tab + 1)));
-    int rc = 0;
-    for (size_t j0 = 0; j0 < jobs.size() && rc == 0; j0 += per) rc = advance(jobs, j0, std::min(jobs.size(), j0 + per));
+    const int rc = in_batches(_api, hs[0], jobs.size(), 2, [&](size_t j0, size_t j1) { return advance(jobs, j0, j1); });
     for (Job &jb : jobs) drop_cur(jb); // a failing call leaves clones behind
     if (rc != 0) return rc;
     // the node's result: its rules in ascending order, a strictly better point wins
@@ -1845,13 +1848,8 @@ private:
       for (const RcList &l : lists) lp.push_back(&l);
       int brc = apply_bound_lists(_api, kids, lp);
       // 3. one batched solve of the round's children, with the default parameters like a B&B child
-      std::vector<int> before(kids.size());
-      if (brc == 0) {
-        for (size_t k = 0; k < kids.size(); k++) before[k] = _api->get_it_cnt(kids[k]);
-        if (_api->simplex_batch) _api->simplex_batch(kids.data(), (int)kids.size(), nullptr, nullptr);
-        else
-          for (void *k : kids) _api->simplex(k, nullptr);
-      }
+      std::vector<int> pivots;
+      if (brc == 0) pivots = solve_counted(_api, kids, nullptr);
       for (size_t k = 0; k < kids.size(); k++) {
         Job &jb = jobs[kj[k]];
         if (brc != 0) {
@@ -1859,7 +1857,7 @@ private:
           continue;
         }
         jb.lps++;
-        jb.pivots += _api->get_it_cnt(kids[k]) - before[k];
+        jb.pivots += pivots[k];
         if (_api->get_status(kids[k]) == MVX_OPT) { // the child replaces cur
           drop_cur(jb);
           jb.cur = kids[k];
@@ -1879,28 +1877,18 @@ private:
       if (brc != 0) return brc;
     }
     // 4. the dives that ended integral: rounded and checked against the root's model
-    std::vector<const void *> rh;
-    std::vector<size_t> rj;
-    for (size_t j = j0; j < j1; j++)
-      if (jobs[j].state == INTEGRAL) {
-        rh.push_back(jobs[j].cur);
-        rj.push_back(j);
-      }
-    std::vector<HeurOut> got;
-    const int rc = _round.run(rh, got);
+    const int rc = round_integral(_round, jobs, j0, j1, [](const Job &jb) { return jb.state == INTEGRAL; });
     if (rc != 0) return rc;
-    for (size_t k = 0; k < rj.size(); k++) jobs[rj[k]].res = std::move(got[k]);
     for (size_t j = j0; j < j1; j++) drop_cur(jobs[j]);
     return 0;
   }
 
   const mvx_lp_api *_api;
   const void *_root;
+  LazyModel &_lm;
   int _rules, _freq, _depth;
   Heuristic _round;
-  bool _device = true; // dive_pick_many is used while it accepts the model
-  bool _ready = false;
-  RoundHost _M;
+  DeviceOrTwin _route;
 };
 
 // ---- feasibility pump (DESIGN.md "Feasibility pump") ----
@@ -1914,8 +1902,9 @@ struct PumpStep {
 // The step on one solved node (the host twin of k_pumpobj: same tests, every operation rounded on its own): the rounding of the
 // integer columns, the move of a repeated rounding, the distance slopes and the new objective in the node's own direction,
 // c_j = a * (-sg * d_j) + (q * sqrt(nnz(d))) * c0_j.  The bounds are the node's own, the integer flags and c0 the root's.
-static int pump_obj_host(const mvx_lp_api *api, const RoundHost &M, const void *P, const double *xprev, int has_prev, double a, double q,
+static int pump_obj_host(const mvx_lp_api *api, const HostModel &M, const void *P, const double *xprev, int has_prev, double a, double q,
                          PumpStep &out) {
+  if (!M.priced) return -2;
   const int n = M.n;
   if (!P || api->get_num_cols(P) != n || (has_prev && !xprev)) return -1;
   if (api->get_status(P) != MVX_OPT) return -3;
@@ -2005,10 +1994,9 @@ struct PumpOut {
 // depends on its node's LP only.
 class Pump {
 public:
-  Pump(const mvx_lp_api *api, const void *root, const mvx_bnb_params &prm)
-      : _api(api), _root(root), _iters(prm.pump), _freq(prm.pump_freq), _alpha(prm.pump_alpha), _round(api, root, 1) {}
-  Pump(const mvx_lp_api *api, const void *root, int iters, double alpha)
-      : _api(api), _root(root), _iters(iters), _freq(0), _alpha(alpha), _round(api, root, 1) {}
+  Pump(LazyModel &lm, const mvx_bnb_params &prm) : Pump(lm, prm.pump, prm.pump_alpha, prm.pump_freq) {}
+  Pump(LazyModel &lm, int iters, double alpha, int freq = 0)
+      : _api(lm.api), _root(lm.root), _lm(lm), _iters(iters), _freq(freq), _alpha(alpha), _round(lm, 1) {}
   bool on() const { return _iters > 0; }
   // the root, and with pump_freq = F > 0 every node whose oid F divides
   bool selects(const MVOLP::NodeData &node) const { return _iters > 0 && (node.inital || (_freq > 0 && node.oid % _freq == 0)); }
@@ -2021,35 +2009,33 @@ public:
     if (K == 0) return 0;
     const int n = _api->get_num_cols(_root);
     const size_t row = (size_t)n + 1;
-    if (_api->pump_obj_many && _device) {
-      std::vector<double> xp(K * row, 0.0), xt(K * row), c(K * row);
-      std::vector<int> hp(K), info(K * 4);
-      for (size_t k = 0; k < K; k++) {
-        hp[k] = xprev[k] ? 1 : 0;
-        if (xprev[k]) std::memcpy(xp.data() + k * row, xprev[k], row * 8);
-      }
-      const int rc = _api->pump_obj_many(_root, hs.data(), (int)K, xp.data(), hp.data(), ab.data(), info.data(), xt.data(), c.data());
-      if (rc == 0) {
-        for (size_t k = 0; k < K; k++) {
-          out[k].nfrac = info[4 * k];
-          out[k].moved = info[4 * k + 1];
-          out[k].stalled = info[4 * k + 2];
-          out[k].nnz = info[4 * k + 3];
-          out[k].xt.assign(xt.begin() + k * row, xt.begin() + (k + 1) * row);
-          out[k].c.assign(c.begin() + k * row, c.begin() + (k + 1) * row);
-        }
-        return 0;
-      }
-      if (rc != -5) return rc;
-      _device = false; // more columns than the kernel holds: the host twin, same bits, for the rest of the tree
-    }
-    int rc = model();
-    if (rc != 0) return rc;
-    for (size_t k = 0; k < K; k++) {
-      rc = pump_obj_host(_api, _M, hs[k], xprev[k], xprev[k] ? 1 : 0, ab[2 * k], ab[2 * k + 1], out[k]);
-      if (rc != 0) return rc;
-    }
-    return 0;
+    return _route.run(
+        _api->pump_obj_many != nullptr, _lm,
+        [&]() {
+          std::vector<double> xp(K * row, 0.0), xt(K * row), c(K * row);
+          std::vector<int> hp(K), info(K * 4);
+          for (size_t k = 0; k < K; k++) {
+            hp[k] = xprev[k] ? 1 : 0;
+            if (xprev[k]) std::memcpy(xp.data() + k * row, xprev[k], row * 8);
+          }
+          const int rc = _api->pump_obj_many(_root, hs.data(), (int)K, xp.data(), hp.data(), ab.data(), info.data(), xt.data(), c.data());
+          for (size_t k = 0; k < K && rc == 0; k++) {
+            out[k].nfrac = info[4 * k];
+            out[k].moved = info[4 * k + 1];
+            out[k].stalled = info[4 * k + 2];
+            out[k].nnz = info[4 * k + 3];
+            out[k].xt.assign(xt.begin() + k * row, xt.begin() + (k + 1) * row);
+            out[k].c.assign(c.begin() + k * row, c.begin() + (k + 1) * row);
+          }
+          return rc;
+        },
+        [&](const HostModel &M) {
+          for (size_t k = 0; k < K; k++) {
+            const int rc = pump_obj_host(_api, M, hs[k], xprev[k], xprev[k] ? 1 : 0, ab[2 * k], ab[2 * k + 1], out[k]);
+            if (rc != 0) return rc;
+          }
+          return 0;
+        });
   }
 
   // hs: solved (OPT) nodes, left untouched; 0, or the failing call's code.  The pumps are cut into batches that fit the
@@ -2070,10 +2056,7 @@ public:
       _norm_ready = true;
     }
     std::vector<Job> jobs(hs.size());
-    const size_t tab = (size_t)(_api->get_num_rows(hs[0]) + 1) * (size_t)(_api->get_num_cols(hs[0]) + 1) * 8;
-    const size_t per = std::max<size_t>(1, std::min(jobs.size(), sb_budget() / (tab + 1)));
-    int rc = 0;
-    for (size_t j0 = 0; j0 < jobs.size() && rc == 0; j0 += per) rc = advance(hs, jobs, j0, std::min(jobs.size(), j0 + per));
+    const int rc = in_batches(_api, hs[0], jobs.size(), 1, [&](size_t j0, size_t j1) { return advance(hs, jobs, j0, j1); });
     for (Job &jb : jobs) drop(jb); // a failing call leaves clones behind
     if (rc != 0) return rc;
     for (size_t t = 0; t < jobs.size(); t++) {
@@ -2101,12 +2084,6 @@ private:
   void drop(Job &jb) {
     if (jb.cur) _api->delete_prob(jb.cur);
     jb.cur = nullptr;
-  }
-  int model() {
-    if (_ready) return 0;
-    const int rc = round_host_model(_api, _root, _M);
-    if (rc == 0) _ready = true;
-    return rc;
   }
   // the objectives cs[k] applied to hs[k]
   int apply(const std::vector<void *> &hs, const std::vector<const std::vector<double> *> &cs) {
@@ -2169,69 +2146,37 @@ private:
       // 3. one objective apply and one batched solve with the default parameters: the basis is primal feasible
       rc = apply(gh, gc);
       if (rc != 0) return rc;
-      std::vector<int> before(gh.size());
-      for (size_t k = 0; k < gh.size(); k++) before[k] = _api->get_it_cnt(gh[k]);
-      if (_api->simplex_batch) _api->simplex_batch(gh.data(), (int)gh.size(), nullptr, nullptr);
-      else
-        for (void *h : gh) _api->simplex(h, nullptr);
+      const std::vector<int> pivots = solve_counted(_api, gh, nullptr);
       for (size_t k = 0; k < gh.size(); k++) {
         Job &jb = jobs[gj[k]];
         jb.lps++;
-        jb.pivots += _api->get_it_cnt(gh[k]) - before[k];
+        jb.pivots += pivots[k];
         jb.k++;
         jb.alpha = jb.alpha * 0.9;
         if (_api->get_status(gh[k]) != MVX_OPT) jb.end = MVX_PUMP_FAILED;
       }
     }
     // 4. the pumps that ended integral: rounded and checked against the root's model, priced with the root's objective
-    std::vector<const void *> rh;
-    std::vector<size_t> rj;
-    for (size_t j = j0; j < j1; j++)
-      if (jobs[j].end == MVX_PUMP_INTEGRAL) {
-        rh.push_back(jobs[j].cur);
-        rj.push_back(j);
-      }
-    std::vector<HeurOut> got;
-    const int rc = _round.run(rh, got);
+    const int rc = round_integral(_round, jobs, j0, j1, [](const Job &jb) { return jb.end == MVX_PUMP_INTEGRAL; });
     if (rc != 0) return rc;
-    for (size_t k = 0; k < rj.size(); k++) jobs[rj[k]].res = std::move(got[k]);
     for (size_t j = j0; j < j1; j++) drop(jobs[j]);
     return 0;
   }
 
   const mvx_lp_api *_api;
   const void *_root;
+  LazyModel &_lm;
   int _iters, _freq;
   double _alpha;
   Heuristic _round;
-  bool _device = true; // pump_obj_many is used while it accepts the model
-  bool _ready = false, _norm_ready = false;
+  DeviceOrTwin _route;
+  bool _norm_ready = false;
   double _norm = 0.0;
-  RoundHost _M;
 };
 
-// The pumps' counts, booked the way the serial loop meets the nodes.
-struct PumpBook {
+// The counts of one point-finding rule (rounding, pump, dives), booked the way the serial loop meets the nodes.
+struct RuleBook {
   long long calls = 0, found = 0, improved = 0, lps = 0, pivots = 0;
-  void store(mvx_bnb_result *res) const {
-    res->pump_calls = calls;
-    res->pump_found = found;
-    res->pump_improved = improved;
-    res->pump_lps = lps;
-    res->pump_pivots = pivots;
-  }
-};
-
-// The dives' counts, booked the way the serial loop meets the nodes.
-struct DiveBook {
-  long long calls = 0, found = 0, improved = 0, lps = 0, pivots = 0;
-  void store(mvx_bnb_result *res) const {
-    res->dive_calls = calls;
-    res->dive_found = found;
-    res->dive_improved = improved;
-    res->dive_lps = lps;
-    res->dive_pivots = pivots;
-  }
 };
 
 // ---- what the three drivers share: the tree's state and what happens to a node once its LP is solved ----
@@ -2261,16 +2206,16 @@ struct Tree {
   int has_incumbent = 0, incumbent_oid = 0;
   int hit_limit = 0, count = 0, rc_out = 0;
   long long sb_lps = 0, sb_pivots = 0;
-  HeurBook hbook;
-  DiveBook dbook;
-  PumpBook pbook;
-  Polish pol; // reads `model`: the rows from before the root cut loop, as the other rules that read the model do
+  RuleBook hbook, dbook, pbook;
+  int incumbent_src = 0; // where the incumbent in hand came from: 0 a node's own LP, 1 the rounding heuristic, 2 a dive, 3 a pump
+  LazyModel hm; // of `model`: the rows from before the root cut loop; the rules that read the model borrow it
+  Polish pol;
   long long polish_calls = 0, polish_moves = 0, polish_improved = 0;
   bool failed = false; // a point could not be polished: the run ends with -2
 
   Tree(const mvx_lp_api *api_, const void *prob, const mvx_bnb_params &p, const void *model = nullptr)
       : api(api_), prm(p), quirks(p.reference_quirks != 0), sg(MVOLP::sense_of(api_, prob, p)), n0(api_->get_num_cols(prob)),
-        bestLower(-sg * std::numeric_limits<double>::infinity()), xbest((size_t)n0 + 1, 0.0), pol(api_, model ? model : prob, p.polish) {}
+        bestLower(-sg * std::numeric_limits<double>::infinity()), xbest((size_t)n0 + 1, 0.0), hm(api_, model ? model : prob), pol(hm, p.polish) {}
 
   std::shared_ptr<MVOLP::NodeData> root(const void *prob) { // bs.cpp:80
     auto S1 = std::make_shared<MVOLP::NodeData>(api, prob, id);
@@ -2303,13 +2248,10 @@ struct Tree {
       if (!node.inital) rec.emit(MVX_EV_INTEGER, node.oid, obj, 0.0, 0, 0);
       // the root: bs.cpp:144-149 leaves without the event and without recording the solution; repaired mode keeps it
       if (node.inital ? !quirks : sg * obj > sg * bestLower) {
-        bestLower = obj;
-        has_incumbent = 1;
-        incumbent_oid = node.oid;
-        hbook.incumbent = 0; // the node's own point, not the heuristic's
+        std::vector<double> x = xbest;
         const int na = api->get_num_cols(h);
-        for (int i = 1; i <= na && i <= n0; i++) xbest[(size_t)i] = api->get_col_prim(h, i);
-        polish_incumbent();
+        for (int i = 1; i <= na && i <= n0; i++) x[(size_t)i] = api->get_col_prim(h, i);
+        adopt(0, obj, x, node.oid);
       }
       return node.inital ? STOP : INTEGER;
     }
@@ -2346,43 +2288,29 @@ struct Tree {
     for (size_t j = 1; j < xbest.size(); j++) xbest[j] = x[j];
   }
 
-  void book_heur(const HeurOut &h, int oid) {
-    const long long before = hbook.improved;
-    hbook.book(h, oid, sg, bestLower, has_incumbent, incumbent_oid, xbest);
-    if (hbook.improved != before) polish_incumbent();
-  }
-  // a dived node that branches: its work is booked, and its point becomes the incumbent when it is strictly better
-  void book_dive(const DiveOut &d, int oid) {
-    dbook.calls++;
-    dbook.lps += d.lps;
-    dbook.pivots += d.pivots;
-    if (!d.found) return;
-    dbook.found++;
-    if (!(sg * d.obj > sg * bestLower)) return;
-    dbook.improved++;
-    bestLower = d.obj;
+  // The point x[1..] of objective `obj`, found at node `oid` by `source` (incumbent_src), becomes the incumbent and is polished.
+  void adopt(int source, double obj, const std::vector<double> &x, int oid) {
+    bestLower = obj;
     has_incumbent = 1;
     incumbent_oid = oid;
-    hbook.incumbent = 2;
-    for (size_t j = 1; j < xbest.size() && j < d.x.size(); j++) xbest[j] = d.x[j];
+    incumbent_src = source;
+    for (size_t j = 1; j < xbest.size() && j < x.size(); j++) xbest[j] = x[j];
     polish_incumbent();
   }
-  // a pumped node that branches: its work is booked, and its point becomes the incumbent when it is strictly better
-  void book_pump(const PumpOut &p, int oid) {
-    pbook.calls++;
-    pbook.lps += p.lps;
-    pbook.pivots += p.pivots;
-    if (!p.found) return;
-    pbook.found++;
-    if (!(sg * p.obj > sg * bestLower)) return;
-    pbook.improved++;
-    bestLower = p.obj;
-    has_incumbent = 1;
-    incumbent_oid = oid;
-    hbook.incumbent = 3;
-    for (size_t j = 1; j < xbest.size() && j < p.x.size(); j++) xbest[j] = p.x[j];
-    polish_incumbent();
+  // a rule's run on a node that branches: its work is booked, and its point is adopted when it is strictly better
+  void book(RuleBook &b, int source, int found, double obj, const std::vector<double> &x, long long lps, long long pivots, int oid) {
+    b.calls++;
+    b.lps += lps;
+    b.pivots += pivots;
+    if (!found) return;
+    b.found++;
+    if (!(sg * obj > sg * bestLower)) return;
+    b.improved++;
+    adopt(source, obj, x, oid);
   }
+  void book_heur(const HeurOut &h, int oid) { book(hbook, 1, h.found, h.obj, h.x, 0, 0, oid); }
+  void book_dive(const DiveOut &d, int oid) { book(dbook, 2, d.found, d.obj, d.x, d.lps, d.pivots, oid); }
+  void book_pump(const PumpOut &p, int oid) { book(pbook, 3, p.found, p.obj, p.x, p.lps, p.pivots, oid); }
   void book_choice(const Choice &c) {
     sb_lps += c.sb_lps;
     sb_pivots += c.sb_pivots;
@@ -2408,6 +2336,14 @@ struct Tree {
     return hit_limit != 0;
   }
 
+  static void store(const RuleBook &b, long long &calls, long long &found, long long &improved, long long *lps = nullptr,
+                    long long *pivots = nullptr) {
+    calls = b.calls;
+    found = b.found;
+    improved = b.improved;
+    if (lps) *lps = b.lps;
+    if (pivots) *pivots = b.pivots;
+  }
   int finish(mvx_bnb_result *res, const RcFix *rcfix, const Prop *prop) const {
     std::memset(res, 0, sizeof(*res));
     res->n_nodes = id - 1;
@@ -2426,9 +2362,10 @@ struct Tree {
     res->hit_limit = hit_limit;
     res->sb_lps = sb_lps;
     res->sb_pivots = sb_pivots;
-    hbook.store(res);
-    dbook.store(res);
-    pbook.store(res);
+    store(hbook, res->heur_calls, res->heur_found, res->heur_improved);
+    store(dbook, res->dive_calls, res->dive_found, res->dive_improved, &res->dive_lps, &res->dive_pivots);
+    store(pbook, res->pump_calls, res->pump_found, res->pump_improved, &res->pump_lps, &res->pump_pivots);
+    res->incumbent_heur = incumbent_src;
     res->polish_calls = polish_calls;
     res->polish_moves = polish_moves;
     res->polish_improved = polish_improved;
@@ -2467,11 +2404,11 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const void *model, const m
   std::deque<std::shared_ptr<MVOLP::NodeData>> leafContainer;
   leafContainer.push_back(T.root(prob));
   void *a = api->create_prob(); // bs.cpp:89
-  Heuristic heur(api, model, prm.heur);
+  Heuristic heur(T.hm, prm.heur);
   RcFix rcfix(api);
-  Prop prop(api, model, prm.prop);
-  Dive dive(api, model, prm);
-  Pump pump(api, model, prm);
+  Prop prop(T.hm, prm.prop);
+  Dive dive(T.hm, prm);
+  Pump pump(T.hm, prm);
 
   while (!leafContainer.empty()) { // bs.cpp:96
     if (T.node_limit()) break;
@@ -2561,15 +2498,7 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const void *model, const m
       }
       // bs.cpp:279 and :287 solve two independent clones; an engine with a batch entry runs them
       // side by side (identical results), otherwise one after the other as the reference does
-      if (api->simplex_batch) {
-        void *pair[2] = {S2->prob, S3->prob};
-        const int before = api->get_it_cnt(S2->prob) + api->get_it_cnt(S3->prob);
-        api->simplex_batch(pair, 2, nullptr, nullptr);
-        rec.pivots += api->get_it_cnt(S2->prob) + api->get_it_cnt(S3->prob) - before;
-      } else {
-        solve(api, S2->prob, rec);
-        solve(api, S3->prob, rec);
-      }
+      for (int piv : solve_counted(api, {S2->prob, S3->prob}, nullptr)) rec.pivots += piv;
       leafContainer.push_back(S2); // bs.cpp:297-298
       leafContainer.push_back(S3);
       T.candidates(*S2, api->get_obj_val(S2->prob), *S3, api->get_obj_val(S3->prob));
@@ -2594,11 +2523,11 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const void *model, c
   std::deque<std::shared_ptr<MVOLP::NodeData>> leafContainer;
   leafContainer.push_back(T.root(prob));
   bool stop = false;
-  Heuristic heur(api, model, prm.heur);
+  Heuristic heur(T.hm, prm.heur);
   RcFix rcfix(api);
-  Prop prop(api, model, prm.prop);
-  Dive dive(api, model, prm);
-  Pump pump(api, model, prm);
+  Prop prop(T.hm, prm.prop);
+  Dive dive(T.hm, prm);
+  Pump pump(T.hm, prm);
   auto fail = [&]() { // whatever code a failing call gives, the tree so far goes back with -2
     T.rc_out = -2;
     stop = true;
@@ -3057,7 +2986,7 @@ int branchAndBoundBest(const mvx_lp_api *api, void *prob, const void *model, con
   push(T.root(prob));
   long long rounds = 0, speculated = 0;
   bool stop = false;
-  Heuristic heur(api, model, prm.heur);
+  Heuristic heur(T.hm, prm.heur);
   const size_t W = (size_t)prm.best_window;
   const bool timing = std::getenv("MVX_BNB_TIMING") != nullptr;
   double tA = 0, tInfo = 0, tSpec = 0, tKids = 0, tReplay = 0;
@@ -3435,12 +3364,10 @@ static std::vector<int> cut_select(int k, const double *eff, const double *gram,
 
 // ---- clique cuts (cut_families bit 2, DESIGN.md "Clique cuts (cut_families)") ----
 
-// The conflict graph of the binary columns of `P` through the table (the host twin of k_conflict_rows / k_conflict: the
+// The conflict graph of the binary columns of `P`, whose model is M (the host twin of k_conflict_rows / k_conflict: the
 // activities are step 1 of prop_host at the handle's own bounds, every product and sum rounded on its own, and a pair's test
 // adds the lower column's coefficient first).  adj: (n+1) x W words.
-static int conflict_graph_host(const mvx_lp_api *api, const void *P, unsigned long long *adj, long long *edges) {
-  PropHost M;
-  if (prop_host_model(api, P, M) != 0) return -2;
+static int conflict_graph_host(const mvx_lp_api *api, const HostModel &M, const void *P, unsigned long long *adj, long long *edges) {
   const int n = M.n, m0 = M.m0;
   const size_t W = ((size_t)n + 1 + 63) / 64;
   std::vector<double> l((size_t)n + 1, 0.0), u((size_t)n + 1, 0.0);
@@ -3580,9 +3507,11 @@ static int cut_loop(const mvx_lp_api *api, void *P, int R, int K, double maxpar,
   std::vector<unsigned long long> adj;
   if (families & 2) {
     adj.assign(row * ((row + 63) / 64), 0ULL);
-    int grc = api->conflict_graph ? api->conflict_graph(P, adj.data(), &o.conflicts) : -5;
-    if (grc == -5) grc = conflict_graph_host(api, P, adj.data(), &o.conflicts);
-    if (grc != 0) return -2;
+    LazyModel lm(api, P);
+    if (DeviceOrTwin().run(
+            api->conflict_graph != nullptr, lm, [&]() { return api->conflict_graph(P, adj.data(), &o.conflicts); },
+            [&](const HostModel &M) { return conflict_graph_host(api, M, P, adj.data(), &o.conflicts); }) != 0)
+      return -2;
   }
   auto solve_lp = [&]() {
     const int before = api->get_it_cnt(P);
@@ -3796,7 +3725,8 @@ int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *
       infeasible_root(MVOLP::FEAS);
     } else if (params->prop > 0) {
       // the root's own propagation, on the same copy: its list is applied before the first solve
-      Prop root_prop(api, work, params->prop);
+      LazyModel root_model(api, work); // read before the root's bounds are final: the tree reads its own
+      Prop root_prop(root_model, params->prop);
       std::vector<PropOut> got;
       if (root_prop.compute({work}, got) != 0) {
         infeasible_root(MVOLP::NONE); // nothing ran: the tree so far is the unsolved root
@@ -3877,8 +3807,8 @@ int mvx_bnb_penalties(const mvx_lp_api *api, const void *prob, const int *cols, 
 int mvx_bnb_round(const mvx_lp_api *api, const void *prob, const void *root, int mode, double *obj, int *found, double *x) {
   if (!api) api = &g_hip_api;
   if (!prob || !root || mode < 1 || mode > 2 || !obj || !found || !x) return -1;
-  RoundHost M;
-  const int rc = round_host_model(api, root, M);
+  HostModel M;
+  const int rc = read_host_model(api, root, M);
   if (rc != 0) return rc;
   return round_host(api, M, prob, mode, obj, found, x);
 }
@@ -3886,8 +3816,8 @@ int mvx_bnb_round(const mvx_lp_api *api, const void *prob, const void *root, int
 int mvx_bnb_dive_pick(const mvx_lp_api *api, const void *prob, const void *root, int rule, int *nfrac, int *col, int *dir, double *val) {
   if (!api) api = &g_hip_api;
   if (!prob || !root || (rule != 1 && rule != 2 && rule != 4) || !nfrac || !col || !dir || !val) return -1;
-  RoundHost M;
-  int rc = round_host_model(api, root, M);
+  HostModel M;
+  int rc = read_host_model(api, root, M);
   if (rc != 0) return rc;
   DivePick p;
   rc = dive_pick_host(api, M, prob, rule, p);
@@ -3906,7 +3836,8 @@ int mvx_bnb_dive(const mvx_lp_api *api, const void *prob, const void *root, int 
       api->get_num_cols(prob) != api->get_num_cols(root))
     return -1;
   if (api->get_status(prob) != MVX_OPT) return -3;
-  Dive dive(api, root, rules, depth);
+  LazyModel lm(api, root);
+  Dive dive(lm, rules, depth);
   std::vector<DiveOut> out;
   const int rc = dive.run({prob}, out);
   if (rc != 0) return rc;
@@ -3922,8 +3853,8 @@ int mvx_bnb_pump_obj(const mvx_lp_api *api, const void *prob, const void *root, 
                      int *info, double *xt, double *c) {
   if (!api) api = &g_hip_api;
   if (!prob || !root || !ab || !info || !xt || !c || (has_prev && !xprev)) return -1;
-  RoundHost M;
-  int rc = round_host_model(api, root, M);
+  HostModel M;
+  int rc = read_host_model(api, root, M);
   if (rc != 0) return rc;
   PumpStep st;
   rc = pump_obj_host(api, M, prob, xprev, has_prev ? 1 : 0, ab[0], ab[1], st);
@@ -3942,7 +3873,8 @@ int mvx_bnb_pump(const mvx_lp_api *api, const void *prob, const void *root, int 
   if (api->get_num_cols(prob) != api->get_num_cols(root)) return -1;
   if (!api->get_status) return -2;
   if (api->get_status(prob) != MVX_OPT) return -3;
-  Pump pump(api, root, iters, alpha);
+  LazyModel lm(api, root);
+  Pump pump(lm, iters, alpha);
   std::vector<PumpOut> out;
   const int rc = pump.run(std::vector<const void *>(1, prob), out);
   if (rc != 0) return rc;
@@ -3962,12 +3894,7 @@ int mvx_bnb_rc_tighten(const mvx_lp_api *api, const void *prob, double cutoff, d
   *cnt = 0;
   const int rc = rc_tighten_host(api, prob, cutoff, tol, l);
   if (rc != 0) return rc;
-  *cnt = (int)l.size();
-  for (size_t k = 0; k < l.size(); k++) {
-    cols[k] = l[k].col;
-    lb[k] = l[k].lb;
-    ub[k] = l[k].ub;
-  }
+  list_out(l, cnt, cols, lb, ub);
   return 0;
 }
 
@@ -3975,21 +3902,16 @@ int mvx_bnb_propagate(const mvx_lp_api *api, const void *prob, const void *root,
                       int *cols, double *lb, double *ub) {
   if (!api) api = &g_hip_api;
   if (!prob || !root || max_rounds < 1 || !infeasible || !rounds || !cnt || !cols || !lb || !ub) return -1;
-  PropHost M;
+  HostModel M;
   *infeasible = *rounds = *cnt = 0;
-  int rc = prop_host_model(api, root, M);
+  int rc = read_host_model(api, root, M);
   if (rc != 0) return rc;
   PropOut out;
   rc = prop_host(api, M, prob, max_rounds, out);
   if (rc != 0) return rc;
   *infeasible = out.infeasible;
   *rounds = out.rounds;
-  *cnt = (int)out.list.size();
-  for (size_t k = 0; k < out.list.size(); k++) {
-    cols[k] = out.list[k].col;
-    lb[k] = out.list[k].lb;
-    ub[k] = out.list[k].ub;
-  }
+  list_out(out.list, cnt, cols, lb, ub);
   return 0;
 }
 
@@ -4043,18 +3965,20 @@ int mvx_bnb_cut_loop(const mvx_lp_api *api, void *prob, int rounds, int K, doubl
 int mvx_bnb_polish(const mvx_lp_api *api, const void *root, double *x, int max_moves, double *obj, int *moves, int *ok) {
   if (!api) api = &g_hip_api;
   if (!root || !x || !obj || !moves || !ok || max_moves < 1 || max_moves > 100000) return -1;
-  RoundHost M;
-  const int rc = round_host_model(api, root, M);
+  HostModel M;
+  const int rc = read_host_model(api, root, M);
   if (rc != 0) return rc;
-  polish_host(M, x, max_moves, obj, moves, ok);
-  return 0;
+  return polish_host(M, x, max_moves, obj, moves, ok);
 }
 
 int mvx_bnb_conflict_graph(const mvx_lp_api *api, const void *model, unsigned long long *adj, long long *edges) {
   if (!api) api = &g_hip_api;
   if (!model || !adj || !edges) return -1;
   *edges = 0;
-  return conflict_graph_host(api, model, adj, edges);
+  HostModel M;
+  const int rc = read_host_model(api, model, M);
+  if (rc != 0) return rc;
+  return conflict_graph_host(api, M, model, adj, edges);
 }
 
 int mvx_bnb_clique_cuts(int n, const unsigned long long *adj, const double *x, int max_cuts, double *vals, double *rhs, int *count) {

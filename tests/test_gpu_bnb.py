@@ -333,3 +333,22 @@ def test_first_bnb_of_a_fresh_process_is_the_same_tree(gpu):
         assert out.returncode == 0, out.stderr[-2000:]
         got = json.loads(out.stdout.strip().splitlines()[-1])
         assert got == {"count": here["count"], "pivots": here["total_pivots"], "digest": treedigest.digest(here)}
+
+
+def test_every_rule_refused_at_once_gives_the_oracles_tree(gpu, orc):
+    """n = 4 200 is more than the rules' kernels hold (4 096): round_many, pump_obj_many, dive_pick_many, propagate_many and
+    polish_many all answer -5 in the same tree, each rule goes to its twin on the tree's one host model, and the tree is the
+    oracle's, whose table has none of the entries."""
+    A, b, c, U = synth.dense_ilp(12, 4200, 3, 2)
+    kw = dict(quirks=0, heur=2, pump=20, dive=7, dive_depth=6, prop=8, polish=1000, window=64, max_nodes=40)
+    got = bnb.branch_and_bound(lpgen.load_ilp(gpu, A, b, c, U), **kw)
+    ref = bnb.branch_and_bound(lpgen.load_ilp(orc, A, b, c, U), table=bnb.table_from(orc), **kw)
+    assert got["rc"] == 0 and ref["rc"] == 0
+    same_result(got, ref)
+    for rule, names in (("heur", ("calls", "found", "improved")), ("pump", ("calls", "found", "improved", "lps", "pivots")),
+                        ("dive", ("calls", "found", "improved", "lps", "pivots")), ("prop", ("calls", "fixed", "tightened", "infeasible")),
+                        ("polish", ("calls", "moves", "improved"))):
+        for name in names:
+            assert got["%s_%s" % (rule, name)] == ref["%s_%s" % (rule, name)], (rule, name)
+    assert got["incumbent_heur"] == ref["incumbent_heur"]
+    assert got["heur_calls"] >= 1 and got["pump_calls"] >= 1 and got["dive_calls"] >= 1 and got["prop_calls"] >= 1
