@@ -85,6 +85,15 @@ int mvx_add_rows(mvx_prob *P, int nrs);                                      /* 
    becomes MVX_UNDEF and the next solve takes no pivot; when one is non-basic the tableau is given up and the next solve starts
    from the slack basis.  Returns 0; -1 and nothing changed for a null, nrs < 1, a number out of range or a duplicate. */
 int mvx_del_rows(mvx_prob *P, int nrs, const int *num);
+/* mvx_del_rows on `count` distinct handles of one column count in one call (DESIGN.md "Cut purging in the tree (node_purge)"):
+   handle t loses the model rows rows[off[t] .. off[t+1]-1] (1-based, distinct, any order; off[0] = 0, off ascending).  Every
+   handle ends as mvx_del_rows(Ps[t], ...) leaves it, bit for bit -- model, tableau, basis arrays, mirrors, pending bound edits,
+   status MVX_UNDEF -- and the device work of all of them is one upload and one k_delrows_many launch.  A handle with an empty
+   list is not touched at all (its status stays); one without a tableau gets the model edit only; one in which a listed row's
+   auxiliary variable is non-basic has its tableau given up, the others are unaffected.  Returns 0; -1 and no handle changed for
+   a null, count < 1, a handle listed twice, differing column counts, a descending off, or a row number out of range or
+   duplicated in any handle. */
+int mvx_del_rows_many(mvx_prob *const *Ps, int count, const int *off, const int *rows);
 int mvx_add_cols(mvx_prob *P, int ncs);                                      /* (readers) */
 void mvx_set_row_bnds(mvx_prob *P, int i, int type, double lb, double ub);   /* cut.cpp:43 */
 void mvx_set_col_bnds(mvx_prob *P, int j, int type, double lb, double ub);   /* bs.cpp:274,282 */

@@ -129,6 +129,10 @@ typedef struct mvx_lp_api {
   /* optional (may be NULL): the incumbent polishing (DESIGN.md "Incumbent polishing (polish)") of `count` points in one call
      (mvx_polish_many), the model taken from `root`; without it, or when it returns -5, the host twin mvx_bnb_polish runs */
   int (*polish_many)(const void *root, int count, double *x, int max_moves, double *obj, int *moves, int *ok);
+  /* optional (may be NULL): del_rows on `count` distinct handles in one call (mvx_del_rows_many; DESIGN.md "Cut purging in the
+     tree (node_purge)"): handle t loses the rows rows[off[t] .. off[t+1]-1] (1-based), 0 on success; without it, or when it
+     fails, the tree's purge calls del_rows handle by handle, and without that makes each purged row a free row */
+  int (*del_rows_many)(void *const *Ps, int count, const int *off, const int *rows);
 } mvx_lp_api;
 
 const mvx_lp_api *mvx_hip_lp_api(void);
@@ -209,6 +213,11 @@ typedef struct {
                            pump's -- is first improved by a best-improvement search over one- and two-column unit moves; the
                            decision whether it becomes the incumbent is taken on the point as found.  Needs reference_quirks = 0;
                            allowed with best_window > 0 */
+  int node_purge;       /* purging of slack cut rows in the tree (DESIGN.md "Cut purging in the tree (node_purge)"): 0 (default) no
+                           row leaves; A = 1..64: a row behind the caller's rows -- a cut_strat row of an ancestor, or a row of the
+                           root cut rounds -- leaves both children of a branching node once its auxiliary variable has been basic
+                           at A consecutive branching nodes on the path.  Outside 0..64: refused; A > 0 needs
+                           reference_quirks = 0 and best_window = 0, and get_row_stat in the table */
 } mvx_bnb_params;
 
 /* B&B events at the emit points of bs.cpp (message.h EventType) */
@@ -283,6 +292,9 @@ typedef struct {
   long long polish_calls;    /* polish > 0: points polished (every point that became the incumbent) */
   long long polish_moves;    /* ... moves taken, summed */
   long long polish_improved; /* ... points that came back with a better objective */
+  long long node_purge_calls;   /* node_purge > 0: child handles that lost at least one row */
+  long long node_purge_rows;    /* ... rows removed, summed over the child handles (deleted, or made free rows) */
+  long long node_cut_rows_peak; /* the most live rows behind the caller's rows that any solved node carried (with node_purge = 0 too) */
 } mvx_bnb_result;
 
 void mvx_bnb_default_params(mvx_bnb_params *p);
@@ -441,6 +453,15 @@ int mvx_bnb_cut_loop_families(const mvx_lp_api *api, void *prob, int rounds, int
    mvx_bnb_cut_loop_families is this function with purge = 0 */
 int mvx_bnb_cut_loop_purge(const mvx_lp_api *api, void *prob, int rounds, int K, double maxpar, int families, int purge,
                            long long *counters, double *bounds);
+
+/* The age step of the tree's purge (DESIGN.md "Cut purging in the tree (node_purge)") from numbers only: age[0..k) are the ages
+   of a node's rows behind the caller's rows, ascending by row, basic[t] is 1 when row t's auxiliary variable is MVX_BS at the
+   node.  A row whose age is 255 is dead (a free row) and is skipped; every other age goes up by one, saturating at 254, when
+   the row is basic and becomes 0 otherwise.  out[0..*nout) receives the positions whose age has reached A, ascending.
+   Returns 0; -1 for k < 0, A outside 1..64 or a null pointer (age, basic and out may be null when k = 0).  mvx_branchAndBound
+   returns -1 (*res empty) for node_purge outside 0..64 and for node_purge > 0 with reference_quirks = 1 or best_window > 0,
+   and -2 with the tree so far when a purge could not be carried out on any path */
+int mvx_bnb_purge_ages(int k, const int *basic, int A, unsigned char *age, int *out, int *nout);
 
 /* Clique cuts (DESIGN.md "Clique cuts (cut_families)"), host twin of mvx_conflict_graph through the table only (get_mat_row, row
    and column bounds, get_col_kind): the same (n+1) x W words and edge count for the handle `model`, which need not be solved and

@@ -17,7 +17,7 @@ _FIELDS = [
 _OPTIONAL = ["simplex_batch", "get_obj_dir", "gmi_cuts", "gmi_cuts_many", "get_col_prim_all", "classify_many", "get_tableau", "get_basis",
              "branch_penalties_many", "round_many", "rc_tighten_many", "tighten_cols_many", "propagate_many", "set_col_bnds_many",
              "dive_pick_many", "set_obj_coef", "set_obj_many", "pump_obj_many", "cut_scores", "add_cut_rows", "conflict_graph", "del_rows",
-             "polish_many"]
+             "polish_many", "del_rows_many"]
 
 
 class LpApiTable(C.Structure):
@@ -56,6 +56,7 @@ class BnbParams(C.Structure):
         ("cut_families", C.c_int),
         ("cut_purge", C.c_int),
         ("polish", C.c_int),
+        ("node_purge", C.c_int),
     ]
 
 
@@ -128,6 +129,9 @@ class BnbResult(C.Structure):
         ("polish_calls", C.c_longlong),
         ("polish_moves", C.c_longlong),
         ("polish_improved", C.c_longlong),
+        ("node_purge_calls", C.c_longlong),
+        ("node_purge_rows", C.c_longlong),
+        ("node_cut_rows_peak", C.c_longlong),
     ]
 
 
@@ -226,6 +230,10 @@ def _bind(lib):
     lib.mvx_bnb_conflict_graph.argtypes = [C.c_void_p, C.c_void_p, _UP, _LP]
     lib.mvx_bnb_clique_cuts.restype = C.c_int
     lib.mvx_bnb_clique_cuts.argtypes = [C.c_int, _UP, _DP, C.c_int, _DP, _DP, _IP]
+    lib.mvx_del_rows_many.restype = C.c_int
+    lib.mvx_del_rows_many.argtypes = [C.c_void_p, C.c_int, _IP, _IP]
+    lib.mvx_bnb_purge_ages.restype = C.c_int
+    lib.mvx_bnb_purge_ages.argtypes = [C.c_int, _IP, C.c_int, C.POINTER(C.c_ubyte), _IP, _IP]
     lib.mvx_polish_many.restype = C.c_int
     lib.mvx_polish_many.argtypes = [C.c_void_p, C.c_int, _DP, C.c_int, _DP, _IP, _IP]
     lib.mvx_bnb_polish.restype = C.c_int
@@ -307,13 +315,16 @@ def result_to_dict(res):
         "polish_calls": res.polish_calls,
         "polish_moves": res.polish_moves,
         "polish_improved": res.polish_improved,
+        "node_purge_calls": res.node_purge_calls,
+        "node_purge_rows": res.node_purge_rows,
+        "node_cut_rows_peak": res.node_cut_rows_peak,
     }
 
 
 def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, window=None, cut_select=0, cut_chance=1.0,
                 best_window=None, sb_cands=None, sb_iters=None, heur=None, rc_fix=None, prop=None, dive=None, dive_freq=None,
                 dive_depth=None, pump=None, pump_freq=None, pump_alpha=None, cut_rounds=None, cut_round_max=None, cut_maxpar=None,
-                cut_families=None, cut_purge=None, polish=None):
+                cut_families=None, cut_purge=None, polish=None, node_purge=None):
     """mvx_bnb_params with ParameterObj's defaults (util.h:65-67) overridden by the arguments (None: the default)."""
     pr = BnbParams()
     lib().mvx_bnb_default_params(C.byref(pr))
@@ -358,13 +369,15 @@ def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, l
         pr.cut_purge = cut_purge
     if polish is not None:
         pr.polish = polish
+    if node_purge is not None:
+        pr.node_purge = node_purge
     return pr
 
 
 def branch_and_bound(prob, var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, table=None, window=None,
                      cut_select=0, cut_chance=1.0, best_window=None, sb_cands=None, sb_iters=None, heur=None, rc_fix=None, prop=None,
                      dive=None, dive_freq=None, dive_depth=None, pump=None, pump_freq=None, pump_alpha=None, cut_rounds=None,
-                     cut_round_max=None, cut_maxpar=None, cut_families=None, cut_purge=None, polish=None):
+                     cut_round_max=None, cut_maxpar=None, cut_families=None, cut_purge=None, polish=None, node_purge=None):
     """Run the driver on `prob` (a capi.Prob).  table=None uses the gfx950 engine's own table.  best_window > 1 with
     node_strat=1: the speculative best-bound window (mvx_bnb_params.best_window).  var_strat 3 / 4: branching on the node
     LP's penalties / strong branching (sb_cands candidates, sb_iters pivots per child).  heur 1 / 2: the primal rounding
@@ -381,13 +394,15 @@ def branch_and_bound(prob, var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, 
     (the default), 2 clique cuts from the conflict graph of the binary columns; cut_purge = A in 1..64 takes a row of those rounds
     out again once its auxiliary variable has been basic after A consecutive re-solves (0, the default: no row leaves).
     polish = N in 1..100000: every point that becomes the incumbent is first improved by a best-improvement search over one- and
-    two-column unit moves, at most N of them (quirks=0; every single-GPU driver, best_window included).  The
+    two-column unit moves, at most N of them (quirks=0; every single-GPU driver, best_window included).  node_purge = A in
+    1..64: a cut row behind the caller's rows leaves both children of a branching node once its auxiliary variable has been basic
+    at A branching nodes in a row on the path (quirks=0, not with best_window; NODE_PURGE_COUNTERS in the dictionary).  The
     dictionary's "rc" is mvx_branchAndBound's return code (-1 refused parameters, -2 penalties, heuristic, tightening,
     propagation, pumps or dives unavailable)."""
     L = lib()
     pr = make_params(var_strat, node_strat, cut_strat, max_nodes, quirks, lazy_pool, window, cut_select, cut_chance, best_window, sb_cands,
                      sb_iters, heur, rc_fix, prop, dive, dive_freq, dive_depth, pump, pump_freq, pump_alpha, cut_rounds, cut_round_max,
-                     cut_maxpar, cut_families, cut_purge, polish)
+                     cut_maxpar, cut_families, cut_purge, polish, node_purge)
     res = BnbResult()
     tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
     rc = L.mvx_branchAndBound(tptr, prob.h, C.byref(pr), C.byref(res))
@@ -867,6 +882,38 @@ def add_cut_rows(prob, vals, rhs):
 
 
 PURGE_COUNTERS = ("cutloop_purged", "cutloop_live_rows")
+
+
+NODE_PURGE_COUNTERS = ("node_purge_calls", "node_purge_rows", "node_cut_rows_peak")
+
+
+def del_rows_many(handles, lists, table=None):
+    """mvx_del_rows_many: handle t loses the model rows lists[t] (1-based, distinct, any order), every handle left as mvx_del_rows
+    leaves it, the device work of all of them in one launch.  table=None: the gfx950 engine's own entry point; otherwise the
+    del_rows_many entry of `table` (None when the table has none).  Returns the call's code (0; -1 and nothing changed)."""
+    hs, off, flat = _flat(handles, lists)
+    IP = C.POINTER(C.c_int)
+    if table is None:
+        return lib().mvx_del_rows_many(hs, len(handles), off.ctypes.data_as(IP), flat.ctypes.data_as(IP))
+    if not table.del_rows_many:
+        return None
+    fn = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, IP, IP)(table.del_rows_many)
+    return fn(C.cast(hs, C.c_void_p), len(handles), off.ctypes.data_as(IP), flat.ctypes.data_as(IP))
+
+
+def purge_ages(basic, A, age):
+    """mvx_bnb_purge_ages, the age step of the tree's purge from numbers only: (rc, the new ages as a list, the positions whose
+    age has reached A)."""
+    import numpy as np
+
+    b = np.ascontiguousarray(np.asarray(basic, dtype=np.int32))
+    a = np.ascontiguousarray(np.asarray(age, dtype=np.uint8)).copy()
+    k = len(a)
+    out = np.zeros(max(1, k), dtype=np.int32)
+    nout = C.c_int(0)
+    IP = C.POINTER(C.c_int)
+    rc = lib().mvx_bnb_purge_ages(k, b.ctypes.data_as(IP), A, a.ctypes.data_as(C.POINTER(C.c_ubyte)), out.ctypes.data_as(IP), C.byref(nout))
+    return rc, a.tolist(), out[: nout.value].tolist()
 
 
 def cut_loop(prob, rounds=5, K=0, maxpar=0.0, table=None, families=None, purge=None):

@@ -54,6 +54,7 @@ extern "C" int mvx_conflict_graph(const mvx_prob *model, unsigned long long *adj
 extern "C" int mvx_polish_many(const mvx_prob *root, int count, double *x, int max_moves, double *obj, int *moves, int *ok)
     __attribute__((weak));
 extern "C" int mvx_del_rows(mvx_prob *P, int nrs, const int *num) __attribute__((weak));
+extern "C" int mvx_del_rows_many(mvx_prob *const *Ps, int count, const int *off, const int *rows) __attribute__((weak));
 
 namespace {
 
@@ -306,6 +307,9 @@ struct NodeData { // util.h:35-54
   bool inital;
   int oid;
   int repiv = -1; // window driver: pivots of the pop-time re-solve (bs.cpp:117) when it was done ahead, else -1
+  // node_purge > 0: one age per row behind the caller's rows, ascending (255: a dead row, purged as a free row), and their number
+  std::vector<unsigned char> age;
+  int dead = 0;
 
 private:
   const mvx_lp_api *_api;
@@ -2212,14 +2216,25 @@ struct Tree {
   Polish pol;
   long long polish_calls = 0, polish_moves = 0, polish_improved = 0;
   bool failed = false; // a point could not be polished: the run ends with -2
+  const int m0; // the rows of `model`: every row of a node behind them is a tree cut row (DESIGN.md "Cut purging in the tree")
+  long long purge_calls = 0, purge_rows = 0, cut_rows_peak = 0;
+  // MVX_BNB_WORK (a measurement aid, scripts/node_purge_profile.py): the sum over the solves that are booked of pivots x (live rows
+  // of the handle + 1), the entries a dense pivot touches per column, printed to stderr when the tree ends
+  const bool count_work = std::getenv("MVX_BNB_WORK") != nullptr;
+  long long work = 0;
+  void worked(const MVOLP::NodeData &nd, const void *h, long long pivots) {
+    if (count_work && h) work += pivots * (long long)(api->get_num_rows(h) - nd.dead + 1);
+  }
 
   Tree(const mvx_lp_api *api_, const void *prob, const mvx_bnb_params &p, const void *model = nullptr)
       : api(api_), prm(p), quirks(p.reference_quirks != 0), sg(MVOLP::sense_of(api_, prob, p)), n0(api_->get_num_cols(prob)),
-        bestLower(-sg * std::numeric_limits<double>::infinity()), xbest((size_t)n0 + 1, 0.0), hm(api_, model ? model : prob), pol(hm, p.polish) {}
+        bestLower(-sg * std::numeric_limits<double>::infinity()), xbest((size_t)n0 + 1, 0.0), hm(api_, model ? model : prob), pol(hm, p.polish),
+        m0(api_->get_num_rows(model ? model : prob)) {}
 
   std::shared_ptr<MVOLP::NodeData> root(const void *prob) { // bs.cpp:80
     auto S1 = std::make_shared<MVOLP::NodeData>(api, prob, id);
     S1->inital = true;
+    if (prm.node_purge > 0) S1->age.assign((size_t)std::max(0, api->get_num_rows(prob) - m0), 0); // the root cut rounds' live rows
     rec.node(S1->oid, 0);
     return S1;
   }
@@ -2237,6 +2252,7 @@ struct Tree {
   // (bs.cpp:135-223).  On BRANCH nothing but the bound is booked yet.
   Verdict verdict(MVOLP::NodeData &node, const void *h, int status, double obj) {
     const size_t o = (size_t)node.oid;
+    cut_rows_peak = std::max(cut_rows_peak, (long long)(api->get_num_rows(h) - m0 - node.dead));
     if (node.inital && status == -1) { // bs.cpp:139-143
       rec.prune[o] = MVOLP::FEAS;
       return STOP;
@@ -2329,6 +2345,72 @@ struct Tree {
     rec.emit(MVX_EV_CANDIDATE, S2.oid, obj2, 0.0, 0, 0);
     rec.emit(MVX_EV_CANDIDATE, S3.oid, obj3, 0.0, 0, 0);
   }
+  // node_purge = A > 0, at a node that branches, in front of its cut step (host mirrors only): the ages of the node's tree cut
+  // rows move on, and `out` takes the positions of the rows that leave both children.  false: the table cannot tell
+  bool purge_ages(MVOLP::NodeData &node, const void *h, std::vector<int> &out) {
+    out.clear();
+    const int k = (int)node.age.size();
+    if (prm.node_purge <= 0 || k == 0) return true;
+    if (!api->get_row_stat || !api->set_row_bnds) return false;
+    std::vector<int> basic((size_t)k, 0);
+    for (int t = 0; t < k; t++)
+      if (node.age[(size_t)t] != 255) basic[(size_t)t] = api->get_row_stat(h, m0 + 1 + t) == MVX_BS;
+    out.resize((size_t)k);
+    int nout = 0;
+    mvx_bnb_purge_ages(k, basic.data(), prm.node_purge, node.age.data(), out.data(), &nout);
+    out.resize((size_t)nout);
+    return true;
+  }
+  // the rows the node's cut step has appended start at age 0; the children take the node's ages as they stand
+  void purge_inherit(MVOLP::NodeData &node, const void *h, MVOLP::NodeData &S2, MVOLP::NodeData &S3) {
+    if (prm.node_purge <= 0) return;
+    node.age.resize((size_t)std::max(0, api->get_num_rows(h) - m0), 0);
+    S2.age = node.age;
+    S3.age = node.age;
+    S2.dead = S3.dead = node.dead;
+  }
+  // Child kids[t] loses the rows at the positions *lists[t] of its age array (ascending, not empty), behind its branching bound
+  // and in front of everything else that happens to it: all of them in one del_rows_many call; without the entry, or when it
+  // fails, del_rows handle by handle; without that, or when it fails, each row becomes a free row (the same LP, not the same
+  // bits), which stays where it is, dead.  Behind a deletion the child's ages are compacted as its rows are.
+  void purge_children(const std::vector<MVOLP::NodeData *> &kids, const std::vector<const std::vector<int> *> &lists) {
+    if (kids.empty()) return;
+    std::vector<void *> hs;
+    std::vector<int> off(1, 0), rows;
+    for (size_t t = 0; t < kids.size(); t++) {
+      hs.push_back(kids[t]->prob);
+      for (int p : *lists[t]) rows.push_back(m0 + 1 + p);
+      off.push_back((int)rows.size());
+    }
+    const bool all = api->del_rows_many && api->del_rows_many(hs.data(), (int)hs.size(), off.data(), rows.data()) == 0;
+    for (size_t t = 0; t < kids.size(); t++) {
+      MVOLP::NodeData &kid = *kids[t];
+      const std::vector<int> &l = *lists[t];
+      const int cnt = (int)l.size();
+      bool deleted = all;
+      if (!deleted && api->del_rows) {
+        std::vector<int> num(1, 0);
+        num.insert(num.end(), rows.begin() + off[t], rows.begin() + off[t + 1]);
+        deleted = api->del_rows(kid.prob, cnt, num.data()) == 0;
+      }
+      if (deleted) {
+        size_t w = 0, d = 0;
+        for (size_t q = 0; q < kid.age.size(); q++) {
+          if (d < l.size() && (size_t)l[d] == q) d++;
+          else kid.age[w++] = kid.age[q];
+        }
+        kid.age.resize(w);
+      } else {
+        for (int p : l) {
+          api->set_row_bnds(kid.prob, m0 + 1 + p, MVX_FR, 0.0, 0.0);
+          kid.age[(size_t)p] = 255;
+        }
+        kid.dead += cnt;
+      }
+      purge_calls++;
+      purge_rows += cnt;
+    }
+  }
   // a node is done (bs.cpp:326); true when a branching met the loop limit: bs.cpp:320-323 calls std::exit(-1), here the run stops
   bool counted(bool branching) {
     if (branching && count > prm.loop_limit) hit_limit = 1;
@@ -2371,6 +2453,10 @@ struct Tree {
     res->polish_improved = polish_improved;
     if (rcfix) rcfix->store(res);
     if (prop) prop->store(res);
+    res->node_purge_calls = purge_calls;
+    res->node_purge_rows = purge_rows;
+    res->node_cut_rows_peak = cut_rows_peak;
+    if (count_work) std::fprintf(stderr, "bnb work: %lld\n", work);
     return rc_out;
   }
 };
@@ -2416,7 +2502,11 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const void *model, const m
     std::shared_ptr<MVOLP::NodeData> node = params.pickNode(leafContainer, index); // bs.cpp:101
     api->erase_prob(a);                       // bs.cpp:114-115
     api->copy_prob(a, node->prob, MVX_OFF);   // bs.cpp:116
-    solve(api, a, rec);                       // bs.cpp:117
+    {
+      const long long piv0 = rec.pivots;
+      solve(api, a, rec); // bs.cpp:117
+      T.worked(*node, a, rec.pivots - piv0);
+    }
     const double obj = api->get_obj_val(a);
     rec.emit(MVX_EV_PREGNANT, node->oid, obj, 0.0, 0, 0); // bs.cpp:119-129
 
@@ -2479,6 +2569,12 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const void *model, const m
         bound = api->get_col_prim(a, pick);
         T.book_choice(ch[0]);
       }
+      // node_purge: the ages move on in front of the cut step; the rows that have reached the limit leave both children
+      std::vector<int> gone;
+      if (!T.purge_ages(*node, a, gone)) {
+        T.rc_out = -2;
+        break;
+      }
       add_node_cuts(api, a, prm, T.quirks, pool); // bs.cpp:249-258
       if (prm.var_strat < 3) {
         pick = params.pickVar(vars);         // bs.cpp:260
@@ -2490,6 +2586,8 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const void *model, const m
       auto S3 = std::make_shared<MVOLP::NodeData>(api, a, T.id);
       T.children(*node, *S2, *S3);
       child_bounds(api, a, pick, bound, T.quirks, S2->prob, S3->prob);
+      T.purge_inherit(*node, a, *S2, *S3);
+      if (!gone.empty()) T.purge_children({S2.get(), S3.get()}, {&gone, &gone});
       // prop: both children behind their branching bound and the rc_fix list, in front of their first solve; whatever code
       // a failing call gives (no accessors, device memory, a refused list), the tree so far goes back with -2
       if ((!rcl.empty() && rcfix.apply({S2->prob, S3->prob}, {&rcl, &rcl}) != 0) || (prm.prop > 0 && prop.run({S2->prob, S3->prob}) != 0)) {
@@ -2498,7 +2596,12 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const void *model, const m
       }
       // bs.cpp:279 and :287 solve two independent clones; an engine with a batch entry runs them
       // side by side (identical results), otherwise one after the other as the reference does
-      for (int piv : solve_counted(api, {S2->prob, S3->prob}, nullptr)) rec.pivots += piv;
+      {
+        const std::vector<int> pivs = solve_counted(api, {S2->prob, S3->prob}, nullptr);
+        for (int piv : pivs) rec.pivots += piv;
+        T.worked(*S2, S2->prob, pivs[0]);
+        T.worked(*S3, S3->prob, pivs[1]);
+      }
       leafContainer.push_back(S2); // bs.cpp:297-298
       leafContainer.push_back(S3);
       T.candidates(*S2, api->get_obj_val(S2->prob), *S3, api->get_obj_val(S3->prob));
@@ -2538,6 +2641,7 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const void *model, c
     std::shared_ptr<MVOLP::NodeData> S2, S3;
     int before2, before3;
     RcList rc; // rc_fix: the bound list both children take in front of their first solve
+    std::vector<int> gone; // node_purge: the positions of the tree cut rows both children lose
   };
   // One round of the loop.  Its child solves (phase C) run on a worker thread while the main thread replays
   // the next window, whose nodes were solved rounds ago: a breadth-first queue is longer than the window
@@ -2582,6 +2686,8 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const void *model, c
       Branch &br = R.branches[b];
       const size_t k2 = 2 * b, k3 = 2 * b + 1;
       rec.pivots += (R.after1[k2] - br.before2) + (R.after1[k3] - br.before3);
+      T.worked(*br.S2, br.S2->prob, R.after1[k2] - br.before2);
+      T.worked(*br.S3, br.S3->prob, R.after1[k3] - br.before3);
       br.S2->repiv = R.repiv[k2];
       br.S3->repiv = R.repiv[k3];
       rec.sink = &R.node_events[br.slot];
@@ -2747,6 +2853,7 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const void *model, c
       void *aw = a[w];
       rec.sink = &cur.node_events[w];
       rec.pivots += (node->repiv >= 0) ? node->repiv : api->get_it_cnt(aw) - before[w];
+      T.worked(*node, aw, (node->repiv >= 0) ? node->repiv : api->get_it_cnt(aw) - before[w]);
       processed++;
       const double obj = api->get_obj_val(aw);
       rec.emit(MVX_EV_PREGNANT, node->oid, obj, 0.0, 0, 0);
@@ -2783,6 +2890,11 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const void *model, c
         const int pick = prm.var_strat >= 3 ? choice[w].pick : params.pickVar(vars);
         const double bound = api->get_col_prim(aw, pick);
         if (prm.var_strat >= 3) T.book_choice(choice[w]);
+        std::vector<int> gone;
+        if (!T.purge_ages(*node, aw, gone)) {
+          fail();
+          break;
+        }
         ti = now();
         add_node_cuts(api, aw, prm, quirks, pool, pre.empty() ? nullptr : pre[w].get());
         tB_cuts += now() - ti;
@@ -2802,6 +2914,8 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const void *model, c
         br.before2 = api->get_it_cnt(br.S2->prob);
         br.before3 = api->get_it_cnt(br.S3->prob);
         br.rc = std::move(node_rc);
+        T.purge_inherit(*node, aw, *br.S2, *br.S3);
+        br.gone = std::move(gone);
         branches.push_back(br);
         leafContainer.push_back(br.S2); // the queue order bs.cpp:297-298 gives them
         leafContainer.push_back(br.S3);
@@ -2812,6 +2926,20 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const void *model, c
       }
     }
     rec.sink = nullptr;
+    // node_purge: every child of the round loses its parent's list of rows in one call, behind its branching bound and in front
+    // of everything else
+    if (prm.node_purge > 0) {
+      std::vector<MVOLP::NodeData *> kids;
+      std::vector<const std::vector<int> *> lists;
+      for (const Branch &br : branches)
+        if (!br.gone.empty()) {
+          kids.push_back(br.S2.get());
+          kids.push_back(br.S3.get());
+          lists.push_back(&br.gone);
+          lists.push_back(&br.gone);
+        }
+      T.purge_children(kids, lists);
+    }
     // rc_fix: every child of the round takes its parent's list in one call, behind its branching bound and in front of its
     // first solve
     if (prm.rc_fix > 0) {
@@ -3242,6 +3370,9 @@ const mvx_lp_api g_hip_api = {
     mvx_polish_many ? +[](const void *root, int count, double *x, int max_moves, double *obj, int *moves, int *ok) {
       return mvx_polish_many((const mvx_prob *)root, count, x, max_moves, obj, moves, ok);
     } : nullptr,
+    mvx_del_rows_many ? +[](void *const *Ps, int count, const int *off, const int *rows) {
+      return mvx_del_rows_many((mvx_prob *const *)Ps, count, off, rows);
+    } : nullptr,
 };
 
 } // namespace
@@ -3279,6 +3410,7 @@ void mvx_bnb_default_params(mvx_bnb_params *p) {
   p->cut_families = 0;
   p->cut_purge = 0;
   p->polish = 0;
+  p->node_purge = 0;
 }
 
 // Repaired mode's rule for an integer column whose bounds are not integers (legal input: LP and MPS files may carry them):
@@ -3687,7 +3819,10 @@ int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *
                                   params->cut_families < 0 || params->cut_families > 3 || params->cut_purge < 0 ||
                                   params->cut_purge > 64)) ||
       // polish: the repaired mode's incumbent; every single-GPU driver
-      params->polish < 0 || params->polish > 100000 || (params->polish > 0 && params->reference_quirks != 0)) {
+      params->polish < 0 || params->polish > 100000 || (params->polish > 0 && params->reference_quirks != 0) ||
+      // node_purge: the repaired mode's own cut rows (the bug-compatible pool re-adds its cuts); not (yet) in the best-bound window
+      params->node_purge < 0 || params->node_purge > 64 ||
+      (params->node_purge > 0 && (params->reference_quirks != 0 || params->best_window > 0))) {
     std::memset(res, 0, sizeof(*res));
     return -1;
   }
@@ -3927,6 +4062,19 @@ int mvx_bnb_cut_select(int k, const double *eff, const double *gram, int K, doub
   std::vector<int> got = cut_select(k, eff, gram, K, maxpar, budget);
   for (size_t i = 0; i < got.size(); i++) taken[i] = got[i];
   *ntaken = (int)got.size();
+  return 0;
+}
+
+int mvx_bnb_purge_ages(int k, const int *basic, int A, unsigned char *age, int *out, int *nout) {
+  if (k < 0 || A < 1 || A > 64 || !nout || (k > 0 && (!basic || !age || !out))) return -1;
+  int w = 0;
+  for (int t = 0; t < k; t++) {
+    if (age[t] == 255) continue; // a dead row
+    if (!basic[t]) age[t] = 0;
+    else if (age[t] < 254) age[t]++;
+    if (age[t] >= A) out[w++] = t;
+  }
+  *nout = w;
   return 0;
 }
 

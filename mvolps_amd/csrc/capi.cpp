@@ -185,24 +185,30 @@ int mvx_add_rows(mvx_prob *P, int nrs) {
   return first;
 }
 
-int mvx_del_rows(mvx_prob *P, int nrs, const int *num) {
-  if (!P || nrs < 1 || !num) return -1;
+// the rows num[0..nrs) of P, checked: 0 with `rows` the list in ascending order, -1 for a number out of range or a duplicate
+static int del_rows_check(const mvx_prob *P, int nrs, const int *num, std::vector<int> &rows) {
   const int m = P->m;
   std::vector<char> mark((size_t)m + 1, 0);
-  for (int k = 1; k <= nrs; k++) {
+  for (int k = 0; k < nrs; k++) {
     const int i = num[k];
     if (i < 1 || i > m || mark[(size_t)i]) return -1;
     mark[(size_t)i] = 1;
   }
-  std::vector<int> rows;
-  std::vector<size_t> idx;
+  rows.clear();
   rows.reserve((size_t)nrs);
-  idx.reserve((size_t)nrs);
+  for (int i = 1; i <= m; i++)
+    if (mark[(size_t)i]) rows.push_back(i);
+  return 0;
+}
+// the model edit of a checked deletion (`rows` ascending): the engine has not been told yet
+static void del_rows_model(mvx_prob *P, const std::vector<int> &rows) {
+  const int m = P->m;
+  std::vector<size_t> idx(rows.begin(), rows.end());
   int w = 0;
+  size_t d = 0;
   for (int i = 1; i <= m; i++) {
-    if (mark[(size_t)i]) {
-      rows.push_back(i);
-      idx.push_back((size_t)i);
+    if (d < rows.size() && rows[d] == i) {
+      d++;
       continue;
     }
     ++w;
@@ -215,8 +221,43 @@ int mvx_del_rows(mvx_prob *P, int nrs, const int *num) {
   P->rlb.resize((size_t)w + 1);
   P->rub.resize((size_t)w + 1);
   P->m = w;
+}
+
+int mvx_del_rows(mvx_prob *P, int nrs, const int *num) {
+  if (!P || nrs < 1 || !num) return -1;
+  const int m = P->m;
+  std::vector<int> rows;
+  if (del_rows_check(P, nrs, num + 1, rows) != 0) return -1;
+  del_rows_model(P, rows);
   mvx::engine_del_rows(P, rows, m);
   P->status = MVX_UNDEF;
+  return 0;
+}
+
+int mvx_del_rows_many(mvx_prob *const *Ps, int count, const int *off, const int *rows) {
+  if (!Ps || count < 1 || !off || off[0] != 0) return -1;
+  for (int t = 0; t < count; t++) {
+    if (!Ps[t] || off[t + 1] < off[t] || Ps[t]->n != Ps[0]->n) return -1;
+    for (int s = 0; s < t; s++)
+      if (Ps[s] == Ps[t]) return -1;
+  }
+  if (off[count] > 0 && !rows) return -1;
+  // every list is checked before the first handle is edited
+  std::vector<mvx_prob *> hs;
+  std::vector<std::vector<int>> lists;
+  std::vector<int> m_old;
+  for (int t = 0; t < count; t++) {
+    if (off[t + 1] == off[t]) continue; // not touched at all
+    std::vector<int> l;
+    if (del_rows_check(Ps[t], off[t + 1] - off[t], rows + off[t], l) != 0) return -1;
+    hs.push_back(Ps[t]);
+    lists.push_back(std::move(l));
+    m_old.push_back(Ps[t]->m);
+  }
+  if (hs.empty()) return 0;
+  for (size_t k = 0; k < hs.size(); k++) del_rows_model(hs[k], lists[k]);
+  mvx::engine_del_rows_many(hs.data(), (int)hs.size(), lists.data(), m_old.data());
+  for (mvx_prob *P : hs) P->status = MVX_UNDEF;
   return 0;
 }
 

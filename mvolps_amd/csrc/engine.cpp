@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
+#include <functional>
 #include <limits>
 #include <map>
 #include <mutex>
@@ -2238,35 +2239,73 @@ int engine_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rh
 // so a solve that follows takes no pivot.  The map goes up through the node entries' pinned block; nothing waits for the device
 // in front of the launch.  When a deleted row's auxiliary is non-basic, the column it holds cannot be dropped without a pivot:
 // the tableau is given up and the next solve starts from the slack basis.
-void engine_del_rows(mvx_prob *P, const std::vector<int> &rows, int m_old) {
-  if (P->dmat && rows.front() <= P->dmat->m0) P->dmat.reset();
-  if (P->rmod && rows.front() <= P->rmod->m0) P->rmod.reset();
-  if (!P->valid) return;
-  const int nrs = (int)rows.size(), n = P->n;
+// What a deletion does to one tableau, worked out on the host before anything is launched: `first` the first removed tableau
+// row, src[t] the source of destination row first + t, newpos the new place of every tableau row (0: removed).
+struct DelPlan {
+  int first = 0;
+  std::vector<int> src, newpos;
+};
+// false: a deleted row's auxiliary variable is non-basic (the plan is then not filled in)
+static bool del_plan(const mvx_prob *P, const std::vector<int> &rows, int m_old, DelPlan &pl) {
   std::vector<char> gone((size_t)m_old + 1, 0); // by tableau row
-  int first = m_old + 1;
+  pl.first = m_old + 1;
   for (int i : rows) {
     const int pos = P->pos[i];
-    if (pos <= 0) {
-      // the slab is kept (the out-of-memory path below gives it back): the next solve builds the slack tableau in it, so a
-      // recorded clone INTO it must land first
-      Context &c = ctx();
-      MAIN_LOCK(c);
-      flush_copies(c);
-      engine_invalidate(P);
-      return;
-    }
+    if (pos <= 0) return false;
     gone[(size_t)pos] = 1;
-    first = std::min(first, pos);
+    pl.first = std::min(pl.first, pos);
   }
-  std::vector<int> newpos((size_t)m_old + 1, 0); // tableau row -> its new place, 0 for a removed one
-  std::vector<int> src;
+  pl.newpos.assign((size_t)m_old + 1, 0);
+  pl.src.clear();
   for (int r = 1, w = 0; r <= m_old; r++) {
     if (gone[(size_t)r]) continue;
-    newpos[(size_t)r] = ++w;
-    if (r > first) src.push_back(r);
+    pl.newpos[(size_t)r] = ++w;
+    if (r > pl.first) pl.src.push_back(r);
   }
-  const int nmove = (int)src.size();
+  return true;
+}
+// the host side of a planned deletion: the mirrors take the kernel's compaction and renumbering, pending bound edits follow
+// their rows, and what the mirrors hold of the rows in front of the first removed one stays current
+static void del_mirrors(mvx_prob *P, const std::vector<int> &rows, int m_old, const DelPlan &pl) {
+  const int nrs = (int)rows.size(), n = P->n;
+  auto renumber = [&](int k) {
+    if (k > m_old) return k - nrs;
+    return k - (int)(std::lower_bound(rows.begin(), rows.end(), k) - rows.begin());
+  };
+  for (int r = 1; r <= m_old; r++)
+    if (pl.newpos[(size_t)r]) P->bvar[(size_t)pl.newpos[(size_t)r]] = renumber(P->bvar[(size_t)r]);
+  P->bvar.resize((size_t)P->m + 1);
+  for (int q = 1; q <= n; q++) P->nvar[(size_t)q] = renumber(P->nvar[(size_t)q]);
+  rebuild_pos(P);
+  // those of removed rows have nothing left to apply to
+  size_t w = 0;
+  for (const auto &e : P->pending)
+    if (pl.newpos[(size_t)e.row]) P->pending[w++] = {pl.newpos[(size_t)e.row], e.lb, e.ub};
+  P->pending.resize(w);
+  P->fresh_rows = P->sol_fresh ? pl.first - 1 : std::min(P->fresh_rows, pl.first - 1);
+  P->sol_fresh = false;
+  P->status = MVX_UNDEF;
+}
+static void del_drop_model_copies(mvx_prob *P, const std::vector<int> &rows) {
+  if (P->dmat && rows.front() <= P->dmat->m0) P->dmat.reset();
+  if (P->rmod && rows.front() <= P->rmod->m0) P->rmod.reset();
+}
+
+void engine_del_rows(mvx_prob *P, const std::vector<int> &rows, int m_old) {
+  del_drop_model_copies(P, rows);
+  if (!P->valid) return;
+  const int nrs = (int)rows.size(), n = P->n;
+  DelPlan pl;
+  if (!del_plan(P, rows, m_old, pl)) {
+    // the slab is kept (the out-of-memory path below gives it back): the next solve builds the slack tableau in it, so a
+    // recorded clone INTO it must land first
+    Context &c = ctx();
+    MAIN_LOCK(c);
+    flush_copies(c);
+    engine_invalidate(P);
+    return;
+  }
+  const int first = pl.first, nmove = (int)pl.src.size();
   NodeCall f(NodeFlush::AtEntry, NodeResults::None);
   const size_t o_src = f.up((size_t)std::max(1, nmove) * 4), o_del = f.up((size_t)nrs * 4);
   if (!f.reserve()) {
@@ -2274,7 +2313,7 @@ void engine_del_rows(mvx_prob *P, const std::vector<int> &rows, int m_old) {
     engine_invalidate(P);
     return;
   }
-  if (nmove) std::memcpy(f.hb + o_src, src.data(), (size_t)nmove * 4);
+  if (nmove) std::memcpy(f.hb + o_src, pl.src.data(), (size_t)nmove * 4);
   std::memcpy(f.hb + o_del, rows.data(), (size_t)nrs * 4);
   f.upload();
   DelRowsArgs a;
@@ -2285,26 +2324,86 @@ void engine_del_rows(mvx_prob *P, const std::vector<int> &rows, int m_old) {
   a.del = (const int *)(f.db + o_del);
   a.first = first; a.nmove = nmove; a.m_old = m_old; a.nrs = nrs; a.n = n; a.ld = P->ld;
   launch_delrows(a, f.stream());
-  // host mirrors: the same compaction and renumbering
-  auto renumber = [&](int k) {
-    if (k > m_old) return k - nrs;
-    return k - (int)(std::lower_bound(rows.begin(), rows.end(), k) - rows.begin());
-  };
-  for (int r = 1; r <= m_old; r++)
-    if (newpos[(size_t)r]) P->bvar[(size_t)newpos[(size_t)r]] = renumber(P->bvar[(size_t)r]);
-  P->bvar.resize((size_t)P->m + 1);
-  for (int q = 1; q <= n; q++) P->nvar[(size_t)q] = renumber(P->nvar[(size_t)q]);
-  rebuild_pos(P);
-  // pending bound edits follow their rows; those of removed rows have nothing left to apply to
-  size_t w = 0;
-  for (const auto &e : P->pending)
-    if (newpos[(size_t)e.row]) P->pending[w++] = {newpos[(size_t)e.row], e.lb, e.ub};
-  P->pending.resize(w);
-  // the rows in front of the first removed one sit where they sat: what the mirrors hold of those stays current
-  P->fresh_rows = P->sol_fresh ? first - 1 : std::min(P->fresh_rows, first - 1);
-  P->sol_fresh = false;
-  P->status = MVX_UNDEF;
+  del_mirrors(P, rows, m_old, pl); // host mirrors: the same compaction and renumbering
   f.fetch(); // the pinned block is free again
+}
+
+// engine_del_rows on `count` handles whose models have been edited (mvx_del_rows_many): handle t has lost rows[t] (ascending,
+// old numbers, not empty) of its m_old[t] rows.  Every handle ends as engine_del_rows leaves it, bit for bit; the device work
+// of all of them is one upload of [descriptors | src and del lists] and one k_delrows_many launch behind the recorded clones,
+// with no synchronise in front.  A handle without a tableau, or with a non-basic deleted row (tableau given up), takes no part
+// in the launch.  When the arena cannot be reserved for all of them the handles go in two halves, and so on down to a single
+// handle, which then ends as engine_del_rows' out-of-memory path leaves it.
+void engine_del_rows_many(mvx_prob *const *Ps, int count, const std::vector<int> *rows, const int *m_old) {
+  struct Item {
+    mvx_prob *P;
+    const std::vector<int> *rows;
+    int m_old;
+    DelPlan pl;
+  };
+  std::vector<Item> items;
+  for (int t = 0; t < count; t++) {
+    del_drop_model_copies(Ps[t], rows[t]);
+    if (Ps[t]->valid) items.push_back(Item{Ps[t], &rows[t], m_old[t], DelPlan()});
+  }
+  size_t w = 0;
+  for (size_t k = 0; k < items.size(); k++) {
+    if (!del_plan(items[k].P, *items[k].rows, items[k].m_old, items[k].pl)) {
+      Context &c = ctx(); // as in engine_del_rows: the slab is kept, a recorded clone INTO it must land first
+      MAIN_LOCK(c);
+      flush_copies(c);
+      engine_invalidate(items[k].P);
+      continue;
+    }
+    if (w != k) items[w] = std::move(items[k]);
+    w++;
+  }
+  items.resize(w);
+  const size_t GRID_Y = 65535;
+  // handles [lo, hi) in as few launches as the arena allows
+  std::function<void(size_t, size_t)> run = [&](size_t lo, size_t hi) {
+    if (hi <= lo) return;
+    if (hi - lo > GRID_Y) {
+      run(lo, lo + GRID_Y);
+      run(lo + GRID_Y, hi);
+      return;
+    }
+    NodeCall f(NodeFlush::AtEntry, NodeResults::None);
+    size_t ints = 0; // the lists of all handles lie back to back behind the descriptors: src, then del, handle by handle
+    for (size_t k = lo; k < hi; k++) ints += items[k].pl.src.size() + items[k].rows->size();
+    const size_t o_hs = f.up((hi - lo) * sizeof(DelManyDesc)), o_lists = f.up(std::max<size_t>(1, ints) * 4);
+    if (!f.reserve()) {
+      if (hi - lo == 1) {
+        release_device(items[lo].P);
+        engine_invalidate(items[lo].P);
+        return;
+      }
+      const size_t mid = lo + (hi - lo) / 2;
+      run(lo, mid);
+      run(mid, hi);
+      return;
+    }
+    DelManyDesc *hs = (DelManyDesc *)(f.hb + o_hs);
+    size_t o = o_lists;
+    int max_ld = 0;
+    for (size_t k = lo; k < hi; k++) {
+      const Item &it = items[k];
+      const mvx_prob *P = it.P;
+      const size_t nmove = it.pl.src.size(), nrs = it.rows->size();
+      const size_t o_src = o, o_del = o + nmove * 4;
+      if (nmove) std::memcpy(f.hb + o_src, it.pl.src.data(), nmove * 4);
+      std::memcpy(f.hb + o_del, it.rows->data(), nrs * 4);
+      o = o_del + nrs * 4;
+      hs[k - lo] = DelManyDesc{P->d_T, P->d_bvar, P->d_nvar, P->d_blb, P->d_bub, (unsigned long long)o_src, (unsigned long long)o_del,
+                               it.pl.first, (int)nmove, it.m_old, (int)nrs, P->n, P->ld};
+      max_ld = std::max(max_ld, P->ld);
+    }
+    f.upload();
+    launch_delrows_many((const DelManyDesc *)(f.db + o_hs), f.db, (int)(hi - lo), max_ld, f.stream());
+    for (size_t k = lo; k < hi; k++) del_mirrors(items[k].P, *items[k].rows, items[k].m_old, items[k].pl);
+    f.fetch(); // the pinned block is free again
+  };
+  run(0, items.size());
 }
 
 void engine_recompute_cost_row(mvx_prob *P) {

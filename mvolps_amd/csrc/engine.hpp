@@ -20,6 +20,8 @@ void engine_add_rows(mvx_prob *P, int first, int nrs); // P->m already updated
 // model rows `rows` (ascending, old numbers) are gone, P->m already updated, the mirrors still those of m_old rows; also drops
 // the device copies of the model that covered one of them (that part runs without a tableau)
 void engine_del_rows(mvx_prob *P, const std::vector<int> &rows, int m_old);
+// the same for `count` distinct handles (rows[t] not empty, m_old[t] handle t's row count before): one k_delrows_many launch
+void engine_del_rows_many(mvx_prob *const *Ps, int count, const std::vector<int> *rows, const int *m_old);
 void engine_row_from_model(mvx_prob *P, int i);      // row i's auxiliary is basic: rebuild its tableau row
 void engine_recompute_cost_row(mvx_prob *P);
 void engine_invalidate(mvx_prob *P); // drop device state; next solve starts from the slack basis

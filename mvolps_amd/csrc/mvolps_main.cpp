@@ -28,6 +28,9 @@ public:
 private:
   std::vector<std::string> tokens;
 };
+// --node-purge without a number (DESIGN.md "Cut purging in the tree (node_purge)": the smallest age limit of the CPU sweep
+// whose work is not above that of no purge on any of its sets)
+const long NODE_PURGE_DEFAULT = 1;
 } // namespace
 
 int main(int argc, char **argv) {
@@ -89,6 +92,8 @@ int main(int argc, char **argv) {
               << "                  row (1..64; 3 without a number)\n"
               << "  --polish [N]    with --repaired: every point that becomes the incumbent is first improved by a search over one- and\n"
               << "                  two-column unit moves, at most N of them (1..100000; 1000 without a number)\n"
+              << "  --node-purge [A] with --repaired, not with --best-window: a cut row leaves both children of a branching node once it\n"
+              << "                  has been slack at A branching nodes in a row on its path (1..64; 1 without a number)\n"
               << "Help:\n  -h/--help\n";
     return 0;
   }
@@ -238,6 +243,18 @@ int main(int argc, char **argv) {
       return -1;
     }
   }
+  if (input.CMDOptionExists("--node-purge")) {
+    // the number is optional, as for --cut-purge; what follows the flag and is neither a number nor the next flag is refused
+    const std::string &k = input.getCMDOption("--node-purge");
+    const bool numeric = !k.empty() && k.size() <= 3 && std::all_of(k.begin(), k.end(), [](char ch) { return ch >= '0' && ch <= '9'; });
+    const long kv = numeric ? std::strtol(k.c_str(), nullptr, 10) : NODE_PURGE_DEFAULT;
+    const bool absent = k.empty() || k[0] == '-'; // the next flag, or the end of the line
+    params.node_purge = (numeric || absent) && kv >= 1 && kv <= 64 ? (int)kv : -1;
+    if (params.node_purge < 1) {
+      std::fprintf(stderr, "Unknown parameter value for --node-purge\n");
+      return -1;
+    }
+  }
   if (input.CMDOptionExists("--cut-select")) params.cut_select = std::atoi(input.getCMDOption("--cut-select").c_str());
   if (input.CMDOptionExists("--window")) params.window = std::atoi(input.getCMDOption("--window").c_str());
   if (input.CMDOptionExists("--best-window")) params.best_window = std::atoi(input.getCMDOption("--best-window").c_str());
@@ -248,16 +265,16 @@ int main(int argc, char **argv) {
   mvx_bnb_result res;
   const int brc = mvx_branchAndBound(nullptr, prob, &params, &res);
   if (brc == -1) {
-    std::fprintf(stderr, "-vs %d / --heur %d%s%s%s%s%s%s are not supported with these options (-vs 3 / 4: not with --best-window; --heur: only "
-                 "with --repaired; --rcfix / --prop / --dive / --pump: only with --repaired and without --best-window; --cut-rounds / --polish: only with --repaired)\n",
+    std::fprintf(stderr, "-vs %d / --heur %d%s%s%s%s%s%s%s are not supported with these options (-vs 3 / 4: not with --best-window; --heur: only "
+                 "with --repaired; --rcfix / --prop / --dive / --pump / --node-purge: only with --repaired and without --best-window; --cut-rounds / --polish: only with --repaired)\n",
                  params.var_strat, params.heur, params.rc_fix ? " / --rcfix" : "", params.prop ? " / --prop" : "",
                  params.dive ? " / --dive" : "", params.pump ? " / --pump" : "", params.cut_rounds ? " / --cut-rounds" : "",
-                 params.polish ? " / --polish" : "");
+                 params.polish ? " / --polish" : "", params.node_purge ? " / --node-purge" : "");
     mvx_delete_prob(prob);
     return -1;
   }
   if (brc != 0)
-    std::fprintf(stderr, "branch-and-bound stopped: the branching penalties, the heuristic, the propagation, a pump, a dive, the root cut rounds or the polishing could not be computed (%d)\n", brc);
+    std::fprintf(stderr, "branch-and-bound stopped: the branching penalties, the heuristic, the propagation, a pump, a dive, the root cut rounds or the polishing could not be computed, or a purge could not be carried out (%d)\n", brc);
   if (input.CMDOptionExists("--events")) mvx_bnb_write_events(&res, input.getCMDOption("--events").c_str());
   mvx_bnb_print_tree(&res, nullptr); // bs.cpp:329-343
   std::vector<char> buf(64 + 64 * (size_t)res.n);
@@ -293,6 +310,9 @@ int main(int argc, char **argv) {
   if (verbose && params.polish > 0)
     std::printf("Incumbent polishing: %lld points, %lld moves, %lld came back better\n", res.polish_calls, res.polish_moves,
                 res.polish_improved);
+  if (verbose && params.node_purge > 0)
+    std::printf("Tree cut purging: %lld children purged, %lld rows removed, at most %lld live cut rows on a node\n", res.node_purge_calls,
+                res.node_purge_rows, res.node_cut_rows_peak);
   const int limit = res.hit_limit || brc != 0;
   mvx_bnb_free_result(&res);
   mvx_delete_prob(prob);

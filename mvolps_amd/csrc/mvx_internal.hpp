@@ -414,6 +414,15 @@ struct DelRowsArgs {
   const int *del; // [nrs]
   int first, nmove, m_old, nrs, n, ld;
 };
+// one handle of k_delrows_many (mvx_del_rows_many): DelRowsArgs with the two lists as byte offsets into the uploaded block that
+// holds the descriptors as well; nrs = 0 marks a handle the launch leaves alone
+struct DelManyDesc {
+  double *T;
+  int *bvar, *nvar;
+  double *blb, *bub;
+  unsigned long long o_src, o_del;
+  int first, nmove, m_old, nrs, n, ld;
+};
 
 // arguments of k_conflict_rows / k_conflict (mvx_conflict_graph): the model of one handle as k_prop reads it -- its rows by
 // column (At) and by row (Ar), the row bounds, the RND_INT flags and the handle's own column bounds -- the per-row numbers the
@@ -510,6 +519,7 @@ void launch_pumpobj(const PumpArgs &a, hipStream_t);
 void launch_cutgram(const CutGramArgs &a, hipStream_t);
 void launch_cutrows(const CutRowsArgs &a, hipStream_t);
 void launch_delrows(const DelRowsArgs &a, hipStream_t);
+void launch_delrows_many(const DelManyDesc *hs, const unsigned char *base, int handles, int max_ld, hipStream_t);
 void launch_conflict(const ConflictArgs &a, hipStream_t);
 void launch_lsact(const LsArgs &a, int final, hipStream_t);
 void launch_lsiter(const LsArgs &a, hipStream_t);

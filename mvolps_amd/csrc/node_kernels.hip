@@ -1171,9 +1171,10 @@ __device__ __forceinline__ int del_renumber(int k, const int *del, int nrs, int 
   return k - lo;
 }
 
-__global__ __launch_bounds__(64) void k_delrows(DelRowsArgs a) {
-  const int lane = TIDX;
-  const int j = (int)blockIdx.x * 64 + lane;
+// The work of one wave on one handle: the 64 columns of tile `tile`, and for tile 0 the basis arrays and the variable numbers.
+// k_delrows calls it with its own arguments, k_delrows_many with those of the handle its workgroup belongs to.
+__device__ __forceinline__ void delrows_wave(const DelRowsArgs &a, int tile, int lane) {
+  const int j = tile * 64 + lane;
   const size_t ld = (size_t)a.ld;
   const int first = a.first, nmove = a.nmove;
   if (j < a.ld) {
@@ -1197,7 +1198,7 @@ __global__ __launch_bounds__(64) void k_delrows(DelRowsArgs a) {
     }
     for (int i = first + nmove; i <= a.m_old; i++) Tj[(size_t)i * ld] = 0.0;
   }
-  if (blockIdx.x != 0) return;
+  if (tile != 0) return;
   const int nrs = a.nrs, m_old = a.m_old;
   for (int i = 1 + lane; i < first; i += 64) a.bvar[i] = del_renumber(a.bvar[i], a.del, nrs, m_old);
   for (int t0 = 0; t0 < nmove; t0 += 64) {
@@ -1220,8 +1221,37 @@ __global__ __launch_bounds__(64) void k_delrows(DelRowsArgs a) {
   for (int q = 1 + lane; q <= a.n; q += 64) a.nvar[q] = del_renumber(a.nvar[q], a.del, nrs, m_old);
 }
 
+__global__ __launch_bounds__(64) void k_delrows(DelRowsArgs a) { delrows_wave(a, (int)blockIdx.x, TIDX); }
+
 void launch_delrows(const DelRowsArgs &a, hipStream_t s) {
   hipLaunchKernelGGL(k_delrows, dim3((unsigned)((a.ld + 63) / 64)), dim3(64), 0, s, a);
+}
+
+// ---------------------------------------------------------------------------- k_delrows_many
+// The same deletion on many handles in one launch (mvx_del_rows_many, DESIGN.md "Cut purging in the tree (node_purge)"): the
+// grid is (column tiles of the widest handle, handles), a workgroup is one wave and owns 64 columns of ONE handle, which it
+// treats exactly as k_delrows treats them (delrows_wave).  hs[blockIdx.y] is the handle's descriptor -- k_delrows' arguments,
+// with its src and del lists given as byte offsets into the uploaded block `base` that holds the descriptors too -- read at
+// one address by the whole wave.  Handles differ in m, in ld and in how many rows move: a workgroup whose tile lies beyond its
+// handle's ld, or whose handle has nothing to delete, returns at once (the whole wave, so the barrier in delrows_wave is met
+// by all or by none).  Handles own disjoint slabs, and within a handle no two workgroups share a column: no atomics, no LDS, no
+// hand-off between workgroups.
+__global__ __launch_bounds__(64) void k_delrows_many(const DelManyDesc *__restrict__ hs, const unsigned char *__restrict__ base) {
+  const DelManyDesc &h = hs[blockIdx.y];
+  const int tile = (int)blockIdx.x;
+  if (h.nrs <= 0 || tile * 64 >= h.ld) return;
+  DelRowsArgs a;
+  a.T = h.T;
+  a.bvar = h.bvar; a.nvar = h.nvar;
+  a.blb = h.blb; a.bub = h.bub;
+  a.src = (const int *)(base + h.o_src);
+  a.del = (const int *)(base + h.o_del);
+  a.first = h.first; a.nmove = h.nmove; a.m_old = h.m_old; a.nrs = h.nrs; a.n = h.n; a.ld = h.ld;
+  delrows_wave(a, tile, TIDX);
+}
+
+void launch_delrows_many(const DelManyDesc *hs, const unsigned char *base, int handles, int max_ld, hipStream_t s) {
+  hipLaunchKernelGGL(k_delrows_many, dim3((unsigned)((max_ld + 63) / 64), (unsigned)handles), dim3(64), 0, s, hs, base);
 }
 
 // ---------------------------------------------------------------------------- k_conflict_rows / k_conflict
