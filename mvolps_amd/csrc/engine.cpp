@@ -1276,10 +1276,9 @@ static void job_enqueue(Context &c, SolveJob &J) {
             if (cl) chain_launch(steps);
             else
               for (int t = 0; t < steps; t++) launch_pstep(J.cargs, t, sc.stream);
-            ev(); // the profiled pair of events brackets the bulk pass alone
+            ev(); // the profiled pair of events brackets the bulk launch: the pass and, beside it, the chain's patch jobs
             launch_fbc3(J.cargs, steps, sc.stream);
             ev();
-            launch_fpatch(J.cargs, steps, sc.stream);
             left -= steps;
           }
           // a run that may end on the pivot limit: one more selection, which finds the limit and reports it

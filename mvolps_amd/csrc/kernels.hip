@@ -16,6 +16,7 @@
 // infrastructure); compiled with -ffp-contract=off so fma() appears exactly where written.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 
@@ -1911,8 +1912,8 @@ __global__ __launch_bounds__(256) void k_fb(Ctl *c) {
 //                flip of the entering variable: a step of its own kind); row p_g carried through the chain -> scaled
 //                pivot row; objective row, devex weights, statuses and bounds of the columns as the step leaves them;
 //                pricing partials for step g+1
-//   k_fbc3       the bulk pass: the plain multiply-adds of every step
-//   k_fpatch     the chain's pivot rows, pivot columns and column 0; the chain's bookkeeping
+//   k_fbc3       the bulk pass: tile blocks do the plain multiply-adds of every step, patch blocks write the chain's
+//                pivot rows, pivot columns and column 0; the first tile block does the chain's bookkeeping
 // What two rounds of in-kernel stamps taught (scripts/fcsdbg.py): a step is a chain of dependent
 // memory round trips, so (1) pointers, geometry and tolerances come by value (ChainArgs): every load whose address is
 // known on entry is requested on entry; (2) loads are unconditional -- indices are clamped, results masked -- because a
@@ -2126,7 +2127,7 @@ __global__ __launch_bounds__(256) void k_pc(const ChainArgs A, int g) {
     }
   }
   if (done != D_RUN || fstate != F_RUN) return;
-  if (lead && g == 0) c->pc_n = 0; // a new chain: nothing recorded yet (the bulk pass and k_fpatch apply pc_n steps)
+  if (lead && g == 0) c->pc_n = 0; // a new chain: nothing recorded yet (the tile and patch blocks of the bulk pass apply pc_n steps)
   if (g > 0 && okprev != epoch) return; // the chain ended before this step
   Cand key{m_q ? m_sc : 0.0, 0.0, m_q, lane};
   key = wave_bcast_best<0>(key);
@@ -2939,7 +2940,7 @@ __global__ __launch_bounds__(256) void k_chain(const ChainArgs A) {
 // (variable, bounds) between row p_t and column q_t.  The bounds need no exchange: the selection recorded what enters
 // row p_t (ch_elb / ch_eub) and what comes to sit in column q_t (ch_llb / ch_lub), so the last step that touches a row
 // or a column writes them; the variable numbers go through the swaps in LDS (one lane, no memory round trip per step),
-// lane t holding step t.  Nothing the bulk pass or k_fpatch reads is touched (they read the chain's record and pc_n).
+// lane t holding step t.  Nothing the tile or patch blocks of the bulk pass read is touched (they read the chain's record and pc_n).
 __device__ void chain_commit(const ChainArgs &A, Ctl *c, int nch) {
   __shared__ int s_cp[KCH], s_cq[KCH], s_ck[KCH], s_rf[KCH], s_cf[KCH], s_R[KCH], s_C[KCH];
   const int t = TIDX;
@@ -3010,76 +3011,252 @@ __device__ void chain_commit(const ChainArgs &A, Ctl *c, int nch) {
   }
 }
 
+// Beside the bulk pass, in the same launch (the patch blocks of k_fbc3): the chain's pivot rows and pivot columns (what
+// they hold after their own step does not depend on what they held before it: written from the chain's data and carried
+// through the steps that follow), column 0 (from its old values, which no tile block stores: bound flips move it) with
+// its contiguous copy.  Jobs: 0 .. K-1 the pivot row of step `job`, K .. 2K-1 the pivot column of step job - K, 2K
+// column 0; block xb of a job has its entries 256 xb .. 256 xb + 255.  An entry that two jobs cover gets the same value
+// from both.  The rules of the bulk update in full: the pivot row becomes -s_j (1/piv at the pivot, x_q - s_0 in column
+// 0), the pivot column c_i / piv, a bound flip moves column 0 only, everything else fma(-c_i, s_j, v).  Every operand
+// of every step is requested up front (the steps' descriptions and the operand that is the same for the whole job into
+// LDS, the other one into registers; the steps' descriptions come with the launch's verdict, lane t holding step t):
+// two memory round trips per block, not two per step.  Nothing read here is written
+// by a tile block and nothing written here is stored by one (they leave the pivot rows of the chain's pivots, their
+// pivot columns and column 0 alone), so the two kinds of block need no order between them.  The LDS is the kernel's.
+struct PatchLds {
+  int kind[KCH], p[KCH], q[KCH];
+  double piv[KCH], ip[KCH], xq[KCH], delta[KCH], u[KCH];
+};
+__device__ __forceinline__ void fbc3_patch(const ChainArgs &A, Ctl *c, int kmax, int job, int xb, PatchLds &L) {
+  // first round trip: the launch's verdict and the steps' descriptions, lane t of every wave holding step t (every
+  // address is known on entry; what lies behind the chain's last step is loaded and never used)
+  const int t32 = TIDX & (KCH - 1);
+  const int kind = c->ch_kind[t32], chp = c->ch_p[t32], chq = c->ch_q[t32];
+  const double piv = c->ch_piv[t32], xq = c->ch_xq[t32], delta = c->ch_delta[t32];
+  const int done = c->done, fstate = c->fstate, nch = c->pc_n;
+  if (done != D_RUN || fstate != F_RUN || nch <= 0) return;
+  const int m = A.m, n = A.n;
+  const size_t ld = (size_t)A.ld;
+  const int x = xb * 256 + TIDX;
+  // job kind 0: row p_l (x = column), 1: column q_l (x = row), 2: column 0 (x = row)
+  const int jk = (job < kmax) ? 0 : (job < 2 * kmax) ? 1 : 2;
+  const int l = (jk == 0) ? job : (jk == 1) ? job - kmax : -1;
+  const int lc = (l >= 0 && l < nch) ? l : 0;
+  bool live = (jk == 2) || (l < nch && __builtin_amdgcn_readlane(kind, lc) == ST_PIVOT);
+  const int span = (jk == 0) ? n : (jk == 1) ? m : A.mcap1 - 1;
+  if (xb * 256 > span) live = false; // nothing of this job in this block
+  if (!live) return;
+  const int lp = (l >= 0) ? __builtin_amdgcn_readlane(chp, lc) : 0, lq = (l >= 0) ? __builtin_amdgcn_readlane(chq, lc) : 0;
+  // second round trip: the operands and, for column 0, the entry itself
+  if (TIDX < KCH) {
+    const int t = (TIDX < nch) ? TIDX : nch - 1;
+    L.kind[TIDX] = kind;
+    L.p[TIDX] = chp;
+    L.q[TIDX] = chq;
+    L.piv[TIDX] = piv;
+    L.ip[TIDX] = (kind == ST_PIVOT) ? xdiv(1.0, piv) : 0.0;
+    L.xq[TIDX] = xq;
+    L.delta[TIDX] = delta;
+    // the operand every entry of the job shares: row job c_t[p_l]; column job s_t[q_l]; column 0 s_t[0]
+    L.u[TIDX] = (jk == 0) ? A.colq0[(size_t)t * A.cstride + lp] : A.srow0[(size_t)t * A.sstride + (jk == 1 ? lq : 0)];
+  }
+  const int xc = (x >= 1 && x <= span) ? x : 1;
+  double op[KCH]; // the other operand, per entry: row job s_t[x]; column jobs c_t[x]
+#pragma unroll
+  for (int t = 0; t < KCH; t++) {
+    const int tc = (t < nch) ? t : nch - 1;
+    op[t] = (jk == 0) ? A.srow0[(size_t)tc * A.sstride + xc] : A.colq0[(size_t)tc * A.cstride + xc];
+  }
+  double *dst = (jk == 0) ? A.T + (size_t)lp * ld + xc : A.T + (size_t)xc * ld + (jk == 1 ? lq : 0);
+  double val = (jk == 2) ? *dst : 0.0;
+  __syncthreads();
+  const int i = (jk == 0) ? lp : xc, j = (jk == 0) ? xc : (jk == 1) ? lq : 0;
+  const int l0 = (jk == 2) ? 0 : l;
+#pragma unroll
+  for (int t = 0; t < KCH; t++) {
+    if (t >= l0 && t < nch) {
+      const double ci = (jk == 0) ? L.u[t] : op[t], sj = (jk == 0) ? op[t] : L.u[t];
+      if (L.kind[t] == ST_FLIP) {
+        if (j == 0) val = fma(ci, L.delta[t], val);
+      } else if (i == L.p[t]) {
+        val = (j == L.q[t]) ? L.ip[t] : (j == 0) ? L.xq[t] - sj : -sj;
+      } else if (j == L.q[t]) {
+        val = xdiv(ci, L.piv[t]);
+      } else {
+        val = fma(-ci, sj, val);
+      }
+    }
+  }
+  if (x >= 1 && x <= span) {
+    if (jk != 2 || x <= m) *dst = val; // spare rows behind row m: their pivot-column entries are zero, the value stays
+    if (jk == 2) A.betab[x] = val;
+  }
+}
+
 // The bulk pass of a chain.  Every entry is loaded once, goes through the chain's steps in registers and is stored
-// once.  What a step needs besides the entry -- the pivot-column entries of the tile's rows -- is the same for every
-// lane: it comes in through scalar loads (constant address space: nothing in this launch writes it) and sits in SGPRs,
-// so there is no LDS staging and no barrier.  The loop body is 2 TR multiply-adds per lane and nothing else: a bound
-// flip runs them on zeros (fma(-0, 0, v) = v bit for bit), and the entries a step treats differently -- the pivot row
-// (becomes -s_j), the pivot column (c_i / piv), column 0 under a bound flip -- are not this kernel's business: what they
-// hold after their step does not depend on what they held before, so k_fpatch writes the chain's pivot rows, pivot
-// columns and column 0 afterwards from the chain's own data.  (With the exceptions inside this loop the compiler kept
-// two or three copies of the tile in registers and moved the tile between them every step: 210 VGPRs, 140 us for 16
-// steps; profiles/r03_*.)  Column 0 is never stored here: k_fpatch needs it as it was.
-typedef const double __attribute__((address_space(4))) *kconst_f64;
+// once.  What a step needs besides the entry is the same for a whole row or a whole column of the tile: the
+// pivot-column entries of the tile's rows are staged in LDS behind the launch's one barrier (one broadcast ds_read per
+// row and step), the pairs of the scaled pivot rows come in groups of FBG steps.  The loop body is 2 TR multiply-adds
+// per lane and nothing else: a bound flip runs them on zeros (fma(-0, 0, v) = v bit for bit, because BOTH operands are
+// zero), and the entries a step treats differently -- the pivot row (becomes -s_j), the pivot column (c_i / piv),
+// column 0 under a bound flip -- are not this kernel's business: what they hold after their step does not depend on
+// what they held before, so the patch blocks (fbc3_patch) write the chain's pivot rows, pivot columns and column 0 from the
+// chain's own data, and no tile block stores them.  (With the exceptions inside this loop the compiler kept two or three copies of the tile in
+// registers and moved the tile between them every step: 210 VGPRs, 140 us for 16 steps; profiles/r03_*.)  Column 0 is
+// never stored by a tile block: its patch job needs it as it was.
+// A wave of this kernel lives on memory round trips, so none of them may stand behind another one that it does not
+// depend on.  Loads retire in the order they were issued, hence the order of the requests: the steps' kinds (one
+// vector load, lane l holding step l; the flip mask is a ballot), the staging operands, the first two groups of row
+// pairs, and only then the tile -- the staging writes and the barrier wait on a counted vmcnt with the tile in flight.
+// From there two groups are in flight at any time: group g + 2 is requested before the multiply-adds of group g + 1,
+// into the registers group g has just left.  The first group is applied outside the loop: it is the one that waits for
+// the tile, and inside the loop that wait would drain the operand queue in every round.  Nothing in the loop stands
+// behind a condition (a load behind one makes every wait after it an uncounted one, a step behind one leaves its
+// operand pending): the chain's last group is filled up with steps on zeros, like bound flips, and a request past
+// the last group reads the zeros once more.  (Checked in the ISA: between the tile loads and the stores only the
+// last group waits for vmcnt(0).)
+constexpr int FBG = 4; // steps to a group of row pairs
+static_assert(KCH % FBG == 0, "whole groups: the last group's filling steps need rows of their own in the staging area");
+template <int TR>
+__device__ __forceinline__ void fbc3_apply(double2 (&v)[TR], const double2 (&s)[FBG], const double *cq, int l0) {
+#pragma unroll
+  for (int k = 0; k < FBG; k++) {
+#pragma unroll
+    for (int r = 0; r < TR; r++) {
+      // v = fma(-c_i, s_j, v) in place (an instruction with a tied operand: left to itself the compiler gives each
+      // step's results new registers and copies the whole tile back)
+      const double ci = cq[(l0 + k) * TR + r];
+      asm("v_fma_f64 %0, -%1, %2, %0" : "+v"(v[r].x) : "v"(ci), "v"(s[k].x));
+      asm("v_fma_f64 %0, -%1, %2, %0" : "+v"(v[r].y) : "v"(ci), "v"(s[k].y));
+    }
+  }
+}
+// The grid is one-dimensional and carries two kinds of block: tile blocks (tile t: column block t % ncb, row tile
+// t / ncb) and patch blocks (patch g: job g % (2 kmax + 1), entry block g / (2 kmax + 1)).  The patch blocks live on a
+// few dependent round trips and move little: in front they would hold every slot of the chip for their first
+// microseconds with no stream running, behind they would be a tail, so one of them follows every `every` tile blocks
+// (every = 0: fewer tiles than patch blocks, the tiles go first).
+struct BulkGrid {
+  int kmax, ncb, ntile, npatch, every;
+  int rev; // the row tiles are swept bottom to top (every other launch: what the last pass touched last is touched first)
+};
 template <int TR, int NT>
-__global__ __launch_bounds__(256) void k_fbc3(const ChainArgs A) {
-  __shared__ double s_cq[KCH][TR]; // the tile's rows of every step's pivot column (zeros for a bound flip)
+__global__ __launch_bounds__(256) void k_fbc3(const ChainArgs A, const BulkGrid G) {
+  // the tile's rows of every step's pivot column, [step][row] (zeros for a step that runs on zeros); every thread
+  // writes one or two entries, needed or not: a store behind a condition would take its load along, behind the tile
+  constexpr int NS = (KCH * TR + 255) / 256;
+  __shared__ double s_cq[NS * 256];
+  __shared__ PatchLds s_patch;
   Ctl *const c = A.c;
-  if (c->done != D_RUN || c->fstate != F_RUN) return;
-  const int nch = c->pc_n;
-  if (nch == 0) return;
+  int tile = -1, patch = -1; // which of the two kinds this block is: known without a load
+  {
+    const int b = (int)blockIdx.x;
+    if (G.every > 0) {
+      const int g = b / (G.every + 1), rm = b - g * (G.every + 1);
+      if (g >= G.npatch) tile = b - G.npatch;
+      else if (rm == G.every) patch = g;
+      else tile = g * G.every + rm;
+    } else if (b < G.ntile) {
+      tile = b;
+    } else {
+      patch = b - G.ntile;
+    }
+  }
+  if (patch >= 0) {
+    const int njobs = 2 * G.kmax + 1;
+    fbc3_patch(A, c, G.kmax, patch % njobs, patch / njobs, s_patch);
+    return;
+  }
+  // everything whose address is known on entry is requested together: one round trip, not one per field
+  const int kind = c->ch_kind[TIDX & (KCH - 1)], chp = c->ch_p[TIDX & (KCH - 1)], chq = c->ch_q[TIDX & (KCH - 1)];
+  const int done = c->done, fstate = c->fstate, nch = c->pc_n;
+  if (done != D_RUN || fstate != F_RUN || nch <= 0) return;
+  const int bx = tile % G.ncb, by = G.rev ? G.ntile / G.ncb - 1 - tile / G.ncb : tile / G.ncb;
   const int n = A.n;
   const size_t ld = (size_t)A.ld;
-  const int j0 = 2 * ((int)blockIdx.x * 256 + TIDX);
-  const int i0 = 1 + (int)blockIdx.y * TR;
+  const int j0 = 2 * (bx * 256 + TIDX);
+  const int i0 = 1 + by * TR;
   const int xf = nch & 1; // the set the chain's last step wrote
   const bool act = (j0 <= n);
   const int jc = act ? j0 : 0;
+  // the tile's pivot-column entries, one or two per thread: clamped, not skipped (masked when they are staged)
+  double cs[NS];
+#pragma unroll
+  for (int u = 0; u < NS; u++) {
+    const int e = TIDX + u * 256, ec = (e < nch * TR) ? e : 0;
+    cs[u] = A.colq0[(size_t)(ec / TR) * A.cstride + i0 + ec % TR];
+  }
+  // which steps run on zeros: the bound flips, and what the chain leaves of its last group -- so every group is a
+  // whole one and the loop below has no step of its own kind.  Known before any step's operands are requested.
+  const unsigned zsteps = (unsigned)__ballot((TIDX & 63) >= nch || kind == ST_FLIP);
+  // the pair of step l's scaled pivot row, or of the zeros: a uniform base and the lane's offset
+  const double *const srow = A.srow0 + jc;
+  const ptrdiff_t zrow = A.zeros - A.srow0, sstride = (ptrdiff_t)A.sstride;
+  auto rowpair = [&](int l) {
+    const int lk = (l < KCH) ? l : KCH - 1;
+    return *reinterpret_cast<const double2 *>(srow + (((zsteps >> lk) & 1u) ? zrow : lk * sstride));
+  };
+  double2 sa[FBG], sb[FBG];
+#pragma unroll
+  for (int k = 0; k < FBG; k++) sa[k] = rowpair(k);
+#pragma unroll
+  for (int k = 0; k < FBG; k++) sb[k] = rowpair(FBG + k);
   double *base = A.T + (size_t)i0 * ld + jc;
   double2 v[TR];
 #pragma unroll
   for (int r = 0; r < TR; r++) v[r] = ld2<NT>(reinterpret_cast<const double2 *>(base + (size_t)r * ld));
-  unsigned flips = 0; // which steps are bound flips: known before the loop, so no step waits for its own description
-  for (int l = 0; l < nch; l++) flips |= (c->ch_kind[l] == ST_FLIP) ? (1u << l) : 0u;
-  for (int e = TIDX; e < nch * TR; e += 256) {
-    const int l = e / TR, r = e % TR;
-    s_cq[l][r] = ((flips >> l) & 1u) ? 0.0 : A.colq0[(size_t)l * A.cstride + i0 + r];
+#pragma unroll
+  for (int u = 0; u < NS; u++) {
+    const int e = TIDX + u * 256;
+    s_cq[e] = ((zsteps >> ((e / TR) & (KCH - 1))) & 1u) ? 0.0 : cs[u];
+  }
+  // What the patch blocks own is not stored from here: the pivot rows of the chain's pivots (the same for the whole
+  // workgroup: one ballot per row of the tile), their pivot columns and column 0 (per lane; decided here, before the
+  // multiply-adds, and only in a wave that has a pivot column among its 128 columns).  A bound flip owns nothing.
+  const bool pivot = (TIDX & 63) < nch && kind == ST_PIVOT;
+  unsigned rowown = 0;
+#pragma unroll
+  for (int r = 0; r < TR; r++) rowown |= __ballot(pivot && chp == i0 + r) ? (1u << r) : 0u;
+  bool own_x = (j0 == 0), own_y = false; // the halves of the lane's pair that are not its to store
+  {
+    const int jw = 2 * (bx * 256 + (TIDX & ~63));
+    unsigned long long cm = __ballot(pivot && (unsigned)(chq - jw) < 128u);
+    while (cm) {
+      const int l = __ffsll((long long)cm) - 1;
+      cm &= cm - 1;
+      const int ql = __builtin_amdgcn_readlane(chq, l);
+      own_x |= (ql == j0);
+      own_y |= (ql == j0 + 1);
+    }
   }
   __syncthreads();
-  const double *sp = A.srow0 + jc;
-  const double *zp = A.zeros + jc;
-  // four steps to a group: the group's pairs of the scaled pivot rows are requested together, so that one memory round
-  // trip is paid per group and not per step
-  for (int l0 = 0; l0 < nch; l0 += 4) {
-    double2 s4[4];
+  fbc3_apply<TR>(v, sa, s_cq, 0);
+  // two groups a round and no way out between them (an exit there leaves a group requested and unused on a path
+  // that, for the compiler, leads back to the loop's head -- and the head then waits for everything); sb holds group l0
+  int l0 = FBG;
+  for (; l0 + FBG < nch; l0 += 2 * FBG) {
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const int lk = (l0 + k < nch) ? l0 + k : nch - 1;
-      s4[k] = *reinterpret_cast<const double2 *>(((flips >> lk) & 1u) ? zp : sp + (size_t)lk * A.sstride);
-    }
+    for (int k = 0; k < FBG; k++) sa[k] = rowpair(l0 + FBG + k);
+    fbc3_apply<TR>(v, sb, s_cq, l0);
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
-      if (l0 + k < nch) {
-#pragma unroll
-        for (int r = 0; r < TR; r++) {
-          // v = fma(-c_i, s_j, v) in place (an instruction with a tied operand: left to itself the compiler gives each
-          // step's results new registers and copies the whole tile back)
-          const double ci = s_cq[l0 + k][r];
-          asm("v_fma_f64 %0, -%1, %2, %0" : "+v"(v[r].x) : "v"(ci), "v"(s4[k].x));
-          asm("v_fma_f64 %0, -%1, %2, %0" : "+v"(v[r].y) : "v"(ci), "v"(s4[k].y));
-        }
-      }
-    }
+    for (int k = 0; k < FBG; k++) sb[k] = rowpair(l0 + 2 * FBG + k);
+    fbc3_apply<TR>(v, sa, s_cq, l0 + FBG);
   }
+  if (l0 < nch) fbc3_apply<TR>(v, sb, s_cq, l0);
   if (act) {
-    if (j0 == 0) {
+    if (!own_x && !own_y) {
 #pragma unroll
-      for (int r = 0; r < TR; r++) base[(size_t)r * ld + 1] = v[r].y;
+      for (int r = 0; r < TR; r++)
+        if (!((rowown >> r) & 1u)) st2<NT>(reinterpret_cast<double2 *>(base + (size_t)r * ld), v[r]);
     } else {
 #pragma unroll
-      for (int r = 0; r < TR; r++) st2<NT>(reinterpret_cast<double2 *>(base + (size_t)r * ld), v[r]);
+      for (int r = 0; r < TR; r++) {
+        if ((rowown >> r) & 1u) continue;
+        if (!own_x) base[(size_t)r * ld] = v[r].x;
+        if (!own_y) base[(size_t)r * ld + 1] = v[r].y;
+      }
     }
-    if (blockIdx.y == 0) { // the objective row and the weights live outside the row blocks: back to where the other paths read them
+    if (by == 0) { // the objective row and the weights live outside the row blocks: back to where the other paths read them
       *reinterpret_cast<double2 *>(A.T + j0) = *reinterpret_cast<const double2 *>(A.drowk[xf] + j0);
       const double2 w = *reinterpret_cast<const double2 *>(A.pwk[xf] + j0);
       *reinterpret_cast<double2 *>(A.pw[0] + j0) = w;
@@ -3087,81 +3264,7 @@ __global__ __launch_bounds__(256) void k_fbc3(const ChainArgs A) {
     }
   }
   // the first workgroup to be dispatched also commits the chain's bookkeeping, beside the rest of the pass
-  if (blockIdx.x == 0 && blockIdx.y == 0) chain_commit(A, c, nch);
-}
-
-// After the bulk pass: the chain's pivot rows and pivot columns (what they hold after their own step does not depend
-// on what they held before it: written from the chain's data and carried through the steps that follow), column 0 (from
-// its old values, which the bulk pass leaves alone: bound flips move it) with its contiguous copy.  Jobs (blockIdx.y): 0 .. K-1 the pivot row of step y, K .. 2K-1
-// the pivot column of step y - K, 2K column 0.  An entry that two jobs cover gets the same value from both.  The rules
-// of the bulk update in full: the pivot row becomes -s_j (1/piv at the pivot, x_q - s_0 in column 0), the pivot column
-// c_i / piv, a bound flip moves column 0 only, everything else fma(-c_i, s_j, v).  Every operand of every step is
-// requested up front (the steps' descriptions and the operand that is the same for the whole job into LDS, the other
-// one into registers): two memory round trips per launch, not two per step.
-__global__ __launch_bounds__(256) void k_fpatch(const ChainArgs A, int kmax) {
-  __shared__ int s_kind[KCH], s_p[KCH], s_q[KCH];
-  __shared__ double s_piv[KCH], s_ip[KCH], s_xq[KCH], s_delta[KCH], s_u[KCH];
-  Ctl *const c = A.c;
-  if (c->done != D_RUN || c->fstate != F_RUN) return;
-  const int nch = c->pc_n;
-  if (nch == 0) return;
-  const int m = A.m, n = A.n;
-  const size_t ld = (size_t)A.ld;
-  const int job = (int)blockIdx.y, x = (int)blockIdx.x * 256 + TIDX;
-  // job kind 0: row p_l (x = column), 1: column q_l (x = row), 2: column 0 (x = row)
-  const int jk = (job < kmax) ? 0 : (job < 2 * kmax) ? 1 : 2;
-  const int l = (jk == 0) ? job : (jk == 1) ? job - kmax : -1;
-  bool live = (jk == 2) || (l < nch && c->ch_kind[l < nch ? l : 0] == ST_PIVOT);
-  const int span = (jk == 0) ? n : (jk == 1) ? m : A.mcap1 - 1;
-  if ((int)blockIdx.x * 256 > span) live = false; // nothing of this job in this block
-  if (live) {
-    const int lp = (l >= 0) ? c->ch_p[l] : 0, lq = (l >= 0) ? c->ch_q[l] : 0;
-    if (TIDX < KCH) {
-      const int t = (TIDX < nch) ? TIDX : nch - 1;
-      const int kind = c->ch_kind[t];
-      const double piv = c->ch_piv[t];
-      s_kind[TIDX] = kind;
-      s_p[TIDX] = c->ch_p[t];
-      s_q[TIDX] = c->ch_q[t];
-      s_piv[TIDX] = piv;
-      s_ip[TIDX] = (kind == ST_PIVOT) ? xdiv(1.0, piv) : 0.0;
-      s_xq[TIDX] = c->ch_xq[t];
-      s_delta[TIDX] = c->ch_delta[t];
-      // the operand every entry of the job shares: row job c_t[p_l]; column job s_t[q_l]; column 0 s_t[0]
-      s_u[TIDX] = (jk == 0) ? A.colq0[(size_t)t * A.cstride + lp] : A.srow0[(size_t)t * A.sstride + (jk == 1 ? lq : 0)];
-    }
-    const int xc = (x >= 1 && x <= span) ? x : 1;
-    double op[KCH]; // the other operand, per entry: row job s_t[x]; column jobs c_t[x]
-#pragma unroll
-    for (int t = 0; t < KCH; t++) {
-      const int tc = (t < nch) ? t : nch - 1;
-      op[t] = (jk == 0) ? A.srow0[(size_t)tc * A.sstride + xc] : A.colq0[(size_t)tc * A.cstride + xc];
-    }
-    double *dst = (jk == 0) ? A.T + (size_t)lp * ld + xc : A.T + (size_t)xc * ld + (jk == 1 ? lq : 0);
-    double val = (jk == 2) ? *dst : 0.0;
-    __syncthreads();
-    const int i = (jk == 0) ? lp : xc, j = (jk == 0) ? xc : (jk == 1) ? lq : 0;
-    const int l0 = (jk == 2) ? 0 : l;
-#pragma unroll
-    for (int t = 0; t < KCH; t++) {
-      if (t >= l0 && t < nch) {
-        const double ci = (jk == 0) ? s_u[t] : op[t], sj = (jk == 0) ? op[t] : s_u[t];
-        if (s_kind[t] == ST_FLIP) {
-          if (j == 0) val = fma(ci, s_delta[t], val);
-        } else if (i == s_p[t]) {
-          val = (j == s_q[t]) ? s_ip[t] : (j == 0) ? s_xq[t] - sj : -sj;
-        } else if (j == s_q[t]) {
-          val = xdiv(ci, s_piv[t]);
-        } else {
-          val = fma(-ci, sj, val);
-        }
-      }
-    }
-    if (x >= 1 && x <= span) {
-      if (jk != 2 || x <= m) *dst = val; // spare rows behind row m: their pivot-column entries are zero, the value stays
-      if (jk == 2) A.betab[x] = val;
-    }
-  }
+  if (tile == 0) chain_commit(A, c, nch);
 }
 
 // ======================================================================= fused dual path
@@ -3858,22 +3961,33 @@ int launch_chain(const ChainArgs &a, hipStream_t s) {
   else hipLaunchKernelGGL((k_chain<1, 1>), dim3(8 * a.nw), dim3(256), lds, s, a);
   return 0;
 }
-void launch_fpatch(const ChainArgs &a, int steps, hipStream_t s) {
-  const int span = a.mcap1 > a.n + 1 ? a.mcap1 : a.n + 1;
-  hipLaunchKernelGGL(k_fpatch, dim3((span + 255) / 256, 2 * steps + 1), dim3(256), 0, s, a, steps);
-}
 void launch_fbc3(const ChainArgs &a, int steps, hipStream_t s) {
   const int m = a.m, n = a.n;
   const int pairs = (n + 2) / 2;
   int tr = pick_tr(m, n);
   if (tr > 16) tr = 16;
-  // long chains: shallower tiles, more waves to a SIMD to cover the per-step operand fetches (scripts/bulktime.py:
-  // 4096x8192, 32 steps: 117.7 us with 16-row tiles, 104.8 with 8; 10 steps: 82.3 / 81.6; one step: 76.1 / 79.6)
-  if (!g_tr && tr == 16 && steps >= 12) tr = 8;
+  // 8-row tiles at most: with the sweep alternating they are the faster ones at every chain length (scripts/bulktime.py,
+  // 4096x8192, pass and patch jobs, 8 rows against 16: one step 77.5 / 80.1 us, 4 steps 74.7 / 76.4, 10 steps 78.1 /
+  // 81.9, 16 steps 87.2 / 94.6, 32 steps 104.9 / 106.7; profiles/bulk_pass_*)
+  if (!g_tr && tr > 8) tr = 8;
   const int nt = pick_nt(m, n);
-  dim3 grid((pairs + 255) / 256, (m + tr - 1) / tr);
+  // tile blocks, and the patch blocks among them: 2 steps + 1 jobs (pivot rows, pivot columns, column 0) of
+  // ceil(span / 256) blocks each
+  const int span = a.mcap1 > n + 1 ? a.mcap1 : n + 1;
+  BulkGrid g;
+  g.kmax = steps;
+  g.ncb = (pairs + 255) / 256;
+  g.ntile = g.ncb * ((m + tr - 1) / tr);
+  g.npatch = (2 * steps + 1) * ((span + 255) / 256);
+  g.every = g.ntile / g.npatch;
+  // every other chained launch sweeps the row tiles bottom to top: a tableau just over the last-level cache's size is
+  // then met again, half of it, before the pass in between has pushed it out (4096x8192: 257 MiB; 32 steps 104.9 us
+  // against 113.9, 10 steps 78.1 against 82.1).  Not the passes of one or two steps: 77.5 us against 76.7 there.
+  static std::atomic<unsigned> launches{0};
+  g.rev = (steps >= 4) ? (int)(launches.fetch_add(1, std::memory_order_relaxed) & 1u) : 0;
+  const dim3 grid(g.ntile + g.npatch);
 #define FBC2_CASE(TR_, NT_) \
-  if (tr == TR_ && nt == NT_) { hipLaunchKernelGGL((k_fbc3<TR_, NT_>), grid, dim3(256), 0, s, a); return; }
+  if (tr == TR_ && nt == NT_) { hipLaunchKernelGGL((k_fbc3<TR_, NT_>), grid, dim3(256), 0, s, a, g); return; }
   FBC2_CASE(16, 0) FBC2_CASE(16, 1) FBC2_CASE(16, 2) FBC2_CASE(8, 0) FBC2_CASE(8, 1) FBC2_CASE(8, 2) FBC2_CASE(4, 0) FBC2_CASE(4, 1) FBC2_CASE(4, 2)
 #undef FBC2_CASE
   std::abort(); // unreachable

@@ -123,9 +123,9 @@ struct Ctl {
   double ch_llb[KCH], ch_lub[KCH]; // bounds of the leaving variable (become column q's)
   double *srowk[KCH], *colqk[KCH]; // scaled pivot row / pivot column of step l
   // Chained primal path (k_pboot / k_pc / k_pr / k_fbc3): what the device decides about the pending chain
-  int pc_n;        // steps recorded in the pending chain (k_fbc3 applies them and resets it)
+  int pc_n;        // steps recorded in the pending chain (k_fbc3 applies them; the next selection starts from 0)
   int pc_epoch;    // chains applied so far + 1
-  unsigned pc_arrive; // k_fbc3: workgroups that have finished (the last one commits the chain's bookkeeping)
+  unsigned pc_arrive; // unused: the first tile block of k_fbc3 commits the chain's bookkeeping, no arrival is counted
   int ch_kind[KCH], ch_cnt[KCH], ch_ok[KCH]; // ST_PIVOT / ST_FLIP; pivots among steps 0..l; == pc_epoch once step l is recorded
   int ch_okc[KCH];  // == pc_epoch once k_pc has chosen step l's entering column
   int hd_q[KCH], hd_sdir[KCH], hd_fq[KCH]; // the entering column of step l as k_pc found it: column, direction, status,
@@ -163,7 +163,7 @@ struct ChainArgs {
   int m, n, ld, mcap1, ncb, nrb; // ncb column blocks (k_pr), nrb row blocks (k_pc)
   double tol_dj, tol_piv, tol_bnd, sgn;
   int stall_limit;
-  const double *zeros; // max(ld, m_cap + 1) zeros: the operands of a bound flip in the bulk pass
+  const double *zeros; // max(ld, m_cap + 1) zeros: the operands of a bound flip, and of what fills the chain's last group of steps, in the bulk pass
   // one-XCD cluster selection (k_chain): exchange area, tags, participants, steps this launch may take
   unsigned *xg;
   int xg_bytes;
@@ -491,7 +491,6 @@ void launch_pboot(const ChainArgs &, hipStream_t);
 void launch_pstep(const ChainArgs &, int g, hipStream_t);
 void launch_pc(const ChainArgs &, int g, hipStream_t);
 void launch_fbc3(const ChainArgs &, int steps, hipStream_t);
-void launch_fpatch(const ChainArgs &, int steps, hipStream_t);
 int launch_chain(const ChainArgs &, hipStream_t);
 int chain_cluster_nw(int m, int n);
 int chain_cluster_kmax(int m, int n);
