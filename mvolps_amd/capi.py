@@ -234,6 +234,12 @@ class Prob:
     def row_prim(self):
         return np.array([self.api.get_row_prim(self.h, i) for i in range(1, self.m + 1)])
 
+    def col_dual(self):
+        return np.array([self.api.get_col_dual(self.h, j) for j in range(1, self.n + 1)])
+
+    def row_dual(self):
+        return np.array([self.api.get_row_dual(self.h, i) for i in range(1, self.m + 1)])
+
     def col_stat(self):
         return np.array([self.api.get_col_stat(self.h, j) for j in range(1, self.n + 1)], dtype=np.int32)
 

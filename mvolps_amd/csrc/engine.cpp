@@ -76,6 +76,18 @@ struct Carver {
   }
 };
 
+// Names a buffer's pieces once for both passes over them: piece(p, count) carves count elements of p's type and, given
+// the allocation's base, points p at them; with a null base the walk only measures (carve.off is the total).
+struct Pieces {
+  unsigned char *base;
+  Carver carve;
+  template <class T>
+  void operator()(T *&p, size_t count) {
+    const size_t o = carve(count * sizeof(T));
+    if (base) p = (T *)(base + o);
+  }
+};
+
 // ------------------------------------------------------------------------------ context
 // One solve context = one HIP stream with its own control block, scratch and staging.  The main
 // context serves every single-handle call; mvx_simplex_batch has its own (BatchCtx below).
@@ -382,8 +394,37 @@ public:
 // the common part of a node-entry descriptor
 static NodeRef node_ref(const mvx_prob *P) { return NodeRef{P->d_T, P->d_bvar, P->d_nvar, P->d_nflag, P->d_nlb, P->d_nub, P->m, P->ld}; }
 
-static size_t stage_size(int m_cap, int ld) {
-  return align_up(sizeof(Ctl) + (size_t)(m_cap + 1) * 8 + (size_t)ld * 8 + (size_t)(m_cap + 1) * 4 + (size_t)ld * 8, 256);
+// every piece of a solve context's scratch, in layout order (see Pieces), and the strides of the two partial arrays, which
+// size their pieces; returns the bytes of the whole
+static size_t scratch_pieces(SolveCtx &sc, int mc, int l, unsigned char *base) {
+  const size_t row = (size_t)mc + 1, col = (size_t)l, var = (size_t)mc + l + 1; // per tableau row / column / variable number
+  const int nchunks = (mc + ROWCOMB_CHUNK - 1) / ROWCOMB_CHUNK + 1;
+  Pieces piece{base};
+  piece(sc.d_colq, row), piece(sc.d_srow, col), piece(sc.d_cost1, col);
+  piece(sc.d_wts, row), piece(sc.d_rcbase, col), piece(sc.d_gflag, row);
+  piece(sc.d_part, (size_t)nchunks * l);
+  piece(sc.d_colqx[0], row), piece(sc.d_colqx[1], row);
+  piece(sc.d_betac[0], row), piece(sc.d_betac[1], row);
+  piece(sc.d_pp[0], (size_t)fused_npb(l)), piece(sc.d_pp[1], (size_t)fused_npb(l));
+  piece(sc.d_rp, (size_t)fused_nrb_max(mc));
+  piece(sc.d_olb, var), piece(sc.d_oub, var);
+  piece(sc.d_dw, row), piece(sc.d_dw2, row);
+  piece(sc.d_p1list, row + 1);
+  piece(sc.d_pw[0], col), piece(sc.d_pw[1], col);
+  piece(sc.d_tflag, var);
+  piece(sc.d_rpc, (size_t)(mc + 255) / 256 + 1);
+  for (int k = 0; k < KCH; k++) piece(sc.d_srowk[k], col);
+  for (int k = 0; k < KCH; k++) piece(sc.d_colqk[k], row);
+  for (int k = 0; k < 2; k++) {
+    piece(sc.d_drowk[k], col), piece(sc.d_pwk[k], col), piece(sc.d_nlbk[k], col), piece(sc.d_nubk[k], col);
+    piece(sc.d_nflagk[k], 2 * col); // as wide as its neighbours of doubles
+    piece(sc.d_betak[k], row), piece(sc.d_blbk[k], row), piece(sc.d_bubk[k], row);
+  }
+  sc.pp_stride = align_up((size_t)chain_ncb(l) + 1, 32);
+  sc.rp_stride = align_up((size_t)chain_nrb(mc) + 1, 32);
+  piece(sc.d_betab, row), piece(sc.d_ppart, 8 * sc.pp_stride), piece(sc.d_rpart, 4 * sc.rp_stride);
+  piece(sc.d_zeros, std::max(col, row) + 32);
+  return piece.carve.off;
 }
 
 static void ensure_scratch(SolveCtx &sc, int m_cap, int ld) {
@@ -395,81 +436,13 @@ static void ensure_scratch(SolveCtx &sc, int m_cap, int ld) {
   if (sc.d_stage && !sc.stage_zc) HIPCHECK(hipFree(sc.d_stage));
   if (sc.h_stage) HIPCHECK(hipHostFree(sc.h_stage));
   sc.d_stage = nullptr;
-  const int nchunks = (mc + ROWCOMB_CHUNK - 1) / ROWCOMB_CHUNK + 1;
-  Carver carve;
-  size_t o_colq =carve((size_t)(mc + 1) * 8), o_srow = carve((size_t)l * 8), o_cost1 = carve((size_t)l * 8);
-  size_t o_wts = carve((size_t)(mc + 1) * 8), o_rcb = carve((size_t)l * 8), o_g = carve((size_t)(mc + 1) * 4);
-  size_t o_part = carve((size_t)nchunks * l * 8);
-  size_t o_cx0 = carve((size_t)(mc + 1) * 8), o_cx1 = carve((size_t)(mc + 1) * 8);
-  size_t o_bc0 = carve((size_t)(mc + 1) * 8), o_bc1 = carve((size_t)(mc + 1) * 8);
-  size_t o_pp0 = carve((size_t)fused_npb(l) * sizeof(Cand)), o_pp1 = carve((size_t)fused_npb(l) * sizeof(Cand));
-  size_t o_rp = carve((size_t)fused_nrb_max(mc) * sizeof(Cand));
-  size_t o_olb = carve((size_t)(mc + l + 1) * 8), o_oub = carve((size_t)(mc + l + 1) * 8);
-  size_t o_dw = carve((size_t)(mc + 1) * 8), o_dw2 = carve((size_t)(mc + 1) * 8);
-  size_t o_p1l = carve((size_t)(mc + 2) * 4);
-  size_t o_pw0 = carve((size_t)l * 8), o_pw1 = carve((size_t)l * 8);
-  size_t o_tf = carve((size_t)(mc + l + 1) * 4);
-  size_t o_sk[KCH], o_ck[KCH];
-  size_t o_rpc = carve((size_t)((mc + 255) / 256 + 1) * sizeof(Cand));
-  for (int k = 0; k < KCH; k++) o_sk[k] = carve((size_t)l * 8);
-  for (int k = 0; k < KCH; k++) o_ck[k] = carve((size_t)(mc + 1) * 8);
-  size_t o_colset[2][5], o_rowset[2][3];
-  for (int k = 0; k < 2; k++) {
-    for (int f = 0; f < 5; f++) o_colset[k][f] = carve((size_t)l * 8);
-    for (int f = 0; f < 3; f++) o_rowset[k][f] = carve((size_t)(mc + 1) * 8);
-  }
-  const size_t pps = align_up((size_t)chain_ncb(l) + 1, 32), rps = align_up((size_t)chain_nrb(mc) + 1, 32);
-  const size_t o_betab = carve((size_t)(mc + 1) * 8), o_ppart = carve(8 * pps * 8), o_rpart = carve(4 * rps * 8);
-  const size_t o_zeros = carve((size_t)std::max(l, mc + 1) * 8 + 256);
-  HIPCHECK(hipMalloc(&sc.scratch, carve.off));
-  HIPCHECK(hipMemsetAsync(sc.scratch, 0, carve.off, sc.stream));
-  unsigned char *b = (unsigned char *)sc.scratch;
-  sc.d_colq = (double *)(b + o_colq);
-  sc.d_srow = (double *)(b + o_srow);
-  sc.d_cost1 = (double *)(b + o_cost1);
-  sc.d_wts = (double *)(b + o_wts);
-  sc.d_rcbase = (double *)(b + o_rcb);
-  sc.d_gflag = (int *)(b + o_g);
-  sc.d_part = (double *)(b + o_part);
-  sc.d_colqx[0] = (double *)(b + o_cx0);
-  sc.d_colqx[1] = (double *)(b + o_cx1);
-  sc.d_betac[0] = (double *)(b + o_bc0);
-  sc.d_betac[1] = (double *)(b + o_bc1);
-  sc.d_pp[0] = (Cand *)(b + o_pp0);
-  sc.d_pp[1] = (Cand *)(b + o_pp1);
-  sc.d_rp = (Cand *)(b + o_rp);
-  sc.d_olb = (double *)(b + o_olb);
-  sc.d_oub = (double *)(b + o_oub);
-  sc.d_dw = (double *)(b + o_dw);
-  sc.d_dw2 = (double *)(b + o_dw2);
-  sc.d_p1list = (int *)(b + o_p1l);
-  sc.d_pw[0] = (double *)(b + o_pw0);
-  sc.d_pw[1] = (double *)(b + o_pw1);
-  sc.d_tflag = (int *)(b + o_tf);
-  sc.d_rpc = (Cand *)(b + o_rpc);
-  for (int k = 0; k < KCH; k++) {
-    sc.d_srowk[k] = (double *)(b + o_sk[k]);
-    sc.d_colqk[k] = (double *)(b + o_ck[k]);
-  }
-  for (int k = 0; k < 2; k++) {
-    sc.d_drowk[k] = (double *)(b + o_colset[k][0]);
-    sc.d_pwk[k] = (double *)(b + o_colset[k][1]);
-    sc.d_nlbk[k] = (double *)(b + o_colset[k][2]);
-    sc.d_nubk[k] = (double *)(b + o_colset[k][3]);
-    sc.d_nflagk[k] = (int *)(b + o_colset[k][4]);
-    sc.d_betak[k] = (double *)(b + o_rowset[k][0]);
-    sc.d_blbk[k] = (double *)(b + o_rowset[k][1]);
-    sc.d_bubk[k] = (double *)(b + o_rowset[k][2]);
-  }
-  sc.d_betab = (double *)(b + o_betab);
-  sc.d_ppart = (double *)(b + o_ppart);
-  sc.d_rpart = (double *)(b + o_rpart);
-  sc.d_zeros = (double *)(b + o_zeros);
-  sc.pp_stride = pps;
-  sc.rp_stride = rps;
-  sc.sk_stride = (o_sk[1] - o_sk[0]) / 8;
-  sc.ck_stride = (o_ck[1] - o_ck[0]) / 8;
-  sc.stage_bytes = stage_size(mc, l);
+  const size_t bytes = scratch_pieces(sc, mc, l, nullptr);
+  HIPCHECK(hipMalloc(&sc.scratch, bytes));
+  HIPCHECK(hipMemsetAsync(sc.scratch, 0, bytes, sc.stream));
+  scratch_pieces(sc, mc, l, (unsigned char *)sc.scratch);
+  sc.sk_stride = (size_t)(sc.d_srowk[1] - sc.d_srowk[0]);
+  sc.ck_stride = (size_t)(sc.d_colqk[1] - sc.d_colqk[0]);
+  sc.stage_bytes = StageView::bytes(mc, l);
   HIPCHECK(hipHostMalloc((void **)&sc.h_stage, sc.stage_bytes));
   {
     static int zc = -1;
@@ -772,8 +745,9 @@ static bool cluster_wanted() {
   return v != 0 && !g_cluster_broken.load();
 }
 
-// Steps per bulk launch of the chained primal path.  A step costs one small launch (k_fcs), a pass over the tableau
-// costs its bytes: chains pay at every size, the longer the pass the longer the chain (scripts/chainsweep.py).
+// Steps per bulk launch of the chained primal path.  A step costs two small launches (k_pc / k_pr) or its share of one
+// k_chain launch, a pass over the tableau costs its bytes: chains pay at every size, the longer the pass the longer the
+// chain (scripts/chainsweep.py).
 // MVX_CHAIN=1 turns the chaining off, 2..KCH fixes the length.
 static int g_chain = -1;
 static int chain_length(const mvx_prob *P) {
@@ -806,18 +780,35 @@ static int dual_chain_length(bool wide, bool on_chip = false) {
   return wide ? 8 : 4;
 }
 
-static void fill_ctl(SolveCtx &sc, mvx_prob *P, Ctl *h) {
+// No limit asked for: a safety cap stands in (belt and braces behind the anti-cycling rule; a stalled
+// degenerate LP must end with EITLIM rather than spin on the device).  Same formula as the oracle.
+static int pivot_budget(const mvx_prob *P, const mvx_smcp &parm) {
+  return parm.it_lim >= 0 ? parm.it_lim : 200 * (P->m + P->n) + 100000;
+}
+
+// The handle's part of a fresh control block, the same for a single solve (fill_ctl) and a job of a batch (batch_fill_job):
+// everything else is zero, the scratch pointers and chain lengths are the caller's.
+static void ctl_for_handle(Ctl *h, const mvx_prob *P, double tol_bnd, double tol_dj, double tol_piv, int budget) {
   std::memset(h, 0, sizeof(Ctl));
   h->T = P->d_T;
   h->bvar = P->d_bvar; h->blb = P->d_blb; h->bub = P->d_bub;
   h->nvar = P->d_nvar; h->nflag = P->d_nflag; h->nlb = P->d_nlb; h->nub = P->d_nub;
-  h->colq = sc.d_colq; h->srow = sc.d_srow; h->cost1 = sc.d_cost1; h->wts = sc.d_wts;
-  h->gflag = sc.d_gflag; h->part = sc.d_part; h->rc_base = nullptr; h->rc_out = sc.d_cost1;
   h->m = P->m; h->n = P->n; h->ld = P->ld; h->m_cap = P->m_cap;
   h->sgn = (P->dir == MVX_MAX) ? 1.0 : -1.0;
-  h->tol_bnd = 1e-9; h->tol_dj = 1e-9; h->tol_piv = 1e-9;
-  h->phase = PH_START; h->done = D_RUN; h->budget = -1;
+  h->tol_bnd = tol_bnd; h->tol_dj = tol_dj; h->tol_piv = tol_piv;
+  h->phase = PH_START; h->done = D_RUN; h->budget = budget;
   h->stall = 0; h->stall_limit = g_stall_limit > 0 ? g_stall_limit : 64 + (P->m + P->n) / 8;
+  h->fstate = F_OFF;
+  h->nch = 1;
+}
+
+// control block of a launch sequence on `sc`.  Without parm (mirror exports, tableau refresh, model edits): tolerances 1e-9,
+// no pivot budget
+static void fill_ctl(SolveCtx &sc, mvx_prob *P, Ctl *h, const mvx_smcp *parm = nullptr) {
+  if (parm) ctl_for_handle(h, P, parm->tol_bnd, parm->tol_dj, parm->tol_piv, pivot_budget(P, *parm));
+  else ctl_for_handle(h, P, 1e-9, 1e-9, 1e-9, -1);
+  h->colq = sc.d_colq; h->srow = sc.d_srow; h->cost1 = sc.d_cost1; h->wts = sc.d_wts;
+  h->gflag = sc.d_gflag; h->part = sc.d_part; h->rc_base = nullptr; h->rc_out = sc.d_cost1;
   h->olb = sc.d_olb; h->oub = sc.d_oub; h->dw = sc.d_dw;
   h->dwx[0] = sc.d_dw; h->dwx[1] = sc.d_dw2;
   h->pw[0] = sc.d_pw[0]; h->pw[1] = sc.d_pw[1];
@@ -826,7 +817,6 @@ static void fill_ctl(SolveCtx &sc, mvx_prob *P, Ctl *h) {
   h->betac[0] = sc.d_betac[0]; h->betac[1] = sc.d_betac[1];
   h->pp[0] = sc.d_pp[0]; h->pp[1] = sc.d_pp[1]; h->rp = sc.d_rp;
   h->npb = fused_npb(P->n); h->nrb = 0; // nrb is published by k_fb (its grid height)
-  h->fstate = F_OFF;
   for (int k = 0; k < KCH; k++) {
     h->srowk[k] = sc.d_srowk[k];
     h->colqk[k] = sc.d_colqk[k];
@@ -848,7 +838,6 @@ static void fill_ctl(SolveCtx &sc, mvx_prob *P, Ctl *h) {
   h->rpc = sc.d_rpc;
   h->chain_max = chain_length(P);
   h->dchain_max = dual_chain_length((size_t)(P->m + 1) * (size_t)P->ld * 8 >= ((size_t)16 << 20), P->m <= 1024 && P->n <= 1024);
-  h->nch = 1;
 }
 
 // the handle's pending bound edits ride in the control block of the solve that is about to start
@@ -872,25 +861,23 @@ static void upload_ctl(SolveCtx &sc) {
   HIPCHECK(hipMemcpyAsync(sc.d_ctl, sc.h_ctl, sizeof(Ctl), hipMemcpyHostToDevice, sc.stream));
 }
 
-// copy the staging buffer back and refresh the host mirrors
-static void pull_stage(SolveCtx &sc, mvx_prob *P, bool mirrors) {
-  if (!sc.stage_zc) HIPCHECK(hipMemcpyAsync(sc.h_stage, sc.d_stage, stage_size(P->m_cap, P->ld), hipMemcpyDeviceToHost, sc.stream));
-  HIPCHECK(hipStreamSynchronize(sc.stream));
-  if (!mirrors) return;
-  const unsigned char *s = sc.h_stage;
-  const double *beta = (const double *)(s + sizeof(Ctl));
-  const double *dj = beta + (P->m_cap + 1);
-  const int *bv = (const int *)(dj + P->ld);
-  const int *nv = bv + (P->m_cap + 1);
-  const int *nf = nv + P->ld;
-  P->beta.assign(beta, beta + P->m + 1);
-  P->dj.assign(dj, dj + P->n + 1);
-  P->bvar.assign(bv, bv + P->m + 1);
-  P->nvar.assign(nv, nv + P->n + 1);
-  P->nflag.assign(nf, nf + P->n + 1);
+// the basis / solution mirrors an export packed into a staging area become the handle's
+static void publish_mirrors(mvx_prob *P, const StageView &v) {
+  P->beta.assign(v.beta, v.beta + P->m + 1);
+  P->dj.assign(v.dj, v.dj + P->n + 1);
+  P->bvar.assign(v.bvar, v.bvar + P->m + 1);
+  P->nvar.assign(v.nvar, v.nvar + P->n + 1);
+  P->nflag.assign(v.nflag, v.nflag + P->n + 1);
   rebuild_pos(P);
   P->sol_fresh = true;
   P->fresh_rows = -1;
+}
+
+// copy the staging buffer back and refresh the host mirrors
+static void pull_stage(SolveCtx &sc, mvx_prob *P, bool mirrors) {
+  if (!sc.stage_zc) HIPCHECK(hipMemcpyAsync(sc.h_stage, sc.d_stage, StageView::bytes(P->m_cap, P->ld), hipMemcpyDeviceToHost, sc.stream));
+  HIPCHECK(hipStreamSynchronize(sc.stream));
+  if (mirrors) publish_mirrors(P, StageView(sc.h_stage, P->m_cap, P->ld));
 }
 
 void refresh_solution(const mvx_prob *Pc) {
@@ -1042,7 +1029,7 @@ static bool persist_plan(Context &c, const mvx_prob *P, PersistPlan *pl) {
   return pl->lds <= (size_t)150 * 1024;
 }
 
-static bool ensure_persist(Context &c, SolveCtx &sc, const mvx_prob *P, const PersistPlan &pl) {
+static bool ensure_persist(Context &c, SolveCtx &sc, const mvx_prob *P) {
   const int words = persist_slot_words(P->m_cap);
   if (!sc.d_pabort) {
     HIPCHECK(hipMalloc((void **)&sc.d_pabort, 1024));
@@ -1073,7 +1060,6 @@ static bool ensure_persist(Context &c, SolveCtx &sc, const mvx_prob *P, const Pe
       return false;
     }
   }
-  (void)pl;
   return true;
 }
 
@@ -1098,15 +1084,9 @@ struct SolveJob {
   Ctl snap;
 };
 
-// No limit asked for: a safety cap stands in (belt and braces behind the anti-cycling rule; a stalled
-// degenerate LP must end with EITLIM rather than spin on the device).  Same formula as the oracle.
-static int pivot_budget(const mvx_prob *P, const mvx_smcp &parm) {
-  return parm.it_lim >= 0 ? parm.it_lim : 200 * (P->m + P->n) + 100000;
-}
-
 static void stage_copy_async(SolveCtx &sc, const mvx_prob *P) {
   HIPCHECK(hipEventRecord(sc.ev_b, sc.stream)); // end of the device work queued so far (last_solve_ms)
-  if (!sc.stage_zc) HIPCHECK(hipMemcpyAsync(sc.h_stage, sc.d_stage, stage_size(P->m_cap, P->ld), hipMemcpyDeviceToHost, sc.stream));
+  if (!sc.stage_zc) HIPCHECK(hipMemcpyAsync(sc.h_stage, sc.d_stage, StageView::bytes(P->m_cap, P->ld), hipMemcpyDeviceToHost, sc.stream));
   if (sc.d_pabort) HIPCHECK(hipMemcpyAsync(sc.h_pabort, sc.d_pabort, 512, hipMemcpyDeviceToHost, sc.stream)); // abort flag + phase cycle totals
 }
 
@@ -1131,11 +1111,7 @@ static void job_begin(Context &c, SolveJob &J) {
   SolveCtx &sc = *J.sc;
   ensure_scratch(sc, P->m_cap, P->ld);
   Ctl *h = sc.h_ctl;
-  fill_ctl(sc, P, h);
-  h->tol_bnd = J.parm.tol_bnd;
-  h->tol_dj = J.parm.tol_dj;
-  h->tol_piv = J.parm.tol_piv;
-  h->budget = pivot_budget(P, J.parm);
+  fill_ctl(sc, P, h, &J.parm);
   take_edits(P, h);
   upload_ctl(sc);
   HIPCHECK(hipEventRecord(sc.ev_a, sc.stream));
@@ -1217,106 +1193,124 @@ static void job_enqueue(Context &c, SolveJob &J) {
   int depth;
   if (J.try_fused) depth = std::max(0, std::min(batch, remaining)); // + the generic step that closes the batch, if the limit leaves it a pivot
   else depth = std::max(1, std::min(batch, remaining));
-  auto body = [&](int m_grid) {
-    if (J.try_fused) {
-      PersistPlan pl;
-      // the resident-tableau kernel serves where the cluster chain is not on offer (mvx_set_cluster(0), a cluster launch
-      // that gave up): since round 3 the chain is the faster one at every size that fits k_persist (scripts/smalltime.py:
-      // 512x1024 9.1 against 12.3 us per pivot, 128x256 9.7 against 10.8)
-      if (depth > 0 && !J.profiled && J.resident && !(J.cluster && !g_cluster_broken.load()) && persist_plan(c, P, &pl) && ensure_persist(c, sc, P, pl)) {
-        // cache-resident size: one generic step settles the phase, then the whole run of primal pivots in ONE launch
-        // with the tableau held in LDS.  In front of it a backup (slab, control block, both devex weight sets): a
-        // launch whose workgroups do not all become resident in time aborts mid-step, and the backup is what the
-        // two-kernel path then carries on from.
-        launch_select(sc.d_ctl, sc.stream);
-        launch_update(sc.d_ctl, m_grid, n, sc.stream, 1, 1);
-        HIPCHECK(hipMemcpyAsync(sc.p_backup, P->slab, P->slab_bytes, hipMemcpyDeviceToDevice, sc.stream));
-        HIPCHECK(hipMemcpyAsync(sc.d_pctl, sc.d_ctl, sizeof(Ctl), hipMemcpyDeviceToDevice, sc.stream));
-        HIPCHECK(hipMemcpyAsync(sc.d_ppw, sc.d_pw[0], (size_t)P->ld * 8, hipMemcpyDeviceToDevice, sc.stream));
-        HIPCHECK(hipMemcpyAsync(sc.d_ppw + P->ld, sc.d_pw[1], (size_t)P->ld * 8, hipMemcpyDeviceToDevice, sc.stream));
-        const int head_stride = 4; // 4 B .. 4 KB between heads measured the same
-        HIPCHECK(hipMemsetAsync(sc.d_pcand, 0, (size_t)2 * pl.nw * head_stride * 8, sc.stream));
-        const int steps = 1 << 24; // the pivot limit is the control block's `budget`, which the kernel counts down
-        if (launch_persist(sc.d_ctl, sc.d_pcand, sc.d_pmsg, sc.d_pabort, (unsigned long long *)(sc.d_pabort + 16), P->m, pl.cpw, pl.nw, sc.p_msg_words, steps, head_stride, sc.stream) == 0) {
-          J.persist_queued = true;
-          g_persist_launches++;
-          // what the run ended on (optimum, unbounded ray, stall, pivot limit) is settled by one generic step
-          launch_select(sc.d_ctl, sc.stream);
-          launch_update(sc.d_ctl, m_grid, n, sc.stream, 1, 1);
-        } else {
-          g_persist_broken = true;
-        }
-      } else {
-        // The fused two-kernel pipeline (k_fa / k_fb) first: k_fboot takes a call from its very first pivot when the
-        // basis it starts from is primal feasible, and otherwise (dual simplex, phase 1, Bland's rule in force) turns
-        // the pipeline off, so that its launches return at once.  One generic step closes the batch: it settles what
-        // a stopped run ended on (optimum, unbounded ray, stall) in the same host round trip, and is an ordinary
-        // pivot when nothing stopped.  Its events come first in the pool: the leading pairs are the ones that stepped.
-        const size_t e_generic = J.ev_used;
-        if (J.profiled) J.ev_used += 2;
-        if (depth > 0) {
-          // chained path: k_pboot once, then per chain of up to `kc` steps two small launches per step (k_pc / k_pr)
-          // and one bulk launch (k_fbc3), so `depth` pivots take depth / kc passes over the tableau when every chain
-          // fills (a chain that ends early leaves pivots for the next batch)
-          const bool cl = J.cluster && !g_cluster_broken.load();
-          if (!cl) launch_pboot(J.cargs, sc.stream); // k_chain does the start-of-batch checks itself (first launch: boot)
-          bool first = true;
-          const int kc = cl ? std::max(1, std::min(J.chain0, chain_cluster_kmax(m, n))) : std::max(1, J.chain);
-          auto chain_launch = [&](int steps) { // k_chain: the whole selection of a chain of up to `steps` steps
-            J.cargs.kmax = steps;
-            J.cargs.boot = first ? 1 : 0;
-            first = false;
-            J.cargs.tagbase = sc.xtag;
-            sc.xtag += 128;
-            if (launch_chain(J.cargs, sc.stream) != 0) g_cluster_broken.store(true);
-            g_cluster_launches++;
-          };
-          for (int left = depth; left > 0;) {
-            const int steps = std::min(kc, left); // the last pass of a limited run chains only what the limit leaves
-            if (cl) chain_launch(steps);
-            else
-              for (int t = 0; t < steps; t++) launch_pstep(J.cargs, t, sc.stream);
-            ev(); // the profiled pair of events brackets the bulk launch: the pass and, beside it, the chain's patch jobs
-            launch_fbc3(J.cargs, steps, sc.stream);
-            ev();
-            left -= steps;
-          }
-          // a run that may end on the pivot limit: one more selection, which finds the limit and reports it
-          // (k_chain notes it itself when the limit falls on the end of its last chain: pc_itlim)
-          if (J.parm.it_lim >= 0 && depth >= remaining && !cl) launch_pc(J.cargs, 0, sc.stream);
-        }
-        launch_select(sc.d_ctl, sc.stream);
-        if (J.profiled) HIPCHECK(hipEventRecord(c.ev_pool[e_generic], sc.stream));
-        launch_update(sc.d_ctl, m_grid, n, sc.stream, 1, 1);
-        if (J.profiled) HIPCHECK(hipEventRecord(c.ev_pool[e_generic + 1], sc.stream));
-      }
-    } else if (J.try_dfused) {
-      // one generic step settles the phase (and restarts the dual devex weights when the phase has just been
-      // entered); if it is the dual simplex, the fused pair k_da / k_fb<DUAL> takes over, otherwise its launches
-      // return at once
+  if (J.try_fused) {
+    PersistPlan pl;
+    // the resident-tableau kernel serves where the cluster chain is not on offer (mvx_set_cluster(0), a cluster launch
+    // that gave up): since round 3 the chain is the faster one at every size that fits k_persist (scripts/smalltime.py:
+    // 512x1024 9.1 against 12.3 us per pivot, 128x256 9.7 against 10.8)
+    if (depth > 0 && !J.profiled && J.resident && !(J.cluster && !g_cluster_broken.load()) && persist_plan(c, P, &pl) && ensure_persist(c, sc, P)) {
+      // cache-resident size: one generic step settles the phase, then the whole run of primal pivots in ONE launch
+      // with the tableau held in LDS.  In front of it a backup (slab, control block, both devex weight sets): a
+      // launch whose workgroups do not all become resident in time aborts mid-step, and the backup is what the
+      // two-kernel path then carries on from.
       launch_select(sc.d_ctl, sc.stream);
-      launch_update(sc.d_ctl, m_grid, n, sc.stream, 1, 1);
-      if (depth > 1) {
-        launch_dboot(sc.d_ctl, n, sc.stream);
-        launch_db(sc.d_ctl, m_grid, n, sc.stream);
-        for (int k = 0; k < depth - 1; k++) {
-          launch_da(sc.d_ctl, n, sc.stream);
-          launch_db(sc.d_ctl, m_grid, n, sc.stream);
-        }
+      launch_update(sc.d_ctl, m, n, sc.stream, 1, 1);
+      HIPCHECK(hipMemcpyAsync(sc.p_backup, P->slab, P->slab_bytes, hipMemcpyDeviceToDevice, sc.stream));
+      HIPCHECK(hipMemcpyAsync(sc.d_pctl, sc.d_ctl, sizeof(Ctl), hipMemcpyDeviceToDevice, sc.stream));
+      HIPCHECK(hipMemcpyAsync(sc.d_ppw, sc.d_pw[0], (size_t)P->ld * 8, hipMemcpyDeviceToDevice, sc.stream));
+      HIPCHECK(hipMemcpyAsync(sc.d_ppw + P->ld, sc.d_pw[1], (size_t)P->ld * 8, hipMemcpyDeviceToDevice, sc.stream));
+      const int head_stride = 4; // 4 B .. 4 KB between heads measured the same
+      HIPCHECK(hipMemsetAsync(sc.d_pcand, 0, (size_t)2 * pl.nw * head_stride * 8, sc.stream));
+      const int steps = 1 << 24; // the pivot limit is the control block's `budget`, which the kernel counts down
+      if (launch_persist(sc.d_ctl, sc.d_pcand, sc.d_pmsg, sc.d_pabort, (unsigned long long *)(sc.d_pabort + 16), P->m, pl.cpw, pl.nw, sc.p_msg_words, steps, head_stride, sc.stream) == 0) {
+        J.persist_queued = true;
+        g_persist_launches++;
+        // what the run ended on (optimum, unbounded ray, stall, pivot limit) is settled by one generic step
+        launch_select(sc.d_ctl, sc.stream);
+        launch_update(sc.d_ctl, m, n, sc.stream, 1, 1);
+      } else {
+        g_persist_broken = true;
       }
     } else {
-      for (int k = 0; k < depth; k++) {
-        launch_dsel(sc.d_ctl, m, n, sc.stream); // a dual phase carrying on (warm starts): the chain on chip, k_select then returns
-        launch_select(sc.d_ctl, sc.stream);
-        ev();
-        launch_update(sc.d_ctl, m_grid, n, sc.stream, 1, 1);
-        ev();
+      // The fused two-kernel pipeline (k_fa / k_fb) first: k_fboot takes a call from its very first pivot when the
+      // basis it starts from is primal feasible, and otherwise (dual simplex, phase 1, Bland's rule in force) turns
+      // the pipeline off, so that its launches return at once.  One generic step closes the batch: it settles what
+      // a stopped run ended on (optimum, unbounded ray, stall) in the same host round trip, and is an ordinary
+      // pivot when nothing stopped.  Its events come first in the pool: the leading pairs are the ones that stepped.
+      const size_t e_generic = J.ev_used;
+      if (J.profiled) J.ev_used += 2;
+      if (depth > 0) {
+        // chained path: k_pboot once, then per chain of up to `kc` steps two small launches per step (k_pc / k_pr)
+        // and one bulk launch (k_fbc3), so `depth` pivots take depth / kc passes over the tableau when every chain
+        // fills (a chain that ends early leaves pivots for the next batch)
+        const bool cl = J.cluster && !g_cluster_broken.load();
+        if (!cl) launch_pboot(J.cargs, sc.stream); // k_chain does the start-of-batch checks itself (first launch: boot)
+        bool first = true;
+        const int kc = cl ? std::max(1, std::min(J.chain0, chain_cluster_kmax(m, n))) : std::max(1, J.chain);
+        auto chain_launch = [&](int steps) { // k_chain: the whole selection of a chain of up to `steps` steps
+          J.cargs.kmax = steps;
+          J.cargs.boot = first ? 1 : 0;
+          first = false;
+          J.cargs.tagbase = sc.xtag;
+          sc.xtag += 128;
+          if (launch_chain(J.cargs, sc.stream) != 0) g_cluster_broken.store(true);
+          g_cluster_launches++;
+        };
+        for (int left = depth; left > 0;) {
+          const int steps = std::min(kc, left); // the last pass of a limited run chains only what the limit leaves
+          if (cl) chain_launch(steps);
+          else
+            for (int t = 0; t < steps; t++) launch_pstep(J.cargs, t, sc.stream);
+          ev(); // the profiled pair of events brackets the bulk launch: the pass and, beside it, the chain's patch jobs
+          launch_fbc3(J.cargs, steps, sc.stream);
+          ev();
+          left -= steps;
+        }
+        // a run that may end on the pivot limit: one more selection, which finds the limit and reports it
+        // (k_chain notes it itself when the limit falls on the end of its last chain: pc_itlim)
+        if (J.parm.it_lim >= 0 && depth >= remaining && !cl) launch_pc(J.cargs, 0, sc.stream);
+      }
+      launch_select(sc.d_ctl, sc.stream);
+      if (J.profiled) HIPCHECK(hipEventRecord(c.ev_pool[e_generic], sc.stream));
+      launch_update(sc.d_ctl, m, n, sc.stream, 1, 1);
+      if (J.profiled) HIPCHECK(hipEventRecord(c.ev_pool[e_generic + 1], sc.stream));
+    }
+  } else if (J.try_dfused) {
+    // one generic step settles the phase (and restarts the dual devex weights when the phase has just been
+    // entered); if it is the dual simplex, the fused pair k_da / k_fb<DUAL> takes over, otherwise its launches
+    // return at once
+    launch_select(sc.d_ctl, sc.stream);
+    launch_update(sc.d_ctl, m, n, sc.stream, 1, 1);
+    if (depth > 1) {
+      launch_dboot(sc.d_ctl, n, sc.stream);
+      launch_db(sc.d_ctl, m, n, sc.stream);
+      for (int k = 0; k < depth - 1; k++) {
+        launch_da(sc.d_ctl, n, sc.stream);
+        launch_db(sc.d_ctl, m, n, sc.stream);
       }
     }
-    launch_export(sc.d_ctl, sc.d_stage, m_grid, n, 0, sc.stream);
-    stage_copy_async(sc, P);
-  };
-  body(m);
+  } else {
+    for (int k = 0; k < depth; k++) {
+      launch_dsel(sc.d_ctl, m, n, sc.stream); // a dual phase carrying on (warm starts): the chain on chip, k_select then returns
+      launch_select(sc.d_ctl, sc.stream);
+      ev();
+      launch_update(sc.d_ctl, m, n, sc.stream, 1, 1);
+      ev();
+    }
+  }
+  launch_export(sc.d_ctl, sc.d_stage, m, n, 0, sc.stream);
+  stage_copy_async(sc, P);
+}
+
+// What a solve that has ended reports on its handle, for a single solve and a job of a batch alike: the counters of the
+// control block `snap` it ended with, and status and return code by `done` -- the single path's own verdict (D_FAIL after
+// 64 phase-1 rounds) or the snapshot's.  Returns the code.
+static int book_result(mvx_prob *P, const Ctl &snap, int done, double last_ms) {
+  P->it_cnt += snap.it_cnt;
+  P->bland_cnt += snap.n_bland;
+  P->pert_cnt += snap.n_pert;
+  // a job of a batch that is neither primal nor dual feasible: nothing has ended, the single-handle path carries on from
+  // the pivots made so far and books its own
+  if (done == D_NEED_PHASE1) return 0;
+  P->last_ms = last_ms;
+  P->hint_dual = false;
+  switch (done) {
+    case D_OPT: P->status = MVX_OPT; return 0;
+    case D_UNBND: P->status = MVX_UNBND; return 0;
+    case D_NOFEAS: P->status = MVX_NOFEAS; return 0;
+    case D_ITLIM: P->status = (snap.phase == PH_PRIMAL2) ? MVX_FEAS : MVX_INFEAS; return MVX_EITLIM;
+    default: P->status = MVX_UNDEF; return MVX_EFAIL;
+  }
 }
 
 // The staging buffer holds the control block and, because the solve has ended (k_export packs the
@@ -1324,38 +1318,10 @@ static void job_enqueue(Context &c, SolveJob &J) {
 static bool job_finalize(SolveJob &J) {
   mvx_prob *P = J.P;
   SolveCtx &sc = *J.sc;
-  const Ctl &snap = J.snap;
-  const unsigned char *s = sc.h_stage;
-  const double *beta = (const double *)(s + sizeof(Ctl));
-  const double *dj = beta + (P->m_cap + 1);
-  const int *bv = (const int *)(dj + P->ld);
-  const int *nv = bv + (P->m_cap + 1);
-  const int *nf = nv + P->ld;
-  P->beta.assign(beta, beta + P->m + 1);
-  P->dj.assign(dj, dj + P->n + 1);
-  P->bvar.assign(bv, bv + P->m + 1);
-  P->nvar.assign(nv, nv + P->n + 1);
-  P->nflag.assign(nf, nf + P->n + 1);
-  rebuild_pos(P);
-  P->sol_fresh = true;
-  P->fresh_rows = -1;
+  publish_mirrors(P, StageView(sc.h_stage, P->m_cap, P->ld));
   float ms = 0.f;
   HIPCHECK(hipEventElapsedTime(&ms, sc.ev_a, sc.ev_b));
-  P->last_ms = ms;
-  P->it_cnt += snap.it_cnt;
-  P->bland_cnt += snap.n_bland;
-  P->pert_cnt += snap.n_pert;
-  P->hint_dual = false;
-  switch (J.done) {
-    case D_OPT: P->status = MVX_OPT; J.rc = 0; break;
-    case D_UNBND: P->status = MVX_UNBND; J.rc = 0; break;
-    case D_NOFEAS: P->status = MVX_NOFEAS; J.rc = 0; break;
-    case D_ITLIM:
-      P->status = (snap.phase == PH_PRIMAL2) ? MVX_FEAS : MVX_INFEAS;
-      J.rc = MVX_EITLIM;
-      break;
-    default: P->status = MVX_UNDEF; J.rc = MVX_EFAIL; break;
-  }
+  J.rc = book_result(P, J.snap, J.done, ms);
   return true;
 }
 
@@ -1470,32 +1436,38 @@ static void remember_tolerances(mvx_prob *P, const mvx_smcp &parm) {
   P->last_tol[2] = parm.tol_piv;
 }
 
+// What every solve does with a handle before any device work, single or in a batch.  true: the handle goes on to the
+// device, with a tableau; false: the call ends here for it with *rc.
+static bool admit(mvx_prob *P, const mvx_smcp &parm, int *rc) {
+  if (P->m < 1 || P->n < 1) {
+    P->status = MVX_UNDEF;
+    *rc = MVX_EFAIL;
+    return false;
+  }
+  if (already_solved(P, parm)) {
+    P->last_ms = 0.0;
+    *rc = 0;
+    return false;
+  }
+  if (!P->valid && !build_slack_tableau(P)) {
+    *rc = MVX_EFAIL;
+    return false;
+  }
+  remember_tolerances(P, parm);
+  P->fresh_rows = -1; // the solve rewrites the tableau: whatever ends it exports the mirrors anew, or leaves them stale
+  return true;
+}
+
 static bool job_prepare(SolveJob &J, mvx_prob *P, const mvx_smcp *parm) {
   J.P = P;
   if (parm) J.parm = *parm;
   else mvx_init_smcp(&J.parm);
-  if (P->m < 1 || P->n < 1) {
-    P->status = MVX_UNDEF;
-    J.rc = MVX_EFAIL;
-    return false;
-  }
-  if (already_solved(P, J.parm)) {
-    P->last_ms = 0.0;
-    J.rc = 0;
-    return false;
-  }
-  if (!P->valid && !build_slack_tableau(P)) {
-    J.rc = MVX_EFAIL;
-    return false;
-  }
-  remember_tolerances(P, J.parm);
-  return true;
+  return admit(P, J.parm, &J.rc);
 }
 
 static int solve_once(mvx_prob *P, const mvx_smcp *parm, bool aux) {
   SolveJob J;
   if (!job_prepare(J, P, parm)) return J.rc;
-  P->fresh_rows = -1; // the solve rewrites the tableau: whatever ends it exports the mirrors anew, or leaves them stale
   Context &c = ctx();
   HIPCHECK(hipSetDevice(c.dev)); // the current device is per host thread (the B&B driver solves from a worker thread)
   std::unique_lock<std::recursive_mutex> main_lock(c.main_mu);
@@ -1694,60 +1666,57 @@ static void sync_batch_stream() {
 }
 static int g_batch_slots = 64;
 
+// a device / pinned host array of `count` elements in place of the one p holds, if any; nothing is kept
+template <class T>
+static void renew_dev(T *&p, size_t count) {
+  if (p) HIPCHECK(hipFree(p));
+  HIPCHECK(hipMalloc((void **)&p, sizeof(T) * count));
+}
+template <class T>
+static void renew_host(T *&p, size_t count) {
+  if (p) HIPCHECK(hipHostFree(p));
+  HIPCHECK(hipHostMalloc((void **)&p, sizeof(T) * count));
+}
+
+// every piece of one slot's scratch, in layout order (see Pieces); returns a slot's bytes
+static size_t slot_pieces(SlotScratch &sp, int mc, int l, unsigned char *base) {
+  const size_t row = (size_t)mc + 1, col = (size_t)l, var = (size_t)mc + l + 1;
+  Pieces piece{base};
+  piece(sp.colq, row), piece(sp.srow, col), piece(sp.olb, var), piece(sp.oub, var), piece(sp.dw, row);
+  piece(sp.pw, col); // generic path only: one set of primal weights
+  // dual chains: DCH_MAX - 1 pairs (pivot column, scaled pivot row); k_select finds their parts by the two strides
+  const size_t o_chain = piece.carve.off;
+  piece(sp.chain, row);
+  sp.chain_col = piece.carve.off - o_chain;
+  piece.carve(col * 8);
+  sp.chain_stride = piece.carve.off - o_chain;
+  piece.carve((size_t)(DCH_MAX - 2) * sp.chain_stride);
+  return piece.carve.off;
+}
+
 static void ensure_batch(BatchCtx &bc, int slots, int jobs, int m_cap, int ld) {
   if (!bc.stream) HIPCHECK(hipStreamCreateWithFlags(&bc.stream, hipStreamNonBlocking));
   if (!bc.poll_ev) HIPCHECK(hipEventCreateWithFlags(&bc.poll_ev, hipEventDisableTiming));
   if (slots <= bc.slots && jobs <= bc.jobs && m_cap <= bc.m_cap && ld <= bc.ld) return;
   HIPCHECK(hipStreamSynchronize(bc.stream));
-  if (bc.d_ctl) HIPCHECK(hipFree(bc.d_ctl));
-  if (bc.h_ctl) HIPCHECK(hipHostFree(bc.h_ctl));
-  if (bc.d_jobs) HIPCHECK(hipFree(bc.d_jobs));
-  if (bc.h_jobs) HIPCHECK(hipHostFree(bc.h_jobs));
-  if (bc.h_fill) HIPCHECK(hipHostFree(bc.h_fill));
-  if (bc.d_sp) HIPCHECK(hipFree(bc.d_sp));
-  if (bc.h_sp) HIPCHECK(hipHostFree(bc.h_sp));
-  if (bc.d_cnt) HIPCHECK(hipFree(bc.d_cnt));
-  if (bc.h_cnt) HIPCHECK(hipHostFree(bc.h_cnt));
-  if (bc.scratch) HIPCHECK(hipFree(bc.scratch));
-  if (bc.d_stage) HIPCHECK(hipFree(bc.d_stage));
-  if (bc.h_stage) HIPCHECK(hipHostFree(bc.h_stage));
   bc.slots = std::max(slots, bc.slots);
   bc.jobs = std::max(jobs + jobs / 2, bc.jobs);
   bc.m_cap = std::max(m_cap, bc.m_cap);
   bc.ld = std::max(ld, bc.ld);
-  HIPCHECK(hipMalloc((void **)&bc.d_ctl, sizeof(Ctl) * bc.slots));
-  HIPCHECK(hipHostMalloc((void **)&bc.h_ctl, sizeof(Ctl) * bc.slots));
-  HIPCHECK(hipMalloc((void **)&bc.d_jobs, sizeof(Ctl) * bc.jobs));
-  HIPCHECK(hipHostMalloc((void **)&bc.h_jobs, sizeof(Ctl) * bc.jobs));
-  HIPCHECK(hipHostMalloc((void **)&bc.h_fill, sizeof(Ctl) * bc.slots));
-  HIPCHECK(hipMalloc((void **)&bc.d_sp, sizeof(SlotScratch) * bc.slots));
-  HIPCHECK(hipHostMalloc((void **)&bc.h_sp, sizeof(SlotScratch) * bc.slots));
-  HIPCHECK(hipMalloc((void **)&bc.d_cnt, sizeof(int) * 4));
+  SlotScratch measure;
+  bc.scratch_stride = slot_pieces(measure, bc.m_cap, bc.ld, nullptr);
+  bc.stage_stride = StageView::bytes(bc.m_cap, bc.ld);
+  renew_dev(bc.d_ctl, bc.slots), renew_host(bc.h_ctl, bc.slots);
+  renew_dev(bc.d_jobs, bc.jobs), renew_host(bc.h_jobs, bc.jobs);
+  renew_host(bc.h_fill, bc.slots);
+  renew_dev(bc.d_sp, bc.slots), renew_host(bc.h_sp, bc.slots);
+  renew_dev(bc.d_cnt, 4), renew_host(bc.h_cnt, 8);
+  renew_dev(bc.scratch, bc.scratch_stride * bc.slots);
+  renew_dev(bc.d_stage, bc.stage_stride * bc.jobs), renew_host(bc.h_stage, bc.stage_stride * bc.jobs);
   HIPCHECK(hipMemsetAsync(bc.d_cnt, 0, sizeof(int) * 4, bc.stream)); // on the batch's own stream: a null-stream memset is not ordered with it
-  HIPCHECK(hipHostMalloc((void **)&bc.h_cnt, sizeof(int) * 8));
-  const size_t s_row = align_up((size_t)(bc.m_cap + 1) * 8, 256), s_col = align_up((size_t)bc.ld * 8, 256);
-  const size_t s_var = align_up((size_t)(bc.m_cap + bc.ld + 1) * 8, 256);
-  const size_t s_chain = (size_t)(DCH_MAX - 1) * (s_row + s_col);
-  bc.scratch_stride = s_row + s_col + 2 * s_var + s_row + s_col + s_chain;
-  HIPCHECK(hipMalloc((void **)&bc.scratch, bc.scratch_stride * bc.slots));
   HIPCHECK(hipMemsetAsync(bc.scratch, 0, bc.scratch_stride * bc.slots, bc.stream));
-  for (int k = 0; k < bc.slots; k++) {
-    unsigned char *sb = bc.scratch + (size_t)k * bc.scratch_stride;
-    SlotScratch &sp = bc.h_sp[k];
-    sp.colq = (double *)sb;
-    sp.srow = (double *)(sb + s_row);
-    sp.olb = (double *)(sb + s_row + s_col);
-    sp.oub = (double *)(sb + s_row + s_col + s_var);
-    sp.dw = (double *)(sb + s_row + s_col + 2 * s_var);
-    sp.pw = (double *)(sb + s_row + s_col + 2 * s_var + s_row); // generic path only: one set of primal weights
-    sp.chain = (double *)(sb + s_row + s_col + 2 * s_var + s_row + s_col);
-    sp.chain_col = s_row;
-    sp.chain_stride = s_row + s_col;
-  }
+  for (int k = 0; k < bc.slots; k++) slot_pieces(bc.h_sp[k], bc.m_cap, bc.ld, bc.scratch + (size_t)k * bc.scratch_stride);
   HIPCHECK(hipMemcpyAsync(bc.d_sp, bc.h_sp, sizeof(SlotScratch) * bc.slots, hipMemcpyHostToDevice, bc.stream));
-  bc.stage_stride = stage_size(bc.m_cap, bc.ld);
-  HIPCHECK(hipMalloc((void **)&bc.d_stage, bc.stage_stride * bc.jobs));
-  HIPCHECK(hipHostMalloc((void **)&bc.h_stage, bc.stage_stride * bc.jobs));
   // an idle slot reads as finished and holds no job
   std::memset(bc.h_ctl, 0, sizeof(Ctl) * bc.slots);
   for (int k = 0; k < bc.slots; k++) {
@@ -1756,57 +1725,24 @@ static void ensure_batch(BatchCtx &bc, int slots, int jobs, int m_cap, int ld) {
   }
 }
 
-// control block of one job; the slot that pulls it points it at its own scratch (k_select)
+// control block of one job; the scratch pointers, chain_max, pc_epoch and npb stay zero: the slot that pulls the job points
+// it at its own scratch (k_select)
 static void batch_fill_job(Ctl *h, mvx_prob *P, const mvx_smcp &parm, int njobs) {
-  std::memset(h, 0, sizeof(Ctl));
-  h->T = P->d_T;
-  h->bvar = P->d_bvar; h->blb = P->d_blb; h->bub = P->d_bub;
-  h->nvar = P->d_nvar; h->nflag = P->d_nflag; h->nlb = P->d_nlb; h->nub = P->d_nub;
-  h->m = P->m; h->n = P->n; h->ld = P->ld; h->m_cap = P->m_cap;
-  h->sgn = (P->dir == MVX_MAX) ? 1.0 : -1.0;
-  h->tol_bnd = parm.tol_bnd; h->tol_dj = parm.tol_dj; h->tol_piv = parm.tol_piv;
-  h->phase = PH_START; h->done = D_RUN; h->budget = pivot_budget(P, parm);
-  h->stall = 0; h->stall_limit = g_stall_limit > 0 ? g_stall_limit : 64 + (P->m + P->n) / 8;
-  h->fstate = F_OFF;
+  ctl_for_handle(h, P, parm.tol_bnd, parm.tol_dj, parm.tol_piv, pivot_budget(P, parm));
   h->job = -1;
-  h->nch = 1;
   h->dchain_max = dual_chain_length(njobs >= 32, P->m <= 1024 && P->n <= 1024);
   take_edits(P, h);
 }
 
 // mirrors + status of a finished job; layout inside the staging area follows the handle's own m_cap / ld
 static int batch_finish_job(BatchCtx &bc, int j, mvx_prob *P, int *done_code, int *pivots) {
-  const unsigned char *s = bc.h_stage + (size_t)j * bc.stage_stride;
+  unsigned char *s = bc.h_stage + (size_t)j * bc.stage_stride;
   Ctl snap;
   std::memcpy(&snap, s, sizeof(Ctl));
   *done_code = snap.done;
   *pivots = snap.it_cnt;
-  P->it_cnt += snap.it_cnt;
-  P->bland_cnt += snap.n_bland;
-  P->pert_cnt += snap.n_pert;
-  if (snap.done == D_NEED_PHASE1) return 0; // neither primal nor dual feasible: the caller finishes it on the single-handle path
-  const double *beta = (const double *)(s + sizeof(Ctl));
-  const double *dj = beta + (P->m_cap + 1);
-  const int *bv = (const int *)(dj + P->ld);
-  const int *nv = bv + (P->m_cap + 1);
-  const int *nf = nv + P->ld;
-  P->beta.assign(beta, beta + P->m + 1);
-  P->dj.assign(dj, dj + P->n + 1);
-  P->bvar.assign(bv, bv + P->m + 1);
-  P->nvar.assign(nv, nv + P->n + 1);
-  P->nflag.assign(nf, nf + P->n + 1);
-  rebuild_pos(P);
-  P->sol_fresh = true;
-  P->fresh_rows = -1;
-  P->last_ms = 0.0;
-  P->hint_dual = false;
-  switch (snap.done) {
-    case D_OPT: P->status = MVX_OPT; return 0;
-    case D_UNBND: P->status = MVX_UNBND; return 0;
-    case D_NOFEAS: P->status = MVX_NOFEAS; return 0;
-    case D_ITLIM: P->status = (snap.phase == PH_PRIMAL2) ? MVX_FEAS : MVX_INFEAS; return MVX_EITLIM;
-    default: P->status = MVX_UNDEF; return MVX_EFAIL;
-  }
+  if (snap.done != D_NEED_PHASE1) publish_mirrors(P, StageView(s, P->m_cap, P->ld));
+  return book_result(P, snap, snap.done, 0.0);
 }
 
 int engine_simplex_batch(mvx_prob **probs, int count, const mvx_smcp *parm_in, int *rcs) {
@@ -1820,22 +1756,11 @@ int engine_simplex_batch(mvx_prob **probs, int count, const mvx_smcp *parm_in, i
   int m_cap = 0, ld = 0, m_max = 0, n_max = 0;
   for (int i = 0; i < count; i++) {
     mvx_prob *P = probs[i];
-    if (P->m < 1 || P->n < 1) {
-      P->status = MVX_UNDEF;
-      if (rcs) rcs[i] = MVX_EFAIL;
+    int rc = 0;
+    if (!admit(P, parm, &rc)) {
+      if (rcs) rcs[i] = rc;
       continue;
     }
-    if (already_solved(P, parm)) {
-      P->last_ms = 0.0;
-      if (rcs) rcs[i] = 0;
-      continue;
-    }
-    if (!P->valid && !build_slack_tableau(P)) {
-      if (rcs) rcs[i] = MVX_EFAIL;
-      continue;
-    }
-    remember_tolerances(P, parm);
-    P->fresh_rows = -1; // as in solve_once
     pending.push_back(i);
     m_cap = std::max(m_cap, P->m_cap);
     ld = std::max(ld, P->ld);
@@ -3648,7 +3573,7 @@ void persist_cycles(unsigned long long *out5) {
   const unsigned long long *d = (const unsigned long long *)(g_ctx->main.h_pabort + 16);
   for (int k = 0; k < 48; k++) out5[k] = d[k];
 }
-// diagnostic (MVX_FCS_DBG=1): the last phase stamps of k_fcs, 8 per chain position (+1 row for the boot launch), 10 ns ticks
+// diagnostic (MVX_FCS_DBG=1): the last phase stamps of k_pc / k_pr (8 each) or k_chain per chain position, 10 ns ticks
 int fcs_debug_stamps(unsigned long long *out) {
   Context &c = ctx();
   if (!c.main.h_ctl || !c.main.h_ctl->dbg) return 0;

@@ -1123,24 +1123,19 @@ __device__ void select_step(Ctl *c, Cand *lds) {
   }
 }
 
-// What the host needs after a solve, packed into one staging area (all threads of the block call):
-//   [Ctl][beta (m_cap+1) f64][d (ld) f64][bvar (m_cap+1) i32][nvar (ld) i32][nflag (ld) i32]
+// What the host needs after a solve, packed into one staging area (StageView; all threads of the block call)
 __device__ void pack_mirrors(const Ctl *c, unsigned char *stage, int t0, int step) {
-  const int m = c->m, n = c->n, ld = c->ld, mc = c->m_cap;
-  double *beta = reinterpret_cast<double *>(stage + sizeof(Ctl));
-  double *dj = beta + (mc + 1);
-  int *bv = reinterpret_cast<int *>(dj + ld);
-  int *nv = bv + (mc + 1);
-  int *nf = nv + ld;
+  const int m = c->m, n = c->n, ld = c->ld;
+  const StageView v(stage, c->m_cap, ld);
   for (int t = t0; t <= m || t <= n; t += step) {
     if (t <= m) {
-      beta[t] = c->T[(size_t)t * ld];
-      bv[t] = c->bvar[t];
+      v.beta[t] = c->T[(size_t)t * ld];
+      v.bvar[t] = c->bvar[t];
     }
     if (t <= n) {
-      dj[t] = c->T[t];
-      nv[t] = c->nvar[t];
-      nf[t] = c->nflag[t];
+      v.dj[t] = c->T[t];
+      v.nvar[t] = c->nvar[t];
+      v.nflag[t] = c->nflag[t];
     }
   }
 }
@@ -1675,8 +1670,7 @@ __global__ __launch_bounds__(256) void k_add_rows(double *T, int ld, int n, int 
 }
 
 // ---------------------------------------------------------------------------- k_export
-// Pack what the host needs after a solve into one staging buffer:
-//   [Ctl][beta (m_cap+1) f64][d (ld) f64][bvar (m_cap+1) i32][nvar (ld) i32][nflag (ld) i32]
+// Pack what the host needs after a solve into one staging buffer (StageView)
 __global__ __launch_bounds__(256) void k_export(Ctl *c, unsigned char *stage, int force, size_t slot_stride) {
   c += blockIdx.z;
   stage += (size_t)blockIdx.z * slot_stride;

@@ -28,7 +28,7 @@ constexpr double DEGEN_TOL = 1e-9; // a step / dual ratio no longer than this co
 constexpr double PERT_EPS = 1e-6; // relative size of the anti-stalling bound perturbation (oracle: PERT_EPS)
 constexpr size_t NT_THRESHOLD_BYTES = (size_t)320 << 20; // tableaux larger than this stream with non-temporal access (pick_nt)
 constexpr size_t WT_MIN_BYTES = (size_t)96 << 20, WT_MAX_BYTES = (size_t)272 << 20; // write-through stores in this band (pick_nt)
-constexpr int KCH = 32;          // most steps one bulk launch of the chained primal path applies (k_fcs / k_fbc3)
+constexpr int KCH = 32;          // most steps one bulk launch of the chained primal path applies (chosen by k_pc / k_pr or k_chain, applied by k_fbc3)
 constexpr int DCH_MAX = 8;  // most dual pivots one k_update applies (dual_chain)
 constexpr int DA_THREADS = 1024; // k_dboot / k_da workgroup size: the O(m) leaving-row pass is redundant per block
 constexpr int MAX_EDITS = 8;      // pending bound edits a control block carries (more are flushed by launches)
@@ -135,7 +135,26 @@ struct Ctl {
                         // on offer: the generic step that closes the batch reports it without pricing again
   int dsel;             // k_dsel has prepared the coming step (a dual phase carrying on): the k_select that follows returns at once
   int cl_abort;         // k_chain gave up waiting for its peer workgroups: the chain was dropped, nothing was changed
-  unsigned long long *dbg; // diagnostic phase stamps of k_fcs (MVX_FCS_DBG=1), nullptr otherwise
+  unsigned long long *dbg; // diagnostic phase stamps of k_pc / k_pr / k_chain (MVX_FCS_DBG=1), nullptr otherwise
+};
+
+// What the host needs after a solve, packed into one staging area:
+//   [Ctl][beta (m_cap+1) f64][d (ld) f64][bvar (m_cap+1) i32][nvar (ld) i32][nflag (ld) i32]
+// with the handle's own m_cap and ld.  pack_mirrors (k_export, a queue slot of k_select) writes through this view, the
+// host reads through it (publish_mirrors); nothing else knows the layout.
+struct StageView {
+  double *beta, *dj;
+  int *bvar, *nvar, *nflag;
+  __host__ __device__ StageView(unsigned char *base, int m_cap, int ld) {
+    beta = reinterpret_cast<double *>(base + sizeof(Ctl));
+    dj = beta + (m_cap + 1);
+    bvar = reinterpret_cast<int *>(dj + ld);
+    nvar = bvar + (m_cap + 1);
+    nflag = nvar + ld;
+  }
+  static size_t bytes(int m_cap, int ld) { // of one staging area, rounded up to 256
+    return (sizeof(Ctl) + (size_t)(m_cap + 1) * (8 + 4) + (size_t)ld * (8 + 4 + 4) + 255) / 256 * 256;
+  }
 };
 
 // What the kernels of the chained primal path (k_pboot / k_pc / k_pr / k_fbc3) need that the host knows -- pointers,

@@ -500,6 +500,97 @@ def test_batch_with_few_slots_refills_and_compacts(gpu, orc, slots):
         gpu.set_batch_slots(64)
 
 
+def _batch(gpu, handles, parm=None):
+    arr = (C.c_void_p * len(handles))(*[g.h for g in handles])
+    rcs = (C.c_int * len(handles))()
+    assert gpu.simplex_batch(arr, len(handles), C.byref(parm) if parm is not None else None, rcs) == 0
+    return list(rcs)
+
+
+def _single_path_jobs(gpu):
+    """mvx_debug_counters slot 4: jobs a batch has handed to the single-handle path so far"""
+    out = (C.c_longlong * 8)()
+    gpu.lib.mvx_debug_counters(out, 0)
+    return out[4]
+
+
+def test_batch_books_counters_and_duals_like_single_solves(gpu, orc):
+    """What a job of a batch books on its handle -- return code, the anti-stalling counters, the dual values read from the
+    published mirrors -- against one oracle solve per handle, with the stall limit at 1 so that the rules fire.  The cycling
+    LPs and the degenerate one are `<=` LPs with b >= 0 and columns at a zero lower bound: their slack basis is primal
+    feasible, so the batch itself solves them, whatever it hands to the single-handle path among the general ones."""
+    try:
+        gpu.set_stall_limit(1)
+        orc.set_stall_limit(1)
+        pairs = []
+        for name, (A, b, c) in lpgen.CYCLING.items():
+            A, b, c = (np.array(v, float) for v in (A, b, c))
+            assert (b >= 0).all()
+            hs = [api.create() for api in (gpu, orc)]
+            for P in hs:
+                P.load_dense(A, b, c)
+            pairs.append(hs)
+        A, b, c = lpgen.degenerate_lp(60, 80, 2)
+        assert (b >= 0).all()
+        pairs.append([lpgen.load_degenerate(api, A, b, c) for api in (gpu, orc)])
+        stays = len(pairs)  # the first `stays` handles cannot leave the batch
+        rng = np.random.default_rng(77)
+        for k in range(10):
+            A, row_b, col_b, c, direction = lpgen.random_general_lp(rng)
+            hs = [api.create() for api in (gpu, orc)]
+            for P in hs:
+                P.load_general(A, row_b, col_b, c, c0=1.5, direction=direction)
+            pairs.append(hs)
+        ref = [o.simplex() for _, o in pairs]
+        assert pairs[stays - 1][1].pert_cnt == 1
+        assert any(o.bland_cnt + o.pert_cnt > 0 for _, o in pairs[:stays])
+        before = _single_path_jobs(gpu)
+        rcs = _batch(gpu, [g for g, _ in pairs])
+        assert _single_path_jobs(gpu) - before <= len(pairs) - stays
+        for k, ((g, o), rc) in enumerate(zip(pairs, rcs)):
+            assert rc == ref[k], k
+            assert (g.bland_cnt, g.pert_cnt) == (o.bland_cnt, o.pert_cnt), k
+            assert_same_state(g, o, "stalling batch, handle %d" % k)
+            assert g.col_dual().tobytes() == o.col_dual().tobytes(), k
+            assert g.row_dual().tobytes() == o.row_dual().tobytes(), k
+    finally:
+        gpu.set_stall_limit(0)
+        orc.set_stall_limit(0)
+
+
+def test_batch_limit_statuses_and_resume(gpu, orc):
+    """Two batch calls on the same four handles: a pivot limit of 3 (the limit's statuses and return code), then no limit
+    (a handle that ended optimal is answered from the state at hand, the others carry on where they stopped).  The
+    generator's seed is one at which the oracle ends the first general LP within the limit and stops the second in an
+    infeasible basis."""
+    rng = np.random.default_rng(29)
+    pairs = []
+    for (m, n, seed) in [(33, 70, 2), (64, 40, 3)]:
+        hs = [api.create() for api in (gpu, orc)]
+        for P in hs:
+            P.load_dense(*synth.dense_lp(m, n, seed))
+        pairs.append(hs)
+    for k in range(2):
+        A, row_b, col_b, c, direction = lpgen.random_general_lp(rng)
+        hs = [api.create() for api in (gpu, orc)]
+        for P in hs:
+            P.load_general(A, row_b, col_b, c, c0=0.5, direction=direction)
+        pairs.append(hs)
+    parm = capi.Smcp()
+    gpu.init_smcp(C.byref(parm))
+    parm.it_lim = 3
+    for what, lim, p in (("limit 3", 3, parm), ("resumed", None, None)):
+        ref = [o.simplex(it_lim=lim) for _, o in pairs]
+        if lim is not None:
+            assert ref.count(capi.EITLIM) >= 2  # at least two handles are still open: the second call is a batch too
+            assert {capi.FEAS, capi.INFEAS, capi.OPT} <= {o.status for _, o in pairs}
+        rcs = _batch(gpu, [g for g, _ in pairs], p)
+        for k, ((g, o), rc) in enumerate(zip(pairs, rcs)):
+            assert rc == ref[k], (what, k)
+            assert (g.bland_cnt, g.pert_cnt) == (o.bland_cnt, o.pert_cnt), (what, k)
+            assert_same_state(g, o, "%s, handle %d" % (what, k))
+
+
 def test_glpk_default_tolerances_behind_null_parameters(gpu, orc):
     """mvx_set_default_tolerances(1e-7, 1e-7, 1e-9): GLPK's own defaults [GLPK-recalled] behind every NULL-parameter
     solve -- all MVOLPS ever makes (bs.cpp:117,279,287).  Oracle and device take the same switch and stay bit-identical,
