@@ -190,6 +190,18 @@ int mvx_classify_many(const mvx_prob *const *Ps, int count, int quirks, int *sta
    is not MVX_OPT; -4 a column that is not basic. */
 int mvx_branch_penalties_many(const mvx_prob *const *Ps, int count, const int *cols, const int *col_off, double tol, double *pen_down,
                               double *pen_up, int *arg_down, int *arg_up);
+/* Sensitivity ranges (DESIGN.md "Sensitivity ranges (ranges)") of one solved handle: how far every variable k = 1..m+n
+   (auxiliaries first, then the structurals) may move before the basis stops being optimal.  val is (m+n+1) x 6 doubles,
+   columns ACT_DN, ACT_UP, OBJ_DN, OBJ_UP, COST_DN, COST_UP; var is (m+n+1) x 4 ints, columns LIM_DN, LIM_UP, ENT_DN, ENT_UP;
+   row 0 of both is zero.  A non-basic variable gets its activity range (ratio test down its tableau column: the step in each
+   direction, the basic variable that limits it, the size of the objective change there) and the allowable change of its cost
+   from its reduced cost; a basic variable gets the allowable change of its cost (ratio test along its tableau row) and the
+   non-basic variable that would enter.  An entry counts where it exceeds the default pivot tolerance (mvx_init_smcp); +inf
+   means no limit.  Pure: the handle is only read.  Bit-identical to mvx_bnb_ranges (mvx_bnb.h).  Returns 0; -1 a null
+   argument; -2 device out of memory (nothing written); -3 the handle's status is not MVX_OPT or it has no tableau. */
+int mvx_ranges(const mvx_prob *P, double *val, int *var);
+/* the tableau rows one workgroup of the column-wise ratio test (k_rangecols) walks: up to this many rows are one chunk */
+int mvx_ranges_chunk(void);
 /* Primal rounding heuristic (DESIGN.md "Primal rounding heuristic") on `count` solved handles, one device launch: each
    handle's column values rounded (mode 1) and filled greedily (mode 2), checked against the model of `root` -- its rows
    1..m0 (m0 = root's row count; rows a handle has beyond them, cut rows, are ignored), row bounds, column bounds and

@@ -344,6 +344,21 @@ int mvx_bnb_fractional_bounds(const mvx_lp_api *api, const void *prob);
 int mvx_bnb_penalties(const mvx_lp_api *api, const void *prob, const int *cols, int count, double tol, double *pen_down, double *pen_up,
                       int *arg_down, int *arg_up);
 
+/* Sensitivity ranges (DESIGN.md "Sensitivity ranges (ranges)"), host twin of mvx_ranges for one solved handle: val
+   (m+n+1) x 6 doubles (ACT_DN, ACT_UP, OBJ_DN, OBJ_UP, COST_DN, COST_UP) and var (m+n+1) x 4 ints (LIM_DN, LIM_UP, ENT_DN,
+   ENT_UP) by variable number, row 0 zero.  Works through the table only (get_tableau, get_basis, row and column bounds,
+   get_obj_dir, get_status, get_num_rows, get_num_cols); the handle is not changed; entries count above the default pivot
+   tolerance.  The same bits as mvx_ranges.  Returns 0; -1 a null argument; -2 the table lacks an accessor it needs (or
+   get_tableau / get_basis failed); -3 the handle is not MVX_OPT */
+int mvx_bnb_ranges(const mvx_lp_api *api, const void *prob, double *val, int *var);
+/* The text report of those tables, one line per variable k = 1..m+n, written to `path` (NULL: stdout):
+     k name st value act_dn lim_dn act_up lim_up obj_dn obj_up cost_dn ent_dn cost_up ent_up
+   name is R<i> for an auxiliary and the column's name, or C<j> without one, for a structural (names are read from the gfx950
+   engine's handles only; another table gives C<j>); st one of B NL NU NF NS; value the variable's value (get_row_prim's /
+   get_col_prim's bits, from the tableau and the bounds); doubles as %.17g.  Returns 0; -1 a null argument; -2 the table lacks
+   an accessor; -3 the handle is not MVX_OPT; -4 the file cannot be written */
+int mvx_bnb_print_ranges(const mvx_lp_api *api, const void *prob, const double *val, const int *var, const char *path);
+
 /* Primal rounding heuristic (DESIGN.md "Primal rounding heuristic"), host twin of mvx_round_many for one solved handle:
    the node LP's column values (get_col_prim) rounded, checked against rows 1..m0 of `root` (m0 = its row count; cut
    rows are ignored), root's column bounds and objective, and with mode 2 filled greedily.  *obj the candidate's

@@ -15,6 +15,8 @@ LIB_PATH = os.path.join(_HERE, "lib", "libmvolps_amd.so")
 _EXTRA = {
     "del_rows": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "del_rows_many": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "ranges": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "ranges_chunk": (C.c_int, []),
     "device_count": (C.c_int, []),
     "set_device": (C.c_int, [C.c_int]),
     "profile_enable": (None, [C.c_int]),

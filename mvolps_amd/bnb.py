@@ -5,6 +5,7 @@ branch_and_bound(prob, ...) mirrors `int branchAndBound(glp_prob*, MVOLP::Parame
 /root/reference/2test.cpp:85-149).
 """
 import ctypes as C
+import os
 
 from . import capi
 
@@ -238,6 +239,14 @@ def _bind(lib):
     lib.mvx_polish_many.argtypes = [C.c_void_p, C.c_int, _DP, C.c_int, _DP, _IP, _IP]
     lib.mvx_bnb_polish.restype = C.c_int
     lib.mvx_bnb_polish.argtypes = [C.c_void_p, C.c_void_p, _DP, C.c_int, _DP, _IP, _IP]
+    lib.mvx_ranges.restype = C.c_int
+    lib.mvx_ranges.argtypes = [C.c_void_p, _DP, _IP]
+    lib.mvx_ranges_chunk.restype = C.c_int
+    lib.mvx_ranges_chunk.argtypes = []
+    lib.mvx_bnb_ranges.restype = C.c_int
+    lib.mvx_bnb_ranges.argtypes = [C.c_void_p, C.c_void_p, _DP, _IP]
+    lib.mvx_bnb_print_ranges.restype = C.c_int
+    lib.mvx_bnb_print_ranges.argtypes = [C.c_void_p, C.c_void_p, _DP, _IP, C.c_char_p]
     lib.mvx_generateCutGMI.restype = C.c_int
     lib.mvx_generateCutGMI.argtypes = [C.c_void_p, C.c_void_p, C.c_int, _IP, _DP, _DP, _DP]
     lib.mvx_generateCut3.restype = C.c_int
@@ -609,6 +618,46 @@ def polish_many(root, xs, max_moves=1000, table=False):
                 break
             obj[t], moves[t], ok[t] = o.value, mv.value, good.value
     return rc, x, obj[:k], moves[:k], ok[:k]
+
+
+RANGE_VAL = ("ACT_DN", "ACT_UP", "OBJ_DN", "OBJ_UP", "COST_DN", "COST_UP")
+RANGE_VAR = ("LIM_DN", "LIM_UP", "ENT_DN", "ENT_UP")
+
+
+def ranges(prob, table=False):
+    """The sensitivity ranges (DESIGN.md "Sensitivity ranges (ranges)") of the solved handle `prob`.  table=False: mvx_ranges, the
+    gfx950 engine's kernels; otherwise the host twin mvx_bnb_ranges through `table` (None = the gfx950 engine's table).
+    Returns (rc, val, var): val (m + n + 1, 6) doubles with the columns RANGE_VAL, var (m + n + 1, 4) ints with the columns
+    RANGE_VAR, by variable number (auxiliaries 1..m, then the structurals); row 0 is zero."""
+    import numpy as np
+
+    rows = prob.m + prob.n + 1
+    val = np.zeros((rows, 6), dtype=np.float64)
+    var = np.zeros((rows, 4), dtype=np.int32)
+    DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    if table is False:
+        rc = lib().mvx_ranges(prob.h, val.ctypes.data_as(DP), var.ctypes.data_as(IP))
+    else:
+        tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
+        rc = lib().mvx_bnb_ranges(tptr, prob.h, val.ctypes.data_as(DP), var.ctypes.data_as(IP))
+    return rc, val, var
+
+
+def ranges_chunk():
+    """mvx_ranges_chunk: the tableau rows one workgroup of k_rangecols walks."""
+    return lib().mvx_ranges_chunk()
+
+
+def print_ranges(prob, val, var, path=None, table=None):
+    """mvx_bnb_print_ranges: the text report of ranges() for `prob` (through `table`; None = the gfx950 engine's table), one line
+    per variable, to `path` (None: stdout).  Returns the return code."""
+    import numpy as np
+
+    val = np.ascontiguousarray(val, dtype=np.float64)
+    var = np.ascontiguousarray(var, dtype=np.int32)
+    tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
+    return lib().mvx_bnb_print_ranges(tptr, prob.h, val.ctypes.data_as(C.POINTER(C.c_double)), var.ctypes.data_as(C.POINTER(C.c_int)),
+                                      os.fsencode(path) if path is not None else None)
 
 
 def rc_tighten_many(probs, cutoffs, tol=1e-9):

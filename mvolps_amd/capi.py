@@ -264,6 +264,15 @@ class Prob:
             raise RuntimeError("no basis")
         return head, nb, flag
 
+    def ranges(self):
+        """mvx_ranges (the gfx950 engine's library only): the sensitivity ranges of the solved handle.  Returns (rc, val, var):
+        val (m + n + 1, 6) doubles and var (m + n + 1, 4) ints by variable number, row 0 zero (columns: bnb.RANGE_VAL / RANGE_VAR)."""
+        rows = self.m + self.n + 1
+        val = np.zeros((rows, 6), dtype=np.float64)
+        var = np.zeros((rows, 4), dtype=np.int32)
+        rc = self.api.ranges(self.h, _dp(val), _ip(var))
+        return rc, val, var
+
     def eval_tab_row(self, k):
         n = self.n
         ind = np.zeros(n + 1, dtype=np.int32)

@@ -10,6 +10,7 @@
 #include <chrono>
 #include <cfloat>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <deque>
@@ -55,6 +56,7 @@ extern "C" int mvx_polish_many(const mvx_prob *root, int count, double *x, int m
     __attribute__((weak));
 extern "C" int mvx_del_rows(mvx_prob *P, int nrs, const int *num) __attribute__((weak));
 extern "C" int mvx_del_rows_many(mvx_prob *const *Ps, int count, const int *off, const int *rows) __attribute__((weak));
+extern "C" const char *mvx_get_col_name(const mvx_prob *P, int j) __attribute__((weak));
 
 namespace {
 
@@ -923,6 +925,125 @@ static double tab_bound(double b) { // the table reports an absent bound as -+DB
   return b <= -DBL_MAX ? -inf : b >= DBL_MAX ? inf : b;
 }
 static double round_tol(double b) { return 1e-9 * std::max(1.0, std::fabs(b)); } // a row bound's feasibility tolerance
+
+// ---- sensitivity ranges (DESIGN.md "Sensitivity ranges (ranges)") ----
+
+// What the ranges and their report read of a solved handle: the packed tableau, the basis and the bounds by variable number
+struct RangeView {
+  int m = 0, n = 0, maxdir = 1;
+  std::vector<double> T, lb, ub; // T (m+1) x (n+1); lb / ub [m+n+1], +-inf when absent
+  std::vector<int> head, nb, flag;
+};
+
+// 0; -2 an accessor is missing or failed; -3 the handle is not MVX_OPT
+static int read_range_view(const mvx_lp_api *api, const void *P, RangeView &V) {
+  if (!api->get_tableau || !api->get_basis || !api->get_row_lb || !api->get_row_ub || !api->get_col_lb || !api->get_col_ub || !api->get_status ||
+      !api->get_num_rows || !api->get_num_cols)
+    return -2;
+  if (api->get_status(P) != MVX_OPT) return -3;
+  const int m = V.m = api->get_num_rows(P), n = V.n = api->get_num_cols(P);
+  V.maxdir = (api->get_obj_dir && api->get_obj_dir(P) == MVX_MIN) ? 0 : 1;
+  V.T.assign((size_t)(m + 1) * (size_t)(n + 1), 0.0);
+  V.head.assign((size_t)m + 1, 0);
+  V.nb.assign((size_t)n + 1, 0);
+  V.flag.assign((size_t)n + 1, 0);
+  if (api->get_basis(P, V.head.data(), V.nb.data(), V.flag.data()) != 0 || api->get_tableau(P, V.T.data()) != 0) return -2;
+  V.lb.assign((size_t)m + n + 1, 0.0);
+  V.ub.assign((size_t)m + n + 1, 0.0);
+  for (int i = 1; i <= m; i++) {
+    V.lb[(size_t)i] = tab_bound(api->get_row_lb(P, i));
+    V.ub[(size_t)i] = tab_bound(api->get_row_ub(P, i));
+  }
+  for (int j = 1; j <= n; j++) {
+    V.lb[(size_t)(m + j)] = tab_bound(api->get_col_lb(P, j));
+    V.ub[(size_t)(m + j)] = tab_bound(api->get_col_ub(P, j));
+  }
+  return 0;
+}
+
+// The host twin of k_rangecols / k_rangefin / k_rangerows: the same tests, the same divisions, one walk over ascending rows
+// (part A) and ascending positions (part B) with a strict compare -- the same bits.
+static void host_ranges(const RangeView &V, double tol, double *val, int *var) {
+  const int m = V.m, n = V.n;
+  const size_t ldt = (size_t)n + 1;
+  const double inf = std::numeric_limits<double>::infinity();
+  std::fill(val, val + (size_t)(m + n + 1) * 6, 0.0);
+  std::fill(var, var + (size_t)(m + n + 1) * 4, 0);
+  const double *r0 = V.T.data();
+  for (int q = 1; q <= n; q++) { // part A
+    double tu = inf, td = inf;
+    int iu = 0, id = 0;
+    for (int i = 1; i <= m; i++) {
+      const double e = V.T[(size_t)i * ldt + (size_t)q];
+      const double ae = std::fabs(e);
+      if (!(ae > tol)) continue;
+      const double beta = V.T[(size_t)i * ldt];
+      const double lb = V.lb[(size_t)V.head[(size_t)i]], ub = V.ub[(size_t)V.head[(size_t)i]];
+      const double su = std::fmax(ub - beta, 0.0), sl = std::fmax(beta - lb, 0.0);
+      const bool hu = ub != inf, hl = lb != -inf, pos = e > 0.0;
+      if (pos ? hu : hl) {
+        const double t = (pos ? su : sl) / ae;
+        if (t < tu) {
+          tu = t;
+          iu = i;
+        }
+      }
+      if (pos ? hl : hu) {
+        const double t = (pos ? sl : su) / ae;
+        if (t < td) {
+          td = t;
+          id = i;
+        }
+      }
+    }
+    const int k = V.nb[(size_t)q], f = V.flag[(size_t)q];
+    const double d = std::fabs(r0[q]);
+    const bool lo = f == MVX_NL || f == MVX_NF, hi = f == MVX_NU || f == MVX_NF;
+    const bool cu = V.maxdir ? lo : hi, cd = V.maxdir ? hi : lo;
+    const double none = d > 0.0 ? inf : 0.0;
+    double *v = val + (size_t)k * 6;
+    int *w = var + (size_t)k * 4;
+    v[0] = td;
+    v[1] = tu;
+    v[2] = td == inf ? none : d * td;
+    v[3] = tu == inf ? none : d * tu;
+    v[4] = cd ? d : inf;
+    v[5] = cu ? d : inf;
+    w[0] = id ? V.head[(size_t)id] : 0;
+    w[1] = iu ? V.head[(size_t)iu] : 0;
+  }
+  for (int i = 1; i <= m; i++) { // part B
+    const double *ri = &V.T[(size_t)i * ldt];
+    double bd = inf, bu = inf;
+    int qd = 0, qu = 0;
+    for (int q = 1; q <= n; q++) {
+      const double e = ri[q];
+      if (!(std::fabs(e) > tol)) continue;
+      const int f = V.flag[(size_t)q];
+      const bool inc = f == MVX_NL || f == MVX_NF, dec = f == MVX_NU || f == MVX_NF;
+      const bool down = (inc && e < 0.0) || (dec && e > 0.0);
+      const bool up = (inc && e > 0.0) || (dec && e < 0.0);
+      if (!down && !up) continue;
+      const double r = std::fabs(r0[q]) / std::fabs(e);
+      if (down && r < bd) {
+        bd = r;
+        qd = q;
+      }
+      if (up && r < bu) {
+        bu = r;
+        qu = q;
+      }
+    }
+    const int k = V.head[(size_t)i];
+    const int vd = qd ? V.nb[(size_t)qd] : 0, vu = qu ? V.nb[(size_t)qu] : 0;
+    double *v = val + (size_t)k * 6;
+    int *w = var + (size_t)k * 4;
+    v[4] = V.maxdir ? bd : bu;
+    v[5] = V.maxdir ? bu : bd;
+    w[2] = V.maxdir ? vd : vu;
+    w[3] = V.maxdir ? vu : vd;
+  }
+}
 
 // 0, or -2 when the table lacks an accessor of the rows, the bounds or the column kinds
 static int read_host_model(const mvx_lp_api *api, const void *root, HostModel &M) {
@@ -4117,6 +4238,59 @@ int mvx_bnb_polish(const mvx_lp_api *api, const void *root, double *x, int max_m
   const int rc = read_host_model(api, root, M);
   if (rc != 0) return rc;
   return polish_host(M, x, max_moves, obj, moves, ok);
+}
+
+int mvx_bnb_ranges(const mvx_lp_api *api, const void *prob, double *val, int *var) {
+  if (!api) api = &g_hip_api;
+  if (!prob || !val || !var) return -1;
+  RangeView V;
+  const int rc = read_range_view(api, prob, V);
+  if (rc != 0) return rc;
+  host_ranges(V, default_smcp().tol_piv, val, var);
+  return 0;
+}
+
+int mvx_bnb_print_ranges(const mvx_lp_api *api, const void *prob, const double *val, const int *var, const char *path) {
+  if (!api) api = &g_hip_api;
+  if (!prob || !val || !var) return -1;
+  RangeView V;
+  const int rc = read_range_view(api, prob, V);
+  if (rc != 0) return rc;
+  const int m = V.m, n = V.n;
+  std::vector<int> row((size_t)m + n + 1, 0), posn((size_t)m + n + 1, 0); // tableau row / non-basic position of a variable
+  for (int i = 1; i <= m; i++) row[(size_t)V.head[(size_t)i]] = i;
+  for (int q = 1; q <= n; q++) posn[(size_t)V.nb[(size_t)q]] = q;
+  FILE *out = path ? std::fopen(path, "w") : stdout;
+  if (!out) return -4;
+  const bool named = api == &g_hip_api && mvx_get_col_name; // names live in the gfx950 engine's handles only
+  for (int k = 1; k <= m + n; k++) {
+    char name[64];
+    const char *nm = (named && k > m) ? mvx_get_col_name((const mvx_prob *)prob, k - m) : nullptr;
+    if (!nm) {
+      std::snprintf(name, sizeof name, "%c%d", k <= m ? 'R' : 'C', k <= m ? k : k - m);
+      nm = name;
+    }
+    const char *st = "B";
+    double x = 0.0;
+    if (row[(size_t)k]) {
+      x = V.T[(size_t)row[(size_t)k] * ((size_t)n + 1)];
+    } else {
+      const int f = V.flag[(size_t)posn[(size_t)k]];
+      st = f == MVX_NL ? "NL" : f == MVX_NU ? "NU" : f == MVX_NF ? "NF" : "NS";
+      x = f == MVX_NL ? V.lb[(size_t)k] : f == MVX_NU ? V.ub[(size_t)k] : f == MVX_NS ? V.lb[(size_t)k] : 0.0;
+    }
+    const double *v = val + (size_t)k * 6;
+    const int *w = var + (size_t)k * 4;
+    std::fprintf(out, "%d %s %s %.17g %.17g %d %.17g %d %.17g %.17g %.17g %d %.17g %d\n", k, nm, st, x, v[0], w[0], v[1], w[1], v[2], v[3],
+                 v[4], w[2], v[5], w[3]);
+  }
+  const bool bad = std::ferror(out) != 0;
+  if (path) {
+    if (std::fclose(out) != 0) return -4;
+  } else {
+    std::fflush(out);
+  }
+  return bad ? -4 : 0;
 }
 
 int mvx_bnb_conflict_graph(const mvx_lp_api *api, const void *model, unsigned long long *adj, long long *edges) {

@@ -586,6 +586,8 @@ int mvx_branch_penalties_many(const mvx_prob *const *Ps, int count, const int *c
                               double *pen_up, int *arg_down, int *arg_up) {
   return mvx::engine_penalties_many(Ps, count, cols, col_off, tol, pen_down, pen_up, arg_down, arg_up);
 }
+int mvx_ranges(const mvx_prob *P, double *val, int *var) { return mvx::engine_ranges(P, g_tol_piv, val, var); }
+int mvx_ranges_chunk(void) { return mvx::RANGE_CHUNK; }
 int mvx_round_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, int mode, double *obj, int *found, double *x) {
   return mvx::engine_round_many(root, Ps, count, mode, obj, found, x);
 }

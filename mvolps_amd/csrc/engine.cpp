@@ -2707,6 +2707,38 @@ int engine_penalties_many(const mvx_prob *const *Ps, int count, const int *cols,
   return 0;
 }
 
+// ------------------------------------------------------------------ sensitivity ranges (k_rangecols, k_rangefin, k_rangerows)
+// Post-optimal ranges of one solved handle (mvx_ranges): nothing goes up but the kernels' arguments, which travel by value;
+// three launches read the tableau, the basis and the bounds where they lie in the slab, one copy brings both tables back.
+// The handle is only read.  Return codes: 0; -1 a null argument; -2 device out of memory (nothing written); -3 a handle whose
+// status is not MVX_OPT or that has no tableau.
+int engine_ranges(const mvx_prob *P, double tol, double *val, int *var) {
+  if (!P || !val || !var) return -1;
+  if (!P->valid || P->status != MVX_OPT || P->m < 1 || P->n < 1) return -3;
+  const int m = P->m, n = P->n;
+  const size_t rows = (size_t)m + (size_t)n + 1;
+  const int nchunks = (m + RANGE_CHUNK - 1) / RANGE_CHUNK;
+  NodeCall f(NodeFlush::AtEntry, NodeResults::Device);
+  // back: [val][var]; device only: [partial minima][their rows]
+  const size_t o_val = f.out(rows * 6 * 8), o_var = f.out(rows * 4 * 4);
+  const size_t o_pt = f.dev((size_t)2 * nchunks * (size_t)(n + 1) * 8), o_pi = f.dev((size_t)2 * nchunks * (size_t)(n + 1) * 4);
+  if (!f.reserve()) return -2;
+  unsigned char *hb = f.hb, *db = f.db;
+  RangeArgs a;
+  a.nd = node_ref(P);
+  a.blb = P->d_blb; a.bub = P->d_bub;
+  a.pt = (double *)(db + o_pt); a.pi = (int *)(db + o_pi);
+  a.val = (double *)(db + o_val); a.var = (int *)(db + o_var);
+  a.tol = tol; a.n = n; a.nchunks = nchunks; a.maxdir = P->dir == MVX_MAX ? 1 : 0; a.pad = 0;
+  launch_ranges(a, f.stream());
+  f.fetch();
+  std::memcpy(val, hb + o_val, rows * 6 * 8);
+  std::memcpy(var, hb + o_var, rows * 4 * 4);
+  std::memset(val, 0, 6 * 8); // row 0: no variable
+  std::memset(var, 0, 4 * 4);
+  return 0;
+}
+
 // ------------------------------------------------------------------ reduced-cost tightening (k_rcfix)
 // Reduced-cost bound tightening of `count` solved handles (mvx_rc_tighten_many): one upload of the descriptors and the
 // kinds, one k_rcfix launch, one copy back; the per-position results are mapped to columns through the nvar mirror and

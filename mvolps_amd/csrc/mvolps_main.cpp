@@ -1,7 +1,7 @@
 // mvolps -- command-line front end over libmvolps_amd.so; counterpart of MVOLPS's main
 // (/root/reference/2test.cpp:13-157): same flags, same dispatch on the file extension
 // (2test.cpp:65-81), then initProblem (util.cpp:277-292) and branchAndBound (bs.cpp:54).
-// Extra flags of this build: --repaired (reference_quirks = 0), --max-nodes N, --events FILE.
+// Extra flags of this build: --repaired (reference_quirks = 0), --max-nodes N, --events FILE, --ranges FILE.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -40,6 +40,8 @@ int main(int argc, char **argv) {
               << "File input options:\n"
               << "  -f/--file [FILENAME.{mps|lp}]\n\n"
               << "  --events [FILE] write the B&B event stream (one line per event) to FILE\n"
+              << "  --ranges [FILE] solve the root LP, write its sensitivity ranges (one line per row and column: activity ranges,\n"
+              << "                  objective changes, allowable cost changes) to FILE, then run as without the flag\n"
               << "Output verbosity options:\n"
               << "  -s/--silent\n  -v/--verbose\n  -d/--debug\n  -so/--solver-output\n\n"
               << "Algorithm strategy options:\n"
@@ -261,6 +263,26 @@ int main(int argc, char **argv) {
   if (input.CMDOptionExists("--max-nodes")) params.max_nodes = std::atoi(input.getCMDOption("--max-nodes").c_str());
   if (input.CMDOptionExists("--server"))
     std::fprintf(stderr, "--server: the ZeroMQ sink is not part of this build; use --events FILE for the same stream\n");
+
+  if (input.CMDOptionExists("--ranges")) {
+    const std::string &path = input.getCMDOption("--ranges");
+    if (path.empty() || path[0] == '-') { // the end of the line, or the next flag
+      std::fprintf(stderr, "Unknown parameter value for --ranges\n");
+      return -1;
+    }
+    // the root LP as the tree will first solve it, on a copy: the run below starts from the handle as it was read
+    mvx_prob *root = mvx_create_prob();
+    mvx_copy_prob(root, prob, MVX_ON);
+    if (!params.reference_quirks) mvx_bnb_integral_bounds(nullptr, root);
+    mvx_simplex(root, nullptr);
+    const size_t rows = (size_t)mvx_get_num_rows(root) + (size_t)mvx_get_num_cols(root) + 1;
+    std::vector<double> val(rows * 6);
+    std::vector<int> var(rows * 4);
+    int rrc = mvx_ranges(root, val.data(), var.data());
+    if (rrc == 0) rrc = mvx_bnb_print_ranges(nullptr, root, val.data(), var.data(), path.c_str());
+    if (rrc != 0) std::fprintf(stderr, "--ranges: no report (%d): the root LP has no optimal basis, or %s cannot be written\n", rrc, path.c_str());
+    mvx_delete_prob(root);
+  }
 
   mvx_bnb_result res;
   const int brc = mvx_branchAndBound(nullptr, prob, &params, &res);

@@ -281,6 +281,20 @@ struct PenArgs {
   int count, pad;
 };
 
+// arguments of k_rangecols / k_rangefin / k_rangerows (mvx_ranges, DESIGN.md "Sensitivity ranges (ranges)"): one solved handle,
+// the bounds of its basic variables, the partial records of the column-wise ratio test and the two result tables
+constexpr int RANGE_CHUNK = 256; // tableau rows one k_rangecols workgroup walks: m <= RANGE_CHUNK is one chunk
+struct RangeArgs {
+  NodeRef nd;
+  const double *blb, *bub; // [m+1] bounds of the basic variables, +-inf when absent
+  double *pt;              // [2][nchunks][n+1] partial minima of part A: side 0 down, side 1 up
+  int *pi;                 // [2][nchunks][n+1] their tableau rows (0x7fffffff: none)
+  double *val;             // [m+n+1][6] ACT_DN, ACT_UP, OBJ_DN, OBJ_UP, COST_DN, COST_UP
+  int *var;                // [m+n+1][4] LIM_DN, LIM_UP, ENT_DN, ENT_UP
+  double tol;              // |T[i][q]| must exceed it
+  int n, nchunks, maxdir, pad; // maxdir: 1 under MVX_MAX
+};
+
 // one handle of a rounding launch (k_round, mvx_round_many)
 using RndNode = NodeRef;
 
@@ -528,6 +542,7 @@ void launch_copy_many(const CopyBatch &b, hipStream_t);
 void launch_gmi(const GmiArgs &a, hipStream_t);
 void launch_classify(const ClsArgs &a, hipStream_t);
 void launch_penalty(const PenArgs &a, hipStream_t);
+void launch_ranges(const RangeArgs &a, hipStream_t);
 void launch_round(const RndArgs &a, hipStream_t);
 void launch_rcfix(const RcArgs &a, hipStream_t);
 void launch_prop(const PropArgs &a, hipStream_t);

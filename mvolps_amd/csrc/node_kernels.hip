@@ -1,5 +1,5 @@
 // node_kernels.hip -- gfx950 kernels of the batched node entries of branch and bound (engine.cpp: engine_*_many): GMI cuts,
-// classification, branching penalties, the rounding heuristic, reduced-cost tightening, bound propagation, bound lists, the
+// classification, branching penalties, sensitivity ranges, the rounding heuristic, reduced-cost tightening, bound propagation, bound lists, the
 // diving pick, objective replacement, the feasibility pump's step, and the scores and the batched append of a cut round.  Each takes its arguments by value and the handles it works on as an array of descriptors (NodeRef and what
 // the kernel needs beyond it, mvx_internal.hpp).  Same flags as kernels.hip: -ffp-contract=off, so every kernel has the bits
 // of its host twin.
@@ -343,6 +343,202 @@ __global__ __launch_bounds__(256) void k_penalty(PenArgs a) {
 
 void launch_penalty(const PenArgs &a, hipStream_t s) {
   hipLaunchKernelGGL(k_penalty, dim3((unsigned)a.count), dim3(256), 0, s, a);
+}
+
+// ---------------------------------------------------------------------------- k_rangecols / k_rangefin / k_rangerows
+// Sensitivity ranges of a solved LP (mvx_ranges, DESIGN.md "Sensitivity ranges (ranges)").
+//
+// Part A, activity ranging of the non-basic positions, is a ratio test DOWN every column of the row-major tableau.
+// k_rangecols: grid (strips of 64 positions, chunks of RANGE_CHUNK rows), 256 threads.  A lane owns one position, the four
+// waves take the rows of the chunk in turn (row i0 + wave, i0 + wave + 4, ...), so a wave's read of a row is 64 consecutive
+// doubles and the row's own numbers (basic value, bounds of its basic variable) are the same in every lane.  Per row and
+// direction one correctly rounded quotient (xdiv), RANGE_AHEAD rows at a time: their entries are requested together and their
+// quotients formed without a branch between them; a lane keeps (t, row) per direction with a strict compare over ascending
+// rows; the four waves meet in LDS under the order (t, row) and one record per (chunk, position) goes to scratch.
+// k_rangefin: a thread per position takes the chunks in ascending order, strict compare -- the lowest row wins a tie, as in the
+// host twin's single walk -- and writes the row of the position's variable in both result tables.
+//
+// Part B, cost ranging of the basic variables, is k_penalty's test for every tableau row: k_rangerows, one workgroup per row,
+// rows 0 and i streamed coalesced, two running (r, q) minima, wave shuffles, four partials through LDS.
+//
+// min is exact and every quotient and product is rounded once: the tables have the host twin's bits.
+constexpr int RANGE_AHEAD = 8; // tableau rows (k_rangecols) / positions (k_rangerows) a thread requests before it uses the first
+struct RngMin {
+  double t;
+  int i;
+};
+__device__ __forceinline__ RngMin rng_min(RngMin a, RngMin b) { // smaller t; equal t: lower row (0x7fffffff: none)
+  return (b.t < a.t || (b.t == a.t && b.i < a.i)) ? b : a;
+}
+
+__global__ __launch_bounds__(256) void k_rangecols(RangeArgs a) {
+  __shared__ double s_t[2][4][64];
+  __shared__ int s_i[2][4][64];
+  const int lane = TIDX & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(TIDX >> 6);
+  const int q = 1 + (int)blockIdx.x * 64 + lane;
+  const int m = a.nd.m, ld = a.nd.ld;
+  const int i0 = 1 + (int)blockIdx.y * RANGE_CHUNK;
+  const int i1 = (i0 + RANGE_CHUNK - 1 < m) ? i0 + RANGE_CHUNK - 1 : m;
+  const double inf = __builtin_huge_val();
+  const double tol = a.tol;
+  RngMin dn = {inf, 0x7fffffff}, up = {inf, 0x7fffffff};
+  if (q <= a.n) {
+    const double *col = a.nd.T + q;
+    // RANGE_AHEAD rows of this wave are requested before the first is used (a row past the chunk reads row i1 and is skipped)
+    for (int ib = i0 + wv; ib <= i1; ib += 4 * RANGE_AHEAD) {
+      double e[RANGE_AHEAD];
+#pragma unroll
+      for (int u = 0; u < RANGE_AHEAD; u++) {
+        const int i = ib + 4 * u;
+        e[u] = col[(size_t)(i <= i1 ? i : i1) * (size_t)ld];
+      }
+      // the quotients of the RANGE_AHEAD rows do not depend on each other: no branch stands between them, so their division
+      // sequences overlap.  A side that does not count divides +inf by 1: +inf never passes the strict compare
+      double tu[RANGE_AHEAD], td[RANGE_AHEAD];
+#pragma unroll
+      for (int u = 0; u < RANGE_AHEAD; u++) {
+        const int i = ib + 4 * u, ic = i <= i1 ? i : i1;
+        const double beta = a.nd.T[(size_t)ic * (size_t)ld], lb = a.blb[ic], ub = a.bub[ic]; // the same in every lane
+        const double su = fmax(ub - beta, 0.0), sl = fmax(beta - lb, 0.0); // room towards the upper / the lower bound
+        const bool hu = ub != inf, hl = lb != -inf;
+        const double ae = fabs(e[u]);
+        const bool counts = i <= i1 && ae > tol;
+        const bool pos = e[u] > 0.0;
+        // x_k up: the row's basic variable moves towards its upper bound when e > 0, its lower when e < 0; x_k down: the reverse
+        const bool oku = counts && (pos ? hu : hl), okd = counts && (pos ? hl : hu);
+        const double den = counts ? ae : 1.0;
+        tu[u] = xdiv(oku ? (pos ? su : sl) : inf, den);
+        td[u] = xdiv(okd ? (pos ? sl : su) : inf, den);
+      }
+#pragma unroll
+      for (int u = 0; u < RANGE_AHEAD; u++) { // ascending rows, strict compare
+        const int i = ib + 4 * u;
+        if (tu[u] < up.t) up = RngMin{tu[u], i};
+        if (td[u] < dn.t) dn = RngMin{td[u], i};
+      }
+    }
+  }
+  s_t[0][wv][lane] = dn.t; s_i[0][wv][lane] = dn.i;
+  s_t[1][wv][lane] = up.t; s_i[1][wv][lane] = up.i;
+  __syncthreads();
+  if (TIDX < 128) { // waves 0 and 1: side 0 (down) and side 1 (up) of the 64 positions
+    const int side = TIDX >> 6;
+    RngMin b = {s_t[side][0][lane], s_i[side][0][lane]};
+    for (int w = 1; w < 4; w++) b = rng_min(b, RngMin{s_t[side][w][lane], s_i[side][w][lane]});
+    if (q <= a.n) {
+      const size_t o = ((size_t)side * (size_t)a.nchunks + blockIdx.y) * (size_t)(a.n + 1) + (size_t)q;
+      a.pt[o] = b.t;
+      a.pi[o] = b.i;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_rangefin(RangeArgs a) {
+  const int q = 1 + (int)blockIdx.x * 256 + TIDX;
+  if (q > a.n) return;
+  const double inf = __builtin_huge_val();
+  const size_t stride = (size_t)(a.n + 1), side1 = (size_t)a.nchunks * stride;
+  RngMin dn = {inf, 0x7fffffff}, up = {inf, 0x7fffffff};
+  for (int c = 0; c < a.nchunks; c++) { // ascending chunks hold ascending rows: strict compare keeps the lowest row
+    const size_t o = (size_t)c * stride + (size_t)q;
+    const double td = a.pt[o], tu = a.pt[side1 + o];
+    if (td < dn.t) dn = RngMin{td, a.pi[o]};
+    if (tu < up.t) up = RngMin{tu, a.pi[side1 + o]};
+  }
+  const int k = a.nd.nvar[q], f = a.nd.nflag[q];
+  const double d = fabs(a.nd.T[q]);
+  // how far c_k may rise / fall: the side the variable rests against, turned round under MIN
+  const bool lo = f == MVX_NL || f == MVX_NF, hi = f == MVX_NU || f == MVX_NF;
+  const bool cu = a.maxdir ? lo : hi, cd = a.maxdir ? hi : lo;
+  const double none = d > 0.0 ? inf : 0.0; // no row limits the move: inf * 0 is never formed
+  double *v = a.val + (size_t)k * 6;
+  int *w = a.var + (size_t)k * 4;
+  v[0] = dn.t;
+  v[1] = up.t;
+  v[2] = dn.t == inf ? none : d * dn.t;
+  v[3] = up.t == inf ? none : d * up.t;
+  v[4] = cd ? d : inf;
+  v[5] = cu ? d : inf;
+  w[0] = dn.i == 0x7fffffff ? 0 : a.nd.bvar[dn.i];
+  w[1] = up.i == 0x7fffffff ? 0 : a.nd.bvar[up.i];
+  w[2] = 0;
+  w[3] = 0;
+}
+
+__global__ __launch_bounds__(256) void k_rangerows(RangeArgs a) {
+  __shared__ double s_r[2][4];
+  __shared__ int s_q[2][4];
+  const int i = 1 + (int)blockIdx.x;
+  const double *r0 = a.nd.T;
+  const double *ri = a.nd.T + (size_t)i * (size_t)a.nd.ld;
+  const double tol = a.tol;
+  const double inf = __builtin_huge_val();
+  PenMin dn = {inf, 0x7fffffff}, up = {inf, 0x7fffffff};
+  for (int qb = 1 + TIDX; qb <= a.n; qb += 256 * RANGE_AHEAD) {
+    double e[RANGE_AHEAD], d[RANGE_AHEAD];
+    int f[RANGE_AHEAD];
+#pragma unroll
+    for (int u = 0; u < RANGE_AHEAD; u++) { // a position past the row reads position 0 and is skipped
+      const int q = qb + 256 * u;
+      const int o = q <= a.n ? q : 0;
+      e[u] = ri[o];
+      d[u] = r0[o];
+      f[u] = a.nd.nflag[o];
+    }
+    // as in k_rangecols: the quotients first, without a branch between them (a position that does not count divides +inf by 1)
+    double r[RANGE_AHEAD];
+    bool down[RANGE_AHEAD], upw[RANGE_AHEAD];
+#pragma unroll
+    for (int u = 0; u < RANGE_AHEAD; u++) {
+      const int q = qb + 256 * u;
+      const bool counts = q <= a.n && fabs(e[u]) > tol;
+      const bool inc = f[u] == MVX_NL || f[u] == MVX_NF, dec = f[u] == MVX_NU || f[u] == MVX_NF; // allowed directions s = +1 / -1
+      down[u] = counts && ((inc && e[u] < 0.0) || (dec && e[u] > 0.0));
+      upw[u] = counts && ((inc && e[u] > 0.0) || (dec && e[u] < 0.0));
+      const bool any = down[u] || upw[u];
+      r[u] = xdiv(any ? fabs(d[u]) : inf, any ? fabs(e[u]) : 1.0);
+    }
+#pragma unroll
+    for (int u = 0; u < RANGE_AHEAD; u++) { // ascending positions, strict compare
+      const int q = qb + 256 * u;
+      if (down[u] && r[u] < dn.r) dn = PenMin{r[u], q};
+      if (upw[u] && r[u] < up.r) up = PenMin{r[u], q};
+    }
+  }
+  dn = pen_wave_min(dn);
+  up = pen_wave_min(up);
+  const int lane = TIDX & 63, wv = TIDX >> 6;
+  if (lane == 0) {
+    s_r[0][wv] = dn.r; s_q[0][wv] = dn.q;
+    s_r[1][wv] = up.r; s_q[1][wv] = up.q;
+  }
+  __syncthreads();
+  if (TIDX == 0) {
+    PenMin bd = {s_r[0][0], s_q[0][0]}, bu = {s_r[1][0], s_q[1][0]};
+    for (int w = 1; w < 4; w++) {
+      bd = pen_min(bd, PenMin{s_r[0][w], s_q[0][w]});
+      bu = pen_min(bu, PenMin{s_r[1][w], s_q[1][w]});
+    }
+    const int qd = bd.q == 0x7fffffff ? 0 : a.nd.nvar[bd.q], qu = bu.q == 0x7fffffff ? 0 : a.nd.nvar[bu.q];
+    const int k = a.nd.bvar[i];
+    double *v = a.val + (size_t)k * 6;
+    int *w = a.var + (size_t)k * 4;
+    v[0] = 0.0; v[1] = 0.0; v[2] = 0.0; v[3] = 0.0;
+    v[4] = a.maxdir ? bd.r : bu.r;
+    v[5] = a.maxdir ? bu.r : bd.r;
+    w[0] = 0; w[1] = 0;
+    w[2] = a.maxdir ? qd : qu;
+    w[3] = a.maxdir ? qu : qd;
+  }
+}
+
+// val / var row 0 is zeroed by the host; every variable 1..m+n is basic in one row or non-basic in one position, so the two
+// writers together cover every other row exactly once
+void launch_ranges(const RangeArgs &a, hipStream_t s) {
+  hipLaunchKernelGGL(k_rangecols, dim3((unsigned)((a.n + 63) / 64), (unsigned)a.nchunks), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_rangefin, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_rangerows, dim3((unsigned)a.nd.m), dim3(256), 0, s, a);
 }
 
 // ---------------------------------------------------------------------------- k_round
