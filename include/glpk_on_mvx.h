@@ -49,6 +49,7 @@ typedef mvx_smcp glp_smcp;
 #define glp_add_rows mvx_add_rows         /* cut.cpp:23 */
 #define glp_add_cols mvx_add_cols         /* (model construction) */
 #define glp_set_mat_row mvx_set_mat_row   /* cut.cpp:40 */
+#define glp_set_mat_col mvx_set_mat_col   /* (model construction by columns) */
 #define glp_set_row_bnds mvx_set_row_bnds /* cut.cpp:43 */
 #define glp_set_col_bnds mvx_set_col_bnds /* bs.cpp:274,282 */
 #define glp_set_obj_coef mvx_set_obj_coef /* util.cpp:55 */
@@ -77,6 +78,7 @@ typedef mvx_smcp glp_smcp;
 #define glp_get_col_type mvx_get_col_type /* util.cpp:319 */
 #define glp_get_col_name mvx_get_col_name /* (readers keep column names; glp_copy_prob names flag, util.cpp:34) */
 #define glp_get_mat_row mvx_get_mat_row   /* gmi.cpp:84; util.cpp:349 */
+#define glp_get_mat_col mvx_get_mat_col   /* (model readers by columns) */
 #define glp_get_obj_dir mvx_get_obj_dir   /* util.cpp:51 */
 #define glp_eval_tab_row mvx_eval_tab_row /* gmi.cpp:36 */
 /* I/O + environment */

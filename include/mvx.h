@@ -286,6 +286,27 @@ int mvx_cut_scores(const mvx_prob *P, int k, const double *vals, double *dot, do
    for the next solve.  Returns 0; -1 bad arguments, nothing changed (k < 1, a null, a NaN, a handle without a valid tableau);
    -2 device out of memory: the model has the rows, the tableau is given up as mvx_add_rows gives it up. */
 int mvx_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rhs);
+/* Column append (DESIGN.md "Column append (add_cols)"): `k` dense structural columns join the model as columns n+1..n+k and,
+   where the handle has a valid tableau, the tableau and the basis in one device pass (k_addcols): the new columns are
+   non-basic at their resting bound, the basis and every other body entry keep their bits.  cols is k x (m+1) row-major:
+   cols[t*(m+1) + i] the coefficient of new column t in model row i = 1..m (entry 0 is not read); obj[t] its objective
+   coefficient; type[t] in MVX_FR..MVX_FX with lb[t] / ub[t] read as mvx_set_col_bnds reads them; kind[t] MVX_CV or MVX_IV
+   (kind == NULL: all MVX_CV).  The model ends as mvx_add_cols(k), mvx_set_mat_col, mvx_set_col_bnds, mvx_set_obj_coef and
+   mvx_set_col_kind leave it.  On a handle without a valid tableau only the model is edited (no device is needed).  Returns 0;
+   -1 bad arguments, nothing changed (a null, k < 1, a NaN, a type outside FR..FX, lb > ub on a DB column, a kind outside
+   CV / IV); -2 device out of memory: the model has the columns and the tableau is given up, as mvx_add_cut_rows gives it up. */
+int mvx_add_dense_cols(mvx_prob *P, int k, const double *cols, const double *obj, const int *type, const double *lb, const double *ub,
+                       const int *kind);
+/* The images mvx_add_dense_cols would write, without appending: dj[t] the reduced cost (row 0 of the image) of candidate column
+   t, img (nullable) k x (m+1) the whole images by tableau row 0..m.  With img == NULL only row 0 of the tableau is read.  Pure:
+   the handle is only read.  Bit-identical to mvx_bnb_price_cols (mvx_bnb.h).  Returns 0; -1 bad arguments; -2 device out of
+   memory, nothing written; -3 the handle has no valid tableau. */
+int mvx_price_cols(const mvx_prob *P, int k, const double *cols, const double *obj, double *dj, double *img);
+int mvx_price_cols_tile(void); /* candidate columns one k_addcols workgroup carries per pass over its rows */
+/* glp_set_mat_col / glp_get_mat_col (model layer, 1-based, element 0 ignored).  mvx_set_mat_col on a handle with a tableau gives
+   the tableau up, as mvx_add_cols does; mvx_get_mat_col returns the non-zeros in ascending row order. */
+void mvx_set_mat_col(mvx_prob *P, int j, int len, const int *ind, const double *val);
+int mvx_get_mat_col(const mvx_prob *P, int j, int *ind, double *val);
 /* Clique cuts (DESIGN.md "Clique cuts (cut_families)"): the conflict graph of the binary columns of `model` (integer, bounds 0
    and 1 exactly), two device launches (k_conflict_rows, k_conflict).  Columns j < k are adjacent when one of rows 1..m (m the
    handle's row count) forbids x_j = x_k = 1 with every other term at its least: (Lmin_i + a_ij) + a_ik > rub_i + tol(rub_i) on

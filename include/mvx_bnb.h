@@ -351,6 +351,13 @@ int mvx_bnb_penalties(const mvx_lp_api *api, const void *prob, const int *cols, 
    tolerance.  The same bits as mvx_ranges.  Returns 0; -1 a null argument; -2 the table lacks an accessor it needs (or
    get_tableau / get_basis failed); -3 the handle is not MVX_OPT */
 int mvx_bnb_ranges(const mvx_lp_api *api, const void *prob, double *val, int *var);
+
+/* Column append (DESIGN.md "Column append (add_cols)"), host twin of mvx_price_cols: the images of `k` candidate columns against
+   the tableau of `prob` -- cols k x (m+1) by model row, obj[k]; dj[t] row 0 of image t, img (nullable) k x (m+1) by tableau row.
+   Works through the table only (get_num_rows, get_num_cols, get_tableau, get_basis); the handle is not changed.  The same bits
+   as mvx_price_cols: 64 chains over the non-basic positions, the written tree, the base added last.  Returns 0; -1 bad
+   arguments; -2 the table lacks an accessor it needs (or get_tableau / get_basis failed) */
+int mvx_bnb_price_cols(const mvx_lp_api *api, const void *prob, int k, const double *cols, const double *obj, double *dj, double *img);
 /* The text report of those tables, one line per variable k = 1..m+n, written to `path` (NULL: stdout):
      k name st value act_dn lim_dn act_up lim_up obj_dn obj_up cost_dn ent_dn cost_up ent_up
    name is R<i> for an auxiliary and the column's name, or C<j> without one, for a structural (names are read from the gfx950

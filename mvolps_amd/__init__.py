@@ -17,6 +17,13 @@ _EXTRA = {
     "del_rows_many": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ranges": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "ranges_chunk": (C.c_int, []),
+    "add_dense_cols": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int),
+                                 C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "price_cols": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                             C.POINTER(C.c_double)]),
+    "price_cols_tile": (C.c_int, []),
+    "set_mat_col": (None, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    "get_mat_col": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     "device_count": (C.c_int, []),
     "set_device": (C.c_int, [C.c_int]),
     "profile_enable": (None, [C.c_int]),

@@ -247,6 +247,10 @@ def _bind(lib):
     lib.mvx_bnb_ranges.argtypes = [C.c_void_p, C.c_void_p, _DP, _IP]
     lib.mvx_bnb_print_ranges.restype = C.c_int
     lib.mvx_bnb_print_ranges.argtypes = [C.c_void_p, C.c_void_p, _DP, _IP, C.c_char_p]
+    lib.mvx_price_cols.restype = C.c_int
+    lib.mvx_price_cols.argtypes = [C.c_void_p, C.c_int, _DP, _DP, _DP, _DP]
+    lib.mvx_bnb_price_cols.restype = C.c_int
+    lib.mvx_bnb_price_cols.argtypes = [C.c_void_p, C.c_void_p, C.c_int, _DP, _DP, _DP, _DP]
     lib.mvx_generateCutGMI.restype = C.c_int
     lib.mvx_generateCutGMI.argtypes = [C.c_void_p, C.c_void_p, C.c_int, _IP, _DP, _DP, _DP]
     lib.mvx_generateCut3.restype = C.c_int
@@ -641,6 +645,28 @@ def ranges(prob, table=False):
         tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
         rc = lib().mvx_bnb_ranges(tptr, prob.h, val.ctypes.data_as(DP), var.ctypes.data_as(IP))
     return rc, val, var
+
+
+def price_cols(prob, cols, obj, table=False):
+    """The images of candidate columns against the tableau of `prob` (DESIGN.md "Column append (add_cols)").  table=False:
+    mvx_price_cols, the gfx950 engine's k_addcols; otherwise the host twin mvx_bnb_price_cols through `table` (None = the gfx950
+    engine's table).  cols is (k, m) or (k, m+1) as Prob.add_dense_cols takes it.  Returns (rc, dj array of k, img array (k, m+1))."""
+    import numpy as np
+
+    m = prob.m
+    obj = np.ascontiguousarray(np.atleast_1d(obj), dtype=np.float64)
+    k = len(obj)
+    cols = capi._cols_block(cols, k, m)
+    dj = np.zeros(k, dtype=np.float64)
+    img = np.zeros((k, m + 1), dtype=np.float64)
+    DP = C.POINTER(C.c_double)
+    if table is False:
+        rc = lib().mvx_price_cols(prob.h, k, cols.ctypes.data_as(DP), obj.ctypes.data_as(DP), dj.ctypes.data_as(DP), img.ctypes.data_as(DP))
+    else:
+        tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
+        rc = lib().mvx_bnb_price_cols(tptr, prob.h, k, cols.ctypes.data_as(DP), obj.ctypes.data_as(DP), dj.ctypes.data_as(DP),
+                                      img.ctypes.data_as(DP))
+    return rc, dj, img
 
 
 def ranges_chunk():

@@ -97,6 +97,18 @@ def _ip(a):
     return a.ctypes.data_as(_IP)
 
 
+def _cols_block(cols, k, m):
+    """k candidate columns as the C layout k x (m+1), entry 0 of each unused: from (k, m), (k, m+1) or, for k = 1, one vector."""
+    cols = np.asarray(cols, dtype=np.float64)
+    if cols.ndim == 1:
+        cols = cols.reshape(1, -1)
+    if cols.shape == (k, m):
+        cols = np.hstack([np.zeros((k, 1)), cols])
+    if cols.shape != (k, m + 1):
+        raise ValueError("columns need shape (%d, %d) or (%d, %d), got %r" % (k, m, k, m + 1, cols.shape))
+    return np.ascontiguousarray(cols, dtype=np.float64)
+
+
 class LpApi:
     """Function table of one engine library."""
 
@@ -184,6 +196,55 @@ class Prob:
         their auxiliary variables are basic, the device tableau in place.  Returns 0, or -1 with nothing changed."""
         num = np.concatenate([[0], np.asarray(list(rows), dtype=np.int32)]).astype(np.int32)
         return self.api.del_rows(self.h, len(num) - 1, _ip(num))
+
+    def add_dense_cols(self, cols, obj, types, lb, ub, kinds=None):
+        """mvx_add_dense_cols (the gfx950 engine's library only): k dense columns join the model as columns n+1..n+k and, where
+        the handle has a tableau, the live tableau (DESIGN.md "Column append (add_cols)").  cols is (k, m) -- cols[t, i-1] the
+        coefficient of new column t in model row i -- or (k, m+1) in the C layout (entry 0 unused).  Returns the return code."""
+        m = self.m
+        obj = np.ascontiguousarray(np.atleast_1d(obj), dtype=np.float64)
+        k = len(obj)
+        cols = _cols_block(cols, k, m)
+        types = np.ascontiguousarray(np.atleast_1d(types), dtype=np.int32)
+        lb = np.ascontiguousarray(np.atleast_1d(lb), dtype=np.float64)
+        ub = np.ascontiguousarray(np.atleast_1d(ub), dtype=np.float64)
+        if not (len(types) == len(lb) == len(ub) == k):
+            raise ValueError("add_dense_cols: obj, types, lb and ub need one entry per column")
+        kp = None
+        if kinds is not None:
+            kinds = np.ascontiguousarray(np.atleast_1d(kinds), dtype=np.int32)
+            if len(kinds) != k:
+                raise ValueError("add_dense_cols: kinds needs one entry per column")
+            kp = _ip(kinds)
+        return self.api.add_dense_cols(self.h, k, _dp(cols), _dp(obj), _ip(types), _dp(lb), _dp(ub), kp)
+
+    def price_cols(self, cols, obj, images=False):
+        """mvx_price_cols (the gfx950 engine's library only): the reduced costs, and with images=True the whole images (k, m+1) by
+        tableau row, that add_dense_cols would write for the candidate columns, without appending them.  Returns (rc, dj) or
+        (rc, dj, img)."""
+        m = self.m
+        obj = np.ascontiguousarray(np.atleast_1d(obj), dtype=np.float64)
+        k = len(obj)
+        cols = _cols_block(cols, k, m)
+        dj = np.zeros(k, dtype=np.float64)
+        if not images:
+            return self.api.price_cols(self.h, k, _dp(cols), _dp(obj), _dp(dj), None), dj
+        img = np.zeros((k, m + 1), dtype=np.float64)
+        rc = self.api.price_cols(self.h, k, _dp(cols), _dp(obj), _dp(dj), _dp(img))
+        return rc, dj, img
+
+    def set_mat_col(self, j, ind, val):
+        """mvx_set_mat_col: GLPK's shape, ind[0] / val[0] ignored."""
+        ind = np.ascontiguousarray(ind, dtype=np.int32)
+        val = np.ascontiguousarray(val, dtype=np.float64)
+        self.api.set_mat_col(self.h, j, len(ind) - 1, _ip(ind), _dp(val))
+
+    def get_mat_col(self, j):
+        m = self.m
+        ind = np.zeros(m + 1, dtype=np.int32)
+        val = np.zeros(m + 1, dtype=np.float64)
+        ln = self.api.get_mat_col(self.h, j, _ip(ind), _dp(val))
+        return ind[1 : ln + 1].copy(), val[1 : ln + 1].copy()
 
     # --- solve
     def simplex(self, it_lim=None, meth=None, tol=None):

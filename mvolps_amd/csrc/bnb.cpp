@@ -4250,6 +4250,44 @@ int mvx_bnb_ranges(const mvx_lp_api *api, const void *prob, double *val, int *va
   return 0;
 }
 
+// The host twin of k_addcols' pricing pass (DESIGN.md "Column append (add_cols)").  Image t, tableau row p: base + S, where
+// S sums w_q * T[p][q] over the non-basic positions q that hold an auxiliary i (w_q = -cols[t][i]) in 64 chains -- chain l takes
+// q = l+1, l+65, ... ascending, fma from +0.0, zero weights skipped -- the chains are combined by s[l] += s[l+h], h = 32 .. 1,
+// and the base (obj[t] in row 0, the coefficient of the row's basic auxiliary below it, else 0) is added last.
+int mvx_bnb_price_cols(const mvx_lp_api *api, const void *prob, int k, const double *cols, const double *obj, double *dj, double *img) {
+  if (!api) api = &g_hip_api;
+  if (!prob || k < 1 || !cols || !obj || !dj) return -1;
+  if (!api->get_num_rows || !api->get_num_cols || !api->get_tableau || !api->get_basis) return -2;
+  const int m = api->get_num_rows(prob), n = api->get_num_cols(prob);
+  const size_t ldt = (size_t)n + 1, crow = (size_t)m + 1;
+  std::vector<double> T((size_t)(m + 1) * ldt, 0.0);
+  std::vector<int> head((size_t)m + 1, 0), nb((size_t)n + 1, 0), flag((size_t)n + 1, 0);
+  if (api->get_basis(prob, head.data(), nb.data(), flag.data()) != 0 || api->get_tableau(prob, T.data()) != 0) return -2;
+  std::vector<double> w((size_t)n + 1, 0.0);
+  const int rows = img ? m + 1 : 1;
+  for (int t = 0; t < k; t++) {
+    const double *a = cols + (size_t)t * crow;
+    for (int q = 1; q <= n; q++) w[(size_t)q] = nb[(size_t)q] <= m ? -a[(size_t)nb[(size_t)q]] : 0.0;
+    for (int p = 0; p < rows; p++) {
+      const double *Tp = T.data() + (size_t)p * ldt;
+      double s[64];
+      for (int l = 0; l < 64; l++) {
+        double acc = 0.0;
+        for (int q = l + 1; q <= n; q += 64)
+          if (w[(size_t)q] != 0.0) acc = std::fma(w[(size_t)q], Tp[q], acc);
+        s[l] = acc;
+      }
+      for (int h = 32; h >= 1; h >>= 1)
+        for (int l = 0; l < h; l++) s[l] = s[l] + s[l + h];
+      const double base = p == 0 ? obj[t] : (head[(size_t)p] <= m ? a[(size_t)head[(size_t)p]] : 0.0);
+      const double v = base + s[0];
+      if (img) img[(size_t)t * crow + (size_t)p] = v;
+      if (p == 0) dj[t] = v;
+    }
+  }
+  return 0;
+}
+
 int mvx_bnb_print_ranges(const mvx_lp_api *api, const void *prob, const double *val, const int *var, const char *path) {
   if (!api) api = &g_hip_api;
   if (!prob || !val || !var) return -1;

@@ -1,6 +1,7 @@
 // capi.cpp -- the C ABI (include/mvx.h): problem model on the host, GLPK-shaped edit and
 // query semantics, dispatch into the device engine.  Replaces the glp_* surface MVOLPS
 // binds; each function cites its reference call site in mvx.h.
+#include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <cstdio>
@@ -279,6 +280,93 @@ int mvx_add_cols(mvx_prob *P, int ncs) {
   if (P->valid) mvx::engine_invalidate(P);
   P->status = MVX_UNDEF;
   return first;
+}
+
+int mvx_add_dense_cols(mvx_prob *P, int k, const double *cols, const double *obj, const int *type, const double *lb, const double *ub,
+                       const int *kind) {
+  if (!P || k < 1 || !cols || !obj || !type || !lb || !ub) return -1;
+  const int m = P->m, n = P->n;
+  const size_t crow = (size_t)m + 1;
+  for (int t = 0; t < k; t++) {
+    if (type[t] < MVX_FR || type[t] > MVX_FX) return -1;
+    if (std::isnan(obj[t]) || std::isnan(lb[t]) || std::isnan(ub[t])) return -1;
+    if (type[t] == MVX_DB && lb[t] > ub[t]) return -1;
+    if (kind && kind[t] != MVX_CV && kind[t] != MVX_IV) return -1;
+    for (int i = 1; i <= m; i++)
+      if (std::isnan(cols[(size_t)t * crow + (size_t)i])) return -1;
+  }
+  // the model: what add_cols + set_mat_col + set_col_bnds + set_obj_coef + set_col_kind write
+  std::vector<int> flag((size_t)k);
+  std::vector<double> nlb((size_t)k), nub((size_t)k);
+  P->n = n + k;
+  P->c.resize((size_t)P->n + 1, 0.0);
+  P->kind.resize((size_t)P->n + 1, MVX_CV);
+  P->ctype.resize((size_t)P->n + 1, MVX_FX);
+  P->clb.resize((size_t)P->n + 1, 0.0);
+  P->cub.resize((size_t)P->n + 1, 0.0);
+  if (!P->cname.empty()) P->cname.mut().resize((size_t)P->n + 1);
+  for (int t = 0; t < k; t++) {
+    const size_t j = (size_t)(n + 1 + t);
+    P->c[j] = obj[t];
+    P->kind[j] = kind ? kind[t] : MVX_CV;
+    P->ctype[j] = type[t];
+    norm_bounds(type[t], lb[t], ub[t], &P->clb[j], &P->cub[j]);
+    flag[(size_t)t] = std_flag(type[t]);
+    nlb[(size_t)t] = P->clb[j];
+    nub[(size_t)t] = P->cub[j];
+  }
+  for (int i = 1; i <= m; i++) { // the list is copy-on-write: a clone keeps the rows it has
+    const std::vector<double> &old = *P->A[i];
+    auto row = std::make_shared<std::vector<double>>();
+    row->reserve((size_t)P->n + 1); // one allocation, one copy of the old part
+    row->assign(old.begin(), old.begin() + (long)std::min(old.size(), (size_t)n + 1));
+    row->resize((size_t)n + 1, 0.0);
+    for (int t = 0; t < k; t++) row->push_back(cols[(size_t)t * crow + (size_t)i]);
+    P->A.set((size_t)i, row);
+  }
+  P->status = MVX_UNDEF;
+  if (!P->valid) return 0;
+  return mvx::engine_add_cols_live(P, k, cols, obj, flag.data(), nlb.data(), nub.data());
+}
+
+int mvx_price_cols(const mvx_prob *P, int k, const double *cols, const double *obj, double *dj, double *img) {
+  return mvx::engine_price_cols(P, k, cols, obj, dj, img);
+}
+int mvx_price_cols_tile(void) { return ADDCOLS_CT; }
+
+void mvx_set_mat_col(mvx_prob *P, int j, int len, const int *ind, const double *val) {
+  if (j < 1 || j > P->n) fault("set_mat_col: column out of range");
+  if (len < 0 || len > P->m) fault("set_mat_col: invalid length");
+  std::vector<double> col((size_t)P->m + 1, 0.0);
+  std::vector<char> seen((size_t)P->m + 1, 0);
+  for (int k = 1; k <= len; k++) {
+    if (ind[k] < 1 || ind[k] > P->m) fault("set_mat_col: row index out of range");
+    if (seen[(size_t)ind[k]]) fault("set_mat_col: duplicate row index");
+    seen[(size_t)ind[k]] = 1;
+    col[(size_t)ind[k]] = val[k];
+  }
+  for (int i = 1; i <= P->m; i++) {
+    if (std::memcmp(&(*P->A[i])[(size_t)j], &col[(size_t)i], sizeof(double)) == 0) continue;
+    auto row = std::make_shared<std::vector<double>>(*P->A[i]); // rows are shared between clones
+    (*row)[(size_t)j] = col[(size_t)i];
+    P->A.set((size_t)i, row);
+  }
+  if (P->valid) mvx::engine_invalidate(P); // a live column is not rewritten in place
+  P->status = MVX_UNDEF;
+}
+
+int mvx_get_mat_col(const mvx_prob *P, int j, int *ind, double *val) {
+  if (j < 1 || j > P->n) fault("get_mat_col: column out of range");
+  int len = 0;
+  for (int i = 1; i <= P->m; i++) {
+    const double a = (*P->A[i])[(size_t)j];
+    if (a != 0.0) {
+      len++;
+      if (ind) ind[len] = i;
+      if (val) val[len] = a;
+    }
+  }
+  return len;
 }
 
 void mvx_set_row_bnds(mvx_prob *P, int i, int type, double lb, double ub) {

@@ -2155,6 +2155,145 @@ int engine_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rh
   return 0;
 }
 
+// ------------------------------------------------------------------ column append and pricing (k_addcols)
+// k_addcols reads the columns a tile at a time: [tile][model row][ADDCOLS_CT], zero behind column k (AddColsArgs::cols)
+static size_t addcols_tiled_bytes(int k, int m) { return (size_t)((k + ADDCOLS_CT - 1) / ADDCOLS_CT) * ((size_t)m + 1) * ADDCOLS_CT * 8; }
+static void addcols_tile_columns(double *dst, const double *cols, int k, int m) {
+  const size_t crow = (size_t)m + 1;
+  std::memset(dst, 0, addcols_tiled_bytes(k, m));
+  for (int t = 0; t < k; t++) {
+    double *d = dst + (size_t)(t / ADDCOLS_CT) * crow * ADDCOLS_CT + (size_t)(t % ADDCOLS_CT);
+    const double *s = cols + (size_t)t * crow;
+    for (size_t i = 1; i < crow; i++) d[i * ADDCOLS_CT] = s[i];
+  }
+}
+// `k` structural columns have joined the model as columns n_old+1 .. P->n (mvx_add_dense_cols; DESIGN.md "Column append
+// (add_cols)"): one upload and one k_addcols launch make them non-basic columns of the live tableau.  cols is k x (m+1) by model
+// row, flag / lb / ub the new positions' statuses and normalised bounds.  While ld_for(n) does not change the columns are written
+// in place; otherwise the handle moves to a slab (m_cap, ld_for(n)) that the same launch writes whole, and the old slab is
+// recycled behind the launch, as grow_rows does it.  Recorded clones leave first (NodeFlush::AtEntry): a recorded clone of this
+// handle receives the bits from before the append.  Pending bound edits stay pending: they are keyed by tableau row.
+// Return codes: 0; -2 device out of memory, the tableau is given up.
+int engine_add_cols_live(mvx_prob *P, int k, const double *cols, const double *obj, const int *flag, const double *lb, const double *ub) {
+  const int m = P->m, n = P->n - k; // n: the columns of the tableau as it stands
+  const size_t crow = (size_t)m + 1;
+  NodeCall f(NodeFlush::AtEntry, NodeResults::None);
+  const size_t o_cols = f.up(addcols_tiled_bytes(k, m)), o_obj = f.up((size_t)k * 8), o_xs = f.up((size_t)k * 8);
+  const size_t o_lb = f.up((size_t)k * 8), o_ub = f.up((size_t)k * 8), o_flag = f.up((size_t)k * 4);
+  const int ld_new = ld_for(n + k);
+  void *o_slab = nullptr, *n_slab = nullptr;
+  size_t o_bytes = 0;
+  bool ok = f.reserve();
+  if (ok && ld_new != P->ld) {
+    n_slab = slab_alloc(*f.c, slab_layout(P->m_cap, ld_new).total);
+    ok = n_slab != nullptr;
+  }
+  if (!ok) {
+    release_device(P);
+    engine_invalidate(P);
+    return -2;
+  }
+  unsigned char *hb = f.hb, *db = f.db;
+  addcols_tile_columns((double *)(hb + o_cols), cols, k, m);
+  std::memcpy(hb + o_obj, obj, (size_t)k * 8);
+  std::memcpy(hb + o_lb, lb, (size_t)k * 8);
+  std::memcpy(hb + o_ub, ub, (size_t)k * 8);
+  std::memcpy(hb + o_flag, flag, (size_t)k * 4);
+  double *h_xs = (double *)(hb + o_xs);
+  for (int t = 0; t < k; t++) h_xs[t] = nb_value(flag[t], lb[t], ub[t]);
+  f.upload();
+  AddColsArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.Ts = P->d_T;
+  a.bvar = P->d_bvar; a.nvar = P->d_nvar;
+  a.ld_s = P->ld;
+  if (n_slab) {
+    a.s_nflag = P->d_nflag;
+    a.s_blb = P->d_blb; a.s_bub = P->d_bub; a.s_nlb = P->d_nlb; a.s_nub = P->d_nub;
+    o_slab = P->slab;
+    o_bytes = P->slab_bytes;
+    bind_slab(P, n_slab, P->m_cap, ld_new);
+  }
+  a.Td = P->d_T;
+  a.ld_d = P->ld;
+  a.d_bvar = P->d_bvar; a.d_nvar = P->d_nvar; a.d_nflag = P->d_nflag;
+  a.d_blb = P->d_blb; a.d_bub = P->d_bub; a.d_nlb = P->d_nlb; a.d_nub = P->d_nub;
+  a.cols = (const double *)(db + o_cols);
+  a.obj = (const double *)(db + o_obj);
+  a.xs = (const double *)(db + o_xs);
+  a.nlb_new = (const double *)(db + o_lb);
+  a.nub_new = (const double *)(db + o_ub);
+  a.nflag_new = (const int *)(db + o_flag);
+  a.m = m; a.n = n; a.k = k;
+  a.rows = m + 1;
+  a.rows_all = P->m_cap + 1;
+  launch_addcols(a, f.stream());
+  if (o_slab) slab_recycle(*f.c, o_slab, o_bytes); // in-order stream: the launch completes before any reuse
+  // host mirrors
+  P->nvar.resize((size_t)n + k + 1);
+  P->nflag.resize((size_t)n + k + 1);
+  for (int t = 0; t < k; t++) {
+    P->nvar[(size_t)(n + 1 + t)] = m + n + 1 + t;
+    P->nflag[(size_t)(n + 1 + t)] = flag[t];
+  }
+  rebuild_pos(P);
+  P->hint_dual = false;
+  P->dmat.reset();
+  P->rmod.reset();
+  P->sol_fresh = false;
+  P->fresh_rows = -1;
+  P->status = MVX_UNDEF;
+  f.fetch(); // the pinned block is free again
+  return 0;
+}
+
+// The images k_addcols would append, without appending (mvx_price_cols): dj[t] row 0 of image t, img (nullable) k x (m+1).  Pure.
+// The candidates go through the node-entry arena a range at a time; a range the arena cannot hold is halved.  Return codes: 0;
+// -1 bad arguments; -2 device out of memory, nothing written; -3 no valid tableau.
+int engine_price_cols(const mvx_prob *P, int k, const double *cols, const double *obj, double *dj, double *img) {
+  if (!P || k < 1 || !cols || !obj || !dj) return -1;
+  if (!P->valid) return -3;
+  const int m = P->m, n = P->n;
+  const size_t crow = (size_t)m + 1;
+  std::vector<double> r_dj((size_t)k), r_img(img ? (size_t)k * crow : 0);
+  int kk = k;
+  for (int t0 = 0; t0 < k;) {
+    const int cnt = std::min(kk, k - t0);
+    NodeCall f(NodeFlush::AtEntry, NodeResults::Device);
+    const size_t o_cols = f.up(addcols_tiled_bytes(cnt, m)), o_obj = f.up((size_t)cnt * 8);
+    const size_t o_dj = f.out((size_t)cnt * 8), o_img = f.out(img ? (size_t)cnt * crow * 8 : 0);
+    if (!f.reserve()) {
+      if (cnt == 1) return -2;
+      kk = cnt / 2;
+      (void)take_last_error(); // the smaller range may fit
+      continue;
+    }
+    addcols_tile_columns((double *)(f.hb + o_cols), cols + (size_t)t0 * crow, cnt, m);
+    std::memcpy(f.hb + o_obj, obj + t0, (size_t)cnt * 8);
+    f.upload();
+    AddColsArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.Ts = P->d_T;
+    a.bvar = P->d_bvar; a.nvar = P->d_nvar;
+    a.ld_s = P->ld;
+    a.cols = (const double *)(f.db + o_cols);
+    a.obj = (const double *)(f.db + o_obj);
+    a.dj = (double *)(f.db + o_dj);
+    a.img = img ? (double *)(f.db + o_img) : nullptr;
+    a.m = m; a.n = n; a.k = cnt;
+    a.rows = img ? m + 1 : 1;
+    a.rows_all = a.rows;
+    launch_addcols(a, f.stream());
+    f.fetch();
+    std::memcpy(r_dj.data() + t0, f.hb + o_dj, (size_t)cnt * 8);
+    if (img) std::memcpy(r_img.data() + (size_t)t0 * crow, f.hb + o_img, (size_t)cnt * crow * 8);
+    t0 += cnt;
+  }
+  std::memcpy(dj, r_dj.data(), (size_t)k * 8);
+  if (img) std::memcpy(img, r_img.data(), (size_t)k * crow * 8);
+  return 0;
+}
+
 // Model rows `rows` (ascending, distinct, numbered as before the call) have left the model (mvx_del_rows; P->m is the new row
 // count, the mirrors and P->pos still describe the m_old rows).  The device copies of the model that cover one of them are
 // dropped.  With a valid tableau: when every deleted row's auxiliary variable is basic, its tableau rows are taken out in place

@@ -435,6 +435,38 @@ struct CutRowsArgs {
   int m, n, ld, k;     // m: rows before the append
 };
 
+// arguments of k_addcols (mvx_add_dense_cols, mvx_price_cols; DESIGN.md "Column append (add_cols)"): `k` dense structural columns
+// against one tableau.  Image t, tableau row p, is base + S: S sums w_q * T[p][q] over the non-basic positions q = 1..n that hold
+// an auxiliary i <= m (w_q = -cols[t][i]), base is obj[t] in row 0 and cols[t][bvar[p]] where row p's basic variable is an
+// auxiliary.  Pricing (img or dj set): the images go to img / dj and nothing of a slab is written.  Append: the images become
+// columns n+1..n+k of Td (== Ts in place; another slab with stride ld_d on a relayout, which the launch then writes whole: old
+// entries, new columns, zeros), column 0 is shifted by the new columns' resting values xs, and the blocks of row block 0 write the
+// new positions' nvar / nflag / nlb / nub (and carry the per-row and per-position arrays over on a relayout)
+#define ADDCOLS_CT 4      // columns per tile: accumulators a lane holds per row
+#define ADDCOLS_RW 1      // rows a wave owns
+#define ADDCOLS_WAVES 8   // waves per workgroup: ADDCOLS_WAVES * ADDCOLS_RW rows share one gather of the weights
+#define ADDCOLS_CHUNK 512 // non-basic positions whose weights one gather stages in LDS: one per thread
+struct AddColsArgs {
+  const double *Ts; // source tableau, stride ld_s
+  double *Td;       // append: destination tableau, stride ld_d; pricing: nullptr
+  const int *bvar, *nvar; // source basis
+  const double *cols;     // [ceil(k / ADDCOLS_CT)][m+1][ADDCOLS_CT]: the columns of a tile side by side, so that the weights of a
+                          // position are one 32-byte read; zero behind column k
+  const double *obj;      // [k]
+  const double *xs;       // [k] resting values of the new columns (append)
+  const int *nflag_new;   // [k] their statuses (append)
+  const double *nlb_new, *nub_new; // [k] their bounds, +-inf when absent (append)
+  double *img, *dj;       // pricing: [k][m+1] (nullable) and [k]
+  // append: the destination's arrays; on a relayout the source's too (nullptr in place)
+  int *d_bvar, *d_nvar, *d_nflag;
+  double *d_blb, *d_bub, *d_nlb, *d_nub;
+  const int *s_nflag;
+  const double *s_blb, *s_bub, *s_nlb, *s_nub;
+  int m, n, k, ld_s, ld_d;
+  int rows;     // tableau rows 0..rows-1 get images (m + 1; 1 when only dj is wanted)
+  int rows_all; // rows the launch covers: rows, or m_cap + 1 on a relayout
+};
+
 // arguments of k_delrows (mvx_del_rows): rows taken out of one tableau in place.  Tableau rows 0..first-1 stay where they are;
 // destination row first + t takes source row src[t] (ascending, src[t] > first + t); rows first + nmove .. m_old (behind the new
 // row m = first + nmove - 1) are vacated and zeroed.  del[0..nrs) are the deleted auxiliary variables (= model rows), ascending, for the renumbering
@@ -551,6 +583,7 @@ void launch_objrow(const ObjNode *nodes, int n, int count, hipStream_t);
 void launch_pumpobj(const PumpArgs &a, hipStream_t);
 void launch_cutgram(const CutGramArgs &a, hipStream_t);
 void launch_cutrows(const CutRowsArgs &a, hipStream_t);
+void launch_addcols(const AddColsArgs &a, hipStream_t);
 void launch_delrows(const DelRowsArgs &a, hipStream_t);
 void launch_delrows_many(const DelManyDesc *hs, const unsigned char *base, int handles, int max_ld, hipStream_t);
 void launch_conflict(const ConflictArgs &a, hipStream_t);

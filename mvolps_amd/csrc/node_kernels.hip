@@ -1,6 +1,6 @@
 // node_kernels.hip -- gfx950 kernels of the batched node entries of branch and bound (engine.cpp: engine_*_many): GMI cuts,
 // classification, branching penalties, sensitivity ranges, the rounding heuristic, reduced-cost tightening, bound propagation, bound lists, the
-// diving pick, objective replacement, the feasibility pump's step, and the scores and the batched append of a cut round.  Each takes its arguments by value and the handles it works on as an array of descriptors (NodeRef and what
+// diving pick, objective replacement, the feasibility pump's step, the scores and the batched append of a cut round, and the append and pricing of columns.  Each takes its arguments by value and the handles it works on as an array of descriptors (NodeRef and what
 // the kernel needs beyond it, mvx_internal.hpp).  Same flags as kernels.hip: -ffp-contract=off, so every kernel has the bits
 // of its host twin.
 #include <hip/hip_runtime.h>
@@ -1342,6 +1342,178 @@ __global__ __launch_bounds__(256) void k_cutrows(CutRowsArgs a) {
 
 void launch_cutrows(const CutRowsArgs &a, hipStream_t s) {
   hipLaunchKernelGGL(k_cutrows, dim3((unsigned)((a.n + 1 + 255) / 256), (unsigned)((a.k + CUT_TILE - 1) / CUT_TILE)), dim3(256), 0, s, a);
+}
+
+// ---------------------------------------------------------------------------- k_addcols
+// k dense structural columns against one tableau in one pass (mvx_add_dense_cols, mvx_price_cols; DESIGN.md "Column append
+// (add_cols)"): k_cutrows turned by 90 degrees.  The image of new column t in tableau row p is base + S, S the sum of
+// w_q * T[p][q] over the non-basic positions q that hold an auxiliary i (w_q = -cols[t][i]).  The order of S is the definition's:
+// 64 chains, chain l over q = l+1, l+65, ... ascending, each an fma chain from +0.0 that skips zero weights; the chains are
+// combined by s[l] += s[l+h], h = 32 .. 1; the base is added last.  A chain is a lane: a wave owns ADDCOLS_RW rows and its lanes
+// walk each of them with stride 64 (coalesced 512-byte reads), every lane holding one accumulator per (row, tile column) across
+// the whole row, so the chains cost nothing and there is no second pass.  The weights of a tile of ADDCOLS_CT columns are gathered
+// once per workgroup and chunk of ADDCOLS_CHUNK positions into LDS (nvar[q] -> cols[t][i], or zero: `cols` holds the columns of
+// a tile side by side, so the weights of a position are one 32-byte read) and serve all ADDCOLS_WAVES * ADDCOLS_RW rows of the
+// block; a chunk without a non-zero weight (positions that hold structurals only) is skipped by the whole workgroup.
+// Pricing: grid (row blocks, tiles), the images go to img / dj.  Append: one workgroup carries ALL tiles of its rows, one after
+// the other, because the shift of column 0 by the new columns' resting values (k_shift_nonbasic's fma, t ascending) needs the
+// finished images of the row: lane 0 of the wave that owns the row keeps the running value.  On a relayout the same workgroups
+// first write their rows of the new slab over its whole stride (old entries, zeros; the new columns follow), spare rows included.
+// The blocks of row block 0 do the bookkeeping.  Reads (columns 1..n of Ts, bvar, nvar[1..n]) and writes (column 0, columns
+// n+1..n+k, nvar[n+1..]) never meet, so no workgroup waits for another.
+#define ADDCOLS_THREADS (64 * ADDCOLS_WAVES)
+__global__ __launch_bounds__(ADDCOLS_THREADS) void k_addcols(AddColsArgs a) {
+  __shared__ double s_w[ADDCOLS_CT][ADDCOLS_CHUNK];
+  constexpr int RB = ADDCOLS_WAVES * ADDCOLS_RW;
+  const int lane = TIDX & 63, wave = TIDX >> 6;
+  const int m = a.m, n = a.n, k = a.k;
+  const size_t lds = (size_t)a.ld_s, ldd = (size_t)a.ld_d, crow = (size_t)m + 1;
+  const int rb0 = (int)blockIdx.x * RB;
+  const bool append = a.Td != nullptr;
+  const bool relayout = append && a.Td != a.Ts;
+  if (append) {
+    for (int r = 0; r < RB; r++) {
+      const int p = rb0 + r;
+      if (p >= a.rows_all) break;
+      const bool img_row = p < a.rows;
+      double *dst = a.Td + (size_t)p * ldd;
+      if (relayout) {
+        const double *src = a.Ts + (size_t)p * lds;
+        for (int j = TIDX; j < a.ld_d; j += ADDCOLS_THREADS) {
+          if (j == 0 && img_row) continue; // the row's owner writes column 0 behind the shift
+          if (j <= n) dst[j] = src[j];
+          else if (j > n + k || !img_row) dst[j] = 0.0;
+        }
+      } else if (!img_row) {
+        for (int j = n + 1 + TIDX; j <= n + k; j += ADDCOLS_THREADS) dst[j] = 0.0;
+      }
+    }
+  }
+  if (rb0 >= a.rows) return;
+  const int p0 = rb0 + wave * ADDCOLS_RW;
+  int nr = a.rows - p0;
+  nr = nr < 0 ? 0 : (nr > ADDCOLS_RW ? ADDCOLS_RW : nr);
+  double c0[ADDCOLS_RW];
+  int hv[ADDCOLS_RW];
+#pragma unroll
+  for (int r = 0; r < ADDCOLS_RW; r++) {
+    c0[r] = (append && lane == 0 && r < nr) ? a.Ts[(size_t)(p0 + r) * lds] : 0.0;
+    hv[r] = (lane == 0 && r < nr && p0 + r >= 1) ? a.bvar[p0 + r] : 0;
+  }
+  for (int t0 = (int)blockIdx.y * ADDCOLS_CT; t0 < k; t0 += (int)gridDim.y * ADDCOLS_CT) {
+    const int nt = k - t0 < ADDCOLS_CT ? k - t0 : ADDCOLS_CT;
+    double acc[ADDCOLS_RW][ADDCOLS_CT];
+#pragma unroll
+    for (int r = 0; r < ADDCOLS_RW; r++)
+#pragma unroll
+      for (int c = 0; c < ADDCOLS_CT; c++) acc[r][c] = 0.0;
+    // the weights of a chunk are gathered one chunk ahead, into registers: the two dependent loads (nvar[q], then cols[t][i])
+    // are in flight while the rows of the chunk before are streamed
+    const double *tile = a.cols + (size_t)(t0 / ADDCOLS_CT) * crow * ADDCOLS_CT; // [m+1][ADDCOLS_CT]
+    double wn[ADDCOLS_CT];
+    auto gather = [&](int q0) {
+      const int q = q0 + TIDX; // ADDCOLS_CHUNK == workgroup size: one position per thread
+      const int v = q <= n ? a.nvar[q] : m + 1;
+#pragma unroll
+      for (int c = 0; c < ADDCOLS_CT; c++) wn[c] = (c < nt && v <= m) ? -tile[(size_t)v * ADDCOLS_CT + c] : 0.0;
+    };
+    gather(1);
+    for (int q0 = 1; q0 <= n; q0 += ADDCOLS_CHUNK) {
+      __syncthreads(); // the last chunk's readers are done
+      int nz = 0;
+#pragma unroll
+      for (int c = 0; c < ADDCOLS_CT; c++) {
+        s_w[c][TIDX] = wn[c];
+        nz |= (wn[c] != 0.0) ? 1 : 0;
+      }
+      const int any = __syncthreads_or(nz);
+      if (q0 + ADDCOLS_CHUNK <= n) gather(q0 + ADDCOLS_CHUNK);
+      if (!any) continue; // structurals only: nothing to add, for any row of the block
+#pragma unroll
+      for (int j = 0; j < ADDCOLS_CHUNK / 64; j++) {
+        const int q = q0 + j * 64 + lane;
+        double v[ADDCOLS_RW];
+#pragma unroll
+        for (int r = 0; r < ADDCOLS_RW; r++) v[r] = (q <= n && r < nr) ? a.Ts[(size_t)(p0 + r) * lds + (size_t)q] : 0.0;
+#pragma unroll
+        for (int c = 0; c < ADDCOLS_CT; c++) {
+          const double w = s_w[c][j * 64 + lane];
+          if (w != 0.0) {
+#pragma unroll
+            for (int r = 0; r < ADDCOLS_RW; r++) acc[r][c] = fma(w, v[r], acc[r][c]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < ADDCOLS_RW; r++) {
+#pragma unroll
+      for (int c = 0; c < ADDCOLS_CT; c++) {
+        double s = acc[r][c];
+#pragma unroll
+        for (int h = 32; h >= 1; h >>= 1) s = s + __shfl_down(s, h);
+        if (lane == 0 && r < nr && c < nt) {
+          const int p = p0 + r, t = t0 + c;
+          double base;
+          if (p == 0) base = a.obj[t];
+          else base = hv[r] <= m ? tile[(size_t)hv[r] * ADDCOLS_CT + c] : 0.0;
+          const double val = base + s;
+          if (append) {
+            a.Td[(size_t)p * ldd + (size_t)(n + 1 + t)] = val;
+            const double x = a.xs[t];
+            if (x != 0.0) c0[r] = fma(val, x, c0[r]);
+          } else {
+            if (a.img) a.img[(size_t)t * crow + (size_t)p] = val;
+            if (p == 0) a.dj[t] = val;
+          }
+        }
+      }
+    }
+  }
+  if (!append) return;
+  if (lane == 0) {
+#pragma unroll
+    for (int r = 0; r < ADDCOLS_RW; r++)
+      if (r < nr) a.Td[(size_t)(p0 + r) * ldd] = c0[r];
+  }
+  if (blockIdx.x != 0) return;
+  for (int t = TIDX; t < k; t += ADDCOLS_THREADS) {
+    a.d_nvar[n + 1 + t] = m + n + 1 + t;
+    a.d_nflag[n + 1 + t] = a.nflag_new[t];
+    a.d_nlb[n + 1 + t] = a.nlb_new[t];
+    a.d_nub[n + 1 + t] = a.nub_new[t];
+  }
+  if (!relayout) return;
+  for (int g = TIDX; g < a.rows_all; g += ADDCOLS_THREADS) {
+    a.d_bvar[g] = a.bvar[g];
+    a.d_blb[g] = a.s_blb[g];
+    a.d_bub[g] = a.s_bub[g];
+  }
+  for (int g = TIDX; g < a.ld_d; g += ADDCOLS_THREADS) {
+    if (g <= n) {
+      a.d_nvar[g] = a.nvar[g];
+      a.d_nflag[g] = a.s_nflag[g];
+      a.d_nlb[g] = a.s_nlb[g];
+      a.d_nub[g] = a.s_nub[g];
+    } else if (g > n + k) {
+      a.d_nvar[g] = 0;
+      a.d_nflag[g] = MVX_NS;
+      a.d_nlb[g] = 0.0;
+      a.d_nub[g] = 0.0;
+    }
+  }
+}
+
+void launch_addcols(const AddColsArgs &a, hipStream_t s) {
+  static_assert(ADDCOLS_CHUNK == ADDCOLS_THREADS, "k_addcols gathers one position per thread");
+  constexpr int RB = ADDCOLS_WAVES * ADDCOLS_RW;
+  const unsigned nrb = (unsigned)((a.rows_all + RB - 1) / RB);
+  unsigned nty = 1;
+  if (!a.Td) { // pricing: the tiles are independent
+    const int tiles = (a.k + ADDCOLS_CT - 1) / ADDCOLS_CT;
+    nty = (unsigned)(tiles < 65535 ? tiles : 65535);
+  }
+  hipLaunchKernelGGL(k_addcols, dim3(nrb, nty), dim3(ADDCOLS_THREADS), 0, s, a);
 }
 
 // ---------------------------------------------------------------------------- k_delrows
