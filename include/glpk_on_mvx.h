@@ -48,6 +48,8 @@ typedef mvx_smcp glp_smcp;
 /* build / modify */
 #define glp_add_rows mvx_add_rows         /* cut.cpp:23 */
 #define glp_add_cols mvx_add_cols         /* (model construction) */
+#define glp_del_rows mvx_del_rows         /* (model editing; MVOLPS never calls it) */
+#define glp_del_cols mvx_del_cols         /* (model editing; MVOLPS never calls it) */
 #define glp_set_mat_row mvx_set_mat_row   /* cut.cpp:40 */
 #define glp_set_mat_col mvx_set_mat_col   /* (model construction by columns) */
 #define glp_set_row_bnds mvx_set_row_bnds /* cut.cpp:43 */

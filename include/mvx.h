@@ -307,6 +307,17 @@ int mvx_price_cols_tile(void); /* candidate columns one k_addcols workgroup carr
    the tableau up, as mvx_add_cols does; mvx_get_mat_col returns the non-zeros in ascending row order. */
 void mvx_set_mat_col(mvx_prob *P, int j, int len, const int *ind, const double *val);
 int mvx_get_mat_col(const mvx_prob *P, int j, int *ind, double *val);
+/* Column deletion (DESIGN.md "Column deletion (del_cols)"), the shape of glp_del_cols: the distinct columns num[1..ncs] (1-based,
+   num[0] is not read) leave the model, the others keep their order.  Where the handle has a valid tableau and every deleted
+   column is non-basic, the columns leave the tableau in one device pass (k_delcols): column 0 is shifted for the resting values
+   of the deleted columns (a deleted variable counts as 0 from now on), the kept positions close up in their order bit for bit,
+   the basis stays and the next solve is warm; the row stride follows the new column count.  Where a deleted column is basic the
+   tableau is given up and the next solve starts from the slack basis.  On a handle without a valid tableau only the model is
+   edited (no device is needed).  Returns 0; -1 bad arguments, nothing changed (a null, ncs < 1, a number outside 1..n, a
+   duplicate, or ncs == n: the engine has no LP without columns, so the last column cannot leave); -2 device out of memory:
+   the model has lost the columns and the tableau is given up, as mvx_add_cut_rows gives it up. */
+int mvx_del_cols(mvx_prob *P, int ncs, const int *num);
+int mvx_del_cols_span(void); /* destination positions a wave of k_delcols moves per batch */
 /* Clique cuts (DESIGN.md "Clique cuts (cut_families)"): the conflict graph of the binary columns of `model` (integer, bounds 0
    and 1 exactly), two device launches (k_conflict_rows, k_conflict).  Columns j < k are adjacent when one of rows 1..m (m the
    handle's row count) forbids x_j = x_k = 1 with every other term at its least: (Lmin_i + a_ij) + a_ik > rub_i + tol(rub_i) on

@@ -22,6 +22,8 @@ _EXTRA = {
     "price_cols": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                              C.POINTER(C.c_double)]),
     "price_cols_tile": (C.c_int, []),
+    "del_cols": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "del_cols_span": (C.c_int, []),
     "set_mat_col": (None, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     "get_mat_col": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     "device_count": (C.c_int, []),

@@ -251,6 +251,10 @@ def _bind(lib):
     lib.mvx_price_cols.argtypes = [C.c_void_p, C.c_int, _DP, _DP, _DP, _DP]
     lib.mvx_bnb_price_cols.restype = C.c_int
     lib.mvx_bnb_price_cols.argtypes = [C.c_void_p, C.c_void_p, C.c_int, _DP, _DP, _DP, _DP]
+    lib.mvx_del_cols.restype = C.c_int
+    lib.mvx_del_cols.argtypes = [C.c_void_p, C.c_int, _IP]
+    lib.mvx_del_cols_span.restype = C.c_int
+    lib.mvx_del_cols_span.argtypes = []
     lib.mvx_generateCutGMI.restype = C.c_int
     lib.mvx_generateCutGMI.argtypes = [C.c_void_p, C.c_void_p, C.c_int, _IP, _DP, _DP, _DP]
     lib.mvx_generateCut3.restype = C.c_int
@@ -667,6 +671,11 @@ def price_cols(prob, cols, obj, table=False):
         rc = lib().mvx_bnb_price_cols(tptr, prob.h, k, cols.ctypes.data_as(DP), obj.ctypes.data_as(DP), dj.ctypes.data_as(DP),
                                       img.ctypes.data_as(DP))
     return rc, dj, img
+
+
+def del_cols_span():
+    """mvx_del_cols_span: the destination positions a wave of k_delcols moves per batch."""
+    return lib().mvx_del_cols_span()
 
 
 def ranges_chunk():

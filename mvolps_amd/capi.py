@@ -197,6 +197,13 @@ class Prob:
         num = np.concatenate([[0], np.asarray(list(rows), dtype=np.int32)]).astype(np.int32)
         return self.api.del_rows(self.h, len(num) - 1, _ip(num))
 
+    def del_cols(self, cols):
+        """mvx_del_cols (the gfx950 engine's library only): the distinct 1-based column numbers `cols` leave the model and, where
+        the handle has a tableau and they are all non-basic, the live tableau in one device pass (DESIGN.md "Column deletion
+        (del_cols)"); a basic one gives the tableau up.  Returns 0, -1 with nothing changed, or -2 (device out of memory)."""
+        num = np.concatenate([[0], np.asarray(list(cols), dtype=np.int32)]).astype(np.int32)
+        return self.api.del_cols(self.h, len(num) - 1, _ip(num))
+
     def add_dense_cols(self, cols, obj, types, lb, ub, kinds=None):
         """mvx_add_dense_cols (the gfx950 engine's library only): k dense columns join the model as columns n+1..n+k and, where
         the handle has a tableau, the live tableau (DESIGN.md "Column append (add_cols)").  cols is (k, m) -- cols[t, i-1] the

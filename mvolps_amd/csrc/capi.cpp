@@ -329,6 +329,70 @@ int mvx_add_dense_cols(mvx_prob *P, int k, const double *cols, const double *obj
   return mvx::engine_add_cols_live(P, k, cols, obj, flag.data(), nlb.data(), nub.data());
 }
 
+int mvx_del_cols(mvx_prob *P, int ncs, const int *num) {
+  if (!P || ncs < 1 || !num) return -1;
+  const int m = P->m, n = P->n;
+  if (ncs >= n) return -1; // the engine has no LP without columns
+  std::vector<char> mark((size_t)n + 1, 0);
+  for (int k = 1; k <= ncs; k++) {
+    const int j = num[k];
+    if (j < 1 || j > n || mark[(size_t)j]) return -1;
+    mark[(size_t)j] = 1;
+  }
+  std::vector<int> cols; // ascending
+  std::vector<double> dlb, dub;
+  cols.reserve((size_t)ncs);
+  for (int j = 1; j <= n; j++)
+    if (mark[(size_t)j]) {
+      cols.push_back(j);
+      dlb.push_back(P->clb[(size_t)j]);
+      dub.push_back(P->cub[(size_t)j]);
+    }
+  // the model: the kept columns close up in their order
+  std::vector<std::string> *names = P->cname.empty() ? nullptr : &P->cname.mut();
+  if (names && names->size() < (size_t)n + 1) names->resize((size_t)n + 1);
+  int w = 0;
+  for (int j = 1; j <= n; j++) {
+    if (mark[(size_t)j]) continue;
+    ++w;
+    if (w == j) continue;
+    P->c[(size_t)w] = P->c[(size_t)j];
+    P->kind[(size_t)w] = P->kind[(size_t)j];
+    P->ctype[(size_t)w] = P->ctype[(size_t)j];
+    P->clb[(size_t)w] = P->clb[(size_t)j];
+    P->cub[(size_t)w] = P->cub[(size_t)j];
+    if (names) (*names)[(size_t)w] = (*names)[(size_t)j];
+  }
+  P->n = w;
+  P->c.resize((size_t)w + 1);
+  P->kind.resize((size_t)w + 1);
+  P->ctype.resize((size_t)w + 1);
+  P->clb.resize((size_t)w + 1);
+  P->cub.resize((size_t)w + 1);
+  if (names) names->resize((size_t)w + 1);
+  std::vector<std::pair<size_t, size_t>> runs; // the kept columns as [from, to): a row is copied a run at a time
+  for (int j = 1; j <= n; j++) {
+    if (mark[(size_t)j]) continue;
+    if (!runs.empty() && runs.back().second == (size_t)j) runs.back().second++;
+    else runs.emplace_back((size_t)j, (size_t)j + 1);
+  }
+  for (int i = 1; i <= m; i++) { // the list is copy-on-write: a clone keeps the rows it has
+    const std::vector<double> &old = *P->A[i];
+    auto row = std::make_shared<std::vector<double>>();
+    row->reserve((size_t)w + 1); // one allocation
+    row->push_back(0.0);
+    for (const auto &r : runs) {
+      const size_t to = std::min(r.second, old.size());
+      if (r.first < to) row->insert(row->end(), old.begin() + (long)r.first, old.begin() + (long)to);
+    }
+    row->resize((size_t)w + 1, 0.0); // a row shorter than n + 1 ends in zeros
+    P->A.set((size_t)i, row);
+  }
+  P->status = MVX_UNDEF;
+  return mvx::engine_del_cols(P, cols, n, dlb.data(), dub.data());
+}
+int mvx_del_cols_span(void) { return 64 * DELC_BATCH; }
+
 int mvx_price_cols(const mvx_prob *P, int k, const double *cols, const double *obj, double *dj, double *img) {
   return mvx::engine_price_cols(P, k, cols, obj, dj, img);
 }

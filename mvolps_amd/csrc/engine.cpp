@@ -2294,6 +2294,129 @@ int engine_price_cols(const mvx_prob *P, int k, const double *cols, const double
   return 0;
 }
 
+// ------------------------------------------------------------------ column deletion (k_delcols)
+// Model columns `cols` (ascending, distinct, numbered as before the call) have left the model (mvx_del_cols; DESIGN.md "Column
+// deletion (del_cols)"; P->n is the new column count, the mirrors and P->pos still describe the n_old columns; lb / ub are the
+// deleted columns' normalised bounds, in the order of `cols`).  The device copies of the model cover all columns and are dropped.
+// With a valid tableau: when every deleted column is non-basic, one upload and one k_delcols launch take their positions out --
+// column 0 is shifted for their resting values in ascending position order, the kept positions close up in their order bit
+// for bit with nflag / nlb / nub, the structural variables are renumbered on the device and in the mirrors -- and the basis
+// stays what it was.  While ld_for(n) does not change this happens in place; otherwise the handle moves to a slab (m_cap,
+// ld_for(n)) that the same launch writes whole, and the old slab is recycled behind the launch, as engine_add_cols_live does
+// it.  The rows behind row m take part: the first of them holds the cost row of the last primal phase 1 (tableau row m+1, see Ctl), so
+// they are not zero over the whole stride; in place they close up like the others, on a relayout they are written as zeros.
+// Recorded clones leave first (NodeFlush::AtEntry): a recorded clone of this handle receives the bits from before the
+// deletion.  Pending bound edits stay pending: they are keyed by tableau row, and no row moves.  When a deleted column is
+// basic it cannot leave without a pivot: the tableau is given up and the next solve starts from the slack basis.
+// Return codes: 0; -2 device out of memory, the tableau is given up.
+int engine_del_cols(mvx_prob *P, const std::vector<int> &cols, int n_old, const double *lb, const double *ub) {
+  P->dmat.reset();
+  P->rmod.reset();
+  if (!P->valid) return 0;
+  const int m = P->m, ncs = (int)cols.size(), n_new = n_old - ncs;
+  std::vector<int> delpos; // deleted positions
+  delpos.reserve((size_t)ncs);
+  for (int j : cols) {
+    const int pos = P->pos[(size_t)(m + j)];
+    if (pos > 0) {
+      // the slab is kept: the next solve builds the slack tableau in it, so a recorded clone INTO it must land first
+      Context &c = ctx();
+      MAIN_LOCK(c);
+      flush_copies(c);
+      engine_invalidate(P);
+      return 0;
+    }
+    delpos.push_back(-pos);
+  }
+  std::vector<char> gone((size_t)n_old + 1, 0); // by position
+  for (int q : delpos) gone[(size_t)q] = 1;
+  std::sort(delpos.begin(), delpos.end());
+  const int first = delpos.front(), nmove = n_new - first + 1;
+  std::vector<int> src; // the source of destination position first + t
+  src.reserve((size_t)nmove);
+  for (int q = first + 1; q <= n_old; q++)
+    if (!gone[(size_t)q]) src.push_back(q);
+  std::vector<int> sh_pos; // the deleted positions that rest on a non-zero value, ascending, and the negated values
+  std::vector<double> sh_negx;
+  for (int q : delpos) {
+    const size_t t = (size_t)(std::lower_bound(cols.begin(), cols.end(), P->nvar[(size_t)q] - m) - cols.begin());
+    const double x = nb_value(P->nflag[(size_t)q], lb[t], ub[t]);
+    if (x != 0.0) {
+      sh_pos.push_back(q);
+      sh_negx.push_back(-x);
+    }
+  }
+  const int nsh = (int)sh_pos.size();
+  NodeCall f(NodeFlush::AtEntry, NodeResults::None);
+  const size_t o_src = f.up((size_t)std::max(1, nmove) * 4), o_del = f.up((size_t)ncs * 4);
+  const size_t o_shp = f.up((size_t)std::max(1, nsh) * 4), o_shx = f.up((size_t)std::max(1, nsh) * 8);
+  const int ld_new = ld_for(n_new);
+  void *o_slab = nullptr, *n_slab = nullptr;
+  size_t o_bytes = 0;
+  bool ok = f.reserve();
+  if (ok && ld_new != P->ld) {
+    n_slab = slab_alloc(*f.c, slab_layout(P->m_cap, ld_new).total);
+    ok = n_slab != nullptr;
+  }
+  if (!ok) {
+    release_device(P);
+    engine_invalidate(P);
+    return -2;
+  }
+  unsigned char *hb = f.hb, *db = f.db;
+  if (nmove) std::memcpy(hb + o_src, src.data(), (size_t)nmove * 4);
+  std::memcpy(hb + o_del, cols.data(), (size_t)ncs * 4);
+  if (nsh) {
+    std::memcpy(hb + o_shp, sh_pos.data(), (size_t)nsh * 4);
+    std::memcpy(hb + o_shx, sh_negx.data(), (size_t)nsh * 8);
+  }
+  f.upload();
+  DelColsArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.Ts = P->d_T;
+  a.ld_s = P->ld;
+  a.s_bvar = P->d_bvar; a.s_nvar = P->d_nvar; a.s_nflag = P->d_nflag;
+  a.s_blb = P->d_blb; a.s_bub = P->d_bub; a.s_nlb = P->d_nlb; a.s_nub = P->d_nub;
+  if (n_slab) {
+    o_slab = P->slab;
+    o_bytes = P->slab_bytes;
+    bind_slab(P, n_slab, P->m_cap, ld_new);
+  }
+  a.Td = P->d_T;
+  a.ld_d = P->ld;
+  a.d_bvar = P->d_bvar; a.d_nvar = P->d_nvar; a.d_nflag = P->d_nflag;
+  a.d_blb = P->d_blb; a.d_bub = P->d_bub; a.d_nlb = P->d_nlb; a.d_nub = P->d_nub;
+  a.src = (const int *)(db + o_src);
+  a.delc = (const int *)(db + o_del);
+  a.sh_pos = (const int *)(db + o_shp);
+  a.sh_negx = (const double *)(db + o_shx);
+  a.m = m; a.n_old = n_old; a.ncs = ncs; a.first = first; a.nmove = nmove; a.nsh = nsh;
+  a.rows_all = P->m_cap + 1;
+  launch_delcols(a, f.stream());
+  if (o_slab) slab_recycle(*f.c, o_slab, o_bytes); // in-order stream: the launch completes before any reuse
+  // host mirrors: the same compaction and renumbering
+  auto renumber = [&](int k) {
+    if (k <= m) return k;
+    return k - (int)(std::lower_bound(cols.begin(), cols.end(), k - m) - cols.begin());
+  };
+  for (int i = 1; i <= m; i++) P->bvar[(size_t)i] = renumber(P->bvar[(size_t)i]);
+  for (int q = 1, w = 0; q <= n_old; q++) {
+    if (gone[(size_t)q]) continue;
+    ++w;
+    P->nvar[(size_t)w] = renumber(P->nvar[(size_t)q]);
+    P->nflag[(size_t)w] = P->nflag[(size_t)q];
+  }
+  P->nvar.resize((size_t)n_new + 1);
+  P->nflag.resize((size_t)n_new + 1);
+  rebuild_pos(P);
+  if (nsh) P->hint_dual = true; // resting values left column 0: the reduced costs stand, a basic variable may have left its bounds
+  P->sol_fresh = false;
+  P->fresh_rows = -1;
+  P->status = MVX_UNDEF;
+  f.fetch(); // the pinned block is free again
+  return 0;
+}
+
 // Model rows `rows` (ascending, distinct, numbered as before the call) have left the model (mvx_del_rows; P->m is the new row
 // count, the mirrors and P->pos still describe the m_old rows).  The device copies of the model that cover one of them are
 // dropped.  With a valid tableau: when every deleted row's auxiliary variable is basic, its tableau rows are taken out in place

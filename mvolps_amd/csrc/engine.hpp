@@ -63,6 +63,9 @@ int engine_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rh
 // the new positions' statuses and normalised bounds), and the same images without appending; see engine.cpp
 int engine_add_cols_live(mvx_prob *P, int k, const double *cols, const double *obj, const int *flag, const double *lb, const double *ub);
 int engine_price_cols(const mvx_prob *P, int k, const double *cols, const double *obj, double *dj, double *img);
+// model columns `cols` (ascending, old numbers; lb / ub their normalised bounds) have left the model: where every one of them is
+// non-basic they leave the live tableau in one device pass (k_delcols), otherwise the tableau is given up; see engine.cpp
+int engine_del_cols(mvx_prob *P, const std::vector<int> &cols, int n_old, const double *lb, const double *ub);
 int engine_conflict_graph(const mvx_prob *R, unsigned long long *adj, long long *edges);
 // incumbent polishing of `count` points against root's model (k_lsact, k_lsmove, k_lsapply); see engine.cpp
 int engine_polish_many(const mvx_prob *root, int count, double *x, int max_moves, double *obj, int *moves, int *ok);

@@ -489,6 +489,33 @@ struct DelManyDesc {
   int first, nmove, m_old, nrs, n, ld;
 };
 
+// arguments of k_delcols (mvx_del_cols; DESIGN.md "Column deletion (del_cols)"): non-basic columns taken out of one tableau.
+// Positions 1..first-1 stay where they are; destination position first + t takes source position src[t] (ascending,
+// src[t] > first + t), t < nmove, so that the last kept position is n_new = first + nmove - 1; positions n_new+1 .. n_old are
+// vacated.  Before any entry of a row moves, its column 0 takes the chain T[p][0] = fma(T[p][sh_pos[s]], sh_negx[s], T[p][0]),
+// s = 0 .. nsh-1 (the deleted positions with a non-zero resting value, ascending; sh_negx the negated value), rows 0..m only.
+// Td == Ts: in place, rows 0..rows_all-1 are compacted and their vacated positions zeroed.  Td != Ts (another slab, stride
+// ld_d): the launch writes rows 0..rows_all-1 of Td over the whole stride -- kept entries, zero padding, zero rows behind row
+// m -- and carries the per-row and per-position arrays over.  delc[0..ncs) are the deleted columns, ascending, for the
+// renumbering of the structural variables: m + j becomes m + j - #{deleted < j}
+#define DELC_BATCH 8 // batches of 64 destinations a lane holds in registers before it stores them
+#define DELC_WAVES 8 // waves per workgroup: a wave owns one row
+struct DelColsArgs {
+  const double *Ts; // source tableau, stride ld_s
+  double *Td;       // destination tableau, stride ld_d
+  const int *src;   // [nmove]
+  const int *sh_pos;     // [nsh]
+  const double *sh_negx; // [nsh]
+  const int *delc;       // [ncs]
+  // the source's arrays and the destination's (the same in place)
+  const int *s_bvar, *s_nvar, *s_nflag;
+  const double *s_blb, *s_bub, *s_nlb, *s_nub;
+  int *d_bvar, *d_nvar, *d_nflag;
+  double *d_blb, *d_bub, *d_nlb, *d_nub;
+  int m, n_old, ncs, first, nmove, nsh, ld_s, ld_d;
+  int rows_all; // rows the launch covers: m_cap + 1
+};
+
 // arguments of k_conflict_rows / k_conflict (mvx_conflict_graph): the model of one handle as k_prop reads it -- its rows by
 // column (At) and by row (Ar), the row bounds, the RND_INT flags and the handle's own column bounds -- the per-row numbers the
 // first kernel leaves for the second, and the adjacency words
@@ -584,6 +611,7 @@ void launch_pumpobj(const PumpArgs &a, hipStream_t);
 void launch_cutgram(const CutGramArgs &a, hipStream_t);
 void launch_cutrows(const CutRowsArgs &a, hipStream_t);
 void launch_addcols(const AddColsArgs &a, hipStream_t);
+void launch_delcols(const DelColsArgs &a, hipStream_t);
 void launch_delrows(const DelRowsArgs &a, hipStream_t);
 void launch_delrows_many(const DelManyDesc *hs, const unsigned char *base, int handles, int max_ld, hipStream_t);
 void launch_conflict(const ConflictArgs &a, hipStream_t);

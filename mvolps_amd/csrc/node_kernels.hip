@@ -1,6 +1,6 @@
 // node_kernels.hip -- gfx950 kernels of the batched node entries of branch and bound (engine.cpp: engine_*_many): GMI cuts,
 // classification, branching penalties, sensitivity ranges, the rounding heuristic, reduced-cost tightening, bound propagation, bound lists, the
-// diving pick, objective replacement, the feasibility pump's step, the scores and the batched append of a cut round, and the append and pricing of columns.  Each takes its arguments by value and the handles it works on as an array of descriptors (NodeRef and what
+// diving pick, objective replacement, the feasibility pump's step, the scores and the batched append of a cut round, and the append, pricing and deletion of columns.  Each takes its arguments by value and the handles it works on as an array of descriptors (NodeRef and what
 // the kernel needs beyond it, mvx_internal.hpp).  Same flags as kernels.hip: -ffp-contract=off, so every kernel has the bits
 // of its host twin.
 #include <hip/hip_runtime.h>
@@ -1514,6 +1514,179 @@ void launch_addcols(const AddColsArgs &a, hipStream_t s) {
     nty = (unsigned)(tiles < 65535 ? tiles : 65535);
   }
   hipLaunchKernelGGL(k_addcols, dim3(nrb, nty), dim3(ADDCOLS_THREADS), 0, s, a);
+}
+
+// ---------------------------------------------------------------------------- k_delcols
+// Non-basic columns taken out of one tableau in one pass (mvx_del_cols; DESIGN.md "Column deletion (del_cols)"): k_addcols'
+// counterpart.  A wave owns one row, DELC_WAVES rows per workgroup; the last workgroup of the grid owns no row and does the
+// per-position and per-row arrays.  A wave reads only the uploaded lists (src, sh_pos / sh_negx, delc), never nvar / nflag,
+// which that last workgroup rewrites in the same launch.
+// Column 0 first: the row's chain T[p][0] = fma(T[p][q], -x_q, T[p][0]) over the deleted positions q with a non-zero resting
+// value, ascending (the mirror of k_addcols' shift and of k_shift_nonbasic: a deleted variable counts as 0 from now on).  The
+// chain reads positions the compaction overwrites, so it runs before any body store of the row; 64 of its operands are
+// gathered at a time, one per lane, and every lane runs the same chain on them.
+// Then the row closes up: destination first + t takes source src[t], in batches of 64 * DELC_BATCH destinations, ascending, all
+// of a batch's loads in registers before its stores (coalesced 512-byte reads and writes).  Positions in front of `first` are
+// not touched.  Why in place is safe: src[t] > first + t and src ascends, so the sources of a later batch lie strictly behind
+// every destination stored so far -- a store never lands on an entry that is still to be loaded by a LATER batch.  Within a
+// batch a store of one lane may land on the source of another lane, of the same or of another load of the batch, and no store
+// depends on every load, so the compiler's own counted waits do not cover it: between the loads and the stores of a batch stands
+// a full wait -- every memory counter at zero, then __syncthreads(), as delrows_wave has it for its basis arrays.  All waves of a
+// workgroup run the same number of batches (a wave without a row loads and stores nothing), so the barrier is met by all.
+// On a relayout source and destination are different slabs and ordering is no concern: the wave writes its row of the new slab
+// over the whole stride -- kept entries, zero padding, and zeros in the rows behind row m.
+// No atomics, no LDS, no hand-off between workgroups: a row has one owner, and the small arrays have one.
+#define DELC_THREADS (64 * DELC_WAVES)
+__device__ __forceinline__ int delc_renumber(int k, const int *delc, int ncs, int m) {
+  if (k <= m) return k;
+  const int j = k - m;
+  int lo = 0, hi = ncs; // deleted columns below j: delc is ascending and does not hold j
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (delc[mid] < j) lo = mid + 1;
+    else hi = mid;
+  }
+  return k - lo;
+}
+// every load of this wave has returned, and no lane of the workgroup goes on before all have got here
+__device__ __forceinline__ void delc_full_wait() {
+  __builtin_amdgcn_s_waitcnt(0); // vmcnt(0) expcnt(0) lgkmcnt(0)
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(DELC_THREADS) void k_delcols(DelColsArgs a) {
+  constexpr int SPAN = 64 * DELC_BATCH;
+  const int lane = TIDX & 63, wave = TIDX >> 6;
+  const int m = a.m, first = a.first, nmove = a.nmove, n_old = a.n_old, ncs = a.ncs;
+  const int n_new = first + nmove - 1;
+  const bool relayout = a.Td != a.Ts;
+  if (blockIdx.x + 1 == gridDim.x) { // the small arrays
+    const int tid = TIDX;
+    if (!relayout) {
+      for (int g = 1 + tid; g <= m; g += DELC_THREADS) a.d_bvar[g] = delc_renumber(a.s_bvar[g], a.delc, ncs, m);
+      for (int q = 1 + tid; q < first; q += DELC_THREADS) a.d_nvar[q] = delc_renumber(a.s_nvar[q], a.delc, ncs, m);
+      for (int t0 = 0; t0 < nmove; t0 += DELC_THREADS) {
+        const int t = t0 + tid;
+        int k = 0, fl = 0;
+        double lb = 0.0, ub = 0.0;
+        if (t < nmove) {
+          const int s = a.src[t];
+          k = a.s_nvar[s];
+          fl = a.s_nflag[s];
+          lb = a.s_nlb[s];
+          ub = a.s_nub[s];
+        }
+        delc_full_wait(); // a destination may be another thread's source
+        if (t < nmove) {
+          a.d_nvar[first + t] = delc_renumber(k, a.delc, ncs, m);
+          a.d_nflag[first + t] = fl;
+          a.d_nlb[first + t] = lb;
+          a.d_nub[first + t] = ub;
+        }
+      }
+      delc_full_wait();
+      for (int q = n_new + 1 + tid; q <= n_old; q += DELC_THREADS) { // as a freshly built handle has its padding
+        a.d_nvar[q] = 0;
+        a.d_nflag[q] = MVX_NS;
+        a.d_nlb[q] = 0.0;
+        a.d_nub[q] = 0.0;
+      }
+    } else {
+      for (int g = tid; g < a.rows_all; g += DELC_THREADS) {
+        const int k = a.s_bvar[g];
+        a.d_bvar[g] = (g >= 1 && g <= m) ? delc_renumber(k, a.delc, ncs, m) : k;
+        a.d_blb[g] = a.s_blb[g];
+        a.d_bub[g] = a.s_bub[g];
+      }
+      for (int g = tid; g < a.ld_d; g += DELC_THREADS) {
+        if (g <= n_new) {
+          const int s = g < first ? g : a.src[g - first];
+          a.d_nvar[g] = g ? delc_renumber(a.s_nvar[s], a.delc, ncs, m) : a.s_nvar[0];
+          a.d_nflag[g] = a.s_nflag[s];
+          a.d_nlb[g] = a.s_nlb[s];
+          a.d_nub[g] = a.s_nub[s];
+        } else {
+          a.d_nvar[g] = 0;
+          a.d_nflag[g] = MVX_NS;
+          a.d_nlb[g] = 0.0;
+          a.d_nub[g] = 0.0;
+        }
+      }
+    }
+    return;
+  }
+  const int p = (int)blockIdx.x * DELC_WAVES + wave;
+  const bool live = p < a.rows_all; // wave-uniform
+  const bool body = p <= m;         // rows 0..m; the rows behind them are spare (rows_all > m + 1)
+  const double *S = a.Ts + (size_t)(live ? p : 0) * (size_t)a.ld_s;
+  double *D = a.Td + (size_t)(live ? p : 0) * (size_t)a.ld_d;
+  double c0 = 0.0;
+  if (body) {
+    c0 = S[0];
+    for (int s0 = 0; s0 < a.nsh; s0 += 64) {
+      const int cnt = a.nsh - s0 < 64 ? a.nsh - s0 : 64;
+      const int s = s0 + (lane < cnt ? lane : cnt - 1);
+      const double v = S[a.sh_pos[s]], x = a.sh_negx[s];
+      for (int i = 0; i < cnt; i++) c0 = fma(__shfl(v, i), __shfl(x, i), c0);
+    }
+  }
+  if (relayout) {
+    if (!live) return;
+    if (!body) { // a row behind row m of the new slab: zeros
+      for (int j = lane; j < a.ld_d; j += 64) D[j] = 0.0;
+      return;
+    }
+    // the same batches: every load of a batch is issued before its first store, and none of them sits behind a branch (the
+    // index is clamped to the kept positions, the padding takes its zero afterwards)
+    for (int j0 = 0; j0 < a.ld_d; j0 += SPAN) {
+      double v[DELC_BATCH];
+#pragma unroll
+      for (int b = 0; b < DELC_BATCH; b++) {
+        const int j = j0 + b * 64 + lane;
+        const int jj = j <= n_new ? j : n_new;
+        int s = jj;
+        if (nmove > 0) {
+          const int t = jj - first;
+          const int sm = a.src[t > 0 ? t : 0];
+          s = t >= 0 ? sm : jj;
+        }
+        v[b] = S[s];
+      }
+#pragma unroll
+      for (int b = 0; b < DELC_BATCH; b++) {
+        const int j = j0 + b * 64 + lane;
+        if (j < a.ld_d) D[j] = j == 0 ? c0 : (j <= n_new ? v[b] : 0.0);
+      }
+    }
+    return;
+  }
+  for (int t0 = 0; t0 < nmove; t0 += SPAN) {
+    double v[DELC_BATCH];
+    if (live) {
+#pragma unroll
+      for (int b = 0; b < DELC_BATCH; b++) {
+        const int t = t0 + b * 64 + lane;
+        v[b] = S[a.src[t < nmove ? t : nmove - 1]]; // behind the last destination: a load nobody stores
+      }
+    }
+    delc_full_wait();
+    if (live) {
+#pragma unroll
+      for (int b = 0; b < DELC_BATCH; b++) {
+        const int t = t0 + b * 64 + lane;
+        if (t < nmove) D[first + t] = v[b];
+      }
+    }
+  }
+  delc_full_wait(); // the chain's loads and the last batch's: the zeros land on positions they read
+  if (!live) return;
+  for (int j = n_new + 1 + lane; j <= n_old; j += 64) D[j] = 0.0;
+  if (body && lane == 0 && a.nsh > 0) D[0] = c0;
+}
+
+void launch_delcols(const DelColsArgs &a, hipStream_t s) {
+  const unsigned nrb = (unsigned)((a.rows_all + DELC_WAVES - 1) / DELC_WAVES);
+  hipLaunchKernelGGL(k_delcols, dim3(nrb + 1), dim3(DELC_THREADS), 0, s, a);
 }
 
 // ---------------------------------------------------------------------------- k_delrows
