@@ -186,19 +186,19 @@ int mvx_add_rows(mvx_prob *P, int nrs) {
   return first;
 }
 
-// the rows num[0..nrs) of P, checked: 0 with `rows` the list in ascending order, -1 for a number out of range or a duplicate
-static int del_rows_check(const mvx_prob *P, int nrs, const int *num, std::vector<int> &rows) {
-  const int m = P->m;
-  std::vector<char> mark((size_t)m + 1, 0);
-  for (int k = 0; k < nrs; k++) {
+// the numbers num[0..cnt) out of 1..N, checked: 0 with `list` holding them in ascending order and `mark` saying which of
+// 0..N are in it, -1 for a number out of range or a duplicate
+static int checked_list(int N, int cnt, const int *num, std::vector<int> &list, std::vector<char> &mark) {
+  mark.assign((size_t)N + 1, 0);
+  for (int k = 0; k < cnt; k++) {
     const int i = num[k];
-    if (i < 1 || i > m || mark[(size_t)i]) return -1;
+    if (i < 1 || i > N || mark[(size_t)i]) return -1;
     mark[(size_t)i] = 1;
   }
-  rows.clear();
-  rows.reserve((size_t)nrs);
-  for (int i = 1; i <= m; i++)
-    if (mark[(size_t)i]) rows.push_back(i);
+  list.clear();
+  list.reserve((size_t)cnt);
+  for (int i = 1; i <= N; i++)
+    if (mark[(size_t)i]) list.push_back(i);
   return 0;
 }
 // the model edit of a checked deletion (`rows` ascending): the engine has not been told yet
@@ -228,7 +228,8 @@ int mvx_del_rows(mvx_prob *P, int nrs, const int *num) {
   if (!P || nrs < 1 || !num) return -1;
   const int m = P->m;
   std::vector<int> rows;
-  if (del_rows_check(P, nrs, num + 1, rows) != 0) return -1;
+  std::vector<char> mark;
+  if (checked_list(m, nrs, num + 1, rows, mark) != 0) return -1;
   del_rows_model(P, rows);
   mvx::engine_del_rows(P, rows, m);
   P->status = MVX_UNDEF;
@@ -247,10 +248,11 @@ int mvx_del_rows_many(mvx_prob *const *Ps, int count, const int *off, const int 
   std::vector<mvx_prob *> hs;
   std::vector<std::vector<int>> lists;
   std::vector<int> m_old;
+  std::vector<char> mark;
   for (int t = 0; t < count; t++) {
     if (off[t + 1] == off[t]) continue; // not touched at all
     std::vector<int> l;
-    if (del_rows_check(Ps[t], off[t + 1] - off[t], rows + off[t], l) != 0) return -1;
+    if (checked_list(Ps[t]->m, off[t + 1] - off[t], rows + off[t], l, mark) != 0) return -1;
     hs.push_back(Ps[t]);
     lists.push_back(std::move(l));
     m_old.push_back(Ps[t]->m);
@@ -262,16 +264,21 @@ int mvx_del_rows_many(mvx_prob *const *Ps, int count, const int *off, const int 
   return 0;
 }
 
+// the model has n columns from now on: the per-column arrays grow, the new columns are continuous, free of cost and fixed at 0
+static void grow_col_arrays(mvx_prob *P, int n) {
+  P->n = n;
+  P->c.resize((size_t)n + 1, 0.0);
+  P->kind.resize((size_t)n + 1, MVX_CV);
+  P->ctype.resize((size_t)n + 1, MVX_FX); // GLPK default column: fixed at 0 [GLPK-recalled]
+  P->clb.resize((size_t)n + 1, 0.0);
+  P->cub.resize((size_t)n + 1, 0.0);
+  if (!P->cname.empty()) P->cname.mut().resize((size_t)n + 1);
+}
+
 int mvx_add_cols(mvx_prob *P, int ncs) {
   if (ncs < 1) fault("add_cols: invalid count");
   const int first = P->n + 1;
-  P->n += ncs;
-  P->c.resize((size_t)P->n + 1, 0.0);
-  P->kind.resize((size_t)P->n + 1, MVX_CV);
-  P->ctype.resize((size_t)P->n + 1, MVX_FX); // GLPK default column: fixed at 0 [GLPK-recalled]
-  P->clb.resize((size_t)P->n + 1, 0.0);
-  P->cub.resize((size_t)P->n + 1, 0.0);
-  if (!P->cname.empty()) P->cname.mut().resize((size_t)P->n + 1);
+  grow_col_arrays(P, P->n + ncs);
   for (int i = 1; i <= P->m; i++) {
     auto row = std::make_shared<std::vector<double>>(*P->A[i]);
     row->resize((size_t)P->n + 1, 0.0);
@@ -298,13 +305,7 @@ int mvx_add_dense_cols(mvx_prob *P, int k, const double *cols, const double *obj
   // the model: what add_cols + set_mat_col + set_col_bnds + set_obj_coef + set_col_kind write
   std::vector<int> flag((size_t)k);
   std::vector<double> nlb((size_t)k), nub((size_t)k);
-  P->n = n + k;
-  P->c.resize((size_t)P->n + 1, 0.0);
-  P->kind.resize((size_t)P->n + 1, MVX_CV);
-  P->ctype.resize((size_t)P->n + 1, MVX_FX);
-  P->clb.resize((size_t)P->n + 1, 0.0);
-  P->cub.resize((size_t)P->n + 1, 0.0);
-  if (!P->cname.empty()) P->cname.mut().resize((size_t)P->n + 1);
+  grow_col_arrays(P, n + k);
   for (int t = 0; t < k; t++) {
     const size_t j = (size_t)(n + 1 + t);
     P->c[j] = obj[t];
@@ -333,21 +334,14 @@ int mvx_del_cols(mvx_prob *P, int ncs, const int *num) {
   if (!P || ncs < 1 || !num) return -1;
   const int m = P->m, n = P->n;
   if (ncs >= n) return -1; // the engine has no LP without columns
-  std::vector<char> mark((size_t)n + 1, 0);
-  for (int k = 1; k <= ncs; k++) {
-    const int j = num[k];
-    if (j < 1 || j > n || mark[(size_t)j]) return -1;
-    mark[(size_t)j] = 1;
-  }
   std::vector<int> cols; // ascending
+  std::vector<char> mark;
+  if (checked_list(n, ncs, num + 1, cols, mark) != 0) return -1;
   std::vector<double> dlb, dub;
-  cols.reserve((size_t)ncs);
-  for (int j = 1; j <= n; j++)
-    if (mark[(size_t)j]) {
-      cols.push_back(j);
-      dlb.push_back(P->clb[(size_t)j]);
-      dub.push_back(P->cub[(size_t)j]);
-    }
+  for (int j : cols) {
+    dlb.push_back(P->clb[(size_t)j]);
+    dub.push_back(P->cub[(size_t)j]);
+  }
   // the model: the kept columns close up in their order
   std::vector<std::string> *names = P->cname.empty() ? nullptr : &P->cname.mut();
   if (names && names->size() < (size_t)n + 1) names->resize((size_t)n + 1);

@@ -481,21 +481,26 @@ static SlabLayout slab_layout(int m_cap, int ld) {
   return L;
 }
 
-static void bind_slab(mvx_prob *P, void *slab, int m_cap, int ld) {
-  SlabLayout L = slab_layout(m_cap, ld);
+// the view of a raw slab laid out as L with row stride ld, and of the slab a handle is bound to
+static SlabView slab_view_at(void *slab, const SlabLayout &L, int ld) {
   unsigned char *b = (unsigned char *)slab;
+  return SlabView{(double *)(b + L.o_T),  (int *)(b + L.o_bvar),  (double *)(b + L.o_blb), (double *)(b + L.o_bub),
+                  (int *)(b + L.o_nvar), (int *)(b + L.o_nflag), (double *)(b + L.o_nlb), (double *)(b + L.o_nub), ld};
+}
+static SlabView slab_view(const mvx_prob *P) {
+  return SlabView{P->d_T, P->d_bvar, P->d_blb, P->d_bub, P->d_nvar, P->d_nflag, P->d_nlb, P->d_nub, P->ld};
+}
+
+static void bind_slab(mvx_prob *P, void *slab, int m_cap, int ld) {
+  const SlabLayout L = slab_layout(m_cap, ld);
+  const SlabView v = slab_view_at(slab, L, ld);
   P->slab = slab;
   P->slab_bytes = L.total;
   P->m_cap = m_cap;
   P->ld = ld;
-  P->d_T = (double *)(b + L.o_T);
-  P->d_bvar = (int *)(b + L.o_bvar);
-  P->d_blb = (double *)(b + L.o_blb);
-  P->d_bub = (double *)(b + L.o_bub);
-  P->d_nvar = (int *)(b + L.o_nvar);
-  P->d_nflag = (int *)(b + L.o_nflag);
-  P->d_nlb = (double *)(b + L.o_nlb);
-  P->d_nub = (double *)(b + L.o_nub);
+  P->d_T = v.T;
+  P->d_bvar = v.bvar, P->d_blb = v.blb, P->d_bub = v.bub;
+  P->d_nvar = v.nvar, P->d_nflag = v.nflag, P->d_nlb = v.nlb, P->d_nub = v.nub;
   // debugging aid: MVX_BIND_FILL="t,a" fills the tableau region with byte t and the small arrays with byte a at every
   // binding (-1: leave), on the main stream (the caller's upload or clone follows on it)
   static const char *bf = std::getenv("MVX_BIND_FILL");
@@ -503,8 +508,8 @@ static void bind_slab(mvx_prob *P, void *slab, int m_cap, int ld) {
     int t = -1, a = -1;
     std::sscanf(bf, "%d,%d", &t, &a);
     hipStream_t st = ctx().main.stream;
-    if (t >= 0) HIPCHECK(hipMemsetAsync(b + L.o_T, t & 255, L.o_bvar - L.o_T, st));
-    if (a >= 0) HIPCHECK(hipMemsetAsync(b + L.o_bvar, a & 255, L.total - L.o_bvar, st));
+    if (t >= 0) HIPCHECK(hipMemsetAsync(v.T, t & 255, L.o_bvar - L.o_T, st));
+    if (a >= 0) HIPCHECK(hipMemsetAsync(v.bvar, a & 255, L.total - L.o_bvar, st));
   }
 }
 
@@ -663,33 +668,51 @@ static bool alloc_device(mvx_prob *P, int m_cap, int ld) {
 
 static int ld_for(int n) { return (int)align_up((size_t)n + 1, LD_ALIGN); }
 
+// A handle on its way to a slab of another geometry (DESIGN.md "Live edits").  slab_move binds the new slab and hands back
+// the view the device work reads (`from`, the old slab) and the one it writes (`to`); both are the handle's own view when the
+// geometry is the one it has.  Once that work is queued, slab_move_done recycles the old slab behind it (in-order stream: the
+// work completes before any reuse).  false: the device is out of memory, the handle is left as it was.
+struct SlabMove {
+  SlabView from, to;
+  void *old_slab = nullptr;
+  size_t old_bytes = 0;
+};
+static bool slab_move(Context &c, mvx_prob *P, int m_cap, int ld, SlabMove &mv) {
+  mv.from = mv.to = slab_view(P);
+  if (m_cap == P->m_cap && ld == P->ld) return true;
+  void *slab = slab_alloc(c, slab_layout(m_cap, ld).total);
+  if (!slab) return false;
+  mv.old_slab = P->slab;
+  mv.old_bytes = P->slab_bytes;
+  bind_slab(P, slab, m_cap, ld);
+  mv.to = slab_view(P);
+  return true;
+}
+static void slab_move_done(Context &c, SlabMove &mv) {
+  if (mv.old_slab) slab_recycle(c, mv.old_slab, mv.old_bytes);
+  mv.old_slab = nullptr;
+}
+
 // grow row capacity, preserving contents; false (handle left as it was) when the device is out of memory
 static bool grow_rows(mvx_prob *P, int m_new) {
   if (m_new + ROW_SPARE <= P->m_cap) return true;
   Context &c = ctx();
   MAIN_LOCK(c);
   flush_copies(c);
-  SolveCtx &sc = c.main;
-  const int cap = m_new + ROW_SLACK;
-  void *o_slab = P->slab;
-  const size_t o_bytes = P->slab_bytes;
-  const int o_rows = P->m_cap + 1, ld = P->ld;
-  double *oT = P->d_T, *oblb = P->d_blb, *obub = P->d_bub, *onlb = P->d_nlb, *onub = P->d_nub;
-  int *obvar = P->d_bvar, *onvar = P->d_nvar, *onflag = P->d_nflag;
-  SlabLayout Ln = slab_layout(cap, ld);
-  void *slab = slab_alloc(c, Ln.total);
-  if (!slab) return false;
-  bind_slab(P, slab, cap, ld);
-  HIPCHECK(hipMemcpyAsync(P->d_T, oT, (size_t)o_rows * ld * 8, hipMemcpyDeviceToDevice, sc.stream));
-  HIPCHECK(hipMemcpyAsync(P->d_bvar, obvar, (size_t)o_rows * 4, hipMemcpyDeviceToDevice, sc.stream));
-  HIPCHECK(hipMemcpyAsync(P->d_blb, oblb, (size_t)o_rows * 8, hipMemcpyDeviceToDevice, sc.stream));
-  HIPCHECK(hipMemcpyAsync(P->d_bub, obub, (size_t)o_rows * 8, hipMemcpyDeviceToDevice, sc.stream));
-  HIPCHECK(hipMemcpyAsync(P->d_nvar, onvar, (size_t)ld * 4, hipMemcpyDeviceToDevice, sc.stream));
-  HIPCHECK(hipMemcpyAsync(P->d_nflag, onflag, (size_t)ld * 4, hipMemcpyDeviceToDevice, sc.stream));
-  HIPCHECK(hipMemcpyAsync(P->d_nlb, onlb, (size_t)ld * 8, hipMemcpyDeviceToDevice, sc.stream));
-  HIPCHECK(hipMemcpyAsync(P->d_nub, onub, (size_t)ld * 8, hipMemcpyDeviceToDevice, sc.stream));
-  // recycle the old slab (in-order stream: the copies above complete before any reuse)
-  slab_recycle(c, o_slab, o_bytes);
+  hipStream_t st = c.main.stream;
+  const size_t rows = (size_t)P->m_cap + 1, ld = (size_t)P->ld;
+  SlabMove mv;
+  if (!slab_move(c, P, m_new + ROW_SLACK, P->ld, mv)) return false;
+  const SlabView &o = mv.from, &v = mv.to;
+  HIPCHECK(hipMemcpyAsync(v.T, o.T, rows * ld * 8, hipMemcpyDeviceToDevice, st));
+  HIPCHECK(hipMemcpyAsync(v.bvar, o.bvar, rows * 4, hipMemcpyDeviceToDevice, st));
+  HIPCHECK(hipMemcpyAsync(v.blb, o.blb, rows * 8, hipMemcpyDeviceToDevice, st));
+  HIPCHECK(hipMemcpyAsync(v.bub, o.bub, rows * 8, hipMemcpyDeviceToDevice, st));
+  HIPCHECK(hipMemcpyAsync(v.nvar, o.nvar, ld * 4, hipMemcpyDeviceToDevice, st));
+  HIPCHECK(hipMemcpyAsync(v.nflag, o.nflag, ld * 4, hipMemcpyDeviceToDevice, st));
+  HIPCHECK(hipMemcpyAsync(v.nlb, o.nlb, ld * 8, hipMemcpyDeviceToDevice, st));
+  HIPCHECK(hipMemcpyAsync(v.nub, o.nub, ld * 8, hipMemcpyDeviceToDevice, st));
+  slab_move_done(c, mv);
   return true;
 }
 
@@ -1890,6 +1913,92 @@ int engine_simplex_batch(mvx_prob **probs, int count, const mvx_smcp *parm_in, i
 }
 
 // -------------------------------------------------------------------------- model edits
+// What every edit of a live tableau shares is written here once (DESIGN.md "Live edits"): the footer, the two ways of giving the
+// tableau up, and the call frame of an edit with device work.
+// The footer of an edit that leaves a valid tableau: what the mirrors hold of tableau rows 1..keep stays current (-1: nothing
+// does), the solution is stale, the status unknown.  fresh_rows is never below -1, so keep = -1 leaves it at -1.
+static void edit_footer(mvx_prob *P, int keep) {
+  P->fresh_rows = P->sol_fresh ? keep : std::min(P->fresh_rows, keep);
+  P->sol_fresh = false;
+  P->status = MVX_UNDEF;
+}
+// The tableau is given up: the next solve starts from the slack basis.  release = false (the edit cannot stay warm): the slab
+// is kept and the next solve builds the slack tableau in it, so a recorded clone INTO it must land first.  release = true (the
+// device is out of memory): the slab goes back to the cache.
+static void edit_give_up(mvx_prob *P, bool release) {
+  if (release) release_device(P);
+  else {
+    Context &c = ctx();
+    MAIN_LOCK(c);
+    flush_copies(c);
+  }
+  engine_invalidate(P);
+}
+// The call frame of an edit of one handle with device work: a NodeCall that sends the recorded clones off first (a recorded
+// clone of the handle receives the bits from before the edit) and brings nothing back.  The caller declares its upload pieces,
+// then begin(): the reservation and, where the edit changes the slab's geometry, the move (from() / to() are the views the
+// launch reads and writes, the same unless the handle moved); false sends the caller to out_of_memory().  Then the pinned side is
+// filled, upload(), the launch, the mirrors, and done(keep): the old slab is recycled behind the launch, the footer, and the
+// synchronise that frees the pinned block.
+class LiveEdit : public NodeCall {
+  mvx_prob *P_;
+  SlabMove mv_;
+
+public:
+  explicit LiveEdit(mvx_prob *P) : NodeCall(NodeFlush::AtEntry, NodeResults::None), P_(P) {}
+  bool begin(int m_cap, int ld) { return reserve() && slab_move(*c, P_, m_cap, ld, mv_); }
+  bool begin() { return begin(P_->m_cap, P_->ld); }
+  const SlabView &from() const { return mv_.from; }
+  const SlabView &to() const { return mv_.to; }
+  int out_of_memory() {
+    edit_give_up(P_, true);
+    return -2;
+  }
+  void done(int keep) {
+    slab_move_done(*c, mv_);
+    edit_footer(P_, keep);
+    fetch();
+  }
+};
+// `cnt` rows have been appended behind row m_old (P->m is the new count): the structural variable numbers move up by cnt and
+// the new rows hold their own auxiliaries
+static void mirrors_rows_appended(mvx_prob *P, int m_old, int cnt) {
+  for (int i = 1; i <= m_old; i++)
+    if (P->bvar[i] > m_old) P->bvar[i] += cnt;
+  for (int q = 1; q <= P->n; q++)
+    if (P->nvar[q] > m_old) P->nvar[q] += cnt;
+  P->bvar.resize((size_t)P->m + 1);
+  for (int t = 0; t < cnt; t++) P->bvar[(size_t)(m_old + 1 + t)] = m_old + 1 + t;
+  rebuild_pos(P);
+}
+// What taking the indices `removed` out of 1..N does to the others, which close up in their order (tableau rows for a row
+// deletion, non-basic positions for a column deletion): `first` the first removed index, src[t] the index that moves to
+// first + t (ascending: what k_delrows and k_delcols are given), newpos the new index of every old one (0: removed)
+struct Compaction {
+  int first = 0;
+  std::vector<int> src, newpos;
+};
+static Compaction compaction(const std::vector<int> &removed, int N) {
+  Compaction pl;
+  pl.newpos.assign((size_t)N + 1, 0);
+  pl.first = N + 1;
+  for (int i : removed) {
+    pl.newpos[(size_t)i] = -1;
+    pl.first = std::min(pl.first, i);
+  }
+  for (int i = 1, w = 0; i <= N; i++) {
+    if (pl.newpos[(size_t)i]) {
+      pl.newpos[(size_t)i] = 0;
+      continue;
+    }
+    pl.newpos[(size_t)i] = ++w;
+    if (i > pl.first) pl.src.push_back(i);
+  }
+  return pl;
+}
+// how many numbers of the ascending list lie below k
+static int count_below(const std::vector<int> &list, int k) { return (int)(std::lower_bound(list.begin(), list.end(), k) - list.begin()); }
+
 void engine_apply_bounds(mvx_prob *P, int k, int type, double old_lb, double old_ub, double lb, double ub) {
   if (!P->valid) return;
   Context &c = ctx();
@@ -1930,9 +2039,7 @@ void engine_apply_bounds(mvx_prob *P, int k, int type, double old_lb, double old
     const double xn = nb_value(flag, lb, ub);
     if (xn != xo) launch_shift_nonbasic(P->d_T, P->ld, P->m, jj, xn - xo, sc.stream);
   }
-  P->sol_fresh = false;
-  P->fresh_rows = -1;
-  P->status = MVX_UNDEF;
+  edit_footer(P, -1);
 }
 
 void engine_add_rows(mvx_prob *P, int first, int nrs) {
@@ -1941,24 +2048,10 @@ void engine_add_rows(mvx_prob *P, int first, int nrs) {
   MAIN_LOCK(c);
   SolveCtx &sc = c.main;
   flush_copies(c);
-  if (!grow_rows(P, P->m)) { // out of memory: the tableau is given up, the next solve restarts from the slack basis
-    release_device(P);
-    engine_invalidate(P);
-    return;
-  }
+  if (!grow_rows(P, P->m)) return edit_give_up(P, true);
   launch_add_rows(P->d_T, P->ld, P->n, P->d_bvar, P->d_blb, P->d_bub, P->d_nvar, first, nrs, P->m, sc.stream);
-  // host mirrors
-  for (int i = 1; i < first; i++)
-    if (P->bvar[i] >= first) P->bvar[i] += nrs;
-  for (int j = 1; j <= P->n; j++)
-    if (P->nvar[j] >= first) P->nvar[j] += nrs;
-  P->bvar.resize((size_t)P->m + 1);
-  for (int r = 0; r < nrs; r++) P->bvar[first + r] = first + r;
-  rebuild_pos(P);
-  // the new rows sit behind the old ones: what the mirrors hold of those stays current
-  P->fresh_rows = P->sol_fresh ? first - 1 : std::min(P->fresh_rows, first - 1);
-  P->sol_fresh = false;
-  P->status = MVX_UNDEF;
+  mirrors_rows_appended(P, first - 1, nrs); // mvx_add_rows appends: first is the old m + 1
+  edit_footer(P, first - 1);                // the new rows sit behind the old ones
 }
 
 // run k_rowcomb with host-provided weights / base, writing row `dst_row` of the tableau
@@ -2022,9 +2115,7 @@ void engine_row_from_model(mvx_prob *P, int i) {
   base[0] = b0;
   rowcomb_into_row(P, w, base, pos);
   P->hint_dual = true; // appended cut rows (cut.cpp:40) leave the basis dual feasible
-  P->fresh_rows = P->sol_fresh ? pos - 1 : std::min(P->fresh_rows, pos - 1); // only tableau row `pos` has been rewritten
-  P->sol_fresh = false;
-  P->status = MVX_UNDEF;
+  edit_footer(P, pos - 1); // only tableau row `pos` has been rewritten
 }
 
 // ------------------------------------------------------------------ a round of cuts: scores (k_cutgram), append (k_cutrows)
@@ -2059,14 +2150,14 @@ int engine_cut_scores(const mvx_prob *P, int k, const double *vals, const double
 
 // `k` dense MVX_LO rows appended in one device pass (mvx_add_cut_rows): the handle is left as k times (add_rows(1), set_mat_row
 // with all n indices, set_row_bnds(LO)) leave it -- model, mirrors, tableau, pending bound edits, fresh_rows, hint_dual,
-// status -- with one grow_rows call, one renumbering of the mirrors, one upload and one k_cutrows launch.  What the kernel
+// status -- with one grow_rows call, one renumbering of the mirrors, one upload and one k_cutrows launch (a LiveEdit).  What the kernel
 // needs of the basis goes up as two index lists (the structural column of every row and of every non-basic position, taken
 // before the renumbering); the weights and the base of engine_row_from_model are entries of `vals` under those lists, and
 // only the row's value at the non-basic point (base[0]) is computed here, in engine_row_from_model's order.
 // The bound of a new row is a pending edit, as engine_apply_bounds leaves it; of the edits that the k single calls would have
 // flushed on the way (MAX_EDITS), those of new rows are written by the kernel itself and those of older rows are launched.
 // Return codes: 0; -1 bad arguments, nothing changed (k < 1, a null, a NaN, a handle without a valid tableau); -2 device out of
-// memory: the model has the rows and the tableau is given up, as engine_add_rows gives it up.
+// memory: the model has the rows and the tableau is given up.
 int engine_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rhs) {
   if (!P || k < 1 || !vals || !rhs || !P->valid) return -1;
   const int m = P->m, n = P->n;
@@ -2087,14 +2178,10 @@ int engine_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rh
   }
   P->m = m + k;
   P->status = MVX_UNDEF;
-  NodeCall f(NodeFlush::AtEntry, NodeResults::None);
+  LiveEdit f(P);
   const size_t o_vals = f.up((size_t)k * row * 8), o_rowcol = f.up((size_t)(m + 1) * 4), o_nbcol = f.up(row * 4);
   const size_t o_rowlb = f.up((size_t)k * 8), o_extra = f.up((size_t)k * 4);
-  if (!grow_rows(P, P->m) || !f.reserve()) {
-    release_device(P);
-    engine_invalidate(P);
-    return -2;
-  }
+  if (!grow_rows(P, P->m) || !f.begin()) return f.out_of_memory();
   unsigned char *hb = f.hb, *db = f.db;
   double *h_vals = (double *)(hb + o_vals), *h_rowlb = (double *)(hb + o_rowlb);
   int *h_rowcol = (int *)(hb + o_rowcol), *h_nbcol = (int *)(hb + o_nbcol), *h_extra = (int *)(hb + o_extra);
@@ -2130,28 +2217,17 @@ int engine_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rh
   }
   f.upload();
   CutRowsArgs a;
-  a.T = P->d_T;
-  a.bvar = P->d_bvar; a.nvar = P->d_nvar;
-  a.blb = P->d_blb; a.bub = P->d_bub;
+  a.v = f.to();
   a.vals = (const double *)(db + o_vals);
   a.rowcol = (const int *)(db + o_rowcol);
   a.nbcol = (const int *)(db + o_nbcol);
   a.rowlb = (const double *)(db + o_rowlb);
   a.extra = (const int *)(db + o_extra);
-  a.m = m; a.n = n; a.ld = P->ld; a.k = k;
+  a.m = m; a.n = n; a.k = k;
   launch_cutrows(a, f.stream());
-  // host mirrors, once
-  for (int i = 1; i <= m; i++)
-    if (P->bvar[i] > m) P->bvar[i] += k;
-  for (int q = 1; q <= n; q++)
-    if (P->nvar[q] > m) P->nvar[q] += k;
-  P->bvar.resize((size_t)P->m + 1);
-  for (int t = 0; t < k; t++) P->bvar[(size_t)(m + 1 + t)] = m + 1 + t;
-  rebuild_pos(P);
+  mirrors_rows_appended(P, m, k); // once
   P->hint_dual = true;
-  P->fresh_rows = P->sol_fresh ? m : std::min(P->fresh_rows, m);
-  P->sol_fresh = false;
-  f.fetch(); // the pinned block is free again
+  f.done(m);
   return 0;
 }
 
@@ -2168,31 +2244,18 @@ static void addcols_tile_columns(double *dst, const double *cols, int k, int m) 
   }
 }
 // `k` structural columns have joined the model as columns n_old+1 .. P->n (mvx_add_dense_cols; DESIGN.md "Column append
-// (add_cols)"): one upload and one k_addcols launch make them non-basic columns of the live tableau.  cols is k x (m+1) by model
-// row, flag / lb / ub the new positions' statuses and normalised bounds.  While ld_for(n) does not change the columns are written
-// in place; otherwise the handle moves to a slab (m_cap, ld_for(n)) that the same launch writes whole, and the old slab is
-// recycled behind the launch, as grow_rows does it.  Recorded clones leave first (NodeFlush::AtEntry): a recorded clone of this
-// handle receives the bits from before the append.  Pending bound edits stay pending: they are keyed by tableau row.
+// (add_cols)"): one upload and one k_addcols launch (a LiveEdit) make them non-basic columns of the live tableau.  cols is
+// k x (m+1) by model row, flag / lb / ub the new positions' statuses and normalised bounds.  While ld_for(n) does not change the
+// columns are written in place; otherwise the handle moves to a slab (m_cap, ld_for(n)) that the same launch writes whole.
+// Pending bound edits stay pending: they are keyed by tableau row.
 // Return codes: 0; -2 device out of memory, the tableau is given up.
 int engine_add_cols_live(mvx_prob *P, int k, const double *cols, const double *obj, const int *flag, const double *lb, const double *ub) {
   const int m = P->m, n = P->n - k; // n: the columns of the tableau as it stands
   const size_t crow = (size_t)m + 1;
-  NodeCall f(NodeFlush::AtEntry, NodeResults::None);
+  LiveEdit f(P);
   const size_t o_cols = f.up(addcols_tiled_bytes(k, m)), o_obj = f.up((size_t)k * 8), o_xs = f.up((size_t)k * 8);
   const size_t o_lb = f.up((size_t)k * 8), o_ub = f.up((size_t)k * 8), o_flag = f.up((size_t)k * 4);
-  const int ld_new = ld_for(n + k);
-  void *o_slab = nullptr, *n_slab = nullptr;
-  size_t o_bytes = 0;
-  bool ok = f.reserve();
-  if (ok && ld_new != P->ld) {
-    n_slab = slab_alloc(*f.c, slab_layout(P->m_cap, ld_new).total);
-    ok = n_slab != nullptr;
-  }
-  if (!ok) {
-    release_device(P);
-    engine_invalidate(P);
-    return -2;
-  }
+  if (!f.begin(P->m_cap, ld_for(n + k))) return f.out_of_memory();
   unsigned char *hb = f.hb, *db = f.db;
   addcols_tile_columns((double *)(hb + o_cols), cols, k, m);
   std::memcpy(hb + o_obj, obj, (size_t)k * 8);
@@ -2204,20 +2267,8 @@ int engine_add_cols_live(mvx_prob *P, int k, const double *cols, const double *o
   f.upload();
   AddColsArgs a;
   std::memset(&a, 0, sizeof a);
-  a.Ts = P->d_T;
-  a.bvar = P->d_bvar; a.nvar = P->d_nvar;
-  a.ld_s = P->ld;
-  if (n_slab) {
-    a.s_nflag = P->d_nflag;
-    a.s_blb = P->d_blb; a.s_bub = P->d_bub; a.s_nlb = P->d_nlb; a.s_nub = P->d_nub;
-    o_slab = P->slab;
-    o_bytes = P->slab_bytes;
-    bind_slab(P, n_slab, P->m_cap, ld_new);
-  }
-  a.Td = P->d_T;
-  a.ld_d = P->ld;
-  a.d_bvar = P->d_bvar; a.d_nvar = P->d_nvar; a.d_nflag = P->d_nflag;
-  a.d_blb = P->d_blb; a.d_bub = P->d_bub; a.d_nlb = P->d_nlb; a.d_nub = P->d_nub;
+  a.s = f.from();
+  a.d = f.to();
   a.cols = (const double *)(db + o_cols);
   a.obj = (const double *)(db + o_obj);
   a.xs = (const double *)(db + o_xs);
@@ -2228,7 +2279,6 @@ int engine_add_cols_live(mvx_prob *P, int k, const double *cols, const double *o
   a.rows = m + 1;
   a.rows_all = P->m_cap + 1;
   launch_addcols(a, f.stream());
-  if (o_slab) slab_recycle(*f.c, o_slab, o_bytes); // in-order stream: the launch completes before any reuse
   // host mirrors
   P->nvar.resize((size_t)n + k + 1);
   P->nflag.resize((size_t)n + k + 1);
@@ -2240,10 +2290,7 @@ int engine_add_cols_live(mvx_prob *P, int k, const double *cols, const double *o
   P->hint_dual = false;
   P->dmat.reset();
   P->rmod.reset();
-  P->sol_fresh = false;
-  P->fresh_rows = -1;
-  P->status = MVX_UNDEF;
-  f.fetch(); // the pinned block is free again
+  f.done(-1);
   return 0;
 }
 
@@ -2273,9 +2320,7 @@ int engine_price_cols(const mvx_prob *P, int k, const double *cols, const double
     f.upload();
     AddColsArgs a;
     std::memset(&a, 0, sizeof a);
-    a.Ts = P->d_T;
-    a.bvar = P->d_bvar; a.nvar = P->d_nvar;
-    a.ld_s = P->ld;
+    a.s = slab_view(P); // no destination
     a.cols = (const double *)(f.db + o_cols);
     a.obj = (const double *)(f.db + o_obj);
     a.dj = (double *)(f.db + o_dj);
@@ -2301,13 +2346,12 @@ int engine_price_cols(const mvx_prob *P, int k, const double *cols, const double
 // With a valid tableau: when every deleted column is non-basic, one upload and one k_delcols launch take their positions out --
 // column 0 is shifted for their resting values in ascending position order, the kept positions close up in their order bit
 // for bit with nflag / nlb / nub, the structural variables are renumbered on the device and in the mirrors -- and the basis
-// stays what it was.  While ld_for(n) does not change this happens in place; otherwise the handle moves to a slab (m_cap,
-// ld_for(n)) that the same launch writes whole, and the old slab is recycled behind the launch, as engine_add_cols_live does
-// it.  The rows behind row m take part: the first of them holds the cost row of the last primal phase 1 (tableau row m+1, see Ctl), so
-// they are not zero over the whole stride; in place they close up like the others, on a relayout they are written as zeros.
-// Recorded clones leave first (NodeFlush::AtEntry): a recorded clone of this handle receives the bits from before the
-// deletion.  Pending bound edits stay pending: they are keyed by tableau row, and no row moves.  When a deleted column is
-// basic it cannot leave without a pivot: the tableau is given up and the next solve starts from the slack basis.
+// stays what it was (a LiveEdit).  While ld_for(n) does not change this happens in place; otherwise the handle moves to a slab
+// (m_cap, ld_for(n)) that the same launch writes whole.  The rows behind row m take part: the first of them holds the cost row
+// of the last primal phase 1 (tableau row m+1, see Ctl), so they are not zero over the whole stride; in place they close up
+// like the others, on a relayout they are written as zeros.
+// Pending bound edits stay pending: they are keyed by tableau row, and no row moves.  When a deleted column is basic it cannot
+// leave without a pivot: the tableau is given up.
 // Return codes: 0; -2 device out of memory, the tableau is given up.
 int engine_del_cols(mvx_prob *P, const std::vector<int> &cols, int n_old, const double *lb, const double *ub) {
   P->dmat.reset();
@@ -2319,27 +2363,18 @@ int engine_del_cols(mvx_prob *P, const std::vector<int> &cols, int n_old, const 
   for (int j : cols) {
     const int pos = P->pos[(size_t)(m + j)];
     if (pos > 0) {
-      // the slab is kept: the next solve builds the slack tableau in it, so a recorded clone INTO it must land first
-      Context &c = ctx();
-      MAIN_LOCK(c);
-      flush_copies(c);
-      engine_invalidate(P);
+      edit_give_up(P, false);
       return 0;
     }
     delpos.push_back(-pos);
   }
-  std::vector<char> gone((size_t)n_old + 1, 0); // by position
-  for (int q : delpos) gone[(size_t)q] = 1;
   std::sort(delpos.begin(), delpos.end());
-  const int first = delpos.front(), nmove = n_new - first + 1;
-  std::vector<int> src; // the source of destination position first + t
-  src.reserve((size_t)nmove);
-  for (int q = first + 1; q <= n_old; q++)
-    if (!gone[(size_t)q]) src.push_back(q);
+  const Compaction pl = compaction(delpos, n_old); // over the non-basic positions
+  const int first = pl.first, nmove = (int)pl.src.size();
   std::vector<int> sh_pos; // the deleted positions that rest on a non-zero value, ascending, and the negated values
   std::vector<double> sh_negx;
   for (int q : delpos) {
-    const size_t t = (size_t)(std::lower_bound(cols.begin(), cols.end(), P->nvar[(size_t)q] - m) - cols.begin());
+    const size_t t = (size_t)count_below(cols, P->nvar[(size_t)q] - m);
     const double x = nb_value(P->nflag[(size_t)q], lb[t], ub[t]);
     if (x != 0.0) {
       sh_pos.push_back(q);
@@ -2347,24 +2382,12 @@ int engine_del_cols(mvx_prob *P, const std::vector<int> &cols, int n_old, const 
     }
   }
   const int nsh = (int)sh_pos.size();
-  NodeCall f(NodeFlush::AtEntry, NodeResults::None);
+  LiveEdit f(P);
   const size_t o_src = f.up((size_t)std::max(1, nmove) * 4), o_del = f.up((size_t)ncs * 4);
   const size_t o_shp = f.up((size_t)std::max(1, nsh) * 4), o_shx = f.up((size_t)std::max(1, nsh) * 8);
-  const int ld_new = ld_for(n_new);
-  void *o_slab = nullptr, *n_slab = nullptr;
-  size_t o_bytes = 0;
-  bool ok = f.reserve();
-  if (ok && ld_new != P->ld) {
-    n_slab = slab_alloc(*f.c, slab_layout(P->m_cap, ld_new).total);
-    ok = n_slab != nullptr;
-  }
-  if (!ok) {
-    release_device(P);
-    engine_invalidate(P);
-    return -2;
-  }
+  if (!f.begin(P->m_cap, ld_for(n_new))) return f.out_of_memory();
   unsigned char *hb = f.hb, *db = f.db;
-  if (nmove) std::memcpy(hb + o_src, src.data(), (size_t)nmove * 4);
+  if (nmove) std::memcpy(hb + o_src, pl.src.data(), (size_t)nmove * 4);
   std::memcpy(hb + o_del, cols.data(), (size_t)ncs * 4);
   if (nsh) {
     std::memcpy(hb + o_shp, sh_pos.data(), (size_t)nsh * 4);
@@ -2373,19 +2396,8 @@ int engine_del_cols(mvx_prob *P, const std::vector<int> &cols, int n_old, const 
   f.upload();
   DelColsArgs a;
   std::memset(&a, 0, sizeof a);
-  a.Ts = P->d_T;
-  a.ld_s = P->ld;
-  a.s_bvar = P->d_bvar; a.s_nvar = P->d_nvar; a.s_nflag = P->d_nflag;
-  a.s_blb = P->d_blb; a.s_bub = P->d_bub; a.s_nlb = P->d_nlb; a.s_nub = P->d_nub;
-  if (n_slab) {
-    o_slab = P->slab;
-    o_bytes = P->slab_bytes;
-    bind_slab(P, n_slab, P->m_cap, ld_new);
-  }
-  a.Td = P->d_T;
-  a.ld_d = P->ld;
-  a.d_bvar = P->d_bvar; a.d_nvar = P->d_nvar; a.d_nflag = P->d_nflag;
-  a.d_blb = P->d_blb; a.d_bub = P->d_bub; a.d_nlb = P->d_nlb; a.d_nub = P->d_nub;
+  a.s = f.from();
+  a.d = f.to();
   a.src = (const int *)(db + o_src);
   a.delc = (const int *)(db + o_del);
   a.sh_pos = (const int *)(db + o_shp);
@@ -2393,27 +2405,20 @@ int engine_del_cols(mvx_prob *P, const std::vector<int> &cols, int n_old, const 
   a.m = m; a.n_old = n_old; a.ncs = ncs; a.first = first; a.nmove = nmove; a.nsh = nsh;
   a.rows_all = P->m_cap + 1;
   launch_delcols(a, f.stream());
-  if (o_slab) slab_recycle(*f.c, o_slab, o_bytes); // in-order stream: the launch completes before any reuse
   // host mirrors: the same compaction and renumbering
-  auto renumber = [&](int k) {
-    if (k <= m) return k;
-    return k - (int)(std::lower_bound(cols.begin(), cols.end(), k - m) - cols.begin());
-  };
+  auto renumber = [&](int k) { return k <= m ? k : k - count_below(cols, k - m); };
   for (int i = 1; i <= m; i++) P->bvar[(size_t)i] = renumber(P->bvar[(size_t)i]);
-  for (int q = 1, w = 0; q <= n_old; q++) {
-    if (gone[(size_t)q]) continue;
-    ++w;
-    P->nvar[(size_t)w] = renumber(P->nvar[(size_t)q]);
-    P->nflag[(size_t)w] = P->nflag[(size_t)q];
+  for (int q = 1; q <= n_old; q++) {
+    const size_t w = (size_t)pl.newpos[(size_t)q]; // w <= q
+    if (!w) continue;
+    P->nvar[w] = renumber(P->nvar[(size_t)q]);
+    P->nflag[w] = P->nflag[(size_t)q];
   }
   P->nvar.resize((size_t)n_new + 1);
   P->nflag.resize((size_t)n_new + 1);
   rebuild_pos(P);
   if (nsh) P->hint_dual = true; // resting values left column 0: the reduced costs stand, a basic variable may have left its bounds
-  P->sol_fresh = false;
-  P->fresh_rows = -1;
-  P->status = MVX_UNDEF;
-  f.fetch(); // the pinned block is free again
+  f.done(-1);
   return 0;
 }
 
@@ -2424,40 +2429,23 @@ int engine_del_cols(mvx_prob *P, const std::vector<int> &cols, int n_old, const 
 // numbers are rewritten on the device and in the mirrors, pending edits follow their rows -- and the basis stays what it was,
 // so a solve that follows takes no pivot.  The map goes up through the node entries' pinned block; nothing waits for the device
 // in front of the launch.  When a deleted row's auxiliary is non-basic, the column it holds cannot be dropped without a pivot:
-// the tableau is given up and the next solve starts from the slack basis.
-// What a deletion does to one tableau, worked out on the host before anything is launched: `first` the first removed tableau
-// row, src[t] the source of destination row first + t, newpos the new place of every tableau row (0: removed).
-struct DelPlan {
-  int first = 0;
-  std::vector<int> src, newpos;
-};
-// false: a deleted row's auxiliary variable is non-basic (the plan is then not filled in)
-static bool del_plan(const mvx_prob *P, const std::vector<int> &rows, int m_old, DelPlan &pl) {
-  std::vector<char> gone((size_t)m_old + 1, 0); // by tableau row
-  pl.first = m_old + 1;
+// the tableau is given up.
+// false: a deleted row's auxiliary variable is non-basic (the plan, over tableau rows, is then not filled in)
+static bool del_plan(const mvx_prob *P, const std::vector<int> &rows, int m_old, Compaction &pl) {
+  std::vector<int> gone; // tableau rows
+  gone.reserve(rows.size());
   for (int i : rows) {
-    const int pos = P->pos[i];
-    if (pos <= 0) return false;
-    gone[(size_t)pos] = 1;
-    pl.first = std::min(pl.first, pos);
+    if (P->pos[i] <= 0) return false;
+    gone.push_back(P->pos[i]);
   }
-  pl.newpos.assign((size_t)m_old + 1, 0);
-  pl.src.clear();
-  for (int r = 1, w = 0; r <= m_old; r++) {
-    if (gone[(size_t)r]) continue;
-    pl.newpos[(size_t)r] = ++w;
-    if (r > pl.first) pl.src.push_back(r);
-  }
+  pl = compaction(gone, m_old);
   return true;
 }
 // the host side of a planned deletion: the mirrors take the kernel's compaction and renumbering, pending bound edits follow
-// their rows, and what the mirrors hold of the rows in front of the first removed one stays current
-static void del_mirrors(mvx_prob *P, const std::vector<int> &rows, int m_old, const DelPlan &pl) {
+// their rows; what the mirrors hold of the rows in front of the first removed one stays current (the caller's footer)
+static void del_mirrors(mvx_prob *P, const std::vector<int> &rows, int m_old, const Compaction &pl) {
   const int nrs = (int)rows.size(), n = P->n;
-  auto renumber = [&](int k) {
-    if (k > m_old) return k - nrs;
-    return k - (int)(std::lower_bound(rows.begin(), rows.end(), k) - rows.begin());
-  };
+  auto renumber = [&](int k) { return k > m_old ? k - nrs : k - count_below(rows, k); };
   for (int r = 1; r <= m_old; r++)
     if (pl.newpos[(size_t)r]) P->bvar[(size_t)pl.newpos[(size_t)r]] = renumber(P->bvar[(size_t)r]);
   P->bvar.resize((size_t)P->m + 1);
@@ -2468,50 +2456,36 @@ static void del_mirrors(mvx_prob *P, const std::vector<int> &rows, int m_old, co
   for (const auto &e : P->pending)
     if (pl.newpos[(size_t)e.row]) P->pending[w++] = {pl.newpos[(size_t)e.row], e.lb, e.ub};
   P->pending.resize(w);
-  P->fresh_rows = P->sol_fresh ? pl.first - 1 : std::min(P->fresh_rows, pl.first - 1);
-  P->sol_fresh = false;
-  P->status = MVX_UNDEF;
 }
 static void del_drop_model_copies(mvx_prob *P, const std::vector<int> &rows) {
   if (P->dmat && rows.front() <= P->dmat->m0) P->dmat.reset();
   if (P->rmod && rows.front() <= P->rmod->m0) P->rmod.reset();
 }
 
+// one handle's k_delrows arguments; the two lists are already in device memory
+static DelRowsArgs delrows_args(const mvx_prob *P, const Compaction &pl, int m_old, const int *d_src, int nrs, const int *d_del) {
+  return DelRowsArgs{slab_view(P), d_src, d_del, pl.first, (int)pl.src.size(), m_old, nrs, P->n};
+}
+
 void engine_del_rows(mvx_prob *P, const std::vector<int> &rows, int m_old) {
   del_drop_model_copies(P, rows);
   if (!P->valid) return;
-  const int nrs = (int)rows.size(), n = P->n;
-  DelPlan pl;
-  if (!del_plan(P, rows, m_old, pl)) {
-    // the slab is kept (the out-of-memory path below gives it back): the next solve builds the slack tableau in it, so a
-    // recorded clone INTO it must land first
-    Context &c = ctx();
-    MAIN_LOCK(c);
-    flush_copies(c);
-    engine_invalidate(P);
-    return;
-  }
-  const int first = pl.first, nmove = (int)pl.src.size();
-  NodeCall f(NodeFlush::AtEntry, NodeResults::None);
+  const int nrs = (int)rows.size();
+  Compaction pl;
+  if (!del_plan(P, rows, m_old, pl)) return edit_give_up(P, false);
+  const int nmove = (int)pl.src.size();
+  LiveEdit f(P);
   const size_t o_src = f.up((size_t)std::max(1, nmove) * 4), o_del = f.up((size_t)nrs * 4);
-  if (!f.reserve()) {
-    release_device(P);
-    engine_invalidate(P);
+  if (!f.begin()) {
+    f.out_of_memory();
     return;
   }
   if (nmove) std::memcpy(f.hb + o_src, pl.src.data(), (size_t)nmove * 4);
   std::memcpy(f.hb + o_del, rows.data(), (size_t)nrs * 4);
   f.upload();
-  DelRowsArgs a;
-  a.T = P->d_T;
-  a.bvar = P->d_bvar; a.nvar = P->d_nvar;
-  a.blb = P->d_blb; a.bub = P->d_bub;
-  a.src = (const int *)(f.db + o_src);
-  a.del = (const int *)(f.db + o_del);
-  a.first = first; a.nmove = nmove; a.m_old = m_old; a.nrs = nrs; a.n = n; a.ld = P->ld;
-  launch_delrows(a, f.stream());
+  launch_delrows(delrows_args(P, pl, m_old, (const int *)(f.db + o_src), nrs, (const int *)(f.db + o_del)), f.stream());
   del_mirrors(P, rows, m_old, pl); // host mirrors: the same compaction and renumbering
-  f.fetch(); // the pinned block is free again
+  f.done(pl.first - 1);
 }
 
 // engine_del_rows on `count` handles whose models have been edited (mvx_del_rows_many): handle t has lost rows[t] (ascending,
@@ -2519,26 +2493,24 @@ void engine_del_rows(mvx_prob *P, const std::vector<int> &rows, int m_old) {
 // of all of them is one upload of [descriptors | src and del lists] and one k_delrows_many launch behind the recorded clones,
 // with no synchronise in front.  A handle without a tableau, or with a non-basic deleted row (tableau given up), takes no part
 // in the launch.  When the arena cannot be reserved for all of them the handles go in two halves, and so on down to a single
-// handle, which then ends as engine_del_rows' out-of-memory path leaves it.
+// handle, which then ends as engine_del_rows' out-of-memory path leaves it.  The frame is a NodeCall of its own: one
+// reservation and one upload serve all handles, and each handle takes its ending from the same functions.
 void engine_del_rows_many(mvx_prob *const *Ps, int count, const std::vector<int> *rows, const int *m_old) {
   struct Item {
     mvx_prob *P;
     const std::vector<int> *rows;
     int m_old;
-    DelPlan pl;
+    Compaction pl;
   };
   std::vector<Item> items;
   for (int t = 0; t < count; t++) {
     del_drop_model_copies(Ps[t], rows[t]);
-    if (Ps[t]->valid) items.push_back(Item{Ps[t], &rows[t], m_old[t], DelPlan()});
+    if (Ps[t]->valid) items.push_back(Item{Ps[t], &rows[t], m_old[t], Compaction()});
   }
   size_t w = 0;
   for (size_t k = 0; k < items.size(); k++) {
     if (!del_plan(items[k].P, *items[k].rows, items[k].m_old, items[k].pl)) {
-      Context &c = ctx(); // as in engine_del_rows: the slab is kept, a recorded clone INTO it must land first
-      MAIN_LOCK(c);
-      flush_copies(c);
-      engine_invalidate(items[k].P);
+      edit_give_up(items[k].P, false);
       continue;
     }
     if (w != k) items[w] = std::move(items[k]);
@@ -2557,19 +2529,15 @@ void engine_del_rows_many(mvx_prob *const *Ps, int count, const std::vector<int>
     NodeCall f(NodeFlush::AtEntry, NodeResults::None);
     size_t ints = 0; // the lists of all handles lie back to back behind the descriptors: src, then del, handle by handle
     for (size_t k = lo; k < hi; k++) ints += items[k].pl.src.size() + items[k].rows->size();
-    const size_t o_hs = f.up((hi - lo) * sizeof(DelManyDesc)), o_lists = f.up(std::max<size_t>(1, ints) * 4);
+    const size_t o_hs = f.up((hi - lo) * sizeof(DelRowsArgs)), o_lists = f.up(std::max<size_t>(1, ints) * 4);
     if (!f.reserve()) {
-      if (hi - lo == 1) {
-        release_device(items[lo].P);
-        engine_invalidate(items[lo].P);
-        return;
-      }
+      if (hi - lo == 1) return edit_give_up(items[lo].P, true);
       const size_t mid = lo + (hi - lo) / 2;
       run(lo, mid);
       run(mid, hi);
       return;
     }
-    DelManyDesc *hs = (DelManyDesc *)(f.hb + o_hs);
+    DelRowsArgs *hs = (DelRowsArgs *)(f.hb + o_hs);
     size_t o = o_lists;
     int max_ld = 0;
     for (size_t k = lo; k < hi; k++) {
@@ -2580,13 +2548,15 @@ void engine_del_rows_many(mvx_prob *const *Ps, int count, const std::vector<int>
       if (nmove) std::memcpy(f.hb + o_src, it.pl.src.data(), nmove * 4);
       std::memcpy(f.hb + o_del, it.rows->data(), nrs * 4);
       o = o_del + nrs * 4;
-      hs[k - lo] = DelManyDesc{P->d_T, P->d_bvar, P->d_nvar, P->d_blb, P->d_bub, (unsigned long long)o_src, (unsigned long long)o_del,
-                               it.pl.first, (int)nmove, it.m_old, (int)nrs, P->n, P->ld};
+      hs[k - lo] = delrows_args(P, it.pl, it.m_old, (const int *)(f.db + o_src), (int)nrs, (const int *)(f.db + o_del));
       max_ld = std::max(max_ld, P->ld);
     }
     f.upload();
-    launch_delrows_many((const DelManyDesc *)(f.db + o_hs), f.db, (int)(hi - lo), max_ld, f.stream());
-    for (size_t k = lo; k < hi; k++) del_mirrors(items[k].P, *items[k].rows, items[k].m_old, items[k].pl);
+    launch_delrows_many((const DelRowsArgs *)(f.db + o_hs), (int)(hi - lo), max_ld, f.stream());
+    for (size_t k = lo; k < hi; k++) {
+      del_mirrors(items[k].P, *items[k].rows, items[k].m_old, items[k].pl);
+      edit_footer(items[k].P, items[k].pl.first - 1);
+    }
     f.fetch(); // the pinned block is free again
   };
   run(0, items.size());
@@ -2609,9 +2579,7 @@ void engine_recompute_cost_row(mvx_prob *P) {
   }
   base[0] = z;
   rowcomb_into_row(P, w, base, 0);
-  P->sol_fresh = false;
-  P->fresh_rows = -1;
-  P->status = MVX_UNDEF;
+  edit_footer(P, -1);
 }
 
 void engine_invalidate(mvx_prob *P) {

@@ -230,6 +230,18 @@ struct NodeRef {
   int m, ld; // rows of this handle (cut rows included), its row stride
 };
 
+// A handle's slab as a kernel that edits it reads or writes it: the tableau with its row stride, the per-row arrays
+// (m_cap + 1 entries) and the per-position arrays (ld entries).  slab_view (engine.cpp) fills it from the handle,
+// slab_view_at from a raw slab and its geometry; a kernel that moves a handle to another slab takes two of them
+struct SlabView {
+  double *T;
+  int *bvar;
+  double *blb, *bub;
+  int *nvar, *nflag;
+  double *nlb, *nub;
+  int ld;
+};
+
 // one cut of a GMI launch: the solved handle it is taken from (a round of a B&B window takes one cut from each of up to
 // 64 node LPs: same columns and same first m0 model rows, their own tableaux, bases and appended cut rows)
 struct GmiNode : NodeRef {
@@ -424,22 +436,20 @@ struct CutGramArgs {
 // and the structural variable numbers moved up by k
 #define CUT_TILE 8 // cuts per lane: each T[i][j] is loaded once for that many new rows
 struct CutRowsArgs {
-  double *T;
-  int *bvar, *nvar;
-  double *blb, *bub;
+  SlabView v;
   const double *vals;  // [k][n+1]
   const int *rowcol;   // [m+1] structural column basic in row i, 0 for an auxiliary
   const int *nbcol;    // [n+1] structural column at non-basic position q, 0 for an auxiliary
   const double *rowlb; // [k] lower bound of new row t on the device (-inf while its edit is still pending on the host)
   const int *extra;    // [k] 1: the t-th single append would have summed a trailing chunk of zero weights (+0.0 added once more)
-  int m, n, ld, k;     // m: rows before the append
+  int m, n, k;         // m: rows before the append
 };
 
 // arguments of k_addcols (mvx_add_dense_cols, mvx_price_cols; DESIGN.md "Column append (add_cols)"): `k` dense structural columns
 // against one tableau.  Image t, tableau row p, is base + S: S sums w_q * T[p][q] over the non-basic positions q = 1..n that hold
 // an auxiliary i <= m (w_q = -cols[t][i]), base is obj[t] in row 0 and cols[t][bvar[p]] where row p's basic variable is an
 // auxiliary.  Pricing (img or dj set): the images go to img / dj and nothing of a slab is written.  Append: the images become
-// columns n+1..n+k of Td (== Ts in place; another slab with stride ld_d on a relayout, which the launch then writes whole: old
+// columns n+1..n+k of d (== s in place; another slab with its own stride on a relayout, which the launch then writes whole: old
 // entries, new columns, zeros), column 0 is shifted by the new columns' resting values xs, and the blocks of row block 0 write the
 // new positions' nvar / nflag / nlb / nub (and carry the per-row and per-position arrays over on a relayout)
 #define ADDCOLS_CT 4      // columns per tile: accumulators a lane holds per row
@@ -447,9 +457,8 @@ struct CutRowsArgs {
 #define ADDCOLS_WAVES 8   // waves per workgroup: ADDCOLS_WAVES * ADDCOLS_RW rows share one gather of the weights
 #define ADDCOLS_CHUNK 512 // non-basic positions whose weights one gather stages in LDS: one per thread
 struct AddColsArgs {
-  const double *Ts; // source tableau, stride ld_s
-  double *Td;       // append: destination tableau, stride ld_d; pricing: nullptr
-  const int *bvar, *nvar; // source basis
+  SlabView s; // the tableau as it stands; of its arrays pricing and the in-place append read bvar and nvar only
+  SlabView d; // append: the destination (s again in place); pricing: all null
   const double *cols;     // [ceil(k / ADDCOLS_CT)][m+1][ADDCOLS_CT]: the columns of a tile side by side, so that the weights of a
                           // position are one 32-byte read; zero behind column k
   const double *obj;      // [k]
@@ -457,12 +466,7 @@ struct AddColsArgs {
   const int *nflag_new;   // [k] their statuses (append)
   const double *nlb_new, *nub_new; // [k] their bounds, +-inf when absent (append)
   double *img, *dj;       // pricing: [k][m+1] (nullable) and [k]
-  // append: the destination's arrays; on a relayout the source's too (nullptr in place)
-  int *d_bvar, *d_nvar, *d_nflag;
-  double *d_blb, *d_bub, *d_nlb, *d_nub;
-  const int *s_nflag;
-  const double *s_blb, *s_bub, *s_nlb, *s_nub;
-  int m, n, k, ld_s, ld_d;
+  int m, n, k;
   int rows;     // tableau rows 0..rows-1 get images (m + 1; 1 when only dj is wanted)
   int rows_all; // rows the launch covers: rows, or m_cap + 1 on a relayout
 };
@@ -472,21 +476,10 @@ struct AddColsArgs {
 // row m = first + nmove - 1) are vacated and zeroed.  del[0..nrs) are the deleted auxiliary variables (= model rows), ascending, for the renumbering
 #define DEL_BATCH 8 // source rows a lane holds in registers before it stores them
 struct DelRowsArgs {
-  double *T;
-  int *bvar, *nvar;
-  double *blb, *bub;
+  SlabView v;
   const int *src; // [nmove]
   const int *del; // [nrs]
-  int first, nmove, m_old, nrs, n, ld;
-};
-// one handle of k_delrows_many (mvx_del_rows_many): DelRowsArgs with the two lists as byte offsets into the uploaded block that
-// holds the descriptors as well; nrs = 0 marks a handle the launch leaves alone
-struct DelManyDesc {
-  double *T;
-  int *bvar, *nvar;
-  double *blb, *bub;
-  unsigned long long o_src, o_del;
-  int first, nmove, m_old, nrs, n, ld;
+  int first, nmove, m_old, nrs, n; // k_delrows_many: nrs = 0 marks a handle the launch leaves alone
 };
 
 // arguments of k_delcols (mvx_del_cols; DESIGN.md "Column deletion (del_cols)"): non-basic columns taken out of one tableau.
@@ -494,25 +487,19 @@ struct DelManyDesc {
 // src[t] > first + t), t < nmove, so that the last kept position is n_new = first + nmove - 1; positions n_new+1 .. n_old are
 // vacated.  Before any entry of a row moves, its column 0 takes the chain T[p][0] = fma(T[p][sh_pos[s]], sh_negx[s], T[p][0]),
 // s = 0 .. nsh-1 (the deleted positions with a non-zero resting value, ascending; sh_negx the negated value), rows 0..m only.
-// Td == Ts: in place, rows 0..rows_all-1 are compacted and their vacated positions zeroed.  Td != Ts (another slab, stride
-// ld_d): the launch writes rows 0..rows_all-1 of Td over the whole stride -- kept entries, zero padding, zero rows behind row
+// d == s: in place, rows 0..rows_all-1 are compacted and their vacated positions zeroed.  d != s (another slab, its own
+// stride): the launch writes rows 0..rows_all-1 of d over the whole stride -- kept entries, zero padding, zero rows behind row
 // m -- and carries the per-row and per-position arrays over.  delc[0..ncs) are the deleted columns, ascending, for the
 // renumbering of the structural variables: m + j becomes m + j - #{deleted < j}
 #define DELC_BATCH 8 // batches of 64 destinations a lane holds in registers before it stores them
 #define DELC_WAVES 8 // waves per workgroup: a wave owns one row
 struct DelColsArgs {
-  const double *Ts; // source tableau, stride ld_s
-  double *Td;       // destination tableau, stride ld_d
-  const int *src;   // [nmove]
+  SlabView s, d; // source and destination (the same in place)
+  const int *src;        // [nmove]
   const int *sh_pos;     // [nsh]
   const double *sh_negx; // [nsh]
   const int *delc;       // [ncs]
-  // the source's arrays and the destination's (the same in place)
-  const int *s_bvar, *s_nvar, *s_nflag;
-  const double *s_blb, *s_bub, *s_nlb, *s_nub;
-  int *d_bvar, *d_nvar, *d_nflag;
-  double *d_blb, *d_bub, *d_nlb, *d_nub;
-  int m, n_old, ncs, first, nmove, nsh, ld_s, ld_d;
+  int m, n_old, ncs, first, nmove, nsh;
   int rows_all; // rows the launch covers: m_cap + 1
 };
 
@@ -613,7 +600,8 @@ void launch_cutrows(const CutRowsArgs &a, hipStream_t);
 void launch_addcols(const AddColsArgs &a, hipStream_t);
 void launch_delcols(const DelColsArgs &a, hipStream_t);
 void launch_delrows(const DelRowsArgs &a, hipStream_t);
-void launch_delrows_many(const DelManyDesc *hs, const unsigned char *base, int handles, int max_ld, hipStream_t);
+void launch_delrows_many(const DelRowsArgs *hs, int handles, int max_ld, hipStream_t); // hs: device memory
+
 void launch_conflict(const ConflictArgs &a, hipStream_t);
 void launch_lsact(const LsArgs &a, int final, hipStream_t);
 void launch_lsiter(const LsArgs &a, hipStream_t);

@@ -1275,7 +1275,7 @@ void launch_cutgram(const CutGramArgs &a, hipStream_t s) {
 __global__ __launch_bounds__(256) void k_cutrows(CutRowsArgs a) {
   __shared__ double s_w[CUT_TILE][ROWCOMB_CHUNK];
   const int m = a.m, n = a.n, k = a.k;
-  const size_t ld = (size_t)a.ld, row = (size_t)n + 1;
+  const size_t ld = (size_t)a.v.ld, row = (size_t)n + 1;
   const int t0 = (int)blockIdx.y * CUT_TILE;
   const int nt = k - t0 < CUT_TILE ? k - t0 : CUT_TILE;
   const int j = (int)blockIdx.x * 256 + TIDX;
@@ -1304,7 +1304,7 @@ __global__ __launch_bounds__(256) void k_cutrows(CutRowsArgs a) {
     if (live) {
 #pragma unroll
       for (int c = 0; c < CUT_TILE; c++) acc[c] = 0.0;
-      const double *Tj = a.T + (size_t)i0 * ld + (size_t)j;
+      const double *Tj = a.v.T + (size_t)i0 * ld + (size_t)j;
       for (int r = 0; r < cnt; r++) {
         const double v = Tj[(size_t)r * ld];
 #pragma unroll
@@ -1323,25 +1323,68 @@ __global__ __launch_bounds__(256) void k_cutrows(CutRowsArgs a) {
       if (c < nt) {
         double o = out[c];
         if (a.extra[t0 + c]) o = o + 0.0;
-        a.T[(size_t)(m + 1 + t0 + c) * ld + (size_t)j] = o;
+        a.v.T[(size_t)(m + 1 + t0 + c) * ld + (size_t)j] = o;
       }
   }
   if (blockIdx.y != 0) return;
   // k_add_rows, k times over: the structural variable numbers move up by k, the new rows hold their own auxiliaries
   const int span = (int)gridDim.x * 256;
   for (int g = j; g <= m || g <= n || g < k; g += span) {
-    if (g >= 1 && g <= m && a.bvar[g] > m) a.bvar[g] += k;
-    if (g >= 1 && g <= n && a.nvar[g] > m) a.nvar[g] += k;
+    if (g >= 1 && g <= m && a.v.bvar[g] > m) a.v.bvar[g] += k;
+    if (g >= 1 && g <= n && a.v.nvar[g] > m) a.v.nvar[g] += k;
     if (g < k) {
-      a.bvar[m + 1 + g] = m + 1 + g;
-      a.blb[m + 1 + g] = a.rowlb[g];
-      a.bub[m + 1 + g] = INFINITY;
+      a.v.bvar[m + 1 + g] = m + 1 + g;
+      a.v.blb[m + 1 + g] = a.rowlb[g];
+      a.v.bub[m + 1 + g] = INFINITY;
     }
   }
 }
 
 void launch_cutrows(const CutRowsArgs &a, hipStream_t s) {
   hipLaunchKernelGGL(k_cutrows, dim3((unsigned)((a.n + 1 + 255) / 256), (unsigned)((a.k + CUT_TILE - 1) / CUT_TILE)), dim3(256), 0, s, a);
+}
+
+// ---------------------------------------------------------------------------- shared by the live-edit kernels
+// position q of a slab's per-position arrays as a freshly built handle has its padding
+__device__ __forceinline__ void slab_pad(const SlabView &d, int q) {
+  d.nvar[q] = 0;
+  d.nflag[q] = MVX_NS;
+  d.nlb[q] = 0.0;
+  d.nub[q] = 0.0;
+}
+// The per-row and per-position arrays of a relayout, by one workgroup of THREADS threads: bvar / blb / bub of rows
+// 0..rows_all-1 are carried over; position g <= kept of `d` takes position from(g) of `s` (from(0) == 0), positions from
+// pad_from on take the padding, those between are the caller's.  renum rewrites the variable number of rows 1..m and of the
+// positions behind 0.
+template <int THREADS, class From, class Renum>
+__device__ __forceinline__ void slab_carry_over(const SlabView &s, const SlabView &d, int tid, int rows_all, int m, int kept, int pad_from,
+                                                From from, Renum renum) {
+  for (int g = tid; g < rows_all; g += THREADS) {
+    const int k = s.bvar[g];
+    d.bvar[g] = (g >= 1 && g <= m) ? renum(k) : k;
+    d.blb[g] = s.blb[g];
+    d.bub[g] = s.bub[g];
+  }
+  for (int g = tid; g < d.ld; g += THREADS) {
+    if (g <= kept) {
+      const int q = from(g);
+      d.nvar[g] = g ? renum(s.nvar[q]) : s.nvar[0];
+      d.nflag[g] = s.nflag[q];
+      d.nlb[g] = s.nlb[q];
+      d.nub[g] = s.nub[q];
+    } else if (g >= pad_from)
+      slab_pad(d, g);
+  }
+}
+// how many entries of the ascending list[0..cnt) lie below k
+__device__ __forceinline__ int count_below(const int *list, int cnt, int k) {
+  int lo = 0, hi = cnt;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (list[mid] < k) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
 }
 
 // ---------------------------------------------------------------------------- k_addcols
@@ -1359,7 +1402,7 @@ void launch_cutrows(const CutRowsArgs &a, hipStream_t s) {
 // the other, because the shift of column 0 by the new columns' resting values (k_shift_nonbasic's fma, t ascending) needs the
 // finished images of the row: lane 0 of the wave that owns the row keeps the running value.  On a relayout the same workgroups
 // first write their rows of the new slab over its whole stride (old entries, zeros; the new columns follow), spare rows included.
-// The blocks of row block 0 do the bookkeeping.  Reads (columns 1..n of Ts, bvar, nvar[1..n]) and writes (column 0, columns
+// The blocks of row block 0 do the bookkeeping.  Reads (columns 1..n of s.T, bvar, nvar[1..n]) and writes (column 0, columns
 // n+1..n+k, nvar[n+1..]) never meet, so no workgroup waits for another.
 #define ADDCOLS_THREADS (64 * ADDCOLS_WAVES)
 __global__ __launch_bounds__(ADDCOLS_THREADS) void k_addcols(AddColsArgs a) {
@@ -1367,19 +1410,19 @@ __global__ __launch_bounds__(ADDCOLS_THREADS) void k_addcols(AddColsArgs a) {
   constexpr int RB = ADDCOLS_WAVES * ADDCOLS_RW;
   const int lane = TIDX & 63, wave = TIDX >> 6;
   const int m = a.m, n = a.n, k = a.k;
-  const size_t lds = (size_t)a.ld_s, ldd = (size_t)a.ld_d, crow = (size_t)m + 1;
+  const size_t lds = (size_t)a.s.ld, ldd = (size_t)a.d.ld, crow = (size_t)m + 1;
   const int rb0 = (int)blockIdx.x * RB;
-  const bool append = a.Td != nullptr;
-  const bool relayout = append && a.Td != a.Ts;
+  const bool append = a.d.T != nullptr;
+  const bool relayout = append && a.d.T != a.s.T;
   if (append) {
     for (int r = 0; r < RB; r++) {
       const int p = rb0 + r;
       if (p >= a.rows_all) break;
       const bool img_row = p < a.rows;
-      double *dst = a.Td + (size_t)p * ldd;
+      double *dst = a.d.T + (size_t)p * ldd;
       if (relayout) {
-        const double *src = a.Ts + (size_t)p * lds;
-        for (int j = TIDX; j < a.ld_d; j += ADDCOLS_THREADS) {
+        const double *src = a.s.T + (size_t)p * lds;
+        for (int j = TIDX; j < a.d.ld; j += ADDCOLS_THREADS) {
           if (j == 0 && img_row) continue; // the row's owner writes column 0 behind the shift
           if (j <= n) dst[j] = src[j];
           else if (j > n + k || !img_row) dst[j] = 0.0;
@@ -1397,8 +1440,8 @@ __global__ __launch_bounds__(ADDCOLS_THREADS) void k_addcols(AddColsArgs a) {
   int hv[ADDCOLS_RW];
 #pragma unroll
   for (int r = 0; r < ADDCOLS_RW; r++) {
-    c0[r] = (append && lane == 0 && r < nr) ? a.Ts[(size_t)(p0 + r) * lds] : 0.0;
-    hv[r] = (lane == 0 && r < nr && p0 + r >= 1) ? a.bvar[p0 + r] : 0;
+    c0[r] = (append && lane == 0 && r < nr) ? a.s.T[(size_t)(p0 + r) * lds] : 0.0;
+    hv[r] = (lane == 0 && r < nr && p0 + r >= 1) ? a.s.bvar[p0 + r] : 0;
   }
   for (int t0 = (int)blockIdx.y * ADDCOLS_CT; t0 < k; t0 += (int)gridDim.y * ADDCOLS_CT) {
     const int nt = k - t0 < ADDCOLS_CT ? k - t0 : ADDCOLS_CT;
@@ -1413,7 +1456,7 @@ __global__ __launch_bounds__(ADDCOLS_THREADS) void k_addcols(AddColsArgs a) {
     double wn[ADDCOLS_CT];
     auto gather = [&](int q0) {
       const int q = q0 + TIDX; // ADDCOLS_CHUNK == workgroup size: one position per thread
-      const int v = q <= n ? a.nvar[q] : m + 1;
+      const int v = q <= n ? a.s.nvar[q] : m + 1;
 #pragma unroll
       for (int c = 0; c < ADDCOLS_CT; c++) wn[c] = (c < nt && v <= m) ? -tile[(size_t)v * ADDCOLS_CT + c] : 0.0;
     };
@@ -1434,7 +1477,7 @@ __global__ __launch_bounds__(ADDCOLS_THREADS) void k_addcols(AddColsArgs a) {
         const int q = q0 + j * 64 + lane;
         double v[ADDCOLS_RW];
 #pragma unroll
-        for (int r = 0; r < ADDCOLS_RW; r++) v[r] = (q <= n && r < nr) ? a.Ts[(size_t)(p0 + r) * lds + (size_t)q] : 0.0;
+        for (int r = 0; r < ADDCOLS_RW; r++) v[r] = (q <= n && r < nr) ? a.s.T[(size_t)(p0 + r) * lds + (size_t)q] : 0.0;
 #pragma unroll
         for (int c = 0; c < ADDCOLS_CT; c++) {
           const double w = s_w[c][j * 64 + lane];
@@ -1459,7 +1502,7 @@ __global__ __launch_bounds__(ADDCOLS_THREADS) void k_addcols(AddColsArgs a) {
           else base = hv[r] <= m ? tile[(size_t)hv[r] * ADDCOLS_CT + c] : 0.0;
           const double val = base + s;
           if (append) {
-            a.Td[(size_t)p * ldd + (size_t)(n + 1 + t)] = val;
+            a.d.T[(size_t)p * ldd + (size_t)(n + 1 + t)] = val;
             const double x = a.xs[t];
             if (x != 0.0) c0[r] = fma(val, x, c0[r]);
           } else {
@@ -1474,34 +1517,17 @@ __global__ __launch_bounds__(ADDCOLS_THREADS) void k_addcols(AddColsArgs a) {
   if (lane == 0) {
 #pragma unroll
     for (int r = 0; r < ADDCOLS_RW; r++)
-      if (r < nr) a.Td[(size_t)(p0 + r) * ldd] = c0[r];
+      if (r < nr) a.d.T[(size_t)(p0 + r) * ldd] = c0[r];
   }
   if (blockIdx.x != 0) return;
   for (int t = TIDX; t < k; t += ADDCOLS_THREADS) {
-    a.d_nvar[n + 1 + t] = m + n + 1 + t;
-    a.d_nflag[n + 1 + t] = a.nflag_new[t];
-    a.d_nlb[n + 1 + t] = a.nlb_new[t];
-    a.d_nub[n + 1 + t] = a.nub_new[t];
+    a.d.nvar[n + 1 + t] = m + n + 1 + t;
+    a.d.nflag[n + 1 + t] = a.nflag_new[t];
+    a.d.nlb[n + 1 + t] = a.nlb_new[t];
+    a.d.nub[n + 1 + t] = a.nub_new[t];
   }
   if (!relayout) return;
-  for (int g = TIDX; g < a.rows_all; g += ADDCOLS_THREADS) {
-    a.d_bvar[g] = a.bvar[g];
-    a.d_blb[g] = a.s_blb[g];
-    a.d_bub[g] = a.s_bub[g];
-  }
-  for (int g = TIDX; g < a.ld_d; g += ADDCOLS_THREADS) {
-    if (g <= n) {
-      a.d_nvar[g] = a.nvar[g];
-      a.d_nflag[g] = a.s_nflag[g];
-      a.d_nlb[g] = a.s_nlb[g];
-      a.d_nub[g] = a.s_nub[g];
-    } else if (g > n + k) {
-      a.d_nvar[g] = 0;
-      a.d_nflag[g] = MVX_NS;
-      a.d_nlb[g] = 0.0;
-      a.d_nub[g] = 0.0;
-    }
-  }
+  slab_carry_over<ADDCOLS_THREADS>(a.s, a.d, TIDX, a.rows_all, m, n, n + k + 1, [](int g) { return g; }, [](int v) { return v; });
 }
 
 void launch_addcols(const AddColsArgs &a, hipStream_t s) {
@@ -1509,7 +1535,7 @@ void launch_addcols(const AddColsArgs &a, hipStream_t s) {
   constexpr int RB = ADDCOLS_WAVES * ADDCOLS_RW;
   const unsigned nrb = (unsigned)((a.rows_all + RB - 1) / RB);
   unsigned nty = 1;
-  if (!a.Td) { // pricing: the tiles are independent
+  if (!a.d.T) { // pricing: the tiles are independent
     const int tiles = (a.k + ADDCOLS_CT - 1) / ADDCOLS_CT;
     nty = (unsigned)(tiles < 65535 ? tiles : 65535);
   }
@@ -1538,15 +1564,7 @@ void launch_addcols(const AddColsArgs &a, hipStream_t s) {
 // No atomics, no LDS, no hand-off between workgroups: a row has one owner, and the small arrays have one.
 #define DELC_THREADS (64 * DELC_WAVES)
 __device__ __forceinline__ int delc_renumber(int k, const int *delc, int ncs, int m) {
-  if (k <= m) return k;
-  const int j = k - m;
-  int lo = 0, hi = ncs; // deleted columns below j: delc is ascending and does not hold j
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (delc[mid] < j) lo = mid + 1;
-    else hi = mid;
-  }
-  return k - lo;
+  return k <= m ? k : k - count_below(delc, ncs, k - m); // delc does not hold k - m
 }
 // every load of this wave has returned, and no lane of the workgroup goes on before all have got here
 __device__ __forceinline__ void delc_full_wait() {
@@ -1559,67 +1577,45 @@ __global__ __launch_bounds__(DELC_THREADS) void k_delcols(DelColsArgs a) {
   const int lane = TIDX & 63, wave = TIDX >> 6;
   const int m = a.m, first = a.first, nmove = a.nmove, n_old = a.n_old, ncs = a.ncs;
   const int n_new = first + nmove - 1;
-  const bool relayout = a.Td != a.Ts;
+  const bool relayout = a.d.T != a.s.T;
   if (blockIdx.x + 1 == gridDim.x) { // the small arrays
     const int tid = TIDX;
     if (!relayout) {
-      for (int g = 1 + tid; g <= m; g += DELC_THREADS) a.d_bvar[g] = delc_renumber(a.s_bvar[g], a.delc, ncs, m);
-      for (int q = 1 + tid; q < first; q += DELC_THREADS) a.d_nvar[q] = delc_renumber(a.s_nvar[q], a.delc, ncs, m);
+      for (int g = 1 + tid; g <= m; g += DELC_THREADS) a.d.bvar[g] = delc_renumber(a.s.bvar[g], a.delc, ncs, m);
+      for (int q = 1 + tid; q < first; q += DELC_THREADS) a.d.nvar[q] = delc_renumber(a.s.nvar[q], a.delc, ncs, m);
       for (int t0 = 0; t0 < nmove; t0 += DELC_THREADS) {
         const int t = t0 + tid;
         int k = 0, fl = 0;
         double lb = 0.0, ub = 0.0;
         if (t < nmove) {
           const int s = a.src[t];
-          k = a.s_nvar[s];
-          fl = a.s_nflag[s];
-          lb = a.s_nlb[s];
-          ub = a.s_nub[s];
+          k = a.s.nvar[s];
+          fl = a.s.nflag[s];
+          lb = a.s.nlb[s];
+          ub = a.s.nub[s];
         }
         delc_full_wait(); // a destination may be another thread's source
         if (t < nmove) {
-          a.d_nvar[first + t] = delc_renumber(k, a.delc, ncs, m);
-          a.d_nflag[first + t] = fl;
-          a.d_nlb[first + t] = lb;
-          a.d_nub[first + t] = ub;
+          a.d.nvar[first + t] = delc_renumber(k, a.delc, ncs, m);
+          a.d.nflag[first + t] = fl;
+          a.d.nlb[first + t] = lb;
+          a.d.nub[first + t] = ub;
         }
       }
       delc_full_wait();
-      for (int q = n_new + 1 + tid; q <= n_old; q += DELC_THREADS) { // as a freshly built handle has its padding
-        a.d_nvar[q] = 0;
-        a.d_nflag[q] = MVX_NS;
-        a.d_nlb[q] = 0.0;
-        a.d_nub[q] = 0.0;
-      }
+      for (int q = n_new + 1 + tid; q <= n_old; q += DELC_THREADS) slab_pad(a.d, q);
     } else {
-      for (int g = tid; g < a.rows_all; g += DELC_THREADS) {
-        const int k = a.s_bvar[g];
-        a.d_bvar[g] = (g >= 1 && g <= m) ? delc_renumber(k, a.delc, ncs, m) : k;
-        a.d_blb[g] = a.s_blb[g];
-        a.d_bub[g] = a.s_bub[g];
-      }
-      for (int g = tid; g < a.ld_d; g += DELC_THREADS) {
-        if (g <= n_new) {
-          const int s = g < first ? g : a.src[g - first];
-          a.d_nvar[g] = g ? delc_renumber(a.s_nvar[s], a.delc, ncs, m) : a.s_nvar[0];
-          a.d_nflag[g] = a.s_nflag[s];
-          a.d_nlb[g] = a.s_nlb[s];
-          a.d_nub[g] = a.s_nub[s];
-        } else {
-          a.d_nvar[g] = 0;
-          a.d_nflag[g] = MVX_NS;
-          a.d_nlb[g] = 0.0;
-          a.d_nub[g] = 0.0;
-        }
-      }
+      slab_carry_over<DELC_THREADS>(
+          a.s, a.d, tid, a.rows_all, m, n_new, n_new + 1, [&](int g) { return g < first ? g : a.src[g - first]; },
+          [&](int k) { return delc_renumber(k, a.delc, ncs, m); });
     }
     return;
   }
   const int p = (int)blockIdx.x * DELC_WAVES + wave;
   const bool live = p < a.rows_all; // wave-uniform
   const bool body = p <= m;         // rows 0..m; the rows behind them are spare (rows_all > m + 1)
-  const double *S = a.Ts + (size_t)(live ? p : 0) * (size_t)a.ld_s;
-  double *D = a.Td + (size_t)(live ? p : 0) * (size_t)a.ld_d;
+  const double *S = a.s.T + (size_t)(live ? p : 0) * (size_t)a.s.ld;
+  double *D = a.d.T + (size_t)(live ? p : 0) * (size_t)a.d.ld;
   double c0 = 0.0;
   if (body) {
     c0 = S[0];
@@ -1633,12 +1629,12 @@ __global__ __launch_bounds__(DELC_THREADS) void k_delcols(DelColsArgs a) {
   if (relayout) {
     if (!live) return;
     if (!body) { // a row behind row m of the new slab: zeros
-      for (int j = lane; j < a.ld_d; j += 64) D[j] = 0.0;
+      for (int j = lane; j < a.d.ld; j += 64) D[j] = 0.0;
       return;
     }
     // the same batches: every load of a batch is issued before its first store, and none of them sits behind a branch (the
     // index is clamped to the kept positions, the padding takes its zero afterwards)
-    for (int j0 = 0; j0 < a.ld_d; j0 += SPAN) {
+    for (int j0 = 0; j0 < a.d.ld; j0 += SPAN) {
       double v[DELC_BATCH];
 #pragma unroll
       for (int b = 0; b < DELC_BATCH; b++) {
@@ -1655,7 +1651,7 @@ __global__ __launch_bounds__(DELC_THREADS) void k_delcols(DelColsArgs a) {
 #pragma unroll
       for (int b = 0; b < DELC_BATCH; b++) {
         const int j = j0 + b * 64 + lane;
-        if (j < a.ld_d) D[j] = j == 0 ? c0 : (j <= n_new ? v[b] : 0.0);
+        if (j < a.d.ld) D[j] = j == 0 ? c0 : (j <= n_new ? v[b] : 0.0);
       }
     }
     return;
@@ -1702,24 +1698,17 @@ void launch_delcols(const DelColsArgs &a, hipStream_t s) {
 // an auxiliary k becomes k - #{deleted < k}, a structural one moves down by the number of deleted rows.
 // No atomics, no LDS, no hand-off between workgroups.
 __device__ __forceinline__ int del_renumber(int k, const int *del, int nrs, int m_old) {
-  if (k > m_old) return k - nrs;
-  int lo = 0, hi = nrs; // deleted auxiliaries below k: del is ascending and does not hold k
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (del[mid] < k) lo = mid + 1;
-    else hi = mid;
-  }
-  return k - lo;
+  return k > m_old ? k - nrs : k - count_below(del, nrs, k); // del does not hold k
 }
 
 // The work of one wave on one handle: the 64 columns of tile `tile`, and for tile 0 the basis arrays and the variable numbers.
 // k_delrows calls it with its own arguments, k_delrows_many with those of the handle its workgroup belongs to.
 __device__ __forceinline__ void delrows_wave(const DelRowsArgs &a, int tile, int lane) {
   const int j = tile * 64 + lane;
-  const size_t ld = (size_t)a.ld;
+  const size_t ld = (size_t)a.v.ld;
   const int first = a.first, nmove = a.nmove;
-  if (j < a.ld) {
-    double *Tj = a.T + (size_t)j;
+  if (j < a.v.ld) {
+    double *Tj = a.v.T + (size_t)j;
     int t0 = 0;
     for (; t0 + DEL_BATCH <= nmove; t0 += DEL_BATCH) {
       double v[DEL_BATCH];
@@ -1741,58 +1730,52 @@ __device__ __forceinline__ void delrows_wave(const DelRowsArgs &a, int tile, int
   }
   if (tile != 0) return;
   const int nrs = a.nrs, m_old = a.m_old;
-  for (int i = 1 + lane; i < first; i += 64) a.bvar[i] = del_renumber(a.bvar[i], a.del, nrs, m_old);
+  for (int i = 1 + lane; i < first; i += 64) a.v.bvar[i] = del_renumber(a.v.bvar[i], a.del, nrs, m_old);
   for (int t0 = 0; t0 < nmove; t0 += 64) {
     const int t = t0 + lane;
     int k = 0;
     double lb = 0.0, ub = 0.0;
     if (t < nmove) {
       const int s = a.src[t];
-      k = a.bvar[s];
-      lb = a.blb[s];
-      ub = a.bub[s];
+      k = a.v.bvar[s];
+      lb = a.v.blb[s];
+      ub = a.v.bub[s];
     }
     __syncthreads(); // every lane's loads of this step are done before any lane stores: a destination may be another lane's source
     if (t < nmove) {
-      a.bvar[first + t] = del_renumber(k, a.del, nrs, m_old);
-      a.blb[first + t] = lb;
-      a.bub[first + t] = ub;
+      a.v.bvar[first + t] = del_renumber(k, a.del, nrs, m_old);
+      a.v.blb[first + t] = lb;
+      a.v.bub[first + t] = ub;
     }
   }
-  for (int q = 1 + lane; q <= a.n; q += 64) a.nvar[q] = del_renumber(a.nvar[q], a.del, nrs, m_old);
+  for (int q = 1 + lane; q <= a.n; q += 64) a.v.nvar[q] = del_renumber(a.v.nvar[q], a.del, nrs, m_old);
 }
 
 __global__ __launch_bounds__(64) void k_delrows(DelRowsArgs a) { delrows_wave(a, (int)blockIdx.x, TIDX); }
 
 void launch_delrows(const DelRowsArgs &a, hipStream_t s) {
-  hipLaunchKernelGGL(k_delrows, dim3((unsigned)((a.ld + 63) / 64)), dim3(64), 0, s, a);
+  hipLaunchKernelGGL(k_delrows, dim3((unsigned)((a.v.ld + 63) / 64)), dim3(64), 0, s, a);
 }
 
 // ---------------------------------------------------------------------------- k_delrows_many
 // The same deletion on many handles in one launch (mvx_del_rows_many, DESIGN.md "Cut purging in the tree (node_purge)"): the
 // grid is (column tiles of the widest handle, handles), a workgroup is one wave and owns 64 columns of ONE handle, which it
 // treats exactly as k_delrows treats them (delrows_wave).  hs[blockIdx.y] is the handle's descriptor -- k_delrows' arguments,
-// with its src and del lists given as byte offsets into the uploaded block `base` that holds the descriptors too -- read at
-// one address by the whole wave.  Handles differ in m, in ld and in how many rows move: a workgroup whose tile lies beyond its
-// handle's ld, or whose handle has nothing to delete, returns at once (the whole wave, so the barrier in delrows_wave is met
-// by all or by none).  Handles own disjoint slabs, and within a handle no two workgroups share a column: no atomics, no LDS, no
-// hand-off between workgroups.
-__global__ __launch_bounds__(64) void k_delrows_many(const DelManyDesc *__restrict__ hs, const unsigned char *__restrict__ base) {
-  const DelManyDesc &h = hs[blockIdx.y];
+// its src and del lists in the uploaded block that holds the descriptors too -- read at one address by the whole wave, and
+// copied once: delrows_wave stores through pointers the compiler cannot tell from hs.  (The lists are reached through pointers
+// out of memory here, so their entries are vector loads of one address where k_delrows has scalar loads.)  Handles
+// differ in m, in ld and in how many rows move: a workgroup whose tile lies beyond its handle's ld, or whose handle has nothing
+// to delete, returns at once (the whole wave, so the barrier in delrows_wave is met by all or by none).  Handles own disjoint
+// slabs, and within a handle no two workgroups share a column: no atomics, no LDS, no hand-off between workgroups.
+__global__ __launch_bounds__(64) void k_delrows_many(const DelRowsArgs *__restrict__ hs) {
+  const DelRowsArgs a = hs[blockIdx.y];
   const int tile = (int)blockIdx.x;
-  if (h.nrs <= 0 || tile * 64 >= h.ld) return;
-  DelRowsArgs a;
-  a.T = h.T;
-  a.bvar = h.bvar; a.nvar = h.nvar;
-  a.blb = h.blb; a.bub = h.bub;
-  a.src = (const int *)(base + h.o_src);
-  a.del = (const int *)(base + h.o_del);
-  a.first = h.first; a.nmove = h.nmove; a.m_old = h.m_old; a.nrs = h.nrs; a.n = h.n; a.ld = h.ld;
+  if (a.nrs <= 0 || tile * 64 >= a.v.ld) return;
   delrows_wave(a, tile, TIDX);
 }
 
-void launch_delrows_many(const DelManyDesc *hs, const unsigned char *base, int handles, int max_ld, hipStream_t s) {
-  hipLaunchKernelGGL(k_delrows_many, dim3((unsigned)((max_ld + 63) / 64), (unsigned)handles), dim3(64), 0, s, hs, base);
+void launch_delrows_many(const DelRowsArgs *hs, int handles, int max_ld, hipStream_t s) {
+  hipLaunchKernelGGL(k_delrows_many, dim3((unsigned)((max_ld + 63) / 64), (unsigned)handles), dim3(64), 0, s, hs);
 }
 
 // ---------------------------------------------------------------------------- k_conflict_rows / k_conflict

@@ -4,6 +4,7 @@
                   for the age limit A = 0..4: every fourth general fixture with an optimum at 5 rounds of GMI cuts, and the four
                   binary dense_ilp models of the clique table that take more than one round, at 10 rounds with both families.
                   Work is counted as tree pivots x (rows the tree's root holds + 1), the entries a dense pivot touches per column.
+  --part call     the first half of --part device alone: the single calls, no trees.
   --part device   one mvx_del_rows(k) call, k = 8 / 32 / 128, on clones of the solved wide 512x1024 root carrying 128 of its own GMI
                   rows, beside one mvx_add_cut_rows(k) call of the same session: host clocks around calls that end in a
                   synchronise, one warm-up first, medians of 7 (--out).  Then whole trees at window 64 with cut_rounds 5 and
@@ -78,10 +79,9 @@ def part_cpu(out):
         sweep("dense_ilp%r" % (case,), [((lambda model=model: synth.load_ilp(orc, *model)), opt)], cut_rounds=10, cut_families=3)
 
 
-def part_device(out, out_trees):
-    import mvolps_amd
+def part_call(out):
     import numpy as np
-    from mvolps_amd import bnb, synth
+    from mvolps_amd import bnb
     from mvolps_amd.capi import BS, OPT
 
     from scripts.cutloop_profile import wide_root_cuts
@@ -117,6 +117,13 @@ def part_device(out, out_trees):
               sum(1 for i in rows if i > m0), "first_row": rows[0], "reps": len(dele), "del_rows_ms": statistics.median(dele) * 1e3,
               "add_cut_rows_ms": statistics.median(app) * 1e3, "pivots_after": a.it_cnt - it0, "same_objective": bool(a.obj == base.obj)}, out)
 
+
+def part_device(out, out_trees):
+    import mvolps_amd
+    from mvolps_amd import bnb, synth
+
+    part_call(out)
+
     def tree(model, **kw):
         t0 = time.perf_counter()
         r = bnb.branch_and_bound(synth.load_ilp(mvolps_amd.api(), *model), quirks=0, window=64, **kw)
@@ -135,12 +142,14 @@ def part_device(out, out_trees):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", choices=["cpu", "device"], required=True)
+    ap.add_argument("--part", choices=["cpu", "call", "device"], required=True)
     ap.add_argument("--out", default=None)
     ap.add_argument("--out-trees", default=None)
     a = ap.parse_args()
     if a.part == "cpu":
         part_cpu(a.out)
+    elif a.part == "call":
+        part_call(a.out)
     else:
         part_device(a.out, a.out_trees)
 
