@@ -286,6 +286,18 @@ int mvx_cut_scores(const mvx_prob *P, int k, const double *vals, double *dot, do
    for the next solve.  Returns 0; -1 bad arguments, nothing changed (k < 1, a null, a NaN, a handle without a valid tableau);
    -2 device out of memory: the model has the rows, the tableau is given up as mvx_add_rows gives it up. */
 int mvx_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rhs);
+/* mvx_add_cut_rows on `count` distinct handles of one column count in one call (DESIGN.md "Row append across handles
+   (add_cut_rows_many)"): handle t takes rows off[t] .. off[t+1]-1 of vals / rhs (off[0] = 0, off ascending; vals is
+   off[count] x (n+1) row-major in the layout of mvx_gmi_cuts, rhs[r] the lower bound of row r).  The handles' row counts may
+   differ.  Every handle that is given rows ends as mvx_add_cut_rows(Ps[t], k_t, vals + off[t]*(n+1), rhs + off[t]) leaves it, bit
+   for bit -- model, tableau, basis arrays, mirrors, pending bound edits, status MVX_UNDEF, a dual warm start -- and the device
+   work of all of them is the recorded clones flushed once, one upload and one k_cutrows_many launch.  A handle that is given no
+   rows is not touched at all (its status stays).  Returns 0; -1 and no handle changed for a null, count < 1, a handle listed
+   twice, differing column counts, a descending off, a NaN in an entry that is read, or a handle without a valid tableau that is
+   given rows (everything is checked before the first handle is edited); -2 device out of memory: the handles that could not
+   get their memory have the rows in the model and their tableau given up, as mvx_add_cut_rows leaves them, the others are
+   complete, and mvx_last_error reads MVX_ENOMEM. */
+int mvx_add_cut_rows_many(mvx_prob *const *Ps, int count, const int *off, const double *vals, const double *rhs);
 /* Column append (DESIGN.md "Column append (add_cols)"): `k` dense structural columns join the model as columns n+1..n+k and,
    where the handle has a valid tableau, the tableau and the basis in one device pass (k_addcols): the new columns are
    non-basic at their resting bound, the basis and every other body entry keep their bits.  cols is k x (m+1) row-major:

@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libmvolps_amd.so")
 _EXTRA = {
     "del_rows": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "del_rows_many": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "add_cut_rows_many": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "ranges": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "ranges_chunk": (C.c_int, []),
     "add_dense_cols": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int),

@@ -233,6 +233,8 @@ def _bind(lib):
     lib.mvx_bnb_clique_cuts.argtypes = [C.c_int, _UP, _DP, C.c_int, _DP, _DP, _IP]
     lib.mvx_del_rows_many.restype = C.c_int
     lib.mvx_del_rows_many.argtypes = [C.c_void_p, C.c_int, _IP, _IP]
+    lib.mvx_add_cut_rows_many.restype = C.c_int
+    lib.mvx_add_cut_rows_many.argtypes = [C.c_void_p, C.c_int, _IP, _DP, _DP]
     lib.mvx_bnb_purge_ages.restype = C.c_int
     lib.mvx_bnb_purge_ages.argtypes = [C.c_int, _IP, C.c_int, C.POINTER(C.c_ubyte), _IP, _IP]
     lib.mvx_polish_many.restype = C.c_int
@@ -963,6 +965,33 @@ def add_cut_rows(prob, vals, rhs):
         return -1
     DP = C.POINTER(C.c_double)
     return lib().mvx_add_cut_rows(prob.h, k, v.ctypes.data_as(DP), r.ctypes.data_as(DP))
+
+
+def add_cut_rows_many(handles, vals_list, rhs_list):
+    """mvx_add_cut_rows_many: handle t of the gfx950 engine takes the rows vals_list[t] (k_t x (n + 1), entry 0 of a row unused;
+    k_t = 0: an empty list, the handle is not touched) as MVX_LO rows with the bounds rhs_list[t]; every handle is left as
+    mvx_add_cut_rows leaves it, the device work of all of them in one upload and one launch.  Returns the call's code (0; -1 bad
+    arguments, no handle changed; -2 device out of memory for some handle)."""
+    import numpy as np
+
+    if len(vals_list) != len(handles) or len(rhs_list) != len(handles):
+        return -1
+    n1 = handles[0].n + 1 if handles else 1
+    vs, rs = [], []
+    for v, r in zip(vals_list, rhs_list):
+        v = np.asarray(v, dtype=np.float64).reshape(-1, n1) if np.size(v) else np.zeros((0, n1))
+        r = np.asarray(r, dtype=np.float64).reshape(-1)
+        if len(r) != v.shape[0]:
+            return -1
+        vs.append(v)
+        rs.append(r)
+    hs = (C.c_void_p * max(1, len(handles)))(*[p.h for p in handles])
+    off = np.zeros(len(handles) + 1, dtype=np.int32)
+    off[1:] = np.cumsum([len(r) for r in rs])
+    vals = np.ascontiguousarray(np.concatenate(vs + [np.zeros((1, n1))]))
+    rhs = np.ascontiguousarray(np.concatenate(rs + [np.zeros(1)]))
+    DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    return lib().mvx_add_cut_rows_many(hs, len(handles), off.ctypes.data_as(IP), vals.ctypes.data_as(DP), rhs.ctypes.data_as(DP))
 
 
 PURGE_COUNTERS = ("cutloop_purged", "cutloop_live_rows")

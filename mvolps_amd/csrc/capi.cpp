@@ -768,6 +768,9 @@ int mvx_cut_scores(const mvx_prob *P, int k, const double *vals, double *dot, do
   return mvx::engine_cut_scores(P, k, vals, x.data(), dot, gram);
 }
 int mvx_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rhs) { return mvx::engine_add_cut_rows(P, k, vals, rhs); }
+int mvx_add_cut_rows_many(mvx_prob *const *Ps, int count, const int *off, const double *vals, const double *rhs) {
+  return mvx::engine_add_cut_rows_many(Ps, count, off, vals, rhs);
+}
 int mvx_conflict_graph(const mvx_prob *model, unsigned long long *adj, long long *edges) {
   return mvx::engine_conflict_graph(model, adj, edges);
 }

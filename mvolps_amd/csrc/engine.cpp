@@ -4,6 +4,7 @@
 // makes (/root/reference/bs.cpp:114-117,274-288; cut.cpp:23-43).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -2158,16 +2159,21 @@ int engine_cut_scores(const mvx_prob *P, int k, const double *vals, const double
 // flushed on the way (MAX_EDITS), those of new rows are written by the kernel itself and those of older rows are launched.
 // Return codes: 0; -1 bad arguments, nothing changed (k < 1, a null, a NaN, a handle without a valid tableau); -2 device out of
 // memory: the model has the rows and the tableau is given up.
-int engine_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rhs) {
-  if (!P || k < 1 || !vals || !rhs || !P->valid) return -1;
-  const int m = P->m, n = P->n;
+// The host work of one handle's append, shared by engine_add_cut_rows and engine_add_cut_rows_many: the checks, the model
+// rows, the pieces of the upload and what goes into them, and the ending.
+// the rows that are read hold no NaN (entry 0 of a row is not read)
+static bool cut_rows_readable(int n, int k, const double *vals, const double *rhs) {
   const size_t row = (size_t)n + 1;
   for (int t = 0; t < k; t++) {
-    if (std::isnan(rhs[t])) return -1;
+    if (std::isnan(rhs[t])) return false;
     for (int j = 1; j <= n; j++)
-      if (std::isnan(vals[(size_t)t * row + (size_t)j])) return -1;
+      if (std::isnan(vals[(size_t)t * row + (size_t)j])) return false;
   }
-  // the model: what add_rows + set_mat_row + set_row_bnds write
+  return true;
+}
+// the model: what add_rows + set_mat_row + set_row_bnds write
+static void cut_rows_model(mvx_prob *P, int k, const double *vals, const double *rhs) {
+  const size_t row = (size_t)P->n + 1;
   for (int t = 0; t < k; t++) {
     auto r = std::make_shared<std::vector<double>>(vals + (size_t)t * row, vals + (size_t)(t + 1) * row);
     (*r)[0] = 0.0;
@@ -2176,15 +2182,27 @@ int engine_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rh
     P->rlb.push_back(rhs[t]);
     P->rub.push_back(INFINITY);
   }
-  P->m = m + k;
+  P->m += k;
   P->status = MVX_UNDEF;
-  LiveEdit f(P);
-  const size_t o_vals = f.up((size_t)k * row * 8), o_rowcol = f.up((size_t)(m + 1) * 4), o_nbcol = f.up(row * 4);
-  const size_t o_rowlb = f.up((size_t)k * 8), o_extra = f.up((size_t)k * 4);
-  if (!grow_rows(P, P->m) || !f.begin()) return f.out_of_memory();
-  unsigned char *hb = f.hb, *db = f.db;
-  double *h_vals = (double *)(hb + o_vals), *h_rowlb = (double *)(hb + o_rowlb);
-  int *h_rowcol = (int *)(hb + o_rowcol), *h_nbcol = (int *)(hb + o_nbcol), *h_extra = (int *)(hb + o_extra);
+}
+// where one handle's pieces lie in the frame's arena (m: rows before the append)
+struct CutRowsPieces {
+  size_t o_vals, o_rowcol, o_nbcol, o_rowlb, o_extra;
+};
+static CutRowsPieces cut_rows_pieces(NodeCall &f, int m, int n, int k) {
+  CutRowsPieces p;
+  p.o_vals = f.up((size_t)k * ((size_t)n + 1) * 8), p.o_rowcol = f.up((size_t)(m + 1) * 4), p.o_nbcol = f.up(((size_t)n + 1) * 4);
+  p.o_rowlb = f.up((size_t)k * 8), p.o_extra = f.up((size_t)k * 4);
+  return p;
+}
+// fills the pinned side of the pieces from the handle as it stands before the renumbering (P->m is already m + k), and books
+// the new rows' bounds as pending edits; edits of older rows that overflow on the way are launched on the frame's stream
+static void cut_rows_fill(mvx_prob *P, int m, int k, const double *vals, const double *rhs, unsigned char *hb, const CutRowsPieces &p,
+                          hipStream_t st) {
+  const int n = P->n;
+  const size_t row = (size_t)n + 1;
+  double *h_vals = (double *)(hb + p.o_vals), *h_rowlb = (double *)(hb + p.o_rowlb);
+  int *h_rowcol = (int *)(hb + p.o_rowcol), *h_nbcol = (int *)(hb + p.o_nbcol), *h_extra = (int *)(hb + p.o_extra);
   std::memcpy(h_vals, vals, (size_t)k * row * 8);
   h_rowcol[0] = 0;
   for (int i = 1; i <= m; i++) h_rowcol[i] = P->bvar[i] > m ? P->bvar[i] - m : 0;
@@ -2208,27 +2226,133 @@ int engine_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rh
   for (int t = 0; t < k; t++) {
     if ((int)P->pending.size() == MAX_EDITS) {
       for (const auto &e : P->pending) {
-        if (e.row <= m) launch_set_basic_bounds(P->d_blb, P->d_bub, e.row, e.lb, e.ub, f.stream());
+        if (e.row <= m) launch_set_basic_bounds(P->d_blb, P->d_bub, e.row, e.lb, e.ub, st);
         else h_rowlb[e.row - m - 1] = e.lb;
       }
       P->pending.clear();
     }
     P->pending.push_back({m + 1 + t, rhs[t], INFINITY});
   }
-  f.upload();
+}
+static CutRowsArgs cut_rows_args(const SlabView &v, int m, int n, int k, const unsigned char *db, const CutRowsPieces &p) {
   CutRowsArgs a;
-  a.v = f.to();
-  a.vals = (const double *)(db + o_vals);
-  a.rowcol = (const int *)(db + o_rowcol);
-  a.nbcol = (const int *)(db + o_nbcol);
-  a.rowlb = (const double *)(db + o_rowlb);
-  a.extra = (const int *)(db + o_extra);
+  a.v = v;
+  a.vals = (const double *)(db + p.o_vals);
+  a.rowcol = (const int *)(db + p.o_rowcol);
+  a.nbcol = (const int *)(db + p.o_nbcol);
+  a.rowlb = (const double *)(db + p.o_rowlb);
+  a.extra = (const int *)(db + p.o_extra);
   a.m = m; a.n = n; a.k = k;
-  launch_cutrows(a, f.stream());
-  mirrors_rows_appended(P, m, k); // once
+  return a;
+}
+// the launch is queued: the mirrors follow it, once (what remains is the footer with keep = m)
+static void cut_rows_appended(mvx_prob *P, int m, int k) {
+  mirrors_rows_appended(P, m, k);
   P->hint_dual = true;
+}
+
+int engine_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rhs) {
+  if (!P || k < 1 || !vals || !rhs || !P->valid) return -1;
+  const int m = P->m, n = P->n;
+  if (!cut_rows_readable(n, k, vals, rhs)) return -1;
+  cut_rows_model(P, k, vals, rhs);
+  LiveEdit f(P);
+  const CutRowsPieces p = cut_rows_pieces(f, m, n, k);
+  if (!grow_rows(P, P->m) || !f.begin()) return f.out_of_memory();
+  cut_rows_fill(P, m, k, vals, rhs, f.hb, p, f.stream());
+  f.upload();
+  launch_cutrows(cut_rows_args(f.to(), m, n, k, f.db, p), f.stream());
+  cut_rows_appended(P, m, k);
   f.done(m);
   return 0;
+}
+
+// engine_add_cut_rows on `count` handles of the same column count in one call (mvx_add_cut_rows_many; DESIGN.md "Row append
+// across handles (add_cut_rows_many)"): handle t takes rows off[t] .. off[t+1]-1 of vals / rhs, and every handle that is given
+// rows ends as engine_add_cut_rows leaves it, bit for bit, through the same functions.  The device work of all of them is the
+// recorded clones flushed once, one upload of [descriptors | first tiles | each handle's lists and rows] and one
+// k_cutrows_many launch, with the grow_rows copies of handles that run out of spare rows and the overflowing bound edits of
+// older rows queued on the same stream in front of it.  A handle that is given no rows is not touched.  Everything is checked
+// before the first handle is edited.  When the arena cannot be reserved for all handles they go in two halves, and so on down to
+// a single handle; that one, or one whose larger slab cannot be had, ends as engine_add_cut_rows' out-of-memory path leaves
+// it while the others complete.  The frame is a NodeCall of its own: one reservation and one upload serve all handles.
+// Return codes: 0; -1 bad arguments, nothing changed (a null, count < 1, a handle twice, differing column counts, a descending
+// off, a NaN that would be read, a handle without a valid tableau that is given rows); -2 device out of memory for some handle.
+int engine_add_cut_rows_many(mvx_prob *const *Ps, int count, const int *off, const double *vals, const double *rhs) {
+  if (!Ps || count < 1 || !off || !vals || !rhs || off[0] != 0) return -1;
+  for (int t = 0; t < count; t++)
+    if (!Ps[t] || off[t + 1] < off[t] || Ps[t]->n != Ps[0]->n) return -1;
+  {
+    std::vector<const mvx_prob *> seen(Ps, Ps + count);
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return -1;
+  }
+  const int n = Ps[0]->n;
+  const size_t row = (size_t)n + 1;
+  struct Item {
+    mvx_prob *P;
+    const double *vals, *rhs;
+    int m, k; // m: rows before the append
+    CutRowsPieces p;
+  };
+  std::vector<Item> items;
+  for (int t = 0; t < count; t++) {
+    const int k = off[t + 1] - off[t];
+    if (k == 0) continue; // not touched at all
+    const double *v = vals + (size_t)off[t] * row, *r = rhs + off[t];
+    if (!Ps[t]->valid || !cut_rows_readable(n, k, v, r)) return -1;
+    items.push_back(Item{Ps[t], v, r, Ps[t]->m, k, CutRowsPieces()});
+  }
+  if (items.empty()) return 0;
+  for (const Item &it : items) cut_rows_model(it.P, it.k, it.vals, it.rhs);
+  int rc = 0;
+  const size_t GRID_Y = 65535;
+  // handles [lo, hi) in as few launches as the arena allows
+  std::function<void(size_t, size_t)> run = [&](size_t lo, size_t hi) {
+    if (hi <= lo) return;
+    NodeCall f(NodeFlush::AtEntry, NodeResults::None);
+    const size_t o_hs = f.up((hi - lo) * sizeof(CutRowsHandle)), o_tiles = f.up((hi - lo) * 4);
+    for (size_t i = lo; i < hi; i++) items[i].p = cut_rows_pieces(f, items[i].m, n, items[i].k);
+    if (!f.reserve()) {
+      rc = -2;
+      if (hi - lo == 1) return edit_give_up(items[lo].P, true);
+      const size_t mid = lo + (hi - lo) / 2;
+      run(lo, mid);
+      run(mid, hi);
+      return;
+    }
+    CutRowsHandle *hs = (CutRowsHandle *)(f.hb + o_hs);
+    int *tiles = (int *)(f.hb + o_tiles);
+    std::vector<Item *> done;
+    size_t ntiles = 0;
+    for (size_t i = lo; i < hi; i++) {
+      Item &it = items[i];
+      if (!grow_rows(it.P, it.P->m)) { // the model has the rows, the tableau is given up; the others complete
+        edit_give_up(it.P, true);
+        rc = -2;
+        continue;
+      }
+      cut_rows_fill(it.P, it.m, it.k, it.vals, it.rhs, f.hb, it.p, f.stream());
+      const CutRowsPieces &p = it.p;
+      tiles[done.size()] = (int)ntiles;
+      hs[done.size()] = CutRowsHandle{slab_view(it.P), p.o_vals, p.o_rowcol, p.o_nbcol, p.o_rowlb, p.o_extra, it.m, it.k, (int)ntiles, 0};
+      ntiles += (size_t)(it.k + CUT_TILE - 1) / CUT_TILE;
+      done.push_back(&it);
+    }
+    if (!done.empty()) {
+      f.upload();
+      for (size_t t0 = 0; t0 < ntiles; t0 += GRID_Y)
+        launch_cutrows_many((const CutRowsHandle *)(f.db + o_hs), (const int *)(f.db + o_tiles), (int)done.size(), f.db, n, (int)t0,
+                            (int)std::min(GRID_Y, ntiles - t0), f.stream());
+      for (Item *it : done) {
+        cut_rows_appended(it->P, it->m, it->k);
+        edit_footer(it->P, it->m);
+      }
+    }
+    f.fetch(); // the pinned block is free again
+  };
+  run(0, items.size());
+  return rc;
 }
 
 // ------------------------------------------------------------------ column append and pricing (k_addcols)

@@ -59,6 +59,7 @@ int engine_pump_obj_many(const mvx_prob *root, const mvx_prob *const *Ps, int co
 // the Gram matrix), and `k` dense MVX_LO rows appended in one device pass (k_cutrows); see engine.cpp
 int engine_cut_scores(const mvx_prob *P, int k, const double *vals, const double *x, double *dot, double *gram);
 int engine_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rhs);
+int engine_add_cut_rows_many(mvx_prob *const *Ps, int count, const int *off, const double *vals, const double *rhs);
 // `k` dense structural columns appended to the live tableau in one device pass (k_addcols; P->n already updated, flag / lb / ub
 // the new positions' statuses and normalised bounds), and the same images without appending; see engine.cpp
 int engine_add_cols_live(mvx_prob *P, int k, const double *cols, const double *obj, const int *flag, const double *lb, const double *ub);

@@ -445,6 +445,17 @@ struct CutRowsArgs {
   int m, n, k;         // m: rows before the append
 };
 
+// one handle of k_cutrows_many (mvx_add_cut_rows_many): k_cutrows' arguments with the pieces as byte offsets into the uploaded
+// block that holds the descriptors too (n is the same for all handles and an argument of the launch), and the handle's first
+// row tile in the launch's flattened tile index
+struct CutRowsHandle {
+  SlabView v;
+  size_t o_vals, o_rowcol, o_nbcol, o_rowlb, o_extra;
+  int m, k;  // m: rows before the append
+  int tile0; // tiles of the handles in front of this one (CUT_TILE rows each)
+  int pad;
+};
+
 // arguments of k_addcols (mvx_add_dense_cols, mvx_price_cols; DESIGN.md "Column append (add_cols)"): `k` dense structural columns
 // against one tableau.  Image t, tableau row p, is base + S: S sums w_q * T[p][q] over the non-basic positions q = 1..n that hold
 // an auxiliary i <= m (w_q = -cols[t][i]), base is obj[t] in row 0 and cols[t][bvar[p]] where row p's basic variable is an
@@ -597,6 +608,10 @@ void launch_objrow(const ObjNode *nodes, int n, int count, hipStream_t);
 void launch_pumpobj(const PumpArgs &a, hipStream_t);
 void launch_cutgram(const CutGramArgs &a, hipStream_t);
 void launch_cutrows(const CutRowsArgs &a, hipStream_t);
+// hs, tile0s (the handles' first tiles, ascending) and base (what the descriptors' offsets count from): device memory;
+// the launch covers tiles [tile_base, tile_base + ntiles) of the flattened index, ntiles <= 65535
+void launch_cutrows_many(const CutRowsHandle *hs, const int *tile0s, int handles, const unsigned char *base, int n, int tile_base, int ntiles,
+                         hipStream_t);
 void launch_addcols(const AddColsArgs &a, hipStream_t);
 void launch_delcols(const DelColsArgs &a, hipStream_t);
 void launch_delrows(const DelRowsArgs &a, hipStream_t);

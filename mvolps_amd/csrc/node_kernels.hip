@@ -1272,11 +1272,12 @@ void launch_cutgram(const CutGramArgs &a, hipStream_t s) {
 // all of them (coalesced), and reads the chunk's weights from LDS, where the workgroup gathers them from `vals` once per chunk
 // (every lane reads the same word: a broadcast).  No partial buffer, no second launch.  The workgroups of the first tile row
 // also do the bookkeeping of k_add_rows; they write bvar / nvar / blb / bub, which no workgroup of this kernel reads.
-__global__ __launch_bounds__(256) void k_cutrows(CutRowsArgs a) {
-  __shared__ double s_w[CUT_TILE][ROWCOMB_CHUNK];
+// The work of one workgroup: column tile blockIdx.x and row tile `ty` of the handle whose arguments are `a`.  k_cutrows calls
+// it with its own arguments, k_cutrows_many with those of the handle its workgroup belongs to.
+__device__ __forceinline__ void cutrows_tile(const CutRowsArgs &a, int ty, double (*s_w)[ROWCOMB_CHUNK]) {
   const int m = a.m, n = a.n, k = a.k;
   const size_t ld = (size_t)a.v.ld, row = (size_t)n + 1;
-  const int t0 = (int)blockIdx.y * CUT_TILE;
+  const int t0 = ty * CUT_TILE;
   const int nt = k - t0 < CUT_TILE ? k - t0 : CUT_TILE;
   const int j = (int)blockIdx.x * 256 + TIDX;
   const bool live = j <= n;
@@ -1326,7 +1327,7 @@ __global__ __launch_bounds__(256) void k_cutrows(CutRowsArgs a) {
         a.v.T[(size_t)(m + 1 + t0 + c) * ld + (size_t)j] = o;
       }
   }
-  if (blockIdx.y != 0) return;
+  if (ty != 0) return;
   // k_add_rows, k times over: the structural variable numbers move up by k, the new rows hold their own auxiliaries
   const int span = (int)gridDim.x * 256;
   for (int g = j; g <= m || g <= n || g < k; g += span) {
@@ -1338,6 +1339,11 @@ __global__ __launch_bounds__(256) void k_cutrows(CutRowsArgs a) {
       a.v.bub[m + 1 + g] = INFINITY;
     }
   }
+}
+
+__global__ __launch_bounds__(256) void k_cutrows(CutRowsArgs a) {
+  __shared__ double s_w[CUT_TILE][ROWCOMB_CHUNK];
+  cutrows_tile(a, (int)blockIdx.y, s_w);
 }
 
 void launch_cutrows(const CutRowsArgs &a, hipStream_t s) {
@@ -1776,6 +1782,42 @@ __global__ __launch_bounds__(64) void k_delrows_many(const DelRowsArgs *__restri
 
 void launch_delrows_many(const DelRowsArgs *hs, int handles, int max_ld, hipStream_t s) {
   hipLaunchKernelGGL(k_delrows_many, dim3((unsigned)((max_ld + 63) / 64), (unsigned)handles), dim3(64), 0, s, hs);
+}
+
+// ---------------------------------------------------------------------------- k_cutrows_many
+// The same append on many handles in one launch (mvx_add_cut_rows_many, DESIGN.md "Row append across handles
+// (add_cut_rows_many)"): blockIdx.x is the 256-column tile (all handles have n columns), tile_base + blockIdx.y a row tile of
+// the launch's flattened index over all handles, CUT_TILE new rows of ONE handle, which the workgroup treats exactly as k_cutrows
+// treats them (cutrows_tile).  tile0s[h] is the first tile of handle h, ascending and strictly so (every handle of the launch
+// has rows): the workgroup's handle is the last one whose first tile is not behind its own, found with count_below.  The
+// descriptors are reached by pointer and hs[h] is read at one address by the whole workgroup; its pieces are offsets into the
+// uploaded block `base`, which holds the descriptors too.  It is copied once: cutrows_tile stores through pointers the compiler
+// cannot tell from hs.  The first tile of each handle does that handle's bookkeeping, which no workgroup of the launch reads
+// (the structural lists come up with the call).  Handles own disjoint slabs, and within a handle a workgroup owns its 256
+// columns of its CUT_TILE new rows: no atomics, no hand-off between workgroups.
+__global__ __launch_bounds__(256) void k_cutrows_many(const CutRowsHandle *__restrict__ hs, const int *__restrict__ tile0s, int handles,
+                                                      const unsigned char *__restrict__ base, int n, int tile_base) {
+  __shared__ double s_w[CUT_TILE][ROWCOMB_CHUNK];
+  const int tile = tile_base + (int)blockIdx.y;
+  const int h = count_below(tile0s, handles, tile + 1) - 1; // tile0s[0] == 0: h >= 0
+  const CutRowsHandle d = hs[h];
+  CutRowsArgs a;
+  a.v = d.v;
+  a.vals = (const double *)(base + d.o_vals);
+  a.rowcol = (const int *)(base + d.o_rowcol);
+  a.nbcol = (const int *)(base + d.o_nbcol);
+  a.rowlb = (const double *)(base + d.o_rowlb);
+  a.extra = (const int *)(base + d.o_extra);
+  a.m = d.m; a.n = n; a.k = d.k;
+  const int ty = tile - d.tile0;
+  if (ty * CUT_TILE >= d.k) return; // not reached: the tiles of a launch are those of its handles
+  cutrows_tile(a, ty, s_w);
+}
+
+void launch_cutrows_many(const CutRowsHandle *hs, const int *tile0s, int handles, const unsigned char *base, int n, int tile_base, int ntiles,
+                         hipStream_t s) {
+  hipLaunchKernelGGL(k_cutrows_many, dim3((unsigned)((n + 1 + 255) / 256), (unsigned)ntiles), dim3(256), 0, s, hs, tile0s, handles, base, n,
+                     tile_base);
 }
 
 // ---------------------------------------------------------------------------- k_conflict_rows / k_conflict
