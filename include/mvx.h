@@ -339,6 +339,18 @@ int mvx_del_cols_span(void); /* destination positions a wave of k_delcols moves 
    Bit-identical to mvx_bnb_conflict_graph (mvx_bnb.h).  Returns 0; -1 bad arguments; -2 device out of memory; -5 is kept for a
    kernel with a size limit (the driver then runs the twin): k_conflict has none and never returns it. */
 int mvx_conflict_graph(const mvx_prob *model, unsigned long long *adj, long long *edges);
+/* Clique cuts in the tree (DESIGN.md "Clique cuts in the tree (node_cliques)"): the separation of mvx_bnb_clique_cuts (mvx_bnb.h)
+   for `count` solved handles in one launch (k_cliquesep), against the conflict graph of `root` -- exactly mvx_conflict_graph(root),
+   computed on the device on the first call and kept with `root` beside the model of mvx_round_many, checked on every call by the
+   same rule -- and each handle's own column values, the bits mvx_get_col_prim returns.  cnt[t] the cliques kept for handle t, in
+   the order of the twin; q[(t*max_cuts + c)*W + w] the member set of clique c in the word layout of adj (W = ceil((n+1)/64),
+   bit 0 zero); sum[t*max_cuts + c] its s, summed over ascending columns from +0.0.  Slots from cnt[t] on are zero.  Pure: no
+   handle changes; the handles may have other row counts than `root` (cut rows).  Bit-identical to mvx_bnb_clique_masks.  Returns
+   0 (count == 0 does nothing); -1 bad arguments (a null, count < 0, max_cuts outside 1..64, a handle with another column
+   count); -2 device out of memory, nothing written; -3 a handle whose status is not MVX_OPT; -5 more than 4096 columns (the
+   driver then runs the twin). */
+int mvx_clique_cuts_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, int max_cuts, int *cnt, unsigned long long *q,
+                         double *sum);
 /* Incumbent polishing (DESIGN.md "Incumbent polishing (polish)"): a best-improvement search over one- and two-column unit moves
    from each of `count` points, against the model of `root` (rows 1..m0, row and column bounds, kinds, objective and sense; kept
    with `root` and checked on every call, as for mvx_round_many, the by-row copy of mvx_propagate_many included).  x is count x

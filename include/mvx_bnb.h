@@ -133,6 +133,15 @@ typedef struct mvx_lp_api {
      tree (node_purge)"): handle t loses the rows rows[off[t] .. off[t+1]-1] (1-based), 0 on success; without it, or when it
      fails, the tree's purge calls del_rows handle by handle, and without that makes each purged row a free row */
   int (*del_rows_many)(void *const *Ps, int count, const int *off, const int *rows);
+  /* optional (may be NULL): the clique separation of `count` solved handles against the conflict graph of `root` in one call
+     (mvx_clique_cuts_many; DESIGN.md "Clique cuts in the tree (node_cliques)"); without it, or when it returns -5, the host twin
+     mvx_bnb_clique_masks runs handle by handle */
+  int (*clique_cuts_many)(const void *root, const void *const *Ps, int count, int max_cuts, int *cnt, unsigned long long *q, double *sum);
+  /* optional (may be NULL): add_cut_rows on `count` distinct handles in one call (mvx_add_cut_rows_many): handle t takes rows
+     off[t] .. off[t+1]-1 of vals / rhs; without it, or when it returns -1, the tree's clique rows go through add_cut_rows handle
+     by handle, and without that through add_rows / set_mat_row / set_row_bnds row by row.  -2 (device memory) means the rows are
+     in every model: nothing is appended again */
+  int (*add_cut_rows_many)(void *const *Ps, int count, const int *off, const double *vals, const double *rhs);
 } mvx_lp_api;
 
 const mvx_lp_api *mvx_hip_lp_api(void);
@@ -218,6 +227,12 @@ typedef struct {
                            root cut rounds -- leaves both children of a branching node once its auxiliary variable has been basic
                            at A consecutive branching nodes on the path.  Outside 0..64: refused; A > 0 needs
                            reference_quirks = 0 and best_window = 0, and get_row_stat in the table */
+  int node_cliques;     /* clique cuts in the tree (DESIGN.md "Clique cuts in the tree (node_cliques)"): 0 (default) off; K = 1..64:
+                           every node that reaches the branch decision with an OPT LP has up to K violated cliques of the model's
+                           conflict graph separated against its LP as solved, and their rows go to both children, behind the
+                           purge and in front of the rc_fix lists, the propagation and the first solve.  Outside 0..64: refused;
+                           K > 0 needs reference_quirks = 0 and best_window = 0.  Independent of cut_strat and of the root cut
+                           rounds */
 } mvx_bnb_params;
 
 /* B&B events at the emit points of bs.cpp (message.h EventType) */
@@ -295,6 +310,9 @@ typedef struct {
   long long node_purge_calls;   /* node_purge > 0: child handles that lost at least one row */
   long long node_purge_rows;    /* ... rows removed, summed over the child handles (deleted, or made free rows) */
   long long node_cut_rows_peak; /* the most live rows behind the caller's rows that any solved node carried (with node_purge = 0 too) */
+  long long node_clique_conflicts; /* node_cliques > 0: edges of the conflict graph of the model */
+  long long node_clique_calls;     /* ... branching nodes whose LP was separated */
+  long long node_clique_rows;      /* ... cliques kept for them, summed: each is one row in both children */
 } mvx_bnb_result;
 
 void mvx_bnb_default_params(mvx_bnb_params *p);
@@ -497,6 +515,15 @@ int mvx_bnb_conflict_graph(const mvx_lp_api *api, const void *model, unsigned lo
    on Q and 0 elsewhere and rhs[t] = -1: the MVX_LO row sum_{j in Q} x_j <= 1.  Stops at max_cuts; *count the rows written.
    Returns 0; -1 bad arguments (n < 0, max_cuts < 0, a null) */
 int mvx_bnb_clique_cuts(int n, const unsigned long long *adj, const double *x, int max_cuts, double *vals, double *rhs, int *count);
+/* Clique cuts in the tree (DESIGN.md "Clique cuts in the tree (node_cliques)"), host twin of mvx_clique_cuts_many for one solved
+   handle: the separation above against the column values of `prob` (get_col_prim_all / get_col_prim) and the graph adj of n
+   columns.  *cnt the cliques kept, q[c*W + w] the member set of clique c in the word layout of adj (W = ceil((n+1)/64)), sum[c]
+   its s; the slots from *cnt to max_cuts are zero.  Works through the table only; the handle is not changed.  Returns 0; -1 bad
+   arguments (a null, max_cuts outside 1..64, another column count); -2 the table lacks an accessor it needs; -3 the handle is
+   not MVX_OPT.  mvx_branchAndBound returns -1 (*res empty) for node_cliques outside 0..64 and for node_cliques > 0 with
+   reference_quirks = 1 or best_window > 0, and -2, with the tree so far, when the graph or a separation could not be computed */
+int mvx_bnb_clique_masks(const mvx_lp_api *api, const void *prob, int n, const unsigned long long *adj, int max_cuts, int *cnt,
+                         unsigned long long *q, double *sum);
 
 /* Incumbent polishing (DESIGN.md "Incumbent polishing (polish)"), host twin of mvx_polish_many for one point x[1..n] (x[0] is not
    touched), edited in place, against the model of `root`: its rows, bounds, kinds, objective and sense.  *ok 0: the point is

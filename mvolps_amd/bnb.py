@@ -19,15 +19,63 @@ _OPTIONAL = ["simplex_batch", "get_obj_dir", "gmi_cuts", "gmi_cuts_many", "get_c
              "branch_penalties_many", "round_many", "rc_tighten_many", "tighten_cols_many", "propagate_many", "set_col_bnds_many",
              "dive_pick_many", "set_obj_coef", "set_obj_many", "pump_obj_many", "cut_scores", "add_cut_rows", "conflict_graph", "del_rows",
              "polish_many", "del_rows_many"]
+# What the C structs have gained behind the fields listed in this file's three classes.  The classes keep their lists (code that
+# walks _fields_ or _OPTIONAL sees what it saw before); an instance made by calling the class is allocated over the WHOLE C
+# struct, zeroed, and the appended part is reached by name: tail_get / tail_set for any of them, table_entry / set_table_entry
+# for the table, attributes for the parameters and counters.  Views on memory the library owns (from_address, pointers) are
+# whole structs already.
+_TABLE_TAIL = ["clique_cuts_many", "add_cut_rows_many"]
 
 
-class LpApiTable(C.Structure):
+def _with_tail(cls, tail):
+    """Gives cls the layout of the whole C struct (its own fields, then `tail`) for allocation and for access by name."""
+    cls._full_ = type(cls.__name__ + "Whole", (C.Structure,), {"_fields_": list(cls._fields_) + list(tail)})
+    cls._tail_ = {name: (getattr(cls._full_, name).offset, ctype) for name, ctype in tail}
+    for name, ctype in cls._fields_:  # the listed fields sit where the C struct has them
+        assert getattr(cls, name).offset == getattr(cls._full_, name).offset
+
+
+def tail_get(obj, name):
+    off, ctype = type(obj)._tail_[name]
+    return ctype.from_address(C.addressof(obj) + off).value
+
+
+def tail_set(obj, name, value):
+    off, ctype = type(obj)._tail_[name]
+    ctype.from_address(C.addressof(obj) + off).value = value
+
+
+def _tail_attr(name):
+    return property(lambda self: tail_get(self, name), lambda self, value: tail_set(self, name, value))
+
+
+class _WholeStruct(C.Structure):
+    def __new__(cls, *args, **kw):
+        return cls.from_buffer(cls._full_())
+
+
+class LpApiTable(_WholeStruct):
     """struct mvx_lp_api: the GLPK-shaped function table the driver calls through."""
 
     _fields_ = [(name, C.c_void_p) for name in _FIELDS + _OPTIONAL]
 
 
-class BnbParams(C.Structure):
+_with_tail(LpApiTable, [(name, C.c_void_p) for name in _TABLE_TAIL])
+
+
+def table_entry(table, name):
+    """An entry of the table by name, appended ones (_TABLE_TAIL) included: its address, or None."""
+    return tail_get(table, name) if name in _TABLE_TAIL else getattr(table, name)
+
+
+def set_table_entry(table, name, value):
+    if name in _TABLE_TAIL:
+        tail_set(table, name, value)
+    else:
+        setattr(table, name, value)
+
+
+class BnbParams(_WholeStruct):
     _fields_ = [
         ("var_strat", C.c_int),
         ("node_strat", C.c_int),
@@ -59,6 +107,10 @@ class BnbParams(C.Structure):
         ("polish", C.c_int),
         ("node_purge", C.c_int),
     ]
+    node_cliques = _tail_attr("node_cliques")
+
+
+_with_tail(BnbParams, [("node_cliques", C.c_int)])
 
 
 class BnbEvent(C.Structure):
@@ -74,7 +126,7 @@ class BnbEvent(C.Structure):
     ]
 
 
-class BnbResult(C.Structure):
+class BnbResult(_WholeStruct):
     _fields_ = [
         ("n_nodes", C.c_int),
         ("parent", C.POINTER(C.c_int)),
@@ -134,6 +186,13 @@ class BnbResult(C.Structure):
         ("node_purge_rows", C.c_longlong),
         ("node_cut_rows_peak", C.c_longlong),
     ]
+    node_clique_conflicts = _tail_attr("node_clique_conflicts")
+    node_clique_calls = _tail_attr("node_clique_calls")
+    node_clique_rows = _tail_attr("node_clique_rows")
+
+
+NODE_CLIQUE_COUNTERS = ("node_clique_conflicts", "node_clique_calls", "node_clique_rows")
+_with_tail(BnbResult, [(name, C.c_longlong) for name in NODE_CLIQUE_COUNTERS])
 
 
 def table_from(api):
@@ -142,9 +201,9 @@ def table_from(api):
     for name in _FIELDS:
         fn = getattr(api.lib, api.prefix + name)
         setattr(t, name, C.cast(fn, C.c_void_p).value)
-    for name in _OPTIONAL:  # optional entries stay NULL when the library does not export them
+    for name in _OPTIONAL + _TABLE_TAIL:  # optional entries stay NULL when the library does not export them
         fn = getattr(api.lib, api.prefix + name, None) if hasattr(api.lib, api.prefix + name) else None
-        setattr(t, name, C.cast(fn, C.c_void_p).value if fn is not None else None)
+        set_table_entry(t, name, C.cast(fn, C.c_void_p).value if fn is not None else None)
     return t
 
 
@@ -231,6 +290,10 @@ def _bind(lib):
     lib.mvx_bnb_conflict_graph.argtypes = [C.c_void_p, C.c_void_p, _UP, _LP]
     lib.mvx_bnb_clique_cuts.restype = C.c_int
     lib.mvx_bnb_clique_cuts.argtypes = [C.c_int, _UP, _DP, C.c_int, _DP, _DP, _IP]
+    lib.mvx_clique_cuts_many.restype = C.c_int
+    lib.mvx_clique_cuts_many.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, _IP, _UP, _DP]
+    lib.mvx_bnb_clique_masks.restype = C.c_int
+    lib.mvx_bnb_clique_masks.argtypes = [C.c_void_p, C.c_void_p, C.c_int, _UP, C.c_int, _IP, _UP, _DP]
     lib.mvx_del_rows_many.restype = C.c_int
     lib.mvx_del_rows_many.argtypes = [C.c_void_p, C.c_int, _IP, _IP]
     lib.mvx_add_cut_rows_many.restype = C.c_int
@@ -337,13 +400,16 @@ def result_to_dict(res):
         "node_purge_calls": res.node_purge_calls,
         "node_purge_rows": res.node_purge_rows,
         "node_cut_rows_peak": res.node_cut_rows_peak,
+        "node_clique_conflicts": res.node_clique_conflicts,
+        "node_clique_calls": res.node_clique_calls,
+        "node_clique_rows": res.node_clique_rows,
     }
 
 
 def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, window=None, cut_select=0, cut_chance=1.0,
                 best_window=None, sb_cands=None, sb_iters=None, heur=None, rc_fix=None, prop=None, dive=None, dive_freq=None,
                 dive_depth=None, pump=None, pump_freq=None, pump_alpha=None, cut_rounds=None, cut_round_max=None, cut_maxpar=None,
-                cut_families=None, cut_purge=None, polish=None, node_purge=None):
+                cut_families=None, cut_purge=None, polish=None, node_purge=None, node_cliques=None):
     """mvx_bnb_params with ParameterObj's defaults (util.h:65-67) overridden by the arguments (None: the default)."""
     pr = BnbParams()
     lib().mvx_bnb_default_params(C.byref(pr))
@@ -390,13 +456,16 @@ def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, l
         pr.polish = polish
     if node_purge is not None:
         pr.node_purge = node_purge
+    if node_cliques is not None:
+        pr.node_cliques = node_cliques
     return pr
 
 
 def branch_and_bound(prob, var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, table=None, window=None,
                      cut_select=0, cut_chance=1.0, best_window=None, sb_cands=None, sb_iters=None, heur=None, rc_fix=None, prop=None,
                      dive=None, dive_freq=None, dive_depth=None, pump=None, pump_freq=None, pump_alpha=None, cut_rounds=None,
-                     cut_round_max=None, cut_maxpar=None, cut_families=None, cut_purge=None, polish=None, node_purge=None):
+                     cut_round_max=None, cut_maxpar=None, cut_families=None, cut_purge=None, polish=None, node_purge=None,
+                     node_cliques=None):
     """Run the driver on `prob` (a capi.Prob).  table=None uses the gfx950 engine's own table.  best_window > 1 with
     node_strat=1: the speculative best-bound window (mvx_bnb_params.best_window).  var_strat 3 / 4: branching on the node
     LP's penalties / strong branching (sb_cands candidates, sb_iters pivots per child).  heur 1 / 2: the primal rounding
@@ -415,13 +484,15 @@ def branch_and_bound(prob, var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, 
     polish = N in 1..100000: every point that becomes the incumbent is first improved by a best-improvement search over one- and
     two-column unit moves, at most N of them (quirks=0; every single-GPU driver, best_window included).  node_purge = A in
     1..64: a cut row behind the caller's rows leaves both children of a branching node once its auxiliary variable has been basic
-    at A branching nodes in a row on the path (quirks=0, not with best_window; NODE_PURGE_COUNTERS in the dictionary).  The
+    at A branching nodes in a row on the path (quirks=0, not with best_window; NODE_PURGE_COUNTERS in the dictionary).
+    node_cliques = K in 1..64: up to K violated cliques of the model's conflict graph are separated at every branching node and
+    appended to both children (quirks=0, not with best_window; NODE_CLIQUE_COUNTERS in the dictionary).  The
     dictionary's "rc" is mvx_branchAndBound's return code (-1 refused parameters, -2 penalties, heuristic, tightening,
     propagation, pumps or dives unavailable)."""
     L = lib()
     pr = make_params(var_strat, node_strat, cut_strat, max_nodes, quirks, lazy_pool, window, cut_select, cut_chance, best_window, sb_cands,
                      sb_iters, heur, rc_fix, prop, dive, dive_freq, dive_depth, pump, pump_freq, pump_alpha, cut_rounds, cut_round_max,
-                     cut_maxpar, cut_families, cut_purge, polish, node_purge)
+                     cut_maxpar, cut_families, cut_purge, polish, node_purge, node_cliques)
     res = BnbResult()
     tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
     rc = L.mvx_branchAndBound(tptr, prob.h, C.byref(pr), C.byref(res))
@@ -1107,6 +1178,40 @@ def clique_cuts(adj, x, max_cuts):
     rc = lib().mvx_bnb_clique_cuts(n, words.ctypes.data_as(C.POINTER(C.c_ulonglong)), xs.ctypes.data_as(DP), max_cuts, vals.ctypes.data_as(DP),
                                    rhs.ctypes.data_as(DP), C.byref(cnt))
     return rc, vals[: cnt.value], rhs[: cnt.value]
+
+
+def clique_cuts_many(root, probs, max_cuts, table=False, adj=None):
+    """The clique separation of the solved handles `probs` against the conflict graph of `root` (DESIGN.md "Clique cuts in the
+    tree (node_cliques)"): (rc, cnt int32 array of count, q uint64 array (count, max_cuts, W), sum array (count, max_cuts)).
+    table=False: mvx_clique_cuts_many, the gfx950 engine's kernel.  Otherwise the host twin mvx_bnb_clique_masks handle by handle
+    through `table` (None = the gfx950 engine's table), the graph taken by conflict_words(root, table) unless `adj` gives its
+    words; rc is then the first failing call's code."""
+    import numpy as np
+
+    n, count = root.n, len(probs)
+    W = (n + 1 + 63) // 64
+    k = max(1, max_cuts)
+    cnt = np.zeros(max(1, count), dtype=np.int32)
+    q = np.zeros((max(1, count), k, W), dtype=np.uint64)
+    s = np.zeros((max(1, count), k), dtype=np.float64)
+    IP, UP, DP = C.POINTER(C.c_int), C.POINTER(C.c_ulonglong), C.POINTER(C.c_double)
+    if table is False:
+        hs = (C.c_void_p * max(1, count))(*[P.h for P in probs])
+        rc = lib().mvx_clique_cuts_many(root.h, hs, count, max_cuts, cnt.ctypes.data_as(IP), q.ctypes.data_as(UP), s.ctypes.data_as(DP))
+    else:
+        tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
+        rc = 0
+        if adj is None:
+            rc, adj, _edges = conflict_words(root, table)
+        words = np.ascontiguousarray(adj, dtype=np.uint64)
+        for t, P in enumerate(probs):
+            if rc != 0:
+                break
+            one = C.c_int(0)
+            rc = lib().mvx_bnb_clique_masks(tptr, P.h, n, words.ctypes.data_as(UP), max_cuts, C.byref(one), q[t].ctypes.data_as(UP),
+                                            s[t].ctypes.data_as(DP))
+            cnt[t] = one.value
+    return rc, cnt[:count], q[:count], s[:count]
 
 
 def generate_cut_gmi(prob, j, table=None):

@@ -57,6 +57,10 @@ extern "C" int mvx_polish_many(const mvx_prob *root, int count, double *x, int m
 extern "C" int mvx_del_rows(mvx_prob *P, int nrs, const int *num) __attribute__((weak));
 extern "C" int mvx_del_rows_many(mvx_prob *const *Ps, int count, const int *off, const int *rows) __attribute__((weak));
 extern "C" const char *mvx_get_col_name(const mvx_prob *P, int j) __attribute__((weak));
+extern "C" int mvx_clique_cuts_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, int max_cuts, int *cnt, unsigned long long *q,
+                                    double *sum) __attribute__((weak));
+extern "C" int mvx_add_cut_rows_many(mvx_prob *const *Ps, int count, const int *off, const double *vals, const double *rhs)
+    __attribute__((weak));
 
 namespace {
 
@@ -2304,6 +2308,119 @@ struct RuleBook {
   long long calls = 0, found = 0, improved = 0, lps = 0, pivots = 0;
 };
 
+// ---- clique cuts in the tree (node_cliques, DESIGN.md "Clique cuts in the tree (node_cliques)") ----
+
+// What the separation kept for one node: cnt member sets of W words each, in the twin's order.
+struct CliqueOut {
+  int cnt = 0;
+  std::vector<unsigned long long> q;
+};
+
+// The rule's state for one tree: the conflict graph of `model`, taken once, the route to the separation (the table's
+// clique_cuts_many while it accepts the model, the twin without it or once it has answered -5) and the counters.
+class NodeCliques {
+public:
+  NodeCliques(const mvx_lp_api *api, const void *model, int K) : _api(api), _model(model), _K(K) {}
+  bool on() const { return _K > 0 && _edges > 0; }
+  // tree start: the graph through the table's conflict_graph, or through the twin without it or on -5.  0, or -2
+  int start() {
+    if (_K <= 0) return 0;
+    _n = _api->get_num_cols(_model);
+    _W = ((size_t)_n + 1 + 63) / 64;
+    _adj.assign(((size_t)_n + 1) * _W, 0ULL);
+    int rc = _api->conflict_graph ? _api->conflict_graph(_model, _adj.data(), &_edges) : -5;
+    if (rc == -5) rc = mvx_bnb_conflict_graph(_api, _model, _adj.data(), &_edges);
+    if (rc != 0) _edges = 0;
+    return rc == 0 ? 0 : -2;
+  }
+  // the separation of the solved handles hs, one result each; 0, or the failing call's code
+  int compute(const std::vector<const void *> &hs, std::vector<CliqueOut> &out) {
+    const size_t count = hs.size(), per = (size_t)_K * _W;
+    out.assign(count, CliqueOut());
+    if (count == 0) return 0;
+    std::vector<int> cnt(count, 0);
+    std::vector<unsigned long long> q(count * per, 0ULL);
+    std::vector<double> sum(count * (size_t)_K, 0.0);
+    bool done = false;
+    if (_api->clique_cuts_many && _device) {
+      const int rc = _api->clique_cuts_many(_model, hs.data(), (int)count, _K, cnt.data(), q.data(), sum.data());
+      if (rc == -5) _device = false;
+      else if (rc != 0) return rc;
+      else done = true;
+    }
+    if (!done)
+      for (size_t t = 0; t < count; t++) {
+        const int rc = mvx_bnb_clique_masks(_api, hs[t], _n, _adj.data(), _K, &cnt[t], &q[t * per], &sum[t * (size_t)_K]);
+        if (rc != 0) return rc;
+      }
+    for (size_t t = 0; t < count; t++) {
+      out[t].cnt = cnt[t];
+      out[t].q.assign(q.begin() + (long)(t * per), q.begin() + (long)(t * per + (size_t)cnt[t] * _W));
+    }
+    return 0;
+  }
+  // a node that branches books its result
+  void book(const CliqueOut &o) {
+    _calls++;
+    _rows += o.cnt;
+  }
+  // Child kids[t] takes the cliques *lists[t] (not empty) as rows -1 on Q >= -1, all children in one add_cut_rows_many call; on
+  // -1, or without the entry, add_cut_rows handle by handle, and without that add_rows / set_mat_row / set_row_bnds row by row.
+  // -2 is device memory: the rows are in every model, nothing is appended again.  With `ages` the rows enter the children's
+  // age arrays at 0.
+  void append(const std::vector<MVOLP::NodeData *> &kids, const std::vector<const CliqueOut *> &lists, bool ages) {
+    if (kids.empty()) return;
+    const size_t row = (size_t)_n + 1;
+    std::vector<void *> hs;
+    std::vector<int> off(1, 0);
+    std::vector<double> vals, rhs;
+    for (size_t t = 0; t < kids.size(); t++) {
+      hs.push_back(kids[t]->prob);
+      for (int c = 0; c < lists[t]->cnt; c++) {
+        const size_t base = vals.size();
+        vals.resize(base + row, 0.0);
+        for (int j = 1; j <= _n; j++)
+          if ((lists[t]->q[(size_t)c * _W + (size_t)j / 64] >> (j % 64)) & 1ULL) vals[base + (size_t)j] = -1.0;
+        rhs.push_back(-1.0);
+      }
+      off.push_back((int)rhs.size());
+    }
+    const int rc = _api->add_cut_rows_many ? _api->add_cut_rows_many(hs.data(), (int)hs.size(), off.data(), vals.data(), rhs.data()) : -1;
+    if (rc != 0 && rc != -2) {
+      std::vector<int> inds(row);
+      for (size_t j = 0; j < row; j++) inds[j] = (int)j;
+      for (size_t t = 0; t < kids.size(); t++) {
+        const int k = lists[t]->cnt;
+        const double *v = vals.data() + (size_t)off[t] * row, *r = rhs.data() + off[t];
+        const int arc = _api->add_cut_rows ? _api->add_cut_rows(hs[t], k, v, r) : -1;
+        if (arc == 0 || arc == -2) continue;
+        for (int c = 0; c < k; c++) {
+          const int index = _api->add_rows(hs[t], 1);
+          _api->set_mat_row(hs[t], index, _n, inds.data(), v + (size_t)c * row);
+          _api->set_row_bnds(hs[t], index, MVX_LO, r[c], 0);
+        }
+      }
+    }
+    if (ages)
+      for (size_t t = 0; t < kids.size(); t++) kids[t]->age.resize(kids[t]->age.size() + (size_t)lists[t]->cnt, 0);
+  }
+  void store(mvx_bnb_result *res) const {
+    res->node_clique_conflicts = _edges;
+    res->node_clique_calls = _calls;
+    res->node_clique_rows = _rows;
+  }
+
+private:
+  const mvx_lp_api *_api;
+  const void *_model;
+  const int _K;
+  int _n = 0;
+  size_t _W = 0;
+  std::vector<unsigned long long> _adj;
+  long long _edges = 0, _calls = 0, _rows = 0;
+  bool _device = true;
+};
+
 // ---- what the three drivers share: the tree's state and what happens to a node once its LP is solved ----
 
 // bs.cpp:229-233: the sum of the fractional parts of a solved node's violated columns
@@ -2616,6 +2733,11 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const void *model, const m
   Prop prop(T.hm, prm.prop);
   Dive dive(T.hm, prm);
   Pump pump(T.hm, prm);
+  NodeCliques ncl(api, T.hm.root, prm.node_cliques);
+  if (ncl.start() != 0) { // the graph could not be taken: the tree so far is the unsolved root
+    T.rc_out = -2;
+    leafContainer.clear();
+  }
 
   while (!leafContainer.empty()) { // bs.cpp:96
     if (T.node_limit()) break;
@@ -2677,6 +2799,17 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const void *model, const m
         rcl = std::move(got[0]);
         rcfix.book(rcl);
       }
+      // node_cliques: the violated cliques of the LP as solved, in front of the cut step; their rows go to both children
+      CliqueOut ncq;
+      if (ncl.on() && api->get_status(a) == MVX_OPT) {
+        std::vector<CliqueOut> got;
+        if (ncl.compute({a}, got) != 0) {
+          T.rc_out = -2;
+          break;
+        }
+        ncq = std::move(got[0]);
+        ncl.book(ncq);
+      }
       // var_strat 3 / 4 read the node's LP: they choose on it as solved, in front of the cut step
       int pick = 0;
       double bound = 0.0;
@@ -2709,6 +2842,7 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const void *model, const m
       child_bounds(api, a, pick, bound, T.quirks, S2->prob, S3->prob);
       T.purge_inherit(*node, a, *S2, *S3);
       if (!gone.empty()) T.purge_children({S2.get(), S3.get()}, {&gone, &gone});
+      if (ncq.cnt > 0) ncl.append({S2.get(), S3.get()}, {&ncq, &ncq}, prm.node_purge > 0);
       // prop: both children behind their branching bound and the rc_fix list, in front of their first solve; whatever code
       // a failing call gives (no accessors, device memory, a refused list), the tree so far goes back with -2
       if ((!rcl.empty() && rcfix.apply({S2->prob, S3->prob}, {&rcl, &rcl}) != 0) || (prm.prop > 0 && prop.run({S2->prob, S3->prob}) != 0)) {
@@ -2731,7 +2865,9 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const void *model, const m
   }
   leafContainer.clear();
   api->delete_prob(a);
-  return T.finish(res, &rcfix, &prop);
+  const int rc = T.finish(res, &rcfix, &prop);
+  ncl.store(res);
+  return rc;
 }
 
 // Window mode: the front W nodes of the FIFO deque are solved together (one batched launch carries
@@ -2752,10 +2888,12 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const void *model, c
   Prop prop(T.hm, prm.prop);
   Dive dive(T.hm, prm);
   Pump pump(T.hm, prm);
+  NodeCliques ncl(api, T.hm.root, prm.node_cliques);
   auto fail = [&]() { // whatever code a failing call gives, the tree so far goes back with -2
     T.rc_out = -2;
     stop = true;
   };
+  if (ncl.start() != 0) fail(); // the graph could not be taken: the tree so far is the unsolved root
 
   struct Branch {
     size_t slot;
@@ -2763,6 +2901,7 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const void *model, c
     int before2, before3;
     RcList rc; // rc_fix: the bound list both children take in front of their first solve
     std::vector<int> gone; // node_purge: the positions of the tree cut rows both children lose
+    CliqueOut cliques;     // node_cliques: the rows both children take
   };
   // One round of the loop.  Its child solves (phase C) run on a worker thread while the main thread replays
   // the next window, whose nodes were solved rounds ago: a breadth-first queue is longer than the window
@@ -2896,7 +3035,7 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const void *model, c
     // that qualify.  may[w]: node w is neither infeasible nor integral, so it branches unless its bound prunes it; opt[w]: and
     // its LP ended OPT.
     std::vector<char> may, opt;
-    if (prm.var_strat >= 3 || prm.heur > 0 || prm.rc_fix > 0 || dive.on() || pump.on()) {
+    if (prm.var_strat >= 3 || prm.heur > 0 || prm.rc_fix > 0 || dive.on() || pump.on() || ncl.on()) {
       if (info.empty()) {
         info.resize(W);
         for (size_t w = 0; w < W; w++) info[w] = printInfo(api, a[w], quirks);
@@ -2942,6 +3081,13 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const void *model, c
     for (size_t w = 0; w < dsel.size(); w++) dsel[w] = opt[w] && dive.selects(*leafContainer[w]);
     std::vector<DiveOut> dres(dsel.size());
     if (dive.on() && on_slots(a, dsel, 0, dres, [&](const auto &hs, const auto &, auto &got) { return dive.run(hs, got); }) != 0) {
+      fail();
+      break;
+    }
+    // node_cliques: the separation of every node of the window that may branch, in one call; booked by the replay for the nodes
+    // that do branch.  A result depends on the node's own LP and the model's graph only, so it is the serial loop's
+    std::vector<CliqueOut> cres(ncl.on() ? W : 0);
+    if (ncl.on() && on_slots(a, opt, 0, cres, [&](const auto &hs, const auto &, auto &got) { return ncl.compute(hs, got); }) != 0) {
       fail();
       break;
     }
@@ -3008,6 +3154,11 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const void *model, c
           node_rc = std::move(rclist[w]);
           rcfix.book(node_rc);
         }
+        CliqueOut node_cl;
+        if (ncl.on() && opt[w]) {
+          node_cl = std::move(cres[w]);
+          ncl.book(node_cl);
+        }
         const int pick = prm.var_strat >= 3 ? choice[w].pick : params.pickVar(vars);
         const double bound = api->get_col_prim(aw, pick);
         if (prm.var_strat >= 3) T.book_choice(choice[w]);
@@ -3037,6 +3188,7 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const void *model, c
         br.rc = std::move(node_rc);
         T.purge_inherit(*node, aw, *br.S2, *br.S3);
         br.gone = std::move(gone);
+        br.cliques = std::move(node_cl);
         branches.push_back(br);
         leafContainer.push_back(br.S2); // the queue order bs.cpp:297-298 gives them
         leafContainer.push_back(br.S3);
@@ -3060,6 +3212,19 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const void *model, c
           lists.push_back(&br.gone);
         }
       T.purge_children(kids, lists);
+    }
+    // node_cliques: every child of the round takes its parent's cliques as rows in one call, behind the purge
+    if (ncl.on()) {
+      std::vector<MVOLP::NodeData *> kids;
+      std::vector<const CliqueOut *> lists;
+      for (const Branch &br : branches)
+        if (br.cliques.cnt > 0) {
+          kids.push_back(br.S2.get());
+          kids.push_back(br.S3.get());
+          lists.push_back(&br.cliques);
+          lists.push_back(&br.cliques);
+        }
+      ncl.append(kids, lists, prm.node_purge > 0);
     }
     // rc_fix: every child of the round takes its parent's list in one call, behind its branching bound and in front of its
     // first solve
@@ -3165,7 +3330,9 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const void *model, c
     std::fprintf(stderr, "bnb window timing: A %.1f ms  B %.1f ms (printInfo %.1f, clone %.1f, cuts %.1f of which the round's device pass %.1f)  waiting for child solves %.1f ms\n", tA * 1e3,
                  tB * 1e3, tB_info * 1e3, tB_clone * 1e3, tB_cuts * 1e3, tB_rcuts * 1e3, tWait * 1e3);
   leafContainer.clear();
-  return T.finish(res, &rcfix, &prop);
+  const int rc = T.finish(res, &rcfix, &prop);
+  ncl.store(res);
+  return rc;
 }
 
 // printInfo of a round's nodes: one mvx_lp_api.classify_many call when the engine has it (one device launch for all of
@@ -3494,6 +3661,12 @@ const mvx_lp_api g_hip_api = {
     mvx_del_rows_many ? +[](void *const *Ps, int count, const int *off, const int *rows) {
       return mvx_del_rows_many((mvx_prob *const *)Ps, count, off, rows);
     } : nullptr,
+    mvx_clique_cuts_many ? +[](const void *root, const void *const *Ps, int count, int max_cuts, int *cnt, unsigned long long *q, double *sum) {
+      return mvx_clique_cuts_many((const mvx_prob *)root, (const mvx_prob *const *)Ps, count, max_cuts, cnt, q, sum);
+    } : nullptr,
+    mvx_add_cut_rows_many ? +[](void *const *Ps, int count, const int *off, const double *vals, const double *rhs) {
+      return mvx_add_cut_rows_many((mvx_prob *const *)Ps, count, off, vals, rhs);
+    } : nullptr,
 };
 
 } // namespace
@@ -3532,6 +3705,7 @@ void mvx_bnb_default_params(mvx_bnb_params *p) {
   p->cut_purge = 0;
   p->polish = 0;
   p->node_purge = 0;
+  p->node_cliques = 0;
 }
 
 // Repaired mode's rule for an integer column whose bounds are not integers (legal input: LP and MPS files may carry them):
@@ -3943,7 +4117,10 @@ int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *
       params->polish < 0 || params->polish > 100000 || (params->polish > 0 && params->reference_quirks != 0) ||
       // node_purge: the repaired mode's own cut rows (the bug-compatible pool re-adds its cuts); not (yet) in the best-bound window
       params->node_purge < 0 || params->node_purge > 64 ||
-      (params->node_purge > 0 && (params->reference_quirks != 0 || params->best_window > 0))) {
+      (params->node_purge > 0 && (params->reference_quirks != 0 || params->best_window > 0)) ||
+      // node_cliques: rows on the repaired mode's children; not (yet) in the best-bound window
+      params->node_cliques < 0 || params->node_cliques > 64 ||
+      (params->node_cliques > 0 && (params->reference_quirks != 0 || params->best_window > 0))) {
     std::memset(res, 0, sizeof(*res));
     return -1;
   }
@@ -4351,6 +4528,33 @@ int mvx_bnb_clique_cuts(int n, const unsigned long long *adj, const double *x, i
     rhs[t] = -1.0;
   }
   *count = (int)got.size();
+  return 0;
+}
+
+int mvx_bnb_clique_masks(const mvx_lp_api *api, const void *prob, int n, const unsigned long long *adj, int max_cuts, int *cnt,
+                         unsigned long long *q, double *sum) {
+  if (!api) api = &g_hip_api;
+  if (!prob || !adj || !cnt || !q || !sum || max_cuts < 1 || max_cuts > 64 || n < 0) return -1;
+  if (!api->get_num_cols || !api->get_status || (!api->get_col_prim_all && !api->get_col_prim)) return -2;
+  if (api->get_num_cols(prob) != n) return -1;
+  if (api->get_status(prob) != MVX_OPT) return -3;
+  const size_t W = ((size_t)n + 1 + 63) / 64;
+  std::vector<double> x((size_t)n + 1, 0.0);
+  if (api->get_col_prim_all) api->get_col_prim_all(prob, x.data());
+  else
+    for (int j = 1; j <= n; j++) x[(size_t)j] = api->get_col_prim(prob, j);
+  const std::vector<std::vector<int>> got = clique_cuts(n, adj, x.data(), max_cuts);
+  std::fill(q, q + (size_t)max_cuts * W, 0ULL);
+  std::fill(sum, sum + max_cuts, 0.0);
+  for (size_t t = 0; t < got.size(); t++) {
+    double s = 0.0;
+    for (int j : got[t]) {
+      q[t * W + (size_t)j / 64] |= 1ULL << (j % 64);
+      s = s + x[(size_t)j];
+    }
+    sum[t] = s;
+  }
+  *cnt = (int)got.size();
   return 0;
 }
 

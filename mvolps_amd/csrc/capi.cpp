@@ -774,6 +774,10 @@ int mvx_add_cut_rows_many(mvx_prob *const *Ps, int count, const int *off, const 
 int mvx_conflict_graph(const mvx_prob *model, unsigned long long *adj, long long *edges) {
   return mvx::engine_conflict_graph(model, adj, edges);
 }
+int mvx_clique_cuts_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, int max_cuts, int *cnt, unsigned long long *q,
+                         double *sum) {
+  return mvx::engine_clique_cuts_many(root, Ps, count, max_cuts, cnt, q, sum);
+}
 int mvx_polish_many(const mvx_prob *root, int count, double *x, int max_moves, double *obj, int *moves, int *ok) {
   return mvx::engine_polish_many(root, count, x, max_moves, obj, moves, ok);
 }

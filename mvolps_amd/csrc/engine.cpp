@@ -43,6 +43,8 @@ struct RoundModel {
   void *dev = nullptr; // [At (n+1) x ldm][rlo m0][rhi m0][clo n+1][chi n+1][c n+1][flags n+1][dl n+1][ul n+1][len n+1]
   void *dev_rows = nullptr; // [Ar m0 x ldn]: the same rows by row, for k_prop; uploaded on the first propagation
   int ldn = 0;
+  void *dev_graph = nullptr; // [adj (n+1) x W][member n+1]: the conflict graph for k_cliquesep, computed on its first call
+  size_t o_member = 0;
   size_t o_rlo = 0, o_rhi = 0, o_clo = 0, o_chi = 0, o_c = 0, o_flags = 0;
   size_t o_dl = 0, o_ul = 0, o_len = 0; // per column: rows that lock it down / up, its non-zeros (k_divepick)
   std::vector<mvx::RowPtr> rows; // owned: a row's address cannot be reused while the model compares against it
@@ -51,6 +53,7 @@ struct RoundModel {
   ~RoundModel() {
     if (dev) (void)hipFree(dev);
     if (dev_rows) (void)hipFree(dev_rows);
+    if (dev_graph) (void)hipFree(dev_graph);
   }
 };
 
@@ -3549,6 +3552,88 @@ int engine_conflict_graph(const mvx_prob *R, unsigned long long *adj, long long 
   long long bits = 0;
   for (size_t w = 0; w < words; w++) bits += __builtin_popcountll(adj[w]);
   *edges = bits / 2;
+  return 0;
+}
+
+// ------------------------------------------------------------------ clique cuts in the tree (k_cliquemembers, k_cliquesep)
+// The conflict graph of root's rounding model on the device, next to the model and gone with it (round_model_current): computed
+// by k_conflict_rows / k_conflict on the first separation over this model, with the columns that have a neighbour.  The row
+// numbers k_conflict_rows leaves for k_conflict live behind the graph in the same allocation.
+static bool round_model_graph(Context &c, RoundModel *M) {
+  if (M->dev_graph) return true;
+  const int n = M->n, m0 = M->m0;
+  const size_t W = ((size_t)n + 1 + 63) / 64;
+  Carver carve;
+  carve(((size_t)n + 1) * W * 8);
+  M->o_member = carve(((size_t)n + 1) * 4);
+  const size_t o_info = carve((size_t)std::max(1, m0) * 4 * 8);
+  if (hipMalloc(&M->dev_graph, carve.off) != hipSuccess) {
+    (void)hipGetLastError();
+    M->dev_graph = nullptr;
+    g_last_error.store(MVX_ENOMEM);
+    return false;
+  }
+  const unsigned char *mb = (const unsigned char *)M->dev;
+  unsigned char *gb = (unsigned char *)M->dev_graph;
+  ConflictArgs a;
+  a.At = (const double *)mb;
+  a.Ar = (const double *)M->dev_rows;
+  a.rlo = (const double *)(mb + M->o_rlo); a.rhi = (const double *)(mb + M->o_rhi);
+  a.clo = (const double *)(mb + M->o_clo); a.chi = (const double *)(mb + M->o_chi);
+  a.flags = (const int *)(mb + M->o_flags);
+  a.rowinfo = (double *)(gb + o_info);
+  a.adj = (unsigned long long *)gb;
+  a.n = n; a.m0 = m0; a.ldm = M->ldm; a.ldn = M->ldn; a.W = (int)W; a.pad = 0;
+  launch_conflict(a, c.main.stream);
+  launch_clique_members(a.adj, (int *)(gb + M->o_member), n, (int)W, c.main.stream);
+  return true;
+}
+
+// The clique separation of `count` solved handles against root's conflict graph (mvx_clique_cuts_many): the descriptors go up,
+// one k_cliquesep launch, the counts, sets and sums come back once.  No handle is changed.  Return codes: 0; -1 bad arguments;
+// -2 device out of memory, nothing written; -3 a handle whose status is not MVX_OPT; -5 n > RND_NMAX.
+int engine_clique_cuts_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, int max_cuts, int *cnt, unsigned long long *q,
+                            double *sum) {
+  if (!root || count < 0 || max_cuts < 1 || max_cuts > CLQ_KMAX) return -1;
+  if (count == 0) return 0;
+  if (!Ps || !cnt || !q || !sum) return -1;
+  const int n = root->n;
+  for (int t = 0; t < count; t++)
+    if (!Ps[t] || Ps[t]->n != n) return -1;
+  if (n > RND_NMAX) return -5;
+  for (int t = 0; t < count; t++)
+    if (!Ps[t]->valid || Ps[t]->status != MVX_OPT) return -3;
+  NodeCall f(NodeFlush::AtEntry, NodeResults::Device);
+  const RoundModel *M = round_model(*f.c, root);
+  if (!M || !round_model_rows(*f.c, root, root->rmod.get()) || !round_model_graph(*f.c, root->rmod.get())) return -2;
+  const size_t W = ((size_t)n + 1 + 63) / 64, slots = (size_t)count * (size_t)max_cuts;
+  // up: [descriptors]; back: [cnt][sum][q]
+  const size_t o_nodes = f.up((size_t)count * sizeof(NodeRef));
+  const size_t o_cnt = f.out((size_t)count * 4), o_sum = f.out(slots * 8), o_q = f.out(slots * W * 8);
+  if (!f.reserve()) return -2;
+  NodeRef *h_nodes = (NodeRef *)(f.hb + o_nodes);
+  for (int t = 0; t < count; t++) h_nodes[t] = node_ref(Ps[t]);
+  f.upload();
+  const unsigned char *gb = (const unsigned char *)M->dev_graph;
+  CliqueArgs a;
+  a.nodes = (const NodeRef *)(f.db + o_nodes);
+  a.adj = (const unsigned long long *)gb;
+  a.member = (const int *)(gb + M->o_member);
+  a.cnt = (int *)(f.db + o_cnt);
+  a.sum = (double *)(f.db + o_sum);
+  a.q = (unsigned long long *)(f.db + o_q);
+  a.n = n; a.W = (int)W; a.max_cuts = max_cuts; a.count = count;
+  launch_cliquesep(a, f.stream());
+  f.fetch();
+  // the kernel writes the kept slots only: the others are zero here
+  std::memcpy(cnt, f.hb + o_cnt, (size_t)count * 4);
+  std::memset(q, 0, slots * W * 8);
+  std::memset(sum, 0, slots * 8);
+  for (int t = 0; t < count; t++) {
+    const size_t o = (size_t)t * (size_t)max_cuts, k = (size_t)cnt[t];
+    std::memcpy(q + o * W, f.hb + o_q + o * W * 8, k * W * 8);
+    std::memcpy(sum + o, f.hb + o_sum + o * 8, k * 8);
+  }
   return 0;
 }
 

@@ -68,6 +68,9 @@ int engine_price_cols(const mvx_prob *P, int k, const double *cols, const double
 // non-basic they leave the live tableau in one device pass (k_delcols), otherwise the tableau is given up; see engine.cpp
 int engine_del_cols(mvx_prob *P, const std::vector<int> &cols, int n_old, const double *lb, const double *ub);
 int engine_conflict_graph(const mvx_prob *R, unsigned long long *adj, long long *edges);
+// the clique separation of `count` solved handles against root's conflict graph, one launch (k_cliquesep); see engine.cpp
+int engine_clique_cuts_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, int max_cuts, int *cnt, unsigned long long *q,
+                            double *sum);
 // incumbent polishing of `count` points against root's model (k_lsact, k_lsmove, k_lsapply); see engine.cpp
 int engine_polish_many(const mvx_prob *root, int count, double *x, int max_moves, double *obj, int *moves, int *ok);
 // reduced-cost bound tightening of `count` solved handles, one launch (k_rcfix), and the bound lists of many handles applied

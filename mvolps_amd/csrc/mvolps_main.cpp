@@ -31,6 +31,9 @@ private:
 // --node-purge without a number (DESIGN.md "Cut purging in the tree (node_purge)": the smallest age limit of the CPU sweep
 // whose work is not above that of no purge on any of its sets)
 const long NODE_PURGE_DEFAULT = 1;
+// --node-cliques without a number (DESIGN.md "Clique cuts in the tree (node_cliques)": the smallest K of the CPU sweep behind
+// which a larger K no longer cuts the node counts of its instances)
+const long NODE_CLIQUES_DEFAULT = 4;
 } // namespace
 
 int main(int argc, char **argv) {
@@ -96,6 +99,8 @@ int main(int argc, char **argv) {
               << "                  two-column unit moves, at most N of them (1..100000; 1000 without a number)\n"
               << "  --node-purge [A] with --repaired, not with --best-window: a cut row leaves both children of a branching node once it\n"
               << "                  has been slack at A branching nodes in a row on its path (1..64; 1 without a number)\n"
+              << "  --node-cliques [K] with --repaired, not with --best-window: up to K violated cliques of the binary columns' conflict\n"
+              << "                  graph are separated at every branching node and appended to both children (1..64; 4 without a number)\n"
               << "Help:\n  -h/--help\n";
     return 0;
   }
@@ -257,6 +262,22 @@ int main(int argc, char **argv) {
       return -1;
     }
   }
+  if (input.CMDOptionExists("--node-cliques")) {
+    // the number is optional, as for --node-purge
+    const std::string &k = input.getCMDOption("--node-cliques");
+    const bool numeric = !k.empty() && k.size() <= 3 && std::all_of(k.begin(), k.end(), [](char ch) { return ch >= '0' && ch <= '9'; });
+    const long kv = numeric ? std::strtol(k.c_str(), nullptr, 10) : NODE_CLIQUES_DEFAULT;
+    const bool absent = k.empty() || k[0] == '-'; // the next flag, or the end of the line
+    params.node_cliques = (numeric || absent) && kv >= 1 && kv <= 64 ? (int)kv : -1;
+    if (params.node_cliques < 1) {
+      std::fprintf(stderr, "Unknown parameter value for --node-cliques\n");
+      return -1;
+    }
+    if (params.reference_quirks != 0) {
+      std::fprintf(stderr, "--node-cliques needs --repaired\n");
+      return -1;
+    }
+  }
   if (input.CMDOptionExists("--cut-select")) params.cut_select = std::atoi(input.getCMDOption("--cut-select").c_str());
   if (input.CMDOptionExists("--window")) params.window = std::atoi(input.getCMDOption("--window").c_str());
   if (input.CMDOptionExists("--best-window")) params.best_window = std::atoi(input.getCMDOption("--best-window").c_str());
@@ -287,11 +308,12 @@ int main(int argc, char **argv) {
   mvx_bnb_result res;
   const int brc = mvx_branchAndBound(nullptr, prob, &params, &res);
   if (brc == -1) {
-    std::fprintf(stderr, "-vs %d / --heur %d%s%s%s%s%s%s%s are not supported with these options (-vs 3 / 4: not with --best-window; --heur: only "
-                 "with --repaired; --rcfix / --prop / --dive / --pump / --node-purge: only with --repaired and without --best-window; --cut-rounds / --polish: only with --repaired)\n",
+    std::fprintf(stderr, "-vs %d / --heur %d%s%s%s%s%s%s%s%s are not supported with these options (-vs 3 / 4: not with --best-window; --heur: only "
+                 "with --repaired; --rcfix / --prop / --dive / --pump / --node-purge / --node-cliques: only with --repaired and without --best-window; --cut-rounds / --polish: only with --repaired)\n",
                  params.var_strat, params.heur, params.rc_fix ? " / --rcfix" : "", params.prop ? " / --prop" : "",
                  params.dive ? " / --dive" : "", params.pump ? " / --pump" : "", params.cut_rounds ? " / --cut-rounds" : "",
-                 params.polish ? " / --polish" : "", params.node_purge ? " / --node-purge" : "");
+                 params.polish ? " / --polish" : "", params.node_purge ? " / --node-purge" : "",
+                 params.node_cliques ? " / --node-cliques" : "");
     mvx_delete_prob(prob);
     return -1;
   }
@@ -335,6 +357,9 @@ int main(int argc, char **argv) {
   if (verbose && params.node_purge > 0)
     std::printf("Tree cut purging: %lld children purged, %lld rows removed, at most %lld live cut rows on a node\n", res.node_purge_calls,
                 res.node_purge_rows, res.node_cut_rows_peak);
+  if (verbose && params.node_cliques > 0)
+    std::printf("Node cliques: %lld conflicts, %lld nodes separated, %lld rows\n", res.node_clique_conflicts, res.node_clique_calls,
+                res.node_clique_rows);
   const int limit = res.hit_limit || brc != 0;
   mvx_bnb_free_result(&res);
   mvx_delete_prob(prob);

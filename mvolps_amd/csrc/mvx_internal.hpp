@@ -529,6 +529,20 @@ struct ConflictArgs {
   int n, m0, ldm, ldn, W, pad;
 };
 
+// arguments of k_cliquemembers / k_cliquesep (mvx_clique_cuts_many): the conflict graph of the root, kept on the device with its
+// rounding model, the columns that have a neighbour, and `count` solved handles whose column values are separated against it
+#define CLQ_WAVES 4 // waves of a k_cliquesep workgroup: one seed each, the next CLQ_WAVES seeds of the order together
+#define CLQ_KMAX 64 // most cliques kept per handle
+struct CliqueArgs {
+  const NodeRef *nodes;          // [count]
+  const unsigned long long *adj; // [n+1][W]
+  const int *member;             // [n+1] 1: the column's adjacency row is not empty
+  int *cnt;                      // [count] cliques kept
+  unsigned long long *q;         // [count][max_cuts][W] their member sets; slots from cnt on are not written
+  double *sum;                   // [count][max_cuts] their s
+  int n, W, max_cuts, count;
+};
+
 // arguments of k_lsact / k_lsmove / k_lsapply (mvx_polish_many): the root's model in both orientations, as k_conflict reads it,
 // with the objective, and per point its values, row activities, the records of one iteration and its counters
 #define LS_GROUP 8 // iterations the host enqueues between two looks at the done flags
@@ -618,6 +632,8 @@ void launch_delrows(const DelRowsArgs &a, hipStream_t);
 void launch_delrows_many(const DelRowsArgs *hs, int handles, int max_ld, hipStream_t); // hs: device memory
 
 void launch_conflict(const ConflictArgs &a, hipStream_t);
+void launch_clique_members(const unsigned long long *adj, int *member, int n, int W, hipStream_t);
+void launch_cliquesep(const CliqueArgs &a, hipStream_t);
 void launch_lsact(const LsArgs &a, int final, hipStream_t);
 void launch_lsiter(const LsArgs &a, hipStream_t);
 void launch_setbnds(const SetbHandle *hs, const SetbEntry *es, const SetbShift *ss, int handles, hipStream_t);

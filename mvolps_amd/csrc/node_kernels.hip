@@ -1,6 +1,6 @@
 // node_kernels.hip -- gfx950 kernels of the batched node entries of branch and bound (engine.cpp: engine_*_many): GMI cuts,
 // classification, branching penalties, sensitivity ranges, the rounding heuristic, reduced-cost tightening, bound propagation, bound lists, the
-// diving pick, objective replacement, the feasibility pump's step, the scores and the batched append of a cut round, and the append, pricing and deletion of columns.  Each takes its arguments by value and the handles it works on as an array of descriptors (NodeRef and what
+// diving pick, objective replacement, the feasibility pump's step, the scores and the batched append of a cut round, the clique separation of a window, and the append, pricing and deletion of columns.  Each takes its arguments by value and the handles it works on as an array of descriptors (NodeRef and what
 // the kernel needs beyond it, mvx_internal.hpp).  Same flags as kernels.hip: -ffp-contract=off, so every kernel has the bits
 // of its host twin.
 #include <hip/hip_runtime.h>
@@ -1894,6 +1894,163 @@ __global__ __launch_bounds__(64 * CONF_WAVES) void k_conflict(ConflictArgs a) {
 void launch_conflict(const ConflictArgs &a, hipStream_t s) {
   if (a.m0 > 0) hipLaunchKernelGGL(k_conflict_rows, dim3((unsigned)((a.m0 + 255) / 256)), dim3(256), 0, s, a);
   hipLaunchKernelGGL(k_conflict, dim3((unsigned)(a.n + 1), (unsigned)((a.W + CONF_WAVES - 1) / CONF_WAVES)), dim3(64 * CONF_WAVES), 0, s, a);
+}
+
+// ---------------------------------------------------------------------------- k_cliquemembers / k_cliquesep
+// Clique separation in the tree (mvx_clique_cuts_many, DESIGN.md "Clique cuts in the tree (node_cliques)"): the separation of
+// mvx_bnb_clique_cuts for a window of solved handles against the root's conflict graph, which stays on the device.
+// k_cliquemembers, once per graph: the columns whose adjacency row is not empty, a thread per column.
+__global__ __launch_bounds__(256) void k_cliquemembers(const unsigned long long *adj, int *member, int n, int W) {
+  const int j = (int)blockIdx.x * 256 + TIDX;
+  if (j > n) return;
+  unsigned long long any = 0ull;
+  for (int w = 0; w < W; w++) any |= adj[(size_t)j * (size_t)W + (size_t)w];
+  member[j] = (j >= 1 && any != 0ull) ? 1 : 0;
+}
+
+// k_cliquesep, one workgroup per handle.
+//  1. the node LP's column values (node_col_values: get_col_prim's bits) into LDS;
+//  2. the member columns sorted by value descending, column ascending (k_round's bitonic sort in LDS; the others sink behind
+//     them with a key of -inf); the seeds are the prefix of that order with x > 1e-6;
+//  3. a wave owns one seed: lane l holds words l and 64 + l of the mask (W <= 128) and of the set Q.  It walks the whole order;
+//     the column's mask bit comes from its owner by a lane broadcast, and on a hit mask &= adj[column] is one coalesced load.
+//     Once the mask is empty nothing can join any more and the walk ends: the same set as the full walk;
+//  4. the CLQ_WAVES waves take the next seeds of the order together and leave their sets in LDS; wave 0 then takes them in seed
+//     order: s over ascending columns from +0.0, the test s - 1 > 1e-6, the comparison with the sets already kept, the cap.
+// What is kept depends on the seed order only, not on which wave grew which seed.  No atomics, no LDS reduction of doubles,
+// nothing shared between workgroups; every loop is bounded by n, W or max_cuts.
+static_assert(64 * CLQ_WAVES == 256, "node_col_values walks with 256 threads");
+__global__ __launch_bounds__(64 * CLQ_WAVES) void k_cliquesep(CliqueArgs a) {
+  __shared__ double s_x[RND_NMAX + 1];
+  __shared__ double s_key[RND_NMAX];
+  __shared__ int s_idx[RND_NMAX];
+  __shared__ unsigned long long s_q[CLQ_WAVES][128];
+  __shared__ int s_part[2][CLQ_WAVES];
+  __shared__ int s_kept;
+  const int t = (int)blockIdx.x;
+  const NodeRef nd = a.nodes[t];
+  const int n = a.n, W = a.W, max_cuts = a.max_cuts;
+  const int lane = TIDX & 63, wv = __builtin_amdgcn_readfirstlane(TIDX >> 6);
+  const double inf = __builtin_huge_val();
+  if (TIDX == 0) s_kept = 0;
+  node_col_values(nd, n, [&](int j, double v) { s_x[j] = v; });
+  __syncthreads();
+  int np = 1;
+  while (np < n) np <<= 1;
+  int mem = 0, pos = 0;
+  for (int j = 1 + TIDX; j <= n; j += 256) {
+    const bool in = a.member[j] != 0;
+    const double v = s_x[j];
+    s_key[j - 1] = in ? v : -inf;
+    s_idx[j - 1] = j;
+    mem += in ? 1 : 0;
+    pos += (in && v > 1e-6) ? 1 : 0;
+  }
+  for (int p = n + TIDX; p < np; p += 256) {
+    s_key[p] = -inf;
+    s_idx[p] = 0x7fffffff;
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    mem += __shfl_xor(mem, off, 64);
+    pos += __shfl_xor(pos, off, 64);
+  }
+  if (lane == 0) {
+    s_part[0][wv] = mem;
+    s_part[1][wv] = pos;
+  }
+  __syncthreads();
+  for (int k2 = 2; k2 <= np; k2 <<= 1)
+    for (int jj = k2 >> 1; jj > 0; jj >>= 1) {
+      for (int i = TIDX; i < np; i += 256) {
+        const int l = i ^ jj;
+        if (l <= i) continue;
+        const double ki = s_key[i], kl = s_key[l];
+        const int ii = s_idx[i], il = s_idx[l];
+        const bool sw = ((i & k2) == 0) ? rnd_before(kl, il, ki, ii) : rnd_before(ki, ii, kl, il);
+        if (sw) {
+          s_key[i] = kl; s_key[l] = ki;
+          s_idx[i] = il; s_idx[l] = ii;
+        }
+      }
+      __syncthreads();
+    }
+  int no = 0, ns = 0; // members (the order's length) and seeds (its prefix)
+  for (int w = 0; w < CLQ_WAVES; w++) {
+    no += s_part[0][w];
+    ns += s_part[1][w];
+  }
+  unsigned long long *qo = a.q + (size_t)t * (size_t)max_cuts * (size_t)W;
+  double *so = a.sum + (size_t)t * (size_t)max_cuts;
+  const bool has0 = lane < W, has1 = 64 + lane < W;
+  for (int b0 = 0; b0 < ns; b0 += CLQ_WAVES) {
+    const int k = b0 + wv;
+    if (k < ns) {
+      const int seed = s_idx[k];
+      const unsigned long long *rs = a.adj + (size_t)seed * (size_t)W;
+      unsigned long long m0 = has0 ? rs[lane] : 0ull, m1 = has1 ? rs[64 + lane] : 0ull;
+      unsigned long long q0 = 0ull, q1 = 0ull;
+      if (lane == ((seed >> 6) & 63)) {
+        if ((seed >> 6) < 64) q0 |= 1ull << (seed & 63);
+        else q1 |= 1ull << (seed & 63);
+      }
+      for (int p = 0; p < no; p++) {
+        const int c = s_idx[p];
+        const int wd = c >> 6;
+        const unsigned long long word = __shfl(wd < 64 ? m0 : m1, wd & 63, 64);
+        if (!((word >> (c & 63)) & 1ull)) continue;
+        const unsigned long long *rc = a.adj + (size_t)c * (size_t)W;
+        m0 &= has0 ? rc[lane] : 0ull;
+        m1 &= has1 ? rc[64 + lane] : 0ull;
+        if (lane == (wd & 63)) {
+          if (wd < 64) q0 |= 1ull << (c & 63);
+          else q1 |= 1ull << (c & 63);
+        }
+        if (__ballot((m0 | m1) != 0ull) == 0ull) break;
+      }
+      s_q[wv][lane] = q0;
+      s_q[wv][64 + lane] = q1;
+    }
+    __syncthreads();
+    if (wv == 0) {
+      int kept = s_kept;
+      for (int u = 0; u < CLQ_WAVES && b0 + u < ns && kept < max_cuts; u++) {
+        double s = 0.0;
+        for (int w = 0; w < W; w++) {
+          unsigned long long mk = s_q[u][w];
+          while (mk) {
+            const int b = __builtin_ctzll(mk);
+            mk &= mk - 1ull;
+            s = __dadd_rn(s, s_x[64 * w + b]);
+          }
+        }
+        if (!(__dsub_rn(s, 1.0) > 1e-6)) continue;
+        const unsigned long long q0 = s_q[u][lane], q1 = s_q[u][64 + lane];
+        bool dup = false;
+        for (int e = 0; e < kept && !dup; e++) {
+          const unsigned long long *qe = qo + (size_t)e * (size_t)W;
+          const bool same = (!has0 || qe[lane] == q0) && (!has1 || qe[64 + lane] == q1);
+          dup = __ballot(!same) == 0ull;
+        }
+        if (dup) continue;
+        unsigned long long *qk = qo + (size_t)kept * (size_t)W;
+        if (has0) qk[lane] = q0;
+        if (has1) qk[64 + lane] = q1;
+        if (lane == 0) so[kept] = s;
+        kept++;
+      }
+      if (lane == 0) s_kept = kept;
+    }
+    __syncthreads();
+    if (s_kept >= max_cuts) break;
+  }
+  if (TIDX == 0) a.cnt[t] = s_kept;
+}
+
+void launch_clique_members(const unsigned long long *adj, int *member, int n, int W, hipStream_t s) {
+  hipLaunchKernelGGL(k_cliquemembers, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, s, adj, member, n, W);
+}
+void launch_cliquesep(const CliqueArgs &a, hipStream_t s) {
+  hipLaunchKernelGGL(k_cliquesep, dim3((unsigned)a.count), dim3(64 * CLQ_WAVES), 0, s, a);
 }
 
 // ---------------------------------------------------------------------------- k_lsact / k_lsmove / k_lsapply
