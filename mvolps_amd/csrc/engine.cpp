@@ -28,7 +28,7 @@ struct DevMatrix {
   int m0 = 0, n = 0, lda = 0;
   double *plain = nullptr, *packed = nullptr;
   int *len = nullptr; // nullptr: every row has n non-zeros
-  std::vector<const void *> rows; // identity of the host rows this was built from
+  std::vector<mvx::RowPtr> rows; // the host rows this was built from, owned: a row's address cannot be reused while compared against
   ~DevMatrix() {
     if (packed && packed != plain) (void)hipFree(packed);
     if (plain) (void)hipFree(plain);
@@ -2808,7 +2808,7 @@ static std::shared_ptr<DevMatrix> build_dev_matrix(Context &c, const mvx_prob *P
   bool dense = true;
   for (int i = 1; i <= m0; i++) {
     const double *a = P->A[(size_t)i]->data();
-    D->rows.push_back(P->A[(size_t)i].get());
+    D->rows.push_back(P->A[(size_t)i]);
     std::memcpy(&plain[(size_t)i * lda + 1], a + 1, (size_t)n * 8);
     int l = 0;
     for (int j = 1; j <= n; j++) l += (a[j] != 0.0);
@@ -2850,7 +2850,7 @@ static bool dev_matrix_current(const mvx_prob *P) {
   const DevMatrix *D = P->dmat.get();
   if (!D || D->n != P->n || D->m0 > P->m) return false;
   for (int i = 1; i <= D->m0; i++)
-    if (D->rows[(size_t)i - 1] != P->A[(size_t)i].get()) return false;
+    if (D->rows[(size_t)i - 1] != P->A[(size_t)i]) return false;
   return true;
 }
 
