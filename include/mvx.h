@@ -387,7 +387,11 @@ double mvx_last_solve_ms(const mvx_prob *P);
    its own copy `base` of the root model.  The `_from` forms also carry the model rows appended since
    `base` (rows base.m+1 .. m: GMI cut rows, cut.cpp:23-43), so that a node with cuts can migrate; the plain
    forms carry none and need a receiver `base` with the same number of rows.  The image also carries the
-   tolerances of the solve that produced the status, so a migrated optimal node is not solved again. */
+   tolerances of the solve that produced the status, so a migrated optimal node is not solved again.
+   Refusals, all -1: the `_from` forms for a `base` with more rows than P or another number of columns (a
+   handle whose columns were edited travels as its own base, mvx_pack); mvx_unpack for dst == base, a buffer
+   that holds no image, and an image of another base.m or n than `base` has -- dst is then a model-only copy
+   of `base`. */
 long long mvx_pack_size(const mvx_prob *P);
 int mvx_pack(const mvx_prob *P, void *dev_buf);
 long long mvx_pack_size_from(const mvx_prob *P, const mvx_prob *base);

@@ -786,8 +786,16 @@ int mvx_device_count(void) { return mvx::device_count(); }
 int mvx_set_device(int dev) { return mvx::set_device(dev); }
 long long mvx_pack_size(const mvx_prob *P) { return mvx::engine_pack_size(P, P->m); }
 int mvx_pack(const mvx_prob *P, void *dev_buf) { return mvx::engine_pack(P, P->m, dev_buf); }
-long long mvx_pack_size_from(const mvx_prob *P, const mvx_prob *base) { return mvx::engine_pack_size(P, base ? base->m : P->m); }
-int mvx_pack_from(const mvx_prob *P, const mvx_prob *base, void *dev_buf) { return mvx::engine_pack(P, base ? base->m : P->m, dev_buf); }
+// An image against a base of another column count could only be refused by the receiver, after the transfer: refuse it here,
+// where the coordinator still agrees on pack failures before it posts transfers.
+long long mvx_pack_size_from(const mvx_prob *P, const mvx_prob *base) {
+  if (base && base->n != P->n) return -1;
+  return mvx::engine_pack_size(P, base ? base->m : P->m);
+}
+int mvx_pack_from(const mvx_prob *P, const mvx_prob *base, void *dev_buf) {
+  if (base && base->n != P->n) return -1;
+  return mvx::engine_pack(P, base ? base->m : P->m, dev_buf);
+}
 int mvx_unpack(mvx_prob *dst, const mvx_prob *base, const void *dev_buf) {
   if (dst == base) return -1;
   // model rows / objective / kinds come from the receiver's own copy of the root problem
@@ -797,6 +805,11 @@ int mvx_unpack(mvx_prob *dst, const mvx_prob *base, const void *dev_buf) {
   dst->rtype = base->rtype; dst->rlb = base->rlb; dst->rub = base->rub;
   dst->ctype = base->ctype; dst->clb = base->clb; dst->cub = base->cub;
   dst->valid = false; dst->sol_fresh = false; dst->fresh_rows = -1;
+  // nothing of dst's earlier life stays: a refused image leaves a model-only copy of the base, as mvx_copy_prob of an unsolved
+  // base would, not the status, counters and pending edits of whatever dst held before
+  dst->status = MVX_UNDEF; dst->it_cnt = 0; dst->bland_cnt = 0; dst->pert_cnt = 0; dst->piv_since_check = 0;
+  dst->hint_dual = false; dst->pending.clear();
+  dst->last_tol[0] = dst->last_tol[1] = dst->last_tol[2] = 0.0;
   return mvx::engine_unpack(dst, dev_buf);
 }
 void mvx_set_tuning(int tr, int hot, int nt) { mvx::tuning(tr, hot, nt); }

@@ -3888,7 +3888,8 @@ int engine_pack(const mvx_prob *P, int m_base, void *dev_buf) {
   std::vector<unsigned char> host(hb, 0);
   unsigned char *b = host.data();
   PackHdr h{};
-  h.magic = PACK_MAGIC; h.m = m; h.n = n; h.ld = P->ld; h.m_cap = P->m_cap; h.status = P->status;
+  // a handle without a tableau has no slab: whatever geometry its fields still hold is not part of its image
+  h.magic = PACK_MAGIC; h.m = m; h.n = n; h.ld = P->valid ? P->ld : 0; h.m_cap = P->valid ? P->m_cap : 0; h.status = P->status;
   h.it_cnt = P->it_cnt; h.valid = P->valid; h.hint_dual = P->hint_dual; h.host_bytes = (long long)hb; h.m_base = m_base; h.reserved = P->piv_since_check;
   std::memcpy(h.last_tol, P->last_tol, sizeof(h.last_tol));
   std::memcpy(b, &h, sizeof(h));

@@ -82,6 +82,7 @@ def api():
             "set_refresh": (None, [C.c_int, C.c_double]),
             "get_refresh_cnt": (C.c_int, [C.c_void_p]),
             "row_residual": (C.c_double, [C.c_void_p]),
+            "simplex_batch": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
             "pack_size": (C.c_longlong, [C.c_void_p]),
             "pack": (C.c_int, [C.c_void_p, C.c_void_p]),
             "pack_size_from": (C.c_longlong, [C.c_void_p, C.c_void_p]),

@@ -75,7 +75,17 @@ def _worker(rank, world, port, outdir, case, kw, use_gpu):
         else:
             eng = OracleNodeEngine()
         root = lpgen.load_case(eng.api, tuple(case))
+        grown = [0]  # images this rank received that carried appended rows (m > m_base)
+        unpack = eng.unpack
+
+        def counting_unpack(base, t):
+            q = unpack(base, t)
+            grown[0] += int(q.m > base.m)
+            return q
+
+        eng.unpack = counting_unpack
         res = dist_bnb.branch_and_bound(eng, root, **kw)
+        res["grown_images"] = grown[0]
         with open(os.path.join(outdir, "rank%d.json" % rank), "w") as f:
             json.dump(res, f)
     finally:
@@ -132,6 +142,27 @@ def oracle_tables():
     return api, bnb.table_from(api), dist_native.image_api_from(api, libc.malloc, libc.free)
 
 
+def _grown_counting_comm(dist_native):
+    """TorchComm over device buffers that counts the engine images this rank receives with appended rows: the first words of an
+    image are its header (engine.cpp PackHdr: 64-bit magic, m, n, ld, m_cap, status, it_cnt, valid, hint_dual, host_bytes, m_base)."""
+
+    class Counting(dist_native.TorchComm):
+        grown = 0
+
+        def _exchange(self, ctx, sends, ns, recvs, nr):
+            rc = super()._exchange(ctx, sends, ns, recvs, nr)
+            try:
+                for k in range(nr if rc == 0 else 0):
+                    hdr = self._view(recvs[k])[:88].cpu().numpy().view(np.int64)
+                    self.grown += int(hdr[1] > hdr[10])
+            except Exception as e:  # an exception must not cross the C frame
+                self.error = e
+                return 1
+            return rc
+
+    return Counting(device_buffers=True)
+
+
 def _native_worker(rank, world, port, outdir, case, kw, use_gpu):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
@@ -150,12 +181,13 @@ def _native_worker(rank, world, port, outdir, case, kw, use_gpu):
             api, table, image = mvolps_amd.api(), None, None  # the engine's own tables; both ranks share cuda:0
             api.set_device(0)
             torch.cuda.set_device(0)
-            comm = dist_native.TorchComm(device_buffers=True)  # gloo moves host copies of the device images
+            comm = _grown_counting_comm(dist_native)  # gloo moves host copies of the device images
         else:
             api, table, image = oracle_tables()
             comm = dist_native.TorchComm()
         root = lpgen.load_case(api, tuple(case))
         res = dist_native.branch_and_bound(root, comm=comm, table=table, image=image, **kw)
+        res["grown_images"] = getattr(comm, "grown", None)
         with open(os.path.join(outdir, "rank%d.json" % rank), "w") as f:
             json.dump(res, f)
     finally:

@@ -99,3 +99,18 @@ def test_two_ranks_one_gpu_match_serial(gpu, tmp_path):
         for k in KEYS:
             assert r[k] == serial[k], k
     assert res[0]["dist"]["migrated"] > 0
+
+
+@pytest.mark.parametrize("kw", [dict(quirks=0, cut_strat=1), dict(quirks=1, cut_strat=1, max_nodes=300)], ids=["repaired", "bugcompat"])
+def test_two_ranks_one_gpu_with_gmi_cuts_match_serial(gpu, tmp_path, kw):
+    """The device counterpart of test_dist_bnb.py::test_world2_with_gmi_cuts_matches_serial through the C++ entry: cut rows ride
+    in the engine's migration images (m > m_base), so a node with cuts changes ranks and goes on as the serial driver's does."""
+    case = (10, 20, 4, 3)
+    A, b, c, U = synth.dense_ilp(*case)
+    serial = canon(bnb.branch_and_bound(lpgen.load_ilp(gpu, A, b, c, U), **kw))
+    res = dist_helpers.run_world_native(2, case, dict(per_rank=2, **kw), str(tmp_path), use_gpu=True)
+    for r in res:
+        for k in KEYS:
+            assert r[k] == serial[k], k
+    assert serial["count"] > 20 and res[0]["dist"]["migrated"] > 0
+    assert sum(r["grown_images"] for r in res) > 0  # at least one migrated image carried appended rows
