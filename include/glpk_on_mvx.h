@@ -83,6 +83,12 @@ typedef mvx_smcp glp_smcp;
 #define glp_get_mat_col mvx_get_mat_col   /* (model readers by columns) */
 #define glp_get_obj_dir mvx_get_obj_dir   /* util.cpp:51 */
 #define glp_eval_tab_row mvx_eval_tab_row /* gmi.cpp:36 */
+#define glp_check_kkt mvx_check_kkt       /* (solution checking; MVOLPS never calls it) sol = GLP_SOL, cond = GLP_KKT_* */
+#define GLP_SOL 1
+#define GLP_KKT_PE MVX_KKT_PE
+#define GLP_KKT_PB MVX_KKT_PB
+#define GLP_KKT_DE MVX_KKT_DE
+#define GLP_KKT_DB MVX_KKT_DB
 /* I/O + environment */
 #define glp_read_lp mvx_read_lp           /* util.cpp:284 */
 #define glp_read_mps mvx_read_mps         /* util.cpp:290 */

@@ -202,6 +202,27 @@ int mvx_branch_penalties_many(const mvx_prob *const *Ps, int count, const int *c
 int mvx_ranges(const mvx_prob *P, double *val, int *var);
 /* the tableau rows one workgroup of the column-wise ratio test (k_rangecols) walks: up to this many rows are one chunk */
 int mvx_ranges_chunk(void);
+/* KKT check (DESIGN.md "KKT check (kkt)") of `count` solved handles against their own models, in one device call: does what
+   the getters publish -- get_col_prim, get_row_prim, get_row_dual, get_col_dual, the statuses and the bounds, read where they
+   lie in each handle's tableau slab -- still satisfy xR - A xS = 0 (PE), the variables' bounds (PB), c - A'lambda - d = 0 (DE)
+   and the signs of the duals (DB)?  val[8 t ..] holds ae_max, re_max of PE, PB, DE, DB in that order for handle t, ind[8 t ..]
+   the row (PE), column (DE) or variable k = 1..m+n, auxiliaries first (PB, DB) where each maximum occurs: the lowest among
+   equals, 0 when the maximum is 0.  Every handle has root's n columns and root's m0 rows as its first rows, the same objects
+   (clones of root, as for mvx_gmi_cuts_many); rows behind them are cut rows.  Pure: no handle is changed.  Bit-identical to
+   mvx_bnb_kkt (mvx_bnb.h).  Returns 0 (count == 0 does nothing); -1 bad arguments (a null, count < 0, differing column
+   counts); -2 device out of memory, nothing written; -3 a handle that is MVX_UNDEF or has no tableau (or that
+   carries bound edits no solve has taken up yet: such a handle is MVX_UNDEF in any case), or one that does not share root's
+   rows. */
+int mvx_kkt_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, double *val, int *ind);
+/* The same for one handle against itself; r_pe[0..m] and r_de[0..n] (either may be NULL) receive the residuals
+   r_i = xR_i - sum_j a_ij xS_j and r_j = (c_j - sum_i a_ij lambda_i) - d_j, entry 0 of each 0. */
+int mvx_kkt(const mvx_prob *P, double *val, int *ind, double *r_pe, double *r_de);
+/* glp_check_kkt's shape [GLPK-recalled]: sol must be 1 (the basic solution), cond 1 PE, 2 PB, 3 DE, 4 DB; -1 otherwise. */
+#define MVX_KKT_PE 1
+#define MVX_KKT_PB 2
+#define MVX_KKT_DE 3
+#define MVX_KKT_DB 4
+int mvx_check_kkt(const mvx_prob *P, int sol, int cond, double *ae_max, int *ae_ind, double *re_max, int *re_ind);
 /* Primal rounding heuristic (DESIGN.md "Primal rounding heuristic") on `count` solved handles, one device launch: each
    handle's column values rounded (mode 1) and filled greedily (mode 2), checked against the model of `root` -- its rows
    1..m0 (m0 = root's row count; rows a handle has beyond them, cut rows, are ignored), row bounds, column bounds and

@@ -142,6 +142,9 @@ typedef struct mvx_lp_api {
      by handle, and without that through add_rows / set_mat_row / set_row_bnds row by row.  -2 (device memory) means the rows are
      in every model: nothing is appended again */
   int (*add_cut_rows_many)(void *const *Ps, int count, const int *off, const double *vals, const double *rhs);
+  /* optional (may be NULL): the KKT check of `count` solved handles against the rows of `root` in one call (mvx_kkt_many; DESIGN.md
+     "KKT check (kkt)"): val / ind take 8 entries per handle; without it the host twin mvx_bnb_kkt runs handle by handle */
+  int (*kkt_many)(const void *root, const void *const *Ps, int count, double *val, int *ind);
 } mvx_lp_api;
 
 const mvx_lp_api *mvx_hip_lp_api(void);
@@ -233,6 +236,11 @@ typedef struct {
                            purge and in front of the rc_fix lists, the propagation and the first solve.  Outside 0..64: refused;
                            K > 0 needs reference_quirks = 0 and best_window = 0.  Independent of cut_strat and of the root cut
                            rounds */
+  int kkt;              /* KKT check (DESIGN.md "KKT check (kkt)"): 0 (default) off; 1: every node LP the tree solves -- whatever its end
+                           status -- is checked against the model as solved, a window's nodes in one kkt_many call; the tree's worst
+                           relative errors go to kkt_re / kkt_oid.  Pure observation: the tree, oids, events, pivots, incumbent
+                           and every other counter are those of kkt = 0, and the booked values do not depend on the window.  Outside 0..1: refused; 1 needs best_window = 0; allowed
+                           in both quirk modes */
 } mvx_bnb_params;
 
 /* B&B events at the emit points of bs.cpp (message.h EventType) */
@@ -313,6 +321,9 @@ typedef struct {
   long long node_clique_conflicts; /* node_cliques > 0: edges of the conflict graph of the model */
   long long node_clique_calls;     /* ... branching nodes whose LP was separated */
   long long node_clique_rows;      /* ... cliques kept for them, summed: each is one row in both children */
+  long long kkt_nodes;             /* kkt = 1: node LPs checked (every node the tree solved) */
+  double kkt_re[4];                /* ... the worst re_max over them per condition: PE, PB, DE, DB */
+  int kkt_oid[4];                  /* ... the lowest oid at which each worst value occurred, 0 while it is 0 */
 } mvx_bnb_result;
 
 void mvx_bnb_default_params(mvx_bnb_params *p);
@@ -369,6 +380,22 @@ int mvx_bnb_penalties(const mvx_lp_api *api, const void *prob, const int *cols, 
    tolerance.  The same bits as mvx_ranges.  Returns 0; -1 a null argument; -2 the table lacks an accessor it needs (or
    get_tableau / get_basis failed); -3 the handle is not MVX_OPT */
 int mvx_bnb_ranges(const mvx_lp_api *api, const void *prob, double *val, int *var);
+
+/* KKT check (DESIGN.md "KKT check (kkt)") from numbers only: m rows and n columns, rows m x (n+1) dense by row (entry 0 of each
+   unused), c[0..n], the four value vectors xs[0..n] (get_col_prim), xr[0..m] (get_row_prim), lam[0..m] (get_row_dual), dj[0..n]
+   (get_col_dual), lb / ub / stat [0..m+n] by variable number, auxiliaries first (+-inf for an absent bound; MVX_BS .. MVX_NS),
+   dir MVX_MIN / MVX_MAX.  val[8] = ae_max, re_max of PE, PB, DE, DB, ind[8] where they occur (lowest among equals, 0 for a zero
+   maximum); r_pe[0..m] / r_de[0..n] (nullable) the residuals, entry 0 zero.  Sums run in 64 chains with fma, combined by the
+   halving tree.  Returns 0; -1 bad arguments (m < 1, n < 1, a null, another dir) */
+int mvx_bnb_kkt_values(int m, int n, const double *rows, const double *c, const double *xs, const double *xr, const double *lam,
+                       const double *dj, const double *lb, const double *ub, const int *stat, int dir, double *val, int *ind, double *r_pe,
+                       double *r_de);
+/* Host twin of mvx_kkt for one solved handle, through the table only (get_mat_row, row and column bounds, get_obj_coef,
+   get_obj_dir, get_tableau, get_basis, get_status, get_num_rows, get_num_cols): the four vectors are derived by the getters' own
+   rule; the handle is not changed.  The same bits as mvx_kkt.  Returns 0; -1 a null argument; -2 the table lacks an accessor it
+   needs (or one failed); -3 the handle is MVX_UNDEF.  mvx_branchAndBound returns -1 (*res empty) for kkt outside 0..1 and kkt = 1
+   with best_window > 0, and -2, with the tree so far, when a check could not be carried out */
+int mvx_bnb_kkt(const mvx_lp_api *api, const void *prob, double *val, int *ind, double *r_pe, double *r_de);
 
 /* Column append (DESIGN.md "Column append (add_cols)"), host twin of mvx_price_cols: the images of `k` candidate columns against
    the tableau of `prob` -- cols k x (m+1) by model row, obj[k]; dj[t] row 0 of image t, img (nullable) k x (m+1) by tableau row.

@@ -25,23 +25,33 @@ _OPTIONAL = ["simplex_batch", "get_obj_dir", "gmi_cuts", "gmi_cuts_many", "get_c
 # for the table, attributes for the parameters and counters.  Views on memory the library owns (from_address, pointers) are
 # whole structs already.
 _TABLE_TAIL = ["clique_cuts_many", "add_cut_rows_many"]
+# ... and behind that tail: a further list per class (_more_), reached by name in the same way, so that `_tail_` keeps the
+# members it had; `_full_` covers the fields, the tail and this list -- the whole C struct
+_TABLE_MORE = ["kkt_many"]
 
 
-def _with_tail(cls, tail):
-    """Gives cls the layout of the whole C struct (its own fields, then `tail`) for allocation and for access by name."""
-    cls._full_ = type(cls.__name__ + "Whole", (C.Structure,), {"_fields_": list(cls._fields_) + list(tail)})
+def _with_tail(cls, tail, more=()):
+    """Gives cls the layout of the whole C struct (its own fields, then `tail`, then `more`) for allocation and for access by name."""
+    cls._full_ = type(cls.__name__ + "Whole", (C.Structure,), {"_fields_": list(cls._fields_) + list(tail) + list(more)})
     cls._tail_ = {name: (getattr(cls._full_, name).offset, ctype) for name, ctype in tail}
+    cls._more_ = {name: (getattr(cls._full_, name).offset, ctype) for name, ctype in more}
     for name, ctype in cls._fields_:  # the listed fields sit where the C struct has them
         assert getattr(cls, name).offset == getattr(cls._full_, name).offset
 
 
+def _behind(obj, name):
+    cls = type(obj)
+    return cls._tail_[name] if name in cls._tail_ else cls._more_[name]
+
+
 def tail_get(obj, name):
-    off, ctype = type(obj)._tail_[name]
-    return ctype.from_address(C.addressof(obj) + off).value
+    off, ctype = _behind(obj, name)
+    at = ctype.from_address(C.addressof(obj) + off)
+    return list(at) if isinstance(at, C.Array) else at.value
 
 
 def tail_set(obj, name, value):
-    off, ctype = type(obj)._tail_[name]
+    off, ctype = _behind(obj, name)
     ctype.from_address(C.addressof(obj) + off).value = value
 
 
@@ -60,16 +70,16 @@ class LpApiTable(_WholeStruct):
     _fields_ = [(name, C.c_void_p) for name in _FIELDS + _OPTIONAL]
 
 
-_with_tail(LpApiTable, [(name, C.c_void_p) for name in _TABLE_TAIL])
+_with_tail(LpApiTable, [(name, C.c_void_p) for name in _TABLE_TAIL], [(name, C.c_void_p) for name in _TABLE_MORE])
 
 
 def table_entry(table, name):
     """An entry of the table by name, appended ones (_TABLE_TAIL) included: its address, or None."""
-    return tail_get(table, name) if name in _TABLE_TAIL else getattr(table, name)
+    return tail_get(table, name) if name in _TABLE_TAIL + _TABLE_MORE else getattr(table, name)
 
 
 def set_table_entry(table, name, value):
-    if name in _TABLE_TAIL:
+    if name in _TABLE_TAIL + _TABLE_MORE:
         tail_set(table, name, value)
     else:
         setattr(table, name, value)
@@ -108,9 +118,10 @@ class BnbParams(_WholeStruct):
         ("node_purge", C.c_int),
     ]
     node_cliques = _tail_attr("node_cliques")
+    kkt = _tail_attr("kkt")
 
 
-_with_tail(BnbParams, [("node_cliques", C.c_int)])
+_with_tail(BnbParams, [("node_cliques", C.c_int)], [("kkt", C.c_int)])
 
 
 class BnbEvent(C.Structure):
@@ -189,10 +200,17 @@ class BnbResult(_WholeStruct):
     node_clique_conflicts = _tail_attr("node_clique_conflicts")
     node_clique_calls = _tail_attr("node_clique_calls")
     node_clique_rows = _tail_attr("node_clique_rows")
+    kkt_nodes = _tail_attr("kkt_nodes")
+    kkt_re = _tail_attr("kkt_re")
+    kkt_oid = _tail_attr("kkt_oid")
 
 
 NODE_CLIQUE_COUNTERS = ("node_clique_conflicts", "node_clique_calls", "node_clique_rows")
-_with_tail(BnbResult, [(name, C.c_longlong) for name in NODE_CLIQUE_COUNTERS])
+# kkt = 1: node LPs checked; the worst re_max per condition (KKT_CONDS) over the tree, a list of 4; the lowest oid of each
+KKT_COUNTERS = ("kkt_nodes", "kkt_re", "kkt_oid")
+KKT_CONDS = ("PE", "PB", "DE", "DB")
+_with_tail(BnbResult, [(name, C.c_longlong) for name in NODE_CLIQUE_COUNTERS],
+           [("kkt_nodes", C.c_longlong), ("kkt_re", C.c_double * 4), ("kkt_oid", C.c_int * 4)])
 
 
 def table_from(api):
@@ -201,7 +219,7 @@ def table_from(api):
     for name in _FIELDS:
         fn = getattr(api.lib, api.prefix + name)
         setattr(t, name, C.cast(fn, C.c_void_p).value)
-    for name in _OPTIONAL + _TABLE_TAIL:  # optional entries stay NULL when the library does not export them
+    for name in _OPTIONAL + _TABLE_TAIL + _TABLE_MORE:  # optional entries stay NULL when the library does not export them
         fn = getattr(api.lib, api.prefix + name, None) if hasattr(api.lib, api.prefix + name) else None
         set_table_entry(t, name, C.cast(fn, C.c_void_p).value if fn is not None else None)
     return t
@@ -306,6 +324,16 @@ def _bind(lib):
     lib.mvx_bnb_polish.argtypes = [C.c_void_p, C.c_void_p, _DP, C.c_int, _DP, _IP, _IP]
     lib.mvx_ranges.restype = C.c_int
     lib.mvx_ranges.argtypes = [C.c_void_p, _DP, _IP]
+    lib.mvx_kkt_many.restype = C.c_int
+    lib.mvx_kkt_many.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, _DP, _IP]
+    lib.mvx_kkt.restype = C.c_int
+    lib.mvx_kkt.argtypes = [C.c_void_p, _DP, _IP, _DP, _DP]
+    lib.mvx_check_kkt.restype = C.c_int
+    lib.mvx_check_kkt.argtypes = [C.c_void_p, C.c_int, C.c_int, _DP, _IP, _DP, _IP]
+    lib.mvx_bnb_kkt.restype = C.c_int
+    lib.mvx_bnb_kkt.argtypes = [C.c_void_p, C.c_void_p, _DP, _IP, _DP, _DP]
+    lib.mvx_bnb_kkt_values.restype = C.c_int
+    lib.mvx_bnb_kkt_values.argtypes = [C.c_int, C.c_int, _DP, _DP, _DP, _DP, _DP, _DP, _DP, _DP, _IP, C.c_int, _DP, _IP, _DP, _DP]
     lib.mvx_ranges_chunk.restype = C.c_int
     lib.mvx_ranges_chunk.argtypes = []
     lib.mvx_bnb_ranges.restype = C.c_int
@@ -403,13 +431,16 @@ def result_to_dict(res):
         "node_clique_conflicts": res.node_clique_conflicts,
         "node_clique_calls": res.node_clique_calls,
         "node_clique_rows": res.node_clique_rows,
+        "kkt_nodes": res.kkt_nodes,
+        "kkt_re": res.kkt_re,
+        "kkt_oid": res.kkt_oid,
     }
 
 
 def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, window=None, cut_select=0, cut_chance=1.0,
                 best_window=None, sb_cands=None, sb_iters=None, heur=None, rc_fix=None, prop=None, dive=None, dive_freq=None,
                 dive_depth=None, pump=None, pump_freq=None, pump_alpha=None, cut_rounds=None, cut_round_max=None, cut_maxpar=None,
-                cut_families=None, cut_purge=None, polish=None, node_purge=None, node_cliques=None):
+                cut_families=None, cut_purge=None, polish=None, node_purge=None, node_cliques=None, kkt=None):
     """mvx_bnb_params with ParameterObj's defaults (util.h:65-67) overridden by the arguments (None: the default)."""
     pr = BnbParams()
     lib().mvx_bnb_default_params(C.byref(pr))
@@ -458,6 +489,8 @@ def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, l
         pr.node_purge = node_purge
     if node_cliques is not None:
         pr.node_cliques = node_cliques
+    if kkt is not None:
+        pr.kkt = kkt
     return pr
 
 
@@ -465,7 +498,7 @@ def branch_and_bound(prob, var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, 
                      cut_select=0, cut_chance=1.0, best_window=None, sb_cands=None, sb_iters=None, heur=None, rc_fix=None, prop=None,
                      dive=None, dive_freq=None, dive_depth=None, pump=None, pump_freq=None, pump_alpha=None, cut_rounds=None,
                      cut_round_max=None, cut_maxpar=None, cut_families=None, cut_purge=None, polish=None, node_purge=None,
-                     node_cliques=None):
+                     node_cliques=None, kkt=None):
     """Run the driver on `prob` (a capi.Prob).  table=None uses the gfx950 engine's own table.  best_window > 1 with
     node_strat=1: the speculative best-bound window (mvx_bnb_params.best_window).  var_strat 3 / 4: branching on the node
     LP's penalties / strong branching (sb_cands candidates, sb_iters pivots per child).  heur 1 / 2: the primal rounding
@@ -486,13 +519,15 @@ def branch_and_bound(prob, var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, 
     1..64: a cut row behind the caller's rows leaves both children of a branching node once its auxiliary variable has been basic
     at A branching nodes in a row on the path (quirks=0, not with best_window; NODE_PURGE_COUNTERS in the dictionary).
     node_cliques = K in 1..64: up to K violated cliques of the model's conflict graph are separated at every branching node and
-    appended to both children (quirks=0, not with best_window; NODE_CLIQUE_COUNTERS in the dictionary).  The
+    appended to both children (quirks=0, not with best_window; NODE_CLIQUE_COUNTERS in the dictionary).  kkt = 1: every node LP the
+    tree solves is checked against the model (DESIGN.md "KKT check (kkt)"), pure observation, in both quirk modes, not with
+    best_window; KKT_COUNTERS in the dictionary.  The
     dictionary's "rc" is mvx_branchAndBound's return code (-1 refused parameters, -2 penalties, heuristic, tightening,
     propagation, pumps or dives unavailable)."""
     L = lib()
     pr = make_params(var_strat, node_strat, cut_strat, max_nodes, quirks, lazy_pool, window, cut_select, cut_chance, best_window, sb_cands,
                      sb_iters, heur, rc_fix, prop, dive, dive_freq, dive_depth, pump, pump_freq, pump_alpha, cut_rounds, cut_round_max,
-                     cut_maxpar, cut_families, cut_purge, polish, node_purge, node_cliques)
+                     cut_maxpar, cut_families, cut_purge, polish, node_purge, node_cliques, kkt)
     res = BnbResult()
     tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
     rc = L.mvx_branchAndBound(tptr, prob.h, C.byref(pr), C.byref(res))
@@ -749,6 +784,76 @@ def price_cols(prob, cols, obj, table=False):
 def del_cols_span():
     """mvx_del_cols_span: the destination positions a wave of k_delcols moves per batch."""
     return lib().mvx_del_cols_span()
+
+
+def _kkt_out(m, n, residuals):
+    import numpy as np
+
+    val, ind = np.zeros(8, dtype=np.float64), np.zeros(8, dtype=np.int32)
+    r_pe = np.zeros(m + 1, dtype=np.float64) if residuals else None
+    r_de = np.zeros(n + 1, dtype=np.float64) if residuals else None
+    return val, ind, r_pe, r_de
+
+
+def kkt(prob, table=False, residuals=True):
+    """KKT check of one solved handle (DESIGN.md "KKT check (kkt)"): (rc, val[8], ind[8], r_pe[0..m], r_de[0..n]); val holds ae_max,
+    re_max of PE, PB, DE, DB (KKT_CONDS), ind where they occur; the residual vectors are None with residuals=False.  table=False:
+    mvx_kkt, the gfx950 engine's kernels.  Otherwise the host twin mvx_bnb_kkt through `table` (None: the engine's own table) --
+    the same bits."""
+    DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    val, ind, r_pe, r_de = _kkt_out(prob.m, prob.n, residuals)
+    pe = r_pe.ctypes.data_as(DP) if residuals else None
+    de = r_de.ctypes.data_as(DP) if residuals else None
+    if table is False:
+        rc = lib().mvx_kkt(prob.h, val.ctypes.data_as(DP), ind.ctypes.data_as(IP), pe, de)
+    else:
+        tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
+        rc = lib().mvx_bnb_kkt(tptr, prob.h, val.ctypes.data_as(DP), ind.ctypes.data_as(IP), pe, de)
+    return rc, val, ind, r_pe, r_de
+
+
+def kkt_many(root, nodes, table=False):
+    """KKT check of the solved handles `nodes` over the rows of `root`: (rc, val (count, 8), ind (count, 8)).  table=False:
+    mvx_kkt_many, one device call for all of them.  Otherwise the host twin mvx_bnb_kkt handle by handle through `table`; rc is
+    then the first failing call's."""
+    import numpy as np
+
+    DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    count = len(nodes)
+    val, ind = np.zeros((count, 8), dtype=np.float64), np.zeros((count, 8), dtype=np.int32)
+    if table is False:
+        hs = (C.c_void_p * max(1, count))(*[p.h for p in nodes])
+        return lib().mvx_kkt_many(root.h, hs, count, val.ctypes.data_as(DP), ind.ctypes.data_as(IP)), val, ind
+    tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
+    for t, p in enumerate(nodes):
+        rc = lib().mvx_bnb_kkt(tptr, p.h, val[t].ctypes.data_as(DP), ind[t].ctypes.data_as(IP), None, None)
+        if rc != 0:
+            return rc, val, ind
+    return 0, val, ind
+
+
+def kkt_values(rows, c, xs, xr, lam, dj, lb, ub, stat, direction=capi.MAX):
+    """mvx_bnb_kkt_values, the check from numbers only: rows (m, n) the dense model rows, c (n,) the objective, xs / dj (n,) and
+    xr / lam (m,) the four value vectors, lb / ub / stat (m + n,) by variable with the auxiliaries first (+-inf for an absent
+    bound).  Returns (rc, val[8], ind[8], r_pe[0..m], r_de[0..n])."""
+    import numpy as np
+
+    DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    rows = np.asarray(rows, dtype=np.float64)
+    m, n = rows.shape
+
+    def lead(v, k, dtype=np.float64):  # the C layout: entry 0 unused
+        v = np.asarray(v, dtype=dtype)
+        assert v.shape == (k,), (v.shape, k)
+        return np.ascontiguousarray(np.concatenate([np.zeros(1, dtype=dtype), v]))
+
+    R = np.ascontiguousarray(np.hstack([np.zeros((m, 1)), rows]))
+    args = [lead(c, n), lead(xs, n), lead(xr, m), lead(lam, m), lead(dj, n), lead(lb, m + n), lead(ub, m + n)]
+    st = lead(stat, m + n, np.int32)
+    val, ind, r_pe, r_de = _kkt_out(m, n, True)
+    rc = lib().mvx_bnb_kkt_values(m, n, R.ctypes.data_as(DP), *[a.ctypes.data_as(DP) for a in args], st.ctypes.data_as(IP), int(direction),
+                                  val.ctypes.data_as(DP), ind.ctypes.data_as(IP), r_pe.ctypes.data_as(DP), r_de.ctypes.data_as(DP))
+    return rc, val, ind, r_pe, r_de
 
 
 def ranges_chunk():

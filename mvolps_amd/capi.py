@@ -341,6 +341,24 @@ class Prob:
         rc = self.api.ranges(self.h, _dp(val), _ip(var))
         return rc, val, var
 
+    def kkt(self, residuals=True):
+        """mvx_kkt (the gfx950 engine's library only): the KKT check of the solved handle against its own model.  Returns (rc, val,
+        ind, r_pe, r_de): val[8] = ae_max, re_max of PE, PB, DE, DB, ind[8] where they occur, r_pe[0..m] / r_de[0..n] the residuals
+        (None with residuals=False)."""
+        val = np.zeros(8, dtype=np.float64)
+        ind = np.zeros(8, dtype=np.int32)
+        r_pe = np.zeros(self.m + 1, dtype=np.float64) if residuals else None
+        r_de = np.zeros(self.n + 1, dtype=np.float64) if residuals else None
+        rc = self.api.kkt(self.h, _dp(val), _ip(ind), _dp(r_pe) if residuals else None, _dp(r_de) if residuals else None)
+        return rc, val, ind, r_pe, r_de
+
+    def check_kkt(self, cond, sol=1):
+        """mvx_check_kkt, glp_check_kkt's shape: (rc, ae_max, ae_ind, re_max, re_ind) of condition cond = 1 PE, 2 PB, 3 DE, 4 DB."""
+        ae, re = C.c_double(0.0), C.c_double(0.0)
+        ai, ri = C.c_int(0), C.c_int(0)
+        rc = self.api.check_kkt(self.h, sol, cond, C.byref(ae), C.byref(ai), C.byref(re), C.byref(ri))
+        return rc, ae.value, ai.value, re.value, ri.value
+
     def eval_tab_row(self, k):
         n = self.n
         ind = np.zeros(n + 1, dtype=np.int32)

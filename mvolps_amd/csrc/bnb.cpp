@@ -61,6 +61,7 @@ extern "C" int mvx_clique_cuts_many(const mvx_prob *root, const mvx_prob *const 
                                     double *sum) __attribute__((weak));
 extern "C" int mvx_add_cut_rows_many(mvx_prob *const *Ps, int count, const int *off, const double *vals, const double *rhs)
     __attribute__((weak));
+extern "C" int mvx_kkt_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, double *val, int *ind) __attribute__((weak));
 
 namespace {
 
@@ -939,12 +940,14 @@ struct RangeView {
   std::vector<int> head, nb, flag;
 };
 
-// 0; -2 an accessor is missing or failed; -3 the handle is not MVX_OPT
-static int read_range_view(const mvx_lp_api *api, const void *P, RangeView &V) {
-  if (!api->get_tableau || !api->get_basis || !api->get_row_lb || !api->get_row_ub || !api->get_col_lb || !api->get_col_ub || !api->get_status ||
-      !api->get_num_rows || !api->get_num_cols)
-    return -2;
-  if (api->get_status(P) != MVX_OPT) return -3;
+static bool has_view_accessors(const mvx_lp_api *api) {
+  return api->get_tableau && api->get_basis && api->get_row_lb && api->get_row_ub && api->get_col_lb && api->get_col_ub && api->get_status &&
+         api->get_num_rows && api->get_num_cols;
+}
+
+// the tableau, basis and bounds of a handle whatever its status (the table has the accessors: has_view_accessors); 0, or -2 when
+// get_basis / get_tableau failed
+static int read_tableau_view(const mvx_lp_api *api, const void *P, RangeView &V) {
   const int m = V.m = api->get_num_rows(P), n = V.n = api->get_num_cols(P);
   V.maxdir = (api->get_obj_dir && api->get_obj_dir(P) == MVX_MIN) ? 0 : 1;
   V.T.assign((size_t)(m + 1) * (size_t)(n + 1), 0.0);
@@ -963,6 +966,13 @@ static int read_range_view(const mvx_lp_api *api, const void *P, RangeView &V) {
     V.ub[(size_t)(m + j)] = tab_bound(api->get_col_ub(P, j));
   }
   return 0;
+}
+
+// 0; -2 an accessor is missing or failed; -3 the handle is not MVX_OPT
+static int read_range_view(const mvx_lp_api *api, const void *P, RangeView &V) {
+  if (!has_view_accessors(api)) return -2;
+  if (api->get_status(P) != MVX_OPT) return -3;
+  return read_tableau_view(api, P, V);
 }
 
 // The host twin of k_rangecols / k_rangefin / k_rangerows: the same tests, the same divisions, one walk over ascending rows
@@ -1048,6 +1058,171 @@ static void host_ranges(const RangeView &V, double tol, double *val, int *var) {
     w[3] = V.maxdir ? vu : vd;
   }
 }
+
+// ---- KKT check (DESIGN.md "KKT check (kkt)") ----
+
+// sum over k = 1..cnt of a(k) * v[k] in the order of mvx_price_cols' S: 64 chains, chain l taking k = l+1, l+65, ... ascending with
+// fma from +0.0, combined by s[l] += s[l+h], h = 32 .. 1.  Zeros are not skipped
+template <typename A>
+static double kkt_chain_sum(int cnt, A a, const double *v) {
+  double s[64];
+  for (int l = 0; l < 64; l++) {
+    double acc = 0.0;
+    for (int k = l + 1; k <= cnt; k += 64) acc = std::fma(a(k), v[k], acc);
+    s[l] = acc;
+  }
+  for (int h = 32; h >= 1; h >>= 1)
+    for (int l = 0; l < h; l++) s[l] = s[l] + s[l + h];
+  return s[0];
+}
+
+// a maximum with a strict compare over ascending indices: the lowest index among equals, 0 while the maximum is 0
+struct KktMax {
+  double v = 0.0;
+  int i = 0;
+  void see(double w, int k) {
+    if (w > v) {
+      v = w;
+      i = k;
+    }
+  }
+};
+
+// The host twin of k_kkt_rows / k_kkt_cols / k_kkt_fin from numbers only: rows m x (n+1) dense (entry 0 of each unused), c[0..n],
+// xs / dj [0..n], xr / lam [0..m], lb / ub / stat [0..m+n] by variable (+-inf where absent), sg +1 minimise / -1 maximise
+static void kkt_host(int m, int n, const double *rows, const double *c, const double *xs, const double *xr, const double *lam, const double *dj,
+                     const double *lb, const double *ub, const int *stat, double sg, double *val, int *ind, double *r_pe, double *r_de) {
+  const size_t ldr = (size_t)n + 1;
+  const double inf = std::numeric_limits<double>::infinity();
+  KktMax mx[8];
+  if (r_pe) r_pe[0] = 0.0;
+  if (r_de) r_de[0] = 0.0;
+  for (int i = 1; i <= m; i++) { // PE
+    const double *ai = rows + (size_t)(i - 1) * ldr;
+    const double s = kkt_chain_sum(n, [&](int j) { return ai[j]; }, xs);
+    const double r = xr[i] - s, ae = std::fabs(r);
+    if (r_pe) r_pe[i] = r;
+    mx[0].see(ae, i);
+    mx[1].see(ae / (1.0 + std::fabs(xr[i])), i);
+  }
+  for (int j = 1; j <= n; j++) { // DE
+    const double t = kkt_chain_sum(m, [&](int i) { return rows[(size_t)(i - 1) * ldr + (size_t)j]; }, lam);
+    const double r = (c[j] - t) - dj[j], ae = std::fabs(r);
+    if (r_de) r_de[j] = r;
+    mx[4].see(ae, j);
+    mx[5].see(ae / (1.0 + std::fabs(c[j])), j);
+  }
+  for (int k = 1; k <= m + n; k++) { // PB, DB
+    const double x = k <= m ? xr[k] : xs[k - m], d = k <= m ? lam[k] : dj[k - m];
+    const double l = lb[k], u = ub[k];
+    double ae = 0.0, re = 0.0;
+    if (std::fabs(l) != inf && x < l) {
+      ae = l - x;
+      re = ae / (1.0 + std::fabs(l));
+    } else if (std::fabs(u) != inf && x > u) {
+      ae = x - u;
+      re = ae / (1.0 + std::fabs(u));
+    }
+    mx[2].see(ae, k);
+    mx[3].see(re, k);
+    const double e = sg * d;
+    double v;
+    switch (stat[k]) {
+      case MVX_NL: v = -e > 0.0 ? -e : 0.0; break;
+      case MVX_NU: v = e > 0.0 ? e : 0.0; break;
+      case MVX_NF: v = std::fabs(e); break;
+      case MVX_NS: v = 0.0; break;
+      default: v = std::fabs(d); break;
+    }
+    mx[6].see(v, k);
+    mx[7].see(v / (1.0 + std::fabs(d)), k);
+  }
+  for (int t = 0; t < 8; t++) {
+    val[t] = mx[t].v;
+    ind[t] = mx[t].i;
+  }
+}
+
+// The twin through the table: the model's rows, bounds and objective, and the four value vectors by the getters' own rule out of
+// get_tableau and get_basis -- column 0 where a variable is basic, the bound its status names (0 for MVX_NF) where it is not;
+// row 0 at a non-basic variable's position, 0 for a basic one.  0; -2 an accessor is missing or failed; -3 MVX_UNDEF
+static int kkt_through_table(const mvx_lp_api *api, const void *P, double *val, int *ind, double *r_pe, double *r_de) {
+  if (!api->get_mat_row || !api->get_obj_coef || !has_view_accessors(api)) return -2;
+  if (api->get_status(P) == MVX_UNDEF) return -3; // every state a solve leaves behind will do
+  RangeView V;
+  const int rc = read_tableau_view(api, P, V);
+  if (rc != 0) return rc;
+  const int m = V.m, n = V.n;
+  const size_t ldr = (size_t)n + 1;
+  std::vector<double> rows((size_t)m * ldr, 0.0), c(ldr, 0.0), xs(ldr, 0.0), dj(ldr, 0.0), xr((size_t)m + 1, 0.0), lam((size_t)m + 1, 0.0);
+  std::vector<int> stat((size_t)m + n + 1, 0), idx(ldr);
+  std::vector<double> buf(ldr);
+  for (int i = 1; i <= m; i++) {
+    const int len = api->get_mat_row(P, i, idx.data(), buf.data());
+    for (int k = 1; k <= len; k++) rows[(size_t)(i - 1) * ldr + (size_t)idx[(size_t)k]] = buf[(size_t)k];
+  }
+  for (int j = 1; j <= n; j++) c[(size_t)j] = api->get_obj_coef(P, j);
+  auto put = [&](int k, double x, double d, int s) {
+    (k <= m ? xr[(size_t)k] : xs[(size_t)(k - m)]) = x;
+    (k <= m ? lam[(size_t)k] : dj[(size_t)(k - m)]) = d;
+    stat[(size_t)k] = s;
+  };
+  for (int i = 1; i <= m; i++) put(V.head[(size_t)i], V.T[(size_t)i * ldr], 0.0, MVX_BS);
+  for (int q = 1; q <= n; q++) {
+    const int k = V.nb[(size_t)q], f = V.flag[(size_t)q];
+    const double x = f == MVX_NL ? V.lb[(size_t)k] : f == MVX_NU ? V.ub[(size_t)k] : f == MVX_NS ? V.lb[(size_t)k] : 0.0;
+    put(k, x, V.T[(size_t)q], f);
+  }
+  kkt_host(m, n, rows.data(), c.data(), xs.data(), xr.data(), lam.data(), dj.data(), V.lb.data(), V.ub.data(), stat.data(),
+           V.maxdir ? -1.0 : 1.0, val, ind, r_pe, r_de);
+  return 0;
+}
+
+// The rule's state for one tree: the route to the check (the table's kkt_many over `model`, the twin without the entry) and
+// what the tree reports -- the nodes checked, the worst re_max per condition and the lowest oid it occurred at.
+class KktCheck {
+public:
+  KktCheck(const mvx_lp_api *api, const void *model, int on) : _api(api), _model(model), _on(on > 0) {}
+  bool on() const { return _on; }
+  // val[8 t ..] of the solved handles hs; 0, or the failing call's code
+  int compute(const std::vector<const void *> &hs, std::vector<double> &val) {
+    val.assign(hs.size() * 8, 0.0);
+    if (hs.empty()) return 0;
+    std::vector<int> ind(hs.size() * 8, 0);
+    if (_api->kkt_many) return _api->kkt_many(_model, hs.data(), (int)hs.size(), val.data(), ind.data());
+    for (size_t t = 0; t < hs.size(); t++) {
+      const int rc = kkt_through_table(_api, hs[t], &val[t * 8], &ind[t * 8], nullptr, nullptr);
+      if (rc != 0) return rc;
+    }
+    return 0;
+  }
+  // a solved node books its result, in the order the serial loop meets the nodes
+  void book(const double *val, int oid) {
+    _nodes++;
+    for (int c = 0; c < 4; c++) {
+      const double re = val[2 * c + 1];
+      if (re > _re[c] || (re == _re[c] && re > 0.0 && oid < _oid[c])) { // the lowest oid among equals, 0 while nothing is violated
+        _re[c] = re;
+        _oid[c] = oid;
+      }
+    }
+  }
+  void store(mvx_bnb_result *res) const {
+    res->kkt_nodes = _nodes;
+    for (int c = 0; c < 4; c++) {
+      res->kkt_re[c] = _re[c];
+      res->kkt_oid[c] = _oid[c];
+    }
+  }
+
+private:
+  const mvx_lp_api *_api;
+  const void *_model;
+  const bool _on;
+  long long _nodes = 0;
+  double _re[4] = {0.0, 0.0, 0.0, 0.0};
+  int _oid[4] = {0, 0, 0, 0};
+};
 
 // 0, or -2 when the table lacks an accessor of the rows, the bounds or the column kinds
 static int read_host_model(const mvx_lp_api *api, const void *root, HostModel &M) {
@@ -2734,6 +2909,7 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const void *model, const m
   Dive dive(T.hm, prm);
   Pump pump(T.hm, prm);
   NodeCliques ncl(api, T.hm.root, prm.node_cliques);
+  KktCheck kkt(api, T.hm.root, prm.kkt);
   if (ncl.start() != 0) { // the graph could not be taken: the tree so far is the unsolved root
     T.rc_out = -2;
     leafContainer.clear();
@@ -2749,6 +2925,14 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const void *model, const m
       const long long piv0 = rec.pivots;
       solve(api, a, rec); // bs.cpp:117
       T.worked(*node, a, rec.pivots - piv0);
+    }
+    if (kkt.on()) { // kkt: the node's LP as solved, whatever its end status; nothing of the tree reads the result
+      std::vector<double> kv;
+      if (kkt.compute({a}, kv) != 0) {
+        T.rc_out = -2;
+        break;
+      }
+      kkt.book(kv.data(), node->oid);
     }
     const double obj = api->get_obj_val(a);
     rec.emit(MVX_EV_PREGNANT, node->oid, obj, 0.0, 0, 0); // bs.cpp:119-129
@@ -2867,6 +3051,7 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const void *model, const m
   api->delete_prob(a);
   const int rc = T.finish(res, &rcfix, &prop);
   ncl.store(res);
+  kkt.store(res);
   return rc;
 }
 
@@ -2889,6 +3074,7 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const void *model, c
   Dive dive(T.hm, prm);
   Pump pump(T.hm, prm);
   NodeCliques ncl(api, T.hm.root, prm.node_cliques);
+  KktCheck kkt(api, T.hm.root, prm.kkt);
   auto fail = [&]() { // whatever code a failing call gives, the tree so far goes back with -2
     T.rc_out = -2;
     stop = true;
@@ -3002,6 +3188,12 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const void *model, c
       if (st != MVX_OPT) need.push_back(a[w]);
     }
     if (!need.empty()) api->simplex_batch(need.data(), (int)need.size(), nullptr, nullptr); // none of them is in flight
+    // kkt: the nodes this round has solved, in one call; booked by the replay for the nodes it reaches
+    std::vector<double> kval;
+    if (kkt.on() && kkt.compute(std::vector<const void *>(a.begin(), a.end()), kval) != 0) {
+      fail();
+      break;
+    }
     tA += now() - t0; t0 = now();
     // the lazy cut modes: the one cut of every node of the window that may branch, in one device pass (round_cuts);
     // printInfo of the window is taken ahead for that and reused by the replay
@@ -3122,6 +3314,7 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const void *model, c
       rec.pivots += (node->repiv >= 0) ? node->repiv : api->get_it_cnt(aw) - before[w];
       T.worked(*node, aw, (node->repiv >= 0) ? node->repiv : api->get_it_cnt(aw) - before[w]);
       processed++;
+      if (kkt.on()) kkt.book(&kval[w * 8], node->oid);
       const double obj = api->get_obj_val(aw);
       rec.emit(MVX_EV_PREGNANT, node->oid, obj, 0.0, 0, 0);
       double ti = now();
@@ -3332,6 +3525,7 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const void *model, c
   leafContainer.clear();
   const int rc = T.finish(res, &rcfix, &prop);
   ncl.store(res);
+  kkt.store(res);
   return rc;
 }
 
@@ -3667,6 +3861,9 @@ const mvx_lp_api g_hip_api = {
     mvx_add_cut_rows_many ? +[](void *const *Ps, int count, const int *off, const double *vals, const double *rhs) {
       return mvx_add_cut_rows_many((mvx_prob *const *)Ps, count, off, vals, rhs);
     } : nullptr,
+    mvx_kkt_many ? +[](const void *root, const void *const *Ps, int count, double *val, int *ind) {
+      return mvx_kkt_many((const mvx_prob *)root, (const mvx_prob *const *)Ps, count, val, ind);
+    } : nullptr,
 };
 
 } // namespace
@@ -3706,6 +3903,7 @@ void mvx_bnb_default_params(mvx_bnb_params *p) {
   p->polish = 0;
   p->node_purge = 0;
   p->node_cliques = 0;
+  p->kkt = 0;
 }
 
 // Repaired mode's rule for an integer column whose bounds are not integers (legal input: LP and MPS files may carry them):
@@ -4120,7 +4318,9 @@ int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *
       (params->node_purge > 0 && (params->reference_quirks != 0 || params->best_window > 0)) ||
       // node_cliques: rows on the repaired mode's children; not (yet) in the best-bound window
       params->node_cliques < 0 || params->node_cliques > 64 ||
-      (params->node_cliques > 0 && (params->reference_quirks != 0 || params->best_window > 0))) {
+      (params->node_cliques > 0 && (params->reference_quirks != 0 || params->best_window > 0)) ||
+      // kkt: observation of every solved node, in both quirk modes; not (yet) in the best-bound window
+      params->kkt < 0 || params->kkt > 1 || (params->kkt > 0 && params->best_window > 0)) {
     std::memset(res, 0, sizeof(*res));
     return -1;
   }
@@ -4415,6 +4615,21 @@ int mvx_bnb_polish(const mvx_lp_api *api, const void *root, double *x, int max_m
   const int rc = read_host_model(api, root, M);
   if (rc != 0) return rc;
   return polish_host(M, x, max_moves, obj, moves, ok);
+}
+
+int mvx_bnb_kkt_values(int m, int n, const double *rows, const double *c, const double *xs, const double *xr, const double *lam,
+                       const double *dj, const double *lb, const double *ub, const int *stat, int dir, double *val, int *ind, double *r_pe,
+                       double *r_de) {
+  if (m < 1 || n < 1 || !rows || !c || !xs || !xr || !lam || !dj || !lb || !ub || !stat || !val || !ind || (dir != MVX_MIN && dir != MVX_MAX))
+    return -1;
+  kkt_host(m, n, rows, c, xs, xr, lam, dj, lb, ub, stat, dir == MVX_MIN ? 1.0 : -1.0, val, ind, r_pe, r_de);
+  return 0;
+}
+
+int mvx_bnb_kkt(const mvx_lp_api *api, const void *prob, double *val, int *ind, double *r_pe, double *r_de) {
+  if (!api) api = &g_hip_api;
+  if (!prob || !val || !ind) return -1;
+  return kkt_through_table(api, prob, val, ind, r_pe, r_de);
 }
 
 int mvx_bnb_ranges(const mvx_lp_api *api, const void *prob, double *val, int *var) {

@@ -734,6 +734,25 @@ int mvx_branch_penalties_many(const mvx_prob *const *Ps, int count, const int *c
 }
 int mvx_ranges(const mvx_prob *P, double *val, int *var) { return mvx::engine_ranges(P, g_tol_piv, val, var); }
 int mvx_ranges_chunk(void) { return mvx::RANGE_CHUNK; }
+int mvx_kkt_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, double *val, int *ind) {
+  return mvx::engine_kkt_many(root, Ps, count, val, ind, nullptr, nullptr);
+}
+int mvx_kkt(const mvx_prob *P, double *val, int *ind, double *r_pe, double *r_de) {
+  if (!P) return -1;
+  return mvx::engine_kkt_many(P, &P, 1, val, ind, r_pe, r_de);
+}
+int mvx_check_kkt(const mvx_prob *P, int sol, int cond, double *ae_max, int *ae_ind, double *re_max, int *re_ind) {
+  if (!P || sol != 1 || cond < 1 || cond > 4 || !ae_max || !ae_ind || !re_max || !re_ind) return -1;
+  double val[8];
+  int ind[8];
+  const int rc = mvx::engine_kkt_many(P, &P, 1, val, ind, nullptr, nullptr);
+  if (rc != 0) return rc;
+  *ae_max = val[2 * (cond - 1)];
+  *ae_ind = ind[2 * (cond - 1)];
+  *re_max = val[2 * (cond - 1) + 1];
+  *re_ind = ind[2 * (cond - 1) + 1];
+  return 0;
+}
 int mvx_round_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, int mode, double *obj, int *found, double *x) {
   return mvx::engine_round_many(root, Ps, count, mode, obj, found, x);
 }

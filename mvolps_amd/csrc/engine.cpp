@@ -3637,6 +3637,105 @@ int engine_clique_cuts_many(const mvx_prob *root, const mvx_prob *const *Ps, int
   return 0;
 }
 
+// ------------------------------------------------------------------ KKT check (k_kkt_vals, k_kkt_rows, k_kkt_cols, k_kkt_fin)
+// The KKT conditions of `count` solved handles against their own models (mvx_kkt_many, DESIGN.md "KKT check (kkt)"): rows 1..m0
+// are read from root's rounding model in both orientations (uploaded on first use, checked on every call), each handle's cut
+// rows m0+1..m and, where it differs from root's, its objective go up with the descriptors in the call's one upload, and the
+// values, duals, statuses and bounds are read where they lie in each handle's slab.  One flush of the recorded clones, one
+// upload, one launch sequence, one copy back; no handle is changed.  r_pe / r_de (nullable): the residual vectors of handle 0,
+// which the single-handle entry asks for.  Return codes: 0; -1 bad arguments; -2 device out of memory, nothing written; -3 a
+// handle that is MVX_UNDEF or has no tableau (or bound edits still pending), or one whose first m0 rows are not root's.
+int engine_kkt_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, double *val, int *ind, double *r_pe, double *r_de) {
+  if (!root || count < 0) return -1;
+  if (count == 0) return 0;
+  if (!Ps || !val || !ind) return -1;
+  const int n = root->n, m0 = root->m;
+  for (int t = 0; t < count; t++)
+    if (!Ps[t] || Ps[t]->n != n) return -1;
+  if (n < 1 || m0 < 1) return -3;
+  size_t vars = 0, cut_rows = 0, own_obj = 0;
+  int mmax = 0;
+  for (int t = 0; t < count; t++) {
+    const mvx_prob *P = Ps[t];
+    if (!P->valid || P->status == MVX_UNDEF || !P->pending.empty() || P->m < m0) return -3;
+    if (P != root)
+      for (int i = 1; i <= m0; i++)
+        if (P->A[(size_t)i].get() != root->A[(size_t)i].get()) return -3;
+    vars += (size_t)P->m + (size_t)n + 1;
+    cut_rows += (size_t)(P->m - m0);
+    own_obj += P != root && P->c != root->c;
+    mmax = std::max(mmax, P->m);
+  }
+  NodeCall f(NodeFlush::AtEntry, NodeResults::Device);
+  const RoundModel *M = round_model(*f.c, root);
+  if (!M || !round_model_rows(*f.c, root, root->rmod.get())) return -2;
+  const size_t row = (size_t)n + 1;
+  const bool want_r = r_pe || r_de;
+  // up: [descriptors][cut rows][own objectives]; back: [val][ind] (and the residuals when they are wanted); device only: the
+  // by-variable arrays
+  const size_t o_nodes = f.up((size_t)count * sizeof(KktNode)), o_cuts = f.up(cut_rows * row * 8), o_obj = f.up(own_obj * row * 8);
+  const size_t o_val = f.out((size_t)count * 8 * 8), o_ind = f.out((size_t)count * 8 * 4);
+  const size_t o_res = want_r ? f.out(vars * 8) : f.dev(vars * 8);
+  const size_t o_x = f.dev(vars * 8), o_du = f.dev(vars * 8), o_lo = f.dev(vars * 8), o_up = f.dev(vars * 8), o_st = f.dev(vars * 4);
+  size_t o_term[8];
+  for (int k = 0; k < 8; k++) o_term[k] = f.dev(vars * 8);
+  if (!f.reserve()) return -2;
+  unsigned char *hb = f.hb, *db = f.db;
+  KktNode *h_nodes = (KktNode *)(hb + o_nodes);
+  size_t voff = 0, cut_at = 0, obj_at = 0;
+  for (int t = 0; t < count; t++) {
+    const mvx_prob *P = Ps[t];
+    KktNode &nd = h_nodes[t];
+    static_cast<NodeRef &>(nd) = node_ref(P);
+    nd.blb = P->d_blb;
+    nd.bub = P->d_bub;
+    nd.cuts = nullptr;
+    nd.c = nullptr;
+    if (P->m > m0) {
+      nd.cuts = (const double *)(db + o_cuts) + cut_at * row;
+      for (int i = m0 + 1; i <= P->m; i++, cut_at++) {
+        if (P->A[(size_t)i]) std::memcpy(hb + o_cuts + cut_at * row * 8, P->A[(size_t)i]->data(), row * 8);
+        else std::memset(hb + o_cuts + cut_at * row * 8, 0, row * 8); // a row that was never filled is empty
+      }
+    }
+    if (P != root && P->c != root->c) {
+      nd.c = (const double *)(db + o_obj) + obj_at * row;
+      std::memcpy(hb + o_obj + (obj_at++) * row * 8, P->c.data(), row * 8);
+    }
+    nd.voff = voff;
+    nd.sg = P->dir == MVX_MIN ? 1.0 : -1.0;
+    voff += (size_t)P->m + row;
+  }
+  f.upload();
+  const unsigned char *mb = (const unsigned char *)M->dev;
+  KktArgs a;
+  a.nodes = (const KktNode *)(db + o_nodes);
+  a.At = (const double *)mb;
+  a.Ar = (const double *)M->dev_rows;
+  a.c0 = (const double *)(mb + M->o_c);
+  a.x = (double *)(db + o_x); a.du = (double *)(db + o_du); a.lo = (double *)(db + o_lo); a.up = (double *)(db + o_up);
+  a.res = (double *)(db + o_res);
+  a.st = (int *)(db + o_st);
+  for (int k = 0; k < 8; k++) a.term[k] = (double *)(db + o_term[k]);
+  a.val = (double *)(db + o_val); a.ind = (int *)(db + o_ind);
+  a.n = n; a.m0 = m0; a.ldm = M->ldm; a.ldn = M->ldn; a.count = count; a.mmax = mmax;
+  launch_kkt(a, f.stream());
+  f.copy_back(want_r ? o_res + ((size_t)Ps[0]->m + row) * 8 : 0); // of the residuals, handle 0's slice only
+  f.sync();
+  std::memcpy(val, hb + o_val, (size_t)count * 8 * 8);
+  std::memcpy(ind, hb + o_ind, (size_t)count * 8 * 4);
+  const double *h_res = (const double *)(hb + o_res);
+  if (r_pe) {
+    r_pe[0] = 0.0;
+    std::memcpy(r_pe + 1, h_res + 1, (size_t)Ps[0]->m * 8);
+  }
+  if (r_de) {
+    r_de[0] = 0.0;
+    std::memcpy(r_de + 1, h_res + (size_t)Ps[0]->m + 1, (size_t)n * 8);
+  }
+  return 0;
+}
+
 // ------------------------------------------------------------------ incumbent polishing (k_lsact, k_lsmove, k_lsapply)
 // The exchange search of mvx_polish_many on `count` points against root's model (both orientations, as the conflict graph
 // reads it): the points go up, k_lsact takes the entry, then iterations (k_lsmove + k_lsapply) are enqueued LS_GROUP at a time

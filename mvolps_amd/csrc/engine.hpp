@@ -45,6 +45,8 @@ int engine_penalties_many(const mvx_prob *const *Ps, int count, const int *cols,
                           double *pen_up, int *arg_down, int *arg_up);
 // sensitivity ranges of one solved handle: val (m+n+1) x 6, var (m+n+1) x 4 (k_rangecols, k_rangefin, k_rangerows); see engine.cpp
 int engine_ranges(const mvx_prob *P, double tol, double *val, int *var);
+// KKT check of `count` solved handles over root's rows (k_kkt_vals, k_kkt_rows, k_kkt_cols, k_kkt_fin); see engine.cpp
+int engine_kkt_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, double *val, int *ind, double *r_pe, double *r_de);
 // primal rounding heuristic on `count` solved handles against root's model, one launch (k_round); see engine.cpp
 int engine_round_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, int mode, double *obj, int *found, double *x);
 // the diving heuristic's branching pick for `count` (solved handle, rule) pairs against root's model, one launch (k_divepick)

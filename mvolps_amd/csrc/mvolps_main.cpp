@@ -1,7 +1,7 @@
 // mvolps -- command-line front end over libmvolps_amd.so; counterpart of MVOLPS's main
 // (/root/reference/2test.cpp:13-157): same flags, same dispatch on the file extension
 // (2test.cpp:65-81), then initProblem (util.cpp:277-292) and branchAndBound (bs.cpp:54).
-// Extra flags of this build: --repaired (reference_quirks = 0), --max-nodes N, --events FILE, --ranges FILE.
+// Extra flags of this build: --repaired (reference_quirks = 0), --max-nodes N, --events FILE, --ranges FILE, --kkt FILE.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -45,6 +45,9 @@ int main(int argc, char **argv) {
               << "  --events [FILE] write the B&B event stream (one line per event) to FILE\n"
               << "  --ranges [FILE] solve the root LP, write its sensitivity ranges (one line per row and column: activity ranges,\n"
               << "                  objective changes, allowable cost changes) to FILE, then run as without the flag\n"
+              << "  --kkt [FILE]    solve the root LP, write its KKT check against the model (four lines KKT.PE, KKT.PB, KKT.DE, KKT.DB:\n"
+              << "                  ae_max, its index, re_max, its index) to FILE, run the tree with every node LP checked, and append\n"
+              << "                  the tree's summary (nodes checked, worst re_max per condition and its node); not with --best-window\n"
               << "Output verbosity options:\n"
               << "  -s/--silent\n  -v/--verbose\n  -d/--debug\n  -so/--solver-output\n\n"
               << "Algorithm strategy options:\n"
@@ -305,6 +308,38 @@ int main(int argc, char **argv) {
     mvx_delete_prob(root);
   }
 
+  std::string kkt_path;
+  if (input.CMDOptionExists("--kkt")) {
+    kkt_path = input.getCMDOption("--kkt");
+    if (kkt_path.empty() || kkt_path[0] == '-') { // the end of the line, or the next flag
+      std::fprintf(stderr, "Unknown parameter value for --kkt\n");
+      return -1;
+    }
+    if (params.best_window > 0) {
+      std::fprintf(stderr, "--kkt is not supported with --best-window\n");
+      return -1;
+    }
+    // the root LP as the tree will first solve it, on a copy: the run below starts from the handle as it was read
+    mvx_prob *root = mvx_create_prob();
+    mvx_copy_prob(root, prob, MVX_ON);
+    if (!params.reference_quirks) mvx_bnb_integral_bounds(nullptr, root);
+    mvx_simplex(root, nullptr);
+    double val[8];
+    int ind[8];
+    const int krc = mvx_kkt(root, val, ind, nullptr, nullptr);
+    FILE *out = krc == 0 ? std::fopen(kkt_path.c_str(), "w") : nullptr;
+    if (out) {
+      static const char *const cond[4] = {"PE", "PB", "DE", "DB"};
+      for (int c = 0; c < 4; c++) std::fprintf(out, "KKT.%s %.17g %d %.17g %d\n", cond[c], val[2 * c], ind[2 * c], val[2 * c + 1], ind[2 * c + 1]);
+      std::fclose(out);
+      params.kkt = 1; // the tree's summary follows the root's lines
+    } else { // nothing was written and nothing will be appended: the run goes on as without the flag
+      std::fprintf(stderr, "--kkt: no report (%d): the root LP could not be checked, or %s cannot be written; the tree runs unchecked\n", krc,
+                   kkt_path.c_str());
+    }
+    mvx_delete_prob(root);
+  }
+
   mvx_bnb_result res;
   const int brc = mvx_branchAndBound(nullptr, prob, &params, &res);
   if (brc == -1) {
@@ -360,6 +395,20 @@ int main(int argc, char **argv) {
   if (verbose && params.node_cliques > 0)
     std::printf("Node cliques: %lld conflicts, %lld nodes separated, %lld rows\n", res.node_clique_conflicts, res.node_clique_calls,
                 res.node_clique_rows);
+  if (params.kkt > 0) {
+    static const char *const cond[4] = {"PE", "PB", "DE", "DB"};
+    if (FILE *out = std::fopen(kkt_path.c_str(), "a")) {
+      std::fprintf(out, "KKT.NODES %lld\n", res.kkt_nodes);
+      for (int c = 0; c < 4; c++) std::fprintf(out, "KKT.TREE.%s %.17g %d\n", cond[c], res.kkt_re[c], res.kkt_oid[c]);
+      std::fclose(out);
+    } else {
+      std::fprintf(stderr, "--kkt: the tree's summary could not be appended to %s\n", kkt_path.c_str());
+    }
+    if (verbose)
+      std::printf("KKT check: %lld nodes, worst relative errors PE %.3g (node %d), PB %.3g (node %d), DE %.3g (node %d), DB %.3g (node %d)\n",
+                  res.kkt_nodes, res.kkt_re[0], res.kkt_oid[0], res.kkt_re[1], res.kkt_oid[1], res.kkt_re[2], res.kkt_oid[2], res.kkt_re[3],
+                  res.kkt_oid[3]);
+  }
   const int limit = res.hit_limit || brc != 0;
   mvx_bnb_free_result(&res);
   mvx_delete_prob(prob);

@@ -307,6 +307,35 @@ struct RangeArgs {
   int n, nchunks, maxdir, pad; // maxdir: 1 under MVX_MAX
 };
 
+// one handle of a KKT launch (k_kkt_vals / k_kkt_rows / k_kkt_cols / k_kkt_fin; mvx_kkt_many, DESIGN.md "KKT check (kkt)"): the
+// handle, the bounds of its basic variables, where its cut rows (rows m0+1..m, dense, n + 1 doubles each) and its own objective
+// lie in the call's upload, and where its slice of the by-variable arrays starts (m + n + 1 entries, entry 0 unused)
+struct KktNode : NodeRef {
+  const double *blb, *bub; // [m+1]
+  const double *cuts;      // [m - m0][n+1], nullptr when m == m0
+  const double *c;         // [n+1] the handle's objective where it differs from the root's, else nullptr
+  size_t voff;
+  double sg;               // +1 minimise, -1 maximise
+};
+
+// arguments of the KKT kernels: `count` handles over the model of one root in both orientations (k_prop's copies).  The
+// by-variable arrays hold one slice per handle (KktNode::voff): x / du / lo / up / st the value, dual, bounds and status of
+// variable k, res the residuals (row i at i, column j at m + j), term[c] the ae (2c) and re (2c + 1) of condition c = PE, PB,
+// DE, DB by row, variable, column, variable
+#define KKT_WAVES 4 // waves of a k_kkt_rows / k_kkt_cols workgroup: a row (a column) each
+struct KktArgs {
+  const KktNode *nodes; // [count]
+  const double *At;     // [n+1][ldm]: At[j*ldm + i] = a_(i+1),j
+  const double *Ar;     // [m0][ldn]: Ar[i*ldn + j] = a_(i+1),j
+  const double *c0;     // [n+1] the root's objective
+  double *x, *du, *lo, *up, *res;
+  int *st;
+  double *term[8];
+  double *val; // [count][8]
+  int *ind;    // [count][8]
+  int n, m0, ldm, ldn, count, mmax; // mmax: the most rows of a handle
+};
+
 // one handle of a rounding launch (k_round, mvx_round_many)
 using RndNode = NodeRef;
 
@@ -614,6 +643,7 @@ void launch_gmi(const GmiArgs &a, hipStream_t);
 void launch_classify(const ClsArgs &a, hipStream_t);
 void launch_penalty(const PenArgs &a, hipStream_t);
 void launch_ranges(const RangeArgs &a, hipStream_t);
+void launch_kkt(const KktArgs &a, hipStream_t);
 void launch_round(const RndArgs &a, hipStream_t);
 void launch_rcfix(const RcArgs &a, hipStream_t);
 void launch_prop(const PropArgs &a, hipStream_t);

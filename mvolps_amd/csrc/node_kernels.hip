@@ -1,6 +1,6 @@
 // node_kernels.hip -- gfx950 kernels of the batched node entries of branch and bound (engine.cpp: engine_*_many): GMI cuts,
 // classification, branching penalties, sensitivity ranges, the rounding heuristic, reduced-cost tightening, bound propagation, bound lists, the
-// diving pick, objective replacement, the feasibility pump's step, the scores and the batched append of a cut round, the clique separation of a window, and the append, pricing and deletion of columns.  Each takes its arguments by value and the handles it works on as an array of descriptors (NodeRef and what
+// diving pick, objective replacement, the feasibility pump's step, the scores and the batched append of a cut round, the clique separation of a window, the KKT check, and the append, pricing and deletion of columns.  Each takes its arguments by value and the handles it works on as an array of descriptors (NodeRef and what
 // the kernel needs beyond it, mvx_internal.hpp).  Same flags as kernels.hip: -ffp-contract=off, so every kernel has the bits
 // of its host twin.
 #include <hip/hip_runtime.h>
@@ -539,6 +539,186 @@ void launch_ranges(const RangeArgs &a, hipStream_t s) {
   hipLaunchKernelGGL(k_rangecols, dim3((unsigned)((a.n + 63) / 64), (unsigned)a.nchunks), dim3(256), 0, s, a);
   hipLaunchKernelGGL(k_rangefin, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
   hipLaunchKernelGGL(k_rangerows, dim3((unsigned)a.nd.m), dim3(256), 0, s, a);
+}
+
+// ---------------------------------------------------------------------------- k_kkt_vals / k_kkt_rows / k_kkt_cols / k_kkt_fin
+// KKT check of solved handles against the model (mvx_kkt_many, DESIGN.md "KKT check (kkt)").  Four launches over all handles:
+//  1. k_kkt_vals, a thread per (handle, tableau row and non-basic position): value, dual, bounds and status of every variable
+//     k = 1..m+n out of the slab -- column 0 and the row bounds where k is basic, the bound its status names, row 0 and the
+//     position bounds where it is not: node_col_values' selection, for the auxiliaries too and spread over workgroups -- into
+//     the handle's slice of the by-variable arrays.  Selections only: the getters' bits;
+//  2. k_kkt_rows, a wave per (handle, row i): s_i = sum_j a_ij xS_j in 64 chains, lane l taking j = l+1, l+65, ... ascending
+//     with fma from +0.0 over a coalesced row of Ar (or of the handle's uploaded cut row), the chains combined by the halving
+//     tree s[l] += s[l+h], h = 32 .. 1, through __shfl_xor (lanes >= h compute sums nobody reads).  Lane 0 writes r_i, the
+//     row's PE terms and the PB and DB terms of auxiliary i;
+//  3. k_kkt_cols, a wave per (handle, column j): t_j = sum_i a_ij lambda_i the same way over a column of At and then the cut
+//     rows; lane 0 writes r_j, the DE terms and the PB and DB terms of structural j;
+//  4. k_kkt_fin, a workgroup per (handle, maximum): a strict compare in ascending index order per thread, combined with
+//     "larger wins, equal goes to the lower index" -- exact, so the order of the combination is free.
+// No atomics, no LDS beyond k_kkt_fin's wave partials, nothing waits on another workgroup.  Quotients are correctly rounded (xdiv).
+__global__ __launch_bounds__(256) void k_kkt_vals(KktArgs a) {
+  const KktNode nd = a.nodes[blockIdx.y];
+  const int m = nd.m, n = a.n;
+  double *x = a.x + nd.voff, *du = a.du + nd.voff, *lo = a.lo + nd.voff, *up = a.up + nd.voff;
+  int *st = a.st + nd.voff;
+  const int g = (int)blockIdx.x * 256 + TIDX + 1; // tableau row g and non-basic position g
+  if (g <= m) {
+    const int k = nd.bvar[g];
+    if (k >= 1 && k <= m + n) {
+      x[k] = nd.T[(size_t)g * (size_t)nd.ld];
+      du[k] = 0.0;
+      lo[k] = nd.blb[g];
+      up[k] = nd.bub[g];
+      st[k] = MVX_BS;
+    }
+  }
+  if (g <= n) {
+    const int k = nd.nvar[g];
+    if (k >= 1 && k <= m + n) {
+      const int f = nd.nflag[g];
+      const double l = nd.nlb[g], u = nd.nub[g];
+      x[k] = dev_nb_value(f, l, u);
+      du[k] = nd.T[g];
+      lo[k] = l;
+      up[k] = u;
+      st[k] = f;
+    }
+  }
+}
+
+// the PB and DB terms of the variable at offset o of the by-variable arrays
+__device__ __forceinline__ void kkt_var_terms(const KktArgs &a, size_t o, double sg) {
+  const double x = a.x[o], l = a.lo[o], u = a.up[o], d = a.du[o];
+  double ae = 0.0, re = 0.0;
+  if (fabs(l) != INFINITY && x < l) {
+    ae = l - x;
+    re = xdiv(ae, 1.0 + fabs(l));
+  } else if (fabs(u) != INFINITY && x > u) {
+    ae = x - u;
+    re = xdiv(ae, 1.0 + fabs(u));
+  }
+  a.term[2][o] = ae;
+  a.term[3][o] = re;
+  const int s = a.st[o];
+  const double e = sg * d;
+  double v;
+  if (s == MVX_NL) v = -e > 0.0 ? -e : 0.0;
+  else if (s == MVX_NU) v = e > 0.0 ? e : 0.0;
+  else if (s == MVX_NF) v = fabs(e);
+  else if (s == MVX_NS) v = 0.0;
+  else v = fabs(d);
+  a.term[6][o] = v;
+  a.term[7][o] = xdiv(v, 1.0 + fabs(d));
+}
+
+__global__ __launch_bounds__(64 * KKT_WAVES) void k_kkt_rows(KktArgs a) {
+  const KktNode nd = a.nodes[blockIdx.y];
+  const int lane = TIDX & 63, i = (int)blockIdx.x * KKT_WAVES + (TIDX >> 6) + 1;
+  if (i > nd.m) return;
+  const int n = a.n;
+  const double *__restrict__ row = i <= a.m0 ? a.Ar + (size_t)(i - 1) * (size_t)a.ldn : nd.cuts + (size_t)(i - a.m0 - 1) * (size_t)(n + 1);
+  const double *__restrict__ xs = a.x + nd.voff + (size_t)nd.m;
+  double acc = 0.0;
+#pragma unroll 4
+  for (int j = lane + 1; j <= n; j += 64) acc = fma(row[j], xs[j], acc);
+  for (int h = 32; h >= 1; h >>= 1) acc = acc + __shfl_xor(acc, h);
+  if (lane != 0) return;
+  const size_t o = nd.voff + (size_t)i;
+  const double xr = a.x[o];
+  const double r = xr - acc, ae = fabs(r);
+  a.res[o] = r;
+  a.term[0][o] = ae;
+  a.term[1][o] = xdiv(ae, 1.0 + fabs(xr));
+  kkt_var_terms(a, o, nd.sg);
+}
+
+__global__ __launch_bounds__(64 * KKT_WAVES) void k_kkt_cols(KktArgs a) {
+  const KktNode nd = a.nodes[blockIdx.y];
+  const int lane = TIDX & 63, j = (int)blockIdx.x * KKT_WAVES + (TIDX >> 6) + 1;
+  const int n = a.n, m = nd.m, m0 = a.m0;
+  if (j > n) return;
+  const double *__restrict__ col = a.At + (size_t)j * (size_t)a.ldm;
+  const double *__restrict__ lam = a.du + nd.voff;
+  double acc = 0.0;
+  int i = lane + 1;
+#pragma unroll 4
+  for (; i <= m0; i += 64) acc = fma(col[i - 1], lam[i], acc);
+  for (; i <= m; i += 64) acc = fma(nd.cuts[(size_t)(i - m0 - 1) * (size_t)(n + 1) + (size_t)j], lam[i], acc);
+  for (int h = 32; h >= 1; h >>= 1) acc = acc + __shfl_xor(acc, h);
+  if (lane != 0) return;
+  const size_t o = nd.voff + (size_t)m + (size_t)j;
+  const double cj = nd.c ? nd.c[j] : a.c0[j];
+  const double r = (cj - acc) - a.du[o], ae = fabs(r);
+  a.res[o] = r;
+  a.term[4][o] = ae;
+  a.term[5][o] = xdiv(ae, 1.0 + fabs(cj));
+  kkt_var_terms(a, o, nd.sg);
+}
+
+__global__ __launch_bounds__(256) void k_kkt_fin(KktArgs a) {
+  __shared__ double s_v[4];
+  __shared__ int s_i[4];
+  const KktNode nd = a.nodes[blockIdx.y];
+  const int m = nd.m, n = a.n, lane = TIDX & 63, wave = TIDX >> 6;
+  const int t = (int)blockIdx.x, c = t >> 1;
+  // PE rows 1..m, PB / DB variables 1..m+n, DE columns 1..n (stored behind the rows)
+  const int cnt = c == 0 ? m : c == 2 ? n : m + n;
+  const double *__restrict__ v = a.term[t] + nd.voff + (size_t)(c == 2 ? m : 0);
+  double best = 0.0;
+  int bi = 0;
+  int k = 1 + TIDX;
+  for (; k + 768 <= cnt; k += 1024) { // four loads in flight, seen in ascending order
+    const double w0 = v[k], w1 = v[k + 256], w2 = v[k + 512], w3 = v[k + 768];
+    if (w0 > best) { best = w0; bi = k; }
+    if (w1 > best) { best = w1; bi = k + 256; }
+    if (w2 > best) { best = w2; bi = k + 512; }
+    if (w3 > best) { best = w3; bi = k + 768; }
+  }
+  for (; k <= cnt; k += 256) {
+    const double w = v[k];
+    if (w > best) {
+      best = w;
+      bi = k;
+    }
+  }
+  for (int h = 32; h >= 1; h >>= 1) {
+    const double w = __shfl_xor(best, h);
+    const int wi = __shfl_xor(bi, h);
+    if (w > best || (w == best && wi < bi)) {
+      best = w;
+      bi = wi;
+    }
+  }
+  if (lane == 0) {
+    s_v[wave] = best;
+    s_i[wave] = bi;
+  }
+  __syncthreads();
+  if (TIDX == 0) {
+    for (int w = 1; w < 4; w++)
+      if (s_v[w] > best || (s_v[w] == best && s_i[w] < bi)) {
+        best = s_v[w];
+        bi = s_i[w];
+      }
+    a.val[(size_t)blockIdx.y * 8 + t] = best;
+    a.ind[(size_t)blockIdx.y * 8 + t] = bi;
+  }
+}
+
+void launch_kkt(const KktArgs &a0, hipStream_t s) {
+  for (int t0 = 0; t0 < a0.count; t0 += 32768) { // the handles ride on grid.y
+    KktArgs a = a0;
+    a.nodes += t0;
+    a.val += (size_t)t0 * 8;
+    a.ind += (size_t)t0 * 8;
+    a.count = a0.count - t0 < 32768 ? a0.count - t0 : 32768;
+    const unsigned cnt = (unsigned)a.count;
+    const int longest = a.mmax > a.n ? a.mmax : a.n;
+    hipLaunchKernelGGL(k_kkt_vals, dim3((unsigned)((longest + 255) / 256), cnt), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_kkt_rows, dim3((unsigned)((a.mmax + KKT_WAVES - 1) / KKT_WAVES), cnt), dim3(64 * KKT_WAVES), 0, s, a);
+    hipLaunchKernelGGL(k_kkt_cols, dim3((unsigned)((a.n + KKT_WAVES - 1) / KKT_WAVES), cnt), dim3(64 * KKT_WAVES), 0, s, a);
+    hipLaunchKernelGGL(k_kkt_fin, dim3(8, cnt), dim3(256), 0, s, a);
+  }
 }
 
 // ---------------------------------------------------------------------------- k_round
