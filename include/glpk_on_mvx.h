@@ -83,6 +83,7 @@ typedef mvx_smcp glp_smcp;
 #define glp_get_mat_col mvx_get_mat_col   /* (model readers by columns) */
 #define glp_get_obj_dir mvx_get_obj_dir   /* util.cpp:51 */
 #define glp_eval_tab_row mvx_eval_tab_row /* gmi.cpp:36 */
+#define glp_get_unbnd_ray mvx_get_unbnd_ray /* (ray of unboundedness; MVOLPS never calls it) */
 #define glp_check_kkt mvx_check_kkt       /* (solution checking; MVOLPS never calls it) sol = GLP_SOL, cond = GLP_KKT_* */
 #define GLP_SOL 1
 #define GLP_KKT_PE MVX_KKT_PE

@@ -223,6 +223,36 @@ int mvx_kkt(const mvx_prob *P, double *val, int *ind, double *r_pe, double *r_de
 #define MVX_KKT_DE 3
 #define MVX_KKT_DB 4
 int mvx_check_kkt(const mvx_prob *P, int sol, int cond, double *ae_max, int *ae_ind, double *re_max, int *re_ind);
+/* Farkas proof (DESIGN.md "Infeasibility and unboundedness proofs (farkas)") of `count` handles against their own models, in one
+   device call: is there a weight vector y over the rows for which sum_r y_r (xR_r - a_r xS) -- zero at every feasible point --
+   cannot reach zero inside the bounds?  Every tableau row of a handle is tried as a suggestion (one pass over the slab), the best
+   one is evaluated on the model (rows 1..m0 from root's device copy, cut rows from the call's upload).  val[4 t ..] holds rel of
+   the tableau side, rel of the model side, the model side's Lo or -Hi, and de, the largest relative distance between the
+   tableau's and the model's structural coefficients; ind[4 t ..] holds found (0 none, 1 the tableau row only, 2 proved on the
+   model), the tableau row, the side (1 lower, 2 upper) and the coefficients the model side dropped under the zero rule; all zero
+   when found = 0, as for every MVX_OPT or MVX_FEAS handle.  Handles are related to root as in mvx_kkt_many.  Pure: no handle is
+   changed.  Bit-identical to mvx_bnb_farkas (mvx_bnb.h).  Returns 0 (count == 0 does nothing); -1 bad arguments (a null,
+   count < 0, differing column counts); -2 device out of memory, nothing written; -3 a handle that is MVX_UNDEF or has no
+   tableau, or one that does not share root's rows. */
+int mvx_farkas_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, double *val, int *ind);
+/* The same for one handle against itself; y[0..m] (may be NULL) receives the row weights, entry 0 zero. */
+int mvx_farkas(const mvx_prob *P, double *val, int *ind, double *y);
+/* The ray that proves a handle unbounded (same section of DESIGN.md), a pure function of the end state: the lowest non-basic
+   position q whose status allows a direction sigma (+1 up, -1 down) in which the published dual of N(q) improves the objective by
+   more than 1e-9 in the LP's own sense, whose own bound on that side is infinite and for which every basic variable, moving by
+   sigma alpha_iq, has that side infinite or |alpha_iq| <= 1e-9.  The ray is d_N(q) = sigma, d_B(i) = sigma alpha_iq, 0 elsewhere.
+   It is checked on the model: rho_r = dR_r - sum_j a_rj dS_j (ae = |rho_r|, re = ae / (1 + |dR_r|), as PE of mvx_kkt_many), the
+   slope sum_j c_j dS_j, and the variables with |d_k| > 1e-9 whose bound on the side d_k points to is finite.  val[4] = the dual,
+   ae_max, re_max, the slope; ind[6] = found, the variable N(q) (k = 1..m+n, auxiliaries first), sigma, the blocking variables,
+   the rows of ae_max and re_max (the lowest among equals, 0 for a zero maximum); found = 2 when the slope improves the objective,
+   re_max <= 1e-9 and nothing blocks, 1 when only the tableau side holds, 0 (everything zero) when there is no such position.
+   d[0..m+n] (may be NULL) receives the ray, entry 0 zero.  Pure: the handle is not changed.  Bit-identical to mvx_bnb_ray
+   (mvx_bnb.h).  Returns 0; -1 a null argument; -2 device out of memory, nothing written; -3 a handle that is MVX_UNDEF or has no
+   tableau. */
+int mvx_ray(const mvx_prob *P, double *val, int *ind, double *d);
+/* glp_get_unbnd_ray's shape [GLPK-recalled]: the variable k = 1..m+n whose move mvx_ray finds (found >= 1) when the handle's
+   status is MVX_UNBND; 0 for any other status, or when none is found. */
+int mvx_get_unbnd_ray(const mvx_prob *P);
 /* Primal rounding heuristic (DESIGN.md "Primal rounding heuristic") on `count` solved handles, one device launch: each
    handle's column values rounded (mode 1) and filled greedily (mode 2), checked against the model of `root` -- its rows
    1..m0 (m0 = root's row count; rows a handle has beyond them, cut rows, are ignored), row bounds, column bounds and

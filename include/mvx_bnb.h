@@ -145,6 +145,10 @@ typedef struct mvx_lp_api {
   /* optional (may be NULL): the KKT check of `count` solved handles against the rows of `root` in one call (mvx_kkt_many; DESIGN.md
      "KKT check (kkt)"): val / ind take 8 entries per handle; without it the host twin mvx_bnb_kkt runs handle by handle */
   int (*kkt_many)(const void *root, const void *const *Ps, int count, double *val, int *ind);
+  /* optional (may be NULL): the Farkas proof of `count` handles against the rows of `root` in one call (mvx_farkas_many; DESIGN.md
+     "Infeasibility and unboundedness proofs (farkas)"): val / ind take 4 entries per handle; without it the host twin
+     mvx_bnb_farkas runs handle by handle */
+  int (*farkas_many)(const void *root, const void *const *Ps, int count, double *val, int *ind);
 } mvx_lp_api;
 
 const mvx_lp_api *mvx_hip_lp_api(void);
@@ -241,6 +245,11 @@ typedef struct {
                            relative errors go to kkt_re / kkt_oid.  Pure observation: the tree, oids, events, pivots, incumbent
                            and every other counter are those of kkt = 0, and the booked values do not depend on the window.  Outside 0..1: refused; 1 needs best_window = 0; allowed
                            in both quirk modes */
+  int farkas;           /* Farkas proof (DESIGN.md "Infeasibility and unboundedness proofs (farkas)"): 0 (default) off; 1: every node LP
+                           that ends MVX_NOFEAS is asked for a proof of its infeasibility on the model, a window round's nodes in one
+                           farkas_many call; the farkas_* members of the result count what was proved.  Pure observation: the tree,
+                           oids, events, pivots, incumbent and every other counter are those of farkas = 0, and the booked values do
+                           not depend on the window.  Outside 0..1: refused; 1 needs best_window = 0; allowed in both quirk modes */
 } mvx_bnb_params;
 
 /* B&B events at the emit points of bs.cpp (message.h EventType) */
@@ -324,6 +333,15 @@ typedef struct {
   long long kkt_nodes;             /* kkt = 1: node LPs checked (every node the tree solved) */
   double kkt_re[4];                /* ... the worst re_max over them per condition: PE, PB, DE, DB */
   int kkt_oid[4];                  /* ... the lowest oid at which each worst value occurred, 0 while it is 0 */
+  long long farkas_nodes;          /* farkas = 1: node LPs that ended MVX_NOFEAS, each asked for a proof */
+  long long farkas_proved;         /* ... found = 2: the proof holds on the model */
+  long long farkas_tableau_only;   /* ... found = 1: a tableau row proves, the model does not confirm it */
+  long long farkas_none;           /* ... found = 0: no tableau row proves */
+  long long farkas_dropped;        /* ... nodes with found > 0 whose model side dropped a coefficient under the zero rule */
+  double farkas_rel_min;           /* ... the smallest model-side rel among the proved nodes, 0 while there is none */
+  double farkas_de_max;            /* ... the largest de among the nodes with found > 0 */
+  int farkas_rel_oid;              /* ... the lowest oid of farkas_rel_min, 0 while there is none */
+  int farkas_de_oid;               /* ... the lowest oid of farkas_de_max, 0 while it is 0 */
 } mvx_bnb_result;
 
 void mvx_bnb_default_params(mvx_bnb_params *p);
@@ -396,6 +414,27 @@ int mvx_bnb_kkt_values(int m, int n, const double *rows, const double *c, const 
    needs (or one failed); -3 the handle is MVX_UNDEF.  mvx_branchAndBound returns -1 (*res empty) for kkt outside 0..1 and kkt = 1
    with best_window > 0, and -2, with the tree so far, when a check could not be carried out */
 int mvx_bnb_kkt(const mvx_lp_api *api, const void *prob, double *val, int *ind, double *r_pe, double *r_de);
+
+/* Farkas proof (DESIGN.md "Infeasibility and unboundedness proofs (farkas)") from numbers only: T (m+1) x (n+1) the tableau as
+   get_tableau packs it, T[i (n+1) + q] = alpha_iq of mvx_eval_tab_row (row 0 and column 0 are not read), head[0..m] the basic
+   variable of each row, nb[0..n] the variable at each non-basic position, rows m x (n+1) dense by row (entry 0 of each unused),
+   lb / ub [0..m+n] by variable number, auxiliaries first (+-inf for an absent bound).  val[4] = rel of the tableau side, rel of the
+   model side, the model side's Lo or -Hi, de; ind[4] = found (0 none, 1 the tableau row only, 2 proved on the model), the row,
+   the side (1 lower, 2 upper), the coefficients the model side dropped; all zero when found = 0.  y[0..m] (nullable) the row
+   weights, entry 0 zero.  Returns 0; -1 bad arguments (m < 1, n < 1, a null) */
+int mvx_bnb_farkas_values(int m, int n, const double *T, const int *head, const int *nb, const double *rows, const double *lb,
+                          const double *ub, double *val, int *ind, double *y);
+/* Host twin of mvx_farkas for one handle, through the table only (get_mat_row, row and column bounds, get_tableau, get_basis,
+   get_status, get_num_rows, get_num_cols); the handle is not changed.  The same bits as mvx_farkas.  Returns 0; -1 a null
+   argument; -2 the table lacks an accessor it needs (or one failed); -3 the handle is MVX_UNDEF.  mvx_branchAndBound returns -1
+   (*res empty) for farkas outside 0..1 and farkas = 1 with best_window > 0, and -2, with the tree so far, when a proof could not
+   be asked for */
+int mvx_bnb_farkas(const mvx_lp_api *api, const void *prob, double *val, int *ind, double *y);
+/* Host twin of mvx_ray (mvx.h) for one handle, through the table only (get_mat_row, get_obj_coef, get_obj_dir, row and column
+   bounds, get_tableau, get_basis, get_status, get_num_rows, get_num_cols): val[4], ind[6] and d[0..m+n] (nullable) as mvx_ray
+   gives them, the same bits; the handle is not changed.  Returns 0; -1 a null argument; -2 the table lacks an accessor it needs
+   (or one failed); -3 the handle is MVX_UNDEF */
+int mvx_bnb_ray(const mvx_lp_api *api, const void *prob, double *val, int *ind, double *d);
 
 /* Column append (DESIGN.md "Column append (add_cols)"), host twin of mvx_price_cols: the images of `k` candidate columns against
    the tableau of `prob` -- cols k x (m+1) by model row, obj[k]; dj[t] row 0 of image t, img (nullable) k x (m+1) by tableau row.

@@ -28,20 +28,24 @@ _TABLE_TAIL = ["clique_cuts_many", "add_cut_rows_many"]
 # ... and behind that tail: a further list per class (_more_), reached by name in the same way, so that `_tail_` keeps the
 # members it had; `_full_` covers the fields, the tail and this list -- the whole C struct
 _TABLE_MORE = ["kkt_many"]
+# ... and behind that one, in the same way (_extra_): members later changes append, so that `_more_` keeps the members it had
+_TABLE_EXTRA = ["farkas_many"]
 
 
-def _with_tail(cls, tail, more=()):
-    """Gives cls the layout of the whole C struct (its own fields, then `tail`, then `more`) for allocation and for access by name."""
-    cls._full_ = type(cls.__name__ + "Whole", (C.Structure,), {"_fields_": list(cls._fields_) + list(tail) + list(more)})
+def _with_tail(cls, tail, more=(), extra=()):
+    """Gives cls the layout of the whole C struct (its own fields, then `tail`, `more` and `extra`) for allocation and for access by
+    name."""
+    cls._full_ = type(cls.__name__ + "Whole", (C.Structure,), {"_fields_": list(cls._fields_) + list(tail) + list(more) + list(extra)})
     cls._tail_ = {name: (getattr(cls._full_, name).offset, ctype) for name, ctype in tail}
     cls._more_ = {name: (getattr(cls._full_, name).offset, ctype) for name, ctype in more}
+    cls._extra_ = {name: (getattr(cls._full_, name).offset, ctype) for name, ctype in extra}
     for name, ctype in cls._fields_:  # the listed fields sit where the C struct has them
         assert getattr(cls, name).offset == getattr(cls._full_, name).offset
 
 
 def _behind(obj, name):
     cls = type(obj)
-    return cls._tail_[name] if name in cls._tail_ else cls._more_[name]
+    return cls._tail_[name] if name in cls._tail_ else cls._more_[name] if name in cls._more_ else cls._extra_[name]
 
 
 def tail_get(obj, name):
@@ -70,16 +74,17 @@ class LpApiTable(_WholeStruct):
     _fields_ = [(name, C.c_void_p) for name in _FIELDS + _OPTIONAL]
 
 
-_with_tail(LpApiTable, [(name, C.c_void_p) for name in _TABLE_TAIL], [(name, C.c_void_p) for name in _TABLE_MORE])
+_with_tail(LpApiTable, [(name, C.c_void_p) for name in _TABLE_TAIL], [(name, C.c_void_p) for name in _TABLE_MORE],
+           [(name, C.c_void_p) for name in _TABLE_EXTRA])
 
 
 def table_entry(table, name):
     """An entry of the table by name, appended ones (_TABLE_TAIL) included: its address, or None."""
-    return tail_get(table, name) if name in _TABLE_TAIL + _TABLE_MORE else getattr(table, name)
+    return tail_get(table, name) if name in _TABLE_TAIL + _TABLE_MORE + _TABLE_EXTRA else getattr(table, name)
 
 
 def set_table_entry(table, name, value):
-    if name in _TABLE_TAIL + _TABLE_MORE:
+    if name in _TABLE_TAIL + _TABLE_MORE + _TABLE_EXTRA:
         tail_set(table, name, value)
     else:
         setattr(table, name, value)
@@ -119,9 +124,10 @@ class BnbParams(_WholeStruct):
     ]
     node_cliques = _tail_attr("node_cliques")
     kkt = _tail_attr("kkt")
+    farkas = _tail_attr("farkas")
 
 
-_with_tail(BnbParams, [("node_cliques", C.c_int)], [("kkt", C.c_int)])
+_with_tail(BnbParams, [("node_cliques", C.c_int)], [("kkt", C.c_int)], [("farkas", C.c_int)])
 
 
 class BnbEvent(C.Structure):
@@ -203,14 +209,29 @@ class BnbResult(_WholeStruct):
     kkt_nodes = _tail_attr("kkt_nodes")
     kkt_re = _tail_attr("kkt_re")
     kkt_oid = _tail_attr("kkt_oid")
+    farkas_nodes = _tail_attr("farkas_nodes")
+    farkas_proved = _tail_attr("farkas_proved")
+    farkas_tableau_only = _tail_attr("farkas_tableau_only")
+    farkas_none = _tail_attr("farkas_none")
+    farkas_dropped = _tail_attr("farkas_dropped")
+    farkas_rel_min = _tail_attr("farkas_rel_min")
+    farkas_de_max = _tail_attr("farkas_de_max")
+    farkas_rel_oid = _tail_attr("farkas_rel_oid")
+    farkas_de_oid = _tail_attr("farkas_de_oid")
 
 
 NODE_CLIQUE_COUNTERS = ("node_clique_conflicts", "node_clique_calls", "node_clique_rows")
 # kkt = 1: node LPs checked; the worst re_max per condition (KKT_CONDS) over the tree, a list of 4; the lowest oid of each
 KKT_COUNTERS = ("kkt_nodes", "kkt_re", "kkt_oid")
 KKT_CONDS = ("PE", "PB", "DE", "DB")
+# farkas = 1: the node LPs that ended NOFEAS; those proved on the model (found = 2), by the tableau row only (1), not at all (0);
+# those whose model side dropped a coefficient; the smallest model-side rel among the proved and the largest de, with their oids
+FARKAS_COUNTERS = ("farkas_nodes", "farkas_proved", "farkas_tableau_only", "farkas_none", "farkas_dropped", "farkas_rel_min",
+                   "farkas_de_max", "farkas_rel_oid", "farkas_de_oid")
 _with_tail(BnbResult, [(name, C.c_longlong) for name in NODE_CLIQUE_COUNTERS],
-           [("kkt_nodes", C.c_longlong), ("kkt_re", C.c_double * 4), ("kkt_oid", C.c_int * 4)])
+           [("kkt_nodes", C.c_longlong), ("kkt_re", C.c_double * 4), ("kkt_oid", C.c_int * 4)],
+           [(name, C.c_longlong) for name in FARKAS_COUNTERS[:5]] + [(name, C.c_double) for name in FARKAS_COUNTERS[5:7]]
+           + [(name, C.c_int) for name in FARKAS_COUNTERS[7:]])
 
 
 def table_from(api):
@@ -219,7 +240,7 @@ def table_from(api):
     for name in _FIELDS:
         fn = getattr(api.lib, api.prefix + name)
         setattr(t, name, C.cast(fn, C.c_void_p).value)
-    for name in _OPTIONAL + _TABLE_TAIL + _TABLE_MORE:  # optional entries stay NULL when the library does not export them
+    for name in _OPTIONAL + _TABLE_TAIL + _TABLE_MORE + _TABLE_EXTRA:  # optional entries stay NULL when the library does not export them
         fn = getattr(api.lib, api.prefix + name, None) if hasattr(api.lib, api.prefix + name) else None
         set_table_entry(t, name, C.cast(fn, C.c_void_p).value if fn is not None else None)
     return t
@@ -334,6 +355,20 @@ def _bind(lib):
     lib.mvx_bnb_kkt.argtypes = [C.c_void_p, C.c_void_p, _DP, _IP, _DP, _DP]
     lib.mvx_bnb_kkt_values.restype = C.c_int
     lib.mvx_bnb_kkt_values.argtypes = [C.c_int, C.c_int, _DP, _DP, _DP, _DP, _DP, _DP, _DP, _DP, _IP, C.c_int, _DP, _IP, _DP, _DP]
+    lib.mvx_farkas_many.restype = C.c_int
+    lib.mvx_farkas_many.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, _DP, _IP]
+    lib.mvx_farkas.restype = C.c_int
+    lib.mvx_farkas.argtypes = [C.c_void_p, _DP, _IP, _DP]
+    lib.mvx_bnb_farkas.restype = C.c_int
+    lib.mvx_bnb_farkas.argtypes = [C.c_void_p, C.c_void_p, _DP, _IP, _DP]
+    lib.mvx_bnb_farkas_values.restype = C.c_int
+    lib.mvx_bnb_farkas_values.argtypes = [C.c_int, C.c_int, _DP, _IP, _IP, _DP, _DP, _DP, _DP, _IP, _DP]
+    lib.mvx_ray.restype = C.c_int
+    lib.mvx_ray.argtypes = [C.c_void_p, _DP, _IP, _DP]
+    lib.mvx_get_unbnd_ray.restype = C.c_int
+    lib.mvx_get_unbnd_ray.argtypes = [C.c_void_p]
+    lib.mvx_bnb_ray.restype = C.c_int
+    lib.mvx_bnb_ray.argtypes = [C.c_void_p, C.c_void_p, _DP, _IP, _DP]
     lib.mvx_ranges_chunk.restype = C.c_int
     lib.mvx_ranges_chunk.argtypes = []
     lib.mvx_bnb_ranges.restype = C.c_int
@@ -434,13 +469,15 @@ def result_to_dict(res):
         "kkt_nodes": res.kkt_nodes,
         "kkt_re": res.kkt_re,
         "kkt_oid": res.kkt_oid,
+        **{name: getattr(res, name) for name in FARKAS_COUNTERS},
     }
 
 
 def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, lazy_pool=1, window=None, cut_select=0, cut_chance=1.0,
                 best_window=None, sb_cands=None, sb_iters=None, heur=None, rc_fix=None, prop=None, dive=None, dive_freq=None,
                 dive_depth=None, pump=None, pump_freq=None, pump_alpha=None, cut_rounds=None, cut_round_max=None, cut_maxpar=None,
-                cut_families=None, cut_purge=None, polish=None, node_purge=None, node_cliques=None, kkt=None):
+                cut_families=None, cut_purge=None, polish=None, node_purge=None, node_cliques=None, kkt=None,
+                farkas=None):
     """mvx_bnb_params with ParameterObj's defaults (util.h:65-67) overridden by the arguments (None: the default)."""
     pr = BnbParams()
     lib().mvx_bnb_default_params(C.byref(pr))
@@ -491,6 +528,8 @@ def make_params(var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, quirks=1, l
         pr.node_cliques = node_cliques
     if kkt is not None:
         pr.kkt = kkt
+    if farkas is not None:
+        pr.farkas = farkas
     return pr
 
 
@@ -498,7 +537,7 @@ def branch_and_bound(prob, var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, 
                      cut_select=0, cut_chance=1.0, best_window=None, sb_cands=None, sb_iters=None, heur=None, rc_fix=None, prop=None,
                      dive=None, dive_freq=None, dive_depth=None, pump=None, pump_freq=None, pump_alpha=None, cut_rounds=None,
                      cut_round_max=None, cut_maxpar=None, cut_families=None, cut_purge=None, polish=None, node_purge=None,
-                     node_cliques=None, kkt=None):
+                     node_cliques=None, kkt=None, farkas=None):
     """Run the driver on `prob` (a capi.Prob).  table=None uses the gfx950 engine's own table.  best_window > 1 with
     node_strat=1: the speculative best-bound window (mvx_bnb_params.best_window).  var_strat 3 / 4: branching on the node
     LP's penalties / strong branching (sb_cands candidates, sb_iters pivots per child).  heur 1 / 2: the primal rounding
@@ -521,13 +560,15 @@ def branch_and_bound(prob, var_strat=0, node_strat=0, cut_strat=0, max_nodes=0, 
     node_cliques = K in 1..64: up to K violated cliques of the model's conflict graph are separated at every branching node and
     appended to both children (quirks=0, not with best_window; NODE_CLIQUE_COUNTERS in the dictionary).  kkt = 1: every node LP the
     tree solves is checked against the model (DESIGN.md "KKT check (kkt)"), pure observation, in both quirk modes, not with
-    best_window; KKT_COUNTERS in the dictionary.  The
+    best_window; KKT_COUNTERS in the dictionary.  farkas = 1: every node LP that ends NOFEAS is asked for a proof of its
+    infeasibility on the model (DESIGN.md "Infeasibility and unboundedness proofs (farkas)"), pure observation, in both quirk modes,
+    not with best_window; FARKAS_COUNTERS in the dictionary.  The
     dictionary's "rc" is mvx_branchAndBound's return code (-1 refused parameters, -2 penalties, heuristic, tightening,
     propagation, pumps or dives unavailable)."""
     L = lib()
     pr = make_params(var_strat, node_strat, cut_strat, max_nodes, quirks, lazy_pool, window, cut_select, cut_chance, best_window, sb_cands,
                      sb_iters, heur, rc_fix, prop, dive, dive_freq, dive_depth, pump, pump_freq, pump_alpha, cut_rounds, cut_round_max,
-                     cut_maxpar, cut_families, cut_purge, polish, node_purge, node_cliques, kkt)
+                     cut_maxpar, cut_families, cut_purge, polish, node_purge, node_cliques, kkt, farkas)
     res = BnbResult()
     tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
     rc = L.mvx_branchAndBound(tptr, prob.h, C.byref(pr), C.byref(res))
@@ -854,6 +895,94 @@ def kkt_values(rows, c, xs, xr, lam, dj, lb, ub, stat, direction=capi.MAX):
     rc = lib().mvx_bnb_kkt_values(m, n, R.ctypes.data_as(DP), *[a.ctypes.data_as(DP) for a in args], st.ctypes.data_as(IP), int(direction),
                                   val.ctypes.data_as(DP), ind.ctypes.data_as(IP), r_pe.ctypes.data_as(DP), r_de.ctypes.data_as(DP))
     return rc, val, ind, r_pe, r_de
+
+
+def farkas(prob, table=False, weights=True):
+    """Farkas proof of one handle (DESIGN.md "Infeasibility and unboundedness proofs (farkas)"): (rc, val[4], ind[4], y[0..m]); val
+    holds rel of the tableau side, rel of the model side, the model side's Lo or -Hi, and de; ind holds found (0 / 1 / 2), the
+    tableau row, the side (1 lower, 2 upper) and the coefficients the model side dropped; y (None with weights=False) the row
+    weights.  table=False: mvx_farkas, the gfx950 engine's kernels.  Otherwise the host twin mvx_bnb_farkas through `table` (None:
+    the engine's own table) -- the same bits."""
+    import numpy as np
+
+    DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    val, ind = np.zeros(4, dtype=np.float64), np.zeros(4, dtype=np.int32)
+    y = np.zeros(prob.m + 1, dtype=np.float64) if weights else None
+    yp = y.ctypes.data_as(DP) if weights else None
+    if table is False:
+        rc = lib().mvx_farkas(prob.h, val.ctypes.data_as(DP), ind.ctypes.data_as(IP), yp)
+    else:
+        tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
+        rc = lib().mvx_bnb_farkas(tptr, prob.h, val.ctypes.data_as(DP), ind.ctypes.data_as(IP), yp)
+    return rc, val, ind, y
+
+
+def farkas_many(root, nodes, table=False):
+    """Farkas proofs of the handles `nodes` over the rows of `root`: (rc, val (count, 4), ind (count, 4)).  table=False:
+    mvx_farkas_many, one device call for all of them.  Otherwise the host twin mvx_bnb_farkas handle by handle through `table`; rc
+    is then the first failing call's."""
+    import numpy as np
+
+    DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    count = len(nodes)
+    val, ind = np.zeros((count, 4), dtype=np.float64), np.zeros((count, 4), dtype=np.int32)
+    if table is False:
+        hs = (C.c_void_p * max(1, count))(*[p.h for p in nodes])
+        return lib().mvx_farkas_many(root.h, hs, count, val.ctypes.data_as(DP), ind.ctypes.data_as(IP)), val, ind
+    tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
+    for t, p in enumerate(nodes):
+        rc = lib().mvx_bnb_farkas(tptr, p.h, val[t].ctypes.data_as(DP), ind[t].ctypes.data_as(IP), None)
+        if rc != 0:
+            return rc, val, ind
+    return 0, val, ind
+
+
+def farkas_values(T, head, nb, rows, lb, ub):
+    """mvx_bnb_farkas_values, the proof from numbers only: T (m, n) the tableau in eval_tab_row's convention (row i of T the
+    coefficients of the basic variable head[i] on the non-basic variables nb[0..n-1]), rows (m, n) the dense model rows, lb / ub
+    (m + n,) by variable with the auxiliaries first (+-inf for an absent bound).  Returns (rc, val[4], ind[4], y[0..m])."""
+    import numpy as np
+
+    DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    rows = np.asarray(rows, dtype=np.float64)
+    m, n = rows.shape
+    T = np.asarray(T, dtype=np.float64)
+    assert T.shape == (m, n), (T.shape, m, n)
+
+    def lead(v, k, dtype=np.float64):  # the C layout: entry 0 unused
+        v = np.asarray(v, dtype=dtype)
+        assert v.shape == (k,), (v.shape, k)
+        return np.ascontiguousarray(np.concatenate([np.zeros(1, dtype=dtype), v]))
+
+    R = np.ascontiguousarray(np.hstack([np.zeros((m, 1)), rows]))
+    Tp = np.zeros((m + 1, n + 1))
+    Tp[1:, 1:] = T
+    hd, nbp, lo, up = lead(head, m, np.int32), lead(nb, n, np.int32), lead(lb, m + n), lead(ub, m + n)
+    val, ind, y = np.zeros(4, dtype=np.float64), np.zeros(4, dtype=np.int32), np.zeros(m + 1, dtype=np.float64)
+    rc = lib().mvx_bnb_farkas_values(m, n, Tp.ctypes.data_as(DP), hd.ctypes.data_as(IP), nbp.ctypes.data_as(IP), R.ctypes.data_as(DP),
+                                     lo.ctypes.data_as(DP), up.ctypes.data_as(DP), val.ctypes.data_as(DP), ind.ctypes.data_as(IP),
+                                     y.ctypes.data_as(DP))
+    return rc, val, ind, y
+
+
+def ray(prob, table=False, direction=True):
+    """The ray that proves a handle unbounded (DESIGN.md "Infeasibility and unboundedness proofs (farkas)"): (rc, val[4], ind[6],
+    d[0..m+n]); val holds the dual, ae_max, re_max and the slope, ind found (0 / 1 / 2), the variable, the direction, the blocking
+    variables and the rows of ae_max and re_max; d (None with direction=False) the ray by variable.  table=False: mvx_ray, the
+    gfx950 engine's kernels.  Otherwise the host twin mvx_bnb_ray through `table` (None: the engine's own table) -- the same
+    bits."""
+    import numpy as np
+
+    DP, IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    val, ind = np.zeros(4, dtype=np.float64), np.zeros(6, dtype=np.int32)
+    d = np.zeros(prob.m + prob.n + 1, dtype=np.float64) if direction else None
+    dp = d.ctypes.data_as(DP) if direction else None
+    if table is False:
+        rc = lib().mvx_ray(prob.h, val.ctypes.data_as(DP), ind.ctypes.data_as(IP), dp)
+    else:
+        tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
+        rc = lib().mvx_bnb_ray(tptr, prob.h, val.ctypes.data_as(DP), ind.ctypes.data_as(IP), dp)
+    return rc, val, ind, d
 
 
 def ranges_chunk():

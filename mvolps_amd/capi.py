@@ -352,6 +352,31 @@ class Prob:
         rc = self.api.kkt(self.h, _dp(val), _ip(ind), _dp(r_pe) if residuals else None, _dp(r_de) if residuals else None)
         return rc, val, ind, r_pe, r_de
 
+    def farkas(self, weights=True):
+        """mvx_farkas (the gfx950 engine's library only): a proof that the handle's LP is infeasible, evaluated on its own model.
+        Returns (rc, val, ind, y): val[4] = rel of the tableau side, rel of the model side, the model side's Lo or -Hi, de; ind[4] =
+        found (0 none, 1 the tableau row only, 2 proved on the model), the row, the side, the dropped coefficients; y[0..m] the row
+        weights (None with weights=False)."""
+        val = np.zeros(4, dtype=np.float64)
+        ind = np.zeros(4, dtype=np.int32)
+        y = np.zeros(self.m + 1, dtype=np.float64) if weights else None
+        rc = self.api.farkas(self.h, _dp(val), _ip(ind), _dp(y) if weights else None)
+        return rc, val, ind, y
+
+    def ray(self, direction=True):
+        """mvx_ray (the gfx950 engine's library only): the ray that proves the handle unbounded, checked on its own model.  Returns
+        (rc, val, ind, d): val[4] = the dual, ae_max, re_max, the slope; ind[6] = found (0 / 1 / 2), the variable, the direction,
+        the blocking variables, the rows of ae_max and re_max; d[0..m+n] the ray by variable (None with direction=False)."""
+        val = np.zeros(4, dtype=np.float64)
+        ind = np.zeros(6, dtype=np.int32)
+        d = np.zeros(self.m + self.n + 1, dtype=np.float64) if direction else None
+        rc = self.api.ray(self.h, _dp(val), _ip(ind), _dp(d) if direction else None)
+        return rc, val, ind, d
+
+    def get_unbnd_ray(self):
+        """mvx_get_unbnd_ray, glp_get_unbnd_ray's shape: the variable whose move proves MVX_UNBND, 0 otherwise."""
+        return self.api.get_unbnd_ray(self.h)
+
     def check_kkt(self, cond, sol=1):
         """mvx_check_kkt, glp_check_kkt's shape: (rc, ae_max, ae_ind, re_max, re_ind) of condition cond = 1 PE, 2 PB, 3 DE, 4 DB."""
         ae, re = C.c_double(0.0), C.c_double(0.0)

@@ -62,6 +62,7 @@ extern "C" int mvx_clique_cuts_many(const mvx_prob *root, const mvx_prob *const 
 extern "C" int mvx_add_cut_rows_many(mvx_prob *const *Ps, int count, const int *off, const double *vals, const double *rhs)
     __attribute__((weak));
 extern "C" int mvx_kkt_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, double *val, int *ind) __attribute__((weak));
+extern "C" int mvx_farkas_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, double *val, int *ind) __attribute__((weak));
 
 namespace {
 
@@ -1222,6 +1223,288 @@ private:
   long long _nodes = 0;
   double _re[4] = {0.0, 0.0, 0.0, 0.0};
   int _oid[4] = {0, 0, 0, 0};
+};
+
+// ---- Farkas proof (DESIGN.md "Infeasibility and unboundedness proofs (farkas)") ----
+
+constexpr double FARKAS_Z = 1e-9;   // a coefficient this small on a variable without the bound it needs is taken for zero
+constexpr double FARKAS_REL = 1e-9; // a side proves when its rel exceeds this
+
+// one side (lower: Lo, upper: Hi) of the interval rule: the sum of the finite terms, the sum of their absolute values, the terms
+// that make the side infinite and those the zero rule dropped
+struct FarkasSide {
+  double sum = 0.0, act = 0.0;
+  int inf = 0, drop = 0;
+  void term(double f, double b) { // b: the bound this side takes of the variable
+    if (std::fabs(b) == std::numeric_limits<double>::infinity()) {
+      if (std::fabs(f) <= FARKAS_Z) drop++;
+      else inf++;
+      b = 0.0;
+    }
+    sum = std::fma(f, b, sum);
+    act = std::fma(std::fabs(f), std::fabs(b), act);
+  }
+};
+
+struct FarkasInterval {
+  double lo, hi, rel_lo, rel_hi; // hi is Hi itself; rel_hi = -Hi / (1 + act_hi)
+  int inf_lo, inf_hi, drop_lo, drop_hi;
+};
+
+// The interval rule I(f) over p = first..last, f(p) with bounds l(p), u(p): 64 chains, chain c taking p = first + c, first + c + 64,
+// ... ascending with fma from +0.0, combined by s[c] += s[c+h], h = 32 .. 1; an exact zero takes part with the bound 0
+template <typename F, typename L, typename U>
+static FarkasInterval farkas_interval(int first, int last, F f, L l, U u) {
+  FarkasSide lo[64], hi[64];
+  for (int c = 0; c < 64; c++)
+    for (int p = first + c; p <= last; p += 64) {
+      const double fp = f(p);
+      double bl = fp < 0.0 ? u(p) : l(p), bh = fp < 0.0 ? l(p) : u(p);
+      if (fp == 0.0) bl = bh = 0.0;
+      lo[c].term(fp, bl);
+      hi[c].term(fp, bh);
+    }
+  for (int h = 32; h >= 1; h >>= 1)
+    for (int c = 0; c < h; c++) {
+      lo[c].sum = lo[c].sum + lo[c + h].sum; lo[c].act = lo[c].act + lo[c + h].act;
+      hi[c].sum = hi[c].sum + hi[c + h].sum; hi[c].act = hi[c].act + hi[c + h].act;
+      lo[c].inf += lo[c + h].inf; lo[c].drop += lo[c + h].drop;
+      hi[c].inf += hi[c + h].inf; hi[c].drop += hi[c + h].drop;
+    }
+  const double ninf = -std::numeric_limits<double>::infinity();
+  FarkasInterval r;
+  r.lo = lo[0].sum; r.hi = hi[0].sum;
+  r.inf_lo = lo[0].inf; r.inf_hi = hi[0].inf; r.drop_lo = lo[0].drop; r.drop_hi = hi[0].drop;
+  r.rel_lo = r.inf_lo == 0 ? r.lo / (1.0 + lo[0].act) : ninf;
+  r.rel_hi = r.inf_hi == 0 ? -r.hi / (1.0 + hi[0].act) : ninf;
+  return r;
+}
+
+// The host twin of k_farkas_rows / k_farkas_pick / k_farkas_vars / k_farkas_cols / k_farkas_fin from numbers only: T (m+1) x (n+1) the
+// tableau as get_tableau packs it (x_B(i) = sum_q T[i][q] x_N(q): eval_tab_row's alpha; row 0 and column 0 are not read), head[0..m]
+// / nb[0..n] the basis, rows m x (n+1) dense, lb / ub [0..m+n] by variable.  y (nullable) [0..m]
+static void farkas_host(int m, int n, const double *T, const int *head, const int *nb, const double *rows, const double *lb, const double *ub,
+                        double *val, int *ind, double *y) {
+  const size_t ldr = (size_t)n + 1;
+  for (int t = 0; t < 4; t++) {
+    val[t] = 0.0;
+    ind[t] = 0;
+  }
+  if (y) std::fill(y, y + m + 1, 0.0);
+  // 1. the tableau side: every row's form f^i over p = 0 (its basic variable, coefficient 1) and p = q (-alpha_iq)
+  double best = FARKAS_REL;
+  int bi = 0, bside = 0;
+  for (int i = 1; i <= m; i++) {
+    const double *Ti = T + (size_t)i * ldr;
+    const FarkasInterval I = farkas_interval(
+        0, n, [&](int p) { return p == 0 ? 1.0 : -Ti[p]; }, [&](int p) { return lb[(size_t)(p == 0 ? head[i] : nb[p])]; },
+        [&](int p) { return ub[(size_t)(p == 0 ? head[i] : nb[p])]; });
+    if (I.rel_lo > best) { best = I.rel_lo; bi = i; bside = 1; }
+    if (I.rel_hi > best) { best = I.rel_hi; bi = i; bside = 2; }
+  }
+  if (bi == 0) return;
+  // 2. the form by variable: y its part over the auxiliaries, z over the structurals
+  std::vector<double> f((size_t)m + n + 1, 0.0), g((size_t)m + n + 1, 0.0);
+  f[(size_t)head[bi]] = 1.0;
+  for (int q = 1; q <= n; q++) f[(size_t)nb[q]] = -T[(size_t)bi * ldr + (size_t)q];
+  // 3. the model side: w = A'y in the order of the KKT check's t_j, g = (y, -w)
+  KktMax de;
+  for (int r = 1; r <= m; r++) g[(size_t)r] = f[(size_t)r];
+  for (int j = 1; j <= n; j++) {
+    const double w = kkt_chain_sum(m, [&](int r) { return rows[(size_t)(r - 1) * ldr + (size_t)j]; }, f.data());
+    const double gj = -w, z = f[(size_t)(m + j)];
+    g[(size_t)(m + j)] = gj;
+    de.see(std::fabs(gj - z) / (1.0 + std::fabs(z)), j);
+  }
+  const FarkasInterval I = farkas_interval(
+      1, m + n, [&](int k) { return g[(size_t)k]; }, [&](int k) { return lb[(size_t)k]; }, [&](int k) { return ub[(size_t)k]; });
+  const bool upper = I.rel_hi > I.rel_lo; // the lower side before the upper
+  const double rel = upper ? I.rel_hi : I.rel_lo;
+  const int inf = upper ? I.inf_hi : I.inf_lo;
+  val[0] = best;
+  val[1] = rel;
+  val[2] = inf != 0 ? -std::numeric_limits<double>::infinity() : upper ? -I.hi : I.lo;
+  val[3] = de.v;
+  ind[0] = rel > FARKAS_REL ? 2 : 1;
+  ind[1] = bi;
+  ind[2] = bside;
+  ind[3] = upper ? I.drop_hi : I.drop_lo;
+  if (y) std::copy(f.begin(), f.begin() + m + 1, y);
+}
+
+// The twin through the table: tableau, basis and bounds as the ranges read them, the rows by get_mat_row.  0; -2 an accessor is
+// missing or failed; -3 MVX_UNDEF
+static int farkas_through_table(const mvx_lp_api *api, const void *P, double *val, int *ind, double *y) {
+  if (!api->get_mat_row || !has_view_accessors(api)) return -2;
+  if (api->get_status(P) == MVX_UNDEF) return -3;
+  RangeView V;
+  const int rc = read_tableau_view(api, P, V);
+  if (rc != 0) return rc;
+  const int m = V.m, n = V.n;
+  const size_t ldr = (size_t)n + 1;
+  std::vector<double> rows((size_t)m * ldr, 0.0), buf(ldr);
+  std::vector<int> idx(ldr);
+  for (int i = 1; i <= m; i++) {
+    const int len = api->get_mat_row(P, i, idx.data(), buf.data());
+    for (int k = 1; k <= len; k++) rows[(size_t)(i - 1) * ldr + (size_t)idx[(size_t)k]] = buf[(size_t)k];
+  }
+  farkas_host(m, n, V.T.data(), V.head.data(), V.nb.data(), rows.data(), V.lb.data(), V.ub.data(), val, ind, y);
+  return 0;
+}
+
+// ---- the unbounded ray (same section of DESIGN.md) ----
+
+constexpr double RAY_TOL = 1e-9; // the published dual must improve by more than this
+
+// The host twin of k_ray_cols / k_ray_pick / k_ray_vars / k_ray_rows / k_ray_fin from numbers only: T (m+1) x (n+1) as get_tableau
+// packs it (row 0 the published duals of the non-basic positions), head / nb / flag the basis, rows m x (n+1) dense, c[0..n], lb /
+// ub [0..m+n] by variable, sg +1 minimise / -1 maximise.  val[4] = the dual, ae, re, the slope; ind[6] = found, the variable, the
+// direction, the blocking variables, the rows of ae and re; d (nullable) [0..m+n]
+static void ray_host(int m, int n, const double *T, const int *head, const int *nb, const int *flag, const double *rows, const double *c,
+                     const double *lb, const double *ub, double sg, double *val, int *ind, double *d) {
+  const size_t ldr = (size_t)n + 1;
+  const double inf = std::numeric_limits<double>::infinity();
+  for (int t = 0; t < 4; t++) val[t] = 0.0;
+  for (int t = 0; t < 6; t++) ind[t] = 0;
+  if (d) std::fill(d, d + m + n + 1, 0.0);
+  // 1. the lowest position whose move improves the objective and that nothing in the tableau stops
+  int qp = 0;
+  double sp = 0.0;
+  for (int q = 1; q <= n && qp == 0; q++) {
+    const double e = sg * T[q];
+    const int f = flag[q];
+    double sigma = 0.0;
+    if (e < -RAY_TOL && (f == MVX_NL || f == MVX_NF)) sigma = 1.0;
+    else if (e > RAY_TOL && (f == MVX_NU || f == MVX_NF)) sigma = -1.0;
+    if (sigma == 0.0) continue;
+    const int k = nb[q];
+    if (sigma > 0.0 ? ub[(size_t)k] != inf : lb[(size_t)k] != -inf) continue;
+    bool open = true;
+    for (int i = 1; i <= m && open; i++) {
+      const double a = T[(size_t)i * ldr + (size_t)q], mv = sigma * a;
+      if (std::fabs(a) <= FARKAS_Z) continue;
+      open = mv > 0.0 ? ub[(size_t)head[i]] == inf : lb[(size_t)head[i]] == -inf;
+    }
+    if (open) {
+      qp = q;
+      sp = sigma;
+    }
+  }
+  if (qp == 0) return;
+  // 2. the ray by variable
+  std::vector<double> r((size_t)m + n + 1, 0.0);
+  r[(size_t)nb[qp]] = sp;
+  for (int i = 1; i <= m; i++) r[(size_t)head[i]] = sp * T[(size_t)i * ldr + (size_t)qp];
+  // 3. against the model: rho_r = dR_r - a_r dS in the order of the KKT check's s_i, the slope c dS, the bounds in the way
+  KktMax ae, re;
+  const double *ds = r.data() + m;
+  for (int i = 1; i <= m; i++) {
+    const double *ai = rows + (size_t)(i - 1) * ldr;
+    const double rho = r[(size_t)i] - kkt_chain_sum(n, [&](int j) { return ai[j]; }, ds), a = std::fabs(rho);
+    ae.see(a, i);
+    re.see(a / (1.0 + std::fabs(r[(size_t)i])), i);
+  }
+  const double slope = kkt_chain_sum(n, [&](int j) { return c[j]; }, ds);
+  int blocked = 0;
+  for (int k = 1; k <= m + n; k++) {
+    const double v = r[(size_t)k];
+    if (std::fabs(v) <= FARKAS_Z) continue; // the zero rule
+    if (v > 0.0 ? ub[(size_t)k] != inf : lb[(size_t)k] != -inf) blocked++;
+  }
+  val[0] = T[qp];
+  val[1] = ae.v;
+  val[2] = re.v;
+  val[3] = slope;
+  ind[0] = (sg * slope < 0.0 && re.v <= RAY_TOL && blocked == 0) ? 2 : 1;
+  ind[1] = nb[qp];
+  ind[2] = sp > 0.0 ? 1 : -1;
+  ind[3] = blocked;
+  ind[4] = ae.i;
+  ind[5] = re.i;
+  if (d) std::copy(r.begin(), r.end(), d);
+  if (d) d[0] = 0.0;
+}
+
+// The twin through the table.  0; -2 an accessor is missing or failed; -3 MVX_UNDEF
+static int ray_through_table(const mvx_lp_api *api, const void *P, double *val, int *ind, double *d) {
+  if (!api->get_mat_row || !api->get_obj_coef || !has_view_accessors(api)) return -2;
+  if (api->get_status(P) == MVX_UNDEF) return -3;
+  RangeView V;
+  const int rc = read_tableau_view(api, P, V);
+  if (rc != 0) return rc;
+  const int m = V.m, n = V.n;
+  const size_t ldr = (size_t)n + 1;
+  std::vector<double> rows((size_t)m * ldr, 0.0), buf(ldr), c(ldr, 0.0);
+  std::vector<int> idx(ldr);
+  for (int i = 1; i <= m; i++) {
+    const int len = api->get_mat_row(P, i, idx.data(), buf.data());
+    for (int k = 1; k <= len; k++) rows[(size_t)(i - 1) * ldr + (size_t)idx[(size_t)k]] = buf[(size_t)k];
+  }
+  for (int j = 1; j <= n; j++) c[(size_t)j] = api->get_obj_coef(P, j);
+  ray_host(m, n, V.T.data(), V.head.data(), V.nb.data(), V.flag.data(), rows.data(), c.data(), V.lb.data(), V.ub.data(),
+           V.maxdir ? -1.0 : 1.0, val, ind, d);
+  return 0;
+}
+
+// The rule's state for one tree: the route to the proof (the table's farkas_many over `model`, the twin without the entry) and what
+// the tree reports of its MVX_NOFEAS node LPs
+class FarkasCheck {
+public:
+  FarkasCheck(const mvx_lp_api *api, const void *model, int on) : _api(api), _model(model), _on(on > 0) {}
+  bool on() const { return _on; }
+  // val[4 t ..], ind[4 t ..] of the handles hs; 0, or the failing call's code
+  int compute(const std::vector<const void *> &hs, std::vector<double> &val, std::vector<int> &ind) {
+    val.assign(hs.size() * 4, 0.0);
+    ind.assign(hs.size() * 4, 0);
+    if (hs.empty()) return 0;
+    if (_api->farkas_many) return _api->farkas_many(_model, hs.data(), (int)hs.size(), val.data(), ind.data());
+    for (size_t t = 0; t < hs.size(); t++) {
+      const int rc = farkas_through_table(_api, hs[t], &val[t * 4], &ind[t * 4], nullptr);
+      if (rc != 0) return rc;
+    }
+    return 0;
+  }
+  // a MVX_NOFEAS node books its result, in the order the serial loop meets the nodes
+  void book(const double *val, const int *ind, int oid) {
+    _nodes++;
+    if (ind[0] == 2) {
+      if (_proved == 0 || val[1] < _rel || (val[1] == _rel && oid < _rel_oid)) { // the lowest oid among equals
+        _rel = val[1];
+        _rel_oid = oid;
+      }
+      _proved++;
+    } else if (ind[0] == 1) {
+      _tableau_only++;
+    } else {
+      _none++;
+    }
+    if (ind[0] > 0) {
+      if (ind[3] > 0) _dropped++;
+      if (val[3] > _de || (val[3] == _de && val[3] > 0.0 && oid < _de_oid)) {
+        _de = val[3];
+        _de_oid = oid;
+      }
+    }
+  }
+  void store(mvx_bnb_result *res) const {
+    res->farkas_nodes = _nodes;
+    res->farkas_proved = _proved;
+    res->farkas_tableau_only = _tableau_only;
+    res->farkas_none = _none;
+    res->farkas_dropped = _dropped;
+    res->farkas_rel_min = _rel;
+    res->farkas_de_max = _de;
+    res->farkas_rel_oid = _rel_oid;
+    res->farkas_de_oid = _de_oid;
+  }
+
+private:
+  const mvx_lp_api *_api;
+  const void *_model;
+  const bool _on;
+  long long _nodes = 0, _proved = 0, _tableau_only = 0, _none = 0, _dropped = 0;
+  double _rel = 0.0, _de = 0.0;
+  int _rel_oid = 0, _de_oid = 0;
 };
 
 // 0, or -2 when the table lacks an accessor of the rows, the bounds or the column kinds
@@ -2910,6 +3193,7 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const void *model, const m
   Pump pump(T.hm, prm);
   NodeCliques ncl(api, T.hm.root, prm.node_cliques);
   KktCheck kkt(api, T.hm.root, prm.kkt);
+  FarkasCheck farkas(api, T.hm.root, prm.farkas);
   if (ncl.start() != 0) { // the graph could not be taken: the tree so far is the unsolved root
     T.rc_out = -2;
     leafContainer.clear();
@@ -2933,6 +3217,15 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const void *model, const m
         break;
       }
       kkt.book(kv.data(), node->oid);
+    }
+    if (farkas.on() && api->get_status(a) == MVX_NOFEAS) { // farkas: the proof of this verdict; nothing of the tree reads it
+      std::vector<double> fv;
+      std::vector<int> fi;
+      if (farkas.compute({a}, fv, fi) != 0) {
+        T.rc_out = -2;
+        break;
+      }
+      farkas.book(fv.data(), fi.data(), node->oid);
     }
     const double obj = api->get_obj_val(a);
     rec.emit(MVX_EV_PREGNANT, node->oid, obj, 0.0, 0, 0); // bs.cpp:119-129
@@ -3052,6 +3345,7 @@ int branchAndBound(const mvx_lp_api *api, void *prob, const void *model, const m
   const int rc = T.finish(res, &rcfix, &prop);
   ncl.store(res);
   kkt.store(res);
+  farkas.store(res);
   return rc;
 }
 
@@ -3075,6 +3369,7 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const void *model, c
   Pump pump(T.hm, prm);
   NodeCliques ncl(api, T.hm.root, prm.node_cliques);
   KktCheck kkt(api, T.hm.root, prm.kkt);
+  FarkasCheck farkas(api, T.hm.root, prm.farkas);
   auto fail = [&]() { // whatever code a failing call gives, the tree so far goes back with -2
     T.rc_out = -2;
     stop = true;
@@ -3193,6 +3488,21 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const void *model, c
     if (kkt.on() && kkt.compute(std::vector<const void *>(a.begin(), a.end()), kval) != 0) {
       fail();
       break;
+    }
+    // farkas: the nodes this round has left MVX_NOFEAS, in one call; booked by the replay for the nodes it reaches
+    std::vector<double> fval;
+    std::vector<int> fidx, fat(W, -1);
+    if (farkas.on()) {
+      std::vector<const void *> nofeas;
+      for (size_t w = 0; w < W; w++)
+        if (api->get_status(a[w]) == MVX_NOFEAS) {
+          fat[w] = (int)nofeas.size();
+          nofeas.push_back(a[w]);
+        }
+      if (farkas.compute(nofeas, fval, fidx) != 0) {
+        fail();
+        break;
+      }
     }
     tA += now() - t0; t0 = now();
     // the lazy cut modes: the one cut of every node of the window that may branch, in one device pass (round_cuts);
@@ -3315,6 +3625,7 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const void *model, c
       T.worked(*node, aw, (node->repiv >= 0) ? node->repiv : api->get_it_cnt(aw) - before[w]);
       processed++;
       if (kkt.on()) kkt.book(&kval[w * 8], node->oid);
+      if (farkas.on() && fat[w] >= 0) farkas.book(&fval[(size_t)fat[w] * 4], &fidx[(size_t)fat[w] * 4], node->oid);
       const double obj = api->get_obj_val(aw);
       rec.emit(MVX_EV_PREGNANT, node->oid, obj, 0.0, 0, 0);
       double ti = now();
@@ -3526,6 +3837,7 @@ int branchAndBoundWindow(const mvx_lp_api *api, void *prob, const void *model, c
   const int rc = T.finish(res, &rcfix, &prop);
   ncl.store(res);
   kkt.store(res);
+  farkas.store(res);
   return rc;
 }
 
@@ -3864,6 +4176,9 @@ const mvx_lp_api g_hip_api = {
     mvx_kkt_many ? +[](const void *root, const void *const *Ps, int count, double *val, int *ind) {
       return mvx_kkt_many((const mvx_prob *)root, (const mvx_prob *const *)Ps, count, val, ind);
     } : nullptr,
+    mvx_farkas_many ? +[](const void *root, const void *const *Ps, int count, double *val, int *ind) {
+      return mvx_farkas_many((const mvx_prob *)root, (const mvx_prob *const *)Ps, count, val, ind);
+    } : nullptr,
 };
 
 } // namespace
@@ -3904,6 +4219,7 @@ void mvx_bnb_default_params(mvx_bnb_params *p) {
   p->node_purge = 0;
   p->node_cliques = 0;
   p->kkt = 0;
+  p->farkas = 0;
 }
 
 // Repaired mode's rule for an integer column whose bounds are not integers (legal input: LP and MPS files may carry them):
@@ -4320,7 +4636,9 @@ int mvx_branchAndBound(const mvx_lp_api *api, void *prob, const mvx_bnb_params *
       params->node_cliques < 0 || params->node_cliques > 64 ||
       (params->node_cliques > 0 && (params->reference_quirks != 0 || params->best_window > 0)) ||
       // kkt: observation of every solved node, in both quirk modes; not (yet) in the best-bound window
-      params->kkt < 0 || params->kkt > 1 || (params->kkt > 0 && params->best_window > 0)) {
+      params->kkt < 0 || params->kkt > 1 || (params->kkt > 0 && params->best_window > 0) ||
+      // farkas: observation of every node that ends MVX_NOFEAS, in both quirk modes; not (yet) in the best-bound window
+      params->farkas < 0 || params->farkas > 1 || (params->farkas > 0 && params->best_window > 0)) {
     std::memset(res, 0, sizeof(*res));
     return -1;
   }
@@ -4630,6 +4948,25 @@ int mvx_bnb_kkt(const mvx_lp_api *api, const void *prob, double *val, int *ind, 
   if (!api) api = &g_hip_api;
   if (!prob || !val || !ind) return -1;
   return kkt_through_table(api, prob, val, ind, r_pe, r_de);
+}
+
+int mvx_bnb_farkas_values(int m, int n, const double *T, const int *head, const int *nb, const double *rows, const double *lb,
+                          const double *ub, double *val, int *ind, double *y) {
+  if (m < 1 || n < 1 || !T || !head || !nb || !rows || !lb || !ub || !val || !ind) return -1;
+  farkas_host(m, n, T, head, nb, rows, lb, ub, val, ind, y);
+  return 0;
+}
+
+int mvx_bnb_farkas(const mvx_lp_api *api, const void *prob, double *val, int *ind, double *y) {
+  if (!api) api = &g_hip_api;
+  if (!prob || !val || !ind) return -1;
+  return farkas_through_table(api, prob, val, ind, y);
+}
+
+int mvx_bnb_ray(const mvx_lp_api *api, const void *prob, double *val, int *ind, double *d) {
+  if (!api) api = &g_hip_api;
+  if (!prob || !val || !ind) return -1;
+  return ray_through_table(api, prob, val, ind, d);
 }
 
 int mvx_bnb_ranges(const mvx_lp_api *api, const void *prob, double *val, int *var) {

@@ -114,6 +114,7 @@ extern "C" int mvx_branchAndBound_dist(const mvx_lp_api *api, const mvx_image_ap
   if (prm.node_purge != 0) return MVX_EFAIL; // nor is the tree's cut purging
   if (prm.node_cliques != 0) return MVX_EFAIL; // nor are the tree's clique cuts
   if (prm.kkt != 0) return MVX_EFAIL;          // nor is the KKT check of the node LPs
+  if (prm.farkas != 0) return MVX_EFAIL;       // nor is the Farkas proof of the infeasible ones
   const int rank = comm ? comm->rank : 0, world = comm ? comm->size : 1;
   const int per_rank = dp.per_rank;
   const int slack = dp.slack >= 0 ? dp.slack : std::max(1, per_rank / 4);

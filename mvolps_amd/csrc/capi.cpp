@@ -753,6 +753,20 @@ int mvx_check_kkt(const mvx_prob *P, int sol, int cond, double *ae_max, int *ae_
   *re_ind = ind[2 * (cond - 1) + 1];
   return 0;
 }
+int mvx_farkas_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, double *val, int *ind) {
+  return mvx::engine_farkas_many(root, Ps, count, val, ind, nullptr);
+}
+int mvx_farkas(const mvx_prob *P, double *val, int *ind, double *y) {
+  if (!P) return -1;
+  return mvx::engine_farkas_many(P, &P, 1, val, ind, y);
+}
+int mvx_ray(const mvx_prob *P, double *val, int *ind, double *d) { return mvx::engine_ray(P, val, ind, d); }
+int mvx_get_unbnd_ray(const mvx_prob *P) {
+  if (!P || !P->valid || P->status != MVX_UNBND) return 0;
+  double val[4];
+  int ind[6];
+  return mvx::engine_ray(P, val, ind, nullptr) == 0 && ind[0] > 0 ? ind[1] : 0;
+}
 int mvx_round_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, int mode, double *obj, int *found, double *x) {
   return mvx::engine_round_many(root, Ps, count, mode, obj, found, x);
 }

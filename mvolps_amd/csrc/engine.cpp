@@ -1602,7 +1602,8 @@ extern "C" void mvx_debug_counters(long long *out, int reset) {
 // oracle: NOFEAS_RECHECK / largest_violation -- a NOFEAS verdict whose largest violation is within the rounding an
 // ill-conditioned tableau puts on column 0 counts on a rebuilt tableau only.  A recheck, not a cure: column 0 still drifts
 // on such a basis.  (The oracle's refresh_tableau cannot fail; here a rebuild that cannot get its slab leaves the verdict
-// as it is.)
+// as it is.)  A verdict above the threshold is not looked at again here; mvx_farkas_many (engine_farkas_many below, DESIGN.md
+// "Infeasibility and unboundedness proofs (farkas)") asks the model, not the tableau, whether any MVX_NOFEAS verdict holds.
 constexpr double NOFEAS_RECHECK = 1e-6;
 static double largest_violation(const mvx_prob *P) {
   refresh_solution(P);
@@ -3732,6 +3733,137 @@ int engine_kkt_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, 
   if (r_de) {
     r_de[0] = 0.0;
     std::memcpy(r_de + 1, h_res + (size_t)Ps[0]->m + 1, (size_t)n * 8);
+  }
+  return 0;
+}
+
+// ------------------------------------------------- Farkas proof (k_farkas_rows, k_farkas_pick, k_farkas_vars, k_farkas_cols, k_farkas_fin)
+// A proof of infeasibility for `count` handles against their own models (mvx_farkas_many, DESIGN.md "Infeasibility and unboundedness
+// proofs (farkas)"): one pass over each handle's tableau slab finds the row that proves, its weights are evaluated on the columns
+// of root's rounding model (uploaded on first use, checked on every call) and on the handle's cut rows m0+1..m, which go up with
+// the descriptors in the call's one upload.  One flush of the recorded clones, one upload, one launch sequence, one copy back; no
+// handle is changed.  y (nullable): the row weights of handle 0, which the single-handle entry asks for.  Return codes: 0; -1 bad
+// arguments; -2 device out of memory, nothing written; -3 a handle that is MVX_UNDEF or has no tableau (or bound edits still
+// pending), or one whose first m0 rows are not root's.
+int engine_farkas_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, double *val, int *ind, double *y) {
+  if (!root || count < 0) return -1;
+  if (count == 0) return 0;
+  if (!Ps || !val || !ind) return -1;
+  const int n = root->n, m0 = root->m;
+  for (int t = 0; t < count; t++)
+    if (!Ps[t] || Ps[t]->n != n) return -1;
+  if (n < 1 || m0 < 1) return -3;
+  size_t vars = 0, cut_rows = 0, rows = 0;
+  int mmax = 0;
+  for (int t = 0; t < count; t++) {
+    const mvx_prob *P = Ps[t];
+    if (!P->valid || P->status == MVX_UNDEF || !P->pending.empty() || P->m < m0) return -3;
+    if (P != root)
+      for (int i = 1; i <= m0; i++)
+        if (P->A[(size_t)i].get() != root->A[(size_t)i].get()) return -3;
+    vars += (size_t)P->m + (size_t)n + 1;
+    rows += (size_t)P->m;
+    cut_rows += (size_t)(P->m - m0);
+    mmax = std::max(mmax, P->m);
+  }
+  NodeCall f(NodeFlush::AtEntry, NodeResults::Device);
+  const RoundModel *M = round_model(*f.c, root);
+  if (!M) return -2;
+  const size_t row = (size_t)n + 1;
+  // up: [descriptors][cut rows]; back: [val][ind] (and the form by variable when y is wanted); device only: the row records, the
+  // picks and the other by-variable arrays
+  const size_t o_nodes = f.up((size_t)count * sizeof(FkNode)), o_cuts = f.up(cut_rows * row * 8);
+  const size_t o_val = f.out((size_t)count * 4 * 8), o_ind = f.out((size_t)count * 4 * 4);
+  const size_t o_f = y ? f.out(vars * 8) : f.dev(vars * 8);
+  const size_t o_g = f.dev(vars * 8), o_lo = f.dev(vars * 8), o_up = f.dev(vars * 8), o_dt = f.dev(vars * 8);
+  const size_t o_rrel = f.dev(rows * 2 * 8), o_pick = f.dev((size_t)count * 4);
+  if (!f.reserve()) return -2;
+  unsigned char *hb = f.hb, *db = f.db;
+  FkNode *h_nodes = (FkNode *)(hb + o_nodes);
+  size_t voff = 0, roff = 0, cut_at = 0;
+  for (int t = 0; t < count; t++) {
+    const mvx_prob *P = Ps[t];
+    FkNode &nd = h_nodes[t];
+    static_cast<NodeRef &>(nd) = node_ref(P);
+    nd.blb = P->d_blb;
+    nd.bub = P->d_bub;
+    nd.cuts = nullptr;
+    if (P->m > m0) {
+      nd.cuts = (const double *)(db + o_cuts) + cut_at * row;
+      for (int i = m0 + 1; i <= P->m; i++, cut_at++) {
+        if (P->A[(size_t)i]) std::memcpy(hb + o_cuts + cut_at * row * 8, P->A[(size_t)i]->data(), row * 8);
+        else std::memset(hb + o_cuts + cut_at * row * 8, 0, row * 8); // a row that was never filled is empty
+      }
+    }
+    nd.voff = voff;
+    nd.roff = roff;
+    voff += (size_t)P->m + row;
+    roff += 2 * (size_t)P->m;
+  }
+  f.upload();
+  FkArgs a;
+  a.nodes = (const FkNode *)(db + o_nodes);
+  a.At = (const double *)M->dev;
+  a.rrel = (double *)(db + o_rrel);
+  a.f = (double *)(db + o_f); a.g = (double *)(db + o_g); a.lo = (double *)(db + o_lo); a.up = (double *)(db + o_up);
+  a.dterm = (double *)(db + o_dt);
+  a.pick = (int *)(db + o_pick);
+  a.val = (double *)(db + o_val); a.ind = (int *)(db + o_ind);
+  a.n = n; a.m0 = m0; a.ldm = M->ldm; a.count = count; a.mmax = mmax;
+  launch_farkas(a, f.stream());
+  f.copy_back(y ? o_f + ((size_t)Ps[0]->m + 1) * 8 : 0); // of the form, handle 0's row weights only
+  f.sync();
+  std::memcpy(val, hb + o_val, (size_t)count * 4 * 8);
+  std::memcpy(ind, hb + o_ind, (size_t)count * 4 * 4);
+  if (y) {
+    y[0] = 0.0;
+    std::memcpy(y + 1, hb + o_f + 8, (size_t)Ps[0]->m * 8);
+  }
+  return 0;
+}
+
+// ------------------------------------------------------- the unbounded ray (k_ray_cols, k_ray_pick, k_ray_vars, k_ray_rows, k_ray_fin)
+// The ray that proves a handle unbounded (mvx_ray, same section of DESIGN.md): one pass down the columns of the slab finds the
+// position, the ray is checked against the handle's own rows by row (the second orientation of its rounding model) and its
+// objective, which goes up with the call.  No handle is changed.  d (nullable): the ray by variable.  Return codes: 0; -1 bad
+// arguments; -2 device out of memory, nothing written; -3 a handle that is MVX_UNDEF or has no tableau (or bound edits pending).
+int engine_ray(const mvx_prob *P, double *val, int *ind, double *d) {
+  if (!P || !val || !ind) return -1;
+  const int n = P->n, m = P->m;
+  if (n < 1 || m < 1 || !P->valid || P->status == MVX_UNDEF || !P->pending.empty()) return -3;
+  NodeCall f(NodeFlush::AtEntry, NodeResults::Device);
+  const RoundModel *M = round_model(*f.c, P);
+  if (!M || !round_model_rows(*f.c, P, P->rmod.get())) return -2;
+  const size_t vars = (size_t)m + (size_t)n + 1;
+  const size_t o_c = f.up(((size_t)n + 1) * 8);
+  const size_t o_val = f.out(4 * 8), o_ind = f.out(6 * 4);
+  const size_t o_d = d ? f.out(vars * 8) : f.dev(vars * 8);
+  const size_t o_lo = f.dev(vars * 8), o_up = f.dev(vars * 8), o_rae = f.dev(((size_t)m + 1) * 8), o_rre = f.dev(((size_t)m + 1) * 8);
+  const size_t o_open = f.dev(((size_t)n + 1) * 4), o_pick = f.dev(4);
+  if (!f.reserve()) return -2;
+  unsigned char *hb = f.hb, *db = f.db;
+  std::memcpy(hb + o_c, P->c.data(), ((size_t)n + 1) * 8);
+  f.upload();
+  RayArgs a;
+  a.nd = node_ref(P);
+  a.blb = P->d_blb;
+  a.bub = P->d_bub;
+  a.Ar = (const double *)M->dev_rows;
+  a.c = (const double *)(db + o_c);
+  a.open = (int *)(db + o_open);
+  a.pick = (int *)(db + o_pick);
+  a.d = (double *)(db + o_d); a.lo = (double *)(db + o_lo); a.up = (double *)(db + o_up);
+  a.rae = (double *)(db + o_rae); a.rre = (double *)(db + o_rre);
+  a.val = (double *)(db + o_val); a.ind = (int *)(db + o_ind);
+  a.sg = P->dir == MVX_MIN ? 1.0 : -1.0;
+  a.n = n; a.ldn = M->ldn;
+  launch_ray(a, f.stream());
+  f.fetch();
+  std::memcpy(val, hb + o_val, 4 * 8);
+  std::memcpy(ind, hb + o_ind, 6 * 4);
+  if (d) {
+    d[0] = 0.0;
+    std::memcpy(d + 1, hb + o_d + 8, (vars - 1) * 8);
   }
   return 0;
 }

@@ -47,6 +47,10 @@ int engine_penalties_many(const mvx_prob *const *Ps, int count, const int *cols,
 int engine_ranges(const mvx_prob *P, double tol, double *val, int *var);
 // KKT check of `count` solved handles over root's rows (k_kkt_vals, k_kkt_rows, k_kkt_cols, k_kkt_fin); see engine.cpp
 int engine_kkt_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, double *val, int *ind, double *r_pe, double *r_de);
+// Farkas proof of `count` handles over root's rows (k_farkas_rows .. k_farkas_fin); y (nullable): handle 0's row weights; see engine.cpp
+int engine_farkas_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, double *val, int *ind, double *y);
+// the ray that proves a handle unbounded, checked on its own model (k_ray_cols .. k_ray_fin); d (nullable) by variable; see engine.cpp
+int engine_ray(const mvx_prob *P, double *val, int *ind, double *d);
 // primal rounding heuristic on `count` solved handles against root's model, one launch (k_round); see engine.cpp
 int engine_round_many(const mvx_prob *root, const mvx_prob *const *Ps, int count, int mode, double *obj, int *found, double *x);
 // the diving heuristic's branching pick for `count` (solved handle, rule) pairs against root's model, one launch (k_divepick)

@@ -1,7 +1,7 @@
 // mvolps -- command-line front end over libmvolps_amd.so; counterpart of MVOLPS's main
 // (/root/reference/2test.cpp:13-157): same flags, same dispatch on the file extension
 // (2test.cpp:65-81), then initProblem (util.cpp:277-292) and branchAndBound (bs.cpp:54).
-// Extra flags of this build: --repaired (reference_quirks = 0), --max-nodes N, --events FILE, --ranges FILE, --kkt FILE.
+// Extra flags of this build: --repaired (reference_quirks = 0), --max-nodes N, --events FILE, --ranges FILE, --kkt FILE, --farkas FILE.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -48,6 +48,10 @@ int main(int argc, char **argv) {
               << "  --kkt [FILE]    solve the root LP, write its KKT check against the model (four lines KKT.PE, KKT.PB, KKT.DE, KKT.DB:\n"
               << "                  ae_max, its index, re_max, its index) to FILE, run the tree with every node LP checked, and append\n"
               << "                  the tree's summary (nodes checked, worst re_max per condition and its node); not with --best-window\n"
+              << "  --farkas [FILE] solve the root LP; when it is infeasible write the proof (FARKAS.ROOT: found, row, side, dropped, rel of the\n"
+              << "                  tableau side, rel of the model side, Lo or -Hi, de) to FILE, when it is unbounded its ray (RAY.ROOT: found,\n"
+              << "                  variable, direction, blocking variables, rows of ae and re, dual, ae, re, slope); run the tree with every infeasible node LP\n"
+              << "                  asked for its proof, and append the tree's totals; not with --best-window\n"
               << "Output verbosity options:\n"
               << "  -s/--silent\n  -v/--verbose\n  -d/--debug\n  -so/--solver-output\n\n"
               << "Algorithm strategy options:\n"
@@ -340,6 +344,42 @@ int main(int argc, char **argv) {
     mvx_delete_prob(root);
   }
 
+  std::string farkas_path;
+  if (input.CMDOptionExists("--farkas")) {
+    farkas_path = input.getCMDOption("--farkas");
+    if (farkas_path.empty() || farkas_path[0] == '-') { // the end of the line, or the next flag
+      std::fprintf(stderr, "Unknown parameter value for --farkas\n");
+      return -1;
+    }
+    if (params.best_window > 0) {
+      std::fprintf(stderr, "--farkas is not supported with --best-window\n");
+      return -1;
+    }
+    // the root LP as the tree will first solve it, on a copy: the run below starts from the handle as it was read
+    mvx_prob *root = mvx_create_prob();
+    mvx_copy_prob(root, prob, MVX_ON);
+    if (!params.reference_quirks) mvx_bnb_integral_bounds(nullptr, root);
+    mvx_simplex(root, nullptr);
+    double val[4] = {0.0, 0.0, 0.0, 0.0};
+    int ind[4] = {0, 0, 0, 0};
+    int rind[6] = {0, 0, 0, 0, 0, 0};
+    const bool nofeas = mvx_get_status(root) == MVX_NOFEAS, unbnd = mvx_get_status(root) == MVX_UNBND;
+    const int frc = nofeas ? mvx_farkas(root, val, ind, nullptr) : unbnd ? mvx_ray(root, val, rind, nullptr) : 0;
+    FILE *out = frc == 0 ? std::fopen(farkas_path.c_str(), "w") : nullptr;
+    if (out) {
+      if (nofeas) std::fprintf(out, "FARKAS.ROOT %d %d %d %d %.17g %.17g %.17g %.17g\n", ind[0], ind[1], ind[2], ind[3], val[0], val[1], val[2], val[3]);
+      if (unbnd)
+        std::fprintf(out, "RAY.ROOT %d %d %d %d %d %d %.17g %.17g %.17g %.17g\n", rind[0], rind[1], rind[2], rind[3], rind[4], rind[5], val[0], val[1],
+                     val[2], val[3]);
+      std::fclose(out);
+      params.farkas = 1; // the tree's totals follow the root's line
+    } else { // nothing was written and nothing will be appended: the run goes on as without the flag
+      std::fprintf(stderr, "--farkas: no report (%d): the root LP's proof could not be asked for, or %s cannot be written; the tree runs unchecked\n",
+                   frc, farkas_path.c_str());
+    }
+    mvx_delete_prob(root);
+  }
+
   mvx_bnb_result res;
   const int brc = mvx_branchAndBound(nullptr, prob, &params, &res);
   if (brc == -1) {
@@ -408,6 +448,21 @@ int main(int argc, char **argv) {
       std::printf("KKT check: %lld nodes, worst relative errors PE %.3g (node %d), PB %.3g (node %d), DE %.3g (node %d), DB %.3g (node %d)\n",
                   res.kkt_nodes, res.kkt_re[0], res.kkt_oid[0], res.kkt_re[1], res.kkt_oid[1], res.kkt_re[2], res.kkt_oid[2], res.kkt_re[3],
                   res.kkt_oid[3]);
+  }
+  if (params.farkas > 0) {
+    if (FILE *out = std::fopen(farkas_path.c_str(), "a")) {
+      std::fprintf(out, "FARKAS.NODES %lld\nFARKAS.PROVED %lld\nFARKAS.TABLEAU_ONLY %lld\nFARKAS.NONE %lld\nFARKAS.DROPPED %lld\n", res.farkas_nodes,
+                   res.farkas_proved, res.farkas_tableau_only, res.farkas_none, res.farkas_dropped);
+      std::fprintf(out, "FARKAS.REL_MIN %.17g %d\nFARKAS.DE_MAX %.17g %d\n", res.farkas_rel_min, res.farkas_rel_oid, res.farkas_de_max,
+                   res.farkas_de_oid);
+      std::fclose(out);
+    } else {
+      std::fprintf(stderr, "--farkas: the tree's totals could not be appended to %s\n", farkas_path.c_str());
+    }
+    if (verbose)
+      std::printf("Farkas proofs: %lld infeasible nodes, %lld proved, %lld by the tableau only, %lld without, smallest rel %.3g (node %d), largest de %.3g (node %d)\n",
+                  res.farkas_nodes, res.farkas_proved, res.farkas_tableau_only, res.farkas_none, res.farkas_rel_min, res.farkas_rel_oid,
+                  res.farkas_de_max, res.farkas_de_oid);
   }
   const int limit = res.hit_limit || brc != 0;
   mvx_bnb_free_result(&res);

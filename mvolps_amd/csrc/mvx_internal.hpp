@@ -336,6 +336,52 @@ struct KktArgs {
   int n, m0, ldm, ldn, count, mmax; // mmax: the most rows of a handle
 };
 
+// one handle of a Farkas launch (k_farkas_rows / k_farkas_pick / k_farkas_vars / k_farkas_cols / k_farkas_fin; mvx_farkas_many,
+// DESIGN.md "Infeasibility and unboundedness proofs (farkas)"): the handle, the bounds of its basic variables, its cut rows in the
+// call's upload, where its slice of the by-variable arrays (m + n + 1 entries, entry 0 unused) and of the row records (two per
+// tableau row) start
+struct FkNode : NodeRef {
+  const double *blb, *bub; // [m+1]
+  const double *cuts;      // [m - m0][n+1], nullptr when m == m0
+  size_t voff, roff;
+};
+
+// arguments of the Farkas kernels: `count` handles over the columns of one root's model (k_prop's copy At).  rrel holds rel of the
+// lower and of the upper side of every tableau row; f the picked row's form by variable, g the model's form (y, -w), lo / up the
+// bounds by variable, dterm the de terms by column (at m + j)
+#define FARKAS_WAVES 4 // waves of a k_farkas_rows / k_farkas_cols workgroup: a tableau row (a column) each
+#define FARKAS_Z 1e-9   // the zero rule: a coefficient this small on a variable without the bound it needs is dropped
+#define FARKAS_REL 1e-9 // a side proves when its rel exceeds this
+struct FkArgs {
+  const FkNode *nodes; // [count]
+  const double *At;    // [n+1][ldm]: At[j*ldm + i] = a_(i+1),j
+  double *rrel;
+  double *f, *g, *lo, *up, *dterm;
+  int *pick;   // [count]: 2 (i - 1) + side - 1 of the candidate, -1 without one
+  double *val; // [count][4]
+  int *ind;    // [count][4]
+  int n, m0, ldm, count, mmax; // mmax: the most rows of a handle
+};
+
+// arguments of the ray kernels (k_ray_cols / k_ray_pick / k_ray_vars / k_ray_rows / k_ray_fin; mvx_ray, same section of DESIGN.md):
+// one handle against its own rows by row (k_prop's copy Ar) and its objective, which goes up with the call.  open[q] holds the
+// direction (+1 / -1) in which position q gives a ray the tableau does not stop, 0 where it gives none; d / lo / up are by variable
+// (m + n + 1 entries), rae / rre the rows' ae and re terms
+#define RAY_TOL 1e-9 // the published dual must improve by more than this
+struct RayArgs {
+  NodeRef nd;
+  const double *blb, *bub; // [m+1]
+  const double *Ar;        // [m][ldn]: Ar[i*ldn + j] = a_(i+1),j
+  const double *c;         // [n+1]
+  int *open;               // [n+1]
+  int *pick;               // [1]: the position, 0 without one
+  double *d, *lo, *up, *rae, *rre;
+  double *val; // [4]
+  int *ind;    // [6]
+  double sg;   // +1 minimise, -1 maximise
+  int n, ldn;
+};
+
 // one handle of a rounding launch (k_round, mvx_round_many)
 using RndNode = NodeRef;
 
@@ -644,6 +690,8 @@ void launch_classify(const ClsArgs &a, hipStream_t);
 void launch_penalty(const PenArgs &a, hipStream_t);
 void launch_ranges(const RangeArgs &a, hipStream_t);
 void launch_kkt(const KktArgs &a, hipStream_t);
+void launch_farkas(const FkArgs &a, hipStream_t);
+void launch_ray(const RayArgs &a, hipStream_t);
 void launch_round(const RndArgs &a, hipStream_t);
 void launch_rcfix(const RcArgs &a, hipStream_t);
 void launch_prop(const PropArgs &a, hipStream_t);

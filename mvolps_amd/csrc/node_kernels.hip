@@ -1,6 +1,6 @@
 // node_kernels.hip -- gfx950 kernels of the batched node entries of branch and bound (engine.cpp: engine_*_many): GMI cuts,
 // classification, branching penalties, sensitivity ranges, the rounding heuristic, reduced-cost tightening, bound propagation, bound lists, the
-// diving pick, objective replacement, the feasibility pump's step, the scores and the batched append of a cut round, the clique separation of a window, the KKT check, and the append, pricing and deletion of columns.  Each takes its arguments by value and the handles it works on as an array of descriptors (NodeRef and what
+// diving pick, objective replacement, the feasibility pump's step, the scores and the batched append of a cut round, the clique separation of a window, the KKT check, the Farkas proof, the unbounded ray, and the append, pricing and deletion of columns.  Each takes its arguments by value and the handles it works on as an array of descriptors (NodeRef and what
 // the kernel needs beyond it, mvx_internal.hpp).  Same flags as kernels.hip: -ffp-contract=off, so every kernel has the bits
 // of its host twin.
 #include <hip/hip_runtime.h>
@@ -611,17 +611,23 @@ __device__ __forceinline__ void kkt_var_terms(const KktArgs &a, size_t o, double
   a.term[7][o] = xdiv(v, 1.0 + fabs(d));
 }
 
+// sum_j row[j] v[j], j = 1..n, by one wave: 64 chains, lane l taking j = l+1, l+65, ... ascending with fma from +0.0 over a
+// coalesced row, combined by the halving tree.  Every lane returns the sum its part of the tree leaves; lane 0's is the sum
+__device__ __forceinline__ double kkt_row_sum(const double *__restrict__ row, const double *__restrict__ v, int n, int lane) {
+  double acc = 0.0;
+#pragma unroll 4
+  for (int j = lane + 1; j <= n; j += 64) acc = fma(row[j], v[j], acc);
+  for (int h = 32; h >= 1; h >>= 1) acc = acc + __shfl_xor(acc, h);
+  return acc;
+}
+
 __global__ __launch_bounds__(64 * KKT_WAVES) void k_kkt_rows(KktArgs a) {
   const KktNode nd = a.nodes[blockIdx.y];
   const int lane = TIDX & 63, i = (int)blockIdx.x * KKT_WAVES + (TIDX >> 6) + 1;
   if (i > nd.m) return;
   const int n = a.n;
   const double *__restrict__ row = i <= a.m0 ? a.Ar + (size_t)(i - 1) * (size_t)a.ldn : nd.cuts + (size_t)(i - a.m0 - 1) * (size_t)(n + 1);
-  const double *__restrict__ xs = a.x + nd.voff + (size_t)nd.m;
-  double acc = 0.0;
-#pragma unroll 4
-  for (int j = lane + 1; j <= n; j += 64) acc = fma(row[j], xs[j], acc);
-  for (int h = 32; h >= 1; h >>= 1) acc = acc + __shfl_xor(acc, h);
+  const double acc = kkt_row_sum(row, a.x + nd.voff + (size_t)nd.m, n, lane);
   if (lane != 0) return;
   const size_t o = nd.voff + (size_t)i;
   const double xr = a.x[o];
@@ -632,19 +638,25 @@ __global__ __launch_bounds__(64 * KKT_WAVES) void k_kkt_rows(KktArgs a) {
   kkt_var_terms(a, o, nd.sg);
 }
 
+// sum_i a_ij v_i, i = 1..m, by one wave: column j of the root's rows (col = At + j ldm) and of the handle's cut rows behind them, in
+// the 64 chains of k_kkt_rows.  Every lane returns the sum its part of the halving tree leaves; lane 0's is the sum
+__device__ __forceinline__ double kkt_col_sum(const double *__restrict__ col, const double *__restrict__ cuts, const double *__restrict__ v,
+                                              int j, int n, int m, int m0, int lane) {
+  double acc = 0.0;
+  int i = lane + 1;
+#pragma unroll 4
+  for (; i <= m0; i += 64) acc = fma(col[i - 1], v[i], acc);
+  for (; i <= m; i += 64) acc = fma(cuts[(size_t)(i - m0 - 1) * (size_t)(n + 1) + (size_t)j], v[i], acc);
+  for (int h = 32; h >= 1; h >>= 1) acc = acc + __shfl_xor(acc, h);
+  return acc;
+}
+
 __global__ __launch_bounds__(64 * KKT_WAVES) void k_kkt_cols(KktArgs a) {
   const KktNode nd = a.nodes[blockIdx.y];
   const int lane = TIDX & 63, j = (int)blockIdx.x * KKT_WAVES + (TIDX >> 6) + 1;
   const int n = a.n, m = nd.m, m0 = a.m0;
   if (j > n) return;
-  const double *__restrict__ col = a.At + (size_t)j * (size_t)a.ldm;
-  const double *__restrict__ lam = a.du + nd.voff;
-  double acc = 0.0;
-  int i = lane + 1;
-#pragma unroll 4
-  for (; i <= m0; i += 64) acc = fma(col[i - 1], lam[i], acc);
-  for (; i <= m; i += 64) acc = fma(nd.cuts[(size_t)(i - m0 - 1) * (size_t)(n + 1) + (size_t)j], lam[i], acc);
-  for (int h = 32; h >= 1; h >>= 1) acc = acc + __shfl_xor(acc, h);
+  const double acc = kkt_col_sum(a.At + (size_t)j * (size_t)a.ldm, nd.cuts, a.du + nd.voff, j, n, m, m0, lane);
   if (lane != 0) return;
   const size_t o = nd.voff + (size_t)m + (size_t)j;
   const double cj = nd.c ? nd.c[j] : a.c0[j];
@@ -719,6 +731,401 @@ void launch_kkt(const KktArgs &a0, hipStream_t s) {
     hipLaunchKernelGGL(k_kkt_cols, dim3((unsigned)((a.n + KKT_WAVES - 1) / KKT_WAVES), cnt), dim3(64 * KKT_WAVES), 0, s, a);
     hipLaunchKernelGGL(k_kkt_fin, dim3(8, cnt), dim3(256), 0, s, a);
   }
+}
+
+// ------------------------------------------------------------- k_farkas_rows / k_farkas_pick / k_farkas_vars / k_farkas_cols / k_farkas_fin
+// Farkas proof of infeasible handles (mvx_farkas_many, DESIGN.md "Infeasibility and unboundedness proofs (farkas)").  Five launches
+// over all handles:
+//  1. k_farkas_rows, a wave per (handle, tableau row i): the interval rule on the row's form over the slab positions p = 0..n -- p = 0
+//     the basic variable with coefficient 1 and the row's bounds, p = q the non-basic position q with -T[i][q] (the slab stores
+//     eval_tab_row's alpha itself) and the position's bounds -- lane l taking p = l, l+64, ... ascending over a coalesced row, the
+//     chains combined by the halving tree through __shfl_xor.  Lane 0 writes rel of both sides;
+//  2. k_farkas_pick, a workgroup per handle: the largest rel above FARKAS_REL, the lowest (row, side) among equals -- exact, so the
+//     order of the combination is free;
+//  3. k_farkas_vars, a thread per (handle, tableau row and non-basic position): the picked row's form and the bounds by variable;
+//  4. k_farkas_cols, a wave per (handle, column j): w_j = sum_r a_rj y_r by kkt_col_sum, g_(m+j) = -w_j and the de term;
+//  5. k_farkas_fin, a workgroup per handle: wave 0 the interval rule on g over k = 1..m+n (lane l taking k = l+1, l+65, ...), waves
+//     1..3 the largest de term; thread 0 writes the handle's val / ind.
+// No atomics, no LDS beyond the wave partials of 2 and 5, nothing waits on another workgroup.  Quotients are correctly rounded (xdiv).
+
+// the two sides of the interval rule as one lane carries them
+struct FkAcc {
+  double lo = 0.0, alo = 0.0, hi = 0.0, ahi = 0.0;
+  int ilo = 0, ihi = 0, dlo = 0, dhi = 0;
+};
+
+// one side's term: a bound that is infinite drops the term (|f| <= FARKAS_Z, counted in d) or makes the side infinite (counted in
+// i); the fma runs either way, with the bound 0
+__device__ __forceinline__ void fk_side(double f, double b, double &sum, double &act, int &i, int &d) {
+  if (fabs(b) == INFINITY) {
+    if (fabs(f) <= FARKAS_Z) d++;
+    else i++;
+    b = 0.0;
+  }
+  sum = fma(f, b, sum);
+  act = fma(fabs(f), fabs(b), act);
+}
+
+__device__ __forceinline__ void fk_term(FkAcc &s, double f, double l, double u) {
+  double bl = f < 0.0 ? u : l, bh = f < 0.0 ? l : u;
+  if (f == 0.0) bl = bh = 0.0; // an exact zero takes part with the bound 0
+  fk_side(f, bl, s.lo, s.alo, s.ilo, s.dlo);
+  fk_side(f, bh, s.hi, s.ahi, s.ihi, s.dhi);
+}
+
+// the halving tree over the 64 lanes of a wave; lane 0 holds the result
+__device__ __forceinline__ void fk_reduce(FkAcc &s) {
+  for (int h = 32; h >= 1; h >>= 1) {
+    s.lo = s.lo + __shfl_xor(s.lo, h);
+    s.alo = s.alo + __shfl_xor(s.alo, h);
+    s.hi = s.hi + __shfl_xor(s.hi, h);
+    s.ahi = s.ahi + __shfl_xor(s.ahi, h);
+    s.ilo += __shfl_xor(s.ilo, h);
+    s.ihi += __shfl_xor(s.ihi, h);
+    s.dlo += __shfl_xor(s.dlo, h);
+    s.dhi += __shfl_xor(s.dhi, h);
+  }
+}
+
+__device__ __forceinline__ double fk_rel_lo(const FkAcc &s) { return s.ilo == 0 ? xdiv(s.lo, 1.0 + s.alo) : -INFINITY; }
+__device__ __forceinline__ double fk_rel_hi(const FkAcc &s) { return s.ihi == 0 ? xdiv(-s.hi, 1.0 + s.ahi) : -INFINITY; }
+
+__global__ __launch_bounds__(64 * FARKAS_WAVES) void k_farkas_rows(FkArgs a) {
+  const FkNode nd = a.nodes[blockIdx.y];
+  const int lane = TIDX & 63, i = (int)blockIdx.x * FARKAS_WAVES + (TIDX >> 6) + 1;
+  if (i > nd.m) return;
+  const int n = a.n;
+  const double *__restrict__ Ti = nd.T + (size_t)i * (size_t)nd.ld;
+  const double *__restrict__ nlb = nd.nlb, *__restrict__ nub = nd.nub;
+  FkAcc s;
+  int p = lane;
+  if (p == 0) { // the basic variable
+    fk_term(s, 1.0, nd.blb[i], nd.bub[i]);
+    p = 64;
+  }
+#pragma unroll 2
+  for (; p <= n; p += 64) fk_term(s, -Ti[p], nlb[p], nub[p]);
+  fk_reduce(s);
+  if (lane != 0) return;
+  double *r = a.rrel + nd.roff + 2 * (size_t)(i - 1);
+  r[0] = fk_rel_lo(s);
+  r[1] = fk_rel_hi(s);
+}
+
+__global__ __launch_bounds__(256) void k_farkas_pick(FkArgs a) {
+  __shared__ double s_v[4];
+  __shared__ int s_i[4];
+  const FkNode nd = a.nodes[blockIdx.x];
+  const int cnt = 2 * nd.m, lane = TIDX & 63, wave = TIDX >> 6;
+  const double *__restrict__ v = a.rrel + nd.roff;
+  double best = FARKAS_REL;
+  int bi = 0x7fffffff; // no candidate
+  for (int e = TIDX; e < cnt; e += 256) {
+    const double w = v[e];
+    if (w > best) {
+      best = w;
+      bi = e;
+    }
+  }
+  for (int h = 32; h >= 1; h >>= 1) {
+    const double w = __shfl_xor(best, h);
+    const int wi = __shfl_xor(bi, h);
+    if (w > best || (w == best && wi < bi)) {
+      best = w;
+      bi = wi;
+    }
+  }
+  if (lane == 0) {
+    s_v[wave] = best;
+    s_i[wave] = bi;
+  }
+  __syncthreads();
+  if (TIDX == 0) {
+    for (int w = 1; w < 4; w++)
+      if (s_v[w] > best || (s_v[w] == best && s_i[w] < bi)) {
+        best = s_v[w];
+        bi = s_i[w];
+      }
+    a.pick[blockIdx.x] = bi == 0x7fffffff ? -1 : bi;
+    a.val[(size_t)blockIdx.x * 4] = bi == 0x7fffffff ? 0.0 : best;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_farkas_vars(FkArgs a) {
+  const FkNode nd = a.nodes[blockIdx.y];
+  const int m = nd.m, n = a.n;
+  const int e = a.pick[blockIdx.y], ip = e < 0 ? 0 : (e >> 1) + 1; // the picked row, 0 without one
+  double *f = a.f + nd.voff, *gv = a.g + nd.voff, *lo = a.lo + nd.voff, *up = a.up + nd.voff;
+  const int g = (int)blockIdx.x * 256 + TIDX + 1; // tableau row g and non-basic position g
+  if (g <= m) {
+    const int k = nd.bvar[g];
+    if (k >= 1 && k <= m + n) {
+      const double v = g == ip ? 1.0 : 0.0;
+      f[k] = v;
+      gv[k] = v;
+      lo[k] = nd.blb[g];
+      up[k] = nd.bub[g];
+    }
+  }
+  if (g <= n) {
+    const int k = nd.nvar[g];
+    if (k >= 1 && k <= m + n) {
+      const double v = ip > 0 ? -nd.T[(size_t)ip * (size_t)nd.ld + (size_t)g] : 0.0;
+      f[k] = v;
+      gv[k] = v;
+      lo[k] = nd.nlb[g];
+      up[k] = nd.nub[g];
+    }
+  }
+}
+
+__global__ __launch_bounds__(64 * FARKAS_WAVES) void k_farkas_cols(FkArgs a) {
+  const FkNode nd = a.nodes[blockIdx.y];
+  const int lane = TIDX & 63, j = (int)blockIdx.x * FARKAS_WAVES + (TIDX >> 6) + 1;
+  const int n = a.n, m = nd.m;
+  if (j > n) return;
+  const double w = kkt_col_sum(a.At + (size_t)j * (size_t)a.ldm, nd.cuts, a.f + nd.voff, j, n, m, a.m0, lane);
+  if (lane != 0) return;
+  const size_t o = nd.voff + (size_t)m + (size_t)j;
+  const double gj = -w, z = a.f[o];
+  a.g[o] = gj;
+  a.dterm[o] = xdiv(fabs(gj - z), 1.0 + fabs(z));
+}
+
+__global__ __launch_bounds__(256) void k_farkas_fin(FkArgs a) {
+  __shared__ double s_v[4];
+  __shared__ int s_i[4];
+  const FkNode nd = a.nodes[blockIdx.x];
+  const int m = nd.m, n = a.n, lane = TIDX & 63, wave = TIDX >> 6;
+  FkAcc s;
+  double best = 0.0;
+  int bi = 0;
+  if (wave == 0) { // the interval rule on g
+    const double *__restrict__ gv = a.g + nd.voff, *__restrict__ lo = a.lo + nd.voff, *__restrict__ up = a.up + nd.voff;
+#pragma unroll 2
+    for (int k = lane + 1; k <= m + n; k += 64) fk_term(s, gv[k], lo[k], up[k]);
+    fk_reduce(s);
+  } else { // the largest de term, the lowest column among equals
+    const double *__restrict__ v = a.dterm + nd.voff + (size_t)m;
+    for (int j = TIDX - 63; j <= n; j += 192) {
+      const double w = v[j];
+      if (w > best) {
+        best = w;
+        bi = j;
+      }
+    }
+    for (int h = 32; h >= 1; h >>= 1) {
+      const double w = __shfl_xor(best, h);
+      const int wi = __shfl_xor(bi, h);
+      if (w > best || (w == best && wi < bi)) {
+        best = w;
+        bi = wi;
+      }
+    }
+    if (lane == 0) {
+      s_v[wave] = best;
+      s_i[wave] = bi;
+    }
+  }
+  __syncthreads();
+  if (TIDX != 0) return;
+  double *val = a.val + (size_t)blockIdx.x * 4;
+  int *ind = a.ind + (size_t)blockIdx.x * 4;
+  const int e = a.pick[blockIdx.x];
+  if (e < 0) {
+    val[0] = val[1] = val[2] = val[3] = 0.0;
+    ind[0] = ind[1] = ind[2] = ind[3] = 0;
+    return;
+  }
+  double de = s_v[1];
+  int dj = s_i[1];
+  for (int w = 2; w < 4; w++)
+    if (s_v[w] > de || (s_v[w] == de && s_i[w] < dj)) {
+      de = s_v[w];
+      dj = s_i[w];
+    }
+  const double rl = fk_rel_lo(s), rh = fk_rel_hi(s);
+  const bool upper = rh > rl; // the lower side before the upper
+  const double rel = upper ? rh : rl;
+  val[1] = rel;
+  val[2] = (upper ? s.ihi : s.ilo) != 0 ? -INFINITY : upper ? -s.hi : s.lo;
+  val[3] = de;
+  ind[0] = rel > FARKAS_REL ? 2 : 1;
+  ind[1] = (e >> 1) + 1;
+  ind[2] = (e & 1) + 1;
+  ind[3] = upper ? s.dhi : s.dlo;
+}
+
+void launch_farkas(const FkArgs &a0, hipStream_t s) {
+  for (int t0 = 0; t0 < a0.count; t0 += 32768) { // the handles ride on grid.y
+    FkArgs a = a0;
+    a.nodes += t0;
+    a.pick += t0;
+    a.val += (size_t)t0 * 4;
+    a.ind += (size_t)t0 * 4;
+    a.count = a0.count - t0 < 32768 ? a0.count - t0 : 32768;
+    const unsigned cnt = (unsigned)a.count;
+    const int longest = a.mmax > a.n ? a.mmax : a.n;
+    hipLaunchKernelGGL(k_farkas_rows, dim3((unsigned)((a.mmax + FARKAS_WAVES - 1) / FARKAS_WAVES), cnt), dim3(64 * FARKAS_WAVES), 0, s, a);
+    hipLaunchKernelGGL(k_farkas_pick, dim3(cnt), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_farkas_vars, dim3((unsigned)((longest + 255) / 256), cnt), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_farkas_cols, dim3((unsigned)((a.n + FARKAS_WAVES - 1) / FARKAS_WAVES), cnt), dim3(64 * FARKAS_WAVES), 0, s, a);
+    hipLaunchKernelGGL(k_farkas_fin, dim3(cnt), dim3(256), 0, s, a);
+  }
+}
+
+// ------------------------------------------------------------------ k_ray_cols / k_ray_pick / k_ray_vars / k_ray_rows / k_ray_fin
+// The ray of an unbounded handle (mvx_ray, DESIGN.md "Infeasibility and unboundedness proofs (farkas)").  Five launches:
+//  1. k_ray_cols, a thread per non-basic position q: the direction its status allows in which the published dual T[0][q] improves
+//     by more than RAY_TOL, provided its own bound on that side is infinite and no basic variable with |alpha_iq| > FARKAS_Z meets
+//     a finite bound on its way -- one walk down column q of the slab, coalesced across the threads;
+//  2. k_ray_pick, one workgroup: the lowest such position;
+//  3. k_ray_vars, a thread per (tableau row and non-basic position): the ray and the bounds by variable;
+//  4. k_ray_rows, a wave per model row: rho_r = dR_r - sum_j a_rj dS_j by kkt_row_sum, the row's ae and re terms;
+//  5. k_ray_fin, one workgroup: wave 0 the slope sum_j c_j dS_j in the same 64 chains, waves 1..3 the largest ae and re (the lowest
+//     row among equals) and the variables whose bound blocks the ray; thread 0 writes val / ind.
+__global__ __launch_bounds__(256) void k_ray_cols(RayArgs a) {
+  const NodeRef nd = a.nd;
+  const int q = (int)blockIdx.x * 256 + TIDX + 1;
+  if (q > a.n) return;
+  const double e = a.sg * nd.T[q];
+  const int f = nd.nflag[q];
+  int sigma = 0;
+  if (e < -RAY_TOL && (f == MVX_NL || f == MVX_NF)) sigma = 1;
+  else if (e > RAY_TOL && (f == MVX_NU || f == MVX_NF)) sigma = -1;
+  if (sigma != 0 && (sigma > 0 ? nd.nub[q] != INFINITY : nd.nlb[q] != -INFINITY)) sigma = 0;
+  if (sigma != 0) {
+    const double sd = (double)sigma;
+    const double *__restrict__ col = nd.T + (size_t)q;
+    for (int i = 1; i <= nd.m; i++) {
+      const double al = col[(size_t)i * (size_t)nd.ld], mv = sd * al;
+      if (fabs(al) <= FARKAS_Z) continue;
+      if (mv > 0.0 ? a.bub[i] != INFINITY : a.blb[i] != -INFINITY) {
+        sigma = 0;
+        break;
+      }
+    }
+  }
+  a.open[q] = sigma;
+}
+
+__global__ __launch_bounds__(256) void k_ray_pick(RayArgs a) {
+  __shared__ int s_q[4];
+  const int lane = TIDX & 63, wave = TIDX >> 6;
+  int best = 0x7fffffff;
+  for (int q = 1 + TIDX; q <= a.n; q += 256)
+    if (a.open[q] != 0 && q < best) best = q;
+  for (int h = 32; h >= 1; h >>= 1) {
+    const int w = __shfl_xor(best, h);
+    if (w < best) best = w;
+  }
+  if (lane == 0) s_q[wave] = best;
+  __syncthreads();
+  if (TIDX == 0) {
+    for (int w = 1; w < 4; w++)
+      if (s_q[w] < best) best = s_q[w];
+    a.pick[0] = best == 0x7fffffff ? 0 : best;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_ray_vars(RayArgs a) {
+  const NodeRef nd = a.nd;
+  const int m = nd.m, n = a.n, qp = a.pick[0];
+  const double sd = qp > 0 ? (double)a.open[qp] : 0.0;
+  const int g = (int)blockIdx.x * 256 + TIDX + 1; // tableau row g and non-basic position g
+  if (g <= m) {
+    const int k = nd.bvar[g];
+    if (k >= 1 && k <= m + n) {
+      a.d[k] = qp > 0 ? sd * nd.T[(size_t)g * (size_t)nd.ld + (size_t)qp] : 0.0;
+      a.lo[k] = a.blb[g];
+      a.up[k] = a.bub[g];
+    }
+  }
+  if (g <= n) {
+    const int k = nd.nvar[g];
+    if (k >= 1 && k <= m + n) {
+      a.d[k] = g == qp ? sd : 0.0;
+      a.lo[k] = nd.nlb[g];
+      a.up[k] = nd.nub[g];
+    }
+  }
+}
+
+__global__ __launch_bounds__(64 * KKT_WAVES) void k_ray_rows(RayArgs a) {
+  const int lane = TIDX & 63, i = (int)blockIdx.x * KKT_WAVES + (TIDX >> 6) + 1;
+  if (i > a.nd.m) return;
+  const double acc = kkt_row_sum(a.Ar + (size_t)(i - 1) * (size_t)a.ldn, a.d + a.nd.m, a.n, lane);
+  if (lane != 0) return;
+  const double dr = a.d[i], ae = fabs(dr - acc);
+  a.rae[i] = ae;
+  a.rre[i] = xdiv(ae, 1.0 + fabs(dr));
+}
+
+__global__ __launch_bounds__(256) void k_ray_fin(RayArgs a) {
+  __shared__ double s_ae[4], s_re[4];
+  __shared__ int s_ai[4], s_ri[4], s_bl[4];
+  const int m = a.nd.m, n = a.n, lane = TIDX & 63, wave = TIDX >> 6;
+  double slope = 0.0;
+  if (wave == 0) {
+    slope = kkt_row_sum(a.c, a.d + m, n, lane);
+  } else {
+    double ae = 0.0, re = 0.0;
+    int ai = 0, ri = 0, bl = 0;
+    for (int i = TIDX - 63; i <= m; i += 192) {
+      const double w = a.rae[i], r = a.rre[i];
+      if (w > ae) { ae = w; ai = i; }
+      if (r > re) { re = r; ri = i; }
+    }
+    for (int k = TIDX - 63; k <= m + n; k += 192) {
+      const double v = a.d[k];
+      if (fabs(v) <= FARKAS_Z) continue; // the zero rule
+      if (v > 0.0 ? a.up[k] != INFINITY : a.lo[k] != -INFINITY) bl++;
+    }
+    for (int h = 32; h >= 1; h >>= 1) {
+      const double w = __shfl_xor(ae, h), r = __shfl_xor(re, h);
+      const int wi = __shfl_xor(ai, h), qi = __shfl_xor(ri, h);
+      if (w > ae || (w == ae && wi < ai)) { ae = w; ai = wi; }
+      if (r > re || (r == re && qi < ri)) { re = r; ri = qi; }
+      bl += __shfl_xor(bl, h);
+    }
+    if (lane == 0) {
+      s_ae[wave] = ae; s_ai[wave] = ai; s_re[wave] = re; s_ri[wave] = ri; s_bl[wave] = bl;
+    }
+  }
+  __syncthreads();
+  if (TIDX != 0) return;
+  const int qp = a.pick[0];
+  if (qp == 0) {
+    a.val[0] = a.val[1] = a.val[2] = a.val[3] = 0.0;
+    for (int t = 0; t < 6; t++) a.ind[t] = 0;
+    return;
+  }
+  double ae = s_ae[1], re = s_re[1];
+  int ai = s_ai[1], ri = s_ri[1], bl = s_bl[1];
+  for (int w = 2; w < 4; w++) {
+    if (s_ae[w] > ae || (s_ae[w] == ae && s_ai[w] < ai)) { ae = s_ae[w]; ai = s_ai[w]; }
+    if (s_re[w] > re || (s_re[w] == re && s_ri[w] < ri)) { re = s_re[w]; ri = s_ri[w]; }
+    bl += s_bl[w];
+  }
+  a.val[0] = a.nd.T[qp];
+  a.val[1] = ae;
+  a.val[2] = re;
+  a.val[3] = slope;
+  a.ind[0] = (a.sg * slope < 0.0 && re <= RAY_TOL && bl == 0) ? 2 : 1;
+  a.ind[1] = a.nd.nvar[qp];
+  a.ind[2] = a.open[qp];
+  a.ind[3] = bl;
+  a.ind[4] = ai;
+  a.ind[5] = ri;
+}
+
+void launch_ray(const RayArgs &a, hipStream_t s) {
+  const int m = a.nd.m, longest = m > a.n ? m : a.n;
+  hipLaunchKernelGGL(k_ray_cols, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_ray_pick, dim3(1), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_ray_vars, dim3((unsigned)((longest + 255) / 256)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_ray_rows, dim3((unsigned)((m + KKT_WAVES - 1) / KKT_WAVES)), dim3(64 * KKT_WAVES), 0, s, a);
+  hipLaunchKernelGGL(k_ray_fin, dim3(1), dim3(256), 0, s, a);
 }
 
 // ---------------------------------------------------------------------------- k_round

@@ -127,7 +127,7 @@ class _Node:
 
 def branch_and_bound(engine, root, var_strat=0, quirks=1, max_nodes=0, loop_limit=200000, per_rank=1, group=None,
                      cut_strat=0, lazy_pool=1, cut_select=0, cut_chance=1.0, deal="owner", slack=None, heur=0, rc_fix=0, prop=0, dive=0, pump=0, cut_rounds=0, polish=0, node_purge=0,
-                     node_cliques=0, kkt=0):
+                     node_cliques=0, kkt=0, farkas=0):
     """Serial-equivalent FIFO branch-and-bound over all ranks of `group`.
 
     `root` is this rank's handle of the (identical) root problem.  Returns the same dictionary as
@@ -160,6 +160,8 @@ def branch_and_bound(engine, root, var_strat=0, quirks=1, max_nodes=0, loop_limi
         raise ValueError("dist_bnb.branch_and_bound: node_cliques %r is not supported (0 only)" % (node_cliques,))
     if kkt:  # nor is the KKT check of the node LPs
         raise ValueError("dist_bnb.branch_and_bound: kkt %r is not supported (0 only)" % (kkt,))
+    if farkas:  # nor is the Farkas proof of the infeasible ones
+        raise ValueError("dist_bnb.branch_and_bound: farkas %r is not supported (0 only)" % (farkas,))
     import torch.distributed as dist
 
     if dist.is_available() and dist.is_initialized():

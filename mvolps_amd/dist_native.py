@@ -241,7 +241,7 @@ class RcclComm:
 
 def branch_and_bound(root, comm=None, table=None, image=None, per_rank=64, slack=None, deal="owner", var_strat=0, cut_strat=0, max_nodes=0,
                      quirks=1, lazy_pool=1, cut_select=0, cut_chance=1.0, heur=0, rc_fix=0, prop=0, dive=0, pump=0, cut_rounds=0, polish=0, node_purge=0,
-                     node_cliques=0, kkt=0):
+                     node_cliques=0, kkt=0, farkas=0):
     """mvx_branchAndBound_dist on this rank's handle `root` of the root problem.  table / image None: the gfx950
     engine's own tables.  Returns mvolps_amd.bnb.branch_and_bound's dictionary (identical on every rank) plus `dist`."""
     if var_strat not in (0, 1, 2):  # var_strat 3 / 4 read the node LP's penalties: refused by the coordinator too
@@ -266,6 +266,8 @@ def branch_and_bound(root, comm=None, table=None, image=None, per_rank=64, slack
         raise ValueError("dist_native.branch_and_bound: node_cliques %r is not supported (0 only)" % (node_cliques,))
     if kkt:  # nor is the KKT check of the node LPs
         raise ValueError("dist_native.branch_and_bound: kkt %r is not supported (0 only)" % (kkt,))
+    if farkas:  # nor is the Farkas proof of the infeasible ones
+        raise ValueError("dist_native.branch_and_bound: farkas %r is not supported (0 only)" % (farkas,))
     L = _lib()
     pr = bnb.make_params(var_strat, 0, cut_strat, max_nodes, quirks, lazy_pool, None, cut_select, cut_chance)
     dp = DistParams()
