@@ -381,6 +381,73 @@ int mvx_get_mat_col(const mvx_prob *P, int j, int *ind, double *val);
    the model has lost the columns and the tableau is given up, as mvx_add_cut_rows gives it up. */
 int mvx_del_cols(mvx_prob *P, int ncs, const int *num);
 int mvx_del_cols_span(void); /* destination positions a wave of k_delcols moves per batch */
+/* Sifting (DESIGN.md "Sifting (sift)"): an LP far wider than the tableau one wants to stream is solved over a narrow working LP and
+   a pool of the other columns that lives on the device.
+   The pool holds dense columns over m rows, numbered 1..N in the order given.  mvx_pool_add_cols takes exactly the arguments of
+   mvx_add_dense_cols (cols is k x (m+1) row-major, entry 0 of a column is not read) and refuses what that call refuses.  It also
+   refuses a column that cannot rest at zero: after the bounds are read as mvx_set_col_bnds reads them, the value the column would
+   rest at as a new non-basic column must be 0 -- MVX_LO / MVX_DB with lb = 0, MVX_UP with ub = 0, MVX_FR, MVX_FX at 0.  A pool
+   column that is absent from the working LP therefore means "at 0", and sifting is sound without shifting right-hand sides.  A
+   refused call returns -1 and changes nothing.  The pool keeps a host copy and a device copy; the device copy is made by the
+   first call that needs the device (mvx_pool_price, mvx_pool_append on a handle with a tableau, mvx_sift) and extended after
+   later mvx_pool_add_cols calls, so create / add / num / get / delete and every refusal run without a device.
+   mvx_pool_get_col: column j as it was given (any output may be NULL; col has m+1 entries, col[0] = 0); -1 for j outside 1..N. */
+typedef struct mvx_colpool mvx_colpool;
+mvx_colpool *mvx_pool_create(int m);
+int mvx_pool_add_cols(mvx_colpool *S, int k, const double *cols, const double *obj, const int *type, const double *lb, const double *ub,
+                      const int *kind);
+int mvx_pool_num_cols(const mvx_colpool *S);
+int mvx_pool_num_rows(const mvx_colpool *S);
+int mvx_pool_get_col(const mvx_colpool *S, int j, double *col, double *obj, int *type, double *lb, double *ub, int *kind);
+void mvx_pool_delete(mvx_colpool *S);
+/* The reduced cost of every pool column against the handle's duals, and the K most attractive columns, in one stream over the
+   device pool (k_poolprice) and a selection on the device (k_poolsel_*).  y_i, i = 1..m, is the row-0 tableau entry at the
+   non-basic position of the auxiliary variable of row i, +0.0 when it is basic (the numbers mvx_price_cols weights by), and
+   d_j = obj_j + S_j, S_j = sum_i (-a_ij) y_i in 64 chains: chain l takes i = l+1, l+65, ... ascending with fma(-a_ij, y_i, acc)
+   from +0.0, rows with y_i == 0 skipped; the chains are combined by s[l] += s[l+h], h = 32 .. 1; obj_j is added last.
+   dj (nullable) [N+1] receives d_j, dj[0] = 0.  Column j is attractive by the engine's primal pricing rule on the status it would
+   enter with, sgn = +1 under MVX_MAX and -1 under MVX_MIN: MVX_LO / MVX_DB sgn d_j > tol_dj, MVX_UP sgn d_j < -tol_dj, MVX_FR
+   |d_j| > tol_dj, MVX_FX never; tol_dj is mvx_init_smcp's.  A column with skip[j] != 0 is never picked (skip nullable, [N+1],
+   skip[0] not read); its d_j is written all the same.  pick[0 .. *npick-1] are the min(K, #attractive) attractive columns of
+   largest |d_j| in descending order of |d_j|, ties to the lower j; K >= 0, K = 0 prices only (pick may then be NULL).  Pure: the
+   handle is only read.  Bit-identical to mvx_bnb_pool_price_values + mvx_bnb_pool_select (mvx_bnb.h).  Returns 0; -1 a null, K < 0
+   or a pool of another row count than the handle; -2 device out of memory, nothing written; -3 the handle has no valid tableau or
+   its status is MVX_UNDEF. */
+int mvx_pool_price(const mvx_prob *P, const mvx_colpool *S, const unsigned char *skip, int K, double *dj, int *pick, int *npick);
+/* The distinct pool columns idx[0..k-1] join the handle exactly as mvx_add_dense_cols(P, k, ...) with those columns' data in that
+   order: model, tableau, basis arrays, mirrors and status end with the same bits, and the return codes are the same.  With a
+   valid tableau the coefficients do not travel from the host: k_poolgather lays them out from the device pool for k_addcols.
+   Without one the call is the model edit only.  -1 also for an index outside 1..N, a duplicate, or another row count. */
+int mvx_pool_append(mvx_prob *P, const mvx_colpool *S, int k, const int *idx);
+/* The sifting loop.  where[1..N] is in / out: 0, or the column of P that already is pool column j (a first call passes zeros, a
+   later call -- after a bound edit, say -- what the last one returned).  Columns of P that no entry names are the caller's own and
+   never leave.  A round: mvx_simplex(P, parm) (parm->it_lim limits each solve); unless the status is MVX_OPT the loop ends with
+   that status; otherwise mvx_pool_price over the absent columns with K; when nothing is attractive the loop ends, and P is optimal
+   for the full LP with every absent column at 0; otherwise the picks are appended (mvx_pool_append) and, with purge = A > 0,
+   every pool column of P that the last A solves in a row left non-basic at 0 -- where an absent column rests; a non-basic column at
+   a non-zero upper bound is in use and stays -- leaves through one mvx_del_cols call (a column appended in this round stays),
+   `where` following the renumbering.
+   info->end tells what ended the loop: MVX_OPT -- optimal for the FULL LP; MVX_UNBND -- the working LP is unbounded, and so is the
+   full LP; MVX_NOFEAS / MVX_INFEAS / MVX_UNDEF / MVX_FEAS -- the status of the WORKING LP only: it says NOTHING about the full LP
+   (an infeasible working LP may become feasible with absent columns; pricing them by a Farkas proof is not built); 0 -- the round
+   limit.  Returns 0; -1 a null, another row count, K < 1, max_rounds < 1, purge outside 0..64, or a `where` entry that is out of
+   range, names a column twice or names a column of P whose coefficients or objective coefficient differ from the pool's (bounds
+   are P's own to edit), nothing changed; -2 device out of memory, the handle as the failing call left it; -4 max_rounds rounds
+   ran and attractive columns are still on offer: P is a valid, solved working LP.  sp == NULL: the defaults; info nullable.
+   mvx_init_sift_parm fills the defaults for a pool over m rows: K = max(m, 64), max_rounds = 200, purge = 0. */
+typedef struct {
+  int K;          /* columns appended per round at most */
+  int max_rounds; /* rounds (solves) at most */
+  int purge;      /* 0: off; A: a pool column non-basic at 0 after A consecutive solves leaves */
+} mvx_sift_parm;
+typedef struct {
+  int rounds, lps;
+  long long priced, appended, purged, pivots;
+  int n_final; /* P's columns at the end */
+  int end;
+} mvx_sift_info;
+void mvx_init_sift_parm(mvx_sift_parm *sp, int m);
+int mvx_sift(mvx_prob *P, const mvx_colpool *S, const mvx_smcp *parm, const mvx_sift_parm *sp, int *where, mvx_sift_info *info);
 /* Clique cuts (DESIGN.md "Clique cuts (cut_families)"): the conflict graph of the binary columns of `model` (integer, bounds 0
    and 1 exactly), two device launches (k_conflict_rows, k_conflict).  Columns j < k are adjacent when one of rows 1..m (m the
    handle's row count) forbids x_j = x_k = 1 with every other term at its least: (Lmin_i + a_ij) + a_ik > rub_i + tol(rub_i) on

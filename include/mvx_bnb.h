@@ -442,6 +442,18 @@ int mvx_bnb_ray(const mvx_lp_api *api, const void *prob, double *val, int *ind, 
    as mvx_price_cols: 64 chains over the non-basic positions, the written tree, the base added last.  Returns 0; -1 bad
    arguments; -2 the table lacks an accessor it needs (or get_tableau / get_basis failed) */
 int mvx_bnb_price_cols(const mvx_lp_api *api, const void *prob, int k, const double *cols, const double *obj, double *dj, double *img);
+
+/* Sifting (DESIGN.md "Sifting (sift)"), the host twins of mvx_pool_price from numbers only.  mvx_bnb_pool_price_values: cols is
+   N x (m+1) row-major as mvx_pool_add_cols takes it (row t is pool column t + 1, its entry 0 is not read), obj[N] and type[N]
+   likewise by t, y[0..m] the row weights (y[0] is not read), dir MVX_MIN or MVX_MAX, tol the dual tolerance.  dj[0..N] receives
+   dj[0] = 0 and d_j = obj_j + S_j in the written order of mvx_pool_price (64 chains over the rows with fma(-a_ij, y_i, acc) from
+   +0.0, rows with y_i == 0 skipped, s[l] += s[l+h] for h = 32 .. 1, obj_j last); attractive (nullable) [0..N] the rule of
+   mvx_pool_price on the status a column of type[t] enters with, attractive[0] = 0.  mvx_bnb_pool_select: of the columns j = 1..N
+   with attractive[j] != 0 and skip[j] == 0 (skip nullable) the min(K, count) of largest |dj[j]| (by its bits), descending, ties to
+   the lower j, into pick[0 .. *npick-1].  Both return 0, or -1 for bad arguments. */
+int mvx_bnb_pool_price_values(int m, int N, const double *cols, const double *obj, const int *type, const double *y, int dir, double tol,
+                              double *dj, unsigned char *attractive);
+int mvx_bnb_pool_select(int N, const double *dj, const unsigned char *attractive, const unsigned char *skip, int K, int *pick, int *npick);
 /* The text report of those tables, one line per variable k = 1..m+n, written to `path` (NULL: stdout):
      k name st value act_dn lim_dn act_up lim_up obj_dn obj_up cost_dn ent_dn cost_up ent_up
    name is R<i> for an auxiliary and the column's name, or C<j> without one, for a structural (names are read from the gfx950

@@ -8,6 +8,7 @@ import ctypes as C
 import os
 
 from . import capi
+from .capi import Pool, SiftInfo, SiftParm  # noqa: F401  (sifting: a column pool and the loop's parameters and counters)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libmvolps_amd.so")
@@ -33,6 +34,20 @@ _EXTRA = {
     "price_cols_tile": (C.c_int, []),
     "del_cols": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "del_cols_span": (C.c_int, []),
+    "pool_create": (C.c_void_p, [C.c_int]),
+    "pool_add_cols": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int),
+                                C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "pool_num_cols": (C.c_int, [C.c_void_p]),
+    "pool_num_rows": (C.c_int, [C.c_void_p]),
+    "pool_get_col": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int),
+                               C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "pool_delete": (None, [C.c_void_p]),
+    "pool_price": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_ubyte), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int),
+                             C.POINTER(C.c_int)]),
+    "pool_append": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "init_sift_parm": (None, [C.POINTER(capi.SiftParm), C.c_int]),
+    "sift": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(capi.Smcp), C.POINTER(capi.SiftParm), C.POINTER(C.c_int),
+                       C.POINTER(capi.SiftInfo)]),
     "set_mat_col": (None, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     "get_mat_col": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     "device_count": (C.c_int, []),
@@ -105,3 +120,8 @@ def require_device():
 def create_prob():
     require_device()
     return api().create()
+
+
+def create_pool(m):
+    """A column pool over m rows (capi.Pool); its model layer needs no device."""
+    return capi.Pool(api(), m)

@@ -381,6 +381,11 @@ def _bind(lib):
     lib.mvx_bnb_price_cols.argtypes = [C.c_void_p, C.c_void_p, C.c_int, _DP, _DP, _DP, _DP]
     lib.mvx_del_cols.restype = C.c_int
     lib.mvx_del_cols.argtypes = [C.c_void_p, C.c_int, _IP]
+    _UP = C.POINTER(C.c_ubyte)
+    lib.mvx_bnb_pool_price_values.restype = C.c_int
+    lib.mvx_bnb_pool_price_values.argtypes = [C.c_int, C.c_int, _DP, _DP, _IP, _DP, C.c_int, C.c_double, _DP, _UP]
+    lib.mvx_bnb_pool_select.restype = C.c_int
+    lib.mvx_bnb_pool_select.argtypes = [C.c_int, _DP, _UP, _UP, C.c_int, _IP, _IP]
     lib.mvx_del_cols_span.restype = C.c_int
     lib.mvx_del_cols_span.argtypes = []
     lib.mvx_generateCutGMI.restype = C.c_int
@@ -798,6 +803,48 @@ def ranges(prob, table=False):
         tptr = C.cast(C.pointer(table), C.c_void_p) if table is not None else None
         rc = lib().mvx_bnb_ranges(tptr, prob.h, val.ctypes.data_as(DP), var.ctypes.data_as(IP))
     return rc, val, var
+
+
+def pool_price_values(cols, obj, types, y, direction, tol):
+    """mvx_bnb_pool_price_values, the host twin of mvx_pool_price's pricing pass, from numbers only: cols (N, m) or (N, m+1) as
+    Pool.add_cols takes them, obj / types one entry per column, y[0..m] the row weights (y[0] unused).  Returns (rc, dj[0..N],
+    attractive[0..N])."""
+    import numpy as np
+
+    obj = np.ascontiguousarray(np.atleast_1d(obj), dtype=np.float64)
+    N = len(obj)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    m = len(y) - 1
+    cols = np.asarray(cols, dtype=np.float64).reshape(N, -1)
+    if cols.shape[1] == m:
+        cols = np.hstack([np.zeros((N, 1)), cols])
+    cols = np.ascontiguousarray(cols, dtype=np.float64)
+    assert cols.shape == (N, m + 1)
+    types = np.ascontiguousarray(np.atleast_1d(types), dtype=np.int32)
+    dj = np.zeros(N + 1, dtype=np.float64)
+    att = np.zeros(N + 1, dtype=np.uint8)
+    DP, IP, UP = C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_ubyte)
+    rc = lib().mvx_bnb_pool_price_values(m, N, cols.ctypes.data_as(DP), obj.ctypes.data_as(DP), types.ctypes.data_as(IP), y.ctypes.data_as(DP),
+                                         int(direction), float(tol), dj.ctypes.data_as(DP), att.ctypes.data_as(UP))
+    return rc, dj, att
+
+
+def pool_select(dj, attractive, K, skip=None):
+    """mvx_bnb_pool_select, the host twin of mvx_pool_price's selection: dj / attractive / skip [0..N].  Returns (rc, picks)."""
+    import numpy as np
+
+    dj = np.ascontiguousarray(dj, dtype=np.float64)
+    N = len(dj) - 1
+    att = np.ascontiguousarray(attractive, dtype=np.uint8)
+    DP, IP, UP = C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_ubyte)
+    sp = None
+    if skip is not None:
+        skip = np.ascontiguousarray(skip, dtype=np.uint8)
+        sp = skip.ctypes.data_as(UP)
+    pick = np.zeros(max(K, 1), dtype=np.int32)
+    npick = C.c_int(0)
+    rc = lib().mvx_bnb_pool_select(N, dj.ctypes.data_as(DP), att.ctypes.data_as(UP), sp, K, pick.ctypes.data_as(IP), C.byref(npick))
+    return rc, pick[: npick.value].copy()
 
 
 def price_cols(prob, cols, obj, table=False):

@@ -29,6 +29,23 @@ class Smcp(C.Structure):
     ]
 
 
+class SiftParm(C.Structure):
+    _fields_ = [("K", C.c_int), ("max_rounds", C.c_int), ("purge", C.c_int)]
+
+
+class SiftInfo(C.Structure):
+    _fields_ = [
+        ("rounds", C.c_int),
+        ("lps", C.c_int),
+        ("priced", C.c_longlong),
+        ("appended", C.c_longlong),
+        ("purged", C.c_longlong),
+        ("pivots", C.c_longlong),
+        ("n_final", C.c_int),
+        ("end", C.c_int),
+    ]
+
+
 _P = C.c_void_p
 _I = C.c_int
 _D = C.c_double
@@ -126,6 +143,59 @@ class LpApi:
 
     def create(self):
         return Prob(self)
+
+
+class Pool:
+    """mvx_colpool (the gfx950 engine's library only): a pool of dense columns over m rows for sifting (DESIGN.md "Sifting (sift)").
+    Its model layer -- add_cols, n, get_col -- needs no device."""
+
+    def __init__(self, api, m):
+        self.api = api
+        self.h = api.pool_create(m)
+        if not self.h:
+            raise ValueError("pool_create: m must not be negative")
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            try:
+                self.api.pool_delete(self.h)
+            except Exception:
+                pass
+            self.h = None
+
+    @property
+    def m(self):
+        return self.api.pool_num_rows(self.h)
+
+    @property
+    def n(self):
+        return self.api.pool_num_cols(self.h)
+
+    def add_cols(self, cols, obj, types, lb, ub, kinds=None):
+        """mvx_pool_add_cols: the arguments of Prob.add_dense_cols.  Returns 0, or -1 with nothing changed."""
+        obj = np.ascontiguousarray(np.atleast_1d(obj), dtype=np.float64)
+        k = len(obj)
+        cols = _cols_block(cols, k, self.m)
+        types = np.ascontiguousarray(np.atleast_1d(types), dtype=np.int32)
+        lb = np.ascontiguousarray(np.atleast_1d(lb), dtype=np.float64)
+        ub = np.ascontiguousarray(np.atleast_1d(ub), dtype=np.float64)
+        if not (len(types) == len(lb) == len(ub) == k):
+            raise ValueError("add_cols: obj, types, lb and ub need one entry per column")
+        kp = None
+        if kinds is not None:
+            kinds = np.ascontiguousarray(np.atleast_1d(kinds), dtype=np.int32)
+            if len(kinds) != k:
+                raise ValueError("add_cols: kinds needs one entry per column")
+            kp = _ip(kinds)
+        return self.api.pool_add_cols(self.h, k, _dp(cols), _dp(obj), _ip(types), _dp(lb), _dp(ub), kp)
+
+    def get_col(self, j):
+        """mvx_pool_get_col: (rc, col[0..m], obj, type, lb, ub, kind) of pool column j as it was given."""
+        col = np.zeros(self.m + 1, dtype=np.float64)
+        obj, lb, ub = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+        ty, kind = C.c_int(0), C.c_int(0)
+        rc = self.api.pool_get_col(self.h, j, _dp(col), C.byref(obj), C.byref(ty), C.byref(lb), C.byref(ub), C.byref(kind))
+        return rc, col, obj.value, ty.value, lb.value, ub.value, kind.value
 
 
 class Prob:
@@ -239,6 +309,52 @@ class Prob:
         img = np.zeros((k, m + 1), dtype=np.float64)
         rc = self.api.price_cols(self.h, k, _dp(cols), _dp(obj), _dp(dj), _dp(img))
         return rc, dj, img
+
+    def pool_price(self, pool, K=0, skip=None, want_dj=True):
+        """mvx_pool_price (the gfx950 engine's library only): the reduced costs dj[0..N] of every column of `pool` against this
+        handle's duals (None with want_dj=False) and the K most attractive columns, in descending |dj|.  skip: N+1 flags, entry 0
+        unused.  Returns (rc, dj, picks)."""
+        N = pool.n
+        dj = np.zeros(N + 1, dtype=np.float64) if want_dj else None
+        pick = np.zeros(max(min(K, N), 1), dtype=np.int32)
+        npick = C.c_int(0)
+        sp = None
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, dtype=np.uint8)
+            if len(skip) != N + 1:
+                raise ValueError("pool_price: skip needs N + 1 entries")
+            sp = skip.ctypes.data_as(C.POINTER(C.c_ubyte))
+        rc = self.api.pool_price(self.h, pool.h, sp, K, _dp(dj) if want_dj else None, _ip(pick), C.byref(npick))
+        return rc, dj, pick[: npick.value].copy()
+
+    def pool_append(self, pool, idx):
+        """mvx_pool_append: the distinct 1-based pool columns idx join the handle as add_dense_cols would append them."""
+        idx = np.ascontiguousarray(np.atleast_1d(idx), dtype=np.int32)
+        return self.api.pool_append(self.h, pool.h, len(idx), _ip(idx))
+
+    def sift(self, pool, where=None, K=None, max_rounds=None, purge=None, it_lim=None):
+        """mvx_sift: solves this working LP plus the columns of `pool` by sifting.  where: N+1 ints (entry 0 unused), 0 or the column
+        of this handle that already is pool column j; None: zeros.  Returns (rc, where, info) with info a SiftInfo."""
+        N = pool.n
+        where = np.zeros(N + 1, dtype=np.int32) if where is None else np.ascontiguousarray(where, dtype=np.int32).copy()
+        if len(where) != N + 1:
+            raise ValueError("sift: where needs N + 1 entries")
+        sp = SiftParm()
+        self.api.init_sift_parm(C.byref(sp), self.m)
+        if K is not None:
+            sp.K = K
+        if max_rounds is not None:
+            sp.max_rounds = max_rounds
+        if purge is not None:
+            sp.purge = purge
+        parm = None
+        if it_lim is not None:
+            parm = Smcp()
+            self.api.init_smcp(C.byref(parm))
+            parm.it_lim = it_lim
+        info = SiftInfo()
+        rc = self.api.sift(self.h, pool.h, C.byref(parm) if parm is not None else None, C.byref(sp), _ip(where), C.byref(info))
+        return rc, where, info
 
     def set_mat_col(self, j, ind, val):
         """mvx_set_mat_col: GLPK's shape, ind[0] / val[0] ignored."""

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/mvx_bnb.h"
+#include "sift_host.hpp"
 
 extern "C" int mvx_classify_many(const mvx_prob *const *Ps, int count, int quirks, int *status, int *nviol, int *viol, double *xviol,
                                  int cap) __attribute__((weak));
@@ -5014,6 +5015,28 @@ int mvx_bnb_price_cols(const mvx_lp_api *api, const void *prob, int k, const dou
       if (p == 0) dj[t] = v;
     }
   }
+  return 0;
+}
+
+// The host twins of mvx_pool_price, from numbers only (DESIGN.md "Sifting (sift)"; the loops are sift_host.hpp's): the reduced
+// costs in the written order with the attractive rule, and the selection.
+int mvx_bnb_pool_price_values(int m, int N, const double *cols, const double *obj, const int *type, const double *y, int dir, double tol,
+                              double *dj, unsigned char *attractive) {
+  if (m < 0 || N < 0 || !dj || (N > 0 && (!cols || !obj || !type)) || (m > 0 && !y) || (dir != MVX_MIN && dir != MVX_MAX)) return -1;
+  const size_t crow = (size_t)m + 1;
+  const double sgn = dir == MVX_MAX ? 1.0 : -1.0;
+  dj[0] = 0.0;
+  if (attractive) attractive[0] = 0;
+  for (int j = 1; j <= N; j++) {
+    const double d = mvx_sifting::price_one(m, cols + (size_t)(j - 1) * crow + 1, y, obj[j - 1]);
+    dj[j] = d;
+    if (attractive) attractive[j] = mvx_sifting::attractive(mvx_sifting::flag_of(type[j - 1]), d, sgn, tol) ? 1 : 0;
+  }
+  return 0;
+}
+int mvx_bnb_pool_select(int N, const double *dj, const unsigned char *attractive, const unsigned char *skip, int K, int *pick, int *npick) {
+  if (N < 0 || K < 0 || !dj || !attractive || !npick || (K > 0 && !pick)) return -1;
+  mvx_sifting::select(N, dj, attractive, skip, K, pick, npick);
   return 0;
 }
 

@@ -289,19 +289,12 @@ int mvx_add_cols(mvx_prob *P, int ncs) {
   return first;
 }
 
-int mvx_add_dense_cols(mvx_prob *P, int k, const double *cols, const double *obj, const int *type, const double *lb, const double *ub,
-                       const int *kind) {
-  if (!P || k < 1 || !cols || !obj || !type || !lb || !ub) return -1;
+// mvx_add_dense_cols behind its argument checks; with a pool S the columns are its columns idx[0..k) (mvx_pool_append: cols holds
+// their host copy for the model, the tableau takes them from the pool's device copy)
+static int add_dense_cols_checked(mvx_prob *P, int k, const double *cols, const double *obj, const int *type, const double *lb,
+                                  const double *ub, const int *kind, const mvx_colpool *S, const int *idx) {
   const int m = P->m, n = P->n;
   const size_t crow = (size_t)m + 1;
-  for (int t = 0; t < k; t++) {
-    if (type[t] < MVX_FR || type[t] > MVX_FX) return -1;
-    if (std::isnan(obj[t]) || std::isnan(lb[t]) || std::isnan(ub[t])) return -1;
-    if (type[t] == MVX_DB && lb[t] > ub[t]) return -1;
-    if (kind && kind[t] != MVX_CV && kind[t] != MVX_IV) return -1;
-    for (int i = 1; i <= m; i++)
-      if (std::isnan(cols[(size_t)t * crow + (size_t)i])) return -1;
-  }
   // the model: what add_cols + set_mat_col + set_col_bnds + set_obj_coef + set_col_kind write
   std::vector<int> flag((size_t)k);
   std::vector<double> nlb((size_t)k), nub((size_t)k);
@@ -327,7 +320,23 @@ int mvx_add_dense_cols(mvx_prob *P, int k, const double *cols, const double *obj
   }
   P->status = MVX_UNDEF;
   if (!P->valid) return 0;
-  return mvx::engine_add_cols_live(P, k, cols, obj, flag.data(), nlb.data(), nub.data());
+  return mvx::engine_add_cols_live(P, k, cols, obj, flag.data(), nlb.data(), nub.data(), S, idx);
+}
+
+int mvx_add_dense_cols(mvx_prob *P, int k, const double *cols, const double *obj, const int *type, const double *lb, const double *ub,
+                       const int *kind) {
+  if (!P || k < 1 || !cols || !obj || !type || !lb || !ub) return -1;
+  const int m = P->m;
+  const size_t crow = (size_t)m + 1;
+  for (int t = 0; t < k; t++) {
+    if (type[t] < MVX_FR || type[t] > MVX_FX) return -1;
+    if (std::isnan(obj[t]) || std::isnan(lb[t]) || std::isnan(ub[t])) return -1;
+    if (type[t] == MVX_DB && lb[t] > ub[t]) return -1;
+    if (kind && kind[t] != MVX_CV && kind[t] != MVX_IV) return -1;
+    for (int i = 1; i <= m; i++)
+      if (std::isnan(cols[(size_t)t * crow + (size_t)i])) return -1;
+  }
+  return add_dense_cols_checked(P, k, cols, obj, type, lb, ub, kind, nullptr, nullptr);
 }
 
 int mvx_del_cols(mvx_prob *P, int ncs, const int *num) {
@@ -391,6 +400,155 @@ int mvx_price_cols(const mvx_prob *P, int k, const double *cols, const double *o
   return mvx::engine_price_cols(P, k, cols, obj, dj, img);
 }
 int mvx_price_cols_tile(void) { return ADDCOLS_CT; }
+
+// ---- sifting over a column pool (DESIGN.md "Sifting (sift)") ----
+mvx_colpool *mvx_pool_create(int m) {
+  if (m < 0) return nullptr;
+  mvx_colpool *S = new mvx_colpool();
+  mvx_sifting::pool_init(S->h, m);
+  return S;
+}
+int mvx_pool_add_cols(mvx_colpool *S, int k, const double *cols, const double *obj, const int *type, const double *lb, const double *ub,
+                      const int *kind) {
+  if (!S) return -1;
+  return mvx_sifting::pool_add(S->h, k, cols, obj, type, lb, ub, kind); // the device copy follows at the next call that needs it
+}
+int mvx_pool_num_cols(const mvx_colpool *S) { return S ? S->h.N : 0; }
+int mvx_pool_num_rows(const mvx_colpool *S) { return S ? S->h.m : 0; }
+int mvx_pool_get_col(const mvx_colpool *S, int j, double *col, double *obj, int *type, double *lb, double *ub, int *kind) {
+  if (!S) return -1;
+  return mvx_sifting::pool_get(S->h, j, col, obj, type, lb, ub, kind);
+}
+void mvx_pool_delete(mvx_colpool *S) {
+  if (!S) return;
+  mvx::engine_pool_release(S);
+  delete S;
+}
+
+int mvx_pool_price(const mvx_prob *P, const mvx_colpool *S, const unsigned char *skip, int K, double *dj, int *pick, int *npick) {
+  if (!P || !S || K < 0 || !npick || (K > 0 && !pick)) return -1;
+  if (P->m != S->h.m) return -1;
+  if (!P->valid || P->status == MVX_UNDEF) return -3;
+  mvx_smcp dflt;
+  mvx_init_smcp(&dflt);
+  return mvx::engine_pool_price(P, S, skip, K, P->dir == MVX_MAX ? 1.0 : -1.0, dflt.tol_dj, dj, pick, npick);
+}
+
+int mvx_pool_append(mvx_prob *P, const mvx_colpool *S, int k, const int *idx) {
+  if (!P || !S || k < 1 || !idx || P->m != S->h.m) return -1;
+  const mvx_sifting::PoolHost &h = S->h;
+  {
+    std::vector<char> seen((size_t)h.N + 1, 0);
+    for (int t = 0; t < k; t++) {
+      if (idx[t] < 1 || idx[t] > h.N || seen[(size_t)idx[t]]) return -1;
+      seen[(size_t)idx[t]] = 1;
+    }
+  }
+  const size_t crow = (size_t)h.m + 1;
+  std::vector<double> cols((size_t)k * crow), obj((size_t)k), lb((size_t)k), ub((size_t)k);
+  std::vector<int> type((size_t)k), kind((size_t)k);
+  for (int t = 0; t < k; t++)
+    mvx_sifting::pool_get(h, idx[t], &cols[(size_t)t * crow], &obj[(size_t)t], &type[(size_t)t], &lb[(size_t)t], &ub[(size_t)t], &kind[(size_t)t]);
+  return add_dense_cols_checked(P, k, cols.data(), obj.data(), type.data(), lb.data(), ub.data(), kind.data(), S, idx);
+}
+
+void mvx_init_sift_parm(mvx_sift_parm *sp, int m) {
+  sp->K = std::max(m, 64);
+  sp->max_rounds = 200;
+  sp->purge = 0;
+}
+
+int mvx_sift(mvx_prob *P, const mvx_colpool *S, const mvx_smcp *parm, const mvx_sift_parm *sp, int *where, mvx_sift_info *info) {
+  if (!P || !S || !where || P->m != S->h.m) return -1;
+  mvx_sift_parm dflt;
+  mvx_init_sift_parm(&dflt, P->m);
+  if (!sp) sp = &dflt;
+  if (sp->K < 1 || sp->max_rounds < 1 || sp->purge < 0 || sp->purge > 64) return -1;
+  const mvx_sifting::PoolHost &h = S->h;
+  const int m = P->m, N = h.N;
+  // owner[w]: the pool column that P's column w is, 0 for a column of the caller's own; age[w]: the re-solves in a row that left
+  // it non-basic at 0
+  std::vector<int> owner((size_t)P->n + 1, 0), age((size_t)P->n + 1, 0);
+  for (int j = 1; j <= N; j++) {
+    const int w = where[j];
+    if (w == 0) continue;
+    if (w < 0 || w > P->n || owner[(size_t)w]) return -1;
+    const double *a = h.cols.data() + (size_t)(j - 1) * (size_t)h.ldp;
+    if (std::memcmp(&P->c[(size_t)w], &h.obj[(size_t)j - 1], 8) != 0) return -1;
+    for (int i = 1; i <= m; i++)
+      if (std::memcmp(&(*P->A[(size_t)i])[(size_t)w], &a[i - 1], 8) != 0) return -1;
+    owner[(size_t)w] = j;
+  }
+  mvx_sift_info st;
+  std::memset(&st, 0, sizeof st);
+  std::vector<unsigned char> skip((size_t)N + 1, 0);
+  std::vector<int> pick((size_t)std::min(sp->K, std::max(N, 1)));
+  int rc = 0;
+  for (;;) {
+    st.rounds++;
+    const int it0 = P->it_cnt;
+    mvx_simplex(P, parm);
+    st.lps++;
+    st.pivots += P->it_cnt - it0;
+    st.end = P->status;
+    if (P->status != MVX_OPT) break;
+    for (int w = 1; w <= P->n; w++)
+      if (owner[(size_t)w]) // idle: non-basic and at 0, where an absent column rests (a column at a non-zero upper bound is in use)
+        age[(size_t)w] = (mvx_get_col_stat(P, w) != MVX_BS && mvx_get_col_prim(P, w) == 0.0) ? age[(size_t)w] + 1 : 0;
+    for (int j = 1; j <= N; j++) skip[(size_t)j] = where[j] != 0;
+    int np = 0;
+    rc = mvx_pool_price(P, S, skip.data(), sp->K, nullptr, pick.data(), &np);
+    if (rc != 0) break;
+    st.priced += N;
+    if (np == 0) break; // optimal for the full LP, every absent column at 0
+    if (st.rounds == sp->max_rounds) {
+      st.end = 0;
+      rc = -4;
+      break;
+    }
+    const int n0 = P->n;
+    rc = mvx_pool_append(P, S, np, pick.data());
+    if (rc == -1) break;
+    for (int t = 0; t < np; t++) { // on -2 the model has the columns too
+      where[pick[(size_t)t]] = n0 + 1 + t;
+      owner.push_back(pick[(size_t)t]);
+      age.push_back(0);
+    }
+    st.appended += np;
+    if (rc != 0) break;
+    if (sp->purge > 0) {
+      std::vector<int> num(1, 0);
+      for (int w = 1; w <= n0; w++)
+        if (owner[(size_t)w] && age[(size_t)w] >= sp->purge) num.push_back(w);
+      if ((int)num.size() - 1 >= P->n) num.erase(num.begin() + 1); // the last column cannot leave: the lowest stays
+      const int nd = (int)num.size() - 1;
+      if (nd > 0) {
+        rc = mvx_del_cols(P, nd, num.data());
+        if (rc == -1) break;
+        int wn = 0;
+        size_t d = 1;
+        for (int w = 1; w <= n0 + np; w++) {
+          if (d < num.size() && num[d] == w) {
+            where[owner[(size_t)w]] = 0;
+            d++;
+            continue;
+          }
+          ++wn;
+          owner[(size_t)wn] = owner[(size_t)w];
+          age[(size_t)wn] = age[(size_t)w];
+          if (owner[(size_t)wn]) where[owner[(size_t)wn]] = wn;
+        }
+        owner.resize((size_t)wn + 1);
+        age.resize((size_t)wn + 1);
+        st.purged += nd;
+        if (rc != 0) break;
+      }
+    }
+  }
+  st.n_final = P->n;
+  if (info) *info = st;
+  return rc;
+}
 
 void mvx_set_mat_col(mvx_prob *P, int j, int len, const int *ind, const double *val) {
   if (j < 1 || j > P->n) fault("set_mat_col: column out of range");

@@ -2373,19 +2373,25 @@ static void addcols_tile_columns(double *dst, const double *cols, int k, int m) 
 }
 // `k` structural columns have joined the model as columns n_old+1 .. P->n (mvx_add_dense_cols; DESIGN.md "Column append
 // (add_cols)"): one upload and one k_addcols launch (a LiveEdit) make them non-basic columns of the live tableau.  cols is
-// k x (m+1) by model row, flag / lb / ub the new positions' statuses and normalised bounds.  While ld_for(n) does not change the
-// columns are written in place; otherwise the handle moves to a slab (m_cap, ld_for(n)) that the same launch writes whole.
+// k x (m+1) by model row, flag / lb / ub the new positions' statuses and normalised bounds.  With a pool S (mvx_pool_append) the
+// columns are its columns idx[0..k): cols is not read, and k_poolgather lays the tiles out on the device.  While ld_for(n) does
+// not change the columns are written in place; otherwise the handle moves to a slab (m_cap, ld_for(n)) that the same launch
+// writes whole.
 // Pending bound edits stay pending: they are keyed by tableau row.
 // Return codes: 0; -2 device out of memory, the tableau is given up.
-int engine_add_cols_live(mvx_prob *P, int k, const double *cols, const double *obj, const int *flag, const double *lb, const double *ub) {
+int engine_add_cols_live(mvx_prob *P, int k, const double *cols, const double *obj, const int *flag, const double *lb, const double *ub,
+                         const mvx_colpool *S, const int *idx) {
   const int m = P->m, n = P->n - k; // n: the columns of the tableau as it stands
   const size_t crow = (size_t)m + 1;
   LiveEdit f(P);
-  const size_t o_cols = f.up(addcols_tiled_bytes(k, m)), o_obj = f.up((size_t)k * 8), o_xs = f.up((size_t)k * 8);
+  // from a pool the tiles are not uploaded: k_poolgather writes them into a device-only piece from the pool's device copy
+  const size_t o_cols = S ? 0 : f.up(addcols_tiled_bytes(k, m)), o_obj = f.up((size_t)k * 8), o_xs = f.up((size_t)k * 8);
   const size_t o_lb = f.up((size_t)k * 8), o_ub = f.up((size_t)k * 8), o_flag = f.up((size_t)k * 4);
-  if (!f.begin(P->m_cap, ld_for(n + k))) return f.out_of_memory();
+  const size_t o_idx = S ? f.up((size_t)k * 4) : 0, o_tiles = S ? f.dev(addcols_tiled_bytes(k, m)) : o_cols;
+  if ((S && engine_pool_sync(S) != 0) || !f.begin(P->m_cap, ld_for(n + k))) return f.out_of_memory();
   unsigned char *hb = f.hb, *db = f.db;
-  addcols_tile_columns((double *)(hb + o_cols), cols, k, m);
+  if (S) std::memcpy(hb + o_idx, idx, (size_t)k * 4);
+  else addcols_tile_columns((double *)(hb + o_cols), cols, k, m);
   std::memcpy(hb + o_obj, obj, (size_t)k * 8);
   std::memcpy(hb + o_lb, lb, (size_t)k * 8);
   std::memcpy(hb + o_ub, ub, (size_t)k * 8);
@@ -2393,11 +2399,12 @@ int engine_add_cols_live(mvx_prob *P, int k, const double *cols, const double *o
   double *h_xs = (double *)(hb + o_xs);
   for (int t = 0; t < k; t++) h_xs[t] = nb_value(flag[t], lb[t], ub[t]);
   f.upload();
+  if (S) launch_pool_gather(PoolGatherArgs{S->d_cols, (const int *)(db + o_idx), (double *)(db + o_tiles), m, S->h.ldp, k}, f.stream());
   AddColsArgs a;
   std::memset(&a, 0, sizeof a);
   a.s = f.from();
   a.d = f.to();
-  a.cols = (const double *)(db + o_cols);
+  a.cols = (const double *)(db + o_tiles);
   a.obj = (const double *)(db + o_obj);
   a.xs = (const double *)(db + o_xs);
   a.nlb_new = (const double *)(db + o_lb);
@@ -2464,6 +2471,118 @@ int engine_price_cols(const mvx_prob *P, int k, const double *cols, const double
   }
   std::memcpy(dj, r_dj.data(), (size_t)k * 8);
   if (img) std::memcpy(img, r_img.data(), (size_t)k * crow * 8);
+  return 0;
+}
+
+// ------------------------------------------------------------------ sifting over a column pool (k_poolprice, k_poolsel_*, k_poolgather)
+// The device copy of a pool (DESIGN.md "Sifting (sift)"): the host image [N][ldp], the objective and the entering statuses, in
+// allocations of their own that grow by half when a later mvx_pool_add_cols outruns them (the columns already there are copied on
+// the device).  0, or -2 when the device has no room: the copy it had stays as it was.
+int engine_pool_sync(const mvx_colpool *S) {
+  const mvx_sifting::PoolHost &h = S->h;
+  if (S->dev_n == h.N) return 0;
+  Context &c = ctx();
+  bind_device(c);
+  MAIN_LOCK(c);
+  const size_t ldp = (size_t)h.ldp;
+  if (h.N > S->dev_cap) {
+    const int cap = (int)std::min<long long>(0x7ffffff0LL, std::max<long long>(h.N, (long long)S->dev_cap + S->dev_cap / 2));
+    double *nc = nullptr, *no = nullptr;
+    int *nf = nullptr;
+    if (hipMalloc((void **)&nc, std::max<size_t>((size_t)cap * ldp * 8, 8)) != hipSuccess ||
+        hipMalloc((void **)&no, (size_t)cap * 8) != hipSuccess || hipMalloc((void **)&nf, (size_t)cap * 4) != hipSuccess) {
+      (void)hipGetLastError();
+      if (nc) (void)hipFree(nc);
+      if (no) (void)hipFree(no);
+      g_last_error.store(MVX_ENOMEM);
+      return -2;
+    }
+    HIPCHECK(hipStreamSynchronize(c.main.stream)); // nothing queued reads the old copy any more
+    if (S->dev_n > 0) {
+      if (ldp) HIPCHECK(hipMemcpy(nc, S->d_cols, (size_t)S->dev_n * ldp * 8, hipMemcpyDeviceToDevice));
+      HIPCHECK(hipMemcpy(no, S->d_obj, (size_t)S->dev_n * 8, hipMemcpyDeviceToDevice));
+      HIPCHECK(hipMemcpy(nf, S->d_flag, (size_t)S->dev_n * 4, hipMemcpyDeviceToDevice));
+    }
+    if (S->d_cols) HIPCHECK(hipFree(S->d_cols));
+    if (S->d_obj) HIPCHECK(hipFree(S->d_obj));
+    if (S->d_flag) HIPCHECK(hipFree(S->d_flag));
+    S->d_cols = nc, S->d_obj = no, S->d_flag = nf;
+    S->dev_cap = cap;
+  }
+  const size_t n0 = (size_t)S->dev_n, cnt = (size_t)h.N - n0;
+  std::vector<int> flag(cnt);
+  for (size_t t = 0; t < cnt; t++) flag[t] = std_flag(h.type[n0 + t]);
+  if (ldp) HIPCHECK(hipMemcpy(S->d_cols + n0 * ldp, h.cols.data() + n0 * ldp, cnt * ldp * 8, hipMemcpyHostToDevice));
+  HIPCHECK(hipMemcpy(S->d_obj + n0, h.obj.data() + n0, cnt * 8, hipMemcpyHostToDevice));
+  HIPCHECK(hipMemcpy(S->d_flag + n0, flag.data(), cnt * 4, hipMemcpyHostToDevice));
+  S->dev_n = h.N;
+  return 0;
+}
+void engine_pool_release(mvx_colpool *S) {
+  if (!S->d_cols && !S->d_obj && !S->d_flag) return; // the pool never met a device
+  Context &c = ctx();
+  bind_device(c);
+  MAIN_LOCK(c);
+  HIPCHECK(hipStreamSynchronize(c.main.stream));
+  if (S->d_cols) HIPCHECK(hipFree(S->d_cols));
+  if (S->d_obj) HIPCHECK(hipFree(S->d_obj));
+  if (S->d_flag) HIPCHECK(hipFree(S->d_flag));
+  S->d_cols = S->d_obj = nullptr;
+  S->d_flag = nullptr;
+  S->dev_n = S->dev_cap = 0;
+}
+
+// The reduced costs of every pool column against the handle's row 0 and the K most attractive of them (mvx_pool_price): one
+// upload of [where the auxiliaries sit | skip], k_pooly, k_poolprice, the selection launches, one copy back of [picks | dj].
+// Pure.  sgn +1 under MVX_MAX, -1 under MVX_MIN.  dj (nullable) [N+1], pick [K], *npick.  Return codes: 0; -2 device out of
+// memory, nothing written; -3 no valid tableau.
+int engine_pool_price(const mvx_prob *P, const mvx_colpool *S, const unsigned char *skip, int K, double sgn, double tol, double *dj, int *pick,
+                      int *npick) {
+  if (!P->valid) return -3;
+  const int m = P->m, N = S->h.N, ldp = S->h.ldp;
+  if (N == 0) {
+    if (dj) dj[0] = 0.0;
+    *npick = 0;
+    return 0;
+  }
+  K = std::min(K, N);
+  if (engine_pool_sync(S) != 0) return -2;
+  NodeCall f(NodeFlush::AtEntry, NodeResults::Device);
+  const size_t o_ypos = f.up(((size_t)m + 1) * 4), o_skip = f.up(skip ? (size_t)N + 1 : 0);
+  const size_t o_pick = f.out(((size_t)K + 1) * 4), o_dj = dj ? f.out(((size_t)N + 1) * 8) : f.dev(((size_t)N + 1) * 8);
+  const size_t pick_end = o_pick + ((size_t)K + 1) * 4;
+  const size_t o_y = f.dev((size_t)std::max(ldp, 1) * 8), o_key = f.dev(((size_t)N + 1) * 8), o_sel = f.dev((size_t)POOLSEL_INTS * 4);
+  const size_t o_ck = f.dev((size_t)std::max(K, 1) * 8), o_cj = f.dev((size_t)std::max(K, 1) * 4);
+  if (!f.reserve()) return -2;
+  int *ypos = (int *)(f.hb + o_ypos);
+  ypos[0] = 0;
+  for (int i = 1; i <= m; i++) ypos[i] = P->pos[(size_t)i] < 0 ? -P->pos[(size_t)i] : 0;
+  if (skip) std::memcpy(f.hb + o_skip, skip, (size_t)N + 1);
+  f.upload();
+  PoolPriceArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.cols = S->d_cols, a.obj = S->d_obj, a.flag = S->d_flag;
+  a.skip = skip ? f.db + o_skip : nullptr;
+  a.T0 = P->d_T;
+  a.ypos = (const int *)(f.db + o_ypos);
+  a.y = (double *)(f.db + o_y);
+  a.d = (double *)(f.db + o_dj);
+  a.key = (unsigned long long *)(f.db + o_key);
+  a.sel = (int *)(f.db + o_sel);
+  a.cand_key = (unsigned long long *)(f.db + o_ck);
+  a.cand_j = (int *)(f.db + o_cj);
+  a.pick = (int *)(f.db + o_pick);
+  a.sgn = sgn, a.tol = tol;
+  a.m = m, a.ldp = ldp, a.N = N, a.K = K;
+  launch_pool_price(a, f.stream());
+  if (K < 1) HIPCHECK(hipMemsetAsync(f.db + o_pick, 0, 4, f.stream()));
+  if (dj) HIPCHECK(hipMemsetAsync(f.db + o_dj, 0, 8, f.stream())); // dj[0]
+  f.copy_back(dj ? 0 : pick_end);
+  f.sync();
+  const int *r = (const int *)(f.hb + o_pick);
+  *npick = r[0];
+  std::memcpy(pick, r + 1, (size_t)r[0] * 4);
+  if (dj) std::memcpy(dj, f.hb + o_dj, ((size_t)N + 1) * 8);
   return 0;
 }
 

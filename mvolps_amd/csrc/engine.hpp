@@ -68,7 +68,15 @@ int engine_add_cut_rows(mvx_prob *P, int k, const double *vals, const double *rh
 int engine_add_cut_rows_many(mvx_prob *const *Ps, int count, const int *off, const double *vals, const double *rhs);
 // `k` dense structural columns appended to the live tableau in one device pass (k_addcols; P->n already updated, flag / lb / ub
 // the new positions' statuses and normalised bounds), and the same images without appending; see engine.cpp
-int engine_add_cols_live(mvx_prob *P, int k, const double *cols, const double *obj, const int *flag, const double *lb, const double *ub);
+// With a pool S the columns are its columns idx[0..k) and their coefficients reach the tableau from the pool's device copy
+int engine_add_cols_live(mvx_prob *P, int k, const double *cols, const double *obj, const int *flag, const double *lb, const double *ub,
+                         const mvx_colpool *S = nullptr, const int *idx = nullptr);
+// sifting over a device-resident column pool (DESIGN.md "Sifting (sift)"): the pool's device copy, the full-pool pricing pass
+// with its top-K selection (k_pooly, k_poolprice, k_poolsel_*); see engine.cpp
+int engine_pool_sync(const mvx_colpool *S);
+void engine_pool_release(mvx_colpool *S);
+int engine_pool_price(const mvx_prob *P, const mvx_colpool *S, const unsigned char *skip, int K, double sgn, double tol, double *dj, int *pick,
+                      int *npick);
 int engine_price_cols(const mvx_prob *P, int k, const double *cols, const double *obj, double *dj, double *img);
 // model columns `cols` (ascending, old numbers; lb / ub their normalised bounds) have left the model: where every one of them is
 // non-basic they leave the live tableau in one device pass (k_delcols), otherwise the tableau is given up; see engine.cpp

@@ -1,7 +1,8 @@
 // mvolps -- command-line front end over libmvolps_amd.so; counterpart of MVOLPS's main
 // (/root/reference/2test.cpp:13-157): same flags, same dispatch on the file extension
 // (2test.cpp:65-81), then initProblem (util.cpp:277-292) and branchAndBound (bs.cpp:54).
-// Extra flags of this build: --repaired (reference_quirks = 0), --max-nodes N, --events FILE, --ranges FILE, --kkt FILE, --farkas FILE.
+// Extra flags of this build: --repaired (reference_quirks = 0), --max-nodes N, --events FILE, --ranges FILE, --kkt FILE, --farkas FILE,
+// --sift [K].
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -52,6 +53,10 @@ int main(int argc, char **argv) {
               << "                  tableau side, rel of the model side, Lo or -Hi, de) to FILE, when it is unbounded its ray (RAY.ROOT: found,\n"
               << "                  variable, direction, blocking variables, rows of ae and re, dual, ae, re, slope); run the tree with every infeasible node LP\n"
               << "                  asked for its proof, and append the tree's totals; not with --best-window\n"
+              << "  --sift [K]      solve the file's LP relaxation by sifting and stop: the columns that cannot rest at 0 form the first\n"
+              << "                  working LP (column 1 when there is none), all others a device-resident pool that is priced whole\n"
+              << "                  every round; at most K columns join per round (max(m, 64) without a number); prints the status, the\n"
+              << "                  objective, the rounds, the columns appended and purged and the final width\n"
               << "Output verbosity options:\n"
               << "  -s/--silent\n  -v/--verbose\n  -d/--debug\n  -so/--solver-output\n\n"
               << "Algorithm strategy options:\n"
@@ -136,6 +141,62 @@ int main(int argc, char **argv) {
     return -1;
   }
   if (verbose) std::printf("%s\nProblem contains %d integer variables\n", mvx_version(), mvx_get_num_int(prob)); // util.cpp:278,298
+
+  if (input.CMDOptionExists("--sift")) {
+    // the LP relaxation by sifting (DESIGN.md "Sifting (sift)"): the columns that cannot rest at 0 are the first working set
+    // (column 1 when there is none), every other column goes to the pool
+    const int m = mvx_get_num_rows(prob), n = mvx_get_num_cols(prob);
+    const std::string kopt = input.getCMDOption("--sift");
+    mvx_sift_parm sp;
+    mvx_init_sift_parm(&sp, m);
+    if (!kopt.empty() && kopt[0] != '-') {
+      sp.K = std::atoi(kopt.c_str());
+      if (sp.K < 1) {
+        std::fprintf(stderr, "Unknown parameter value for --sift\n");
+        return -1;
+      }
+    }
+    if (n < 1) {
+      std::fprintf(stderr, "--sift: the model has no columns\n");
+      return -1;
+    }
+    mvx_colpool *pool = mvx_pool_create(m);
+    std::vector<int> ind((size_t)m + 1), pooled(1, 0);
+    std::vector<double> val((size_t)m + 1), col((size_t)m + 1);
+    auto to_pool = [&](int j) { // 0 when column j can rest at 0 and has joined the pool
+      std::fill(col.begin(), col.end(), 0.0);
+      const int len = mvx_get_mat_col(prob, j, ind.data(), val.data());
+      for (int t = 1; t <= len; t++) col[(size_t)ind[(size_t)t]] = val[(size_t)t];
+      const double obj = mvx_get_obj_coef(prob, j), lb = mvx_get_col_lb(prob, j), ub = mvx_get_col_ub(prob, j); // an absent bound is not read
+      const int type = mvx_get_col_type(prob, j);
+      return mvx_pool_add_cols(pool, 1, col.data(), &obj, &type, &lb, &ub, nullptr);
+    };
+    for (int j = 1; j <= n; j++)
+      if (to_pool(j) == 0) pooled.push_back(j);
+    if ((int)pooled.size() - 1 == n) { // every column can rest at 0: column 1 is the working set; the pool is built again without it
+      mvx_pool_delete(pool);
+      pool = mvx_pool_create(m);
+      pooled.assign(1, 0);
+      for (int j = 2; j <= n; j++)
+        if (to_pool(j) == 0) pooled.push_back(j);
+    }
+    const int N = (int)pooled.size() - 1;
+    if (N > 0 && mvx_del_cols(prob, N, pooled.data()) != 0) {
+      std::fprintf(stderr, "--sift: the working LP could not be formed\n");
+      return -1;
+    }
+    std::vector<int> where((size_t)N + 1, 0);
+    mvx_sift_info info;
+    const int rc = mvx_sift(prob, pool, nullptr, &sp, where.data(), &info);
+    static const char *names[] = {"ROUND LIMIT", "UNDEFINED", "FEASIBLE", "INFEASIBLE (working LP only)", "NO FEASIBLE SOLUTION (working LP only)",
+                                  "OPTIMAL", "UNBOUNDED"};
+    std::printf("SIFT.RC %d\nSIFT.STATUS %s\nSIFT.OBJ %.17g\nSIFT.ROUNDS %d\nSIFT.APPENDED %lld\nSIFT.PURGED %lld\nSIFT.N_FINAL %d of %d\n", rc,
+                names[info.end >= 0 && info.end <= 6 ? info.end : 1], mvx_get_obj_val(prob), info.rounds, info.appended, info.purged,
+                info.n_final, n);
+    mvx_pool_delete(pool);
+    mvx_delete_prob(prob);
+    return rc == 0 ? 0 : 1;
+  }
 
   mvx_bnb_params params;
   mvx_bnb_default_params(&params);

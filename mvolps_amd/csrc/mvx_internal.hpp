@@ -17,6 +17,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "../../include/mvx.h"
+#include "sift_host.hpp"
 
 struct DevMatrix;
 namespace mvx {
@@ -557,6 +558,46 @@ struct AddColsArgs {
   int rows_all; // rows the launch covers: rows, or m_cap + 1 on a relayout
 };
 
+// arguments of the sifting kernels (mvx_pool_price, mvx_pool_append; DESIGN.md "Sifting (sift)") over a device-resident column pool:
+// column j = 1..N at cols[(j-1)*ldp ..], model row i at entry i-1, zero behind row m (ldp a multiple of 64 doubles).
+// k_pooly writes the row weights y (ypos[i] the non-basic position of auxiliary i, 0 when it is basic: y_i = +0.0; zero up to
+// ldp), k_poolprice the reduced costs d[1..N] and the selection keys (the bits of |d_j| where column j is attractive and not
+// skipped, else 0), k_poolsel_hist one digit of the radix select over (key, N - j), k_poolsel_emit the columns at or above the
+// K-th largest, k_poolsel_rank their order
+#define POOL_WAVES 4       // waves of a k_poolprice workgroup: a pool column each
+#define POOL_Y_LDS 4096    // most rows whose weights a k_poolprice workgroup keeps in LDS; beyond, y is read through L2
+#define POOL_AHEAD 8       // loads a lane of k_poolprice has in flight
+#define POOLSEL_PASSES 12  // 8-bit digits of the 96-bit selection key: 8 of |d_j|'s bits, 4 of N - j
+#define POOLSEL_THREADS 256
+#define POOLSEL_COUNT (POOLSEL_PASSES * 256)
+#define POOLSEL_STATE (POOLSEL_COUNT + 2)
+#define POOLSEL_INTS (POOLSEL_STATE + (POOLSEL_PASSES + 1) * 4)
+struct PoolPriceArgs {
+  const double *cols, *obj; // the pool: [N][ldp], [N]
+  const int *flag;          // [N] the status a column would enter with (std_flag of its type)
+  const unsigned char *skip; // [N+1] nullable
+  const double *T0;         // row 0 of the handle's tableau
+  const int *ypos;          // [m+1]
+  double *y;                // [ldp]
+  double *d;                // [N+1]
+  unsigned long long *key;  // [N+1]
+  int *sel;                 // [POOLSEL_INTS], zero before the first pass: POOLSEL_PASSES histograms of 256 bins, then the candidates
+                            // emitted so far and the number of picks, then per pass the digits chosen so far and the rank
+                            // still to find (4 ints)
+  unsigned long long *cand_key; // [K]
+  int *cand_j;              // [K]
+  int *pick;                // [1 + K]: pick[0] the number of picks, then the picks
+  double sgn, tol;
+  int m, ldp, N, K;         // K already min(K, N)
+};
+// arguments of k_poolgather: pool columns idx[0..k) into the tile layout k_addcols reads (AddColsArgs::cols)
+struct PoolGatherArgs {
+  const double *cols; // the pool
+  const int *idx;     // [k] 1-based pool columns
+  double *tiles;      // [ceil(k / ADDCOLS_CT)][m+1][ADDCOLS_CT]
+  int m, ldp, k;
+};
+
 // arguments of k_delrows (mvx_del_rows): rows taken out of one tableau in place.  Tableau rows 0..first-1 stay where they are;
 // destination row first + t takes source row src[t] (ascending, src[t] > first + t); rows first + nmove .. m_old (behind the new
 // row m = first + nmove - 1) are vacated and zeroed.  del[0..nrs) are the deleted auxiliary variables (= model rows), ascending, for the renumbering
@@ -706,6 +747,8 @@ void launch_cutrows_many(const CutRowsHandle *hs, const int *tile0s, int handles
                          hipStream_t);
 void launch_addcols(const AddColsArgs &a, hipStream_t);
 void launch_delcols(const DelColsArgs &a, hipStream_t);
+void launch_pool_price(const PoolPriceArgs &a, hipStream_t); // k_pooly, k_poolprice and, for a.K > 0, the selection
+void launch_pool_gather(const PoolGatherArgs &a, hipStream_t);
 void launch_delrows(const DelRowsArgs &a, hipStream_t);
 void launch_delrows_many(const DelRowsArgs *hs, int handles, int max_ld, hipStream_t); // hs: device memory
 
@@ -822,6 +865,15 @@ public:
 };
 
 } // namespace mvx
+
+// A column pool (mvx_pool_create; DESIGN.md "Sifting (sift)"): the host copy, and the device copy of its first dev_n columns, made
+// by the first call that needs the device (engine_pool_sync) and released by engine_pool_release
+struct mvx_colpool {
+  mvx_sifting::PoolHost h;
+  mutable double *d_cols = nullptr, *d_obj = nullptr;
+  mutable int *d_flag = nullptr;
+  mutable int dev_n = 0, dev_cap = 0;
+};
 
 struct mvx_prob {
   // ---- model (host) ----

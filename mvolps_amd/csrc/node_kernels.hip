@@ -2135,6 +2135,217 @@ void launch_addcols(const AddColsArgs &a, hipStream_t s) {
   hipLaunchKernelGGL(k_addcols, dim3(nrb, nty), dim3(ADDCOLS_THREADS), 0, s, a);
 }
 
+// ---------------------------------------------------------------------------- k_pooly, k_poolprice, k_poolsel_*, k_poolgather
+// Sifting over a device-resident column pool (mvx_pool_price, mvx_pool_append; DESIGN.md "Sifting (sift)").
+// k_pooly: the row weights y_i = T[0][q] at the non-basic position q of auxiliary i, +0.0 where it is basic, zero up to ldp.
+__global__ __launch_bounds__(256) void k_pooly(PoolPriceArgs a) {
+  const int e = (int)blockIdx.x * 256 + TIDX; // entry e holds model row e + 1
+  if (e >= a.ldp) return;
+  const int q = e < a.m ? a.ypos[e + 1] : 0;
+  a.y[e] = q ? a.T0[q] : 0.0;
+}
+
+// k_poolprice: d_j = obj_j + S_j for every pool column in one stream over the pool.  A wave owns a column: its 64 lanes are the
+// 64 chains of the definition (lane l takes rows l+1, l+65, ... ascending, fma(-a_ij, y_i, acc) from +0.0, rows with y_i == 0
+// skipped), every read is a 512-byte row of a contiguous column, and a lane has POOL_AHEAD loads in flight before the first
+// fma.  The chains are combined by s[l] += s[l+h], h = 32 .. 1, in lane 0, which adds obj_j last and writes d_j and the column's
+// selection key.  The weights stay in LDS for the whole launch (LDS_Y; beyond POOL_Y_LDS rows they are read through L2); the
+// workgroups stride over the columns.  Below 64 rows most lanes idle: such a pool is small.
+template <bool LDS_Y>
+__global__ __launch_bounds__(64 * POOL_WAVES) void k_poolprice(PoolPriceArgs a) {
+  extern __shared__ double s_y[];
+  const int lane = TIDX & 63, wave = TIDX >> 6;
+  const int ldp = a.ldp;
+  if (LDS_Y) {
+    for (int i = TIDX; i < ldp; i += 64 * POOL_WAVES) s_y[i] = a.y[i];
+    __syncthreads();
+  }
+  for (int t = (int)blockIdx.x * POOL_WAVES + wave; t < a.N; t += (int)gridDim.x * POOL_WAVES) {
+    const double *col = a.cols + (size_t)t * (size_t)ldp;
+    double acc = 0.0;
+    for (int i0 = lane; i0 < ldp; i0 += 64 * POOL_AHEAD) {
+      double v[POOL_AHEAD];
+#pragma unroll
+      for (int u = 0; u < POOL_AHEAD; u++) v[u] = i0 + u * 64 < ldp ? col[i0 + u * 64] : 0.0;
+#pragma unroll
+      for (int u = 0; u < POOL_AHEAD; u++) {
+        const int i = i0 + u * 64;
+        const double yy = i < ldp ? (LDS_Y ? s_y[i] : a.y[i]) : 0.0;
+        if (yy != 0.0) acc = fma(-v[u], yy, acc);
+      }
+    }
+    double s = acc;
+#pragma unroll
+    for (int h = 32; h >= 1; h >>= 1) s = s + __shfl_down(s, h);
+    if (lane == 0) {
+      const double d = a.obj[t] + s;
+      const int f = a.flag[t];
+      const double v = a.sgn * d;
+      const bool att = f == MVX_NL ? v > a.tol : f == MVX_NU ? v < -a.tol : f == MVX_NF ? fabs(d) > a.tol : false;
+      a.d[t + 1] = d;
+      a.key[t + 1] = (att && !(a.skip && a.skip[t + 1])) ? (unsigned long long)__double_as_longlong(fabs(d)) : 0ULL;
+    }
+  }
+}
+
+// The selection: the K-th largest of the keys (bits of |d_j|, then N - j; a column that is not a candidate has no key) by a
+// radix select, most significant byte first.  Launch p counts byte p of the keys that agree with the bytes chosen so far
+// (integer counts in LDS, then in the launch's own global histogram: a count does not depend on the order of arrival); the
+// next launch reads the finished histogram, chooses the byte that holds the rank still to find and carries on.  Every
+// workgroup takes the same decision from the same numbers.  st = (low and high word of the bytes of |d|, the bytes of N - j,
+// the rank still to find among the keys that agree).
+__device__ __forceinline__ void poolsel_advance(const PoolPriceArgs &a, int p, unsigned long long &hi, unsigned &lo, int &kleft) {
+  __shared__ int s_suf[POOLSEL_THREADS + 1];
+  __shared__ int s_res[2];
+  int *st = a.sel + POOLSEL_STATE;
+  if (p == 1) {
+    hi = 0;
+    lo = 0;
+    kleft = a.K;
+  } else {
+    hi = (unsigned long long)(unsigned)st[(p - 1) * 4] | ((unsigned long long)(unsigned)st[(p - 1) * 4 + 1] << 32);
+    lo = (unsigned)st[(p - 1) * 4 + 2];
+    kleft = st[(p - 1) * 4 + 3];
+  }
+  if (kleft > 0) { // uniform over the workgroup
+    s_suf[TIDX] = a.sel[(p - 1) * 256 + TIDX];
+    if (TIDX == 0) s_suf[POOLSEL_THREADS] = 0;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) { // s_suf[b] becomes the count of bytes >= b
+      const int v = TIDX + off < 256 ? s_suf[TIDX + off] : 0;
+      __syncthreads();
+      s_suf[TIDX] += v;
+      __syncthreads();
+    }
+    if (p == 1) { // every candidate was counted: the picks are min(K, #candidates)
+      kleft = kleft < s_suf[0] ? kleft : s_suf[0];
+      if (blockIdx.x == 0 && TIDX == 0) a.sel[POOLSEL_COUNT + 1] = kleft;
+    }
+    if (kleft > 0) {
+      if (s_suf[TIDX] >= kleft && s_suf[TIDX + 1] < kleft) {
+        s_res[0] = TIDX;
+        s_res[1] = kleft - s_suf[TIDX + 1];
+      }
+      __syncthreads();
+      const unsigned dgt = (unsigned)s_res[0];
+      kleft = s_res[1];
+      if (p - 1 < 8) hi |= (unsigned long long)dgt << (56 - 8 * (p - 1));
+      else lo |= dgt << (24 - 8 * (p - 1 - 8));
+    }
+  }
+  if (blockIdx.x == 0 && TIDX == 0) {
+    st[p * 4] = (int)(unsigned)(hi & 0xffffffffULL);
+    st[p * 4 + 1] = (int)(unsigned)(hi >> 32);
+    st[p * 4 + 2] = (int)lo;
+    st[p * 4 + 3] = kleft;
+  }
+}
+// does (kh, kl) agree with the first p bytes of (hi, lo)?
+__device__ __forceinline__ bool poolsel_agrees(int p, unsigned long long kh, unsigned kl, unsigned long long hi, unsigned lo) {
+  if (p == 0) return true;
+  if (p < 8) return (kh >> (64 - 8 * p)) == (hi >> (64 - 8 * p));
+  if (kh != hi) return false;
+  return p == 8 || (kl >> (32 - 8 * (p - 8))) == (lo >> (32 - 8 * (p - 8)));
+}
+__global__ __launch_bounds__(POOLSEL_THREADS) void k_poolsel_hist(PoolPriceArgs a, int p) {
+  __shared__ int s_h[256];
+  unsigned long long hi = 0;
+  unsigned lo = 0;
+  int kleft = a.K;
+  if (p > 0) {
+    poolsel_advance(a, p, hi, lo, kleft);
+    if (kleft == 0) return; // no candidate at all
+  }
+  s_h[TIDX] = 0;
+  __syncthreads();
+  for (int j = 1 + (int)blockIdx.x * POOLSEL_THREADS + TIDX; j <= a.N; j += (int)gridDim.x * POOLSEL_THREADS) {
+    const unsigned long long kh = a.key[j];
+    if (!kh) continue;
+    const unsigned kl = (unsigned)(a.N - j);
+    if (!poolsel_agrees(p, kh, kl, hi, lo)) continue;
+    const unsigned dgt = p < 8 ? (unsigned)(kh >> (56 - 8 * p)) & 255u : (kl >> (24 - 8 * (p - 8))) & 255u;
+    atomicAdd(&s_h[dgt], 1);
+  }
+  __syncthreads();
+  if (s_h[TIDX]) atomicAdd(&a.sel[p * 256 + TIDX], s_h[TIDX]);
+}
+// the columns whose key is at or above the K-th largest, in the order they arrive: k_poolsel_rank puts them in theirs
+__global__ __launch_bounds__(POOLSEL_THREADS) void k_poolsel_emit(PoolPriceArgs a) {
+  unsigned long long hi;
+  unsigned lo;
+  int kleft;
+  poolsel_advance(a, POOLSEL_PASSES, hi, lo, kleft);
+  if (kleft == 0) return;
+  for (int j = 1 + (int)blockIdx.x * POOLSEL_THREADS + TIDX; j <= a.N; j += (int)gridDim.x * POOLSEL_THREADS) {
+    const unsigned long long kh = a.key[j];
+    if (!kh) continue;
+    const unsigned kl = (unsigned)(a.N - j);
+    if (kh > hi || (kh == hi && kl >= lo)) {
+      const int slot = atomicAdd(&a.sel[POOLSEL_COUNT], 1);
+      if (slot < a.K) {
+        a.cand_key[slot] = kh;
+        a.cand_j[slot] = j;
+      }
+    }
+  }
+}
+// pick[1 + r] = the candidate with r candidates in front of it: larger |d|, or the same |d| and a lower column.  The keys are
+// distinct, so every place is written once, whatever order the candidates arrived in.  The work grows with the square of the
+// picks; they are a working set's worth, not a pool's
+__global__ __launch_bounds__(POOLSEL_THREADS) void k_poolsel_rank(PoolPriceArgs a) {
+  __shared__ unsigned long long s_k[POOLSEL_THREADS];
+  __shared__ int s_j[POOLSEL_THREADS];
+  const int np = a.sel[POOLSEL_COUNT + 1];
+  if (blockIdx.x == 0 && TIDX == 0) a.pick[0] = np;
+  if ((int)blockIdx.x * POOLSEL_THREADS >= np) return;
+  const int t = (int)blockIdx.x * POOLSEL_THREADS + TIDX;
+  const unsigned long long mk = t < np ? a.cand_key[t] : 0ULL;
+  const int mj = t < np ? a.cand_j[t] : 0;
+  int rank = 0;
+  for (int s0 = 0; s0 < np; s0 += POOLSEL_THREADS) {
+    __syncthreads();
+    s_k[TIDX] = s0 + TIDX < np ? a.cand_key[s0 + TIDX] : 0ULL;
+    s_j[TIDX] = s0 + TIDX < np ? a.cand_j[s0 + TIDX] : 0;
+    __syncthreads();
+    const int cnt = np - s0 < POOLSEL_THREADS ? np - s0 : POOLSEL_THREADS;
+    for (int u = 0; u < cnt; u++) rank += (s_k[u] > mk || (s_k[u] == mk && s_j[u] < mj)) ? 1 : 0;
+  }
+  if (t < np) a.pick[1 + rank] = mj;
+}
+
+void launch_pool_price(const PoolPriceArgs &a, hipStream_t s) {
+  hipLaunchKernelGGL(k_pooly, dim3((unsigned)(a.ldp > 0 ? (a.ldp + 255) / 256 : 1)), dim3(256), 0, s, a);
+  const int nb = (a.N + POOL_WAVES - 1) / POOL_WAVES;
+  const dim3 grid((unsigned)(nb < 2048 ? nb : 2048));
+  if (a.ldp <= POOL_Y_LDS) hipLaunchKernelGGL(k_poolprice<true>, grid, dim3(64 * POOL_WAVES), (size_t)a.ldp * 8, s, a);
+  else hipLaunchKernelGGL(k_poolprice<false>, grid, dim3(64 * POOL_WAVES), 0, s, a);
+  if (a.K < 1) return;
+  (void)hipMemsetAsync(a.sel, 0, (size_t)POOLSEL_INTS * 4, s);
+  const int sb = (a.N + POOLSEL_THREADS - 1) / POOLSEL_THREADS;
+  const dim3 sgrid((unsigned)(sb < 1024 ? sb : 1024));
+  for (int p = 0; p < POOLSEL_PASSES; p++) hipLaunchKernelGGL(k_poolsel_hist, sgrid, dim3(POOLSEL_THREADS), 0, s, a, p);
+  hipLaunchKernelGGL(k_poolsel_emit, sgrid, dim3(POOLSEL_THREADS), 0, s, a);
+  hipLaunchKernelGGL(k_poolsel_rank, dim3((unsigned)((a.K + POOLSEL_THREADS - 1) / POOLSEL_THREADS)), dim3(POOLSEL_THREADS), 0, s, a);
+}
+
+// k_poolgather: pool columns idx[0..k) into the layout k_addcols reads -- per tile of ADDCOLS_CT columns (m+1) rows of ADDCOLS_CT
+// doubles, row 0 and the columns behind k zero -- so that an append from the pool sends no coefficient over the bus.  One
+// workgroup per tile; a thread reads its row of the tile's columns (a coalesced read per column) and writes 32 bytes
+__global__ __launch_bounds__(256) void k_poolgather(PoolGatherArgs a) {
+  const int t0 = (int)blockIdx.x * ADDCOLS_CT;
+  const double *src[ADDCOLS_CT];
+#pragma unroll
+  for (int c = 0; c < ADDCOLS_CT; c++) src[c] = t0 + c < a.k ? a.cols + (size_t)(a.idx[t0 + c] - 1) * (size_t)a.ldp : nullptr;
+  double *tile = a.tiles + (size_t)blockIdx.x * ((size_t)a.m + 1) * ADDCOLS_CT;
+  for (int i = TIDX; i <= a.m; i += 256) {
+#pragma unroll
+    for (int c = 0; c < ADDCOLS_CT; c++) tile[(size_t)i * ADDCOLS_CT + c] = (i >= 1 && src[c]) ? src[c][i - 1] : 0.0;
+  }
+}
+void launch_pool_gather(const PoolGatherArgs &a, hipStream_t s) {
+  hipLaunchKernelGGL(k_poolgather, dim3((unsigned)((a.k + ADDCOLS_CT - 1) / ADDCOLS_CT)), dim3(256), 0, s, a);
+}
+
 // ---------------------------------------------------------------------------- k_delcols
 // Non-basic columns taken out of one tableau in one pass (mvx_del_cols; DESIGN.md "Column deletion (del_cols)"): k_addcols'
 // counterpart.  A wave owns one row, DELC_WAVES rows per workgroup; the last workgroup of the grid owns no row and does the
