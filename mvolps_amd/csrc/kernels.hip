@@ -2405,10 +2405,15 @@ __global__ __launch_bounds__(256) void k_pr(const ChainArgs A, int g) {
 //   row phase     load row p, carry it through the chain -> scaled pivot row; objective row, weights, statuses; pricing
 //                 -> exchange: entering column q of the NEXT step with its reduced cost, weight, bounds and its entry in
 //                 the scaled row just made
-// The exchange: every workgroup reduces its candidates (one barrier), publishes ONE record of eight self-tagged 16-byte
-// fields {lo, tag, hi, tag} with a single store instruction, and every wave sweeps all records (field-major: one
-// 16-byte load per field, lane = workgroup) until every tag is the exchange's own, then reduces them with shuffles:
-// no flag, no fence, no atomic; every reduction key is a strict total order, so all waves agree.  Placement: the launch
+// The exchange: every workgroup reduces its candidates (one barrier), publishes ONE record of self-tagged 16-byte
+// fields {lo, tag, hi, tag} with a single store instruction -- seven fields after pricing, six after the ratio test:
+// each instance of xchg() stores and sweeps exactly the fields its receiver cannot rebuild, for a field costs
+// 0.04-0.12 us per exchange (profiles/exchange_cluster_probe.jsonl) -- and every wave sweeps all records (field-major:
+// one 16-byte load per field, lane = workgroup) until every tag is the exchange's own, then reduces them with shuffles:
+// no flag, no fence, no atomic; every reduction key is a strict total order, so all waves agree.  (One sweeping wave
+// per workgroup with the winner handed to the other three through LDS behind a second barrier was measured in the same
+// probe and wins at no field count, 0.06-0.16 us slower at most: the hand-over costs more than 96 fewer readers save.)
+// Placement: the launch
 // has 8 x NW workgroups and only those with blockIdx % 8 == 0 take part -- under the round-robin dispatch of this
 // device they share one XCD, whose L2 then serves the exchange (sc0 stores stay in that L2, sc1 loads bypass the L1:
 // 1.7 us per exchange against 3.3 us across the XCDs, scripts/probe/cluster_probe.hip).  Correctness does not rest on
@@ -2418,7 +2423,7 @@ __global__ __launch_bounds__(256) void k_pr(const ChainArgs A, int g) {
 // of earlier steps) they read with sc1 loads at least one full exchange after the store was issued in front of a sweep:
 // the sweep's loads are behind it in the wave's memory queue, so it has reached the L2 by then.
 constexpr int XNW = 64; // records per field row of the exchange area
-constexpr int XNF = 8;  // fields per record
+constexpr int XNF = 8;  // field rows per region (a record fills the first six or seven; the rest are never touched)
 enum : int { XAUX_SC0 = 1, XAUX_SC1 = 16 };
 typedef unsigned xu4 __attribute__((ext_vector_type(4)));
 
@@ -2438,16 +2443,29 @@ __device__ __forceinline__ double ld_sc1(const double *p) {
 
 // One exchange: `mine` is this thread's candidate with NP payload doubles; returns the winner among all workgroups and
 // its payload, the same in every thread of every workgroup.  One barrier.
+// A record holds only what its instance cannot rebuild, and every field costs (see above):
+//   MODE 0 (pricing)     {k1, aux|idx, payload 0..NP-1}: the second key is not part of the order and price_col leaves it
+//                        0.0, so it does not travel and the winner's k2 is 0.0 as before;
+//   MODE 1 (ratio test)  {k1, aux|idx, k2, payload 1..NP-1}: payload 0 must be the row's pivot-column entry a, of which
+//                        ratio_row makes k2 = fabs(a); its sign bit rides in bit 17 of the aux word and the receiver
+//                        forms pout[0] = sign ? -k2 : k2, which is a bit for bit.  (When no row blocks, idx = 0, the old
+//                        record carried some a that nothing reads; now pout[0] is +-0.0.)
+// Bit 16 of the aux word is the flag, the low 16 bits are the candidate's own aux.
 template <int MODE, int NP>
 __device__ __forceinline__ Cand xchg(XCtx &X, Cand mine, const double (&pin)[NP], double (&pout)[NP], Cand (*s_slots)[4], double (*s_pay)[4][5]) {
+  constexpr int K2 = (MODE == 1) ? 1 : 0;  // the second key travels
+  constexpr int P0 = (MODE == 1) ? 1 : 0;  // first payload double that travels
+  constexpr int NFLD = 2 + K2 + (NP - P0); // fields of this instance's record, <= XNF
+  static_assert(NFLD <= XNF && NP <= 5, "record larger than the exchange area's rows");
   const int lane = TIDX & 63, wave = TIDX >> 6, b = X.xno & 1;
   // workgroup level
   int ol;
   Cand wb = wave_argbest<MODE>(mine, &ol);
   wb.aux = (wb.aux & 0xffff) | (__ballot(X.flag) ? 0x10000 : 0); // the flag rides in the record's aux word
+  if (MODE == 1) wb.aux |= (__double2hiint(rl_d(pin[0], ol)) < 0) ? 0x20000 : 0; // and so does the sign of a
   if (lane == 0) s_slots[b][wave] = wb;
 #pragma unroll
-  for (int k = 0; k < NP; k++) {
+  for (int k = P0; k < NP; k++) {
     const double v = rl_d(pin[k], ol);
     if (lane == 0) s_pay[b][wave][k] = v;
   }
@@ -2463,26 +2481,26 @@ __device__ __forceinline__ Cand xchg(XCtx &X, Cand mine, const double (&pin)[NP]
       bw = k;
     }
   }
-  bb.aux = (bb.aux & 0xffff) | fl;
+  bb.aux = (bb.aux & ~0x10000) | fl;
   const unsigned tag = X.tag;
   const unsigned reg = (unsigned)(X.xno & 3) * (unsigned)(XNF * XNW * 16);
-  if (TIDX < 3 + NP) {
+  if (TIDX < NFLD) {
     double v;
     if (TIDX == 0) v = bb.k1;
-    else if (TIDX == 1) v = bb.k2;
-    else if (TIDX == 2) v = __hiloint2double(bb.aux, bb.idx);
-    else v = s_pay[b][bw][TIDX - 3];
+    else if (TIDX == 1) v = __hiloint2double(bb.aux, bb.idx);
+    else if (K2 && TIDX == 2) v = bb.k2;
+    else v = s_pay[b][bw][TIDX - (2 + K2) + P0];
     const xu4 x = {(unsigned)__double2loint(v), tag, (unsigned)__double2hiint(v), tag};
     __builtin_amdgcn_raw_buffer_store_b128(x, X.rs, reg + (unsigned)(TIDX * XNW + X.w) * 16, 0, XAUX_SC0);
   }
   // every wave sweeps: lane r < nw takes workgroup r's record
-  double rec[3 + NP];
+  double rec[NFLD];
   const int lr = lane < X.nw ? lane : 0;
   unsigned spins = 0;
   for (;;) {
     bool ok = true;
 #pragma unroll
-    for (int f = 0; f < 3 + NP; f++) {
+    for (int f = 0; f < NFLD; f++) {
       const xu4 x = __builtin_amdgcn_raw_buffer_load_b128(X.rs, reg + (unsigned)(f * XNW + lr) * 16, 0, XAUX_SC1);
       ok &= (x.y == tag) & (x.w == tag);
       rec[f] = __hiloint2double((int)x.z, (int)x.x);
@@ -2501,13 +2519,14 @@ __device__ __forceinline__ Cand xchg(XCtx &X, Cand mine, const double (&pin)[NP]
   X.tag++;
   X.xno++;
   Cand rc{0.0, 0.0, 0, 0};
-  if (lane < X.nw && !X.dead) rc = Cand{rec[0], rec[1], __double2loint(rec[2]), __double2hiint(rec[2])};
+  if (lane < X.nw && !X.dead) rc = Cand{rec[0], K2 ? rec[2] : 0.0, __double2loint(rec[1]), __double2hiint(rec[1])};
   int wl;
   Cand win = wave_argbest<MODE>(rc, &wl);
   X.flag = __ballot((rc.aux & 0x10000) != 0) != 0ull;
+  if (MODE == 1) pout[0] = (win.aux & 0x20000) ? -win.k2 : win.k2;
   win.aux = (int)(short)(win.aux & 0xffff);
 #pragma unroll
-  for (int k = 0; k < NP; k++) pout[k] = rl_d(rec[3 + k], wl);
+  for (int k = P0; k < NP; k++) pout[k] = rl_d(rec[2 + K2 + k - P0], wl);
   return win;
 }
 
