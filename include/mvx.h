@@ -547,6 +547,11 @@ void mvx_cluster_stats(long long *launches, long long *aborts);
    shared by 32 or more node LPs and for tableaux of 16 MB and more, else 4), 1 = off, 2..8 = dual pivots one update
    pass applies */
 void mvx_set_dual_chain(int len);
+/* Fused dual path (k_dboot / k_da / k_fb<DUAL>) of a single handle's dual simplex: 0 = never, 1 = by tableau size (from
+   2 M up to 12 M entries), 2 = always, -1 = back to the default (MVX_DUAL_FUSED if set, else 1).  Results are identical
+   either way.  mvx_dual_fused_stats: runs k_dboot started / pivots the fused pair committed, both counted on the device */
+void mvx_set_dual_fused(int mode);
+void mvx_dual_fused_stats(long long *boots, long long *pivots);
 void mvx_persist_stats(long long *launches, long long *aborts);
 /* shader-clock cycles workgroup 0 spent per phase of the resident-tableau loop, summed over launches: propose, gather,
    read, apply; out5[4] = pivots */

@@ -65,6 +65,8 @@ _EXTRA = {
     "set_cluster": (None, [C.c_int]),
     "cluster_stats": (None, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "set_dual_chain": (None, [C.c_int]),
+    "set_dual_fused": (None, [C.c_int]),
+    "dual_fused_stats": (None, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "set_refresh": (None, [C.c_int, C.c_double]),
     "get_refresh_cnt": (C.c_int, [C.c_void_p]),
     "row_residual": (C.c_double, [C.c_void_p]),

@@ -1014,6 +1014,8 @@ void mvx_set_chain(int len) { mvx::set_chain(len); }
 void mvx_set_cluster(int on) { mvx::set_cluster(on); }
 void mvx_cluster_stats(long long *launches, long long *aborts) { mvx::cluster_stats(launches, aborts); }
 void mvx_set_dual_chain(int len) { mvx::set_dual_chain(len); }
+void mvx_set_dual_fused(int mode) { mvx::set_dual_fused(mode); }
+void mvx_dual_fused_stats(long long *boots, long long *pivots) { mvx::dual_fused_stats(boots, pivots); }
 void mvx_persist_stats(long long *launches, long long *aborts) { mvx::persist_stats(launches, aborts); }
 void mvx_persist_cycles(unsigned long long *out5) { mvx::persist_cycles(out5); }
 void mvx_set_batch_slots(int slots) { mvx::set_batch_slots(slots); }

@@ -1119,11 +1119,15 @@ static void stage_copy_async(SolveCtx &sc, const mvx_prob *P) {
 
 // The fused dual pipeline replaces k_select's four dependent stages (34 us at 4096x8192) by k_da (~8 us); below about
 // two million tableau entries the update itself is so short that the two extra bootstrap launches do not pay.
+static std::atomic<int> g_dual_fused{-1}; // 0 never, 1 size rule (default), 2 always; -1: MVX_DUAL_FUSED not read yet
+static std::atomic<long long> g_dfused_boots{0}, g_dfused_pivots{0};
 static bool dual_fused_worth_it(const mvx_prob *P) {
-  static int mode = -1; // MVX_DUAL_FUSED=0 off, 1 size rule (default), 2 always
+  int mode = g_dual_fused.load();
   if (mode < 0) {
     const char *e = std::getenv("MVX_DUAL_FUSED");
-    mode = e ? std::atoi(e) : 1;
+    const int v = e ? std::atoi(e) : 1;
+    mode = v < 0 ? 1 : std::min(2, v);
+    g_dual_fused.store(mode);
   }
   if (mode == 0) return false;
   if (mode >= 2) return true;
@@ -1326,6 +1330,8 @@ static int book_result(mvx_prob *P, const Ctl &snap, int done, double last_ms) {
   P->it_cnt += snap.it_cnt;
   P->bland_cnt += snap.n_bland;
   P->pert_cnt += snap.n_pert;
+  g_dfused_boots += snap.n_dboot; // counted by the lead threads of k_dboot / k_fb<DUAL>
+  g_dfused_pivots += snap.n_dfused;
   // a job of a batch that is neither primal nor dual feasible: nothing has ended, the single-handle path carries on from
   // the pivots made so far and books its own
   if (done == D_NEED_PHASE1) return 0;
@@ -4371,6 +4377,11 @@ void tuning(int tr, int hot, int nt) {
 }
 
 void set_dual_chain(int len) { g_dchain = (len <= 0) ? 0 : std::min(DCH_MAX, len); } // <= 0: by batch width / size
+void set_dual_fused(int mode) { g_dual_fused.store(mode < 0 ? -1 : (mode > 2 ? 2 : mode)); } // -1: MVX_DUAL_FUSED if set, else the size rule
+void dual_fused_stats(long long *boots, long long *pivots) {
+  *boots = g_dfused_boots.load();
+  *pivots = g_dfused_pivots.load();
+}
 void set_chain(int len) { g_chain = (len <= 0) ? 0 : std::min(KCH, len); } // 0: by tableau size
 void set_cluster(int on) { // 0: k_pc / k_pr per step; 1: k_chain (default); also forgets an earlier abort
   g_cluster.store(on != 0);

@@ -111,6 +111,8 @@ void set_chain(int len);
 void set_cluster(int on);
 void cluster_stats(long long *launches, long long *aborts);
 void set_dual_chain(int len);
+void set_dual_fused(int mode);
+void dual_fused_stats(long long *boots, long long *pivots);
 void set_refresh(int check_every, double tol);
 double row_residual(const mvx_prob *P);
 void persist_stats(long long *launches, long long *aborts);

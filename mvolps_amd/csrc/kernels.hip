@@ -1872,6 +1872,7 @@ __device__ __forceinline__ void fb_body(Ctl *c) {
       c->nflag[q] = c->leave_flag;
       c->it_cnt++;
       c->n_bulk++;
+      if (DUAL) c->n_dfused++;
       if (c->budget > 0) c->budget--;
       c->stall = c->stall_new;
     } else if (step == ST_FLIP) {
@@ -3349,6 +3350,7 @@ __global__ __launch_bounds__(DA_THREADS) void k_dboot(Ctl *c) {
     c->p_nextx[a] = p2;
     c->p_up_nextx[a] = p2_up;
     c->fstate = F_RUN_DUAL;
+    c->n_dboot++;
     c->step = ST_NONE;
     c->curB = a ^ 1;
     c->npbd = (int)gridDim.x;

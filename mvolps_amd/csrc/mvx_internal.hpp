@@ -137,6 +137,7 @@ struct Ctl {
   int dsel;             // k_dsel has prepared the coming step (a dual phase carrying on): the k_select that follows returns at once
   int cl_abort;         // k_chain gave up waiting for its peer workgroups: the chain was dropped, nothing was changed
   unsigned long long *dbg; // diagnostic phase stamps of k_pc / k_pr / k_chain (MVX_FCS_DBG=1), nullptr otherwise
+  int n_dboot, n_dfused;   // fused dual path, this call: times k_dboot started a run / pivots k_fb<DUAL> committed (mvx_dual_fused_stats)
 };
 
 // What the host needs after a solve, packed into one staging area:

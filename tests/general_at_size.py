@@ -292,10 +292,11 @@ def certify_sampled_rows(M, P, count=64, seed=0):
     return float((err / lim).max())
 
 
-def certify_end(case, inst, P, rc):
+def certify_end(case, inst, P, rc, exact=None):
     """The certificate of the state a schedule ends on, and the feasibility witness: a full solve gets certify.certify for
-    its status (exact arithmetic up to EXACT_M rows), a pivot-limited one its tableau -- whole where certify.py can afford
-    it, else sampled rows.  A NOFEAS on an instance built around a point is a failure whatever else agrees."""
+    its status (exact arithmetic up to EXACT_M rows, unless `exact` says otherwise: with hundreds of columns the fractions
+    take seconds), a pivot-limited one its tableau -- whole where certify.py can afford it, else sampled rows.  A NOFEAS on
+    an instance built around a point is a failure whatever else agrees."""
     from . import certify as cf
 
     M = model(inst)
@@ -304,7 +305,7 @@ def certify_end(case, inst, P, rc):
         assert P.status != NOFEAS, "%s: NOFEAS on an LP that has the point x0" % case.name
     if rc == 0:
         assert P.status in (OPT, UNBND, NOFEAS)
-        return cf.certify(M, P, exact=(M.m <= cf.EXACT_M), what=case.name)
+        return cf.certify(M, P, exact=(M.m <= cf.EXACT_M) if exact is None else exact, what=case.name)
     if (M.m + 1) * (M.n + 1) > 1500000:
         return certify_sampled_rows(M, P)
     return cf.certify(M, P, what=case.name)

@@ -85,7 +85,7 @@ def paths(gpu):
     gpu.set_chain(0)
     gpu.set_cluster(1)
     gpu.set_persist(1)
-    gpu.set_tuning(0, 1, 0)
+    gpu.set_tuning(0, 1, -1)  # nt = -1: plain, non-temporal or write-through access by tableau size, the engine's default
     gpu.set_dual_chain(0)
     gpu.set_refresh(1024, 1e-9)
 

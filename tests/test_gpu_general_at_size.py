@@ -64,22 +64,29 @@ def side_by_side(api, orc, case, inst):
     return g, stops
 
 
+def dual_fused_pivots(api):
+    boots, pivots = C.c_longlong(0), C.c_longlong(0)
+    api.dual_fused_stats(C.byref(boots), C.byref(pivots))
+    return pivots.value
+
+
 @pytest.mark.parametrize("case", ga.CASES, ids=ga.case_id)
 def test_general_bounds_at_size(gpu, orc, case):
     """Path counters: k_chain's launches are read from cluster_stats wherever a limited call starts in primal phase 2, k_dsel's
     chains from the round histogram on the cold dual starts.  Phase 1 has no counter: that its kernels ran follows from the
-    INFEAS stop after the first call.  dual-1100x2000 is NOT proven to run k_da + k_fb<DUAL>: the fused pair and the generic
-    dual path leave the same bits and no counter tells them apart, so only the entry-count rule of dual_fused_worth_it,
-    restated in the companion, says it is the fused pair."""
+    INFEAS stop after the first call.  dual-1100x2000 lies inside the entry-count rule of dual_fused_worth_it: that k_da +
+    k_fb<DUAL> took pivots of it is read from mvx_dual_fused_stats, counted on the device, and no smaller case moves it."""
     inst = case.instance()
-    before = cluster_counts(gpu)
+    before, fused_before = cluster_counts(gpu), dual_fused_pivots(gpu)
     with round_stats(gpu) as since:
         g, stops = side_by_side(gpu, orc, case, inst)
         d = since()
-    after = cluster_counts(gpu)
-    print("%s: stops %s, k_chain launches +%d aborts +%d, round histogram moved by %s"
-          % (case.name, stops, after[0] - before[0], after[1] - before[1], d.tolist()))
+    after, fused = cluster_counts(gpu), dual_fused_pivots(gpu) - fused_before
+    print("%s: stops %s, k_chain launches +%d aborts +%d, round histogram moved by %s, fused dual pivots +%d"
+          % (case.name, stops, after[0] - before[0], after[1] - before[1], d.tolist(), fused))
     assert stops == case.stops
+    in_rule = ga.DUAL_FUSED_MIN <= (case.rows + 1) * (case.n + 1) < ga.DUAL_FUSED_MAX
+    assert (fused > 0) == (case.family == "cold" and in_rule), (case.name, fused)
     assert after[1] == before[1], "a k_chain launch gave up"
     if len(stops) == 3:  # a limited call that starts in primal phase 2: the chained path, chosen by k_chain
         assert after[0] > before[0], "no k_chain launch was made"

@@ -277,7 +277,7 @@ def test_every_update_variant_is_bit_exact(gpu, orc, tr, hot, nt):
         o.simplex()
         assert_same_state(g, o, "variant %s" % ((tr, hot, nt),))
     finally:
-        gpu.set_tuning(0, 1, 0)
+        gpu.set_tuning(0, 1, -1)  # the true default: nt = -1 picks the access variant by tableau size
 
 
 def test_large_grid_first_pivots_bit_exact(gpu, orc):

@@ -25,7 +25,7 @@ NOFEAS under PIV / ALL: rows the coarse ratio test skipped end up violated; reco
 set) pair is dropped: the seeds are those at which every set ends within four times the DEFAULT pivots (tolerances.py says
 which seeds were passed over and why).  At 1000x2001 tol_dj is not asserted to matter (k_dboot / k_da do not read it and a
 DEFAULT root leaves it nothing to decide); roots under PIV / ALL run past the 4x rule there, so the root is DEFAULT's.
-k_dboot / k_da have no counter: that they take the 1000x2001 children follows from the entry-count rule alone.
+That k_dboot / k_da take the 1000x2001 children is read from mvx_dual_fused_stats, counted on the device.
 
 Oracle seconds (CPU companion): 0.01 per solve up to 128x256, 0.03 at 300x700, 0.7 for the 1000x2001 root.  First device
 run (MI355X, all six positions in the boundary loop): the file 10.5 s for 24 tests, of which 1.6 s is the session's set-up;
@@ -211,9 +211,11 @@ def test_dual_paths_at_128x256_under_every_tolerance_set(paths, orc, dchain):
 
 def test_fused_dual_pair_at_1000x2001_under_every_tolerance_set(gpu, orc):
     """2.0 M entries: k_dboot / k_da by the size rule.  One root (DEFAULT's), three near and three down children under each
-    set."""
+    set; the fused pair's pivot counter must have moved."""
     case = tl.by_name("children-1000x2001")
     assert 2000000 <= (case.m + 1) * (case.n + 1) < 12000000
+    boots0, fused0 = C.c_longlong(0), C.c_longlong(0)
+    gpu.dual_fused_stats(C.byref(boots0), C.byref(fused0))
     A, b, c, U = case.data()
     g, o = synth.load_ilp(gpu, A, b, c, U), synth.load_ilp(orc, A, b, c, U)
     for P in (g, o):
@@ -229,6 +231,9 @@ def test_fused_dual_pair_at_1000x2001_under_every_tolerance_set(gpu, orc):
         assert ((0, o.status, o.it_cnt), [(k[4], k[3].status, k[3].it_cnt) for k in ko]) == case.figures[name]
         for Mc, k in list(zip(tl.child_models(M, kg), kg))[2:4]:  # one near and one down child: the fp64 certificate costs a factor each
             tl.certify_end(Mc, k[3], tol, "1000x2001 child %d/%s under %s" % (k[0], k[1], name))
+    boots, fused = C.c_longlong(0), C.c_longlong(0)
+    gpu.dual_fused_stats(C.byref(boots), C.byref(fused))
+    assert fused.value > fused0.value and boots.value > boots0.value, "k_da + k_fb<DUAL> took no pivot"
 
 
 def test_batched_queue_with_a_non_null_parm(paths, orc):
